@@ -352,6 +352,39 @@ def overlap_slowdown(f, fields, np, torch, frames=4):
         return None
 
 
+DUMP_BYTES = 64_000_000       # --dump-outputs: the most it writes
+
+
+def dump_outputs(path, frame, names, out_dir):
+    """--dump-outputs: what the timed path delivered in its last step, as a reader of the file receives it -- the
+    chunks of frame `frame` of the (closed) file at `path`, read back with the pure-Python reader (no collective, no
+    GPU).  Each chunk goes to out_dir/<chunk name with '/' -> '_'>.npy, float32 chunks as float32, integer chunks as
+    float64 (exact); rows beyond what fits into DUMP_BYTES are a fixed sample (seed 0, sorted row numbers in
+    sample_rows.npy), the same rows for the same arguments whichever build ran."""
+    import numpy as np
+    from pgsd.pypgsd import PGSDFile
+
+    def as_float(a):
+        return a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+
+    os.makedirs(out_dir, exist_ok=True)
+    with open(path, "rb") as fh:
+        f = PGSDFile(fh)
+        chunks = [(name, f.read_chunk(frame, name)) for name in names]
+    per_row = [(n, a) for n, a in chunks if a.shape[0] > 1]        # per-particle chunks; the rest is a few values
+    rows = per_row[0][1].shape[0] if per_row else 0
+    row_bytes = sum(as_float(a[:1]).nbytes for _, a in per_row) + 8          # + its entry in sample_rows.npy
+    keep = min(rows, max(1, (DUMP_BYTES - (1 << 20)) // row_bytes))
+    idx = None
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        np.save(os.path.join(out_dir, "sample_rows.npy"), idx.astype(np.float64))
+    for name, a in chunks:
+        if idx is not None and a.shape[0] == rows:
+            a = a[idx]
+        np.save(os.path.join(out_dir, name.replace("/", "_") + ".npy"), as_float(a))
+
+
 def launch_ranks(n, argv):
     """Parent of a self-launched N-rank run: start N children of this script with RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* set (what torch.distributed.run would export), pass rank 0's stdout through and
@@ -448,9 +481,14 @@ def main():
                          "after the headline; bench_legs.py)")
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="N>1 rehearsal on a one-GPU box: every rank uses cuda:0 and a gloo group")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the run, write the chunks of the last timed frame to DIR/<name>.npy (float32 / "
+                         "float64, a fixed sample of rows beyond 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
 
     # --gpus N is the number of ranks of the run, always.  Ranks started by a launcher (WORLD_SIZE set) must
     # be N of them; without a launcher and N > 1 this process becomes the launcher -- before torch or HIP are
@@ -655,6 +693,10 @@ def main():
                                "transport's own latency"}
     else:
         pack_ms = stats["pack_ms"] / max(stats["pack_launches"], 1)
+    if rank == 0 and args.dump_outputs:
+        # the file is closed on every rank (f.close() flushed it): frame warmup + steps - 1 is the last timed step's
+        dump_outputs(path, args.warmup + args.steps - 1, ["configuration/step"] + [name for name, _ in fields],
+                     args.dump_outputs)
     if rank == 0:
         try:
             os.unlink(path)

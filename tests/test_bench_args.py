@@ -63,3 +63,41 @@ def test_ranks_get_the_ipc_mode_the_pool_needs():
     at_set = src.index('os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")')
     assert at_set < src.index("import torch\n", src.index("def main()"))
     assert 'HSA_ENABLE_IPC_MODE_LEGACY="0"' not in src                     # no longer only in the self-launch path
+
+
+def test_steps_below_one_is_refused():
+    """ms_per_step is the time of one timed step: a run without timed steps has none."""
+    p = run(["--steps", "0"])
+    assert p.returncode != 0 and p.stdout.strip() == "" and "--steps must be at least 1" in p.stderr
+
+
+def test_dump_outputs_writes_the_frame_as_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every chunk of the frame as <name>.npy, float32 kept, integers as exact float64; past the
+    budget a fixed sample of rows, the same on every call."""
+    import numpy as np
+    import scenario as S
+    sys.path.insert(0, ROOT)
+    import bench
+    from pgsd.pypgsd import PGSDFile
+    path = os.path.join(S.GOLDEN, "sph_full.p1.gsd")
+    f = PGSDFile(open(path, "rb"))
+    frame = f.nframes - 1
+    names = [n for n in f.find_matching_chunk_names("particles/") if f.chunk_exists(frame, n)]
+    bench.dump_outputs(path, frame, names, str(tmp_path / "all"))
+    for name in names:
+        got, exp = np.load(str(tmp_path / "all" / (name.replace("/", "_") + ".npy"))), f.read_chunk(frame, name)
+        assert got.dtype == (np.float32 if exp.dtype == np.float32 else np.float64)
+        np.testing.assert_array_equal(got, exp)
+    assert not (tmp_path / "all" / "sample_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES", (1 << 20) + 2000)
+    for d in ("a", "b"):
+        bench.dump_outputs(path, frame, names, str(tmp_path / d))
+    rows = np.load(str(tmp_path / "a" / "sample_rows.npy")).astype(np.int64)
+    assert 0 < len(rows) < f.read_chunk(frame, "particles/position").shape[0]
+    for name in names:
+        n = name.replace("/", "_") + ".npy"
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        np.testing.assert_array_equal(a, b)
+        exp = f.read_chunk(frame, name)
+        np.testing.assert_array_equal(a, exp[rows] if exp.shape[0] > 1 else exp)
+    assert sum(os.path.getsize(str(tmp_path / "a" / n)) for n in os.listdir(str(tmp_path / "a"))) <= bench.DUMP_BYTES

@@ -1,40 +1,24 @@
-"""Files written by this package, read back with the REFERENCE's own pure-Python reader and schema
-layer (imported from /root/reference, which exists in the build container only; on the GPU box the
-test skips).  The reference's hoomd.py imports mpi4py unconditionally (hoomd.py:29) but never uses it
-on the read path, so an empty stand-in module is registered before the import."""
-import importlib.util
+"""Files written by this package, as the REFERENCE's own pure-Python reader and schema layer read them.
+
+The readings are stored under tests/golden/reader/ (tests/golden/make_reader_golden.py made them from a reference
+checkout): each file below was written by this package, read by the reference's PGSDFile / HOOMDTrajectory, and what
+they returned was recorded beside the file's bytes.  Here the package writes the same files again -- they must be
+byte-identical to the ones the reference read -- and the reference's readings must be the values that were written."""
 import os
-import sys
-import types
 
 import numpy as np
-import pytest
 
-REF = "/root/reference/pgsd/pgsd"
-
-pytestmark = [pytest.mark.ref,
-              pytest.mark.skipif(not os.path.exists(os.path.join(REF, "pypgsd.py")),
-                                 reason="reference checkout not present")]
+READER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reader")
+PARTICLE_FIELDS = ('typeid', 'position', 'velocity', 'density', 'auxiliary2', 'image', 'mass')
 
 
-def load_reference_module(name):
-    """Import the reference's module under a private name (keeps it apart from this repo's `pgsd`)."""
-    if "mpi4py" not in sys.modules:
-        stub = types.ModuleType("mpi4py")
-        stub.MPI = object()
-        sys.modules["mpi4py"] = stub
-    spec = importlib.util.spec_from_file_location("reference_" + name, os.path.join(REF, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def test_reference_reader_reads_our_hoomd_file(tmp_gsd):
+def write_hoomd_file(path):
+    """Four frames through pgsd.hoomd on one rank (seeded); -> the Frames written."""
     import pgsd.hoomd as hoomd
     rng = np.random.default_rng(0)
     N = 321
     frames = []
-    with hoomd.open(tmp_gsd, 'w') as t:
+    with hoomd.open(path, 'w') as t:
         for i in range(4):
             f = hoomd.Frame()
             f.configuration.step = 1000 + i
@@ -51,36 +35,53 @@ def test_reference_reader_reads_our_hoomd_file(tmp_gsd):
             f.validate()
             frames.append(f)
             t.append(f)
-    rp = load_reference_module("pypgsd")
-    rh = load_reference_module("hoomd")
-    traj = rh.HOOMDTrajectory(rp.PGSDFile(open(tmp_gsd, 'rb')))
-    assert len(traj) == 4
-    for i in (0, 2, 3):
-        s = traj[i]
-        exp = frames[i]
-        assert s.configuration.step == 1000 + i
-        np.testing.assert_array_equal(s.configuration.box, exp.configuration.box)
-        assert s.particles.N == N and s.particles.types == ['water', 'wall']
-        for name in ('typeid', 'position', 'velocity', 'density', 'auxiliary2', 'image'):
-            np.testing.assert_array_equal(getattr(s.particles, name), getattr(exp.particles, name), err_msg=name)
-        np.testing.assert_array_equal(s.particles.mass, np.ones(N, dtype=np.float32))      # default fallback
-        np.testing.assert_array_equal(s.log['pe'], [float(i)])
+    return frames
 
 
-def test_reference_reader_reads_multi_rank_golden_like_file(tmp_gsd):
+def write_multi_rank_file(path):
     """A 3-rank file (duplicated replicated chunks, per-rank offsets) written by the product driver."""
     import product
     import scenario as S
-    product.run_driver(S.scenario_path("sph_full"), tmp_gsd, 3)
-    rp = load_reference_module("pypgsd")
-    f = rp.PGSDFile(open(tmp_gsd, 'rb'))
-    assert f.nframes == 2 and f.schema == 'hoomd'
-    pos = f.read_chunk(1, 'particles/position')
-    np.testing.assert_array_equal(pos, S.gen_data(9, 8, 0, 333, 3))
-    assert f.read_chunk(0, 'particles/N').dtype == np.uint32
-    ours = __import__("pgsd.pypgsd", fromlist=["PGSDFile"]).PGSDFile(open(tmp_gsd, 'rb'))
-    for name in f.find_matching_chunk_names(''):
+    product.run_driver(S.scenario_path("sph_full"), path, 3)
+
+
+def _same_bytes(path, golden):
+    with open(path, 'rb') as a, open(os.path.join(READER, golden), 'rb') as b:
+        assert a.read() == b.read(), "the package no longer writes the file the reference's reader was shown: " + golden
+
+
+def test_reference_reader_reads_our_hoomd_file(tmp_gsd):
+    frames = write_hoomd_file(tmp_gsd)
+    N = frames[0].particles.N
+    _same_bytes(tmp_gsd, "hoomd4.gsd")
+    rec = np.load(os.path.join(READER, "hoomd4.reference_read.npz"))
+    assert int(rec['len']) == 4
+    for i in (0, 2, 3):
+        exp = frames[i]
+        assert int(rec['%d/step' % i]) == 1000 + i
+        np.testing.assert_array_equal(rec['%d/box' % i], exp.configuration.box)
+        assert int(rec['%d/N' % i]) == N and list(rec['%d/types' % i]) == ['water', 'wall']
+        for name in PARTICLE_FIELDS[:-1]:
+            np.testing.assert_array_equal(rec['%d/%s' % (i, name)], getattr(exp.particles, name), err_msg=name)
+        np.testing.assert_array_equal(rec['%d/mass' % i], np.ones(N, dtype=np.float32))      # default fallback
+        np.testing.assert_array_equal(rec['%d/log/pe' % i], [float(i)])
+
+
+def test_reference_reader_reads_multi_rank_golden_like_file(tmp_gsd):
+    import scenario as S
+    from pgsd.pypgsd import PGSDFile
+    write_multi_rank_file(tmp_gsd)
+    _same_bytes(tmp_gsd, "sph_full3.gsd")
+    rec = np.load(os.path.join(READER, "sph_full3.reference_read.npz"))
+    assert int(rec['nframes']) == 2 and str(rec['schema']) == 'hoomd'
+    np.testing.assert_array_equal(rec['1/particles/position'], S.gen_data(9, 8, 0, 333, 3))
+    assert rec['0/particles/N'].dtype == np.uint32
+    ours = PGSDFile(open(tmp_gsd, 'rb'))
+    for name in rec['names']:
         for frame in range(2):
-            assert f.chunk_exists(frame, name) == ours.chunk_exists(frame, name)
-            if f.chunk_exists(frame, name):
-                np.testing.assert_array_equal(f.read_chunk(frame, name), ours.read_chunk(frame, name))
+            exists = '%d/%s' % (frame, name) in rec.files
+            assert exists == ours.chunk_exists(frame, name)
+            if exists:
+                got = ours.read_chunk(frame, name)
+                np.testing.assert_array_equal(rec['%d/%s' % (frame, name)], got)
+                assert rec['%d/%s' % (frame, name)].dtype == got.dtype
