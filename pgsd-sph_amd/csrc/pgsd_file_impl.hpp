@@ -203,7 +203,9 @@ struct Impl
     // The end of the file as it WILL be once everything this rank has written -- or handed to its pipeline to be
     // written -- is in place: the largest offset + size of any write this handle issued, starting from the file's size
     // at open.  The maximum over the ranks is what MPI_File_get_size returns after all of them have finished
-    // (pgsd.c:1015), known without waiting for a byte: pgsd_expand_file_index needs no drain (round 5).
+    // (pgsd.c:1015), known without waiting for a byte: pgsd_expand_file_index needs no drain (round 5).  Chunk data is
+    // noted in ONE place, place_chunk, the moment a direct chunk gets its offset (every write path goes through it);
+    // metadata in meta_pwrite and expand_file_index.
     long long placed_end = 0;
     void note_placed(long long offset, uint64_t bytes)
         {

@@ -160,6 +160,14 @@ int place_chunk(Impl* s, const char* name, uint32_t type, uint64_t N, uint32_t M
         pl->buffered = false;
         pl->write = all || s->rank == 0;
         pl->file_offset = s->file_size + (long long)(offset * sz);
+        // The bytes THIS rank will write -- rank 0's one copy of a replicated chunk, not the P copies file_size
+        // advances by -- count towards the end of the file from here, whichever path writes them later (host pwrite,
+        // device pipeline, staged commit): expand_file_index puts a relocated index at the ranks' furthest placement.
+        // Also where trusted_place finds this rank's rows unusable (`deliver` false, nothing written): the entry every
+        // rank records claims these bytes, so the index block must not land on them; the failure is reported at the
+        // next flush.
+        if (pl->write && pl->size > 0)
+            s->note_placed(pl->file_offset, pl->size);
         // file_size advances by the sum of the ranks' sizes (MPI_Allreduce SUM, pgsd.c:2240-2249):
         // also when only rank 0 wrote (all == false: the hole is part of the reference's layout)
         // and whatever the caller passed as global_size (replicated data written with all == true
@@ -217,10 +225,7 @@ int deliver_chunk(Impl* s, Queued& q, const Placement& pl, bool skip)
             rc = device_pipeline_commit(s->dev, q.ticket, q.ticket_index, -1, s->write_buffer.data() + at, &err);
             }
         else
-            {
-            s->note_placed(pl.file_offset, pl.size);
             rc = device_pipeline_commit(s->dev, q.ticket, q.ticket_index, pl.file_offset, nullptr, &err);
-            }
         if (rc != PGSD_SUCCESS)
             {
             set_last_error(err);
@@ -240,7 +245,6 @@ int deliver_chunk(Impl* s, Queued& q, const Placement& pl, bool skip)
         return PGSD_SUCCESS;
     // the bytes of the chunk: MPI_File_write_at in the reference (pgsd.c:2229)
     TraceRange tr("pgsd:pwrite_host file_off=%llu bytes=%llu", (unsigned long long)pl.file_offset, pl.size);
-    s->note_placed(pl.file_offset, pl.size);
     int e = writer_pool_pwrite_sync(s->get_pool(), s->fd, data, pl.size, pl.file_offset, s->P > 1);
     if (e != 0)
         {
@@ -500,7 +504,6 @@ extern "C" int pgsd_write_chunk(struct pgsd_handle* handle, const char* name, en
             else if (pl.write)
                 {
                 TraceRange tr("pgsd:pwrite_host file_off=%llu bytes=%llu", (unsigned long long)pl.file_offset, pl.size);
-                s->note_placed(pl.file_offset, pl.size);
                 int e = writer_pool_pwrite_sync(s->get_pool(), s->fd, data, pl.size, pl.file_offset, s->P > 1);
                 if (e != 0)
                     {
@@ -564,7 +567,6 @@ extern "C" int pgsd_write_chunk(struct pgsd_handle* handle, const char* name, en
         else if (pl.write && pl.size > 0)
             {
             // the bytes of the chunk: MPI_File_write_at in the reference (pgsd.c:2229)
-            s->note_placed(pl.file_offset, pl.size);
             int e = writer_pool_pwrite_sync(s->get_pool(), s->fd, data, pl.size, pl.file_offset, s->P > 1);
             if (e != 0)
                 {
@@ -1076,8 +1078,6 @@ extern "C" int pgsd_write_staged_chunks(struct pgsd_handle* handle, uint64_t tic
                 {
                 std::string err;
                 const bool skip = !deliver || pl.size == 0;
-                if (!skip)
-                    s->note_placed(pl.file_offset, pl.size);
                 int drc = device_pipeline_commit(s->dev, e.ticket, i, skip ? -1 : pl.file_offset, nullptr, &err);
                 if (drc != PGSD_SUCCESS && prc == PGSD_SUCCESS)
                     {
@@ -1134,8 +1134,6 @@ extern "C" int pgsd_write_staged_chunks(struct pgsd_handle* handle, uint64_t tic
                 {
                 std::string err;
                 const bool skip = prc != PGSD_SUCCESS || pl.size == 0;
-                if (!skip)
-                    s->note_placed(pl.file_offset, pl.size);
                 int drc = device_pipeline_commit(s->dev, e.ticket, i, skip ? -1 : pl.file_offset, nullptr, &err);
                 if (drc != PGSD_SUCCESS && prc == PGSD_SUCCESS)
                     {

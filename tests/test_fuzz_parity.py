@@ -175,6 +175,129 @@ def make_relocation_script(seed, P):
     return "\n".join(lines) + "\n"
 
 
+def make_partitioned_relocation_script(seed, P):
+    """Relocation-heavy scripts whose relocations happen at the end of frames made ONLY of partitioned chunks (`all 1`:
+    always on the direct path, nothing in the write buffer).  Then no flush of buffered rows writes the true end of the
+    file just before the index moves: where the new block goes comes from the ranks' own placements alone.  All ten
+    types, M 1-4, `list:` partitions with empty ranks -- the last one included, so that a chunk's true end comes from
+    an earlier rank's part.  Frames with replicated (buffered, or with a small write buffer one-rank-only direct) chunks,
+    mid-frame flushes, idxbuf and close + re-open come in between, but never in a frame that relocates the index: the
+    generator counts the index entries (every chunk is one; a frame with direct chunks is flushed at end_frame) and
+    makes each such frame partition-only by construction."""
+    rng = random.Random(seed * 999983 + 17 * P)
+    lines = ["create preloc_%d hoomd 1 4 %s 0" % (seed, rng.choice(["rw", "append"]))]
+    if rng.random() < 0.3:
+        lines.append("maxbuf %d" % rng.choice([16, 64, 4096]))
+    if rng.random() < 0.4:
+        lines.append("idxbuf %d" % rng.choice([1, 3, 40, 200]))
+    n_names = rng.randint(10, 24)
+    shape = {k: (RELOC_TYPES[k] if k < len(RELOC_TYPES) else rng.choice(RELOC_TYPES), 1 + k % 4 if k < 4 else
+                 rng.randint(1, 4)) for k in range(n_names)}
+    budget = rng.choice([rng.randint(140, 250), rng.randint(260, 500), rng.randint(520, 700)])   # 1, 2 or 3 relocations
+    allocated, flushed = 128, 0                 # the file's index block and the entries in it
+    relocations, frame = 0, 0
+
+    def dist():
+        if rng.random() < 0.45:
+            counts = [rng.choice([0, 0, 1, 2, 11, 31, 57]) for _ in range(P)]
+            if P > 1 and rng.random() < 0.5:
+                counts[-1] = 0
+            return "list:" + ",".join(map(str, counts))
+        return "even:%d" % rng.randint(0, 120)
+
+    def last_dist():
+        if P > 1 and rng.random() < 0.5:     # rows on an earlier rank, none on the last one
+            counts = [rng.choice([0, 1, 11, 31]) for _ in range(P - 1)] + [0]
+            counts[rng.randrange(P - 1)] = rng.randint(1, 40)
+            return "list:" + ",".join(map(str, counts))
+        return "even:%d" % rng.randint(P, 120)
+
+    while flushed < budget:
+        per_frame = rng.randint(3, min(n_names, 14))
+        relocates = flushed + per_frame > allocated
+        mixed = not relocates and frame > 0 and rng.random() < 0.3
+        lines.append("seed %d" % rng.randint(0, 10 ** 6))
+        names = rng.sample(range(n_names), per_frame)
+        pending = 0
+        for i, k in enumerate(names):
+            t, M = shape[k]
+            if mixed and i == 0:
+                lines.append("chunk r/%d %s %d 0 same:%d" % (k, t, M, rng.randint(1, 5)))
+            elif i == per_frame - 1:
+                # the frame's last chunk has rows (on an earlier rank only, where the last rank is empty): a relocating
+                # frame ends with data nothing but its own placement accounts for
+                lines.append("chunk r/%d %s %d 1 %s" % (k, t, M, last_dist()))
+            else:
+                lines.append("chunk r/%d %s %d 1 %s" % (k, t, M, dist()))
+            pending += 1
+            if i < per_frame - 1 and rng.random() < 0.04:
+                lines.append("flush")
+                if flushed + pending > allocated:
+                    relocations += 1
+                    while allocated <= flushed + pending:
+                        allocated *= 2
+                flushed, pending = flushed + pending, 0
+        lines.append("end_frame")
+        if flushed + pending > allocated:
+            relocations += 1
+            while allocated <= flushed + pending:
+                allocated *= 2
+        flushed += pending
+        frame += 1
+        r = rng.random()
+        if r < 0.07:
+            lines += ["close", "open %s" % rng.choice(["rw", "append"]), "dump"]
+            if rng.random() < 0.3:
+                lines.append("idxbuf %d" % rng.choice([1, 3, 40]))
+        elif r < 0.12:
+            lines.append("dump")
+    assert relocations >= 1
+    lines += ["dump", "close"]
+    return "\n".join(lines) + "\n"
+
+
+def _relocated(o_log):
+    """the oracle's trace shows an index block larger than the 128 entries of a new file"""
+    import re
+    sizes = [int(m) for ln in o_log for m in re.findall(r"index_allocated=(\d+)", ln)]
+    return bool(sizes) and max(sizes) > 128
+
+
+PARTITIONED_RELOCATION_CASES = [(s, P) for s in range(600, 606) for P in (1, 2, 3) if (s + P) % 2 == 0] + [(606, 5)]
+
+
+@pytest.mark.parametrize("check_eof", ["", "1"])
+@pytest.mark.parametrize("mode", [0, 1, 3])
+@pytest.mark.parametrize("seed,P", PARTITIONED_RELOCATION_CASES)
+def test_partition_only_relocation_scenarios_equal_the_oracle(seed, P, mode, check_eof, tmp_path, monkeypatch):
+    """Index relocations at the end of frames of partitioned direct chunks only (make_partitioned_relocation_script),
+    through the host path in placement modes 0 (one exchange per chunk), 1 (one per frame) and 3 (declared partition),
+    with and without PGSD_CHECK_EOF: file and state trace are the oracle's."""
+    import re
+    if check_eof:
+        monkeypatch.setenv("PGSD_CHECK_EOF", "1")
+    scn = tmp_path / "preloc.scn"
+    scn.write_text(make_partitioned_relocation_script(seed, P))
+    o_path, p_path = str(tmp_path / "oracle.gsd"), str(tmp_path / "product.gsd")
+    o_log = S.run_oracle(str(scn), o_path, P)
+    assert not [ln for ln in o_log if ln.startswith("rc ")], o_log
+    assert _relocated(o_log), "the script did not relocate the index"
+    s2 = str(scn) if mode == 0 else product.batched_script(str(scn), str(tmp_path / "b.scn"), mode)
+    p_log = product.run_driver(s2, p_path, P)
+    with open(o_path, "rb") as a, open(p_path, "rb") as b:
+        want = a.read()
+        assert want == b.read()
+    strip = lambda lines: [re.sub(r"line=\d+ ", "", ln) for ln in lines]
+    assert strip(p_log) == strip(o_log)
+    # the device replays of these scripts (tests/test_gpu_golden_device.py) trust the oracle's relocation layout: it is
+    # the compiled reference's, where that is present
+    if mode == 0 and not check_eof and have_ref():
+        r_path = str(tmp_path / "ref.gsd")
+        out = subprocess.run([MPIEXEC, "-n", str(P), REF_DRIVER, str(scn), r_path], capture_output=True, timeout=120)
+        assert out.returncode == 0, out.stderr.decode()[-500:]
+        with open(r_path, "rb") as r:
+            assert r.read() == want
+
 
 @pytest.mark.parametrize("check_eof", ["", "1"])
 @pytest.mark.parametrize("mode", [0, 1, 3])

@@ -202,6 +202,105 @@ def test_multi_rank_device_write_matches_oracle(counts, async_seal, batched, tmp
         assert a.read() == b.read()
 
 
+RELOCATING_FRAMES = 50         # 3 entries a frame: the 128-entry index moves at the end of frame 43
+
+
+def _bench_frame(seed, row0, n):
+    """one frame as the reference's benchmark-write.cc writes it, without configuration/step: position (xyz of a float4
+    whose w carries the type id's bits), velocity (xyz of a float4), typeid"""
+    pos4 = S.gen_data(9, seed, row0, n, 4)
+    vel4 = S.gen_data(9, seed + 7919, row0, n, 4)
+    tid = S.gen_data(3, seed, row0, n, 1)
+    pos4.view(np.uint32)[:, 3] = tid[:, 0]
+    return pos4, vel4, tid
+
+
+def _relocating_rank_main(rank, P, shm, path, counts, seed, q, wait, batched):
+    try:
+        import sys
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        sys.path.insert(0, os.path.join(root, "pgsd-sph_amd"))
+        sys.path.insert(0, os.path.join(root, "tests"))
+        import torch
+        import pgsd.fl as fl
+        from pgsd import _lib
+        __import__("pgsd.dist").dist.init_shm(shm, rank, P)
+        torch.cuda.set_device(0)
+        n = counts[rank]
+        row0 = int(sum(counts[:rank]))
+        f = fl.open(path, 'w', application='app', schema='hoomd', schema_version=[1, 4])
+        declared = batched == "declared"
+        f.frame_exchange = bool(batched) and not declared
+        if declared:
+            f.set_partition(counts)
+        for frame in range(RELOCATING_FRAMES):
+            pos4, vel4, _ = _bench_frame(seed + frame, row0, n)
+            dpos, dvel = torch.from_numpy(pos4).cuda(), torch.from_numpy(vel4).cuda()
+            f.write_chunks([('particles/position', fl.DeviceField.from_tensor(dpos, columns=(0, 3))),
+                            ('particles/velocity', fl.DeviceField.from_tensor(dvel, columns=(0, 3))),
+                            ('particles/typeid', fl.DeviceField.from_tensor(dpos, columns=(3, 4), out_dtype=np.uint32,
+                                                                            bitcast=True))],
+                           offset="auto" if batched else np.array(counts), rank=rank)
+            f.end_frame(wait=wait)
+        f.close()
+        _lib.lib.pgsd_comm_finalize()
+        q.put((rank, "ok"))
+    except Exception as e:  # pragma: no cover
+        import traceback
+        q.put((rank, traceback.format_exc()))
+        raise
+
+
+@pytest.mark.parametrize("batched", [False, True, "declared"])
+@pytest.mark.parametrize("wait", [True, False])
+@pytest.mark.parametrize("counts", [[600, 401], [0, 333, 1], [777]])
+def test_partition_only_frames_relocate_the_index_where_the_oracle_does(counts, wait, batched, tmp_path):
+    """pgsd_write_chunks_device frames with per-particle chunks only -- nothing in the write buffer, so no flush of
+    buffered rows records the end of the file -- past the 128 entries of the first index block: one exchange per call,
+    the frame's exchange, declared partition; synchronous and asynchronous seals.  The block must move to the file's
+    true end, as in the oracle's file, and early and late frames read back."""
+    import pgsd.fl as fl
+    P = len(counts)
+    seed = 4321
+    mine, ref = str(tmp_path / "mine.gsd"), str(tmp_path / "ref.gsd")
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    shm = "pgsdgpu_%s" % uuid.uuid4().hex[:10]
+    procs = [ctx.Process(target=_relocating_rank_main, args=(r, P, shm, mine, counts, seed, q, wait, batched))
+             for r in range(P)]
+    for p in procs:
+        p.start()
+    results = [q.get(timeout=300) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+    assert all(msg == "ok" for _, msg in results), results
+    row0 = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(int)
+    frames, whole = [], []
+    for frame in range(RELOCATING_FRAMES):
+        parts = [_bench_frame(seed + frame, int(row0[r]), counts[r]) for r in range(P)]
+        pos = [np.ascontiguousarray(p[0][:, :3]) for p in parts]
+        vel = [np.ascontiguousarray(p[1][:, :3]) for p in parts]
+        tid = [p[2] for p in parts]
+        frames.append([('particles/position', 9, 3, True, pos),
+                       ('particles/velocity', 9, 3, True, vel),
+                       ('particles/typeid', 3, 1, True, tid)])
+        whole.append((np.concatenate(pos), np.concatenate(vel), np.concatenate(tid)[:, 0]))
+    _oracle_frames(ref, P, frames)
+    with open(mine, 'rb') as a, open(ref, 'rb') as b:
+        data = a.read()
+        assert data == b.read()
+    # pgsd_header: magic, index_location, index_allocated_entries (pgsd.h)
+    assert np.frombuffer(data[:24], dtype=np.uint64)[2] == 256, "the index did not move"
+    g = fl.open(mine, 'r')
+    assert g.nframes == RELOCATING_FRAMES
+    for frame in (1, RELOCATING_FRAMES - 1):
+        pos, vel, tid = whole[frame]
+        np.testing.assert_array_equal(g.read_chunk(frame, 'particles/position').reshape(-1, 3), pos)
+        np.testing.assert_array_equal(g.read_chunk(frame, 'particles/velocity').reshape(-1, 3), vel)
+        np.testing.assert_array_equal(g.read_chunk(frame, 'particles/typeid').reshape(-1), tid)
+    g.close()
+
+
 @pytest.mark.parametrize("batched", [False, True, "declared"])
 def test_five_ranks_share_the_gpu(batched, tmp_path):
     """as many ranks as the box lets use the card next to the test process itself (6 processes in all): uneven

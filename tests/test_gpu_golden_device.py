@@ -88,22 +88,65 @@ def test_random_scenarios_from_hbm_equal_the_oracle(seed, P, tmp_path):
     assert strip(p_log) == strip(o_log)
 
 
-@pytest.mark.parametrize("seed,P", [(s, P) for s in range(500, 500 + max(4, FUZZ_SEEDS // 4)) for P in (1, 2, 3)])
-def test_relocation_heavy_scenarios_from_hbm_with_asynchronous_seals(seed, P, tmp_path):
-    """The relocation-heavy scripts of tests/test_fuzz_parity.py (one to three index relocations each) with every chunk's
-    rows in HBM and EVERY frame sealed asynchronously: since round 5 a seal stays asynchronous when the index moves
-    (the file's true end comes from the ranks' placements), so the new block is placed while earlier frames' copies
-    and writes are still on their way -- file and state trace must be the oracle's."""
-    from test_fuzz_parity import make_relocation_script
-    scn = tmp_path / "reloc.scn"
-    scn.write_text(make_relocation_script(seed, P))
+def _replay_against_oracle(script, P, tmp_path, mode, batch, async_seal, allow_fail=False):
+    """`script` through the oracle and through the device driver: file and state trace must be the oracle's.
+    `allow_fail`: a driver whose calls failed (exit status 1) is not an error by itself; the `rc` lines of its trace
+    are then what the comparison reports."""
+    scn = tmp_path / "scenario.scn"
+    scn.write_text(script)
     o_path, p_path = str(tmp_path / "oracle.gsd"), str(tmp_path / "device.gsd")
     o_log = S.run_oracle(str(scn), o_path, P)
     assert not [ln for ln in o_log if ln.startswith("rc ")], o_log
-    dscn = product.device_script(str(scn), str(tmp_path / "device.scn"), 2 if seed % 2 else 1, 1, True)
-    p_log = product.run_driver(dscn, p_path, P, driver=product.DEVICE_DRIVER)
-    with open(o_path, "rb") as a, open(p_path, "rb") as b:
-        assert a.read() == b.read()
+    dscn = product.device_script(str(scn), str(tmp_path / "device.scn"), mode, batch, async_seal)
+    p_log = product.run_driver(dscn, p_path, P, allow_fail=allow_fail, driver=product.DEVICE_DRIVER)
     strip = lambda lines: [re.sub(r"line=\d+ ", "", ln) for ln in lines
                            if not ln.startswith("rc ") or not any(c in ln for c in ("cmd=batch", "cmd=device", "cmd=async"))]
     assert strip(p_log) == strip(o_log)
+    with open(o_path, "rb") as a, open(p_path, "rb") as b:
+        assert a.read() == b.read()
+    return o_log
+
+
+def _batch_cases(cases, old_ids=False):
+    """(seed, P) x batch 0 (one exchange per chunk), 1 (one per frame), 3 (declared partition); `old_ids`: batch 1 keeps
+    the id the case had before the test took a batch parameter"""
+    return [pytest.param(seed, P, batch, id=("%d-%d" % (seed, P)) if old_ids and batch == 1 else "%d-%d-batch%d" % (seed, P, batch))
+            for seed, P in cases for batch in (0, 1, 3)]
+
+
+@pytest.mark.parametrize("seed,P,batch", _batch_cases([(s, P) for s in range(500, 500 + max(4, FUZZ_SEEDS // 4)) for P in (1, 2, 3)],
+                                                      old_ids=True))
+def test_relocation_heavy_scenarios_from_hbm_with_asynchronous_seals(seed, P, batch, tmp_path):
+    """The relocation-heavy scripts of tests/test_fuzz_parity.py (one to three index relocations each) with every chunk's
+    rows in HBM and EVERY frame sealed asynchronously: since round 5 a seal stays asynchronous when the index moves
+    (the file's true end comes from the ranks' placements), so the new block is placed while earlier frames' copies
+    and writes are still on their way -- file and state trace must be the oracle's.  Every placement path of
+    pgsd_write_chunk_device: per-chunk exchange, the frame's exchange, declared partition."""
+    from test_fuzz_parity import make_relocation_script
+    _replay_against_oracle(make_relocation_script(seed, P), P, tmp_path, 2 if seed % 2 else 1, batch, True)
+
+
+PARTITIONED_SEEDS = range(600, 600 + max(4, FUZZ_SEEDS // 4))
+
+
+@pytest.mark.parametrize("seed,P,batch", _batch_cases([(s, P) for s in PARTITIONED_SEEDS for P in (1, 2, 3)]))
+def test_partition_only_relocations_from_hbm_equal_the_oracle(seed, P, batch, tmp_path):
+    """The scripts of make_partitioned_relocation_script: the index moves at the end of frames of partitioned chunks
+    only, written from HBM, so nothing but the device chunks' own placements tells the library where the file ends.
+    Dense (even seeds) and strided (odd) device rows; synchronous and asynchronous seals (alternating in pairs of
+    seeds); placement by per-chunk exchange, frame exchange and declared partition."""
+    from test_fuzz_parity import make_partitioned_relocation_script, _relocated
+    o_log = _replay_against_oracle(make_partitioned_relocation_script(seed, P), P, tmp_path, 2 if seed % 2 else 1, batch,
+                                   bool((seed // 2) % 2))
+    assert _relocated(o_log)
+
+
+@pytest.mark.parametrize("seed,P,batch", _batch_cases([(600, 2), (601, 3), (603, 1)]))
+def test_partition_only_relocations_from_hbm_with_the_end_of_file_check(seed, P, batch, tmp_path, monkeypatch):
+    """... with PGSD_CHECK_EOF=1: every relocation compares the end of file computed from the placements with fstat's
+    after a drain, so a wrong end is reported as PGSD_ERROR_FILE_CORRUPT (an `rc` line in the trace, compared with the
+    oracle's trace before the bytes) and not only as different bytes."""
+    from test_fuzz_parity import make_partitioned_relocation_script
+    monkeypatch.setenv("PGSD_CHECK_EOF", "1")
+    _replay_against_oracle(make_partitioned_relocation_script(seed, P), P, tmp_path, 2 if seed % 2 else 1, batch,
+                           bool((seed // 2) % 2), allow_fail=True)
