@@ -7,7 +7,11 @@ arrays, ONE allgather of the ranks' chunk sizes (RCCL over xGMI for N > 1; gives
 count -> file offsets) in flight while the kernel runs, hipMemcpyAsync to pinned slabs, pwrite
 into one shared GSD file on tmpfs, index commit (pgsd_end_frame).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; --full adds the measurements beside the headline
+(CPU baseline, asynchronous-sealing stall and overlap, exchange probe, live PMC traffic, legs), which take runs and
+minutes of their own.
 
 N > 1: one rank per GPU; the ranks share ONE output file, each writing its own partition (weak
 scaling: 10 M particles per GPU).  Either the driver launches the ranks (torch.distributed.run:
@@ -15,9 +19,9 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment, and WORLD_SIZE mus
 -- WORLD_SIZE unset -- this script starts them itself: the parent process spawns N rank children
 BEFORE anything touches torch or the GPU, relays rank 0's JSON line and exits with their status
 (the reference's harness finds its ranks the same way inside the program, benchmark-write.cc:24-45).
-Rank 0 prints one JSON line (contract in the task description) with `roofline` for the pack
-kernel, `exchange_us` for the frame's one allgather and `cpu_baseline` for the reference's CPU
-path on the host's cores (P ranks for N = P GPUs; `nproc` stated).
+Rank 0 prints one JSON line with `roofline` for the pack kernel, `exchange_us` for the frame's
+one allgather and, with --full, `cpu_baseline` for the reference's CPU path on the host's cores
+(P ranks for N = P GPUs; `nproc` stated).
 """
 import argparse
 import ctypes
@@ -213,7 +217,7 @@ def measure_traffic_live(args):
               file=sys.stderr)
         return None, None, None
     child = ["--gpus", "1", "--steps", "4", "--warmup", "1", "--particles", str(args.particles), "--schema", args.schema,
-             "--dir", args.dir, "--no-cpu-baseline", "--traffic", "off", "--no-stall-test", "--no-exchange-probe", "--no-legs"]
+             "--dir", args.dir, "--traffic", "off"]          # a plain run: the pack launches and nothing else
     if args.separate_id:
         child.append("--separate-id")
     fetch = pmc_pass("FETCH_SIZE", child, 240)
@@ -438,7 +442,10 @@ def launch_ranks(n, argv):
     return status
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, with what a plain run skips resolved: without --full the run does the headline alone (no CPU
+    baseline, stall test, overlap measurement, exchange probe, counter passes or legs); --full runs them all, and the
+    --no-* flags drop single ones again."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -448,10 +455,11 @@ def main():
     ap.add_argument("--dir-fallback", action="store_true",
                     help="when --dir lacks room for the run, write to /tmp or the working directory instead of stopping "
                          "(the file system then differs from run to run: config.target_fstype says which it was)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stall-test", action="store_true", help="skip the asynchronous-sealing stall measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the reference's CPU baseline")
+    ap.add_argument("--no-stall-test", action="store_true",
+                    help="--full: skip the asynchronous-sealing stall and overlap measurements")
     ap.add_argument("--no-exchange-probe", action="store_true",
-                    help="N=1: skip timing one exchange on a one-rank RCCL communicator")
+                    help="--full, N=1: skip timing one exchange on a one-rank RCCL communicator")
     ap.add_argument("--slab-mib", type=int, default=0)
     ap.add_argument("--slabs", type=int, default=0)
     ap.add_argument("--writers", type=int, default=0)
@@ -463,10 +471,16 @@ def main():
     ap.add_argument("--comm", choices=["auto", "rccl", "torch"], default="auto",
                     help="N>1: auto = the library's own RCCL communicator, torch.distributed callbacks if it cannot be "
                          "built; rccl = no fallback; torch = callbacks only")
-    ap.add_argument("--traffic", choices=["live", "file", "off"], default="live",
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else the line can carry: the reference's CPU "
+                         "baseline, the asynchronous-sealing stall and overlap, the one-rank RCCL exchange probe, live "
+                         "PMC traffic and (N=1, --schema pvi) the legs.  Without it a run sets up, warms up, times its "
+                         "steps and prints the line")
+    ap.add_argument("--traffic", choices=["live", "file", "off"], default=None,
                     help="roofline.traffic (HBM bytes of one pack launch from the PMC counters): live = two child runs "
                          "of this script under rocprofv3 (--pmc FETCH_SIZE, --pmc WRITE_SIZE, separate passes; N=1 "
-                         "only), falling back to file = profiles/pack_traffic.json when that is not possible")
+                         "only), falling back to file = profiles/pack_traffic.json when that is not possible.  "
+                         "Default: live with --full, off without")
     ap.add_argument("--declared-partition", action="store_true",
                     help="pgsd_set_partition instead of the per-frame allgather: every rank's row count is declared once "
                          "(weak scaling: the same on all ranks), frames then cost NO collective (collectives_per_frame 0). "
@@ -477,14 +491,23 @@ def main():
                          "in-process (MPI_Init_thread through ctypes, every rank a singleton: the file is opened on "
                          "MPI_COMM_SELF); PGSD_LIBMPI names the libmpi to load")
     ap.add_argument("--no-legs", action="store_true",
-                    help="N=1, --schema pvi: skip the `legs` (BASELINE configs 2, 4, 5 and the tag-order gather measured "
-                         "after the headline; bench_legs.py)")
+                    help="--full, N=1, --schema pvi: skip the `legs` (BASELINE configs 2, 4, 5 and the tag-order gather "
+                         "measured after the headline; bench_legs.py)")
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="N>1 rehearsal on a one-GPU box: every rank uses cuda:0 and a gloo group")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the run, write the chunks of the last timed frame to DIR/<name>.npy (float32 / "
                          "float64, a fixed sample of rows beyond 64 MB)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_stall_test = args.no_exchange_probe = args.no_legs = True
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "off"
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
     if args.steps < 1 or args.warmup < 0:

@@ -101,3 +101,19 @@ def test_dump_outputs_writes_the_frame_as_float_arrays_within_the_budget(tmp_pat
         exp = f.read_chunk(frame, name)
         np.testing.assert_array_equal(a, exp[rows] if exp.shape[0] > 1 else exp)
     assert sum(os.path.getsize(str(tmp_path / "a" / n)) for n in os.listdir(str(tmp_path / "a"))) <= bench.DUMP_BYTES
+
+
+def test_a_plain_run_skips_what_only_full_measures():
+    """Without --full the run measures its headline alone; --full turns the rest on, the --no-* flags still drop single
+    measurements under it, and an explicit --traffic is kept either way."""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse_args(["--steps", "3"])
+    assert not plain.full and plain.traffic == "off"
+    assert plain.no_cpu_baseline and plain.no_stall_test and plain.no_exchange_probe and plain.no_legs
+    full = bench.parse_args(["--full"])
+    assert full.traffic == "live"
+    assert not (full.no_cpu_baseline or full.no_stall_test or full.no_exchange_probe or full.no_legs)
+    some = bench.parse_args(["--full", "--no-legs", "--traffic", "file"])
+    assert some.no_legs and not some.no_cpu_baseline and some.traffic == "file"
+    assert bench.parse_args(["--traffic", "file"]).traffic == "file"

@@ -12,9 +12,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*extra, legs=False):
+def run_bench(*extra, legs=False, full=True):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--particles", "300000"] + ([] if legs else ["--no-legs"]) + list(extra),
+                        "--particles", "300000"] + (["--full"] if full else []) + ([] if legs else ["--no-legs"])
+                       + list(extra),
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -50,6 +51,22 @@ def test_bench_line_has_the_contracts_fields():
     assert d["snapshot_stall_ms"] > 0
 
 
+def test_plain_run_measures_the_headline_alone():
+    """Without --full the line is the headline and what the timed steps themselves report: no CPU baseline, stall or
+    overlap measurement, exchange probe, counter passes or legs."""
+    d = run_bench(full=False, legs=True)
+    assert d["metric"] == "snapshot pack+write GB/s at 10M particles/GPU" and d["unit"] == "GB/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1
+    assert isinstance(d["value"], float) and d["value"] > 0 and d["ms_per_step"] > 0
+    r = d["roofline"]
+    assert r["frac"] > 0 and r["avg_ms"] > 0 and r["algorithmic_bytes_per_launch"] == 56 * 300000
+    assert r["traffic"] is None and r["traffic_source"] is None
+    assert not any(k.startswith("legs_") for k in r)
+    assert "cpu_baseline" not in d and "legs" not in d
+    assert d["exchange_probe"] is None and d["snapshot_stall_ms"] is None and d["snapshot_overlap"] is None
+    assert d["pack_aggregate"]["launches_per_rank"] == 3
+
+
 def test_bench_measures_its_hbm_traffic_with_the_pmc_counters():
     """roofline.traffic comes from two rocprofv3 counter passes of the run itself: read bytes = FETCH_SIZE x 2
     (gfx950), written bytes = WRITE_SIZE; for the row kernel they are the source arrays and the chunks."""
@@ -70,7 +87,7 @@ def test_gpus_flag_launches_that_many_ranks():
     rehearsal flag that is refused (one rank per GPU is the contract), with it both ranks share cuda:0 over a gloo
     group and the line says n_gpus 2, one collective per frame, and what that collective cost."""
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-            "--particles", "200000", "--traffic", "off"]
+            "--particles", "200000", "--full", "--traffic", "off"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     import torch
     if torch.cuda.device_count() < 2:

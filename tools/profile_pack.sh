@@ -16,6 +16,6 @@ for cfg in "10M 10000000" "1M 1048576"; do
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$name" -- python3 $BENCH $common > "$OUT/bench_under_rocprof_$name.json" 2> "$OUT/stats_$name.err" || echo "stats $name failed"
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch_$name" -- python3 $BENCH $common > /dev/null 2> "$OUT/fetch_$name.err" || echo "fetch $name failed"
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write_$name" -- python3 $BENCH $common > /dev/null 2> "$OUT/write_$name.err" || echo "write $name failed"
-  python3 $BENCH --particles $n --steps 20 --warmup 5 --no-cpu-baseline --traffic off --no-exchange-probe --no-legs > "$OUT/bench_plain_$name.json" 2> "$OUT/bench_plain_$name.err" || echo "plain $name failed"
+  python3 $BENCH --full --particles $n --steps 20 --warmup 5 --no-cpu-baseline --traffic off --no-exchange-probe --no-legs > "$OUT/bench_plain_$name.json" 2> "$OUT/bench_plain_$name.err" || echo "plain $name failed"
 done
 find "$OUT" -name "*.csv" | head -40

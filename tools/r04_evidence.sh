@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04/evidence
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 # headline: plain run, then the same command under rocprofv3 --kernel-trace --stats
 timeout -k 10 300 $B > $O/bench_n1.json 2> $O/bench_n1.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_10M -- $B --steps 10 --warmup 2 --no-cpu-baseline --traffic off --no-stall-test --no-exchange-probe > $O/bench_under_rocprof_10M.json 2> $O/stats_10M.err

@@ -7,7 +7,7 @@ set -u
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${REHEARSE_TAG:-r05}/rehearse
 rm -rf $O; mkdir -p $O; cd $O
-B="python3 $R/bench.py --particles 5000000 --steps 8 --warmup 2 --traffic off --rehearse-shared-gpu"
+B="python3 $R/bench.py --full --particles 5000000 --steps 8 --warmup 2 --traffic off --rehearse-shared-gpu"
 for n in 2 4; do
   timeout -k 10 240 $B --gpus $n > shared_gpu_$n.json 2> shared_gpu_$n.err
   PGSD_RCCL_LIBRARY=$R/tests/build/libpgsd_fake_rccl.so timeout -k 10 240 $B --gpus $n > rccl_glue_$n.json 2> rccl_glue_$n.err
