@@ -437,6 +437,8 @@ class DevicePipeline
         release_events();
         if (m_cmp_host)
             (void)hipHostFree(m_cmp_host);
+        if (m_bad_host)
+            (void)hipHostFree(m_bad_host);
         if (m_cmp_dev)
             (void)hipFree(m_cmp_dev);
         if (park())
@@ -885,7 +887,12 @@ class DevicePipeline
         }
 
     // ---- read side: file -> pinned slab (pread) -> HBM staging (H2D) -> unpack kernel ----
-    int read_submit(long long file_offset, size_t bytes, pgsd_unpack_job job, uint64_t N)
+    private:
+    struct ReadReq;
+
+    public:
+    int read_submit(long long file_offset, size_t bytes, pgsd_unpack_job job, uint64_t N, const uint32_t* rows = nullptr,
+                    uint64_t src_N = 0, bool stage_only = false, std::shared_ptr<ReadReq>* out = nullptr)
         {
         if (!m_ok)
             return PGSD_ERROR_NO_DEVICE;
@@ -925,6 +932,13 @@ class DevicePipeline
             direct_req->N = N;
             direct_req->pieces_left = 0;
             direct_req->all_copied = nullptr; // nothing to wait for: the bytes are there
+            direct_req->rows = rows;
+            direct_req->src_N = src_N;
+            direct_req->stage_only = stage_only;
+            if (out)
+                *out = direct_req;
+            if (stage_only)
+                return PGSD_SUCCESS;
             std::lock_guard<std::mutex> g(m_copy_mutex);
             m_unpack_pending.push_back(direct_req);
             return PGSD_SUCCESS;
@@ -946,9 +960,14 @@ class DevicePipeline
         req->job = job;
         req->N = N;
         req->pieces_left = (bytes + piece - 1) / piece;
+        req->rows = rows;
+        req->src_N = src_N;
+        req->stage_only = stage_only;
         req->all_copied = get_event(false);
         if (!req->all_copied)
             return PGSD_ERROR_DEVICE;
+        if (out)
+            *out = req;
         std::unique_lock<std::mutex> lk(m_mutex);
         m_reads_outstanding += req->pieces_left; // counted per piece: see read_piece()
         lk.unlock();
@@ -959,6 +978,79 @@ class DevicePipeline
             long long foff = file_offset + (long long)off;
             writer_pool_submit(m_reader->pool, [this, req, dst, n, foff] { read_piece(req, dst, n, foff); });
             }
+        return PGSD_SUCCESS;
+        }
+
+    // Indexed read: the whole chunk is staged as for a slab read -- or, when it is the position chunk the last
+    // select_domain() staged (same file range, no wait_read since), taken from that staging without reading the file
+    // again -- and wait_read's deferred launch gathers rows[0 .. n) of it.
+    int read_rows_submit(long long file_offset, size_t bytes, pgsd_unpack_job job, uint64_t src_N, const uint32_t* rows,
+                         uint64_t n)
+        {
+        if (!m_ok)
+            return PGSD_ERROR_NO_DEVICE;
+        if (failed())
+            return PGSD_ERROR_DEVICE;
+        if (m_kept_src && m_kept_offset == file_offset && m_kept_bytes == bytes)
+            {
+            auto req = std::make_shared<ReadReq>();
+            job.src = m_kept_src;
+            req->job = job;
+            req->N = n;
+            req->pieces_left = 0;
+            req->all_copied = nullptr; // select_domain() synchronised the copies
+            req->rows = rows;
+            req->src_N = src_N;
+            std::lock_guard<std::mutex> g(m_copy_mutex);
+            m_unpack_pending.push_back(req);
+            return PGSD_SUCCESS;
+            }
+        return read_submit(file_offset, bytes, job, n, rows, src_N);
+        }
+
+    // Domain selection: stage the position chunk (file -> pinned -> HBM, or the direct road), select on the pack stream,
+    // synchronise.  The staged rows are kept until the next wait_read for an indexed read of the same chunk.
+    int select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count)
+        {
+        if (!m_ok)
+            return PGSD_ERROR_NO_DEVICE;
+        if (failed())
+            return PGSD_ERROR_DEVICE;
+        HIP_TRY(hipSetDevice(m_cfg.device));
+        std::shared_ptr<ReadReq> req;
+        if (m_kept_src && m_kept_offset == file_offset && m_kept_bytes == bytes)
+            d.pos = m_kept_src;
+        else
+            {
+            pgsd_unpack_job job;
+            memset(&job, 0, sizeof(job));
+            int rc = read_submit(file_offset, bytes, job, d.N, nullptr, 0, true, &req);
+            if (rc != PGSD_SUCCESS)
+                return rc;
+            std::unique_lock<std::mutex> lk(m_mutex);
+            m_cv_done.wait(lk, [this] { return m_reads_outstanding == 0; });
+            lk.unlock();
+            if (failed() || !req)
+                return m_io_error ? PGSD_ERROR_IO : PGSD_ERROR_DEVICE;
+            if (req->all_copied)
+                HIP_TRY(hipStreamWaitEvent(m_pack_stream, req->all_copied, 0));
+            d.pos = req->job.src;
+            }
+        // the row list belongs to the caller: what its stream still does with that memory comes first
+        hipEvent_t ready = get_event(false);
+        if (!ready)
+            return PGSD_ERROR_DEVICE;
+        HIP_TRY(hipEventRecord(ready, m_source_stream));
+        HIP_TRY(hipStreamWaitEvent(m_pack_stream, ready, 0));
+        std::string err;
+        int rc = launch_select_domain(d, out_rows, out_count, m_pack_stream, &err);
+        if (rc == PGSD_ERROR_DEVICE)
+            fail(err);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        m_kept_src = d.pos;
+        m_kept_offset = file_offset;
+        m_kept_bytes = bytes;
         return PGSD_SUCCESS;
         }
 
@@ -976,6 +1068,9 @@ class DevicePipeline
             e = hipStreamSynchronize(m_pack_stream);
         if (e != hipSuccess)
             fail(std::string("stream synchronize: ") + hipGetErrorString(e));
+        // an indexed read met a row outside its chunk: nothing was written for it (the pipeline itself is fine)
+        const bool bad_rows = m_bad_host && __atomic_exchange_n(m_bad_host, 0u, __ATOMIC_ACQ_REL) != 0;
+        m_kept_src = nullptr; // the staging select_domain() kept is given up with every wait
         bool writes_idle;
             {
             std::lock_guard<std::mutex> g(m_mutex);
@@ -987,6 +1082,7 @@ class DevicePipeline
             for (auto& a : m_arenas)
                 a.used = 0;
             m_dused = 0;
+        m_kept_src = nullptr;
             }
         if (failed())
             {
@@ -994,7 +1090,7 @@ class DevicePipeline
                 errno = m_io_errno;
             return m_io_error ? PGSD_ERROR_IO : PGSD_ERROR_DEVICE;
             }
-        return PGSD_SUCCESS;
+        return bad_rows ? PGSD_ERROR_INVALID_ARGUMENT : PGSD_SUCCESS;
         }
 
     void set_source_stream(void* stream)
@@ -1047,6 +1143,7 @@ class DevicePipeline
             for (auto& a : m_arenas)
                 a.used = 0;
             m_dused = 0;
+        m_kept_src = nullptr;
             }
         if (failed())
             {
@@ -1093,6 +1190,9 @@ class DevicePipeline
         uint64_t N;
         size_t pieces_left;
         hipEvent_t all_copied;
+        const uint32_t* rows = nullptr; // indexed read: N destination rows gathered from rows[] of the src_N staged ones
+        uint64_t src_N = 0;
+        bool stage_only = false;        // staged for select_domain(), which waits for the pieces itself: no unpack
         };
     struct Staged
         {
@@ -1195,6 +1295,7 @@ class DevicePipeline
         for (auto& a : m_arenas)
             a.used = 0;
         m_dused = 0;
+        m_kept_src = nullptr;
         return failed() ? PGSD_ERROR_DEVICE : PGSD_SUCCESS;
         }
 
@@ -1228,6 +1329,7 @@ class DevicePipeline
             m_ddev = (char*)dev;
             m_dcap = cap;
             m_dused = 0;
+        m_kept_src = nullptr;
             }
         return m_dcap - m_dused >= bytes;
         }
@@ -1532,12 +1634,26 @@ class DevicePipeline
         while (!pending.empty() && !failed())
             {
             const uint64_t N = pending.front()->N;
+            const uint32_t* rows = pending.front()->rows;
+            const uint64_t src_N = pending.front()->src_N;
             std::vector<pgsd_unpack_job> jobs;
             std::vector<std::shared_ptr<ReadReq>> rest;
             hipError_t e = hipSuccess;
+            if (rows && !m_bad_host)
+                {
+                void* alias = nullptr;
+                e = hipHostMalloc((void**)&m_bad_host, sizeof(uint32_t), hipHostMallocMapped);
+                if (e == hipSuccess)
+                    e = hipHostGetDevicePointer(&alias, m_bad_host, 0);
+                if (e == hipSuccess)
+                    {
+                    *m_bad_host = 0;
+                    m_bad_dev = (uint32_t*)alias;
+                    }
+                }
             for (auto& r : pending)
                 {
-                if (r->N != N)
+                if (r->N != N || r->rows != rows || r->src_N != src_N)
                     {
                     rest.push_back(r);
                     continue;
@@ -1560,7 +1676,8 @@ class DevicePipeline
             std::string err;
             if (e != hipSuccess)
                 fail(std::string("read pipeline event: ") + hipGetErrorString(e));
-            else if (launch_unpack((uint32_t)jobs.size(), jobs.data(), N, m_pack_stream, &err) != PGSD_SUCCESS)
+            else if (launch_unpack((uint32_t)jobs.size(), jobs.data(), N, m_pack_stream, &err, rows, src_N,
+                                   rows ? m_bad_dev : nullptr) != PGSD_SUCCESS)
                 fail(err);
             pending.swap(rest);
             }
@@ -1618,7 +1735,7 @@ class DevicePipeline
                 hipError_t e = hipEventRecord(req->all_copied, m_copy_stream);
                 if (e != hipSuccess)
                     fail(std::string("read pipeline event: ") + hipGetErrorString(e));
-                else
+                else if (!req->stage_only)
                     m_unpack_pending.push_back(req);
                 }
             }
@@ -1703,6 +1820,11 @@ class DevicePipeline
     uint32_t* m_cmp_host_dev = nullptr;
     uint32_t* m_cmp_dev = nullptr;
     uint32_t m_cmp_gen = 0;
+    uint32_t* m_bad_host = nullptr;        // indexed reads: set by a gather that met a row outside its chunk (pinned)
+    uint32_t* m_bad_dev = nullptr;         // ... its device alias
+    const void* m_kept_src = nullptr;      // select_domain(): the staged position rows, kept until the next wait_read
+    long long m_kept_offset = 0;
+    size_t m_kept_bytes = 0;
     bool m_coalesce = true;                // neighbours in the file leave in one pwritev (write_direct)
     size_t m_soft_cap = (size_t)6 << 30;   // staging held by frames on their way before stage() waits (PGSD_STAGING_CAP_MIB)
     std::vector<DirectWrite> m_direct;     // committed direct chunks waiting for their pwrite (m_mutex)
@@ -1834,8 +1956,28 @@ int device_pipeline_read(DevicePipeline* p, long long file_offset, size_t bytes,
 int device_pipeline_wait_read(DevicePipeline* p, std::string* err)
     {
     int rc = p->wait_read();
+    if (rc == PGSD_ERROR_INVALID_ARGUMENT && err)
+        *err = "indexed read: a row index lies outside its chunk (nothing was written for it)";
+    else if (rc != PGSD_SUCCESS && err)
+        *err = p->error();
+    return rc;
+    }
+
+int device_pipeline_read_rows(DevicePipeline* p, long long file_offset, size_t bytes, const pgsd_unpack_job& job,
+                              uint64_t src_N, const uint32_t* rows, uint64_t n, std::string* err)
+    {
+    int rc = p->read_rows_submit(file_offset, bytes, job, src_N, rows, n);
     if (rc != PGSD_SUCCESS && err)
         *err = p->error();
+    return rc;
+    }
+
+int device_pipeline_select_domain(DevicePipeline* p, long long file_offset, size_t bytes, const DomainArgs& d,
+                                  uint32_t* out_rows, uint64_t* out_count, std::string* err)
+    {
+    int rc = p->select_domain(file_offset, bytes, d, out_rows, out_count);
+    if (rc != PGSD_SUCCESS && err)
+        *err = p->error().empty() ? std::string(last_error()) : p->error();
     return rc;
     }
 

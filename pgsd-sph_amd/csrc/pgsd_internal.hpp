@@ -143,6 +143,26 @@ void device_pipeline_set_source_stream(DevicePipeline*, void* stream);
 int device_pipeline_read(DevicePipeline*, long long file_offset, size_t bytes, const pgsd_unpack_job& job, uint64_t N,
                          std::string* err);
 int device_pipeline_wait_read(DevicePipeline*, std::string* err);
+// Domain selection over a staged position chunk (N x 3 float32 / float64 rows): the fractional coordinates of
+// HOOMD's BoxDim::makeFraction, evaluated in float64 without contraction, wrapped into [0, 1) per axis.
+struct DomainArgs
+    {
+    const void* pos;
+    uint64_t N;
+    uint32_t f64;   // 1: rows of doubles
+    uint32_t dims;  // 2: z is ignored
+    double L[3];    // box lengths
+    double xy, xz, yz;
+    double lo[3], hi[3];
+    };
+// indexed read: the chunk's bytes at `file_offset` (src_N rows) are staged whole; wait_read gathers rows[0 .. n) of them
+// into job.dst (job.dst.order is null).  The position rows a select_domain left staged are taken from there.
+int device_pipeline_read_rows(DevicePipeline*, long long file_offset, size_t bytes, const pgsd_unpack_job& job,
+                              uint64_t src_N, const uint32_t* rows, uint64_t n, std::string* err);
+// stage the position chunk at `file_offset` (d.N rows; d.pos is filled in), select the rows inside the domain into
+// out_rows (device), the count into *out_count; synchronous.  The staged rows stay until the next wait_read.
+int device_pipeline_select_domain(DevicePipeline*, long long file_offset, size_t bytes, const DomainArgs& d,
+                                  uint32_t* out_rows, uint64_t* out_count, std::string* err);
 int device_pipeline_drain(DevicePipeline*, std::string* err);
 void device_pipeline_stats(DevicePipeline*, pgsd_device_stats* out, int reset);
 

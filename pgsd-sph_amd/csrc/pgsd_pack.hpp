@@ -4,6 +4,7 @@
 #define PGSD_PACK_HPP
 
 #include "pgsd.h"
+#include "pgsd_internal.hpp"
 #include "pgsd_private.h"
 
 #include <hip/hip_runtime_api.h>
@@ -205,11 +206,33 @@ struct UnrowsArgs
     uint64_t n_blocks;
     uint32_t n_groups;
     uint32_t pad;
+    // indexed read (gather): destination row i takes chunk row rows[i]; an entry >= src_N stores nothing and sets *bad
+    const uint32_t* rows;
+    uint64_t src_N;
+    uint32_t* bad;
     UnrowsGroup g[ROWS_MAX_GROUPS];
     };
 
+// the generic gather of an indexed read: element per lane, dst[k][col0 + c] = convert(chunk[rows[k]][c])
+struct GatherArgs
+    {
+    const void* src;
+    void* dst;
+    const uint32_t* rows;
+    uint32_t* bad;
+    uint64_t n, src_N;
+    uint32_t M, ssz, dsz, kind, dst_stride, dst_col0;
+    };
+
 // Enqueue the unpack of `n_jobs` chunks of N rows each on `stream`. Returns a pgsd_error.
-int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipStream_t stream, std::string* err);
+// With `rows` (device memory, N ascending entries): an indexed read -- destination row i takes row rows[i] of every
+// chunk, whose own height is src_N; an entry >= src_N writes nothing and sets the word *bad (device-visible) to 1.
+int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipStream_t stream, std::string* err,
+                  const uint32_t* rows = nullptr, uint64_t src_N = 0, uint32_t* bad = nullptr);
+
+// count -> one-block scan -> scatter of the rows inside the domain into out_rows (device, room for N), ascending;
+// synchronises `stream` and leaves the count in *out_count (host)
+int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err);
 
 // Enqueue the pack of `n_jobs` fields of N rows each on `stream`. Returns a pgsd_error.
 // ev_start / ev_stop (optional) receive the begin time of the first and the end time of the last kernel.

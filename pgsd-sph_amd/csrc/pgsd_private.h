@@ -11,6 +11,9 @@
  *   housekeeping      pgsd_device_release_parked, pgsd_reload_tuning
  *   binding helpers   pgsd_device_of, pgsd_device_copy (pgsd.fl keeps library-owned device buffers on the pipeline's
  *                     device and clones them without a tensor library)
+ *   restart helpers   pgsd_select_domain_device, pgsd_read_rows_device (pgsd.fl's select_domain_device and
+ *                     read_chunk_device(rows=...), behind pgsd.hoomd's read_frame_device(domain=...): a rank of a
+ *                     domain-decomposed run reads its own particles; the public header has no room for them)
  */
 #ifndef PGSD_PRIVATE_H
 #define PGSD_PRIVATE_H
@@ -74,6 +77,30 @@ extern "C"
     /* `bytes` bytes from src to dst: device memory on `device` (-1: the current one) or host memory, either side
        (hipMemcpyDefault); complete on return. */
     int pgsd_device_copy(int device, void* dst, const void* src, size_t bytes);
+
+    /* ---- restart helpers behind pgsd.fl / pgsd.hoomd ---- */
+
+    /* The rows of a frame's position chunk (N x 3 float32 or float64, N < 2^32) that lie in one spatial domain, in
+       ascending order.  The predicate is HOOMD's BoxDim::makeFraction in float64, operation for operation (no FMA
+       contraction), box = {Lx, Ly, Lz, xy, xz, yz}:
+           sx = ((x + Lx/2) - ((xz - yz*xy)*z + xy*y)) / Lx,  sy = ((y + Ly/2) - yz*z) / Ly,  sz = (z + Lz/2) / Lz
+           s = s - floor(s), then 0 where s >= 1 (periodic wrap);  inside: lo[a] <= s[a] < hi[a] for x, y and -- unless
+           dimensions == 2 -- z.
+       Requires 0 <= lo < hi <= 1 per axis, Lx, Ly > 0 and Lz > 0 unless dimensions == 2 (dimensions is 2 or 3).
+       out_rows: device memory with room for position->N entries; *out_count (host) receives their number.  The chunk is
+       staged into HBM and the call synchronises; the staged rows are kept until the next pgsd_device_wait_read, so a
+       pgsd_read_rows_device of the same chunk before it reads no file bytes again. */
+    int pgsd_select_domain_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position, const float box[6],
+                                  uint32_t dimensions, const double lo[3], const double hi[3], uint32_t* out_rows,
+                                  uint64_t* out_count);
+
+    /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, ascending), converted by the
+       unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is
+       staged whole; like pgsd_read_chunk_device the gather runs at pgsd_device_wait_read, which fails with
+       PGSD_ERROR_INVALID_ARGUMENT if an entry is >= chunk->N (nothing is written for such an entry).  Chunks of 2^32
+       rows or more are refused. */
+    int pgsd_read_rows_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk, const uint32_t* rows,
+                              uint64_t n, const struct pgsd_field_dst* dst);
 
 #ifdef __cplusplus
     }

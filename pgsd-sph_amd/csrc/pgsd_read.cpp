@@ -303,3 +303,131 @@ catch (...)
     {
         return pgsd_amd::abi_guard();
     }
+
+// The file range of a device read of a whole chunk, checked against the file; the flush a read needs comes first.
+static int whole_chunk_range(Impl* s, struct pgsd_handle* handle, const pgsd_index_entry& c, long long* foff, size_t* bytes)
+    {
+    if (s->flags != PGSD_OPEN_READONLY)
+        {
+        int rc = flush_for_read(s);
+        publish(handle, s);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        }
+    const size_t sz = sizeof_type(c.type);
+    if (sz == 0 || c.M == 0)
+        return PGSD_ERROR_FILE_CORRUPT;
+    if (c.N >= (1ull << 32))
+        {
+        set_last_error("chunks of 2^32 rows or more have no 32-bit row list");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    if (c.N == 0)
+        {
+        *foff = 0;
+        *bytes = 0;
+        return PGSD_SUCCESS;
+        }
+    if (c.location == 0)
+        return PGSD_ERROR_FILE_CORRUPT;
+    *bytes = (size_t)(c.N * c.M * sz);
+    *foff = c.location;
+    if ((uint64_t)(c.location + (long long)*bytes) > (uint64_t)s->file_size)
+        return PGSD_ERROR_FILE_CORRUPT;
+    return ensure_device(s);
+    }
+
+extern "C" int pgsd_select_domain_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                         const float box[6], uint32_t dimensions, const double lo[3], const double hi[3],
+                                         uint32_t* out_rows, uint64_t* out_count)
+    try
+    {
+    Impl* s = impl_of(handle);
+    if (!s || !position || !box || !lo || !hi || !out_count || (dimensions != 2 && dimensions != 3))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    for (int a = 0; a < 3; a++)
+        if (!(0.0 <= lo[a] && lo[a] < hi[a] && hi[a] <= 1.0))
+            {
+            set_last_error("pgsd_select_domain_device: the domain must satisfy 0 <= lo < hi <= 1 on every axis");
+            return PGSD_ERROR_INVALID_ARGUMENT;
+            }
+    if (!(box[0] > 0.0f && box[1] > 0.0f && (dimensions == 2 || box[2] > 0.0f)))
+        {
+        set_last_error("pgsd_select_domain_device: box lengths must be positive (Lz unless dimensions == 2)");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    pgsd_index_entry c = *position; // a flush may move the index storage
+    if ((c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE) || c.M != 3)
+        {
+        set_last_error("pgsd_select_domain_device: positions are N x 3 float32 or float64 rows");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    *out_count = 0;
+    if (c.N == 0)
+        return PGSD_SUCCESS;
+    if (!out_rows)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    DomainArgs d;
+    memset(&d, 0, sizeof(d));
+    d.N = c.N;
+    d.f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    d.dims = dimensions;
+    for (int a = 0; a < 3; a++)
+        {
+        d.L[a] = (double)box[a];
+        d.lo[a] = lo[a];
+        d.hi[a] = hi[a];
+        }
+    d.xy = (double)box[3];
+    d.xz = (double)box[4];
+    d.yz = (double)box[5];
+    std::string err;
+    rc = device_pipeline_select_domain(s->dev, foff, bytes, d, out_rows, out_count, &err);
+    if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_read_rows_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk, const uint32_t* rows,
+                                     uint64_t n, const struct pgsd_field_dst* dst)
+    try
+    {
+    Impl* s = impl_of(handle);
+    if (!s || !chunk || !dst || dst->order)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    if (n == 0)
+        return PGSD_SUCCESS; // (an empty destination may have no address)
+    if (!dst->dst)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    pgsd_index_entry c = *chunk; // a flush may move the index storage
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (!rows || n > c.N)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    pgsd_unpack_job job;
+    memset(&job, 0, sizeof(job));
+    job.src_type = c.type;
+    job.M = c.M;
+    job.dst = *dst;
+    std::string err;
+    rc = device_pipeline_read_rows(s->dev, foff, bytes, job, c.N, rows, n, &err);
+    if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }

@@ -356,6 +356,143 @@ __global__ __launch_bounds__(SEL_THREADS) void select_scatter_kernel(const uint8
     for (uint32_t e = head + 4 * nvec + threadIdx.x; e < total; e += SEL_THREADS)
         out[e] = local[e];
     }
+
+// ------------------------------------------------------------------ domain selection (restart of a domain-decomposed run)
+// The rows of a staged position chunk whose fractional coordinates lie in [lo, hi) per axis: HOOMD's
+// BoxDim::makeFraction in float64, in the operation order of pgsd.hoomd.domain_rows (the numpy model, which is the
+// definition), no contraction into FMAs -- a particle on a split plane must land in the same cell as the model says.
+// Lane t of a workgroup owns rows base + k * SEL_THREADS + t, k < SEL_PER_THREAD (consecutive lanes, consecutive rows:
+// coalesced 12-byte loads); bit k of its mask is row k's verdict.  Count pass, the one-block scan of pgsd_select_rows,
+// scatter pass; the scatter orders a workgroup's rows by (k, wave, lane) through wave ballots, i.e. ascending.
+__device__ __forceinline__ bool domain_inside(const DomainArgs& d, double x, double y, double z)
+    {
+#pragma clang fp contract(off)
+    double s[3];
+    s[0] = ((x + d.L[0] / 2.0) - ((d.xz - d.yz * d.xy) * z + d.xy * y)) / d.L[0];
+    s[1] = ((y + d.L[1] / 2.0) - d.yz * z) / d.L[1];
+    s[2] = (z + d.L[2] / 2.0) / d.L[2];
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+        {
+        if (a == 2 && d.dims == 2)
+            break;
+        double f = s[a] - floor(s[a]);
+        if (f >= 1.0)
+            f = 0.0;
+        in = in && d.lo[a] <= f && f < d.hi[a];
+        }
+    return in;
+    }
+
+template<bool F64> __device__ __forceinline__ uint32_t domain_mask(const DomainArgs& d, uint64_t base)
+    {
+    double p[SEL_PER_THREAD][3];
+#pragma unroll
+    for (int k = 0; k < SEL_PER_THREAD; k++)
+        {
+        const uint64_t i = base + (uint64_t)k * SEL_THREADS + threadIdx.x;
+        p[k][0] = p[k][1] = p[k][2] = 0.0;
+        if (i < d.N)
+            {
+            if constexpr (F64)
+                {
+                const double* q = (const double*)d.pos + i * 3;
+                p[k][0] = __builtin_nontemporal_load(q);
+                p[k][1] = __builtin_nontemporal_load(q + 1);
+                p[k][2] = __builtin_nontemporal_load(q + 2);
+                }
+            else
+                {
+                const u32x3 v = __builtin_nontemporal_load((const u32x3_a4*)((const uint32_t*)d.pos + i * 3));
+                p[k][0] = (double)__uint_as_float(v.x);
+                p[k][1] = (double)__uint_as_float(v.y);
+                p[k][2] = (double)__uint_as_float(v.z);
+                }
+            }
+        }
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < SEL_PER_THREAD; k++)
+        {
+        const uint64_t i = base + (uint64_t)k * SEL_THREADS + threadIdx.x;
+        if (i < d.N && domain_inside(d, p[k][0], p[k][1], p[k][2]))
+            m |= 1u << k;
+        }
+    return m;
+    }
+
+template<bool F64> __global__ __launch_bounds__(SEL_THREADS) void domain_count_kernel(const DomainArgs d, uint32_t* block_counts)
+    {
+    __shared__ uint32_t wave_sums[SEL_THREADS / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * SEL_PER_BLOCK;
+    const uint32_t c = (uint32_t)__popc(domain_mask<F64>(d, base));
+    const uint32_t inc = wave_inclusive_scan(c);
+    if ((threadIdx.x & 63) == 63)
+        wave_sums[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        block_counts[blockIdx.x] = wave_sums[0] + wave_sums[1] + wave_sums[2] + wave_sums[3];
+    }
+
+template<bool F64>
+__global__ __launch_bounds__(SEL_THREADS) void domain_scatter_kernel(const DomainArgs d, const uint64_t* block_offsets,
+                                                                     uint32_t* out_index)
+    {
+    constexpr uint32_t W = SEL_THREADS / 64;
+    __shared__ uint32_t cnt[SEL_PER_THREAD][W]; // kept rows per (k, wave), then their exclusive prefix in (k, wave) order
+    __shared__ uint32_t total;
+    __shared__ uint32_t local[SEL_PER_BLOCK];
+    const uint64_t base = (uint64_t)blockIdx.x * SEL_PER_BLOCK;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint32_t m = domain_mask<F64>(d, base);
+#pragma unroll
+    for (int k = 0; k < SEL_PER_THREAD; k++)
+        {
+        const uint64_t b = __ballot((m >> k) & 1u);
+        if (lane == 0)
+            cnt[k][wave] = (uint32_t)__popcll(b);
+        }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        {
+        uint32_t acc = 0;
+        for (int k = 0; k < SEL_PER_THREAD; k++)
+            for (uint32_t w = 0; w < W; w++)
+                {
+                const uint32_t c = cnt[k][w];
+                cnt[k][w] = acc;
+                acc += c;
+                }
+        total = acc;
+        }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SEL_PER_THREAD; k++)
+        {
+        const uint64_t b = __ballot((m >> k) & 1u);
+        if ((m >> k) & 1u)
+            local[cnt[k][wave] + (uint32_t)__popcll(b & below)] = (uint32_t)(base + (uint64_t)k * SEL_THREADS + threadIdx.x);
+        }
+    __syncthreads();
+    const uint32_t n = total;
+    uint32_t* out = out_index + block_offsets[blockIdx.x];
+    // 16-byte stores where the run's start allows, 4-byte stores for the ragged ends
+    const uint32_t lead = (uint32_t)((4u - (((uintptr_t)out >> 2) & 3u)) & 3u);
+    const uint32_t head = lead < n ? lead : n;
+    if (threadIdx.x < head)
+        out[threadIdx.x] = local[threadIdx.x];
+    const uint32_t nvec = (n - head) >> 2;
+    for (uint32_t v = threadIdx.x; v < nvec; v += SEL_THREADS)
+        {
+        const uint32_t e = head + 4 * v;
+        u32x4 q = {local[e], local[e + 1], local[e + 2], local[e + 3]};
+        *(u32x4*)(out + e) = q;
+        }
+    for (uint32_t e = head + 4 * nvec + threadIdx.x; e < n; e += SEL_THREADS)
+        out[e] = local[e];
+    }
     } // namespace pgsd_amd
 
 using namespace pgsd_amd;
@@ -371,7 +508,98 @@ struct SelectScratch
     };
 std::mutex g_select_lock;
 std::map<int, SelectScratch> g_select_scratch;
+
+// the scratch space of a compaction of N rows on `device` (current; g_select_lock held): the count (u64), the block counts
+// (u32) rounded to 8 bytes, the block offsets (u64); and the pinned word the scan leaves the count in
+int select_scratch(int device, uint64_t N, SelectScratch** out)
+    {
+    SelectScratch& sc = g_select_scratch[device];
+    const uint64_t nb = (N + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
+    const size_t need = 8 + (size_t)(((nb * 4 + 7) & ~7ull) + nb * 8);
+    if (need > sc.cap)
+        {
+        if (sc.dev)
+            (void)hipFree(sc.dev);
+        sc.dev = nullptr;
+        sc.cap = 0;
+        const size_t cap = std::max<size_t>(need * 2, 1u << 16);
+        if (hipMalloc(&sc.dev, cap) != hipSuccess)
+            {
+            sc.dev = nullptr;
+            set_last_error("pgsd_select_rows: cannot allocate the scratch space");
+            return PGSD_ERROR_MEMORY_ALLOCATION_FAILED;
+            }
+        sc.cap = cap;
+        }
+    if (!sc.host_count)
+        {
+        void* alias = nullptr;
+        if (hipHostMalloc((void**)&sc.host_count, sizeof(uint64_t), hipHostMallocMapped) != hipSuccess
+            || hipHostGetDevicePointer(&alias, sc.host_count, 0) != hipSuccess)
+            {
+            if (sc.host_count)
+                (void)hipHostFree(sc.host_count);
+            sc.host_count = nullptr;
+            set_last_error("pgsd_select_rows: cannot allocate pinned memory");
+            return PGSD_ERROR_MEMORY_ALLOCATION_FAILED;
+            }
+        sc.host_count_dev = (uint64_t*)alias;
+        }
+    *out = &sc;
+    return PGSD_SUCCESS;
+    }
     } // namespace
+
+namespace pgsd_amd
+    {
+int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err)
+    {
+    *out_count = 0;
+    if (d.N == 0)
+        return PGSD_SUCCESS;
+    if (d.N >= (1ull << 32) || !d.pos || !out_rows)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> guard(g_select_lock);
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess)
+        return PGSD_ERROR_DEVICE;
+    SelectScratch* sc = nullptr;
+    int rc = select_scratch(device, d.N, &sc);
+    if (rc != PGSD_SUCCESS)
+        {
+        if (err)
+            *err = last_error();
+        return rc;
+        }
+    (void)hipGetLastError(); // (see pgsd_select_rows)
+    const uint64_t n_blocks = (d.N + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
+    uint32_t* block_counts = (uint32_t*)((char*)sc->dev + 8);
+    uint64_t* block_offsets = (uint64_t*)((char*)sc->dev + 8 + ((n_blocks * 4 + 7) & ~7ull));
+    if (d.f64)
+        hipLaunchKernelGGL(domain_count_kernel<true>, dim3((unsigned)n_blocks), dim3(SEL_THREADS), 0, stream, d, block_counts);
+    else
+        hipLaunchKernelGGL(domain_count_kernel<false>, dim3((unsigned)n_blocks), dim3(SEL_THREADS), 0, stream, d, block_counts);
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(SEL_THREADS), 0, stream, block_counts, (uint32_t)n_blocks,
+                       block_offsets, (uint64_t*)sc->dev, sc->host_count_dev);
+    if (d.f64)
+        hipLaunchKernelGGL(domain_scatter_kernel<true>, dim3((unsigned)n_blocks), dim3(SEL_THREADS), 0, stream, d,
+                           block_offsets, out_rows);
+    else
+        hipLaunchKernelGGL(domain_scatter_kernel<false>, dim3((unsigned)n_blocks), dim3(SEL_THREADS), 0, stream, d,
+                           block_offsets, out_rows);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(stream); // the kernels are through: the count is in the pinned word
+    if (e != hipSuccess)
+        {
+        if (err)
+            *err = std::string("domain selection: ") + hipGetErrorString(e);
+        return PGSD_ERROR_DEVICE;
+        }
+    *out_count = __atomic_load_n(sc->host_count, __ATOMIC_ACQUIRE);
+    return PGSD_SUCCESS;
+    }
+    } // namespace pgsd_amd
 
 extern "C" int pgsd_select_rows(const uint8_t* flags, uint64_t N, uint32_t* out_index, uint64_t* out_count_host, void* stream_)
     try
@@ -411,41 +639,11 @@ extern "C" int pgsd_select_rows(const uint8_t* flags, uint64_t N, uint32_t* out_
         } scope {current, device != current};
     if (scope.on && hipSetDevice(device) != hipSuccess)
         return PGSD_ERROR_DEVICE;
-    SelectScratch& sc = g_select_scratch[device];
-        {
-        uint64_t nb = (N + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
-        // the count (u64) + block_counts (u32) rounded to 8 bytes + block_offsets (u64)
-        const size_t need = 8 + (size_t)(((nb * 4 + 7) & ~7ull) + nb * 8);
-        if (need > sc.cap)
-            {
-            if (sc.dev)
-                (void)hipFree(sc.dev);
-            sc.dev = nullptr;
-            sc.cap = 0;
-            const size_t cap = std::max<size_t>(need * 2, 1u << 16);
-            if (hipMalloc(&sc.dev, cap) != hipSuccess)
-                {
-                sc.dev = nullptr;
-                set_last_error("pgsd_select_rows: cannot allocate the scratch space");
-                return PGSD_ERROR_MEMORY_ALLOCATION_FAILED;
-                }
-            sc.cap = cap;
-            }
-        if (!sc.host_count)
-            {
-            void* alias = nullptr;
-            if (hipHostMalloc((void**)&sc.host_count, sizeof(uint64_t), hipHostMallocMapped) != hipSuccess
-                || hipHostGetDevicePointer(&alias, sc.host_count, 0) != hipSuccess)
-                {
-                if (sc.host_count)
-                    (void)hipHostFree(sc.host_count);
-                sc.host_count = nullptr;
-                set_last_error("pgsd_select_rows: cannot allocate pinned memory");
-                return PGSD_ERROR_MEMORY_ALLOCATION_FAILED;
-                }
-            sc.host_count_dev = (uint64_t*)alias;
-            }
-        }
+    SelectScratch* scp = nullptr;
+    int rc = select_scratch(device, N, &scp);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    SelectScratch& sc = *scp;
     // whatever an earlier call of this thread left in the runtime's last-error slot (a failed hipMalloc, the caller's own
     // calls) is not this launch's: the slot is read again right behind the launches
     (void)hipGetLastError();

@@ -280,10 +280,32 @@ __device__ __forceinline__ void unrows_place(uint32_t (&v)[4], const uint32_t (&
                 v[e] = w[s];
     }
 
-template<int T, int U, bool F64> __global__ __launch_bounds__(T) void unpack_rows_kernel(const UnrowsArgs args)
+// Source row of destination row i: i itself, or -- an indexed read (G) -- rows[i], bounds-checked against the chunk's
+// height: an entry outside it reads nothing, stores nothing and marks the launch bad (pgsd_device_wait_read fails).
+template<bool G> __device__ __forceinline__ bool unrows_src(const UnrowsArgs& args, uint64_t i, uint64_t* s)
+    {
+    if constexpr (!G)
+        {
+        *s = i;
+        return true;
+        }
+    else
+        {
+        const uint64_t r = args.rows[i];
+        if (r >= args.src_N)
+            {
+            __hip_atomic_store(args.bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            return false;
+            }
+        *s = r;
+        return true;
+        }
+    }
+
+template<int T, int U, bool F64, bool G> __global__ __launch_bounds__(T) void unpack_rows_kernel(const UnrowsArgs args)
     {
     const UnrowsGroup& g = args.g[blockIdx.y];
-    if (g.copy_vecs != 0 || g.copy_tail != 0)
+    if (!G && (g.copy_vecs != 0 || g.copy_tail != 0))
         {
         // dense same-type array: the chunk IS the array
         const u32x4* src = (const u32x4*)g.a;
@@ -308,18 +330,21 @@ template<int T, int U, bool F64> __global__ __launch_bounds__(T) void unpack_row
         {
         // xyz from a chunk, w = a constant (velocity without a mass chunk -> {vx, vy, vz, 1.0f}): whole rows out
         u32x3 xyz[U];
+        bool ok[U];
 #pragma unroll
         for (int k = 0; k < U; k++)
             {
             const uint64_t i = base + (uint64_t)k * T;
-            if (i < N)
-                xyz[k] = __builtin_nontemporal_load((const u32x3_a4*)(a + i * 3));
+            uint64_t s = 0;
+            ok[k] = i < N && unrows_src<G>(args, i, &s);
+            if (ok[k])
+                xyz[k] = __builtin_nontemporal_load((const u32x3_a4*)(a + s * 3));
             }
 #pragma unroll
         for (int k = 0; k < U; k++)
             {
             const uint64_t i = base + (uint64_t)k * T;
-            if (i < N)
+            if (ok[k])
                 {
                 const uint32_t c[4] = {xyz[k].x, xyz[k].y, xyz[k].z, 0};
                 unrows_store_whole<F64>(dst + i * DW, c, 8u, g.fill_lo, g.fill_hi);
@@ -343,14 +368,15 @@ template<int T, int U, bool F64> __global__ __launch_bounds__(T) void unpack_row
         for (int k = 0; k < U; k++)
             {
             const uint64_t i = base + (uint64_t)k * T;
-            if (i >= N)
+            uint64_t s = 0;
+            if (i >= N || !unrows_src<G>(args, i, &s))
                 continue;
             uint32_t wa[4], wb[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0};
-            unrows_load(a + i * g.a_nw, g.a_nw, wa);
+            unrows_load(a + s * g.a_nw, g.a_nw, wa);
             unrows_place(v, wa, g.a_nw, g.a_col0);
             if (b != nullptr)
                 {
-                unrows_load(b + i * g.b_nw, g.b_nw, wb);
+                unrows_load(b + s * g.b_nw, g.b_nw, wb);
                 unrows_place(v, wb, g.b_nw, g.b_col0);
                 }
             unrows_store_whole<F64>(dst + i * DW, v, mask, g.fill_lo, g.fill_hi);
@@ -362,21 +388,24 @@ template<int T, int U, bool F64> __global__ __launch_bounds__(T) void unpack_row
         // the hot shape: xyz from one chunk, w from another, whole rows out
         u32x3 xyz[U];
         uint32_t w[U];
+        bool ok[U];
 #pragma unroll
         for (int k = 0; k < U; k++)
             {
             const uint64_t i = base + (uint64_t)k * T;
-            if (i < N)
+            uint64_t s = 0;
+            ok[k] = i < N && unrows_src<G>(args, i, &s);
+            if (ok[k])
                 {
-                xyz[k] = __builtin_nontemporal_load((const u32x3_a4*)(a + i * 3));
-                w[k] = __builtin_nontemporal_load(b + i);
+                xyz[k] = __builtin_nontemporal_load((const u32x3_a4*)(a + s * 3));
+                w[k] = __builtin_nontemporal_load(b + s);
                 }
             }
 #pragma unroll
         for (int k = 0; k < U; k++)
             {
             const uint64_t i = base + (uint64_t)k * T;
-            if (i < N)
+            if (ok[k])
                 {
                 const uint32_t c[4] = {xyz[k].x, xyz[k].y, xyz[k].z, w[k]};
                 unrows_store<F64>(dst + i * DW, c, 4, 0);
@@ -389,15 +418,46 @@ template<int T, int U, bool F64> __global__ __launch_bounds__(T) void unpack_row
     for (int k = 0; k < U; k++)
         {
         const uint64_t i = base + (uint64_t)k * T;
-        if (i >= N)
+        uint64_t s = 0;
+        if (i >= N || !unrows_src<G>(args, i, &s))
             continue;
         uint32_t wa[4], wb[4] = {0, 0, 0, 0};
-        unrows_load(a + i * g.a_nw, g.a_nw, wa);
+        unrows_load(a + s * g.a_nw, g.a_nw, wa);
         if (b != nullptr)
-            unrows_load(b + i * g.b_nw, g.b_nw, wb);
+            unrows_load(b + s * g.b_nw, g.b_nw, wb);
         unrows_store<F64>(dst + i * DW, wa, g.a_nw, g.a_col0);
         if (b != nullptr)
             unrows_store<F64>(dst + i * DW, wb, g.b_nw, g.b_col0);
+        }
+    }
+
+// ------------------------------------------------------------------ generic gather (indexed reads, every other shape)
+// Element per lane, grid-stride: destination element (k, col0 + c) = convert(chunk row rows[k], column c).  The shapes
+// the row-per-lane kernel takes (Scalar4 rows fed by one or two chunks) never come here; this is the fallback for narrow,
+// wide or converted elements and for dense arrays, whose plain copy has no indexed twin.
+__global__ __launch_bounds__(256) void gather_elems_kernel(const GatherArgs a)
+    {
+    const uint64_t total = a.n * (uint64_t)a.M;
+    for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (uint64_t)gridDim.x * 256)
+        {
+        const uint64_t k = a.M == 1 ? t : t / a.M;
+        const uint32_t c = (uint32_t)(t - k * a.M);
+        const uint64_t r = a.rows[k];
+        if (r >= a.src_N)
+            {
+            __hip_atomic_store(a.bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            continue;
+            }
+        const uint64_t val = unpack_elem<false>((const char*)a.src + (r * a.M + c) * a.ssz, a.ssz, a.dsz, a.kind);
+        char* p = (char*)a.dst + (k * a.dst_stride + a.dst_col0 + c) * a.dsz;
+        if (a.dsz == 8)
+            *(uint64_t*)p = val;
+        else if (a.dsz == 4)
+            *(uint32_t*)p = (uint32_t)val;
+        else if (a.dsz == 2)
+            *(uint16_t*)p = (uint16_t)val;
+        else
+            *(uint8_t*)p = (uint8_t)val;
         }
     }
 
@@ -432,6 +492,18 @@ struct UnrowsPlan
 
 static void launch_unrows(const UnrowsPlan& p, uint64_t N, hipStream_t stream)
     {
+    if (p.args.rows)
+        {
+        // an indexed read: the default shape only (the lane's loads are row-sized pieces at scattered rows)
+        UnrowsArgs a = p.args;
+        a.n_blocks = (N + 127) / 128;
+        const dim3 grid((unsigned)a.n_blocks, a.n_groups);
+        if (p.f64)
+            hipLaunchKernelGGL((unpack_rows_kernel<64, 2, true, true>), grid, dim3(64), 0, stream, a);
+        else
+            hipLaunchKernelGGL((unpack_rows_kernel<64, 2, false, true>), grid, dim3(64), 0, stream, a);
+        return;
+        }
     // measured (profiles/r02_lab_unpack.jsonl, r02_unpack_rows_final.jsonl): thin workgroups; 64 x 2 rows
     // 102.4-103.0 us, 128 x 1 104.6-105.0 us, 256 x 2 105.9-106.0 us (10 M particles, stream events)
     int T = 64, U = 2;
@@ -445,9 +517,9 @@ static void launch_unrows(const UnrowsPlan& p, uint64_t N, hipStream_t stream)
     if (T == TT && U == UU)                                                                                    \
         {                                                                                                      \
         if (p.f64)                                                                                             \
-            hipLaunchKernelGGL((unpack_rows_kernel<TT, UU, true>), grid, dim3(TT), 0, stream, a);              \
+            hipLaunchKernelGGL((unpack_rows_kernel<TT, UU, true, false>), grid, dim3(TT), 0, stream, a);              \
         else                                                                                                   \
-            hipLaunchKernelGGL((unpack_rows_kernel<TT, UU, false>), grid, dim3(TT), 0, stream, a);             \
+            hipLaunchKernelGGL((unpack_rows_kernel<TT, UU, false, false>), grid, dim3(TT), 0, stream, a);             \
         return;                                                                                                \
         }
     UNROWS_LAUNCH(128, 1)
@@ -457,9 +529,9 @@ static void launch_unrows(const UnrowsPlan& p, uint64_t N, hipStream_t stream)
     a.n_blocks = (N + 127) / 128;
     const dim3 grid1((unsigned)a.n_blocks, a.n_groups);
     if (p.f64)
-        hipLaunchKernelGGL((unpack_rows_kernel<64, 2, true>), grid1, dim3(64), 0, stream, a);
+        hipLaunchKernelGGL((unpack_rows_kernel<64, 2, true, false>), grid1, dim3(64), 0, stream, a);
     else
-        hipLaunchKernelGGL((unpack_rows_kernel<64, 2, false>), grid1, dim3(64), 0, stream, a);
+        hipLaunchKernelGGL((unpack_rows_kernel<64, 2, false, false>), grid1, dim3(64), 0, stream, a);
 #undef UNROWS_LAUNCH
     }
 
@@ -563,7 +635,8 @@ void warm_unpack_kernels()
     (void)hipGetLastError();
     }
 
-int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipStream_t stream, std::string* err)
+int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipStream_t stream, std::string* err,
+                  const uint32_t* rows, uint64_t src_N, uint32_t* bad)
     {
     // whatever an earlier call of this thread left in the runtime's last-error slot (a failed hipMalloc, the caller's own
     // calls) is not this launch's: the slot is read again right behind the launches
@@ -586,6 +659,7 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
         else
             ok = ok && !(!s_int && d_int) && !(s_int && !d_int && ssz == 8);
         ok = ok && !(q.dst.fill_rest && q.dst.dst_stride > 32); // the fill addresses columns with a 32-bit mask
+        ok = ok && !(rows && (q.dst.order || !bad));            // an indexed read gathers; it does not scatter too
         if (!ok)
             {
             if (err)
@@ -625,6 +699,9 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
                 UnrowsPlan plan;
                 memset(&plan.args, 0, sizeof(plan.args));
                 plan.args.N = N;
+                plan.args.rows = rows;
+                plan.args.src_N = src_N;
+                plan.args.bad = bad;
                 plan.f64 = f64 != 0;
                 for (size_t i = 0; i < all.size();)
                     {
@@ -644,7 +721,7 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
                     const bool dense = ok && n == 1 && j0.kind == PACK_BITS && j0.ssz == j0.dsz && j0.dst_col0 == 0
                                        && j0.M == j0.dst_stride;
                     if (dense)
-                        ok = f64 == 0; // rides along in the launch of the first pass
+                        ok = f64 == 0 && !rows; // rides along in the launch of the first pass (no indexed twin)
                     else if (ok)
                         {
                         ok = j0.dst_stride == 4 && (f64 ? j0.dsz == 8 : j0.dsz == 4);
@@ -737,6 +814,32 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
                 }
             }
         i = e;
+        }
+    if (rows)
+        {
+        // an indexed read: what the row-per-lane kernel did not take, element by element, in the jobs' order ("the
+        // later chunk wins" by stream order)
+        for (const UnpackJob& j : all)
+            {
+            GatherArgs ga;
+            memset(&ga, 0, sizeof(ga));
+            ga.src = j.src;
+            ga.dst = j.dst;
+            ga.rows = rows;
+            ga.bad = bad;
+            ga.n = N;
+            ga.src_N = src_N;
+            ga.M = j.M;
+            ga.ssz = j.ssz;
+            ga.dsz = j.dsz;
+            ga.kind = j.kind;
+            ga.dst_stride = j.dst_stride;
+            ga.dst_col0 = j.dst_col0;
+            const uint64_t lanes = N * (uint64_t)j.M;
+            const uint64_t blocks = std::min<uint64_t>((lanes + 255) / 256, (uint64_t)num_cus() * 16);
+            hipLaunchKernelGGL(gather_elems_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(256), 0, stream, ga);
+            }
+        all.clear();
         }
     std::vector<UnpackJob> batch;
     uint32_t sum_rowbytes = 0;

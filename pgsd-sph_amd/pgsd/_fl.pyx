@@ -1257,8 +1257,62 @@ cdef class PGSDFile:
             return data_array.reshape([int(n)])
         return data_array
 
+    def select_domain_device(self, frame, name, box, domain, dimensions=3):
+        """The rows of a position chunk that lie in one spatial domain, selected on the GPU.
+
+        Args:
+            frame (int), name (str): the position chunk (N x 3 float32 or float64).
+            box: ``[Lx, Ly, Lz, xy, xz, yz]`` (rounded to float32, as a file stores it).
+            domain: a :class:`pgsd.hoomd.Domain` or a pair ``(lo, hi)`` of three fractions each, ``0 <= lo < hi <= 1``.
+            dimensions (int): 3, or 2 to ignore z.
+
+        Returns:
+            ``(rows, count)`` typed like :func:`select_rows`: the ascending rows whose fractional coordinates (HOOMD's
+            ``BoxDim::makeFraction`` in float64, wrapped into [0, 1)) lie in ``[lo, hi)`` on every axis -- an int32 GPU
+            tensor of ``count`` entries where torch is importable, a :class:`DeviceBuffer` view otherwise.  Exactly
+            :func:`pgsd.hoomd.domain_rows`.  The staged position rows are kept until the next :meth:`wait_read`: a
+            ``read_chunk_device(..., rows=rows)`` of the same chunk before it reads no file bytes again.
+        """
+        self._check_open()
+        torch = _lib._torch
+        cdef const C.pgsd_index_entry* e = self._find(frame, name)
+        if e == NULL:
+            raise KeyError("frame " + str(frame) + " / chunk " + name + " not found in: " + self._name)
+        cdef C.pgsd_index_entry entry = e[0]      # a later flush may move the index storage
+        lo, hi = (domain.lo, domain.hi) if hasattr(domain, 'lo') else domain
+        c_box = numpy.ascontiguousarray(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+        c_lo = numpy.ascontiguousarray(lo, dtype=numpy.float64).reshape(3)
+        c_hi = numpy.ascontiguousarray(hi, dtype=numpy.float64).reshape(3)
+        if c_box.shape[0] != 6:
+            raise ValueError("box must hold 6 values")
+        n = int(entry.N)
+        device = self.pipeline_device()
+        if torch is not None:
+            rows = torch.empty((max(n, 1),), dtype=torch.int32, device=torch.device('cuda', device))
+            p_rows = rows.data_ptr()
+        else:
+            rows = DeviceBuffer((max(n, 1),), numpy.int32, device)
+            p_rows = rows.ptr
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the selection is ordered behind this stream's use of `rows`
+        cdef uintptr_t c_rows = p_rows, c_pbox = c_box.ctypes.data, c_plo = c_lo.ctypes.data, c_phi = c_hi.ctypes.data
+        cdef uint32_t c_dims = int(dimensions)
+        cdef uint64_t k = 0
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_select_domain_device(&self._handle, &entry, <const float*>c_pbox, c_dims,
+                                                 <const double*>c_plo, <const double*>c_phi, <uint32_t*>c_rows, &k)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("select_domain_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
+        _raise_on_error(retval, self._name, err)
+        if isinstance(rows, DeviceBuffer):
+            return rows.view(shape=(int(k),)), int(k)
+        return rows[:int(k)], int(k)
+
     def read_chunk_device(self, frame, name, out=None, N=None, offset=0, columns=None, order=None,
-                          bitcast=False, wait=True, fill=None):
+                          bitcast=False, wait=True, fill=None, rows=None):
         """Read rows ``[offset, offset + N)`` of a chunk straight into GPU memory.
 
         The rows are ``pread`` into pinned slabs, copied to HBM and unpacked by a HIP kernel
@@ -1279,6 +1333,10 @@ cdef class PGSDFile:
             fill: value for the columns of ``out``'s rows that no chunk read before the same :meth:`wait_read`
                 writes (``pgsd_field_dst.fill_rest``): velocity into a ``Scalar4`` array with ``fill=1.0`` gives
                 ``(vx, vy, vz, 1.0)`` rows, stored whole.  ``None``: those columns keep what they hold.
+            rows: an indexed read -- ascending int32 row indices in GPU memory (e.g. from :func:`select_rows` or
+                :meth:`select_domain_device`); row ``k`` of ``out`` takes chunk row ``rows[k]``.  ``N`` defaults to
+                ``len(rows)``, ``offset`` must be 0 and ``order`` ``None``.  The whole chunk is staged and gathered
+                at :meth:`wait_read`, which raises if an entry lies outside the chunk.
 
         Returns:
             the destination tensor.
@@ -1292,6 +1350,20 @@ cdef class PGSDFile:
         eN, eM, etype = int(entry.N), int(entry.M), int(entry.type)
         if etype not in _PGSD_TO_NP:
             raise ValueError("invalid type for chunk: " + name)
+        cdef uintptr_t p_rows = 0
+        index_rows = rows                   # (`rows` is reused below for the destination's height)
+        if index_rows is not None:
+            if order is not None or int(offset) != 0:
+                raise ValueError("an indexed read (rows=) takes neither order nor offset")
+            es = index_rows.element_size() if hasattr(index_rows, 'element_size') else \
+                numpy.dtype(index_rows.__cuda_array_interface__['typestr']).itemsize
+            if es != 4:
+                raise ValueError("rows must hold 32-bit row indices")
+            p_rows, rows_bytes = _device_memory(index_rows, "rows")
+            if N is None:
+                N = rows_bytes // 4
+            if N > rows_bytes // 4 or N > eN:
+                raise ValueError("rows holds fewer entries than requested")
         if N is None:
             N = eN - int(offset)
         if N < 0 or int(offset) + N > eN:
@@ -1359,14 +1431,19 @@ cdef class PGSDFile:
             np_out = numpy.dtype(str(out_dtype)[6:]) if str(out_dtype).startswith('torch.') else numpy.dtype(out_dtype)
             dst.fill_rest = 1
             dst.fill_bits = int(numpy.array([fill], dtype=np_out).view(numpy.dtype('u%d' % np_out.itemsize))[0])
-        self._keepalive.append((out, order))
+        self._keepalive.append((out, order, index_rows))
         if not self._explicit_stream:
             self._sync_source_stream()      # the unpack is ordered behind this stream's use of `out`
         cdef uint64_t c_N = N, c_off = int(offset)
         cdef int retval, err
-        with nogil:
-            retval = C.pgsd_read_chunk_device(&self._handle, &entry, c_N, c_off, &dst)
-            err = errno
+        if index_rows is not None:
+            with nogil:
+                retval = C.pgsd_read_rows_device(&self._handle, &entry, <const uint32_t*>p_rows, c_N, &dst)
+                err = errno
+        else:
+            with nogil:
+                retval = C.pgsd_read_chunk_device(&self._handle, &entry, c_N, c_off, &dst)
+                err = errno
         _raise_on_error(retval, self._name, err)
         if wait:
             self.wait_read()

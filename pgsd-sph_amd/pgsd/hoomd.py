@@ -284,6 +284,106 @@ class Frame(object):
         self.constraints.validate()
 
 
+class Domain(object):
+    """One cell of a spatial domain decomposition: fractional box coordinates ``lo[a] <= s[a] < hi[a]`` per axis.
+
+    Args:
+        lo, hi: three fractions each (x, y, z), ``0 <= lo < hi <= 1``.
+    """
+
+    def __init__(self, lo, hi):
+        lo = tuple(float(v) for v in lo)
+        hi = tuple(float(v) for v in hi)
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError("a domain has three lower and three upper bounds")
+        if not all(0.0 <= a < b <= 1.0 for a, b in zip(lo, hi)):
+            raise ValueError("a domain needs 0 <= lo < hi <= 1 on every axis: %r, %r" % (lo, hi))
+        self.lo, self.hi = lo, hi
+
+    def __eq__(self, other):
+        return isinstance(other, Domain) and (self.lo, self.hi) == (other.lo, other.hi)
+
+    def __hash__(self):
+        return hash((self.lo, self.hi))
+
+    def __repr__(self):
+        return "Domain(lo=%r, hi=%r)" % (self.lo, self.hi)
+
+
+def _split_bounds(n, split, axis):
+    """Cell boundaries along one axis: n cells, `split` = the widths of the first n - 1 as fractions of the box."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n%s must be at least 1" % axis)
+    if split is None:
+        return [i / n for i in range(n)] + [1.0]
+    widths = [float(w) for w in split]
+    if len(widths) != n - 1 or any(not w > 0.0 for w in widths):
+        raise ValueError("%s_split must hold n%s - 1 = %d positive widths" % (axis, axis, n - 1))
+    bounds = [0.0]
+    for w in widths:
+        bounds.append(bounds[-1] + w)
+    if not bounds[-1] < 1.0:
+        raise ValueError("%s_split widths must sum to less than 1" % axis)
+    return bounds + [1.0]
+
+
+def domain_grid(nx, ny, nz, x_split=None, y_split=None, z_split=None):
+    """The cells of an nx x ny x nz domain decomposition as `Domain` objects, in HOOMD's rank order (``Index3D``:
+    rank = x + nx * (y + ny * z), x fastest).  ``x_split`` etc. are the widths of the first n - 1 cells along that axis
+    as fractions of the box, as in HOOMD's domain-decomposition split lists; ``None``: equal cells."""
+    bx = _split_bounds(nx, x_split, 'x')
+    by = _split_bounds(ny, y_split, 'y')
+    bz = _split_bounds(nz, z_split, 'z')
+    return [Domain((bx[i], by[j], bz[k]), (bx[i + 1], by[j + 1], bz[k + 1]))
+            for k in range(int(nz)) for j in range(int(ny)) for i in range(int(nx))]
+
+
+def _domain_bounds(domain):
+    if isinstance(domain, Domain):
+        return domain.lo, domain.hi
+    d = Domain(*domain)
+    return d.lo, d.hi
+
+
+def domain_rows(position, box, domain, dimensions=3):
+    """The rows of ``position`` (N x 3) inside ``domain``, ascending: the definition the GPU selection
+    (`pgsd.fl.PGSDFile.select_domain_device`, ``read_frame_device(domain=...)``) matches bit for bit.
+
+    HOOMD's ``BoxDim::makeFraction`` in float64, in exactly this operation order, box = ``[Lx, Ly, Lz, xy, xz, yz]``
+    rounded to float32 as a file stores it::
+
+        sx = ((x + Lx/2) - ((xz - yz*xy)*z + xy*y)) / Lx
+        sy = ((y + Ly/2) - yz*z) / Ly
+        sz = (z + Lz/2) / Lz
+        s  = s - floor(s); s = 0 where s >= 1          # periodic wrap, per axis
+        inside: lo[a] <= s[a] < hi[a] for x, y (and z unless dimensions == 2)
+    """
+    lo, hi = _domain_bounds(domain)
+    dimensions = int(dimensions)
+    if dimensions not in (2, 3):
+        raise ValueError("dimensions must be 2 or 3")
+    b = numpy.asarray(box, dtype=numpy.float32).reshape(-1)
+    if b.shape[0] < 6:
+        raise ValueError("box must hold 6 values")
+    Lx, Ly, Lz, xy, xz, yz = (numpy.float64(v) for v in b[:6])
+    if not (Lx > 0 and Ly > 0 and (dimensions == 2 or Lz > 0)):
+        raise ValueError("box lengths must be positive (Lz unless dimensions == 2)")
+    p = numpy.asarray(position)
+    p = p.astype(numpy.float64).reshape(-1, 3) if p.size else numpy.zeros((0, 3))
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    with numpy.errstate(invalid='ignore', divide='ignore'):
+        s = [((x + Lx / 2) - ((xz - yz * xy) * z + xy * y)) / Lx,
+             ((y + Ly / 2) - yz * z) / Ly,
+             (z + Lz / 2) / Lz]
+        inside = numpy.ones(p.shape[0], dtype=bool)
+        for a in range(2 if dimensions == 2 else 3):
+            f = s[a] - numpy.floor(s[a])
+            f[f >= 1.0] = 0.0
+            inside &= (lo[a] <= f) & (f < hi[a])
+    return numpy.flatnonzero(inside)
+
+
 class _FrameCursor(object):
     """What ``iter()`` hands out for a trajectory or a subset of one (the role of hoomd.py:471-488):
     it knows how many frames it covers (``len``), yields them in order, and asking it for an iterator
@@ -1101,7 +1201,7 @@ class HOOMDTrajectory(object):
             self._initial_frame = snap
         return snap
 
-    def read_frame_device(self, idx, part=None, scalar4=False, defaults=True):
+    def read_frame_device(self, idx, part=None, scalar4=False, defaults=True, domain=None):
         """Read frame ``idx`` with the per-particle arrays of THIS rank's partition in GPU memory.
 
         Restart path (BASELINE config 5): each rank reads rows ``[row0, row0 + n)`` of every
@@ -1118,6 +1218,11 @@ class HOOMDTrajectory(object):
             defaults (bool): attributes the file holds neither in this frame nor in frame 0 are filled with their
                 default rows as the host reader fills them (hoomd.py:872-881) -- views of one small device copy per
                 read, a third of a 1 024-particle frame's 90 us; False leaves them ``None``.
+            domain (`Domain`): instead of a row slab, the particles whose position lies in this cell of a spatial
+                domain decomposition (`domain_grid`), selected on the GPU from the frame's effective position and box
+                exactly as `domain_rows` defines it; every per-particle array is gathered through that row list, and
+                ``frame.tag`` holds it (file rows: the particle tags of a file written in tag order; int32, typed like
+                `pgsd.fl.select_rows`).  Not together with ``part``.
 
         Returns:
             `Frame` whose ``particles.N`` is this rank's count, ``particles.N_global`` the total.  The per-particle
@@ -1158,6 +1263,12 @@ class HOOMDTrajectory(object):
         else:
             snap.particles.types = snap.particles._default_value['types']
 
+        if domain is not None:
+            if part is not None:
+                raise ValueError("part and domain are mutually exclusive")
+            self._read_domain_device(idx, snap, domain, scalar4, defaults, n_global, frame_of)
+            self._read_logs_device(idx, snap, frame_of)
+            return snap
         if part is None:
             rank, size = self._comm()
             base, rem = divmod(n_global, size)
@@ -1248,6 +1359,11 @@ class HOOMDTrajectory(object):
         f.wait_read()
         for name, chunk in fresh:
             cache[chunk] = getattr(snap.particles, name).clone()
+        self._read_logs_device(idx, snap, frame_of)
+        return snap
+
+    def _read_logs_device(self, idx, snap, frame_of):
+        f = self.file
         for log in self._names_with_prefix('log/'):
             fr = frame_of(log)
             if fr is not None:
@@ -1255,7 +1371,108 @@ class HOOMDTrajectory(object):
         for state in self._names_with_prefix('state/'):
             if f.chunk_exists(idx, state):
                 snap.state[state[6:]] = f.read_chunk(idx, state)
-        return snap
+
+    def _read_domain_device(self, idx, snap, domain, scalar4, defaults, n_global, frame_of):
+        """`read_frame_device(domain=...)`: select the domain's rows from the effective position chunk, then gather every
+        per-particle array through them.  One `wait_read` per group of chunks that share destination rows, so the HBM
+        staging holds one or two chunks at a time, never the frame; the position chunk the selection staged serves the
+        position gather (same index entry, before the group's wait).  Frame 0's device cache of slab reads is not used."""
+        torch = fl._lib._torch
+        f = self.file
+        if not isinstance(domain, Domain):
+            domain = Domain(*domain)
+        dims = int(snap.configuration.dimensions)
+        box = snap.configuration.box
+        n_frame0 = []
+
+        def effective(chunk):
+            # the frame's own chunk, else frame 0's while N is frame 0's, else none (defaults): the host reader's choice
+            fr = frame_of(chunk)
+            if fr == 0 and idx != 0:
+                if not n_frame0:
+                    n_frame0.append(int(self._frame0_small('particles/N')[0]) if f.chunk_exists(0, 'particles/N')
+                                    else n_global)
+                if n_frame0[0] != n_global:
+                    return None
+            return fr
+
+        device = f.pipeline_device()
+        f_pos = effective('particles/position')
+        if f_pos is not None:
+            rows, count = f.select_domain_device(f_pos, 'particles/position', box, domain, dims)
+        else:
+            # no position anywhere: every particle sits at the origin, all of them or none are inside
+            count = n_global if len(domain_rows(numpy.zeros((1, 3), numpy.float32), box, domain, dims)) else 0
+            if torch is None:
+                rows = fl.DeviceBuffer((max(count, 1),), numpy.int32, device,
+                                       pattern=numpy.arange(max(count, 1), dtype=numpy.int32)).view(shape=(count,))
+            else:
+                rows = torch.arange(count, dtype=torch.int32, device=torch.device('cuda', device))
+        snap.particles.N = count
+        snap.particles.N_global = n_global
+        snap.part = None
+        snap.domain = domain
+        snap.tag = rows
+
+        def gather(chunk, fr, **kw):
+            return f.read_chunk_device(fr, chunk, rows=rows, N=count, wait=False, **kw)
+
+        def empty4():
+            if torch is None:
+                return fl.DeviceBuffer((count, 4), numpy.float32, device)
+            return torch.empty((count, 4), dtype=torch.float32, device=torch.device('cuda', device))
+
+        # group 1: position (the staged rows of the selection) and, with scalar4, (x, y, z, typeid bits)
+        done = set()
+        if f_pos is not None:
+            snap.particles.position = gather('particles/position', f_pos)
+            done.add('position')
+        groups = [(('particles/position', 'particles/typeid', True, 0.0), 'pos4'),
+                  (('particles/velocity', 'particles/mass', False, 1.0), 'vel4')] if scalar4 else []
+        for (xyz, w, w_bitcast, w_default), attr in groups:
+            f_xyz, f_w = effective(xyz), effective(w)
+            if f_xyz is None and f_w is None:
+                row = numpy.array([0.0, 0.0, 0.0, w_default], dtype=numpy.float32)
+                if torch is None:
+                    arr = fl.DeviceBuffer((count, 4), numpy.float32, device, pattern=row)
+                else:
+                    arr = torch.zeros((count, 4), dtype=torch.float32, device=torch.device('cuda', device))
+                    arr[:, 3] = w_default
+            else:
+                arr = empty4()
+                if f_xyz is not None:
+                    gather(xyz, f_xyz, out=arr, columns=(0, 3), fill=w_default if f_w is None else None)
+                if f_w is not None:
+                    gather(w, f_w, out=arr, columns=(3, 4), bitcast=w_bitcast, fill=0.0 if f_xyz is None else None)
+            setattr(snap.particles, attr, arr)
+            f.wait_read()
+        if not scalar4:
+            f.wait_read()
+
+        # every other per-particle array: one chunk, one wait
+        default_rows, typed = None, {}
+        for name, (dt, M) in list(_PARTICLE_SPEC.items()) + list(_PARTICLE_SPEC_EXTRA.items()):
+            if name in done:
+                continue
+            chunk = 'particles/' + name
+            fr = effective(chunk)
+            if fr is not None:
+                setattr(snap.particles, name, gather(chunk, fr))
+                f.wait_read()
+            elif defaults and name in snap.particles._default_value:
+                if default_rows is None:
+                    default_rows = self._default_rows_template(device).clone()
+                off, words, ndt = self._default_rows_layout[name]
+                if torch is None:
+                    view = default_rows.view(dtype=ndt, shape=(count, M) if M > 1 else (count,),
+                                             strides=(0, ndt.itemsize) if M > 1 else (0,), offset_bytes=4 * off)
+                else:
+                    tdt = getattr(torch, ndt.name)
+                    base = typed.get(tdt)
+                    if base is None:
+                        base = typed[tdt] = default_rows.view(tdt)
+                    view = base.as_strided((count, M) if M > 1 else (count,), (0, 1) if M > 1 else (0,), off)
+                setattr(snap.particles, name, view)
 
     def _default_rows_template(self, device):
         """All default rows of the SPH schema as ONE int32 device array (every element type of the schema is four

@@ -203,3 +203,8 @@ cdef extern from "pgsd_private.h" nogil:
     int pgsd_frame_exchange(pgsd_handle* handle)
     int pgsd_device_of(pgsd_handle* handle)
     int pgsd_device_copy(int device, void* dst, const void* src, size_t bytes)
+    int pgsd_select_domain_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
+                                  uint32_t dimensions, const double* lo, const double* hi, uint32_t* out_rows,
+                                  uint64_t* out_count)
+    int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
+                              const pgsd_field_dst* dst)
