@@ -891,8 +891,24 @@ class DevicePipeline
     struct ReadReq;
 
     public:
+    // a piece of the file and where it lands in the request's staging
+    struct ReadSpan
+        {
+        long long file_offset;
+        size_t bytes;
+        size_t stage_offset;
+        };
+
     int read_submit(long long file_offset, size_t bytes, pgsd_unpack_job job, uint64_t N, const uint32_t* rows = nullptr,
                     uint64_t src_N = 0, bool stage_only = false, std::shared_ptr<ReadReq>* out = nullptr)
+        {
+        const ReadSpan whole = {file_offset, bytes, 0};
+        return read_submit_spans(&whole, 1, bytes, job, N, rows, src_N, stage_only, out);
+        }
+
+    // `bytes` of staging filled from n_spans file ranges (a whole chunk: one span at 0; a sparse read: the touched runs)
+    int read_submit_spans(const ReadSpan* spans, size_t n_spans, size_t bytes, pgsd_unpack_job job, uint64_t N,
+                          const uint32_t* rows, uint64_t src_N, bool stage_only, std::shared_ptr<ReadReq>* out)
         {
         if (!m_ok)
             return PGSD_ERROR_NO_DEVICE;
@@ -910,21 +926,26 @@ class DevicePipeline
             job.src = m_ddev + m_dused;
             m_dused += padded;
                 {
-                TraceRange tr("pgsd:pread_direct file_off=%llu bytes=%llu", (unsigned long long)file_offset, bytes);
-                size_t got = 0;
-                while (got < bytes)
+                TraceRange tr("pgsd:pread_direct file_off=%llu bytes=%llu", (unsigned long long)spans[0].file_offset, bytes);
+                for (size_t k = 0; k < n_spans; k++)
                     {
-                    ssize_t r = io_pread(m_fd, host + got, bytes - got, file_offset + (long long)got);
-                    if (r < 0 && errno == EINTR)
-                        continue;
-                    if (r <= 0)
-                        break;
-                    got += (size_t)r;
-                    }
-                if (got != bytes)
-                    {
-                    fail("pread returned fewer bytes than the chunk holds", true);
-                    return PGSD_SUCCESS; // reported by pgsd_device_wait_read, like the threaded path
+                    const ReadSpan& sp = spans[k];
+                    size_t got = 0;
+                    while (got < sp.bytes)
+                        {
+                        ssize_t r = io_pread(m_fd, host + sp.stage_offset + got, sp.bytes - got, sp.file_offset + (long long)got);
+                        if (r < 0 && errno == EINTR)
+                            continue;
+                        if (r <= 0)
+                            break;
+                        got += (size_t)r;
+                        }
+                    m_pread_bytes += got;
+                    if (got != sp.bytes)
+                        {
+                        fail("pread returned fewer bytes than the chunk holds", true);
+                        return PGSD_SUCCESS; // reported by pgsd_device_wait_read, like the threaded path
+                        }
                     }
                 }
             auto direct_req = std::make_shared<ReadReq>();
@@ -959,26 +980,102 @@ class DevicePipeline
         auto req = std::make_shared<ReadReq>();
         req->job = job;
         req->N = N;
+        // The spans follow each other in the staging without gaps, so the pieces are cut along the STAGING: a piece of a
+        // sparse read holds many short runs, each pread into its place in the slab, and goes to HBM in one copy (a
+        // piece per run cost 17 us each; 1 000 runs of 48 KB took as long as two thirds of the whole chunk).
         req->pieces_left = (bytes + piece - 1) / piece;
         req->rows = rows;
         req->src_N = src_N;
         req->stage_only = stage_only;
+        if (out)
+            *out = req;
+        if (req->pieces_left == 0)
+            {
+            // (a sparse read none of whose rows lies in the chunk: nothing to stage, the gather still refuses them)
+            req->all_copied = nullptr;
+            if (!stage_only)
+                {
+                std::lock_guard<std::mutex> g(m_copy_mutex);
+                m_unpack_pending.push_back(req);
+                }
+            return PGSD_SUCCESS;
+            }
         req->all_copied = get_event(false);
         if (!req->all_copied)
             return PGSD_ERROR_DEVICE;
-        if (out)
-            *out = req;
         std::unique_lock<std::mutex> lk(m_mutex);
         m_reads_outstanding += req->pieces_left; // counted per piece: see read_piece()
         lk.unlock();
+        size_t k = 0;
         for (size_t off = 0; off < bytes; off += piece)
             {
-            size_t n = std::min(piece, bytes - off);
+            const size_t n = std::min(piece, bytes - off);
             char* dst = (char*)stage + off;
-            long long foff = file_offset + (long long)off;
-            writer_pool_submit(m_reader->pool, [this, req, dst, n, foff] { read_piece(req, dst, n, foff); });
+            if (n_spans == 1)
+                {
+                long long foff = spans[0].file_offset + (long long)off;
+                writer_pool_submit(m_reader->pool, [this, req, dst, n, foff] { read_piece(req, dst, n, foff, nullptr); });
+                continue;
+                }
+            // the parts of the spans that fall into [off, off + n)
+            auto parts = std::make_shared<std::vector<ReadSpan>>();
+            while (k < n_spans && spans[k].stage_offset + spans[k].bytes <= off)
+                k++;
+            for (size_t j = k; j < n_spans && spans[j].stage_offset < off + n; j++)
+                {
+                const size_t a = std::max(spans[j].stage_offset, off);
+                const size_t b = std::min(spans[j].stage_offset + spans[j].bytes, off + n);
+                if (b > a)
+                    parts->push_back({spans[j].file_offset + (long long)(a - spans[j].stage_offset), b - a, a - off});
+                }
+            writer_pool_submit(m_reader->pool, [this, req, dst, n, parts] { read_piece(req, dst, n, 0, parts); });
             }
         return PGSD_SUCCESS;
+        }
+
+    // Sparse indexed read: the touched runs of the plan are read (same reader threads, pinned ring and piece size) and
+    // land at slot * R rows of a staging of plan.staged_rows rows; wait_read's deferred launch gathers through rows2.
+    int read_planned_submit(long long chunk_offset, size_t row_bytes, pgsd_unpack_job job, const RowPlan& plan)
+        {
+        std::vector<ReadSpan> spans(plan.run_first.size());
+        uint64_t slot = 0;
+        for (size_t i = 0; i < spans.size(); i++)
+            {
+            const uint64_t row0 = (uint64_t)plan.run_first[i] * plan.R;
+            const uint64_t nrows = std::min<uint64_t>((uint64_t)plan.run_blocks[i] * plan.R, plan.N - row0);
+            spans[i] = {chunk_offset + (long long)(row0 * row_bytes), (size_t)(nrows * row_bytes),
+                        (size_t)(slot * plan.R * row_bytes)};
+            slot += plan.run_blocks[i];
+            }
+        return read_submit_spans(spans.data(), spans.size(), (size_t)(plan.staged_rows * row_bytes), job, plan.n, plan.rows2,
+                                 plan.staged_rows, false, nullptr);
+        }
+
+    // Row plan: mark / scan / remap on the pack stream, behind what the caller's stream still does with the row list.
+    int plan_rows(RowPlan& plan, std::string* err)
+        {
+        if (!m_ok)
+            return PGSD_ERROR_NO_DEVICE;
+        if (failed())
+            return PGSD_ERROR_DEVICE;
+        HIP_TRY(hipSetDevice(m_cfg.device));
+        hipEvent_t ready = get_event(false);
+        if (!ready)
+            return PGSD_ERROR_DEVICE;
+        HIP_TRY(hipEventRecord(ready, m_source_stream));
+        HIP_TRY(hipStreamWaitEvent(m_pack_stream, ready, 0));
+        int rc = launch_row_plan(plan, m_pack_stream, err);
+        if (rc == PGSD_ERROR_DEVICE && err)
+            fail(*err);
+        return rc;
+        }
+
+    void read_counters(uint64_t* pread_bytes, uint64_t* h2d_bytes, int reset)
+        {
+        if (pread_bytes)
+            *pread_bytes = reset ? m_pread_bytes.exchange(0) : m_pread_bytes.load();
+        if (h2d_bytes)
+            *h2d_bytes = reset ? m_h2d_bytes.exchange(0) : m_h2d_bytes.load();
         }
 
     // Indexed read: the whole chunk is staged as for a slab read -- or, when it is the position chunk the last
@@ -1683,7 +1780,10 @@ class DevicePipeline
             }
         }
 
-    void read_piece(std::shared_ptr<ReadReq> req, char* dst, size_t n, long long foff)
+    // one piece of a request's staging: `n` bytes from `foff`, or -- `parts` -- from several file ranges, each at its
+    // stage_offset within the piece
+    void read_piece(std::shared_ptr<ReadReq> req, char* dst, size_t n, long long foff,
+                    std::shared_ptr<std::vector<ReadSpan>> parts)
         {
         (void)hipSetDevice(m_cfg.device);
         ReadEngine* const reader = m_reader; // the engine may outlive this pipeline, not the other way round
@@ -1695,17 +1795,27 @@ class DevicePipeline
             ReadEngine::Slab& s = reader->slabs[(size_t)si];
             // pread in one go; a short read means the file is shorter than its index claims
             TraceRange tr("pgsd:pread file_off=%llu bytes=%llu", (unsigned long long)foff, n);
-            size_t got = 0;
-            while (got < n)
+            const ReadSpan single = {foff, n, 0};
+            const ReadSpan* sp = parts ? parts->data() : &single;
+            const size_t n_sp = parts ? parts->size() : 1;
+            size_t got = 0, want = 0;
+            for (size_t q = 0; q < n_sp && got == want; q++)
                 {
-                ssize_t r = io_pread(m_fd, s.host + got, n - got, foff + (long long)got);
-                if (r < 0 && errno == EINTR)
-                    continue;
-                if (r <= 0)
-                    break;
-                got += (size_t)r;
+                want += sp[q].bytes;
+                size_t g = 0;
+                while (g < sp[q].bytes)
+                    {
+                    ssize_t r = io_pread(m_fd, s.host + sp[q].stage_offset + g, sp[q].bytes - g, sp[q].file_offset + (long long)g);
+                    if (r < 0 && errno == EINTR)
+                        continue;
+                    if (r <= 0)
+                        break;
+                    g += (size_t)r;
+                    }
+                got += g;
                 }
-            if (got != n)
+            m_pread_bytes += got;
+            if (got != want || want != n)
                 {
                 fail("pread returned fewer bytes than the chunk holds", true);
                 ok = false;
@@ -1717,6 +1827,7 @@ class DevicePipeline
                 {
                 ReadEngine::Slab& s = reader->slabs[(size_t)si];
                 m_copy_used.store(true);
+                m_h2d_bytes += n;
                 hipError_t e = hipMemcpyAsync(dst, s.host, n, hipMemcpyHostToDevice, m_copy_stream);
                 if (e == hipSuccess)
                     e = hipEventRecord(s.copied, m_copy_stream);
@@ -1820,6 +1931,8 @@ class DevicePipeline
     uint32_t* m_cmp_host_dev = nullptr;
     uint32_t* m_cmp_dev = nullptr;
     uint32_t m_cmp_gen = 0;
+    std::atomic<uint64_t> m_pread_bytes {0}; // read side: file bytes pread / bytes copied host-to-device (read_counters)
+    std::atomic<uint64_t> m_h2d_bytes {0};
     uint32_t* m_bad_host = nullptr;        // indexed reads: set by a gather that met a row outside its chunk (pinned)
     uint32_t* m_bad_dev = nullptr;         // ... its device alias
     const void* m_kept_src = nullptr;      // select_domain(): the staged position rows, kept until the next wait_read
@@ -1970,6 +2083,29 @@ int device_pipeline_read_rows(DevicePipeline* p, long long file_offset, size_t b
     if (rc != PGSD_SUCCESS && err)
         *err = p->error();
     return rc;
+    }
+
+int device_pipeline_plan_rows(DevicePipeline* p, RowPlan& plan, std::string* err)
+    {
+    std::string local;
+    int rc = p->plan_rows(plan, &local);
+    if (rc != PGSD_SUCCESS && err)
+        *err = !local.empty() ? local : p->error().empty() ? std::string(last_error()) : p->error();
+    return rc;
+    }
+
+int device_pipeline_read_planned(DevicePipeline* p, long long chunk_offset, size_t row_bytes, const pgsd_unpack_job& job,
+                                 const RowPlan& plan, std::string* err)
+    {
+    int rc = p->read_planned_submit(chunk_offset, row_bytes, job, plan);
+    if (rc != PGSD_SUCCESS && err)
+        *err = p->error();
+    return rc;
+    }
+
+void device_pipeline_read_counters(DevicePipeline* p, uint64_t* pread_bytes, uint64_t* h2d_bytes, int reset)
+    {
+    p->read_counters(pread_bytes, h2d_bytes, reset);
     }
 
 int device_pipeline_select_domain(DevicePipeline* p, long long file_offset, size_t bytes, const DomainArgs& d,

@@ -163,6 +163,29 @@ int device_pipeline_read_rows(DevicePipeline*, long long file_offset, size_t byt
 // out_rows (device), the count into *out_count; synchronous.  The staged rows stay until the next wait_read.
 int device_pipeline_select_domain(DevicePipeline*, long long file_offset, size_t bytes, const DomainArgs& d,
                                   uint32_t* out_rows, uint64_t* out_count, std::string* err);
+// A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
+// least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
+// into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose
+// height is staged_rows (T * R, less where the chunk's short last block is touched).  An entry >= N touches nothing
+// and becomes 0xFFFFFFFF.  rows and rows2 are device memory of the caller's.
+struct RowPlan
+    {
+    uint64_t n = 0, N = 0;
+    uint32_t R = 0;
+    uint64_t staged_rows = 0;
+    const uint32_t* rows = nullptr;
+    uint32_t* rows2 = nullptr;
+    std::vector<uint32_t> blocks, run_first, run_blocks;
+    };
+// fill in a plan (n, N, rows, rows2 set by the caller; R == 0: the tuning variable PGSD_PLAN_BLOCK_ROWS) on the GPU;
+// synchronous
+int device_pipeline_plan_rows(DevicePipeline*, RowPlan& plan, std::string* err);
+// sparse indexed read: only the plan's runs of the chunk at `chunk_offset` (plan.N rows of row_bytes each) are read and
+// staged, block b at slot(b) * R rows; wait_read gathers through plan.rows2.  The plan outlives the wait.
+int device_pipeline_read_planned(DevicePipeline*, long long chunk_offset, size_t row_bytes, const pgsd_unpack_job& job,
+                                 const RowPlan& plan, std::string* err);
+// file bytes the read side has pread and bytes it has copied host-to-device since creation / the last reset
+void device_pipeline_read_counters(DevicePipeline*, uint64_t* pread_bytes, uint64_t* h2d_bytes, int reset);
 int device_pipeline_drain(DevicePipeline*, std::string* err);
 void device_pipeline_stats(DevicePipeline*, pgsd_device_stats* out, int reset);
 

@@ -241,6 +241,7 @@ struct PackTuning
     uint32_t unpack_tile_cap = 0;         // PGSD_UNPACK_TILE (0: by size)
     uint64_t unpack_per_cu = 8;           // PGSD_UNPACK_BLOCKS_PER_CU
     bool unpack_tiles = false;            // PGSD_UNPACK_KERNEL=tiles
+    uint32_t plan_block_rows = 256;       // PGSD_PLAN_BLOCK_ROWS: rows per block of a row plan (profiles/r07_read_tracks_bench.jsonl)
     };
 
 PackTuning tuning();

@@ -641,6 +641,8 @@ static PackTuning read_tuning()
         t.unpack_per_cu = (uint64_t)atoi(e) > 0 ? (uint64_t)atoi(e) : t.unpack_per_cu;
     if (const char* e = getenv("PGSD_UNPACK_KERNEL"))
         t.unpack_tiles = strcmp(e, "tiles") == 0;
+    if (const char* e = getenv("PGSD_PLAN_BLOCK_ROWS"))
+        t.plan_block_rows = atoll(e) > 0 && atoll(e) <= (1 << 24) ? (uint32_t)atoll(e) : t.plan_block_rows;
     return t;
     }
 

@@ -234,6 +234,10 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
 // synchronises `stream` and leaves the count in *out_count (host)
 int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err);
 
+// mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
+// host side (touched blocks, runs, staged_rows) and rows2 (device)
+int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);
+
 // Enqueue the pack of `n_jobs` fields of N rows each on `stream`. Returns a pgsd_error.
 // ev_start / ev_stop (optional) receive the begin time of the first and the end time of the last kernel.
 int launch_pack(uint32_t n_jobs, const pgsd_pack_job* jobs, uint64_t N, hipStream_t stream, std::string* err,

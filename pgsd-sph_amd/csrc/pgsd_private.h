@@ -14,6 +14,10 @@
  *   restart helpers   pgsd_select_domain_device, pgsd_read_rows_device (pgsd.fl's select_domain_device and
  *                     read_chunk_device(rows=...), behind pgsd.hoomd's read_frame_device(domain=...): a rank of a
  *                     domain-decomposed run reads its own particles; the public header has no room for them)
+ *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
+ *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
+ *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
+ *                     reading only the file blocks their rows touch)
  */
 #ifndef PGSD_PRIVATE_H
 #define PGSD_PRIVATE_H
@@ -101,6 +105,35 @@ extern "C"
        rows or more are refused. */
     int pgsd_read_rows_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk, const uint32_t* rows,
                               uint64_t n, const struct pgsd_field_dst* dst);
+
+    /* A row plan for sparse indexed reads of chunks of N rows: the rows are cut into blocks of R rows (the tuning
+       variable PGSD_PLAN_BLOCK_ROWS, read once), the blocks that hold at least one of rows[0 .. n) are the touched blocks
+       (ascending; a block's position in that list is its slot in the compact staging), neighbours merge into runs, and
+       rows2[k] = slot(rows[k] / R) * R + rows[k] % R indexes the staging.  rows need not be ascending and may repeat; an
+       entry >= N touches nothing and becomes 0xFFFFFFFF.  rows and rows2 (n entries each) are device memory of the
+       caller's and must outlive the plan; the plan is computed on the handle's GPU and the call synchronises.  One plan
+       serves every chunk of N rows, whatever its row size, in every frame.  Requires N + R < 2^32. */
+    struct pgsd_row_plan;
+    int pgsd_row_plan_create(struct pgsd_handle* handle, const uint32_t* rows, uint64_t n, uint64_t N, uint32_t* rows2,
+                             struct pgsd_row_plan** out);
+    void pgsd_row_plan_destroy(struct pgsd_row_plan* plan);
+    /* counts: n, N, R, T (touched blocks), runs (of adjacent touched blocks), staged_rows (the height of the compact
+       staging: T * R, less where the short last block is touched).  lists: rows, rows2 (device, n entries), blocks
+       (host, T entries), run_first and run_blocks (host, runs entries: first block and number of blocks of each run);
+       valid until the plan is destroyed. */
+    int pgsd_row_plan_query(const struct pgsd_row_plan* plan, uint64_t counts[6], const uint32_t* lists[5]);
+
+    /* pgsd_read_rows_device through a plan: only the plan's runs of the chunk are read from the file and staged (the HBM
+       staging holds the touched blocks, not the chunk), and the gather at pgsd_device_wait_read indexes them with rows2.
+       dst row k takes chunk row rows[k], k < n; an entry >= N fails the wait exactly as it does there.  A chunk whose N
+       is not the plan's is refused with PGSD_ERROR_INVALID_ARGUMENT.  The plan must outlive the wait. */
+    int pgsd_read_rows_planned_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk,
+                                      const struct pgsd_row_plan* plan, const struct pgsd_field_dst* dst);
+
+    /* File bytes the device read path of this handle has pread, and bytes it has copied host-to-device, since the
+       pipeline was created or the counters were last reset (small reads through the pinned, device-mapped arena copy
+       nothing).  Kept apart from pgsd_device_stats, whose layout is fixed. */
+    int pgsd_device_read_counters(struct pgsd_handle* handle, uint64_t* pread_bytes, uint64_t* h2d_bytes, int reset);
 
 #ifdef __cplusplus
     }

@@ -431,3 +431,117 @@ catch (...)
     {
         return pgsd_amd::abi_guard();
     }
+
+struct pgsd_row_plan
+    {
+    pgsd_amd::RowPlan p;
+    };
+
+extern "C" int pgsd_row_plan_create(struct pgsd_handle* handle, const uint32_t* rows, uint64_t n, uint64_t N, uint32_t* rows2,
+                                    struct pgsd_row_plan** out)
+    try
+    {
+    Impl* s = impl_of(handle);
+    if (!s || !out || (n > 0 && (!rows || !rows2)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    *out = nullptr;
+    int rc = ensure_device(s);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    std::unique_ptr<pgsd_row_plan> plan(new pgsd_row_plan);
+    plan->p.n = n;
+    plan->p.N = N;
+    plan->p.rows = rows;
+    plan->p.rows2 = rows2;
+    std::string err;
+    rc = device_pipeline_plan_rows(s->dev, plan->p, &err);
+    if (rc != PGSD_SUCCESS)
+        {
+        set_last_error(err);
+        return rc;
+        }
+    *out = plan.release();
+    return PGSD_SUCCESS;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" void pgsd_row_plan_destroy(struct pgsd_row_plan* plan)
+    {
+    delete plan;
+    }
+
+extern "C" int pgsd_row_plan_query(const struct pgsd_row_plan* plan, uint64_t counts[6], const uint32_t* lists[5])
+    {
+    if (!plan || !counts || !lists)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const pgsd_amd::RowPlan& p = plan->p;
+    counts[0] = p.n;
+    counts[1] = p.N;
+    counts[2] = p.R;
+    counts[3] = p.blocks.size();
+    counts[4] = p.run_first.size();
+    counts[5] = p.staged_rows;
+    lists[0] = p.rows;
+    lists[1] = p.rows2;
+    lists[2] = p.blocks.data();
+    lists[3] = p.run_first.data();
+    lists[4] = p.run_blocks.data();
+    return PGSD_SUCCESS;
+    }
+
+extern "C" int pgsd_read_rows_planned_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk,
+                                             const struct pgsd_row_plan* plan, const struct pgsd_field_dst* dst)
+    try
+    {
+    Impl* s = impl_of(handle);
+    if (!s || !chunk || !plan || !dst || dst->order)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    if (chunk->N != plan->p.N)
+        {
+        set_last_error("pgsd_read_rows_planned_device: the plan was made for chunks of another N");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    if (plan->p.n == 0)
+        return PGSD_SUCCESS; // (an empty destination may have no address)
+    if (!dst->dst)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    pgsd_index_entry c = *chunk; // a flush may move the index storage
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (c.N == 0)
+        return PGSD_ERROR_INVALID_ARGUMENT; // (rows of an empty chunk: read_rows refuses n > N as well)
+    pgsd_unpack_job job;
+    memset(&job, 0, sizeof(job));
+    job.src_type = c.type;
+    job.M = c.M;
+    job.dst = *dst;
+    std::string err;
+    rc = device_pipeline_read_planned(s->dev, foff, (size_t)c.M * sizeof_type(c.type), job, plan->p, &err);
+    if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_device_read_counters(struct pgsd_handle* handle, uint64_t* pread_bytes, uint64_t* h2d_bytes, int reset)
+    {
+    Impl* s = impl_of(handle);
+    if (!s)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    if (pread_bytes)
+        *pread_bytes = 0;
+    if (h2d_bytes)
+        *h2d_bytes = 0;
+    if (s->dev)
+        device_pipeline_read_counters(s->dev, pread_bytes, h2d_bytes, reset);
+    return PGSD_SUCCESS;
+    }

@@ -493,6 +493,39 @@ __global__ __launch_bounds__(SEL_THREADS) void domain_scatter_kernel(const Domai
     for (uint32_t e = head + 4 * nvec + threadIdx.x; e < n; e += SEL_THREADS)
         out[e] = local[e];
     }
+
+// ------------------------------------------------------------------ row plan (sparse indexed reads)
+// The chunk's N rows are cut into blocks of R rows.  mark: lane per entry, touched[rows[k] / R] = 1 (a plain vector
+// store: lanes racing on one word all store the same value); scan: the one-block scan above over the ceil(N / R) flags
+// gives block b's slot in the compact staging and T, the number of touched blocks; remap: rows2[k] = slot * R + rows[k] % R.
+// An entry >= N marks nothing and becomes 0xFFFFFFFF, which the gather's bounds check refuses.  Grid-stride, 4 bytes per
+// entry in and out: nothing to tune here next to the file reads the plan saves.
+__global__ __launch_bounds__(SEL_THREADS) void plan_mark_kernel(const uint32_t* rows, uint64_t n, uint64_t N, uint32_t R,
+                                                                uint32_t* touched)
+    {
+    for (uint64_t k = (uint64_t)blockIdx.x * SEL_THREADS + threadIdx.x; k < n; k += (uint64_t)gridDim.x * SEL_THREADS)
+        {
+        const uint32_t r = rows[k];
+        if (r < N)
+            touched[r / R] = 1u;
+        }
+    }
+
+__global__ __launch_bounds__(SEL_THREADS) void plan_remap_kernel(const uint32_t* rows, uint64_t n, uint64_t N, uint32_t R,
+                                                                 const uint64_t* slot, uint32_t* rows2)
+    {
+    for (uint64_t k = (uint64_t)blockIdx.x * SEL_THREADS + threadIdx.x; k < n; k += (uint64_t)gridDim.x * SEL_THREADS)
+        {
+        const uint32_t r = rows[k];
+        uint32_t v = 0xFFFFFFFFu;
+        if (r < N)
+            {
+            const uint32_t b = r / R;
+            v = (uint32_t)slot[b] * R + (r - b * R);
+            }
+        rows2[k] = v;
+        }
+    }
     } // namespace pgsd_amd
 
 using namespace pgsd_amd;
@@ -511,10 +544,10 @@ std::map<int, SelectScratch> g_select_scratch;
 
 // the scratch space of a compaction of N rows on `device` (current; g_select_lock held): the count (u64), the block counts
 // (u32) rounded to 8 bytes, the block offsets (u64); and the pinned word the scan leaves the count in
-int select_scratch(int device, uint64_t N, SelectScratch** out)
+int select_scratch(int device, uint64_t N, SelectScratch** out, uint64_t per_block = SEL_PER_BLOCK)
     {
     SelectScratch& sc = g_select_scratch[device];
-    const uint64_t nb = (N + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
+    const uint64_t nb = (N + per_block - 1) / per_block;
     const size_t need = 8 + (size_t)(((nb * 4 + 7) & ~7ull) + nb * 8);
     if (need > sc.cap)
         {
@@ -597,6 +630,94 @@ int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_
         return PGSD_ERROR_DEVICE;
         }
     *out_count = __atomic_load_n(sc->host_count, __ATOMIC_ACQUIRE);
+    return PGSD_SUCCESS;
+    }
+
+int launch_row_plan(RowPlan& p, hipStream_t stream, std::string* err)
+    {
+    if (p.R == 0)
+        p.R = tuning().plan_block_rows;
+    p.blocks.clear();
+    p.run_first.clear();
+    p.run_blocks.clear();
+    p.staged_rows = 0;
+    // (rows2 = slot * R + rest stays below T * R <= N + R, which must stay clear of the 0xFFFFFFFF of a refused entry)
+    if (p.N + p.R >= (1ull << 32) || (p.n > 0 && (!p.rows || !p.rows2)))
+        {
+        if (err)
+            *err = "row plan: no row list, or the chunk's rows do not fit 32-bit indices";
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    if (p.n == 0 || p.N == 0)
+        {
+        // nothing can be touched; every entry (all of them >= N) is refused
+        if (p.n > 0 && hipMemsetAsync(p.rows2, 0xFF, p.n * 4, stream) != hipSuccess)
+            return PGSD_ERROR_DEVICE;
+        return p.n > 0 && hipStreamSynchronize(stream) != hipSuccess ? PGSD_ERROR_DEVICE : PGSD_SUCCESS;
+        }
+    std::lock_guard<std::mutex> guard(g_select_lock);
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess)
+        return PGSD_ERROR_DEVICE;
+    SelectScratch* sc = nullptr;
+    int rc = select_scratch(device, p.N, &sc, p.R);
+    if (rc != PGSD_SUCCESS)
+        {
+        if (err)
+            *err = last_error();
+        return rc;
+        }
+    (void)hipGetLastError(); // (see pgsd_select_rows)
+    const uint64_t nb = (p.N + p.R - 1) / p.R;
+    uint32_t* touched = (uint32_t*)((char*)sc->dev + 8);
+    uint64_t* slot = (uint64_t*)((char*)sc->dev + 8 + ((nb * 4 + 7) & ~7ull));
+    const unsigned grid = (unsigned)std::min<uint64_t>((p.n + SEL_THREADS - 1) / SEL_THREADS, (uint64_t)num_cus() * 8);
+    std::vector<uint32_t> flags(nb);
+    hipError_t e = hipMemsetAsync(touched, 0, nb * 4, stream);
+    if (e == hipSuccess)
+        {
+        hipLaunchKernelGGL(plan_mark_kernel, dim3(grid), dim3(SEL_THREADS), 0, stream, p.rows, p.n, p.N, p.R, touched);
+        hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(SEL_THREADS), 0, stream, touched, (uint32_t)nb, slot,
+                           (uint64_t*)sc->dev, sc->host_count_dev);
+        hipLaunchKernelGGL(plan_remap_kernel, dim3(grid), dim3(SEL_THREADS), 0, stream, p.rows, p.n, p.N, p.R, slot, p.rows2);
+        e = hipGetLastError();
+        }
+    // the touched flags go back to the host (4 bytes per block: 78 KB at 80 M rows and R = 4096)
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(flags.data(), touched, nb * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(stream);
+    if (e != hipSuccess)
+        {
+        if (err)
+            *err = std::string("row plan: ") + hipGetErrorString(e);
+        return PGSD_ERROR_DEVICE;
+        }
+    const uint64_t T = __atomic_load_n(sc->host_count, __ATOMIC_ACQUIRE);
+    p.blocks.reserve(T);
+    for (uint64_t b = 0; b < nb; b++)
+        {
+        if (!flags[b])
+            continue;
+        if (!p.blocks.empty() && p.blocks.back() + 1 == b)
+            p.run_blocks.back()++;
+        else
+            {
+            p.run_first.push_back((uint32_t)b);
+            p.run_blocks.push_back(1);
+            }
+        p.blocks.push_back((uint32_t)b);
+        }
+    if (p.blocks.size() != T)
+        {
+        if (err)
+            *err = "row plan: the scan's count and the touched flags disagree";
+        return PGSD_ERROR_DEVICE;
+        }
+    // a short last block has the highest slot: it shortens the staging and leaves no hole in it
+    p.staged_rows = T * p.R;
+    if (T > 0 && p.blocks.back() == nb - 1)
+        p.staged_rows -= nb * p.R - p.N;
     return PGSD_SUCCESS;
     }
     } // namespace pgsd_amd

@@ -10,6 +10,7 @@ same method accepts **device-resident** data (a torch tensor on the GPU or a :cl
 is packed by the HIP kernels and streamed to the file without a host copy in Python;
 :meth:`PGSDFile.write_chunks` packs several per-particle chunks with one fused launch.
 """
+import collections
 import ctypes
 import errno as _errno
 import logging
@@ -452,6 +453,24 @@ def _device_memory(x, what="array"):
     return (int(iface['data'][0]) if n > 0 else 0), n * dt.itemsize
 
 
+def _device_to_host(x):
+    """A host copy (numpy) of a dense array in GPU memory, typed and shaped like it (no tensor library needed)."""
+    if isinstance(x, DeviceBuffer):
+        return x.to_host()
+    if _is_device_tensor(x):
+        return x.detach().cpu().numpy()
+    iface = x.__cuda_array_interface__
+    out = numpy.empty(tuple(int(v) for v in iface['shape']), dtype=numpy.dtype(iface['typestr']))
+    cdef uintptr_t s = _device_memory(x)[0], d = out.ctypes.data
+    cdef size_t n = out.nbytes
+    cdef int rc
+    if n:
+        with nogil:
+            rc = C.pgsd_device_copy(-1, <void*>d, <const void*>s, n)
+        _raise_on_error(rc, "device to host copy")
+    return out
+
+
 def select_rows(flags):
     """Stream compaction on the GPU for filtered snapshots.
 
@@ -497,6 +516,144 @@ def select_rows(flags):
     if isinstance(index, DeviceBuffer):
         return index.view(shape=(int(k),)), int(k)
     return index[:int(k)], int(k)
+
+
+RowPlanModel = collections.namedtuple('RowPlanModel', ['blocks', 'runs', 'rows2', 'staged_rows'])
+
+# A plan takes the sparse route while its touched fraction T * R / N is at most this (PGSD_PLAN_SPARSE_MAX, read once).
+# Measured (profiles/r07_read_tracks_bench.jsonl, sweep_f): the sparse route is ahead of the whole-chunk route up to a
+# touched fraction of 0.9 and level with it, inside the repeats' spread, at 1.0.
+_PLAN_SPARSE_MAX = float(os.environ.get('PGSD_PLAN_SPARSE_MAX', '0.9'))
+
+
+def row_plan_model(rows, N, block_rows):
+    """The numpy model of a row plan (:meth:`PGSDFile.plan_rows` computes exactly this on the GPU).
+
+    A chunk's ``N`` rows are cut into blocks of ``block_rows`` rows.  Returns a ``RowPlanModel``:
+
+    * ``blocks``: the ascending blocks that hold at least one entry of ``rows`` (uint32); block ``blocks[s]`` has slot
+      ``s`` in the compact staging, which is the touched blocks in file order;
+    * ``runs``: ``(n_runs, 2)`` uint32 rows ``(first block, number of blocks)`` of adjacent touched blocks -- the
+      pieces of the file a sparse read fetches;
+    * ``rows2``: ``slot(rows[k] // R) * R + rows[k] % R`` (uint32), the index of row ``rows[k]`` in that staging;
+    * ``staged_rows``: the staging's height, ``T * R`` less what a touched short last block lacks.
+
+    ``rows`` need not be ascending and may repeat; an entry ``>= N`` touches nothing and becomes ``0xFFFFFFFF``.
+    """
+    R, N = int(block_rows), int(N)
+    if R < 1 or N < 0 or N + R >= 1 << 32:
+        raise ValueError("row_plan_model: block_rows >= 1 and N + block_rows < 2^32")
+    rows = numpy.ascontiguousarray(rows).reshape(-1).astype(numpy.int64, copy=False)
+    if rows.size and rows.min() < 0:
+        rows = rows & 0xFFFFFFFF            # int32 bit patterns of uint32 entries
+    ok = rows < N
+    b = rows[ok] // R
+    blocks = numpy.unique(b)
+    rows2 = numpy.full(rows.shape, 0xFFFFFFFF, dtype=numpy.uint32)
+    rows2[ok] = (numpy.searchsorted(blocks, b) * R + rows[ok] % R).astype(numpy.uint32)
+    if blocks.size:
+        starts = numpy.flatnonzero(numpy.concatenate(([True], numpy.diff(blocks) != 1)))
+        counts = numpy.diff(numpy.concatenate((starts, [blocks.size])))
+        runs = numpy.stack((blocks[starts], counts), axis=1).astype(numpy.uint32)
+    else:
+        runs = numpy.zeros((0, 2), dtype=numpy.uint32)
+    nb = (N + R - 1) // R
+    staged = int(blocks.size) * R
+    if blocks.size and int(blocks[-1]) == nb - 1:
+        staged -= nb * R - N
+    return RowPlanModel(blocks.astype(numpy.uint32), runs, rows2, staged)
+
+
+cdef class RowPlan:
+    """A plan for sparse indexed reads (:meth:`PGSDFile.plan_rows`): which blocks of ``block_rows`` rows the entries of
+    ``rows`` touch, merged into runs, and ``rows2``, the entries' positions in a compact staging of those blocks.  One
+    plan serves every chunk of ``N`` rows of the file it was made on, in every frame.  Pass it as
+    ``read_chunk_device(..., rows=plan)``.
+
+    Attributes:
+        n (int): entries.  N (int): rows of the chunks the plan is for.  block_rows (int): R.
+        touched_blocks (int): T.  runs (int): number of runs of adjacent touched blocks.
+        rows: the caller's index list (kept alive).  rows2 (`DeviceBuffer`): uint32, ``n`` entries.
+        threshold (float): the plan takes the sparse route while ``touched_fraction <= threshold``.
+    """
+    cdef C.pgsd_row_plan* _plan
+    cdef public object rows, rows2, file
+    cdef public double threshold
+
+    def __cinit__(self):
+        self._plan = NULL
+
+    def __dealloc__(self):
+        if self._plan != NULL:
+            C.pgsd_row_plan_destroy(self._plan)
+            self._plan = NULL
+
+    cdef uint64_t _count(self, int i):
+        cdef uint64_t counts[6]
+        cdef const uint32_t* lists[5]
+        memset(counts, 0, sizeof(counts))
+        C.pgsd_row_plan_query(self._plan, counts, lists)
+        return counts[i]
+
+    @property
+    def n(self):
+        return int(self._count(0))
+
+    @property
+    def N(self):
+        return int(self._count(1))
+
+    @property
+    def block_rows(self):
+        return int(self._count(2))
+
+    @property
+    def touched_blocks(self):
+        return int(self._count(3))
+
+    @property
+    def runs(self):
+        return int(self._count(4))
+
+    @property
+    def staged_rows(self):
+        return int(self._count(5))
+
+    @property
+    def touched_fraction(self):
+        """``T * R / N`` (at most 1; 0 for an empty chunk): the share of a chunk the sparse route reads."""
+        N = self.N
+        return min(1.0, float(self.touched_blocks * self.block_rows) / float(N)) if N else 0.0
+
+    @property
+    def sparse(self):
+        """Whether a read through this plan takes the sparse route."""
+        return self.touched_fraction <= self.threshold
+
+    def blocks(self):
+        """The touched blocks (host, uint32, ascending)."""
+        cdef uint64_t counts[6]
+        cdef const uint32_t* lists[5]
+        C.pgsd_row_plan_query(self._plan, counts, lists)
+        out = numpy.empty((int(counts[3]),), dtype=numpy.uint32)
+        cdef uint32_t[::1] v = out
+        cdef uint64_t i
+        for i in range(counts[3]):
+            v[i] = lists[2][i]
+        return out
+
+    def run_list(self):
+        """``(runs, 2)`` uint32: first block and number of blocks of every run."""
+        cdef uint64_t counts[6]
+        cdef const uint32_t* lists[5]
+        C.pgsd_row_plan_query(self._plan, counts, lists)
+        out = numpy.empty((int(counts[4]), 2), dtype=numpy.uint32)
+        cdef uint32_t[:, ::1] v = out
+        cdef uint64_t i
+        for i in range(counts[4]):
+            v[i, 0] = lists[3][i]
+            v[i, 1] = lists[4][i]
+        return out
 
 
 def open(name, mode, application=None, schema=None, schema_version=None, comm=None):
@@ -1179,6 +1336,52 @@ cdef class PGSDFile:
                 "pack_bytes_out": st.pack_bytes_out, "pack_bytes_in": st.pack_bytes_in, "d2h_bytes": st.d2h_bytes,
                 "written_bytes": st.written_bytes, "d2h_ms": st.d2h_ms, "write_ms": st.write_ms}
 
+    def device_read_stats(self, reset=False):
+        """dict: file bytes the device read path has ``pread`` (``pread_bytes``) and bytes it has copied host-to-device
+        (``h2d_bytes``) since the pipeline was created or the counters were last reset.  Small reads go through a
+        pinned, device-mapped arena and copy nothing."""
+        cdef uint64_t a = 0, b = 0
+        self._check_open()
+        _raise_on_error(C.pgsd_device_read_counters(&self._handle, &a, &b, 1 if reset else 0), self._name)
+        return {"pread_bytes": int(a), "h2d_bytes": int(b)}
+
+    def plan_rows(self, rows, N, threshold=None):
+        """Plan sparse indexed reads of ``rows`` from chunks of ``N`` rows (computed on the GPU; see :class:`RowPlan` and
+        :func:`row_plan_model`, which it equals exactly).
+
+        Args:
+            rows: 32-bit row indices in GPU memory (torch GPU tensor, :class:`DeviceBuffer` or
+                ``__cuda_array_interface__``), in any order, repeats allowed.
+            N (int): the row count of the chunks the plan will be used on.
+            threshold (float): touched fraction up to which reads through the plan take the sparse route
+                (default: ``PGSD_PLAN_SPARSE_MAX``).
+        """
+        self._check_open()
+        es = rows.element_size() if hasattr(rows, 'element_size') else \
+            numpy.dtype(rows.__cuda_array_interface__['typestr']).itemsize
+        if es != 4:
+            raise ValueError("rows must hold 32-bit row indices")
+        p_rows, rows_bytes = _device_memory(rows, "rows")
+        n = rows_bytes // 4
+        cdef RowPlan plan = RowPlan.__new__(RowPlan)
+        plan.rows = rows
+        plan.rows2 = DeviceBuffer((max(n, 1),), numpy.uint32, self.pipeline_device()).view(shape=(n,))
+        plan.file = self
+        plan.threshold = _PLAN_SPARSE_MAX if threshold is None else float(threshold)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the plan is ordered behind this stream's use of `rows`
+        cdef uintptr_t c_rows = p_rows, c_rows2 = plan.rows2.ptr
+        cdef uint64_t c_n = n, c_N = int(N)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_row_plan_create(&self._handle, <const uint32_t*>c_rows, c_n, c_N, <uint32_t*>c_rows2, &plan._plan)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("plan_rows: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else ""))
+        _raise_on_error(retval, self._name, err)
+        return plan
+
     # ------------------------------------------------------------------ reading
     cdef const C.pgsd_index_entry* _find(self, frame, name) except? NULL:
         name_b = name.encode('utf-8')
@@ -1333,7 +1536,8 @@ cdef class PGSDFile:
             fill: value for the columns of ``out``'s rows that no chunk read before the same :meth:`wait_read`
                 writes (``pgsd_field_dst.fill_rest``): velocity into a ``Scalar4`` array with ``fill=1.0`` gives
                 ``(vx, vy, vz, 1.0)`` rows, stored whole.  ``None``: those columns keep what they hold.
-            rows: an indexed read -- ascending int32 row indices in GPU memory (e.g. from :func:`select_rows` or
+            rows: an indexed read -- a :class:`RowPlan` (:meth:`plan_rows`: only the file blocks its rows touch are
+                read while they are few, see there), or ascending int32 row indices in GPU memory (e.g. from :func:`select_rows` or
                 :meth:`select_domain_device`); row ``k`` of ``out`` takes chunk row ``rows[k]``.  ``N`` defaults to
                 ``len(rows)``, ``offset`` must be 0 and ``order`` ``None``.  The whole chunk is staged and gathered
                 at :meth:`wait_read`, which raises if an entry lies outside the chunk.
@@ -1351,8 +1555,24 @@ cdef class PGSDFile:
         if etype not in _PGSD_TO_NP:
             raise ValueError("invalid type for chunk: " + name)
         cdef uintptr_t p_rows = 0
+        cdef RowPlan plan = None
+        if isinstance(rows, RowPlan):
+            # a plan: the sparse route while few blocks are touched, today's whole-chunk route with its rows otherwise
+            plan = rows
+            if plan.N != eN:
+                raise ValueError("the plan was made for chunks of %d rows, %s has %d" % (plan.N, name, eN))
+            if N is not None and int(N) != plan.n:
+                raise ValueError("a read through a plan takes all of its rows")
+            rows = plan.rows
+            if plan.sparse:
+                N = plan.n
+            else:
+                plan = None
         index_rows = rows                   # (`rows` is reused below for the destination's height)
-        if index_rows is not None:
+        if plan is not None:
+            if order is not None or int(offset) != 0:
+                raise ValueError("an indexed read (rows=) takes neither order nor offset")
+        elif index_rows is not None:
             if order is not None or int(offset) != 0:
                 raise ValueError("an indexed read (rows=) takes neither order nor offset")
             es = index_rows.element_size() if hasattr(index_rows, 'element_size') else \
@@ -1431,12 +1651,16 @@ cdef class PGSDFile:
             np_out = numpy.dtype(str(out_dtype)[6:]) if str(out_dtype).startswith('torch.') else numpy.dtype(out_dtype)
             dst.fill_rest = 1
             dst.fill_bits = int(numpy.array([fill], dtype=np_out).view(numpy.dtype('u%d' % np_out.itemsize))[0])
-        self._keepalive.append((out, order, index_rows))
+        self._keepalive.append((out, order, index_rows, plan))
         if not self._explicit_stream:
             self._sync_source_stream()      # the unpack is ordered behind this stream's use of `out`
         cdef uint64_t c_N = N, c_off = int(offset)
         cdef int retval, err
-        if index_rows is not None:
+        if plan is not None:
+            with nogil:
+                retval = C.pgsd_read_rows_planned_device(&self._handle, &entry, plan._plan, &dst)
+                err = errno
+        elif index_rows is not None:
             with nogil:
                 retval = C.pgsd_read_rows_device(&self._handle, &entry, <const uint32_t*>p_rows, c_N, &dst)
                 err = errno

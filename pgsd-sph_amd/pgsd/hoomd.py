@@ -384,6 +384,24 @@ def domain_rows(position, box, domain, dimensions=3):
     return numpy.flatnonzero(inside)
 
 
+class Tracks(object):
+    """What `HOOMDTrajectory.read_tracks` / `read_tracks_device` return: ``step`` (host, uint64, one entry per frame),
+    ``rows`` (the K rows followed) and one ``F x K (x M)`` array per requested field, as an attribute and as
+    ``tracks[name]``; ``fields`` lists the names."""
+
+    def __init__(self, step, rows, fields):
+        self.step = step
+        self.rows = rows
+        self.fields = tuple(fields)
+        for name in self.fields:
+            setattr(self, name, None)
+
+    def __getitem__(self, name):
+        if name not in self.fields:
+            raise KeyError(name)
+        return getattr(self, name)
+
+
 class _FrameCursor(object):
     """What ``iter()`` hands out for a trajectory or a subset of one (the role of hoomd.py:471-488):
     it knows how many frames it covers (``len``), yields them in order, and asking it for an iterator
@@ -1362,6 +1380,158 @@ class HOOMDTrajectory(object):
         self._read_logs_device(idx, snap, frame_of)
         return snap
 
+    # ------------------------------------------------------------------ tracks: a few particles through many frames
+    def _track_args(self, rows, frames, fields):
+        """(rows on the host as int64, frame indices, field names) of a tracks read, checked: every frame must hold
+        row max(rows) -- IndexError naming the first that does not, before anything is read."""
+        n = len(self)
+        if frames is None:
+            idxs = list(range(n))
+        elif isinstance(frames, slice):
+            idxs = list(range(*frames.indices(n)))
+        else:
+            idxs = [int(i) + n if int(i) < 0 else int(i) for i in frames]
+        for idx in idxs:
+            if not 0 <= idx < n:
+                raise IndexError("frame %d of %d" % (idx, n))
+        fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        for name in fields:
+            if name not in _PARTICLE_SPEC and name not in _PARTICLE_SPEC_EXTRA:
+                raise ValueError("'%s' is not a per-particle attribute of ParticleData" % name)
+        if isinstance(rows, numpy.ndarray) or not _is_device(rows):
+            host = numpy.asarray(rows)
+        else:
+            host = fl._device_to_host(rows)
+        if host.size and host.dtype.kind not in 'iu':
+            raise ValueError("rows must be integers")
+        host = host.reshape(-1).astype(numpy.int64)
+        if host.size and (host.min() < 0 or host.max() >= 1 << 32):
+            raise ValueError("rows must be file rows, 0 <= row < 2^32")
+        f = self.file
+        counts = []
+        for idx in idxs:
+            if f.chunk_exists(frame=idx, name='particles/N', write_all=False):
+                n_idx = int(f.read_chunk(frame=idx, name='particles/N', offset=numpy.uint32(0), r_all=False)[0])
+            elif f.chunk_exists(frame=0, name='particles/N', write_all=False):
+                n_idx = int(self._frame0_small('particles/N')[0])
+            else:
+                n_idx = 0
+            if host.size and n_idx <= int(host.max()):
+                raise IndexError("frame %d holds %d particles: row %d lies outside it" % (idx, n_idx, int(host.max())))
+            counts.append(n_idx)
+        return host, idxs, fields, counts
+
+    def read_tracks(self, rows, frames=None, fields=('position',)):
+        """A few particles through many frames, on the host: ``read_tracks(rows, frames, fields)[f][i]`` is
+        ``trajectory[frames[i]].particles.<f>[rows]`` -- a plain loop over the frames that reads each field's effective
+        chunk on the host and picks the rows; it is the model of `read_tracks_device`.
+
+        Args:
+            rows: K file rows (the tags of a file written in tag order): a host array, a GPU tensor or anything with
+                ``__cuda_array_interface__``; any order, repeats allowed.
+            frames: frame indices, a slice, or ``None`` for every frame.
+            fields: names of per-particle attributes of `ParticleData`.
+
+        Returns:
+            `Tracks`: ``step`` (uint64, F entries), ``rows`` and per field an ``F x K (x M)`` numpy array of the chunk's
+            dtype (also ``tracks[name]``).  Elided chunks come from frame 0 or the defaults exactly as the reader
+            decides frame by frame.  A frame with ``N <= max(rows)`` raises IndexError before anything is read.
+        """
+        host, idxs, fields, counts = self._track_args(rows, frames, fields)
+        f = self.file
+        out = Tracks(numpy.zeros(len(idxs), dtype=numpy.uint64), host, fields)
+        for i, idx in enumerate(idxs):
+            step = ConfigurationData()
+            self._read_scalar_any(idx, 'configuration/step', step, 'step')
+            out.step[i] = step.step
+            for name in fields:
+                picked = self._read_particle_rows(idx, name, counts[i], host)
+                if out[name] is None:
+                    setattr(out, name, numpy.empty((len(idxs),) + picked.shape, dtype=picked.dtype))
+                out[name][i] = picked
+        for name in fields:
+            if out[name] is None:       # no frames
+                dt, M = _PARTICLE_SPEC.get(name) or _PARTICLE_SPEC_EXTRA[name]
+                setattr(out, name, numpy.empty((0, host.size, M) if M > 1 else (0, host.size), dtype=dt))
+        return out
+
+    def _read_particle_rows(self, idx, name, n_global, rows):
+        """``trajectory[idx].particles.<name>[rows]`` without reading the rest of the frame: the effective chunk's rows,
+        or rows of the default value."""
+        chunk = 'particles/' + name
+        fr = self._effective_frame(idx, chunk, n_global)
+        if fr is not None:
+            return self.file.read_chunk(fr, chunk)[rows]
+        if name not in ParticleData._default_value and not self.file.chunk_exists(0, chunk):
+            raise ValueError("particles/%s is stored neither in frame %d nor in frame 0" % (name, idx))
+        default = numpy.array([ParticleData._default_value.get(name, ParticleData._extra_default_value.get(name))])
+        return numpy.repeat(default, len(rows), axis=0)
+
+    def read_tracks_device(self, rows, frames=None, fields=('position',)):
+        """`read_tracks` into GPU memory, reading only the file blocks the rows touch.
+
+        One row plan (`pgsd.fl.PGSDFile.plan_rows`) per distinct particle count among the frames serves every chunk of
+        every such frame; each frame's gather lands straight in its ``[i]`` slice of the result, and the reads of one
+        frame share one ``wait_read`` (the HBM staging holds one frame's touched blocks).  Arguments as `read_tracks`.
+
+        Returns:
+            `Tracks` whose per-field ``F x K (x M)`` arrays (schema dtype) and ``rows`` (int32) live in GPU memory:
+            torch tensors where torch is importable, `pgsd.fl.DeviceBuffer` objects otherwise; ``step`` stays a host
+            array.
+        """
+        torch = fl._lib._torch
+        f = self.file
+        host, idxs, fields, counts = self._track_args(rows, frames, fields)
+        F, K = len(idxs), int(host.size)
+        device = f.pipeline_device()
+        rows32 = host.astype(numpy.uint32).view(numpy.int32)
+        if torch is None:
+            rows_dev = fl.DeviceBuffer((max(K, 1),), numpy.int32, device, pattern=rows32 if K else None).view(shape=(K,))
+        else:
+            rows_dev = torch.from_numpy(rows32.copy()).to(torch.device('cuda', device))
+        out = Tracks(numpy.zeros(F, dtype=numpy.uint64), rows_dev, fields)
+        for name in fields:
+            dt, M = _PARTICLE_SPEC.get(name) or _PARTICLE_SPEC_EXTRA[name]
+            shape = (F, K, M) if M > 1 else (F, K)
+            if torch is None:
+                default = ParticleData._default_value.get(name, ParticleData._extra_default_value.get(name))
+                row = numpy.ascontiguousarray(numpy.broadcast_to(numpy.asarray(default, dtype=dt), (M,)))
+                arr = fl.DeviceBuffer(shape, dt, device, pattern=row)   # (frames that read a default keep the fill)
+            else:
+                arr = torch.empty(shape, dtype=getattr(torch, numpy.dtype(dt).name), device=torch.device('cuda', device))
+            setattr(out, name, arr)
+        plans = {}
+        for i, idx in enumerate(idxs):
+            step = ConfigurationData()
+            self._read_scalar_any(idx, 'configuration/step', step, 'step')
+            out.step[i] = step.step
+            if K == 0:
+                continue
+            n_idx = counts[i]
+            for name in fields:
+                chunk = 'particles/' + name
+                dt, M = _PARTICLE_SPEC.get(name) or _PARTICLE_SPEC_EXTRA[name]
+                fr = self._effective_frame(idx, chunk, n_idx)
+                if fr is None:
+                    if name not in ParticleData._default_value and not f.chunk_exists(0, chunk):
+                        raise ValueError("particles/%s is stored neither in frame %d nor in frame 0" % (name, idx))
+                    if torch is not None:
+                        default = ParticleData._default_value.get(name, ParticleData._extra_default_value.get(name))
+                        out[name][i] = torch.as_tensor(numpy.asarray(default, dtype=dt), device=out[name].device)
+                    continue
+                plan = plans.get(n_idx)
+                if plan is None:
+                    plan = plans[n_idx] = f.plan_rows(rows_dev, n_idx)
+                if torch is None:
+                    width = K * M * numpy.dtype(dt).itemsize
+                    dst = out[name].view(shape=(K, M) if M > 1 else (K,), offset_bytes=i * width)
+                else:
+                    dst = out[name][i]
+                f.read_chunk_device(fr, chunk, out=dst, rows=plan, wait=False)
+            f.wait_read()
+        out.plans = plans
+        return out
+
     def _read_logs_device(self, idx, snap, frame_of):
         f = self.file
         for log in self._names_with_prefix('log/'):
@@ -1383,18 +1553,9 @@ class HOOMDTrajectory(object):
             domain = Domain(*domain)
         dims = int(snap.configuration.dimensions)
         box = snap.configuration.box
-        n_frame0 = []
 
         def effective(chunk):
-            # the frame's own chunk, else frame 0's while N is frame 0's, else none (defaults): the host reader's choice
-            fr = frame_of(chunk)
-            if fr == 0 and idx != 0:
-                if not n_frame0:
-                    n_frame0.append(int(self._frame0_small('particles/N')[0]) if f.chunk_exists(0, 'particles/N')
-                                    else n_global)
-                if n_frame0[0] != n_global:
-                    return None
-            return fr
+            return self._effective_frame(idx, chunk, n_global)
 
         device = f.pipeline_device()
         f_pos = effective('particles/position')
@@ -1414,7 +1575,17 @@ class HOOMDTrajectory(object):
         snap.domain = domain
         snap.tag = rows
 
-        def gather(chunk, fr, **kw):
+        # The chunks gathered after the position go through a row plan: in a file whose rows are spatially coherent the
+        # domain's rows touch few blocks and only those are read; in a spatially random file every block is touched and
+        # the plan hands the read to the whole-chunk route with the same rows.  (The position itself, and the type id
+        # that shares its Scalar4 rows, gather from the chunk the selection has staged whole anyway.)
+        plan = []
+
+        def gather(chunk, fr, planned=False, **kw):
+            if planned and count > 0:
+                if not plan:
+                    plan.append(f.plan_rows(rows, n_global))
+                return f.read_chunk_device(fr, chunk, rows=plan[0], wait=False, **kw)
             return f.read_chunk_device(fr, chunk, rows=rows, N=count, wait=False, **kw)
 
         def empty4():
@@ -1440,10 +1611,12 @@ class HOOMDTrajectory(object):
                     arr[:, 3] = w_default
             else:
                 arr = empty4()
+                planned = attr != 'pos4'
                 if f_xyz is not None:
-                    gather(xyz, f_xyz, out=arr, columns=(0, 3), fill=w_default if f_w is None else None)
+                    gather(xyz, f_xyz, planned, out=arr, columns=(0, 3), fill=w_default if f_w is None else None)
                 if f_w is not None:
-                    gather(w, f_w, out=arr, columns=(3, 4), bitcast=w_bitcast, fill=0.0 if f_xyz is None else None)
+                    gather(w, f_w, planned, out=arr, columns=(3, 4), bitcast=w_bitcast,
+                           fill=0.0 if f_xyz is None else None)
             setattr(snap.particles, attr, arr)
             f.wait_read()
         if not scalar4:
@@ -1457,7 +1630,7 @@ class HOOMDTrajectory(object):
             chunk = 'particles/' + name
             fr = effective(chunk)
             if fr is not None:
-                setattr(snap.particles, name, gather(chunk, fr))
+                setattr(snap.particles, name, gather(chunk, fr, True))
                 f.wait_read()
             elif defaults and name in snap.particles._default_value:
                 if default_rows is None:
@@ -1473,6 +1646,17 @@ class HOOMDTrajectory(object):
                         base = typed[tdt] = default_rows.view(tdt)
                     view = base.as_strided((count, M) if M > 1 else (count,), (0, 1) if M > 1 else (0,), off)
                 setattr(snap.particles, name, view)
+
+    def _effective_frame(self, idx, chunk, n_global):
+        """The frame whose copy of a per-particle chunk frame ``idx`` (of ``n_global`` particles) reads: its own, else
+        frame 0's while N is frame 0's, else ``None`` (the default value) -- the host reader's choice."""
+        f = self.file
+        if f.chunk_exists(idx, chunk):
+            return idx
+        if not f.chunk_exists(0, chunk):
+            return None
+        n_frame0 = int(self._frame0_small('particles/N')[0]) if f.chunk_exists(0, 'particles/N') else n_global
+        return 0 if n_frame0 == n_global else None
 
     def _default_rows_template(self, device):
         """All default rows of the SPH schema as ONE int32 device array (every element type of the schema is four

@@ -208,3 +208,12 @@ cdef extern from "pgsd_private.h" nogil:
                                   uint64_t* out_count)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                               const pgsd_field_dst* dst)
+    cdef struct pgsd_row_plan:
+        pass
+    int pgsd_row_plan_create(pgsd_handle* handle, const uint32_t* rows, uint64_t n, uint64_t N, uint32_t* rows2,
+                             pgsd_row_plan** out)
+    void pgsd_row_plan_destroy(pgsd_row_plan* plan)
+    int pgsd_row_plan_query(const pgsd_row_plan* plan, uint64_t* counts, const uint32_t** lists)
+    int pgsd_read_rows_planned_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const pgsd_row_plan* plan,
+                                      const pgsd_field_dst* dst)
+    int pgsd_device_read_counters(pgsd_handle* handle, uint64_t* pread_bytes, uint64_t* h2d_bytes, int reset)
