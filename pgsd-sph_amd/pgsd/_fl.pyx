@@ -202,30 +202,10 @@ cdef class DeviceField:
         :meth:`PGSDFile.set_source_stream`, or synchronise it)."""
         if _is_device_tensor(a):
             return cls.from_tensor(a, out_dtype=out_dtype, order=order, bitcast=bitcast, columns=columns)
-        iface = getattr(a, '__cuda_array_interface__', None)
-        if not isinstance(iface, dict) or 'data' not in iface or 'shape' not in iface or 'typestr' not in iface:
-            raise ValueError("not a GPU array: no __cuda_array_interface__")
-        dt = numpy.dtype(iface['typestr'])
-        if dt.byteorder == '>':
-            raise ValueError("big-endian device arrays are not supported")
-        shape = tuple(int(x) for x in iface['shape'])
-        if len(shape) == 1:
-            shape = (shape[0], 1)
-        elif len(shape) != 2:
-            raise ValueError("PGSD can only write 1 or 2 dimensional arrays")
-        N, S = shape
-        strides = iface.get('strides')
-        if strides is None:
-            row = S
-        else:
-            strides = tuple(int(x) for x in strides) if len(iface['shape']) == 2 else (int(strides[0]), dt.itemsize)
-            if (S > 1 and strides[1] != dt.itemsize) or strides[0] % dt.itemsize != 0:
-                raise ValueError("device arrays must be row-major with element-aligned rows")
-            row = strides[0] // dt.itemsize if N > 1 else S
+        ptr, dt, N, S, row = _rows2d(a, "device array")
         c0, c1 = (0, S) if columns is None else (int(columns[0]), int(columns[1]))
         if not (0 <= c0 < c1 <= S) or row < S:
             raise ValueError("columns outside the array's rows")
-        ptr = int(iface['data'][0]) if N * S > 0 else 0
         keep = [a]
         order_ptr = None
         if order is not None:
@@ -471,6 +451,106 @@ def _device_to_host(x):
     return out
 
 
+
+def _device_empty(shape, dtype, device):
+    """An uninitialised array in the memory of GPU ``device``: a torch tensor where torch is importable, a
+    :class:`DeviceBuffer` (the library's own device memory) otherwise.  This and the helpers below are the one place
+    where that choice is made: what they return is taken by every reader of GPU arrays here (`_device_memory`,
+    `_rows2d`, `_device_to_host`), so a caller need not know which of the two it holds."""
+    torch = _lib._torch
+    if torch is None:
+        return DeviceBuffer(shape, dtype, device)
+    return torch.empty(shape, dtype=getattr(torch, numpy.dtype(dtype).name), device=torch.device('cuda', device))
+
+
+def _device_rows(shape, dtype, device, row):
+    """An array of ``shape`` in GPU memory whose rows (last axis) all equal the host array ``row``."""
+    row = numpy.ascontiguousarray(row, dtype=dtype)
+    if _lib._torch is None:
+        return DeviceBuffer(shape, dtype, device, pattern=row)      # ONE row repeated by the allocation
+    return _device_empty(shape, dtype, device).copy_(_lib._torch.from_numpy(row))
+
+
+def _device_from_host(array, device):
+    """A copy of a host array in GPU memory, typed and shaped like it."""
+    a = numpy.ascontiguousarray(array)
+    if _lib._torch is None:
+        return DeviceBuffer((max(a.size, 1),), a.dtype, device, pattern=a if a.size else None).view(shape=a.shape)
+    return _lib._torch.from_numpy(a).to(_lib._torch.device('cuda', device))
+
+
+def _device_head(x, k):
+    """The first ``k`` entries of a 1-D array in GPU memory, as a view."""
+    return x.view(shape=(int(k),)) if isinstance(x, DeviceBuffer) else x[:int(k)]
+
+
+def _device_at(x, i):
+    """``x[i]`` of a dense array in GPU memory, as a view."""
+    if not isinstance(x, DeviceBuffer):
+        return x[i]
+    return x.view(shape=x.shape[1:], offset_bytes=i * (x.nbytes // x.shape[0]))
+
+
+def _device_row_views(words, fields, n):
+    """For every ``(first word, M, numpy dtype)`` of ``fields`` an ``(n,)`` / ``(n, M)`` view of the int32 GPU array
+    ``words`` whose ``n`` rows are all the same ``M`` words (row stride 0): no n-row allocation, no copy."""
+    torch = _lib._torch
+    views, typed = [], {}
+    for off, M, dt in fields:
+        shape = (n, M) if M > 1 else (n,)
+        if torch is None:
+            # one strided view per field
+            views.append(words.view(dtype=dt, shape=shape, strides=(0, dt.itemsize)[:len(shape)], offset_bytes=4 * off))
+            continue
+        base = typed.get(dt)
+        if base is None:
+            base = typed[dt] = words.view(getattr(torch, dt.name))  # one re-typed view of the words per element type
+        views.append(base.as_strided(shape, (0, 1)[:len(shape)], off))
+    return views
+
+
+def _index_rows(rows):
+    """(address, entries) of a dense array of 32-bit row indices in GPU memory."""
+    es = rows.element_size() if hasattr(rows, 'element_size') else \
+        numpy.dtype(rows.__cuda_array_interface__['typestr']).itemsize
+    if es != 4:
+        raise ValueError("rows must hold 32-bit row indices")
+    ptr, nbytes = _device_memory(rows, "rows")
+    return ptr, nbytes // 4
+
+
+def _rows2d(x, what):
+    """(address, numpy dtype, rows, width, row stride in elements) of a 1-D or row-major 2-D array in GPU memory, rows
+    possibly strided: a torch GPU tensor, a :class:`DeviceBuffer` or any object with ``__cuda_array_interface__``
+    (version 2 or 3)."""
+    if _is_device_tensor(x):
+        t2 = x.unsqueeze(1) if x.dim() == 1 else x
+        if t2.dim() != 2 or (t2.shape[1] > 1 and t2.stride(1) != 1):
+            raise ValueError("%s must be 1-D or row-major 2-D" % what)
+        rows, width = int(t2.shape[0]), int(t2.shape[1])
+        return t2.data_ptr(), _PGSD_TO_NP[_pgsd_type(t2.dtype)], rows, width, int(t2.stride(0)) if rows > 1 else width
+    iface = getattr(x, '__cuda_array_interface__', None) if not hasattr(x, 'data_ptr') or isinstance(x, DeviceBuffer) else None
+    if not isinstance(iface, dict) or 'data' not in iface or 'shape' not in iface or 'typestr' not in iface:
+        raise ValueError("%s must live in GPU memory (torch GPU tensor, DeviceBuffer or __cuda_array_interface__)" % what)
+    dt = numpy.dtype(iface['typestr'])
+    if dt.byteorder == '>':
+        raise ValueError("big-endian device arrays are not supported")
+    shape = tuple(int(v) for v in iface['shape'])
+    if len(shape) == 1:
+        shape = (shape[0], 1)
+    if len(shape) != 2:
+        raise ValueError("%s must be 1-D or row-major 2-D" % what)
+    rows, width = shape
+    st = iface.get('strides')
+    if st is None:
+        stride = width
+    else:
+        if (width > 1 and int(st[1]) != dt.itemsize) or int(st[0]) % dt.itemsize != 0:
+            raise ValueError("%s must be 1-D or row-major 2-D with element-aligned rows" % what)
+        stride = int(st[0]) // dt.itemsize if rows > 1 else width
+    return (int(iface['data'][0]) if rows * width > 0 else 0), dt, rows, width, stride
+
+
 def select_rows(flags):
     """Stream compaction on the GPU for filtered snapshots.
 
@@ -513,9 +593,7 @@ def select_rows(flags):
     with nogil:
         retval = C.pgsd_select_rows(<const uint8_t*>p_flags, n, <uint32_t*>p_index, &k, <void*>stream)
     _raise_on_error(retval, "select_rows")
-    if isinstance(index, DeviceBuffer):
-        return index.view(shape=(int(k),)), int(k)
-    return index[:int(k)], int(k)
+    return _device_head(index, k), int(k)
 
 
 RowPlanModel = collections.namedtuple('RowPlanModel', ['blocks', 'runs', 'rows2', 'staged_rows'])
@@ -1357,12 +1435,7 @@ cdef class PGSDFile:
                 (default: ``PGSD_PLAN_SPARSE_MAX``).
         """
         self._check_open()
-        es = rows.element_size() if hasattr(rows, 'element_size') else \
-            numpy.dtype(rows.__cuda_array_interface__['typestr']).itemsize
-        if es != 4:
-            raise ValueError("rows must hold 32-bit row indices")
-        p_rows, rows_bytes = _device_memory(rows, "rows")
-        n = rows_bytes // 4
+        p_rows, n = _index_rows(rows)
         cdef RowPlan plan = RowPlan.__new__(RowPlan)
         plan.rows = rows
         plan.rows2 = DeviceBuffer((max(n, 1),), numpy.uint32, self.pipeline_device()).view(shape=(n,))
@@ -1397,68 +1470,55 @@ cdef class PGSDFile:
         self._check_open()
         return self._find(frame, name) != NULL
 
-    def read_chunk(self, frame, name, N=0, M=0, offset=0, r_all=False):
-        """Read a data chunk and return it as a numpy array (fl.pyx:717-874).
-
-        ``(N,)`` for Nx1 chunks, ``(N, M)`` otherwise.  With ``r_all=True`` only ``N`` rows of
-        ``M`` columns starting at row ``offset`` are read (every rank reads its partition).
-        """
+    cdef int _entry(self, frame, name, C.pgsd_index_entry* entry) except -1:
+        """A copy of a chunk's index entry (a later flush may move the index storage): KeyError if the frame holds no
+        such chunk, ValueError if its element type is unknown."""
         self._check_open()
         cdef const C.pgsd_index_entry* e = self._find(frame, name)
         if e == NULL:
             raise KeyError("frame " + str(frame) + " / chunk " + name + " not found in: " + self._name)
-        cdef uint64_t eN = e.N
-        cdef uint32_t eM = e.M
-        cdef int etype = e.type
-        if etype not in _PGSD_TO_NP:
+        if e.type not in _PGSD_TO_NP:
             raise ValueError("invalid type for chunk: " + name)
-        data_array = numpy.empty(dtype=_PGSD_TO_NP[etype], shape=[eN, eM])
+        entry[0] = e[0]
+        return 0
+
+    cdef _read_entry(self, const C.pgsd_index_entry* e, uint64_t height, uint64_t c_N, uint32_t c_M, uint32_t c_off,
+                     bint c_all):
+        """`pgsd_read_chunk` into a new numpy array of ``height`` rows: ``(height,)`` for Nx1 chunks, ``(height, M)``
+        otherwise."""
+        data_array = numpy.empty(dtype=_PGSD_TO_NP[e.type], shape=[height, e.M])
         cdef Py_buffer view
-        cdef uint64_t c_N = int(N)
-        cdef uint32_t c_M = int(M), c_off = int(offset)
-        cdef bint c_all = bool(r_all)
         cdef int retval, err
-        if eN != 0 and eM != 0:
+        if height != 0 and e.M != 0:
             PyObject_GetBuffer(data_array, &view, PyBUF_ANY_CONTIGUOUS)
             with nogil:
                 retval = C.pgsd_read_chunk(&self._handle, view.buf, e, c_N, c_M, c_off, c_all)
                 err = errno
             PyBuffer_Release(&view)
             _raise_on_error(retval, self._name, err)
-        if eM == 1:
-            return data_array.reshape([eN])
+        if e.M == 1:
+            return data_array.reshape([height])
         return data_array
+
+    def read_chunk(self, frame, name, N=0, M=0, offset=0, r_all=False):
+        """Read a data chunk and return it as a numpy array (fl.pyx:717-874).
+
+        ``(N,)`` for Nx1 chunks, ``(N, M)`` otherwise.  With ``r_all=True`` only ``N`` rows of
+        ``M`` columns starting at row ``offset`` are read (every rank reads its partition).
+        """
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        return self._read_entry(&entry, entry.N, int(N), int(M), int(offset), bool(r_all))
 
     def read_rows(self, frame, name, row0, n):
         """Rows ``[row0, row0 + n)`` of a chunk as an ``(n,)`` / ``(n, M)`` numpy array: `pgsd_read_chunk` with
         ``all == true`` (pgsd.c:2498-2534) into an array of THAT height -- :meth:`read_chunk` with ``r_all=True``
         allocates the chunk's full height like the reference's binding (fl.pyx:838-860), every rank the global array."""
-        self._check_open()
-        cdef const C.pgsd_index_entry* e = self._find(frame, name)
-        if e == NULL:
-            raise KeyError("frame " + str(frame) + " / chunk " + name + " not found in: " + self._name)
-        cdef uint64_t eN = e.N
-        cdef uint32_t eM = e.M
-        cdef int etype = e.type
-        if etype not in _PGSD_TO_NP:
-            raise ValueError("invalid type for chunk: " + name)
-        if int(row0) < 0 or int(n) < 0 or int(row0) + int(n) > eN or int(row0) >= (1 << 32):
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        if int(row0) < 0 or int(n) < 0 or int(row0) + int(n) > entry.N or int(row0) >= (1 << 32):
             raise ValueError("row range outside the chunk: " + name)
-        data_array = numpy.empty(dtype=_PGSD_TO_NP[etype], shape=[int(n), eM])
-        cdef Py_buffer view
-        cdef uint64_t c_N = int(n)
-        cdef uint32_t c_off = int(row0)
-        cdef int retval, err
-        if c_N != 0 and eM != 0:
-            PyObject_GetBuffer(data_array, &view, PyBUF_ANY_CONTIGUOUS)
-            with nogil:
-                retval = C.pgsd_read_chunk(&self._handle, view.buf, e, c_N, eM, c_off, True)
-                err = errno
-            PyBuffer_Release(&view)
-            _raise_on_error(retval, self._name, err)
-        if eM == 1:
-            return data_array.reshape([int(n)])
-        return data_array
+        return self._read_entry(&entry, int(n), int(n), entry.M, int(row0), True)
 
     def select_domain_device(self, frame, name, box, domain, dimensions=3):
         """The rows of a position chunk that lie in one spatial domain, selected on the GPU.
@@ -1476,29 +1536,18 @@ cdef class PGSDFile:
             :func:`pgsd.hoomd.domain_rows`.  The staged position rows are kept until the next :meth:`wait_read`: a
             ``read_chunk_device(..., rows=rows)`` of the same chunk before it reads no file bytes again.
         """
-        self._check_open()
-        torch = _lib._torch
-        cdef const C.pgsd_index_entry* e = self._find(frame, name)
-        if e == NULL:
-            raise KeyError("frame " + str(frame) + " / chunk " + name + " not found in: " + self._name)
-        cdef C.pgsd_index_entry entry = e[0]      # a later flush may move the index storage
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
         lo, hi = (domain.lo, domain.hi) if hasattr(domain, 'lo') else domain
         c_box = numpy.ascontiguousarray(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
         c_lo = numpy.ascontiguousarray(lo, dtype=numpy.float64).reshape(3)
         c_hi = numpy.ascontiguousarray(hi, dtype=numpy.float64).reshape(3)
         if c_box.shape[0] != 6:
             raise ValueError("box must hold 6 values")
-        n = int(entry.N)
-        device = self.pipeline_device()
-        if torch is not None:
-            rows = torch.empty((max(n, 1),), dtype=torch.int32, device=torch.device('cuda', device))
-            p_rows = rows.data_ptr()
-        else:
-            rows = DeviceBuffer((max(n, 1),), numpy.int32, device)
-            p_rows = rows.ptr
+        rows = _device_empty((max(int(entry.N), 1),), numpy.int32, self.pipeline_device())
         if not self._explicit_stream:
             self._sync_source_stream()      # the selection is ordered behind this stream's use of `rows`
-        cdef uintptr_t c_rows = p_rows, c_pbox = c_box.ctypes.data, c_plo = c_lo.ctypes.data, c_phi = c_hi.ctypes.data
+        cdef uintptr_t c_rows = rows.data_ptr(), c_pbox = c_box.ctypes.data, c_plo = c_lo.ctypes.data, c_phi = c_hi.ctypes.data
         cdef uint32_t c_dims = int(dimensions)
         cdef uint64_t k = 0
         cdef int retval, err
@@ -1510,9 +1559,7 @@ cdef class PGSDFile:
             msg = C.pgsd_last_error_string()
             raise ValueError("select_domain_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
         _raise_on_error(retval, self._name, err)
-        if isinstance(rows, DeviceBuffer):
-            return rows.view(shape=(int(k),)), int(k)
-        return rows[:int(k)], int(k)
+        return _device_head(rows, k), int(k)
 
     def read_chunk_device(self, frame, name, out=None, N=None, offset=0, columns=None, order=None,
                           bitcast=False, wait=True, fill=None, rows=None):
@@ -1545,15 +1592,9 @@ cdef class PGSDFile:
         Returns:
             the destination tensor.
         """
-        self._check_open()
-        torch = _lib._torch
-        cdef const C.pgsd_index_entry* e = self._find(frame, name)
-        if e == NULL:
-            raise KeyError("frame " + str(frame) + " / chunk " + name + " not found in: " + self._name)
-        cdef C.pgsd_index_entry entry = e[0]      # a later flush may move the index storage
-        eN, eM, etype = int(entry.N), int(entry.M), int(entry.type)
-        if etype not in _PGSD_TO_NP:
-            raise ValueError("invalid type for chunk: " + name)
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        eN, eM = int(entry.N), int(entry.M)
         cdef uintptr_t p_rows = 0
         cdef RowPlan plan = None
         if isinstance(rows, RowPlan):
@@ -1569,67 +1610,23 @@ cdef class PGSDFile:
             else:
                 plan = None
         index_rows = rows                   # (`rows` is reused below for the destination's height)
-        if plan is not None:
-            if order is not None or int(offset) != 0:
-                raise ValueError("an indexed read (rows=) takes neither order nor offset")
-        elif index_rows is not None:
-            if order is not None or int(offset) != 0:
-                raise ValueError("an indexed read (rows=) takes neither order nor offset")
-            es = index_rows.element_size() if hasattr(index_rows, 'element_size') else \
-                numpy.dtype(index_rows.__cuda_array_interface__['typestr']).itemsize
-            if es != 4:
-                raise ValueError("rows must hold 32-bit row indices")
-            p_rows, rows_bytes = _device_memory(index_rows, "rows")
+        if index_rows is not None and (order is not None or int(offset) != 0):
+            raise ValueError("an indexed read (rows=) takes neither order nor offset")
+        if index_rows is not None and plan is None:
+            p_rows, n_rows = _index_rows(index_rows)
             if N is None:
-                N = rows_bytes // 4
-            if N > rows_bytes // 4 or N > eN:
+                N = n_rows
+            if N > n_rows or N > eN:
                 raise ValueError("rows holds fewer entries than requested")
         if N is None:
             N = eN - int(offset)
         if N < 0 or int(offset) + N > eN:
             raise ValueError("row range outside the chunk: " + name)
-        np_dt = _PGSD_TO_NP[etype]
         if out is None:
-            # on the GPU the pipeline runs on (not a tensor library's "current device"); a torch tensor where torch
-            # is importable, the library's own memory otherwise
-            device = self.pipeline_device()
-            if torch is not None:
-                out = torch.empty((N, eM) if eM > 1 else (N,), dtype=getattr(torch, np_dt.name),
-                                  device=torch.device('cuda', device))
-            else:
-                out = DeviceBuffer((N, eM) if eM > 1 else (N,), np_dt, device)
+            # on the GPU the pipeline runs on (not a tensor library's "current device")
+            out = _device_empty((N, eM) if eM > 1 else (N,), _PGSD_TO_NP[entry.type], self.pipeline_device())
         cdef uintptr_t p_dst, p_order = 0
-        if _is_device_tensor(out):
-            t2 = out.unsqueeze(1) if out.dim() == 1 else out
-            if t2.dim() != 2 or (t2.shape[1] > 1 and t2.stride(1) != 1):
-                raise ValueError("out must be 1-D or row-major 2-D")
-            rows, width = int(t2.shape[0]), int(t2.shape[1])
-            stride = int(t2.stride(0)) if rows > 1 else width
-            out_dtype = t2.dtype
-            p_dst = t2.data_ptr()
-        else:
-            iface = getattr(out, '__cuda_array_interface__', None) if not hasattr(out, 'data_ptr') or isinstance(out, DeviceBuffer) else None
-            if not isinstance(iface, dict):
-                raise ValueError("out must live in GPU memory (torch GPU tensor, DeviceBuffer or __cuda_array_interface__)")
-            out_dtype = numpy.dtype(iface['typestr'])
-            shp = tuple(int(v) for v in iface['shape'])
-            if len(shp) == 1:
-                shp = (shp[0], 1)
-            if len(shp) != 2:
-                raise ValueError("out must be 1-D or row-major 2-D")
-            rows, width = shp
-            st = iface.get('strides')
-            if st is not None and len(iface['shape']) == 2:
-                if (width > 1 and int(st[1]) != out_dtype.itemsize) or int(st[0]) % out_dtype.itemsize != 0:
-                    raise ValueError("out must be 1-D or row-major 2-D")
-                stride = int(st[0]) // out_dtype.itemsize if rows > 1 else width
-            elif st is not None:
-                if int(st[0]) % out_dtype.itemsize != 0:
-                    raise ValueError("out must be 1-D or row-major 2-D")
-                stride = int(st[0]) // out_dtype.itemsize if rows > 1 else 1
-            else:
-                stride = width
-            p_dst = int(iface['data'][0]) if rows * width > 0 else 0
+        p_dst, out_dtype, rows, width, stride = _rows2d(out, "out")
         c0 = 0 if columns is None else int(columns[0])
         if columns is not None and int(columns[1]) - c0 != eM:
             raise ValueError("columns must span the chunk's %d columns" % eM)
@@ -1648,9 +1645,8 @@ cdef class PGSDFile:
         dst.dst_col0 = c0
         dst.bitcast = 1 if bitcast else 0
         if fill is not None:
-            np_out = numpy.dtype(str(out_dtype)[6:]) if str(out_dtype).startswith('torch.') else numpy.dtype(out_dtype)
             dst.fill_rest = 1
-            dst.fill_bits = int(numpy.array([fill], dtype=np_out).view(numpy.dtype('u%d' % np_out.itemsize))[0])
+            dst.fill_bits = int(numpy.array([fill], dtype=out_dtype).view(numpy.dtype('u%d' % out_dtype.itemsize))[0])
         self._keepalive.append((out, order, index_rows, plan))
         if not self._explicit_stream:
             self._sync_source_stream()      # the unpack is ordered behind this stream's use of `out`

@@ -16,6 +16,7 @@ except ImportError as e:  # pragma: no cover - a checkout that was never built
                       "(or python -c 'import __graft_entry__ as g; g.build()'): %s" % e)
 
 from ._fl import DeviceBuffer, DeviceField, PGSDFile, RowPlan, open, select_rows, row_plan_model, logger  # noqa: E402,F401
+from ._fl import _device_empty, _device_rows, _device_from_host, _device_head, _device_at, _device_row_views  # noqa: E402,F401
 from ._fl import _device_to_host, _is_device_tensor, _is_device_array, _pgsd_type, _NP_TO_PGSD, _PGSD_TO_NP  # noqa: E402,F401
 
 __all__ = ["open", "PGSDFile", "DeviceField", "DeviceBuffer", "RowPlan", "select_rows", "row_plan_model"]

@@ -125,23 +125,33 @@ class ConfigurationData(object):
             self.box = self.box.reshape([6])
 
 
-# (dtype, columns) of every per-particle chunk; the first block is the PGSD-SPH schema the
-# reference implements (hoomd.py:167-184), the second the upstream HOOMD attributes that the
-# reference documents (hoomd.py:133-158) but leaves out of its reader.
-_PARTICLE_SPEC = OrderedDict([
-    ('typeid', (numpy.uint32, 1)), ('mass', (numpy.float32, 1)), ('body', (numpy.int32, 1)),
-    ('position', (numpy.float32, 3)), ('velocity', (numpy.float32, 3)),
-    ('slength', (numpy.float32, 1)), ('density', (numpy.float32, 1)), ('pressure', (numpy.float32, 1)),
-    ('energy', (numpy.float32, 1)),
-    ('auxiliary1', (numpy.float32, 3)), ('auxiliary2', (numpy.float32, 3)),
-    ('auxiliary3', (numpy.float32, 3)), ('auxiliary4', (numpy.float32, 3)),
-    ('image', (numpy.int32, 3)),
+def _field(dtype, M, default, upstream=False):
+    return (dtype, M, dtype(default) if M == 1 else numpy.array(default, dtype=dtype), upstream)
+
+
+# Every per-particle chunk in schema order: name -> (dtype, columns, default value, upstream-only?).  The first block
+# is the PGSD-SPH schema the reference implements (hoomd.py:167-184), the second the upstream HOOMD attributes that the
+# reference documents (hoomd.py:133-158) but leaves out of its reader.  `ParticleData._default_value` and
+# `_extra_default_value` are made from this table.
+_PARTICLE_FIELDS = OrderedDict([
+    ('typeid', _field(numpy.uint32, 1, 0)), ('mass', _field(numpy.float32, 1, 1.0)),
+    ('body', _field(numpy.int32, 1, -1)),
+    ('position', _field(numpy.float32, 3, [0, 0, 0])), ('velocity', _field(numpy.float32, 3, [0, 0, 0])),
+    ('slength', _field(numpy.float32, 1, 1.0)), ('density', _field(numpy.float32, 1, 0.0)),
+    ('pressure', _field(numpy.float32, 1, 0.0)), ('energy', _field(numpy.float32, 1, 0.0)),
+    ('auxiliary1', _field(numpy.float32, 3, [0, 0, 0])), ('auxiliary2', _field(numpy.float32, 3, [0, 0, 0])),
+    ('auxiliary3', _field(numpy.float32, 3, [0, 0, 0])), ('auxiliary4', _field(numpy.float32, 3, [0, 0, 0])),
+    ('image', _field(numpy.int32, 3, [0, 0, 0])),
+    ('charge', _field(numpy.float32, 1, 0.0, True)), ('diameter', _field(numpy.float32, 1, 1.0, True)),
+    ('moment_inertia', _field(numpy.float32, 3, [0, 0, 0], True)),
+    ('orientation', _field(numpy.float32, 4, [1, 0, 0, 0], True)),
+    ('angmom', _field(numpy.float32, 4, [0, 0, 0, 0], True)),
 ])
-_PARTICLE_SPEC_EXTRA = OrderedDict([
-    ('charge', (numpy.float32, 1)), ('diameter', (numpy.float32, 1)),
-    ('moment_inertia', (numpy.float32, 3)), ('orientation', (numpy.float32, 4)),
-    ('angmom', (numpy.float32, 4)),
-])
+
+# HOOMD's Scalar4 arrays as `read_frame_device(scalar4=True)` assembles them: attribute -> (xyz chunk, w chunk,
+# w is bit-cast?, default w)
+_SCALAR4 = {'pos4': ('particles/position', 'particles/typeid', True, 0.0),
+            'vel4': ('particles/velocity', 'particles/mass', False, 1.0)}
 
 
 class ParticleData(object):
@@ -152,57 +162,35 @@ class ParticleData(object):
     tensors / :class:`pgsd.fl.DeviceField` objects (write only).
     """
 
-    _default_value = OrderedDict()
-    _default_value['N'] = numpy.uint32(0)
-    _default_value['types'] = ['A']
-    _default_value['typeid'] = numpy.uint32(0)
-    _default_value['mass'] = numpy.float32(1.0)
-    _default_value['body'] = numpy.int32(-1)
-    _default_value['position'] = numpy.array([0, 0, 0], dtype=numpy.float32)
-    _default_value['velocity'] = numpy.array([0, 0, 0], dtype=numpy.float32)
-    _default_value['slength'] = numpy.float32(1.0)
-    _default_value['density'] = numpy.float32(0.0)
-    _default_value['pressure'] = numpy.float32(0.0)
-    _default_value['energy'] = numpy.float32(0.0)
-    _default_value['auxiliary1'] = numpy.array([0, 0, 0], dtype=numpy.float32)
-    _default_value['auxiliary2'] = numpy.array([0, 0, 0], dtype=numpy.float32)
-    _default_value['auxiliary3'] = numpy.array([0, 0, 0], dtype=numpy.float32)
-    _default_value['auxiliary4'] = numpy.array([0, 0, 0], dtype=numpy.float32)
-    _default_value['image'] = numpy.array([0, 0, 0], dtype=numpy.int32)
-    _default_value['type_shapes'] = [{}]
+    _default_value = OrderedDict(
+        [('N', numpy.uint32(0)), ('types', ['A'])]
+        + [(name, field[2]) for name, field in _PARTICLE_FIELDS.items() if not field[3]]
+        + [('type_shapes', [{}])])
 
     # upstream HOOMD attributes: written when set, read back when present in the file
-    _extra_default_value = OrderedDict()
-    _extra_default_value['charge'] = numpy.float32(0.0)
-    _extra_default_value['diameter'] = numpy.float32(1.0)
-    _extra_default_value['moment_inertia'] = numpy.array([0, 0, 0], dtype=numpy.float32)
-    _extra_default_value['orientation'] = numpy.array([1, 0, 0, 0], dtype=numpy.float32)
-    _extra_default_value['angmom'] = numpy.array([0, 0, 0, 0], dtype=numpy.float32)
+    _extra_default_value = OrderedDict((name, field[2]) for name, field in _PARTICLE_FIELDS.items() if field[3])
 
     def __init__(self):
         self.N = 0
         self.types = None
         self.type_shapes = None
-        for name in _PARTICLE_SPEC:
-            setattr(self, name, None)
-        for name in _PARTICLE_SPEC_EXTRA:
+        for name in _PARTICLE_FIELDS:
             setattr(self, name, None)
 
     def validate(self):
         """Convert host arrays to contiguous arrays of the schema dtype and shape
         (hoomd.py:206-270); device-resident attributes are only shape-checked."""
         logger.debug('Validating ParticleData')
-        for spec in (_PARTICLE_SPEC, _PARTICLE_SPEC_EXTRA):
-            for name, (dt, M) in spec.items():
-                value = getattr(self, name)
-                if value is None:
-                    continue
-                if _is_device(value):
-                    if _rows(value) != self.N:
-                        raise ValueError("particles/%s has %d rows, expected N=%d" % (name, _rows(value), self.N))
-                    continue
-                value = numpy.ascontiguousarray(value, dtype=dt)
-                setattr(self, name, value.reshape([self.N]) if M == 1 else value.reshape([self.N, M]))
+        for name, (dt, M, _, _) in _PARTICLE_FIELDS.items():
+            value = getattr(self, name)
+            if value is None:
+                continue
+            if _is_device(value):
+                if _rows(value) != self.N:
+                    raise ValueError("particles/%s has %d rows, expected N=%d" % (name, _rows(value), self.N))
+                continue
+            value = numpy.ascontiguousarray(value, dtype=dt)
+            setattr(self, name, value.reshape([self.N]) if M == 1 else value.reshape([self.N, M]))
         if self.types is not None and (not len(set(self.types)) == len(self.types)):
             raise ValueError("Type names must be unique.")
 
@@ -500,6 +488,12 @@ def _encode_strings(strings):
     return b.view(dtype=numpy.int8).reshape(len(b), wid)
 
 
+def _decode_strings(tmp):
+    """(n, wid) int8 array, NUL padded -> list[str]: the inverse of `_encode_strings` (hoomd.py:757-759)."""
+    tmp = tmp.view(dtype=numpy.dtype((bytes, tmp.shape[1]))).reshape([tmp.shape[0]])
+    return list(a.decode('UTF-8') for a in tmp)
+
+
 def _shape_key(name, value):
     """(type, shape) of a replicated / state / log value as it will be written: what must agree between the ranks."""
     if isinstance(value, (list, tuple)) and name in ('types', 'type_shapes'):
@@ -703,9 +697,9 @@ class HOOMDTrajectory(object):
                 if value is None:
                     entries.append([path, name, False])     # most of the schema, most of the time: not set
                     continue
-                per_particle = particles and (name in _PARTICLE_SPEC or name in _PARTICLE_SPEC_EXTRA)
+                per_particle = particles and name in _PARTICLE_FIELDS
                 if per_particle and _is_device(value):
-                    dt, _ = (_PARTICLE_SPEC.get(name) or _PARTICLE_SPEC_EXTRA.get(name))
+                    dt = _PARTICLE_FIELDS[name][0]
                     field = value if isinstance(value, fl.DeviceField) else fl.DeviceField.from_device_array(value, out_dtype=dt)
                     dev.append((len(entries), path + '/' + name, field))
                     entries.append([path, name, True])
@@ -829,8 +823,8 @@ class HOOMDTrajectory(object):
             chunk = path + '/' + name
             if debug:
                 logger.debug('writing data chunk: ' + chunk)
-            if path == 'particles' and (name in _PARTICLE_SPEC or name in _PARTICLE_SPEC_EXTRA):
-                dt, M = (_PARTICLE_SPEC.get(name) or _PARTICLE_SPEC_EXTRA.get(name))
+            if path == 'particles' and name in _PARTICLE_FIELDS:
+                dt, M, default, _ = _PARTICLE_FIELDS[name]
                 if at in dev_at:
                     k, field = dev_at[at]
                     if ticket is None:
@@ -842,7 +836,6 @@ class HOOMDTrajectory(object):
                     continue
                 if data is None:
                     # another rank needs the chunk: contribute this rank's rows of the default
-                    default = container._default_value.get(name, container._extra_default_value.get(name))
                     data = numpy.empty([n_local] + ([M] if M > 1 else []), dtype=dt)
                     data[...] = default
                 self._flush_device_fields(device_fields, particle_offset, rank)
@@ -952,10 +945,8 @@ class HOOMDTrajectory(object):
         key = (chunk, device)
         ref = self._default_ref.get(key)
         if ref is None:
-            name = chunk.split('/', 1)[1]
-            default = ParticleData._default_value.get(name, ParticleData._extra_default_value.get(name))
             row = numpy.empty((1, int(field.M)), dtype=field.out_dtype)
-            row[...] = default
+            row[...] = _PARTICLE_FIELDS[chunk.split('/', 1)[1]][2]
             # 4096 rows of the default value in the library's own device memory: ONE row repeated by the allocation
             ref = fl.DeviceBuffer((4096 * row.nbytes,), numpy.uint8, device, pattern=row)
             self._default_ref[key] = ref
@@ -1027,6 +1018,7 @@ class HOOMDTrajectory(object):
         frame 0 has no such chunk (hoomd.py:654-694)."""
         container = getattr(frame, path)
         data = getattr(container, name, None)
+        per_particle = path == 'particles' and name in _PARTICLE_FIELDS
         if name == 'N' and path == 'particles':
             data = n_global
         if data is None:
@@ -1036,8 +1028,7 @@ class HOOMDTrajectory(object):
         if self._elision_ref is not None:
             initial_container = getattr(self._elision_ref, path)
             initial_data = getattr(initial_container, name, None)
-            if (initial_data is None and self._elision_lazy and path == 'particles'
-                    and (name in _PARTICLE_SPEC or name in _PARTICLE_SPEC_EXTRA)
+            if (initial_data is None and self._elision_lazy and per_particle
                     and (path + '/' + name) in (self._frame0_chunks or ())):
                 initial_data = self.file.read_chunk(frame=0, name=path + '/' + name, offset=numpy.uint32(0), r_all=False)
                 initial_container.__dict__[name] = initial_data
@@ -1049,9 +1040,7 @@ class HOOMDTrajectory(object):
         # comparison with the default (the dearer of the two) only when it can decide something
         if (path + '/' + name) in (self._frame0_chunks or ()):
             return True
-        default = container._default_value.get(name)
-        if default is None and path == 'particles':
-            default = container._extra_default_value.get(name)
+        default = _PARTICLE_FIELDS[name][2] if per_particle else container._default_value.get(name)
         if name in ('types', 'type_shapes'):
             matches_default_value = data == default
         else:
@@ -1075,12 +1064,11 @@ class HOOMDTrajectory(object):
             container.N = int(f.read_chunk(0, path + '/N')[0]) if f.chunk_exists(0, path + '/N') else 0
         for name in ('types', 'type_shapes'):
             if f.chunk_exists(0, 'particles/' + name):
-                tmp = f.read_chunk(0, 'particles/' + name)
-                tmp = tmp.view(dtype=numpy.dtype((bytes, tmp.shape[1]))).reshape([tmp.shape[0]])
+                tmp = _decode_strings(f.read_chunk(0, 'particles/' + name))
                 if name == 'types':
-                    snap.particles.types = list(a.decode('UTF-8') for a in tmp)
+                    snap.particles.types = tmp
                 else:
-                    snap.particles.type_shapes = list(json.loads(a.decode('UTF-8')) for a in tmp)
+                    snap.particles.type_shapes = list(json.loads(a) for a in tmp)
             else:
                 setattr(snap.particles, name, snap.particles._default_value[name])
         for name in ('value', 'group'):
@@ -1169,8 +1157,7 @@ class HOOMDTrajectory(object):
             if 'types' in container._default_value:
                 if self.file.chunk_exists(frame=idx, name=path + '/types', write_all=False):
                     tmp = self.file.read_chunk(frame=idx, name=path + '/types', offset=numpy.uint32(0), r_all=False)
-                    tmp = tmp.view(dtype=numpy.dtype((bytes, tmp.shape[1]))).reshape([tmp.shape[0]])
-                    container.types = list(a.decode('UTF-8') for a in tmp)
+                    container.types = _decode_strings(tmp)
                 elif initial is not None:
                     container.types = initial.types
                 else:
@@ -1180,8 +1167,7 @@ class HOOMDTrajectory(object):
                 if self.file.chunk_exists(frame=idx, name=path + '/type_shapes', write_all=False):
                     tmp = self.file.read_chunk(frame=idx, name=path + '/type_shapes', offset=numpy.uint32(0),
                                                r_all=False)
-                    tmp = tmp.view(dtype=numpy.dtype((bytes, tmp.shape[1]))).reshape([tmp.shape[0]])
-                    container.type_shapes = list(json.loads(s.decode('UTF-8')) for s in tmp)
+                    container.type_shapes = list(json.loads(s) for s in _decode_strings(tmp))
                 elif initial is not None:
                     container.type_shapes = initial.type_shapes
                 else:
@@ -1247,7 +1233,6 @@ class HOOMDTrajectory(object):
             arrays are torch GPU tensors where torch is importable, `pgsd.fl.DeviceBuffer` objects (the library's own
             device memory, ``__cuda_array_interface__``) otherwise -- on the GPU the file's pipeline runs on.
         """
-        torch = fl._lib._torch          # None: no tensor library in this process
         if idx < 0:
             idx += len(self)
         if idx >= len(self) or idx < 0:
@@ -1256,7 +1241,7 @@ class HOOMDTrajectory(object):
         snap = Frame()
         self._read_scalar_any(idx, 'configuration/step', snap.configuration, 'step')
         self._read_scalar_any(idx, 'configuration/dimensions', snap.configuration, 'dimensions')
-        box_frame = idx if f.chunk_exists(idx, 'configuration/box') else (0 if f.chunk_exists(0, 'configuration/box') else None)
+        box_frame = self._frame_of(idx, 'configuration/box')
         if box_frame is None:
             snap.configuration.box = snap.configuration._default_value['box']
         elif box_frame == 0:
@@ -1264,28 +1249,20 @@ class HOOMDTrajectory(object):
         else:
             snap.configuration.box = f.read_chunk(box_frame, 'configuration/box')
 
-        def frame_of(chunk):
-            if f.chunk_exists(idx, chunk):
-                return idx
-            if f.chunk_exists(0, chunk):
-                return 0
-            return None
-
-        fn = frame_of('particles/N')
+        fn = self._frame_of(idx, 'particles/N')
         n_global = 0 if fn is None else int((self._frame0_small('particles/N') if fn == 0 else f.read_chunk(fn, 'particles/N'))[0])
-        ft = frame_of('particles/types')
+        ft = self._frame_of(idx, 'particles/types')
         if ft is not None:
-            tmp = self._frame0_small('particles/types') if ft == 0 else f.read_chunk(ft, 'particles/types')
-            tmp = tmp.view(dtype=numpy.dtype((bytes, tmp.shape[1]))).reshape([tmp.shape[0]])
-            snap.particles.types = list(a.decode('UTF-8') for a in tmp)
+            snap.particles.types = _decode_strings(self._frame0_small('particles/types') if ft == 0
+                                                   else f.read_chunk(ft, 'particles/types'))
         else:
             snap.particles.types = snap.particles._default_value['types']
 
         if domain is not None:
             if part is not None:
                 raise ValueError("part and domain are mutually exclusive")
-            self._read_domain_device(idx, snap, domain, scalar4, defaults, n_global, frame_of)
-            self._read_logs_device(idx, snap, frame_of)
+            self._read_domain_device(idx, snap, domain, scalar4, defaults, n_global)
+            self._read_logs_device(idx, snap)
             return snap
         if part is None:
             rank, size = self._comm()
@@ -1298,87 +1275,83 @@ class HOOMDTrajectory(object):
         snap.particles.N_global = n_global
         snap.part = (row0, n)
 
-        specs = list(_PARTICLE_SPEC.items()) + list(_PARTICLE_SPEC_EXTRA.items())
         if self._frame0_dev_part != (row0, n):
             self._frame0_dev_part, self._frame0_dev_cache = (row0, n), {}     # rows of ONE partition are kept
         cache, fresh = self._frame0_dev_cache, []
-        n_frame0 = None          # frame 0's arrays stand in only while the particle count is frame 0's (hoomd.py:858-884)
-        default_rows = None      # this read's own copy of the default rows (one small device-to-device copy, below)
-        typed = {}
-        for name, (dt, M) in specs:
-            chunk = 'particles/' + name
-            fr = frame_of(chunk)
-            if fr == 0 and idx != 0:
-                if n_frame0 is None:
-                    n_frame0 = int(self._frame0_small('particles/N')[0]) if f.chunk_exists(0, 'particles/N') else n_global
-                if n_frame0 != n_global:
-                    fr = None
-            if fr == 0 and idx != 0:
+
+        def slab(fr, chunk, attr, **kw):
+            if fr == 0 and idx != 0 and not kw:
                 # an array the frame does not hold because it equals frame 0's (elided by `append`): this partition's
                 # rows of frame 0 are read from the file ONCE and handed out as device-to-device copies from then on
                 # (a trajectory whose static arrays are elided would otherwise re-read them for every frame)
                 cached = cache.get(chunk)
                 if cached is not None:
-                    setattr(snap.particles, name, cached.clone())
-                else:
-                    setattr(snap.particles, name, f.read_chunk_device(0, chunk, N=n, offset=row0, wait=False))
-                    fresh.append((name, chunk))
-            elif fr is not None:
-                setattr(snap.particles, name, f.read_chunk_device(fr, chunk, N=n, offset=row0, wait=False))
-            elif defaults and name in snap.particles._default_value:
-                # like the host reader (hoomd.py:872-881) a default is ONE row broadcast over the particles: no
-                # N-row allocation, no copy; `.contiguous()` / `.clone()` gives an array of its own.  The reference
-                # marks its defaults read-only; torch has no such flag, so every read gets its OWN copy of the rows
-                # (one clone of a 40-word template per frame, not one host->device copy per field): a write
-                # through a view changes this frame's view only, never a later frame's default
-                if default_rows is None:
-                    default_rows = self._default_rows_template(f.pipeline_device()).clone()
-                off, words, ndt = self._default_rows_layout[name]
-                if torch is None:
-                    # one strided view per attribute: n rows that are all the same `words` elements (stride 0)
-                    view = default_rows.view(dtype=ndt, shape=(n, M) if M > 1 else (n,),
-                                             strides=(0, ndt.itemsize) if M > 1 else (0,), offset_bytes=4 * off)
-                else:
-                    tdt = getattr(torch, ndt.name)
-                    base = typed.get(tdt)
-                    if base is None:
-                        base = typed[tdt] = default_rows.view(tdt)  # one re-typed view of the copy per element type
-                    view = base.as_strided((n, M) if M > 1 else (n,), (0, 1) if M > 1 else (0,), off)
-                setattr(snap.particles, name, view)
-        if scalar4 and n >= 0:
-            # HOOMD's Scalar4 arrays, every row stored WHOLE by the unpack launch: the columns a missing chunk
-            # would have fed come from the `fill` of the chunk that is there (type id 0 as bits, mass 1.0,
-            # position / velocity 0) -- no memset of the arrays, no 12-byte stores at a 16-byte stride
-            device = f.pipeline_device()
-            arrays = []
-            for xyz, w, w_bitcast, w_default in (('particles/position', 'particles/typeid', True, 0.0),
-                                                 ('particles/velocity', 'particles/mass', False, 1.0)):
-                f_xyz, f_w = frame_of(xyz), frame_of(w)
-                if f_xyz is None and f_w is None:
-                    # neither chunk anywhere: rows of (0, 0, 0, default w)
-                    row = numpy.array([0.0, 0.0, 0.0, w_default], dtype=numpy.float32)
-                    if torch is None:
-                        arr = fl.DeviceBuffer((n, 4), numpy.float32, device, pattern=row)
-                    else:
-                        arr = torch.zeros((n, 4), dtype=torch.float32, device=torch.device('cuda', device))
-                        arr[:, 3] = w_default
-                elif torch is None:
-                    arr = fl.DeviceBuffer((n, 4), numpy.float32, device)
-                else:
-                    arr = torch.empty((n, 4), dtype=torch.float32, device=torch.device('cuda', device))
-                arrays.append(arr)
-                if f_xyz is not None:
-                    f.read_chunk_device(f_xyz, xyz, out=arr, N=n, offset=row0, columns=(0, 3), wait=False,
-                                        fill=w_default if f_w is None else None)
-                if f_w is not None:
-                    f.read_chunk_device(f_w, w, out=arr, N=n, offset=row0, columns=(3, 4), bitcast=w_bitcast, wait=False,
-                                        fill=0.0 if f_xyz is None else None)
-            snap.particles.pos4, snap.particles.vel4 = arrays
-        f.wait_read()
+                    return cached.clone()
+                fresh.append((attr, chunk))
+            return f.read_chunk_device(fr, chunk, N=n, offset=row0, wait=False, **kw)
+
+        # everything is issued, then ONE wait
+        self._read_particles_device(idx, snap, n, n_global, defaults, slab,
+                                    [tuple(_PARTICLE_FIELDS) + (tuple(_SCALAR4) if scalar4 else ())])
         for name, chunk in fresh:
             cache[chunk] = getattr(snap.particles, name).clone()
-        self._read_logs_device(idx, snap, frame_of)
+        self._read_logs_device(idx, snap)
         return snap
+
+    def _read_particles_device(self, idx, snap, n, n_global, defaults, read, groups):
+        """The per-particle arrays of a device read, for slab and domain reads alike: which frame each chunk comes from
+        (`_effective_frame`), the default rows of what is stored nowhere, and HOOMD's Scalar4 arrays.
+
+        ``read(frame, chunk, attr, **kw)`` issues the read of the caller's ``n`` rows of one chunk without waiting --
+        into ``out=`` and its ``columns=`` where given, else into a new array, which it returns; ``attr`` is the
+        attribute of ``snap.particles`` the rows are for.  ``groups`` lists the attributes to read in the order of
+        their reads, `_SCALAR4`'s names for the assembled arrays, as tuples that each share one ``wait_read``: what
+        is in flight between two waits is what the HBM staging must hold."""
+        f = self.file
+        particles = snap.particles
+        device = f.pipeline_device()
+        frames = dict(('particles/' + name, self._effective_frame(idx, 'particles/' + name, n_global))
+                      for name in _PARTICLE_FIELDS)
+        missing = [name for name, field in _PARTICLE_FIELDS.items()
+                   if defaults and not field[3] and frames['particles/' + name] is None]
+        for group in groups:
+            issued = False
+            for attr in group:
+                if attr in _SCALAR4:
+                    # HOOMD's Scalar4 arrays, every row stored WHOLE by the unpack launch: the columns a missing chunk
+                    # would have fed come from the `fill` of the chunk that is there (type id 0 as bits, mass 1.0,
+                    # position / velocity 0) -- no memset of the arrays, no 12-byte stores at a 16-byte stride
+                    xyz, w, w_bitcast, w_default = _SCALAR4[attr]
+                    f_xyz, f_w = frames[xyz], frames[w]
+                    if f_xyz is None and f_w is None:
+                        # neither chunk anywhere: rows of (0, 0, 0, default w)
+                        arr = fl._device_rows((n, 4), numpy.float32, device, [0.0, 0.0, 0.0, w_default])
+                    else:
+                        arr = fl._device_empty((n, 4), numpy.float32, device)
+                        issued = True
+                    if f_xyz is not None:
+                        read(f_xyz, xyz, attr, out=arr, columns=(0, 3), fill=w_default if f_w is None else None)
+                    if f_w is not None:
+                        read(f_w, w, attr, out=arr, columns=(3, 4), bitcast=w_bitcast,
+                             fill=0.0 if f_xyz is None else None)
+                    setattr(particles, attr, arr)
+                elif frames['particles/' + attr] is not None:
+                    setattr(particles, attr, read(frames['particles/' + attr], 'particles/' + attr, attr))
+                    issued = True
+                elif missing:
+                    # like the host reader (hoomd.py:872-881) a default is ONE row broadcast over the particles: no
+                    # N-row allocation, no copy; `.contiguous()` / `.clone()` gives an array of its own.  The reference
+                    # marks its defaults read-only; torch has no such flag, so every read gets its OWN copy of the rows
+                    # (one clone of a 40-word template per frame, not one host->device copy per field): a write
+                    # through a view changes this frame's view only, never a later frame's default.  All of the
+                    # frame's default views are made here, at the first, behind the reads issued so far
+                    words = self._default_rows_template(device).clone()
+                    views = fl._device_row_views(words, [self._default_rows_layout[name] for name in missing], n)
+                    for name, view in zip(missing, views):
+                        setattr(particles, name, view)
+                    missing = None
+            if issued:
+                f.wait_read()
 
     # ------------------------------------------------------------------ tracks: a few particles through many frames
     def _track_args(self, rows, frames, fields):
@@ -1396,7 +1369,7 @@ class HOOMDTrajectory(object):
                 raise IndexError("frame %d of %d" % (idx, n))
         fields = (fields,) if isinstance(fields, str) else tuple(fields)
         for name in fields:
-            if name not in _PARTICLE_SPEC and name not in _PARTICLE_SPEC_EXTRA:
+            if name not in _PARTICLE_FIELDS:
                 raise ValueError("'%s' is not a per-particle attribute of ParticleData" % name)
         if isinstance(rows, numpy.ndarray) or not _is_device(rows):
             host = numpy.asarray(rows)
@@ -1451,7 +1424,7 @@ class HOOMDTrajectory(object):
                 out[name][i] = picked
         for name in fields:
             if out[name] is None:       # no frames
-                dt, M = _PARTICLE_SPEC.get(name) or _PARTICLE_SPEC_EXTRA[name]
+                dt, M = _PARTICLE_FIELDS[name][:2]
                 setattr(out, name, numpy.empty((0, host.size, M) if M > 1 else (0, host.size), dtype=dt))
         return out
 
@@ -1464,8 +1437,7 @@ class HOOMDTrajectory(object):
             return self.file.read_chunk(fr, chunk)[rows]
         if name not in ParticleData._default_value and not self.file.chunk_exists(0, chunk):
             raise ValueError("particles/%s is stored neither in frame %d nor in frame 0" % (name, idx))
-        default = numpy.array([ParticleData._default_value.get(name, ParticleData._extra_default_value.get(name))])
-        return numpy.repeat(default, len(rows), axis=0)
+        return numpy.repeat(numpy.array([_PARTICLE_FIELDS[name][2]]), len(rows), axis=0)
 
     def read_tracks_device(self, rows, frames=None, fields=('position',)):
         """`read_tracks` into GPU memory, reading only the file blocks the rows touch.
@@ -1479,27 +1451,28 @@ class HOOMDTrajectory(object):
             torch tensors where torch is importable, `pgsd.fl.DeviceBuffer` objects otherwise; ``step`` stays a host
             array.
         """
-        torch = fl._lib._torch
         f = self.file
         host, idxs, fields, counts = self._track_args(rows, frames, fields)
         F, K = len(idxs), int(host.size)
         device = f.pipeline_device()
-        rows32 = host.astype(numpy.uint32).view(numpy.int32)
-        if torch is None:
-            rows_dev = fl.DeviceBuffer((max(K, 1),), numpy.int32, device, pattern=rows32 if K else None).view(shape=(K,))
-        else:
-            rows_dev = torch.from_numpy(rows32.copy()).to(torch.device('cuda', device))
+        rows_dev = fl._device_from_host(host.astype(numpy.uint32).view(numpy.int32), device)
         out = Tracks(numpy.zeros(F, dtype=numpy.uint64), rows_dev, fields)
+        # which frame every (frame, field) reads, settled first: a field that some frame reads the default of is
+        # allocated filled with it (such a frame keeps the fill), every other field uninitialised
+        source = {}
+        for i, idx in enumerate(idxs):
+            for name in fields:
+                chunk = 'particles/' + name
+                source[i, name] = self._effective_frame(idx, chunk, counts[i])
+                if source[i, name] is None and name not in ParticleData._default_value and not f.chunk_exists(0, chunk):
+                    raise ValueError("particles/%s is stored neither in frame %d nor in frame 0" % (name, idx))
         for name in fields:
-            dt, M = _PARTICLE_SPEC.get(name) or _PARTICLE_SPEC_EXTRA[name]
+            dt, M, default, _ = _PARTICLE_FIELDS[name]
             shape = (F, K, M) if M > 1 else (F, K)
-            if torch is None:
-                default = ParticleData._default_value.get(name, ParticleData._extra_default_value.get(name))
-                row = numpy.ascontiguousarray(numpy.broadcast_to(numpy.asarray(default, dtype=dt), (M,)))
-                arr = fl.DeviceBuffer(shape, dt, device, pattern=row)   # (frames that read a default keep the fill)
+            if any(source[i, name] is None for i in range(F)):
+                setattr(out, name, fl._device_rows(shape, dt, device, default))
             else:
-                arr = torch.empty(shape, dtype=getattr(torch, numpy.dtype(dt).name), device=torch.device('cuda', device))
-            setattr(out, name, arr)
+                setattr(out, name, fl._device_empty(shape, dt, device))
         plans = {}
         for i, idx in enumerate(idxs):
             step = ConfigurationData()
@@ -1509,66 +1482,44 @@ class HOOMDTrajectory(object):
                 continue
             n_idx = counts[i]
             for name in fields:
-                chunk = 'particles/' + name
-                dt, M = _PARTICLE_SPEC.get(name) or _PARTICLE_SPEC_EXTRA[name]
-                fr = self._effective_frame(idx, chunk, n_idx)
-                if fr is None:
-                    if name not in ParticleData._default_value and not f.chunk_exists(0, chunk):
-                        raise ValueError("particles/%s is stored neither in frame %d nor in frame 0" % (name, idx))
-                    if torch is not None:
-                        default = ParticleData._default_value.get(name, ParticleData._extra_default_value.get(name))
-                        out[name][i] = torch.as_tensor(numpy.asarray(default, dtype=dt), device=out[name].device)
+                if source[i, name] is None:
                     continue
                 plan = plans.get(n_idx)
                 if plan is None:
                     plan = plans[n_idx] = f.plan_rows(rows_dev, n_idx)
-                if torch is None:
-                    width = K * M * numpy.dtype(dt).itemsize
-                    dst = out[name].view(shape=(K, M) if M > 1 else (K,), offset_bytes=i * width)
-                else:
-                    dst = out[name][i]
-                f.read_chunk_device(fr, chunk, out=dst, rows=plan, wait=False)
+                f.read_chunk_device(source[i, name], 'particles/' + name, out=fl._device_at(out[name], i), rows=plan,
+                                    wait=False)
             f.wait_read()
         out.plans = plans
         return out
 
-    def _read_logs_device(self, idx, snap, frame_of):
+    def _read_logs_device(self, idx, snap):
         f = self.file
         for log in self._names_with_prefix('log/'):
-            fr = frame_of(log)
+            fr = self._frame_of(idx, log)
             if fr is not None:
                 snap.log[log[4:]] = f.read_chunk(fr, log)
         for state in self._names_with_prefix('state/'):
             if f.chunk_exists(idx, state):
                 snap.state[state[6:]] = f.read_chunk(idx, state)
 
-    def _read_domain_device(self, idx, snap, domain, scalar4, defaults, n_global, frame_of):
+    def _read_domain_device(self, idx, snap, domain, scalar4, defaults, n_global):
         """`read_frame_device(domain=...)`: select the domain's rows from the effective position chunk, then gather every
         per-particle array through them.  One `wait_read` per group of chunks that share destination rows, so the HBM
         staging holds one or two chunks at a time, never the frame; the position chunk the selection staged serves the
         position gather (same index entry, before the group's wait).  Frame 0's device cache of slab reads is not used."""
-        torch = fl._lib._torch
         f = self.file
         if not isinstance(domain, Domain):
             domain = Domain(*domain)
         dims = int(snap.configuration.dimensions)
         box = snap.configuration.box
-
-        def effective(chunk):
-            return self._effective_frame(idx, chunk, n_global)
-
-        device = f.pipeline_device()
-        f_pos = effective('particles/position')
+        f_pos = self._effective_frame(idx, 'particles/position', n_global)
         if f_pos is not None:
             rows, count = f.select_domain_device(f_pos, 'particles/position', box, domain, dims)
         else:
             # no position anywhere: every particle sits at the origin, all of them or none are inside
             count = n_global if len(domain_rows(numpy.zeros((1, 3), numpy.float32), box, domain, dims)) else 0
-            if torch is None:
-                rows = fl.DeviceBuffer((max(count, 1),), numpy.int32, device,
-                                       pattern=numpy.arange(max(count, 1), dtype=numpy.int32)).view(shape=(count,))
-            else:
-                rows = torch.arange(count, dtype=torch.int32, device=torch.device('cuda', device))
+            rows = fl._device_from_host(numpy.arange(count, dtype=numpy.int32), f.pipeline_device())
         snap.particles.N = count
         snap.particles.N_global = n_global
         snap.part = None
@@ -1581,71 +1532,28 @@ class HOOMDTrajectory(object):
         # that shares its Scalar4 rows, gather from the chunk the selection has staged whole anyway.)
         plan = []
 
-        def gather(chunk, fr, planned=False, **kw):
-            if planned and count > 0:
-                if not plan:
-                    plan.append(f.plan_rows(rows, n_global))
-                return f.read_chunk_device(fr, chunk, rows=plan[0], wait=False, **kw)
-            return f.read_chunk_device(fr, chunk, rows=rows, N=count, wait=False, **kw)
+        def gather(fr, chunk, attr, **kw):
+            if attr in ('position', 'pos4') or count == 0:
+                return f.read_chunk_device(fr, chunk, rows=rows, N=count, wait=False, **kw)
+            if not plan:
+                plan.append(f.plan_rows(rows, n_global))
+            return f.read_chunk_device(fr, chunk, rows=plan[0], wait=False, **kw)
 
-        def empty4():
-            if torch is None:
-                return fl.DeviceBuffer((count, 4), numpy.float32, device)
-            return torch.empty((count, 4), dtype=torch.float32, device=torch.device('cuda', device))
+        # group 1: position (the staged rows of the selection) and, with scalar4, (x, y, z, typeid bits); then
+        # (vx, vy, vz, mass); then every other per-particle array: one chunk, one wait
+        groups = [('position', 'pos4'), ('vel4',)] if scalar4 else [('position',)]
+        groups += [(name,) for name in _PARTICLE_FIELDS if name != 'position']
+        self._read_particles_device(idx, snap, count, n_global, defaults, gather, groups)
 
-        # group 1: position (the staged rows of the selection) and, with scalar4, (x, y, z, typeid bits)
-        done = set()
-        if f_pos is not None:
-            snap.particles.position = gather('particles/position', f_pos)
-            done.add('position')
-        groups = [(('particles/position', 'particles/typeid', True, 0.0), 'pos4'),
-                  (('particles/velocity', 'particles/mass', False, 1.0), 'vel4')] if scalar4 else []
-        for (xyz, w, w_bitcast, w_default), attr in groups:
-            f_xyz, f_w = effective(xyz), effective(w)
-            if f_xyz is None and f_w is None:
-                row = numpy.array([0.0, 0.0, 0.0, w_default], dtype=numpy.float32)
-                if torch is None:
-                    arr = fl.DeviceBuffer((count, 4), numpy.float32, device, pattern=row)
-                else:
-                    arr = torch.zeros((count, 4), dtype=torch.float32, device=torch.device('cuda', device))
-                    arr[:, 3] = w_default
-            else:
-                arr = empty4()
-                planned = attr != 'pos4'
-                if f_xyz is not None:
-                    gather(xyz, f_xyz, planned, out=arr, columns=(0, 3), fill=w_default if f_w is None else None)
-                if f_w is not None:
-                    gather(w, f_w, planned, out=arr, columns=(3, 4), bitcast=w_bitcast,
-                           fill=0.0 if f_xyz is None else None)
-            setattr(snap.particles, attr, arr)
-            f.wait_read()
-        if not scalar4:
-            f.wait_read()
-
-        # every other per-particle array: one chunk, one wait
-        default_rows, typed = None, {}
-        for name, (dt, M) in list(_PARTICLE_SPEC.items()) + list(_PARTICLE_SPEC_EXTRA.items()):
-            if name in done:
-                continue
-            chunk = 'particles/' + name
-            fr = effective(chunk)
-            if fr is not None:
-                setattr(snap.particles, name, gather(chunk, fr, True))
-                f.wait_read()
-            elif defaults and name in snap.particles._default_value:
-                if default_rows is None:
-                    default_rows = self._default_rows_template(device).clone()
-                off, words, ndt = self._default_rows_layout[name]
-                if torch is None:
-                    view = default_rows.view(dtype=ndt, shape=(count, M) if M > 1 else (count,),
-                                             strides=(0, ndt.itemsize) if M > 1 else (0,), offset_bytes=4 * off)
-                else:
-                    tdt = getattr(torch, ndt.name)
-                    base = typed.get(tdt)
-                    if base is None:
-                        base = typed[tdt] = default_rows.view(tdt)
-                    view = base.as_strided((count, M) if M > 1 else (count,), (0, 1) if M > 1 else (0,), off)
-                setattr(snap.particles, name, view)
+    def _frame_of(self, idx, chunk):
+        """The frame whose copy of a chunk that is NOT per-particle (box, N, types, log/*) frame ``idx`` reads: its
+        own, else frame 0's, else ``None``."""
+        f = self.file
+        if f.chunk_exists(idx, chunk):
+            return idx
+        if f.chunk_exists(0, chunk):
+            return 0
+        return None
 
     def _effective_frame(self, idx, chunk, n_global):
         """The frame whose copy of a per-particle chunk frame ``idx`` (of ``n_global`` particles) reads: its own, else
@@ -1661,21 +1569,16 @@ class HOOMDTrajectory(object):
     def _default_rows_template(self, device):
         """All default rows of the SPH schema as ONE int32 device array (every element type of the schema is four
         bytes wide), built once per trajectory and device; `_default_rows_layout[name]` = (first word, words, numpy
-        dtype).  `read_frame_device` clones it per read and hands out views of the clone.  A torch tensor where torch
-        is importable, the library's own device memory otherwise."""
+        dtype).  `_read_particles_device` clones it per read and hands out views of the clone."""
         cached = getattr(self, '_default_rows_cache', None)
         if cached is not None and cached[0] == device:
             return cached[1]
         words, layout = [], {}
-        for name, (dt, M) in _PARTICLE_SPEC.items():
-            row = numpy.ascontiguousarray(numpy.broadcast_to(numpy.asarray(ParticleData._default_value[name], dtype=dt), (M,)))
-            layout[name] = (len(words), M, numpy.dtype(dt))
-            words += row.view(numpy.int32).tolist()
-        torch = fl._lib._torch
-        if torch is None:
-            template = fl.DeviceBuffer((len(words),), numpy.int32, device, pattern=numpy.array(words, dtype=numpy.int32))
-        else:
-            template = torch.tensor(words, dtype=torch.int32, device=torch.device('cuda', device))
+        for name, (dt, M, default, upstream) in _PARTICLE_FIELDS.items():
+            if not upstream:
+                layout[name] = (len(words), M, numpy.dtype(dt))
+                words += numpy.ascontiguousarray(numpy.broadcast_to(default, (M,))).view(numpy.int32).tolist()
+        template = fl._device_from_host(numpy.array(words, dtype=numpy.int32), device)
         self._default_rows_layout = layout
         self._default_rows_cache = (device, template)
         return template

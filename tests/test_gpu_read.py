@@ -463,3 +463,49 @@ def test_read_frame_device_scalar4_without_mass_and_typeid_chunks(tmp_gsd):
         s = t.read_frame_device(0, part=(1000, 2345), scalar4=True)
         v4 = s.particles.vel4.cpu().numpy()
         assert v4.shape == (2345, 4) and v4[:, :3].tobytes() == vel[1000:3345].tobytes() and (v4[:, 3] == 1.0).all()
+
+
+@pytest.mark.parametrize("with_position", [False, True])
+@pytest.mark.parametrize("n1", [3_001, 5_003])
+def test_read_frame_device_scalar4_when_particle_count_differs_from_frame0(tmp_gsd, n1, with_position):
+    """Frame 0 holds position, velocity, mass and typeid of N0 particles; frame 1 has another particle count and stores
+    only N (or N and position).  Frame 0's arrays do not stand in for a frame of another N (hoomd.py:858-884): pos4 and
+    vel4 are built from the same effective chunks as position, typeid, velocity and mass -- the stored position or
+    the defaults -- for a slab read and for a domain read of the whole box, and equal the host reader's frame.
+    Copies: exact equality."""
+    import pgsd.hoomd as hoomd
+    N0 = 4_099
+    rng = np.random.default_rng(n1)
+    with hoomd.open(tmp_gsd, 'w') as t:
+        fr = hoomd.Frame()
+        fr.particles.N = N0
+        fr.particles.position = rng.uniform(-0.4, 0.4, (N0, 3)).astype(np.float32)
+        fr.particles.velocity = rng.standard_normal((N0, 3)).astype(np.float32)
+        fr.particles.mass = rng.uniform(1.5, 2.5, N0).astype(np.float32)
+        fr.particles.typeid = rng.integers(1, 5, N0).astype(np.uint32)
+        t.append(fr)
+        fr = hoomd.Frame()
+        fr.particles.N = n1
+        if with_position:
+            fr.particles.position = rng.uniform(-0.4, 0.4, (n1, 3)).astype(np.float32)
+        t.append(fr)
+    with hoomd.open(tmp_gsd, 'r') as t:
+        assert t.file.chunk_exists(1, 'particles/N') and t.file.chunk_exists(1, 'particles/position') == with_position
+        for name in ('velocity', 'mass', 'typeid'):
+            assert t.file.chunk_exists(0, 'particles/' + name) and not t.file.chunk_exists(1, 'particles/' + name)
+        host = t[1].particles
+        assert host.N == n1
+        for kw in ({}, {'domain': hoomd.Domain((0, 0, 0), (1, 1, 1))}):
+            p = t.read_frame_device(1, scalar4=True, **kw).particles
+            assert p.N == n1
+            got = dict((name, getattr(p, name).cpu().numpy())
+                       for name in ('position', 'typeid', 'velocity', 'mass', 'pos4', 'vel4'))
+            assert got['pos4'].shape == (n1, 4) and got['vel4'].shape == (n1, 4)
+            assert got['pos4'][:, :3].tobytes() == got['position'].tobytes()
+            assert got['pos4'][:, 3].tobytes() == got['typeid'].tobytes()
+            assert got['vel4'][:, :3].tobytes() == got['velocity'].tobytes()
+            assert got['vel4'][:, 3].tobytes() == got['mass'].tobytes()
+            for name in ('position', 'typeid', 'velocity', 'mass'):
+                want = getattr(host, name)
+                assert got[name].dtype == want.dtype and got[name].shape == want.shape
+                assert np.ascontiguousarray(got[name]).tobytes() == want.tobytes(), (name, kw)
