@@ -17,7 +17,7 @@
 //                                                 the on-disk index is relocated)
 //   MPI_File_write_at                           pwrite at the identical offset, split over a
 //                                                 writer pool; device chunks arrive through
-//                                                 the HIP pipeline (pgsd_device.cpp)
+//                                                 the HIP pipeline (pgsd_device*.cpp)
 //
 // Chunk placement lives in pgsd_placement.cpp, lookups and reads in pgsd_read.cpp; pgsd_file_impl.hpp holds the state
 // they share.

@@ -1,0 +1,495 @@
+// pgsd_device_read.cpp -- the read side of the device pipeline: file -> pinned slab (pread, shared reader threads) ->
+// HBM staging (H2D on the copy stream) -> one deferred unpack launch per wait_read(); the direct road of small reads;
+// sparse (planned) reads, indexed reads and domain selection on top of the same staging.
+#include "pgsd_device_impl.hpp"
+
+#include <cerrno>
+#include <cstdlib>
+#include <cstring>
+
+namespace pgsd_amd
+    {
+// ---- the reader engine of a device ----
+static std::mutex& registry_mutex()
+    {
+    static std::mutex mu;
+    return mu;
+    }
+
+static std::vector<ReadEngine*>& registry()
+    {
+    static std::vector<ReadEngine*> r;
+    return r;
+    }
+
+int ReadEngine::get_slab()
+    {
+    std::unique_lock<std::mutex> lk(m);
+    cv.wait(lk, [this] { return !free_slabs.empty(); });
+    int si = (int)free_slabs.front();
+    free_slabs.pop_front();
+    return si;
+    }
+
+void ReadEngine::put_slab(int si)
+    {
+        {
+        std::lock_guard<std::mutex> g(m);
+        free_slabs.push_back((uint32_t)si);
+        }
+    cv.notify_one();
+    }
+
+ReadEngine* ReadEngine::acquire(int device, const cpu_set_t* cpus, hipError_t* err)
+    {
+    std::lock_guard<std::mutex> g(registry_mutex());
+    for (ReadEngine* e : registry())
+        if (e->device == device)
+            {
+            e->refs++;
+            return e;
+            }
+    std::unique_ptr<ReadEngine> e(new ReadEngine);
+    e->device = device;
+    // Reads of the page cache take no exclusive lock and scale with threads; pieces smaller
+    // than the write slabs keep all of them busy on one chunk and start the H2D copies
+    // earlier (profiles/r01_read_sweep.log: 16 readers x 4 MiB pieces beat 8 x 16 MiB by 20-40 %).
+    unsigned n = 16;
+    if (const char* v = getenv("PGSD_READERS"))
+        n = (unsigned)atoi(v) > 0 ? (unsigned)atoi(v) : n;
+    if (const char* v = getenv("PGSD_READ_PIECE_MIB"))
+        e->piece = (size_t)(atoi(v) > 0 ? atoi(v) : 4) << 20;
+    e->slabs.resize((size_t)n * 2);
+    *err = hipSuccess;
+    run_on_gpu_node(device, cpus, // first touch on the GPU's node, like the write ring
+                    [&]
+                    {
+                        for (auto& s : e->slabs)
+                            {
+                            hipError_t rc = s.alloc(e->piece);
+                            if (rc != hipSuccess && *err == hipSuccess)
+                                *err = rc;
+                            }
+                    });
+    if (*err != hipSuccess)
+        {
+        for (auto& s : e->slabs)
+            s.free();
+        return nullptr;
+        }
+    for (uint32_t i = 0; i < e->slabs.size(); i++)
+        e->free_slabs.push_back(i);
+    e->pool = writer_pool_create(n, cpus);
+    e->refs = 1;
+    registry().push_back(e.get());
+    return e.release();
+    }
+
+void ReadEngine::release(ReadEngine* e)
+    {
+        {
+        std::lock_guard<std::mutex> g(registry_mutex());
+        if (--e->refs > 0)
+            return;
+        auto& r = registry();
+        for (size_t i = 0; i < r.size(); i++)
+            if (r[i] == e)
+                r.erase(r.begin() + (long)i);
+        }
+    if (e->pool)
+        writer_pool_destroy(e->pool); // joins the readers (no pipeline has work queued any more)
+    (void)hipSetDevice(e->device);
+    for (auto& s : e->slabs)
+        s.free();
+    delete e;
+    }
+
+// ---- requests ----
+std::shared_ptr<DevicePipeline::ReadReq> DevicePipeline::make_read_req(const pgsd_unpack_job& job, uint64_t N,
+                                                                       const uint32_t* rows, uint64_t src_N, bool stage_only,
+                                                                       size_t pieces)
+    {
+    auto req = std::make_shared<ReadReq>();
+    req->job = job;
+    req->N = N;
+    req->pieces_left = pieces;
+    req->rows = rows;
+    req->src_N = src_N;
+    req->stage_only = stage_only;
+    return req;
+    }
+
+// The request's bytes are staged (or its copies enqueued, all_copied behind them).  The unpack itself is deferred to
+// wait_read(): the chunks of a frame then go through ONE launch in which chunks restoring the same array are assembled
+// into whole rows.
+void DevicePipeline::defer_unpack(const std::shared_ptr<ReadReq>& req)
+    {
+    if (req->stage_only)
+        return;
+    std::lock_guard<std::mutex> g(m_copy_mutex);
+    m_unpack_pending.push_back(req);
+    }
+
+// n_spans file ranges into base + their stage_offset, each in one go (EINTR retried); stops at the first one the file
+// does not fill -- it is shorter than its index claims.  Returns the bytes read, which are counted.
+size_t DevicePipeline::pread_spans(const ReadSpan* spans, size_t n_spans, char* base)
+    {
+    size_t total = 0;
+    for (size_t k = 0; k < n_spans; k++)
+        {
+        const ReadSpan& sp = spans[k];
+        size_t got = 0;
+        while (got < sp.bytes)
+            {
+            ssize_t r = io_pread(m_fd, base + sp.stage_offset + got, sp.bytes - got, sp.file_offset + (long long)got);
+            if (r < 0 && errno == EINTR)
+                continue;
+            if (r <= 0)
+                break;
+            got += (size_t)r;
+            }
+        total += got;
+        if (got != sp.bytes)
+            break;
+        }
+    m_pread_bytes += total;
+    return total;
+    }
+
+int DevicePipeline::read_submit(long long file_offset, size_t bytes, pgsd_unpack_job job, uint64_t N, const uint32_t* rows,
+                                uint64_t src_N)
+    {
+    const ReadSpan whole = {file_offset, bytes, 0};
+    return read_submit_spans(&whole, 1, bytes, job, N, rows, src_N, false, nullptr);
+    }
+
+// `bytes` of staging filled from n_spans file ranges that follow each other in it without gaps (a whole chunk: one
+// span at 0; a sparse read: the touched runs)
+int DevicePipeline::read_submit_spans(const ReadSpan* spans, size_t n_spans, size_t bytes, pgsd_unpack_job job, uint64_t N,
+                                      const uint32_t* rows, uint64_t src_N, bool stage_only, std::shared_ptr<ReadReq>* out)
+    {
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    const size_t padded = pad256(bytes);
+    if (bytes > 0 && bytes <= m_direct_max && direct_reserve(padded))
+        {
+        // Small read, the short road (twin of the direct write path): THIS thread preads the rows straight
+        // into the pinned, device-mapped arena and the unpack kernel fetches them from there over PCIe --
+        // no reader-thread hand-over, no host->device copy, no staging in HBM.  For a frame of a few
+        // thousand particles those fixed costs were ten times the read itself.
+        char* host = m_res.dhost + m_dused;
+        job.src = m_res.ddev + m_dused;
+        m_dused += padded;
+        TraceRange tr("pgsd:pread_direct file_off=%llu bytes=%llu", (unsigned long long)spans[0].file_offset, bytes);
+        if (pread_spans(spans, n_spans, host) != bytes)
+            {
+            fail("pread returned fewer bytes than the chunk holds", true);
+            return PGSD_SUCCESS; // reported by pgsd_device_wait_read, like the threaded path
+            }
+        auto req = make_read_req(job, N, rows, src_N, stage_only, 0);
+        if (out)
+            *out = req;
+        defer_unpack(req);
+        return PGSD_SUCCESS;
+        }
+    void* stage = nullptr;
+    rc = arena_alloc(bytes, &stage);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    job.src = stage;
+    if (!m_reader)
+        {
+        hipError_t rerr = hipSuccess;
+        m_reader = ReadEngine::acquire(m_cfg.device, m_numa ? &m_numa_cpus : nullptr, &rerr);
+        if (!m_reader)
+            HIP_TRY(rerr);
+        }
+    const size_t piece = m_reader->piece;
+    // The pieces are cut along the STAGING: a piece of a sparse read holds many short runs, each pread into its place in
+    // the slab, and goes to HBM in one copy (a piece per run cost 17 us each; 1 000 runs of 48 KB took as long as two
+    // thirds of the whole chunk).
+    auto req = make_read_req(job, N, rows, src_N, stage_only, (bytes + piece - 1) / piece);
+    if (out)
+        *out = req;
+    if (req->pieces_left == 0)
+        {
+        // (a sparse read none of whose rows lies in the chunk: nothing to stage, the gather still refuses them)
+        defer_unpack(req);
+        return PGSD_SUCCESS;
+        }
+    req->all_copied = get_event(false);
+    if (!req->all_copied)
+        return PGSD_ERROR_DEVICE;
+    std::unique_lock<std::mutex> lk(m_mutex);
+    m_reads_outstanding += req->pieces_left; // counted per piece: see read_piece()
+    lk.unlock();
+    size_t k = 0;
+    for (size_t off = 0; off < bytes; off += piece)
+        {
+        const size_t n = std::min(piece, bytes - off);
+        char* dst = (char*)stage + off;
+        // the parts of the spans that fall into [off, off + n), placed relative to the piece
+        auto parts = std::make_shared<std::vector<ReadSpan>>();
+        while (k < n_spans && spans[k].stage_offset + spans[k].bytes <= off)
+            k++;
+        for (size_t j = k; j < n_spans && spans[j].stage_offset < off + n; j++)
+            {
+            const size_t a = std::max(spans[j].stage_offset, off);
+            const size_t b = std::min(spans[j].stage_offset + spans[j].bytes, off + n);
+            if (b > a)
+                parts->push_back({spans[j].file_offset + (long long)(a - spans[j].stage_offset), b - a, a - off});
+            }
+        writer_pool_submit(m_reader->pool, [this, req, dst, n, parts] { read_piece(req, dst, n, parts); });
+        }
+    return PGSD_SUCCESS;
+    }
+
+// Sparse indexed read: the touched runs of the plan are read (same reader threads, pinned ring and piece size) and
+// land at slot * R rows of a staging of plan.staged_rows rows; wait_read's deferred launch gathers through rows2.
+int DevicePipeline::read_planned_submit(long long chunk_offset, size_t row_bytes, pgsd_unpack_job job, const RowPlan& plan)
+    {
+    std::vector<ReadSpan> spans(plan.run_first.size());
+    uint64_t slot = 0;
+    for (size_t i = 0; i < spans.size(); i++)
+        {
+        const uint64_t row0 = (uint64_t)plan.run_first[i] * plan.R;
+        const uint64_t nrows = std::min<uint64_t>((uint64_t)plan.run_blocks[i] * plan.R, plan.N - row0);
+        spans[i] = {chunk_offset + (long long)(row0 * row_bytes), (size_t)(nrows * row_bytes),
+                    (size_t)(slot * plan.R * row_bytes)};
+        slot += plan.run_blocks[i];
+        }
+    return read_submit_spans(spans.data(), spans.size(), (size_t)(plan.staged_rows * row_bytes), job, plan.n, plan.rows2,
+                             plan.staged_rows, false, nullptr);
+    }
+
+// Row plan: mark / scan / remap on the pack stream, behind what the caller's stream still does with the row list.
+int DevicePipeline::plan_rows(RowPlan& plan, std::string* err)
+    {
+    int rc = enter();
+    if (rc == PGSD_SUCCESS)
+        rc = order_after_source();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = launch_row_plan(plan, m_res.pack_stream, err);
+    if (rc == PGSD_ERROR_DEVICE && err)
+        fail(*err);
+    return rc;
+    }
+
+// Indexed read: the whole chunk is staged as for a slab read -- or, when it is the position chunk the last
+// select_domain() staged (same file range, no wait_read since), taken from that staging without reading the file
+// again -- and wait_read's deferred launch gathers rows[0 .. n) of it.
+int DevicePipeline::read_rows_submit(long long file_offset, size_t bytes, pgsd_unpack_job job, uint64_t src_N,
+                                     const uint32_t* rows, uint64_t n)
+    {
+    if (!(m_kept_src && m_kept_offset == file_offset && m_kept_bytes == bytes))
+        return read_submit(file_offset, bytes, job, n, rows, src_N);
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    job.src = m_kept_src;
+    defer_unpack(make_read_req(job, n, rows, src_N, false, 0)); // (select_domain() synchronised the copies)
+    return PGSD_SUCCESS;
+    }
+
+// Domain selection: stage the position chunk (file -> pinned -> HBM, or the direct road), select on the pack stream,
+// synchronise.  The staged rows are kept until the next wait_read for an indexed read of the same chunk.
+int DevicePipeline::select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count)
+    {
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (m_kept_src && m_kept_offset == file_offset && m_kept_bytes == bytes)
+        d.pos = m_kept_src;
+    else
+        {
+        std::shared_ptr<ReadReq> req;
+        pgsd_unpack_job job;
+        memset(&job, 0, sizeof(job));
+        const ReadSpan whole = {file_offset, bytes, 0};
+        rc = read_submit_spans(&whole, 1, bytes, job, d.N, nullptr, 0, true, &req);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        std::unique_lock<std::mutex> lk(m_mutex);
+        m_cv_done.wait(lk, [this] { return m_reads_outstanding == 0; });
+        lk.unlock();
+        if (failed() || !req)
+            return failure_code();
+        if (req->all_copied)
+            HIP_TRY(hipStreamWaitEvent(m_res.pack_stream, req->all_copied, 0));
+        d.pos = req->job.src;
+        }
+    // the row list belongs to the caller: what its stream still does with that memory comes first
+    rc = order_after_source();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    std::string err;
+    rc = launch_select_domain(d, out_rows, out_count, m_res.pack_stream, &err);
+    if (rc == PGSD_ERROR_DEVICE)
+        fail(err);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    m_kept_src = d.pos;
+    m_kept_offset = file_offset;
+    m_kept_bytes = bytes;
+    return PGSD_SUCCESS;
+    }
+
+int DevicePipeline::wait_read()
+    {
+    if (!m_ok)
+        return PGSD_SUCCESS;
+    std::unique_lock<std::mutex> lk(m_mutex);
+    m_cv_done.wait(lk, [this] { return m_reads_outstanding == 0; });
+    lk.unlock();
+    (void)hipSetDevice(m_cfg.device);
+    launch_pending_unpacks();
+    hipError_t e = m_copy_used.exchange(false) ? hipStreamSynchronize(m_res.copy_stream) : hipSuccess;
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(m_res.pack_stream);
+    if (e != hipSuccess)
+        fail(std::string("stream synchronize: ") + hipGetErrorString(e));
+    // an indexed read met a row outside its chunk: nothing was written for it (the pipeline itself is fine)
+    const bool bad_rows = m_bad_host && __atomic_exchange_n(m_bad_host, 0u, __ATOMIC_ACQ_REL) != 0;
+    m_kept_src = nullptr; // the staging select_domain() kept is given up with every wait, recycled or not
+    bool writes_idle;
+        {
+        std::lock_guard<std::mutex> g(m_mutex);
+        writes_idle = m_outstanding == 0;
+        }
+    if (writes_idle && !staged_open() && !direct_pending())
+        reset_staging();
+    if (failed())
+        return failure_code();
+    return bad_rows ? PGSD_ERROR_INVALID_ARGUMENT : PGSD_SUCCESS;
+    }
+
+// all chunks whose H2D copies are enqueued: one unpack launch per distinct row count, behind the copies
+void DevicePipeline::launch_pending_unpacks()
+    {
+    std::vector<std::shared_ptr<ReadReq>> pending;
+        {
+        std::lock_guard<std::mutex> g(m_copy_mutex);
+        pending.swap(m_unpack_pending);
+        }
+    while (!pending.empty() && !failed())
+        {
+        const uint64_t N = pending.front()->N;
+        const uint32_t* rows = pending.front()->rows;
+        const uint64_t src_N = pending.front()->src_N;
+        std::vector<pgsd_unpack_job> jobs;
+        std::vector<std::shared_ptr<ReadReq>> rest;
+        hipError_t e = hipSuccess;
+        if (rows && !m_bad_host)
+            {
+            void* alias = nullptr;
+            e = hipHostMalloc((void**)&m_bad_host, sizeof(uint32_t), hipHostMallocMapped);
+            if (e == hipSuccess)
+                e = hipHostGetDevicePointer(&alias, m_bad_host, 0);
+            if (e == hipSuccess)
+                {
+                *m_bad_host = 0;
+                m_bad_dev = (uint32_t*)alias;
+                }
+            }
+        for (auto& r : pending)
+            {
+            if (r->N != N || r->rows != rows || r->src_N != src_N)
+                {
+                rest.push_back(r);
+                continue;
+                }
+            jobs.push_back(r->job);
+            if (e == hipSuccess && r->all_copied) // (direct reads have no copy to wait for)
+                e = hipStreamWaitEvent(m_res.pack_stream, r->all_copied, 0);
+            }
+        std::string err;
+        if (e != hipSuccess)
+            fail(std::string("read pipeline event: ") + hipGetErrorString(e));
+        // The destinations belong to the caller: whatever its stream still has in flight on them
+        // (a caching allocator hands out blocks whose previous owner may not have finished) comes
+        // first, exactly as the pack waits for the producers of its sources.
+        // (a failure of which is recorded by order_after_source() itself)
+        else if (order_after_source() == PGSD_SUCCESS
+                 && launch_unpack((uint32_t)jobs.size(), jobs.data(), N, m_res.pack_stream, &err, rows, src_N,
+                                  rows ? m_bad_dev : nullptr) != PGSD_SUCCESS)
+            fail(err);
+        pending.swap(rest);
+        }
+    }
+
+// one piece of a request's staging: the file ranges `parts`, each at its stage_offset within the piece, make up its
+// n bytes
+void DevicePipeline::read_piece(std::shared_ptr<ReadReq> req, char* dst, size_t n,
+                                std::shared_ptr<std::vector<ReadSpan>> parts)
+    {
+    (void)hipSetDevice(m_cfg.device);
+    ReadEngine* const reader = m_reader; // the engine may outlive this pipeline, not the other way round
+    const int si = failed() ? -1 : reader->get_slab();
+    bool ok = si >= 0;
+    if (ok)
+        {
+        const long long foff = parts->empty() ? 0 : parts->front().file_offset;
+        TraceRange tr("pgsd:pread file_off=%llu bytes=%llu", (unsigned long long)foff, n);
+        if (pread_spans(parts->data(), parts->size(), reader->slabs[(size_t)si].host) != n)
+            {
+            fail("pread returned fewer bytes than the chunk holds", true);
+            ok = false;
+            }
+        }
+    bool complete = false;
+        {
+        std::lock_guard<std::mutex> g(m_copy_mutex);
+        if (ok)
+            {
+            PinnedSlab& s = reader->slabs[(size_t)si];
+            m_copy_used.store(true);
+            m_h2d_bytes += n;
+            hipError_t e = hipMemcpyAsync(dst, s.host, n, hipMemcpyHostToDevice, m_res.copy_stream);
+            if (e == hipSuccess)
+                e = hipEventRecord(s.copied, m_res.copy_stream);
+            if (e != hipSuccess)
+                {
+                fail(std::string("hipMemcpyAsync H2D: ") + hipGetErrorString(e));
+                ok = false;
+                }
+            }
+        if (--req->pieces_left == 0 && !failed())
+            {
+            // every piece of this chunk has been enqueued on the copy stream before this point
+            hipError_t e = hipEventRecord(req->all_copied, m_res.copy_stream);
+            if (e != hipSuccess)
+                fail(std::string("read pipeline event: ") + hipGetErrorString(e));
+            complete = e == hipSuccess;
+            }
+        }
+    if (complete)
+        defer_unpack(req);
+    if (si >= 0)
+        {
+        if (ok)
+            (void)hipEventSynchronize(reader->slabs[(size_t)si].copied);
+        reader->put_slab(si);
+        }
+    // Last touch of the pipeline by this piece: the destructor (and wait_read) wait for the count
+    // of PIECES to reach zero, so no straggler of a finished chunk is left behind.
+    read_done();
+    }
+
+void DevicePipeline::read_done()
+    {
+    std::lock_guard<std::mutex> g(m_mutex);
+    if (m_reads_outstanding > 0)
+        m_reads_outstanding--;
+    m_cv_done.notify_all();
+    }
+
+void DevicePipeline::read_counters(uint64_t* pread_bytes, uint64_t* h2d_bytes, int reset)
+    {
+    if (pread_bytes)
+        *pread_bytes = reset ? m_pread_bytes.exchange(0) : m_pread_bytes.load();
+    if (h2d_bytes)
+        *h2d_bytes = reset ? m_h2d_bytes.exchange(0) : m_h2d_bytes.load();
+    }
+    } // namespace pgsd_amd

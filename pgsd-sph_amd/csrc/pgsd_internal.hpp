@@ -105,7 +105,7 @@ int pwrite_full(int fd, const void* buf, size_t bytes, long long offset);
 void pread_some(int fd, void* buf, size_t bytes, long long offset);
 void pread_parallel(int fd, void* buf, size_t bytes, long long offset); // >= 64 MiB: a few threads
 
-// ---- device pipeline (pgsd_device.cpp); created lazily by the first device call ----
+// ---- device pipeline (pgsd_device.cpp, pgsd_device_write.cpp, pgsd_device_read.cpp); created lazily by the first device call ----
 class DevicePipeline;
 struct DeviceChunk
     {
