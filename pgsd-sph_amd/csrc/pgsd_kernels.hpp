@@ -1,7 +1,8 @@
-// pgsd_kernels.hpp -- what the three kernel translation units of libpgsd_amd.so share (round 5: pgsd_pack.hip was one
-// 2 600-line file): pgsd_pack.hip (pack: LDS-tiled, row-per-lane, copy and generic kernels + their launcher),
-// pgsd_unpack.hip (the read path's inverse kernels + launcher) and pgsd_select.hip (chunk comparison, stream compaction,
-// library-owned device memory).  Device helpers are header-only; the few host helpers are defined in pgsd_pack.hip.
+// pgsd_kernels.hpp -- what the kernel translation units of libpgsd_amd.so share: pgsd_pack.hip (pack: LDS-tiled,
+// row-per-lane, copy and generic kernels + their planners), pgsd_unpack.hip (the read path's inverse kernels + planners)
+// and pgsd_select.hip (chunk comparison, stream compaction, library-owned device memory).  Device helpers are header-only
+// and seen by the HIP compiler alone; the host helpers, the tuning variables and the tables of instantiated launch
+// shapes are shared with pgsd_kernels.cpp (host compiler), which defines everything here that is not a kernel.
 #ifndef PGSD_KERNELS_HPP
 #define PGSD_KERNELS_HPP
 
@@ -9,8 +10,10 @@
 #include "pgsd_pack.hpp"
 #include "pgsd_private.h"
 
+#ifdef __HIP__
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#endif
 
 #include <algorithm>
 #include <cstdlib>
@@ -21,14 +24,24 @@
 #include <mutex>
 #include <vector>
 
+// The (threads, rows per lane) pairs the row-per-lane kernels are instantiated for, ONE list per direction: the
+// validation of PGSD_PACK_ROWS_CFG / PGSD_UNPACK_ROWS_CFG, the text of its message and the dispatch all expand it.
+#define PGSD_PACK_ROWS_SHAPES(X) X(64, 2) X(128, 1) X(128, 2) X(256, 1) X(256, 2) X(256, 4) X(256, 8) X(512, 2) X(512, 4)
+#define PGSD_UNPACK_ROWS_SHAPES(X) X(64, 2) X(128, 1) X(128, 2) X(256, 1) X(256, 2)
+#define PGSD_SHAPE_IS(T, U) || (t == T && u == U)
+#define PGSD_SHAPE_TEXT(T, U) " " #T "x" #U
+
 namespace pgsd_amd
     {
 #define PACK_THREADS 256
 
+#ifdef __HIP__
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------ device helpers
-
+// Source tiles are read once and chunk tiles written once: every global access of the kernels is a
+// __builtin_nontemporal_load / _store.  (Round 1 swept LDS-DMA staging, default cache policies and a linear LDS image as
+// compile-time variants: none was better, profiles/r01_pack_sweep.jsonl; the variants were removed in round 2.)
 template<int SSZ> __device__ __forceinline__ uint64_t lds_load(const char* p)
     {
     if constexpr (SSZ == 1)
@@ -103,17 +116,35 @@ __device__ __forceinline__ uint32_t lds_skew(uint32_t byte_off)
     return byte_off + ((byte_off >> 7) << 4);
     }
 
-// source tiles are read once and chunk tiles written once: non-temporal on both sides.  (Round 1 swept
-// LDS-DMA staging, default cache policies and a linear LDS image as compile-time variants: none was better,
-// profiles/r01_pack_sweep.jsonl; the variants were removed in round 2.)
-__device__ __forceinline__ u32x4 stream_load(const u32x4* p)
+// convert_elem for sizes known at run time only (the element-per-lane fallbacks): 1-, 2-, 4-byte -> 4 / 8, 8 -> 4 / 8
+__device__ __forceinline__ uint64_t convert_any(uint64_t raw, uint32_t ssz, uint32_t dsz, uint32_t kind)
     {
-    return __builtin_nontemporal_load(p);
+    switch (ssz)
+        {
+        case 1: return dsz == 8 ? convert_elem<1, 8>(raw, kind) : convert_elem<1, 4>(raw, kind);
+        case 2: return dsz == 8 ? convert_elem<2, 8>(raw, kind) : convert_elem<2, 4>(raw, kind);
+        case 4: return dsz == 8 ? convert_elem<4, 8>(raw, kind) : convert_elem<4, 4>(raw, kind);
+        default: return dsz == 4 ? convert_elem<8, 4>(raw, kind) : convert_elem<8, 8>(raw, kind);
+        }
     }
 
-__device__ __forceinline__ void stream_store(u32x4 v, u32x4* p)
+// the low dsz bytes of val as one element at p
+__device__ __forceinline__ void store_elem(char* p, uint64_t val, uint32_t dsz)
     {
-    __builtin_nontemporal_store(v, p);
+    if (dsz == 8)
+        *(uint64_t*)p = val;
+    else if (dsz == 4)
+        *(uint32_t*)p = (uint32_t)val;
+    else if (dsz == 2)
+        *(uint16_t*)p = (uint16_t)val;
+    else
+        *(uint8_t*)p = (uint8_t)val;
+    }
+
+// rows of the tile that starts at row0: TILE, or what is left of N
+__device__ __forceinline__ uint32_t tile_rows_at(uint64_t N, uint64_t row0, uint32_t TILE)
+    {
+    return (uint32_t)((N - row0 < (uint64_t)TILE) ? N - row0 : TILE);
     }
 
 // ------------------------------------------------------------------ rows in registers (row-per-lane kernels, both directions)
@@ -221,10 +252,46 @@ __device__ __forceinline__ void row_store(uint32_t* p, const uint32_t (&w)[ROWS_
         __builtin_nontemporal_store(w[0], p);
     }
 
-// ------------------------------------------------------------------ host side, shared (definitions: pgsd_pack.hip)
+#endif // __HIP__
+
+// ------------------------------------------------------------------ host side, shared (definitions: pgsd_kernels.cpp)
 // element conversion class PACK_* of (source type, chunk type, bitcast)
 uint32_t conv_kind(uint32_t src_type, uint32_t dst_type, uint32_t bitcast);
 int num_cus();
+
+// ceil(2^32 / M): row = e / M by multiply-high in the kernels, exact for e < 2^32 / M (0 when M == 1: not used)
+uint32_t div_magic(uint32_t M);
+
+// Rows per tile of an LDS-tiled launch: the largest power of two in [16, tile_cap] at which `rowbytes` (the widest source
+// row of a pack batch, the summed chunk rows of an unpack) still fit lds_budget; and the tiles that cover N rows.
+struct TileGeometry
+    {
+    uint32_t tile_rows;
+    uint64_t n_tiles;
+    };
+TileGeometry tile_geometry(uint64_t N, uint32_t rowbytes, uint32_t tile_cap, size_t lds_budget);
+
+// Workgroups of an LDS-tiled launch: one per tile, at most per_cu per CU and never more per CU than the 160 KiB of LDS
+// admit -- the surplus would queue behind the resident ones and run as a ragged second wave.
+uint64_t blocks_for(uint64_t n_tiles, size_t lds_bytes, uint64_t per_cu);
+
+// a launcher's way out: the message where the caller wants one, and the pgsd_error
+inline int launch_fail(std::string* err, int rc, const std::string& what)
+    {
+    if (err)
+        *err = what;
+    return rc;
+    }
+
+inline bool pack_rows_shape_known(int t, int u)
+    {
+    return false PGSD_PACK_ROWS_SHAPES(PGSD_SHAPE_IS);
+    }
+
+inline bool unpack_rows_shape_known(int t, int u)
+    {
+    return false PGSD_UNPACK_ROWS_SHAPES(PGSD_SHAPE_IS);
+    }
 
 // ---- tuning knobs: the PGSD_PACK_* / PGSD_UNPACK_* variables of the sweeps in tools/ (pack_bench.py, unpack_bench.py).
 // Read ONCE, when the first launch needs them; pgsd_reload_tuning() (pgsd_private.h) reads them again for tools
@@ -245,6 +312,7 @@ struct PackTuning
     };
 
 PackTuning tuning();
+void reload_pack_tuning();
     } // namespace pgsd_amd
 
 #endif

@@ -75,7 +75,7 @@ __device__ __forceinline__ void emit_tile(const PackOut& o, const char* lds, uin
                 }
             }
         u32x4 out = {w[0], w[1], w[2], w[3]};
-        stream_store(out, (u32x4*)(gdst + (size_t)v * 16));
+        __builtin_nontemporal_store(out, (u32x4*)(gdst + (size_t)v * 16));
         }
     // ragged end of the last tile: element-wise
     for (uint32_t e = nvec * EPT + tid; e < nelem; e += NT)
@@ -84,15 +84,7 @@ __device__ __forceinline__ void emit_tile(const PackOut& o, const char* lds, uin
         uint32_t col = e - row * M;
         uint64_t raw = lds_load<SSZ>(lds + lds_skew((row * stride_elems + col0 + col) * SSZ));
         uint64_t val = convert_elem<SSZ, DSZ>(raw, kind);
-        char* p = gdst + (size_t)e * DSZ;
-        if constexpr (DSZ == 8)
-            *(uint64_t*)p = val;
-        else if constexpr (DSZ == 4)
-            *(uint32_t*)p = (uint32_t)val;
-        else if constexpr (DSZ == 2)
-            *(uint16_t*)p = (uint16_t)val;
-        else
-            *(uint8_t*)p = (uint8_t)val;
+        store_elem(gdst + (size_t)e * DSZ, val, DSZ);
         }
     }
 
@@ -155,17 +147,17 @@ __device__ __forceinline__ void stage_rows(const PackGroup& g, char* lds, uint32
             // four independent 16-byte loads in flight per lane
             for (; v + 3 * NT < nvec; v += 4 * NT)
                 {
-                u32x4 a = stream_load((const u32x4*)gsrc + v);
-                u32x4 b = stream_load((const u32x4*)gsrc + v + NT);
-                u32x4 c = stream_load((const u32x4*)gsrc + v + 2 * NT);
-                u32x4 d = stream_load((const u32x4*)gsrc + v + 3 * NT);
+                u32x4 a = __builtin_nontemporal_load((const u32x4*)gsrc + v);
+                u32x4 b = __builtin_nontemporal_load((const u32x4*)gsrc + v + NT);
+                u32x4 c = __builtin_nontemporal_load((const u32x4*)gsrc + v + 2 * NT);
+                u32x4 d = __builtin_nontemporal_load((const u32x4*)gsrc + v + 3 * NT);
                 *(u32x4*)(lds + lds_skew(v << 4)) = a;
                 *(u32x4*)(lds + lds_skew((v + NT) << 4)) = b;
                 *(u32x4*)(lds + lds_skew((v + 2 * NT) << 4)) = c;
                 *(u32x4*)(lds + lds_skew((v + 3 * NT) << 4)) = d;
                 }
             for (; v < nvec; v += NT)
-                *(u32x4*)(lds + lds_skew(v << 4)) = stream_load((const u32x4*)gsrc + v);
+                *(u32x4*)(lds + lds_skew(v << 4)) = __builtin_nontemporal_load((const u32x4*)gsrc + v);
             }
         for (uint32_t b = (nvec << 4) + tid; b < nbytes; b += NT)
             lds[lds_skew(b)] = gsrc[b];
@@ -249,7 +241,7 @@ template<int MODE> __global__ __launch_bounds__(PACK_THREADS) void pack_tiles_ke
     for (uint64_t tile = blockIdx.x; tile < args.n_tiles; tile += gridDim.x)
         {
         const uint64_t row0 = tile * TILE;
-        const uint32_t rows = (uint32_t)((args.N - row0 < (uint64_t)TILE) ? args.N - row0 : TILE);
+        const uint32_t rows = tile_rows_at(args.N, row0, TILE);
         // every source array of a batch is in flight before the first byte is consumed:
         // one load latency and two barriers per batch instead of per source array
         for (uint32_t b = 0; b < args.n_batches; b++)
@@ -283,7 +275,7 @@ template<int MODE> __global__ __launch_bounds__(PACK_THREADS) void pack_tiles_pr
     auto issue = [&](uint64_t tile)
     {
         const uint64_t row0 = tile * TILE;
-        const uint32_t rows = (uint32_t)((args.N - row0 < (uint64_t)TILE) ? args.N - row0 : TILE);
+        const uint32_t rows = tile_rows_at(args.N, row0, TILE);
 #pragma unroll
         for (uint32_t gi = 0; gi < PF_GROUPS; gi++)
             {
@@ -304,7 +296,7 @@ template<int MODE> __global__ __launch_bounds__(PACK_THREADS) void pack_tiles_pr
     auto commit = [&](uint64_t tile)
     {
         const uint64_t row0 = tile * TILE;
-        const uint32_t rows = (uint32_t)((args.N - row0 < (uint64_t)TILE) ? args.N - row0 : TILE);
+        const uint32_t rows = tile_rows_at(args.N, row0, TILE);
 #pragma unroll
         for (uint32_t gi = 0; gi < PF_GROUPS; gi++)
             {
@@ -334,7 +326,7 @@ template<int MODE> __global__ __launch_bounds__(PACK_THREADS) void pack_tiles_pr
     for (; tile < args.n_tiles; tile += gridDim.x)
         {
         const uint64_t row0 = tile * TILE;
-        const uint32_t rows = (uint32_t)((args.N - row0 < (uint64_t)TILE) ? args.N - row0 : TILE);
+        const uint32_t rows = tile_rows_at(args.N, row0, TILE);
         commit(tile);
         __syncthreads();
         if (tile + gridDim.x < args.n_tiles)
@@ -490,38 +482,14 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_generic_kernel(const PackGe
         uint64_t raw = 0;
         for (uint32_t b = 0; b < a.ssz; b++)
             raw |= (uint64_t)(uint8_t)sp[b] << (8 * b);
-        uint64_t val;
-        switch (a.ssz)
-            {
-            case 1: val = a.dsz == 8 ? convert_elem<1, 8>(raw, a.kind) : convert_elem<1, 4>(raw, a.kind); break;
-            case 2: val = a.dsz == 8 ? convert_elem<2, 8>(raw, a.kind) : convert_elem<2, 4>(raw, a.kind); break;
-            case 4: val = a.dsz == 8 ? convert_elem<4, 8>(raw, a.kind) : convert_elem<4, 4>(raw, a.kind); break;
-            default: val = a.dsz == 4 ? convert_elem<8, 4>(raw, a.kind) : convert_elem<8, 8>(raw, a.kind); break;
-            }
+        const uint64_t val = convert_any(raw, a.ssz, a.dsz, a.kind);
         char* dp = (char*)a.dst + e * a.dsz;
         for (uint32_t b = 0; b < a.dsz; b++)
             dp[b] = (char)(val >> (8 * b));
         }
     }
 
-// ------------------------------------------------------------------ host side
-
-uint32_t conv_kind(uint32_t src_type, uint32_t dst_type, uint32_t bitcast)
-    {
-    const bool s_int = src_type <= PGSD_TYPE_INT64, d_int = dst_type <= PGSD_TYPE_INT64;
-    const size_t ssz = sizeof_type(src_type), dsz = sizeof_type(dst_type);
-    if (bitcast || src_type == dst_type)
-        return PACK_BITS;
-    if (s_int && d_int)
-        {
-        const bool s_signed = src_type >= PGSD_TYPE_INT8;
-        return (dsz > ssz && s_signed) ? PACK_SEXT : PACK_BITS;
-        }
-    if (!s_int && !d_int)
-        return PACK_F2F;
-    // integer -> float (checked by the caller: source <= 32 bit)
-    return src_type >= PGSD_TYPE_INT8 ? PACK_S2F : PACK_U2F;
-    }
+// ---------------------------- host side: three planners and their driver (tuning, conv_kind ...: pgsd_kernels.cpp)
 
 static bool job_valid(const pgsd_pack_job& j)
     {
@@ -538,137 +506,59 @@ static bool job_valid(const pgsd_pack_job& j)
     return true;
     }
 
-uint64_t pack_algorithmic_bytes_in(const pgsd_pack_job& j, uint64_t N)
+// What the planners need to know about a job, derived once (after job_valid).
+struct JobShape
     {
-    return N * (uint64_t)j.M * sizeof_type(j.src.src_type) + (j.src.order ? N * 4 : 0);
+    uint32_t ssz, dsz, kind; // bytes per source / chunk element, PACK_*
+    uint64_t src_words;  // dwords per source row
+    uint64_t out_words;  // dwords per chunk row
+    bool dense;          // the chunk IS the array: every column, bits unchanged
+    bool aligned16;      // source array and chunk buffer on 16-byte boundaries
+    int rows_kind;       // ROWS_*, or -1: not for the row-per-lane kernel
+    };
+
+// rows_kind: can the row-per-lane kernel take the job?  4- and 8-byte elements moved unchanged or converted between
+// f32 and f64, source rows and chunk rows of at most 8 dwords (dense arrays: any width), 16-byte aligned arrays.
+static JobShape job_shape(const pgsd_pack_job& j, uint64_t N)
+    {
+    JobShape s;
+    s.ssz = (uint32_t)sizeof_type(j.src.src_type);
+    s.dsz = (uint32_t)sizeof_type(j.dst_type);
+    s.kind = conv_kind(j.src.src_type, j.dst_type, j.src.bitcast);
+    s.src_words = (uint64_t)j.src.src_stride * s.ssz / 4;
+    s.out_words = (uint64_t)j.M * s.dsz / 4;
+    s.aligned16 = (((uintptr_t)j.dst | (uintptr_t)j.src.src) & 15) == 0;
+    s.rows_kind = -1;
+    if (s.kind == PACK_BITS && s.ssz == s.dsz && (s.ssz == 4 || s.ssz == 8))
+        s.rows_kind = ROWS_BITS;
+    else if (s.kind == PACK_F2F && s.ssz == 8 && s.dsz == 4)
+        s.rows_kind = ROWS_F64_F32;
+    else if (s.kind == PACK_F2F && s.ssz == 4 && s.dsz == 8)
+        s.rows_kind = ROWS_F32_F64;
+    s.dense = s.rows_kind == ROWS_BITS && j.src.src_col0 == 0 && j.M == j.src.src_stride;
+    const uint64_t rw = s.src_words;
+    const bool widths = (rw == 1 || rw == 2 || rw == 3 || rw == 4 || rw == 6 || rw == 8) && s.out_words <= ROWS_MAX_WORDS;
+    // Gathers (tag order) stay with the LDS-tiled kernel: a random 16-byte row per lane costs a whole memory request either
+    // way, and its four-deep row fetches measured faster (417 vs 480-510 us for two float4 arrays of 10 M rows,
+    // profiles/r02_pack_ab.jsonl).  N < 2^31: one lane per row (or per U rows) keeps the grid below 2^32 threads wide.
+    if ((!s.dense && !widths) || !s.aligned16 || j.src.order != nullptr || N >= (1ull << 31))
+        s.rows_kind = -1;
+    return s;
     }
 
-uint64_t pack_bytes_out(const pgsd_pack_job& j, uint64_t N)
+// every kernel of a call, in issue order; the first one stamps ev_start, the last one ev_stop
+// (hipExtLaunchKernelGGL: the dispatch's own begin / end times, what rocprofv3 reports)
+typedef std::vector<std::function<void(hipEvent_t, hipEvent_t)>> Launches;
+
+struct PackCall
     {
-    return N * (uint64_t)j.M * sizeof_type(j.dst_type);
-    }
-
-static int g_num_cus = 0;
-
-int num_cus()
-    {
-    if (g_num_cus == 0)
-        {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            g_num_cus = prop.multiProcessorCount;
-        if (g_num_cus <= 0)
-            g_num_cus = 256;
-        }
-    return g_num_cus;
-    }
-
-// the LDS-tiled kernels: plain or software-pipelined, one instantiation per conversion class
-
-static void launch_tiles(bool prefetch, int mode, unsigned blocks, size_t lds_bytes, hipStream_t stream,
-                         const PackArgs& args, hipEvent_t ev_start, hipEvent_t ev_stop)
-    {
-    // hipExtLaunchKernelGGL stamps the events with the dispatch's own begin / end times, so a
-    // profiled launch measures the kernel and nothing else (what rocprofv3 reports)
-#define TILES_LAUNCH(KERNEL, MODE)                                                                              \
-    hipExtLaunchKernelGGL((KERNEL<MODE>), dim3(blocks), dim3(PACK_THREADS), (uint32_t)lds_bytes, stream, ev_start, \
-                          ev_stop, 0, args)
-    if (prefetch)
-        {
-        if (mode == PACK_MODE_W32)
-            TILES_LAUNCH(pack_tiles_prefetch_kernel, PACK_MODE_W32);
-        else if (mode == PACK_MODE_F64_F32)
-            TILES_LAUNCH(pack_tiles_prefetch_kernel, PACK_MODE_F64_F32);
-        else
-            TILES_LAUNCH(pack_tiles_prefetch_kernel, PACK_MODE_GENERIC);
-        }
-    else
-        {
-        if (mode == PACK_MODE_W32)
-            TILES_LAUNCH(pack_tiles_kernel, PACK_MODE_W32);
-        else if (mode == PACK_MODE_F64_F32)
-            TILES_LAUNCH(pack_tiles_kernel, PACK_MODE_F64_F32);
-        else
-            TILES_LAUNCH(pack_tiles_kernel, PACK_MODE_GENERIC);
-        }
-#undef TILES_LAUNCH
-    }
-
-// ---- tuning knobs (struct PackTuning: pgsd_kernels.hpp)
-static std::mutex g_tuning_lock;
-static bool g_tuning_loaded = false;
-static PackTuning g_tuning;
-
-static PackTuning read_tuning()
-    {
-    PackTuning t;
-    if (const char* e = getenv("PGSD_PACK_ROWS_CFG"))
-        {
-        // only the instantiated pairs (launch_rows below): the grid is sized from T x U, so a pair the
-        // dispatcher does not know would pack too few rows per block and leave a part of every chunk unwritten
-        int a = 0, u = 0;
-        const bool known = sscanf(e, "%dx%d", &a, &u) == 2
-                           && ((a == 64 && u == 2) || (a == 128 && (u == 1 || u == 2))
-                               || (a == 256 && (u == 1 || u == 2 || u == 4 || u == 8)) || (a == 512 && (u == 2 || u == 4)));
-        if (known)
-            t.rows_t = a, t.rows_u = u;
-        else
-            fprintf(stderr, "pgsd_amd: PGSD_PACK_ROWS_CFG=%s is not one of 64x2 128x1 128x2 256x1 256x2 256x4 256x8 512x2 512x4: ignored\n", e);
-        }
-    if (const char* e = getenv("PGSD_PACK_KERNEL"))
-        t.pack_tiles = strcmp(e, "tiles") == 0;
-    if (const char* e = getenv("PGSD_PACK_BLOCKS_PER_CU"))
-        t.per_cu = (uint64_t)atoi(e) > 0 ? (uint64_t)atoi(e) : t.per_cu;
-    if (const char* e = getenv("PGSD_PACK_TILE"))
-        t.tile_cap = (uint32_t)atoi(e) >= 16 ? (uint32_t)atoi(e) : t.tile_cap;
-    if (const char* e = getenv("PGSD_PACK_LDS_KB"))
-        t.lds_budget = (size_t)atoi(e) > 0 ? (size_t)atoi(e) << 10 : t.lds_budget;
-    if (const char* e = getenv("PGSD_PACK_PREFETCH"))
-        t.prefetch = atoi(e);
-    if (const char* e = getenv("PGSD_UNPACK_ROWS_CFG"))
-        {
-        int a = 0, u = 0;
-        if (sscanf(e, "%dx%d", &a, &u) == 2
-            && ((a == 64 && u == 2) || (a == 128 && (u == 1 || u == 2)) || (a == 256 && (u == 1 || u == 2))))
-            t.unrows_t = a, t.unrows_u = u;
-        else
-            fprintf(stderr, "pgsd_amd: PGSD_UNPACK_ROWS_CFG=%s is not one of 64x2 128x1 128x2 256x1 256x2: ignored\n", e);
-        }
-    if (const char* e = getenv("PGSD_UNPACK_TILE"))
-        t.unpack_tile_cap = (uint32_t)atoi(e) >= 16 ? (uint32_t)atoi(e) : 0;
-    if (const char* e = getenv("PGSD_UNPACK_BLOCKS_PER_CU"))
-        t.unpack_per_cu = (uint64_t)atoi(e) > 0 ? (uint64_t)atoi(e) : t.unpack_per_cu;
-    if (const char* e = getenv("PGSD_UNPACK_KERNEL"))
-        t.unpack_tiles = strcmp(e, "tiles") == 0;
-    if (const char* e = getenv("PGSD_PLAN_BLOCK_ROWS"))
-        t.plan_block_rows = atoll(e) > 0 && atoll(e) <= (1 << 24) ? (uint32_t)atoll(e) : t.plan_block_rows;
-    return t;
-    }
-
-PackTuning tuning()
-    {
-    std::lock_guard<std::mutex> guard(g_tuning_lock);
-    if (!g_tuning_loaded)
-        {
-        g_tuning = read_tuning();
-        g_tuning_loaded = true;
-        }
-    return g_tuning;
-    }
-
-void warm_pack_kernels()
-    {
-    hipFuncAttributes attr;
-    (void)hipFuncGetAttributes(&attr, (const void*)pack_generic_kernel);
-    (void)hipGetLastError();
-    }
-
-void reload_pack_tuning()
-    {
-    std::lock_guard<std::mutex> guard(g_tuning_lock);
-    g_tuning_loaded = false;
-    }
+    uint32_t n_jobs;
+    const pgsd_pack_job* jobs;
+    const JobShape* shapes;
+    uint64_t N;
+    hipStream_t stream;
+    PackTuning tune;
+    };
 
 // ---- row-per-lane launches
 struct RowsCfg
@@ -676,17 +566,15 @@ struct RowsCfg
     int T, U;
     };
 
-static RowsCfg rows_config(uint64_t N, uint32_t n_groups)
+static RowsCfg rows_config(const PackTuning& t, uint64_t N, uint32_t n_groups)
     {
     // measured, interleaved launch by launch in one process (profiles/r02_pack_ab.jsonl): 256 threads x 2
     // rows per lane is the best or within 1-2 % of the best for every workload from 1 M rows up
     // (10 M particles, HOOMD layout: 94.8 us against 106.5 us for the LDS-tiled kernel); a launch of one
     // or two arrays below 2 M rows does better with half as many, fatter workgroups
-    RowsCfg c = (N < (2u << 20) && n_groups <= 2) ? RowsCfg {256, 4} : RowsCfg {256, 2};
-    const PackTuning t = tuning();
     if (t.rows_t)
-        c = RowsCfg {t.rows_t, t.rows_u};
-    return c;
+        return RowsCfg {t.rows_t, t.rows_u};
+    return (N < (2u << 20) && n_groups <= 2) ? RowsCfg {256, 4} : RowsCfg {256, 2};
     }
 
 template<int T, int U>
@@ -716,61 +604,243 @@ static void launch_rows_tu(const RowsArgs& a, bool copy, uint32_t rw, bool bits_
 #undef ROWS_LAUNCH
     }
 
+// c is one of PGSD_PACK_ROWS_SHAPES: plan_rows() refuses any other pair before it gets here
 static void launch_rows(const RowsCfg& c, const RowsArgs& a, bool copy, uint32_t rw, bool bits_only, hipStream_t stream,
                         hipEvent_t e0, hipEvent_t e1)
     {
-    if (c.T == 256 && c.U == 4)
-        launch_rows_tu<256, 4>(a, copy, rw, bits_only, stream, e0, e1);
-    else if (c.T == 256 && c.U == 2)
-        launch_rows_tu<256, 2>(a, copy, rw, bits_only, stream, e0, e1);
-    else if (c.T == 256 && c.U == 1)
-        launch_rows_tu<256, 1>(a, copy, rw, bits_only, stream, e0, e1);
-    else if (c.T == 128 && c.U == 2)
-        launch_rows_tu<128, 2>(a, copy, rw, bits_only, stream, e0, e1);
-    else if (c.T == 64 && c.U == 2)
-        launch_rows_tu<64, 2>(a, copy, rw, bits_only, stream, e0, e1);
-    else if (c.T == 256 && c.U == 8)
-        launch_rows_tu<256, 8>(a, copy, rw, bits_only, stream, e0, e1);
-    else if (c.T == 512 && c.U == 4)
-        launch_rows_tu<512, 4>(a, copy, rw, bits_only, stream, e0, e1);
-    else if (c.T == 512 && c.U == 2)
-        launch_rows_tu<512, 2>(a, copy, rw, bits_only, stream, e0, e1);
-    else
-        launch_rows_tu<128, 1>(a, copy, rw, bits_only, stream, e0, e1);
+#define ROWS_SHAPE(TT, UU)      \
+    if (c.T == TT && c.U == UU) \
+        return launch_rows_tu<TT, UU>(a, copy, rw, bits_only, stream, e0, e1);
+    PGSD_PACK_ROWS_SHAPES(ROWS_SHAPE)
+#undef ROWS_SHAPE
     }
 
-// Can the row-per-lane kernel take this job?  4- and 8-byte elements moved unchanged or converted
-// between f32 and f64, source rows and chunk rows of at most 8 dwords, 16-byte aligned arrays.
-static bool rows_eligible(const pgsd_pack_job& j, uint64_t N, uint32_t* kind_out)
+// Put an eligible job into the launch being assembled; false: it waits for a later launch.  cls_rw = the source-row
+// width of the launch's row-mode arrays (a compile-time parameter of the kernel), 0 while it has none.
+static bool rows_place(RowsArgs& a, uint32_t& cls_rw, const pgsd_pack_job& j, const JobShape& s)
     {
-    const uint32_t ssz = (uint32_t)sizeof_type(j.src.src_type), dsz = (uint32_t)sizeof_type(j.dst_type);
-    if ((ssz != 4 && ssz != 8) || (dsz != 4 && dsz != 8))
+    const uint32_t rw = (uint32_t)s.src_words;
+    if (!s.dense && cls_rw != 0 && rw != cls_rw)
         return false;
-    const uint32_t kind = conv_kind(j.src.src_type, j.dst_type, j.src.bitcast);
-    uint32_t rk;
-    if (kind == PACK_BITS && ssz == dsz)
-        rk = ROWS_BITS;
-    else if (kind == PACK_F2F && ssz == 8 && dsz == 4)
-        rk = ROWS_F64_F32;
-    else if (kind == PACK_F2F && ssz == 4 && dsz == 8)
-        rk = ROWS_F32_F64;
-    else
-        return false;
-    const uint64_t rw = (uint64_t)j.src.src_stride * ssz / 4, nw = (uint64_t)j.M * dsz / 4;
-    const bool dense = rk == ROWS_BITS && j.src.src_col0 == 0 && j.M == j.src.src_stride;
-    if (!dense && ((rw != 1 && rw != 2 && rw != 3 && rw != 4 && rw != 6 && rw != 8) || nw > ROWS_MAX_WORDS))
-        return false;
-    if ((((uintptr_t)j.dst | (uintptr_t)j.src.src) & 15) != 0)
-        return false;
-    // gathers (tag order through a permutation) stay with the LDS-tiled kernel: one random 16-byte row per
-    // lane costs a whole memory request either way, and its four-deep row fetches measured faster than a
-    // row-per-lane gather (417 vs 480-510 us for two float4 arrays of 10 M rows, profiles/r02_pack_ab.jsonl)
-    if (j.src.order != nullptr)
-        return false;
-    if (N >= (1ull << 31)) // one lane per row (or per U rows): keeps the grid's x extent below 2^32 threads
-        return false;
-    *kind_out = rk;
+    int gi = -1;
+    for (uint32_t k = 0; k < a.n_groups && !s.dense; k++)
+        if (a.g[k].copy_vecs == 0 && a.g[k].copy_tail == 0 && a.g[k].src == j.src.src && a.g[k].n_out < PACK_MAX_OUT)
+            gi = (int)k;
+    if (gi < 0)
+        {
+        if (a.n_groups == ROWS_MAX_GROUPS)
+            return false;
+        gi = (int)a.n_groups++;
+        RowsGroup& g = a.g[gi];
+        g.src = j.src.src;
+        g.row_words = rw;
+        const uint64_t bytes = a.N * (uint64_t)j.src.src_stride * s.ssz;
+        if (s.dense)
+            g.copy_vecs = bytes >> 4, g.copy_tail = (uint32_t)(bytes & 15);
+        else
+            cls_rw = rw;
+        }
+    RowsGroup& g = a.g[gi];
+    RowsOut& o = g.out[g.n_out++];
+    o.dst = j.dst;
+    o.col0 = j.src.src_col0 * s.ssz / 4; // first source dword
+    o.M = j.M;
+    o.kind = (uint32_t)s.rows_kind;
+    o.nw_out = (uint32_t)s.out_words;
     return true;
+    }
+
+// 1. The row-per-lane kernel takes every job it can: one launch per class of source-row width, dense same-type arrays
+//    ride along in any launch; up to ROWS_MAX_GROUPS arrays each.  The headline layouts are ONE launch.
+static int plan_rows(const PackCall& c, std::vector<bool>& done, Launches& launches, std::string* err)
+    {
+    while (true)
+        {
+        RowsArgs a;
+        memset(&a, 0, sizeof(a));
+        a.N = c.N;
+        bool bits_only = true;
+        uint32_t cls_rw = 0;
+        // row-mode arrays first decide the class, then the dense ones fill the launch up
+        for (int pass = 0; pass < 2; pass++)
+            for (uint32_t i = 0; i < c.n_jobs; i++)
+                {
+                const JobShape& s = c.shapes[i];
+                if (done[i] || s.rows_kind < 0 || s.dense != (pass == 1) || !rows_place(a, cls_rw, c.jobs[i], s))
+                    continue;
+                bits_only = bits_only && s.rows_kind == ROWS_BITS;
+                done[i] = true;
+                }
+        if (a.n_groups == 0)
+            return PGSD_SUCCESS;
+        const RowsCfg cfg = rows_config(c.tune, c.N, a.n_groups);
+        if (!pack_rows_shape_known(cfg.T, cfg.U))
+            return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
+                               "pack: no row-per-lane kernel of " + std::to_string(cfg.T) + "x" + std::to_string(cfg.U));
+        const uint64_t per_block = (uint64_t)cfg.T * cfg.U;
+        uint64_t blocks = 1;
+        for (uint32_t k = 0; k < a.n_groups; k++)
+            {
+            const uint64_t units = (a.g[k].copy_vecs || a.g[k].copy_tail) ? a.g[k].copy_vecs : c.N;
+            blocks = std::max(blocks, (units + per_block - 1) / per_block);
+            }
+        a.n_blocks = blocks; // N < 2^31 rows (job_shape) keeps the grid's x extent below 2^32 threads
+        const bool copy_only = cls_rw == 0;
+        const hipStream_t stream = c.stream;
+        launches.push_back([=](hipEvent_t e0, hipEvent_t e1)
+                           { launch_rows(cfg, a, copy_only, cls_rw, bits_only, stream, e0, e1); });
+        }
+    }
+
+// 2. What neither the row-per-lane nor the LDS-tiled kernel can take (unaligned pointers, very wide rows) goes through
+//    the generic kernel, one launch per job.
+static void plan_generic(const PackCall& c, std::vector<bool>& done, Launches& launches)
+    {
+    for (uint32_t i = 0; i < c.n_jobs; i++)
+        {
+        const pgsd_pack_job& j = c.jobs[i];
+        const JobShape& s = c.shapes[i];
+        const uint64_t rowbytes = (uint64_t)j.src.src_stride * s.ssz;
+        const bool aligned = s.aligned16 && (j.src.order == nullptr || ((uintptr_t)j.src.order & 3) == 0);
+        if (done[i] || (aligned && rowbytes <= PACK_MAX_ROWBYTES && j.M <= PACK_MAX_M && c.N * rowbytes < (1ull << 62)))
+            continue;
+        const PackGenericArgs a = {j.dst, j.src.src, j.src.order, c.N, j.M, j.src.src_stride, j.src.src_col0,
+                                   s.ssz, s.dsz, s.kind};
+        const uint64_t blocks = std::min((c.N * j.M + PACK_THREADS - 1) / PACK_THREADS, (uint64_t)num_cus() * 8);
+        const hipStream_t stream = c.stream;
+        launches.push_back(
+            [a, blocks, stream](hipEvent_t e0, hipEvent_t e1) {
+                hipExtLaunchKernelGGL(pack_generic_kernel, dim3((unsigned)blocks), dim3(PACK_THREADS), 0, stream, e0, e1, 0, a);
+            });
+        done[i] = true;
+        }
+    }
+
+// ---- the LDS-tiled kernels: plain or software-pipelined, one instantiation per conversion class
+static void launch_tiles(bool prefetch, int mode, unsigned blocks, size_t lds_bytes, hipStream_t stream,
+                         const PackArgs& args, hipEvent_t ev_start, hipEvent_t ev_stop)
+    {
+#define TILES_LAUNCH(KERNEL, MODE)                                                                              \
+    hipExtLaunchKernelGGL((KERNEL<MODE>), dim3(blocks), dim3(PACK_THREADS), (uint32_t)lds_bytes, stream, ev_start, \
+                          ev_stop, 0, args)
+#define TILES_MODE(MODE)                                      \
+    if (prefetch)                                             \
+        TILES_LAUNCH(pack_tiles_prefetch_kernel, MODE);       \
+    else                                                      \
+        TILES_LAUNCH(pack_tiles_kernel, MODE)
+    switch (mode)
+        {
+        case PACK_MODE_W32: TILES_MODE(PACK_MODE_W32); break;
+        case PACK_MODE_F64_F32: TILES_MODE(PACK_MODE_F64_F32); break;
+        default: TILES_MODE(PACK_MODE_GENERIC); break;
+        }
+#undef TILES_MODE
+#undef TILES_LAUNCH
+    }
+
+static int tiles_mode(const JobShape& s)
+    {
+    if (s.ssz == 4 && s.dsz == 4 && s.kind == PACK_BITS)
+        return PACK_MODE_W32;
+    return (s.ssz == 8 && s.dsz == 4 && s.kind == PACK_F2F) ? PACK_MODE_F64_F32 : PACK_MODE_GENERIC;
+    }
+
+// Put a job into the launch being assembled, next to the other chunks of its source array; false: the launch has no
+// room for another source array and the job waits for the next one.
+static bool tiles_place(PackArgs& args, const pgsd_pack_job& j, const JobShape& s)
+    {
+    int gi = -1;
+    for (uint32_t k = 0; k < args.n_groups; k++)
+        if (args.g[k].src == j.src.src && args.g[k].order == j.src.order && args.g[k].ssz == s.ssz
+            && args.g[k].stride == j.src.src_stride && args.g[k].n_out < PACK_MAX_OUT)
+            gi = (int)k;
+    if (gi < 0)
+        {
+        if (args.n_groups == PACK_MAX_GROUPS)
+            return false;
+        gi = (int)args.n_groups++;
+        PackGroup& g = args.g[gi];
+        g.src = j.src.src;
+        g.order = j.src.order;
+        g.ssz = s.ssz;
+        g.stride = j.src.src_stride;
+        g.rowbytes = j.src.src_stride * s.ssz;
+        }
+    PackGroup& g = args.g[gi];
+    PackOut& o = g.out[g.n_out++];
+    o.dst = j.dst;
+    o.M = j.M;
+    o.col0 = j.src.src_col0;
+    o.dsz = s.dsz;
+    o.kind = s.kind;
+    o.magic = div_magic(j.M);
+    return true;
+    }
+
+// Tile size, LDS layout and batches of an assembled launch; returns the LDS bytes a workgroup needs.
+static size_t tiles_layout(PackArgs& args, const PackTuning& tune)
+    {
+    // tile: as many rows as the widest source row allows; consecutive source arrays then share a batch (staged
+    // together, emitted together) while their tiles fit the budget
+    uint32_t max_rowbytes = 0;
+    for (uint32_t k = 0; k < args.n_groups; k++)
+        max_rowbytes = std::max(max_rowbytes, args.g[k].rowbytes);
+    const TileGeometry geo = tile_geometry(args.N, max_rowbytes, tune.tile_cap, tune.lds_budget);
+    args.tile_rows = geo.tile_rows;
+    args.n_tiles = geo.n_tiles;
+    size_t lds_bytes = 0, used = 0;
+    for (uint32_t k = 0; k < args.n_groups; k++)
+        {
+        const size_t lin = (size_t)geo.tile_rows * args.g[k].rowbytes;
+        const size_t need = (lin + ((lin >> 7) << 4) + 31) & ~(size_t)15; // see lds_skew
+        if (used != 0 && used + need > tune.lds_budget)
+            {
+            args.batch_start[++args.n_batches] = (uint8_t)k;
+            used = 0;
+            }
+        args.g[k].lds_off = (uint32_t)used;
+        used += need;
+        lds_bytes = std::max(lds_bytes, used);
+        }
+    args.batch_start[++args.n_batches] = (uint8_t)args.n_groups;
+    return lds_bytes;
+    }
+
+// The software-pipelined kernel takes launches it has registers for -- one batch, linear sources, tiles of at most
+// PF_VECS x 256 vectors -- and, unless PGSD_PACK_PREFETCH says otherwise, only those whose workgroups see one or two tiles.
+static bool tiles_prefetch(const PackArgs& args, uint64_t blocks, int want)
+    {
+    bool prefetch = args.n_batches == 1 && args.n_groups <= PF_GROUPS;
+    for (uint32_t k = 0; k < args.n_groups; k++)
+        prefetch = prefetch && args.g[k].order == nullptr
+                   && (size_t)args.tile_rows * args.g[k].rowbytes <= (size_t)PF_VECS * PACK_THREADS * 16;
+    return prefetch && want != 0 && !(want < 0 && args.n_tiles > 2 * blocks);
+    }
+
+// 3. The LDS-tiled kernel takes the rest: jobs grouped by source array, one launch per conversion class (a compile-time
+//    parameter) and per PACK_MAX_GROUPS source arrays.
+static void plan_tiles(const PackCall& c, std::vector<bool>& done, Launches& launches)
+    {
+    while (std::find(done.begin(), done.end(), false) != done.end())
+        {
+        PackArgs args;
+        memset(&args, 0, sizeof(args));
+        args.N = c.N;
+        int mode = -1; // that of the first job left
+        for (uint32_t i = 0; i < c.n_jobs; i++)
+            {
+            if (done[i] || (mode >= 0 && mode != tiles_mode(c.shapes[i])) || !tiles_place(args, c.jobs[i], c.shapes[i]))
+                continue;
+            mode = tiles_mode(c.shapes[i]);
+            done[i] = true;
+            }
+        const size_t lds_bytes = tiles_layout(args, c.tune);
+        const uint64_t blocks = blocks_for(args.n_tiles, lds_bytes, c.tune.per_cu);
+        const bool prefetch = tiles_prefetch(args, blocks, c.tune.prefetch);
+        const hipStream_t stream = c.stream;
+        launches.push_back([=](hipEvent_t e0, hipEvent_t e1)
+                           { launch_tiles(prefetch, mode, (unsigned)blocks, lds_bytes, stream, args, e0, e1); });
+        }
     }
 
 int launch_pack(uint32_t n_jobs, const pgsd_pack_job* jobs, uint64_t N, hipStream_t stream, std::string* err,
@@ -778,291 +848,46 @@ int launch_pack(uint32_t n_jobs, const pgsd_pack_job* jobs, uint64_t N, hipStrea
     {
     if (n_jobs == 0 || N == 0)
         return PGSD_SUCCESS;
+    std::vector<JobShape> shapes(n_jobs);
     for (uint32_t i = 0; i < n_jobs; i++)
+        {
         if (!job_valid(jobs[i]))
-            {
-            if (err)
-                *err = "invalid pack job (types, columns or pointers)";
-            return PGSD_ERROR_INVALID_ARGUMENT;
-            }
-    // every kernel of the call, in issue order; the first one stamps ev_start, the last one ev_stop
-    // (hipExtLaunchKernelGGL: the dispatch's own begin / end times, what rocprofv3 reports)
-    std::vector<std::function<void(hipEvent_t, hipEvent_t)>> launches;
+            return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "invalid pack job (types, columns or pointers)");
+        shapes[i] = job_shape(jobs[i], N);
+        }
+    // kernel choice: defaults from measurements on MI355X (profiles/); the variables are for the tuning sweeps of
+    // tools/pack_bench.py
+    const PackCall call = {n_jobs, jobs, shapes.data(), N, stream, tuning()};
+    Launches launches;
     std::vector<bool> done(n_jobs, false);
-
-    // kernel choice (defaults from measurements on MI355X, profiles/; env overrides are for the
-    // tuning sweeps of tools/pack_bench.py)
-    enum
+    if (!call.tune.pack_tiles)
         {
-        K_ROWS,
-        K_TILES
-        } kernel
-        = K_ROWS;
-    const PackTuning tune = tuning();
-    if (tune.pack_tiles)
-        kernel = K_TILES;
-
-    // 1. the row-per-lane kernel takes every job it can: one launch per class of source-row width (a
-    //    compile-time parameter), dense same-type arrays ride along in any launch; up to ROWS_MAX_GROUPS
-    //    arrays each.  The headline layouts are ONE launch.
-    if (kernel == K_ROWS)
-        {
-        while (true)
-            {
-            RowsArgs a;
-            memset(&a, 0, sizeof(a));
-            a.N = N;
-            bool bits_only = true;
-            uint32_t cls_rw = 0; // 0: no row-mode array in this launch yet
-            // row-mode arrays first decide the class, then the dense ones fill the launch up
-            for (int pass = 0; pass < 2; pass++)
-                for (uint32_t i = 0; i < n_jobs; i++)
-                    {
-                    if (done[i])
-                        continue;
-                    const pgsd_pack_job& j = jobs[i];
-                    uint32_t rk = 0;
-                    if (!rows_eligible(j, N, &rk))
-                        continue;
-                    const uint32_t ssz = (uint32_t)sizeof_type(j.src.src_type), dsz = (uint32_t)sizeof_type(j.dst_type);
-                    const uint32_t rw = j.src.src_stride * ssz / 4;
-                    const bool dense = rk == ROWS_BITS && j.src.src_col0 == 0 && j.M == j.src.src_stride;
-                    if (dense != (pass == 1))
-                        continue;
-                    if (!dense && cls_rw != 0 && rw != cls_rw)
-                        continue; // another class: a later launch
-                    int gi = -1;
-                    if (!dense)
-                        for (uint32_t k = 0; k < a.n_groups; k++)
-                            if (a.g[k].copy_vecs == 0 && a.g[k].copy_tail == 0 && a.g[k].src == j.src.src
-                                && a.g[k].n_out < PACK_MAX_OUT)
-                                gi = (int)k;
-                    if (gi < 0)
-                        {
-                        if (a.n_groups == ROWS_MAX_GROUPS)
-                            continue; // next launch
-                        gi = (int)a.n_groups++;
-                        RowsGroup& g = a.g[gi];
-                        g.src = j.src.src;
-                        g.row_words = rw;
-                        if (dense)
-                            {
-                            const uint64_t bytes = N * (uint64_t)j.src.src_stride * ssz;
-                            g.copy_vecs = bytes >> 4;
-                            g.copy_tail = (uint32_t)(bytes & 15);
-                            }
-                        else
-                            cls_rw = rw;
-                        }
-                    RowsGroup& g = a.g[gi];
-                    RowsOut& o = g.out[g.n_out++];
-                    o.dst = j.dst;
-                    o.col0 = j.src.src_col0 * ssz / 4; // first source dword
-                    o.M = j.M;
-                    o.kind = rk;
-                    o.nw_out = j.M * dsz / 4;
-                    bits_only = bits_only && rk == ROWS_BITS;
-                    done[i] = true;
-                    }
-            if (a.n_groups == 0)
-                break;
-            const bool copy_only = cls_rw == 0;
-            const RowsCfg cfg = rows_config(N, a.n_groups);
-            const uint64_t per_block = (uint64_t)cfg.T * cfg.U;
-            uint64_t blocks = 1;
-            for (uint32_t k = 0; k < a.n_groups; k++)
-                {
-                const uint64_t units = (a.g[k].copy_vecs || a.g[k].copy_tail) ? a.g[k].copy_vecs : N;
-                blocks = std::max(blocks, (units + per_block - 1) / per_block);
-                }
-            a.n_blocks = blocks; // N < 2^31 rows (rows_eligible) keeps the grid's x extent below 2^32 threads
-            launches.push_back([=](hipEvent_t e0, hipEvent_t e1)
-                               { launch_rows(cfg, a, copy_only, cls_rw, bits_only, stream, e0, e1); });
-            }
+        const int rc = plan_rows(call, done, launches, err);
+        if (rc != PGSD_SUCCESS)
+            return rc;
         }
-
-    // 2. jobs the tiled kernel cannot take either go through the generic kernel
-    for (uint32_t i = 0; i < n_jobs; i++)
-        {
-        if (done[i])
-            continue;
-        const pgsd_pack_job& j = jobs[i];
-        const size_t ssz = sizeof_type(j.src.src_type);
-        const uint64_t rowbytes = (uint64_t)j.src.src_stride * ssz;
-        const bool aligned = (((uintptr_t)j.dst | (uintptr_t)j.src.src) & 15) == 0
-                             && (j.src.order == nullptr || ((uintptr_t)j.src.order & 3) == 0);
-        if (!aligned || rowbytes > PACK_MAX_ROWBYTES || j.M > PACK_MAX_M || N * rowbytes >= (1ull << 62))
-            {
-            PackGenericArgs a;
-            a.dst = j.dst;
-            a.src = j.src.src;
-            a.order = j.src.order;
-            a.N = N;
-            a.M = j.M;
-            a.stride = j.src.src_stride;
-            a.col0 = j.src.src_col0;
-            a.ssz = (uint32_t)ssz;
-            a.dsz = (uint32_t)sizeof_type(j.dst_type);
-            a.kind = conv_kind(j.src.src_type, j.dst_type, j.src.bitcast);
-            uint64_t total = N * j.M;
-            uint64_t blocks = (total + PACK_THREADS - 1) / PACK_THREADS;
-            uint64_t cap = (uint64_t)num_cus() * 8;
-            if (blocks > cap)
-                blocks = cap;
-            launches.push_back(
-                [a, blocks, stream](hipEvent_t e0, hipEvent_t e1)
-                {
-                    hipExtLaunchKernelGGL(pack_generic_kernel, dim3((unsigned)blocks), dim3(PACK_THREADS), 0, stream, e0, e1,
-                                          0, a);
-                });
-            done[i] = true;
-            }
-        }
-
-    // 3. the LDS-tiled kernel: group the remaining jobs by source array, in batches that fit PackArgs
-    uint32_t next = 0;
-    while (next < n_jobs && done[next])
-        next++;
-    while (next < n_jobs)
-        {
-        PackArgs args;
-        memset(&args, 0, sizeof(args));
-        args.N = N;
-        uint32_t max_rowbytes = 0;
-        bool any = false;
-        int mode = -1; // a launch holds jobs of one specialisation only
-        for (uint32_t i = next; i < n_jobs; i++)
-            {
-            if (done[i])
-                continue;
-            const pgsd_pack_job& j = jobs[i];
-            const uint32_t ssz = (uint32_t)sizeof_type(j.src.src_type);
-            const uint32_t jdsz = (uint32_t)sizeof_type(j.dst_type);
-            const uint32_t jkind = conv_kind(j.src.src_type, j.dst_type, j.src.bitcast);
-            const int jmode = (ssz == 4 && jdsz == 4 && jkind == PACK_BITS)  ? PACK_MODE_W32
-                              : (ssz == 8 && jdsz == 4 && jkind == PACK_F2F) ? PACK_MODE_F64_F32
-                                                                             : PACK_MODE_GENERIC;
-            if (mode < 0)
-                mode = jmode;
-            else if (mode != jmode)
-                continue; // next batch
-            // find a group with the same source
-            int gi = -1;
-            for (uint32_t k = 0; k < args.n_groups; k++)
-                if (args.g[k].src == j.src.src && args.g[k].order == j.src.order && args.g[k].ssz == ssz
-                    && args.g[k].stride == j.src.src_stride && args.g[k].n_out < PACK_MAX_OUT)
-                    gi = (int)k;
-            if (gi < 0)
-                {
-                if (args.n_groups == PACK_MAX_GROUPS)
-                    continue; // next batch
-                gi = (int)args.n_groups++;
-                PackGroup& g = args.g[gi];
-                g.src = j.src.src;
-                g.order = j.src.order;
-                g.ssz = ssz;
-                g.stride = j.src.src_stride;
-                g.rowbytes = j.src.src_stride * ssz;
-                g.n_out = 0;
-                max_rowbytes = std::max(max_rowbytes, g.rowbytes);
-                }
-            PackGroup& g = args.g[gi];
-            PackOut& o = g.out[g.n_out++];
-            o.dst = j.dst;
-            o.M = j.M;
-            o.col0 = j.src.src_col0;
-            o.dsz = (uint32_t)sizeof_type(j.dst_type);
-            o.kind = conv_kind(j.src.src_type, j.dst_type, j.src.bitcast);
-            o.magic = j.M == 1 ? 0u : (uint32_t)(((1ull << 32) + j.M - 1) / j.M);
-            done[i] = true;
-            any = true;
-            }
-        if (!any)
-            break;
-        const uint64_t per_cu = tune.per_cu;
-        const uint32_t tile_cap = tune.tile_cap;
-        const size_t lds_budget = tune.lds_budget;
-        // tile: as many rows as the widest source row allows (power of two in [16, tile_cap]);
-        // consecutive source arrays then share a batch while their tiles fit the budget
-        uint32_t tile = 16;
-        while (tile * 2 <= tile_cap && (uint64_t)tile * 2 * max_rowbytes <= lds_budget)
-            tile <<= 1;
-        args.tile_rows = tile;
-        args.n_tiles = (N + tile - 1) / tile;
-        size_t lds_bytes = 0, used = 0;
-        args.n_batches = 0;
-        args.batch_start[0] = 0;
-        for (uint32_t k = 0; k < args.n_groups; k++)
-            {
-            size_t lin = (size_t)tile * args.g[k].rowbytes;
-            size_t need = (lin + ((lin >> 7) << 4) + 31) & ~(size_t)15; // see lds_skew
-            if (used != 0 && used + need > lds_budget)
-                {
-                args.batch_start[++args.n_batches] = (uint8_t)k;
-                used = 0;
-                }
-            args.g[k].lds_off = (uint32_t)used;
-            used += need;
-            lds_bytes = std::max(lds_bytes, used);
-            }
-        args.batch_start[++args.n_batches] = (uint8_t)args.n_groups;
-        // never ask for more workgroups per CU than the 160 KiB of LDS admit: the surplus
-        // would queue behind the resident ones and run as a ragged second wave
-        uint64_t resident = lds_bytes ? (160u * 1024u) / lds_bytes : 8;
-        if (resident < 1)
-            resident = 1;
-        uint64_t blocks = args.n_tiles;
-        uint64_t cap = (uint64_t)num_cus() * std::min<uint64_t>(per_cu, resident);
-        if (blocks > cap)
-            blocks = cap;
-        // the software-pipelined kernel takes launches it has registers for: one batch, linear
-        // sources, tiles of at most PF_VECS x 256 vectors
-        bool prefetch = args.n_batches == 1 && args.n_groups <= PF_GROUPS;
-        for (uint32_t k = 0; k < args.n_groups; k++)
-            prefetch = prefetch && args.g[k].order == nullptr
-                       && (size_t)tile * args.g[k].rowbytes <= (size_t)PF_VECS * PACK_THREADS * 16;
-        const int want = tune.prefetch; // -1: by size
-        if (want == 0 || (want < 0 && args.n_tiles > 2 * blocks))
-            prefetch = false;
-        launches.push_back(
-            [=](hipEvent_t e0, hipEvent_t e1)
-            { launch_tiles(prefetch, mode, (unsigned)blocks, lds_bytes, stream, args, e0, e1); });
-        while (next < n_jobs && done[next])
-            next++;
-        }
+    plan_generic(call, done, launches);
+    plan_tiles(call, done, launches);
     // whatever an earlier call of this thread left in the runtime's last-error slot (a failed hipMalloc, the caller's own
     // calls) is not this launch's: the slot is read again right behind the launches
     (void)hipGetLastError();
     for (size_t i = 0; i < launches.size(); i++)
         launches[i](i == 0 ? ev_start : nullptr, i + 1 == launches.size() ? ev_stop : nullptr);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        {
-        if (err)
-            *err = std::string("pack kernel launch failed: ") + hipGetErrorString(e);
-        return PGSD_ERROR_DEVICE;
-        }
+        return launch_fail(err, PGSD_ERROR_DEVICE, std::string("pack kernel launch failed: ") + hipGetErrorString(e));
     return PGSD_SUCCESS;
+    }
+
+void warm_pack_kernels()
+    {
+    hipFuncAttributes attr;
+    (void)hipFuncGetAttributes(&attr, (const void*)pack_generic_kernel);
+    (void)hipGetLastError();
     }
     } // namespace pgsd_amd
 
 using namespace pgsd_amd;
-
-extern "C" int pgsd_device_available(void)
-    try
-    {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess)
-        {
-        (void)hipGetLastError();
-        return 0;
-        }
-    return n > 0 ? 1 : 0;
-    }
-catch (...)
-    {
-        return pgsd_amd::abi_guard();
-    }
 
 extern "C" int pgsd_pack_fields(uint32_t n_jobs, const struct pgsd_pack_job* jobs, uint64_t N, void* stream, float* kernel_ms)
     try
@@ -1104,24 +929,3 @@ catch (...)
     {
         return pgsd_amd::abi_guard();
     }
-
-// scratch space of pgsd_select_rows: the library's, one per device, grown on demand (a call holds the lock: it ends
-// with a stream synchronisation anyway)
-
-extern "C" void pgsd_reload_tuning(void)
-    try
-    {
-    pgsd_amd::reload_pack_tuning();
-    }
-catch (...)
-    {
-        pgsd_amd::abi_guard();
-    }
-
-extern "C" uint32_t pgsd_abi_version(void)
-    {
-    return PGSD_ABI_VERSION;
-    }
-
-// Device memory owned by the library (include/pgsd.h): what pgsd.fl / pgsd.hoomd keep elision references, device
-// reads and index lists in, so that the Python device path needs no tensor library.

@@ -1,5 +1,5 @@
-// pgsd_pack.hpp -- kernel argument blocks of the pack kernels (pgsd_pack.hip) and the
-// host-side launcher shared with the device pipeline (pgsd_device_write.cpp, pgsd_device_read.cpp).
+// pgsd_pack.hpp -- kernel argument blocks of the pack, unpack and select kernels (pgsd_*.hip) and the
+// host-side launchers shared with the device pipeline (pgsd_device_write.cpp, pgsd_device_read.cpp).
 #ifndef PGSD_PACK_HPP
 #define PGSD_PACK_HPP
 

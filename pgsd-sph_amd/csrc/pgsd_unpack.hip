@@ -23,12 +23,12 @@ template<bool W32> __device__ __forceinline__ uint64_t unpack_elem(const char* p
         return *(const uint32_t*)p;
     else
         {
-        switch (ssz)
+        switch (ssz) // (a constant ssz folds convert_any's own switch away: one load and one conversion per case)
             {
-            case 1: return dsz == 8 ? convert_elem<1, 8>(lds_load<1>(p), kind) : convert_elem<1, 4>(lds_load<1>(p), kind);
-            case 2: return dsz == 8 ? convert_elem<2, 8>(lds_load<2>(p), kind) : convert_elem<2, 4>(lds_load<2>(p), kind);
-            case 4: return dsz == 8 ? convert_elem<4, 8>(lds_load<4>(p), kind) : convert_elem<4, 4>(lds_load<4>(p), kind);
-            default: return dsz == 4 ? convert_elem<8, 4>(lds_load<8>(p), kind) : convert_elem<8, 8>(lds_load<8>(p), kind);
+            case 1: return convert_any(lds_load<1>(p), 1, dsz, kind);
+            case 2: return convert_any(lds_load<2>(p), 2, dsz, kind);
+            case 4: return convert_any(lds_load<4>(p), 4, dsz, kind);
+            default: return convert_any(lds_load<8>(p), 8, dsz, kind);
             }
         }
     }
@@ -44,15 +44,7 @@ __device__ __forceinline__ void scatter_tile(const UnpackJob& j, const char* lds
         uint32_t col = e - row * M;
         uint64_t val = unpack_elem<W32>(lds + (size_t)e * ssz, ssz, dsz, j.kind);
         uint64_t drow = j.order ? (uint64_t)j.order[row0 + row] : row0 + row;
-        char* p = (char*)j.dst + (drow * j.dst_stride + j.dst_col0 + col) * dsz;
-        if (dsz == 8)
-            *(uint64_t*)p = val;
-        else if (dsz == 4)
-            *(uint32_t*)p = (uint32_t)val;
-        else if (dsz == 2)
-            *(uint16_t*)p = (uint16_t)val;
-        else
-            *(uint8_t*)p = (uint8_t)val;
+        store_elem((char*)j.dst + (drow * j.dst_stride + j.dst_col0 + col) * dsz, val, dsz);
         }
     }
 
@@ -159,7 +151,7 @@ template<bool W32> __global__ __launch_bounds__(PACK_THREADS) void unpack_tiles_
     for (uint64_t tile = blockIdx.x; tile < args.n_tiles; tile += gridDim.x)
         {
         const uint64_t row0 = tile * TILE;
-        const uint32_t rows = (uint32_t)((args.N - row0 < (uint64_t)TILE) ? args.N - row0 : TILE);
+        const uint32_t rows = tile_rows_at(args.N, row0, TILE);
         // every chunk tile in flight before the first byte is consumed
         for (uint32_t ji = 0; ji < args.n_jobs; ji++)
             {
@@ -449,15 +441,7 @@ __global__ __launch_bounds__(256) void gather_elems_kernel(const GatherArgs a)
             continue;
             }
         const uint64_t val = unpack_elem<false>((const char*)a.src + (r * a.M + c) * a.ssz, a.ssz, a.dsz, a.kind);
-        char* p = (char*)a.dst + (k * a.dst_stride + a.dst_col0 + c) * a.dsz;
-        if (a.dsz == 8)
-            *(uint64_t*)p = val;
-        else if (a.dsz == 4)
-            *(uint32_t*)p = (uint32_t)val;
-        else if (a.dsz == 2)
-            *(uint16_t*)p = (uint16_t)val;
-        else
-            *(uint8_t*)p = (uint8_t)val;
+        store_elem((char*)a.dst + (k * a.dst_stride + a.dst_col0 + c) * a.dsz, val, a.dsz);
         }
     }
 
@@ -473,69 +457,277 @@ __global__ __launch_bounds__(256) void fill_cols_kernel(const FillArgs a)
     if (row >= a.N || col >= 32 || !((a.colmask >> col) & 1u))
         return;
     const uint64_t r = a.order ? (uint64_t)a.order[row] : row;
-    char* p = (char*)a.dst + (r * a.stride + col) * a.dsz;
-    switch (a.dsz)
+    store_elem((char*)a.dst + (r * a.stride + col) * a.dsz, a.bits, a.dsz);
+    }
+
+// ------------------------------------------------------------------ host side: validation, the plans and their driver
+
+// Validate one job of the ABI and translate it; false: invalid.
+static bool make_unpack_job(const pgsd_unpack_job& q, const uint32_t* rows, const uint32_t* bad, UnpackJob* out)
+    {
+    const uint32_t ssz = (uint32_t)sizeof_type(q.src_type), dsz = (uint32_t)sizeof_type(q.dst.dst_type);
+    const bool s_int = q.src_type <= PGSD_TYPE_INT64, d_int = q.dst.dst_type <= PGSD_TYPE_INT64;
+    bool ok = q.src && q.dst.dst && ssz && dsz && q.M && q.M <= PACK_MAX_M && q.dst.dst_col0 + q.M <= q.dst.dst_stride
+              && (((uintptr_t)q.src) & 15) == 0 && (((uintptr_t)q.dst.dst) & (dsz - 1)) == 0
+              && (uint64_t)q.M * ssz <= PACK_MAX_ROWBYTES;
+    if (q.dst.bitcast)
+        ok = ok && ssz == dsz;
+    else
+        ok = ok && !(!s_int && d_int) && !(s_int && !d_int && ssz == 8);
+    ok = ok && !(q.dst.fill_rest && q.dst.dst_stride > 32); // the fill addresses columns with a 32-bit mask
+    ok = ok && !(rows && (q.dst.order || !bad));            // an indexed read gathers; it does not scatter too
+    if (!ok)
+        return false;
+    UnpackJob j;
+    memset(&j, 0, sizeof(j));
+    j.src = q.src;
+    j.dst = q.dst.dst;
+    j.order = q.dst.order;
+    j.M = q.M;
+    j.ssz = ssz;
+    j.dsz = dsz;
+    j.kind = conv_kind(q.src_type, q.dst.dst_type, q.dst.bitcast);
+    j.dst_stride = q.dst.dst_stride;
+    j.dst_col0 = q.dst.dst_col0;
+    j.magic = div_magic(q.M);
+    j.rowbytes = q.M * ssz;
+    j.fill_rest = q.dst.fill_rest ? 1u : 0u;
+    j.fill_bits = q.dst.fill_bits;
+    *out = j;
+    return true;
+    }
+
+// fn(i, e) for every run [i, e) of chunks of one destination array (the jobs are sorted by dst, their order kept)
+template<class F> static void for_each_dst_run(const std::vector<UnpackJob>& all, F fn)
+    {
+    for (size_t i = 0, e = 0; i < all.size(); i = e)
         {
-        case 1: *(uint8_t*)p = (uint8_t)a.bits; break;
-        case 2: *(uint16_t*)p = (uint16_t)a.bits; break;
-        case 4: *(uint32_t*)p = (uint32_t)a.bits; break;
-        default: *(uint64_t*)p = a.bits; break;
+        while (e < all.size() && all[e].dst == all[i].dst)
+            e++;
+        fn(i, e);
         }
     }
 
-// ---- row-per-lane unpack: which destination arrays it takes and how it is launched
-struct UnrowsPlan
+// ---- row-per-lane unpack
+template<int T, int U> static void launch_unrows_tu(UnrowsArgs a, bool f64, hipStream_t stream)
     {
-    UnrowsArgs args;
-    bool f64 = false;
-    };
+    a.n_blocks = (a.N + (uint64_t)T * U - 1) / ((uint64_t)T * U);
+    const dim3 grid((unsigned)a.n_blocks, a.n_groups);
+    if constexpr (T == 64 && U == 2) // the only shape with an indexed twin
+        if (a.rows)
+            {
+            if (f64)
+                hipLaunchKernelGGL((unpack_rows_kernel<T, U, true, true>), grid, dim3(T), 0, stream, a);
+            else
+                hipLaunchKernelGGL((unpack_rows_kernel<T, U, false, true>), grid, dim3(T), 0, stream, a);
+            return;
+            }
+    if (f64)
+        hipLaunchKernelGGL((unpack_rows_kernel<T, U, true, false>), grid, dim3(T), 0, stream, a);
+    else
+        hipLaunchKernelGGL((unpack_rows_kernel<T, U, false, false>), grid, dim3(T), 0, stream, a);
+    }
 
-static void launch_unrows(const UnrowsPlan& p, uint64_t N, hipStream_t stream)
+// false: the tuning names a pair outside PGSD_UNPACK_ROWS_SHAPES (read_tuning() lets none through)
+static bool launch_unrows(const UnrowsArgs& a, bool f64, hipStream_t stream)
     {
-    if (p.args.rows)
-        {
-        // an indexed read: the default shape only (the lane's loads are row-sized pieces at scattered rows)
-        UnrowsArgs a = p.args;
-        a.n_blocks = (N + 127) / 128;
-        const dim3 grid((unsigned)a.n_blocks, a.n_groups);
-        if (p.f64)
-            hipLaunchKernelGGL((unpack_rows_kernel<64, 2, true, true>), grid, dim3(64), 0, stream, a);
-        else
-            hipLaunchKernelGGL((unpack_rows_kernel<64, 2, false, true>), grid, dim3(64), 0, stream, a);
-        return;
-        }
     // measured (profiles/r02_lab_unpack.jsonl, r02_unpack_rows_final.jsonl): thin workgroups; 64 x 2 rows
-    // 102.4-103.0 us, 128 x 1 104.6-105.0 us, 256 x 2 105.9-106.0 us (10 M particles, stream events)
+    // 102.4-103.0 us, 128 x 1 104.6-105.0 us, 256 x 2 105.9-106.0 us (10 M particles, stream events).  An indexed read
+    // keeps that default (the lane's loads are row-sized pieces at scattered rows).
     int T = 64, U = 2;
     const PackTuning tune = tuning();
-    if (tune.unrows_t)
+    if (tune.unrows_t && !a.rows)
         T = tune.unrows_t, U = tune.unrows_u;
-    UnrowsArgs a = p.args;
-    a.n_blocks = (N + (uint64_t)T * U - 1) / ((uint64_t)T * U);
-    const dim3 grid((unsigned)a.n_blocks, a.n_groups);
-#define UNROWS_LAUNCH(TT, UU)                                                                                  \
-    if (T == TT && U == UU)                                                                                    \
-        {                                                                                                      \
-        if (p.f64)                                                                                             \
-            hipLaunchKernelGGL((unpack_rows_kernel<TT, UU, true, false>), grid, dim3(TT), 0, stream, a);              \
-        else                                                                                                   \
-            hipLaunchKernelGGL((unpack_rows_kernel<TT, UU, false, false>), grid, dim3(TT), 0, stream, a);             \
-        return;                                                                                                \
-        }
-    UNROWS_LAUNCH(128, 1)
-    UNROWS_LAUNCH(256, 1)
-    UNROWS_LAUNCH(256, 2)
-    UNROWS_LAUNCH(128, 2)
-    a.n_blocks = (N + 127) / 128;
-    const dim3 grid1((unsigned)a.n_blocks, a.n_groups);
-    if (p.f64)
-        hipLaunchKernelGGL((unpack_rows_kernel<64, 2, true, false>), grid1, dim3(64), 0, stream, a);
-    else
-        hipLaunchKernelGGL((unpack_rows_kernel<64, 2, false, false>), grid1, dim3(64), 0, stream, a);
-#undef UNROWS_LAUNCH
+#define UNROWS_SHAPE(TT, UU) \
+    if (T == TT && U == UU)  \
+        return launch_unrows_tu<TT, UU>(a, f64, stream), true;
+    PGSD_UNPACK_ROWS_SHAPES(UNROWS_SHAPE)
+#undef UNROWS_SHAPE
+    return false;
     }
 
-// One batch of <= UNPACK_MAX_JOBS validated chunks -> one launch.
+// Does the row-per-lane kernel take the destination array fed by the chunks [i, e) in the pass for f32 (f64 = false) or
+// f64 destinations?  Rows of four 4-byte elements (or four doubles restored from f32 chunks) fed by one or two chunks of
+// 4-byte elements on disjoint columns, no scatter index; or a dense same-type array (the chunk IS the array: any element
+// size, any row width), a plain copy that rides along in the first pass and has no indexed twin.  Fills *out in if so.
+static bool unrows_group(const std::vector<UnpackJob>& all, size_t i, size_t e, bool f64, const uint32_t* rows, uint64_t N,
+                         UnrowsGroup* out)
+    {
+    const UnpackJob& j0 = all[i];
+    const size_t n = e - i;
+    bool ok = n <= 2 && (((uintptr_t)j0.dst) & 15) == 0;
+    for (size_t k = i; k < e && ok; k++)
+        ok = all[k].order == nullptr && all[k].dst_stride == j0.dst_stride && all[k].dsz == j0.dsz
+             && (((uintptr_t)all[k].src) & 15) == 0;
+    if (!ok)
+        return false;
+    UnrowsGroup g;
+    memset(&g, 0, sizeof(g));
+    g.dst = j0.dst;
+    g.a = j0.src;
+    if (n == 1 && j0.kind == PACK_BITS && j0.ssz == j0.dsz && j0.dst_col0 == 0 && j0.M == j0.dst_stride)
+        {
+        if (f64 || rows)
+            return false;
+        const uint64_t bytes = N * (uint64_t)j0.M * j0.ssz;
+        g.copy_vecs = bytes >> 4;
+        g.copy_tail = (uint32_t)(bytes & 15);
+        *out = g;
+        return true;
+        }
+    ok = j0.dst_stride == 4 && j0.dsz == (f64 ? 8u : 4u);
+    for (size_t k = i; k < e && ok; k++)
+        ok = all[k].ssz == 4 && all[k].kind == (uint32_t)(f64 ? PACK_F2F : PACK_BITS) && all[k].M <= 4;
+    if (ok && n == 2) // disjoint columns: no "later chunk wins" question inside a row
+        ok = j0.dst_col0 + j0.M <= all[i + 1].dst_col0 || all[i + 1].dst_col0 + all[i + 1].M <= j0.dst_col0;
+    if (!ok)
+        return false;
+    for (size_t k = i; k < e && !g.fill_on; k++)
+        if (all[k].fill_rest)
+            {
+            g.fill_on = 1;
+            g.fill_lo = (uint32_t)all[k].fill_bits;
+            g.fill_hi = (uint32_t)(all[k].fill_bits >> 32);
+            }
+    // `a` = the chunk of the lower columns (xyz before w: the kernel's static hot shape)
+    const UnpackJob& lo = (n == 2 && all[i + 1].dst_col0 < j0.dst_col0) ? all[i + 1] : j0;
+    g.a = lo.src;
+    g.a_nw = lo.M;
+    g.a_col0 = lo.dst_col0;
+    if (n == 2)
+        {
+        const UnpackJob& hi = (&lo == &j0) ? all[i + 1] : j0;
+        g.b = hi.src;
+        g.b_nw = hi.M;
+        g.b_col0 = hi.dst_col0;
+        }
+    *out = g;
+    return true;
+    }
+
+// 1. The row-per-lane kernel takes every destination array it can (unrows_group): one launch per conversion class (the
+//    f32 pass, then the f64 pass) and per ROWS_MAX_GROUPS arrays.  What it took leaves `all`.
+static bool enqueue_unrows(std::vector<UnpackJob>& all, uint64_t N, const uint32_t* rows, uint64_t src_N, uint32_t* bad,
+                           hipStream_t stream)
+    {
+    std::vector<bool> taken(all.size(), false);
+    for (int f64 = 0; f64 < 2; f64++)
+        while (true)
+            {
+            UnrowsArgs a;
+            memset(&a, 0, sizeof(a));
+            a.N = N;
+            a.rows = rows;
+            a.src_N = src_N;
+            a.bad = bad;
+            for_each_dst_run(all, [&](size_t i, size_t e) {
+                if (taken[i] || a.n_groups == ROWS_MAX_GROUPS || !unrows_group(all, i, e, f64 != 0, rows, N, &a.g[a.n_groups]))
+                    return;
+                a.n_groups++;
+                std::fill(taken.begin() + i, taken.begin() + e, true);
+            });
+            if (a.n_groups == 0)
+                break;
+            if (!launch_unrows(a, f64 != 0, stream))
+                return false;
+            }
+    std::vector<UnpackJob> rest;
+    for (size_t i = 0; i < all.size(); i++)
+        if (!taken[i])
+            rest.push_back(all[i]);
+    all.swap(rest);
+    return true;
+    }
+
+// 2. The fills the remaining (tiled / generic) chunks asked for: one pass per destination array over the columns none of
+//    ITS chunks writes, ahead of the chunks on the stream.
+static void enqueue_fills(const std::vector<UnpackJob>& all, uint64_t N, hipStream_t stream)
+    {
+    for_each_dst_run(all, [&](size_t i, size_t e) {
+        uint32_t covered = 0;
+        const UnpackJob* want = nullptr;
+        for (size_t k = i; k < e; k++)
+            {
+            for (uint32_t c = 0; c < all[k].M && all[k].dst_col0 + c < 32; c++)
+                covered |= 1u << (all[k].dst_col0 + c);
+            if (all[k].fill_rest && !want)
+                want = &all[k];
+            }
+        if (!want || want->dst_stride > 32)
+            return;
+        const uint32_t colmask = ~covered & (want->dst_stride >= 32 ? 0xffffffffu : ((1u << want->dst_stride) - 1u));
+        const FillArgs fa = {want->dst, want->order, N, want->fill_bits, want->dst_stride, want->dsz, colmask, 0};
+        const uint64_t lanes = N * (uint64_t)fa.stride;
+        if (fa.colmask)
+            hipLaunchKernelGGL(fill_cols_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, fa);
+    });
+    }
+
+// 3a. An indexed read: what the row-per-lane kernel did not take, element by element, in the jobs' order ("the later
+//     chunk wins" by stream order).
+static void enqueue_gathers(const std::vector<UnpackJob>& all, uint64_t N, const uint32_t* rows, uint64_t src_N,
+                            uint32_t* bad, hipStream_t stream)
+    {
+    for (const UnpackJob& j : all)
+        {
+        const GatherArgs ga = {j.src, j.dst, rows, bad, N, src_N, j.M, j.ssz, j.dsz, j.kind, j.dst_stride, j.dst_col0};
+        const uint64_t blocks = std::min<uint64_t>((N * (uint64_t)j.M + 255) / 256, (uint64_t)num_cus() * 16);
+        hipLaunchKernelGGL(gather_elems_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(256), 0, stream, ga);
+        }
+    }
+
+// Destination array of chunk i of a tiled launch: do chunks of the launch, seen through one shape, write every column of
+// its rows exactly once?  Then *g maps each column to its chunk.
+static bool assembled_group(const UnpackArgs& args, uint32_t i, UnpackGroup* g)
+    {
+    const UnpackJob& a = args.j[i];
+    uint8_t covered[UNPACK_MAX_ROW_COLS] = {0};
+    uint32_t n_cov = 0;
+    for (uint32_t k = i; k < args.n_jobs; k++)
+        {
+        const UnpackJob& b = args.j[k];
+        if (b.dst != a.dst || b.in_group)
+            continue;
+        if (b.order != a.order || b.dst_stride != a.dst_stride || b.dsz != a.dsz)
+            return false; // same array seen through different shapes: leave it to the element path
+        for (uint32_t c = 0; c < b.M; c++, n_cov++)
+            {
+            if (covered[b.dst_col0 + c])
+                return false;
+            covered[b.dst_col0 + c] = 1;
+            g->col_job[b.dst_col0 + c] = (uint8_t)k;
+            g->col_off[b.dst_col0 + c] = (uint8_t)c;
+            }
+        }
+    return n_cov == a.dst_stride;
+    }
+
+// Destination arrays whose rows the launch restores completely -- rows of 16, 32 or 64 bytes, 4- or 8-byte elements --
+// are assembled in registers and stored whole; their chunks are marked in_group.
+static void find_assembled_groups(UnpackArgs& args)
+    {
+    for (uint32_t i = 0; i < args.n_jobs && args.n_groups < UNPACK_MAX_GROUPS; i++)
+        {
+        const UnpackJob& a = args.j[i];
+        const uint32_t rowbytes = a.dst_stride * a.dsz;
+        UnpackGroup g;
+        memset(&g, 0, sizeof(g));
+        if (a.in_group || (a.dsz != 4 && a.dsz != 8) || (rowbytes != 16 && rowbytes != 32 && rowbytes != 64)
+            || (((uintptr_t)a.dst) & 15) != 0 || !assembled_group(args, i, &g))
+            continue;
+        g.dst = a.dst;
+        g.order = a.order;
+        g.stride = a.dst_stride;
+        g.dsz = a.dsz;
+        g.vec_shift = rowbytes == 16 ? 0u : (rowbytes == 32 ? 1u : 2u);
+        for (uint32_t k = i; k < args.n_jobs; k++)
+            if (args.j[k].dst == a.dst)
+                args.j[k].in_group = 1;
+        args.g[args.n_groups++] = g;
+        }
+    }
+
+// One batch of <= UNPACK_MAX_JOBS validated chunks -> one launch of the LDS-tiled kernel.
 static void launch_unpack_batch(const std::vector<UnpackJob>& jobs, uint64_t N, hipStream_t stream)
     {
     UnpackArgs args;
@@ -550,302 +742,35 @@ static void launch_unpack_batch(const std::vector<UnpackJob>& jobs, uint64_t N, 
         sum_rowbytes += jobs[i].rowbytes;
         w32 = w32 && jobs[i].ssz == 4 && jobs[i].dsz == 4 && jobs[i].kind == PACK_BITS;
         }
-    // destination arrays whose rows this batch restores completely: dst row of 16, 32 or 64 bytes,
-    // 4- or 8-byte elements, every column written by exactly one chunk
-    for (uint32_t i = 0; i < args.n_jobs && args.n_groups < UNPACK_MAX_GROUPS; i++)
-        {
-        UnpackJob& a = args.j[i];
-        if (a.in_group)
-            continue;
-        const uint32_t rowbytes = a.dst_stride * a.dsz;
-        if ((a.dsz != 4 && a.dsz != 8) || (rowbytes != 16 && rowbytes != 32 && rowbytes != 64)
-            || (((uintptr_t)a.dst) & 15) != 0)
-            continue;
-        UnpackGroup g;
-        memset(&g, 0, sizeof(g));
-        uint8_t covered[UNPACK_MAX_ROW_COLS] = {0};
-        uint32_t n_cov = 0;
-        bool clean = true;
-        for (uint32_t k = i; k < args.n_jobs; k++)
-            {
-            const UnpackJob& b = args.j[k];
-            if (b.dst != a.dst || b.in_group)
-                continue;
-            if (b.order != a.order || b.dst_stride != a.dst_stride || b.dsz != a.dsz)
-                {
-                clean = false; // same array seen through different shapes: leave it to the element path
-                break;
-                }
-            for (uint32_t c = 0; c < b.M; c++)
-                {
-                if (covered[b.dst_col0 + c])
-                    clean = false;
-                covered[b.dst_col0 + c] = 1;
-                g.col_job[b.dst_col0 + c] = (uint8_t)k;
-                g.col_off[b.dst_col0 + c] = (uint8_t)c;
-                n_cov++;
-                }
-            }
-        if (!clean || n_cov != a.dst_stride)
-            continue;
-        g.dst = a.dst;
-        g.order = a.order;
-        g.stride = a.dst_stride;
-        g.dsz = a.dsz;
-        g.vec_shift = rowbytes == 16 ? 0u : (rowbytes == 32 ? 1u : 2u);
-        for (uint32_t k = i; k < args.n_jobs; k++)
-            if (args.j[k].dst == a.dst)
-                args.j[k].in_group = 1;
-        args.g[args.n_groups++] = g;
-        }
+    find_assembled_groups(args);
     // measured (profiles/r01_unpack_sweep.log): the unpack wants more resident workgroups than the
     // pack -- 512-row tiles x 8 workgroups per CU beat 1024 x 4 by 8 % at 10 M rows; launches too small
     // to fill the chip twice keep the larger tile
-    uint32_t tile = 16, tile_cap = N > (1ull << 21) ? 512 : 1024;
-    uint64_t per_cu = 8;
     const PackTuning tune = tuning(); // tuning sweeps (tools/unpack_bench.py)
-    if (tune.unpack_tile_cap)
-        tile_cap = tune.unpack_tile_cap;
-    per_cu = tune.unpack_per_cu;
-    while (tile * 2 <= tile_cap && (uint64_t)tile * 2 * sum_rowbytes <= UNPACK_LDS_BYTES)
-        tile <<= 1;
-    args.tile_rows = tile;
-    args.n_tiles = (N + tile - 1) / tile;
+    const uint32_t tile_cap = tune.unpack_tile_cap ? tune.unpack_tile_cap : (N > (1ull << 21) ? 512 : 1024);
+    const TileGeometry geo = tile_geometry(N, sum_rowbytes, tile_cap, UNPACK_LDS_BYTES);
+    args.tile_rows = geo.tile_rows;
+    args.n_tiles = geo.n_tiles;
     size_t lds_bytes = UNPACK_TABLE_BYTES; // the column table of the kernel sits in front
     for (uint32_t i = 0; i < args.n_jobs; i++)
         {
         args.j[i].lds_off = (uint32_t)lds_bytes;
-        lds_bytes += (size_t)tile * args.j[i].rowbytes; // tile is a multiple of 16: stays 16-byte aligned
+        lds_bytes += (size_t)geo.tile_rows * args.j[i].rowbytes; // tile is a multiple of 16: stays 16-byte aligned
         }
-    uint64_t resident = lds_bytes ? (160u * 1024u) / lds_bytes : 8;
-    uint64_t blocks = args.n_tiles;
-    uint64_t cap = (uint64_t)num_cus() * std::max<uint64_t>(1, std::min<uint64_t>(per_cu, resident));
-    if (blocks > cap)
-        blocks = cap;
+    const dim3 grid((unsigned)blocks_for(args.n_tiles, lds_bytes, tune.unpack_per_cu));
     if (w32)
-        hipLaunchKernelGGL(unpack_tiles_kernel<true>, dim3((unsigned)blocks), dim3(PACK_THREADS), lds_bytes, stream, args);
+        hipLaunchKernelGGL(unpack_tiles_kernel<true>, grid, dim3(PACK_THREADS), lds_bytes, stream, args);
     else
-        hipLaunchKernelGGL(unpack_tiles_kernel<false>, dim3((unsigned)blocks), dim3(PACK_THREADS), lds_bytes, stream, args);
+        hipLaunchKernelGGL(unpack_tiles_kernel<false>, grid, dim3(PACK_THREADS), lds_bytes, stream, args);
     }
 
-void warm_unpack_kernels()
+// 3b. Everything else through the LDS-tiled kernel, in batches that fit UnpackArgs and the LDS.
+static void enqueue_tiled(const std::vector<UnpackJob>& all, uint64_t N, hipStream_t stream)
     {
-    hipFuncAttributes attr;
-    (void)hipFuncGetAttributes(&attr, (const void*)fill_cols_kernel);
-    (void)hipGetLastError();
-    }
-
-int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipStream_t stream, std::string* err,
-                  const uint32_t* rows, uint64_t src_N, uint32_t* bad)
-    {
-    // whatever an earlier call of this thread left in the runtime's last-error slot (a failed hipMalloc, the caller's own
-    // calls) is not this launch's: the slot is read again right behind the launches
-    (void)hipGetLastError();
-
-    if (n_jobs == 0 || N == 0)
-        return PGSD_SUCCESS;
-    std::vector<UnpackJob> all;
-    all.reserve(n_jobs);
-    for (uint32_t i = 0; i < n_jobs; i++)
-        {
-        const pgsd_unpack_job& q = jobs[i];
-        const uint32_t ssz = (uint32_t)sizeof_type(q.src_type), dsz = (uint32_t)sizeof_type(q.dst.dst_type);
-        const bool s_int = q.src_type <= PGSD_TYPE_INT64, d_int = q.dst.dst_type <= PGSD_TYPE_INT64;
-        bool ok = q.src && q.dst.dst && ssz && dsz && q.M && q.M <= PACK_MAX_M
-                  && q.dst.dst_col0 + q.M <= q.dst.dst_stride && (((uintptr_t)q.src) & 15) == 0
-                  && (((uintptr_t)q.dst.dst) & (dsz - 1)) == 0 && (uint64_t)q.M * ssz <= PACK_MAX_ROWBYTES;
-        if (q.dst.bitcast)
-            ok = ok && ssz == dsz;
-        else
-            ok = ok && !(!s_int && d_int) && !(s_int && !d_int && ssz == 8);
-        ok = ok && !(q.dst.fill_rest && q.dst.dst_stride > 32); // the fill addresses columns with a 32-bit mask
-        ok = ok && !(rows && (q.dst.order || !bad));            // an indexed read gathers; it does not scatter too
-        if (!ok)
-            {
-            if (err)
-                *err = "invalid unpack job (types, columns, alignment or pointers)";
-            return PGSD_ERROR_INVALID_ARGUMENT;
-            }
-        UnpackJob j;
-        memset(&j, 0, sizeof(j));
-        j.src = q.src;
-        j.dst = q.dst.dst;
-        j.order = q.dst.order;
-        j.M = q.M;
-        j.ssz = ssz;
-        j.dsz = dsz;
-        j.kind = conv_kind(q.src_type, q.dst.dst_type, q.dst.bitcast);
-        j.dst_stride = q.dst.dst_stride;
-        j.dst_col0 = q.dst.dst_col0;
-        j.magic = q.M == 1 ? 0u : (uint32_t)(((1ull << 32) + q.M - 1) / q.M);
-        j.rowbytes = q.M * ssz;
-        j.fill_rest = q.dst.fill_rest ? 1u : 0u;
-        j.fill_bits = q.dst.fill_bits;
-        all.push_back(j);
-        }
-    // chunks of one destination array next to each other (their relative order is kept)
-    std::stable_sort(all.begin(), all.end(), [](const UnpackJob& a, const UnpackJob& b) { return (uintptr_t)a.dst < (uintptr_t)b.dst; });
-    // 1. destination arrays the row-per-lane kernel takes: rows of four 4-byte elements (or four doubles
-    //    restored from f32 chunks) fed by one or two chunks of 4-byte elements on disjoint columns, no
-    //    scatter index; plus dense same-type arrays (the chunk IS the array).  One launch per conversion
-    //    class; everything else goes to the LDS-tiled kernel below.
-    if (N < (1ull << 31) && !tuning().unpack_tiles)
-        {
-        std::vector<bool> taken(all.size(), false);
-        for (int f64 = 0; f64 < 2; f64++)
-            {
-            while (true)
-                {
-                UnrowsPlan plan;
-                memset(&plan.args, 0, sizeof(plan.args));
-                plan.args.N = N;
-                plan.args.rows = rows;
-                plan.args.src_N = src_N;
-                plan.args.bad = bad;
-                plan.f64 = f64 != 0;
-                for (size_t i = 0; i < all.size();)
-                    {
-                    size_t e = i; // [i, e) = the chunks of one destination array (sorted by dst, order kept)
-                    while (e < all.size() && all[e].dst == all[i].dst)
-                        e++;
-                    const UnpackJob& j0 = all[i];
-                    const size_t n = e - i;
-                    bool ok = !taken[i] && n <= 2 && plan.args.n_groups < ROWS_MAX_GROUPS && (((uintptr_t)j0.dst) & 15) == 0;
-                    for (size_t k = i; k < e && ok; k++)
-                        {
-                        const UnpackJob& j = all[k];
-                        ok = j.order == nullptr && j.dst_stride == j0.dst_stride && j.dsz == j0.dsz
-                             && (((uintptr_t)j.src) & 15) == 0;
-                        }
-                    // a dense array of the chunk's own type (any element size, any row width): a plain copy
-                    const bool dense = ok && n == 1 && j0.kind == PACK_BITS && j0.ssz == j0.dsz && j0.dst_col0 == 0
-                                       && j0.M == j0.dst_stride;
-                    if (dense)
-                        ok = f64 == 0 && !rows; // rides along in the launch of the first pass (no indexed twin)
-                    else if (ok)
-                        {
-                        ok = j0.dst_stride == 4 && (f64 ? j0.dsz == 8 : j0.dsz == 4);
-                        for (size_t k = i; k < e && ok; k++)
-                            ok = all[k].ssz == 4 && all[k].kind == (uint32_t)(f64 ? PACK_F2F : PACK_BITS) && all[k].M <= 4;
-                        if (ok && n == 2) // disjoint columns: no "later chunk wins" question inside a row
-                            ok = all[i].dst_col0 + all[i].M <= all[i + 1].dst_col0
-                                 || all[i + 1].dst_col0 + all[i + 1].M <= all[i].dst_col0;
-                        }
-                    if (ok)
-                        {
-                        UnrowsGroup& g = plan.args.g[plan.args.n_groups++];
-                        g.dst = j0.dst;
-                        g.a = j0.src;
-                        for (size_t k = i; k < e && !dense; k++)
-                            if (all[k].fill_rest && !g.fill_on)
-                                {
-                                g.fill_on = 1;
-                                g.fill_lo = (uint32_t)all[k].fill_bits;
-                                g.fill_hi = (uint32_t)(all[k].fill_bits >> 32);
-                                }
-                        if (dense)
-                            {
-                            const uint64_t bytes = N * (uint64_t)j0.M * j0.ssz;
-                            g.copy_vecs = bytes >> 4;
-                            g.copy_tail = (uint32_t)(bytes & 15);
-                            }
-                        else
-                            {
-                            // `a` = the chunk of the lower columns (xyz before w: the kernel's static hot shape)
-                            const UnpackJob& lo = (n == 2 && all[i + 1].dst_col0 < j0.dst_col0) ? all[i + 1] : j0;
-                            g.a = lo.src;
-                            g.a_nw = lo.M;
-                            g.a_col0 = lo.dst_col0;
-                            if (n == 2)
-                                {
-                                const UnpackJob& hi = (&lo == &j0) ? all[i + 1] : j0;
-                                g.b = hi.src;
-                                g.b_nw = hi.M;
-                                g.b_col0 = hi.dst_col0;
-                                }
-                            }
-                        for (size_t k = i; k < e; k++)
-                            taken[k] = true;
-                        }
-                    i = e;
-                    }
-                if (plan.args.n_groups == 0)
-                    break;
-                launch_unrows(plan, N, stream);
-                }
-            }
-        std::vector<UnpackJob> rest;
-        for (size_t i = 0; i < all.size(); i++)
-            if (!taken[i])
-                rest.push_back(all[i]);
-        all.swap(rest);
-        }
-    // fills the remaining (tiled / generic) chunks asked for: one pass per destination array over the columns
-    // none of ITS chunks writes, ahead of the chunks on the stream
-    for (size_t i = 0; i < all.size();)
-        {
-        size_t e = i;
-        while (e < all.size() && all[e].dst == all[i].dst)
-            e++;
-        uint32_t covered = 0;
-        const UnpackJob* want = nullptr;
-        for (size_t k = i; k < e; k++)
-            {
-            for (uint32_t c = 0; c < all[k].M && all[k].dst_col0 + c < 32; c++)
-                covered |= 1u << (all[k].dst_col0 + c);
-            if (all[k].fill_rest && !want)
-                want = &all[k];
-            }
-        if (want && want->dst_stride <= 32)
-            {
-            FillArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            fa.dst = want->dst;
-            fa.order = want->order;
-            fa.N = N;
-            fa.bits = want->fill_bits;
-            fa.stride = want->dst_stride;
-            fa.dsz = want->dsz;
-            fa.colmask = ~covered & (want->dst_stride >= 32 ? 0xffffffffu : ((1u << want->dst_stride) - 1u));
-            if (fa.colmask)
-                {
-                const uint64_t lanes = N * (uint64_t)fa.stride;
-                hipLaunchKernelGGL(fill_cols_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, fa);
-                }
-            }
-        i = e;
-        }
-    if (rows)
-        {
-        // an indexed read: what the row-per-lane kernel did not take, element by element, in the jobs' order ("the
-        // later chunk wins" by stream order)
-        for (const UnpackJob& j : all)
-            {
-            GatherArgs ga;
-            memset(&ga, 0, sizeof(ga));
-            ga.src = j.src;
-            ga.dst = j.dst;
-            ga.rows = rows;
-            ga.bad = bad;
-            ga.n = N;
-            ga.src_N = src_N;
-            ga.M = j.M;
-            ga.ssz = j.ssz;
-            ga.dsz = j.dsz;
-            ga.kind = j.kind;
-            ga.dst_stride = j.dst_stride;
-            ga.dst_col0 = j.dst_col0;
-            const uint64_t lanes = N * (uint64_t)j.M;
-            const uint64_t blocks = std::min<uint64_t>((lanes + 255) / 256, (uint64_t)num_cus() * 16);
-            hipLaunchKernelGGL(gather_elems_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(256), 0, stream, ga);
-            }
-        all.clear();
-        }
     std::vector<UnpackJob> batch;
     uint32_t sum_rowbytes = 0;
-    for (size_t i = 0; i < all.size(); i++)
+    for (const UnpackJob& j : all)
         {
-        const UnpackJob& j = all[i];
         // a chunk that rewrites columns an earlier chunk of the batch wrote goes to the next launch:
         // "the later chunk wins" then holds by stream order
         bool overlap = false;
@@ -864,13 +789,40 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
         }
     if (!batch.empty())
         launch_unpack_batch(batch, N, stream);
-    hipError_t e = hipGetLastError();
+    }
+
+void warm_unpack_kernels()
+    {
+    hipFuncAttributes attr;
+    (void)hipFuncGetAttributes(&attr, (const void*)fill_cols_kernel);
+    (void)hipGetLastError();
+    }
+
+int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipStream_t stream, std::string* err,
+                  const uint32_t* rows, uint64_t src_N, uint32_t* bad)
+    {
+    // whatever an earlier call of this thread left in the runtime's last-error slot (a failed hipMalloc, the caller's own
+    // calls) is not this launch's: the slot is read again right behind the launches
+    (void)hipGetLastError();
+    if (n_jobs == 0 || N == 0)
+        return PGSD_SUCCESS;
+    std::vector<UnpackJob> all(n_jobs);
+    for (uint32_t i = 0; i < n_jobs; i++)
+        if (!make_unpack_job(jobs[i], rows, bad, &all[i]))
+            return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "invalid unpack job (types, columns, alignment or pointers)");
+    // chunks of one destination array next to each other (their relative order is kept)
+    std::stable_sort(all.begin(), all.end(), [](const UnpackJob& a, const UnpackJob& b) { return (uintptr_t)a.dst < (uintptr_t)b.dst; });
+    // stream order: the row-per-lane launches, the fills, then the gathers of an indexed read or the tiled batches
+    if (N < (1ull << 31) && !tuning().unpack_tiles && !enqueue_unrows(all, N, rows, src_N, bad, stream))
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "unpack: no row-per-lane kernel of the tuned shape");
+    enqueue_fills(all, N, stream);
+    if (rows)
+        enqueue_gathers(all, N, rows, src_N, bad, stream);
+    else
+        enqueue_tiled(all, N, stream);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        {
-        if (err)
-            *err = std::string("unpack kernel launch failed: ") + hipGetErrorString(e);
-        return PGSD_ERROR_DEVICE;
-        }
+        return launch_fail(err, PGSD_ERROR_DEVICE, std::string("unpack kernel launch failed: ") + hipGetErrorString(e));
     return PGSD_SUCCESS;
     }
     } // namespace pgsd_amd
