@@ -480,7 +480,7 @@ bool DevicePipeline::direct_reserve(size_t bytes)
     }
 
 // Everything staged is given back: the arenas and the direct arena are rewound, the per-frame events return to their
-// pools, the position rows select_domain() kept (they lie in that staging) are forgotten.  The callers -- drain(),
+// pools, the chunks a selection kept (they lie in that staging) are forgotten.  The callers -- drain(),
 // wait_read(), recycle_staging() -- each know when nothing staged is needed any more.
 void DevicePipeline::reset_staging()
     {
@@ -488,7 +488,7 @@ void DevicePipeline::reset_staging()
     for (auto& a : m_res.arenas)
         a.used = 0;
     m_dused = 0;
-    m_kept_src = nullptr;
+    m_kept.clear();
     }
 
 // Staging is recycled when nothing is in flight (cheap, also serves asynchronously sealed
@@ -665,6 +665,12 @@ int device_pipeline_select_domain(DevicePipeline* p, long long file_offset, size
                                   uint32_t* out_rows, uint64_t* out_count, std::string* err)
     {
     return report(p, p->select_domain(file_offset, bytes, d, out_rows, out_count), err, true);
+    }
+
+int device_pipeline_select_where(DevicePipeline* p, const ChunkRange* ranges, const WhereArgs& w, uint32_t* out_rows,
+                                 uint64_t* out_count, std::string* err)
+    {
+    return report(p, p->select_where(ranges, w, out_rows, out_count), err, true);
     }
 
 void device_pipeline_set_source_stream(DevicePipeline* p, void* stream)

@@ -140,6 +140,7 @@ class DevicePipeline
                          uint64_t n);
     int plan_rows(RowPlan& plan, std::string* err);
     int select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count);
+    int select_where(const ChunkRange* ranges, WhereArgs w, uint32_t* out_rows, uint64_t* out_count);
     int wait_read();
 
     // ---- accessors ----
@@ -168,7 +169,7 @@ class DevicePipeline
         hipEvent_t all_copied = nullptr; // behind the last H2D piece; null: nothing to wait for, the bytes are there
         const uint32_t* rows;            // indexed read: N destination rows gathered from rows[] of the src_N staged ones
         uint64_t src_N;
-        bool stage_only;                 // staged for select_domain(), which waits for the pieces itself: no unpack
+        bool stage_only;                 // staged for a selection, which waits for the pieces itself: no unpack
         };
     struct Staged
         {
@@ -231,6 +232,8 @@ class DevicePipeline
     void read_piece(std::shared_ptr<ReadReq> req, char* dst, size_t n, std::shared_ptr<std::vector<ReadSpan>> parts);
     void read_done();
     void launch_pending_unpacks();
+    const void* kept_chunk(long long file_offset, size_t bytes) const;
+    int stage_chunks(const ChunkRange* ranges, size_t n, uint64_t N, const void** src);
 
     // Who guards what.  m_mutex: the slab ring's free list, the job queue, tickets, committed direct chunks, every event
     // list and pool, both outstanding counts, m_stop, the error state, the statistics.  m_copy_mutex: enqueues on the
@@ -287,9 +290,13 @@ class DevicePipeline
     std::atomic<uint64_t> m_h2d_bytes {0};
     uint32_t* m_bad_host = nullptr;          // indexed reads: set by a gather that met a row outside its chunk (pinned)
     uint32_t* m_bad_dev = nullptr;           // ... its device alias
-    const void* m_kept_src = nullptr;        // select_domain(): the staged position rows, kept until the next wait_read
-    long long m_kept_offset = 0;
-    size_t m_kept_bytes = 0;
+    struct Kept                              // a whole chunk a selection staged, kept until the next wait_read
+        {
+        const void* src;
+        long long file_offset;
+        size_t bytes;
+        };
+    std::vector<Kept> m_kept;
 
     // error state (m_mutex)
     std::string m_error;

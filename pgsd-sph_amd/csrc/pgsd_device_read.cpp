@@ -1,6 +1,6 @@
 // pgsd_device_read.cpp -- the read side of the device pipeline: file -> pinned slab (pread, shared reader threads) ->
 // HBM staging (H2D on the copy stream) -> one deferred unpack launch per wait_read(); the direct road of small reads;
-// sparse (planned) reads, indexed reads and domain selection on top of the same staging.
+// sparse (planned) reads, indexed reads, domain and group selection on top of the same staging.
 #include "pgsd_device_impl.hpp"
 
 #include <cerrno>
@@ -277,49 +277,88 @@ int DevicePipeline::plan_rows(RowPlan& plan, std::string* err)
     return rc;
     }
 
-// Indexed read: the whole chunk is staged as for a slab read -- or, when it is the position chunk the last
-// select_domain() staged (same file range, no wait_read since), taken from that staging without reading the file
-// again -- and wait_read's deferred launch gathers rows[0 .. n) of it.
+// Indexed read: the whole chunk is staged as for a slab read -- or, when it is a chunk the last selection staged (same
+// file range, no wait_read since), taken from that staging without reading the file again -- and wait_read's deferred
+// launch gathers rows[0 .. n) of it.
 int DevicePipeline::read_rows_submit(long long file_offset, size_t bytes, pgsd_unpack_job job, uint64_t src_N,
                                      const uint32_t* rows, uint64_t n)
     {
-    if (!(m_kept_src && m_kept_offset == file_offset && m_kept_bytes == bytes))
+    const void* kept = kept_chunk(file_offset, bytes);
+    if (!kept)
         return read_submit(file_offset, bytes, job, n, rows, src_N);
     int rc = enter();
     if (rc != PGSD_SUCCESS)
         return rc;
-    job.src = m_kept_src;
-    defer_unpack(make_read_req(job, n, rows, src_N, false, 0)); // (select_domain() synchronised the copies)
+    job.src = kept;
+    defer_unpack(make_read_req(job, n, rows, src_N, false, 0)); // (the selection synchronised the copies)
     return PGSD_SUCCESS;
     }
 
-// Domain selection: stage the position chunk (file -> pinned -> HBM, or the direct road), select on the pack stream,
-// synchronise.  The staged rows are kept until the next wait_read for an indexed read of the same chunk.
+const void* DevicePipeline::kept_chunk(long long file_offset, size_t bytes) const
+    {
+    for (const Kept& k : m_kept)
+        if (k.file_offset == file_offset && k.bytes == bytes)
+            return k.src;
+    return nullptr;
+    }
+
+// The n whole chunks of a selection (N rows each) into HBM (file -> pinned -> HBM, or the direct road): src[i] receives
+// chunk i's staged rows, which the pack stream may read on return.  A chunk that is kept already -- by an earlier
+// selection, or because an earlier entry of `ranges` names it -- is not read again; every chunk is kept until the next
+// wait_read.
+int DevicePipeline::stage_chunks(const ChunkRange* ranges, size_t n, uint64_t N, const void** src)
+    {
+    std::vector<std::shared_ptr<ReadReq>> reqs;
+    const size_t kept_before = m_kept.size();
+    int rc = PGSD_SUCCESS;
+    for (size_t i = 0; i < n && rc == PGSD_SUCCESS; i++)
+        {
+        src[i] = kept_chunk(ranges[i].file_offset, ranges[i].bytes);
+        if (src[i])
+            continue;
+        std::shared_ptr<ReadReq> req;
+        pgsd_unpack_job job;
+        memset(&job, 0, sizeof(job));
+        const ReadSpan whole = {ranges[i].file_offset, ranges[i].bytes, 0};
+        rc = read_submit_spans(&whole, 1, ranges[i].bytes, job, N, nullptr, 0, true, &req);
+        if (rc == PGSD_SUCCESS && req)
+            {
+            src[i] = req->job.src;
+            m_kept.push_back({src[i], ranges[i].file_offset, ranges[i].bytes});
+            reqs.push_back(req);
+            }
+        }
+    // (also after a refused submission: the pieces of the chunks before it are on their way)
+    std::unique_lock<std::mutex> lk(m_mutex);
+    m_cv_done.wait(lk, [this] { return m_reads_outstanding == 0; });
+    lk.unlock();
+    if (rc == PGSD_SUCCESS && failed())
+        rc = failure_code();
+    for (size_t i = 0; i < reqs.size() && rc == PGSD_SUCCESS; i++)
+        if (reqs[i]->all_copied && hipStreamWaitEvent(m_res.pack_stream, reqs[i]->all_copied, 0) != hipSuccess)
+            {
+            fail("read pipeline event: hipStreamWaitEvent failed");
+            rc = PGSD_ERROR_DEVICE;
+            }
+    for (size_t i = 0; i < n && rc == PGSD_SUCCESS; i++)
+        if (!src[i])
+            rc = failure_code();
+    if (rc != PGSD_SUCCESS)
+        m_kept.resize(kept_before);
+    return rc;
+    }
+
+// Domain selection: stage the position chunk, select on the pack stream, synchronise.  The staged rows are kept until
+// the next wait_read for an indexed read of the same chunk.
 int DevicePipeline::select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count)
     {
     int rc = enter();
     if (rc != PGSD_SUCCESS)
         return rc;
-    if (m_kept_src && m_kept_offset == file_offset && m_kept_bytes == bytes)
-        d.pos = m_kept_src;
-    else
-        {
-        std::shared_ptr<ReadReq> req;
-        pgsd_unpack_job job;
-        memset(&job, 0, sizeof(job));
-        const ReadSpan whole = {file_offset, bytes, 0};
-        rc = read_submit_spans(&whole, 1, bytes, job, d.N, nullptr, 0, true, &req);
-        if (rc != PGSD_SUCCESS)
-            return rc;
-        std::unique_lock<std::mutex> lk(m_mutex);
-        m_cv_done.wait(lk, [this] { return m_reads_outstanding == 0; });
-        lk.unlock();
-        if (failed() || !req)
-            return failure_code();
-        if (req->all_copied)
-            HIP_TRY(hipStreamWaitEvent(m_res.pack_stream, req->all_copied, 0));
-        d.pos = req->job.src;
-        }
+    const ChunkRange range = {file_offset, bytes};
+    rc = stage_chunks(&range, 1, d.N, &d.pos);
+    if (rc != PGSD_SUCCESS)
+        return rc;
     // the row list belongs to the caller: what its stream still does with that memory comes first
     rc = order_after_source();
     if (rc != PGSD_SUCCESS)
@@ -328,12 +367,34 @@ int DevicePipeline::select_domain(long long file_offset, size_t bytes, DomainArg
     rc = launch_select_domain(d, out_rows, out_count, m_res.pack_stream, &err);
     if (rc == PGSD_ERROR_DEVICE)
         fail(err);
+    return rc;
+    }
+
+// Group selection: stage the chunks of the terms (and the position chunk of the domain, if there is one), select on the
+// pack stream, synchronise.  The staged chunks are kept like select_domain's.
+int DevicePipeline::select_where(const ChunkRange* ranges, WhereArgs w, uint32_t* out_rows, uint64_t* out_count)
+    {
+    int rc = enter();
     if (rc != PGSD_SUCCESS)
         return rc;
-    m_kept_src = d.pos;
-    m_kept_offset = file_offset;
-    m_kept_bytes = bytes;
-    return PGSD_SUCCESS;
+    if (w.n_terms > WHERE_MAX_TERMS)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const void* src[WHERE_MAX_TERMS + 1] = {};
+    rc = stage_chunks(ranges, w.n_terms + (w.has_domain ? 1 : 0), w.N, src);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    for (uint32_t j = 0; j < w.n_terms; j++)
+        w.t[j].base = src[j];
+    if (w.has_domain)
+        w.d.pos = src[w.n_terms];
+    rc = order_after_source();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    std::string err;
+    rc = launch_select_where(w, out_rows, out_count, m_res.pack_stream, &err);
+    if (rc == PGSD_ERROR_DEVICE)
+        fail(err);
+    return rc;
     }
 
 int DevicePipeline::wait_read()
@@ -352,7 +413,7 @@ int DevicePipeline::wait_read()
         fail(std::string("stream synchronize: ") + hipGetErrorString(e));
     // an indexed read met a row outside its chunk: nothing was written for it (the pipeline itself is fine)
     const bool bad_rows = m_bad_host && __atomic_exchange_n(m_bad_host, 0u, __ATOMIC_ACQ_REL) != 0;
-    m_kept_src = nullptr; // the staging select_domain() kept is given up with every wait, recycled or not
+    m_kept.clear(); // the chunks a selection kept are given up with every wait, recycled or not
     bool writes_idle;
         {
         std::lock_guard<std::mutex> g(m_mutex);

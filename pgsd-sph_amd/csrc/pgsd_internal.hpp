@@ -155,6 +155,46 @@ struct DomainArgs
     double xy, xz, yz;
     double lo[3], hi[3];
     };
+// Group selection over up to four staged per-particle chunks (pgsd.hoomd.where_rows is the definition): row i is kept
+// iff every term holds for element (i, column) of its chunk and -- with has_domain -- its position lies in the domain.
+// A range term compares v = (double)x (exact for every element type allowed): kept iff v is no NaN, not v < lo and not
+// v >= hi, so a NaN bound leaves that side open; a set term keeps x iff x < 64 as an unsigned word and bit x of `set`
+// is set (a negative int32 is a large unsigned word).
+enum
+    {
+    WHERE_MAX_TERMS = 4,
+    WHERE_RANGE = 0,
+    WHERE_SET = 1
+    };
+struct WhereTerm
+    {
+    const void* base; // the staged chunk: N x M elements of `type`
+    uint32_t type;    // PGSD_TYPE_UINT32, _INT32, _FLOAT or _DOUBLE (ranges only)
+    uint32_t M, column;
+    uint32_t kind;    // WHERE_RANGE / WHERE_SET
+    double lo, hi;
+    uint64_t set;
+    };
+struct WhereArgs
+    {
+    uint64_t N;
+    uint32_t n_terms;
+    uint32_t has_domain; // d (and its staged position chunk) takes part
+    WhereTerm t[WHERE_MAX_TERMS];
+    DomainArgs d;
+    };
+// one whole chunk of a selection: its file range
+struct ChunkRange
+    {
+    long long file_offset;
+    size_t bytes;
+    };
+// stage the chunks of w's terms (ranges[0 .. n_terms); then the position chunk's, with has_domain) whole -- a chunk an
+// earlier selection left staged is taken from there, one that several terms name is staged once --, fill in their
+// addresses, select into out_rows (device, room for N), the count into *out_count; synchronous.  The staged chunks stay
+// until the next wait_read, like select_domain's.
+int device_pipeline_select_where(DevicePipeline*, const ChunkRange* ranges, const WhereArgs& w, uint32_t* out_rows,
+                                 uint64_t* out_count, std::string* err);
 // indexed read: the chunk's bytes at `file_offset` (src_N rows) are staged whole; wait_read gathers rows[0 .. n) of them
 // into job.dst (job.dst.order is null).  The position rows a select_domain left staged are taken from there.
 int device_pipeline_read_rows(DevicePipeline*, long long file_offset, size_t bytes, const pgsd_unpack_job& job,

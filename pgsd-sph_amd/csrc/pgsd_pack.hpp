@@ -234,6 +234,10 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
 // synchronises `stream` and leaves the count in *out_count (host)
 int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err);
 
+// the same over a group predicate (WhereArgs, every base filled in): the rows that satisfy all of its terms and lie in
+// its domain, if it has one
+int launch_select_where(const WhereArgs& w, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);

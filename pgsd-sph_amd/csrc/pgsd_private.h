@@ -14,6 +14,9 @@
  *   restart helpers   pgsd_select_domain_device, pgsd_read_rows_device (pgsd.fl's select_domain_device and
  *                     read_chunk_device(rows=...), behind pgsd.hoomd's read_frame_device(domain=...): a rank of a
  *                     domain-decomposed run reads its own particles; the public header has no room for them)
+ *                     pgsd_select_where_device (pgsd.fl's select_where_device, behind pgsd.hoomd's
+ *                     read_frame_device(where=...): a particle group -- a set of types, ranges of per-particle values,
+ *                     optionally inside a domain -- selected on the GPU from the staged chunks of its terms)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -97,6 +100,28 @@ extern "C"
     int pgsd_select_domain_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position, const float box[6],
                                   uint32_t dimensions, const double lo[3], const double hi[3], uint32_t* out_rows,
                                   uint64_t* out_count);
+
+    /* The rows of a frame that satisfy EVERY term of a predicate over per-particle chunks and -- with `position` -- lie
+       in a domain, in ascending order (pgsd.hoomd.where_rows is the definition).  Term j -- entry j of the six parallel
+       arrays chunks, columns, kinds, lo, hi, sets (n_terms entries each; the layout tests keep this header free of
+       structs without a ctypes twin) -- looks at element (row, columns[j]) of chunks[j] (uint32, int32, float32 or
+       float64 elements; all chunks of one N < 2^32):
+           kind 0, range   with v = (double)x, exact for all four types: kept iff lo <= v < hi.  A NaN v is never kept;
+                           a NaN bound leaves that side open (hi = +inf does not: it refuses v = +inf); lo >= hi
+                           selects nothing.
+           kind 1, set     integer chunks only: kept iff 0 <= x < 64 and bit x of sets[j] is set.
+       position / box / dimensions / dlo / dhi: as pgsd_select_domain_device's position, box, dimensions, lo, hi; all NULL
+       (dimensions ignored) for a predicate without a domain.  n_terms <= 4; n_terms == 0 needs a domain.
+       out_rows: device memory with room for N entries; *out_count (host) receives their number.  Every chunk is staged
+       whole into HBM (one that several terms name, once) and the call synchronises; the staged chunks are kept until the
+       next pgsd_device_wait_read, so a pgsd_read_rows_device of one of them before it reads no file bytes again.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(): another element type, a set on a float chunk,
+       column >= M, n_terms > 4, chunks that differ in N, neither a term nor a domain. */
+    int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_terms, const struct pgsd_index_entry* chunks,
+                                 const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
+                                 const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],
+                                 uint32_t dimensions, const double dlo[3], const double dhi[3], uint32_t* out_rows,
+                                 uint64_t* out_count);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, ascending), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

@@ -337,34 +337,61 @@ static int whole_chunk_range(Impl* s, struct pgsd_handle* handle, const pgsd_ind
     return ensure_device(s);
     }
 
+// The domain of a selection, checked (`who`: the entry point, for the message) and turned into the kernel's arguments
+// (d->pos stays open).
+static int domain_args(const char* who, const pgsd_index_entry& c, const float box[6], uint32_t dimensions,
+                       const double lo[3], const double hi[3], DomainArgs* d)
+    {
+    if (dimensions != 2 && dimensions != 3)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    for (int a = 0; a < 3; a++)
+        if (!(0.0 <= lo[a] && lo[a] < hi[a] && hi[a] <= 1.0))
+            {
+            set_last_error(std::string(who) + ": the domain must satisfy 0 <= lo < hi <= 1 on every axis");
+            return PGSD_ERROR_INVALID_ARGUMENT;
+            }
+    if (!(box[0] > 0.0f && box[1] > 0.0f && (dimensions == 2 || box[2] > 0.0f)))
+        {
+        set_last_error(std::string(who) + ": box lengths must be positive (Lz unless dimensions == 2)");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    if ((c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE) || c.M != 3)
+        {
+        set_last_error(std::string(who) + ": positions are N x 3 float32 or float64 rows");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    memset(d, 0, sizeof(*d));
+    d->N = c.N;
+    d->f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    d->dims = dimensions;
+    for (int a = 0; a < 3; a++)
+        {
+        d->L[a] = (double)box[a];
+        d->lo[a] = lo[a];
+        d->hi[a] = hi[a];
+        }
+    d->xy = (double)box[3];
+    d->xz = (double)box[4];
+    d->yz = (double)box[5];
+    return PGSD_SUCCESS;
+    }
+
 extern "C" int pgsd_select_domain_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
                                          const float box[6], uint32_t dimensions, const double lo[3], const double hi[3],
                                          uint32_t* out_rows, uint64_t* out_count)
     try
     {
     Impl* s = impl_of(handle);
-    if (!s || !position || !box || !lo || !hi || !out_count || (dimensions != 2 && dimensions != 3))
+    if (!s || !position || !box || !lo || !hi || !out_count)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    for (int a = 0; a < 3; a++)
-        if (!(0.0 <= lo[a] && lo[a] < hi[a] && hi[a] <= 1.0))
-            {
-            set_last_error("pgsd_select_domain_device: the domain must satisfy 0 <= lo < hi <= 1 on every axis");
-            return PGSD_ERROR_INVALID_ARGUMENT;
-            }
-    if (!(box[0] > 0.0f && box[1] > 0.0f && (dimensions == 2 || box[2] > 0.0f)))
-        {
-        set_last_error("pgsd_select_domain_device: box lengths must be positive (Lz unless dimensions == 2)");
-        return PGSD_ERROR_INVALID_ARGUMENT;
-        }
     pgsd_index_entry c = *position; // a flush may move the index storage
-    if ((c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE) || c.M != 3)
-        {
-        set_last_error("pgsd_select_domain_device: positions are N x 3 float32 or float64 rows");
-        return PGSD_ERROR_INVALID_ARGUMENT;
-        }
+    DomainArgs d;
+    int rc = domain_args("pgsd_select_domain_device", c, box, dimensions, lo, hi, &d);
+    if (rc != PGSD_SUCCESS)
+        return rc;
     long long foff = 0;
     size_t bytes = 0;
-    int rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    rc = whole_chunk_range(s, handle, c, &foff, &bytes);
     if (rc != PGSD_SUCCESS)
         return rc;
     *out_count = 0;
@@ -372,22 +399,90 @@ extern "C" int pgsd_select_domain_device(struct pgsd_handle* handle, const struc
         return PGSD_SUCCESS;
     if (!out_rows)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    DomainArgs d;
-    memset(&d, 0, sizeof(d));
-    d.N = c.N;
-    d.f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
-    d.dims = dimensions;
-    for (int a = 0; a < 3; a++)
-        {
-        d.L[a] = (double)box[a];
-        d.lo[a] = lo[a];
-        d.hi[a] = hi[a];
-        }
-    d.xy = (double)box[3];
-    d.xz = (double)box[4];
-    d.yz = (double)box[5];
     std::string err;
     rc = device_pipeline_select_domain(s->dev, foff, bytes, d, out_rows, out_count, &err);
+    if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_terms, const struct pgsd_index_entry* term_chunks,
+                                        const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
+                                        const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],
+                                        uint32_t dimensions, const double dlo[3], const double dhi[3], uint32_t* out_rows,
+                                        uint64_t* out_count)
+    try
+    {
+    static const char* who = "pgsd_select_where_device";
+    Impl* s = impl_of(handle);
+    if (!s || !out_count || (n_terms > 0 && (!term_chunks || !columns || !kinds || !lo || !hi || !sets))
+        || (position && (!box || !dlo || !dhi)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    if (n_terms > WHERE_MAX_TERMS)
+        return refuse("a predicate has at most 4 terms");
+    if (n_terms == 0 && !position)
+        return refuse("neither a term nor a domain");
+    WhereArgs w;
+    memset(&w, 0, sizeof(w));
+    w.n_terms = n_terms;
+    w.has_domain = position ? 1u : 0u;
+    pgsd_index_entry chunks[WHERE_MAX_TERMS + 1]; // copies: a flush may move the index storage
+    const uint32_t n_chunks = n_terms + w.has_domain;
+    for (uint32_t j = 0; j < n_terms; j++)
+        {
+        const pgsd_index_entry& c = chunks[j] = term_chunks[j];
+        const bool integer = c.type == PGSD_TYPE_UINT32 || c.type == PGSD_TYPE_INT32;
+        if (!integer && c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
+            return refuse("a term's chunk holds uint32, int32, float32 or float64 elements");
+        if (kinds[j] != WHERE_RANGE && kinds[j] != WHERE_SET)
+            return refuse("a term is a range (kind 0) or a set (kind 1)");
+        if (kinds[j] == WHERE_SET && !integer)
+            return refuse("a set needs a chunk of integers");
+        if (columns[j] >= c.M)
+            return refuse("column " + std::to_string(columns[j]) + " of a chunk of " + std::to_string(c.M) + " column(s)");
+        if (c.N != chunks[0].N)
+            return refuse("the terms' chunks differ in N");
+        w.t[j].type = c.type;
+        w.t[j].M = c.M;
+        w.t[j].column = columns[j];
+        w.t[j].kind = kinds[j];
+        w.t[j].lo = lo[j];
+        w.t[j].hi = hi[j];
+        w.t[j].set = sets[j];
+        }
+    if (position)
+        {
+        chunks[n_terms] = *position;
+        int rc = domain_args(who, chunks[n_terms], box, dimensions, dlo, dhi, &w.d);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        if (chunks[n_terms].N != chunks[0].N)
+            return refuse("the position chunk and the terms' chunks differ in N");
+        }
+    w.N = chunks[0].N;
+    ChunkRange ranges[WHERE_MAX_TERMS + 1];
+    for (uint32_t j = 0; j < n_chunks; j++)
+        {
+        int rc = whole_chunk_range(s, handle, chunks[j], &ranges[j].file_offset, &ranges[j].bytes);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        }
+    *out_count = 0;
+    if (w.N == 0)
+        return PGSD_SUCCESS;
+    if (!out_rows)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    std::string err;
+    int rc = device_pipeline_select_where(s->dev, ranges, w, out_rows, out_count, &err);
     if (rc != PGSD_SUCCESS)
         set_last_error(err);
     return rc;

@@ -4,6 +4,8 @@
 //   select_*_kernel        stream compaction for filtered snapshots: wave ballot / popcount scans give each workgroup's
 //                          count, a one-block scan turns counts into offsets (= per-chunk row and byte counts) and
 //                          hands the total to the host, a scatter pass writes the index list (pgsd_select_rows)
+//   domain_* / where_*_kernel   the same compaction with the predicate evaluated in both passes instead of a flag array:
+//                          the rows inside a spatial domain, the rows of a particle group (type set, value ranges)
 //   pgsd_device_alloc / _free / _copy   device memory owned by the library (pgsd.fl.DeviceBuffer)
 // Shared device helpers: pgsd_kernels.hpp.
 #include "pgsd_kernels.hpp"
@@ -422,11 +424,11 @@ template<bool F64> __device__ __forceinline__ uint32_t domain_mask(const DomainA
     return m;
     }
 
-template<bool F64> __global__ __launch_bounds__(SEL_THREADS) void domain_count_kernel(const DomainArgs d, uint32_t* block_counts)
+// the count pass of a predicate selection: the workgroup's number of kept rows (the bits of every lane's mask)
+__device__ __forceinline__ void mask_count_block(uint32_t m, uint32_t* block_counts)
     {
     __shared__ uint32_t wave_sums[SEL_THREADS / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * SEL_PER_BLOCK;
-    const uint32_t c = (uint32_t)__popc(domain_mask<F64>(d, base));
+    const uint32_t c = (uint32_t)__popc(m);
     const uint32_t inc = wave_inclusive_scan(c);
     if ((threadIdx.x & 63) == 63)
         wave_sums[threadIdx.x >> 6] = inc;
@@ -435,18 +437,16 @@ template<bool F64> __global__ __launch_bounds__(SEL_THREADS) void domain_count_k
         block_counts[blockIdx.x] = wave_sums[0] + wave_sums[1] + wave_sums[2] + wave_sums[3];
     }
 
-template<bool F64>
-__global__ __launch_bounds__(SEL_THREADS) void domain_scatter_kernel(const DomainArgs d, const uint64_t* block_offsets,
-                                                                     uint32_t* out_index)
+// the scatter pass: bit k of lane t's mask is row base + k * SEL_THREADS + t; the kept rows are ordered by (k, wave,
+// lane) -- ascending -- in LDS and leave as one dense run at the workgroup's offset
+__device__ __forceinline__ void mask_scatter_block(uint32_t m, uint64_t base, const uint64_t* block_offsets, uint32_t* out_index)
     {
     constexpr uint32_t W = SEL_THREADS / 64;
     __shared__ uint32_t cnt[SEL_PER_THREAD][W]; // kept rows per (k, wave), then their exclusive prefix in (k, wave) order
     __shared__ uint32_t total;
     __shared__ uint32_t local[SEL_PER_BLOCK];
-    const uint64_t base = (uint64_t)blockIdx.x * SEL_PER_BLOCK;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t below = (1ull << lane) - 1ull;
-    const uint32_t m = domain_mask<F64>(d, base);
 #pragma unroll
     for (int k = 0; k < SEL_PER_THREAD; k++)
         {
@@ -492,6 +492,104 @@ __global__ __launch_bounds__(SEL_THREADS) void domain_scatter_kernel(const Domai
         }
     for (uint32_t e = head + 4 * nvec + threadIdx.x; e < n; e += SEL_THREADS)
         out[e] = local[e];
+    }
+
+template<bool F64> __global__ __launch_bounds__(SEL_THREADS) void domain_count_kernel(const DomainArgs d, uint32_t* block_counts)
+    {
+    mask_count_block(domain_mask<F64>(d, (uint64_t)blockIdx.x * SEL_PER_BLOCK), block_counts);
+    }
+
+template<bool F64>
+__global__ __launch_bounds__(SEL_THREADS) void domain_scatter_kernel(const DomainArgs d, const uint64_t* block_offsets,
+                                                                     uint32_t* out_index)
+    {
+    const uint64_t base = (uint64_t)blockIdx.x * SEL_PER_BLOCK;
+    mask_scatter_block(domain_mask<F64>(d, base), base, block_offsets, out_index);
+    }
+
+// ------------------------------------------------------------------ group selection (read a particle group)
+// The rows that satisfy every term of a predicate over up to four staged per-particle chunks and -- optionally -- lie
+// in a domain: pgsd.hoomd.where_rows is the definition (WhereArgs, pgsd_internal.hpp, restates it).  Same structure as
+// the domain selection: lane t owns rows base + k * SEL_THREADS + t, both passes evaluate the predicate (no flag
+// array), count -> one-block scan -> scatter.  A term reads the 4 (8: float64) bytes of its column at a stride of the
+// chunk's row: neighbouring lanes read neighbouring rows, so every fetched line is used by the wave that fetched it,
+// whole for M = 1 and one column in M of it otherwise (HBM traffic is the whole chunk either way).  Element type and
+// kind are the same for every lane: plain branches, which a wave takes as one.
+// (a lane whose row lies past the end reads row N - 1 instead -- straight-line loads, no branch per row; where_mask has
+// cleared its bit already)
+__device__ __forceinline__ uint32_t where_term_mask(const WhereTerm& t, uint64_t N, uint64_t base)
+    {
+    uint32_t m = 0;
+    if (t.type == PGSD_TYPE_DOUBLE)
+        {
+        double v[SEL_PER_THREAD];
+#pragma unroll
+        for (int k = 0; k < SEL_PER_THREAD; k++)
+            {
+            const uint64_t i = min(base + (uint64_t)k * SEL_THREADS + threadIdx.x, N - 1);
+            v[k] = __builtin_nontemporal_load((const double*)t.base + (i * t.M + t.column));
+            }
+#pragma unroll
+        for (int k = 0; k < SEL_PER_THREAD; k++)
+            m |= (v[k] == v[k] && !(v[k] < t.lo) && !(v[k] >= t.hi) ? 1u : 0u) << k;
+        }
+    else
+        {
+        uint32_t x[SEL_PER_THREAD];
+#pragma unroll
+        for (int k = 0; k < SEL_PER_THREAD; k++)
+            {
+            const uint64_t i = min(base + (uint64_t)k * SEL_THREADS + threadIdx.x, N - 1);
+            x[k] = __builtin_nontemporal_load((const uint32_t*)t.base + (i * t.M + t.column));
+            }
+        if (t.kind == WHERE_SET)
+            {
+#pragma unroll
+            for (int k = 0; k < SEL_PER_THREAD; k++)
+                m |= (x[k] < 64u ? (uint32_t)((t.set >> x[k]) & 1ull) : 0u) << k;
+            }
+        else
+            {
+#pragma unroll
+            for (int k = 0; k < SEL_PER_THREAD; k++)
+                {
+                const double v = t.type == PGSD_TYPE_FLOAT   ? (double)__uint_as_float(x[k])
+                                 : t.type == PGSD_TYPE_INT32 ? (double)(int32_t)x[k]
+                                                             : (double)x[k];
+                m |= (v == v && !(v < t.lo) && !(v >= t.hi) ? 1u : 0u) << k;
+                }
+            }
+        }
+    return m;
+    }
+
+// bit k: row base + k * SEL_THREADS + threadIdx.x exists and passes (rows past N pass no term; a selection of the
+// domain alone gets them refused by domain_mask)
+__device__ __forceinline__ uint32_t where_mask(const WhereArgs& w, uint64_t base)
+    {
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < SEL_PER_THREAD; k++)
+        m |= (base + (uint64_t)k * SEL_THREADS + threadIdx.x < w.N ? 1u : 0u) << k;
+    // (a loop, not four copies: all terms' loads hoisted to the top cost 247 registers against 120-odd, half the waves)
+#pragma nounroll
+    for (uint32_t j = 0; j < w.n_terms; j++)
+        m &= where_term_mask(w.t[j], w.N, base);
+    if (w.has_domain)
+        m &= w.d.f64 ? domain_mask<true>(w.d, base) : domain_mask<false>(w.d, base);
+    return m;
+    }
+
+__global__ __launch_bounds__(SEL_THREADS) void where_count_kernel(const WhereArgs w, uint32_t* block_counts)
+    {
+    mask_count_block(where_mask(w, (uint64_t)blockIdx.x * SEL_PER_BLOCK), block_counts);
+    }
+
+__global__ __launch_bounds__(SEL_THREADS) void where_scatter_kernel(const WhereArgs w, const uint64_t* block_offsets,
+                                                                    uint32_t* out_index)
+    {
+    const uint64_t base = (uint64_t)blockIdx.x * SEL_PER_BLOCK;
+    mask_scatter_block(where_mask(w, base), base, block_offsets, out_index);
     }
 
 // ------------------------------------------------------------------ row plan (sparse indexed reads)
@@ -585,19 +683,18 @@ int select_scratch(int device, uint64_t N, SelectScratch** out, uint64_t per_blo
 
 namespace pgsd_amd
     {
-int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err)
+// count -> scan -> scatter of a predicate selection over N rows (0 < N < 2^32) on `stream`; `launch(count pass?,
+// blocks, block counts, block offsets)` enqueues the predicate's own kernel for either pass
+template<class Launch>
+static int select_by_predicate(uint64_t N, const char* what, uint64_t* out_count, hipStream_t stream, std::string* err,
+                               Launch launch)
     {
-    *out_count = 0;
-    if (d.N == 0)
-        return PGSD_SUCCESS;
-    if (d.N >= (1ull << 32) || !d.pos || !out_rows)
-        return PGSD_ERROR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> guard(g_select_lock);
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess)
         return PGSD_ERROR_DEVICE;
     SelectScratch* sc = nullptr;
-    int rc = select_scratch(device, d.N, &sc);
+    int rc = select_scratch(device, N, &sc);
     if (rc != PGSD_SUCCESS)
         {
         if (err)
@@ -605,32 +702,77 @@ int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_
         return rc;
         }
     (void)hipGetLastError(); // (see pgsd_select_rows)
-    const uint64_t n_blocks = (d.N + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
+    const uint64_t n_blocks = (N + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
     uint32_t* block_counts = (uint32_t*)((char*)sc->dev + 8);
     uint64_t* block_offsets = (uint64_t*)((char*)sc->dev + 8 + ((n_blocks * 4 + 7) & ~7ull));
-    if (d.f64)
-        hipLaunchKernelGGL(domain_count_kernel<true>, dim3((unsigned)n_blocks), dim3(SEL_THREADS), 0, stream, d, block_counts);
-    else
-        hipLaunchKernelGGL(domain_count_kernel<false>, dim3((unsigned)n_blocks), dim3(SEL_THREADS), 0, stream, d, block_counts);
+    launch(true, (unsigned)n_blocks, block_counts, block_offsets);
     hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(SEL_THREADS), 0, stream, block_counts, (uint32_t)n_blocks,
                        block_offsets, (uint64_t*)sc->dev, sc->host_count_dev);
-    if (d.f64)
-        hipLaunchKernelGGL(domain_scatter_kernel<true>, dim3((unsigned)n_blocks), dim3(SEL_THREADS), 0, stream, d,
-                           block_offsets, out_rows);
-    else
-        hipLaunchKernelGGL(domain_scatter_kernel<false>, dim3((unsigned)n_blocks), dim3(SEL_THREADS), 0, stream, d,
-                           block_offsets, out_rows);
+    launch(false, (unsigned)n_blocks, block_counts, block_offsets);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipStreamSynchronize(stream); // the kernels are through: the count is in the pinned word
     if (e != hipSuccess)
         {
         if (err)
-            *err = std::string("domain selection: ") + hipGetErrorString(e);
+            *err = std::string(what) + ": " + hipGetErrorString(e);
         return PGSD_ERROR_DEVICE;
         }
     *out_count = __atomic_load_n(sc->host_count, __ATOMIC_ACQUIRE);
     return PGSD_SUCCESS;
+    }
+
+int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err)
+    {
+    *out_count = 0;
+    if (d.N == 0)
+        return PGSD_SUCCESS;
+    if (d.N >= (1ull << 32) || !d.pos || !out_rows)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    return select_by_predicate(d.N, "domain selection", out_count, stream, err,
+                               [&](bool count, unsigned n_blocks, uint32_t* block_counts, uint64_t* block_offsets)
+                               {
+                                   if (count && d.f64)
+                                       hipLaunchKernelGGL(domain_count_kernel<true>, dim3(n_blocks), dim3(SEL_THREADS), 0,
+                                                          stream, d, block_counts);
+                                   else if (count)
+                                       hipLaunchKernelGGL(domain_count_kernel<false>, dim3(n_blocks), dim3(SEL_THREADS), 0,
+                                                          stream, d, block_counts);
+                                   else if (d.f64)
+                                       hipLaunchKernelGGL(domain_scatter_kernel<true>, dim3(n_blocks), dim3(SEL_THREADS), 0,
+                                                          stream, d, block_offsets, out_rows);
+                                   else
+                                       hipLaunchKernelGGL(domain_scatter_kernel<false>, dim3(n_blocks), dim3(SEL_THREADS), 0,
+                                                          stream, d, block_offsets, out_rows);
+                               });
+    }
+
+int launch_select_where(const WhereArgs& w, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err)
+    {
+    *out_count = 0;
+    if (w.N == 0)
+        return PGSD_SUCCESS;
+    if (w.N >= (1ull << 32) || w.n_terms > WHERE_MAX_TERMS || (w.n_terms == 0 && !w.has_domain) || !out_rows
+        || (w.has_domain && (!w.d.pos || w.d.N != w.N)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    for (uint32_t j = 0; j < w.n_terms; j++)
+        {
+        const WhereTerm& t = w.t[j];
+        const bool integer = t.type == PGSD_TYPE_UINT32 || t.type == PGSD_TYPE_INT32;
+        if (!t.base || t.column >= t.M || !(integer || t.type == PGSD_TYPE_FLOAT || t.type == PGSD_TYPE_DOUBLE)
+            || (t.kind != WHERE_RANGE && !(t.kind == WHERE_SET && integer)))
+            return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    return select_by_predicate(w.N, "group selection", out_count, stream, err,
+                               [&](bool count, unsigned n_blocks, uint32_t* block_counts, uint64_t* block_offsets)
+                               {
+                                   if (count)
+                                       hipLaunchKernelGGL(where_count_kernel, dim3(n_blocks), dim3(SEL_THREADS), 0, stream,
+                                                          w, block_counts);
+                                   else
+                                       hipLaunchKernelGGL(where_scatter_kernel, dim3(n_blocks), dim3(SEL_THREADS), 0, stream,
+                                                          w, block_offsets, out_rows);
+                               });
     }
 
 int launch_row_plan(RowPlan& p, hipStream_t stream, std::string* err)

@@ -3,7 +3,8 @@
 ``read``   the reference's one command (``__main__.py:52-87``): an interactive Python prompt with
            the file open as ``handle`` and, for the hoomd schema, the trajectory as ``traj``.
 ``info``   header, frame count and the chunks of one frame, printed and done (no prompt).
-``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``).
+``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
+           particles of the named types only.
 """
 import argparse
 import code
@@ -64,7 +65,8 @@ def _cmd_info(args):
 
 def _cmd_vtu(args):
     from . import vtu
-    for name in vtu.pgsd2vtu(args.file, args.output):
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    for name in vtu.pgsd2vtu(args.file, args.output, where=where):
         print(name)
 
 
@@ -86,6 +88,8 @@ def main(argv=None):
     p = sub.add_parser('vtu', help="convert the frames to VTK .vtu files")
     p.add_argument('file', type=str)
     p.add_argument('-o', '--output', type=str, default=None, help="output directory (default: next to the file)")
+    p.add_argument('--types', type=str, default=None, metavar='NAME[,NAME...]',
+                   help="write only the particles of these types")
     p.set_defaults(func=_cmd_vtu)
 
     if '--version' in argv:  # works without a subcommand, like the reference (__main__.py:139-145)

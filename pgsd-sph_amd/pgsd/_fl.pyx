@@ -1561,6 +1561,91 @@ cdef class PGSDFile:
         _raise_on_error(retval, self._name, err)
         return _device_head(rows, k), int(k)
 
+    def select_where_device(self, terms, domain=None, box=None, dimensions=3):
+        """The rows of a frame that satisfy every term of a predicate over per-particle chunks, selected on the GPU.
+
+        Args:
+            terms: up to 4 tuples ``(frame, name, column, value)``: element ``(row, column)`` of chunk ``name`` of
+                ``frame`` (uint32, int32, float32 or float64; all chunks of one N) must lie in ``value`` -- a range, the
+                tuple ``(lo, hi)`` with ``None`` for unbounded (``lo <= float64(x) < hi``; NaN never does), or a set of
+                integers in [0, 64) as a list, set or 64-bit mask (integer chunks only).
+            domain: ``None``, or ``(frame, name, domain)``: the rows must also lie in ``domain`` (a
+                :class:`pgsd.hoomd.Domain` or a pair ``(lo, hi)``) by the position chunk ``name`` of ``frame``, as
+                :meth:`select_domain_device` decides it with ``box`` and ``dimensions``.
+
+        Returns:
+            ``(rows, count)`` typed like :meth:`select_domain_device`: the ascending rows -- exactly
+            :func:`pgsd.hoomd.where_rows`, intersected with :func:`pgsd.hoomd.domain_rows`.  The staged chunks are kept
+            until the next :meth:`wait_read`: a ``read_chunk_device(..., rows=rows)`` of one of them before it reads no
+            file bytes again.
+        """
+        cdef C.pgsd_index_entry c_chunks[4]
+        cdef uint32_t c_columns[4]
+        cdef uint32_t c_kinds[4]
+        cdef double c_los[4]
+        cdef double c_his[4]
+        cdef uint64_t c_sets[4]
+        cdef C.pgsd_index_entry c_pos
+        cdef uint32_t n_terms = 0, c_dims = int(dimensions)
+        cdef bint has_domain = domain is not None
+        terms = list(terms)
+        if len(terms) > 4:
+            raise ValueError("select_where_device: a predicate has at most 4 terms")
+        memset(c_sets, 0, sizeof(c_sets))
+        memset(c_los, 0, sizeof(c_los))
+        memset(c_his, 0, sizeof(c_his))
+        for frame, name, column, value in terms:
+            self._entry(frame, name, &c_chunks[n_terms])
+            c_columns[n_terms] = int(column)
+            if isinstance(value, tuple):
+                lo, hi = value
+                c_kinds[n_terms] = 0
+                c_los[n_terms] = float('nan') if lo is None else float(lo)
+                c_his[n_terms] = float('nan') if hi is None else float(hi)
+                if (lo is not None and lo != lo) or (hi is not None and hi != hi):
+                    c_los[n_terms], c_his[n_terms] = 0.0, 0.0     # a NaN bound of the caller's: nothing is kept
+            else:
+                mask = 0
+                for member in ([] if isinstance(value, int) else value):
+                    if not 0 <= int(member) < 64:
+                        raise ValueError("select_where_device: set members lie in [0, 64)")
+                    mask |= 1 << int(member)
+                c_kinds[n_terms] = 1
+                c_sets[n_terms] = int(value) if isinstance(value, int) else mask
+            n_terms += 1
+        N = int(c_chunks[0].N) if n_terms else 0
+        c_box = c_lo = c_hi = None
+        if has_domain:
+            frame, name, cell = domain
+            self._entry(frame, name, &c_pos)
+            lo, hi = (cell.lo, cell.hi) if hasattr(cell, 'lo') else cell
+            c_box = numpy.ascontiguousarray(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+            c_lo = numpy.ascontiguousarray(lo, dtype=numpy.float64).reshape(3)
+            c_hi = numpy.ascontiguousarray(hi, dtype=numpy.float64).reshape(3)
+            if c_box.shape[0] != 6:
+                raise ValueError("box must hold 6 values")
+            if n_terms == 0:
+                N = int(c_pos.N)
+        rows = _device_empty((max(N, 1),), numpy.int32, self.pipeline_device())
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the selection is ordered behind this stream's use of `rows`
+        cdef uintptr_t c_rows = rows.data_ptr(), c_pbox = 0, c_plo = 0, c_phi = 0
+        if has_domain:
+            c_pbox, c_plo, c_phi = c_box.ctypes.data, c_lo.ctypes.data, c_hi.ctypes.data
+        cdef uint64_t k = 0
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_select_where_device(&self._handle, n_terms, c_chunks, c_columns, c_kinds, c_los, c_his, c_sets,
+                                                &c_pos if has_domain else NULL,
+                                                <const float*>c_pbox, c_dims, <const double*>c_plo, <const double*>c_phi,
+                                                <uint32_t*>c_rows, &k)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("select_where_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else ""))
+        _raise_on_error(retval, self._name, err)
+        return _device_head(rows, k), int(k)
+
     def read_chunk_device(self, frame, name, out=None, N=None, offset=0, columns=None, order=None,
                           bitcast=False, wait=True, fill=None, rows=None):
         """Read rows ``[offset, offset + N)`` of a chunk straight into GPU memory.

@@ -372,6 +372,116 @@ def domain_rows(position, box, domain, dimensions=3):
     return numpy.flatnonzero(inside)
 
 
+_WHERE_MAX_TERMS = 4
+_WHERE_SET_BITS = 64
+
+
+def _where_terms(where, types=None):
+    """The terms of a group predicate (`where_rows`), checked and in the dict's order: ``(name, column, lo, hi, mask)``
+    per term -- ``mask`` is ``None`` for a range (``lo`` / ``hi``: float or ``None`` for unbounded), else the 64-bit
+    set mask (``lo`` and ``hi`` are ``None``).  ValueError for everything `where_rows` lists."""
+    if not isinstance(where, dict):
+        raise ValueError("where must be a dict of attribute -> (lo, hi) range or list of integers")
+    if len(where) > _WHERE_MAX_TERMS:
+        raise ValueError("where takes at most %d terms" % _WHERE_MAX_TERMS)
+    terms = []
+    for key, value in where.items():
+        name, column = key if isinstance(key, tuple) and len(key) == 2 else (key, 0)
+        if name == 'type':
+            if column != 0 or isinstance(value, tuple) or isinstance(value, str):
+                raise ValueError("'type' takes a list of type names")
+            names = list(types) if types is not None else []
+            unknown = [t for t in value if t not in names]
+            if unknown:
+                raise ValueError("unknown particle type %r (types: %r)" % (unknown[0], names))
+            name, value = 'typeid', [names.index(t) for t in value]
+        if not isinstance(name, str) or name not in _PARTICLE_FIELDS:
+            raise ValueError("%r is not a per-particle attribute of ParticleData" % (name,))
+        dt, M = _PARTICLE_FIELDS[name][:2]
+        column = int(column)
+        if not 0 <= column < M:
+            raise ValueError("particles/%s has %d column(s): no column %d" % (name, M, column))
+        if isinstance(value, tuple):
+            if len(value) != 2:
+                raise ValueError("a range is a pair (lo, hi): %r" % (value,))
+            lo, hi = (None if v is None else float(v) for v in value)
+            terms.append((name, column, lo, hi, None))
+        elif isinstance(value, (list, set, frozenset)):
+            if numpy.dtype(dt).kind not in 'iu':
+                raise ValueError("particles/%s holds floats: a set needs an integer attribute" % name)
+            mask = 0
+            for member in value:
+                if int(member) != member or not 0 <= int(member) < _WHERE_SET_BITS:
+                    raise ValueError("set members are integers in [0, %d): %r" % (_WHERE_SET_BITS, member))
+                mask |= 1 << int(member)
+            terms.append((name, column, None, None, mask))
+        else:
+            raise ValueError("a term is a (lo, hi) tuple or a list / set of integers: %r" % (value,))
+    return terms
+
+
+def _where_term_keeps(x, lo, hi, mask):
+    """One term of `where_rows` over the values ``x`` of its column: a bool per row."""
+    if mask is not None:
+        small = (x >= 0) & (x < _WHERE_SET_BITS)
+        bits = numpy.uint64(mask) >> numpy.where(small, x, 0).astype(numpy.uint64)
+        return small & ((bits & numpy.uint64(1)) != 0)
+    v = x.astype(numpy.float64)
+    keep = ~numpy.isnan(v)
+    with numpy.errstate(invalid='ignore'):
+        if lo is not None:
+            keep &= numpy.float64(lo) <= v
+        if hi is not None:
+            keep &= v < numpy.float64(hi)
+    return keep
+
+
+def where_rows(arrays, where, types=None):
+    """The rows that satisfy EVERY term of ``where``, ascending (int32): the definition the GPU selection
+    (`pgsd.fl.PGSDFile.select_where_device`, ``read_frame_device(where=...)``) matches exactly.
+
+    Args:
+        arrays (dict): attribute name -> ``N (x M)`` host array (all of the same N).
+        where (dict): at most 4 terms.  A key is an attribute name of `ParticleData` (column 0) or a pair
+            ``(name, column)``; ``'type'`` is ``'typeid'`` with a list of type names looked up in ``types``.  A value is
+
+            * a range, the tuple ``(lo, hi)`` with ``None`` for unbounded: with ``v = float64(x)`` (exact for float32,
+              int32 and uint32) the row is kept iff ``lo <= v < hi``.  NaN is never kept, ``-0.0 >= 0.0`` holds as in
+              numpy, ``lo >= hi`` selects nothing (and so does a bound that is NaN);
+            * a set, a list or set of integers in [0, 64), on integer attributes only (``typeid``, ``body``, ``image``
+              columns): the row is kept iff ``0 <= x < 64`` and ``x`` is a member.  Negative values never match.
+
+            An empty dict selects every row.
+        types (list): the frame's type names, for ``'type'``.
+
+    ValueError: an unknown attribute or type name, a column the attribute does not have, a set on a float attribute, a
+    set member outside [0, 64), more than 4 terms.
+    """
+    terms = _where_terms(where, types)
+    for name in set(t[0] for t in terms):
+        if name not in arrays or arrays[name] is None:
+            raise ValueError("arrays holds no '%s'" % name)
+    first = next((a for a in arrays.values() if a is not None), None)
+    N = 0 if first is None else int(numpy.asarray(first).shape[0])
+    keep = numpy.ones(N, dtype=bool)
+    for name, column, lo, hi, mask in terms:
+        a = numpy.asarray(arrays[name])
+        if a.shape[0] != N:
+            raise ValueError("'%s' has %d rows, expected %d" % (name, a.shape[0], N))
+        a = a.reshape(N, -1)
+        if column >= a.shape[1]:
+            raise ValueError("'%s' has %d column(s): no column %d" % (name, a.shape[1], column))
+        if mask is not None and a.dtype.kind not in 'iu':
+            raise ValueError("'%s' holds floats: a set needs integers" % name)
+        keep &= _where_term_keeps(a[:, column], lo, hi, mask)
+    return numpy.flatnonzero(keep).astype(numpy.int32)
+
+
+def _particle_arrays(particles):
+    """The per-particle arrays a `ParticleData` holds, by name (`where_rows`'s ``arrays``)."""
+    return dict((name, getattr(particles, name)) for name in _PARTICLE_FIELDS if getattr(particles, name, None) is not None)
+
+
 class Tracks(object):
     """What `HOOMDTrajectory.read_tracks` / `read_tracks_device` return: ``step`` (host, uint64, one entry per frame),
     ``rows`` (the K rows followed) and one ``F x K (x M)`` array per requested field, as an attribute and as
@@ -1205,7 +1315,7 @@ class HOOMDTrajectory(object):
             self._initial_frame = snap
         return snap
 
-    def read_frame_device(self, idx, part=None, scalar4=False, defaults=True, domain=None):
+    def read_frame_device(self, idx, part=None, scalar4=False, defaults=True, domain=None, where=None):
         """Read frame ``idx`` with the per-particle arrays of THIS rank's partition in GPU memory.
 
         Restart path (BASELINE config 5): each rank reads rows ``[row0, row0 + n)`` of every
@@ -1227,6 +1337,12 @@ class HOOMDTrajectory(object):
                 exactly as `domain_rows` defines it; every per-particle array is gathered through that row list, and
                 ``frame.tag`` holds it (file rows: the particle tags of a file written in tag order; int32, typed like
                 `pgsd.fl.select_rows`).  Not together with ``part``.
+            where (dict): instead of a row slab, the particles of a group: the rows that satisfy every term of this
+                predicate over the frame's per-particle chunks -- ``{'type': ['fluid']}``, ``{'density': (1000.0,
+                None)}``, ``{('velocity', 2): (None, 0.0), 'typeid': [0, 2]}`` --, selected on the GPU exactly as
+                `where_rows` defines it; with ``domain`` the rows that also lie in that cell (one selection).  The
+                result is a domain read's: ``frame.tag`` holds the selected file rows, ``frame.where`` the predicate.
+                Not together with ``part``.
 
         Returns:
             `Frame` whose ``particles.N`` is this rank's count, ``particles.N_global`` the total.  The per-particle
@@ -1258,6 +1374,12 @@ class HOOMDTrajectory(object):
         else:
             snap.particles.types = snap.particles._default_value['types']
 
+        if where is not None:
+            if part is not None:
+                raise ValueError("part and where are mutually exclusive")
+            self._read_where_device(idx, snap, where, domain, scalar4, defaults, n_global)
+            self._read_logs_device(idx, snap)
+            return snap
         if domain is not None:
             if part is not None:
                 raise ValueError("part and domain are mutually exclusive")
@@ -1520,30 +1642,84 @@ class HOOMDTrajectory(object):
             # no position anywhere: every particle sits at the origin, all of them or none are inside
             count = n_global if len(domain_rows(numpy.zeros((1, 3), numpy.float32), box, domain, dims)) else 0
             rows = fl._device_from_host(numpy.arange(count, dtype=numpy.int32), f.pipeline_device())
+        snap.domain = domain
+        # group 1: position (the staged rows of the selection) and, with scalar4, (x, y, z, typeid bits)
+        self._gather_rows_device(idx, snap, rows, count, scalar4, defaults, n_global,
+                                 ('position', 'pos4') if scalar4 else ('position',))
+
+    def _gather_rows_device(self, idx, snap, rows, count, scalar4, defaults, n_global, staged):
+        """The gather half of a domain or group read: every per-particle array of frame ``idx`` through the ascending
+        row list ``rows`` (device, ``count`` entries), which becomes ``frame.tag``.  ``staged`` names the attributes
+        whose chunks the selection has left staged whole: they are gathered first, in one group, from that staging."""
+        f = self.file
         snap.particles.N = count
         snap.particles.N_global = n_global
         snap.part = None
-        snap.domain = domain
         snap.tag = rows
 
-        # The chunks gathered after the position go through a row plan: in a file whose rows are spatially coherent the
-        # domain's rows touch few blocks and only those are read; in a spatially random file every block is touched and
-        # the plan hands the read to the whole-chunk route with the same rows.  (The position itself, and the type id
-        # that shares its Scalar4 rows, gather from the chunk the selection has staged whole anyway.)
+        # The chunks gathered after the staged ones go through a row plan: in a file whose rows are spatially coherent
+        # the selection's rows touch few blocks and only those are read; in a spatially random file every block is
+        # touched and the plan hands the read to the whole-chunk route with the same rows.  (The staged attributes, and
+        # the type id that shares the position's Scalar4 rows, gather from chunks that are staged whole anyway.)
         plan = []
 
         def gather(fr, chunk, attr, **kw):
-            if attr in ('position', 'pos4') or count == 0:
+            if attr in staged or count == 0:
                 return f.read_chunk_device(fr, chunk, rows=rows, N=count, wait=False, **kw)
             if not plan:
                 plan.append(f.plan_rows(rows, n_global))
             return f.read_chunk_device(fr, chunk, rows=plan[0], wait=False, **kw)
 
-        # group 1: position (the staged rows of the selection) and, with scalar4, (x, y, z, typeid bits); then
-        # (vx, vy, vz, mass); then every other per-particle array: one chunk, one wait
-        groups = [('position', 'pos4'), ('vel4',)] if scalar4 else [('position',)]
-        groups += [(name,) for name in _PARTICLE_FIELDS if name != 'position']
+        # the staged group; then the Scalar4 arrays not in it; then every other per-particle array: one chunk, one wait
+        groups = [tuple(staged)] if staged else []
+        groups += [(name,) for name in (('pos4', 'vel4') if scalar4 else ()) if name not in staged]
+        groups += [(name,) for name in _PARTICLE_FIELDS if name not in staged]
         self._read_particles_device(idx, snap, count, n_global, defaults, gather, groups)
+
+    def _read_where_device(self, idx, snap, where, domain, scalar4, defaults, n_global):
+        """`read_frame_device(where=...)`: select the rows that satisfy `where_rows` (and lie in ``domain``, if given)
+        on the GPU from the effective chunks of the terms' attributes, then gather every per-particle array through
+        them.  A term whose attribute the file stores nowhere is decided on the host against the one default row."""
+        f = self.file
+        terms = _where_terms(where, snap.particles.types)
+        dims = int(snap.configuration.dimensions)
+        box = snap.configuration.box
+        if domain is not None and not isinstance(domain, Domain):
+            domain = Domain(*domain)
+        all_pass, device_terms, staged = True, [], []
+        for name, column, lo, hi, mask in terms:
+            fr = self._effective_frame(idx, 'particles/' + name, n_global)
+            if (lo is not None and lo != lo) or (hi is not None and hi != hi):
+                all_pass = False            # a NaN bound: nothing is kept
+            elif fr is None:
+                if name not in ParticleData._default_value and not f.chunk_exists(0, 'particles/' + name):
+                    raise ValueError("particles/%s is stored neither in frame %d nor in frame 0" % (name, idx))
+                row = numpy.array([_PARTICLE_FIELDS[name][2]]).reshape(1, -1)
+                all_pass = all_pass and bool(_where_term_keeps(row[:, column], lo, hi, mask)[0])
+            else:
+                device_terms.append((fr, 'particles/' + name, column, (lo, hi) if mask is None else mask))
+                if name not in staged:
+                    staged.append(name)
+        dom = None
+        if domain is not None:
+            f_pos = self._effective_frame(idx, 'particles/position', n_global)
+            if f_pos is not None:
+                dom = (f_pos, 'particles/position', domain)
+                staged = [n for n in staged if n != 'position']
+                staged[:0] = ['position', 'pos4'] if scalar4 else ['position']
+            else:
+                # no position anywhere: every particle sits at the origin, all of them or none are inside
+                all_pass = all_pass and len(domain_rows(numpy.zeros((1, 3), numpy.float32), box, domain, dims)) > 0
+        if not all_pass:
+            rows, count, staged = fl._device_from_host(numpy.zeros(0, dtype=numpy.int32), f.pipeline_device()), 0, []
+        elif device_terms or dom is not None:
+            rows, count = f.select_where_device(device_terms, domain=dom, box=box, dimensions=dims)
+        else:
+            rows, count = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device()), n_global
+        snap.where = where
+        if domain is not None:
+            snap.domain = domain
+        self._gather_rows_device(idx, snap, rows, count, scalar4, defaults, n_global, tuple(staged))
 
     def _frame_of(self, idx, chunk):
         """The frame whose copy of a chunk that is NOT per-particle (box, N, types, log/*) frame ``idx`` reads: its

@@ -206,6 +206,11 @@ cdef extern from "pgsd_private.h" nogil:
     int pgsd_select_domain_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
                                   uint32_t dimensions, const double* lo, const double* hi, uint32_t* out_rows,
                                   uint64_t* out_count)
+    int pgsd_select_where_device(pgsd_handle* handle, uint32_t n_terms, const pgsd_index_entry* chunks,
+                                 const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
+                                 const uint64_t* sets, const pgsd_index_entry* position, const float* box,
+                                 uint32_t dimensions, const double* dlo, const double* dhi, uint32_t* out_rows,
+                                 uint64_t* out_count)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                               const pgsd_field_dst* dst)
     cdef struct pgsd_row_plan:

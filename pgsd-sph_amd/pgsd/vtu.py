@@ -128,11 +128,27 @@ def frame_to_vtu(path, frame):
     write_vtu(path, p.position, data, fields)
 
 
-def pgsd2vtu(gsd_name, out_dir=None, frames=None):
+def _subset(frame, where):
+    """The particles of a host frame that satisfy ``where`` (:func:`pgsd.hoomd.where_rows`), as a new frame."""
+    import copy
+    from . import hoomd
+    rows = hoomd.where_rows(hoomd._particle_arrays(frame.particles), where, frame.particles.types)
+    # (shallow copies: the trajectory keeps frame 0 and hands its arrays to later frames)
+    frame = copy.copy(frame)
+    p = frame.particles = copy.copy(frame.particles)
+    for name in hoomd._PARTICLE_FIELDS:
+        if getattr(p, name, None) is not None:
+            setattr(p, name, getattr(p, name)[rows])
+    p.N = len(rows)
+    return frame
+
+
+def pgsd2vtu(gsd_name, out_dir=None, frames=None, where=None):
     """Convert every frame (or ``frames``, an iterable of indices) of a trajectory.
 
     Files are named ``<stem>_<step, 9 digits>.vtu``; a ``<stem>.pvd`` collection lists them with
-    their time step. Returns the list of files written."""
+    their time step. ``where`` (a predicate of :func:`pgsd.hoomd.where_rows`, e.g. ``{'type': ['fluid']}``)
+    keeps only the particles of each frame that satisfy it. Returns the list of files written."""
     from . import hoomd
     stem = os.path.splitext(os.path.basename(gsd_name))[0]
     out_dir = out_dir or os.path.dirname(os.path.abspath(gsd_name))
@@ -142,6 +158,8 @@ def pgsd2vtu(gsd_name, out_dir=None, frames=None):
         indices = range(len(traj)) if frames is None else frames
         for i in indices:
             frame = traj[i]
+            if where is not None:
+                frame = _subset(frame, where)
             step = int(frame.configuration.step or 0)
             name = os.path.join(out_dir, "%s_%09d.vtu" % (stem, step))
             frame_to_vtu(name, frame)
