@@ -673,6 +673,12 @@ int device_pipeline_select_where(DevicePipeline* p, const ChunkRange* ranges, co
     return report(p, p->select_where(ranges, w, out_rows, out_count), err, true);
     }
 
+int device_pipeline_select_halo(DevicePipeline* p, long long file_offset, size_t bytes, const HaloArgs& h, uint32_t* out_rows,
+                                int32_t* out_shift, uint64_t out_counts[2], std::string* err)
+    {
+    return report(p, p->select_halo(file_offset, bytes, h, out_rows, out_shift, out_counts), err, true);
+    }
+
 void device_pipeline_set_source_stream(DevicePipeline* p, void* stream)
     {
     p->set_source_stream(stream);

@@ -141,6 +141,8 @@ class DevicePipeline
     int plan_rows(RowPlan& plan, std::string* err);
     int select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count);
     int select_where(const ChunkRange* ranges, WhereArgs w, uint32_t* out_rows, uint64_t* out_count);
+    int select_halo(long long file_offset, size_t bytes, HaloArgs h, uint32_t* out_rows, int32_t* out_shift,
+                    uint64_t out_counts[2]);
     int wait_read();
 
     // ---- accessors ----

@@ -370,6 +370,27 @@ int DevicePipeline::select_domain(long long file_offset, size_t bytes, DomainArg
     return rc;
     }
 
+// Ghost layer selection: select_domain's staging, the halo kernels in place of the domain's.
+int DevicePipeline::select_halo(long long file_offset, size_t bytes, HaloArgs h, uint32_t* out_rows, int32_t* out_shift,
+                                uint64_t out_counts[2])
+    {
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    const ChunkRange range = {file_offset, bytes};
+    rc = stage_chunks(&range, 1, h.d.N, &h.d.pos);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = order_after_source(); // (the lists belong to the caller, as in select_domain)
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    std::string err;
+    rc = launch_select_halo(h, out_rows, out_shift, out_counts, m_res.pack_stream, &err);
+    if (rc == PGSD_ERROR_DEVICE)
+        fail(err);
+    return rc;
+    }
+
 // Group selection: stage the chunks of the terms (and the position chunk of the domain, if there is one), select on the
 // pack stream, synchronise.  The staged chunks are kept like select_domain's.
 int DevicePipeline::select_where(const ChunkRange* ranges, WhereArgs w, uint32_t* out_rows, uint64_t* out_count)

@@ -155,6 +155,19 @@ struct DomainArgs
     double xy, xz, yz;
     double lo[3], hi[3];
     };
+// Ghost layer selection (pgsd.hoomd.halo_rows is the definition): the domain's rows -- the OWNED rows -- plus the rows
+// whose wrapped fraction is, on every axis, inside the domain or in one of the axis' four half-open ghost bands and on
+// at least one axis in a band.  band[a] = {below lo, hi, below-wrapped lo, hi, above lo, hi, above-wrapped lo, hi}, an
+// empty band {1, 0}; tested in that order after "inside", the wrapped ones meaning a shift of -1 / +1 box vectors.  The
+// bounds are computed on the host (pgsd.hoomd.halo_bands): the kernel only compares.  divided[a] == 0: the axis has no
+// bands and counts as inside.
+struct HaloArgs
+    {
+    DomainArgs d;
+    double band[3][8];
+    uint32_t divided[3];
+    uint32_t pad;
+    };
 // Group selection over up to four staged per-particle chunks (pgsd.hoomd.where_rows is the definition): row i is kept
 // iff every term holds for element (i, column) of its chunk and -- with has_domain -- its position lies in the domain.
 // A range term compares v = (double)x (exact for every element type allowed): kept iff v is no NaN, not v < lo and not
@@ -203,6 +216,10 @@ int device_pipeline_read_rows(DevicePipeline*, long long file_offset, size_t byt
 // out_rows (device), the count into *out_count; synchronous.  The staged rows stay until the next wait_read.
 int device_pipeline_select_domain(DevicePipeline*, long long file_offset, size_t bytes, const DomainArgs& d,
                                   uint32_t* out_rows, uint64_t* out_count, std::string* err);
+// the same staging, then the ghost layer selection: the owned rows at out_rows[0, out_counts[0]), the ghost rows behind
+// them (out_counts[1]), each ascending; out_shift (device, room for 3 x d.N) receives the ghosts' shifts; synchronous
+int device_pipeline_select_halo(DevicePipeline*, long long file_offset, size_t bytes, const HaloArgs& h, uint32_t* out_rows,
+                                int32_t* out_shift, uint64_t out_counts[2], std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

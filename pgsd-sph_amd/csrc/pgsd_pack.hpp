@@ -225,7 +225,7 @@ struct GatherArgs
     };
 
 // Enqueue the unpack of `n_jobs` chunks of N rows each on `stream`. Returns a pgsd_error.
-// With `rows` (device memory, N ascending entries): an indexed read -- destination row i takes row rows[i] of every
+// With `rows` (device memory, N entries in any order): an indexed read -- destination row i takes row rows[i] of every
 // chunk, whose own height is src_N; an entry >= src_N writes nothing and sets the word *bad (device-visible) to 1.
 int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipStream_t stream, std::string* err,
                   const uint32_t* rows = nullptr, uint64_t src_N = 0, uint32_t* bad = nullptr);
@@ -237,6 +237,11 @@ int launch_select_domain(const DomainArgs& d, uint32_t* out_rows, uint64_t* out_
 // the same over a group predicate (WhereArgs, every base filled in): the rows that satisfy all of its terms and lie in
 // its domain, if it has one
 int launch_select_where(const WhereArgs& w, uint32_t* out_rows, uint64_t* out_count, hipStream_t stream, std::string* err);
+
+// the ghost layer selection (HaloArgs, d.pos filled in): owned rows, then ghost rows, into out_rows (room for N), the ghosts'
+// shifts into out_shift (room for 3 x N), the two counts into out_counts (host); synchronises `stream`
+int launch_select_halo(const HaloArgs& h, uint32_t* out_rows, int32_t* out_shift, uint64_t out_counts[2], hipStream_t stream,
+                       std::string* err);
 
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)

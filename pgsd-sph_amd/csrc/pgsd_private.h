@@ -17,6 +17,9 @@
  *                     pgsd_select_where_device (pgsd.fl's select_where_device, behind pgsd.hoomd's
  *                     read_frame_device(where=...): a particle group -- a set of types, ranges of per-particle values,
  *                     optionally inside a domain -- selected on the GPU from the staged chunks of its terms)
+ *                     pgsd_select_halo_device (pgsd.fl's select_halo_device, behind pgsd.hoomd's
+ *                     read_frame_device(domain=..., ghost=...): a cell plus the ghost layer its neighbours reach -- the
+ *                     owned rows, the ghost rows and the periodic shift of each ghost -- from one staged position chunk)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -101,6 +104,25 @@ extern "C"
                                   uint32_t dimensions, const double lo[3], const double hi[3], uint32_t* out_rows,
                                   uint64_t* out_count);
 
+    /* A domain plus its ghost layer (pgsd.hoomd.halo_rows is the definition).  position, box, dimensions, lo, hi: as
+       pgsd_select_domain_device's, and the OWNED rows are exactly its rows.  bands: per axis (x, y, z) eight bounds
+       in [0, 1] -- four half-open intervals {lo, hi}: below, below wrapped, above, above wrapped; an empty one is {1, 0} --
+       computed by the caller (pgsd.hoomd.halo_bands); divided[a] == 0: axis a has no bands and every fraction counts as
+       inside on it (z is not looked at when dimensions == 2).  A row's state on a divided axis is the first match of:
+       inside [lo, hi), the four bands in that order, else out.  A GHOST row is inside or in a band on every axis and in a
+       band on at least one; its shift on an axis is -1 for the below-wrapped band, +1 for the above-wrapped band, else
+       0: the number of box vectors to add along that axis so that the row lies next to the domain.
+       out_rows: device memory with room for position->N entries: the owned rows at [0, out_counts[0]), the ghost rows at
+       [out_counts[0], out_counts[0] + out_counts[1]), each ascending.  out_shift: device memory with room for 3 x
+       position->N int32 entries (the number of ghosts is the call's result); entry 3 k + a is ghost k's shift on axis a.
+       out_counts (host): owned, ghost.  Staging as pgsd_select_domain_device: the chunk is staged whole, the call
+       synchronises, and the staged rows are kept until the next pgsd_device_wait_read.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(): pgsd_select_domain_device's refusals, a band bound
+       outside [0, 1]. */
+    int pgsd_select_halo_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position, const float box[6],
+                                uint32_t dimensions, const double lo[3], const double hi[3], const double bands[24],
+                                const uint32_t divided[3], uint32_t* out_rows, int32_t* out_shift, uint64_t out_counts[2]);
+
     /* The rows of a frame that satisfy EVERY term of a predicate over per-particle chunks and -- with `position` -- lie
        in a domain, in ascending order (pgsd.hoomd.where_rows is the definition).  Term j -- entry j of the six parallel
        arrays chunks, columns, kinds, lo, hi, sets (n_terms entries each; the layout tests keep this header free of
@@ -123,7 +145,7 @@ extern "C"
                                  uint32_t dimensions, const double dlo[3], const double dhi[3], uint32_t* out_rows,
                                  uint64_t* out_count);
 
-    /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, ascending), converted by the
+    /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is
        staged whole; like pgsd_read_chunk_device the gather runs at pgsd_device_wait_read, which fails with
        PGSD_ERROR_INVALID_ARGUMENT if an entry is >= chunk->N (nothing is written for such an entry).  Chunks of 2^32

@@ -410,6 +410,57 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_select_halo_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position, const float box[6],
+                                       uint32_t dimensions, const double lo[3], const double hi[3], const double bands[24],
+                                       const uint32_t divided[3], uint32_t* out_rows, int32_t* out_shift,
+                                       uint64_t out_counts[2])
+    try
+    {
+    static const char* who = "pgsd_select_halo_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !box || !lo || !hi || !bands || !divided || !out_counts)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    pgsd_index_entry c = *position; // a flush may move the index storage
+    HaloArgs h;
+    memset(&h, 0, sizeof(h));
+    int rc = domain_args(who, c, box, dimensions, lo, hi, &h.d);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    for (int a = 0; a < 3; a++)
+        {
+        h.divided[a] = divided[a] ? 1u : 0u;
+        for (int k = 0; k < 8; k++)
+            {
+            const double b = bands[a * 8 + k];
+            if (!(0.0 <= b && b <= 1.0))
+                {
+                set_last_error(std::string(who) + ": the band bounds must lie in [0, 1]");
+                return PGSD_ERROR_INVALID_ARGUMENT;
+                }
+            h.band[a][k] = b;
+            }
+        }
+    long long foff = 0;
+    size_t bytes = 0;
+    rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    out_counts[0] = out_counts[1] = 0;
+    if (c.N == 0)
+        return PGSD_SUCCESS;
+    if (!out_rows || !out_shift)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    std::string err;
+    rc = device_pipeline_select_halo(s->dev, foff, bytes, h, out_rows, out_shift, out_counts, &err);
+    if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_terms, const struct pgsd_index_entry* term_chunks,
                                         const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
                                         const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],

@@ -366,53 +366,74 @@ __global__ __launch_bounds__(SEL_THREADS) void select_scatter_kernel(const uint8
 // Lane t of a workgroup owns rows base + k * SEL_THREADS + t, k < SEL_PER_THREAD (consecutive lanes, consecutive rows:
 // coalesced 12-byte loads); bit k of its mask is row k's verdict.  Count pass, the one-block scan of pgsd_select_rows,
 // scatter pass; the scatter orders a workgroup's rows by (k, wave, lane) through wave ballots, i.e. ascending.
+// (the two halves of the fraction, shared with the ghost layer's halo_class() below)
+__device__ __forceinline__ void domain_skew(const DomainArgs& d, double x, double y, double z, double s[3])
+    {
+#pragma clang fp contract(off)
+    s[0] = ((x + d.L[0] / 2.0) - ((d.xz - d.yz * d.xy) * z + d.xy * y)) / d.L[0];
+    s[1] = ((y + d.L[1] / 2.0) - d.yz * z) / d.L[1];
+    s[2] = (z + d.L[2] / 2.0) / d.L[2];
+    }
+
+__device__ __forceinline__ double domain_wrap(double s)
+    {
+#pragma clang fp contract(off)
+    double f = s - floor(s);
+    if (f >= 1.0)
+        f = 0.0;
+    return f;
+    }
+
 __device__ __forceinline__ bool domain_inside(const DomainArgs& d, double x, double y, double z)
     {
 #pragma clang fp contract(off)
     double s[3];
-    s[0] = ((x + d.L[0] / 2.0) - ((d.xz - d.yz * d.xy) * z + d.xy * y)) / d.L[0];
-    s[1] = ((y + d.L[1] / 2.0) - d.yz * z) / d.L[1];
-    s[2] = (z + d.L[2] / 2.0) / d.L[2];
+    domain_skew(d, x, y, z, s);
     bool in = true;
 #pragma unroll
     for (int a = 0; a < 3; a++)
         {
         if (a == 2 && d.dims == 2)
             break;
-        double f = s[a] - floor(s[a]);
-        if (f >= 1.0)
-            f = 0.0;
+        const double f = domain_wrap(s[a]);
         in = in && d.lo[a] <= f && f < d.hi[a];
         }
     return in;
     }
 
-template<bool F64> __device__ __forceinline__ uint32_t domain_mask(const DomainArgs& d, uint64_t base)
+// the SEL_PER_THREAD rows of this lane as doubles (zeros past the end): rows base + k * SEL_THREADS + threadIdx.x
+template<bool F64>
+__device__ __forceinline__ void domain_load_rows(const void* pos, uint64_t N, uint64_t base, double p[SEL_PER_THREAD][3])
     {
-    double p[SEL_PER_THREAD][3];
 #pragma unroll
     for (int k = 0; k < SEL_PER_THREAD; k++)
         {
         const uint64_t i = base + (uint64_t)k * SEL_THREADS + threadIdx.x;
         p[k][0] = p[k][1] = p[k][2] = 0.0;
-        if (i < d.N)
+        if (i < N)
             {
             if constexpr (F64)
                 {
-                const double* q = (const double*)d.pos + i * 3;
+                const double* q = (const double*)pos + i * 3;
                 p[k][0] = __builtin_nontemporal_load(q);
                 p[k][1] = __builtin_nontemporal_load(q + 1);
                 p[k][2] = __builtin_nontemporal_load(q + 2);
                 }
             else
                 {
-                const u32x3 v = __builtin_nontemporal_load((const u32x3_a4*)((const uint32_t*)d.pos + i * 3));
+                const u32x3 v = __builtin_nontemporal_load((const u32x3_a4*)((const uint32_t*)pos + i * 3));
                 p[k][0] = (double)__uint_as_float(v.x);
                 p[k][1] = (double)__uint_as_float(v.y);
                 p[k][2] = (double)__uint_as_float(v.z);
                 }
             }
         }
+    }
+
+template<bool F64> __device__ __forceinline__ uint32_t domain_mask(const DomainArgs& d, uint64_t base)
+    {
+    double p[SEL_PER_THREAD][3];
+    domain_load_rows<F64>(d.pos, d.N, base, p);
     uint32_t m = 0;
 #pragma unroll
     for (int k = 0; k < SEL_PER_THREAD; k++)
@@ -505,6 +526,141 @@ __global__ __launch_bounds__(SEL_THREADS) void domain_scatter_kernel(const Domai
     {
     const uint64_t base = (uint64_t)blockIdx.x * SEL_PER_BLOCK;
     mask_scatter_block(domain_mask<F64>(d, base), base, block_offsets, out_index);
+    }
+
+// ------------------------------------------------------------------ ghost layer (a cell plus the halo its neighbours reach)
+// pgsd.hoomd.halo_rows is the definition.  A row is OWNED when domain_inside() holds; it is a GHOST when on every
+// axis its wrapped fraction is inside or in one of the axis' four bands and on at least one it is in a band.  The bands'
+// bounds arrive computed (HaloArgs: pgsd.hoomd.halo_bands, host float64): the kernel only compares, in the model's
+// fixed order -- inside, below, below wrapped, above, above wrapped --, so the result equals the model, planes included.
+// An undivided axis has no bands and counts as inside.  Return value: HALO_OWNED, or HALO_GHOST | code << 2 with two
+// bits per axis (0: no shift, 1: -1, 2: +1 box vectors), or 0.
+enum
+    {
+    HALO_OWNED = 1,
+    HALO_GHOST = 2
+    };
+
+__device__ __forceinline__ uint32_t halo_class(const HaloArgs& h, double x, double y, double z)
+    {
+#pragma clang fp contract(off)
+    double s[3];
+    domain_skew(h.d, x, y, z, s);
+    bool owned = true, reached = true, in_band = false;
+    uint32_t code = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+        {
+        if (a == 2 && h.d.dims == 2)
+            break;
+        const double f = domain_wrap(s[a]);
+        const bool in = h.d.lo[a] <= f && f < h.d.hi[a];
+        owned = owned && in;
+        if (!h.divided[a] || in)
+            continue;
+        const double* b = h.band[a];
+        uint32_t shift = 0;
+        bool hit = true;
+        if (b[0] <= f && f < b[1])
+            shift = 0;
+        else if (b[2] <= f && f < b[3])
+            shift = 1;
+        else if (b[4] <= f && f < b[5])
+            shift = 0;
+        else if (b[6] <= f && f < b[7])
+            shift = 2;
+        else
+            hit = false;
+        reached = reached && hit;
+        in_band = in_band || hit;
+        code |= shift << (2 * a);
+        }
+    if (owned)
+        return HALO_OWNED;
+    return reached && in_band ? HALO_GHOST | (code << 2) : 0u;
+    }
+
+// both verdicts of this lane's SEL_PER_THREAD rows from one pass over their positions: bit k of *owned / *ghost
+template<bool F64> __device__ __forceinline__ void halo_masks(const HaloArgs& h, uint64_t base, uint32_t* owned, uint32_t* ghost)
+    {
+    double p[SEL_PER_THREAD][3];
+    domain_load_rows<F64>(h.d.pos, h.d.N, base, p);
+    uint32_t mo = 0, mg = 0;
+#pragma unroll
+    for (int k = 0; k < SEL_PER_THREAD; k++)
+        {
+        const uint64_t i = base + (uint64_t)k * SEL_THREADS + threadIdx.x;
+        const uint32_t c = i < h.d.N ? halo_class(h, p[k][0], p[k][1], p[k][2]) : 0u;
+        mo |= (c & 1u) << k;
+        mg |= ((c >> 1) & 1u) << k;
+        }
+    *owned = mo;
+    *ghost = mg;
+    }
+
+// (mask_count_block and mask_scatter_block keep their LDS arrays per function, not per call: a barrier between the two
+// uses lets every lane finish reading the first use's before the second overwrites them)
+template<bool F64>
+__global__ __launch_bounds__(SEL_THREADS) void halo_count_kernel(const HaloArgs h, uint32_t* owned_counts, uint32_t* ghost_counts)
+    {
+    uint32_t mo, mg;
+    halo_masks<F64>(h, (uint64_t)blockIdx.x * SEL_PER_BLOCK, &mo, &mg);
+    mask_count_block(mo, owned_counts);
+    __syncthreads();
+    mask_count_block(mg, ghost_counts);
+    }
+
+// owned rows at out_rows[0, n_owned), ghost rows behind them, each ascending; *n_owned is the count word the scan of the
+// owned block counts left in device memory
+template<bool F64>
+__global__ __launch_bounds__(SEL_THREADS) void halo_scatter_kernel(const HaloArgs h, const uint64_t* owned_offsets,
+                                                                   const uint64_t* ghost_offsets, const uint64_t* n_owned,
+                                                                   uint32_t* out_rows)
+    {
+    const uint64_t base = (uint64_t)blockIdx.x * SEL_PER_BLOCK;
+    uint32_t mo, mg;
+    halo_masks<F64>(h, base, &mo, &mg);
+    mask_scatter_block(mo, base, owned_offsets, out_rows);
+    __syncthreads();
+    mask_scatter_block(mg, base, ghost_offsets, out_rows + *n_owned);
+    }
+
+// one lane per ghost row: its position again, its class again, the three shifts (the ghosts are few beside N: no payload
+// travels through the LDS compaction)
+template<bool F64>
+__global__ __launch_bounds__(SEL_THREADS) void halo_shift_kernel(const HaloArgs h, const uint32_t* ghost_rows, uint64_t n_ghost,
+                                                                 int32_t* out_shift)
+    {
+    const uint64_t k = (uint64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
+    if (k >= n_ghost)
+        return;
+    const uint64_t i = ghost_rows[k];
+    uint32_t code = 0;
+    if (i < h.d.N)
+        {
+        double x, y, z;
+        if constexpr (F64)
+            {
+            const double* q = (const double*)h.d.pos + i * 3;
+            x = q[0];
+            y = q[1];
+            z = q[2];
+            }
+        else
+            {
+            const float* q = (const float*)h.d.pos + i * 3;
+            x = (double)q[0];
+            y = (double)q[1];
+            z = (double)q[2];
+            }
+        code = halo_class(h, x, y, z) >> 2;
+        }
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+        {
+        const uint32_t c = (code >> (2 * a)) & 3u;
+        out_shift[k * 3 + a] = c == 1u ? -1 : c == 2u ? 1 : 0;
+        }
     }
 
 // ------------------------------------------------------------------ group selection (read a particle group)
@@ -634,19 +790,26 @@ struct SelectScratch
     {
     void* dev = nullptr;
     size_t cap = 0;
-    uint64_t* host_count = nullptr;     // pinned, device-mapped: the scan writes the count into it
+    uint64_t* host_count = nullptr;     // pinned, device-mapped: the scan writes the count into it (two words: the halo
+                                        // selection's second scan writes into the second)
     uint64_t* host_count_dev = nullptr; // ... through this alias
     };
 std::mutex g_select_lock;
 std::map<int, SelectScratch> g_select_scratch;
 
 // the scratch space of a compaction of N rows on `device` (current; g_select_lock held): the count (u64), the block counts
-// (u32) rounded to 8 bytes, the block offsets (u64); and the pinned word the scan leaves the count in
-int select_scratch(int device, uint64_t N, SelectScratch** out, uint64_t per_block = SEL_PER_BLOCK)
+// (u32) rounded to 8 bytes, the block offsets (u64) -- `sets` such triples, one behind the other (the halo selection
+// compacts two lists) --; and the pinned words the scans leave their counts in
+size_t select_set_bytes(uint64_t nb)
+    {
+    return 8 + (size_t)(((nb * 4 + 7) & ~7ull) + nb * 8);
+    }
+
+int select_scratch(int device, uint64_t N, SelectScratch** out, uint64_t per_block = SEL_PER_BLOCK, unsigned sets = 1)
     {
     SelectScratch& sc = g_select_scratch[device];
     const uint64_t nb = (N + per_block - 1) / per_block;
-    const size_t need = 8 + (size_t)(((nb * 4 + 7) & ~7ull) + nb * 8);
+    const size_t need = sets * select_set_bytes(nb);
     if (need > sc.cap)
         {
         if (sc.dev)
@@ -665,7 +828,7 @@ int select_scratch(int device, uint64_t N, SelectScratch** out, uint64_t per_blo
     if (!sc.host_count)
         {
         void* alias = nullptr;
-        if (hipHostMalloc((void**)&sc.host_count, sizeof(uint64_t), hipHostMallocMapped) != hipSuccess
+        if (hipHostMalloc((void**)&sc.host_count, 2 * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess
             || hipHostGetDevicePointer(&alias, sc.host_count, 0) != hipSuccess)
             {
             if (sc.host_count)
@@ -773,6 +936,88 @@ int launch_select_where(const WhereArgs& w, uint32_t* out_rows, uint64_t* out_co
                                        hipLaunchKernelGGL(where_scatter_kernel, dim3(n_blocks), dim3(SEL_THREADS), 0, stream,
                                                           w, block_offsets, out_rows);
                                });
+    }
+
+// Ghost layer: one count pass leaves two block-count arrays, the one-block scan runs once per array, one scatter pass
+// writes the owned rows and -- behind them, at the owned count the first scan left in device memory -- the ghost rows;
+// with the counts on the host, one lane per ghost row works out its shifts.
+int launch_select_halo(const HaloArgs& h, uint32_t* out_rows, int32_t* out_shift, uint64_t out_counts[2], hipStream_t stream,
+                       std::string* err)
+    {
+    out_counts[0] = out_counts[1] = 0;
+    const uint64_t N = h.d.N;
+    if (N == 0)
+        return PGSD_SUCCESS;
+    if (N >= (1ull << 32) || !h.d.pos || !out_rows || !out_shift)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> guard(g_select_lock);
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess)
+        return PGSD_ERROR_DEVICE;
+    SelectScratch* sc = nullptr;
+    int rc = select_scratch(device, N, &sc, SEL_PER_BLOCK, 2);
+    if (rc != PGSD_SUCCESS)
+        {
+        if (err)
+            *err = last_error();
+        return rc;
+        }
+    (void)hipGetLastError(); // (see pgsd_select_rows)
+    const uint64_t nb = (N + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
+    uint64_t* count[2];
+    uint32_t* block_counts[2];
+    uint64_t* block_offsets[2];
+    for (int j = 0; j < 2; j++)
+        {
+        char* set = (char*)sc->dev + j * select_set_bytes(nb);
+        count[j] = (uint64_t*)set;
+        block_counts[j] = (uint32_t*)(set + 8);
+        block_offsets[j] = (uint64_t*)(set + 8 + ((nb * 4 + 7) & ~7ull));
+        }
+    const dim3 grid((unsigned)nb), block(SEL_THREADS);
+    if (h.d.f64)
+        hipLaunchKernelGGL(halo_count_kernel<true>, grid, block, 0, stream, h, block_counts[0], block_counts[1]);
+    else
+        hipLaunchKernelGGL(halo_count_kernel<false>, grid, block, 0, stream, h, block_counts[0], block_counts[1]);
+    for (int j = 0; j < 2; j++)
+        hipLaunchKernelGGL(select_scan_kernel, dim3(1), block, 0, stream, block_counts[j], (uint32_t)nb, block_offsets[j],
+                           count[j], sc->host_count_dev + j);
+    if (h.d.f64)
+        hipLaunchKernelGGL(halo_scatter_kernel<true>, grid, block, 0, stream, h, block_offsets[0], block_offsets[1], count[0],
+                           out_rows);
+    else
+        hipLaunchKernelGGL(halo_scatter_kernel<false>, grid, block, 0, stream, h, block_offsets[0], block_offsets[1], count[0],
+                           out_rows);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(stream); // the kernels are through: the counts are in the pinned words
+    uint64_t n_owned = 0, n_ghost = 0;
+    if (e == hipSuccess)
+        {
+        // (a row has one verdict: n_owned + n_ghost <= N, the room of out_rows)
+        n_owned = __atomic_load_n(sc->host_count, __ATOMIC_ACQUIRE);
+        n_ghost = __atomic_load_n(sc->host_count + 1, __ATOMIC_ACQUIRE);
+        }
+    if (e == hipSuccess && n_ghost > 0)
+        {
+        const dim3 sgrid((unsigned)((n_ghost + SEL_THREADS - 1) / SEL_THREADS));
+        if (h.d.f64)
+            hipLaunchKernelGGL(halo_shift_kernel<true>, sgrid, block, 0, stream, h, out_rows + n_owned, n_ghost, out_shift);
+        else
+            hipLaunchKernelGGL(halo_shift_kernel<false>, sgrid, block, 0, stream, h, out_rows + n_owned, n_ghost, out_shift);
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(stream);
+        }
+    if (e != hipSuccess)
+        {
+        if (err)
+            *err = std::string("halo selection: ") + hipGetErrorString(e);
+        return PGSD_ERROR_DEVICE;
+        }
+    out_counts[0] = n_owned;
+    out_counts[1] = n_ghost;
+    return PGSD_SUCCESS;
     }
 
 int launch_row_plan(RowPlan& p, hipStream_t stream, std::string* err)

@@ -20,7 +20,7 @@ from pickle import PickleError
 import numpy
 
 from libc.errno cimport errno
-from libc.stdint cimport uint8_t, uint32_t, uint64_t, uintptr_t
+from libc.stdint cimport int32_t, uint8_t, uint32_t, uint64_t, uintptr_t
 from libc.stdlib cimport calloc, free
 from libc.string cimport memset
 from cpython.buffer cimport PyObject_GetBuffer, PyBuffer_Release, PyBUF_ANY_CONTIGUOUS, PyBUF_SIMPLE
@@ -1560,6 +1560,61 @@ cdef class PGSDFile:
             raise ValueError("select_domain_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
         _raise_on_error(retval, self._name, err)
         return _device_head(rows, k), int(k)
+
+    def select_halo_device(self, frame, name, box, domain, ghost, dimensions=3):
+        """A domain plus the ghost layer its neighbours reach, selected on the GPU from one position chunk.
+
+        Args:
+            frame, name, box, domain, dimensions: as :meth:`select_domain_device`.
+            ghost: the layer's width as a real distance (:func:`pgsd.hoomd.ghost_fractions` turns it into fractions of
+                the box) or three fractions ``(gx, gy, gz)``.
+
+        Returns:
+            ``(rows, n_owned, n_ghost, shift)``: ``rows`` (int32, typed like :meth:`select_domain_device`'s) holds the
+            owned rows -- exactly that method's -- and behind them the ghost rows, each ascending; ``shift`` is an
+            ``n_ghost x 3`` int32 array of the same kind, the box vectors to add to each ghost so that it lies next to
+            the domain.  Exactly :func:`pgsd.hoomd.halo_rows`, whose band bounds (:func:`pgsd.hoomd.halo_bands`) are
+            the ones handed to the kernel.  The staged position rows are kept as :meth:`select_domain_device` keeps them.
+        """
+        from . import hoomd as _hoomd       # (the model's helpers; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        cell = domain if hasattr(domain, 'lo') else _hoomd.Domain(*domain)
+        bands, divided = _hoomd.halo_bands(cell, _hoomd._ghost_arg(box, ghost, dimensions), dimensions)
+        c_box = numpy.ascontiguousarray(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+        c_lo = numpy.ascontiguousarray(cell.lo, dtype=numpy.float64).reshape(3)
+        c_hi = numpy.ascontiguousarray(cell.hi, dtype=numpy.float64).reshape(3)
+        c_bands = numpy.ascontiguousarray(bands, dtype=numpy.float64).reshape(24)
+        c_div = numpy.ascontiguousarray(divided, dtype=numpy.uint32).reshape(3)
+        if c_box.shape[0] != 6:
+            raise ValueError("box must hold 6 values")
+        device = self.pipeline_device()
+        rows = _device_empty((max(int(entry.N), 1),), numpy.int32, device)
+        # (the number of ghosts is the call's result: room for every row, and a copy of the ghosts' own behind it)
+        room = _device_empty((max(int(entry.N), 1), 3), numpy.int32, device)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the selection is ordered behind this stream's use of `rows`
+        cdef uintptr_t c_rows = rows.data_ptr(), c_shift = room.data_ptr(), c_pbox = c_box.ctypes.data
+        cdef uintptr_t c_plo = c_lo.ctypes.data, c_phi = c_hi.ctypes.data, c_pb = c_bands.ctypes.data, c_pd = c_div.ctypes.data
+        cdef uint32_t c_dims = int(dimensions)
+        cdef uint64_t k[2]
+        cdef int retval, err
+        k[0] = k[1] = 0
+        with nogil:
+            retval = C.pgsd_select_halo_device(&self._handle, &entry, <const float*>c_pbox, c_dims, <const double*>c_plo,
+                                               <const double*>c_phi, <const double*>c_pb, <const uint32_t*>c_pd,
+                                               <uint32_t*>c_rows, <int32_t*>c_shift, k)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("select_halo_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
+        _raise_on_error(retval, self._name, err)
+        n_owned, n_ghost = int(k[0]), int(k[1])
+        if isinstance(room, DeviceBuffer):
+            shift = room.view(shape=(n_ghost, 3)).clone()
+        else:
+            shift = room[:n_ghost].clone()
+        return _device_head(rows, n_owned + n_ghost), n_owned, n_ghost, shift
 
     def select_where_device(self, terms, domain=None, box=None, dimensions=3):
         """The rows of a frame that satisfy every term of a predicate over per-particle chunks, selected on the GPU.

@@ -348,6 +348,16 @@ def domain_rows(position, box, domain, dimensions=3):
         inside: lo[a] <= s[a] < hi[a] for x, y (and z unless dimensions == 2)
     """
     lo, hi = _domain_bounds(domain)
+    f = _wrapped_fractions(position, box, dimensions)
+    inside = numpy.ones(f[0].shape[0], dtype=bool)
+    for a in range(len(f)):
+        inside &= (lo[a] <= f[a]) & (f[a] < hi[a])
+    return numpy.flatnonzero(inside)
+
+
+def _wrapped_fractions(position, box, dimensions):
+    """The fractional coordinates `domain_rows` documents, wrapped into [0, 1): one float64 array per axis that takes
+    part (x, y, and z unless ``dimensions == 2``).  `domain_rows` and `halo_rows` both compare these."""
     dimensions = int(dimensions)
     if dimensions not in (2, 3):
         raise ValueError("dimensions must be 2 or 3")
@@ -364,12 +374,137 @@ def domain_rows(position, box, domain, dimensions=3):
         s = [((x + Lx / 2) - ((xz - yz * xy) * z + xy * y)) / Lx,
              ((y + Ly / 2) - yz * z) / Ly,
              (z + Lz / 2) / Lz]
-        inside = numpy.ones(p.shape[0], dtype=bool)
+        out = []
         for a in range(2 if dimensions == 2 else 3):
             f = s[a] - numpy.floor(s[a])
             f[f >= 1.0] = 0.0
-            inside &= (lo[a] <= f) & (f < hi[a])
-    return numpy.flatnonzero(inside)
+            out.append(f)
+    return out
+
+
+def ghost_fractions(box, width, dimensions=3):
+    """``(gx, gy, gz)``: a ghost layer of the real width ``width`` (HOOMD's ``r_ghost``) as a fraction of the box along
+    each axis -- ``width`` over the box's nearest plane distance on that axis (``BoxDim::getNearestPlaneDistance``),
+    in float64 from the float32 box values ``[Lx, Ly, Lz, xy, xz, yz]`` a file stores::
+
+        npd_x = Lx / sqrt(1 + xy*xy + (xy*yz - xz)**2),   npd_y = Ly / sqrt(1 + yz*yz),   npd_z = Lz
+
+    ``gz`` is 0 when ``dimensions == 2``.  ``width`` must be finite and >= 0.  Host arithmetic only: the GPU selection
+    receives the band bounds computed from these fractions (`halo_bands`) and never repeats it."""
+    dimensions = int(dimensions)
+    if dimensions not in (2, 3):
+        raise ValueError("dimensions must be 2 or 3")
+    width = float(width)
+    if not (width >= 0.0 and width < float('inf')):
+        raise ValueError("the ghost layer width must be finite and >= 0: %r" % (width,))
+    b = numpy.asarray(box, dtype=numpy.float32).reshape(-1)
+    if b.shape[0] < 6:
+        raise ValueError("box must hold 6 values")
+    Lx, Ly, Lz, xy, xz, yz = (float(v) for v in b[:6])
+    if not (Lx > 0 and Ly > 0 and (dimensions == 2 or Lz > 0)):
+        raise ValueError("box lengths must be positive (Lz unless dimensions == 2)")
+    npd_x = Lx / numpy.sqrt(1.0 + xy * xy + (xy * yz - xz) * (xy * yz - xz))
+    npd_y = Ly / numpy.sqrt(1.0 + yz * yz)
+    return (float(width / npd_x), float(width / npd_y), 0.0 if dimensions == 2 else float(width / Lz))
+
+
+_HALO_EMPTY = (1.0, 0.0)
+
+
+def halo_bands(domain, g, dimensions=3):
+    """The ghost bands of `halo_rows` around ``domain`` for the layer fractions ``g = (gx, gy, gz)``: ``(bands,
+    divided)`` -- ``bands`` a 3 x 8 float64 array, per axis the half-open intervals ``[below), [below, wrapped), [above),
+    [above, wrapped)`` as ``lo, hi`` pairs, an empty one stored as ``[1, 0)``; ``divided`` three flags (uint32), 0 for an
+    axis with ``lo == 0 and hi == 1`` (and for z when ``dimensions == 2``), which has no bands.  The one place the
+    bounds are computed: the model compares against them and the GPU selection receives them as they are."""
+    lo, hi = _domain_bounds(domain)
+    if int(dimensions) not in (2, 3):
+        raise ValueError("dimensions must be 2 or 3")
+    g = tuple(float(v) for v in g)
+    if len(g) != 3 or any(not (v >= 0.0 and v < float('inf')) for v in g):
+        raise ValueError("the ghost layer fractions must be three finite values >= 0: %r" % (g,))
+    bands = numpy.empty((3, 8), dtype=numpy.float64)
+    bands[:, 0::2], bands[:, 1::2] = _HALO_EMPTY
+    divided = numpy.zeros(3, dtype=numpy.uint32)
+    for a in range(2 if int(dimensions) == 2 else 3):
+        l, h, w = float(lo[a]), float(hi[a]), g[a]
+        if l == 0.0 and h == 1.0:
+            continue
+        if 2.0 * w > 1.0 - (h - l):
+            raise ValueError("the ghost layer would show a particle twice on axis %s: 2 * %r > 1 - (%r - %r)"
+                             % ('xyz'[a], w, h, l))
+        divided[a] = 1
+        bands[a, 0:2] = max(l - w, 0.0), l
+        if l - w < 0.0:
+            bands[a, 2:4] = (l - w) + 1.0, 1.0
+        bands[a, 4:6] = h, min(h + w, 1.0)
+        if h + w > 1.0:
+            bands[a, 6:8] = 0.0, (h + w) - 1.0
+    return bands, divided
+
+
+# the slots of an axis' four bands in halo_bands' order, and the number of box vectors each adds
+_HALO_BAND_SHIFT = (0, -1, 0, 1)
+
+
+def _ghost_arg(box, ghost, dimensions):
+    """``ghost`` of `halo_rows` / ``read_frame_device``: a width (a real distance) or three fractions -> fractions."""
+    if isinstance(ghost, (int, float, numpy.integer, numpy.floating)):
+        return ghost_fractions(box, ghost, dimensions)
+    g = tuple(float(v) for v in ghost)
+    if len(g) != 3:
+        raise ValueError("ghost is a width or three fractions (gx, gy, gz)")
+    return g
+
+
+def halo_rows(position, box, domain, ghost, dimensions=3):
+    """A cell plus the ghost layer its neighbours reach: ``(owned, ghost_rows, shift)`` -- the definition the GPU
+    selection (`pgsd.fl.PGSDFile.select_halo_device`, ``read_frame_device(domain=..., ghost=...)``) equals exactly.
+
+    ``owned`` is `domain_rows`.  ``ghost`` is the layer's width as a real distance (`ghost_fractions` turns it into
+    fractions, like HOOMD's ``r_ghost``) or three fractions ``(gx, gy, gz)``.  With ``f[a]`` the wrapped fractional
+    coordinate `domain_rows` computes, an axis that the domain does not divide (``lo == 0 and hi == 1``; z when
+    ``dimensions == 2``) has no bands and every ``f`` counts as inside on it.  A divided axis has four half-open bands,
+    whose bounds `halo_bands` computes once in float64::
+
+        below            [max(lo - g, 0), lo)      shift  0
+        below, wrapped   [(lo - g) + 1, 1)         shift -1    (when lo - g < 0)
+        above            [hi, min(hi + g, 1))      shift  0
+        above, wrapped   [0, (hi + g) - 1)         shift +1    (when hi + g > 1)
+
+    A row's state on an axis is the first match of: inside (``lo <= f < hi``), the bands in this order, else out.  A
+    row is a ghost when it is inside or in a band on every axis and in a band on at least one; ``ghost_rows`` are those
+    rows, ascending (int64 like ``owned``), disjoint from ``owned``.  ``shift`` (``len(ghost_rows) x 3`` int32) holds
+    each axis' band shift, 0 where the axis is inside: the number of box vectors to add so that the ghost lies next to
+    the cell, ``r' = r + sx*a1 + sy*a2 + sz*a3`` with HOOMD's lattice vectors ``a1 = (Lx, 0, 0)``, ``a2 = (xy*Ly, Ly,
+    0)``, ``a3 = (xz*Lz, yz*Lz, Lz)``.  Nothing in the library applies it.
+
+    A layer that would show a particle twice -- ``2*g > 1 - (hi - lo)`` on a divided axis -- raises ValueError;
+    ``g == 0`` on every axis gives no ghosts."""
+    bands, divided = halo_bands(domain, _ghost_arg(box, ghost, dimensions), dimensions)
+    lo, hi = _domain_bounds(domain)
+    f = _wrapped_fractions(position, box, dimensions)
+    n = f[0].shape[0]
+    owned = numpy.ones(n, dtype=bool)
+    reached = numpy.ones(n, dtype=bool)         # inside or in a band on every axis so far
+    in_band = numpy.zeros(n, dtype=bool)        # in a band on at least one
+    shift = numpy.zeros((n, 3), dtype=numpy.int32)
+    for a in range(len(f)):
+        inside = (lo[a] <= f[a]) & (f[a] < hi[a])
+        owned &= inside
+        if not divided[a]:
+            continue
+        open_ = ~inside                         # no earlier state has matched
+        here = numpy.zeros(n, dtype=bool)
+        for slot in range(4):
+            hit = open_ & (bands[a, 2 * slot] <= f[a]) & (f[a] < bands[a, 2 * slot + 1])
+            shift[hit, a] = _HALO_BAND_SHIFT[slot]
+            here |= hit
+            open_ &= ~hit
+        reached &= inside | here
+        in_band |= here
+    ghost_rows = numpy.flatnonzero(reached & in_band)
+    return numpy.flatnonzero(owned), ghost_rows, shift[ghost_rows]
 
 
 _WHERE_MAX_TERMS = 4
@@ -1315,7 +1450,7 @@ class HOOMDTrajectory(object):
             self._initial_frame = snap
         return snap
 
-    def read_frame_device(self, idx, part=None, scalar4=False, defaults=True, domain=None, where=None):
+    def read_frame_device(self, idx, part=None, scalar4=False, defaults=True, domain=None, where=None, ghost=None):
         """Read frame ``idx`` with the per-particle arrays of THIS rank's partition in GPU memory.
 
         Restart path (BASELINE config 5): each rank reads rows ``[row0, row0 + n)`` of every
@@ -1343,6 +1478,14 @@ class HOOMDTrajectory(object):
                 `where_rows` defines it; with ``domain`` the rows that also lie in that cell (one selection).  The
                 result is a domain read's: ``frame.tag`` holds the selected file rows, ``frame.where`` the predicate.
                 Not together with ``part``.
+            ghost: with ``domain``, the cell plus the ghost layer its neighbours reach, as `halo_rows` defines it: the
+                layer's width as a real distance (HOOMD's ``r_ghost``) or three fractions of the box.  Every
+                per-particle array holds the owned rows first, then the ghost rows (each ascending);
+                ``particles.N`` is their total, ``frame.n_owned`` the number of owned rows, ``frame.tag`` the file rows
+                and ``frame.ghost_shift`` an ``n_ghost x 3`` int32 device array: the box vectors to add to each ghost's
+                position so that it lies next to the cell (`halo_rows` gives the formula; positions are returned as
+                stored).  Needs ``domain``; not together with ``part`` or ``where`` -- a ghost layer around a particle
+                group is not provided.
 
         Returns:
             `Frame` whose ``particles.N`` is this rank's count, ``particles.N_global`` the total.  The per-particle
@@ -1353,6 +1496,8 @@ class HOOMDTrajectory(object):
             idx += len(self)
         if idx >= len(self) or idx < 0:
             raise IndexError()
+        if ghost is not None and (domain is None or part is not None or where is not None):
+            raise ValueError("ghost needs domain and goes with neither part nor where")
         f = self.file
         snap = Frame()
         self._read_scalar_any(idx, 'configuration/step', snap.configuration, 'step')
@@ -1383,7 +1528,7 @@ class HOOMDTrajectory(object):
         if domain is not None:
             if part is not None:
                 raise ValueError("part and domain are mutually exclusive")
-            self._read_domain_device(idx, snap, domain, scalar4, defaults, n_global)
+            self._read_domain_device(idx, snap, domain, scalar4, defaults, n_global, ghost)
             self._read_logs_device(idx, snap)
             return snap
         if part is None:
@@ -1625,18 +1770,31 @@ class HOOMDTrajectory(object):
             if f.chunk_exists(idx, state):
                 snap.state[state[6:]] = f.read_chunk(idx, state)
 
-    def _read_domain_device(self, idx, snap, domain, scalar4, defaults, n_global):
+    def _read_domain_device(self, idx, snap, domain, scalar4, defaults, n_global, ghost=None):
         """`read_frame_device(domain=...)`: select the domain's rows from the effective position chunk, then gather every
         per-particle array through them.  One `wait_read` per group of chunks that share destination rows, so the HBM
         staging holds one or two chunks at a time, never the frame; the position chunk the selection staged serves the
-        position gather (same index entry, before the group's wait).  Frame 0's device cache of slab reads is not used."""
+        position gather (same index entry, before the group's wait).  Frame 0's device cache of slab reads is not used.
+        With ``ghost`` the row list is `halo_rows`' -- owned rows, then ghost rows -- and the gather is the same."""
         f = self.file
         if not isinstance(domain, Domain):
             domain = Domain(*domain)
         dims = int(snap.configuration.dimensions)
         box = snap.configuration.box
         f_pos = self._effective_frame(idx, 'particles/position', n_global)
-        if f_pos is not None:
+        if ghost is not None:
+            if f_pos is not None:
+                rows, snap.n_owned, n_ghost, snap.ghost_shift = f.select_halo_device(f_pos, 'particles/position', box,
+                                                                                      domain, ghost, dims)
+            else:
+                # no position anywhere: every particle sits at the origin, all of them owned, ghosts or neither
+                owned, ghosts, shift = halo_rows(numpy.zeros((1, 3), numpy.float32), box, domain, ghost, dims)
+                snap.n_owned, n_ghost = n_global * len(owned), n_global * len(ghosts)
+                rows = fl._device_from_host(numpy.arange(snap.n_owned + n_ghost, dtype=numpy.int32), f.pipeline_device())
+                snap.ghost_shift = fl._device_rows((n_ghost, 3), numpy.int32, f.pipeline_device(),
+                                                   shift[0] if n_ghost else numpy.zeros(3, numpy.int32))
+            count = snap.n_owned + n_ghost
+        elif f_pos is not None:
             rows, count = f.select_domain_device(f_pos, 'particles/position', box, domain, dims)
         else:
             # no position anywhere: every particle sits at the origin, all of them or none are inside
@@ -1648,8 +1806,9 @@ class HOOMDTrajectory(object):
                                  ('position', 'pos4') if scalar4 else ('position',))
 
     def _gather_rows_device(self, idx, snap, rows, count, scalar4, defaults, n_global, staged):
-        """The gather half of a domain or group read: every per-particle array of frame ``idx`` through the ascending
-        row list ``rows`` (device, ``count`` entries), which becomes ``frame.tag``.  ``staged`` names the attributes
+        """The gather half of a domain or group read: every per-particle array of frame ``idx`` through the row list
+        ``rows`` (device, ``count`` entries; ascending, or with a ghost layer two ascending runs -- the gather does not
+        depend on the order), which becomes ``frame.tag``.  ``staged`` names the attributes
         whose chunks the selection has left staged whole: they are gathered first, in one group, from that staging."""
         f = self.file
         snap.particles.N = count

@@ -5,7 +5,7 @@
 # libpgsd.pxd:6; this library's handle starts with a POSIX fd), plus the device path.  The declarations are
 # checked by the C compiler against the real header when pgsd/_fl.pyx is built: a prototype that drifts
 # from include/pgsd.h does not compile.
-from libc.stdint cimport uint8_t, uint16_t, uint32_t, uint64_t, int64_t
+from libc.stdint cimport uint8_t, uint16_t, int32_t, uint32_t, uint64_t, int64_t
 
 
 cdef extern from "pgsd.h" nogil:
@@ -206,6 +206,9 @@ cdef extern from "pgsd_private.h" nogil:
     int pgsd_select_domain_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
                                   uint32_t dimensions, const double* lo, const double* hi, uint32_t* out_rows,
                                   uint64_t* out_count)
+    int pgsd_select_halo_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
+                                uint32_t dimensions, const double* lo, const double* hi, const double* bands,
+                                const uint32_t* divided, uint32_t* out_rows, int32_t* out_shift, uint64_t* out_counts)
     int pgsd_select_where_device(pgsd_handle* handle, uint32_t n_terms, const pgsd_index_entry* chunks,
                                  const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
                                  const uint64_t* sets, const pgsd_index_entry* position, const float* box,

@@ -4,10 +4,12 @@ Writes an N-row frame (position, typeid, velocity, mass, image; positions unifor
 from the device, then times, each on a warm page cache:
   * read_frame_device(0, domain=d, scalar4=True) for every domain d of a 2x2x2 grid (rank 0 .. 7), and
   * read_frame_device(0, part=(r * N/8, N/8), scalar4=True) for the same ranks -- the slab read of config 5.
+With ``--ghost WIDTH`` the selections alone are timed as well, for every domain: select_halo_device (the cell plus a
+ghost layer of that width) beside select_domain_device of the same cell, each with the staging of the position chunk.
 One JSON line per read.  The kernels' own times come from a separate run under
 ``rocprofv3 --kernel-trace --stats -- python tools/read_domain_bench.py --n ... --repeats 1``.
 
-    python tools/read_domain_bench.py [--n 80000000] [--repeats 2] [--out profiles/r06_read_domain.jsonl]
+    python tools/read_domain_bench.py [--n 80000000] [--repeats 2] [--ghost WIDTH] [--out profiles/r06_read_domain.jsonl]
 """
 import argparse
 import json
@@ -58,6 +60,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=80_000_000)
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--ghost", type=float, default=None, help="also time the halo selection with this layer width")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     path = "/dev/shm/pgsd_read_domain_bench_%d.gsd" % os.getpid()
@@ -84,7 +87,23 @@ def main():
                         lines.append(rec)
                         print(json.dumps(rec), flush=True)
                         del fr
-        for kind in ("domain", "slab"):
+            for rep in range(a.repeats if a.ghost is not None else 0):
+                for rank, d in enumerate(grid):
+                    for kind in ("select_halo", "select_domain"):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        if kind == "select_halo":
+                            got = t.file.select_halo_device(0, "particles/position", BOX, d, a.ghost)
+                            rows, ghosts = got[1] + got[2], got[2]
+                        else:
+                            rows, ghosts = t.file.select_domain_device(0, "particles/position", BOX, d)[1], 0
+                        ms = (time.perf_counter() - t0) * 1e3
+                        t.file.wait_read()                              # gives up the staged position rows
+                        rec = {"kind": kind, "rank": rank, "repeat": rep, "N": a.n, "rows": int(rows),
+                               "ghosts": int(ghosts), "ms": round(ms, 2)}
+                        lines.append(rec)
+                        print(json.dumps(rec), flush=True)
+        for kind in ("domain", "slab") + (("select_halo", "select_domain") if a.ghost is not None else ()):
             ms = [r["ms"] for r in lines if r["kind"] == kind and r["repeat"] == a.repeats - 1]
             summary = {"kind": kind + "_summary", "N": a.n, "median_ms": float(np.median(ms)), "min_ms": min(ms),
                        "max_ms": max(ms)}
