@@ -679,6 +679,18 @@ int device_pipeline_select_halo(DevicePipeline* p, long long file_offset, size_t
     return report(p, p->select_halo(file_offset, bytes, h, out_rows, out_shift, out_counts), err, true);
     }
 
+int device_pipeline_domain_histogram(DevicePipeline* p, long long file_offset, size_t bytes, const DomainArgs& d,
+                                     uint32_t bins, uint64_t* out_hist, std::string* err)
+    {
+    return report(p, p->domain_histogram(file_offset, bytes, d, bins, out_hist), err, true);
+    }
+
+int device_pipeline_domain_counts(DevicePipeline* p, long long file_offset, size_t bytes, const CellArgs& c,
+                                  uint64_t* out_counts, uint64_t* out_nowhere, std::string* err)
+    {
+    return report(p, p->domain_counts(file_offset, bytes, c, out_counts, out_nowhere), err, true);
+    }
+
 void device_pipeline_set_source_stream(DevicePipeline* p, void* stream)
     {
     p->set_source_stream(stream);

@@ -143,6 +143,8 @@ class DevicePipeline
     int select_where(const ChunkRange* ranges, WhereArgs w, uint32_t* out_rows, uint64_t* out_count);
     int select_halo(long long file_offset, size_t bytes, HaloArgs h, uint32_t* out_rows, int32_t* out_shift,
                     uint64_t out_counts[2]);
+    int domain_histogram(long long file_offset, size_t bytes, DomainArgs d, uint32_t bins, uint64_t* out_hist);
+    int domain_counts(long long file_offset, size_t bytes, CellArgs c, uint64_t* out_counts, uint64_t* out_nowhere);
     int wait_read();
 
     // ---- accessors ----

@@ -418,6 +418,41 @@ int DevicePipeline::select_where(const ChunkRange* ranges, WhereArgs w, uint32_t
     return rc;
     }
 
+// Domain census: select_domain's staging -- stage_chunks takes the position rows from what an earlier selection or census
+// of this frame kept --, one counting pass on the pack stream, the result on the host.  Nothing of the caller's is
+// written on the device, so there is no source stream to order behind.
+int DevicePipeline::domain_histogram(long long file_offset, size_t bytes, DomainArgs d, uint32_t bins, uint64_t* out_hist)
+    {
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    const ChunkRange range = {file_offset, bytes};
+    rc = stage_chunks(&range, 1, d.N, &d.pos);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    std::string err;
+    rc = launch_axis_histograms(d, bins, out_hist, m_res.pack_stream, &err);
+    if (rc == PGSD_ERROR_DEVICE)
+        fail(err);
+    return rc;
+    }
+
+int DevicePipeline::domain_counts(long long file_offset, size_t bytes, CellArgs c, uint64_t* out_counts, uint64_t* out_nowhere)
+    {
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    const ChunkRange range = {file_offset, bytes};
+    rc = stage_chunks(&range, 1, c.d.N, &c.d.pos);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    std::string err;
+    rc = launch_cell_counts(c, out_counts, out_nowhere, m_res.pack_stream, &err);
+    if (rc == PGSD_ERROR_DEVICE)
+        fail(err);
+    return rc;
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

@@ -220,6 +220,32 @@ int device_pipeline_select_domain(DevicePipeline*, long long file_offset, size_t
 // them (out_counts[1]), each ascending; out_shift (device, room for 3 x d.N) receives the ghosts' shifts; synchronous
 int device_pipeline_select_halo(DevicePipeline*, long long file_offset, size_t bytes, const HaloArgs& h, uint32_t* out_rows,
                                 int32_t* out_shift, uint64_t out_counts[2], std::string* err);
+// Domain census (pgsd.hoomd.axis_histograms / domain_counts are the definitions): the wrapped fractions of a staged
+// position chunk -- DomainArgs without lo / hi -- binned instead of tested against one cell.
+enum
+    {
+    CENSUS_MAX_BINS = 4096,     // bins per axis of a histogram: a power of two, so every edge k / bins is exact
+    CENSUS_MAX_AXIS_CELLS = 64, // cells per axis of a count ...
+    CENSUS_MAX_CELLS = 4096     // ... and in all
+    };
+// the cells of a rectilinear decomposition: n[a] cells on axis a, cut at the n[a] - 1 interior bounds bounds[a][...]
+// (strictly ascending inside (0, 1)); a row's cell on an axis is the number of bounds <= its fraction
+struct CellArgs
+    {
+    DomainArgs d;
+    uint32_t n[3];
+    uint32_t pad;
+    double bounds[3][CENSUS_MAX_AXIS_CELLS - 1];
+    };
+// stage the position chunk at `file_offset` (d.N rows) -- or take it from what an earlier selection or census left
+// staged --, count on the GPU, copy the result to the host; synchronous.  The staged rows stay until the next wait_read.
+// out_hist: 3 x bins counts (x, y, z; the z row zero when d.dims == 2)
+int device_pipeline_domain_histogram(DevicePipeline*, long long file_offset, size_t bytes, const DomainArgs& d, uint32_t bins,
+                                     uint64_t* out_hist, std::string* err);
+// out_counts: n[0] * n[1] * n[2] counts, cell (x, y, z) at x + n[0] * (y + n[1] * z); *out_nowhere: the rows with a NaN
+// fraction on an axis that takes part
+int device_pipeline_domain_counts(DevicePipeline*, long long file_offset, size_t bytes, const CellArgs& c,
+                                  uint64_t* out_counts, uint64_t* out_nowhere, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

@@ -243,6 +243,12 @@ int launch_select_where(const WhereArgs& w, uint32_t* out_rows, uint64_t* out_co
 int launch_select_halo(const HaloArgs& h, uint32_t* out_rows, int32_t* out_shift, uint64_t out_counts[2], hipStream_t stream,
                        std::string* err);
 
+// the domain census (d.pos / c.d.pos filled in): one pass over the position rows bins every wrapped fraction into `bins`
+// bins per axis (out_hist, host: 3 x bins) / counts the rows of every cell (out_counts, host: n[0] * n[1] * n[2];
+// *out_nowhere: rows with a NaN fraction); synchronises `stream`
+int launch_axis_histograms(const DomainArgs& d, uint32_t bins, uint64_t* out_hist, hipStream_t stream, std::string* err);
+int launch_cell_counts(const CellArgs& c, uint64_t* out_counts, uint64_t* out_nowhere, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);

@@ -20,6 +20,10 @@
  *                     pgsd_select_halo_device (pgsd.fl's select_halo_device, behind pgsd.hoomd's
  *                     read_frame_device(domain=..., ghost=...): a cell plus the ghost layer its neighbours reach -- the
  *                     owned rows, the ghost rows and the periodic shift of each ghost -- from one staged position chunk)
+ *                     pgsd_domain_histogram_device, pgsd_domain_counts_device (pgsd.fl's domain_histogram_device and
+ *                     domain_counts_device, behind pgsd.hoomd's axis_histograms_device, domain_counts_device and
+ *                     balanced_grid_device: per-axis histograms of the fractions and per-cell counts of a decomposition,
+ *                     counted on the GPU from one staged position chunk, so that a restart can choose balanced splits)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -144,6 +148,31 @@ extern "C"
                                  const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],
                                  uint32_t dimensions, const double dlo[3], const double dhi[3], uint32_t* out_rows,
                                  uint64_t* out_count);
+
+    /* Domain census: which decomposition to ask for.  Both calls evaluate pgsd_select_domain_device's wrapped fractions
+       f[a] of every row of a position chunk (position, box, dimensions: as there) and count instead of selecting; the
+       results are host arrays.  A row whose fraction on an axis is NaN (NaN or infinite coordinates) is counted in no
+       bin of that axis / in no cell; z takes no part when dimensions == 2.
+       pgsd_domain_histogram_device (pgsd.hoomd.axis_histograms is the definition): out_hist[a * bins + k] is the number
+       of rows with int(f[a] * bins) == k; bins is a power of two in [2, 4096], so every bin edge k / bins is an exact
+       double and no clamp is involved.  The z row is zero when dimensions == 2.
+       pgsd_domain_counts_device (pgsd.hoomd.domain_counts): the rows of every cell of an n[0] x n[1] x n[2] grid cut at
+       interior_bounds -- the (n[0] - 1) + (n[1] - 1) + (n[2] - 1) interior boundaries, x's, then y's, then z's, each
+       axis' strictly ascending inside (0, 1); NULL is allowed for a single cell --: a row's cell on an axis is the number
+       of that axis' bounds b with b <= f, out_counts[x + n[0] * (y + n[1] * z)] is the cell's number of rows -- the count
+       pgsd_select_domain_device returns for that cell -- and *out_nowhere the number of rows with a NaN fraction on an
+       axis that takes part.  1 <= n[a] <= 64 and at most 4096 cells.
+       The position chunk is staged whole and the call synchronises; the staged rows are kept until the next
+       pgsd_device_wait_read, and both calls look there first: a histogram followed by a count (or by a selection's
+       pgsd_read_rows_device) of the same chunk reads its file bytes once.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(): pgsd_select_domain_device's refusals; bins not a
+       power of two in [2, 4096]; an n[a] of 0 or above 64; more than 4096 cells; bounds that do not ascend strictly
+       inside (0, 1); dimensions == 2 with n[2] != 1. */
+    int pgsd_domain_histogram_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position, const float box[6],
+                                     uint32_t dimensions, uint32_t bins, uint64_t* out_hist);
+    int pgsd_domain_counts_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position, const float box[6],
+                                  uint32_t dimensions, const uint32_t n[3], const double* interior_bounds,
+                                  uint64_t* out_counts, uint64_t* out_nowhere);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

@@ -461,6 +461,124 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+// The census entry points' first half: the checks and staging arguments of pgsd_select_domain_device over the whole box.
+static int census_args(const char* who, Impl* s, struct pgsd_handle* handle, const pgsd_index_entry& c, const float box[6],
+                       uint32_t dimensions, DomainArgs* d, long long* foff, size_t* bytes)
+    {
+    static const double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {1.0, 1.0, 1.0};
+    int rc = domain_args(who, c, box, dimensions, lo, hi, d);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    return whole_chunk_range(s, handle, c, foff, bytes);
+    }
+
+extern "C" int pgsd_domain_histogram_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                            const float box[6], uint32_t dimensions, uint32_t bins, uint64_t* out_hist)
+    try
+    {
+    static const char* who = "pgsd_domain_histogram_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !box || !out_hist)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    if (bins < 2 || bins > CENSUS_MAX_BINS || (bins & (bins - 1)) != 0)
+        {
+        set_last_error(std::string(who) + ": bins must be a power of two in [2, 4096]");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    pgsd_index_entry c = *position; // a flush may move the index storage
+    DomainArgs d;
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = census_args(who, s, handle, c, box, dimensions, &d, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (c.N == 0)
+        {
+        memset(out_hist, 0, 3 * (size_t)bins * sizeof(uint64_t));
+        return PGSD_SUCCESS;
+        }
+    std::string err;
+    rc = device_pipeline_domain_histogram(s->dev, foff, bytes, d, bins, out_hist, &err);
+    if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_domain_counts_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                         const float box[6], uint32_t dimensions, const uint32_t n[3],
+                                         const double* interior_bounds, uint64_t* out_counts, uint64_t* out_nowhere)
+    try
+    {
+    static const char* who = "pgsd_domain_counts_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !box || !n || !out_counts || !out_nowhere)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    CellArgs cells;
+    memset(&cells, 0, sizeof(cells));
+    uint64_t n_cells = 1;
+    for (int a = 0; a < 3; a++)
+        {
+        if (n[a] < 1 || n[a] > CENSUS_MAX_AXIS_CELLS)
+            {
+            set_last_error(std::string(who) + ": every axis takes 1 to 64 cells");
+            return PGSD_ERROR_INVALID_ARGUMENT;
+            }
+        n_cells *= n[a];
+        }
+    if (n_cells > CENSUS_MAX_CELLS)
+        {
+        set_last_error(std::string(who) + ": at most 4096 cells");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    if (dimensions == 2 && n[2] != 1)
+        {
+        set_last_error(std::string(who) + ": dimensions == 2 takes one z cell (z is not looked at)");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    if (!interior_bounds && n_cells > 1)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const double* b = interior_bounds;
+    for (int a = 0; a < 3; a++)
+        {
+        cells.n[a] = n[a];
+        double below = 0.0;
+        for (uint32_t j = 0; j + 1 < n[a]; j++, b++)
+            {
+            if (!(below < *b && *b < 1.0))
+                {
+                set_last_error(std::string(who) + ": the interior bounds of an axis must ascend strictly inside (0, 1)");
+                return PGSD_ERROR_INVALID_ARGUMENT;
+                }
+            cells.bounds[a][j] = below = *b;
+            }
+        }
+    pgsd_index_entry c = *position; // a flush may move the index storage
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = census_args(who, s, handle, c, box, dimensions, &cells.d, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    *out_nowhere = 0;
+    if (c.N == 0)
+        {
+        memset(out_counts, 0, (size_t)n_cells * sizeof(uint64_t));
+        return PGSD_SUCCESS;
+        }
+    std::string err;
+    rc = device_pipeline_domain_counts(s->dev, foff, bytes, cells, out_counts, out_nowhere, &err);
+    if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_terms, const struct pgsd_index_entry* term_chunks,
                                         const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
                                         const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],

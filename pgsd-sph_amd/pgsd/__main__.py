@@ -2,7 +2,9 @@
 
 ``read``   the reference's one command (``__main__.py:52-87``): an interactive Python prompt with
            the file open as ``handle`` and, for the hoomd schema, the trajectory as ``traj``.
-``info``   header, frame count and the chunks of one frame, printed and done (no prompt).
+``info``   header, frame count and the chunks of one frame, printed and done (no prompt); ``--balance NX,NY,NZ``
+           adds the split lists that balance the frame's particles over such a decomposition and the per-cell counts
+           of the equal and of the balanced grid (the host models of ``pgsd.hoomd``: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -61,6 +63,31 @@ def _cmd_info(args):
             if f.chunk_exists(frame, name):
                 data = f.read_chunk(frame, name)
                 print("  %-28s %-8s %s" % (name, data.dtype, 'x'.join(str(n) for n in data.shape)))
+    if args.balance:
+        _print_balance(args, frame)
+
+
+def _print_balance(args, frame):
+    """``info --balance``: `pgsd.hoomd.balanced_grid` of one frame on the host, beside the equal grid."""
+    from . import hoomd
+    try:
+        nx, ny, nz = (int(v) for v in args.balance.split(','))
+    except ValueError:
+        raise ValueError("--balance takes NX,NY,NZ: %r" % args.balance)
+    with hoomd.open(args.file, 'r') as traj:
+        snap = traj[frame]
+    position, box, dims = snap.particles.position, snap.configuration.box, int(snap.configuration.dimensions)
+    _, splits = hoomd.balanced_grid(position, box, nx, ny, nz, bins=args.bins, dimensions=dims)
+    print("balance of frame %d over %d x %d x %d cells (%d bins):" % (frame, nx, ny, nz, args.bins))
+    for axis, split in zip('xyz', splits):
+        print("  %s_split:        %s" % (axis, 'None' if split is None else '[' + ', '.join(repr(w) for w in split) + ']'))
+    for label, grid in (('equal', (None, None, None)), ('balanced', splits)):
+        counts, nowhere = hoomd.domain_counts(position, box, nx, ny, nz, *grid, dimensions=dims)
+        mean = counts.sum() / len(counts)
+        print("  %s grid counts: %s" % (label, ' '.join(str(int(c)) for c in counts)))
+        print("  %s grid max / mean: %s" % (label, "%.3f" % (counts.max() / mean) if mean > 0 else 'n/a'))
+        if nowhere:
+            print("  %s grid nowhere: %d" % (label, nowhere))
 
 
 def _cmd_vtu(args):
@@ -84,6 +111,9 @@ def main(argv=None):
     p = sub.add_parser('info', help="print header and chunk list")
     p.add_argument('file', type=str)
     p.add_argument('-f', '--frame', type=int, default=-1, help="frame whose chunks are listed (default: last)")
+    p.add_argument('--balance', type=str, default=None, metavar='NX,NY,NZ',
+                   help="print the split lists that balance the frame over NX x NY x NZ cells, and the cell counts")
+    p.add_argument('--bins', type=int, default=1024, help="histogram bins per axis for --balance (a power of two)")
     p.set_defaults(func=_cmd_info)
     p = sub.add_parser('vtu', help="convert the frames to VTK .vtu files")
     p.add_argument('file', type=str)

@@ -1561,6 +1561,88 @@ cdef class PGSDFile:
         _raise_on_error(retval, self._name, err)
         return _device_head(rows, k), int(k)
 
+    def domain_histogram_device(self, frame, name, box, bins, dimensions=3):
+        """Per-axis histograms of a position chunk's fractional coordinates, counted on the GPU.
+
+        Args:
+            frame, name, box, dimensions: as :meth:`select_domain_device`.
+            bins (int): bins per axis, a power of two in [2, 4096].
+
+        Returns:
+            A ``(3, bins)`` int64 numpy array: row ``a`` counts the rows whose wrapped fraction ``f[a]`` -- the value
+            :meth:`select_domain_device` compares -- has ``int(f[a] * bins) == k``; NaN fractions are counted nowhere
+            and the z row is zero when ``dimensions == 2``.  Exactly :func:`pgsd.hoomd.axis_histograms`.  The staged
+            position rows are kept until the next :meth:`wait_read`: a :meth:`domain_counts_device` or a selection of
+            the same chunk before it reads no file bytes again.  Needs no tensor library.
+        """
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        c_box = numpy.ascontiguousarray(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+        if c_box.shape[0] != 6:
+            raise ValueError("box must hold 6 values")
+        if not 0 <= int(bins) < (1 << 32):
+            raise ValueError("domain_histogram_device: bins must be a power of two in [2, 4096]")
+        hist = numpy.zeros((3, int(bins) if int(bins) <= 4096 else 1), dtype=numpy.uint64)  # (the library refuses the rest)
+        cdef uintptr_t c_pbox = c_box.ctypes.data, c_hist = hist.ctypes.data
+        cdef uint32_t c_dims = int(dimensions), c_bins = int(bins)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_domain_histogram_device(&self._handle, &entry, <const float*>c_pbox, c_dims, c_bins,
+                                                    <uint64_t*>c_hist)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("domain_histogram_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
+        _raise_on_error(retval, self._name, err)
+        return hist.astype(numpy.int64)
+
+    def domain_counts_device(self, frame, name, box, n, bounds, dimensions=3):
+        """The number of rows of a position chunk in every cell of a rectilinear decomposition, counted on the GPU.
+
+        Args:
+            frame, name, box, dimensions: as :meth:`select_domain_device`.
+            n: ``(nx, ny, nz)``, each 1 to 64, at most 4096 cells; ``nz == 1`` when ``dimensions == 2``.
+            bounds: three sequences, per axis its ``n[a] - 1`` interior cell boundaries, strictly ascending inside
+                (0, 1) -- :func:`pgsd.hoomd.grid_bounds` without each list's leading 0 and trailing 1.
+
+        Returns:
+            ``(counts, nowhere)``: ``counts`` a flat int64 numpy array of ``nx * ny * nz`` entries in
+            :func:`pgsd.hoomd.domain_grid`'s rank order -- entry ``r`` is the count :meth:`select_domain_device` returns
+            for cell ``r`` --, ``nowhere`` the number of rows with a NaN fraction.  Exactly
+            :func:`pgsd.hoomd.domain_counts`.  Staging as :meth:`domain_histogram_device`.  Needs no tensor library.
+        """
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        c_box = numpy.ascontiguousarray(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+        if c_box.shape[0] != 6:
+            raise ValueError("box must hold 6 values")
+        cells = [int(v) for v in n]
+        if len(cells) != 3 or len(bounds) != 3:
+            raise ValueError("domain_counts_device: n holds three cell counts and bounds three lists")
+        if any(not 0 <= v < (1 << 32) for v in cells):
+            raise ValueError("domain_counts_device: every axis takes 1 to 64 cells, at most 4096 in all")
+        inner = [numpy.asarray(b, dtype=numpy.float64).reshape(-1) for b in bounds]
+        if any(inner[a].shape[0] != max(cells[a] - 1, 0) for a in range(3)):
+            raise ValueError("domain_counts_device: axis a takes n[a] - 1 interior bounds")
+        c_n = numpy.array(cells, dtype=numpy.uint32)
+        c_b = numpy.ascontiguousarray(numpy.concatenate(inner + [numpy.zeros(1)]))     # (never empty: a valid pointer)
+        n_cells = cells[0] * cells[1] * cells[2]
+        counts = numpy.zeros(n_cells if 1 <= n_cells <= 4096 else 1, dtype=numpy.uint64)    # (the library refuses the rest)
+        cdef uintptr_t c_pbox = c_box.ctypes.data, c_pn = c_n.ctypes.data, c_pb = c_b.ctypes.data
+        cdef uintptr_t c_counts = counts.ctypes.data
+        cdef uint32_t c_dims = int(dimensions)
+        cdef uint64_t nowhere = 0
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_domain_counts_device(&self._handle, &entry, <const float*>c_pbox, c_dims,
+                                                 <const uint32_t*>c_pn, <const double*>c_pb, <uint64_t*>c_counts, &nowhere)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("domain_counts_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
+        _raise_on_error(retval, self._name, err)
+        return counts.astype(numpy.int64), int(nowhere)
+
     def select_halo_device(self, frame, name, box, domain, ghost, dimensions=3):
         """A domain plus the ghost layer its neighbours reach, selected on the GPU from one position chunk.
 

@@ -316,13 +316,17 @@ def _split_bounds(n, split, axis):
     return bounds + [1.0]
 
 
+def grid_bounds(nx, ny, nz, x_split=None, y_split=None, z_split=None):
+    """``(bx, by, bz)``: the cell boundaries of an nx x ny x nz domain decomposition along each axis -- ``n + 1`` ascending
+    fractions from 0.0 to 1.0 --, with `domain_grid`'s split lists.  Cell ``i`` of an axis is ``[b[i], b[i + 1])``."""
+    return (_split_bounds(nx, x_split, 'x'), _split_bounds(ny, y_split, 'y'), _split_bounds(nz, z_split, 'z'))
+
+
 def domain_grid(nx, ny, nz, x_split=None, y_split=None, z_split=None):
     """The cells of an nx x ny x nz domain decomposition as `Domain` objects, in HOOMD's rank order (``Index3D``:
     rank = x + nx * (y + ny * z), x fastest).  ``x_split`` etc. are the widths of the first n - 1 cells along that axis
     as fractions of the box, as in HOOMD's domain-decomposition split lists; ``None``: equal cells."""
-    bx = _split_bounds(nx, x_split, 'x')
-    by = _split_bounds(ny, y_split, 'y')
-    bz = _split_bounds(nz, z_split, 'z')
+    bx, by, bz = grid_bounds(nx, ny, nz, x_split, y_split, z_split)
     return [Domain((bx[i], by[j], bz[k]), (bx[i + 1], by[j + 1], bz[k + 1]))
             for k in range(int(nz)) for j in range(int(ny)) for i in range(int(nx))]
 
@@ -380,6 +384,131 @@ def _wrapped_fractions(position, box, dimensions):
             f[f >= 1.0] = 0.0
             out.append(f)
     return out
+
+
+_CENSUS_MAX_BINS = 4096
+_CENSUS_MAX_AXIS_CELLS = 64
+_CENSUS_MAX_CELLS = 4096
+
+
+def _census_bins(bins):
+    bins = int(bins)
+    if bins < 2 or bins > _CENSUS_MAX_BINS or bins & (bins - 1):
+        raise ValueError("bins must be a power of two in [2, %d]: %r" % (_CENSUS_MAX_BINS, bins))
+    return bins
+
+
+def axis_histograms(position, box, bins, dimensions=3):
+    """Per-axis histograms of the particles' fractional coordinates: a ``(3, bins)`` int64 array, the definition the GPU
+    census (`pgsd.fl.PGSDFile.domain_histogram_device`, `HOOMDTrajectory.axis_histograms_device`) equals exactly.
+
+    With ``f[a]`` the wrapped fraction `domain_rows` compares, row ``a`` counts in bin ``int(f[a] * bins)`` every row
+    whose ``f[a]`` is no NaN (NaN and infinite coordinates give one; such a row is counted in no bin of that axis).
+    ``bins`` is a power of two in [2, 4096]: ``f`` lies in [0, 1), so the product is exact and below ``bins`` -- no
+    clamp --, and every bin edge ``k / bins`` is an exact float64: the cumulative histogram at ``k`` IS the number of
+    rows `domain_rows` gives the slab ``[0, k / bins)``.  With ``dimensions == 2`` the z row is zero."""
+    bins = _census_bins(bins)
+    f = _wrapped_fractions(position, box, dimensions)
+    hist = numpy.zeros((3, bins), dtype=numpy.int64)
+    for a in range(len(f)):
+        fa = f[a][f[a] == f[a]]
+        hist[a] = numpy.bincount((fa * bins).astype(numpy.int64), minlength=bins)
+    return hist
+
+
+def _census_cells(nx, ny, nz, dimensions):
+    n = (int(nx), int(ny), int(nz))
+    if any(v < 1 or v > _CENSUS_MAX_AXIS_CELLS for v in n) or n[0] * n[1] * n[2] > _CENSUS_MAX_CELLS:
+        raise ValueError("a census takes 1 to %d cells per axis and at most %d in all: %r"
+                         % (_CENSUS_MAX_AXIS_CELLS, _CENSUS_MAX_CELLS, n))
+    if int(dimensions) == 2 and n[2] != 1:
+        raise ValueError("dimensions == 2 takes nz == 1: z is not looked at, several z cells would each own every row")
+    return n
+
+
+def _interior_bounds(bounds):
+    """The interior boundaries of `grid_bounds`' three lists, checked: strictly ascending inside (0, 1)."""
+    inner = [numpy.array(b[1:-1], dtype=numpy.float64) for b in bounds]
+    for a, b in enumerate(inner):
+        edges = numpy.concatenate(([0.0], b, [1.0]))
+        if not numpy.all(edges[:-1] < edges[1:]):
+            raise ValueError("the cell boundaries on axis %s do not ascend strictly inside (0, 1)" % 'xyz'[a])
+    return inner
+
+
+def domain_counts(position, box, nx, ny, nz, x_split=None, y_split=None, z_split=None, dimensions=3):
+    """``(counts, nowhere)``: the number of particles in every cell of `domain_grid` ``(nx, ny, nz, x_split, y_split,
+    z_split)`` -- a flat int64 array in its rank order, ``rank = x + nx * (y + ny * z)`` --, the definition the GPU
+    census (`pgsd.fl.PGSDFile.domain_counts_device`, `HOOMDTrajectory.domain_counts_device`) equals exactly.
+
+    A row's cell on an axis is the number of that axis' interior boundaries ``b`` (`grid_bounds`) with ``b <= f``, so
+    ``counts[r] == len(domain_rows(position, box, domain_grid(...)[r], dimensions))``.  A row whose fraction is NaN on an
+    axis that takes part belongs to no cell and is counted in ``nowhere``: ``counts.sum() + nowhere == N``.  Each of
+    ``nx``, ``ny``, ``nz`` is at most 64, their product at most 4096; ``dimensions == 2`` needs ``nz == 1``."""
+    n = _census_cells(nx, ny, nz, dimensions)
+    inner = _interior_bounds(grid_bounds(n[0], n[1], n[2], x_split, y_split, z_split))
+    f = _wrapped_fractions(position, box, dimensions)
+    rows = f[0].shape[0]
+    somewhere = numpy.ones(rows, dtype=bool)
+    cell = numpy.zeros(rows, dtype=numpy.int64)
+    stride = 1
+    for a in range(len(f)):
+        ok = f[a] == f[a]
+        somewhere &= ok
+        cell += numpy.searchsorted(inner[a], numpy.where(ok, f[a], 0.0), side='right') * stride   # bounds <= f
+        stride *= n[a]
+    counts = numpy.bincount(cell[somewhere], minlength=n[0] * n[1] * n[2]).astype(numpy.int64)
+    return counts, int(rows - numpy.count_nonzero(somewhere))
+
+
+def balanced_splits(hist_row, n, min_bins=1):
+    """The split list -- the widths of the first ``n - 1`` cells, as `domain_grid` takes them -- that cuts one axis into
+    ``n`` slabs of nearly equal particle counts, from that axis' row of `axis_histograms`.  Integer arithmetic only.
+
+    With ``cum(k)`` the sum of bins ``[0, k)`` and ``total = cum(bins)``, boundary ``j`` (``1 <= j < n``) is the
+    smallest bin edge ``k`` with ``cum(k) * n >= j * total``, then forced into ``[k_(j-1) + min_bins, bins - (n - j) *
+    min_bins]`` (``k_0 = 0``): every slab is at least ``min_bins`` bins wide -- ``ceil(ghost_fraction * bins)`` keeps
+    a cell no narrower than its ghost layer.  An empty histogram gives equal edges ``max(j * bins // n, j * min_bins)``,
+    forced the same way.  The widths ``(k_j - k_(j-1)) / bins`` are dyadic, so `domain_grid`'s running sums are exact
+    and its boundaries are these edges.  Where nothing was forced, every slab's count differs from ``total / n`` by
+    less than the largest bin's count.  ``n == 1`` gives ``[]``; ``n * min_bins > bins`` raises ValueError."""
+    h = [int(v) for v in numpy.asarray(hist_row).reshape(-1)]
+    bins = _census_bins(len(h))
+    n, min_bins = int(n), int(min_bins)
+    if n < 1 or min_bins < 1:
+        raise ValueError("n and min_bins must be at least 1")
+    if n * min_bins > bins:
+        raise ValueError("%d slabs of at least %d bins do not fit into %d bins" % (n, min_bins, bins))
+    if any(v < 0 for v in h):
+        raise ValueError("a histogram holds counts >= 0")
+    cum = [0]
+    for v in h:
+        cum.append(cum[-1] + v)
+    total = cum[-1]
+    edges, k = [0], 0
+    for j in range(1, n):
+        if total == 0:
+            k = max(j * bins // n, j * min_bins)
+        else:
+            while cum[k] * n < j * total:
+                k += 1
+        edges.append(min(max(k, edges[-1] + min_bins), bins - (n - j) * min_bins))
+    return [(edges[j] - edges[j - 1]) / bins for j in range(1, n)]
+
+
+def _balanced_axis_splits(hist, n, min_bins, dimensions):
+    return (balanced_splits(hist[0], n[0], min_bins), balanced_splits(hist[1], n[1], min_bins),
+            None if int(dimensions) == 2 else balanced_splits(hist[2], n[2], min_bins))
+
+
+def balanced_grid(position, box, nx, ny, nz, bins=1024, min_bins=1, dimensions=3):
+    """``(domains, (x_split, y_split, z_split))``: the decomposition whose slabs hold nearly equal particle counts on
+    every axis -- `axis_histograms` at ``bins`` bins, `balanced_splits` per axis, `domain_grid` over the result (the
+    marginal quantiles, the first step of HOOMD's load balancer; `domain_counts` tells how even the cells came out).
+    The z split is ``None`` when ``dimensions == 2``."""
+    n = _census_cells(nx, ny, nz, dimensions)
+    splits = _balanced_axis_splits(axis_histograms(position, box, bins, dimensions), n, min_bins, dimensions)
+    return domain_grid(n[0], n[1], n[2], *splits), splits
 
 
 def ghost_fractions(box, width, dimensions=3):
@@ -1879,6 +2008,85 @@ class HOOMDTrajectory(object):
         if domain is not None:
             snap.domain = domain
         self._gather_rows_device(idx, snap, rows, count, scalar4, defaults, n_global, tuple(staged))
+
+    def _census_frame(self, idx):
+        """What a census of frame ``idx`` looks at: ``(box, dimensions, n_global, f_pos)`` -- the frame's configuration
+        as a domain read takes it, and the frame whose position chunk it reads (`_effective_frame`; ``None``: stored
+        nowhere, every particle sits on the default row)."""
+        if idx < 0:
+            idx += len(self)
+        if idx >= len(self) or idx < 0:
+            raise IndexError()
+        f = self.file
+        conf = ConfigurationData()
+        self._read_scalar_any(idx, 'configuration/dimensions', conf, 'dimensions')
+        box_frame = self._frame_of(idx, 'configuration/box')
+        if box_frame is None:
+            box = conf._default_value['box']
+        elif box_frame == 0:
+            box = self._frame0_small('configuration/box')
+        else:
+            box = f.read_chunk(box_frame, 'configuration/box')
+        fn = self._frame_of(idx, 'particles/N')
+        n_global = 0 if fn is None else int((self._frame0_small('particles/N') if fn == 0
+                                             else f.read_chunk(fn, 'particles/N'))[0])
+        return box, int(conf.dimensions), n_global, self._effective_frame(idx, 'particles/position', n_global)
+
+    _DEFAULT_POSITION = numpy.zeros((1, 3), dtype=numpy.float32)
+
+    def axis_histograms_device(self, idx, bins=1024):
+        """`axis_histograms` of frame ``idx``, counted on the GPU from the frame's effective position chunk with the
+        frame's box and dimensions: a ``(3, bins)`` int64 numpy array.  The position chunk is staged into HBM, binned
+        there in one pass, and released; no per-particle data reaches the host.  A position stored nowhere is all
+        defaults and is answered on the host from the one default row."""
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        if f_pos is None:
+            return axis_histograms(self._DEFAULT_POSITION, box, bins, dims) * n_global
+        try:
+            return self.file.domain_histogram_device(f_pos, 'particles/position', box, _census_bins(bins), dims)
+        finally:
+            self.file.wait_read()           # the staged chunk is released: a loop over frames piles nothing up in HBM
+
+    def domain_counts_device(self, idx, nx, ny, nz, x_split=None, y_split=None, z_split=None):
+        """`domain_counts` of frame ``idx``, counted on the GPU like `axis_histograms_device`: ``(counts, nowhere)``,
+        the particle count of every cell of ``domain_grid(nx, ny, nz, x_split, y_split, z_split)`` in its rank order --
+        what each rank's ``read_frame_device(idx, domain=...)`` will hold, known before any rank has read."""
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        n = _census_cells(nx, ny, nz, dims)
+        inner = _interior_bounds(grid_bounds(n[0], n[1], n[2], x_split, y_split, z_split))
+        if f_pos is None:
+            counts, nowhere = domain_counts(self._DEFAULT_POSITION, box, n[0], n[1], n[2], x_split, y_split, z_split, dims)
+            return counts * n_global, nowhere * n_global
+        try:
+            return self.file.domain_counts_device(f_pos, 'particles/position', box, n, inner, dims)
+        finally:
+            self.file.wait_read()
+
+    def balanced_grid_device(self, idx, nx, ny, nz, bins=1024, min_bins=1):
+        """`balanced_grid` of frame ``idx`` on the GPU, with the outcome: ``(domains, splits, counts, nowhere)`` -- the
+        decomposition and its split lists as `balanced_grid` returns them, and `domain_counts` of that decomposition.
+        One histogram pass, `balanced_splits` on the host, one counting pass served from the rows the histogram left
+        staged: the position chunk is read from the file once."""
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        n = _census_cells(nx, ny, nz, dims)
+        bins = _census_bins(bins)
+        f = self.file
+        try:
+            if f_pos is None:
+                hist = axis_histograms(self._DEFAULT_POSITION, box, bins, dims) * n_global
+            else:
+                hist = f.domain_histogram_device(f_pos, 'particles/position', box, bins, dims)
+            splits = _balanced_axis_splits(hist, n, min_bins, dims)
+            domains = domain_grid(n[0], n[1], n[2], *splits)
+            if f_pos is None:
+                counts, nowhere = domain_counts(self._DEFAULT_POSITION, box, n[0], n[1], n[2], *splits, dimensions=dims)
+                return domains, splits, counts * n_global, nowhere * n_global
+            inner = _interior_bounds(grid_bounds(n[0], n[1], n[2], *splits))
+            counts, nowhere = f.domain_counts_device(f_pos, 'particles/position', box, n, inner, dims)
+            return domains, splits, counts, nowhere
+        finally:
+            if f_pos is not None:
+                f.wait_read()
 
     def _frame_of(self, idx, chunk):
         """The frame whose copy of a chunk that is NOT per-particle (box, N, types, log/*) frame ``idx`` reads: its

@@ -214,6 +214,11 @@ cdef extern from "pgsd_private.h" nogil:
                                  const uint64_t* sets, const pgsd_index_entry* position, const float* box,
                                  uint32_t dimensions, const double* dlo, const double* dhi, uint32_t* out_rows,
                                  uint64_t* out_count)
+    int pgsd_domain_histogram_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
+                                     uint32_t dimensions, uint32_t bins, uint64_t* out_hist)
+    int pgsd_domain_counts_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
+                                  uint32_t dimensions, const uint32_t* n, const double* interior_bounds,
+                                  uint64_t* out_counts, uint64_t* out_nowhere)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                               const pgsd_field_dst* dst)
     cdef struct pgsd_row_plan:
