@@ -691,6 +691,16 @@ int device_pipeline_domain_counts(DevicePipeline* p, long long file_offset, size
     return report(p, p->domain_counts(file_offset, bytes, c, out_counts, out_nowhere), err, true);
     }
 
+int device_pipeline_order_rows(DevicePipeline* p, long long file_offset, size_t bytes, const OrderArgs& o, uint32_t* rows,
+                               int32_t* shift, int32_t* out_cell, std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->order_rows(file_offset, bytes, o, rows, shift, out_cell, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
 void device_pipeline_set_source_stream(DevicePipeline* p, void* stream)
     {
     p->set_source_stream(stream);

@@ -145,6 +145,8 @@ class DevicePipeline
                     uint64_t out_counts[2]);
     int domain_histogram(long long file_offset, size_t bytes, DomainArgs d, uint32_t bins, uint64_t* out_hist);
     int domain_counts(long long file_offset, size_t bytes, CellArgs c, uint64_t* out_counts, uint64_t* out_nowhere);
+    int order_rows(long long file_offset, size_t bytes, OrderArgs o, uint32_t* rows, int32_t* shift, int32_t* out_cell,
+                   std::string* why);
     int wait_read();
 
     // ---- accessors ----

@@ -453,6 +453,28 @@ int DevicePipeline::domain_counts(long long file_offset, size_t bytes, CellArgs 
     return rc;
     }
 
+// Cell order: select_domain's staging -- after a selection of the same frame stage_chunks finds the position rows in the
+// kept list and reads no file byte --, then keys, sort and apply on the pack stream, synchronised.  The lists are the
+// caller's, so what its stream still does with them comes first.
+int DevicePipeline::order_rows(long long file_offset, size_t bytes, OrderArgs o, uint32_t* rows, int32_t* shift,
+                               int32_t* out_cell, std::string* why)
+    {
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    const ChunkRange range = {file_offset, bytes};
+    rc = stage_chunks(&range, 1, o.d.N, &o.d.pos);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = order_after_source();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = launch_order_rows(o, rows, shift, out_cell, m_res.pack_stream, why);
+    if (rc == PGSD_ERROR_DEVICE && why)
+        fail(*why);
+    return rc;
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

@@ -246,6 +246,26 @@ int device_pipeline_domain_histogram(DevicePipeline*, long long file_offset, siz
 // fraction on an axis that takes part
 int device_pipeline_domain_counts(DevicePipeline*, long long file_offset, size_t bytes, const CellArgs& c,
                                   uint64_t* out_counts, uint64_t* out_nowhere, std::string* err);
+// Cell order (pgsd.hoomd.cell_ids / cell_order are the definitions): a row list sorted by the cell its rows' wrapped
+// fractions -- DomainArgs without lo / hi -- fall into in a uniform cells[0] x cells[1] x cells[2] grid, stably; entries
+// [n_owned, n) are a second run (the ghosts) that is sorted on its own.
+enum
+    {
+    ORDER_MAX_AXIS_CELLS = 1024 // cells per axis: 2 * (1024^3 + 1) keys still fit 32 bits
+    };
+struct OrderArgs
+    {
+    DomainArgs d;
+    uint64_t n, n_owned; // entries of the list; the first n_owned are the owned run
+    uint32_t cells[3];
+    uint32_t n_cells;    // their product: the id of a row with a NaN fraction
+    };
+// stage the position chunk at `file_offset` (o.d.N rows) -- or take it from what an earlier selection left staged --,
+// sort rows[0 .. o.n) (device, the caller's) by cell in place, permute shift (device, 3 x (o.n - o.n_owned) int32, or
+// null) like the ghost run, write the sorted cell ids to out_cell (device, o.n int32, or null); synchronous.  An entry
+// >= o.d.N refuses the call with nothing written.  The staged rows stay until the next wait_read.
+int device_pipeline_order_rows(DevicePipeline*, long long file_offset, size_t bytes, const OrderArgs& o, uint32_t* rows,
+                               int32_t* shift, int32_t* out_cell, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

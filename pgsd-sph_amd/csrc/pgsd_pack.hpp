@@ -249,6 +249,13 @@ int launch_select_halo(const HaloArgs& h, uint32_t* out_rows, int32_t* out_shift
 int launch_axis_histograms(const DomainArgs& d, uint32_t bins, uint64_t* out_hist, hipStream_t stream, std::string* err);
 int launch_cell_counts(const CellArgs& c, uint64_t* out_counts, uint64_t* out_nowhere, hipStream_t stream, std::string* err);
 
+// cell order (OrderArgs, d.pos filled in): keys -> stable radix sort of (key, entry) pairs -> apply; rows (device, o.n
+// entries) is sorted in place, shift (device, 3 x ghosts, or null) follows its ghosts, out_cell (device, o.n, or null)
+// receives the sorted cell ids; synchronises `stream`.  PGSD_ERROR_INVALID_ARGUMENT, with nothing written, if an entry
+// is >= o.d.N
+int launch_order_rows(const OrderArgs& o, uint32_t* rows, int32_t* shift, int32_t* out_cell, hipStream_t stream,
+                      std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);

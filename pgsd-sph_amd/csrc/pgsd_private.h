@@ -174,6 +174,26 @@ extern "C"
                                   uint32_t dimensions, const uint32_t n[3], const double* interior_bounds,
                                   uint64_t* out_counts, uint64_t* out_nowhere);
 
+    /* Cell order: sort a row list by the grid cell of its rows' positions (pgsd.hoomd.cell_ids and cell_order are the
+       definitions).  position, box, dimensions: as pgsd_select_domain_device's.  With f[a] the wrapped fraction of a row
+       on axis a, i_a = min(int(f[a] * cells[a]), cells[a] - 1) and the row's cell id is i_x + cells[0] * (i_y + cells[1] *
+       i_z); a row with a NaN fraction on an axis that takes part gets cells[0] * cells[1] * cells[2], which sorts last;
+       z takes no part when dimensions == 2.  1 <= cells[a] <= 1024.
+       rows (device, n entries, any order, repeats allowed) is reordered IN PLACE by a stable sort on the cell id: entries
+       of one cell keep their order.  Entries [0, n_owned) and [n_owned, n) -- the owned and the ghost run of
+       pgsd_select_halo_device; n_owned == n without ghosts -- are sorted separately and stay where they are.  shift
+       (device, 3 x (n - n_owned) int32, or NULL): the ghost run's rows of three, permuted like its entries.  out_cell
+       (device, n int32, or NULL) receives the sorted cell ids, the ghost run's ascending on their own.
+       The position chunk is staged whole unless an earlier selection or census of the same chunk left it staged (then no
+       file byte is read), the sort runs on the handle's GPU and the call synchronises; the staged rows are kept until
+       the next pgsd_device_wait_read.  n == 0 succeeds and touches nothing.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(): pgsd_select_domain_device's refusals; a cells[a] of 0
+       or above 1024; dimensions == 2 with cells[2] != 1; n_owned > n; n >= 2^32; an entry >= position->N -- found
+       before anything of the caller's is written: rows, shift and out_cell are as they were. */
+    int pgsd_order_rows_by_cell_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                       const float box[6], uint32_t dimensions, const uint32_t cells[3], uint32_t* rows,
+                                       uint64_t n, uint64_t n_owned, int32_t* shift, int32_t* out_cell);
+
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is
        staged whole; like pgsd_read_chunk_device the gather runs at pgsd_device_wait_read, which fails with

@@ -579,6 +579,65 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_order_rows_by_cell_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                              const float box[6], uint32_t dimensions, const uint32_t cells[3],
+                                              uint32_t* rows, uint64_t n, uint64_t n_owned, int32_t* shift, int32_t* out_cell)
+    try
+    {
+    static const char* who = "pgsd_order_rows_by_cell_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !box || !cells)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    OrderArgs o;
+    memset(&o, 0, sizeof(o));
+    o.n_cells = 1;
+    for (int a = 0; a < 3; a++)
+        {
+        if (cells[a] < 1 || cells[a] > ORDER_MAX_AXIS_CELLS)
+            return refuse("every axis takes 1 to 1024 cells");
+        o.cells[a] = cells[a];
+        o.n_cells *= cells[a];
+        }
+    if (dimensions == 2 && cells[2] != 1)
+        return refuse("dimensions == 2 takes one z cell (z is not looked at)");
+    if (n_owned > n)
+        return refuse("n_owned exceeds the number of entries");
+    if (n >= (1ull << 32))
+        return refuse("a row list holds fewer than 2^32 entries");
+    pgsd_index_entry c = *position; // a flush may move the index storage
+    DomainArgs d;
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = census_args(who, s, handle, c, box, dimensions, &d, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (n == 0)
+        return PGSD_SUCCESS;
+    if (!rows)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    if (c.N == 0)
+        return refuse("an entry of the row list lies outside the position chunk (nothing was reordered)");
+    o.d = d;
+    o.n = n;
+    o.n_owned = n_owned;
+    std::string err;
+    rc = device_pipeline_order_rows(s->dev, foff, bytes, o, rows, shift, out_cell, &err);
+    if (rc == PGSD_ERROR_INVALID_ARGUMENT)
+        return refuse(err.empty() ? std::string("refused") : err);
+    if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_terms, const struct pgsd_index_entry* term_chunks,
                                         const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
                                         const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],

@@ -1698,6 +1698,70 @@ cdef class PGSDFile:
             shift = room[:n_ghost].clone()
         return _device_head(rows, n_owned + n_ghost), n_owned, n_ghost, shift
 
+    def order_rows_by_cell_device(self, frame, name, box, cells, rows, n=None, n_owned=None, shift=None, dimensions=3):
+        """Sort a row list by the grid cell of its rows' positions, on the GPU and in place.
+
+        Args:
+            frame, name, box, dimensions: as :meth:`select_domain_device` (the position chunk the rows index).
+            cells: ``(cx, cy, cz)``, each 1 to 1024; ``cz == 1`` when ``dimensions == 2``.
+            rows: 32-bit row indices in GPU memory (e.g. :meth:`select_domain_device`'s), any order, repeats allowed.
+            n (int): the number of entries to sort (default: all of ``rows``).
+            n_owned (int): entries ``[0, n_owned)`` and ``[n_owned, n)`` -- :meth:`select_halo_device`'s owned and ghost
+                runs -- are sorted separately and stay in that order (default: ``n``, one run).
+            shift: the ghost run's ``(n - n_owned) x 3`` int32 array in GPU memory, permuted with its rows.
+
+        Returns:
+            The sorted cell ids of the ``n`` entries, int32 in GPU memory, typed like :func:`select_rows`' lists.  ``rows``
+            (and ``shift``) are reordered in place by a stable sort on :func:`pgsd.hoomd.cell_ids`: exactly
+            :func:`pgsd.hoomd.cell_order`.  After a selection of the same chunk (before the next :meth:`wait_read`) the
+            staged position rows are used and no file byte is read.  An entry outside the chunk raises ValueError and
+            leaves ``rows`` as it was.  Needs no tensor library.
+        """
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        c_box = numpy.ascontiguousarray(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+        if c_box.shape[0] != 6:
+            raise ValueError("box must hold 6 values")
+        grid = [int(v) for v in cells]
+        if len(grid) != 3 or any(not 0 <= v < (1 << 32) for v in grid):
+            raise ValueError("order_rows_by_cell_device: cells holds three counts, each 1 to 1024")
+        c_cells = numpy.array(grid, dtype=numpy.uint32)
+        p_rows, n_rows = _index_rows(rows)
+        count = n_rows if n is None else int(n)
+        owned = count if n_owned is None else int(n_owned)
+        if count >= (1 << 32):
+            raise ValueError("order_rows_by_cell_device: a row list holds fewer than 2^32 entries")
+        if count < 0 or count > n_rows:
+            raise ValueError("order_rows_by_cell_device: rows holds fewer entries than n")
+        if owned < 0 or owned > count:
+            raise ValueError("order_rows_by_cell_device: n_owned exceeds the number of entries")
+        cdef uintptr_t c_shift = 0
+        if shift is not None:
+            if (shift.element_size() if hasattr(shift, 'element_size')
+                    else numpy.dtype(shift.__cuda_array_interface__['typestr']).itemsize) != 4:
+                raise ValueError("order_rows_by_cell_device: shift holds 32-bit integers")
+            p_shift, shift_bytes = _device_memory(shift, "shift")
+            if shift_bytes < 12 * (count - owned):
+                raise ValueError("order_rows_by_cell_device: shift holds fewer than 3 x (n - n_owned) entries")
+            c_shift = p_shift
+        cell = _device_empty((max(count, 1),), numpy.int32, self.pipeline_device())
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the sort is ordered behind this stream's use of `rows` and `shift`
+        cdef uintptr_t c_rows = p_rows, c_cell = cell.data_ptr(), c_pbox = c_box.ctypes.data, c_pc = c_cells.ctypes.data
+        cdef uint32_t c_dims = int(dimensions)
+        cdef uint64_t c_n = count, c_owned = owned
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_order_rows_by_cell_device(&self._handle, &entry, <const float*>c_pbox, c_dims,
+                                                      <const uint32_t*>c_pc, <uint32_t*>c_rows, c_n, c_owned,
+                                                      <int32_t*>c_shift, <int32_t*>c_cell)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("order_rows_by_cell_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
+        _raise_on_error(retval, self._name, err)
+        return _device_head(cell, count)
+
     def select_where_device(self, terms, domain=None, box=None, dimensions=3):
         """The rows of a frame that satisfy every term of a predicate over per-particle chunks, selected on the GPU.
 

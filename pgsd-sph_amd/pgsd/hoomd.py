@@ -636,6 +636,85 @@ def halo_rows(position, box, domain, ghost, dimensions=3):
     return numpy.flatnonzero(owned), ghost_rows, shift[ghost_rows]
 
 
+_ORDER_MAX_AXIS_CELLS = 1024
+
+
+def _order_cells(cells, dimensions):
+    c = tuple(int(v) for v in cells)
+    if len(c) != 3 or any(v < 1 or v > _ORDER_MAX_AXIS_CELLS for v in c):
+        raise ValueError("a cell grid takes three counts (cx, cy, cz), each 1 to %d: %r" % (_ORDER_MAX_AXIS_CELLS, cells))
+    if int(dimensions) == 2 and c[2] != 1:
+        raise ValueError("dimensions == 2 takes cz == 1: z is not looked at")
+    return c
+
+
+def cell_ids(position, box, cells, dimensions=3):
+    """The cell of every row of ``position`` (N x 3) in a uniform ``cells = (cx, cy, cz)`` grid over the box: an int64
+    array, the definition the GPU ordering (`pgsd.fl.PGSDFile.order_rows_by_cell_device`,
+    ``read_frame_device(cell_order=...)``) equals exactly.
+
+    With ``f[a]`` the wrapped fraction `domain_rows` compares, ``i_a = min(int(f[a] * c_a), c_a - 1)`` in float64 and
+    ``id = i_x + cx * (i_y + cy * i_z)`` -- x fastest, like `domain_grid`'s ranks.  Each count is 1 to 1024;
+    ``dimensions == 2`` needs ``cz == 1`` and does not look at z.  A row whose fraction is NaN on an axis that takes part
+    (NaN or infinite coordinates) gets ``cx * cy * cz``, the "nowhere" id, which sorts behind every cell.  The ``min``
+    never binds: ``f <= 1 - 2**-53`` and for every ``c <= 1024`` the float64 product ``f * c`` rounds below ``c``."""
+    c = _order_cells(cells, dimensions)
+    f = _wrapped_fractions(position, box, dimensions)
+    rows = f[0].shape[0]
+    somewhere = numpy.ones(rows, dtype=bool)
+    ids = numpy.zeros(rows, dtype=numpy.int64)
+    stride = 1
+    for a in range(len(f)):
+        ok = f[a] == f[a]
+        somewhere &= ok
+        ids += numpy.minimum((numpy.where(ok, f[a], 0.0) * c[a]).astype(numpy.int64), c[a] - 1) * stride
+        stride *= c[a]
+    ids[~somewhere] = c[0] * c[1] * c[2]
+    return ids
+
+
+def cell_order(position, box, rows, cells, dimensions=3, n_owned=None):
+    """``(rows_sorted, cell_sorted, perm)``: the row list ``rows`` of ``position`` ordered by cell -- a stable sort
+    (``numpy.argsort(kind='stable')``) on ``cell_ids(position[rows], box, cells, dimensions)``, so the rows of one cell
+    keep their relative order (ascending file rows for a selection's list).  ``rows_sorted = rows[perm]`` and
+    ``cell_sorted`` are int64, ``perm`` the permutation applied.
+
+    With ``n_owned`` the owned run ``rows[:n_owned]`` and the ghost run ``rows[n_owned:]`` of `halo_rows` are sorted
+    separately and stay in that order; each run's ids ascend on their own, and `halo_rows`' shift rows are permuted with
+    ``perm[n_owned:] - n_owned``.  An entry outside ``position`` raises ValueError."""
+    p = numpy.asarray(position)
+    p = p.reshape(-1, 3) if p.size else numpy.zeros((0, 3))
+    rows = numpy.asarray(rows, dtype=numpy.int64).reshape(-1)
+    n = rows.shape[0]
+    n_owned = n if n_owned is None else int(n_owned)
+    if n_owned < 0 or n_owned > n:
+        raise ValueError("n_owned exceeds the number of entries: %r of %d" % (n_owned, n))
+    _order_cells(cells, dimensions)
+    if n and (rows.min() < 0 or rows.max() >= p.shape[0]):
+        raise ValueError("an entry of the row list lies outside the position array")
+    ids = cell_ids(p[rows], box, cells, dimensions)
+    perm = numpy.concatenate((numpy.argsort(ids[:n_owned], kind='stable'),
+                              numpy.argsort(ids[n_owned:], kind='stable') + n_owned)).astype(numpy.int64)
+    return rows[perm], ids[perm], perm
+
+
+def cell_grid_for(box, width, dimensions=3):
+    """``(cx, cy, cz)``: the largest cell counts whose cells are no narrower than the real distance ``width`` (an
+    interaction range, a neighbour-search cell) -- ``c_a = clamp(floor(1 / g_a), 1, 1024)`` with ``g =``
+    `ghost_fractions` ``(box, width, dimensions)``, the width as a fraction of the box's nearest plane distance on each
+    axis; ``cz == 1`` when ``dimensions == 2``.  A width of 0 gives 1024 on every axis that takes part."""
+    g = ghost_fractions(box, width, dimensions)
+    counts = []
+    for a in range(3):
+        if a == 2 and int(dimensions) == 2:
+            counts.append(1)
+        elif g[a] > 0.0:
+            counts.append(int(min(max(numpy.floor(1.0 / g[a]), 1.0), float(_ORDER_MAX_AXIS_CELLS))))
+        else:
+            counts.append(_ORDER_MAX_AXIS_CELLS)
+    return tuple(counts)
+
+
 _WHERE_MAX_TERMS = 4
 _WHERE_SET_BITS = 64
 
@@ -1579,7 +1658,8 @@ class HOOMDTrajectory(object):
             self._initial_frame = snap
         return snap
 
-    def read_frame_device(self, idx, part=None, scalar4=False, defaults=True, domain=None, where=None, ghost=None):
+    def read_frame_device(self, idx, part=None, scalar4=False, defaults=True, domain=None, where=None, ghost=None,
+                          cell_order=None):
         """Read frame ``idx`` with the per-particle arrays of THIS rank's partition in GPU memory.
 
         Restart path (BASELINE config 5): each rank reads rows ``[row0, row0 + n)`` of every
@@ -1615,6 +1695,17 @@ class HOOMDTrajectory(object):
                 position so that it lies next to the cell (`halo_rows` gives the formula; positions are returned as
                 stored).  Needs ``domain``; not together with ``part`` or ``where`` -- a ghost layer around a particle
                 group is not provided.
+            cell_order: with ``domain`` and / or ``where`` (and with ``ghost``), a tuple ``(cx, cy, cz)``: the selected row
+                list is sorted by the cell of a uniform grid over the box its particles lie in -- on the GPU, between the
+                selection and the gather, exactly as `cell_order` defines it (`cell_grid_for` gives the counts for an
+                interaction range) --, and ``frame.tag``, every per-particle array, ``pos4`` / ``vel4`` follow that
+                order: the particles of one cell are neighbours in memory, in ascending file-row order.  ``frame.cell``
+                holds the sorted cell ids (int32, device; `cell_ids`), ``frame.cell_grid`` the counts.  With ``ghost``
+                the owned and the ghost run are sorted separately: ``frame.n_owned`` is unchanged, the ghost run's ids
+                ascend on their own and ``frame.ghost_shift`` is permuted with its ghosts.  A position that is stored
+                nowhere puts every row at the origin: the order is unchanged and all rows share one id.  The other
+                chunks are gathered through rows that are no longer ascending.  Not together with ``part``, and not
+                without a selection: ValueError.
 
         Returns:
             `Frame` whose ``particles.N`` is this rank's count, ``particles.N_global`` the total.  The per-particle
@@ -1627,6 +1718,10 @@ class HOOMDTrajectory(object):
             raise IndexError()
         if ghost is not None and (domain is None or part is not None or where is not None):
             raise ValueError("ghost needs domain and goes with neither part nor where")
+        if cell_order is not None:
+            if part is not None or (domain is None and where is None):
+                raise ValueError("cell_order needs domain or where and does not go with part")
+            cell_order = _order_cells(cell_order, 3)
         f = self.file
         snap = Frame()
         self._read_scalar_any(idx, 'configuration/step', snap.configuration, 'step')
@@ -1651,13 +1746,13 @@ class HOOMDTrajectory(object):
         if where is not None:
             if part is not None:
                 raise ValueError("part and where are mutually exclusive")
-            self._read_where_device(idx, snap, where, domain, scalar4, defaults, n_global)
+            self._read_where_device(idx, snap, where, domain, scalar4, defaults, n_global, cell_order)
             self._read_logs_device(idx, snap)
             return snap
         if domain is not None:
             if part is not None:
                 raise ValueError("part and domain are mutually exclusive")
-            self._read_domain_device(idx, snap, domain, scalar4, defaults, n_global, ghost)
+            self._read_domain_device(idx, snap, domain, scalar4, defaults, n_global, ghost, cell_order)
             self._read_logs_device(idx, snap)
             return snap
         if part is None:
@@ -1899,7 +1994,7 @@ class HOOMDTrajectory(object):
             if f.chunk_exists(idx, state):
                 snap.state[state[6:]] = f.read_chunk(idx, state)
 
-    def _read_domain_device(self, idx, snap, domain, scalar4, defaults, n_global, ghost=None):
+    def _read_domain_device(self, idx, snap, domain, scalar4, defaults, n_global, ghost=None, cell_order=None):
         """`read_frame_device(domain=...)`: select the domain's rows from the effective position chunk, then gather every
         per-particle array through them.  One `wait_read` per group of chunks that share destination rows, so the HBM
         staging holds one or two chunks at a time, never the frame; the position chunk the selection staged serves the
@@ -1930,9 +2025,31 @@ class HOOMDTrajectory(object):
             count = n_global if len(domain_rows(numpy.zeros((1, 3), numpy.float32), box, domain, dims)) else 0
             rows = fl._device_from_host(numpy.arange(count, dtype=numpy.int32), f.pipeline_device())
         snap.domain = domain
+        if cell_order is not None:
+            self._order_rows_device(snap, rows, count, cell_order, f_pos, snap.n_owned if ghost is not None else None)
         # group 1: position (the staged rows of the selection) and, with scalar4, (x, y, z, typeid bits)
         self._gather_rows_device(idx, snap, rows, count, scalar4, defaults, n_global,
                                  ('position', 'pos4') if scalar4 else ('position',))
+
+    def _order_rows_device(self, snap, rows, count, cells, f_pos, n_owned=None):
+        """``read_frame_device(cell_order=...)``: sort the selection's row list (device, ``count`` entries) by cell in
+        place, between the selection and the gather -- `pgsd.fl.PGSDFile.order_rows_by_cell_device` over the position
+        chunk of frame ``f_pos``, which a selection by domain has left staged (a selection by ``where`` alone has not:
+        the chunk is staged here and serves the position gather).  With ``n_owned`` the ghost run is sorted on its own
+        and ``snap.ghost_shift`` follows it.  ``f_pos`` None: the position is stored nowhere, every row sits at the
+        origin in one cell and the order stays."""
+        f = self.file
+        dims = int(snap.configuration.dimensions)
+        box = snap.configuration.box
+        cells = _order_cells(cells, dims)
+        snap.cell_grid = cells
+        if f_pos is not None:
+            snap.cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, cells, rows, n=count, n_owned=n_owned,
+                                                    shift=snap.ghost_shift if n_owned is not None else None,
+                                                    dimensions=dims)
+        else:
+            one = cell_ids(numpy.zeros((1, 3), numpy.float32), box, cells, dims).astype(numpy.int32)
+            snap.cell = fl._device_rows((count,), numpy.int32, f.pipeline_device(), one)
 
     def _gather_rows_device(self, idx, snap, rows, count, scalar4, defaults, n_global, staged):
         """The gather half of a domain or group read: every per-particle array of frame ``idx`` through the row list
@@ -1964,7 +2081,7 @@ class HOOMDTrajectory(object):
         groups += [(name,) for name in _PARTICLE_FIELDS if name not in staged]
         self._read_particles_device(idx, snap, count, n_global, defaults, gather, groups)
 
-    def _read_where_device(self, idx, snap, where, domain, scalar4, defaults, n_global):
+    def _read_where_device(self, idx, snap, where, domain, scalar4, defaults, n_global, cell_order=None):
         """`read_frame_device(where=...)`: select the rows that satisfy `where_rows` (and lie in ``domain``, if given)
         on the GPU from the effective chunks of the terms' attributes, then gather every per-particle array through
         them.  A term whose attribute the file stores nowhere is decided on the host against the one default row."""
@@ -2007,6 +2124,11 @@ class HOOMDTrajectory(object):
         snap.where = where
         if domain is not None:
             snap.domain = domain
+        if cell_order is not None:
+            f_pos = self._effective_frame(idx, 'particles/position', n_global)
+            self._order_rows_device(snap, rows, count, cell_order, f_pos)
+            if f_pos is not None and count > 0 and 'position' not in staged:
+                staged[:0] = ['position', 'pos4'] if scalar4 else ['position']      # (staged by the ordering)
         self._gather_rows_device(idx, snap, rows, count, scalar4, defaults, n_global, tuple(staged))
 
     def _census_frame(self, idx):

@@ -219,6 +219,9 @@ cdef extern from "pgsd_private.h" nogil:
     int pgsd_domain_counts_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
                                   uint32_t dimensions, const uint32_t* n, const double* interior_bounds,
                                   uint64_t* out_counts, uint64_t* out_nowhere)
+    int pgsd_order_rows_by_cell_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
+                                       uint32_t dimensions, const uint32_t* cells, uint32_t* rows, uint64_t n,
+                                       uint64_t n_owned, int32_t* shift, int32_t* out_cell)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                               const pgsd_field_dst* dst)
     cdef struct pgsd_row_plan:
