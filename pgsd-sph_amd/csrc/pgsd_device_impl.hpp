@@ -176,6 +176,7 @@ class DevicePipeline
         const uint32_t* rows;            // indexed read: N destination rows gathered from rows[] of the src_N staged ones
         uint64_t src_N;
         bool stage_only;                 // staged for a selection, which waits for the pieces itself: no unpack
+        uint64_t seq = 0;                // submission number: the order of the unpacks, whichever pread finishes first
         };
     struct Staged
         {
@@ -238,6 +239,7 @@ class DevicePipeline
     void read_piece(std::shared_ptr<ReadReq> req, char* dst, size_t n, std::shared_ptr<std::vector<ReadSpan>> parts);
     void read_done();
     void launch_pending_unpacks();
+    void fill_across_launches(std::vector<std::shared_ptr<ReadReq>>& pending);
     const void* kept_chunk(long long file_offset, size_t bytes) const;
     int stage_chunks(const ChunkRange* ranges, size_t n, uint64_t N, const void** src);
 
@@ -291,6 +293,7 @@ class DevicePipeline
     // read side
     ReadEngine* m_reader = nullptr;          // shared reader threads + pinned ring of this device
     size_t m_reads_outstanding = 0;          // m_mutex; counted per piece
+    uint64_t m_read_seq = 0;                 // ReadReq::seq of the next submission
     std::vector<std::shared_ptr<ReadReq>> m_unpack_pending; // m_copy_mutex
     std::atomic<uint64_t> m_pread_bytes {0}; // file bytes pread / bytes copied host-to-device (read_counters)
     std::atomic<uint64_t> m_h2d_bytes {0};

@@ -3,6 +3,7 @@
 // sparse (planned) reads, indexed reads, domain and group selection on top of the same staging.
 #include "pgsd_device_impl.hpp"
 
+#include <algorithm>
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
@@ -119,9 +120,66 @@ std::shared_ptr<DevicePipeline::ReadReq> DevicePipeline::make_read_req(const pgs
     return req;
     }
 
+// A destination array fed by requests of MORE THAN ONE launch (their keys differ), one of which asks for a fill: every
+// launch computes its fill from its own chunks, so the one with the fill would store the fill element over the columns
+// another launch feeds (whole rows, in the row-per-lane kernel).  Those arrays get ONE fill pass here, ahead of all
+// their launches, over the columns none of the pending requests covers and over the largest row count among them; their
+// jobs lose fill_rest.  A wait whose arrays each belong to one launch -- every frame read of pgsd.hoomd -- launches
+// nothing here and leaves its jobs alone.
+void DevicePipeline::fill_across_launches(std::vector<std::shared_ptr<ReadReq>>& pending)
+    {
+    const auto same_launch = [](const ReadReq& a, const ReadReq& b)
+    { return a.N == b.N && a.rows == b.rows && a.src_N == b.src_N; };
+    std::vector<bool> seen(pending.size(), false);
+    bool ordered = false;
+    for (size_t i = 0; i < pending.size() && !failed(); i++)
+        {
+        if (seen[i])
+            continue;
+        const pgsd_field_dst& d0 = pending[i]->job.dst;
+        const ReadReq* want = nullptr;
+        bool several = false, plain = true;
+        uint32_t covered = 0;
+        uint64_t rows_max = 0;
+        for (size_t k = i; k < pending.size(); k++)
+            {
+            const ReadReq& r = *pending[k];
+            if (r.job.dst.dst != d0.dst)
+                continue;
+            seen[k] = true;
+            several = several || !same_launch(r, *pending[i]);
+            // (one array seen through different shapes, or scattered: left to the launches, as before)
+            plain = plain && r.job.dst.order == nullptr && r.job.dst.dst_stride == d0.dst_stride
+                    && r.job.dst.dst_type == d0.dst_type && d0.dst_stride <= 32;
+            for (uint32_t c = 0; c < r.job.M && r.job.dst.dst_col0 + c < 32; c++)
+                covered |= 1u << (r.job.dst.dst_col0 + c);
+            rows_max = std::max(rows_max, r.N);
+            if (r.job.dst.fill_rest && !want)
+                want = &r;
+            }
+        if (!several || !plain || !want)
+            continue;
+        std::string err;
+        if (!ordered && order_after_source() != PGSD_SUCCESS) // (the destinations are the caller's: see below)
+            return;
+        ordered = true;
+        // the rows the fill's own list refuses stay as they are, like in its launch
+        if (launch_fill_rest(want->job, covered, rows_max, m_res.pack_stream, &err, want->rows, want->src_N, want->N)
+            != PGSD_SUCCESS)
+            {
+            fail(err);
+            return;
+            }
+        for (size_t k = i; k < pending.size(); k++)
+            if (pending[k]->job.dst.dst == d0.dst)
+                pending[k]->job.dst.fill_rest = 0;
+        }
+    }
+
 // The request's bytes are staged (or its copies enqueued, all_copied behind them).  The unpack itself is deferred to
 // wait_read(): the chunks of a frame then go through ONE launch in which chunks restoring the same array are assembled
-// into whole rows.
+// into whole rows.  Reader threads come here in the order their preads finish; launch_pending_unpacks() puts the requests
+// back into the order of their submission (ReadReq::seq).
 void DevicePipeline::defer_unpack(const std::shared_ptr<ReadReq>& req)
     {
     if (req->stage_only)
@@ -188,6 +246,7 @@ int DevicePipeline::read_submit_spans(const ReadSpan* spans, size_t n_spans, siz
             return PGSD_SUCCESS; // reported by pgsd_device_wait_read, like the threaded path
             }
         auto req = make_read_req(job, N, rows, src_N, stage_only, 0);
+        req->seq = m_read_seq++;
         if (out)
             *out = req;
         defer_unpack(req);
@@ -210,6 +269,7 @@ int DevicePipeline::read_submit_spans(const ReadSpan* spans, size_t n_spans, siz
     // the slab, and goes to HBM in one copy (a piece per run cost 17 us each; 1 000 runs of 48 KB took as long as two
     // thirds of the whole chunk).
     auto req = make_read_req(job, N, rows, src_N, stage_only, (bytes + piece - 1) / piece);
+    req->seq = m_read_seq++;
     if (out)
         *out = req;
     if (req->pieces_left == 0)
@@ -290,7 +350,9 @@ int DevicePipeline::read_rows_submit(long long file_offset, size_t bytes, pgsd_u
     if (rc != PGSD_SUCCESS)
         return rc;
     job.src = kept;
-    defer_unpack(make_read_req(job, n, rows, src_N, false, 0)); // (the selection synchronised the copies)
+    auto req = make_read_req(job, n, rows, src_N, false, 0); // (the selection synchronised the copies)
+    req->seq = m_read_seq++;
+    defer_unpack(req);
     return PGSD_SUCCESS;
     }
 
@@ -512,6 +574,11 @@ void DevicePipeline::launch_pending_unpacks()
         std::lock_guard<std::mutex> g(m_copy_mutex);
         pending.swap(m_unpack_pending);
         }
+    // in the order the caller submitted them: "the later chunk wins" where two chunks write the same column, whichever
+    // pread finished first; the grouping below is stable, so the order holds within every launch
+    std::stable_sort(pending.begin(), pending.end(),
+                     [](const std::shared_ptr<ReadReq>& a, const std::shared_ptr<ReadReq>& b) { return a->seq < b->seq; });
+    fill_across_launches(pending);
     while (!pending.empty() && !failed())
         {
         const uint64_t N = pending.front()->N;

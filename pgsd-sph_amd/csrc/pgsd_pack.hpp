@@ -128,6 +128,10 @@ struct FillArgs
     uint64_t N;
     uint64_t bits;
     uint32_t stride, dsz, colmask, pad;
+    // indexed read: row k < rows_n whose entry rows[k] lies outside the chunk (>= src_N) is left alone, as the gathers
+    // leave it (nullptr: every row is filled)
+    const uint32_t* rows;
+    uint64_t src_N, rows_n;
     };
 
 struct PackGenericArgs
@@ -229,6 +233,12 @@ struct GatherArgs
 // chunk, whose own height is src_N; an entry >= src_N writes nothing and sets the word *bad (device-visible) to 1.
 int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipStream_t stream, std::string* err,
                   const uint32_t* rows = nullptr, uint64_t src_N = 0, uint32_t* bad = nullptr);
+
+// A fill pass of its own, for a destination array whose chunks are spread over several launches (each of which sees its
+// own chunks only): the columns of rows [0, N) of `want`'s destination that are not in `covered` (bit c = column c) take
+// want's fill element.  With `rows`: the rows k < rows_n whose entry is >= src_N are left alone.
+int launch_fill_rest(const pgsd_unpack_job& want, uint32_t covered, uint64_t N, hipStream_t stream, std::string* err,
+                     const uint32_t* rows = nullptr, uint64_t src_N = 0, uint64_t rows_n = 0);
 
 // count -> one-block scan -> scatter of the rows inside the domain into out_rows (device, room for N), ascending;
 // synchronises `stream` and leaves the count in *out_count (host)

@@ -448,13 +448,16 @@ __global__ __launch_bounds__(256) void gather_elems_kernel(const GatherArgs a)
 // ------------------------------------------------------------------ fill of untouched columns (generic paths)
 // pgsd_field_dst.fill_rest where the launch does not assemble whole rows (scatter index, narrow or wide
 // elements, more than two chunks per array): the columns in colmask of every destination row receive the fill
-// element before the chunks' kernels run.  Element per lane: a fallback, not a hot path.
+// element before the chunks' kernels run.  Element per lane: a fallback, not a hot path.  An indexed read fills what its
+// gathers write: the row of an entry outside the chunk keeps what it holds, as in the row-per-lane kernel.
 __global__ __launch_bounds__(256) void fill_cols_kernel(const FillArgs a)
     {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const uint64_t row = t / a.stride;
     const uint32_t col = (uint32_t)(t % a.stride);
     if (row >= a.N || col >= 32 || !((a.colmask >> col) & 1u))
+        return;
+    if (a.rows != nullptr && row < a.rows_n && (uint64_t)a.rows[row] >= a.src_N)
         return;
     const uint64_t r = a.order ? (uint64_t)a.order[row] : row;
     store_elem((char*)a.dst + (r * a.stride + col) * a.dsz, a.bits, a.dsz);
@@ -639,9 +642,23 @@ static bool enqueue_unrows(std::vector<UnpackJob>& all, uint64_t N, const uint32
     return true;
     }
 
+// one fill pass: the columns of rows [0, N) of a destination array that are not in `covered`
+static void enqueue_fill(void* dst, const uint32_t* order, uint64_t N, uint64_t bits, uint32_t stride, uint32_t dsz,
+                         uint32_t covered, const uint32_t* rows, uint64_t src_N, uint64_t rows_n, hipStream_t stream)
+    {
+    if (stride == 0 || stride > 32)
+        return;
+    const uint32_t colmask = ~covered & (stride >= 32 ? 0xffffffffu : ((1u << stride) - 1u));
+    const FillArgs fa = {dst, order, N, bits, stride, dsz, colmask, 0, rows, src_N, rows_n};
+    const uint64_t lanes = N * (uint64_t)fa.stride;
+    if (fa.colmask && lanes)
+        hipLaunchKernelGGL(fill_cols_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, fa);
+    }
+
 // 2. The fills the remaining (tiled / generic) chunks asked for: one pass per destination array over the columns none of
 //    ITS chunks writes, ahead of the chunks on the stream.
-static void enqueue_fills(const std::vector<UnpackJob>& all, uint64_t N, hipStream_t stream)
+static void enqueue_fills(const std::vector<UnpackJob>& all, uint64_t N, const uint32_t* rows, uint64_t src_N,
+                          hipStream_t stream)
     {
     for_each_dst_run(all, [&](size_t i, size_t e) {
         uint32_t covered = 0;
@@ -653,13 +670,9 @@ static void enqueue_fills(const std::vector<UnpackJob>& all, uint64_t N, hipStre
             if (all[k].fill_rest && !want)
                 want = &all[k];
             }
-        if (!want || want->dst_stride > 32)
-            return;
-        const uint32_t colmask = ~covered & (want->dst_stride >= 32 ? 0xffffffffu : ((1u << want->dst_stride) - 1u));
-        const FillArgs fa = {want->dst, want->order, N, want->fill_bits, want->dst_stride, want->dsz, colmask, 0};
-        const uint64_t lanes = N * (uint64_t)fa.stride;
-        if (fa.colmask)
-            hipLaunchKernelGGL(fill_cols_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, fa);
+        if (want)
+            enqueue_fill(want->dst, want->order, N, want->fill_bits, want->dst_stride, want->dsz, covered, rows, src_N, N,
+                         stream);
     });
     }
 
@@ -815,7 +828,7 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
     // stream order: the row-per-lane launches, the fills, then the gathers of an indexed read or the tiled batches
     if (N < (1ull << 31) && !tuning().unpack_tiles && !enqueue_unrows(all, N, rows, src_N, bad, stream))
         return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "unpack: no row-per-lane kernel of the tuned shape");
-    enqueue_fills(all, N, stream);
+    enqueue_fills(all, N, rows, src_N, stream);
     if (rows)
         enqueue_gathers(all, N, rows, src_N, bad, stream);
     else
@@ -823,6 +836,22 @@ int launch_unpack(uint32_t n_jobs, const pgsd_unpack_job* jobs, uint64_t N, hipS
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return launch_fail(err, PGSD_ERROR_DEVICE, std::string("unpack kernel launch failed: ") + hipGetErrorString(e));
+    return PGSD_SUCCESS;
+    }
+
+int launch_fill_rest(const pgsd_unpack_job& want, uint32_t covered, uint64_t N, hipStream_t stream, std::string* err,
+                     const uint32_t* rows, uint64_t src_N, uint64_t rows_n)
+    {
+    (void)hipGetLastError();
+    const uint32_t dsz = (uint32_t)sizeof_type(want.dst.dst_type);
+    if (!want.dst.dst || !dsz || want.dst.dst_stride == 0 || want.dst.dst_stride > 32
+        || (((uintptr_t)want.dst.dst) & (dsz - 1)) != 0)
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "invalid fill (type, stride, alignment or pointer)");
+    enqueue_fill(want.dst.dst, want.dst.order, N, want.dst.fill_bits, want.dst.dst_stride, dsz, covered, rows, src_N, rows_n,
+                 stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return launch_fail(err, PGSD_ERROR_DEVICE, std::string("fill kernel launch failed: ") + hipGetErrorString(e));
     return PGSD_SUCCESS;
     }
     } // namespace pgsd_amd

@@ -1868,12 +1868,14 @@ cdef class PGSDFile:
             wait (bool): block until the data is in ``out`` (else call :meth:`wait_read`).
             fill: value for the columns of ``out``'s rows that no chunk read before the same :meth:`wait_read`
                 writes (``pgsd_field_dst.fill_rest``): velocity into a ``Scalar4`` array with ``fill=1.0`` gives
-                ``(vx, vy, vz, 1.0)`` rows, stored whole.  ``None``: those columns keep what they hold.
+                ``(vx, vy, vz, 1.0)`` rows, stored whole.  ``None``: those columns keep what they hold.  Where
+                several reads before one :meth:`wait_read` write the same column, the one submitted last wins.
             rows: an indexed read -- a :class:`RowPlan` (:meth:`plan_rows`: only the file blocks its rows touch are
-                read while they are few, see there), or ascending int32 row indices in GPU memory (e.g. from :func:`select_rows` or
-                :meth:`select_domain_device`); row ``k`` of ``out`` takes chunk row ``rows[k]``.  ``N`` defaults to
-                ``len(rows)``, ``offset`` must be 0 and ``order`` ``None``.  The whole chunk is staged and gathered
-                at :meth:`wait_read`, which raises if an entry lies outside the chunk.
+                read while they are few, see there), or 32-bit row indices in GPU memory, in any order, repeats
+                allowed (e.g. from :func:`select_rows` or :meth:`select_domain_device`); row ``k`` of ``out`` takes
+                chunk row ``rows[k]``.  ``N`` defaults to ``len(rows)``, ``offset`` must be 0 and ``order`` ``None``.
+                The whole chunk is staged and gathered at :meth:`wait_read`, which raises if an entry lies outside
+                the chunk; nothing is written to row ``k`` of ``out`` for such an entry, the ``fill`` included.
 
         Returns:
             the destination tensor.
