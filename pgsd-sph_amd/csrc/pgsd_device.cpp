@@ -701,6 +701,16 @@ int device_pipeline_order_rows(DevicePipeline* p, long long file_offset, size_t 
     return rc;
     }
 
+int device_pipeline_chunk_stats(DevicePipeline* p, long long file_offset, size_t bytes, const StatsArgs& s,
+                                uint64_t* out_counts, double* out_values, std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->chunk_stats(file_offset, bytes, s, out_counts, out_values, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
 void device_pipeline_set_source_stream(DevicePipeline* p, void* stream)
     {
     p->set_source_stream(stream);

@@ -147,6 +147,8 @@ class DevicePipeline
     int domain_counts(long long file_offset, size_t bytes, CellArgs c, uint64_t* out_counts, uint64_t* out_nowhere);
     int order_rows(long long file_offset, size_t bytes, OrderArgs o, uint32_t* rows, int32_t* shift, int32_t* out_cell,
                    std::string* why);
+    int chunk_stats(long long file_offset, size_t bytes, StatsArgs s, uint64_t* out_counts, double* out_values,
+                    std::string* why);
     int wait_read();
 
     // ---- accessors ----

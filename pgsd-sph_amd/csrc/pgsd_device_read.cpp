@@ -537,6 +537,28 @@ int DevicePipeline::order_rows(long long file_offset, size_t bytes, OrderArgs o,
     return rc;
     }
 
+// Chunk statistics: stage the chunk -- stage_chunks looks in the kept list first, so a chunk that a selection, a census,
+// an ordering or an earlier statistics call staged is not read again --, the tile and the final kernel on the pack stream,
+// one synchronisation.  The row list is the caller's, so what its stream still does with it comes first.
+int DevicePipeline::chunk_stats(long long file_offset, size_t bytes, StatsArgs s, uint64_t* out_counts, double* out_values,
+                                std::string* why)
+    {
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    const ChunkRange range = {file_offset, bytes};
+    rc = stage_chunks(&range, 1, s.N, &s.base);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = order_after_source();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = launch_chunk_stats(s, out_counts, out_values, m_res.pack_stream, why);
+    if (rc == PGSD_ERROR_DEVICE && why)
+        fail(*why);
+    return rc;
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

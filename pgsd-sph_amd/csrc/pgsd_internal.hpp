@@ -5,6 +5,7 @@
 #include "pgsd.h"
 #include "pgsd_private.h"
 
+#include <cmath>
 #include <cstdint>
 #include <sched.h>
 #include <sys/uio.h>
@@ -266,6 +267,52 @@ struct OrderArgs
 // >= o.d.N refuses the call with nothing written.  The staged rows stay until the next wait_read.
 int device_pipeline_order_rows(DevicePipeline*, long long file_offset, size_t bytes, const OrderArgs& o, uint32_t* rows,
                                int32_t* shift, int32_t* out_cell, std::string* err);
+// Chunk statistics (pgsd.hoomd.column_stats is the definition): per column of a staged chunk of N x M float32, float64,
+// int32 or uint32 elements -- of all its rows, or of the n entries of a row list in list order -- the count, the NaN and
+// the infinite entries, minimum, maximum and the sum of the finite entries in the definition's order; with norm2 (float
+// chunks of three columns) one more column, (x*x + y*y) + z*z in float64.
+struct StatsArgs
+    {
+    const void* base;     // the staged chunk
+    uint64_t N;           // its rows
+    const uint32_t* rows; // device, or null: every row
+    uint64_t n;           // entries of the list
+    uint32_t type, M;     // enum pgsd_type, columns
+    uint32_t norm2;
+    uint32_t pad;
+    };
+// is (type, M, norm2) something the statistics kernels take?  `why` receives the refusal
+inline bool chunk_stats_supported(uint32_t type, uint32_t M, uint32_t norm2, std::string* why)
+    {
+    const bool real = type == PGSD_TYPE_FLOAT || type == PGSD_TYPE_DOUBLE;
+    const char* msg = nullptr;
+    if (!real && type != PGSD_TYPE_INT32 && type != PGSD_TYPE_UINT32)
+        msg = "the chunk holds float32, float64, int32 or uint32 elements";
+    else if (M == 0 || M > 4)
+        msg = "the chunk has 1 to 4 columns";
+    else if (norm2 && (!real || M != 3))
+        msg = "norm2 needs a float chunk of three columns";
+    if (msg && why)
+        *why = msg;
+    return msg == nullptr;
+    }
+// the statistics of no entry, for C columns
+inline void chunk_stats_of_nothing(uint32_t C, uint64_t* out_counts, double* out_values)
+    {
+    for (uint32_t c = 0; c < C; c++)
+        {
+        out_counts[3 * c + 0] = out_counts[3 * c + 1] = out_counts[3 * c + 2] = 0;
+        out_values[3 * c + 0] = HUGE_VAL;
+        out_values[3 * c + 1] = -HUGE_VAL;
+        out_values[3 * c + 2] = 0.0;
+        }
+    }
+// stage the chunk at `file_offset` (s.N rows; s.base is filled in) -- or take it from what an earlier selection, census
+// or statistics call left staged --, reduce on the GPU, copy the results to the host: out_counts C x 3 (count, NaN,
+// infinite), out_values C x 3 (min, max, sum), C = s.M + (s.norm2 ? 1 : 0), written on success only; synchronous.  An
+// entry >= s.N refuses the call.  The staged rows stay until the next wait_read.
+int device_pipeline_chunk_stats(DevicePipeline*, long long file_offset, size_t bytes, const StatsArgs& s, uint64_t* out_counts,
+                                double* out_values, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

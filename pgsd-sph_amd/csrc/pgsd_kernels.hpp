@@ -1,6 +1,7 @@
 // pgsd_kernels.hpp -- what the kernel translation units of libpgsd_amd.so share: pgsd_pack.hip (pack: LDS-tiled,
-// row-per-lane, copy and generic kernels + their planners), pgsd_unpack.hip (the read path's inverse kernels + planners)
-// and pgsd_select.hip (chunk comparison, stream compaction, library-owned device memory).  Device helpers are header-only
+// row-per-lane, copy and generic kernels + their planners), pgsd_unpack.hip (the read path's inverse kernels + planners),
+// pgsd_select.hip (chunk comparison, stream compaction, census, cell order, library-owned device memory) and
+// pgsd_stats.hip (per-column statistics of a staged chunk).  Device helpers are header-only
 // and seen by the HIP compiler alone; the host helpers, the tuning variables and the tables of instantiated launch
 // shapes are shared with pgsd_kernels.cpp (host compiler), which defines everything here that is not a kernel.
 #ifndef PGSD_KERNELS_HPP
@@ -34,6 +35,13 @@
 namespace pgsd_amd
     {
 #define PACK_THREADS 256
+
+// The row layout of the selection, census and statistics kernels (pgsd_select.hip, pgsd_stats.hip): a workgroup of
+// SEL_THREADS lanes owns a tile of SEL_PER_BLOCK consecutive rows (or list entries), lane t the rows base + k *
+// SEL_THREADS + t for k < SEL_PER_THREAD.
+#define SEL_THREADS 256
+#define SEL_PER_THREAD 16
+#define SEL_PER_BLOCK (SEL_THREADS * SEL_PER_THREAD)
 
 #ifdef __HIP__
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

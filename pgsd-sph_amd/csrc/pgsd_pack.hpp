@@ -266,6 +266,11 @@ int launch_cell_counts(const CellArgs& c, uint64_t* out_counts, uint64_t* out_no
 int launch_order_rows(const OrderArgs& o, uint32_t* rows, int32_t* shift, int32_t* out_cell, hipStream_t stream,
                       std::string* err);
 
+// chunk statistics (StatsArgs, base filled in): one pass of a workgroup per tile of 4096 entries, one workgroup over the
+// tiles' partial results; out_counts / out_values (host, C x 3 each) are written on success only; synchronises `stream`.
+// PGSD_ERROR_INVALID_ARGUMENT if an entry of the row list is >= s.N
+int launch_chunk_stats(const StatsArgs& s, uint64_t* out_counts, double* out_values, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);

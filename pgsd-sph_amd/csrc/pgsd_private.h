@@ -24,6 +24,10 @@
  *                     domain_counts_device, behind pgsd.hoomd's axis_histograms_device, domain_counts_device and
  *                     balanced_grid_device: per-axis histograms of the fractions and per-cell counts of a decomposition,
  *                     counted on the GPU from one staged position chunk, so that a restart can choose balanced splits)
+ *                     pgsd_chunk_stats_device (pgsd.fl's chunk_stats_device, behind pgsd.hoomd's frame_stats_device:
+ *                     per column of a staged chunk, or of a selection's row list over it, the NaN and infinite entries,
+ *                     minimum, maximum and a sum in a fixed order, so that "did the run blow up, what is the largest
+ *                     speed, what is the density range" cost one pass over rows that are in HBM already)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -193,6 +197,30 @@ extern "C"
     int pgsd_order_rows_by_cell_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
                                        const float box[6], uint32_t dimensions, const uint32_t cells[3], uint32_t* rows,
                                        uint64_t n, uint64_t n_owned, int32_t* shift, int32_t* out_cell);
+
+    /* Chunk statistics (pgsd.hoomd.column_stats is the definition, and the results equal it exactly, the sums bit for
+       bit).  chunk: N x M elements of float32, float64, int32 or uint32, 1 <= M <= 4, N < 2^32.  rows (device memory, n
+       entries, any order, repeats allowed) or NULL: the statistics are those of rows[0 .. n) in list order, or of all
+       chunk->N rows (n is then not looked at).  Every element is converted to float64 first, which is exact.  With
+       C = M + (with_norm2 ? 1 : 0) columns -- with_norm2 appends the column (x*x + y*y) + z*z in float64, no contraction,
+       to a float chunk of three columns -- the results are HOST arrays:
+           out_counts[3 c + 0 .. 2]   the entries, those that are NaN, those that are +-infinity
+           out_values[3 c + 0 .. 2]   minimum and maximum over the entries that are no NaN (+inf / -inf when there is
+                                      none; the sign of a zero is not specified) and the sum of the finite entries
+       The sum's order is fixed: entry k belongs to tile k / 4096, lane k % 256, step (k % 4096) / 256; a lane adds its 16
+       entries in step order to +0.0 (an entry that is not finite or lies past the end adds +0.0); the 256 lane sums are
+       combined by the block tree -- inside each run of 64 lanes p[i] += p[i + h] for h = 32, 16, 8, 4, 2, 1, then
+       (w0 + w1) + (w2 + w3) --; lane t of a last workgroup adds the sums of tiles t, t + 256, ... in that order to +0.0
+       and the block tree gives the result.  It depends on neither the grid nor the device.
+       The chunk is staged whole unless an earlier selection, census, ordering or statistics call of the same chunk left
+       it staged (then no file byte is read), the reduction runs on the handle's GPU and the call synchronises; the
+       staged rows are kept until the next pgsd_device_wait_read.  n == 0 (or chunk->N == 0 without a list) succeeds with
+       zero counts, +inf, -inf and 0.0 and launches nothing.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(): another element type; M == 0 or M > 4; with_norm2 on
+       an integer chunk or with M != 3; chunk->N >= 2^32 or n >= 2^32; an entry >= chunk->N.  out_counts and out_values
+       are written on success only. */
+    int pgsd_chunk_stats_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk, const uint32_t* rows,
+                                uint64_t n, uint32_t with_norm2, uint64_t* out_counts, double* out_values);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

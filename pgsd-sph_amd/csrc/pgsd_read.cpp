@@ -638,6 +638,74 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_chunk_stats_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk, const uint32_t* rows,
+                                       uint64_t n, uint32_t with_norm2, uint64_t* out_counts, double* out_values)
+    try
+    {
+    static const char* who = "pgsd_chunk_stats_device";
+    Impl* s = impl_of(handle);
+    if (!s || !chunk || !out_counts || !out_values)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    pgsd_index_entry c = *chunk; // a flush may move the index storage
+    std::string why;
+    if (!chunk_stats_supported(c.type, c.M, with_norm2, &why))
+        return refuse(why);
+    if (c.N >= (1ull << 32))
+        return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+    if (rows && n >= (1ull << 32))
+        return refuse("a row list holds fewer than 2^32 entries");
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    StatsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = c.N;
+    a.rows = rows;
+    a.n = rows ? n : c.N;
+    a.type = c.type;
+    a.M = c.M;
+    a.norm2 = with_norm2 ? 1u : 0u;
+    const uint32_t C = a.M + a.norm2;
+    if (a.n == 0)
+        {
+        chunk_stats_of_nothing(C, out_counts, out_values);
+        return PGSD_SUCCESS;
+        }
+    if (c.N == 0)
+        return refuse("an entry of the row list lies outside the chunk (nothing was computed)");
+    // (the outputs are written on success only: the launcher fills these and they are copied out then)
+    uint64_t counts[15];
+    double values[15];
+    std::string err;
+    rc = device_pipeline_chunk_stats(s->dev, foff, bytes, a, counts, values, &err);
+    if (rc == PGSD_ERROR_INVALID_ARGUMENT)
+        {
+        const std::string prefix = "chunk statistics: ";
+        if (err.compare(0, prefix.size(), prefix) == 0)
+            err.erase(0, prefix.size());
+        return refuse(err.empty() ? std::string("refused") : err);
+        }
+    if (rc != PGSD_SUCCESS)
+        {
+        set_last_error(err);
+        return rc;
+        }
+    std::copy(counts, counts + 3 * C, out_counts);
+    std::copy(values, values + 3 * C, out_values);
+    return PGSD_SUCCESS;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_terms, const struct pgsd_index_entry* term_chunks,
                                         const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
                                         const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],

@@ -213,10 +213,7 @@ int launch_compare(uint32_t n_jobs, const CompareJob* jobs, uint32_t gen, uint32
     }
 
 // ------------------------------------------------------------------ select (compaction)
-#define SEL_THREADS 256
-#define SEL_PER_THREAD 16
-#define SEL_PER_BLOCK (SEL_THREADS * SEL_PER_THREAD)
-
+// (SEL_THREADS, SEL_PER_THREAD, SEL_PER_BLOCK: pgsd_kernels.hpp -- pgsd_stats.hip shares the row layout)
 // number of non-zero flag bytes among the 16 this lane owns
 __device__ __forceinline__ uint32_t sel_load16(const uint8_t* flags, uint64_t base, uint64_t N, uint32_t* mask)
     {

@@ -4,7 +4,10 @@
            the file open as ``handle`` and, for the hoomd schema, the trajectory as ``traj``.
 ``info``   header, frame count and the chunks of one frame, printed and done (no prompt); ``--balance NX,NY,NZ``
            adds the split lists that balance the frame's particles over such a decomposition and the per-cell counts
-           of the equal and of the balanced grid (the host models of ``pgsd.hoomd``: no GPU).
+           of the equal and of the balanced grid (the host models of ``pgsd.hoomd``: no GPU); ``--stats`` adds per
+           field and column the count, the NaN and infinite entries, minimum, maximum and mean of one frame, and the
+           largest norm of three-column float fields (``--fields``, ``--types``); ``--stats --all-frames`` prints one
+           line per frame with the number of non-finite entries and the largest speed: the blow-up scan.
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -65,6 +68,48 @@ def _cmd_info(args):
                 print("  %-28s %-8s %s" % (name, data.dtype, 'x'.join(str(n) for n in data.shape)))
     if args.balance:
         _print_balance(args, frame)
+    if args.stats:
+        _print_stats(args, frame)
+
+
+def _print_stats(args, frame):
+    """``info --stats``: `pgsd.hoomd.frame_stats` of one frame, or of every frame in one line each, on the host."""
+    from . import hoomd
+    fields = [n for n in args.fields.split(',') if n] if args.fields else list(hoomd._STATS_FIELDS)
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        if args.all_frames:
+            print("non-finite entries and largest speed per frame (%s):" % ', '.join(fields))
+            for i in range(len(traj)):
+                snap = traj[i]
+                stats = hoomd.frame_stats(snap, fields, where=where)
+                bad = sum(int(st.nan[:_stats_columns(hoomd, name)].sum() + st.inf[:_stats_columns(hoomd, name)].sum())
+                          for name, st in stats.items())      # (the norm column is derived: its rows are counted already)
+                speed = hoomd.frame_stats(snap, ['velocity'], where=where)['velocity'].max[3]
+                print("  frame %-6d step %-10d non-finite %-8d max |velocity| %s"
+                      % (i, int(snap.configuration.step), bad, _norm_text(speed)))
+            return
+        stats = hoomd.frame_stats(traj[frame], fields, where=where)
+    print("statistics of frame %d%s:" % (frame, " (types %s)" % args.types if args.types else ""))
+    for name, st in stats.items():
+        M = _stats_columns(hoomd, name)
+        mean = st.mean
+        for c in range(M):
+            print("  %-12s %d  count %d  nan %d  inf %d  min %r  max %r  mean %r"
+                  % (name, c, st.count[c], st.nan[c], st.inf[c], float(st.min[c]), float(st.max[c]), float(mean[c])))
+        if M < len(st.count):
+            print("  %-12s max norm %s" % (name, _norm_text(st.max[M])))
+
+
+def _stats_columns(hoomd, name):
+    """The stored columns of a field: what `frame_stats` returns for it, without the norm column."""
+    return hoomd._PARTICLE_FIELDS[name][1]
+
+
+def _norm_text(norm2):
+    """The largest norm from the largest squared norm (``-inf``: no row took part)."""
+    import math
+    return 'n/a' if norm2 == -math.inf else repr(math.sqrt(norm2))
 
 
 def _print_balance(args, frame):
@@ -114,6 +159,14 @@ def main(argv=None):
     p.add_argument('--balance', type=str, default=None, metavar='NX,NY,NZ',
                    help="print the split lists that balance the frame over NX x NY x NZ cells, and the cell counts")
     p.add_argument('--bins', type=int, default=1024, help="histogram bins per axis for --balance (a power of two)")
+    p.add_argument('--stats', action='store_true',
+                   help="print count, nan, inf, min, max and mean per field and column of the frame")
+    p.add_argument('--fields', type=str, default=None, metavar='NAME[,NAME...]',
+                   help="the per-particle fields of --stats (default: position,velocity,density,pressure,energy)")
+    p.add_argument('--types', type=str, default=None, metavar='NAME[,NAME...]',
+                   help="--stats over the particles of these types only")
+    p.add_argument('--all-frames', action='store_true',
+                   help="with --stats: one line per frame with the non-finite entries and the largest speed")
     p.set_defaults(func=_cmd_info)
     p = sub.add_parser('vtu', help="convert the frames to VTK .vtu files")
     p.add_argument('file', type=str)

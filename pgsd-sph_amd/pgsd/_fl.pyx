@@ -1643,6 +1643,65 @@ cdef class PGSDFile:
         _raise_on_error(retval, self._name, err)
         return counts.astype(numpy.int64), int(nowhere)
 
+    def chunk_stats_device(self, frame, name, rows=None, n=None, norm2=False):
+        """Per-column statistics of a chunk, or of a row list over it, reduced on the GPU.
+
+        Args:
+            frame (int), name (str): the chunk: N x M float32, float64, int32 or uint32 elements, ``1 <= M <= 4``.
+            rows: ``None`` for all rows, or 32-bit row indices in GPU memory (e.g. :meth:`select_domain_device`'s), any
+                order, repeats allowed: the statistics are those of ``chunk[rows]`` in list order.
+            n (int): the number of entries of ``rows`` to take (default: all of them).
+            norm2 (bool): append the column ``(x*x + y*y) + z*z`` (float64) of a float chunk of three columns; its
+                ``max`` is the square of the largest speed.
+
+        Returns:
+            A :class:`pgsd.hoomd.FieldStats`: per column ``count``, ``nan``, ``inf`` (int64), ``min``, ``max``, ``sum``
+            (float64) and the property ``mean``.  Exactly :func:`pgsd.hoomd.column_stats`, the sum included: its order
+            is part of the definition.  The chunk is staged whole unless a selection, a census, an ordering or an earlier
+            statistics call of the same chunk left it staged; the staged rows are kept until the next :meth:`wait_read`.
+            An entry outside the chunk raises ValueError.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        cdef uintptr_t c_rows = 0
+        cdef uint32_t c_empty = 0
+        count = 0
+        if rows is not None:
+            p_rows, n_rows = _index_rows(rows)
+            count = n_rows if n is None else int(n)
+            if count >= (1 << 32):
+                raise ValueError("chunk_stats_device: a row list holds fewer than 2^32 entries")
+            if count < 0 or count > n_rows:
+                raise ValueError("chunk_stats_device: rows holds fewer entries than n")
+            c_rows = p_rows
+            if count == 0:
+                # an empty list is still a list -- its statistics are those of no entry, not of the whole chunk --, but
+                # may have no address: nothing of it is read
+                c_rows = <uintptr_t>&c_empty
+        elif n is not None:
+            raise ValueError("chunk_stats_device: n goes with rows")
+        columns = int(entry.M) + (1 if norm2 else 0)
+        counts = numpy.zeros((max(columns, 1) if columns <= 5 else 1, 3), dtype=numpy.uint64)     # (the library refuses the rest)
+        values = numpy.zeros(counts.shape, dtype=numpy.float64)
+        if rows is not None and not self._explicit_stream:
+            self._sync_source_stream()      # the reduction is ordered behind this stream's use of `rows`
+        cdef uintptr_t c_counts = counts.ctypes.data, c_values = values.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_norm2 = 1 if norm2 else 0
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_chunk_stats_device(&self._handle, &entry, <const uint32_t*>c_rows, c_n, c_norm2,
+                                               <uint64_t*>c_counts, <double*>c_values)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("chunk_stats_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
+        _raise_on_error(retval, self._name, err)
+        counts = counts.astype(numpy.int64)
+        return _hoomd.FieldStats(counts[:, 0].copy(), counts[:, 1].copy(), counts[:, 2].copy(), values[:, 0].copy(),
+                                 values[:, 1].copy(), values[:, 2].copy())
+
     def select_halo_device(self, frame, name, box, domain, ghost, dimensions=3):
         """A domain plus the ghost layer its neighbours reach, selected on the GPU from one position chunk.
 

@@ -811,7 +811,7 @@ def where_rows(arrays, where, types=None):
         a = numpy.asarray(arrays[name])
         if a.shape[0] != N:
             raise ValueError("'%s' has %d rows, expected %d" % (name, a.shape[0], N))
-        a = a.reshape(N, -1)
+        a = a.reshape(N, a.shape[1] if a.ndim == 2 else 1)      # (not -1: a frame may hold no particle)
         if column >= a.shape[1]:
             raise ValueError("'%s' has %d column(s): no column %d" % (name, a.shape[1], column))
         if mask is not None and a.dtype.kind not in 'iu':
@@ -823,6 +823,199 @@ def where_rows(arrays, where, types=None):
 def _particle_arrays(particles):
     """The per-particle arrays a `ParticleData` holds, by name (`where_rows`'s ``arrays``)."""
     return dict((name, getattr(particles, name)) for name in _PARTICLE_FIELDS if getattr(particles, name, None) is not None)
+
+
+# ---- frame statistics: the definition the GPU reduction (`pgsd.fl.PGSDFile.chunk_stats_device`) equals exactly
+_STATS_LANES = 256          # the row layout of the selection kernels: a tile of 4096 entries, lane k % 256,
+_STATS_STEPS = 16           # step (k % 4096) / 256
+_STATS_TILE = _STATS_LANES * _STATS_STEPS
+_STATS_TYPES = (numpy.float32, numpy.float64, numpy.int32, numpy.uint32)
+_STATS_FIELDS = ('position', 'velocity', 'density', 'pressure', 'energy')
+
+
+class FieldStats(object):
+    """Per-column statistics of a per-particle array (`column_stats`): arrays of one entry per column.
+
+    Attributes:
+        count, nan, inf (int64): the entries, those that are NaN, those that are +-infinity.
+        min, max (float64): over the entries that are no NaN (infinities take part); ``+inf`` / ``-inf`` when there is
+            none.  The sign of a zero is not specified.
+        sum (float64): the sum of the finite entries in `column_stats`' order.
+        mean (property): ``sum / (count - nan - inf)``, NaN where no entry is finite.
+
+    With ``norm2`` the last column is the squared norm of the rows: ``max[-1]`` is the square of the largest speed.
+    """
+
+    __slots__ = ('count', 'nan', 'inf', 'min', 'max', 'sum')
+
+    def __init__(self, count, nan, inf, min, max, sum):
+        self.count = numpy.asarray(count, dtype=numpy.int64)
+        self.nan = numpy.asarray(nan, dtype=numpy.int64)
+        self.inf = numpy.asarray(inf, dtype=numpy.int64)
+        self.min = numpy.asarray(min, dtype=numpy.float64)
+        self.max = numpy.asarray(max, dtype=numpy.float64)
+        self.sum = numpy.asarray(sum, dtype=numpy.float64)
+
+    @property
+    def mean(self):
+        finite = self.count - self.nan - self.inf
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(finite > 0, self.sum / numpy.maximum(finite, 1), numpy.nan)
+
+    def __repr__(self):
+        return "FieldStats(count=%r, nan=%r, inf=%r, min=%r, max=%r, sum=%r)" % tuple(
+            getattr(self, name).tolist() for name in self.__slots__)
+
+
+def _block_tree(p):
+    """The block tree over the last axis (256 lane sums): inside each run of 64 lanes ``p[i] += p[i + h]`` for
+    ``h = 32 .. 1``, then ``(w0 + w1) + (w2 + w3)``."""
+    w = p.reshape(p.shape[:-1] + (_STATS_LANES // 64, 64))
+    for h in (32, 16, 8, 4, 2, 1):
+        w = w[..., :h] + w[..., h:2 * h]
+    w = w[..., 0]
+    return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+
+
+def _ordered_sum(v):
+    """The sum of the float64 values ``v`` (entries that do not count replaced by ``+0.0``) in `column_stats`' order."""
+    n = v.shape[0]
+    tiles = (n + _STATS_TILE - 1) // _STATS_TILE
+    a = numpy.zeros(tiles * _STATS_TILE, dtype=numpy.float64)
+    a[:n] = v
+    a = a.reshape(tiles, _STATS_STEPS, _STATS_LANES)
+    lane = numpy.zeros((tiles, _STATS_LANES), dtype=numpy.float64)
+    for step in range(_STATS_STEPS):
+        lane = lane + a[:, step, :]
+    tile_sums = _block_tree(lane)                               # one sum per tile
+    rounds = (tiles + _STATS_LANES - 1) // _STATS_LANES
+    b = numpy.zeros(rounds * _STATS_LANES, dtype=numpy.float64)
+    b[:tiles] = tile_sums
+    b = b.reshape(rounds, _STATS_LANES)
+    lane = numpy.zeros(_STATS_LANES, dtype=numpy.float64)
+    for r in range(rounds):
+        lane = lane + b[r]
+    return float(_block_tree(lane))
+
+
+def column_stats(values, rows=None, norm2=False):
+    """Per-column statistics of ``values``: the definition the GPU reduction (`pgsd.fl.PGSDFile.chunk_stats_device`,
+    `HOOMDTrajectory.frame_stats_device`) equals exactly, the sums bit for bit.
+
+    Args:
+        values: an ``N`` or ``N x M`` array of float32, float64, int32 or uint32, ``M <= 4``.
+        rows: ``None``, or row indices in any order, repeats allowed: the statistics of ``values[rows]`` in list order.
+        norm2 (bool): append one column (float arrays with ``M == 3`` only) whose per-row value is
+            ``(x*x + y*y) + z*z`` in float64, in exactly that association and without a fused multiply-add.  Its ``max``
+            is the square of the largest speed; a row with a NaN component counts in ``nan``, a row whose value is
+            infinite in ``inf``.
+
+    Every element is first converted to float64 (exact for all four types).  `FieldStats` says what is returned.  **The
+    order of the sum** is the row layout of the selection kernels: entry ``k`` (of the list, or row ``k``) belongs to
+    tile ``k // 4096``, lane ``k % 256``, step ``(k % 4096) // 256``.
+
+    1. A lane starts at ``+0.0`` and adds its 16 entries in step order; an entry that is not finite, or lies past the
+       end, is ``+0.0`` (the identity: a running sum that starts at ``+0.0`` is never ``-0.0``).
+    2. The 256 lane sums of a tile are combined by the block tree: inside each of the four waves (lanes ``64 w ..
+       64 w + 63``) ``p[i] += p[i + h]`` for ``h = 32, 16, 8, 4, 2, 1``, then ``(w0 + w1) + (w2 + w3)``.
+    3. The tile sums are combined the same way: lane ``t`` starts at ``+0.0`` and adds tiles ``t, t + 256, ...`` in
+       that order, then the block tree.
+
+    ValueError: another element type, more than two dimensions, ``M`` of 0 or above 4, ``norm2`` on integers or with
+    ``M != 3``, a row index outside ``[0, N)``.
+    """
+    values = numpy.asarray(values)
+    if values.dtype.type not in _STATS_TYPES:
+        raise ValueError("statistics take float32, float64, int32 or uint32 arrays: %s" % values.dtype)
+    if values.ndim not in (1, 2):
+        raise ValueError("statistics take an N or N x M array")
+    N = values.shape[0]
+    M = values.shape[1] if values.ndim == 2 else 1
+    if not 1 <= M <= 4:
+        raise ValueError("statistics take 1 to 4 columns: %d" % M)
+    if norm2 and (values.dtype.kind != 'f' or M != 3):
+        raise ValueError("norm2 needs a float array of three columns")
+    values = values.reshape(N, M)
+    if rows is not None:
+        rows = numpy.asarray(rows).reshape(-1)
+        if rows.size and rows.dtype.kind not in 'iu':
+            raise ValueError("rows holds integer row indices")
+        rows = rows.astype(numpy.int64)
+        if rows.size and (rows.min() < 0 or rows.max() >= N):
+            raise ValueError("an entry of the row list lies outside the array")
+        values = values[rows]
+    v = values.astype(numpy.float64)
+    if norm2:
+        with numpy.errstate(over='ignore', invalid='ignore'):
+            q = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+        v = numpy.concatenate([v, q.reshape(-1, 1)], axis=1)
+    n, C = v.shape
+    is_nan, is_inf = numpy.isnan(v), numpy.isinf(v)
+    lo, hi, total = numpy.empty(C), numpy.empty(C), numpy.empty(C)
+    for c in range(C):
+        kept = v[~is_nan[:, c], c]
+        lo[c] = kept.min(initial=numpy.inf)
+        hi[c] = kept.max(initial=-numpy.inf)
+        total[c] = _ordered_sum(numpy.where(is_nan[:, c] | is_inf[:, c], 0.0, v[:, c]))
+    return FieldStats(numpy.full(C, n), is_nan.sum(axis=0), is_inf.sum(axis=0), lo, hi, total)
+
+
+def _stats_norm2(dtype, M):
+    """Does a field of this element type and width get the norm column?"""
+    return numpy.dtype(dtype).kind == 'f' and M == 3
+
+
+def _stats_fields(fields):
+    """The field names of a statistics call, checked."""
+    names = [fields] if isinstance(fields, str) else list(fields)
+    for name in names:
+        if not isinstance(name, str) or name not in _PARTICLE_FIELDS:
+            raise ValueError("%r is not a per-particle attribute of ParticleData" % (name,))
+    return names
+
+
+def frame_stats(frame_or_arrays, fields=_STATS_FIELDS, where=None, types=None, domain=None, box=None, dimensions=3):
+    """`column_stats` of the per-particle arrays ``fields`` over a selection: the host twin of
+    `HOOMDTrajectory.frame_stats_device`, which equals it exactly.
+
+    Args:
+        frame_or_arrays: a `Frame` (``types``, ``box`` and ``dimensions`` default to its own) or a dict of attribute
+            name -> ``N (x M)`` host array.
+        fields: attribute names of `ParticleData`.
+        where (dict): a group predicate, as `where_rows` takes it.
+        domain (`Domain`): a cell, as `domain_rows` takes it, over ``arrays['position']`` and ``box``.
+
+    With ``where`` and ``domain`` the rows satisfy both; with neither the statistics are those of every row.  Float
+    fields of three columns get the ``norm2`` column.  Returns a dict from field name to `FieldStats`.
+
+    ValueError: what `where_rows`, `domain_rows` and `column_stats` refuse; a field the arrays do not hold; a domain
+    without box or position.
+    """
+    if hasattr(frame_or_arrays, 'particles'):
+        frame = frame_or_arrays
+        arrays = _particle_arrays(frame.particles)
+        types = frame.particles.types if types is None else types
+        box = frame.configuration.box if box is None else box
+        if frame.configuration.dimensions is not None:
+            dimensions = int(frame.configuration.dimensions)
+    else:
+        arrays = dict((k, v) for k, v in frame_or_arrays.items() if v is not None)
+    names = _stats_fields(fields)
+    rows = None
+    if where is not None:
+        rows = where_rows(arrays, where, types)
+    if domain is not None:
+        if box is None or 'position' not in arrays:
+            raise ValueError("a domain needs box and the 'position' array")
+        inside = domain_rows(arrays['position'], box, domain, dimensions)
+        rows = inside if rows is None else numpy.intersect1d(rows, inside)
+    out = OrderedDict()
+    for name in names:
+        if name not in arrays:
+            raise ValueError("arrays holds no '%s'" % name)
+        a = numpy.asarray(arrays[name])
+        out[name] = column_stats(a, rows, norm2=_stats_norm2(a.dtype, a.shape[1] if a.ndim == 2 else 1))
+    return out
 
 
 class Tracks(object):
@@ -2018,18 +2211,24 @@ class HOOMDTrajectory(object):
                 snap.ghost_shift = fl._device_rows((n_ghost, 3), numpy.int32, f.pipeline_device(),
                                                    shift[0] if n_ghost else numpy.zeros(3, numpy.int32))
             count = snap.n_owned + n_ghost
-        elif f_pos is not None:
-            rows, count = f.select_domain_device(f_pos, 'particles/position', box, domain, dims)
         else:
-            # no position anywhere: every particle sits at the origin, all of them or none are inside
-            count = n_global if len(domain_rows(numpy.zeros((1, 3), numpy.float32), box, domain, dims)) else 0
-            rows = fl._device_from_host(numpy.arange(count, dtype=numpy.int32), f.pipeline_device())
+            rows, count = self._domain_row_list(f_pos, box, dims, domain, n_global)
         snap.domain = domain
         if cell_order is not None:
             self._order_rows_device(snap, rows, count, cell_order, f_pos, snap.n_owned if ghost is not None else None)
         # group 1: position (the staged rows of the selection) and, with scalar4, (x, y, z, typeid bits)
         self._gather_rows_device(idx, snap, rows, count, scalar4, defaults, n_global,
                                  ('position', 'pos4') if scalar4 else ('position',))
+
+    def _domain_row_list(self, f_pos, box, dims, domain, n_global):
+        """The row list of a domain read without a ghost layer, ``(rows, count)`` in GPU memory: selected from the
+        position chunk of frame ``f_pos``, which stays staged.  Shared by `read_frame_device` and `frame_stats_device`."""
+        f = self.file
+        if f_pos is not None:
+            return f.select_domain_device(f_pos, 'particles/position', box, domain, dims)
+        # no position anywhere: every particle sits at the origin, all of them or none are inside
+        count = n_global if len(domain_rows(numpy.zeros((1, 3), numpy.float32), box, domain, dims)) else 0
+        return fl._device_from_host(numpy.arange(count, dtype=numpy.int32), f.pipeline_device()), count
 
     def _order_rows_device(self, snap, rows, count, cells, f_pos, n_owned=None):
         """``read_frame_device(cell_order=...)``: sort the selection's row list (device, ``count`` entries) by cell in
@@ -2085,12 +2284,26 @@ class HOOMDTrajectory(object):
         """`read_frame_device(where=...)`: select the rows that satisfy `where_rows` (and lie in ``domain``, if given)
         on the GPU from the effective chunks of the terms' attributes, then gather every per-particle array through
         them.  A term whose attribute the file stores nowhere is decided on the host against the one default row."""
-        f = self.file
-        terms = _where_terms(where, snap.particles.types)
         dims = int(snap.configuration.dimensions)
         box = snap.configuration.box
         if domain is not None and not isinstance(domain, Domain):
             domain = Domain(*domain)
+        rows, count, staged = self._where_row_list(idx, snap.particles.types, box, dims, where, domain, scalar4, n_global)
+        snap.where = where
+        if domain is not None:
+            snap.domain = domain
+        if cell_order is not None:
+            f_pos = self._effective_frame(idx, 'particles/position', n_global)
+            self._order_rows_device(snap, rows, count, cell_order, f_pos)
+            if f_pos is not None and count > 0 and 'position' not in staged:
+                staged[:0] = ['position', 'pos4'] if scalar4 else ['position']      # (staged by the ordering)
+        self._gather_rows_device(idx, snap, rows, count, scalar4, defaults, n_global, tuple(staged))
+
+    def _where_row_list(self, idx, types, box, dims, where, domain, scalar4, n_global):
+        """The row list of a group read, ``(rows, count, staged)``: the rows in GPU memory, and the attributes whose
+        chunks the selection has left staged whole.  Shared by `read_frame_device` and `frame_stats_device`."""
+        f = self.file
+        terms = _where_terms(where, types)
         all_pass, device_terms, staged = True, [], []
         for name, column, lo, hi, mask in terms:
             fr = self._effective_frame(idx, 'particles/' + name, n_global)
@@ -2121,15 +2334,7 @@ class HOOMDTrajectory(object):
             rows, count = f.select_where_device(device_terms, domain=dom, box=box, dimensions=dims)
         else:
             rows, count = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device()), n_global
-        snap.where = where
-        if domain is not None:
-            snap.domain = domain
-        if cell_order is not None:
-            f_pos = self._effective_frame(idx, 'particles/position', n_global)
-            self._order_rows_device(snap, rows, count, cell_order, f_pos)
-            if f_pos is not None and count > 0 and 'position' not in staged:
-                staged[:0] = ['position', 'pos4'] if scalar4 else ['position']      # (staged by the ordering)
-        self._gather_rows_device(idx, snap, rows, count, scalar4, defaults, n_global, tuple(staged))
+        return rows, count, staged
 
     def _census_frame(self, idx):
         """What a census of frame ``idx`` looks at: ``(box, dimensions, n_global, f_pos)`` -- the frame's configuration
@@ -2209,6 +2414,69 @@ class HOOMDTrajectory(object):
         finally:
             if f_pos is not None:
                 f.wait_read()
+
+    def frame_stats(self, idx, fields=_STATS_FIELDS, where=None, domain=None):
+        """`frame_stats` of frame ``idx`` read through the host path: a dict from field name to `FieldStats`.  The
+        definition of `frame_stats_device`."""
+        return frame_stats(self[int(idx)], fields, where=where, domain=domain)
+
+    def frame_stats_device(self, idx, fields=_STATS_FIELDS, where=None, domain=None):
+        """`frame_stats` of frame ``idx``, reduced on the GPU: a dict from field name to `FieldStats` that equals
+        ``frame_stats(idx, ...)`` exactly, the sums bit for bit.
+
+        The selection is `read_frame_device`'s own -- ``where``, ``domain`` or both, selected on the GPU --; without one
+        every row counts and no row list exists.  Each field's effective chunk (the frame's, else frame 0's) is staged
+        into HBM -- a chunk the selection staged is not read again: those fields are reduced first --, reduced there in
+        one pass (`pgsd.fl.PGSDFile.chunk_stats_device`) and released by one `wait_read`: a loop over fields or frames
+        holds the selection's chunks or one field's in HBM, and no per-particle data reaches the host.  Float fields of three columns get the
+        ``norm2`` column: ``stats['velocity'].max[3]`` is the square of the largest speed.  A field that is stored
+        nowhere is all defaults and is answered on the host from the one default row.
+        """
+        if idx < 0:
+            idx += len(self)
+        if idx >= len(self) or idx < 0:
+            raise IndexError()
+        names = _stats_fields(fields)
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        rows, count, staged = None, n_global, []
+        try:
+            if where is not None:
+                ft = self._frame_of(idx, 'particles/types')
+                types = ParticleData._default_value['types'] if ft is None else _decode_strings(
+                    self._frame0_small('particles/types') if ft == 0 else f.read_chunk(ft, 'particles/types'))
+                if domain is not None and not isinstance(domain, Domain):
+                    domain = Domain(*domain)
+                rows, count, staged = self._where_row_list(idx, types, box, dims, where, domain, False, n_global)
+            elif domain is not None:
+                if not isinstance(domain, Domain):
+                    domain = Domain(*domain)
+                rows, count = self._domain_row_list(f_pos, box, dims, domain, n_global)
+                staged = ['position']
+            # the fields whose chunks the selection left staged come first and share one wait: they are not read again
+            first = [name for name in names if name in staged]
+            out = {}
+            for name in first + [name for name in names if name not in first]:
+                dt, M, default, upstream = _PARTICLE_FIELDS[name]
+                norm2 = _stats_norm2(dt, M)
+                fr = self._effective_frame(idx, 'particles/' + name, n_global)
+                if fr is None:
+                    if upstream:
+                        raise ValueError("arrays holds no '%s'" % name)
+                    # stored nowhere: `count` copies of the default row, in the definition's order
+                    row = numpy.ascontiguousarray(numpy.broadcast_to(numpy.asarray(default, dtype=dt), (M,)))
+                    out[name] = column_stats(numpy.broadcast_to(row, (count, M)), norm2=norm2)
+                    continue
+                try:
+                    out[name] = f.chunk_stats_device(fr, 'particles/' + name, rows=rows,
+                                                     n=None if rows is None else count, norm2=norm2)
+                finally:
+                    if name not in first[:-1]:
+                        f.wait_read()   # the staged chunk is released: a loop over fields piles nothing up in HBM
+            return OrderedDict((name, out[name]) for name in names)
+        finally:
+            if rows is not None:
+                f.wait_read()           # (a selection whose chunks no field used)
 
     def _frame_of(self, idx, chunk):
         """The frame whose copy of a chunk that is NOT per-particle (box, N, types, log/*) frame ``idx`` reads: its
