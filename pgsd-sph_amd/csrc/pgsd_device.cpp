@@ -711,6 +711,16 @@ int device_pipeline_chunk_stats(DevicePipeline* p, long long file_offset, size_t
     return rc;
     }
 
+int device_pipeline_frame_moments(DevicePipeline* p, const ChunkRange* ranges, const MomentsArgs& m, uint64_t* out_counts,
+                                  double* out_sums, std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->frame_moments(ranges, m, out_counts, out_sums, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
 void device_pipeline_set_source_stream(DevicePipeline* p, void* stream)
     {
     p->set_source_stream(stream);

@@ -149,6 +149,7 @@ class DevicePipeline
                    std::string* why);
     int chunk_stats(long long file_offset, size_t bytes, StatsArgs s, uint64_t* out_counts, double* out_values,
                     std::string* why);
+    int frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums, std::string* why);
     int wait_read();
 
     // ---- accessors ----

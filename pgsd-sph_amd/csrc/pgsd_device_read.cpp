@@ -559,6 +559,36 @@ int DevicePipeline::chunk_stats(long long file_offset, size_t bytes, StatsArgs s
     return rc;
     }
 
+// Conservation sums: chunk_stats' flow over up to five chunks of one N -- one stage_chunks over those that are stored, so
+// what a selection, a census or a statistics call left staged is not read again --, the tile and the final kernel on the
+// pack stream, one synchronisation.  The row list is the caller's, so what its stream still does with it comes first.
+int DevicePipeline::frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums,
+                                  std::string* why)
+    {
+    int rc = enter();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    ChunkRange stored[MOMENTS_CHUNKS];
+    const void* src[MOMENTS_CHUNKS] = {};
+    size_t n_stored = 0;
+    for (int i = 0; i < MOMENTS_CHUNKS; i++)
+        if (m.present & (1u << i))
+            stored[n_stored++] = ranges[i];
+    rc = stage_chunks(stored, n_stored, m.N, src);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    n_stored = 0;
+    for (int i = 0; i < MOMENTS_CHUNKS; i++)
+        m.chunk[i] = (m.present & (1u << i)) ? src[n_stored++] : nullptr;
+    rc = order_after_source();
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = launch_frame_moments(m, out_counts, out_sums, m_res.pack_stream, why);
+    if (rc == PGSD_ERROR_DEVICE && why)
+        fail(*why);
+    return rc;
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

@@ -313,6 +313,36 @@ inline void chunk_stats_of_nothing(uint32_t C, uint64_t* out_counts, double* out
 // entry >= s.N refuses the call.  The staged rows stay until the next wait_read.
 int device_pipeline_chunk_stats(DevicePipeline*, long long file_offset, size_t bytes, const StatsArgs& s, uint64_t* out_counts,
                                 double* out_values, std::string* err);
+// Conservation sums (pgsd.hoomd.particle_moments is the definition): per particle type of a group of up to four
+// consecutive types the entries, those with a value that is not finite, and nine sums in chunk statistics' order -- mass
+// m, momentum m * v[a], kinetic energy (0.5 * m) * ((vx*vx + vy*vy) + vz*vz), internal energy m * e, first moment
+// m * x[a] -- over several staged chunks of one N read row by row, every element converted to float64 first.
+enum
+    {
+    MOMENTS_CHUNKS = 5,     // typeid, mass, velocity, energy, position
+    MOMENTS_QUANTITIES = 9,
+    MOMENTS_MAX_TYPES = 4   // types per launch
+    };
+struct MomentsArgs
+    {
+    const void* chunk[MOMENTS_CHUNKS]; // the staged chunks in the order above; null: the default row stands for every row
+    double defaults[8];                // mass, v[3], energy, x[3]
+    uint64_t N;                        // rows of every chunk that is present
+    const uint32_t* rows;              // device, or null: every row
+    uint64_t n;                        // entries of the list
+    uint32_t type0, n_types;           // the types [type0, type0 + n_types); without a typeid chunk every entry is type0's
+    uint32_t f64;                      // the float chunks hold float64 (else float32)
+    uint32_t typeid_signed;            // the typeid chunk holds int32: a negative id belongs to no type
+    uint32_t present;                  // bit i: chunk i is stored (its address is filled in by the staging)
+    uint32_t pad;
+    };
+// stage the chunks that are present (ranges[i] belongs to chunk i; m.chunk[i] is filled in) -- or take them from what an
+// earlier selection, census or statistics call left staged --, reduce on the GPU, copy the
+// results to the host: out_counts n_types x 2 (entries, bad), then the entries of no type of the group; out_sums
+// n_types x 9; written on success only; synchronous.  An entry >= m.N refuses the call.  The staged rows stay until the
+// next wait_read.
+int device_pipeline_frame_moments(DevicePipeline*, const ChunkRange* ranges, const MomentsArgs& m, uint64_t* out_counts,
+                                  double* out_sums, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

@@ -271,6 +271,12 @@ int launch_order_rows(const OrderArgs& o, uint32_t* rows, int32_t* shift, int32_
 // PGSD_ERROR_INVALID_ARGUMENT if an entry of the row list is >= s.N
 int launch_chunk_stats(const StatsArgs& s, uint64_t* out_counts, double* out_values, hipStream_t stream, std::string* err);
 
+// conservation sums (MomentsArgs, the addresses of the chunks that are present filled in): one pass of a workgroup per
+// tile of 4096 entries over all chunks, one workgroup per (type, quantity) over the tiles' partial results; out_counts
+// (host, n_types x 2, then the entries of no type) and out_sums (host, n_types x 9) are written on success only;
+// synchronises `stream`.  PGSD_ERROR_INVALID_ARGUMENT if an entry of the row list is >= m.N
+int launch_frame_moments(const MomentsArgs& m, uint64_t* out_counts, double* out_sums, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);

@@ -28,6 +28,10 @@
  *                     per column of a staged chunk, or of a selection's row list over it, the NaN and infinite entries,
  *                     minimum, maximum and a sum in a fixed order, so that "did the run blow up, what is the largest
  *                     speed, what is the density range" cost one pass over rows that are in HBM already)
+ *                     pgsd_frame_moments_device (pgsd.fl's frame_moments_device, behind pgsd.hoomd's
+ *                     frame_moments_device: per particle type the mass, momentum, kinetic and internal energy and first
+ *                     moment of a frame or of a selection, from the staged typeid, mass, velocity, energy and position
+ *                     chunks in one pass, so that "did the run conserve what it must" costs no read to the host)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -221,6 +225,33 @@ extern "C"
        are written on success only. */
     int pgsd_chunk_stats_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk, const uint32_t* rows,
                                 uint64_t n, uint32_t with_norm2, uint64_t* out_counts, double* out_values);
+
+    /* Conservation sums (pgsd.hoomd.particle_moments is the definition, and the results equal it exactly, the sums bit
+       for bit).  typeid_chunk: N x 1 uint32 or int32; mass, energy: N x 1; velocity, position: N x 3; the four float
+       chunks hold float32 or float64, all the same; every chunk that is given has the same N < 2^32.  A chunk that is
+       NULL is stored nowhere: defaults -- mass, v[3], energy, x[3] -- holds the row that stands for each of its rows, and
+       a NULL typeid_chunk puts every entry into one group (n_types must be 1).  rows (device memory, n entries, any
+       order, repeats allowed) or NULL: the entries are rows[0 .. n) in list order, or all N rows; when no chunk is given
+       and rows is NULL, n is the number of entries.  Every element is converted to float64 first.  Per entry nine
+       values, in this association and without a fused multiply-add:
+           0 m   1..3 m * v[a]   4 (0.5 * m) * ((vx*vx + vy*vy) + vz*vz)   5 m * e   6..8 m * x[a]
+       Per type t of [type0, type0 + n_types), 1 <= n_types <= 4, the results are HOST arrays:
+           out_counts[2 t + 0 .. 1]   the entries of the type, those of them with a value that is not finite
+           out_counts[2 n_types]      the entries of no type of the group (a negative int32 id is one)
+           out_sums[9 t + q]          the sum, in pgsd_chunk_stats_device's order, of value q over the list's entries, an
+                                      entry of another type or a value that is not finite counting as +0.0
+       The chunks are staged whole unless an earlier selection, census, ordering, statistics or moments call left them
+       staged (then no file byte is read), the reduction runs on the handle's GPU and the call synchronises; the staged
+       rows are kept until the next pgsd_device_wait_read.  No entry succeeds with zeros and launches nothing.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(): a float chunk of another element type, or of both;
+       a typeid chunk that is neither uint32 nor int32; a wrong number of columns; chunks that differ in N; n_types of 0
+       or above 4; a NULL typeid_chunk with n_types != 1; N or n >= 2^32; an entry >= N.  out_counts and out_sums are
+       written on success only. */
+    int pgsd_frame_moments_device(struct pgsd_handle* handle, const struct pgsd_index_entry* typeid_chunk,
+                                  const struct pgsd_index_entry* mass, const struct pgsd_index_entry* velocity,
+                                  const struct pgsd_index_entry* energy, const struct pgsd_index_entry* position,
+                                  const double defaults[8], uint32_t type0, uint32_t n_types, const uint32_t* rows,
+                                  uint64_t n, uint64_t* out_counts, double* out_sums);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

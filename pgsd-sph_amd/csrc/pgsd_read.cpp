@@ -706,6 +706,108 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_frame_moments_device(struct pgsd_handle* handle, const struct pgsd_index_entry* typeid_chunk,
+                                         const struct pgsd_index_entry* mass, const struct pgsd_index_entry* velocity,
+                                         const struct pgsd_index_entry* energy, const struct pgsd_index_entry* position,
+                                         const double defaults[8], uint32_t type0, uint32_t n_types, const uint32_t* rows,
+                                         uint64_t n, uint64_t* out_counts, double* out_sums)
+    try
+    {
+    static const char* who = "pgsd_frame_moments_device";
+    Impl* s = impl_of(handle);
+    if (!s || !defaults || !out_counts || !out_sums)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    static const char* const names[MOMENTS_CHUNKS] = {"typeid", "mass", "velocity", "energy", "position"};
+    static const uint32_t widths[MOMENTS_CHUNKS] = {1, 1, 3, 1, 3};
+    const struct pgsd_index_entry* given[MOMENTS_CHUNKS] = {typeid_chunk, mass, velocity, energy, position};
+    if (n_types < 1 || n_types > MOMENTS_MAX_TYPES)
+        return refuse("a call takes 1 to 4 types");
+    if (!typeid_chunk && n_types != 1)
+        return refuse("without a typeid chunk there is one group: n_types must be 1");
+    MomentsArgs a;
+    memset(&a, 0, sizeof(a));
+    ChunkRange ranges[MOMENTS_CHUNKS];
+    memset(ranges, 0, sizeof(ranges));
+    uint32_t float_type = 0;
+    for (int i = 0; i < MOMENTS_CHUNKS; i++)
+        {
+        if (!given[i])
+            continue;
+        pgsd_index_entry c = *given[i]; // a flush may move the index storage
+        if (i == 0)
+            {
+            if (c.type != PGSD_TYPE_UINT32 && c.type != PGSD_TYPE_INT32)
+                return refuse("the typeid chunk holds uint32 or int32 elements");
+            a.typeid_signed = c.type == PGSD_TYPE_INT32 ? 1u : 0u;
+            }
+        else
+            {
+            if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
+                return refuse(std::string("the ") + names[i] + " chunk holds float32 or float64 elements");
+            if (float_type && c.type != float_type)
+                return refuse("the float chunks share one element type (float32 or float64, not mixed)");
+            float_type = c.type;
+            }
+        if (c.M != widths[i])
+            return refuse(std::string("the ") + names[i] + " chunk has " + std::to_string(widths[i])
+                          + (widths[i] == 1 ? " column" : " columns"));
+        if (c.N >= (1ull << 32))
+            return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+        if (a.present && c.N != a.N)
+            return refuse("the chunks differ in their number of rows");
+        a.N = c.N;
+        int rc = whole_chunk_range(s, handle, c, &ranges[i].file_offset, &ranges[i].bytes);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        a.present |= 1u << i;
+        }
+    if (n >= (1ull << 32) && (rows || !a.present))
+        return refuse("a row list holds fewer than 2^32 entries");
+    // without a stored chunk nothing bounds the entries of a list (no row is loaded); without a list the call says how many
+    if (!a.present)
+        a.N = rows ? (1ull << 32) : n;
+    std::copy(defaults, defaults + 8, a.defaults);
+    a.rows = rows;
+    a.n = rows ? n : a.N;
+    a.type0 = type0;
+    a.n_types = n_types;
+    a.f64 = float_type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    // (the outputs are written on success only: the launcher fills these and they are copied out then)
+    uint64_t counts[2 * MOMENTS_MAX_TYPES + 1] = {};
+    double sums[MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES] = {};
+    if (a.n > 0)
+        {
+        if (a.N == 0)
+            return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
+        std::string err;
+        int rc = device_pipeline_frame_moments(s->dev, ranges, a, counts, sums, &err);
+        if (rc == PGSD_ERROR_INVALID_ARGUMENT)
+            {
+            const std::string prefix = "conservation sums: ";
+            if (err.compare(0, prefix.size(), prefix) == 0)
+                err.erase(0, prefix.size());
+            return refuse(err.empty() ? std::string("refused") : err);
+            }
+        if (rc != PGSD_SUCCESS)
+            {
+            set_last_error(err);
+            return rc;
+            }
+        }
+    std::copy(counts, counts + 2 * n_types + 1, out_counts);
+    std::copy(sums, sums + MOMENTS_QUANTITIES * n_types, out_sums);
+    return PGSD_SUCCESS;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_terms, const struct pgsd_index_entry* term_chunks,
                                         const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
                                         const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],

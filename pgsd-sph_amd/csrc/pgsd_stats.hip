@@ -15,6 +15,9 @@
 // starts at +0.0 and only ever adds is never -0.0.  Every element is converted to float64 first (exact for float32,
 // int32 and uint32); the appended norm2 column of a three-column float chunk is (x*x + y*y) + z*z in float64 without
 // contraction.  Shared device helpers and the row layout: pgsd_kernels.hpp.
+// The second half of the file holds the conservation sums -- moments_tile_kernel, moments_final_kernel: per particle
+// type the sums of m, m * v, (0.5 * m) |v|^2, m * e and m * x over several staged chunks read row by row --, which use
+// the same tile layout, the same trees and the same scratch; pgsd.hoomd.particle_moments is their definition.
 #include "pgsd_kernels.hpp"
 
 namespace pgsd_amd
@@ -277,6 +280,239 @@ __global__ __launch_bounds__(SEL_THREADS) void stats_final_kernel(const double* 
         }
     }
 
+// ------------------------------------------------------------------ conservation sums
+// pgsd.hoomd.particle_moments is the definition.  Per entry nine float64 values -- m; m * v[a]; (0.5 * m) * ((vx*vx +
+// vy*vy) + vz*vz); m * e; m * x[a] --, without contraction, from the rows of up to five staged chunks (typeid, mass,
+// velocity, energy, position); per type of the launch's group the sum of each value over the entries of that type where
+// the value is finite, in the order of the statistics above (an entry of another type, a value that is not finite and an
+// entry past the end add +0.0), the entries of the type and those with a value that is not finite; and the entries of
+// no type of the group.
+//   moments_tile_kernel<G, F64, TG>   the tile layout of stats_tile_kernel; TG (1, 2, 4) types per launch, all
+//                          accumulators in registers.  A chunk that is stored nowhere is a null pointer (uniform over
+//                          the launch) and its default row, passed by value.  Adding +0.0 to a sum that started at +0.0
+//                          changes no bit, so a wave skips the adds of a type none of its lanes holds (types lie in long
+//                          runs in real files).  Partials to td[(q * TG + t) * n_tiles + tile], counters to
+//                          tu[(c * TG + t) * n_tiles + tile] (c = entries, bad) and tu[2 * TG * n_tiles + tile] (other)
+//   moments_final_kernel   one workgroup per column of either table: the walk and the tree of stats_final_kernel
+enum
+    {
+    MOMENTS_RESULT_WORDS = MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES + 2 * MOMENTS_MAX_TYPES + 1 + 1 // sums, counters, flag
+    };
+
+template<bool G, bool F64, int TG>
+__global__ __launch_bounds__(SEL_THREADS) void moments_tile_kernel(const MomentsArgs s, uint32_t n_tiles, double* td,
+                                                                   uint32_t* tu, uint32_t* flag_dev, uint32_t* flag_host)
+    {
+#pragma clang fp contract(off)
+    constexpr int T = F64 ? STATS_F64 : STATS_F32;
+    constexpr int W1 = F64 ? 2 : 1, W3 = 3 * W1; // 32-bit words of a scalar and of a three-column row
+    constexpr int BATCH = F64 ? 2 : 4;           // entries a lane has in flight (up to 17 and 9 words each)
+    constexpr int Q = MOMENTS_QUANTITIES, NU = 2 * TG + 1;
+    __shared__ double wave_d[Q * TG][STATS_WAVES];
+    __shared__ uint32_t wave_u[NU][STATS_WAVES];
+    const uint32_t tile = blockIdx.x;
+    const uint64_t base = (uint64_t)tile * SEL_PER_BLOCK;
+    const uint64_t n = G ? s.n : s.N;
+    const uint32_t* c_tid = (const uint32_t*)s.chunk[0];
+    const uint32_t* c_mass = (const uint32_t*)s.chunk[1];
+    const uint32_t* c_vel = (const uint32_t*)s.chunk[2];
+    const uint32_t* c_energy = (const uint32_t*)s.chunk[3];
+    const uint32_t* c_pos = (const uint32_t*)s.chunk[4];
+    double acc[TG][Q];
+    uint32_t cnt[TG], bad[TG], other = 0;
+    bool seen[TG]; // (wave-uniform) a lane of this wave held an entry of type t: else everything of the type is zero
+#pragma unroll
+    for (int t = 0; t < TG; t++)
+        {
+        cnt[t] = bad[t] = 0;
+        seen[t] = false;
+#pragma unroll
+        for (int q = 0; q < Q; q++)
+            acc[t][q] = 0.0;
+        }
+#pragma unroll
+    for (int k0 = 0; k0 < SEL_PER_THREAD; k0 += BATCH)
+        {
+        RowRegs r_tid[BATCH], r_mass[BATCH], r_vel[BATCH], r_energy[BATCH], r_pos[BATCH];
+        bool ok[BATCH];
+#pragma unroll
+        for (int j = 0; j < BATCH; j++)
+            {
+            const uint64_t k = base + (uint64_t)(k0 + j) * SEL_THREADS + threadIdx.x;
+            ok[j] = k < n;
+            uint64_t row = min(k, n - 1);
+            const u32x4 zero = {0u, 0u, 0u, 0u};
+            r_tid[j].lo = r_mass[j].lo = r_vel[j].lo = r_vel[j].hi = r_energy[j].lo = r_pos[j].lo = r_pos[j].hi = zero;
+            if constexpr (G)
+                {
+                row = s.rows[row];
+                if (ok[j] && row >= s.N)
+                    {
+                    __hip_atomic_store(flag_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(flag_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    }
+                ok[j] = ok[j] && row < s.N;
+                }
+            if (!G || ok[j])
+                {
+                if (c_tid)
+                    row_load<1>(c_tid + row, r_tid[j]);
+                if (c_mass)
+                    row_load<W1>(c_mass + row * W1, r_mass[j]);
+                if (c_vel)
+                    row_load<W3>(c_vel + row * W3, r_vel[j]);
+                if (c_energy)
+                    row_load<W1>(c_energy + row * W1, r_energy[j]);
+                if (c_pos)
+                    row_load<W3>(c_pos + row * W3, r_pos[j]);
+                }
+            }
+#pragma unroll
+        for (int j = 0; j < BATCH; j++)
+            {
+            const double m = c_mass ? stats_elem<T>(r_mass[j], 0) : s.defaults[0];
+            const double e = c_energy ? stats_elem<T>(r_energy[j], 0) : s.defaults[4];
+            double v[3], x[3], val[Q];
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+                {
+                v[a] = c_vel ? stats_elem<T>(r_vel[j], a) : s.defaults[1 + a];
+                x[a] = c_pos ? stats_elem<T>(r_pos[j], a) : s.defaults[5 + a];
+                }
+            val[0] = m;
+            val[4] = (0.5 * m) * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+            val[5] = m * e;
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+                {
+                val[1 + a] = m * v[a];
+                val[6 + a] = m * x[a];
+                }
+            bool fin[Q], all_fin = true;
+#pragma unroll
+            for (int q = 0; q < Q; q++)
+                {
+                fin[q] = __builtin_fabs(val[q]) < __builtin_huge_val(); // (false for a NaN as well)
+                all_fin = all_fin && fin[q];
+                }
+            // the entry's place in the group; a negative int32 id, like any id outside the group, belongs to no type
+            const uint32_t id = r_tid[j].lo.x;
+            const uint32_t ty = c_tid ? id - s.type0 : 0u;
+            const bool in = ok[j] && ty < s.n_types && !(c_tid && id < s.type0) && !(s.typeid_signed && (int32_t)id < 0);
+            other += (ok[j] && !in) ? 1u : 0u;
+#pragma unroll
+            for (int t = 0; t < TG; t++)
+                {
+                const bool mine = in && ty == (uint32_t)t;
+                if (__ballot(mine) != 0ull) // (wave-uniform; skipping adds only +0.0 to sums that are never -0.0)
+                    {
+                    seen[t] = true;
+                    cnt[t] += mine ? 1u : 0u;
+                    bad[t] += (mine && !all_fin) ? 1u : 0u;
+#pragma unroll
+                    for (int q = 0; q < Q; q++)
+                        acc[t][q] = acc[t][q] + ((mine && fin[q]) ? val[q] : 0.0);
+                    }
+                }
+            }
+        }
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // (the tree over 64 sums of +0.0 is +0.0: a wave that held no entry of a type writes that without the shuffles)
+#pragma unroll
+    for (int t = 0; t < TG; t++)
+        {
+#pragma unroll
+        for (int q = 0; q < Q; q++)
+            {
+            const double sum = seen[t] ? stats_wave_sum(acc[t][q]) : 0.0;
+            if (lane == 0)
+                wave_d[q * TG + t][wave] = sum;
+            }
+        if (seen[t])
+            {
+#pragma unroll
+            for (int h = 32; h >= 1; h >>= 1)
+                {
+                cnt[t] += __shfl_xor(cnt[t], h, 64);
+                bad[t] += __shfl_xor(bad[t], h, 64);
+                }
+            }
+        if (lane == 0)
+            {
+            wave_u[t][wave] = cnt[t];
+            wave_u[TG + t][wave] = bad[t];
+            }
+        }
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1)
+        other += __shfl_xor(other, h, 64);
+    if (lane == 0)
+        wave_u[2 * TG][wave] = other;
+    __syncthreads();
+    if (threadIdx.x < Q * TG)
+        {
+        const double* w = wave_d[threadIdx.x];
+        td[(size_t)threadIdx.x * n_tiles + tile] = (w[0] + w[1]) + (w[2] + w[3]);
+        }
+    else if (threadIdx.x >= 64 && threadIdx.x < 64 + NU)
+        {
+        const uint32_t* u = wave_u[threadIdx.x - 64];
+        tu[(size_t)(threadIdx.x - 64) * n_tiles + tile] = u[0] + u[1] + u[2] + u[3];
+        }
+    }
+
+// One workgroup per column: the first n_d columns are the sums (stats_final_kernel's walk t, t + 256, ... per lane, then
+// the block tree), the next n_u the counters.  out: MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES doubles (column b at word b),
+// then the counters, then the flag word, handed over and cleared as there.
+__global__ __launch_bounds__(SEL_THREADS) void moments_final_kernel(const double* __restrict__ td, const uint32_t* __restrict__ tu,
+                                                                    uint32_t n_tiles, uint32_t n_d, uint32_t* flag_dev,
+                                                                    uint64_t* __restrict__ out)
+    {
+#pragma clang fp contract(off)
+    __shared__ double wave_d[STATS_WAVES];
+    __shared__ uint64_t wave_u[STATS_WAVES];
+    const uint32_t b = blockIdx.x;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (b < n_d)
+        {
+        const double* t_sum = td + (size_t)b * n_tiles;
+        double sum = 0.0;
+#pragma unroll 8
+        for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
+            sum = sum + t_sum[t];
+        sum = stats_wave_sum(sum);
+        if (lane == 0)
+            wave_d[wave] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            {
+            double* values = (double*)out;
+            values[b] = (wave_d[0] + wave_d[1]) + (wave_d[2] + wave_d[3]);
+            }
+        }
+    else
+        {
+        const uint32_t* t_cnt = tu + (size_t)(b - n_d) * n_tiles;
+        uint64_t count = 0;
+#pragma unroll 8
+        for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
+            count += t_cnt[t];
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1)
+            count += (uint64_t)__shfl_xor((unsigned long long)count, h, 64);
+        if (lane == 0)
+            wave_u[wave] = count;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            out[MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES + (b - n_d)] = wave_u[0] + wave_u[1] + wave_u[2] + wave_u[3];
+        }
+    if (b == 0 && threadIdx.x == 0)
+        {
+        out[MOMENTS_RESULT_WORDS - 1] = *flag_dev;
+        *flag_dev = 0u;
+        }
+    }
+
 // ------------------------------------------------------------------ host side
 namespace
     {
@@ -293,7 +529,9 @@ struct StatsScratch
     };
 std::map<int, StatsScratch> g_stats_scratch;
 std::mutex g_stats_lock;
-constexpr size_t STATS_HEAD_BYTES = (STATS_RESULT_WORDS + 1) * sizeof(uint64_t); // results, then the flag word
+// the head of the allocation: the result words of either reduction (chunk statistics, conservation sums), then the flag word
+constexpr size_t STATS_HEAD_WORDS = (STATS_RESULT_WORDS > MOMENTS_RESULT_WORDS ? STATS_RESULT_WORDS : MOMENTS_RESULT_WORDS);
+constexpr size_t STATS_HEAD_BYTES = (STATS_HEAD_WORDS + 1) * sizeof(uint64_t);
 
 int stats_scratch(int device, size_t table_bytes, StatsScratch** out)
     {
@@ -318,7 +556,7 @@ int stats_scratch(int device, size_t table_bytes, StatsScratch** out)
             }
         sc.cap_bytes = cap;
         }
-    if (!sc.host && hipHostMalloc((void**)&sc.host, STATS_RESULT_WORDS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
+    if (!sc.host && hipHostMalloc((void**)&sc.host, STATS_HEAD_WORDS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
         {
         sc.host = nullptr;
         set_last_error("chunk statistics: cannot allocate pinned memory");
@@ -416,7 +654,7 @@ int launch_chunk_stats(const StatsArgs& s, uint64_t* out_counts, double* out_val
         }
     (void)hipGetLastError(); // (an error of an earlier, unrelated launch is not this call's)
     uint64_t* result = (uint64_t*)sc->dev;
-    uint32_t* flag_dev = (uint32_t*)(sc->dev + STATS_RESULT_WORDS * sizeof(uint64_t));
+    uint32_t* flag_dev = (uint32_t*)(sc->dev + STATS_HEAD_WORDS * sizeof(uint64_t));
     double* td = (double*)(sc->dev + STATS_HEAD_BYTES);
     uint32_t* tu = (uint32_t*)(sc->dev + STATS_HEAD_BYTES + td_bytes);
     __atomic_store_n(sc->host_flag, 0u, __ATOMIC_RELEASE);
@@ -438,6 +676,98 @@ int launch_chunk_stats(const StatsArgs& s, uint64_t* out_counts, double* out_val
     const double* values = (const double*)(sc->host + 3 * STATS_MAX_COLUMNS);
     std::copy(sc->host, sc->host + 3 * C, out_counts);
     std::copy(values, values + 3 * C, out_values);
+    return PGSD_SUCCESS;
+    }
+
+namespace
+    {
+template<bool G, bool F64, int TG>
+void moments_tile_launch(const MomentsArgs& m, uint32_t n_tiles, double* td, uint32_t* tu, uint32_t* flag_dev,
+                         uint32_t* flag_host, hipStream_t stream)
+    {
+    hipLaunchKernelGGL((moments_tile_kernel<G, F64, TG>), dim3(n_tiles), dim3(SEL_THREADS), 0, stream, m, n_tiles, td, tu,
+                       flag_dev, flag_host);
+    }
+
+template<bool G, bool F64>
+void moments_tile_by_group(const MomentsArgs& m, uint32_t TG, uint32_t n_tiles, double* td, uint32_t* tu, uint32_t* flag_dev,
+                           uint32_t* flag_host, hipStream_t stream)
+    {
+    switch (TG)
+        {
+        case 1: return moments_tile_launch<G, F64, 1>(m, n_tiles, td, tu, flag_dev, flag_host, stream);
+        case 2: return moments_tile_launch<G, F64, 2>(m, n_tiles, td, tu, flag_dev, flag_host, stream);
+        default: return moments_tile_launch<G, F64, 4>(m, n_tiles, td, tu, flag_dev, flag_host, stream);
+        }
+    }
+    } // namespace
+
+int launch_frame_moments(const MomentsArgs& m, uint64_t* out_counts, double* out_sums, hipStream_t stream, std::string* err)
+    {
+    if (!out_counts || !out_sums || m.n_types < 1 || m.n_types > MOMENTS_MAX_TYPES || (!m.chunk[0] && m.n_types != 1))
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "conservation sums: 1 to 4 types, one without a typeid chunk");
+    const uint64_t n = m.rows ? m.n : m.N;
+    if (n >= (1ull << 32) || m.N > (1ull << 32))
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "conservation sums: 2^32 rows or entries and more are not indexed");
+    if (n == 0)
+        {
+        std::fill(out_counts, out_counts + 2 * m.n_types + 1, 0);
+        std::fill(out_sums, out_sums + MOMENTS_QUANTITIES * m.n_types, 0.0);
+        return PGSD_SUCCESS;
+        }
+    if (m.N == 0)
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
+                           "conservation sums: an entry of the row list lies outside the chunks (nothing was computed)");
+    std::lock_guard<std::mutex> guard(g_stats_lock);
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess)
+        return PGSD_ERROR_DEVICE;
+    const uint32_t TG = m.n_types == 3 ? 4u : m.n_types; // the kernels' group sizes: 1, 2, 4
+    const uint32_t n_d = MOMENTS_QUANTITIES * TG, n_u = 2 * TG + 1;
+    const uint32_t n_tiles = (uint32_t)((n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK);
+    const size_t td_bytes = (size_t)n_d * n_tiles * sizeof(double), tu_bytes = (size_t)n_u * n_tiles * sizeof(uint32_t);
+    StatsScratch* sc = nullptr;
+    int rc = stats_scratch(device, td_bytes + tu_bytes, &sc);
+    if (rc != PGSD_SUCCESS)
+        {
+        if (err)
+            *err = last_error();
+        return rc;
+        }
+    (void)hipGetLastError(); // (an error of an earlier, unrelated launch is not this call's)
+    uint64_t* result = (uint64_t*)sc->dev;
+    uint32_t* flag_dev = (uint32_t*)(sc->dev + STATS_HEAD_WORDS * sizeof(uint64_t));
+    double* td = (double*)(sc->dev + STATS_HEAD_BYTES);
+    uint32_t* tu = (uint32_t*)(sc->dev + STATS_HEAD_BYTES + td_bytes);
+    __atomic_store_n(sc->host_flag, 0u, __ATOMIC_RELEASE);
+    if (m.rows)
+        m.f64 ? moments_tile_by_group<true, true>(m, TG, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream)
+              : moments_tile_by_group<true, false>(m, TG, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream);
+    else
+        m.f64 ? moments_tile_by_group<false, true>(m, TG, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream)
+              : moments_tile_by_group<false, false>(m, TG, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream);
+    hipLaunchKernelGGL(moments_final_kernel, dim3(n_d + n_u), dim3(SEL_THREADS), 0, stream, td, tu, n_tiles, n_d, flag_dev,
+                       result);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(sc->host, result, MOMENTS_RESULT_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(stream);
+    if (e != hipSuccess)
+        return launch_fail(err, PGSD_ERROR_DEVICE, std::string("conservation sums: ") + hipGetErrorString(e));
+    if (__atomic_load_n(sc->host_flag, __ATOMIC_ACQUIRE) != 0 || sc->host[MOMENTS_RESULT_WORDS - 1] != 0)
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
+                           "conservation sums: an entry of the row list lies outside the chunks (nothing was computed)");
+    const double* sums = (const double*)sc->host;
+    const uint64_t* counters = sc->host + MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES;
+    for (uint32_t t = 0; t < m.n_types; t++)
+        {
+        out_counts[2 * t + 0] = counters[t];
+        out_counts[2 * t + 1] = counters[TG + t];
+        for (uint32_t q = 0; q < MOMENTS_QUANTITIES; q++)
+            out_sums[MOMENTS_QUANTITIES * t + q] = sums[q * TG + t];
+        }
+    out_counts[2 * m.n_types] = counters[2 * TG];
     return PGSD_SUCCESS;
     }
     } // namespace pgsd_amd

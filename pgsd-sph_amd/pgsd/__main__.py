@@ -7,7 +7,10 @@
            of the equal and of the balanced grid (the host models of ``pgsd.hoomd``: no GPU); ``--stats`` adds per
            field and column the count, the NaN and infinite entries, minimum, maximum and mean of one frame, and the
            largest norm of three-column float fields (``--fields``, ``--types``); ``--stats --all-frames`` prints one
-           line per frame with the number of non-finite entries and the largest speed: the blow-up scan.
+           line per frame with the number of non-finite entries and the largest speed: the blow-up scan;
+           ``--moments`` adds per particle type the count, mass, momentum, kinetic and internal energy and centre of
+           mass of one frame and a total line (``--types``), ``--moments --all-frames`` one line per frame with the
+           totals: the conservation table (``pgsd.hoomd.frame_moments`` on the host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -70,6 +73,40 @@ def _cmd_info(args):
         _print_balance(args, frame)
     if args.stats:
         _print_stats(args, frame)
+    if args.moments:
+        _print_moments(args, frame)
+
+
+def _vector_text(v):
+    return '(' + ', '.join(repr(float(c)) for c in v) + ')'
+
+
+def _print_moments(args, frame):
+    """``info --moments``: `pgsd.hoomd.frame_moments` of one frame per type, or the totals of every frame in one line
+    each, on the host."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        if args.all_frames:
+            print("conservation sums per frame%s:" % (" (types %s)" % args.types if args.types else ""))
+            for i in range(len(traj)):
+                snap = traj[i]
+                t = hoomd.frame_moments(snap, where=where).total()
+                print("  frame %-6d step %-10d count %-8d bad %-6d mass %r  momentum %s  kinetic %r  internal %r"
+                      % (i, int(snap.configuration.step), t.count[0], t.bad[0], float(t.mass[0]),
+                         _vector_text(t.momentum[0]), float(t.kinetic[0]), float(t.internal[0])))
+            return
+        snap = traj[frame]
+        m = hoomd.frame_moments(snap, where=where)
+        names = list(snap.particles.types)
+    print("conservation sums of frame %d%s:" % (frame, " (types %s)" % args.types if args.types else ""))
+    total = m.total()
+    for name, part, k in [(names[k], m, k) for k in range(len(names))] + [('total', total, 0)]:
+        print("  %-12s count %d  bad %d  mass %r  momentum %s  kinetic %r  internal %r  centre of mass %s"
+              % (name, part.count[k], part.bad[k], float(part.mass[k]), _vector_text(part.momentum[k]),
+                 float(part.kinetic[k]), float(part.internal[k]), _vector_text(part.centre_of_mass[k])))
+    if m.other:
+        print("  %d particles of no listed type" % m.other)
 
 
 def _print_stats(args, frame):
@@ -164,9 +201,12 @@ def main(argv=None):
     p.add_argument('--fields', type=str, default=None, metavar='NAME[,NAME...]',
                    help="the per-particle fields of --stats (default: position,velocity,density,pressure,energy)")
     p.add_argument('--types', type=str, default=None, metavar='NAME[,NAME...]',
-                   help="--stats over the particles of these types only")
+                   help="--stats and --moments over the particles of these types only")
     p.add_argument('--all-frames', action='store_true',
-                   help="with --stats: one line per frame with the non-finite entries and the largest speed")
+                   help="with --stats: one line per frame with the non-finite entries and the largest speed; "
+                        "with --moments: one line per frame with the totals")
+    p.add_argument('--moments', action='store_true',
+                   help="print count, mass, momentum, kinetic and internal energy and centre of mass per particle type")
     p.set_defaults(func=_cmd_info)
     p = sub.add_parser('vtu', help="convert the frames to VTK .vtu files")
     p.add_argument('file', type=str)

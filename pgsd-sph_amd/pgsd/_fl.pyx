@@ -1702,6 +1702,91 @@ cdef class PGSDFile:
         return _hoomd.FieldStats(counts[:, 0].copy(), counts[:, 1].copy(), counts[:, 2].copy(), values[:, 0].copy(),
                                  values[:, 1].copy(), values[:, 2].copy())
 
+    def frame_moments_device(self, chunks, defaults=None, type0=0, n_types=1, rows=None, n=None):
+        """Mass, momentum, kinetic and internal energy and first moment per particle type, reduced on the GPU in one
+        pass over up to five chunks.
+
+        Args:
+            chunks: five entries in the order typeid, mass, velocity, energy, position, each ``(frame, name)`` -- any
+                chunk of the file, so that an elided chunk can come from frame 0 -- or ``None``: stored nowhere.  The
+                typeid chunk is N x 1 uint32 or int32, mass and energy N x 1, velocity and position N x 3, the four
+                float32 or float64, all the same; every chunk has the same N.  Without a typeid chunk every entry
+                belongs to one group and ``n_types`` is 1.
+            defaults: eight values -- mass, v[3], energy, x[3] --: the row that stands for every row of a chunk that is
+                ``None`` (default: the schema's, 1, 0, 0, 0, 0, 0, 0, 0).
+            type0, n_types: the types ``[type0, type0 + n_types)``, ``1 <= n_types <= 4``.
+            rows: ``None`` for all rows, or 32-bit row indices in GPU memory, any order, repeats allowed.
+            n (int): the number of entries of ``rows`` to take (default: all of them); without ``rows`` and without a
+                chunk, the number of entries.
+
+        Returns:
+            A :class:`pgsd.hoomd.Moments`.  Exactly :func:`pgsd.hoomd.particle_moments`, the sums included: their order
+            is part of the definition.  The chunks are staged whole unless a selection, a census, an ordering, a
+            statistics or an earlier moments call left them staged; the staged rows are kept until the next
+            :meth:`wait_read`.  An entry outside the chunks raises ValueError.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entries[5]
+        cdef const C.pgsd_index_entry* given[5]
+        chunks = list(chunks)
+        if len(chunks) != 5:
+            raise ValueError("frame_moments_device: chunks holds typeid, mass, velocity, energy, position (or None)")
+        cdef int i
+        for i in range(5):
+            given[i] = NULL
+            if chunks[i] is not None:
+                frame, name = chunks[i]
+                self._entry(frame, name, &entries[i])
+                given[i] = &entries[i]
+        self._check_open()
+        c_defaults = numpy.ascontiguousarray(
+            numpy.array([1, 0, 0, 0, 0, 0, 0, 0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+        if c_defaults.shape[0] != 8:
+            raise ValueError("frame_moments_device: defaults holds mass, v[3], energy, x[3]")
+        if not 0 <= int(type0) < (1 << 32) or not 0 <= int(n_types) < (1 << 32):
+            raise ValueError("frame_moments_device: a call takes 1 to 4 types from a type id on")
+        cdef uintptr_t c_rows = 0
+        cdef uint32_t c_empty = 0
+        count = 0
+        if rows is not None:
+            p_rows, n_rows = _index_rows(rows)
+            count = n_rows if n is None else int(n)
+            if count >= (1 << 32):
+                raise ValueError("frame_moments_device: a row list holds fewer than 2^32 entries")
+            if count < 0 or count > n_rows:
+                raise ValueError("frame_moments_device: rows holds fewer entries than n")
+            c_rows = p_rows
+            if count == 0:
+                c_rows = <uintptr_t>&c_empty      # an empty list is still a list, but may have no address
+        elif n is not None:
+            if any(c is not None for c in chunks):
+                raise ValueError("frame_moments_device: n goes with rows, or with no chunk at all")
+            count = int(n)
+            if count < 0:
+                raise ValueError("frame_moments_device: n is a number of entries")
+        elif all(c is None for c in chunks):
+            raise ValueError("frame_moments_device: without a chunk and without rows, n says how many entries there are")
+        T = int(n_types) if 1 <= int(n_types) <= 4 else 1         # (the library refuses the rest)
+        counts = numpy.zeros(2 * T + 1, dtype=numpy.uint64)
+        sums = numpy.zeros((T, 9), dtype=numpy.float64)
+        if rows is not None and not self._explicit_stream:
+            self._sync_source_stream()      # the reduction is ordered behind this stream's use of `rows`
+        cdef uintptr_t c_counts = counts.ctypes.data, c_sums = sums.ctypes.data, c_pdef = c_defaults.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_type0 = int(type0), c_ntypes = int(n_types)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_frame_moments_device(&self._handle, given[0], given[1], given[2], given[3], given[4],
+                                                 <const double*>c_pdef, c_type0, c_ntypes, <const uint32_t*>c_rows, c_n,
+                                                 <uint64_t*>c_counts, <double*>c_sums)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("frame_moments_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else "refused"))
+        _raise_on_error(retval, self._name, err)
+        counts = counts.astype(numpy.int64)
+        return _hoomd.Moments.from_sums(counts[0:2 * T:2].copy(), counts[1:2 * T:2].copy(), int(counts[2 * T]), sums)
+
     def select_halo_device(self, frame, name, box, domain, ghost, dimensions=3):
         """A domain plus the ghost layer its neighbours reach, selected on the GPU from one position chunk.
 

@@ -1018,6 +1018,247 @@ def frame_stats(frame_or_arrays, fields=_STATS_FIELDS, where=None, types=None, d
     return out
 
 
+# ---- conservation sums: the definition the GPU reduction (`pgsd.fl.PGSDFile.frame_moments_device`) equals exactly
+_MOMENTS_QUANTITIES = 9     # mass, momentum x 3, kinetic, internal, first moment x 3
+_MOMENTS_MAX_TYPES = 4      # types per call (and per launch)
+_MOMENTS_INPUTS = (('mass', 1, 1.0), ('velocity', 3, (0.0, 0.0, 0.0)), ('energy', 1, 0.0), ('position', 3, (0.0, 0.0, 0.0)))
+
+
+class Moments(object):
+    """Conservation sums per particle type (`particle_moments`): arrays of one entry (or one row) per type.
+
+    Attributes:
+        count, bad (int64, T): the entries of the type, and those of them at which at least one of the nine per-entry
+            values is not finite.
+        other (int): the entries of no type of the call.
+        mass, kinetic, internal (float64, T): ``sum m``, ``sum (0.5 m) |v|^2``, ``sum m e`` (``energy`` is specific).
+        momentum, first_moment (float64, T x 3): ``sum m v``, ``sum m x``.
+        centre_of_mass, mean_velocity (properties, T x 3): ``first_moment / mass`` and ``momentum / mass``, NaN where
+            the mass is 0.
+
+    Every sum is over the finite values only and in `column_stats`' order.
+    """
+
+    __slots__ = ('count', 'bad', 'other', 'mass', 'momentum', 'kinetic', 'internal', 'first_moment')
+
+    def __init__(self, count, bad, other, mass, momentum, kinetic, internal, first_moment):
+        self.count = numpy.asarray(count, dtype=numpy.int64).reshape(-1)
+        T = self.count.shape[0]
+        self.bad = numpy.asarray(bad, dtype=numpy.int64).reshape(T)
+        self.other = int(other)
+        self.mass = numpy.asarray(mass, dtype=numpy.float64).reshape(T)
+        self.momentum = numpy.asarray(momentum, dtype=numpy.float64).reshape(T, 3)
+        self.kinetic = numpy.asarray(kinetic, dtype=numpy.float64).reshape(T)
+        self.internal = numpy.asarray(internal, dtype=numpy.float64).reshape(T)
+        self.first_moment = numpy.asarray(first_moment, dtype=numpy.float64).reshape(T, 3)
+
+    @classmethod
+    def from_sums(cls, count, bad, other, sums):
+        """From the ``T x 9`` table of sums in the order of the per-entry values."""
+        s = numpy.asarray(sums, dtype=numpy.float64).reshape(-1, _MOMENTS_QUANTITIES)
+        return cls(count, bad, other, s[:, 0].copy(), s[:, 1:4].copy(), s[:, 4].copy(), s[:, 5].copy(), s[:, 6:9].copy())
+
+    @property
+    def sums(self):
+        """The ``T x 9`` table of sums in the order of the per-entry values."""
+        return numpy.concatenate([self.mass[:, None], self.momentum, self.kinetic[:, None], self.internal[:, None],
+                                  self.first_moment], axis=1)
+
+    @property
+    def centre_of_mass(self):
+        return self._per_mass(self.first_moment)
+
+    @property
+    def mean_velocity(self):
+        return self._per_mass(self.momentum)
+
+    def _per_mass(self, a):
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(self.mass[:, None] != 0, a / self.mass[:, None], numpy.nan)
+
+    def total(self):
+        """All types as one: a `Moments` of one row whose sums are the types' added in ascending type order by plain
+        float64 additions; ``other`` stays."""
+        s = self.sums
+        acc = numpy.zeros(_MOMENTS_QUANTITIES, dtype=numpy.float64)
+        for t in range(s.shape[0]):
+            acc = s[t].copy() if t == 0 else acc + s[t]
+        return Moments.from_sums([int(self.count.sum())], [int(self.bad.sum())], self.other, acc)
+
+    @staticmethod
+    def concatenate(parts, n_entries):
+        """The `Moments` of consecutive groups of types (each over the same ``n_entries`` entries) as one."""
+        count = numpy.concatenate([p.count for p in parts])
+        return Moments.from_sums(count, numpy.concatenate([p.bad for p in parts]), int(n_entries) - int(count.sum()),
+                                 numpy.concatenate([p.sums for p in parts], axis=0))
+
+    def __repr__(self):
+        return "Moments(%s)" % ', '.join("%s=%r" % (name, getattr(self, name).tolist() if name != 'other' else self.other)
+                                         for name in self.__slots__)
+
+
+def _list_rows(rows, N):
+    """A row list as `column_stats` takes it, checked: int64 indices into ``N`` rows."""
+    rows = numpy.asarray(rows).reshape(-1)
+    if rows.size and rows.dtype.kind not in 'iu':
+        raise ValueError("rows holds integer row indices")
+    rows = rows.astype(numpy.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= N):
+        raise ValueError("an entry of the row list lies outside the array")
+    return rows
+
+
+def particle_moments(mass, velocity, energy=None, position=None, typeid=None, type0=0, n_types=1, rows=None, N=None):
+    """Mass, momentum, kinetic and internal energy and first moment per particle type: the definition the GPU reduction
+    (`pgsd.fl.PGSDFile.frame_moments_device`, `HOOMDTrajectory.frame_moments_device`) equals exactly, the sums bit for
+    bit.
+
+    Args:
+        mass (N), velocity (N x 3), energy (N), position (N x 3): float32 or float64 arrays, all that are arrays of one
+            element type.  Each may instead be a default row -- a scalar, or three values -- that stands for N copies of
+            it (converted to the arrays' element type; to float64 when there is no array), or ``None``: the schema's
+            default, 1.0, (0, 0, 0), 0.0 and (0, 0, 0).
+        typeid (N): uint32 or int32, or ``None``: no types, every entry belongs to the one group and ``n_types`` is 1.
+        type0, n_types: the types ``[type0, type0 + n_types)``, ``1 <= n_types <= 4``.
+        rows: as `column_stats` takes them: any order, repeats allowed, list order is entry order.
+        N (int): the number of rows when no input is an array (else it must agree with them).
+
+    Every element is converted to float64 first.  Per entry nine values, in float64, in exactly this association and
+    without a fused multiply-add: ``m``; ``m * v[a]``; ``(0.5 * m) * ((vx*vx + vy*vy) + vz*vz)``; ``m * e``;
+    ``m * x[a]``.  Per type ``t`` the result (`Moments`) holds the entries with ``typeid == t``, those of them with a
+    value that is not finite (``inf * 0`` included), and per value the sum **in `column_stats`' order** of the sequence
+    whose entry ``k`` is the value where ``typeid[k] == t`` and the value is finite, and ``+0.0`` otherwise: each value
+    skips only its own non-finite entries, and a type with no entry has sums of ``+0.0``.  ``other`` counts the entries
+    of no type of the range; a negative int32 id is one.
+
+    ValueError: other element types, mixed float types, wrong shapes or lengths, ``n_types`` of 0 or above 4, a typeid
+    of float elements, no typeid with ``n_types != 1``, no array and no ``N``, what `column_stats` refuses for ``rows``.
+    """
+    given = dict(zip(('mass', 'velocity', 'energy', 'position'), (mass, velocity, energy, position)))
+    arrays, dt, n_rows = {}, None, None if N is None else int(N)
+    for name, M, default in _MOMENTS_INPUTS:
+        a = numpy.asarray(default if given[name] is None else given[name])
+        if a.ndim == (1 if M == 1 else 2):          # an array of N rows
+            if a.dtype.type not in (numpy.float32, numpy.float64):
+                raise ValueError("moments take float32 or float64 arrays: %s is %s" % (name, a.dtype))
+            if dt is not None and a.dtype != dt:
+                raise ValueError("moments take arrays of one float type, not float32 and float64 mixed")
+            if M == 3 and a.shape[1] != 3:
+                raise ValueError("%s is an N x 3 array" % name)
+            if n_rows is not None and a.shape[0] != n_rows:
+                raise ValueError("the arrays differ in their number of rows (%s has %d)" % (name, a.shape[0]))
+            dt, n_rows = a.dtype, a.shape[0]
+        elif a.ndim != (0 if M == 1 else 1) or (M == 3 and a.shape[0] != 3) or a.dtype.kind not in 'fiu':
+            raise ValueError("%s is %s" % (name, "an array of N values or one value" if M == 1 else
+                                           "an N x 3 array or three values"))
+        arrays[name] = a
+    if not isinstance(n_types, (int, numpy.integer)) or not 1 <= n_types <= _MOMENTS_MAX_TYPES:
+        raise ValueError("a call takes 1 to 4 types: %r" % (n_types,))
+    if not isinstance(type0, (int, numpy.integer)) or not 0 <= type0 < 2 ** 32:
+        raise ValueError("type0 is a type id: %r" % (type0,))
+    if typeid is not None:
+        typeid = numpy.asarray(typeid)
+        if typeid.dtype.type not in (numpy.uint32, numpy.int32):
+            raise ValueError("typeid holds uint32 or int32 elements: %s" % typeid.dtype)
+        if typeid.ndim != 1:
+            raise ValueError("typeid is an array of N values")
+        if n_rows is not None and typeid.shape[0] != n_rows:
+            raise ValueError("the arrays differ in their number of rows (typeid has %d)" % typeid.shape[0])
+        n_rows = typeid.shape[0]
+    elif n_types != 1:
+        raise ValueError("without a typeid there is one group: n_types must be 1")
+    if n_rows is None:
+        raise ValueError("no input is an array: N says how many rows there are")
+    if n_rows < 0:
+        raise ValueError("N is a number of rows")
+    dt = numpy.dtype(numpy.float64) if dt is None else dt
+    if rows is not None:
+        rows = _list_rows(rows, n_rows)
+    n = n_rows if rows is None else rows.shape[0]
+
+    def column(name, c):
+        a, M = arrays[name], 1 if name in ('mass', 'energy') else 3
+        if a.ndim == (1 if M == 1 else 2):
+            a = a if M == 1 else a[:, c]
+            return (a if rows is None else a[rows]).astype(numpy.float64)
+        return numpy.full(n, numpy.float64(a.astype(dt).reshape(-1)[c]))
+
+    m, e = column('mass', 0), column('energy', 0)
+    v = [column('velocity', a) for a in range(3)]
+    x = [column('position', a) for a in range(3)]
+    with numpy.errstate(over='ignore', invalid='ignore', under='ignore'):
+        values = ([m] + [m * v[a] for a in range(3)]
+                  + [(0.5 * m) * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]), m * e] + [m * x[a] for a in range(3)])
+    finite = [numpy.isfinite(q) for q in values]
+    all_finite = numpy.logical_and.reduce(finite) if n else numpy.zeros(0, dtype=bool)
+    if typeid is None:
+        group = numpy.zeros(n, dtype=numpy.int64)
+    else:
+        group = (typeid if rows is None else typeid[rows]).astype(numpy.int64) - int(type0)
+    count, bad = numpy.zeros(n_types, numpy.int64), numpy.zeros(n_types, numpy.int64)
+    sums = numpy.zeros((n_types, _MOMENTS_QUANTITIES), dtype=numpy.float64)
+    for t in range(n_types):
+        mine = group == t
+        count[t], bad[t] = mine.sum(), (mine & ~all_finite).sum()
+        for q in range(_MOMENTS_QUANTITIES):
+            sums[t, q] = _ordered_sum(numpy.where(mine & finite[q], values[q], 0.0))
+    return Moments.from_sums(count, bad, n - int(count.sum()), sums)
+
+
+def frame_moments(frame_or_arrays, by_type=True, centre=True, where=None, types=None, domain=None, box=None, dimensions=3):
+    """`particle_moments` of a frame's ``mass``, ``velocity``, ``energy``, ``position`` and ``typeid`` over a selection:
+    the host twin of `HOOMDTrajectory.frame_moments_device`, which equals it exactly.
+
+    Args:
+        frame_or_arrays: a `Frame` (``types``, ``box`` and ``dimensions`` default to its own) or a dict of attribute
+            name -> ``N (x M)`` host array; an attribute that is missing is the schema's default.
+        by_type (bool): one row per type of ``types``, computed in groups of four consecutive types; ``False``: one row
+            for all entries, and no typeid is looked at.
+        centre (bool): ``False`` leaves the position out: the first moment is that of the default row, zero.
+        where, domain: the selection, as `frame_stats` takes it.
+
+    ``position`` is used as stored, wrapped into the box: in a periodic box the centre of mass is that of the wrapped
+    image, and the image flags are not applied.  Returns a `Moments`.
+
+    ValueError: what `where_rows`, `domain_rows` and `particle_moments` refuse; ``by_type`` without ``types``; a domain
+    without box or position.
+    """
+    if hasattr(frame_or_arrays, 'particles'):
+        frame = frame_or_arrays
+        arrays = _particle_arrays(frame.particles)
+        types = frame.particles.types if types is None else types
+        box = frame.configuration.box if box is None else box
+        if frame.configuration.dimensions is not None:
+            dimensions = int(frame.configuration.dimensions)
+        N = int(frame.particles.N)
+    else:
+        arrays = dict((k, v) for k, v in frame_or_arrays.items() if v is not None)
+        if not arrays:
+            raise ValueError("arrays holds no per-particle array")
+        N = len(next(iter(arrays.values())))
+    rows = None
+    if where is not None:
+        rows = where_rows(arrays, where, types)
+    if domain is not None:
+        if box is None or 'position' not in arrays:
+            raise ValueError("a domain needs box and the 'position' array")
+        inside = domain_rows(arrays['position'], box, domain, dimensions)
+        rows = inside if rows is None else numpy.intersect1d(rows, inside)
+    inputs = dict(mass=arrays.get('mass'), velocity=arrays.get('velocity'), energy=arrays.get('energy'),
+                  position=arrays.get('position') if centre else None, rows=rows, N=N)
+    if not by_type:
+        return particle_moments(**inputs)
+    if types is None:
+        raise ValueError("by_type needs the list of type names (types)")
+    typeid = numpy.zeros(N, dtype=numpy.uint32) if arrays.get('typeid') is None else numpy.asarray(arrays['typeid'])
+    n = N if rows is None else len(rows)
+    parts = [particle_moments(typeid=typeid, type0=t0, n_types=min(_MOMENTS_MAX_TYPES, len(types) - t0), **inputs)
+             for t0 in range(0, len(types), _MOMENTS_MAX_TYPES)]
+    if not parts:
+        return Moments.from_sums([], [], n, numpy.zeros((0, _MOMENTS_QUANTITIES)))
+    return Moments.concatenate(parts, n)
+
+
 class Tracks(object):
     """What `HOOMDTrajectory.read_tracks` / `read_tracks_device` return: ``step`` (host, uint64, one entry per frame),
     ``rows`` (the K rows followed) and one ``F x K (x M)`` array per requested field, as an attribute and as
@@ -2477,6 +2718,66 @@ class HOOMDTrajectory(object):
         finally:
             if rows is not None:
                 f.wait_read()           # (a selection whose chunks no field used)
+
+    def frame_moments(self, idx, by_type=True, centre=True, where=None, domain=None):
+        """`frame_moments` of frame ``idx`` read through the host path: a `Moments`.  The definition of
+        `frame_moments_device`."""
+        return frame_moments(self[int(idx)], by_type=by_type, centre=centre, where=where, domain=domain)
+
+    def frame_moments_device(self, idx, by_type=True, centre=True, where=None, domain=None):
+        """`frame_moments` of frame ``idx``, reduced on the GPU: a `Moments` that equals ``frame_moments(idx, ...)``
+        exactly, the sums bit for bit.
+
+        The selection is `frame_stats_device`'s -- ``where``, ``domain`` or both, selected on the GPU --; without one
+        every row counts and no row list exists.  The effective chunks (the frame's, else frame 0's) of ``typeid``,
+        ``mass``, ``velocity``, ``energy`` and, with ``centre``, ``position`` are staged into HBM -- a chunk the selection
+        staged is not read again -- and reduced there in one pass over all of them
+        (`pgsd.fl.PGSDFile.frame_moments_device`); a chunk that is stored nowhere costs nothing: its schema default
+        stands for every row and nothing is materialised.  More than four types take consecutive passes over the same
+        staged chunks, so no file byte is read twice; one `wait_read` at the end releases them.  No per-particle data
+        reaches the host.  ``position`` is used as stored: see `frame_moments`.
+        """
+        if idx < 0:
+            idx += len(self)
+        if idx >= len(self) or idx < 0:
+            raise IndexError()
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        ft = self._frame_of(idx, 'particles/types')
+        types = ParticleData._default_value['types'] if ft is None else _decode_strings(
+            self._frame0_small('particles/types') if ft == 0 else f.read_chunk(ft, 'particles/types'))
+        if domain is not None and not isinstance(domain, Domain):
+            domain = Domain(*domain)
+        rows, count = None, n_global
+        try:
+            if where is not None:
+                rows, count, _ = self._where_row_list(idx, types, box, dims, where, domain, False, n_global)
+            elif domain is not None:
+                rows, count = self._domain_row_list(f_pos, box, dims, domain, n_global)
+            names = ['typeid' if by_type else None, 'mass', 'velocity', 'energy', 'position' if centre else None]
+            chunks = []
+            for name in names:
+                fr = None if name is None else self._effective_frame(idx, 'particles/' + name, n_global)
+                chunks.append(None if fr is None else (fr, 'particles/' + name))
+            defaults = numpy.concatenate([numpy.broadcast_to(numpy.asarray(_PARTICLE_FIELDS[name][2], dtype=numpy.float32),
+                                                             (M,)) for name, M, _ in _MOMENTS_INPUTS]).astype(numpy.float64)
+            n = count if rows is not None or all(c is None for c in chunks) else None
+            T = len(types)
+            if by_type and T == 0:
+                return Moments.from_sums([], [], count, numpy.zeros((0, _MOMENTS_QUANTITIES)))
+            if not by_type or chunks[0] is None:
+                # one group; by type without a stored typeid every particle is of type 0
+                part = f.frame_moments_device(chunks, defaults, rows=rows, n=n)
+                if not by_type or T == 1:
+                    return part
+                zero = Moments.from_sums([0] * (T - 1), [0] * (T - 1), 0, numpy.zeros((T - 1, _MOMENTS_QUANTITIES)))
+                return Moments.concatenate([part, zero], count)
+            parts = [f.frame_moments_device(chunks, defaults, type0=t0, n_types=min(_MOMENTS_MAX_TYPES, T - t0),
+                                            rows=rows, n=n)
+                     for t0 in range(0, T, _MOMENTS_MAX_TYPES)]
+            return Moments.concatenate(parts, count)
+        finally:
+            f.wait_read()
 
     def _frame_of(self, idx, chunk):
         """The frame whose copy of a chunk that is NOT per-particle (box, N, types, log/*) frame ``idx`` reads: its

@@ -222,6 +222,11 @@ cdef extern from "pgsd_private.h" nogil:
     int pgsd_order_rows_by_cell_device(pgsd_handle* handle, const pgsd_index_entry* position, const float* box,
                                        uint32_t dimensions, const uint32_t* cells, uint32_t* rows, uint64_t n,
                                        uint64_t n_owned, int32_t* shift, int32_t* out_cell)
+    int pgsd_frame_moments_device(pgsd_handle* handle, const pgsd_index_entry* typeid_chunk, const pgsd_index_entry* mass,
+                                  const pgsd_index_entry* velocity, const pgsd_index_entry* energy,
+                                  const pgsd_index_entry* position, const double* defaults, uint32_t type0,
+                                  uint32_t n_types, const uint32_t* rows, uint64_t n, uint64_t* out_counts,
+                                  double* out_sums)
     int pgsd_chunk_stats_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                                 uint32_t with_norm2, uint64_t* out_counts, double* out_values)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
