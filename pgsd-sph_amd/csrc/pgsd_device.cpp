@@ -206,6 +206,9 @@ int DevicePipeline::init()
         warm_pack_kernels();
         warm_unpack_kernels();
         warm_select_kernels();
+        warm_compaction_kernels();
+        warm_census_kernels();
+        warm_order_kernels();
         int brc = compare_buffers();
         if (brc != PGSD_SUCCESS)
             return brc;

@@ -410,183 +410,136 @@ int DevicePipeline::stage_chunks(const ChunkRange* ranges, size_t n, uint64_t N,
     return rc;
     }
 
-// Domain selection: stage the position chunk, select on the pack stream, synchronise.  The staged rows are kept until
-// the next wait_read for an indexed read of the same chunk.
-int DevicePipeline::select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count)
+// One staged launch, the flow of every GPU pass over whole chunks: enter(); the n chunks of `ranges` (N rows each) into
+// HBM -- stage_chunks looks in the kept list first, so a chunk that an earlier selection, census, ordering or reduction
+// of this frame staged is not read again, and every chunk stays kept until the next wait_read for an indexed read of
+// the same chunk --; *slots[i] receives chunk i's staged rows; where the pass writes or reads memory of the caller's on
+// the device (`callers_memory`: a row list, shifts), what the caller's stream still does with that memory comes first;
+// `enqueue(why)` launches on the pack stream, synchronises it and returns a pgsd_error; a PGSD_ERROR_DEVICE fails the
+// pipeline with the launcher's message, where the caller takes one.  `refused`: what the entry point has against its
+// arguments, returned once the pipeline is entered.
+template<class Enqueue>
+int DevicePipeline::staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint64_t N, bool callers_memory,
+                                  std::string* why, Enqueue enqueue, int refused)
     {
     int rc = enter();
     if (rc != PGSD_SUCCESS)
         return rc;
-    const ChunkRange range = {file_offset, bytes};
-    rc = stage_chunks(&range, 1, d.N, &d.pos);
+    const void* src[STAGED_MAX_CHUNKS] = {};
+    if (refused != PGSD_SUCCESS || n > STAGED_MAX_CHUNKS)
+        return refused != PGSD_SUCCESS ? refused : PGSD_ERROR_INVALID_ARGUMENT;
+    rc = stage_chunks(ranges, n, N, src);
     if (rc != PGSD_SUCCESS)
         return rc;
-    // the row list belongs to the caller: what its stream still does with that memory comes first
-    rc = order_after_source();
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    std::string err;
-    rc = launch_select_domain(d, out_rows, out_count, m_res.pack_stream, &err);
-    if (rc == PGSD_ERROR_DEVICE)
-        fail(err);
+    for (size_t i = 0; i < n; i++)
+        *slots[i] = src[i];
+    if (callers_memory)
+        {
+        rc = order_after_source();
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        }
+    rc = enqueue(why);
+    if (rc == PGSD_ERROR_DEVICE && why)
+        fail(*why);
     return rc;
     }
 
-// Ghost layer selection: select_domain's staging, the halo kernels in place of the domain's.
+// Domain selection over the position chunk; the row list is the caller's.
+int DevicePipeline::select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count)
+    {
+    const ChunkRange range = {file_offset, bytes};
+    const void** const slot = &d.pos;
+    std::string message;
+    return staged_launch(&range, &slot, 1, d.N, true, &message, [&](std::string* err)
+                         { return launch_select_domain(d, out_rows, out_count, m_res.pack_stream, err); });
+    }
+
+// Ghost layer selection: the halo kernels in place of the domain's; the lists are the caller's.
 int DevicePipeline::select_halo(long long file_offset, size_t bytes, HaloArgs h, uint32_t* out_rows, int32_t* out_shift,
                                 uint64_t out_counts[2])
     {
-    int rc = enter();
-    if (rc != PGSD_SUCCESS)
-        return rc;
     const ChunkRange range = {file_offset, bytes};
-    rc = stage_chunks(&range, 1, h.d.N, &h.d.pos);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    rc = order_after_source(); // (the lists belong to the caller, as in select_domain)
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    std::string err;
-    rc = launch_select_halo(h, out_rows, out_shift, out_counts, m_res.pack_stream, &err);
-    if (rc == PGSD_ERROR_DEVICE)
-        fail(err);
-    return rc;
+    const void** const slot = &h.d.pos;
+    std::string message;
+    return staged_launch(&range, &slot, 1, h.d.N, true, &message, [&](std::string* err)
+                         { return launch_select_halo(h, out_rows, out_shift, out_counts, m_res.pack_stream, err); });
     }
 
-// Group selection: stage the chunks of the terms (and the position chunk of the domain, if there is one), select on the
-// pack stream, synchronise.  The staged chunks are kept like select_domain's.
+// Group selection: the chunks of the terms, then the position chunk of the domain, if there is one.
 int DevicePipeline::select_where(const ChunkRange* ranges, WhereArgs w, uint32_t* out_rows, uint64_t* out_count)
     {
-    int rc = enter();
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    if (w.n_terms > WHERE_MAX_TERMS)
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    const void* src[WHERE_MAX_TERMS + 1] = {};
-    rc = stage_chunks(ranges, w.n_terms + (w.has_domain ? 1 : 0), w.N, src);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    for (uint32_t j = 0; j < w.n_terms; j++)
-        w.t[j].base = src[j];
-    if (w.has_domain)
-        w.d.pos = src[w.n_terms];
-    rc = order_after_source();
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    std::string err;
-    rc = launch_select_where(w, out_rows, out_count, m_res.pack_stream, &err);
-    if (rc == PGSD_ERROR_DEVICE)
-        fail(err);
-    return rc;
+    const int refused = w.n_terms > WHERE_MAX_TERMS ? PGSD_ERROR_INVALID_ARGUMENT : PGSD_SUCCESS;
+    const void** slots[WHERE_MAX_TERMS + 1];
+    const uint32_t n_terms = refused ? 0 : w.n_terms;
+    for (uint32_t j = 0; j < n_terms; j++)
+        slots[j] = &w.t[j].base;
+    slots[n_terms] = &w.d.pos;
+    std::string message;
+    return staged_launch(
+        ranges, slots, n_terms + (w.has_domain ? 1 : 0), w.N, true, &message,
+        [&](std::string* err) { return launch_select_where(w, out_rows, out_count, m_res.pack_stream, err); }, refused);
     }
 
-// Domain census: select_domain's staging -- stage_chunks takes the position rows from what an earlier selection or census
-// of this frame kept --, one counting pass on the pack stream, the result on the host.  Nothing of the caller's is
-// written on the device, so there is no source stream to order behind.
+// Domain census: one counting pass, the result on the host.  Nothing of the caller's is touched on the device, so there
+// is no source stream to order behind.
 int DevicePipeline::domain_histogram(long long file_offset, size_t bytes, DomainArgs d, uint32_t bins, uint64_t* out_hist)
     {
-    int rc = enter();
-    if (rc != PGSD_SUCCESS)
-        return rc;
     const ChunkRange range = {file_offset, bytes};
-    rc = stage_chunks(&range, 1, d.N, &d.pos);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    std::string err;
-    rc = launch_axis_histograms(d, bins, out_hist, m_res.pack_stream, &err);
-    if (rc == PGSD_ERROR_DEVICE)
-        fail(err);
-    return rc;
+    const void** const slot = &d.pos;
+    std::string message;
+    return staged_launch(&range, &slot, 1, d.N, false, &message, [&](std::string* err)
+                         { return launch_axis_histograms(d, bins, out_hist, m_res.pack_stream, err); });
     }
 
 int DevicePipeline::domain_counts(long long file_offset, size_t bytes, CellArgs c, uint64_t* out_counts, uint64_t* out_nowhere)
     {
-    int rc = enter();
-    if (rc != PGSD_SUCCESS)
-        return rc;
     const ChunkRange range = {file_offset, bytes};
-    rc = stage_chunks(&range, 1, c.d.N, &c.d.pos);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    std::string err;
-    rc = launch_cell_counts(c, out_counts, out_nowhere, m_res.pack_stream, &err);
-    if (rc == PGSD_ERROR_DEVICE)
-        fail(err);
-    return rc;
+    const void** const slot = &c.d.pos;
+    std::string message;
+    return staged_launch(&range, &slot, 1, c.d.N, false, &message, [&](std::string* err)
+                         { return launch_cell_counts(c, out_counts, out_nowhere, m_res.pack_stream, err); });
     }
 
-// Cell order: select_domain's staging -- after a selection of the same frame stage_chunks finds the position rows in the
-// kept list and reads no file byte --, then keys, sort and apply on the pack stream, synchronised.  The lists are the
-// caller's, so what its stream still does with them comes first.
+// Cell order: keys, sort and apply; the lists are the caller's and are written in place.
 int DevicePipeline::order_rows(long long file_offset, size_t bytes, OrderArgs o, uint32_t* rows, int32_t* shift,
                                int32_t* out_cell, std::string* why)
     {
-    int rc = enter();
-    if (rc != PGSD_SUCCESS)
-        return rc;
     const ChunkRange range = {file_offset, bytes};
-    rc = stage_chunks(&range, 1, o.d.N, &o.d.pos);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    rc = order_after_source();
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    rc = launch_order_rows(o, rows, shift, out_cell, m_res.pack_stream, why);
-    if (rc == PGSD_ERROR_DEVICE && why)
-        fail(*why);
-    return rc;
+    const void** const slot = &o.d.pos;
+    return staged_launch(&range, &slot, 1, o.d.N, true, why, [&](std::string* err)
+                         { return launch_order_rows(o, rows, shift, out_cell, m_res.pack_stream, err); });
     }
 
-// Chunk statistics: stage the chunk -- stage_chunks looks in the kept list first, so a chunk that a selection, a census,
-// an ordering or an earlier statistics call staged is not read again --, the tile and the final kernel on the pack stream,
-// one synchronisation.  The row list is the caller's, so what its stream still does with it comes first.
+// Chunk statistics: the tile and the final kernel; the row list is the caller's.
 int DevicePipeline::chunk_stats(long long file_offset, size_t bytes, StatsArgs s, uint64_t* out_counts, double* out_values,
                                 std::string* why)
     {
-    int rc = enter();
-    if (rc != PGSD_SUCCESS)
-        return rc;
     const ChunkRange range = {file_offset, bytes};
-    rc = stage_chunks(&range, 1, s.N, &s.base);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    rc = order_after_source();
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    rc = launch_chunk_stats(s, out_counts, out_values, m_res.pack_stream, why);
-    if (rc == PGSD_ERROR_DEVICE && why)
-        fail(*why);
-    return rc;
+    const void** const slot = &s.base;
+    return staged_launch(&range, &slot, 1, s.N, true, why, [&](std::string* err)
+                         { return launch_chunk_stats(s, out_counts, out_values, m_res.pack_stream, err); });
     }
 
-// Conservation sums: chunk_stats' flow over up to five chunks of one N -- one stage_chunks over those that are stored, so
-// what a selection, a census or a statistics call left staged is not read again --, the tile and the final kernel on the
-// pack stream, one synchronisation.  The row list is the caller's, so what its stream still does with it comes first.
+// Conservation sums over up to five chunks of one N: only the stored chunks are staged and the absent ones stay null;
+// the row list is the caller's.
 int DevicePipeline::frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums,
                                   std::string* why)
     {
-    int rc = enter();
-    if (rc != PGSD_SUCCESS)
-        return rc;
     ChunkRange stored[MOMENTS_CHUNKS];
-    const void* src[MOMENTS_CHUNKS] = {};
+    const void** slots[MOMENTS_CHUNKS];
     size_t n_stored = 0;
     for (int i = 0; i < MOMENTS_CHUNKS; i++)
+        {
+        m.chunk[i] = nullptr;
         if (m.present & (1u << i))
-            stored[n_stored++] = ranges[i];
-    rc = stage_chunks(stored, n_stored, m.N, src);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    n_stored = 0;
-    for (int i = 0; i < MOMENTS_CHUNKS; i++)
-        m.chunk[i] = (m.present & (1u << i)) ? src[n_stored++] : nullptr;
-    rc = order_after_source();
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    rc = launch_frame_moments(m, out_counts, out_sums, m_res.pack_stream, why);
-    if (rc == PGSD_ERROR_DEVICE && why)
-        fail(*why);
-    return rc;
+            {
+            stored[n_stored] = ranges[i];
+            slots[n_stored++] = &m.chunk[i];
+            }
+        }
+    return staged_launch(stored, slots, n_stored, m.N, true, why, [&](std::string* err)
+                         { return launch_frame_moments(m, out_counts, out_sums, m_res.pack_stream, err); });
     }
 
 int DevicePipeline::wait_read()

@@ -14,11 +14,12 @@
 // An entry that is not finite contributes +0.0, and so does an entry past the end: the identity here, because a sum that
 // starts at +0.0 and only ever adds is never -0.0.  Every element is converted to float64 first (exact for float32,
 // int32 and uint32); the appended norm2 column of a three-column float chunk is (x*x + y*y) + z*z in float64 without
-// contraction.  Shared device helpers and the row layout: pgsd_kernels.hpp.
+// contraction.  Shared device helpers and the row layout: pgsd_kernels.hpp; the launchers' host side: pgsd_scratch.hpp.
 // The second half of the file holds the conservation sums -- moments_tile_kernel, moments_final_kernel: per particle
 // type the sums of m, m * v, (0.5 * m) |v|^2, m * e and m * x over several staged chunks read row by row --, which use
 // the same tile layout, the same trees and the same scratch; pgsd.hoomd.particle_moments is their definition.
 #include "pgsd_kernels.hpp"
+#include "pgsd_scratch.hpp"
 
 namespace pgsd_amd
     {
@@ -517,68 +518,49 @@ __global__ __launch_bounds__(SEL_THREADS) void moments_final_kernel(const double
 namespace
     {
 // Grow-only, per device (g_stats_lock held): the result words, the device flag word and the table of the tiles'
-// partials in one allocation; the pinned twin of the result words; the pinned, device-mapped flag word.  Nothing is
-// allocated by a call that finds them large enough.
-struct StatsScratch
-    {
-    char* dev = nullptr;
-    size_t cap_bytes = 0;
-    uint64_t* host = nullptr;          // pinned: the result words after the copy
-    uint32_t* host_flag = nullptr;     // pinned, device-mapped
-    uint32_t* host_flag_dev = nullptr; // ... through this alias
-    };
-std::map<int, StatsScratch> g_stats_scratch;
-std::mutex g_stats_lock;
+// partials in one allocation; the pinned twin of the result words; the pinned, device-mapped flag word.
 // the head of the allocation: the result words of either reduction (chunk statistics, conservation sums), then the flag word
 constexpr size_t STATS_HEAD_WORDS = (STATS_RESULT_WORDS > MOMENTS_RESULT_WORDS ? STATS_RESULT_WORDS : MOMENTS_RESULT_WORDS);
 constexpr size_t STATS_HEAD_BYTES = (STATS_HEAD_WORDS + 1) * sizeof(uint64_t);
+// (growth policy, head and bytes per tile: restated by tests/test_gpu_scratch_reuse.py)
+Scratch g_stats_scratch("chunk statistics", 1.25, 1u << 16, STATS_HEAD_WORDS * sizeof(uint64_t), sizeof(uint64_t));
+std::mutex g_stats_lock;
 
-int stats_scratch(int device, size_t table_bytes, StatsScratch** out)
+// The launch scope of either reduction and the parts of its scratch space: head (result words, flag word), then the
+// tiles' doubles (td_bytes of them), then their counters (tu_bytes).  A fresh allocation's head is cleared -- the flag
+// word starts clear; from then on the final kernel clears it behind every call -- and the pinned flag word is lowered.
+struct StatsLaunch
     {
-    StatsScratch& sc = g_stats_scratch[device];
-    const size_t bytes = STATS_HEAD_BYTES + table_bytes;
-    if (bytes > sc.cap_bytes)
+    LaunchScope scope;
+    uint64_t *result = nullptr, *host = nullptr;
+    uint32_t *flag_dev = nullptr, *flag_host = nullptr, *flag_host_dev = nullptr, *tu = nullptr;
+    double* td = nullptr;
+    StatsLaunch(size_t td_bytes, size_t tu_bytes, hipStream_t stream, std::string* err)
+        : scope(g_stats_lock, g_stats_scratch, STATS_HEAD_BYTES + td_bytes + tu_bytes, stream, err, STATS_HEAD_BYTES)
         {
-        if (sc.dev)
-            (void)hipFree(sc.dev);
-        sc.dev = nullptr;
-        sc.cap_bytes = 0;
-        const size_t cap = std::max<size_t>(bytes + bytes / 4, 1u << 16);
-        // (the flag word starts clear; from then on the final kernel clears it behind every call)
-        if (hipMalloc((void**)&sc.dev, cap) != hipSuccess || hipMemset(sc.dev, 0, STATS_HEAD_BYTES) != hipSuccess)
-            {
-            if (sc.dev)
-                (void)hipFree(sc.dev);
-            sc.dev = nullptr;
-            (void)hipGetLastError();
-            set_last_error("chunk statistics: cannot allocate the scratch space");
-            return PGSD_ERROR_MEMORY_ALLOCATION_FAILED;
-            }
-        sc.cap_bytes = cap;
+        if (scope.rc() != PGSD_SUCCESS)
+            return;
+        const Scratch::Block& mem = scope.mem();
+        result = (uint64_t*)mem.dev;
+        flag_dev = (uint32_t*)(mem.dev + STATS_HEAD_WORDS * sizeof(uint64_t));
+        td = (double*)(mem.dev + STATS_HEAD_BYTES);
+        tu = (uint32_t*)(mem.dev + STATS_HEAD_BYTES + td_bytes);
+        host = (uint64_t*)mem.host;
+        flag_host = (uint32_t*)mem.mapped;
+        flag_host_dev = (uint32_t*)mem.mapped_dev;
+        __atomic_store_n(flag_host, 0u, __ATOMIC_RELEASE);
         }
-    if (!sc.host && hipHostMalloc((void**)&sc.host, STATS_HEAD_WORDS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
+    // the result words to the pinned twin, the stream's verdict; true where an entry was outside (either flag word)
+    int finish(const char* what, size_t result_words, size_t flag_word, bool* outside)
         {
-        sc.host = nullptr;
-        set_last_error("chunk statistics: cannot allocate pinned memory");
-        return PGSD_ERROR_MEMORY_ALLOCATION_FAILED;
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(host, result, result_words * sizeof(uint64_t), hipMemcpyDeviceToHost, scope.stream());
+        const int rc = scope.finish(what, e);
+        *outside = rc == PGSD_SUCCESS && (__atomic_load_n(flag_host, __ATOMIC_ACQUIRE) != 0 || host[flag_word] != 0);
+        return rc;
         }
-    if (!sc.host_flag)
-        {
-        void* alias = nullptr;
-        if (hipHostMalloc((void**)&sc.host_flag, sizeof(uint64_t), hipHostMallocMapped) != hipSuccess
-            || hipHostGetDevicePointer(&alias, sc.host_flag, 0) != hipSuccess)
-            {
-            if (sc.host_flag)
-                (void)hipHostFree(sc.host_flag);
-            sc.host_flag = nullptr;
-            set_last_error("chunk statistics: cannot allocate pinned memory");
-            return PGSD_ERROR_MEMORY_ALLOCATION_FAILED;
-            }
-        sc.host_flag_dev = (uint32_t*)alias;
-        }
-    *out = &sc;
-    return PGSD_SUCCESS;
-    }
+    };
 
 template<bool G, int T, int M, bool NORM2>
 void stats_tile_launch(const StatsArgs& s, uint32_t n_tiles, double* td, uint32_t* tu, uint32_t* flag_dev, uint32_t* flag_host,
@@ -638,43 +620,26 @@ int launch_chunk_stats(const StatsArgs& s, uint64_t* out_counts, double* out_val
                            "chunk statistics: an entry of the row list lies outside the chunk (nothing was computed)");
     if (!s.base)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> guard(g_stats_lock);
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess)
-        return PGSD_ERROR_DEVICE;
     const uint32_t n_tiles = (uint32_t)((n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK);
     const size_t td_bytes = (size_t)3 * C * n_tiles * sizeof(double), tu_bytes = (size_t)2 * C * n_tiles * sizeof(uint32_t);
-    StatsScratch* sc = nullptr;
-    int rc = stats_scratch(device, td_bytes + tu_bytes, &sc);
-    if (rc != PGSD_SUCCESS)
-        {
-        if (err)
-            *err = last_error();
-        return rc;
-        }
-    (void)hipGetLastError(); // (an error of an earlier, unrelated launch is not this call's)
-    uint64_t* result = (uint64_t*)sc->dev;
-    uint32_t* flag_dev = (uint32_t*)(sc->dev + STATS_HEAD_WORDS * sizeof(uint64_t));
-    double* td = (double*)(sc->dev + STATS_HEAD_BYTES);
-    uint32_t* tu = (uint32_t*)(sc->dev + STATS_HEAD_BYTES + td_bytes);
-    __atomic_store_n(sc->host_flag, 0u, __ATOMIC_RELEASE);
+    StatsLaunch sc(td_bytes, tu_bytes, stream, err);
+    if (sc.scope.rc() != PGSD_SUCCESS)
+        return sc.scope.rc();
     if (s.rows)
-        stats_tile_by_type<true>(s, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream);
+        stats_tile_by_type<true>(s, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
     else
-        stats_tile_by_type<false>(s, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream);
-    hipLaunchKernelGGL(stats_final_kernel, dim3(C), dim3(SEL_THREADS), 0, stream, td, tu, n_tiles, C, n, flag_dev, result);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(sc->host, result, STATS_RESULT_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(stream);
-    if (e != hipSuccess)
-        return launch_fail(err, PGSD_ERROR_DEVICE, std::string("chunk statistics: ") + hipGetErrorString(e));
-    if (__atomic_load_n(sc->host_flag, __ATOMIC_ACQUIRE) != 0 || sc->host[6 * STATS_MAX_COLUMNS] != 0)
+        stats_tile_by_type<false>(s, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
+    hipLaunchKernelGGL(stats_final_kernel, dim3(C), dim3(SEL_THREADS), 0, stream, sc.td, sc.tu, n_tiles, C, n, sc.flag_dev,
+                       sc.result);
+    bool outside = false;
+    const int rc = sc.finish("chunk statistics", STATS_RESULT_WORDS, 6 * STATS_MAX_COLUMNS, &outside);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (outside)
         return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
                            "chunk statistics: an entry of the row list lies outside the chunk (nothing was computed)");
-    const double* values = (const double*)(sc->host + 3 * STATS_MAX_COLUMNS);
-    std::copy(sc->host, sc->host + 3 * C, out_counts);
+    const double* values = (const double*)(sc.host + 3 * STATS_MAX_COLUMNS);
+    std::copy(sc.host, sc.host + 3 * C, out_counts);
     std::copy(values, values + 3 * C, out_values);
     return PGSD_SUCCESS;
     }
@@ -718,48 +683,30 @@ int launch_frame_moments(const MomentsArgs& m, uint64_t* out_counts, double* out
     if (m.N == 0)
         return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
                            "conservation sums: an entry of the row list lies outside the chunks (nothing was computed)");
-    std::lock_guard<std::mutex> guard(g_stats_lock);
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess)
-        return PGSD_ERROR_DEVICE;
     const uint32_t TG = m.n_types == 3 ? 4u : m.n_types; // the kernels' group sizes: 1, 2, 4
     const uint32_t n_d = MOMENTS_QUANTITIES * TG, n_u = 2 * TG + 1;
     const uint32_t n_tiles = (uint32_t)((n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK);
     const size_t td_bytes = (size_t)n_d * n_tiles * sizeof(double), tu_bytes = (size_t)n_u * n_tiles * sizeof(uint32_t);
-    StatsScratch* sc = nullptr;
-    int rc = stats_scratch(device, td_bytes + tu_bytes, &sc);
-    if (rc != PGSD_SUCCESS)
-        {
-        if (err)
-            *err = last_error();
-        return rc;
-        }
-    (void)hipGetLastError(); // (an error of an earlier, unrelated launch is not this call's)
-    uint64_t* result = (uint64_t*)sc->dev;
-    uint32_t* flag_dev = (uint32_t*)(sc->dev + STATS_HEAD_WORDS * sizeof(uint64_t));
-    double* td = (double*)(sc->dev + STATS_HEAD_BYTES);
-    uint32_t* tu = (uint32_t*)(sc->dev + STATS_HEAD_BYTES + td_bytes);
-    __atomic_store_n(sc->host_flag, 0u, __ATOMIC_RELEASE);
+    StatsLaunch sc(td_bytes, tu_bytes, stream, err);
+    if (sc.scope.rc() != PGSD_SUCCESS)
+        return sc.scope.rc();
     if (m.rows)
-        m.f64 ? moments_tile_by_group<true, true>(m, TG, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream)
-              : moments_tile_by_group<true, false>(m, TG, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream);
+        m.f64 ? moments_tile_by_group<true, true>(m, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream)
+              : moments_tile_by_group<true, false>(m, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
     else
-        m.f64 ? moments_tile_by_group<false, true>(m, TG, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream)
-              : moments_tile_by_group<false, false>(m, TG, n_tiles, td, tu, flag_dev, sc->host_flag_dev, stream);
-    hipLaunchKernelGGL(moments_final_kernel, dim3(n_d + n_u), dim3(SEL_THREADS), 0, stream, td, tu, n_tiles, n_d, flag_dev,
-                       result);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(sc->host, result, MOMENTS_RESULT_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(stream);
-    if (e != hipSuccess)
-        return launch_fail(err, PGSD_ERROR_DEVICE, std::string("conservation sums: ") + hipGetErrorString(e));
-    if (__atomic_load_n(sc->host_flag, __ATOMIC_ACQUIRE) != 0 || sc->host[MOMENTS_RESULT_WORDS - 1] != 0)
+        m.f64 ? moments_tile_by_group<false, true>(m, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream)
+              : moments_tile_by_group<false, false>(m, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
+    hipLaunchKernelGGL(moments_final_kernel, dim3(n_d + n_u), dim3(SEL_THREADS), 0, stream, sc.td, sc.tu, n_tiles, n_d,
+                       sc.flag_dev, sc.result);
+    bool outside = false;
+    const int rc = sc.finish("conservation sums", MOMENTS_RESULT_WORDS, MOMENTS_RESULT_WORDS - 1, &outside);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (outside)
         return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
                            "conservation sums: an entry of the row list lies outside the chunks (nothing was computed)");
-    const double* sums = (const double*)sc->host;
-    const uint64_t* counters = sc->host + MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES;
+    const double* sums = (const double*)sc.host;
+    const uint64_t* counters = sc.host + MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES;
     for (uint32_t t = 0; t < m.n_types; t++)
         {
         out_counts[2 * t + 0] = counters[t];
