@@ -724,6 +724,16 @@ int device_pipeline_frame_moments(DevicePipeline* p, const ChunkRange* ranges, c
     return rc;
     }
 
+int device_pipeline_frame_displacements(DevicePipeline* p, const ChunkRange* ranges, const DisplacementArgs& d,
+                                        uint64_t* out_counts, double* out_values, std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->frame_displacements(ranges, d, out_counts, out_values, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
 void device_pipeline_set_source_stream(DevicePipeline* p, void* stream)
     {
     p->set_source_stream(stream);

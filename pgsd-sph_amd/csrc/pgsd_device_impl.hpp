@@ -150,6 +150,8 @@ class DevicePipeline
     int chunk_stats(long long file_offset, size_t bytes, StatsArgs s, uint64_t* out_counts, double* out_values,
                     std::string* why);
     int frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums, std::string* why);
+    int frame_displacements(const ChunkRange* ranges, DisplacementArgs d, uint64_t* out_counts, double* out_values,
+                            std::string* why);
     int wait_read();
 
     // ---- accessors ----
@@ -245,9 +247,11 @@ class DevicePipeline
     void fill_across_launches(std::vector<std::shared_ptr<ReadReq>>& pending);
     const void* kept_chunk(long long file_offset, size_t bytes) const;
     int stage_chunks(const ChunkRange* ranges, size_t n, uint64_t N, const void** src);
+    // the most chunks one pass stages: the larger of what a predicate, the conservation sums and the displacements take
     enum
         {
-        STAGED_MAX_CHUNKS = (WHERE_MAX_TERMS + 1 > MOMENTS_CHUNKS ? WHERE_MAX_TERMS + 1 : MOMENTS_CHUNKS)
+        STAGED_WHERE_OR_MOMENTS = (WHERE_MAX_TERMS + 1 > MOMENTS_CHUNKS ? WHERE_MAX_TERMS + 1 : MOMENTS_CHUNKS),
+        STAGED_MAX_CHUNKS = (STAGED_WHERE_OR_MOMENTS > DISPLACEMENT_CHUNKS ? STAGED_WHERE_OR_MOMENTS : DISPLACEMENT_CHUNKS)
         };
     template<class Enqueue>
     int staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint64_t N, bool callers_memory,

@@ -542,6 +542,40 @@ int DevicePipeline::frame_moments(const ChunkRange* ranges, MomentsArgs m, uint6
                          { return launch_frame_moments(m, out_counts, out_sums, m_res.pack_stream, err); });
     }
 
+// Frame displacements over up to five chunks of one N, two of them positions of different frames.  Two chunks of one
+// file range -- an elided chunk that both frames read from frame 0 -- are staged once and share the address: the
+// staging is never handed one range twice.  The row list and the optional output are the caller's.
+int DevicePipeline::frame_displacements(const ChunkRange* ranges, DisplacementArgs d, uint64_t* out_counts,
+                                        double* out_values, std::string* why)
+    {
+    static_assert((int)DISPLACEMENT_CHUNKS <= (int)STAGED_MAX_CHUNKS, "every chunk of the pass has a staging slot");
+    ChunkRange stored[DISPLACEMENT_CHUNKS];
+    const void** slots[DISPLACEMENT_CHUNKS];
+    int same_as[DISPLACEMENT_CHUNKS];
+    size_t n_stored = 0;
+    for (int i = 0; i < DISPLACEMENT_CHUNKS; i++)
+        {
+        d.chunk[i] = nullptr;
+        same_as[i] = -1;
+        if (!(d.present & (1u << i)))
+            continue;
+        for (int j = 0; j < i && same_as[i] < 0; j++)
+            if ((d.present & (1u << j)) && ranges[j].file_offset == ranges[i].file_offset && ranges[j].bytes == ranges[i].bytes)
+                same_as[i] = same_as[j] < 0 ? j : same_as[j];
+        if (same_as[i] >= 0)
+            continue;
+        stored[n_stored] = ranges[i];
+        slots[n_stored++] = &d.chunk[i];
+        }
+    return staged_launch(stored, slots, n_stored, d.N, true, why, [&](std::string* err)
+                         {
+                             for (int i = 0; i < DISPLACEMENT_CHUNKS; i++)
+                                 if (same_as[i] >= 0)
+                                     d.chunk[i] = d.chunk[same_as[i]];
+                             return launch_frame_displacements(d, out_counts, out_values, m_res.pack_stream, err);
+                         });
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

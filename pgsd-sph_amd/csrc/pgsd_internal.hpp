@@ -343,6 +343,54 @@ struct MomentsArgs
 // next wait_read.
 int device_pipeline_frame_moments(DevicePipeline*, const ChunkRange* ranges, const MomentsArgs& m, uint64_t* out_counts,
                                   double* out_sums, std::string* err);
+// Frame displacements (pgsd.hoomd.particle_displacements is the definition): row k of frame a and row k of frame b are
+// one particle; per entry the difference d of the two positions, each unwrapped through its image flags and its box
+// vectors (or folded into frame b's box: the minimum image), and s = |d|^2; per particle type of a group of up to four
+// consecutive types the entries, those with a value that is not finite, the sums of d[a] and of s in chunk statistics'
+// order, the largest s and the smallest entry that attains it.
+enum
+    {
+    DISPLACEMENT_CHUNKS = 5,    // position a, image a, position b, image b, typeid
+    DISPLACEMENT_SUMS = 4,      // d[0], d[1], d[2], s
+    DISPLACEMENT_VALUES = 5,    // the sums, then the largest s
+    DISPLACEMENT_MAX_TYPES = 4, // types per launch
+    DISPLACEMENT_MINIMUM_IMAGE = 1u // bit of the entry point's flags
+    };
+struct DisplacementArgs
+    {
+    const void* chunk[DISPLACEMENT_CHUNKS]; // the staged chunks in the order above; null: stored nowhere
+    double va[6], vb[6];                    // Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz of frame a and of frame b
+    uint64_t N;                             // rows of every chunk
+    const uint32_t* rows;                   // device, or null: every row
+    uint64_t n;                             // entries of the list
+    double* out;                            // device, n x 3, or null: entry k's d
+    uint32_t type0, n_types;                // the types [type0, type0 + n_types); without a typeid chunk every entry is type0's
+    uint32_t f64;                           // the position chunks hold float64 (else float32)
+    uint32_t typeid_signed;                 // the typeid chunk holds int32: a negative id belongs to no type
+    uint32_t present;                       // bit i: chunk i is stored (its address is filled in by the staging)
+    uint32_t minimum_image, dimensions;     // fold d into frame b's box (no image chunk then); 2: z is not folded
+    uint32_t pad;
+    };
+// the results of no entry: zero counts, no largest entry, +0.0 sums, -inf
+inline void displacements_of_nothing(uint32_t n_types, uint64_t* out_counts, double* out_values)
+    {
+    for (uint32_t t = 0; t < n_types; t++)
+        {
+        out_counts[3 * t + 0] = out_counts[3 * t + 1] = 0;
+        out_counts[3 * t + 2] = UINT64_MAX;
+        for (int q = 0; q < DISPLACEMENT_SUMS; q++)
+            out_values[DISPLACEMENT_VALUES * t + q] = 0.0;
+        out_values[DISPLACEMENT_VALUES * t + DISPLACEMENT_SUMS] = -HUGE_VAL;
+        }
+    out_counts[3 * n_types] = 0;
+    }
+// stage the chunks that are present (ranges[i] belongs to chunk i; d.chunk[i] is filled in; two chunks of one file range
+// are staged once and share the address) -- or take them from what an earlier call left staged --, reduce on the GPU,
+// copy the results to the host: out_counts n_types x 3 (entries, bad, largest entry or UINT64_MAX), then the entries of
+// no type of the group; out_values n_types x 5; written on success only; synchronous.  An entry >= d.N refuses the
+// call.  The staged rows stay until the next wait_read.
+int device_pipeline_frame_displacements(DevicePipeline*, const ChunkRange* ranges, const DisplacementArgs& d,
+                                        uint64_t* out_counts, double* out_values, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

@@ -277,6 +277,14 @@ int launch_chunk_stats(const StatsArgs& s, uint64_t* out_counts, double* out_val
 // synchronises `stream`.  PGSD_ERROR_INVALID_ARGUMENT if an entry of the row list is >= m.N
 int launch_frame_moments(const MomentsArgs& m, uint64_t* out_counts, double* out_sums, hipStream_t stream, std::string* err);
 
+// frame displacements (DisplacementArgs, the addresses of the chunks that are present filled in): one pass of a
+// workgroup per tile of 4096 entries over the rows of both frames, one workgroup per (type, value) over the tiles'
+// partial results; out_counts (host, n_types x 3, then the entries of no type) and out_values (host, n_types x 5) are
+// written on success only; d.out (device, or null) receives every entry's displacement; synchronises `stream`.
+// PGSD_ERROR_INVALID_ARGUMENT if an entry of the row list is >= d.N
+int launch_frame_displacements(const DisplacementArgs& d, uint64_t* out_counts, double* out_values, hipStream_t stream,
+                               std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);

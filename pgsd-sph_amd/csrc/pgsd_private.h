@@ -32,6 +32,10 @@
  *                     frame_moments_device: per particle type the mass, momentum, kinetic and internal energy and first
  *                     moment of a frame or of a selection, from the staged typeid, mass, velocity, energy and position
  *                     chunks in one pass, so that "did the run conserve what it must" costs no read to the host)
+ *                     pgsd_frame_displacements_device (pgsd.fl's frame_displacements_device, behind pgsd.hoomd's
+ *                     frame_displacements_device: per particle type the drift, the squared displacement and the largest
+ *                     move between two frames, unwrapped through image flags and box vectors, from the staged position
+ *                     and image chunks of both frames in one pass)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -252,6 +256,45 @@ extern "C"
                                   const struct pgsd_index_entry* energy, const struct pgsd_index_entry* position,
                                   const double defaults[8], uint32_t type0, uint32_t n_types, const uint32_t* rows,
                                   uint64_t n, uint64_t* out_counts, double* out_sums);
+
+    /* Frame displacements (pgsd.hoomd.particle_displacements is the definition, and the results equal it exactly, the
+       sums bit for bit).  Row k of frame a and row k of frame b are one particle.  position_a, position_b: N x 3 float32
+       or float64, both the same; image_a, image_b: N x 3 int32, or NULL: stored nowhere, (0, 0, 0) in every row;
+       typeid_chunk: N x 1 uint32 or int32, or NULL: one group (n_types must be 1); every chunk has the same N < 2^32.
+       vectors_a, vectors_b: Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz of each frame's box as float64 (pgsd.hoomd.box_vectors: the
+       products are rounded once, by the caller).  rows (device memory, n entries, any order, repeats allowed) or NULL:
+       the entries are rows[0 .. n) in list order, or all N rows.  Every element is converted to float64 first; no fused
+       multiply-add.  Per entry and frame, with i the image:
+           u[0] = x[0] + ((i[0]*Lx + i[1]*xyLy) + i[2]*xzLz)   u[1] = x[1] + (i[1]*Ly + i[2]*yzLz)   u[2] = x[2] + i[2]*Lz
+       (u = x without an image chunk), d = u_b - u_a; with bit 0 of flags, the minimum image (no image chunk allowed), d
+       is folded with frame b's vectors: n = rint(d[2] / Lz), d[2] -= n*Lz, d[1] -= n*yzLz, d[0] -= n*xzLz (dimensions
+       == 3 only), n = rint(d[1] / Ly), d[1] -= n*Ly, d[0] -= n*xyLy, n = rint(d[0] / Lx), d[0] -= n*Lx, rint rounding
+       half to even; s = (d[0]*d[0] + d[1]*d[1]) + d[2]*d[2].
+       Per type t of [type0, type0 + n_types), 1 <= n_types <= 4, the results are HOST arrays:
+           out_counts[3 t + 0 .. 2]   the entries of the type, those of them where a d[a] or s is not finite, and the
+                                      smallest entry (a position in rows, else a row) that attains the largest s
+                                      (UINT64_MAX when no entry of the type has an s that is a number)
+           out_counts[3 n_types]      the entries of no type of the group (a negative int32 id is one)
+           out_values[5 t + 0 .. 3]   the sums, in pgsd_chunk_stats_device's order, of d[0], d[1], d[2] and s over the
+                                      list's entries, an entry of another type or a value that is not finite counting
+                                      as +0.0
+           out_values[5 t + 4]        the largest s over the entries of the type where s is no NaN; -inf without one
+       out_rows (device memory, n x 3 float64, n the number of entries) or NULL: entry k's d at out_rows[3 k .. 3 k + 2].
+       The chunks are staged whole unless an earlier call left them staged (then no file byte is read); two chunks that
+       are one stored chunk -- an elided position both frames read from frame 0 -- are staged once.  The reduction runs
+       on the handle's GPU and the call synchronises; the staged rows are kept until the next pgsd_device_wait_read.
+       No entry succeeds with zero counts, +0.0, -inf and UINT64_MAX and launches nothing.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(): positions of another element type, or of both; an
+       image that is not int32; a typeid that is neither uint32 nor int32; a wrong number of columns; chunks that differ
+       in N; n_types of 0 or above 4; a NULL typeid_chunk with n_types != 1; the minimum image together with an image
+       chunk; another bit of flags; dimensions not 2 or 3; N or n >= 2^32; an entry >= N (out_rows beyond such an entry
+       is unspecified).  out_counts and out_values are written on success only. */
+    int pgsd_frame_displacements_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position_a,
+                                        const struct pgsd_index_entry* image_a, const struct pgsd_index_entry* position_b,
+                                        const struct pgsd_index_entry* image_b, const struct pgsd_index_entry* typeid_chunk,
+                                        const double vectors_a[6], const double vectors_b[6], uint32_t flags,
+                                        uint32_t dimensions, uint32_t type0, uint32_t n_types, const uint32_t* rows,
+                                        uint64_t n, double* out_rows, uint64_t* out_counts, double* out_values);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

@@ -808,6 +808,124 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position_a,
+                                               const struct pgsd_index_entry* image_a,
+                                               const struct pgsd_index_entry* position_b,
+                                               const struct pgsd_index_entry* image_b,
+                                               const struct pgsd_index_entry* typeid_chunk, const double vectors_a[6],
+                                               const double vectors_b[6], uint32_t flags, uint32_t dimensions, uint32_t type0,
+                                               uint32_t n_types, const uint32_t* rows, uint64_t n, double* out_rows,
+                                               uint64_t* out_counts, double* out_values)
+    try
+    {
+    static const char* who = "pgsd_frame_displacements_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position_a || !position_b || !vectors_a || !vectors_b || !out_counts || !out_values)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    static const char* const names[DISPLACEMENT_CHUNKS] = {"position", "image", "position", "image", "typeid"};
+    static const uint32_t widths[DISPLACEMENT_CHUNKS] = {3, 3, 3, 3, 1};
+    const struct pgsd_index_entry* given[DISPLACEMENT_CHUNKS] = {position_a, image_a, position_b, image_b, typeid_chunk};
+    if (n_types < 1 || n_types > DISPLACEMENT_MAX_TYPES)
+        return refuse("a call takes 1 to 4 types");
+    if (!typeid_chunk && n_types != 1)
+        return refuse("without a typeid chunk there is one group: n_types must be 1");
+    if (flags & ~(uint32_t)DISPLACEMENT_MINIMUM_IMAGE)
+        return refuse("flags holds the minimum-image bit and nothing else");
+    if ((flags & DISPLACEMENT_MINIMUM_IMAGE) && (image_a || image_b))
+        return refuse("the minimum image is taken without image chunks");
+    if (dimensions != 2 && dimensions != 3)
+        return refuse("dimensions is 2 or 3");
+    DisplacementArgs a;
+    memset(&a, 0, sizeof(a));
+    ChunkRange ranges[DISPLACEMENT_CHUNKS];
+    memset(ranges, 0, sizeof(ranges));
+    uint32_t float_type = 0;
+    for (int i = 0; i < DISPLACEMENT_CHUNKS; i++)
+        {
+        if (!given[i])
+            continue;
+        pgsd_index_entry c = *given[i]; // a flush may move the index storage
+        if (i == 4)
+            {
+            if (c.type != PGSD_TYPE_UINT32 && c.type != PGSD_TYPE_INT32)
+                return refuse("the typeid chunk holds uint32 or int32 elements");
+            a.typeid_signed = c.type == PGSD_TYPE_INT32 ? 1u : 0u;
+            }
+        else if (i == 1 || i == 3)
+            {
+            if (c.type != PGSD_TYPE_INT32)
+                return refuse("an image chunk holds int32 elements");
+            }
+        else
+            {
+            if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
+                return refuse("a position chunk holds float32 or float64 elements");
+            if (float_type && c.type != float_type)
+                return refuse("the position chunks share one element type (float32 or float64, not mixed)");
+            float_type = c.type;
+            }
+        if (c.M != widths[i])
+            return refuse(std::string("the ") + names[i] + " chunk has " + std::to_string(widths[i])
+                          + (widths[i] == 1 ? " column" : " columns"));
+        if (c.N >= (1ull << 32))
+            return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+        if (a.present && c.N != a.N)
+            return refuse("the chunks differ in their number of rows");
+        a.N = c.N;
+        int rc = whole_chunk_range(s, handle, c, &ranges[i].file_offset, &ranges[i].bytes);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        a.present |= 1u << i;
+        }
+    if (rows && n >= (1ull << 32))
+        return refuse("a row list holds fewer than 2^32 entries");
+    std::copy(vectors_a, vectors_a + 6, a.va);
+    std::copy(vectors_b, vectors_b + 6, a.vb);
+    a.rows = rows;
+    a.n = rows ? n : a.N;
+    a.out = out_rows;
+    a.type0 = type0;
+    a.n_types = n_types;
+    a.f64 = float_type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    a.minimum_image = (flags & DISPLACEMENT_MINIMUM_IMAGE) ? 1u : 0u;
+    a.dimensions = dimensions;
+    // (the outputs are written on success only: the launcher fills these and they are copied out then)
+    uint64_t counts[3 * DISPLACEMENT_MAX_TYPES + 1];
+    double values[DISPLACEMENT_VALUES * DISPLACEMENT_MAX_TYPES];
+    displacements_of_nothing(n_types, counts, values);
+    if (a.n > 0)
+        {
+        if (a.N == 0)
+            return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
+        std::string err;
+        int rc = device_pipeline_frame_displacements(s->dev, ranges, a, counts, values, &err);
+        if (rc == PGSD_ERROR_INVALID_ARGUMENT)
+            {
+            const std::string prefix = "frame displacements: ";
+            if (err.compare(0, prefix.size(), prefix) == 0)
+                err.erase(0, prefix.size());
+            return refuse(err.empty() ? std::string("refused") : err);
+            }
+        if (rc != PGSD_SUCCESS)
+            {
+            set_last_error(err);
+            return rc;
+            }
+        }
+    std::copy(counts, counts + 3 * n_types + 1, out_counts);
+    std::copy(values, values + DISPLACEMENT_VALUES * n_types, out_values);
+    return PGSD_SUCCESS;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_terms, const struct pgsd_index_entry* term_chunks,
                                         const uint32_t* columns, const uint32_t* kinds, const double* lo, const double* hi,
                                         const uint64_t* sets, const struct pgsd_index_entry* position, const float box[6],

@@ -18,6 +18,9 @@
 // The second half of the file holds the conservation sums -- moments_tile_kernel, moments_final_kernel: per particle
 // type the sums of m, m * v, (0.5 * m) |v|^2, m * e and m * x over several staged chunks read row by row --, which use
 // the same tile layout, the same trees and the same scratch; pgsd.hoomd.particle_moments is their definition.
+// The third part holds the frame displacements -- displacement_tile_kernel, displacement_final_kernel: per particle type
+// the sums of the difference of two frames' unwrapped positions and of its square, and the largest square with the entry
+// that attains it --, again in that layout and scratch; pgsd.hoomd.particle_displacements is their definition.
 #include "pgsd_kernels.hpp"
 #include "pgsd_scratch.hpp"
 
@@ -514,13 +517,359 @@ __global__ __launch_bounds__(SEL_THREADS) void moments_final_kernel(const double
         }
     }
 
+// ------------------------------------------------------------------ frame displacements
+// pgsd.hoomd.particle_displacements is the definition.  Per entry the rows of up to five staged chunks -- position a,
+// image a, position b, image b, typeid --; u = x + (image . box vectors) per frame in the definition's association (u = x
+// without an image chunk: no product is formed), d = u_b - u_a, with the minimum image folded z, y, x into frame b's
+// box, s = (d0*d0 + d1*d1) + d2*d2, all in float64 without contraction; per type of the launch's group the sums of d[a]
+// and of s over the entries where the value is finite, in the order of the statistics above, the entries, those with a
+// value that is not finite, and the largest s (NaN takes no part) with the smallest entry that attains it.
+//   displacement_tile_kernel<G, F64, TG>   the tile layout and the sums of moments_tile_kernel; a lane keeps (mx, k)
+//                          per type and replaces it on s > mx only, so that -- its entries ascend -- it keeps the smallest
+//                          k; across lanes, waves and tiles the rule is "larger mx, then smaller k", which is
+//                          associative and commutative: its order is free.  No entry: (-inf, 0xFFFFFFFF).  Partials to
+//                          td[(q * TG + t) * n_tiles + tile] (q = d0, d1, d2, s, largest), counters to
+//                          tu[(c * TG + t) * n_tiles + tile] (c = entries, bad, largest entry) and
+//                          tu[3 * TG * n_tiles + tile] (other).  With `out`, entry k's d goes to out[3 k .. 3 k + 2]
+//   displacement_final_kernel   one workgroup per column of either table: sums and counters as moments_final_kernel,
+//                          the largest s of a type by the pair rule
+enum
+    {
+    DISP_Q = DISPLACEMENT_SUMS,
+    DISP_NO_ENTRY = 0xFFFFFFFFu,
+    // the result words: 5 x 4 doubles (value q of type t at q * TG + t), 2 x 4 + 1 counters, 4 largest entries, the flag
+    DISP_WORD_COUNTERS = DISPLACEMENT_VALUES * DISPLACEMENT_MAX_TYPES,
+    DISP_WORD_ENTRIES = DISP_WORD_COUNTERS + 2 * DISPLACEMENT_MAX_TYPES + 1,
+    DISP_WORD_FLAG = DISP_WORD_ENTRIES + DISPLACEMENT_MAX_TYPES,
+    DISPLACEMENT_RESULT_WORDS = DISP_WORD_FLAG + 1
+    };
+
+// (mx, k) takes (om, ok) where that is the larger value, or the same value at a smaller entry
+__device__ __forceinline__ void disp_pair(double& mx, uint32_t& k, double om, uint32_t ok)
+    {
+    const bool better = om > mx || (om == mx && ok < k);
+    mx = better ? om : mx;
+    k = better ? ok : k;
+    }
+
+// the pair rule across the wave (every lane ends with the result)
+__device__ __forceinline__ void disp_wave_pair(double& mx, uint32_t& k)
+    {
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1)
+        {
+        const double om = __shfl_xor(mx, h, 64);
+        const uint32_t ok = __shfl_xor(k, h, 64);
+        disp_pair(mx, k, om, ok);
+        }
+    }
+
+// u = x + image . vectors of one frame, in the definition's association
+__device__ __forceinline__ void disp_unwrap(double u[3], const RowRegs& image, const double v[6])
+    {
+#pragma clang fp contract(off)
+    const double i0 = stats_elem<STATS_I32>(image, 0), i1 = stats_elem<STATS_I32>(image, 1), i2 = stats_elem<STATS_I32>(image, 2);
+    u[0] = u[0] + ((i0 * v[0] + i1 * v[3]) + i2 * v[4]);
+    u[1] = u[1] + (i1 * v[1] + i2 * v[5]);
+    u[2] = u[2] + i2 * v[2];
+    }
+
+// HOOMD's minImage: z (three dimensions only), then y, then x; rint is round-to-nearest-even
+__device__ __forceinline__ void disp_fold(double d[3], const double v[6], bool three)
+    {
+#pragma clang fp contract(off)
+    if (three)
+        {
+        const double n = __builtin_rint(d[2] / v[2]);
+        d[2] = d[2] - n * v[2];
+        d[1] = d[1] - n * v[5];
+        d[0] = d[0] - n * v[4];
+        }
+    double n = __builtin_rint(d[1] / v[1]);
+    d[1] = d[1] - n * v[1];
+    d[0] = d[0] - n * v[3];
+    n = __builtin_rint(d[0] / v[0]);
+    d[0] = d[0] - n * v[0];
+    }
+
+template<bool G, bool F64, int TG>
+__global__ __launch_bounds__(SEL_THREADS) void displacement_tile_kernel(const DisplacementArgs s, uint32_t n_tiles, double* td,
+                                                                        uint32_t* tu, uint32_t* flag_dev, uint32_t* flag_host)
+    {
+#pragma clang fp contract(off)
+    constexpr int T = F64 ? STATS_F64 : STATS_F32;
+    constexpr int W3 = F64 ? 6 : 3;    // 32-bit words of a position row
+    constexpr int BATCH = F64 ? 2 : 4; // entries a lane has in flight (up to 19 and 13 words each)
+    constexpr int Q = DISP_Q, NU = 3 * TG + 1;
+    __shared__ double wave_d[(Q + 1) * TG][STATS_WAVES];
+    __shared__ uint32_t wave_u[NU][STATS_WAVES];
+    const uint32_t tile = blockIdx.x;
+    const uint64_t base = (uint64_t)tile * SEL_PER_BLOCK;
+    const uint64_t n = G ? s.n : s.N;
+    const uint32_t* c_pa = (const uint32_t*)s.chunk[0];
+    const uint32_t* c_ia = (const uint32_t*)s.chunk[1];
+    const uint32_t* c_pb = (const uint32_t*)s.chunk[2];
+    const uint32_t* c_ib = (const uint32_t*)s.chunk[3];
+    const uint32_t* c_tid = (const uint32_t*)s.chunk[4];
+    double acc[TG][Q], mx[TG];
+    uint32_t cnt[TG], bad[TG], at[TG], other = 0;
+    bool seen[TG]; // (wave-uniform) a lane of this wave held an entry of type t: else everything of the type is nothing
+#pragma unroll
+    for (int t = 0; t < TG; t++)
+        {
+        cnt[t] = bad[t] = 0;
+        seen[t] = false;
+        mx[t] = -__builtin_huge_val();
+        at[t] = DISP_NO_ENTRY;
+#pragma unroll
+        for (int q = 0; q < Q; q++)
+            acc[t][q] = 0.0;
+        }
+#pragma unroll
+    for (int k0 = 0; k0 < SEL_PER_THREAD; k0 += BATCH)
+        {
+        RowRegs r_pa[BATCH], r_ia[BATCH], r_pb[BATCH], r_ib[BATCH], r_tid[BATCH];
+        bool ok[BATCH];
+#pragma unroll
+        for (int j = 0; j < BATCH; j++)
+            {
+            const uint64_t k = base + (uint64_t)(k0 + j) * SEL_THREADS + threadIdx.x;
+            ok[j] = k < n;
+            uint64_t row = min(k, n - 1);
+            const u32x4 zero = {0u, 0u, 0u, 0u};
+            r_pa[j].lo = r_pa[j].hi = r_pb[j].lo = r_pb[j].hi = r_ia[j].lo = r_ib[j].lo = r_tid[j].lo = zero;
+            if constexpr (G)
+                {
+                row = s.rows[row];
+                if (ok[j] && row >= s.N)
+                    {
+                    __hip_atomic_store(flag_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(flag_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    }
+                ok[j] = ok[j] && row < s.N;
+                }
+            if (!G || ok[j])
+                {
+                row_load<W3>(c_pa + row * W3, r_pa[j]);
+                row_load<W3>(c_pb + row * W3, r_pb[j]);
+                if (c_ia)
+                    row_load<3>(c_ia + row * 3, r_ia[j]);
+                if (c_ib)
+                    row_load<3>(c_ib + row * 3, r_ib[j]);
+                if (c_tid)
+                    row_load<1>(c_tid + row, r_tid[j]);
+                }
+            }
+#pragma unroll
+        for (int j = 0; j < BATCH; j++)
+            {
+            const uint64_t k = base + (uint64_t)(k0 + j) * SEL_THREADS + threadIdx.x;
+            double ua[3], d[3], val[Q];
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+                {
+                ua[a] = stats_elem<T>(r_pa[j], a);
+                d[a] = stats_elem<T>(r_pb[j], a);
+                }
+            if (c_ia)
+                disp_unwrap(ua, r_ia[j], s.va);
+            if (c_ib)
+                disp_unwrap(d, r_ib[j], s.vb);
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+                d[a] = d[a] - ua[a];
+            if (s.minimum_image)
+                disp_fold(d, s.vb, s.dimensions == 3);
+            const double sq = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+            if (s.out && ok[j])
+                {
+                double* o = s.out + 3 * k;
+                o[0] = d[0];
+                o[1] = d[1];
+                o[2] = d[2];
+                }
+            val[0] = d[0];
+            val[1] = d[1];
+            val[2] = d[2];
+            val[3] = sq;
+            bool fin[Q], all_fin = true;
+#pragma unroll
+            for (int q = 0; q < Q; q++)
+                {
+                fin[q] = __builtin_fabs(val[q]) < __builtin_huge_val(); // (false for a NaN as well)
+                all_fin = all_fin && fin[q];
+                }
+            // the entry's place in the group; a negative int32 id, like any id outside the group, belongs to no type
+            const uint32_t id = r_tid[j].lo.x;
+            const uint32_t ty = c_tid ? id - s.type0 : 0u;
+            const bool in = ok[j] && ty < s.n_types && !(c_tid && id < s.type0) && !(s.typeid_signed && (int32_t)id < 0);
+            other += (ok[j] && !in) ? 1u : 0u;
+#pragma unroll
+            for (int t = 0; t < TG; t++)
+                {
+                const bool mine = in && ty == (uint32_t)t;
+                if (__ballot(mine) != 0ull) // (wave-uniform; skipping adds only +0.0 to sums that are never -0.0)
+                    {
+                    seen[t] = true;
+                    cnt[t] += mine ? 1u : 0u;
+                    bad[t] += (mine && !all_fin) ? 1u : 0u;
+#pragma unroll
+                    for (int q = 0; q < Q; q++)
+                        acc[t][q] = acc[t][q] + ((mine && fin[q]) ? val[q] : 0.0);
+                    const bool larger = mine && sq > mx[t]; // (a NaN compares false; the lane's entries ascend)
+                    mx[t] = larger ? sq : mx[t];
+                    at[t] = larger ? (uint32_t)k : at[t];
+                    }
+                }
+            }
+        }
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int t = 0; t < TG; t++)
+        {
+#pragma unroll
+        for (int q = 0; q < Q; q++)
+            {
+            const double sum = seen[t] ? stats_wave_sum(acc[t][q]) : 0.0;
+            if (lane == 0)
+                wave_d[q * TG + t][wave] = sum;
+            }
+        if (seen[t])
+            {
+            disp_wave_pair(mx[t], at[t]);
+#pragma unroll
+            for (int h = 32; h >= 1; h >>= 1)
+                {
+                cnt[t] += __shfl_xor(cnt[t], h, 64);
+                bad[t] += __shfl_xor(bad[t], h, 64);
+                }
+            }
+        if (lane == 0)
+            {
+            wave_d[Q * TG + t][wave] = mx[t];
+            wave_u[t][wave] = cnt[t];
+            wave_u[TG + t][wave] = bad[t];
+            wave_u[2 * TG + t][wave] = at[t];
+            }
+        }
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1)
+        other += __shfl_xor(other, h, 64);
+    if (lane == 0)
+        wave_u[3 * TG][wave] = other;
+    __syncthreads();
+    if (threadIdx.x < Q * TG)
+        {
+        const double* w = wave_d[threadIdx.x];
+        td[(size_t)threadIdx.x * n_tiles + tile] = (w[0] + w[1]) + (w[2] + w[3]);
+        }
+    else if (threadIdx.x >= 64 && threadIdx.x < 64 + TG)
+        {
+        const uint32_t t = threadIdx.x - 64;
+        const double* w = wave_d[Q * TG + t];
+        const uint32_t* u = wave_u[2 * TG + t];
+        double m = w[0];
+        uint32_t k = u[0];
+#pragma unroll
+        for (int i = 1; i < STATS_WAVES; i++)
+            disp_pair(m, k, w[i], u[i]);
+        td[(size_t)(Q * TG + t) * n_tiles + tile] = m;
+        tu[(size_t)(2 * TG + t) * n_tiles + tile] = k;
+        }
+    else if (threadIdx.x >= 128 && threadIdx.x < 128 + 2 * TG + 1)
+        {
+        const uint32_t c = threadIdx.x - 128 < 2 * TG ? threadIdx.x - 128 : 3 * TG; // entries and bad per type, then other
+        const uint32_t* u = wave_u[c];
+        tu[(size_t)c * n_tiles + tile] = u[0] + u[1] + u[2] + u[3];
+        }
+    }
+
+// One workgroup per column: the first 4 * TG columns are the sums (stats_final_kernel's walk t, t + 256, ... per lane,
+// then the block tree), the next TG the largest values with their entries (the pair rule; the order is free), the last
+// 2 * TG + 1 the counters.  out: see DISP_WORD_*; the flag word is handed over and cleared as there.
+__global__ __launch_bounds__(SEL_THREADS) void displacement_final_kernel(const double* __restrict__ td,
+                                                                         const uint32_t* __restrict__ tu, uint32_t n_tiles,
+                                                                         uint32_t TG, uint32_t* flag_dev,
+                                                                         uint64_t* __restrict__ out)
+    {
+#pragma clang fp contract(off)
+    __shared__ double wave_d[STATS_WAVES];
+    __shared__ uint64_t wave_u[STATS_WAVES];
+    const uint32_t b = blockIdx.x;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t n_sums = DISP_Q * TG, n_d = n_sums + TG;
+    double* values = (double*)out;
+    if (b < n_sums)
+        {
+        const double* t_sum = td + (size_t)b * n_tiles;
+        double sum = 0.0;
+#pragma unroll 8
+        for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
+            sum = sum + t_sum[t];
+        sum = stats_wave_sum(sum);
+        if (lane == 0)
+            wave_d[wave] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            values[b] = (wave_d[0] + wave_d[1]) + (wave_d[2] + wave_d[3]);
+        }
+    else if (b < n_d)
+        {
+        const double* t_max = td + (size_t)b * n_tiles;
+        const uint32_t* t_at = tu + (size_t)(2 * TG + (b - n_sums)) * n_tiles;
+        double mx = -__builtin_huge_val();
+        uint32_t at = DISP_NO_ENTRY;
+#pragma unroll 8
+        for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
+            disp_pair(mx, at, t_max[t], t_at[t]);
+        disp_wave_pair(mx, at);
+        if (lane == 0)
+            {
+            wave_d[wave] = mx;
+            wave_u[wave] = at;
+            }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            {
+            for (int i = 1; i < STATS_WAVES; i++)
+                disp_pair(mx, at, wave_d[i], (uint32_t)wave_u[i]);
+            values[b] = mx;
+            out[DISP_WORD_ENTRIES + (b - n_sums)] = at;
+            }
+        }
+    else
+        {
+        const uint32_t j = b - n_d; // entries and bad per type, then other
+        const uint32_t* t_cnt = tu + (size_t)(j < 2 * TG ? j : 3 * TG) * n_tiles;
+        uint64_t count = 0;
+#pragma unroll 8
+        for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
+            count += t_cnt[t];
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1)
+            count += (uint64_t)__shfl_xor((unsigned long long)count, h, 64);
+        if (lane == 0)
+            wave_u[wave] = count;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            out[DISP_WORD_COUNTERS + j] = wave_u[0] + wave_u[1] + wave_u[2] + wave_u[3];
+        }
+    if (b == 0 && threadIdx.x == 0)
+        {
+        out[DISP_WORD_FLAG] = *flag_dev;
+        *flag_dev = 0u;
+        }
+    }
+
 // ------------------------------------------------------------------ host side
 namespace
     {
 // Grow-only, per device (g_stats_lock held): the result words, the device flag word and the table of the tiles'
 // partials in one allocation; the pinned twin of the result words; the pinned, device-mapped flag word.
-// the head of the allocation: the result words of either reduction (chunk statistics, conservation sums), then the flag word
+// the head of the allocation: the result words of any of the reductions (chunk statistics, conservation sums, frame
+// displacements, whose 34 words fit as it is), then the flag word
 constexpr size_t STATS_HEAD_WORDS = (STATS_RESULT_WORDS > MOMENTS_RESULT_WORDS ? STATS_RESULT_WORDS : MOMENTS_RESULT_WORDS);
+static_assert(DISPLACEMENT_RESULT_WORDS <= STATS_HEAD_WORDS, "the displacements' result words fit the head as it is");
 constexpr size_t STATS_HEAD_BYTES = (STATS_HEAD_WORDS + 1) * sizeof(uint64_t);
 // (growth policy, head and bytes per tile: restated by tests/test_gpu_scratch_reuse.py)
 Scratch g_stats_scratch("chunk statistics", 1.25, 1u << 16, STATS_HEAD_WORDS * sizeof(uint64_t), sizeof(uint64_t));
@@ -715,6 +1064,90 @@ int launch_frame_moments(const MomentsArgs& m, uint64_t* out_counts, double* out
             out_sums[MOMENTS_QUANTITIES * t + q] = sums[q * TG + t];
         }
     out_counts[2 * m.n_types] = counters[2 * TG];
+    return PGSD_SUCCESS;
+    }
+
+namespace
+    {
+template<bool G, bool F64, int TG>
+void displacement_tile_launch(const DisplacementArgs& d, uint32_t n_tiles, double* td, uint32_t* tu, uint32_t* flag_dev,
+                              uint32_t* flag_host, hipStream_t stream)
+    {
+    hipLaunchKernelGGL((displacement_tile_kernel<G, F64, TG>), dim3(n_tiles), dim3(SEL_THREADS), 0, stream, d, n_tiles, td, tu,
+                       flag_dev, flag_host);
+    }
+
+template<bool G, bool F64>
+void displacement_tile_by_group(const DisplacementArgs& d, uint32_t TG, uint32_t n_tiles, double* td, uint32_t* tu,
+                                uint32_t* flag_dev, uint32_t* flag_host, hipStream_t stream)
+    {
+    switch (TG)
+        {
+        case 1: return displacement_tile_launch<G, F64, 1>(d, n_tiles, td, tu, flag_dev, flag_host, stream);
+        case 2: return displacement_tile_launch<G, F64, 2>(d, n_tiles, td, tu, flag_dev, flag_host, stream);
+        default: return displacement_tile_launch<G, F64, 4>(d, n_tiles, td, tu, flag_dev, flag_host, stream);
+        }
+    }
+    } // namespace
+
+int launch_frame_displacements(const DisplacementArgs& d, uint64_t* out_counts, double* out_values, hipStream_t stream,
+                               std::string* err)
+    {
+    static const char* outside_msg
+        = "frame displacements: an entry of the row list lies outside the chunks (nothing was computed)";
+    if (!out_counts || !out_values || d.n_types < 1 || d.n_types > DISPLACEMENT_MAX_TYPES || (!d.chunk[4] && d.n_types != 1))
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "frame displacements: 1 to 4 types, one without a typeid chunk");
+    if (d.minimum_image && (d.chunk[1] || d.chunk[3]))
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
+                           "frame displacements: the minimum image is taken without image chunks");
+    if (d.dimensions != 2 && d.dimensions != 3)
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "frame displacements: dimensions is 2 or 3");
+    const uint64_t n = d.rows ? d.n : d.N;
+    if (n >= (1ull << 32) || d.N >= (1ull << 32))
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "frame displacements: 2^32 rows or entries and more are not indexed");
+    if (n == 0)
+        {
+        displacements_of_nothing(d.n_types, out_counts, out_values);
+        return PGSD_SUCCESS;
+        }
+    if (d.N == 0)
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, outside_msg);
+    if (!d.chunk[0] || !d.chunk[2])
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const uint32_t TG = d.n_types == 3 ? 4u : d.n_types; // the kernels' group sizes: 1, 2, 4
+    const uint32_t n_d = DISPLACEMENT_VALUES * TG, n_u = 3 * TG + 1;
+    const uint32_t n_tiles = (uint32_t)((n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK);
+    const size_t td_bytes = (size_t)n_d * n_tiles * sizeof(double), tu_bytes = (size_t)n_u * n_tiles * sizeof(uint32_t);
+    StatsLaunch sc(td_bytes, tu_bytes, stream, err);
+    if (sc.scope.rc() != PGSD_SUCCESS)
+        return sc.scope.rc();
+    if (d.rows)
+        d.f64 ? displacement_tile_by_group<true, true>(d, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream)
+              : displacement_tile_by_group<true, false>(d, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
+    else
+        d.f64 ? displacement_tile_by_group<false, true>(d, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream)
+              : displacement_tile_by_group<false, false>(d, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
+    // one workgroup per sum and per largest value, and per counter that is summed (entries, bad, other)
+    hipLaunchKernelGGL(displacement_final_kernel, dim3(n_d + 2 * TG + 1), dim3(SEL_THREADS), 0, stream, sc.td, sc.tu, n_tiles,
+                       TG, sc.flag_dev, sc.result);
+    bool outside = false;
+    const int rc = sc.finish("frame displacements", DISPLACEMENT_RESULT_WORDS, DISP_WORD_FLAG, &outside);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (outside)
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, outside_msg);
+    const double* values = (const double*)sc.host;
+    const uint64_t* counters = sc.host + DISP_WORD_COUNTERS;
+    const uint64_t* entries = sc.host + DISP_WORD_ENTRIES;
+    for (uint32_t t = 0; t < d.n_types; t++)
+        {
+        out_counts[3 * t + 0] = counters[t];
+        out_counts[3 * t + 1] = counters[TG + t];
+        out_counts[3 * t + 2] = entries[t] == DISP_NO_ENTRY ? UINT64_MAX : entries[t];
+        for (uint32_t q = 0; q < DISPLACEMENT_VALUES; q++)
+            out_values[DISPLACEMENT_VALUES * t + q] = values[q * TG + t];
+        }
+    out_counts[3 * d.n_types] = counters[2 * TG];
     return PGSD_SUCCESS;
     }
     } // namespace pgsd_amd

@@ -10,7 +10,12 @@
            line per frame with the number of non-finite entries and the largest speed: the blow-up scan;
            ``--moments`` adds per particle type the count, mass, momentum, kinetic and internal energy and centre of
            mass of one frame and a total line (``--types``), ``--moments --all-frames`` one line per frame with the
-           totals: the conservation table (``pgsd.hoomd.frame_moments`` on the host: no GPU).
+           totals: the conservation table (``pgsd.hoomd.frame_moments`` on the host: no GPU);
+           ``--displacement`` adds per particle type the count, mean drift, mean-squared displacement and the largest
+           move with its row between frame ``--origin`` and the frame, unwrapped through the image flags
+           (``--minimum-image``: the wrapped positions' difference folded into the box instead; ``--types``), and a
+           total line; ``--displacement --all-frames`` one line per frame against the origin: the MSD curve
+           (``pgsd.hoomd.frame_displacements`` on the host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -75,10 +80,47 @@ def _cmd_info(args):
         _print_stats(args, frame)
     if args.moments:
         _print_moments(args, frame)
+    if args.displacement:
+        _print_displacement(args, frame)
 
 
 def _vector_text(v):
     return '(' + ', '.join(repr(float(c)) for c in v) + ')'
+
+
+def _displacement_text(part, k):
+    return ("count %d  bad %d  mean drift %s  msd %r  largest distance %r  row %d"
+            % (part.count[k], part.bad[k], _vector_text(part.mean_drift[k]), float(part.msd[k]),
+               float(part.largest_distance[k]), part.largest_entry[k]))
+
+
+def _print_displacement(args, frame):
+    """``info --displacement``: `pgsd.hoomd.frame_displacements` between the origin and one frame per type, or the
+    totals of every frame against the origin in one line each, on the host.  With ``--types`` the row of the largest
+    move is a position in the selection's ascending row list."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    options = dict(where=where, minimum_image=args.minimum_image, images=not args.minimum_image)
+    with hoomd.open(args.file, 'r') as traj:
+        origin = args.origin if args.origin >= 0 else len(traj) + args.origin
+        if not 0 <= origin < len(traj):
+            raise ValueError("frame %d is not in the file" % args.origin)
+        note = "%s%s" % (" (types %s)" % args.types if args.types else "", " (minimum image)" if args.minimum_image else "")
+        if args.all_frames:
+            print("displacements per frame against frame %d%s:" % (origin, note))
+            for i in range(len(traj)):
+                step = int(traj[i].configuration.step)
+                t = traj.frame_displacements(i, origin, **options).total()
+                print("  frame %-6d step %-10d %s" % (i, step, _displacement_text(t, 0)))
+            return
+        m = traj.frame_displacements(frame, origin, **options)
+        names = list(traj[frame].particles.types)
+    print("displacements of frame %d against frame %d%s:" % (frame, origin, note))
+    total = m.total()
+    for name, part, k in [(names[k], m, k) for k in range(len(names))] + [('total', total, 0)]:
+        print("  %-12s %s" % (name, _displacement_text(part, k)))
+    if m.other:
+        print("  %d particles of no listed type" % m.other)
 
 
 def _print_moments(args, frame):
@@ -201,12 +243,19 @@ def main(argv=None):
     p.add_argument('--fields', type=str, default=None, metavar='NAME[,NAME...]',
                    help="the per-particle fields of --stats (default: position,velocity,density,pressure,energy)")
     p.add_argument('--types', type=str, default=None, metavar='NAME[,NAME...]',
-                   help="--stats and --moments over the particles of these types only")
+                   help="--stats, --moments and --displacement over the particles of these types only")
     p.add_argument('--all-frames', action='store_true',
                    help="with --stats: one line per frame with the non-finite entries and the largest speed; "
-                        "with --moments: one line per frame with the totals")
+                        "with --moments: one line per frame with the totals; "
+                        "with --displacement: one line per frame against the origin")
     p.add_argument('--moments', action='store_true',
                    help="print count, mass, momentum, kinetic and internal energy and centre of mass per particle type")
+    p.add_argument('--displacement', action='store_true',
+                   help="print count, mean drift, mean-squared displacement and the largest move per particle type "
+                        "between the origin and the frame")
+    p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")
+    p.add_argument('--minimum-image', action='store_true',
+                   help="--displacement of the wrapped positions, folded into the box, instead of through the image flags")
     p.set_defaults(func=_cmd_info)
     p = sub.add_parser('vtu', help="convert the frames to VTK .vtu files")
     p.add_argument('file', type=str)

@@ -1787,6 +1787,101 @@ cdef class PGSDFile:
         counts = counts.astype(numpy.int64)
         return _hoomd.Moments.from_sums(counts[0:2 * T:2].copy(), counts[1:2 * T:2].copy(), int(counts[2 * T]), sums)
 
+    def frame_displacements_device(self, chunks, vectors_a, vectors_b, minimum_image=False, dimensions=3, type0=0,
+                                   n_types=1, rows=None, n=None, out=None):
+        """Drift, squared displacement and the largest move between two frames per particle type, reduced on the GPU in
+        one pass over up to five chunks.
+
+        Args:
+            chunks: five entries in the order position a, image a, position b, image b, typeid, each ``(frame, name)``
+                -- any chunk of the file, so that an elided chunk can come from frame 0 -- or ``None``: stored nowhere
+                (the images: ``(0, 0, 0)`` in every row; the typeid: one group, ``n_types`` is 1).  The positions are
+                N x 3 float32 or float64, both the same, the images N x 3 int32, the typeid N x 1 uint32 or int32;
+                every chunk has the same N.
+            vectors_a, vectors_b: :func:`pgsd.hoomd.box_vectors` of each frame's box.
+            minimum_image (bool): fold the difference into frame b's box; allowed without image chunks only.
+            dimensions (int): 2 leaves z unfolded.
+            type0, n_types: the types ``[type0, type0 + n_types)``, ``1 <= n_types <= 4``.
+            rows: ``None`` for all rows, or 32-bit row indices in GPU memory, any order, repeats allowed.
+            n (int): the number of entries of ``rows`` to take (default: all of them).
+            out: ``None``, or GPU memory of at least ``entries x 3`` float64 (a :class:`DeviceBuffer` or a tensor): entry
+                ``k``'s displacement is stored at ``out[k]``.
+
+        Returns:
+            A :class:`pgsd.hoomd.Displacements`.  Exactly :func:`pgsd.hoomd.particle_displacements`, the sums included:
+            their order is part of the definition.  The chunks are staged whole unless an earlier call left them staged
+            (two chunks that are one stored chunk are staged once); the staged rows are kept until the next
+            :meth:`wait_read`.  An entry outside the chunks raises ValueError.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entries[5]
+        cdef const C.pgsd_index_entry* given[5]
+        chunks = list(chunks)
+        if len(chunks) != 5:
+            raise ValueError("frame_displacements_device: chunks holds position a, image a, position b, image b, typeid "
+                             "(the images and the typeid may be None)")
+        if chunks[0] is None or chunks[2] is None:
+            raise ValueError("frame_displacements_device: both positions are chunks of the file")
+        cdef int i
+        for i in range(5):
+            given[i] = NULL
+            if chunks[i] is not None:
+                frame, name = chunks[i]
+                self._entry(frame, name, &entries[i])
+                given[i] = &entries[i]
+        self._check_open()
+        c_va = numpy.ascontiguousarray(numpy.asarray(vectors_a, dtype=numpy.float64).reshape(-1))
+        c_vb = numpy.ascontiguousarray(numpy.asarray(vectors_b, dtype=numpy.float64).reshape(-1))
+        if c_va.shape[0] != 6 or c_vb.shape[0] != 6:
+            raise ValueError("frame_displacements_device: box vectors hold six values (pgsd.hoomd.box_vectors)")
+        if not 0 <= int(type0) < (1 << 32) or not 0 <= int(n_types) < (1 << 32) or not 0 <= int(dimensions) < (1 << 32):
+            raise ValueError("frame_displacements_device: a call takes 1 to 4 types from a type id on, in 2 or 3 dimensions")
+        cdef uintptr_t c_rows = 0, c_out = 0
+        cdef uint32_t c_empty = 0
+        count = int(entries[0].N)
+        if rows is not None:
+            p_rows, n_rows = _index_rows(rows)
+            count = n_rows if n is None else int(n)
+            if count >= (1 << 32):
+                raise ValueError("frame_displacements_device: a row list holds fewer than 2^32 entries")
+            if count < 0 or count > n_rows:
+                raise ValueError("frame_displacements_device: rows holds fewer entries than n")
+            c_rows = p_rows
+            if count == 0:
+                c_rows = <uintptr_t>&c_empty      # an empty list is still a list, but may have no address
+        elif n is not None:
+            raise ValueError("frame_displacements_device: n goes with rows")
+        if out is not None:
+            p_out, out_bytes = _device_memory(out, "out")
+            if out_bytes < count * 24:
+                raise ValueError("frame_displacements_device: out holds fewer than entries x 3 float64 values")
+            c_out = p_out
+        T = int(n_types) if 1 <= int(n_types) <= 4 else 1         # (the library refuses the rest)
+        counts = numpy.zeros(3 * T + 1, dtype=numpy.uint64)
+        values = numpy.zeros((T, 5), dtype=numpy.float64)
+        if (rows is not None or out is not None) and not self._explicit_stream:
+            self._sync_source_stream()      # the reduction is ordered behind this stream's use of `rows` and `out`
+        cdef uintptr_t c_counts = counts.ctypes.data, c_values = values.ctypes.data
+        cdef uintptr_t c_pva = c_va.ctypes.data, c_pvb = c_vb.ctypes.data
+        cdef uint64_t c_n = count if rows is not None else 0
+        cdef uint32_t c_type0 = int(type0), c_ntypes = int(n_types), c_dims = int(dimensions)
+        cdef uint32_t c_flags = 1 if minimum_image else 0
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_frame_displacements_device(&self._handle, given[0], given[1], given[2], given[3], given[4],
+                                                       <const double*>c_pva, <const double*>c_pvb, c_flags, c_dims, c_type0,
+                                                       c_ntypes, <const uint32_t*>c_rows, c_n, <double*>c_out,
+                                                       <uint64_t*>c_counts, <double*>c_values)
+            err = errno
+        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+            msg = C.pgsd_last_error_string()
+            raise ValueError("frame_displacements_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else "refused"))
+        _raise_on_error(retval, self._name, err)
+        entry = counts[2:3 * T:3].astype(numpy.int64)            # (UINT64_MAX, no entry, becomes -1)
+        counts = counts.astype(numpy.int64)
+        return _hoomd.Displacements.from_sums(counts[0:3 * T:3].copy(), counts[1:3 * T:3].copy(), entry, int(counts[3 * T]),
+                                              values)
+
     def select_halo_device(self, frame, name, box, domain, ghost, dimensions=3):
         """A domain plus the ghost layer its neighbours reach, selected on the GPU from one position chunk.
 

@@ -1259,6 +1259,345 @@ def frame_moments(frame_or_arrays, by_type=True, centre=True, where=None, types=
     return Moments.concatenate(parts, n)
 
 
+# ---- frame displacements: the definition the GPU reduction (`pgsd.fl.PGSDFile.frame_displacements_device`) equals exactly
+_DISPLACEMENT_VALUES = 5    # drift x 3, square, largest
+_DISPLACEMENT_MAX_TYPES = 4
+
+
+def box_vectors(box):
+    """The six float64 values ``(Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz)`` of a box ``(Lx, Ly, Lz, xy, xz, yz)``: each value is
+    converted to float64 first, then one float64 product each.  The unwrap and the fold of `particle_displacements`
+    (and of the GPU kernel) take these as given, so the products are rounded once, here."""
+    b = numpy.asarray(box, dtype=numpy.float64).reshape(-1)
+    if b.shape[0] != 6:
+        raise ValueError("a box holds six values (Lx, Ly, Lz, xy, xz, yz)")
+    with numpy.errstate(over='ignore', invalid='ignore'):
+        return numpy.array([b[0], b[1], b[2], b[3] * b[1], b[4] * b[2], b[5] * b[2]], dtype=numpy.float64)
+
+
+class Displacements(object):
+    """Displacements between two frames per particle type (`particle_displacements`): arrays of one entry (or one row)
+    per type.
+
+    Attributes:
+        count, bad (int64, T): the entries of the type, and those of them at which a component of the displacement or
+            its squared length is not finite.
+        largest_entry (int64, T): the smallest entry that attains ``largest`` (a position in the row list when there is
+            one, else a row); ``-1`` when the type has no entry whose squared length is a number.
+        other (int): the entries of no type of the call.
+        drift (float64, T x 3): ``sum d``.  square (float64, T): ``sum |d|^2``.
+        largest (float64, T): the largest ``|d|^2`` (infinities included, NaN not); ``-inf`` when there is none.
+        msd, mean_drift (properties): ``square / (count - bad)`` and ``drift / (count - bad)``, NaN where that is 0.
+        largest_distance (property): ``sqrt(largest)``.
+
+    Both sums are over the finite values only and in `column_stats`' order.
+    """
+
+    __slots__ = ('count', 'bad', 'largest_entry', 'other', 'drift', 'square', 'largest')
+
+    def __init__(self, count, bad, largest_entry, other, drift, square, largest):
+        self.count = numpy.asarray(count, dtype=numpy.int64).reshape(-1)
+        T = self.count.shape[0]
+        self.bad = numpy.asarray(bad, dtype=numpy.int64).reshape(T)
+        self.largest_entry = numpy.asarray(largest_entry, dtype=numpy.int64).reshape(T)
+        self.other = int(other)
+        self.drift = numpy.asarray(drift, dtype=numpy.float64).reshape(T, 3)
+        self.square = numpy.asarray(square, dtype=numpy.float64).reshape(T)
+        self.largest = numpy.asarray(largest, dtype=numpy.float64).reshape(T)
+
+    @classmethod
+    def from_sums(cls, count, bad, largest_entry, other, sums):
+        """From the ``T x 5`` table of values: drift x 3, square, largest."""
+        s = numpy.asarray(sums, dtype=numpy.float64).reshape(-1, _DISPLACEMENT_VALUES)
+        return cls(count, bad, largest_entry, other, s[:, 0:3].copy(), s[:, 3].copy(), s[:, 4].copy())
+
+    @property
+    def sums(self):
+        """The ``T x 5`` table of values: drift x 3, square, largest."""
+        return numpy.concatenate([self.drift, self.square[:, None], self.largest[:, None]], axis=1)
+
+    def _per_entry(self, a):
+        good = (self.count - self.bad).astype(numpy.float64)
+        good = good if a.ndim == 1 else good[:, None]
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(good != 0, a / good, numpy.nan)
+
+    @property
+    def msd(self):
+        return self._per_entry(self.square)
+
+    @property
+    def mean_drift(self):
+        return self._per_entry(self.drift)
+
+    @property
+    def largest_distance(self):
+        with numpy.errstate(invalid='ignore'):
+            return numpy.sqrt(self.largest)
+
+    def total(self):
+        """All types as one: a `Displacements` of one row whose sums are the types' added in ascending type order by
+        plain float64 additions, with the largest ``largest`` (on a tie the smaller entry); ``other`` stays."""
+        s = self.sums
+        acc = numpy.zeros(4, dtype=numpy.float64)
+        best, entry = -numpy.inf, -1
+        for t in range(s.shape[0]):
+            acc = s[t, 0:4].copy() if t == 0 else acc + s[t, 0:4]
+            e = int(self.largest_entry[t])
+            if e >= 0 and (entry < 0 or s[t, 4] > best or (s[t, 4] == best and e < entry)):
+                best, entry = s[t, 4], e
+        return Displacements.from_sums([int(self.count.sum())], [int(self.bad.sum())], [entry], self.other,
+                                       numpy.concatenate([acc, [best]]))
+
+    @staticmethod
+    def concatenate(parts, n_entries):
+        """The `Displacements` of consecutive groups of types (each over the same ``n_entries`` entries) as one."""
+        count = numpy.concatenate([p.count for p in parts])
+        return Displacements.from_sums(count, numpy.concatenate([p.bad for p in parts]),
+                                       numpy.concatenate([p.largest_entry for p in parts]),
+                                       int(n_entries) - int(count.sum()), numpy.concatenate([p.sums for p in parts], axis=0))
+
+    def __repr__(self):
+        return "Displacements(%s)" % ', '.join(
+            "%s=%r" % (name, getattr(self, name).tolist() if name != 'other' else self.other) for name in self.__slots__)
+
+
+def _displacement_inputs(position_a, position_b, image_a, image_b, vectors_a, vectors_b, minimum_image, dimensions):
+    """The inputs of `displacement_vectors`, checked: positions, images (or None), vectors (or None)."""
+    pa, pb = numpy.asarray(position_a), numpy.asarray(position_b)
+    for p in (pa, pb):
+        if p.dtype.type not in (numpy.float32, numpy.float64):
+            raise ValueError("displacements take float32 or float64 positions: %s" % p.dtype)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("a position is an N x 3 array")
+    if pa.dtype != pb.dtype:
+        raise ValueError("displacements take positions of one float type, not float32 and float64 mixed")
+    if pa.shape[0] != pb.shape[0]:
+        raise ValueError("the frames differ in their number of rows (%d and %d)" % (pa.shape[0], pb.shape[0]))
+    images = []
+    for im in (image_a, image_b):
+        if im is not None:
+            im = numpy.asarray(im)
+            if im.dtype.type is not numpy.int32:
+                raise ValueError("an image holds int32 elements: %s" % im.dtype)
+            if im.ndim != 2 or im.shape[1] != 3:
+                raise ValueError("an image is an N x 3 array")
+            if im.shape[0] != pa.shape[0]:
+                raise ValueError("the arrays differ in their number of rows (an image has %d)" % im.shape[0])
+        images.append(im)
+    if dimensions not in (2, 3):
+        raise ValueError("dimensions is 2 or 3: %r" % (dimensions,))
+    if minimum_image and (images[0] is not None or images[1] is not None):
+        raise ValueError("the minimum image is taken without image flags: pass no image array")
+    vectors = []
+    for v, needed in ((vectors_a, images[0] is not None), (vectors_b, images[1] is not None or minimum_image)):
+        if v is None:
+            if needed:
+                raise ValueError("an image array and the minimum image need the frame's box vectors (box_vectors)")
+        else:
+            v = numpy.asarray(v, dtype=numpy.float64).reshape(-1)
+            if v.shape[0] != 6:
+                raise ValueError("box vectors hold six values (box_vectors)")
+        vectors.append(v)
+    return pa, pb, images[0], images[1], vectors[0], vectors[1]
+
+
+def _unwrapped(x, image, v):
+    """The three float64 columns of ``x`` unwrapped through ``image`` and the box vectors ``v``."""
+    x = [x[:, a].astype(numpy.float64) for a in range(3)]
+    if image is None:
+        return x
+    i = [image[:, a].astype(numpy.float64) for a in range(3)]
+    return [x[0] + ((i[0] * v[0] + i[1] * v[3]) + i[2] * v[4]),
+            x[1] + (i[1] * v[1] + i[2] * v[5]),
+            x[2] + i[2] * v[2]]
+
+
+def displacement_vectors(position_a, position_b, image_a=None, image_b=None, vectors_a=None, vectors_b=None,
+                         minimum_image=False, dimensions=3, rows=None):
+    """The per-entry displacement ``d`` of `particle_displacements` as an ``n x 3`` float64 array: what the GPU pass
+    stores per entry when it is given an output (``return_rows``), bit for bit."""
+    pa, pb, ia, ib, va, vb = _displacement_inputs(position_a, position_b, image_a, image_b, vectors_a, vectors_b,
+                                                  minimum_image, dimensions)
+    if rows is not None:
+        rows = _list_rows(rows, pa.shape[0])
+        pa, pb = pa[rows], pb[rows]
+        ia, ib = None if ia is None else ia[rows], None if ib is None else ib[rows]
+    with numpy.errstate(over='ignore', invalid='ignore', under='ignore', divide='ignore'):
+        ua, ub = _unwrapped(pa, ia, va), _unwrapped(pb, ib, vb)
+        d = [ub[a] - ua[a] for a in range(3)]
+        if minimum_image:
+            Lx, Ly, Lz, xyLy, xzLz, yzLz = (numpy.float64(c) for c in vb)
+            if dimensions == 3:
+                n = numpy.rint(d[2] / Lz)
+                d[2] = d[2] - n * Lz
+                d[1] = d[1] - n * yzLz
+                d[0] = d[0] - n * xzLz
+            n = numpy.rint(d[1] / Ly)
+            d[1] = d[1] - n * Ly
+            d[0] = d[0] - n * xyLy
+            n = numpy.rint(d[0] / Lx)
+            d[0] = d[0] - n * Lx
+    return numpy.stack(d, axis=1)
+
+
+def particle_displacements(position_a, position_b, image_a=None, image_b=None, vectors_a=None, vectors_b=None,
+                           minimum_image=False, dimensions=3, typeid=None, type0=0, n_types=1, rows=None):
+    """Drift, squared displacement and the largest move between two frames per particle type: the definition the GPU
+    reduction (`pgsd.fl.PGSDFile.frame_displacements_device`, `HOOMDTrajectory.frame_displacements_device`) equals
+    exactly, the sums bit for bit.  Row ``k`` of frame a is the particle of row ``k`` of frame b.
+
+    Args:
+        position_a, position_b (N x 3): float32 or float64, both the same.
+        image_a, image_b (N x 3): int32, or ``None``: the schema's default ``(0, 0, 0)`` in every row.
+        vectors_a, vectors_b: `box_vectors` of each frame's box (needed with an image array; ``vectors_b`` with
+            ``minimum_image``); the two frames may have different boxes.
+        minimum_image (bool): fold the difference into frame b's box (HOOMD's ``minImage``: z, then y, then x; z not in
+            two dimensions); allowed only without image arrays.
+        typeid (N): uint32 or int32, or ``None``: one group, ``n_types`` is 1.
+        type0, n_types, rows: as `particle_moments` takes them.
+
+    Every element is converted to float64 first; no fused multiply-add, and the association is fixed.  With ``i`` the
+    image as float64 and ``(Lx, Ly, Lz, xyLy, xzLz, yzLz)`` the frame's vectors::
+
+        u[0] = x[0] + ((i[0]*Lx + i[1]*xyLy) + i[2]*xzLz)
+        u[1] = x[1] + (i[1]*Ly + i[2]*yzLz)
+        u[2] = x[2] + i[2]*Lz
+
+    and ``u = x`` without an image array (no product is formed: an infinite box value creates no NaN).
+    ``d = u_b - u_a``; with ``minimum_image`` and frame b's vectors ``n = rint(d[2] / Lz)``, ``d[2] -= n*Lz``,
+    ``d[1] -= n*yzLz``, ``d[0] -= n*xzLz`` (three dimensions only), ``n = rint(d[1] / Ly)``, ``d[1] -= n*Ly``,
+    ``d[0] -= n*xyLy``, ``n = rint(d[0] / Lx)``, ``d[0] -= n*Lx``; ``rint`` rounds half to even and every ``-=`` is one
+    product and one subtraction.  ``s = (d[0]*d[0] + d[1]*d[1]) + d[2]*d[2]``.
+
+    Per type ``t`` the result (`Displacements`) holds the entries of the type, those of them where a ``d[a]`` or ``s``
+    is not finite, the sums of ``d[a]`` and of ``s`` **in `column_stats`' order** over the sequence whose entry ``k`` is
+    the value where ``typeid[k] == t`` and the value is finite and ``+0.0`` otherwise, the maximum of ``s`` over the
+    entries of the type where ``s`` is no NaN (``-inf`` when there is none) and the smallest entry that attains it
+    (``-1``).  ``other`` counts the entries of no type of the range; a negative int32 id is one.
+
+    ValueError: other element types, mixed float types, wrong shapes or lengths, ``minimum_image`` with an image array,
+    an image array or ``minimum_image`` without vectors, ``dimensions`` not 2 or 3, ``n_types`` of 0 or above 4, no
+    typeid with ``n_types != 1``, what `column_stats` refuses for ``rows``.
+    """
+    if not isinstance(n_types, (int, numpy.integer)) or not 1 <= n_types <= _DISPLACEMENT_MAX_TYPES:
+        raise ValueError("a call takes 1 to 4 types: %r" % (n_types,))
+    if not isinstance(type0, (int, numpy.integer)) or not 0 <= type0 < 2 ** 32:
+        raise ValueError("type0 is a type id: %r" % (type0,))
+    d = displacement_vectors(position_a, position_b, image_a, image_b, vectors_a, vectors_b, minimum_image, dimensions,
+                             rows)
+    N = numpy.asarray(position_a).shape[0]
+    if typeid is not None:
+        typeid = numpy.asarray(typeid)
+        if typeid.dtype.type not in (numpy.uint32, numpy.int32):
+            raise ValueError("typeid holds uint32 or int32 elements: %s" % typeid.dtype)
+        if typeid.ndim != 1:
+            raise ValueError("typeid is an array of N values")
+        if typeid.shape[0] != N:
+            raise ValueError("the arrays differ in their number of rows (typeid has %d)" % typeid.shape[0])
+    elif n_types != 1:
+        raise ValueError("without a typeid there is one group: n_types must be 1")
+    if rows is not None:
+        rows = _list_rows(rows, N)
+    n = d.shape[0]
+    with numpy.errstate(over='ignore', invalid='ignore', under='ignore'):
+        s = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    values = [d[:, 0], d[:, 1], d[:, 2], s]
+    finite = [numpy.isfinite(q) for q in values]
+    all_finite = numpy.logical_and.reduce(finite) if n else numpy.zeros(0, dtype=bool)
+    if typeid is None:
+        group = numpy.zeros(n, dtype=numpy.int64)
+    else:
+        group = (typeid if rows is None else typeid[rows]).astype(numpy.int64) - int(type0)
+    count, bad = numpy.zeros(n_types, numpy.int64), numpy.zeros(n_types, numpy.int64)
+    entry = numpy.full(n_types, -1, numpy.int64)
+    sums = numpy.zeros((n_types, _DISPLACEMENT_VALUES), dtype=numpy.float64)
+    sums[:, 4] = -numpy.inf
+    for t in range(n_types):
+        mine = group == t
+        count[t], bad[t] = mine.sum(), (mine & ~all_finite).sum()
+        for q in range(4):
+            sums[t, q] = _ordered_sum(numpy.where(mine & finite[q], values[q], 0.0))
+        taking = numpy.flatnonzero(mine & ~numpy.isnan(s))
+        if taking.size:
+            sums[t, 4] = s[taking].max()
+            entry[t] = taking[numpy.argmax(s[taking] == sums[t, 4])]
+    return Displacements.from_sums(count, bad, entry, n - int(count.sum()), sums)
+
+
+def _displacement_frame(frame_or_arrays, box):
+    """``(arrays, types, box, dimensions, N)`` of one frame of `frame_displacements`."""
+    if hasattr(frame_or_arrays, 'particles'):
+        frame = frame_or_arrays
+        dims = None if frame.configuration.dimensions is None else int(frame.configuration.dimensions)
+        return (_particle_arrays(frame.particles), frame.particles.types,
+                frame.configuration.box if box is None else box, dims, int(frame.particles.N))
+    arrays = dict((k, v) for k, v in frame_or_arrays.items() if v is not None)
+    if 'position' not in arrays:
+        raise ValueError("arrays holds no 'position'")
+    return arrays, None, box, None, len(arrays['position'])
+
+
+def frame_displacements(frame_a, frame_b, by_type=True, images=True, minimum_image=False, where=None, types=None,
+                        domain=None, box=None, dimensions=3):
+    """`particle_displacements` from ``frame_a`` to ``frame_b`` over a selection: the host twin of
+    `HOOMDTrajectory.frame_displacements_device`, which equals it exactly.
+
+    Args:
+        frame_a, frame_b: two `Frame` objects (``types``, the boxes and ``dimensions`` default to their own, frame b's
+            where there is one of them) or two dicts of attribute name -> host array holding ``position`` and, where
+            stored, ``image`` and ``typeid``.
+        by_type (bool): one row per type of ``types``, computed in groups of four consecutive types, by frame b's
+            ``typeid``; ``False``: one row for all entries.
+        images (bool): ``False`` passes no image array: the difference of the wrapped positions.
+        minimum_image (bool): fold the difference into frame b's box; needs ``images=False`` or frames without images.
+        where, domain: the selection, as `frame_moments` takes it, evaluated on **frame b**.
+        box: one box for both frames, or a pair ``(box_a, box_b)``; needed for dicts with images, the minimum image or
+            a domain.
+
+    ValueError: frames of different N; what `where_rows`, `domain_rows` and `particle_displacements` refuse;
+    ``by_type`` without ``types``; a domain without box.
+    """
+    if box is not None and len(box) == 2 and numpy.ndim(box[0]) == 1:
+        box_a, box_b = box
+    else:
+        box_a = box_b = box
+    arrays_a, _, box_a, _, N_a = _displacement_frame(frame_a, box_a)
+    arrays_b, types_b, box_b, dims_b, N_b = _displacement_frame(frame_b, box_b)
+    if N_a != N_b:
+        raise ValueError("the frames differ in their number of particles (%d and %d)" % (N_a, N_b))
+    types = types_b if types is None else types
+    dimensions = dims_b if dims_b is not None else dimensions
+    N = N_b
+    if 'position' not in arrays_a or 'position' not in arrays_b:
+        raise ValueError("both frames need the 'position' array")
+    rows = None
+    if where is not None:
+        rows = where_rows(arrays_b, where, types)
+    if domain is not None:
+        if box_b is None:
+            raise ValueError("a domain needs box and the 'position' array")
+        inside = domain_rows(arrays_b['position'], box_b, domain, dimensions)
+        rows = inside if rows is None else numpy.intersect1d(rows, inside)
+    image_a = arrays_a.get('image') if images else None
+    image_b = arrays_b.get('image') if images else None
+    inputs = dict(position_a=arrays_a['position'], position_b=arrays_b['position'], image_a=image_a, image_b=image_b,
+                  vectors_a=None if box_a is None else box_vectors(box_a),
+                  vectors_b=None if box_b is None else box_vectors(box_b),
+                  minimum_image=minimum_image, dimensions=dimensions, rows=rows)
+    if not by_type:
+        return particle_displacements(**inputs)
+    if types is None:
+        raise ValueError("by_type needs the list of type names (types)")
+    typeid = numpy.zeros(N, dtype=numpy.uint32) if arrays_b.get('typeid') is None else numpy.asarray(arrays_b['typeid'])
+    n = N if rows is None else len(rows)
+    parts = [particle_displacements(typeid=typeid, type0=t0, n_types=min(_DISPLACEMENT_MAX_TYPES, len(types) - t0), **inputs)
+             for t0 in range(0, len(types), _DISPLACEMENT_MAX_TYPES)]
+    if not parts:
+        return Displacements.from_sums([], [], [], n, numpy.zeros((0, _DISPLACEMENT_VALUES)))
+    return Displacements.concatenate(parts, n)
+
+
 class Tracks(object):
     """What `HOOMDTrajectory.read_tracks` / `read_tracks_device` return: ``step`` (host, uint64, one entry per frame),
     ``rows`` (the K rows followed) and one ``F x K (x M)`` array per requested field, as an attribute and as
@@ -2776,6 +3115,118 @@ class HOOMDTrajectory(object):
                                             rows=rows, n=n)
                      for t0 in range(0, T, _MOMENTS_MAX_TYPES)]
             return Moments.concatenate(parts, count)
+        finally:
+            f.wait_read()
+
+    def _frame_index(self, idx):
+        idx = int(idx)
+        if idx < 0:
+            idx += len(self)
+        if idx >= len(self) or idx < 0:
+            raise IndexError()
+        return idx
+
+    def frame_displacements(self, idx, origin=0, by_type=True, images=True, minimum_image=False, where=None, domain=None,
+                            return_rows=False):
+        """`frame_displacements` from frame ``origin`` to frame ``idx``, both read through the host path: a
+        `Displacements` (with ``return_rows`` also `displacement_vectors` of the selection, a host array).  The
+        definition of `frame_displacements_device`.  An image that is stored nowhere is no array (``u = x``)."""
+        idx, origin = self._frame_index(idx), self._frame_index(origin)
+        snaps, arrays = [self[origin], self[idx]], []
+        for at, snap in zip((origin, idx), snaps):
+            a = _particle_arrays(snap.particles)
+            if self._effective_frame(at, 'particles/image', int(snap.particles.N)) is None:
+                a.pop('image', None)
+            arrays.append(a)
+        if int(snaps[0].particles.N) != int(snaps[1].particles.N):
+            raise ValueError("the frames differ in their number of particles (%d and %d)"
+                             % (snaps[0].particles.N, snaps[1].particles.N))
+        boxes = (snaps[0].configuration.box, snaps[1].configuration.box)
+        dims = int(snaps[1].configuration.dimensions)
+        types = snaps[1].particles.types
+        got = frame_displacements(arrays[0], arrays[1], by_type=by_type, images=images, minimum_image=minimum_image,
+                                  where=where, types=types, domain=domain, box=boxes, dimensions=dims)
+        if not return_rows:
+            return got
+        rows = None
+        if where is not None:
+            rows = where_rows(arrays[1], where, types)
+        if domain is not None:
+            inside = domain_rows(arrays[1]['position'], boxes[1], domain, dims)
+            rows = inside if rows is None else numpy.intersect1d(rows, inside)
+        d = displacement_vectors(arrays[0]['position'], arrays[1]['position'], arrays[0].get('image') if images else None,
+                                 arrays[1].get('image') if images else None, box_vectors(boxes[0]), box_vectors(boxes[1]),
+                                 minimum_image, dims, rows)
+        return got, d
+
+    def frame_displacements_device(self, idx, origin=0, by_type=True, images=True, minimum_image=False, where=None,
+                                   domain=None, return_rows=False):
+        """`frame_displacements` from frame ``origin`` to frame ``idx``, reduced on the GPU: a `Displacements` that
+        equals ``frame_displacements(idx, origin, ...)`` exactly, the sums bit for bit.
+
+        The selection is `frame_moments_device`'s own, on frame ``idx``; the types are frame ``idx``'s.  The effective
+        chunks (each frame's own, else frame 0's) of both positions, with ``images`` of both images and with
+        ``by_type`` of the typeid are staged into HBM -- a chunk the selection staged is not read again, and a chunk
+        both frames read from frame 0 is staged once -- and reduced there in one pass
+        (`pgsd.fl.PGSDFile.frame_displacements_device`); an image that is stored nowhere costs nothing.  More than four
+        types take consecutive passes over the same staged chunks; one `wait_read` at the end releases them.  With
+        ``return_rows`` the result is ``(displacements, d)``, ``d`` the ``count x 3`` float64 displacements of the
+        selection's entries in GPU memory.  A position that neither frame nor frame 0 stores is answered on the host.
+
+        ValueError: frames of different N (before anything is read); what `frame_displacements` refuses.
+        """
+        idx, origin = self._frame_index(idx), self._frame_index(origin)
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        box_o, _, n_origin, f_pos_o = self._census_frame(origin)
+        if n_origin != n_global:
+            raise ValueError("the frames differ in their number of particles (%d and %d)" % (n_origin, n_global))
+        if f_pos is None or f_pos_o is None:
+            # a degenerate file: no kernel path for a position that is all defaults
+            got = self.frame_displacements(idx, origin, by_type, images, minimum_image, where, domain, return_rows)
+            return (got[0], fl._device_from_host(got[1], f.pipeline_device())) if return_rows else got
+        ft = self._frame_of(idx, 'particles/types')
+        types = ParticleData._default_value['types'] if ft is None else _decode_strings(
+            self._frame0_small('particles/types') if ft == 0 else f.read_chunk(ft, 'particles/types'))
+        if domain is not None and not isinstance(domain, Domain):
+            domain = Domain(*domain)
+        rows, count = None, n_global
+        try:
+            if where is not None:
+                rows, count, _ = self._where_row_list(idx, types, box, dims, where, domain, False, n_global)
+            elif domain is not None:
+                rows, count = self._domain_row_list(f_pos, box, dims, domain, n_global)
+            chunks = [(f_pos_o, 'particles/position'), None, (f_pos, 'particles/position'), None, None]
+            for slot, at, name, wanted in ((1, origin, 'image', images), (3, idx, 'image', images), (4, idx, 'typeid', by_type)):
+                fr = self._effective_frame(at, 'particles/' + name, n_global) if wanted else None
+                chunks[slot] = None if fr is None else (fr, 'particles/' + name)
+            if minimum_image and (chunks[1] is not None or chunks[3] is not None):
+                raise ValueError("the minimum image is taken without image flags: pass no image array")
+            out = result = None
+            if return_rows:
+                out = fl._device_empty((max(count, 1), 3), numpy.float64, f.pipeline_device())
+                result = out if count > 0 else (out.view(shape=(0, 3)) if isinstance(out, fl.DeviceBuffer) else out[:0])
+            common = dict(vectors_a=box_vectors(box_o), vectors_b=box_vectors(box), minimum_image=minimum_image,
+                          dimensions=dims, rows=rows, n=None if rows is None else count)
+            T = len(types)
+            if by_type and T == 0:
+                if out is not None:
+                    f.frame_displacements_device(chunks[:4] + [None], out=out, **common)
+                got = Displacements.from_sums([], [], [], count, numpy.zeros((0, _DISPLACEMENT_VALUES)))
+            elif not by_type or chunks[4] is None:
+                # one group; by type without a stored typeid every particle is of type 0
+                got = f.frame_displacements_device(chunks, out=out, **common)
+                if by_type and T > 1:
+                    nothing = numpy.zeros((T - 1, _DISPLACEMENT_VALUES))
+                    nothing[:, 4] = -numpy.inf
+                    zero = Displacements.from_sums([0] * (T - 1), [0] * (T - 1), [-1] * (T - 1), 0, nothing)
+                    got = Displacements.concatenate([got, zero], count)
+            else:
+                parts = [f.frame_displacements_device(chunks, type0=t0, n_types=min(_DISPLACEMENT_MAX_TYPES, T - t0),
+                                                      out=out if t0 == 0 else None, **common)
+                         for t0 in range(0, T, _DISPLACEMENT_MAX_TYPES)]
+                got = Displacements.concatenate(parts, count)
+            return (got, result) if return_rows else got
         finally:
             f.wait_read()
 

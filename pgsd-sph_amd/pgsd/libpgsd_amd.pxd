@@ -227,6 +227,12 @@ cdef extern from "pgsd_private.h" nogil:
                                   const pgsd_index_entry* position, const double* defaults, uint32_t type0,
                                   uint32_t n_types, const uint32_t* rows, uint64_t n, uint64_t* out_counts,
                                   double* out_sums)
+    int pgsd_frame_displacements_device(pgsd_handle* handle, const pgsd_index_entry* position_a,
+                                        const pgsd_index_entry* image_a, const pgsd_index_entry* position_b,
+                                        const pgsd_index_entry* image_b, const pgsd_index_entry* typeid_chunk,
+                                        const double* vectors_a, const double* vectors_b, uint32_t flags,
+                                        uint32_t dimensions, uint32_t type0, uint32_t n_types, const uint32_t* rows,
+                                        uint64_t n, double* out_rows, uint64_t* out_counts, double* out_values)
     int pgsd_chunk_stats_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                                 uint32_t with_norm2, uint64_t* out_counts, double* out_values)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
