@@ -247,15 +247,15 @@ class DevicePipeline
     void fill_across_launches(std::vector<std::shared_ptr<ReadReq>>& pending);
     const void* kept_chunk(long long file_offset, size_t bytes) const;
     int stage_chunks(const ChunkRange* ranges, size_t n, uint64_t N, const void** src);
-    // the most chunks one pass stages: the larger of what a predicate, the conservation sums and the displacements take
+    // the most chunks one pass stages: the larger of what a predicate and a grouped reduction take
     enum
         {
-        STAGED_WHERE_OR_MOMENTS = (WHERE_MAX_TERMS + 1 > MOMENTS_CHUNKS ? WHERE_MAX_TERMS + 1 : MOMENTS_CHUNKS),
-        STAGED_MAX_CHUNKS = (STAGED_WHERE_OR_MOMENTS > DISPLACEMENT_CHUNKS ? STAGED_WHERE_OR_MOMENTS : DISPLACEMENT_CHUNKS)
+        STAGED_MAX_CHUNKS = (WHERE_MAX_TERMS + 1 > GROUPED_CHUNKS ? WHERE_MAX_TERMS + 1 : GROUPED_CHUNKS)
         };
     template<class Enqueue>
     int staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint64_t N, bool callers_memory,
                       std::string* why, Enqueue enqueue, int refused = PGSD_SUCCESS);
+    template<class Launch> int staged_grouped(const ChunkRange* ranges, GroupedArgs& g, std::string* why, Launch launch);
 
     // Who guards what.  m_mutex: the slab ring's free list, the job queue, tickets, committed direct chunks, every event
     // list and pool, both outstanding counts, m_stop, the error state, the statistics.  m_copy_mutex: enqueues on the

@@ -521,59 +521,52 @@ int DevicePipeline::chunk_stats(long long file_offset, size_t bytes, StatsArgs s
                          { return launch_chunk_stats(s, out_counts, out_values, m_res.pack_stream, err); });
     }
 
-// Conservation sums over up to five chunks of one N: only the stored chunks are staged and the absent ones stay null;
-// the row list is the caller's.
-int DevicePipeline::frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums,
-                                  std::string* why)
+// A grouped reduction over up to five chunks of one N: only the stored chunks are staged and the absent ones stay null.
+// Two chunks of one file range -- an elided chunk that both frames of a displacement read from frame 0 -- are staged once
+// and share the address: the staging is never handed one range twice.  `launch` runs once every address is filled in.
+template<class Launch>
+int DevicePipeline::staged_grouped(const ChunkRange* ranges, GroupedArgs& g, std::string* why, Launch launch)
     {
-    ChunkRange stored[MOMENTS_CHUNKS];
-    const void** slots[MOMENTS_CHUNKS];
+    ChunkRange stored[GROUPED_CHUNKS];
+    const void** slots[GROUPED_CHUNKS];
+    int same_as[GROUPED_CHUNKS];
     size_t n_stored = 0;
-    for (int i = 0; i < MOMENTS_CHUNKS; i++)
+    for (int i = 0; i < GROUPED_CHUNKS; i++)
         {
-        m.chunk[i] = nullptr;
-        if (m.present & (1u << i))
-            {
-            stored[n_stored] = ranges[i];
-            slots[n_stored++] = &m.chunk[i];
-            }
-        }
-    return staged_launch(stored, slots, n_stored, m.N, true, why, [&](std::string* err)
-                         { return launch_frame_moments(m, out_counts, out_sums, m_res.pack_stream, err); });
-    }
-
-// Frame displacements over up to five chunks of one N, two of them positions of different frames.  Two chunks of one
-// file range -- an elided chunk that both frames read from frame 0 -- are staged once and share the address: the
-// staging is never handed one range twice.  The row list and the optional output are the caller's.
-int DevicePipeline::frame_displacements(const ChunkRange* ranges, DisplacementArgs d, uint64_t* out_counts,
-                                        double* out_values, std::string* why)
-    {
-    static_assert((int)DISPLACEMENT_CHUNKS <= (int)STAGED_MAX_CHUNKS, "every chunk of the pass has a staging slot");
-    ChunkRange stored[DISPLACEMENT_CHUNKS];
-    const void** slots[DISPLACEMENT_CHUNKS];
-    int same_as[DISPLACEMENT_CHUNKS];
-    size_t n_stored = 0;
-    for (int i = 0; i < DISPLACEMENT_CHUNKS; i++)
-        {
-        d.chunk[i] = nullptr;
+        g.chunk[i] = nullptr;
         same_as[i] = -1;
-        if (!(d.present & (1u << i)))
+        if (!(g.present & (1u << i)))
             continue;
         for (int j = 0; j < i && same_as[i] < 0; j++)
-            if ((d.present & (1u << j)) && ranges[j].file_offset == ranges[i].file_offset && ranges[j].bytes == ranges[i].bytes)
+            if ((g.present & (1u << j)) && ranges[j].file_offset == ranges[i].file_offset && ranges[j].bytes == ranges[i].bytes)
                 same_as[i] = same_as[j] < 0 ? j : same_as[j];
         if (same_as[i] >= 0)
             continue;
         stored[n_stored] = ranges[i];
-        slots[n_stored++] = &d.chunk[i];
+        slots[n_stored++] = &g.chunk[i];
         }
-    return staged_launch(stored, slots, n_stored, d.N, true, why, [&](std::string* err)
+    return staged_launch(stored, slots, n_stored, g.N, true, why, [&](std::string* err)
                          {
-                             for (int i = 0; i < DISPLACEMENT_CHUNKS; i++)
+                             for (int i = 0; i < GROUPED_CHUNKS; i++)
                                  if (same_as[i] >= 0)
-                                     d.chunk[i] = d.chunk[same_as[i]];
-                             return launch_frame_displacements(d, out_counts, out_values, m_res.pack_stream, err);
+                                     g.chunk[i] = g.chunk[same_as[i]];
+                             return launch(err);
                          });
+    }
+
+// Conservation sums and frame displacements; the row list and the displacements' optional output are the caller's.
+int DevicePipeline::frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums,
+                                  std::string* why)
+    {
+    return staged_grouped(ranges, m, why, [&](std::string* err)
+                          { return launch_frame_moments(m, out_counts, out_sums, m_res.pack_stream, err); });
+    }
+
+int DevicePipeline::frame_displacements(const ChunkRange* ranges, DisplacementArgs d, uint64_t* out_counts,
+                                        double* out_values, std::string* why)
+    {
+    return staged_grouped(ranges, d, why, [&](std::string* err)
+                          { return launch_frame_displacements(d, out_counts, out_values, m_res.pack_stream, err); });
     }
 
 int DevicePipeline::wait_read()

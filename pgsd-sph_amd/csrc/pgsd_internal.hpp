@@ -313,20 +313,17 @@ inline void chunk_stats_of_nothing(uint32_t C, uint64_t* out_counts, double* out
 // entry >= s.N refuses the call.  The staged rows stay until the next wait_read.
 int device_pipeline_chunk_stats(DevicePipeline*, long long file_offset, size_t bytes, const StatsArgs& s, uint64_t* out_counts,
                                 double* out_values, std::string* err);
-// Conservation sums (pgsd.hoomd.particle_moments is the definition): per particle type of a group of up to four
-// consecutive types the entries, those with a value that is not finite, and nine sums in chunk statistics' order -- mass
-// m, momentum m * v[a], kinetic energy (0.5 * m) * ((vx*vx + vy*vy) + vz*vz), internal energy m * e, first moment
-// m * x[a] -- over several staged chunks of one N read row by row, every element converted to float64 first.
+// What the grouped reductions (conservation sums, frame displacements) share: up to five staged chunks of one N read row
+// by row, one of them the typeid, and a group of up to four consecutive types.  Passed to the kernels by value inside
+// the pass's own arguments.
 enum
     {
-    MOMENTS_CHUNKS = 5,     // typeid, mass, velocity, energy, position
-    MOMENTS_QUANTITIES = 9,
-    MOMENTS_MAX_TYPES = 4   // types per launch
+    GROUPED_CHUNKS = 5,
+    GROUPED_MAX_TYPES = 4 // types per launch
     };
-struct MomentsArgs
+struct GroupedArgs
     {
-    const void* chunk[MOMENTS_CHUNKS]; // the staged chunks in the order above; null: the default row stands for every row
-    double defaults[8];                // mass, v[3], energy, x[3]
+    const void* chunk[GROUPED_CHUNKS]; // the staged chunks in the pass's order; null: stored nowhere
     uint64_t N;                        // rows of every chunk that is present
     const uint32_t* rows;              // device, or null: every row
     uint64_t n;                        // entries of the list
@@ -335,6 +332,37 @@ struct MomentsArgs
     uint32_t typeid_signed;            // the typeid chunk holds int32: a negative id belongs to no type
     uint32_t present;                  // bit i: chunk i is stored (its address is filled in by the staging)
     uint32_t pad;
+    };
+// the results of no entry, Q sums per type (and a largest value with its entry): zero counts, +0.0 sums, -inf at no entry
+inline void grouped_of_nothing(uint32_t Q, bool largest, uint32_t n_types, uint64_t* out_counts, double* out_values)
+    {
+    const uint32_t cs = 2 + (largest ? 1 : 0), vs = Q + (largest ? 1 : 0);
+    for (uint32_t t = 0; t < n_types; t++)
+        {
+        out_counts[cs * t + 0] = out_counts[cs * t + 1] = 0;
+        for (uint32_t q = 0; q < Q; q++)
+            out_values[vs * t + q] = 0.0;
+        if (largest)
+            {
+            out_counts[cs * t + 2] = UINT64_MAX;
+            out_values[vs * t + Q] = -HUGE_VAL;
+            }
+        }
+    out_counts[cs * n_types] = 0;
+    }
+// Conservation sums (pgsd.hoomd.particle_moments is the definition): per particle type of a group of up to four
+// consecutive types the entries, those with a value that is not finite, and nine sums in chunk statistics' order -- mass
+// m, momentum m * v[a], kinetic energy (0.5 * m) * ((vx*vx + vy*vy) + vz*vz), internal energy m * e, first moment
+// m * x[a] -- over several staged chunks of one N read row by row, every element converted to float64 first.
+enum
+    {
+    MOMENTS_CHUNKS = GROUPED_CHUNKS, // typeid, mass, velocity, energy, position
+    MOMENTS_QUANTITIES = 9,
+    MOMENTS_MAX_TYPES = GROUPED_MAX_TYPES
+    };
+struct MomentsArgs : GroupedArgs // chunk: the order above; null: the default row stands for every row
+    {
+    double defaults[8]; // mass, v[3], energy, x[3]
     };
 // stage the chunks that are present (ranges[i] belongs to chunk i; m.chunk[i] is filled in) -- or take them from what an
 // earlier selection, census or statistics call left staged --, reduce on the GPU, copy the
@@ -350,39 +378,22 @@ int device_pipeline_frame_moments(DevicePipeline*, const ChunkRange* ranges, con
 // order, the largest s and the smallest entry that attains it.
 enum
     {
-    DISPLACEMENT_CHUNKS = 5,    // position a, image a, position b, image b, typeid
+    DISPLACEMENT_CHUNKS = GROUPED_CHUNKS, // position a, image a, position b, image b, typeid
     DISPLACEMENT_SUMS = 4,      // d[0], d[1], d[2], s
     DISPLACEMENT_VALUES = 5,    // the sums, then the largest s
-    DISPLACEMENT_MAX_TYPES = 4, // types per launch
+    DISPLACEMENT_MAX_TYPES = GROUPED_MAX_TYPES,
     DISPLACEMENT_MINIMUM_IMAGE = 1u // bit of the entry point's flags
     };
-struct DisplacementArgs
+struct DisplacementArgs : GroupedArgs // chunk: the order above; null: stored nowhere
     {
-    const void* chunk[DISPLACEMENT_CHUNKS]; // the staged chunks in the order above; null: stored nowhere
-    double va[6], vb[6];                    // Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz of frame a and of frame b
-    uint64_t N;                             // rows of every chunk
-    const uint32_t* rows;                   // device, or null: every row
-    uint64_t n;                             // entries of the list
-    double* out;                            // device, n x 3, or null: entry k's d
-    uint32_t type0, n_types;                // the types [type0, type0 + n_types); without a typeid chunk every entry is type0's
-    uint32_t f64;                           // the position chunks hold float64 (else float32)
-    uint32_t typeid_signed;                 // the typeid chunk holds int32: a negative id belongs to no type
-    uint32_t present;                       // bit i: chunk i is stored (its address is filled in by the staging)
-    uint32_t minimum_image, dimensions;     // fold d into frame b's box (no image chunk then); 2: z is not folded
-    uint32_t pad;
+    double va[6], vb[6];                // Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz of frame a and of frame b
+    double* out;                        // device, n x 3, or null: entry k's d
+    uint32_t minimum_image, dimensions; // fold d into frame b's box (no image chunk then); 2: z is not folded
     };
 // the results of no entry: zero counts, no largest entry, +0.0 sums, -inf
 inline void displacements_of_nothing(uint32_t n_types, uint64_t* out_counts, double* out_values)
     {
-    for (uint32_t t = 0; t < n_types; t++)
-        {
-        out_counts[3 * t + 0] = out_counts[3 * t + 1] = 0;
-        out_counts[3 * t + 2] = UINT64_MAX;
-        for (int q = 0; q < DISPLACEMENT_SUMS; q++)
-            out_values[DISPLACEMENT_VALUES * t + q] = 0.0;
-        out_values[DISPLACEMENT_VALUES * t + DISPLACEMENT_SUMS] = -HUGE_VAL;
-        }
-    out_counts[3 * n_types] = 0;
+    grouped_of_nothing(DISPLACEMENT_SUMS, true, n_types, out_counts, out_values);
     }
 // stage the chunks that are present (ranges[i] belongs to chunk i; d.chunk[i] is filled in; two chunks of one file range
 // are staged once and share the address) -- or take them from what an earlier call left staged --, reduce on the GPU,

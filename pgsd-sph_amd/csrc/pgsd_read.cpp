@@ -638,6 +638,105 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+namespace
+    {
+// The tail of a reduction's entry point: `call` runs the pipeline; a refusal loses the launcher's prefix and becomes
+// the entry point's own, any other failure keeps its text.  The caller copies the results out on success only.
+template<class Call> int reduction_call(const char* who, const std::string& prefix, Call call)
+    {
+    std::string err;
+    const int rc = call(&err);
+    if (rc == PGSD_ERROR_INVALID_ARGUMENT)
+        {
+        if (err.compare(0, prefix.size(), prefix) == 0)
+            err.erase(0, prefix.size());
+        set_last_error(std::string(who) + ": " + (err.empty() ? std::string("refused") : err));
+        }
+    else if (rc != PGSD_SUCCESS)
+        set_last_error(err);
+    return rc;
+    }
+
+// One chunk slot of a grouped reduction (conservation sums, frame displacements): its name and columns, what it holds,
+// and how the pass speaks of it where its elements are of another kind.
+enum GroupedKind
+    {
+    GROUPED_TYPEID,
+    GROUPED_FLOAT,
+    GROUPED_IMAGE
+    };
+struct GroupedSlot
+    {
+    const char* name;
+    uint32_t columns;
+    GroupedKind kind;
+    const char* subject;
+    };
+const GroupedSlot g_moments_slots[GROUPED_CHUNKS] = {{"typeid", 1, GROUPED_TYPEID, "the typeid chunk"},
+                                                     {"mass", 1, GROUPED_FLOAT, "the mass chunk"},
+                                                     {"velocity", 3, GROUPED_FLOAT, "the velocity chunk"},
+                                                     {"energy", 1, GROUPED_FLOAT, "the energy chunk"},
+                                                     {"position", 3, GROUPED_FLOAT, "the position chunk"}};
+const GroupedSlot g_displacement_slots[GROUPED_CHUNKS] = {{"position", 3, GROUPED_FLOAT, "a position chunk"},
+                                                          {"image", 3, GROUPED_IMAGE, "an image chunk"},
+                                                          {"position", 3, GROUPED_FLOAT, "a position chunk"},
+                                                          {"image", 3, GROUPED_IMAGE, "an image chunk"},
+                                                          {"typeid", 1, GROUPED_TYPEID, "the typeid chunk"}};
+
+// The chunks a grouped reduction was given: element kind, columns, N below 2^32 and equal, the whole chunk's file range.
+// Fills ranges[i] and a's present, N, typeid_signed and f64.  A refusal sets *why; any other failure leaves it empty.
+int grouped_chunks(Impl* s, struct pgsd_handle* handle, const GroupedSlot* slots, const char* floats,
+                   const struct pgsd_index_entry* const* given, GroupedArgs* a, ChunkRange* ranges, std::string* why)
+    {
+    const auto refuse = [why](const std::string& msg)
+    {
+        *why = msg;
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    uint32_t float_type = 0;
+    for (int i = 0; i < GROUPED_CHUNKS; i++)
+        {
+        if (!given[i])
+            continue;
+        const GroupedSlot& slot = slots[i];
+        pgsd_index_entry c = *given[i]; // a flush may move the index storage
+        if (slot.kind == GROUPED_TYPEID)
+            {
+            if (c.type != PGSD_TYPE_UINT32 && c.type != PGSD_TYPE_INT32)
+                return refuse(std::string(slot.subject) + " holds uint32 or int32 elements");
+            a->typeid_signed = c.type == PGSD_TYPE_INT32 ? 1u : 0u;
+            }
+        else if (slot.kind == GROUPED_IMAGE)
+            {
+            if (c.type != PGSD_TYPE_INT32)
+                return refuse(std::string(slot.subject) + " holds int32 elements");
+            }
+        else
+            {
+            if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
+                return refuse(std::string(slot.subject) + " holds float32 or float64 elements");
+            if (float_type && c.type != float_type)
+                return refuse(std::string("the ") + floats + " chunks share one element type (float32 or float64, not mixed)");
+            float_type = c.type;
+            }
+        if (c.M != slot.columns)
+            return refuse(std::string("the ") + slot.name + " chunk has " + std::to_string(slot.columns)
+                          + (slot.columns == 1 ? " column" : " columns"));
+        if (c.N >= (1ull << 32))
+            return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+        if (a->present && c.N != a->N)
+            return refuse("the chunks differ in their number of rows");
+        a->N = c.N;
+        int rc = whole_chunk_range(s, handle, c, &ranges[i].file_offset, &ranges[i].bytes);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        a->present |= 1u << i;
+        }
+    a->f64 = float_type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    return PGSD_SUCCESS;
+    }
+    } // namespace
+
 extern "C" int pgsd_chunk_stats_device(struct pgsd_handle* handle, const struct pgsd_index_entry* chunk, const uint32_t* rows,
                                        uint64_t n, uint32_t with_norm2, uint64_t* out_counts, double* out_values)
     try
@@ -683,20 +782,10 @@ extern "C" int pgsd_chunk_stats_device(struct pgsd_handle* handle, const struct 
     // (the outputs are written on success only: the launcher fills these and they are copied out then)
     uint64_t counts[15];
     double values[15];
-    std::string err;
-    rc = device_pipeline_chunk_stats(s->dev, foff, bytes, a, counts, values, &err);
-    if (rc == PGSD_ERROR_INVALID_ARGUMENT)
-        {
-        const std::string prefix = "chunk statistics: ";
-        if (err.compare(0, prefix.size(), prefix) == 0)
-            err.erase(0, prefix.size());
-        return refuse(err.empty() ? std::string("refused") : err);
-        }
+    rc = reduction_call(who, "chunk statistics: ", [&](std::string* err)
+                        { return device_pipeline_chunk_stats(s->dev, foff, bytes, a, counts, values, err); });
     if (rc != PGSD_SUCCESS)
-        {
-        set_last_error(err);
         return rc;
-        }
     std::copy(counts, counts + 3 * C, out_counts);
     std::copy(values, values + 3 * C, out_values);
     return PGSD_SUCCESS;
@@ -722,8 +811,6 @@ extern "C" int pgsd_frame_moments_device(struct pgsd_handle* handle, const struc
         set_last_error(std::string(who) + ": " + msg);
         return PGSD_ERROR_INVALID_ARGUMENT;
     };
-    static const char* const names[MOMENTS_CHUNKS] = {"typeid", "mass", "velocity", "energy", "position"};
-    static const uint32_t widths[MOMENTS_CHUNKS] = {1, 1, 3, 1, 3};
     const struct pgsd_index_entry* given[MOMENTS_CHUNKS] = {typeid_chunk, mass, velocity, energy, position};
     if (n_types < 1 || n_types > MOMENTS_MAX_TYPES)
         return refuse("a call takes 1 to 4 types");
@@ -733,39 +820,10 @@ extern "C" int pgsd_frame_moments_device(struct pgsd_handle* handle, const struc
     memset(&a, 0, sizeof(a));
     ChunkRange ranges[MOMENTS_CHUNKS];
     memset(ranges, 0, sizeof(ranges));
-    uint32_t float_type = 0;
-    for (int i = 0; i < MOMENTS_CHUNKS; i++)
-        {
-        if (!given[i])
-            continue;
-        pgsd_index_entry c = *given[i]; // a flush may move the index storage
-        if (i == 0)
-            {
-            if (c.type != PGSD_TYPE_UINT32 && c.type != PGSD_TYPE_INT32)
-                return refuse("the typeid chunk holds uint32 or int32 elements");
-            a.typeid_signed = c.type == PGSD_TYPE_INT32 ? 1u : 0u;
-            }
-        else
-            {
-            if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
-                return refuse(std::string("the ") + names[i] + " chunk holds float32 or float64 elements");
-            if (float_type && c.type != float_type)
-                return refuse("the float chunks share one element type (float32 or float64, not mixed)");
-            float_type = c.type;
-            }
-        if (c.M != widths[i])
-            return refuse(std::string("the ") + names[i] + " chunk has " + std::to_string(widths[i])
-                          + (widths[i] == 1 ? " column" : " columns"));
-        if (c.N >= (1ull << 32))
-            return refuse("chunks of 2^32 rows or more have no 32-bit row list");
-        if (a.present && c.N != a.N)
-            return refuse("the chunks differ in their number of rows");
-        a.N = c.N;
-        int rc = whole_chunk_range(s, handle, c, &ranges[i].file_offset, &ranges[i].bytes);
-        if (rc != PGSD_SUCCESS)
-            return rc;
-        a.present |= 1u << i;
-        }
+    std::string why;
+    int rc = grouped_chunks(s, handle, g_moments_slots, "float", given, &a, ranges, &why);
+    if (rc != PGSD_SUCCESS)
+        return why.empty() ? rc : refuse(why);
     if (n >= (1ull << 32) && (rows || !a.present))
         return refuse("a row list holds fewer than 2^32 entries");
     // without a stored chunk nothing bounds the entries of a list (no row is loaded); without a list the call says how many
@@ -776,7 +834,6 @@ extern "C" int pgsd_frame_moments_device(struct pgsd_handle* handle, const struc
     a.n = rows ? n : a.N;
     a.type0 = type0;
     a.n_types = n_types;
-    a.f64 = float_type == PGSD_TYPE_DOUBLE ? 1u : 0u;
     // (the outputs are written on success only: the launcher fills these and they are copied out then)
     uint64_t counts[2 * MOMENTS_MAX_TYPES + 1] = {};
     double sums[MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES] = {};
@@ -784,20 +841,10 @@ extern "C" int pgsd_frame_moments_device(struct pgsd_handle* handle, const struc
         {
         if (a.N == 0)
             return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
-        std::string err;
-        int rc = device_pipeline_frame_moments(s->dev, ranges, a, counts, sums, &err);
-        if (rc == PGSD_ERROR_INVALID_ARGUMENT)
-            {
-            const std::string prefix = "conservation sums: ";
-            if (err.compare(0, prefix.size(), prefix) == 0)
-                err.erase(0, prefix.size());
-            return refuse(err.empty() ? std::string("refused") : err);
-            }
+        rc = reduction_call(who, "conservation sums: ", [&](std::string* err)
+                            { return device_pipeline_frame_moments(s->dev, ranges, a, counts, sums, err); });
         if (rc != PGSD_SUCCESS)
-            {
-            set_last_error(err);
             return rc;
-            }
         }
     std::copy(counts, counts + 2 * n_types + 1, out_counts);
     std::copy(sums, sums + MOMENTS_QUANTITIES * n_types, out_sums);
@@ -827,8 +874,6 @@ extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const
         set_last_error(std::string(who) + ": " + msg);
         return PGSD_ERROR_INVALID_ARGUMENT;
     };
-    static const char* const names[DISPLACEMENT_CHUNKS] = {"position", "image", "position", "image", "typeid"};
-    static const uint32_t widths[DISPLACEMENT_CHUNKS] = {3, 3, 3, 3, 1};
     const struct pgsd_index_entry* given[DISPLACEMENT_CHUNKS] = {position_a, image_a, position_b, image_b, typeid_chunk};
     if (n_types < 1 || n_types > DISPLACEMENT_MAX_TYPES)
         return refuse("a call takes 1 to 4 types");
@@ -844,44 +889,10 @@ extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const
     memset(&a, 0, sizeof(a));
     ChunkRange ranges[DISPLACEMENT_CHUNKS];
     memset(ranges, 0, sizeof(ranges));
-    uint32_t float_type = 0;
-    for (int i = 0; i < DISPLACEMENT_CHUNKS; i++)
-        {
-        if (!given[i])
-            continue;
-        pgsd_index_entry c = *given[i]; // a flush may move the index storage
-        if (i == 4)
-            {
-            if (c.type != PGSD_TYPE_UINT32 && c.type != PGSD_TYPE_INT32)
-                return refuse("the typeid chunk holds uint32 or int32 elements");
-            a.typeid_signed = c.type == PGSD_TYPE_INT32 ? 1u : 0u;
-            }
-        else if (i == 1 || i == 3)
-            {
-            if (c.type != PGSD_TYPE_INT32)
-                return refuse("an image chunk holds int32 elements");
-            }
-        else
-            {
-            if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
-                return refuse("a position chunk holds float32 or float64 elements");
-            if (float_type && c.type != float_type)
-                return refuse("the position chunks share one element type (float32 or float64, not mixed)");
-            float_type = c.type;
-            }
-        if (c.M != widths[i])
-            return refuse(std::string("the ") + names[i] + " chunk has " + std::to_string(widths[i])
-                          + (widths[i] == 1 ? " column" : " columns"));
-        if (c.N >= (1ull << 32))
-            return refuse("chunks of 2^32 rows or more have no 32-bit row list");
-        if (a.present && c.N != a.N)
-            return refuse("the chunks differ in their number of rows");
-        a.N = c.N;
-        int rc = whole_chunk_range(s, handle, c, &ranges[i].file_offset, &ranges[i].bytes);
-        if (rc != PGSD_SUCCESS)
-            return rc;
-        a.present |= 1u << i;
-        }
+    std::string why;
+    int rc = grouped_chunks(s, handle, g_displacement_slots, "position", given, &a, ranges, &why);
+    if (rc != PGSD_SUCCESS)
+        return why.empty() ? rc : refuse(why);
     if (rows && n >= (1ull << 32))
         return refuse("a row list holds fewer than 2^32 entries");
     std::copy(vectors_a, vectors_a + 6, a.va);
@@ -891,7 +902,6 @@ extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const
     a.out = out_rows;
     a.type0 = type0;
     a.n_types = n_types;
-    a.f64 = float_type == PGSD_TYPE_DOUBLE ? 1u : 0u;
     a.minimum_image = (flags & DISPLACEMENT_MINIMUM_IMAGE) ? 1u : 0u;
     a.dimensions = dimensions;
     // (the outputs are written on success only: the launcher fills these and they are copied out then)
@@ -902,20 +912,10 @@ extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const
         {
         if (a.N == 0)
             return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
-        std::string err;
-        int rc = device_pipeline_frame_displacements(s->dev, ranges, a, counts, values, &err);
-        if (rc == PGSD_ERROR_INVALID_ARGUMENT)
-            {
-            const std::string prefix = "frame displacements: ";
-            if (err.compare(0, prefix.size(), prefix) == 0)
-                err.erase(0, prefix.size());
-            return refuse(err.empty() ? std::string("refused") : err);
-            }
+        rc = reduction_call(who, "frame displacements: ", [&](std::string* err)
+                            { return device_pipeline_frame_displacements(s->dev, ranges, a, counts, values, err); });
         if (rc != PGSD_SUCCESS)
-            {
-            set_last_error(err);
             return rc;
-            }
         }
     std::copy(counts, counts + 3 * n_types + 1, out_counts);
     std::copy(values, values + DISPLACEMENT_VALUES * n_types, out_values);

@@ -8,7 +8,7 @@
 //                      in the one-block scan and lives in the compaction scratch
 //   pgsd_census.hip    the domain census: axis histograms and cell counts
 //   pgsd_order.hip     cell order: keys, a stable radix sort, the pass that applies the permutation
-//   pgsd_stats.hip     frame statistics, conservation sums and frame displacements
+//   pgsd_stats.hip     frame statistics; conservation sums and frame displacements on one final kernel and launcher
 //   pgsd_device_memory.cpp   pgsd_device_alloc / _free / _copy: device memory owned by the library (no kernel)
 //   pgsd_scratch.hpp / .cpp  the host side all of them stand on: scratch space, launch scope, device scope
 //   pgsd_kernels.hpp / .cpp  row layout (SEL_THREADS ...), vector types, tuning, what the pack and unpack kernels share

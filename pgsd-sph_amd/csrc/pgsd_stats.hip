@@ -15,12 +15,11 @@
 // starts at +0.0 and only ever adds is never -0.0.  Every element is converted to float64 first (exact for float32,
 // int32 and uint32); the appended norm2 column of a three-column float chunk is (x*x + y*y) + z*z in float64 without
 // contraction.  Shared device helpers and the row layout: pgsd_kernels.hpp; the launchers' host side: pgsd_scratch.hpp.
-// The second half of the file holds the conservation sums -- moments_tile_kernel, moments_final_kernel: per particle
-// type the sums of m, m * v, (0.5 * m) |v|^2, m * e and m * x over several staged chunks read row by row --, which use
-// the same tile layout, the same trees and the same scratch; pgsd.hoomd.particle_moments is their definition.
-// The third part holds the frame displacements -- displacement_tile_kernel, displacement_final_kernel: per particle type
-// the sums of the difference of two frames' unwrapped positions and of its square, and the largest square with the entry
-// that attains it --, again in that layout and scratch; pgsd.hoomd.particle_displacements is their definition.
+// The second half of the file holds the grouped reductions: per particle type sums over several staged chunks read row by
+// row, in the same tile layout, the same trees and the same scratch.  The conservation sums (moments_tile_kernel;
+// pgsd.hoomd.particle_moments is the definition) and the frame displacements (displacement_tile_kernel;
+// pgsd.hoomd.particle_displacements) have a tile kernel each and share one table layout, grouped_final_kernel and one
+// launcher.
 #include "pgsd_kernels.hpp"
 #include "pgsd_scratch.hpp"
 
@@ -81,6 +80,34 @@ __device__ __forceinline__ double stats_wave_sum(double p)
     for (int h = 32; h >= 1; h >>= 1)
         p = p + __shfl_down(p, h, 64);
     return p;
+    }
+
+// the rest of the block tree: the four waves' sums, (w0 + w1) + (w2 + w3)
+__device__ __forceinline__ double stats_block_sum(const double* w)
+    {
+#pragma clang fp contract(off)
+    return (w[0] + w[1]) + (w[2] + w[3]);
+    }
+
+// a final kernel's walk over one column of the tiles' sums -- lane t adds the partials of tiles t, t + 256, ... in that
+// order to +0.0 -- and the wave part of the block tree (lane 0 of each wave ends with its wave's sum)
+__device__ __forceinline__ double stats_column_sum(const double* __restrict__ t_sum, uint32_t n_tiles)
+    {
+#pragma clang fp contract(off)
+    double sum = 0.0;
+#pragma unroll 8
+    for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
+        sum = sum + t_sum[t];
+    return stats_wave_sum(sum);
+    }
+
+// a 64-bit counter across the wave (every lane ends with the result)
+__device__ __forceinline__ uint64_t stats_wave_count(uint64_t c)
+    {
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1)
+        c += (uint64_t)__shfl_xor((unsigned long long)c, h, 64);
+    return c;
     }
 
 // minimum, maximum and the counters across the wave (every lane ends with the result; the order is free)
@@ -191,7 +218,7 @@ __global__ __launch_bounds__(SEL_THREADS) void stats_tile_kernel(const StatsArgs
         {
         const uint32_t c = threadIdx.x;
         const double* w = wave_d[STATS_Q_SUM][c];
-        td[((size_t)STATS_Q_SUM * C + c) * n_tiles + tile] = (w[0] + w[1]) + (w[2] + w[3]);
+        td[((size_t)STATS_Q_SUM * C + c) * n_tiles + tile] = stats_block_sum(w);
         w = wave_d[STATS_Q_MIN][c];
         td[((size_t)STATS_Q_MIN * C + c) * n_tiles + tile] = fmin(fmin(w[0], w[1]), fmin(w[2], w[3]));
         w = wave_d[STATS_Q_MAX][c];
@@ -250,9 +277,9 @@ __global__ __launch_bounds__(SEL_THREADS) void stats_final_kernel(const double* 
         const double lo = __shfl_xor(mn, h, 64), hi = __shfl_xor(mx, h, 64);
         mn = lo < mn ? lo : mn;
         mx = hi > mx ? hi : mx;
-        n_nan += (uint64_t)__shfl_xor((unsigned long long)n_nan, h, 64);
-        n_inf += (uint64_t)__shfl_xor((unsigned long long)n_inf, h, 64);
         }
+    n_nan = stats_wave_count(n_nan);
+    n_inf = stats_wave_count(n_inf);
     if (lane == 0)
         {
         wave_d[STATS_Q_SUM][wave] = sum;
@@ -274,8 +301,7 @@ __global__ __launch_bounds__(SEL_THREADS) void stats_final_kernel(const double* 
         values[3 * c + 0] = fmin(fmin(w[0], w[1]), fmin(w[2], w[3]));
         w = wave_d[STATS_Q_MAX];
         values[3 * c + 1] = fmax(fmax(w[0], w[1]), fmax(w[2], w[3]));
-        w = wave_d[STATS_Q_SUM];
-        values[3 * c + 2] = (w[0] + w[1]) + (w[2] + w[3]);
+        values[3 * c + 2] = stats_block_sum(wave_d[STATS_Q_SUM]);
         if (c == 0)
             {
             out[6 * STATS_MAX_COLUMNS] = *flag_dev;
@@ -284,25 +310,79 @@ __global__ __launch_bounds__(SEL_THREADS) void stats_final_kernel(const double* 
         }
     }
 
-// ------------------------------------------------------------------ conservation sums
-// pgsd.hoomd.particle_moments is the definition.  Per entry nine float64 values -- m; m * v[a]; (0.5 * m) * ((vx*vx +
-// vy*vy) + vz*vz); m * e; m * x[a] --, without contraction, from the rows of up to five staged chunks (typeid, mass,
-// velocity, energy, position); per type of the launch's group the sum of each value over the entries of that type where
-// the value is finite, in the order of the statistics above (an entry of another type, a value that is not finite and an
-// entry past the end add +0.0), the entries of the type and those with a value that is not finite; and the entries of
-// no type of the group.
-//   moments_tile_kernel<G, F64, TG>   the tile layout of stats_tile_kernel; TG (1, 2, 4) types per launch, all
-//                          accumulators in registers.  A chunk that is stored nowhere is a null pointer (uniform over
-//                          the launch) and its default row, passed by value.  Adding +0.0 to a sum that started at +0.0
-//                          changes no bit, so a wave skips the adds of a type none of its lanes holds (types lie in long
-//                          runs in real files).  Partials to td[(q * TG + t) * n_tiles + tile], counters to
-//                          tu[(c * TG + t) * n_tiles + tile] (c = entries, bad) and tu[2 * TG * n_tiles + tile] (other)
-//   moments_final_kernel   one workgroup per column of either table: the walk and the tree of stats_final_kernel
+// ------------------------------------------------------------------ grouped reductions
+// Conservation sums and frame displacements are two PASSES of one shape.  Per entry a pass loads the rows of up to five
+// staged chunks and forms Q float64 values without contraction; per type of the launch's group it sums each value over
+// the entries of that type where the value is finite, in the order of the statistics above (an entry of another type, a
+// value that is not finite and an entry past the end add +0.0), counts the entries of the type, those with a value that
+// is not finite, and the entries of no type of the group; the displacements also keep the largest of their last value
+// (NaN takes no part) with the smallest entry that attains it.
+//   moments_tile_kernel<G, F64, TG>, displacement_tile_kernel<G, F64, TG>
+//                          the tile layout of stats_tile_kernel; TG (1, 2, 4) types per launch, all accumulators in
+//                          registers.  Adding +0.0 to a sum that started at +0.0 changes no bit, so a wave skips the adds
+//                          of a type none of its lanes holds (types lie in long runs in real files).  For the largest
+//                          value a lane keeps (mx, k) per type and replaces it on value > mx only, so that -- its entries
+//                          ascend -- it keeps the smallest k; across lanes, waves and tiles the rule is "larger mx, then
+//                          smaller k", which is associative and commutative: its order is free.  No entry: (-inf,
+//                          0xFFFFFFFF).  One table layout for both: partials to td[(q * TG + t) * n_tiles + tile] (the
+//                          largest value at q = Q), counters to tu[(c * TG + t) * n_tiles + tile] (c = entries, bad,
+//                          largest entry if there is one) and tu[(2 + largest) * TG * n_tiles + tile] (other).
+//                          The two bodies stay apart: one inlined body behind two kernels, and even inlined helpers for
+//                          the classification and the adds, cost the float64 instances registers with this compiler
+//                          (DESIGN.md has the figures).
+//   grouped_final_kernel   one workgroup per column of either table: the walk and the tree of stats_final_kernel for a
+//                          sum or a counter, the pair rule for a largest value
+// The launcher (launch_grouped below) knows a pass by a small description: its args type, Q, whether it keeps a largest
+// value, the chunk slot of the typeid, its name, its own refusals and its kernels.
 enum
     {
-    MOMENTS_RESULT_WORDS = MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES + 2 * MOMENTS_MAX_TYPES + 1 + 1 // sums, counters, flag
+    GROUPED_NO_ENTRY = 0xFFFFFFFFu,
+    GROUPED_COUNTERS = 2 * GROUPED_MAX_TYPES + 1 // entries and bad per type, other
+    };
+// The result words: (Q + largest) x 4 doubles (value q of type t at q * TG + t), the counters, 4 largest entries if
+// there are any, the flag word.
+constexpr uint32_t grouped_word_counters(uint32_t Q, bool largest)
+    {
+    return (Q + (largest ? 1 : 0)) * GROUPED_MAX_TYPES;
+    }
+constexpr uint32_t grouped_word_entries(uint32_t Q, bool largest)
+    {
+    return grouped_word_counters(Q, largest) + GROUPED_COUNTERS;
+    }
+constexpr uint32_t grouped_word_flag(uint32_t Q, bool largest)
+    {
+    return grouped_word_entries(Q, largest) + (largest ? GROUPED_MAX_TYPES : 0);
+    }
+enum
+    {
+    MOMENTS_RESULT_WORDS = grouped_word_flag(MOMENTS_QUANTITIES, false) + 1,
+    DISPLACEMENT_RESULT_WORDS = grouped_word_flag(DISPLACEMENT_SUMS, true) + 1
     };
 
+// (mx, k) takes (om, ok) where that is the larger value, or the same value at a smaller entry
+__device__ __forceinline__ void grouped_pair(double& mx, uint32_t& k, double om, uint32_t ok)
+    {
+    const bool better = om > mx || (om == mx && ok < k);
+    mx = better ? om : mx;
+    k = better ? ok : k;
+    }
+
+// the pair rule across the wave (every lane ends with the result)
+__device__ __forceinline__ void grouped_wave_pair(double& mx, uint32_t& k)
+    {
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1)
+        {
+        const double om = __shfl_xor(mx, h, 64);
+        const uint32_t ok = __shfl_xor(k, h, 64);
+        grouped_pair(mx, k, om, ok);
+        }
+    }
+
+// ------------------------------------------------------------------ conservation sums
+// pgsd.hoomd.particle_moments is the definition.  Per entry nine float64 values -- m; m * v[a]; (0.5 * m) * ((vx*vx +
+// vy*vy) + vz*vz); m * e; m * x[a] -- from the rows of typeid, mass, velocity, energy and position; a chunk that is
+// stored nowhere is a null pointer (uniform over the launch) and its default row, passed by value.
 template<bool G, bool F64, int TG>
 __global__ __launch_bounds__(SEL_THREADS) void moments_tile_kernel(const MomentsArgs s, uint32_t n_tiles, double* td,
                                                                    uint32_t* tu, uint32_t* flag_dev, uint32_t* flag_host)
@@ -465,104 +545,27 @@ __global__ __launch_bounds__(SEL_THREADS) void moments_tile_kernel(const Moments
         }
     }
 
-// One workgroup per column: the first n_d columns are the sums (stats_final_kernel's walk t, t + 256, ... per lane, then
-// the block tree), the next n_u the counters.  out: MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES doubles (column b at word b),
-// then the counters, then the flag word, handed over and cleared as there.
-__global__ __launch_bounds__(SEL_THREADS) void moments_final_kernel(const double* __restrict__ td, const uint32_t* __restrict__ tu,
-                                                                    uint32_t n_tiles, uint32_t n_d, uint32_t* flag_dev,
-                                                                    uint64_t* __restrict__ out)
+// what the launcher needs to know of the pass
+struct MomentsPass
     {
-#pragma clang fp contract(off)
-    __shared__ double wave_d[STATS_WAVES];
-    __shared__ uint64_t wave_u[STATS_WAVES];
-    const uint32_t b = blockIdx.x;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (b < n_d)
-        {
-        const double* t_sum = td + (size_t)b * n_tiles;
-        double sum = 0.0;
-#pragma unroll 8
-        for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
-            sum = sum + t_sum[t];
-        sum = stats_wave_sum(sum);
-        if (lane == 0)
-            wave_d[wave] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            {
-            double* values = (double*)out;
-            values[b] = (wave_d[0] + wave_d[1]) + (wave_d[2] + wave_d[3]);
-            }
-        }
-    else
-        {
-        const uint32_t* t_cnt = tu + (size_t)(b - n_d) * n_tiles;
-        uint64_t count = 0;
-#pragma unroll 8
-        for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
-            count += t_cnt[t];
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1)
-            count += (uint64_t)__shfl_xor((unsigned long long)count, h, 64);
-        if (lane == 0)
-            wave_u[wave] = count;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            out[MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES + (b - n_d)] = wave_u[0] + wave_u[1] + wave_u[2] + wave_u[3];
-        }
-    if (b == 0 && threadIdx.x == 0)
-        {
-        out[MOMENTS_RESULT_WORDS - 1] = *flag_dev;
-        *flag_dev = 0u;
-        }
-    }
-
-// ------------------------------------------------------------------ frame displacements
-// pgsd.hoomd.particle_displacements is the definition.  Per entry the rows of up to five staged chunks -- position a,
-// image a, position b, image b, typeid --; u = x + (image . box vectors) per frame in the definition's association (u = x
-// without an image chunk: no product is formed), d = u_b - u_a, with the minimum image folded z, y, x into frame b's
-// box, s = (d0*d0 + d1*d1) + d2*d2, all in float64 without contraction; per type of the launch's group the sums of d[a]
-// and of s over the entries where the value is finite, in the order of the statistics above, the entries, those with a
-// value that is not finite, and the largest s (NaN takes no part) with the smallest entry that attains it.
-//   displacement_tile_kernel<G, F64, TG>   the tile layout and the sums of moments_tile_kernel; a lane keeps (mx, k)
-//                          per type and replaces it on s > mx only, so that -- its entries ascend -- it keeps the smallest
-//                          k; across lanes, waves and tiles the rule is "larger mx, then smaller k", which is
-//                          associative and commutative: its order is free.  No entry: (-inf, 0xFFFFFFFF).  Partials to
-//                          td[(q * TG + t) * n_tiles + tile] (q = d0, d1, d2, s, largest), counters to
-//                          tu[(c * TG + t) * n_tiles + tile] (c = entries, bad, largest entry) and
-//                          tu[3 * TG * n_tiles + tile] (other).  With `out`, entry k's d goes to out[3 k .. 3 k + 2]
-//   displacement_final_kernel   one workgroup per column of either table: sums and counters as moments_final_kernel,
-//                          the largest s of a type by the pair rule
-enum
-    {
-    DISP_Q = DISPLACEMENT_SUMS,
-    DISP_NO_ENTRY = 0xFFFFFFFFu,
-    // the result words: 5 x 4 doubles (value q of type t at q * TG + t), 2 x 4 + 1 counters, 4 largest entries, the flag
-    DISP_WORD_COUNTERS = DISPLACEMENT_VALUES * DISPLACEMENT_MAX_TYPES,
-    DISP_WORD_ENTRIES = DISP_WORD_COUNTERS + 2 * DISPLACEMENT_MAX_TYPES + 1,
-    DISP_WORD_FLAG = DISP_WORD_ENTRIES + DISPLACEMENT_MAX_TYPES,
-    DISPLACEMENT_RESULT_WORDS = DISP_WORD_FLAG + 1
+    using Args = MomentsArgs;
+    static constexpr uint32_t Q = MOMENTS_QUANTITIES, TYPEID = 0;
+    static constexpr bool LARGEST = false;
+    static constexpr const char* what = "conservation sums";
+    // the pass's own refusal, or null; whether every chunk it cannot do without has an address
+    static const char* refusal(const Args&) { return nullptr; }
+    static bool ready(const Args&) { return true; }
+    // (without a stored chunk and with a row list N is 2^32: nothing bounds the entries)
+    static constexpr uint64_t N_LIMIT = (1ull << 32) + 1;
+    template<bool G, bool F64, int TG> static auto kernel() { return moments_tile_kernel<G, F64, TG>; }
     };
 
-// (mx, k) takes (om, ok) where that is the larger value, or the same value at a smaller entry
-__device__ __forceinline__ void disp_pair(double& mx, uint32_t& k, double om, uint32_t ok)
-    {
-    const bool better = om > mx || (om == mx && ok < k);
-    mx = better ? om : mx;
-    k = better ? ok : k;
-    }
-
-// the pair rule across the wave (every lane ends with the result)
-__device__ __forceinline__ void disp_wave_pair(double& mx, uint32_t& k)
-    {
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1)
-        {
-        const double om = __shfl_xor(mx, h, 64);
-        const uint32_t ok = __shfl_xor(k, h, 64);
-        disp_pair(mx, k, om, ok);
-        }
-    }
+// ------------------------------------------------------------------ frame displacements
+// pgsd.hoomd.particle_displacements is the definition.  Per entry the rows of position a, image a, position b, image b
+// and typeid; u = x + (image . box vectors) per frame in the definition's association (u = x without an image chunk: no
+// product is formed), d = u_b - u_a, with the minimum image folded z, y, x into frame b's box, s = (d0*d0 + d1*d1) +
+// d2*d2; the values are d[a] and s, and s is the one whose largest is kept.  With `out`, entry k's d goes to
+// out[3 k .. 3 k + 2].
 
 // u = x + image . vectors of one frame, in the definition's association
 __device__ __forceinline__ void disp_unwrap(double u[3], const RowRegs& image, const double v[6])
@@ -600,7 +603,7 @@ __global__ __launch_bounds__(SEL_THREADS) void displacement_tile_kernel(const Di
     constexpr int T = F64 ? STATS_F64 : STATS_F32;
     constexpr int W3 = F64 ? 6 : 3;    // 32-bit words of a position row
     constexpr int BATCH = F64 ? 2 : 4; // entries a lane has in flight (up to 19 and 13 words each)
-    constexpr int Q = DISP_Q, NU = 3 * TG + 1;
+    constexpr int Q = DISPLACEMENT_SUMS, NU = 3 * TG + 1;
     __shared__ double wave_d[(Q + 1) * TG][STATS_WAVES];
     __shared__ uint32_t wave_u[NU][STATS_WAVES];
     const uint32_t tile = blockIdx.x;
@@ -620,7 +623,7 @@ __global__ __launch_bounds__(SEL_THREADS) void displacement_tile_kernel(const Di
         cnt[t] = bad[t] = 0;
         seen[t] = false;
         mx[t] = -__builtin_huge_val();
-        at[t] = DISP_NO_ENTRY;
+        at[t] = GROUPED_NO_ENTRY;
 #pragma unroll
         for (int q = 0; q < Q; q++)
             acc[t][q] = 0.0;
@@ -736,7 +739,7 @@ __global__ __launch_bounds__(SEL_THREADS) void displacement_tile_kernel(const Di
             }
         if (seen[t])
             {
-            disp_wave_pair(mx[t], at[t]);
+            grouped_wave_pair(mx[t], at[t]);
 #pragma unroll
             for (int h = 32; h >= 1; h >>= 1)
                 {
@@ -772,7 +775,7 @@ __global__ __launch_bounds__(SEL_THREADS) void displacement_tile_kernel(const Di
         uint32_t k = u[0];
 #pragma unroll
         for (int i = 1; i < STATS_WAVES; i++)
-            disp_pair(m, k, w[i], u[i]);
+            grouped_pair(m, k, w[i], u[i]);
         td[(size_t)(Q * TG + t) * n_tiles + tile] = m;
         tu[(size_t)(2 * TG + t) * n_tiles + tile] = k;
         }
@@ -784,45 +787,59 @@ __global__ __launch_bounds__(SEL_THREADS) void displacement_tile_kernel(const Di
         }
     }
 
-// One workgroup per column: the first 4 * TG columns are the sums (stats_final_kernel's walk t, t + 256, ... per lane,
-// then the block tree), the next TG the largest values with their entries (the pair rule; the order is free), the last
-// 2 * TG + 1 the counters.  out: see DISP_WORD_*; the flag word is handed over and cleared as there.
-__global__ __launch_bounds__(SEL_THREADS) void displacement_final_kernel(const double* __restrict__ td,
-                                                                         const uint32_t* __restrict__ tu, uint32_t n_tiles,
-                                                                         uint32_t TG, uint32_t* flag_dev,
-                                                                         uint64_t* __restrict__ out)
+struct DisplacementPass
+    {
+    using Args = DisplacementArgs;
+    static constexpr uint32_t Q = DISPLACEMENT_SUMS, TYPEID = 4;
+    static constexpr bool LARGEST = true;
+    static constexpr const char* what = "frame displacements";
+    static const char* refusal(const Args& d)
+        {
+        if (d.minimum_image && (d.chunk[1] || d.chunk[3]))
+            return "the minimum image is taken without image chunks";
+        if (d.dimensions != 2 && d.dimensions != 3)
+            return "dimensions is 2 or 3";
+        return nullptr;
+        }
+    static bool ready(const Args& d) { return d.chunk[0] && d.chunk[2]; }
+    static constexpr uint64_t N_LIMIT = 1ull << 32;
+    template<bool G, bool F64, int TG> static auto kernel() { return displacement_tile_kernel<G, F64, TG>; }
+    };
+
+// One workgroup per column: the first Q * TG columns are the sums (stats_final_kernel's walk t, t + 256, ... per lane,
+// then the block tree), the next TG -- with `largest` -- the largest values with their entries (the pair rule; the order
+// is free), the last 2 * TG + 1 the counters that are summed (entries and bad per type, other).  out: see
+// grouped_word_*; the flag word is handed over and cleared as there.
+__global__ __launch_bounds__(SEL_THREADS) void grouped_final_kernel(const double* __restrict__ td, const uint32_t* __restrict__ tu,
+                                                                    uint32_t n_tiles, uint32_t Q, uint32_t TG, uint32_t largest,
+                                                                    uint32_t* flag_dev, uint64_t* __restrict__ out)
     {
 #pragma clang fp contract(off)
     __shared__ double wave_d[STATS_WAVES];
     __shared__ uint64_t wave_u[STATS_WAVES];
     const uint32_t b = blockIdx.x;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t n_sums = DISP_Q * TG, n_d = n_sums + TG;
+    const uint32_t n_sums = Q * TG, n_d = n_sums + largest * TG;
     double* values = (double*)out;
     if (b < n_sums)
         {
-        const double* t_sum = td + (size_t)b * n_tiles;
-        double sum = 0.0;
-#pragma unroll 8
-        for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
-            sum = sum + t_sum[t];
-        sum = stats_wave_sum(sum);
+        const double sum = stats_column_sum(td + (size_t)b * n_tiles, n_tiles);
         if (lane == 0)
             wave_d[wave] = sum;
         __syncthreads();
         if (threadIdx.x == 0)
-            values[b] = (wave_d[0] + wave_d[1]) + (wave_d[2] + wave_d[3]);
+            values[b] = stats_block_sum(wave_d);
         }
     else if (b < n_d)
         {
         const double* t_max = td + (size_t)b * n_tiles;
         const uint32_t* t_at = tu + (size_t)(2 * TG + (b - n_sums)) * n_tiles;
         double mx = -__builtin_huge_val();
-        uint32_t at = DISP_NO_ENTRY;
+        uint32_t at = GROUPED_NO_ENTRY;
 #pragma unroll 8
         for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
-            disp_pair(mx, at, t_max[t], t_at[t]);
-        disp_wave_pair(mx, at);
+            grouped_pair(mx, at, t_max[t], t_at[t]);
+        grouped_wave_pair(mx, at);
         if (lane == 0)
             {
             wave_d[wave] = mx;
@@ -832,31 +849,29 @@ __global__ __launch_bounds__(SEL_THREADS) void displacement_final_kernel(const d
         if (threadIdx.x == 0)
             {
             for (int i = 1; i < STATS_WAVES; i++)
-                disp_pair(mx, at, wave_d[i], (uint32_t)wave_u[i]);
+                grouped_pair(mx, at, wave_d[i], (uint32_t)wave_u[i]);
             values[b] = mx;
-            out[DISP_WORD_ENTRIES + (b - n_sums)] = at;
+            out[grouped_word_entries(Q, largest) + (b - n_sums)] = at;
             }
         }
     else
         {
         const uint32_t j = b - n_d; // entries and bad per type, then other
-        const uint32_t* t_cnt = tu + (size_t)(j < 2 * TG ? j : 3 * TG) * n_tiles;
+        const uint32_t* t_cnt = tu + (size_t)(j < 2 * TG ? j : (2 + largest) * TG) * n_tiles;
         uint64_t count = 0;
 #pragma unroll 8
         for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
             count += t_cnt[t];
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1)
-            count += (uint64_t)__shfl_xor((unsigned long long)count, h, 64);
+        count = stats_wave_count(count);
         if (lane == 0)
             wave_u[wave] = count;
         __syncthreads();
         if (threadIdx.x == 0)
-            out[DISP_WORD_COUNTERS + j] = wave_u[0] + wave_u[1] + wave_u[2] + wave_u[3];
+            out[grouped_word_counters(Q, largest) + j] = wave_u[0] + wave_u[1] + wave_u[2] + wave_u[3];
         }
     if (b == 0 && threadIdx.x == 0)
         {
-        out[DISP_WORD_FLAG] = *flag_dev;
+        out[grouped_word_flag(Q, largest)] = *flag_dev;
         *flag_dev = 0u;
         }
     }
@@ -995,159 +1010,94 @@ int launch_chunk_stats(const StatsArgs& s, uint64_t* out_counts, double* out_val
 
 namespace
     {
-template<bool G, bool F64, int TG>
-void moments_tile_launch(const MomentsArgs& m, uint32_t n_tiles, double* td, uint32_t* tu, uint32_t* flag_dev,
-                         uint32_t* flag_host, hipStream_t stream)
+template<class Pass, bool G, bool F64>
+void grouped_tile_by_group(const typename Pass::Args& a, uint32_t TG, uint32_t n_tiles, const StatsLaunch& sc, hipStream_t stream)
     {
-    hipLaunchKernelGGL((moments_tile_kernel<G, F64, TG>), dim3(n_tiles), dim3(SEL_THREADS), 0, stream, m, n_tiles, td, tu,
-                       flag_dev, flag_host);
-    }
-
-template<bool G, bool F64>
-void moments_tile_by_group(const MomentsArgs& m, uint32_t TG, uint32_t n_tiles, double* td, uint32_t* tu, uint32_t* flag_dev,
-                           uint32_t* flag_host, hipStream_t stream)
+    const auto launch = [&](auto kernel)
     {
+        hipLaunchKernelGGL(kernel, dim3(n_tiles), dim3(SEL_THREADS), 0, stream, a, n_tiles, sc.td, sc.tu, sc.flag_dev,
+                           sc.flag_host_dev);
+    };
     switch (TG)
         {
-        case 1: return moments_tile_launch<G, F64, 1>(m, n_tiles, td, tu, flag_dev, flag_host, stream);
-        case 2: return moments_tile_launch<G, F64, 2>(m, n_tiles, td, tu, flag_dev, flag_host, stream);
-        default: return moments_tile_launch<G, F64, 4>(m, n_tiles, td, tu, flag_dev, flag_host, stream);
+        case 1: return launch(Pass::template kernel<G, F64, 1>());
+        case 2: return launch(Pass::template kernel<G, F64, 2>());
+        default: return launch(Pass::template kernel<G, F64, 4>());
         }
+    }
+
+// Either grouped reduction: out_counts n_types x (entries, bad[, largest entry or UINT64_MAX]), then the entries of no
+// type of the group; out_values n_types x (Q sums[, the largest value]).
+template<class Pass>
+int launch_grouped(const typename Pass::Args& a, uint64_t* out_counts, double* out_values, hipStream_t stream, std::string* err)
+    {
+    constexpr uint32_t Q = Pass::Q, L = Pass::LARGEST ? 1 : 0;
+    const auto fail = [err](const char* why)
+    { return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, std::string(Pass::what) + ": " + why); };
+    static const char* outside_msg = "an entry of the row list lies outside the chunks (nothing was computed)";
+    if (!out_counts || !out_values || a.n_types < 1 || a.n_types > GROUPED_MAX_TYPES || (!a.chunk[Pass::TYPEID] && a.n_types != 1))
+        return fail("1 to 4 types, one without a typeid chunk");
+    if (const char* why = Pass::refusal(a))
+        return fail(why);
+    const uint64_t n = a.rows ? a.n : a.N;
+    if (n >= (1ull << 32) || a.N >= Pass::N_LIMIT)
+        return fail("2^32 rows or entries and more are not indexed");
+    if (n == 0)
+        {
+        grouped_of_nothing(Q, Pass::LARGEST, a.n_types, out_counts, out_values);
+        return PGSD_SUCCESS;
+        }
+    if (a.N == 0)
+        return fail(outside_msg);
+    if (!Pass::ready(a))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const uint32_t TG = a.n_types == 3 ? 4u : a.n_types; // the kernels' group sizes: 1, 2, 4
+    const uint32_t n_d = (Q + L) * TG, n_u = (2 + L) * TG + 1;
+    const uint32_t n_tiles = (uint32_t)((n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK);
+    const size_t td_bytes = (size_t)n_d * n_tiles * sizeof(double), tu_bytes = (size_t)n_u * n_tiles * sizeof(uint32_t);
+    StatsLaunch sc(td_bytes, tu_bytes, stream, err);
+    if (sc.scope.rc() != PGSD_SUCCESS)
+        return sc.scope.rc();
+    if (a.rows)
+        a.f64 ? grouped_tile_by_group<Pass, true, true>(a, TG, n_tiles, sc, stream)
+              : grouped_tile_by_group<Pass, true, false>(a, TG, n_tiles, sc, stream);
+    else
+        a.f64 ? grouped_tile_by_group<Pass, false, true>(a, TG, n_tiles, sc, stream)
+              : grouped_tile_by_group<Pass, false, false>(a, TG, n_tiles, sc, stream);
+    // one workgroup per sum and per largest value, and per counter that is summed (entries, bad, other)
+    hipLaunchKernelGGL(grouped_final_kernel, dim3(n_d + 2 * TG + 1), dim3(SEL_THREADS), 0, stream, sc.td, sc.tu, n_tiles, Q, TG,
+                       L, sc.flag_dev, sc.result);
+    bool outside = false;
+    const int rc = sc.finish(Pass::what, grouped_word_flag(Q, Pass::LARGEST) + 1, grouped_word_flag(Q, Pass::LARGEST), &outside);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (outside)
+        return fail(outside_msg);
+    const double* values = (const double*)sc.host;
+    const uint64_t* counters = sc.host + grouped_word_counters(Q, Pass::LARGEST);
+    const uint64_t* entries = sc.host + grouped_word_entries(Q, Pass::LARGEST);
+    for (uint32_t t = 0; t < a.n_types; t++)
+        {
+        out_counts[(2 + L) * t + 0] = counters[t];
+        out_counts[(2 + L) * t + 1] = counters[TG + t];
+        if (Pass::LARGEST)
+            out_counts[(2 + L) * t + 2] = entries[t] == GROUPED_NO_ENTRY ? UINT64_MAX : entries[t];
+        for (uint32_t q = 0; q < Q + L; q++)
+            out_values[(Q + L) * t + q] = values[q * TG + t];
+        }
+    out_counts[(2 + L) * a.n_types] = counters[2 * TG];
+    return PGSD_SUCCESS;
     }
     } // namespace
 
 int launch_frame_moments(const MomentsArgs& m, uint64_t* out_counts, double* out_sums, hipStream_t stream, std::string* err)
     {
-    if (!out_counts || !out_sums || m.n_types < 1 || m.n_types > MOMENTS_MAX_TYPES || (!m.chunk[0] && m.n_types != 1))
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "conservation sums: 1 to 4 types, one without a typeid chunk");
-    const uint64_t n = m.rows ? m.n : m.N;
-    if (n >= (1ull << 32) || m.N > (1ull << 32))
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "conservation sums: 2^32 rows or entries and more are not indexed");
-    if (n == 0)
-        {
-        std::fill(out_counts, out_counts + 2 * m.n_types + 1, 0);
-        std::fill(out_sums, out_sums + MOMENTS_QUANTITIES * m.n_types, 0.0);
-        return PGSD_SUCCESS;
-        }
-    if (m.N == 0)
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
-                           "conservation sums: an entry of the row list lies outside the chunks (nothing was computed)");
-    const uint32_t TG = m.n_types == 3 ? 4u : m.n_types; // the kernels' group sizes: 1, 2, 4
-    const uint32_t n_d = MOMENTS_QUANTITIES * TG, n_u = 2 * TG + 1;
-    const uint32_t n_tiles = (uint32_t)((n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK);
-    const size_t td_bytes = (size_t)n_d * n_tiles * sizeof(double), tu_bytes = (size_t)n_u * n_tiles * sizeof(uint32_t);
-    StatsLaunch sc(td_bytes, tu_bytes, stream, err);
-    if (sc.scope.rc() != PGSD_SUCCESS)
-        return sc.scope.rc();
-    if (m.rows)
-        m.f64 ? moments_tile_by_group<true, true>(m, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream)
-              : moments_tile_by_group<true, false>(m, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
-    else
-        m.f64 ? moments_tile_by_group<false, true>(m, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream)
-              : moments_tile_by_group<false, false>(m, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
-    hipLaunchKernelGGL(moments_final_kernel, dim3(n_d + n_u), dim3(SEL_THREADS), 0, stream, sc.td, sc.tu, n_tiles, n_d,
-                       sc.flag_dev, sc.result);
-    bool outside = false;
-    const int rc = sc.finish("conservation sums", MOMENTS_RESULT_WORDS, MOMENTS_RESULT_WORDS - 1, &outside);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    if (outside)
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
-                           "conservation sums: an entry of the row list lies outside the chunks (nothing was computed)");
-    const double* sums = (const double*)sc.host;
-    const uint64_t* counters = sc.host + MOMENTS_QUANTITIES * MOMENTS_MAX_TYPES;
-    for (uint32_t t = 0; t < m.n_types; t++)
-        {
-        out_counts[2 * t + 0] = counters[t];
-        out_counts[2 * t + 1] = counters[TG + t];
-        for (uint32_t q = 0; q < MOMENTS_QUANTITIES; q++)
-            out_sums[MOMENTS_QUANTITIES * t + q] = sums[q * TG + t];
-        }
-    out_counts[2 * m.n_types] = counters[2 * TG];
-    return PGSD_SUCCESS;
+    return launch_grouped<MomentsPass>(m, out_counts, out_sums, stream, err);
     }
-
-namespace
-    {
-template<bool G, bool F64, int TG>
-void displacement_tile_launch(const DisplacementArgs& d, uint32_t n_tiles, double* td, uint32_t* tu, uint32_t* flag_dev,
-                              uint32_t* flag_host, hipStream_t stream)
-    {
-    hipLaunchKernelGGL((displacement_tile_kernel<G, F64, TG>), dim3(n_tiles), dim3(SEL_THREADS), 0, stream, d, n_tiles, td, tu,
-                       flag_dev, flag_host);
-    }
-
-template<bool G, bool F64>
-void displacement_tile_by_group(const DisplacementArgs& d, uint32_t TG, uint32_t n_tiles, double* td, uint32_t* tu,
-                                uint32_t* flag_dev, uint32_t* flag_host, hipStream_t stream)
-    {
-    switch (TG)
-        {
-        case 1: return displacement_tile_launch<G, F64, 1>(d, n_tiles, td, tu, flag_dev, flag_host, stream);
-        case 2: return displacement_tile_launch<G, F64, 2>(d, n_tiles, td, tu, flag_dev, flag_host, stream);
-        default: return displacement_tile_launch<G, F64, 4>(d, n_tiles, td, tu, flag_dev, flag_host, stream);
-        }
-    }
-    } // namespace
 
 int launch_frame_displacements(const DisplacementArgs& d, uint64_t* out_counts, double* out_values, hipStream_t stream,
                                std::string* err)
     {
-    static const char* outside_msg
-        = "frame displacements: an entry of the row list lies outside the chunks (nothing was computed)";
-    if (!out_counts || !out_values || d.n_types < 1 || d.n_types > DISPLACEMENT_MAX_TYPES || (!d.chunk[4] && d.n_types != 1))
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "frame displacements: 1 to 4 types, one without a typeid chunk");
-    if (d.minimum_image && (d.chunk[1] || d.chunk[3]))
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
-                           "frame displacements: the minimum image is taken without image chunks");
-    if (d.dimensions != 2 && d.dimensions != 3)
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "frame displacements: dimensions is 2 or 3");
-    const uint64_t n = d.rows ? d.n : d.N;
-    if (n >= (1ull << 32) || d.N >= (1ull << 32))
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, "frame displacements: 2^32 rows or entries and more are not indexed");
-    if (n == 0)
-        {
-        displacements_of_nothing(d.n_types, out_counts, out_values);
-        return PGSD_SUCCESS;
-        }
-    if (d.N == 0)
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, outside_msg);
-    if (!d.chunk[0] || !d.chunk[2])
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    const uint32_t TG = d.n_types == 3 ? 4u : d.n_types; // the kernels' group sizes: 1, 2, 4
-    const uint32_t n_d = DISPLACEMENT_VALUES * TG, n_u = 3 * TG + 1;
-    const uint32_t n_tiles = (uint32_t)((n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK);
-    const size_t td_bytes = (size_t)n_d * n_tiles * sizeof(double), tu_bytes = (size_t)n_u * n_tiles * sizeof(uint32_t);
-    StatsLaunch sc(td_bytes, tu_bytes, stream, err);
-    if (sc.scope.rc() != PGSD_SUCCESS)
-        return sc.scope.rc();
-    if (d.rows)
-        d.f64 ? displacement_tile_by_group<true, true>(d, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream)
-              : displacement_tile_by_group<true, false>(d, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
-    else
-        d.f64 ? displacement_tile_by_group<false, true>(d, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream)
-              : displacement_tile_by_group<false, false>(d, TG, n_tiles, sc.td, sc.tu, sc.flag_dev, sc.flag_host_dev, stream);
-    // one workgroup per sum and per largest value, and per counter that is summed (entries, bad, other)
-    hipLaunchKernelGGL(displacement_final_kernel, dim3(n_d + 2 * TG + 1), dim3(SEL_THREADS), 0, stream, sc.td, sc.tu, n_tiles,
-                       TG, sc.flag_dev, sc.result);
-    bool outside = false;
-    const int rc = sc.finish("frame displacements", DISPLACEMENT_RESULT_WORDS, DISP_WORD_FLAG, &outside);
-    if (rc != PGSD_SUCCESS)
-        return rc;
-    if (outside)
-        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, outside_msg);
-    const double* values = (const double*)sc.host;
-    const uint64_t* counters = sc.host + DISP_WORD_COUNTERS;
-    const uint64_t* entries = sc.host + DISP_WORD_ENTRIES;
-    for (uint32_t t = 0; t < d.n_types; t++)
-        {
-        out_counts[3 * t + 0] = counters[t];
-        out_counts[3 * t + 1] = counters[TG + t];
-        out_counts[3 * t + 2] = entries[t] == DISP_NO_ENTRY ? UINT64_MAX : entries[t];
-        for (uint32_t q = 0; q < DISPLACEMENT_VALUES; q++)
-            out_values[DISPLACEMENT_VALUES * t + q] = values[q * TG + t];
-        }
-    out_counts[3 * d.n_types] = counters[2 * TG];
-    return PGSD_SUCCESS;
+    return launch_grouped<DisplacementPass>(d, out_counts, out_values, stream, err);
     }
     } // namespace pgsd_amd

@@ -519,6 +519,29 @@ def _index_rows(rows):
     return ptr, nbytes // 4
 
 
+cdef uint32_t _no_rows = 0      # where an empty row list stands: it may have no address of its own, and nothing of it is read
+
+
+def _row_list(who, rows, n):
+    """(address, entries) of the first ``n`` entries (default: all) of a row list in GPU memory.  An empty list is still
+    a list -- its result is that of no entry, not of every row -- and gets an address that is valid."""
+    p_rows, n_rows = _index_rows(rows)
+    count = n_rows if n is None else int(n)
+    if count >= (1 << 32):
+        raise ValueError("%s: a row list holds fewer than 2^32 entries" % who)
+    if count < 0 or count > n_rows:
+        raise ValueError("%s: rows holds fewer entries than n" % who)
+    return (<uintptr_t>&_no_rows if count == 0 else p_rows), count
+
+
+cdef _raise_refused(who, int retval, fallback, extra, int err):
+    """A reduction's return code -> exception: a refusal is a ValueError that carries the library's message."""
+    if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
+        msg = C.pgsd_last_error_string()
+        raise ValueError("%s: %s" % (who, msg.decode('utf-8', 'replace') if msg != NULL else fallback))
+    _raise_on_error(retval, extra, err)
+
+
 def _rows2d(x, what):
     """(address, numpy dtype, rows, width, row stride in elements) of a 1-D or row-major 2-D array in GPU memory, rows
     possibly strided: a torch GPU tensor, a :class:`DeviceBuffer` or any object with ``__cuda_array_interface__``
@@ -1482,6 +1505,19 @@ cdef class PGSDFile:
         entry[0] = e[0]
         return 0
 
+    cdef int _entries(self, chunks, C.pgsd_index_entry* entries, const C.pgsd_index_entry** given) except -1:
+        """The five chunk slots of a grouped reduction, each ``(frame, name)`` or ``None``: :meth:`_entry` of every chunk
+        that is given, NULL for the others."""
+        cdef int i
+        for i in range(5):
+            given[i] = NULL
+            if chunks[i] is not None:
+                frame, name = chunks[i]
+                self._entry(frame, name, &entries[i])
+                given[i] = &entries[i]
+        self._check_open()
+        return 0
+
     cdef _read_entry(self, const C.pgsd_index_entry* e, uint64_t height, uint64_t c_N, uint32_t c_M, uint32_t c_off,
                      bint c_all):
         """`pgsd_read_chunk` into a new numpy array of ``height`` rows: ``(height,)`` for Nx1 chunks, ``(height, M)``
@@ -1665,20 +1701,9 @@ cdef class PGSDFile:
         cdef C.pgsd_index_entry entry
         self._entry(frame, name, &entry)
         cdef uintptr_t c_rows = 0
-        cdef uint32_t c_empty = 0
         count = 0
         if rows is not None:
-            p_rows, n_rows = _index_rows(rows)
-            count = n_rows if n is None else int(n)
-            if count >= (1 << 32):
-                raise ValueError("chunk_stats_device: a row list holds fewer than 2^32 entries")
-            if count < 0 or count > n_rows:
-                raise ValueError("chunk_stats_device: rows holds fewer entries than n")
-            c_rows = p_rows
-            if count == 0:
-                # an empty list is still a list -- its statistics are those of no entry, not of the whole chunk --, but
-                # may have no address: nothing of it is read
-                c_rows = <uintptr_t>&c_empty
+            c_rows, count = _row_list("chunk_stats_device", rows, n)
         elif n is not None:
             raise ValueError("chunk_stats_device: n goes with rows")
         columns = int(entry.M) + (1 if norm2 else 0)
@@ -1694,10 +1719,7 @@ cdef class PGSDFile:
             retval = C.pgsd_chunk_stats_device(&self._handle, &entry, <const uint32_t*>c_rows, c_n, c_norm2,
                                                <uint64_t*>c_counts, <double*>c_values)
             err = errno
-        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
-            msg = C.pgsd_last_error_string()
-            raise ValueError("chunk_stats_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else name))
-        _raise_on_error(retval, self._name, err)
+        _raise_refused("chunk_stats_device", retval, name, self._name, err)
         counts = counts.astype(numpy.int64)
         return _hoomd.FieldStats(counts[:, 0].copy(), counts[:, 1].copy(), counts[:, 2].copy(), values[:, 0].copy(),
                                  values[:, 1].copy(), values[:, 2].copy())
@@ -1731,14 +1753,7 @@ cdef class PGSDFile:
         chunks = list(chunks)
         if len(chunks) != 5:
             raise ValueError("frame_moments_device: chunks holds typeid, mass, velocity, energy, position (or None)")
-        cdef int i
-        for i in range(5):
-            given[i] = NULL
-            if chunks[i] is not None:
-                frame, name = chunks[i]
-                self._entry(frame, name, &entries[i])
-                given[i] = &entries[i]
-        self._check_open()
+        self._entries(chunks, entries, given)
         c_defaults = numpy.ascontiguousarray(
             numpy.array([1, 0, 0, 0, 0, 0, 0, 0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
         if c_defaults.shape[0] != 8:
@@ -1746,18 +1761,9 @@ cdef class PGSDFile:
         if not 0 <= int(type0) < (1 << 32) or not 0 <= int(n_types) < (1 << 32):
             raise ValueError("frame_moments_device: a call takes 1 to 4 types from a type id on")
         cdef uintptr_t c_rows = 0
-        cdef uint32_t c_empty = 0
         count = 0
         if rows is not None:
-            p_rows, n_rows = _index_rows(rows)
-            count = n_rows if n is None else int(n)
-            if count >= (1 << 32):
-                raise ValueError("frame_moments_device: a row list holds fewer than 2^32 entries")
-            if count < 0 or count > n_rows:
-                raise ValueError("frame_moments_device: rows holds fewer entries than n")
-            c_rows = p_rows
-            if count == 0:
-                c_rows = <uintptr_t>&c_empty      # an empty list is still a list, but may have no address
+            c_rows, count = _row_list("frame_moments_device", rows, n)
         elif n is not None:
             if any(c is not None for c in chunks):
                 raise ValueError("frame_moments_device: n goes with rows, or with no chunk at all")
@@ -1780,10 +1786,7 @@ cdef class PGSDFile:
                                                  <const double*>c_pdef, c_type0, c_ntypes, <const uint32_t*>c_rows, c_n,
                                                  <uint64_t*>c_counts, <double*>c_sums)
             err = errno
-        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
-            msg = C.pgsd_last_error_string()
-            raise ValueError("frame_moments_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else "refused"))
-        _raise_on_error(retval, self._name, err)
+        _raise_refused("frame_moments_device", retval, "refused", self._name, err)
         counts = counts.astype(numpy.int64)
         return _hoomd.Moments.from_sums(counts[0:2 * T:2].copy(), counts[1:2 * T:2].copy(), int(counts[2 * T]), sums)
 
@@ -1822,14 +1825,7 @@ cdef class PGSDFile:
                              "(the images and the typeid may be None)")
         if chunks[0] is None or chunks[2] is None:
             raise ValueError("frame_displacements_device: both positions are chunks of the file")
-        cdef int i
-        for i in range(5):
-            given[i] = NULL
-            if chunks[i] is not None:
-                frame, name = chunks[i]
-                self._entry(frame, name, &entries[i])
-                given[i] = &entries[i]
-        self._check_open()
+        self._entries(chunks, entries, given)
         c_va = numpy.ascontiguousarray(numpy.asarray(vectors_a, dtype=numpy.float64).reshape(-1))
         c_vb = numpy.ascontiguousarray(numpy.asarray(vectors_b, dtype=numpy.float64).reshape(-1))
         if c_va.shape[0] != 6 or c_vb.shape[0] != 6:
@@ -1837,18 +1833,9 @@ cdef class PGSDFile:
         if not 0 <= int(type0) < (1 << 32) or not 0 <= int(n_types) < (1 << 32) or not 0 <= int(dimensions) < (1 << 32):
             raise ValueError("frame_displacements_device: a call takes 1 to 4 types from a type id on, in 2 or 3 dimensions")
         cdef uintptr_t c_rows = 0, c_out = 0
-        cdef uint32_t c_empty = 0
         count = int(entries[0].N)
         if rows is not None:
-            p_rows, n_rows = _index_rows(rows)
-            count = n_rows if n is None else int(n)
-            if count >= (1 << 32):
-                raise ValueError("frame_displacements_device: a row list holds fewer than 2^32 entries")
-            if count < 0 or count > n_rows:
-                raise ValueError("frame_displacements_device: rows holds fewer entries than n")
-            c_rows = p_rows
-            if count == 0:
-                c_rows = <uintptr_t>&c_empty      # an empty list is still a list, but may have no address
+            c_rows, count = _row_list("frame_displacements_device", rows, n)
         elif n is not None:
             raise ValueError("frame_displacements_device: n goes with rows")
         if out is not None:
@@ -1873,10 +1860,7 @@ cdef class PGSDFile:
                                                        c_ntypes, <const uint32_t*>c_rows, c_n, <double*>c_out,
                                                        <uint64_t*>c_counts, <double*>c_values)
             err = errno
-        if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
-            msg = C.pgsd_last_error_string()
-            raise ValueError("frame_displacements_device: %s" % (msg.decode('utf-8', 'replace') if msg != NULL else "refused"))
-        _raise_on_error(retval, self._name, err)
+        _raise_refused("frame_displacements_device", retval, "refused", self._name, err)
         entry = counts[2:3 * T:3].astype(numpy.int64)            # (UINT64_MAX, no entry, becomes -1)
         counts = counts.astype(numpy.int64)
         return _hoomd.Displacements.from_sums(counts[0:3 * T:3].copy(), counts[1:3 * T:3].copy(), entry, int(counts[3 * T]),

@@ -3012,27 +3012,13 @@ class HOOMDTrajectory(object):
         ``norm2`` column: ``stats['velocity'].max[3]`` is the square of the largest speed.  A field that is stored
         nowhere is all defaults and is answered on the host from the one default row.
         """
-        if idx < 0:
-            idx += len(self)
-        if idx >= len(self) or idx < 0:
-            raise IndexError()
+        idx = self._frame_index(idx)
         names = _stats_fields(fields)
         f = self.file
         box, dims, n_global, f_pos = self._census_frame(idx)
-        rows, count, staged = None, n_global, []
+        rows = None
         try:
-            if where is not None:
-                ft = self._frame_of(idx, 'particles/types')
-                types = ParticleData._default_value['types'] if ft is None else _decode_strings(
-                    self._frame0_small('particles/types') if ft == 0 else f.read_chunk(ft, 'particles/types'))
-                if domain is not None and not isinstance(domain, Domain):
-                    domain = Domain(*domain)
-                rows, count, staged = self._where_row_list(idx, types, box, dims, where, domain, False, n_global)
-            elif domain is not None:
-                if not isinstance(domain, Domain):
-                    domain = Domain(*domain)
-                rows, count = self._domain_row_list(f_pos, box, dims, domain, n_global)
-                staged = ['position']
+            rows, count, staged = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
             # the fields whose chunks the selection left staged come first and share one wait: they are not read again
             first = [name for name in names if name in staged]
             out = {}
@@ -3076,23 +3062,12 @@ class HOOMDTrajectory(object):
         staged chunks, so no file byte is read twice; one `wait_read` at the end releases them.  No per-particle data
         reaches the host.  ``position`` is used as stored: see `frame_moments`.
         """
-        if idx < 0:
-            idx += len(self)
-        if idx >= len(self) or idx < 0:
-            raise IndexError()
+        idx = self._frame_index(idx)
         f = self.file
         box, dims, n_global, f_pos = self._census_frame(idx)
-        ft = self._frame_of(idx, 'particles/types')
-        types = ParticleData._default_value['types'] if ft is None else _decode_strings(
-            self._frame0_small('particles/types') if ft == 0 else f.read_chunk(ft, 'particles/types'))
-        if domain is not None and not isinstance(domain, Domain):
-            domain = Domain(*domain)
-        rows, count = None, n_global
+        types = self._types_of(idx)
         try:
-            if where is not None:
-                rows, count, _ = self._where_row_list(idx, types, box, dims, where, domain, False, n_global)
-            elif domain is not None:
-                rows, count = self._domain_row_list(f_pos, box, dims, domain, n_global)
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos, types)
             names = ['typeid' if by_type else None, 'mass', 'velocity', 'energy', 'position' if centre else None]
             chunks = []
             for name in names:
@@ -3101,22 +3076,45 @@ class HOOMDTrajectory(object):
             defaults = numpy.concatenate([numpy.broadcast_to(numpy.asarray(_PARTICLE_FIELDS[name][2], dtype=numpy.float32),
                                                              (M,)) for name, M, _ in _MOMENTS_INPUTS]).astype(numpy.float64)
             n = count if rows is not None or all(c is None for c in chunks) else None
-            T = len(types)
-            if by_type and T == 0:
-                return Moments.from_sums([], [], count, numpy.zeros((0, _MOMENTS_QUANTITIES)))
-            if not by_type or chunks[0] is None:
-                # one group; by type without a stored typeid every particle is of type 0
-                part = f.frame_moments_device(chunks, defaults, rows=rows, n=n)
-                if not by_type or T == 1:
-                    return part
-                zero = Moments.from_sums([0] * (T - 1), [0] * (T - 1), 0, numpy.zeros((T - 1, _MOMENTS_QUANTITIES)))
-                return Moments.concatenate([part, zero], count)
-            parts = [f.frame_moments_device(chunks, defaults, type0=t0, n_types=min(_MOMENTS_MAX_TYPES, T - t0),
-                                            rows=rows, n=n)
-                     for t0 in range(0, T, _MOMENTS_MAX_TYPES)]
-            return Moments.concatenate(parts, count)
+            return self._grouped_by_type(
+                lambda t0, n_types: f.frame_moments_device(chunks, defaults, type0=t0, n_types=n_types, rows=rows, n=n),
+                Moments, lambda k: Moments.from_sums([0] * k, [0] * k, 0, numpy.zeros((k, _MOMENTS_QUANTITIES))),
+                _MOMENTS_MAX_TYPES, len(types), by_type, chunks[0] is not None, count)
         finally:
             f.wait_read()
+
+    def _types_of(self, idx):
+        """The type names frame ``idx`` reads: its own, else frame 0's, else the schema's default."""
+        ft = self._frame_of(idx, 'particles/types')
+        return ParticleData._default_value['types'] if ft is None else _decode_strings(
+            self._frame0_small('particles/types') if ft == 0 else self.file.read_chunk(ft, 'particles/types'))
+
+    def _selection_row_list(self, idx, where, domain, box, dims, n_global, f_pos, types=None):
+        """``where``, ``domain`` or both, selected on the GPU in frame ``idx``: ``(rows, count, staged)`` -- the row list
+        in GPU memory, its entries and the fields whose chunks the selection left staged --; without a selection every
+        row counts and no row list exists: ``(None, n_global, [])``."""
+        if domain is not None and not isinstance(domain, Domain):
+            domain = Domain(*domain)
+        if where is not None:
+            return self._where_row_list(idx, self._types_of(idx) if types is None else types, box, dims, where, domain,
+                                        False, n_global)
+        if domain is not None:
+            rows, count = self._domain_row_list(f_pos, box, dims, domain, n_global)
+            return rows, count, ['position']
+        return None, n_global, []
+
+    @staticmethod
+    def _grouped_by_type(launch, cls, nothing, group, T, by_type, has_typeid, count):
+        """A grouped reduction's result (a ``cls``: `Moments`, `Displacements`) over ``T`` types and ``count`` entries.
+        ``launch(type0, n_types)`` is one pass over the staged chunks for up to ``group`` consecutive types, ``nothing(k)``
+        the result of ``k`` types that hold no entry.  More than ``group`` types take consecutive passes."""
+        if by_type and T == 0:
+            return cls.concatenate([nothing(0)], count)
+        if not by_type or not has_typeid:
+            # one group; by type without a stored typeid every particle is of type 0
+            part = launch(0, 1)
+            return part if not by_type or T == 1 else cls.concatenate([part, nothing(T - 1)], count)
+        return cls.concatenate([launch(t0, min(group, T - t0)) for t0 in range(0, T, group)], count)
 
     def _frame_index(self, idx):
         idx = int(idx)
@@ -3185,17 +3183,9 @@ class HOOMDTrajectory(object):
             # a degenerate file: no kernel path for a position that is all defaults
             got = self.frame_displacements(idx, origin, by_type, images, minimum_image, where, domain, return_rows)
             return (got[0], fl._device_from_host(got[1], f.pipeline_device())) if return_rows else got
-        ft = self._frame_of(idx, 'particles/types')
-        types = ParticleData._default_value['types'] if ft is None else _decode_strings(
-            self._frame0_small('particles/types') if ft == 0 else f.read_chunk(ft, 'particles/types'))
-        if domain is not None and not isinstance(domain, Domain):
-            domain = Domain(*domain)
-        rows, count = None, n_global
+        types = self._types_of(idx)
         try:
-            if where is not None:
-                rows, count, _ = self._where_row_list(idx, types, box, dims, where, domain, False, n_global)
-            elif domain is not None:
-                rows, count = self._domain_row_list(f_pos, box, dims, domain, n_global)
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos, types)
             chunks = [(f_pos_o, 'particles/position'), None, (f_pos, 'particles/position'), None, None]
             for slot, at, name, wanted in ((1, origin, 'image', images), (3, idx, 'image', images), (4, idx, 'typeid', by_type)):
                 fr = self._effective_frame(at, 'particles/' + name, n_global) if wanted else None
@@ -3208,24 +3198,18 @@ class HOOMDTrajectory(object):
                 result = out if count > 0 else (out.view(shape=(0, 3)) if isinstance(out, fl.DeviceBuffer) else out[:0])
             common = dict(vectors_a=box_vectors(box_o), vectors_b=box_vectors(box), minimum_image=minimum_image,
                           dimensions=dims, rows=rows, n=None if rows is None else count)
-            T = len(types)
-            if by_type and T == 0:
-                if out is not None:
-                    f.frame_displacements_device(chunks[:4] + [None], out=out, **common)
-                got = Displacements.from_sums([], [], [], count, numpy.zeros((0, _DISPLACEMENT_VALUES)))
-            elif not by_type or chunks[4] is None:
-                # one group; by type without a stored typeid every particle is of type 0
-                got = f.frame_displacements_device(chunks, out=out, **common)
-                if by_type and T > 1:
-                    nothing = numpy.zeros((T - 1, _DISPLACEMENT_VALUES))
-                    nothing[:, 4] = -numpy.inf
-                    zero = Displacements.from_sums([0] * (T - 1), [0] * (T - 1), [-1] * (T - 1), 0, nothing)
-                    got = Displacements.concatenate([got, zero], count)
-            else:
-                parts = [f.frame_displacements_device(chunks, type0=t0, n_types=min(_DISPLACEMENT_MAX_TYPES, T - t0),
-                                                      out=out if t0 == 0 else None, **common)
-                         for t0 in range(0, T, _DISPLACEMENT_MAX_TYPES)]
-                got = Displacements.concatenate(parts, count)
+            if by_type and len(types) == 0 and out is not None:
+                f.frame_displacements_device(chunks[:4] + [None], out=out, **common)
+
+            def nothing(k):
+                values = numpy.zeros((k, _DISPLACEMENT_VALUES))
+                values[:, 4] = -numpy.inf
+                return Displacements.from_sums([0] * k, [0] * k, [-1] * k, 0, values)
+
+            got = self._grouped_by_type(
+                lambda t0, n_types: f.frame_displacements_device(chunks, type0=t0, n_types=n_types,
+                                                                 out=out if t0 == 0 else None, **common),
+                Displacements, nothing, _DISPLACEMENT_MAX_TYPES, len(types), by_type, chunks[4] is not None, count)
             return (got, result) if return_rows else got
         finally:
             f.wait_read()

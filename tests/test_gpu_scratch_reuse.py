@@ -58,7 +58,8 @@ def wide(n, dtype=np.float32):
     return (rng.standard_normal(n) * 10.0 ** rng.integers(-3, 12, n)).astype(dtype)
 
 
-# ---- one small file: position chunks of three heights, a four-column chunk of 64 rows, the five inputs of the sums
+# ---- one small file: position chunks of three heights, a four-column chunk of 64 rows, the five inputs of the sums, a
+# second position and an image for the displacements
 A = {'pos5': rng.uniform(-3.0, 3.0, size=(5, 3)).astype(np.float32),
      'pos4096': rng.uniform(-3.0, 3.0, size=(4096, 3)).astype(np.float32),
      'pos70001': rng.uniform(-3.0, 3.0, size=(70001, 3)).astype(np.float32),
@@ -67,11 +68,15 @@ A = {'pos5': rng.uniform(-3.0, 3.0, size=(5, 3)).astype(np.float32),
      'e': wide(64), 'x': rng.uniform(-3.0, 3.0, size=(64, 3)).astype(np.float32)}
 A['c4'][[3, 17, 63], [0, 1, 3]] = [np.nan, np.inf, -0.0]
 A['v'][9, 1] = np.nan
+A['x2'] = rng.uniform(-3.0, 3.0, size=(64, 3)).astype(np.float32)
+A['img'] = rng.integers(-2, 3, size=(64, 3)).astype(np.int32)
 with fl.open(path, 'w', application="test", schema="none", schema_version=[1, 0]) as f:
     for name, a in A.items():
         f.write_chunk(name, a.reshape(len(a), -1))
     f.end_frame()
 MOMENTS = ['tid', 'm', 'v', 'e', 'x']
+DISPLACEMENTS = ['x', None, 'x2', 'img', 'tid']                     # position a, image a, position b, image b, typeid
+VECTORS = hoomd.box_vectors(TRI)
 
 
 def dev(f, rows):
@@ -137,6 +142,21 @@ def check_moments(f, n, n_types=4):
     same_fields(got, want, ('count', 'bad') + sums, sums, ('moments', n))
 
 
+def displacements(f, rows, n_types=4):
+    return f.frame_displacements_device([None if name is None else (0, name) for name in DISPLACEMENTS], VECTORS, VECTORS,
+                                        type0=0, n_types=n_types, rows=dev(f, rows))
+
+
+def check_displacements(f, n, n_types=4):
+    rows = rng.integers(0, 64, size=n).astype(np.int32)
+    got = displacements(f, rows, n_types)
+    want = hoomd.particle_displacements(A['x'], A['x2'], None, A['img'], VECTORS, VECTORS, typeid=A['tid'], type0=0,
+                                        n_types=n_types, rows=rows)
+    assert got.other == want.other, n
+    values = ('drift', 'square', 'largest')
+    same_fields(got, want, ('count', 'bad', 'largest_entry') + values, values, ('displacements', n))
+
+
 def check_domain(f, name, cell):
     rows, count = f.select_domain_device(0, name, TRI, cell)
     want = hoomd.domain_rows(A[name], TRI, cell)
@@ -192,7 +212,8 @@ with fl.open(path, 'r') as f:
         check_hist(f, 'pos5', 2)
     elif case == "interleaved":
         # a halo selection (two compaction sets) between two domain selections of different N; a plan and a compaction of
-        # flags on the same allocation; statistics between two conservation sums
+        # flags on the same allocation; statistics, conservation sums and displacements in turn: one final kernel clears
+        # the flag word behind all grouped calls
         cell = hoomd.domain_grid(2, 2, 1)[1]
         check_domain(f, 'pos5', cell)
         check_halo(f, 'pos70001', cell)
@@ -202,8 +223,11 @@ with fl.open(path, 'r') as f:
         check_halo(f, 'pos4096', cell)
         check_domain(f, 'pos70001', cell)
         check_moments(f, 4097)
+        check_displacements(f, 5)
         check_stats(f, 70001)
+        check_displacements(f, 4097)
         check_moments(f, 5, n_types=2)
+        check_displacements(f, 5001, n_types=2)
         check_stats(f, 5)
         check_order(f, 4097)
         check_hist(f, 'pos4096', 64)
@@ -216,6 +240,12 @@ with fl.open(path, 'r') as f:
         refused(lambda: f.frame_moments_device([(0, name) for name in MOMENTS], n_types=4, rows=dev(f, bad)),
                 "an entry of the row list lies outside the chunks")
         check_moments(f, 5001)
+        check_displacements(f, 5001)
+        # a refused displacement between a statistics call and a sums call: the call before and the call after are exact
+        check_stats(f, 4097)
+        refused(lambda: displacements(f, bad), "an entry of the row list lies outside the chunks")
+        check_moments(f, 4097)
+        check_displacements(f, 5)
         check_stats(f, 63)
         bad[4999] = 4096
         refused(lambda: f.order_rows_by_cell_device(0, 'pos4096', TRI, (8, 8, 4), dev(f, bad)), "outside the position chunk")

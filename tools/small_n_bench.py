@@ -64,6 +64,9 @@ with fl.open(path, 'r') as f:
     timed("order_64^3", lambda: f.order_rows_by_cell_device(0, 'pos', TRI, (64, 64, 64), rows))
     timed("chunk_stats", lambda: f.chunk_stats_device(0, 'v', norm2=True))
     timed("frame_moments", lambda: f.frame_moments_device([(0, k) for k in ('tid', 'm', 'v', 'e', 'pos')], n_types=4))
+    vectors = hoomd.box_vectors(TRI)
+    timed("frame_displacements", lambda: f.frame_displacements_device([(0, 'pos'), None, (0, 'pos'), None, (0, 'tid')], vectors,
+                                                                     vectors, n_types=4))
     timed("plan_rows", lambda: f.plan_rows(rows, N))
     f.wait_read()
 os.unlink(path)
