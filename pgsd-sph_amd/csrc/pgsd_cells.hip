@@ -1,0 +1,432 @@
+// pgsd_cells.hip -- cell fields on gfx950: mass, momentum, kinetic and internal energy and first moment per grid cell of
+// a row list in cell order (pgsd_order_rows_by_cell_device leaves such a list and its cell ids).  pgsd.hoomd.cell_moments
+// is the definition and this file equals it exactly, sums included.  A grid has up to 2^20 cells, so the sum is
+// SEGMENTED and its order is the cell's own -- it depends on the cell's entries alone, not on where the cell lies in the
+// list, on the grid of the launch or on the device:
+//   a cell's entries, in list order, are cut into PIECES of 1024 counted from the cell's first entry; in a piece lane l of
+//   64 adds entries l, l + 64, ... to +0.0 (an entry past the end and a value that is not finite add +0.0); the 64 lane
+//   sums go through the wave tree of the statistics (p[i] += p[i + h], h = 32 .. 1); the piece sums are added to +0.0 in
+//   ascending order.
+//   cells_check_kernel     lane per entry: a row >= N, an id outside [0, n_cells] or below its predecessor raises both
+//                          flag words (order_key_kernel's protocol); every later kernel reads the device flag first and
+//                          does nothing where it is set, and clamps what it derives from the offsets to n
+//   cells_offsets_kernel   lane per c in [0, n_cells + 1]: offs[c] = the lower bound of c in cell[0 .. n), by binary
+//                          search; one writer per word, plain stores, nothing to clear
+//   cells_piece_kernel     one WAVE per slab of 1024 consecutive sorted entries, four per workgroup; the wave owns the
+//                          pieces that START in its slab (k is a start iff cell[k] < n_cells and (k - offs[cell[k]]) %
+//                          1024 == 0), found by ballot and handled in ascending order; per piece ceil(len / 64)
+//                          wave-uniform steps of gathered loads, nine trees and one counter.  A wave touches at most 2047
+//                          entries whatever the grid.  The piece of a cell of at most 1024 entries is the cell: lane 0
+//                          stores it into the result table.  A longer cell's pieces go to a partials table of TWO slots
+//                          per slab (the argument is at the kernel)
+//   cells_long_kernel      lane per slab and value: where the slab holds the first piece of a long cell the lane adds
+//                          that cell's piece sums to +0.0 in ascending order and stores the result
+// No global atomic on a float, no contraction wherever a value is formed or added.  Shared device helpers: pgsd_stats.hpp,
+// pgsd_kernels.hpp; the launchers' host side: pgsd_scratch.hpp.
+#include "pgsd_stats.hpp"
+#include "pgsd_scratch.hpp"
+
+namespace pgsd_amd
+    {
+#define CELLS_WAVES (SEL_THREADS / 64)
+#define CELLS_STEPS (CELLS_PIECE / 64)
+enum
+    {
+    CELLS_Q = MOMENTS_QUANTITIES,
+    CELLS_SLOT_WORDS = CELLS_Q + 1, // nine sums and the bad entries (a 64-bit counter) of a piece
+    CELLS_NO_PIECE = 0xFFFFFFFFu
+    };
+static_assert(CELLS_STEPS == SEL_PER_THREAD, "a slab is 16 steps of a wave");
+
+__device__ __forceinline__ void cells_raise(uint32_t* flag_dev, uint32_t* flag_host)
+    {
+    __hip_atomic_store(flag_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(flag_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+
+// rows: null for the offsets call, which has no rows to check
+__global__ __launch_bounds__(SEL_THREADS) void cells_check_kernel(const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                                                  uint64_t N, uint32_t n_cells, uint32_t* flag_dev,
+                                                                  uint32_t* flag_host)
+    {
+    const uint64_t k = (uint64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
+    if (k >= n)
+        return;
+    const int32_t c = cell[k];
+    bool bad = c < 0 || (uint32_t)c > n_cells || (k > 0 && c < cell[k - 1]);
+    if (rows)
+        bad = bad || rows[k] >= N;
+    if (bad)
+        cells_raise(flag_dev, flag_host);
+    }
+
+__global__ __launch_bounds__(SEL_THREADS) void cells_offsets_kernel(const int32_t* cell, uint64_t n, uint32_t n_cells,
+                                                                    const uint32_t* flag_dev, uint32_t* offs)
+    {
+    const uint32_t c = blockIdx.x * SEL_THREADS + threadIdx.x;
+    if (c > n_cells + 1u || *flag_dev != 0)
+        return;
+    uint64_t lo = 0, hi = n; // the first position whose id is not below c
+    while (lo < hi)
+        {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)cell[mid] < (int64_t)c)
+            lo = mid + 1;
+        else
+            hi = mid;
+        }
+    offs[c] = (uint32_t)lo;
+    }
+
+// Why two slots per slab suffice for the pieces of long cells (cells of more than 1024 entries):
+//   * piece j of a cell whose first entry is s starts at s + 1024 j; with s in slab w that lies in slab w + j, so the
+//     long kernel finds a cell's pieces without a list;
+//   * a slab holds at most one piece of number >= 1: the 1024 entries before such a piece's start belong to its cell, so
+//     a second start of number >= 1 in the same slab would lie in the same cell less than 1024 entries away -- but a
+//     cell's starts are 1024 apart;
+//   * a slab holds at most one FIRST piece of a long cell: the 1024 entries behind its start belong to that cell, so no
+//     other cell starts in the rest of the slab.
+// Slot 0 takes the piece of number >= 1, slot 1 the first piece of a long cell; first[w] is that piece's start, or
+// CELLS_NO_PIECE (every slab's wave writes it: one writer per word, nothing to clear).
+template<bool F64>
+__global__ __launch_bounds__(SEL_THREADS) void cells_piece_kernel(const CellMomentsArgs s, const uint32_t* __restrict__ offs,
+                                                                  const uint32_t* flag_dev, double* __restrict__ table,
+                                                                  uint64_t* __restrict__ table_bad, double* __restrict__ part,
+                                                                  uint32_t* __restrict__ first, uint32_t n_slabs)
+    {
+#pragma clang fp contract(off)
+    constexpr int T = F64 ? STATS_F64 : STATS_F32;
+    constexpr int W1 = F64 ? 2 : 1, W3 = 3 * W1; // 32-bit words of a scalar and of a three-column row
+    constexpr int BATCH = F64 ? 2 : 4;           // steps a lane has in flight (up to 16 and 8 words each)
+    constexpr int Q = CELLS_Q;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * CELLS_WAVES + (threadIdx.x >> 6));
+    if (w >= n_slabs || *flag_dev != 0)
+        return;
+    const uint64_t n = s.n;
+    const uint64_t base = (uint64_t)w * CELLS_PIECE;
+    const uint32_t* c_mass = (const uint32_t*)s.chunk[1];
+    const uint32_t* c_vel = (const uint32_t*)s.chunk[2];
+    const uint32_t* c_energy = (const uint32_t*)s.chunk[3];
+    const uint32_t* c_pos = (const uint32_t*)s.chunk[4];
+    // the slab's ids, 16 per lane and coalesced; bit j of `starts`: entry base + 64 j + lane starts a piece
+    int32_t id[CELLS_STEPS];
+#pragma unroll
+    for (int j = 0; j < CELLS_STEPS; j++)
+        {
+        const uint64_t k = base + (uint64_t)j * 64 + lane;
+        id[j] = k < n ? s.cell[k] : (int32_t)s.n_cells;
+        }
+    uint32_t starts = 0;
+#pragma unroll
+    for (int j = 0; j < CELLS_STEPS; j++)
+        {
+        const uint64_t k = base + (uint64_t)j * 64 + lane;
+        if (id[j] >= 0 && (uint32_t)id[j] < s.n_cells)
+            {
+            const uint64_t o = min((uint64_t)offs[id[j]], n);
+            if (o <= k && ((k - o) & (CELLS_PIECE - 1)) == 0)
+                starts |= 1u << j;
+            }
+        }
+    uint32_t first_long = CELLS_NO_PIECE;
+    for (int j = 0; j < CELLS_STEPS; j++)
+        {
+        uint64_t mask = __ballot((starts >> j) & 1u);
+        while (mask != 0)
+            {
+            const uint32_t b = (uint32_t)__builtin_ctzll(mask);
+            mask &= mask - 1;
+            const uint64_t at = base + (uint64_t)j * 64 + b; // (wave-uniform, < n: only an entry of the list starts a piece)
+            const uint32_t c = min((uint32_t)__builtin_amdgcn_readfirstlane(s.cell[at]), s.n_cells - 1u);
+            const uint64_t c_lo = min((uint64_t)offs[c], n), c_hi = min((uint64_t)offs[c + 1], n);
+            const uint64_t end = min(at + CELLS_PIECE, c_hi);
+            const bool is_long = c_hi > c_lo && c_hi - c_lo > CELLS_PIECE;
+            const bool is_first = at == c_lo;
+            const uint32_t steps = end > at ? (uint32_t)((end - at + 63) >> 6) : 0u;
+            double acc[Q];
+            uint32_t bad = 0;
+#pragma unroll
+            for (int q = 0; q < Q; q++)
+                acc[q] = 0.0;
+            for (uint32_t t0 = 0; t0 < steps; t0 += BATCH)
+                {
+                RowRegs r_mass[BATCH], r_vel[BATCH], r_energy[BATCH], r_pos[BATCH];
+                bool ok[BATCH];
+#pragma unroll
+                for (int i = 0; i < BATCH; i++)
+                    {
+                    const uint64_t k = at + (uint64_t)(t0 + i) * 64 + lane;
+                    ok[i] = k < end;
+                    const u32x4 zero = {0u, 0u, 0u, 0u};
+                    r_mass[i].lo = r_vel[i].lo = r_vel[i].hi = r_energy[i].lo = r_pos[i].lo = r_pos[i].hi = zero;
+                    const uint64_t row = ok[i] ? s.rows[k] : 0;
+                    ok[i] = ok[i] && row < s.N; // (the check kernel has refused such a list: nothing is loaded for it)
+                    if (ok[i])
+                        {
+                        if (c_mass)
+                            row_load<W1>(c_mass + row * W1, r_mass[i]);
+                        if (c_vel)
+                            row_load<W3>(c_vel + row * W3, r_vel[i]);
+                        if (c_energy)
+                            row_load<W1>(c_energy + row * W1, r_energy[i]);
+                        if (c_pos)
+                            row_load<W3>(c_pos + row * W3, r_pos[i]);
+                        }
+                    }
+#pragma unroll
+                for (int i = 0; i < BATCH; i++)
+                    {
+                    // the nine values of the conservation sums (moments_tile_kernel), in the same association
+                    const double m = c_mass ? stats_elem<T>(r_mass[i], 0) : s.defaults[0];
+                    const double e = c_energy ? stats_elem<T>(r_energy[i], 0) : s.defaults[4];
+                    double v[3], x[3], val[Q];
+#pragma unroll
+                    for (int a = 0; a < 3; a++)
+                        {
+                        v[a] = c_vel ? stats_elem<T>(r_vel[i], a) : s.defaults[1 + a];
+                        x[a] = c_pos ? stats_elem<T>(r_pos[i], a) : s.defaults[5 + a];
+                        }
+                    val[0] = m;
+                    val[4] = (0.5 * m) * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+                    val[5] = m * e;
+#pragma unroll
+                    for (int a = 0; a < 3; a++)
+                        {
+                        val[1 + a] = m * v[a];
+                        val[6 + a] = m * x[a];
+                        }
+                    bool all_fin = true;
+#pragma unroll
+                    for (int q = 0; q < Q; q++)
+                        {
+                        const bool fin = __builtin_fabs(val[q]) < __builtin_huge_val(); // (false for a NaN as well)
+                        all_fin = all_fin && fin;
+                        acc[q] = acc[q] + ((ok[i] && fin) ? val[q] : 0.0);
+                        }
+                    bad += (ok[i] && !all_fin) ? 1u : 0u;
+                    }
+                }
+            double sum[Q];
+#pragma unroll
+            for (int q = 0; q < Q; q++)
+                sum[q] = stats_wave_sum(acc[q]);
+            const uint64_t n_bad = stats_wave_count(bad);
+            if (is_long && is_first)
+                first_long = (uint32_t)at;
+            if (lane == 0)
+                {
+                double* out = is_long ? part + ((size_t)2 * w + (is_first ? 1 : 0)) * CELLS_SLOT_WORDS : table + (size_t)c * Q;
+#pragma unroll
+                for (int q = 0; q < Q; q++)
+                    out[q] = sum[q];
+                if (is_long)
+                    ((uint64_t*)out)[Q] = n_bad;
+                else
+                    table_bad[c] = n_bad;
+                }
+            }
+        }
+    if (lane == 0)
+        first[w] = first_long;
+    }
+
+__global__ __launch_bounds__(SEL_THREADS) void cells_long_kernel(const int32_t* __restrict__ cell, const uint32_t* __restrict__ offs,
+                                                                 const uint32_t* flag_dev, const double* __restrict__ part,
+                                                                 const uint32_t* __restrict__ first, uint64_t n,
+                                                                 uint32_t n_cells, uint32_t n_slabs, double* __restrict__ table,
+                                                                 uint64_t* __restrict__ table_bad)
+    {
+#pragma clang fp contract(off)
+    const uint64_t i = (uint64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
+    const uint32_t w = (uint32_t)(i / CELLS_SLOT_WORDS), q = (uint32_t)(i % CELLS_SLOT_WORDS);
+    if (w >= n_slabs || *flag_dev != 0)
+        return;
+    const uint32_t at = first[w];
+    if (at == CELLS_NO_PIECE || at >= n)
+        return;
+    const uint32_t c = min((uint32_t)cell[at], n_cells - 1u);
+    const uint64_t c_lo = min((uint64_t)offs[c], n), c_hi = min((uint64_t)offs[c + 1], n);
+    const uint64_t pieces = c_hi > c_lo ? (c_hi - c_lo + CELLS_PIECE - 1) / CELLS_PIECE : 0;
+    double sum = 0.0;
+    uint64_t count = 0;
+    for (uint64_t j = 0; j < pieces && w + j < n_slabs; j++)
+        {
+        const double* slot = part + ((size_t)2 * (w + j) + (j == 0 ? 1 : 0)) * CELLS_SLOT_WORDS;
+        if (q < CELLS_Q)
+            sum = sum + slot[q];
+        else
+            count += ((const uint64_t*)slot)[CELLS_Q];
+        }
+    if (q < CELLS_Q)
+        table[(size_t)c * CELLS_Q + q] = sum;
+    else
+        table_bad[c] = count;
+    }
+
+// ------------------------------------------------------------------ host side
+namespace
+    {
+// The family's scratch space (grow-only, per device, its own lock held), in bytes: the device flag word (16), the
+// offsets (n_cells + 2 words), the slabs' first long pieces (one word each), the result table (n_cells x 9 doubles and
+// n_cells counters) and the partials (two slots of ten words per slab); the pinned flag word is the host's view of a
+// refused list.
+Scratch g_cells_scratch("cell fields", 1.25, 1u << 16, 0, sizeof(uint64_t));
+std::mutex g_cells_lock;
+
+size_t round16(size_t bytes)
+    {
+    return (bytes + 15) & ~(size_t)15;
+    }
+
+const char* cells_refused = "a cell id descends or lies outside [0, n_cells], or an entry of the row list lies outside the "
+                            "chunks (nothing was computed)";
+
+int cells_arguments(uint64_t n, uint32_t n_cells, std::string* err, const char* what)
+    {
+    if (n >= (1ull << 32))
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, std::string(what) + ": a list holds fewer than 2^32 entries");
+    if (n_cells < 1 || n_cells > CELLS_MAX_CELLS)
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, std::string(what) + ": a grid holds 1 to 2^20 cells");
+    return PGSD_SUCCESS;
+    }
+    } // namespace
+
+void warm_cells_kernels()
+    {
+    warm_kernel((const void*)cells_offsets_kernel);
+    }
+
+int launch_cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets, hipStream_t stream,
+                        std::string* err)
+    {
+    static const char* what = "cell offsets";
+    int rc = cells_arguments(n, n_cells, err, what);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (!out_offsets || (n > 0 && !cell))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    LaunchScope scope(g_cells_lock, g_cells_scratch, 16, stream, err);
+    if (scope.rc() != PGSD_SUCCESS)
+        return scope.rc();
+    uint32_t* flag_dev = (uint32_t*)scope.mem().dev;
+    uint32_t* host_flag = (uint32_t*)scope.mem().mapped;
+    __atomic_store_n(host_flag, 0u, __ATOMIC_RELEASE);
+    const dim3 block(SEL_THREADS);
+    hipError_t e;
+    if (n == 0)
+        e = hipMemsetAsync(out_offsets, 0, ((size_t)n_cells + 2) * sizeof(uint32_t), stream);
+    else
+        {
+        e = hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), stream);
+        if (e == hipSuccess)
+            {
+            hipLaunchKernelGGL(cells_check_kernel, dim3((unsigned)((n + SEL_THREADS - 1) / SEL_THREADS)), block, 0, stream,
+                               (const uint32_t*)nullptr, cell, n, (uint64_t)0, n_cells, flag_dev,
+                               (uint32_t*)scope.mem().mapped_dev);
+            hipLaunchKernelGGL(cells_offsets_kernel, dim3((n_cells + 2 + SEL_THREADS - 1) / SEL_THREADS), block, 0, stream, cell,
+                               n, n_cells, flag_dev, out_offsets);
+            e = hipGetLastError();
+            }
+        }
+    rc = scope.finish(what, e);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (__atomic_load_n(host_flag, __ATOMIC_ACQUIRE) != 0)
+        return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT,
+                           std::string(what) + ": a cell id descends or lies outside [0, n_cells] (nothing was written)");
+    return PGSD_SUCCESS;
+    }
+
+int launch_cell_moments(const CellMomentsArgs& a, uint64_t* out_counts, double* out_sums, hipStream_t stream, std::string* err)
+    {
+    static const char* what = "cell fields";
+    const auto fail = [err](const char* why) { return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, std::string(what) + ": " + why); };
+    if (!out_counts || !out_sums)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    int rc = cells_arguments(a.n, a.n_cells, err, what);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (a.N >= (1ull << 32) + 1)
+        return fail("2^32 rows or entries and more are not indexed");
+    const uint64_t n = a.n;
+    const uint32_t n_cells = a.n_cells;
+    if (n == 0)
+        {
+        std::fill(out_counts, out_counts + 2 * (size_t)n_cells + 1, (uint64_t)0);
+        std::fill(out_sums, out_sums + (size_t)CELLS_Q * n_cells, 0.0);
+        return PGSD_SUCCESS;
+        }
+    if (a.N == 0)
+        return fail(cells_refused);
+    if (!a.rows || !a.cell)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    for (int i = 1; i < GROUPED_CHUNKS; i++)
+        if ((a.present & (1u << i)) && !a.chunk[i])
+            return PGSD_ERROR_INVALID_ARGUMENT;
+    const uint32_t n_slabs = (uint32_t)((n + CELLS_PIECE - 1) / CELLS_PIECE);
+    const size_t offs_bytes = round16(((size_t)n_cells + 2) * sizeof(uint32_t)), first_bytes = round16((size_t)n_slabs * sizeof(uint32_t));
+    const size_t table_bytes = (size_t)n_cells * CELLS_Q * sizeof(double), bad_bytes = (size_t)n_cells * sizeof(uint64_t);
+    const size_t part_bytes = (size_t)n_slabs * 2 * CELLS_SLOT_WORDS * sizeof(double);
+    LaunchScope scope(g_cells_lock, g_cells_scratch, 16 + offs_bytes + first_bytes + table_bytes + bad_bytes + part_bytes, stream,
+                      err);
+    if (scope.rc() != PGSD_SUCCESS)
+        return scope.rc();
+    char* dev = scope.mem().dev;
+    uint32_t* flag_dev = (uint32_t*)dev;
+    uint32_t* offs = (uint32_t*)(dev + 16);
+    uint32_t* first = (uint32_t*)(dev + 16 + offs_bytes);
+    double* table = (double*)(dev + 16 + offs_bytes + first_bytes);
+    uint64_t* table_bad = (uint64_t*)((char*)table + table_bytes);
+    double* part = (double*)((char*)table_bad + bad_bytes);
+    uint32_t* host_flag = (uint32_t*)scope.mem().mapped;
+    uint32_t* host_flag_dev = (uint32_t*)scope.mem().mapped_dev;
+    __atomic_store_n(host_flag, 0u, __ATOMIC_RELEASE);
+    const dim3 block(SEL_THREADS);
+    hipError_t e = hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), stream);
+    // (empty cells: +0.0 and no bad entry)
+    if (e == hipSuccess)
+        e = hipMemsetAsync(table, 0, table_bytes + bad_bytes, stream);
+    if (e == hipSuccess)
+        {
+        hipLaunchKernelGGL(cells_check_kernel, dim3((unsigned)((n + SEL_THREADS - 1) / SEL_THREADS)), block, 0, stream, a.rows,
+                           a.cell, n, a.N, n_cells, flag_dev, host_flag_dev);
+        hipLaunchKernelGGL(cells_offsets_kernel, dim3((n_cells + 2 + SEL_THREADS - 1) / SEL_THREADS), block, 0, stream, a.cell, n,
+                           n_cells, flag_dev, offs);
+        const dim3 per_slab((n_slabs + CELLS_WAVES - 1) / CELLS_WAVES);
+        if (a.f64)
+            hipLaunchKernelGGL(cells_piece_kernel<true>, per_slab, block, 0, stream, a, offs, flag_dev, table, table_bad, part,
+                               first, n_slabs);
+        else
+            hipLaunchKernelGGL(cells_piece_kernel<false>, per_slab, block, 0, stream, a, offs, flag_dev, table, table_bad, part,
+                               first, n_slabs);
+        const uint64_t long_lanes = (uint64_t)n_slabs * CELLS_SLOT_WORDS;
+        hipLaunchKernelGGL(cells_long_kernel, dim3((unsigned)((long_lanes + SEL_THREADS - 1) / SEL_THREADS)), block, 0, stream,
+                           a.cell, offs, flag_dev, part, first, n, n_cells, n_slabs, table, table_bad);
+        e = hipGetLastError();
+        }
+    rc = scope.finish(what, e);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (__atomic_load_n(host_flag, __ATOMIC_ACQUIRE) != 0)
+        return fail(cells_refused);
+    // success: the result table straight into the caller's sums, the offsets and counters through host copies
+    std::vector<uint32_t> h_offs((size_t)n_cells + 2);
+    std::vector<uint64_t> h_bad(n_cells);
+    e = hipMemcpyAsync(out_sums, table, table_bytes, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(h_offs.data(), offs, h_offs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(h_bad.data(), table_bad, bad_bytes, hipMemcpyDeviceToHost, stream);
+    rc = scope.finish(what, e);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    for (uint32_t c = 0; c < n_cells; c++)
+        {
+        out_counts[2 * (size_t)c + 0] = h_offs[c + 1] - h_offs[c];
+        out_counts[2 * (size_t)c + 1] = h_bad[c];
+        }
+    out_counts[2 * (size_t)n_cells] = h_offs[n_cells + 1] - h_offs[n_cells];
+    return PGSD_SUCCESS;
+    }
+    } // namespace pgsd_amd

@@ -209,6 +209,7 @@ int DevicePipeline::init()
         warm_compaction_kernels();
         warm_census_kernels();
         warm_order_kernels();
+        warm_cells_kernels();
         int brc = compare_buffers();
         if (brc != PGSD_SUCCESS)
             return brc;
@@ -729,6 +730,26 @@ int device_pipeline_frame_displacements(DevicePipeline* p, const ChunkRange* ran
     {
     std::string local;
     int rc = report(p, p->frame_displacements(ranges, d, out_counts, out_values, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
+int device_pipeline_cell_offsets(DevicePipeline* p, const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets,
+                                 std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->cell_offsets(cell, n, n_cells, out_offsets, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
+int device_pipeline_cell_moments(DevicePipeline* p, const ChunkRange* ranges, const CellMomentsArgs& c, uint64_t* out_counts,
+                                 double* out_sums, std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->cell_moments(ranges, c, out_counts, out_sums, &local), err, true);
     if (rc != PGSD_SUCCESS && err && !local.empty())
         *err = local; // the launcher's own message comes first
     return rc;

@@ -152,6 +152,8 @@ class DevicePipeline
     int frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums, std::string* why);
     int frame_displacements(const ChunkRange* ranges, DisplacementArgs d, uint64_t* out_counts, double* out_values,
                             std::string* why);
+    int cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets, std::string* why);
+    int cell_moments(const ChunkRange* ranges, CellMomentsArgs c, uint64_t* out_counts, double* out_sums, std::string* why);
     int wait_read();
 
     // ---- accessors ----

@@ -569,6 +569,21 @@ int DevicePipeline::frame_displacements(const ChunkRange* ranges, DisplacementAr
                           { return launch_frame_displacements(d, out_counts, out_values, m_res.pack_stream, err); });
     }
 
+// Cell fields: the lists are the caller's.  The offsets call stages nothing; the sums stage the chunks that are present
+// like the conservation sums (the typeid slot stays empty).
+int DevicePipeline::cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets, std::string* why)
+    {
+    return staged_launch(nullptr, nullptr, 0, 0, true, why, [&](std::string* err)
+                         { return launch_cell_offsets(cell, n, n_cells, out_offsets, m_res.pack_stream, err); });
+    }
+
+int DevicePipeline::cell_moments(const ChunkRange* ranges, CellMomentsArgs c, uint64_t* out_counts, double* out_sums,
+                                 std::string* why)
+    {
+    return staged_grouped(ranges, c, why, [&](std::string* err)
+                          { return launch_cell_moments(c, out_counts, out_sums, m_res.pack_stream, err); });
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

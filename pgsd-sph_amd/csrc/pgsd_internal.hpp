@@ -402,6 +402,31 @@ inline void displacements_of_nothing(uint32_t n_types, uint64_t* out_counts, dou
 // call.  The staged rows stay until the next wait_read.
 int device_pipeline_frame_displacements(DevicePipeline*, const ChunkRange* ranges, const DisplacementArgs& d,
                                         uint64_t* out_counts, double* out_values, std::string* err);
+// Cell fields (pgsd.hoomd.cell_moments is the definition): the nine values of the conservation sums per entry of a row
+// list in cell order, summed per grid cell in an order of the cell's own (pieces of 1024 entries from the cell's first
+// entry, 64 strided lanes, the wave tree, the pieces in sequence).  chunk: the conservation sums' order; the typeid slot
+// stays empty.
+enum
+    {
+    CELLS_MAX_CELLS = 1u << 20,
+    CELLS_PIECE = 1024 // entries of a piece, and of a slab of the sorted list
+    };
+struct CellMomentsArgs : GroupedArgs
+    {
+    double defaults[8];  // mass, v[3], energy, x[3]
+    const int32_t* cell; // device, n entries, non-decreasing, in [0, n_cells]; n_cells: nowhere
+    uint32_t n_cells;
+    uint32_t pad2;
+    };
+// the CSR offsets of a sorted cell list alone: out_offsets (device, n_cells + 2 words) is written on success only
+int device_pipeline_cell_offsets(DevicePipeline*, const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets,
+                                 std::string* err);
+// stage the chunks that are present, check the lists, sum per cell on the GPU, copy the results to the host: out_counts
+// n_cells x 2 (entries, bad), then the entries nowhere; out_sums n_cells x 9; written on success only; synchronous.  An
+// entry >= c.N, an id outside [0, n_cells] and a descending id refuse the call.  The staged rows stay until the next
+// wait_read.
+int device_pipeline_cell_moments(DevicePipeline*, const ChunkRange* ranges, const CellMomentsArgs& c, uint64_t* out_counts,
+                                 double* out_sums, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

@@ -285,6 +285,16 @@ int launch_frame_moments(const MomentsArgs& m, uint64_t* out_counts, double* out
 int launch_frame_displacements(const DisplacementArgs& d, uint64_t* out_counts, double* out_values, hipStream_t stream,
                                std::string* err);
 
+// cell fields (pgsd_cells.hip).  launch_cell_offsets: check and offsets kernels over a sorted cell list; out_offsets
+// (device, n_cells + 2) is written on success only (zeros for n == 0).  launch_cell_moments (CellMomentsArgs, the
+// addresses of the chunks that are present filled in): check, offsets, one wave per slab of 1024 sorted entries, one lane
+// per slab and value for the cells of more than 1024 entries; out_counts (host, n_cells x 2, then the entries nowhere)
+// and out_sums (host, n_cells x 9) are written on success only.  Both synchronise `stream`;
+// PGSD_ERROR_INVALID_ARGUMENT for an id that descends or lies outside [0, n_cells] and for an entry >= c.N
+int launch_cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets, hipStream_t stream,
+                        std::string* err);
+int launch_cell_moments(const CellMomentsArgs& c, uint64_t* out_counts, double* out_sums, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);
@@ -342,6 +352,7 @@ void warm_select_kernels();
 void warm_compaction_kernels();
 void warm_census_kernels();
 void warm_order_kernels();
+void warm_cells_kernels();
 
 // algorithmic traffic of one job: bytes that must be read (needed columns only, plus the
 // gather index) and chunk bytes written

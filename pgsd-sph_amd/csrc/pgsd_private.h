@@ -36,6 +36,11 @@
  *                     frame_displacements_device: per particle type the drift, the squared displacement and the largest
  *                     move between two frames, unwrapped through image flags and box vectors, from the staged position
  *                     and image chunks of both frames in one pass)
+ *                     pgsd_cell_offsets_device, pgsd_cell_moments_device (pgsd.fl's cell_offsets_device and
+ *                     cell_moments_device, behind pgsd.hoomd's cell_moments_device: the CSR offsets of a row list in
+ *                     cell order, and per grid cell the mass, momentum, kinetic and internal energy and first moment of
+ *                     its entries -- the coarse-grained density and velocity field -- from the staged chunks in one
+ *                     segmented pass)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -295,6 +300,39 @@ extern "C"
                                         const double vectors_a[6], const double vectors_b[6], uint32_t flags,
                                         uint32_t dimensions, uint32_t type0, uint32_t n_types, const uint32_t* rows,
                                         uint64_t n, double* out_rows, uint64_t* out_counts, double* out_values);
+
+    /* CSR offsets of a cell list in cell order (pgsd.hoomd.cell_offsets is the definition).  cell (device memory, n
+       int32 entries, non-decreasing, in [0, n_cells]; n_cells is pgsd_order_rows_by_cell_device's "nowhere" id).
+       out_offsets (device memory, n_cells + 2 words): out_offsets[c] is the first position whose id is not below c --
+       the first entry of cell c --, out_offsets[n_cells + 1] == n.  Runs on the handle's GPU and synchronises.  n == 0
+       writes zeros.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), out_offsets as it was: an id that is below its
+       predecessor or outside [0, n_cells]; n >= 2^32; n_cells of 0 or above 2^20. */
+    int pgsd_cell_offsets_device(struct pgsd_handle* handle, const int32_t* cell, uint64_t n, uint32_t n_cells,
+                                 uint32_t* out_offsets);
+
+    /* Cell fields (pgsd.hoomd.cell_moments is the definition, and the results equal it exactly, the sums bit for bit).
+       mass, velocity, energy, position, defaults: as pgsd_frame_moments_device's, and so are the nine values per entry.
+       rows (device memory, n entries) and cell (device memory, n int32 entries, non-decreasing, in [0, n_cells]) are a
+       row list in cell order and the ids of its entries, as pgsd_order_rows_by_cell_device leaves them; an entry with
+       id n_cells is nowhere and is summed nowhere.  The results are HOST arrays:
+           out_counts[2 c + 0 .. 1]   the entries of cell c, those of them with a value that is not finite
+           out_counts[2 n_cells]      the entries nowhere
+           out_sums[9 c + q]          the sum of value q over the cell's entries, a value that is not finite counting as
+                                      +0.0, in the cell's own order
+       The order: the cell's entries in list order are cut into pieces of 1024 from the cell's first entry; in a piece lane
+       l of 64 adds entries l, l + 64, ..., l + 960 in that order to +0.0 (an entry past the end adds +0.0); the 64 lane
+       sums are combined by p[i] += p[i + h] for h = 32, 16, 8, 4, 2, 1; the piece sums are added to +0.0 in ascending
+       order.  A cell without entries has sums of +0.0.  It depends on neither the grid of the launch nor the device.
+       The chunks are staged whole unless an earlier call left them staged (then no file byte is read), the reduction runs
+       on the handle's GPU and the call synchronises; the staged rows are kept until the next pgsd_device_wait_read.
+       n == 0 succeeds with zeros and launches nothing.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(): pgsd_frame_moments_device's refusals for the chunks;
+       pgsd_cell_offsets_device's; an entry >= N.  out_counts and out_sums are written on success only. */
+    int pgsd_cell_moments_device(struct pgsd_handle* handle, const struct pgsd_index_entry* mass,
+                                 const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* energy,
+                                 const struct pgsd_index_entry* position, const double defaults[8], const uint32_t* rows,
+                                 const int32_t* cell, uint64_t n, uint32_t n_cells, uint64_t* out_counts, double* out_sums);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

@@ -855,6 +855,86 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_cell_offsets_device(struct pgsd_handle* handle, const int32_t* cell, uint64_t n, uint32_t n_cells,
+                                        uint32_t* out_offsets)
+    try
+    {
+    static const char* who = "pgsd_cell_offsets_device";
+    Impl* s = impl_of(handle);
+    if (!s || !out_offsets || (n > 0 && !cell))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    if (n >= (1ull << 32))
+        return refuse("a list holds fewer than 2^32 entries");
+    if (n_cells < 1 || n_cells > CELLS_MAX_CELLS)
+        return refuse("a grid holds 1 to 2^20 cells");
+    return reduction_call(who, "cell offsets: ", [&](std::string* err)
+                          { return device_pipeline_cell_offsets(s->dev, cell, n, n_cells, out_offsets, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_cell_moments_device(struct pgsd_handle* handle, const struct pgsd_index_entry* mass,
+                                        const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* energy,
+                                        const struct pgsd_index_entry* position, const double defaults[8], const uint32_t* rows,
+                                        const int32_t* cell, uint64_t n, uint32_t n_cells, uint64_t* out_counts,
+                                        double* out_sums)
+    try
+    {
+    static const char* who = "pgsd_cell_moments_device";
+    Impl* s = impl_of(handle);
+    if (!s || !defaults || !out_counts || !out_sums || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    const struct pgsd_index_entry* given[MOMENTS_CHUNKS] = {nullptr, mass, velocity, energy, position};
+    CellMomentsArgs a;
+    memset(&a, 0, sizeof(a));
+    ChunkRange ranges[MOMENTS_CHUNKS];
+    memset(ranges, 0, sizeof(ranges));
+    std::string why;
+    int rc = grouped_chunks(s, handle, g_moments_slots, "float", given, &a, ranges, &why);
+    if (rc != PGSD_SUCCESS)
+        return why.empty() ? rc : refuse(why);
+    if (n >= (1ull << 32))
+        return refuse("a list holds fewer than 2^32 entries");
+    if (n_cells < 1 || n_cells > CELLS_MAX_CELLS)
+        return refuse("a grid holds 1 to 2^20 cells");
+    // without a stored chunk nothing bounds the entries of the list (no row is loaded)
+    if (!a.present)
+        a.N = 1ull << 32;
+    std::copy(defaults, defaults + 8, a.defaults);
+    a.rows = rows;
+    a.cell = cell;
+    a.n = n;
+    a.n_cells = n_cells;
+    a.n_types = 1;
+    if (n == 0)
+        {
+        std::fill(out_counts, out_counts + 2 * (size_t)n_cells + 1, (uint64_t)0);
+        std::fill(out_sums, out_sums + (size_t)MOMENTS_QUANTITIES * n_cells, 0.0);
+        return PGSD_SUCCESS;
+        }
+    if (a.N == 0)
+        return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "cell fields: ", [&](std::string* err)
+                          { return device_pipeline_cell_moments(s->dev, ranges, a, out_counts, out_sums, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position_a,
                                                const struct pgsd_index_entry* image_a,
                                                const struct pgsd_index_entry* position_b,

@@ -9,6 +9,8 @@
 //   pgsd_census.hip    the domain census: axis histograms and cell counts
 //   pgsd_order.hip     cell order: keys, a stable radix sort, the pass that applies the permutation
 //   pgsd_stats.hip     frame statistics; conservation sums and frame displacements on one final kernel and launcher
+//   pgsd_cells.hip     cell fields: the conservation sums' values per grid cell of a list in cell order, CSR offsets
+//   pgsd_stats.hpp     what the two reduction units share: an element as a double, the wave tree, the wave counter
 //   pgsd_device_memory.cpp   pgsd_device_alloc / _free / _copy: device memory owned by the library (no kernel)
 //   pgsd_scratch.hpp / .cpp  the host side all of them stand on: scratch space, launch scope, device scope
 //   pgsd_kernels.hpp / .cpp  row layout (SEL_THREADS ...), vector types, tuning, what the pack and unpack kernels share

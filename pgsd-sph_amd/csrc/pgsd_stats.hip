@@ -20,39 +20,12 @@
 // pgsd.hoomd.particle_moments is the definition) and the frame displacements (displacement_tile_kernel;
 // pgsd.hoomd.particle_displacements) have a tile kernel each and share one table layout, grouped_final_kernel and one
 // launcher.
-#include "pgsd_kernels.hpp"
+#include "pgsd_stats.hpp" // (stats_elem, stats_wave_sum, stats_wave_count: shared with pgsd_cells.hip)
 #include "pgsd_scratch.hpp"
 
 namespace pgsd_amd
     {
 #define STATS_WAVES (SEL_THREADS / 64)
-
-enum
-    {
-    STATS_F32 = 0,
-    STATS_F64 = 1,
-    STATS_I32 = 2,
-    STATS_U32 = 3
-    };
-
-// word i (a constant once the loops are unrolled) of a row in registers
-__device__ __forceinline__ uint32_t stats_word(const RowRegs& r, int i)
-    {
-    return i < 4 ? r.lo[i] : r.hi[i - 4];
-    }
-
-// element c of a row as a double: exact for all four element types
-template<int T> __device__ __forceinline__ double stats_elem(const RowRegs& r, int c)
-    {
-    if constexpr (T == STATS_F64)
-        return __longlong_as_double((long long)(((uint64_t)stats_word(r, 2 * c + 1) << 32) | stats_word(r, 2 * c)));
-    else if constexpr (T == STATS_F32)
-        return (double)__uint_as_float(stats_word(r, c));
-    else if constexpr (T == STATS_I32)
-        return (double)(int32_t)stats_word(r, c);
-    else
-        return (double)stats_word(r, c);
-    }
 
 // what a lane, and then a tile, knows about one column
 struct StatsAcc
@@ -73,15 +46,6 @@ __device__ __forceinline__ void stats_take(StatsAcc& a, double v, bool ok)
     a.sum = a.sum + ((ok && !is_nan && !is_inf) ? v : 0.0);
     }
 
-// the wave part of the block tree: lane 0 of the wave ends with ((..) + (..)) over the halvings 32, 16, 8, 4, 2, 1
-__device__ __forceinline__ double stats_wave_sum(double p)
-    {
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1)
-        p = p + __shfl_down(p, h, 64);
-    return p;
-    }
-
 // the rest of the block tree: the four waves' sums, (w0 + w1) + (w2 + w3)
 __device__ __forceinline__ double stats_block_sum(const double* w)
     {
@@ -99,15 +63,6 @@ __device__ __forceinline__ double stats_column_sum(const double* __restrict__ t_
     for (uint32_t t = threadIdx.x; t < n_tiles; t += SEL_THREADS)
         sum = sum + t_sum[t];
     return stats_wave_sum(sum);
-    }
-
-// a 64-bit counter across the wave (every lane ends with the result)
-__device__ __forceinline__ uint64_t stats_wave_count(uint64_t c)
-    {
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1)
-        c += (uint64_t)__shfl_xor((unsigned long long)c, h, 64);
-    return c;
     }
 
 // minimum, maximum and the counters across the wave (every lane ends with the result; the order is free)

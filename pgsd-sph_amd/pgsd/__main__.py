@@ -15,7 +15,10 @@
            move with its row between frame ``--origin`` and the frame, unwrapped through the image flags
            (``--minimum-image``: the wrapped positions' difference folded into the box instead; ``--types``), and a
            total line; ``--displacement --all-frames`` one line per frame against the origin: the MSD curve
-           (``pgsd.hoomd.frame_displacements`` on the host: no GPU).
+           (``pgsd.hoomd.frame_displacements`` on the host: no GPU);
+           ``--cells CX,CY,CZ`` adds the occupied cells of such a grid, the smallest and largest count, the largest
+           density and mean speed with their cell indices and the particles nowhere (``--types``;
+           ``pgsd.hoomd.frame_cell_moments`` on the host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -82,6 +85,43 @@ def _cmd_info(args):
         _print_moments(args, frame)
     if args.displacement:
         _print_displacement(args, frame)
+    if args.cells:
+        _print_cells(args, frame)
+
+
+def _print_cells(args, frame):
+    """``info --cells``: `pgsd.hoomd.frame_cell_moments` of one frame over a CX x CY x CZ grid, on the host."""
+    import numpy
+    from . import hoomd
+    try:
+        cells = tuple(int(v) for v in args.cells.split(','))
+        if len(cells) != 3:
+            raise ValueError
+    except ValueError:
+        raise ValueError("--cells takes CX,CY,CZ: %r" % args.cells)
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_cell_moments(traj[frame], cells, where=where)
+    cx, cy = m.grid[0], m.grid[1]
+
+    def index(c):
+        return "(%d, %d, %d)" % (c % cx, (c // cx) % cy, c // (cx * cy))
+
+    occupied = numpy.nonzero(m.count > 0)[0]
+    print("cell fields of frame %d over %d x %d x %d cells%s:" % ((frame,) + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  occupied cells:  %d of %d" % (len(occupied), len(m.count)))
+    if len(occupied):
+        print("  count:           smallest %d  largest %d" % (m.count[occupied].min(), m.count[occupied].max()))
+        c = int(numpy.argmax(m.density))
+        print("  largest density: %r in cell %s" % (float(m.density[c]), index(c)))
+        v = m.mean_velocity
+        speed = numpy.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+        if numpy.isfinite(speed).any():
+            c = int(numpy.nanargmax(speed))
+            print("  largest speed:   %r in cell %s" % (float(speed[c]), index(c)))
+    if m.bad.sum():
+        print("  entries with a value that is not finite: %d" % int(m.bad.sum()))
+    print("  nowhere:         %d" % m.nowhere)
 
 
 def _vector_text(v):
@@ -253,6 +293,9 @@ def main(argv=None):
     p.add_argument('--displacement', action='store_true',
                    help="print count, mean drift, mean-squared displacement and the largest move per particle type "
                         "between the origin and the frame")
+    p.add_argument('--cells', type=str, default=None, metavar='CX,CY,CZ',
+                   help="print the occupied cells, the smallest and largest count, the largest density and speed with "
+                        "their cells and the particles nowhere, over a uniform CX x CY x CZ grid")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")
     p.add_argument('--minimum-image', action='store_true',
                    help="--displacement of the wrapped positions, folded into the box, instead of through the image flags")

@@ -1790,6 +1790,92 @@ cdef class PGSDFile:
         counts = counts.astype(numpy.int64)
         return _hoomd.Moments.from_sums(counts[0:2 * T:2].copy(), counts[1:2 * T:2].copy(), int(counts[2 * T]), sums)
 
+    def cell_offsets_device(self, cell, n, n_cells):
+        """The CSR offsets of a cell list in cell order, on the GPU.
+
+        Args:
+            cell: int32 cell ids in GPU memory, non-decreasing, in ``[0, n_cells]`` (:meth:`order_rows_by_cell_device`'s).
+            n (int): the number of entries to take (``None``: all of ``cell``).
+            n_cells (int): the cells of the grid, 1 to 2^20; the id ``n_cells`` is "nowhere".
+
+        Returns:
+            ``n_cells + 2`` int32 offsets in GPU memory: entry ``c`` is the first position of cell ``c``, the last entry
+            is ``n``.  Exactly :func:`pgsd.hoomd.cell_offsets`.  Ids that descend or lie outside the range raise
+            ValueError.  Needs no tensor library.
+        """
+        self._check_open()
+        c_cell, count = _row_list("cell_offsets_device", cell, n)
+        cells = int(n_cells)
+        if not 0 <= cells < (1 << 32):
+            raise ValueError("cell_offsets_device: a grid holds 1 to 2^20 cells")
+        offs = _device_empty((cells + 2 if 1 <= cells <= (1 << 20) else 2,), numpy.int32, self.pipeline_device())
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `cell`
+        cdef uintptr_t p_cell = c_cell, p_offs = _device_memory(offs)[0]
+        cdef uint64_t c_n = count
+        cdef uint32_t c_cells = cells
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_cell_offsets_device(&self._handle, <const int32_t*>p_cell, c_n, c_cells, <uint32_t*>p_offs)
+            err = errno
+        _raise_refused("cell_offsets_device", retval, "refused", self._name, err)
+        return offs
+
+    def cell_moments_device(self, chunks, rows, cell, n, n_cells, defaults=None):
+        """Mass, momentum, kinetic and internal energy and first moment per grid cell of a row list in cell order,
+        reduced on the GPU in one segmented pass.
+
+        Args:
+            chunks: four entries in the order mass, velocity, energy, position, each ``(frame, name)`` or ``None``:
+                stored nowhere, as :meth:`frame_moments_device` takes them.
+            rows, cell: 32-bit row indices and int32 cell ids in GPU memory, one id per entry, non-decreasing, in
+                ``[0, n_cells]`` -- what :meth:`order_rows_by_cell_device` leaves.
+            n (int): the number of entries to take (``None``: all of ``rows``).
+            n_cells (int): the cells of the grid, 1 to 2^20.
+            defaults: as :meth:`frame_moments_device`'s.
+
+        Returns:
+            A :class:`pgsd.hoomd.CellMoments` (``grid`` and ``cell_volume`` unset).  Exactly
+            :func:`pgsd.hoomd.cell_moments`, the sums included: their order is part of the definition.  The chunks are
+            staged whole unless an earlier call left them staged; the staged rows are kept until the next
+            :meth:`wait_read`.  Ids that descend or lie outside the range and an entry outside the chunks raise
+            ValueError.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entries[5]
+        cdef const C.pgsd_index_entry* given[5]
+        chunks = list(chunks)
+        if len(chunks) != 4:
+            raise ValueError("cell_moments_device: chunks holds mass, velocity, energy, position (or None)")
+        self._entries([None] + chunks, entries, given)
+        c_defaults = numpy.ascontiguousarray(
+            numpy.array([1, 0, 0, 0, 0, 0, 0, 0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+        if c_defaults.shape[0] != 8:
+            raise ValueError("cell_moments_device: defaults holds mass, v[3], energy, x[3]")
+        c_rows, count = _row_list("cell_moments_device", rows, n)
+        c_cell, _ = _row_list("cell_moments_device", cell, count)
+        cells = int(n_cells)
+        if not 0 <= cells < (1 << 32):
+            raise ValueError("cell_moments_device: a grid holds 1 to 2^20 cells")
+        T = cells if 1 <= cells <= (1 << 20) else 1           # (the library refuses the rest)
+        counts = numpy.zeros(2 * T + 1, dtype=numpy.uint64)
+        sums = numpy.zeros((T, 9), dtype=numpy.float64)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the reduction is ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell
+        cdef uintptr_t c_counts = counts.ctypes.data, c_sums = sums.ctypes.data, c_pdef = c_defaults.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_cells = cells
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_cell_moments_device(&self._handle, given[1], given[2], given[3], given[4], <const double*>c_pdef,
+                                                <const uint32_t*>p_rows, <const int32_t*>p_cell, c_n, c_cells,
+                                                <uint64_t*>c_counts, <double*>c_sums)
+            err = errno
+        _raise_refused("cell_moments_device", retval, "refused", self._name, err)
+        counts = counts.astype(numpy.int64)
+        return _hoomd.CellMoments.from_sums(counts[0:2 * T:2].copy(), counts[1:2 * T:2].copy(), int(counts[2 * T]), sums)
+
     def frame_displacements_device(self, chunks, vectors_a, vectors_b, minimum_image=False, dimensions=3, type0=0,
                                    n_types=1, rows=None, n=None, out=None):
         """Drift, squared displacement and the largest move between two frames per particle type, reduced on the GPU in

@@ -1134,6 +1134,42 @@ def particle_moments(mass, velocity, energy=None, position=None, typeid=None, ty
     ValueError: other element types, mixed float types, wrong shapes or lengths, ``n_types`` of 0 or above 4, a typeid
     of float elements, no typeid with ``n_types != 1``, no array and no ``N``, what `column_stats` refuses for ``rows``.
     """
+    arrays, dt, n_rows = _moments_arrays(mass, velocity, energy, position, N)
+    if not isinstance(n_types, (int, numpy.integer)) or not 1 <= n_types <= _MOMENTS_MAX_TYPES:
+        raise ValueError("a call takes 1 to 4 types: %r" % (n_types,))
+    if not isinstance(type0, (int, numpy.integer)) or not 0 <= type0 < 2 ** 32:
+        raise ValueError("type0 is a type id: %r" % (type0,))
+    if typeid is not None:
+        typeid = numpy.asarray(typeid)
+        if typeid.dtype.type not in (numpy.uint32, numpy.int32):
+            raise ValueError("typeid holds uint32 or int32 elements: %s" % typeid.dtype)
+        if typeid.ndim != 1:
+            raise ValueError("typeid is an array of N values")
+        if n_rows is not None and typeid.shape[0] != n_rows:
+            raise ValueError("the arrays differ in their number of rows (typeid has %d)" % typeid.shape[0])
+        n_rows = typeid.shape[0]
+    elif n_types != 1:
+        raise ValueError("without a typeid there is one group: n_types must be 1")
+    n_rows, rows, n = _moments_rows(n_rows, rows)
+    values, finite, all_finite = _moments_values(arrays, dt, rows, n)
+    if typeid is None:
+        group = numpy.zeros(n, dtype=numpy.int64)
+    else:
+        group = (typeid if rows is None else typeid[rows]).astype(numpy.int64) - int(type0)
+    count, bad = numpy.zeros(n_types, numpy.int64), numpy.zeros(n_types, numpy.int64)
+    sums = numpy.zeros((n_types, _MOMENTS_QUANTITIES), dtype=numpy.float64)
+    for t in range(n_types):
+        mine = group == t
+        count[t], bad[t] = mine.sum(), (mine & ~all_finite).sum()
+        for q in range(_MOMENTS_QUANTITIES):
+            sums[t, q] = _ordered_sum(numpy.where(mine & finite[q], values[q], 0.0))
+    return Moments.from_sums(count, bad, n - int(count.sum()), sums)
+
+
+def _moments_arrays(mass, velocity, energy, position, N):
+    """The four float inputs of `particle_moments` (and `cell_moments`), checked: ``(arrays, dt, n_rows)`` -- per name
+    the array or the default row, the arrays' element type (``None`` without an array) and their number of rows
+    (``N`` without an array)."""
     given = dict(zip(('mass', 'velocity', 'energy', 'position'), (mass, velocity, energy, position)))
     arrays, dt, n_rows = {}, None, None if N is None else int(N)
     for name, M, default in _MOMENTS_INPUTS:
@@ -1152,29 +1188,24 @@ def particle_moments(mass, velocity, energy=None, position=None, typeid=None, ty
             raise ValueError("%s is %s" % (name, "an array of N values or one value" if M == 1 else
                                            "an N x 3 array or three values"))
         arrays[name] = a
-    if not isinstance(n_types, (int, numpy.integer)) or not 1 <= n_types <= _MOMENTS_MAX_TYPES:
-        raise ValueError("a call takes 1 to 4 types: %r" % (n_types,))
-    if not isinstance(type0, (int, numpy.integer)) or not 0 <= type0 < 2 ** 32:
-        raise ValueError("type0 is a type id: %r" % (type0,))
-    if typeid is not None:
-        typeid = numpy.asarray(typeid)
-        if typeid.dtype.type not in (numpy.uint32, numpy.int32):
-            raise ValueError("typeid holds uint32 or int32 elements: %s" % typeid.dtype)
-        if typeid.ndim != 1:
-            raise ValueError("typeid is an array of N values")
-        if n_rows is not None and typeid.shape[0] != n_rows:
-            raise ValueError("the arrays differ in their number of rows (typeid has %d)" % typeid.shape[0])
-        n_rows = typeid.shape[0]
-    elif n_types != 1:
-        raise ValueError("without a typeid there is one group: n_types must be 1")
+    return arrays, dt, n_rows
+
+
+def _moments_rows(n_rows, rows):
+    """``(n_rows, rows, n)``: the number of rows settled, the row list checked, the number of entries."""
     if n_rows is None:
         raise ValueError("no input is an array: N says how many rows there are")
     if n_rows < 0:
         raise ValueError("N is a number of rows")
-    dt = numpy.dtype(numpy.float64) if dt is None else dt
     if rows is not None:
         rows = _list_rows(rows, n_rows)
-    n = n_rows if rows is None else rows.shape[0]
+    return n_rows, rows, n_rows if rows is None else rows.shape[0]
+
+
+def _moments_values(arrays, dt, rows, n):
+    """The nine float64 values per entry of `particle_moments`: ``(values, finite, all_finite)``, nine arrays of ``n``
+    values, the same of flags "is finite", and their conjunction.  The one place where the values are formed."""
+    dt = numpy.dtype(numpy.float64) if dt is None else dt
 
     def column(name, c):
         a, M = arrays[name], 1 if name in ('mass', 'energy') else 3
@@ -1191,18 +1222,237 @@ def particle_moments(mass, velocity, energy=None, position=None, typeid=None, ty
                   + [(0.5 * m) * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]), m * e] + [m * x[a] for a in range(3)])
     finite = [numpy.isfinite(q) for q in values]
     all_finite = numpy.logical_and.reduce(finite) if n else numpy.zeros(0, dtype=bool)
-    if typeid is None:
-        group = numpy.zeros(n, dtype=numpy.int64)
+    return values, finite, all_finite
+
+
+# ---- cell fields: the definition the GPU reduction (`pgsd.fl.PGSDFile.cell_moments_device`) equals exactly
+_CELLS_MAX_CELLS = 2 ** 20
+_CELLS_PIECE = 1024          # entries of a piece of a cell's sum
+_CELLS_LANES = 64
+
+
+class CellMoments(object):
+    """Conservation sums per grid cell (`cell_moments`): arrays of one entry (or one row) per cell, x fastest like
+    `cell_ids`.
+
+    Attributes:
+        count, bad (int64, n_cells): the entries of the cell, and those of them at which at least one of the nine
+            per-entry values is not finite.
+        nowhere (int): the entries with the id ``n_cells``, summed nowhere.
+        mass, kinetic, internal (float64, n_cells); momentum, first_moment (float64, n_cells x 3): as `Moments`'.
+        grid: ``(cx, cy, cz)`` or ``None``; cell_volume (float): the box volume (in 2-D the area) over ``n_cells``, or
+            ``None``.
+        mean_velocity, centre_of_mass (properties, n_cells x 3): NaN where the mass is 0.
+        density (property): ``mass / cell_volume``.
+
+    Every sum is over the finite values only and in the cell's own order (`cell_moments`).
+    """
+
+    __slots__ = ('count', 'bad', 'nowhere', 'mass', 'momentum', 'kinetic', 'internal', 'first_moment', 'grid', 'cell_volume')
+
+    def __init__(self, count, bad, nowhere, mass, momentum, kinetic, internal, first_moment, grid=None, cell_volume=None):
+        self.count = numpy.asarray(count, dtype=numpy.int64).reshape(-1)
+        T = self.count.shape[0]
+        self.bad = numpy.asarray(bad, dtype=numpy.int64).reshape(T)
+        self.nowhere = int(nowhere)
+        self.mass = numpy.asarray(mass, dtype=numpy.float64).reshape(T)
+        self.momentum = numpy.asarray(momentum, dtype=numpy.float64).reshape(T, 3)
+        self.kinetic = numpy.asarray(kinetic, dtype=numpy.float64).reshape(T)
+        self.internal = numpy.asarray(internal, dtype=numpy.float64).reshape(T)
+        self.first_moment = numpy.asarray(first_moment, dtype=numpy.float64).reshape(T, 3)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.cell_volume = None if cell_volume is None else float(cell_volume)
+
+    @classmethod
+    def from_sums(cls, count, bad, nowhere, sums, grid=None, cell_volume=None):
+        """From the ``n_cells x 9`` table of sums in the order of the per-entry values."""
+        s = numpy.asarray(sums, dtype=numpy.float64).reshape(-1, _MOMENTS_QUANTITIES)
+        return cls(count, bad, nowhere, s[:, 0].copy(), s[:, 1:4].copy(), s[:, 4].copy(), s[:, 5].copy(), s[:, 6:9].copy(),
+                   grid, cell_volume)
+
+    @property
+    def sums(self):
+        """The ``n_cells x 9`` table of sums in the order of the per-entry values."""
+        return numpy.concatenate([self.mass[:, None], self.momentum, self.kinetic[:, None], self.internal[:, None],
+                                  self.first_moment], axis=1)
+
+    @property
+    def centre_of_mass(self):
+        return self._per_mass(self.first_moment)
+
+    @property
+    def mean_velocity(self):
+        return self._per_mass(self.momentum)
+
+    @property
+    def density(self):
+        if self.cell_volume is None:
+            raise ValueError("the cell volume is not known: density needs a box (frame_cell_moments)")
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return self.mass / self.cell_volume
+
+    def _per_mass(self, a):
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(self.mass[:, None] != 0, a / self.mass[:, None], numpy.nan)
+
+    def as_grid(self, name):
+        """Attribute or property ``name`` shaped ``(cz, cy, cx)`` (``(cz, cy, cx, 3)`` for a vector)."""
+        if self.grid is None:
+            raise ValueError("the grid is not known: as_grid needs cell counts (frame_cell_moments)")
+        a = numpy.asarray(getattr(self, name))
+        cx, cy, cz = self.grid
+        return a.reshape((cz, cy, cx) + a.shape[1:])
+
+    def __repr__(self):
+        return "CellMoments(n_cells=%d, grid=%r, entries=%d, nowhere=%d)" % (self.count.shape[0], self.grid,
+                                                                            int(self.count.sum()), self.nowhere)
+
+
+def _cell_list(cell, n_cells):
+    """A list of cell ids, checked: int64 ids in ``[0, n_cells]``."""
+    if not isinstance(n_cells, (int, numpy.integer)) or not 1 <= n_cells <= _CELLS_MAX_CELLS:
+        raise ValueError("a grid holds 1 to 2^20 cells: %r" % (n_cells,))
+    cell = numpy.asarray(cell).reshape(-1)
+    if cell.size and cell.dtype.kind not in 'iu':
+        raise ValueError("cell holds integer cell ids")
+    cell = cell.astype(numpy.int64)
+    if cell.size and (cell.min() < 0 or cell.max() > n_cells):
+        raise ValueError("a cell id lies outside [0, n_cells]")
+    return cell
+
+
+def cell_offsets(cell_sorted, n_cells):
+    """The CSR offsets of a list of cell ids in cell order: int64, ``n_cells + 2`` entries,
+    ``numpy.searchsorted(cell_sorted, arange(n_cells + 2), side='left')``.  Entry ``c`` is the first position of cell
+    ``c`` (``n_cells`` is `cell_ids`' "nowhere" id) and the last entry is the list's length.  The definition of
+    `pgsd.fl.PGSDFile.cell_offsets_device`.  ValueError for ids that descend or lie outside ``[0, n_cells]``."""
+    cell = _cell_list(cell_sorted, n_cells)
+    if cell.size > 1 and (cell[1:] < cell[:-1]).any():
+        raise ValueError("the cell ids descend: the list is not in cell order")
+    return numpy.searchsorted(cell, numpy.arange(int(n_cells) + 2, dtype=numpy.int64), side='left').astype(numpy.int64)
+
+
+def _cell_ordered_sums(values, cell_sorted, offs, n_cells):
+    """Per cell the sum of ``values`` (float64, in cell order, non-finite values replaced by ``+0.0`` already) in the
+    order of `cell_moments`: one ``lanes[piece, lane]`` array and a loop over the 16 steps, the wave tree, then the
+    pieces of every cell in sequence."""
+    k = numpy.nonzero(cell_sorted < n_cells)[0]
+    within = k - offs[cell_sorted[k]]                        # the entry's place in its cell
+    per_cell = (numpy.diff(offs[:n_cells + 1]) + _CELLS_PIECE - 1) // _CELLS_PIECE
+    piece0 = numpy.concatenate(([0], numpy.cumsum(per_cell)))  # the first piece of every cell, all pieces numbered
+    piece = piece0[cell_sorted[k]] + within // _CELLS_PIECE
+    lane, step = within % _CELLS_LANES, (within % _CELLS_PIECE) // _CELLS_LANES
+    lanes = numpy.zeros((int(piece0[-1]), _CELLS_LANES), dtype=numpy.float64)
+    for t in range(_CELLS_PIECE // _CELLS_LANES):
+        at = step == t      # (one entry per lane and step: the indexed add is one float64 addition per touched lane)
+        lanes[piece[at], lane[at]] = lanes[piece[at], lane[at]] + values[k[at]]
+    h = _CELLS_LANES // 2
+    while h >= 1:
+        lanes = lanes[:, :h] + lanes[:, h:2 * h]
+        h //= 2
+    pieces = lanes[:, 0]
+    sums = numpy.zeros(n_cells, dtype=numpy.float64)
+    for j in range(int(per_cell.max()) if n_cells and per_cell.size else 0):
+        has = per_cell > j
+        sums[has] = sums[has] + pieces[piece0[:-1][has] + j]
+    return sums
+
+
+def cell_moments(mass, velocity, energy=None, position=None, cell=None, n_cells=None, rows=None, N=None):
+    """Mass, momentum, kinetic and internal energy and first moment per grid cell: the definition the GPU reduction
+    (`pgsd.fl.PGSDFile.cell_moments_device`, `HOOMDTrajectory.cell_moments_device`) equals exactly, the sums bit for bit.
+
+    Args:
+        mass, velocity, energy, position, rows, N: exactly `particle_moments`', and so are the nine float64 values per
+            entry.
+        cell: an integer array with one id per **list entry** (per row without ``rows``), in ``[0, n_cells]``, in any
+            order; ``n_cells`` is `cell_ids`' "nowhere" id.
+        n_cells (int): the cells, 1 to 2^20.
+
+    Per cell ``c < n_cells`` the result (`CellMoments`) holds the entries of the cell, those of them with a value that
+    is not finite, and the nine sums; ``nowhere`` counts the entries with id ``n_cells``, which are summed nowhere.
+
+    **The order of a cell's sum.**  The cell's entries are taken in list order (the order a stable sort by cell leaves
+    them in); a value that is not finite counts as ``+0.0``, each value for itself.  The sequence is cut into pieces of
+    1024 consecutive entries counted from the cell's first entry.  In a piece lane ``l`` of 64 starts at ``+0.0`` and adds
+    the piece's entries ``l, l + 64, ..., l + 960`` in that order, an entry past the end being ``+0.0``; the 64 lane sums
+    go through the wave tree of `column_stats`, ``p[i] += p[i + h]`` for ``h = 32 .. 1``; the cell's sum starts at
+    ``+0.0`` and adds the piece sums in ascending piece order.  A cell without entries has sums of ``+0.0``.  No fused
+    multiply-add anywhere.
+
+    ValueError: what `particle_moments` refuses for its inputs; ``n_cells`` outside 1 to 2^20; ``cell`` of another
+    length than the list, of non-integers or with an id outside ``[0, n_cells]``.
+    """
+    arrays, dt, n_rows = _moments_arrays(mass, velocity, energy, position, N)
+    n_rows, rows, n = _moments_rows(n_rows, rows)
+    if cell is None or n_cells is None:
+        raise ValueError("cell_moments takes one cell id per entry (cell) and the number of cells (n_cells)")
+    cell = _cell_list(cell, n_cells)
+    n_cells = int(n_cells)
+    if cell.shape[0] != n:
+        raise ValueError("cell holds one id per list entry: %d ids for %d entries" % (cell.shape[0], n))
+    values, finite, all_finite = _moments_values(arrays, dt, rows, n)
+    perm = numpy.argsort(cell, kind='stable')
+    cell_sorted = cell[perm]
+    offs = cell_offsets(cell_sorted, n_cells)
+    count = numpy.diff(offs[:n_cells + 1])
+    bad = numpy.bincount(cell_sorted[~all_finite[perm]], minlength=n_cells + 1)[:n_cells] if n else numpy.zeros(n_cells, numpy.int64)
+    sums = numpy.zeros((n_cells, _MOMENTS_QUANTITIES), dtype=numpy.float64)
+    for q in range(_MOMENTS_QUANTITIES):
+        sums[:, q] = _cell_ordered_sums(numpy.where(finite[q], values[q], 0.0)[perm], cell_sorted, offs, n_cells)
+    return CellMoments.from_sums(count, bad, int(offs[n_cells + 1] - offs[n_cells]), sums)
+
+
+def frame_cell_moments(frame_or_arrays, cells, centre=True, where=None, types=None, domain=None, box=None, dimensions=3):
+    """`cell_moments` of a frame's ``mass``, ``velocity``, ``energy`` and ``position`` over a selection, per cell of a
+    uniform ``cells = (cx, cy, cz)`` grid over the box: the host twin of `HOOMDTrajectory.cell_moments_device`, which
+    equals it exactly.
+
+    The rows come from `where_rows`, `domain_rows` or their intersection, as `frame_moments` forms them, and
+    ``cell = cell_ids(position[rows], box, cells, dimensions)``; ``cx * cy * cz <= 2**20``.  ``cell_volume`` is the box
+    volume (in 2-D the area) over the number of cells: the cells are equal in fractional coordinates and therefore in
+    volume, in a triclinic box too.  A position that is stored nowhere puts every row into the origin's cell.
+    ``centre=False`` leaves the position out of the sums (not out of the cells).  Returns a `CellMoments`.
+    """
+    if hasattr(frame_or_arrays, 'particles'):
+        frame = frame_or_arrays
+        arrays = _particle_arrays(frame.particles)
+        types = frame.particles.types if types is None else types
+        box = frame.configuration.box if box is None else box
+        if frame.configuration.dimensions is not None:
+            dimensions = int(frame.configuration.dimensions)
+        N = int(frame.particles.N)
     else:
-        group = (typeid if rows is None else typeid[rows]).astype(numpy.int64) - int(type0)
-    count, bad = numpy.zeros(n_types, numpy.int64), numpy.zeros(n_types, numpy.int64)
-    sums = numpy.zeros((n_types, _MOMENTS_QUANTITIES), dtype=numpy.float64)
-    for t in range(n_types):
-        mine = group == t
-        count[t], bad[t] = mine.sum(), (mine & ~all_finite).sum()
-        for q in range(_MOMENTS_QUANTITIES):
-            sums[t, q] = _ordered_sum(numpy.where(mine & finite[q], values[q], 0.0))
-    return Moments.from_sums(count, bad, n - int(count.sum()), sums)
+        arrays = dict((k, v) for k, v in frame_or_arrays.items() if v is not None)
+        if not arrays:
+            raise ValueError("arrays holds no per-particle array")
+        N = len(next(iter(arrays.values())))
+    if box is None:
+        raise ValueError("a cell grid needs the box")
+    grid = _order_cells(cells, dimensions)
+    n_cells = grid[0] * grid[1] * grid[2]
+    if n_cells > _CELLS_MAX_CELLS:
+        raise ValueError("a grid holds at most 2^20 cells: %r" % (cells,))
+    rows = None
+    if where is not None:
+        rows = where_rows(arrays, where, types)
+    if domain is not None:
+        if 'position' not in arrays:
+            raise ValueError("a domain needs box and the 'position' array")
+        inside = domain_rows(arrays['position'], box, domain, dimensions)
+        rows = inside if rows is None else numpy.intersect1d(rows, inside)
+    n = N if rows is None else len(rows)
+    if arrays.get('position') is None:
+        cell = numpy.repeat(cell_ids(numpy.zeros((1, 3), numpy.float32), box, grid, dimensions), n)
+    else:
+        p = numpy.asarray(arrays['position']).reshape(-1, 3)
+        cell = cell_ids(p if rows is None else p[numpy.asarray(rows, dtype=numpy.int64)], box, grid, dimensions)
+    got = cell_moments(arrays.get('mass'), arrays.get('velocity'), arrays.get('energy'),
+                       arrays.get('position') if centre else None, cell=cell, n_cells=n_cells, rows=rows, N=N)
+    b = numpy.asarray(box, dtype=numpy.float64).reshape(-1)
+    got.grid = grid
+    got.cell_volume = (b[0] * b[1] * (b[2] if int(dimensions) == 3 else 1.0)) / n_cells
+    return got
 
 
 def frame_moments(frame_or_arrays, by_type=True, centre=True, where=None, types=None, domain=None, box=None, dimensions=3):
@@ -3082,6 +3332,52 @@ class HOOMDTrajectory(object):
                 _MOMENTS_MAX_TYPES, len(types), by_type, chunks[0] is not None, count)
         finally:
             f.wait_read()
+
+    def cell_moments(self, idx, cells, centre=True, where=None, domain=None):
+        """`frame_cell_moments` of frame ``idx`` read through the host path: a `CellMoments`.  The definition of
+        `cell_moments_device`."""
+        return frame_cell_moments(self[int(idx)], cells, centre=centre, where=where, domain=domain)
+
+    def cell_moments_device(self, idx, cells, centre=True, where=None, domain=None):
+        """`frame_cell_moments` of frame ``idx``, reduced on the GPU: a `CellMoments` that equals
+        ``cell_moments(idx, cells, ...)`` exactly, the sums bit for bit.
+
+        The selection is `frame_moments_device`'s; without one the row list is every row in file order.  The list is
+        sorted by cell over the staged position chunk (`pgsd.fl.PGSDFile.order_rows_by_cell_device`) and the effective
+        chunks of ``mass``, ``velocity``, ``energy`` and, with ``centre``, ``position`` are reduced per cell in one
+        segmented pass (`pgsd.fl.PGSDFile.cell_moments_device`); a chunk the selection or the ordering staged is not read
+        again, a chunk that is stored nowhere costs nothing, and a position that is stored nowhere puts every row into
+        the origin's cell.  One `wait_read` at the end releases the staged chunks.  No per-particle data reaches the host.
+        """
+        idx = self._frame_index(idx)
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        grid = _order_cells(cells, dims)
+        n_cells = grid[0] * grid[1] * grid[2]
+        if n_cells > _CELLS_MAX_CELLS:
+            raise ValueError("a grid holds at most 2^20 cells: %r" % (cells,))
+        try:
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
+            if rows is None:
+                rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
+            if f_pos is not None:
+                cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
+            else:
+                one = cell_ids(numpy.zeros((1, 3), numpy.float32), box, grid, dims).astype(numpy.int32)
+                cell = fl._device_rows((max(count, 1),), numpy.int32, f.pipeline_device(), one)
+            chunks = []
+            for name in ('mass', 'velocity', 'energy', 'position' if centre else None):
+                fr = None if name is None else self._effective_frame(idx, 'particles/' + name, n_global)
+                chunks.append(None if fr is None else (fr, 'particles/' + name))
+            defaults = numpy.concatenate([numpy.broadcast_to(numpy.asarray(_PARTICLE_FIELDS[name][2], dtype=numpy.float32),
+                                                             (M,)) for name, M, _ in _MOMENTS_INPUTS]).astype(numpy.float64)
+            got = f.cell_moments_device(chunks, rows, cell, count, n_cells, defaults)
+        finally:
+            f.wait_read()
+        b = numpy.asarray(box, dtype=numpy.float64).reshape(-1)
+        got.grid = grid
+        got.cell_volume = (b[0] * b[1] * (b[2] if dims == 3 else 1.0)) / n_cells
+        return got
 
     def _types_of(self, idx):
         """The type names frame ``idx`` reads: its own, else frame 0's, else the schema's default."""

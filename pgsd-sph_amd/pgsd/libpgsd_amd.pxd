@@ -233,6 +233,12 @@ cdef extern from "pgsd_private.h" nogil:
                                         const double* vectors_a, const double* vectors_b, uint32_t flags,
                                         uint32_t dimensions, uint32_t type0, uint32_t n_types, const uint32_t* rows,
                                         uint64_t n, double* out_rows, uint64_t* out_counts, double* out_values)
+    int pgsd_cell_offsets_device(pgsd_handle* handle, const int32_t* cell, uint64_t n, uint32_t n_cells,
+                                 uint32_t* out_offsets)
+    int pgsd_cell_moments_device(pgsd_handle* handle, const pgsd_index_entry* mass, const pgsd_index_entry* velocity,
+                                 const pgsd_index_entry* energy, const pgsd_index_entry* position, const double* defaults,
+                                 const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t n_cells,
+                                 uint64_t* out_counts, double* out_sums)
     int pgsd_chunk_stats_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                                 uint32_t with_norm2, uint64_t* out_counts, double* out_values)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
