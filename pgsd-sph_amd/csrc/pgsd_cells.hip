@@ -24,6 +24,7 @@
 // No global atomic on a float, no contraction wherever a value is formed or added.  Shared device helpers: pgsd_stats.hpp,
 // pgsd_kernels.hpp; the launchers' host side: pgsd_scratch.hpp.
 #include "pgsd_stats.hpp"
+#include "pgsd_cells.hpp"
 #include "pgsd_scratch.hpp"
 
 namespace pgsd_amd

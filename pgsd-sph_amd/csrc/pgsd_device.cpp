@@ -210,6 +210,7 @@ int DevicePipeline::init()
         warm_census_kernels();
         warm_order_kernels();
         warm_cells_kernels();
+        warm_neighbours_kernels();
         int brc = compare_buffers();
         if (brc != PGSD_SUCCESS)
             return brc;
@@ -750,6 +751,18 @@ int device_pipeline_cell_moments(DevicePipeline* p, const ChunkRange* ranges, co
     {
     std::string local;
     int rc = report(p, p->cell_moments(ranges, c, out_counts, out_sums, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
+int device_pipeline_neighbours(DevicePipeline* p, long long file_offset, size_t bytes, const NeighboursArgs& a,
+                               const double* edges2, uint32_t* out_count, double* out_nearest2, uint32_t* out_nearest,
+                               uint64_t* out_summary, double* out_closest2, std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->neighbours(file_offset, bytes, a, edges2, out_count, out_nearest2, out_nearest, out_summary,
+                                     out_closest2, &local), err, true);
     if (rc != PGSD_SUCCESS && err && !local.empty())
         *err = local; // the launcher's own message comes first
     return rc;

@@ -154,6 +154,8 @@ class DevicePipeline
                             std::string* why);
     int cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets, std::string* why);
     int cell_moments(const ChunkRange* ranges, CellMomentsArgs c, uint64_t* out_counts, double* out_sums, std::string* why);
+    int neighbours(long long file_offset, size_t bytes, NeighboursArgs a, const double* edges2, uint32_t* out_count,
+                   double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2, std::string* why);
     int wait_read();
 
     // ---- accessors ----

@@ -584,6 +584,19 @@ int DevicePipeline::cell_moments(const ChunkRange* ranges, CellMomentsArgs c, ui
                           { return launch_cell_moments(c, out_counts, out_sums, m_res.pack_stream, err); });
     }
 
+// Neighbour census: the position chunk the ordering left staged (or staged here); the lists and the per-entry outputs are
+// the caller's.
+int DevicePipeline::neighbours(long long file_offset, size_t bytes, NeighboursArgs a, const double* edges2, uint32_t* out_count,
+                               double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2,
+                               std::string* why)
+    {
+    const ChunkRange range = {file_offset, bytes};
+    const void** const slot = &a.pos;
+    return staged_launch(&range, &slot, 1, a.N, true, why, [&](std::string* err)
+                         { return launch_neighbours(a, edges2, out_count, out_nearest2, out_nearest, out_summary, out_closest2,
+                                                    m_res.pack_stream, err); });
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

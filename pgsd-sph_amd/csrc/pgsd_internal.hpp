@@ -427,6 +427,44 @@ int device_pipeline_cell_offsets(DevicePipeline*, const int32_t* cell, uint64_t 
 // wait_read.
 int device_pipeline_cell_moments(DevicePipeline*, const ChunkRange* ranges, const CellMomentsArgs& c, uint64_t* out_counts,
                                  double* out_sums, std::string* err);
+// Neighbour census (pgsd.hoomd.particle_neighbours is the definition): per entry of a row list in cell order the
+// entries of the periodically adjacent cells whose single-shift minimum-image distance lies strictly inside r, the
+// nearest of them, and over the list the count histogram, the closest pair and a pair histogram over given edges.
+enum
+    {
+    NEIGHBOURS_MAX_BINS = 1024,  // bins of the pair histogram
+    NEIGHBOURS_COUNT_BINS = 257, // 0 .. 255 neighbours, then 256 and more
+    NEIGHBOURS_HEAD_WORDS = 8,   // n, nowhere, pairs, count_min, count_max, closest, the closest pair's two rows
+    NEIGHBOURS_NONE = 0xFFFFFFFFu
+    };
+struct NeighboursArgs
+    {
+    const void* pos;      // the staged position chunk
+    uint64_t N;           // its rows
+    const uint32_t* rows; // device, n entries in cell order
+    const int32_t* cell;  // device, n ids, non-decreasing, in [0, n_cells]; n_cells: nowhere
+    uint64_t n;
+    double vectors[6];    // Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz
+    double r, r2;         // the range and r * r, formed once
+    uint32_t cells[3];
+    uint32_t n_cells;
+    uint32_t dims, f64, bins, pad;
+    };
+// the summary of no entry: bins words of pair histogram behind the head and the count histogram
+inline void neighbours_of_nothing(uint32_t bins, uint64_t* out_summary, double* out_closest2)
+    {
+    std::fill(out_summary, out_summary + NEIGHBOURS_HEAD_WORDS + NEIGHBOURS_COUNT_BINS + bins, (uint64_t)0);
+    out_summary[5] = out_summary[6] = out_summary[7] = NEIGHBOURS_NONE;
+    *out_closest2 = HUGE_VAL;
+    }
+// stage the position chunk at `file_offset` (a.N rows; a.pos is filled in) -- or take it from what the ordering left
+// staged --, check the lists, search on the GPU; edges2 (host, a.bins + 1 doubles, or null without bins); out_count,
+// out_nearest2, out_nearest (device, a.n entries each, or null); out_summary (host, 8 + 257 + a.bins words) and
+// out_closest2 (host) are written on success only, and so are the device outputs; synchronous.  An entry >= a.N, an id
+// outside [0, n_cells] and a descending id refuse the call.  The staged rows stay until the next wait_read.
+int device_pipeline_neighbours(DevicePipeline*, long long file_offset, size_t bytes, const NeighboursArgs& a,
+                               const double* edges2, uint32_t* out_count, double* out_nearest2, uint32_t* out_nearest,
+                               uint64_t* out_summary, double* out_closest2, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

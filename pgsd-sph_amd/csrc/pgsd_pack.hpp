@@ -295,6 +295,14 @@ int launch_cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint3
                         std::string* err);
 int launch_cell_moments(const CellMomentsArgs& c, uint64_t* out_counts, double* out_sums, hipStream_t stream, std::string* err);
 
+// neighbour census (pgsd_neighbours.hip; NeighboursArgs, a.pos filled in): check, offsets, compaction of the listed
+// positions, one lane per entry over the runs of the adjacent cells, one workgroup for the minima.  edges2 (host, a.bins
+// + 1 doubles; null without bins); out_count, out_nearest2, out_nearest (device, a.n entries each, or null); out_summary
+// (host, 8 + 257 + a.bins words) and out_closest2 (host) are written on success only.  Synchronises `stream`;
+// PGSD_ERROR_INVALID_ARGUMENT for an id that descends or lies outside [0, n_cells] and for an entry >= a.N
+int launch_neighbours(const NeighboursArgs& a, const double* edges2, uint32_t* out_count, double* out_nearest2,
+                      uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);
@@ -353,6 +361,7 @@ void warm_compaction_kernels();
 void warm_census_kernels();
 void warm_order_kernels();
 void warm_cells_kernels();
+void warm_neighbours_kernels();
 
 // algorithmic traffic of one job: bytes that must be read (needed columns only, plus the
 // gather index) and chunk bytes written

@@ -41,6 +41,9 @@
  *                     cell order, and per grid cell the mass, momentum, kinetic and internal energy and first moment of
  *                     its entries -- the coarse-grained density and velocity field -- from the staged chunks in one
  *                     segmented pass)
+ *                     pgsd_neighbours_device (pgsd.fl's neighbours_device, behind pgsd.hoomd's frame_neighbours_device:
+ *                     per entry of a row list in cell order the neighbours inside a range and the nearest of them, and
+ *                     over the list the count histogram, the closest pair and the pair histogram of g(r))
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -333,6 +336,47 @@ extern "C"
                                  const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* energy,
                                  const struct pgsd_index_entry* position, const double defaults[8], const uint32_t* rows,
                                  const int32_t* cell, uint64_t n, uint32_t n_cells, uint64_t* out_counts, double* out_sums);
+
+    /* Neighbour census (pgsd.hoomd.particle_neighbours is the definition, and the results equal it exactly: every
+       counter and index, the two distances bit for bit).  position: an N x 3 float32 or float64 chunk.  vectors:
+       (Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz) of the box, r the range, cells the grid (cx, cy, cz; cz == 1 with dimensions ==
+       2).  rows (device memory, n entries) and cell (device memory, n int32 entries, non-decreasing, in [0, n_cells]) are
+       a row list in cell order and the ids of its entries, as pgsd_order_rows_by_cell_device leaves them for the same
+       grid; an entry with id n_cells is nowhere and is nobody's neighbour.
+       Entry j is a CANDIDATE of entry i when j != i as a list position (the same row listed twice is two entries), both
+       have a cell and j's cell is periodically adjacent to i's: per axis the offsets {0} at one cell, {0, +1} at two and
+       {-1, 0, +1} otherwise, indices wrapping.  The DISTANCE of i -> j, float64 from the stored values, no contraction:
+       d = x_j - x_i; if d_z >= Lz/2 subtract (xz*Lz, yz*Lz, Lz), else if d_z < -(Lz/2) add it (dimensions == 3 only;
+       otherwise d_z = 0); the same for y with Ly/2 and (xy*Ly, Ly), then for x with Lx/2 and Lx; d2 = (d_x*d_x +
+       d_y*d_y) + d_z*d_z.  j is a NEIGHBOUR when d2 < r*r, strictly, r*r formed once.
+       Device outputs, n entries each, each optional (NULL):
+           out_count[k]      the neighbours of entry k
+           out_nearest2[k]   the smallest d2 among them, +inf without one
+           out_nearest[k]    the smallest list position that attains it, 0xFFFFFFFF without one
+       Host outputs:
+           out_summary[0 .. 7]       n; the entries nowhere; the sum of the counts (ordered pairs); the smallest and the
+                                     largest count over the entries that have a cell (0 without one); the smallest list
+                                     position whose nearest2 is the smallest; that entry's row and its nearest's row (the
+                                     last three 0xFFFFFFFF where no entry has a neighbour)
+           out_summary[8 + k]        k < 256: the entries that have a cell and k neighbours; k == 256: 256 or more
+           out_summary[265 + b]      b < bins: the neighbour pairs with edges2[b] <= d2 < edges2[b + 1] -- the bin
+                                     searchsorted(edges2, d2, 'right') - 1; a pair outside the edges is in no bin
+           *out_closest2             the smallest nearest2, +inf where no entry has a neighbour
+       edges2: a HOST array of bins + 1 doubles (pgsd.hoomd.neighbour_edges2), copied as it is: the GPU never recomputes
+       an edge.  bins == 0: no pair histogram, edges2 may be NULL.
+       The chunk is staged whole unless an earlier call (the ordering) left it staged, the search runs on the handle's GPU
+       and the call synchronises; the staged rows are kept until the next pgsd_device_wait_read.  n == 0 succeeds with
+       the summary of no entry and launches nothing.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), every output as it was: a chunk that is not float32
+       or float64 or has another column count than 3; N or n >= 2^32; dimensions other than 2 or 3; r not finite or not
+       positive; a box length that is not positive; a count outside 1 to 1024, cz != 1 with dimensions == 2, more than
+       2^20 cells; r above half the nearest plane distance of an axis that takes part (an image would count twice); a
+       count above floor(plane distance / r) (cells narrower than r); bins > 1024; edges that descend or are not numbers;
+       an id that is below its predecessor or outside [0, n_cells]; an entry >= N. */
+    int pgsd_neighbours_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position, const double vectors[6],
+                               double r, uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
+                               const int32_t* cell, uint64_t n, uint32_t bins, const double* edges2, uint32_t* out_count,
+                               double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

@@ -935,6 +935,107 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_neighbours_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                      const double vectors[6], double r, uint32_t dimensions, const uint32_t cells[3],
+                                      const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t bins, const double* edges2,
+                                      uint32_t* out_count, double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary,
+                                      double* out_closest2)
+    try
+    {
+    static const char* who = "pgsd_neighbours_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !vectors || !cells || !out_summary || !out_closest2 || (n > 0 && (!rows || !cell))
+        || (bins > 0 && !edges2))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    pgsd_index_entry c = *position; // a flush may move the index storage
+    if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
+        return refuse("the position chunk holds float32 or float64 elements");
+    if (c.M != 3)
+        return refuse("the position chunk has 3 columns");
+    if (c.N >= (1ull << 32))
+        return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+    if (n >= (1ull << 32))
+        return refuse("a list holds fewer than 2^32 entries");
+    if (dimensions != 2 && dimensions != 3)
+        return refuse("dimensions is 2 or 3");
+    if (!(r > 0.0 && r < HUGE_VAL))
+        return refuse("the range must be finite and positive");
+    const double Lx = vectors[0], Ly = vectors[1], Lz = vectors[2];
+    if (!(Lx > 0.0 && Ly > 0.0 && (dimensions == 2 || Lz > 0.0)))
+        return refuse("box lengths must be positive (Lz unless dimensions == 2)");
+    // pgsd.hoomd.ghost_fractions and cell_grid_for, from the tilt factors the vectors hold (xy * Ly is an exact product
+    // of float32 values, so the quotient is the stored factor)
+    const double xy = vectors[3] / Ly, xz = Lz > 0.0 ? vectors[4] / Lz : 0.0, yz = Lz > 0.0 ? vectors[5] / Lz : 0.0;
+    const double t = xy * yz - xz;
+    const double u = 1.0 + xy * xy;
+    const double plane[3] = {Lx / std::sqrt(u + t * t), Ly / std::sqrt(1.0 + yz * yz), Lz};
+    uint64_t n_cells = 1;
+    for (int a = 0; a < 3; a++)
+        {
+        if (cells[a] < 1 || cells[a] > ORDER_MAX_AXIS_CELLS)
+            return refuse("every axis takes 1 to 1024 cells");
+        n_cells *= cells[a];
+        if (a == 2 && dimensions == 2)
+            {
+            if (cells[2] != 1)
+                return refuse("dimensions == 2 takes one z cell (z is not looked at)");
+            continue;
+            }
+        const double g = r / plane[a];
+        if (!(g <= 0.5))
+            return refuse("the range exceeds half the box's nearest plane distance on an axis: an image would count twice");
+        const double most = std::min(std::max(std::floor(1.0 / g), 1.0), (double)ORDER_MAX_AXIS_CELLS);
+        if ((double)cells[a] > most)
+            return refuse("the cells are narrower than the range on an axis");
+        }
+    if (n_cells > CELLS_MAX_CELLS)
+        return refuse("a grid holds 1 to 2^20 cells");
+    if (bins > NEIGHBOURS_MAX_BINS)
+        return refuse("the pair histogram holds at most 1024 bins");
+    for (uint32_t k = 0; k < bins; k++)
+        if (!(edges2[k] <= edges2[k + 1]))
+            return refuse("the edges of the pair histogram descend (or are not numbers)");
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    NeighboursArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = c.N;
+    a.rows = rows;
+    a.cell = cell;
+    a.n = n;
+    std::copy(vectors, vectors + 6, a.vectors);
+    a.r = r;
+    a.r2 = r * r;
+    std::copy(cells, cells + 3, a.cells);
+    a.n_cells = (uint32_t)n_cells;
+    a.dims = dimensions;
+    a.f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    a.bins = bins;
+    if (n == 0)
+        {
+        neighbours_of_nothing(bins, out_summary, out_closest2);
+        return PGSD_SUCCESS;
+        }
+    if (c.N == 0)
+        return refuse("an entry of the row list lies outside the position chunk (nothing was computed)");
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "neighbour census: ", [&](std::string* err)
+                          { return device_pipeline_neighbours(s->dev, foff, bytes, a, edges2, out_count, out_nearest2,
+                                                              out_nearest, out_summary, out_closest2, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position_a,
                                                const struct pgsd_index_entry* image_a,
                                                const struct pgsd_index_entry* position_b,

@@ -18,7 +18,11 @@
            (``pgsd.hoomd.frame_displacements`` on the host: no GPU);
            ``--cells CX,CY,CZ`` adds the occupied cells of such a grid, the smallest and largest count, the largest
            density and mean speed with their cell indices and the particles nowhere (``--types``;
-           ``pgsd.hoomd.frame_cell_moments`` on the host: no GPU).
+           ``pgsd.hoomd.frame_cell_moments`` on the host: no GPU);
+           ``--neighbours R`` adds the neighbour census inside the range R: the search grid, the entries and those
+           nowhere, the mean, smallest and largest neighbour count, the isolated entries and the closest pair with its
+           rows and distance, and with ``--bins B`` the g(r) table (``--types``; ``pgsd.hoomd.frame_neighbours`` on the
+           host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -87,7 +91,32 @@ def _cmd_info(args):
         _print_displacement(args, frame)
     if args.cells:
         _print_cells(args, frame)
+    if args.neighbours is not None:
+        _print_neighbours(args, frame)
 
+
+def _print_neighbours(args, frame):
+    """``info --neighbours``: `pgsd.hoomd.frame_neighbours` of one frame inside the range R, on the host."""
+    import numpy
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        snap = traj[frame]
+        m = hoomd.frame_neighbours(snap, args.neighbours, bins=args.bins or 0, where=where)
+    print("neighbours of frame %d inside %r over %d x %d x %d cells%s:"
+          % ((frame, m.r) + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  entries:      %d  nowhere: %d" % (m.n, m.nowhere))
+    if m.n > m.nowhere:
+        print("  count:        mean %r  smallest %d  largest %d" % (m.mean_count, m.count_min, m.count_max))
+        print("  isolated:     %d" % m.isolated)
+    if m.closest_rows is not None:
+        print("  closest pair: rows %d and %d at distance %r" % (m.closest_rows + (m.closest_distance,)))
+    if m.bins:
+        b = numpy.asarray(snap.configuration.box, dtype=numpy.float64)
+        mid, g = m.rdf(b[0] * b[1] * (b[2] if m.dimensions == 3 else 1.0))
+        print("  g(r):")
+        for k in range(m.bins):
+            print("    %-12.6g %-12.6g %d" % (mid[k], g[k], m.pair_hist[k]))
 
 def _print_cells(args, frame):
     """``info --cells``: `pgsd.hoomd.frame_cell_moments` of one frame over a CX x CY x CZ grid, on the host."""
@@ -241,8 +270,9 @@ def _print_balance(args, frame):
     with hoomd.open(args.file, 'r') as traj:
         snap = traj[frame]
     position, box, dims = snap.particles.position, snap.configuration.box, int(snap.configuration.dimensions)
-    _, splits = hoomd.balanced_grid(position, box, nx, ny, nz, bins=args.bins, dimensions=dims)
-    print("balance of frame %d over %d x %d x %d cells (%d bins):" % (frame, nx, ny, nz, args.bins))
+    bins = 1024 if args.bins is None else args.bins
+    _, splits = hoomd.balanced_grid(position, box, nx, ny, nz, bins=bins, dimensions=dims)
+    print("balance of frame %d over %d x %d x %d cells (%d bins):" % (frame, nx, ny, nz, bins))
     for axis, split in zip('xyz', splits):
         print("  %s_split:        %s" % (axis, 'None' if split is None else '[' + ', '.join(repr(w) for w in split) + ']'))
     for label, grid in (('equal', (None, None, None)), ('balanced', splits)):
@@ -277,7 +307,9 @@ def main(argv=None):
     p.add_argument('-f', '--frame', type=int, default=-1, help="frame whose chunks are listed (default: last)")
     p.add_argument('--balance', type=str, default=None, metavar='NX,NY,NZ',
                    help="print the split lists that balance the frame over NX x NY x NZ cells, and the cell counts")
-    p.add_argument('--bins', type=int, default=1024, help="histogram bins per axis for --balance (a power of two)")
+    p.add_argument('--bins', type=int, default=None, metavar='B',
+                   help="histogram bins per axis for --balance (a power of two; default: 1024); with --neighbours the "
+                        "g(r) table over B bins (1 to 1024; default: no table)")
     p.add_argument('--stats', action='store_true',
                    help="print count, nan, inf, min, max and mean per field and column of the frame")
     p.add_argument('--fields', type=str, default=None, metavar='NAME[,NAME...]',
@@ -296,6 +328,9 @@ def main(argv=None):
     p.add_argument('--cells', type=str, default=None, metavar='CX,CY,CZ',
                    help="print the occupied cells, the smallest and largest count, the largest density and speed with "
                         "their cells and the particles nowhere, over a uniform CX x CY x CZ grid")
+    p.add_argument('--neighbours', type=float, default=None, metavar='R',
+                   help="print the neighbour census inside the range R: grid, entries, mean, smallest and largest count, "
+                        "isolated entries and the closest pair")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")
     p.add_argument('--minimum-image', action='store_true',
                    help="--displacement of the wrapped positions, folded into the box, instead of through the image flags")

@@ -1876,6 +1876,84 @@ cdef class PGSDFile:
         counts = counts.astype(numpy.int64)
         return _hoomd.CellMoments.from_sums(counts[0:2 * T:2].copy(), counts[1:2 * T:2].copy(), int(counts[2 * T]), sums)
 
+    def neighbours_device(self, frame, name, box, r, cells, rows, cell, n=None, dimensions=3, bins=0, return_rows=False):
+        """The neighbour census of a row list in cell order inside the range ``r``, on the GPU: the code base's pair pass.
+
+        Args:
+            frame (int), name (str): the position chunk, N x 3 float32 or float64.
+            box: ``(Lx, Ly, Lz, xy, xz, yz)``; the kernel receives :func:`pgsd.hoomd.box_vectors` of it.
+            r (float): the range, finite and positive, at most half the box's nearest plane distance on every axis.
+            cells: ``(cx, cy, cz)``, no narrower than ``r`` (:func:`pgsd.hoomd.neighbour_grid_for`), up to 2^20 cells.
+            rows, cell: 32-bit row indices and int32 cell ids in GPU memory, one id per entry, non-decreasing, in
+                ``[0, n_cells]`` -- what :meth:`order_rows_by_cell_device` leaves for the same grid.
+            n (int): the number of entries to take (``None``: all of ``rows``).
+            dimensions (int): 2 never looks at z.
+            bins (int): 0, or 1 to 1024 bins of the pair histogram over :func:`pgsd.hoomd.neighbour_edges2`, which are
+                computed here on the host and handed to the kernel as they are.
+            return_rows (bool): keep the per-entry results in GPU memory.
+
+        Returns:
+            A :class:`pgsd.hoomd.Neighbours`: exactly :func:`pgsd.hoomd.particle_neighbours` of the same list -- every
+            counter and index, ``closest2`` bit for bit.  With ``return_rows`` its ``rows`` and ``cell`` are the arguments
+            and ``count``, ``nearest`` (int32, typed like the row lists: ``0xFFFFFFFF``, no neighbour, reads ``-1``) and
+            ``nearest2`` (float64) are arrays of ``n`` entries in GPU memory; otherwise the five are ``None``.  The chunk
+            is staged whole unless the ordering left it staged; the staged rows are kept until the next
+            :meth:`wait_read`.  What the library refuses (:c:func:`pgsd_neighbours_device`) raises ValueError and
+            computes nothing.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        c_box = numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6]
+        if c_box.shape[0] != 6:
+            raise ValueError("box must hold 6 values")
+        c_vectors = numpy.ascontiguousarray(_hoomd.box_vectors(c_box), dtype=numpy.float64)
+        grid = [int(v) for v in cells]
+        if len(grid) != 3 or any(not 0 <= v < (1 << 32) for v in grid):
+            raise ValueError("neighbours_device: cells holds three counts, each 1 to 1024")
+        c_cells = numpy.array(grid, dtype=numpy.uint32)
+        k_bins = int(bins)
+        if not 0 <= k_bins < (1 << 32):
+            raise ValueError("neighbours_device: bins is 0 or 1 to 1024")
+        range_ = float(r)
+        if 1 <= k_bins <= 1024 and range_ > 0.0 and range_ < float('inf'):
+            c_edges = numpy.ascontiguousarray(_hoomd.neighbour_edges2(range_, k_bins), dtype=numpy.float64)
+        else:
+            c_edges = numpy.zeros(1 + (k_bins if k_bins <= 1024 else 0), dtype=numpy.float64)   # (the library refuses the rest)
+        c_rows, count = _row_list("neighbours_device", rows, n)
+        c_cell, _ = _row_list("neighbours_device", cell, count)
+        summary = numpy.zeros(8 + 257 + (k_bins if k_bins <= 1024 else 0), dtype=numpy.uint64)
+        closest2 = numpy.zeros(1, dtype=numpy.float64)
+        cdef uintptr_t p_count = 0, p_nearest2 = 0, p_nearest = 0
+        out_count = out_nearest2 = out_nearest = None
+        if return_rows:
+            device = self.pipeline_device()
+            out_count = _device_empty((max(count, 1),), numpy.int32, device)
+            out_nearest = _device_empty((max(count, 1),), numpy.int32, device)
+            out_nearest2 = _device_empty((max(count, 1),), numpy.float64, device)
+            p_count, p_nearest, p_nearest2 = out_count.data_ptr(), out_nearest.data_ptr(), out_nearest2.data_ptr()
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_edges = c_edges.ctypes.data, p_summary = summary.ctypes.data, p_closest2 = closest2.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0, c_bins = k_bins
+        cdef double c_r = range_
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_neighbours_device(&self._handle, &entry, <const double*>p_vectors, c_r, c_dims,
+                                              <const uint32_t*>p_cells, <const uint32_t*>p_rows, <const int32_t*>p_cell, c_n,
+                                              c_bins, <const double*>p_edges, <uint32_t*>p_count, <double*>p_nearest2,
+                                              <uint32_t*>p_nearest, <uint64_t*>p_summary, <double*>p_closest2)
+            err = errno
+        _raise_refused("neighbours_device", retval, "refused", self._name, err)
+        got = _hoomd.Neighbours(range_, k_bins, grid, int(dimensions), summary, closest2[0])
+        if return_rows:
+            got.rows, got.cell = _device_head(rows, count), _device_head(cell, count)
+            got.count, got.nearest = _device_head(out_count, count), _device_head(out_nearest, count)
+            got.nearest2 = _device_head(out_nearest2, count)
+        return got
+
     def frame_displacements_device(self, chunks, vectors_a, vectors_b, minimum_image=False, dimensions=3, type0=0,
                                    n_types=1, rows=None, n=None, out=None):
         """Drift, squared displacement and the largest move between two frames per particle type, reduced on the GPU in

@@ -1455,6 +1455,345 @@ def frame_cell_moments(frame_or_arrays, cells, centre=True, where=None, types=No
     return got
 
 
+# ---- neighbour census: the definition the GPU pair pass (`pgsd.fl.PGSDFile.neighbours_device`) equals exactly
+_NEIGHBOURS_NONE = 0xFFFFFFFF       # no list position: `nearest` of an entry without a neighbour, `closest` of no pair
+_NEIGHBOURS_COUNT_BINS = 257        # count_hist: 0 .. 255 neighbours, then 256 and more
+_NEIGHBOURS_MAX_BINS = 1024         # pair_hist
+_NEIGHBOURS_SUMMARY_WORDS = 8       # n, nowhere, pairs, count_min, count_max, closest, closest_rows[2]
+_NEIGHBOURS_PAIRS_PER_STEP = 1 << 22
+
+
+def pair_distance2(xi, xj, vectors, dimensions=3):
+    """The squared distance of the pair ``i -> j`` under HOOMD's single-shift minimum image: the arithmetic of one pair of
+    `particle_neighbours` and of the GPU pair kernel, float64 throughout (float32 positions are converted exactly, no
+    fused multiply-add).
+
+    ``xi``, ``xj``: ``... x 3`` positions that broadcast; ``vectors``: `box_vectors` ``(Lx, Ly, Lz, xy*Ly, xz*Lz,
+    yz*Lz)``.  ``d = xj - xi`` per axis; then, z first (only if ``dimensions == 3``): if ``d_z >= Lz/2`` the vector
+    ``(xz*Lz, yz*Lz, Lz)`` is subtracted from ``(d_x, d_y, d_z)``, else if ``d_z < -(Lz/2)`` it is added; y the same
+    with ``Ly/2`` and ``(xy*Ly, Ly)`` on ``(d_x, d_y)``; x the same with ``Lx/2`` and ``Lx`` on ``d_x``.  With
+    ``dimensions == 2`` ``d_z`` is 0 and z is never looked at.  ``d2 = (d_x*d_x + d_y*d_y) + d_z*d_z``.
+
+    One shift per axis and no division: this is not the ``rint(d / L)`` fold of `displacement_vectors`.  It has HOOMD's
+    range of validity -- a stored position more than one image outside the box is not folded fully, and its pairs are
+    whatever this formula gives, here and on the GPU alike."""
+    dimensions = int(dimensions)
+    if dimensions not in (2, 3):
+        raise ValueError("dimensions must be 2 or 3")
+    v = numpy.asarray(vectors, dtype=numpy.float64).reshape(-1)
+    if v.shape[0] != 6:
+        raise ValueError("box vectors hold six values (pgsd.hoomd.box_vectors)")
+    a = numpy.asarray(xi).astype(numpy.float64)
+    b = numpy.asarray(xj).astype(numpy.float64)
+    with numpy.errstate(over='ignore', invalid='ignore'):
+        dx = b[..., 0] - a[..., 0]
+        dy = b[..., 1] - a[..., 1]
+        if dimensions == 3:
+            dz = b[..., 2] - a[..., 2]
+            h = v[2] / 2
+            up, down = dz >= h, dz < -h
+            dx = numpy.where(up, dx - v[4], numpy.where(down, dx + v[4], dx))
+            dy = numpy.where(up, dy - v[5], numpy.where(down, dy + v[5], dy))
+            dz = numpy.where(up, dz - v[2], numpy.where(down, dz + v[2], dz))
+        else:
+            dz = numpy.zeros(numpy.broadcast(dx, dy).shape, dtype=numpy.float64)
+        h = v[1] / 2
+        up, down = dy >= h, dy < -h
+        dx = numpy.where(up, dx - v[3], numpy.where(down, dx + v[3], dx))
+        dy = numpy.where(up, dy - v[1], numpy.where(down, dy + v[1], dy))
+        h = v[0] / 2
+        up, down = dx >= h, dx < -h
+        dx = numpy.where(up, dx - v[0], numpy.where(down, dx + v[0], dx))
+        return (dx * dx + dy * dy) + dz * dz
+
+
+def _neighbour_range(r):
+    r = float(r)
+    if not (r > 0.0 and r < float('inf')):
+        raise ValueError("the neighbour range must be finite and positive: %r" % (r,))
+    return r
+
+
+def neighbour_grid_for(box, r, dimensions=3):
+    """``(cx, cy, cz)``: the grid `particle_neighbours` searches with for the range ``r`` -- `cell_grid_for` ``(box, r,
+    dimensions)``, and while ``cx*cy*cz > 2**20`` (`cell_offsets`' limit) the largest count ``c`` replaced by
+    ``(c + 1) // 2``, the lowest axis on a tie.  The coarsening only makes cells wider."""
+    c = list(cell_grid_for(box, _neighbour_range(r), dimensions))
+    while c[0] * c[1] * c[2] > _CELLS_MAX_CELLS:
+        a = c.index(max(c))
+        c[a] = (c[a] + 1) // 2
+    return tuple(c)
+
+
+def _neighbour_grid(box, r, cells, dimensions):
+    """The grid of a neighbour search, checked (`particle_neighbours` lists what is refused)."""
+    r = _neighbour_range(r)
+    dimensions = int(dimensions)
+    g = ghost_fractions(box, r, dimensions)
+    for a in range(2 if dimensions == 2 else 3):
+        if g[a] > 0.5:
+            raise ValueError("the range %r exceeds half the box's nearest plane distance on axis %d: an image would "
+                             "count twice" % (r, a))
+    if cells is None:
+        return neighbour_grid_for(box, r, dimensions)
+    grid = _order_cells(cells, dimensions)
+    widest = cell_grid_for(box, r, dimensions)
+    for a in range(3):
+        if grid[a] > widest[a]:
+            raise ValueError("cells %r are narrower than the range %r on axis %d (at most %d cells)"
+                             % (tuple(cells), r, a, widest[a]))
+    if grid[0] * grid[1] * grid[2] > _CELLS_MAX_CELLS:
+        raise ValueError("a grid holds at most 2^20 cells: %r" % (tuple(cells),))
+    return grid
+
+
+def neighbour_edges2(r, bins):
+    """The ``bins + 1`` squared bin edges of `particle_neighbours`' ``pair_hist``, float64: ``(k * (r / bins))**2`` for
+    ``k < bins`` and ``r*r`` for ``k == bins``.  Host arithmetic: the GPU receives these and never recomputes them."""
+    r = _neighbour_range(r)
+    bins = int(bins)
+    if not 1 <= bins <= _NEIGHBOURS_MAX_BINS:
+        raise ValueError("bins is 0 (no pair histogram) or 1 to %d: %r" % (_NEIGHBOURS_MAX_BINS, bins))
+    w = numpy.float64(r) / numpy.float64(bins)
+    e = numpy.arange(bins + 1, dtype=numpy.float64) * w
+    e = e * e
+    e[bins] = numpy.float64(r) * numpy.float64(r)
+    return e
+
+
+class Neighbours(object):
+    """The neighbour census of a list in cell order (`particle_neighbours`).
+
+    Attributes:
+        r (float), bins (int), grid (``(cx, cy, cz)``), dimensions (int): what was asked.
+        rows, cell: the list in cell order and its cell ids (``n_cells``: nowhere).
+        count (uint32), nearest2 (float64), nearest (uint32): per entry, in list order, the neighbours, the smallest
+            squared distance among them (``+inf`` without one) and the smallest list position that attains it
+            (``0xFFFFFFFF`` without one).  The five per-entry arrays are numpy arrays from the model; from the GPU they
+            are ``None`` unless ``return_rows`` left them in GPU memory.
+        n, nowhere (int): the entries, and those without a cell.
+        pairs (int): the sum of ``count``: ORDERED pairs (at an exact half-box tie in a tilted box ``i -> j`` and
+            ``j -> i`` may differ, so it need not be even).
+        count_hist (uint64, 257): bin ``k < 256``: the entries that have a cell and ``k`` neighbours; bin 256: 256 or more.
+        count_min, count_max (int): over the entries that have a cell (0 where there is none).
+        closest2 (float): the smallest ``nearest2``; closest (int): the smallest list position that attains it
+            (``0xFFFFFFFF``: no pair); closest_rows: that entry's row and its nearest's row (``None``: no pair).
+        pair_hist (uint64, bins) or ``None``; edges2 (float64, bins + 1) or ``None``: `neighbour_edges2`.
+        mean_count, isolated, closest_distance (properties); `rdf`.
+    """
+
+    __slots__ = ('r', 'bins', 'grid', 'dimensions', 'rows', 'cell', 'count', 'nearest2', 'nearest', 'n', 'nowhere', 'pairs',
+                 'count_hist', 'count_min', 'count_max', 'closest2', 'closest', 'closest_rows', 'pair_hist', 'edges2')
+
+    def __init__(self, r, bins, grid, dimensions, summary, closest2, rows=None, cell=None, count=None, nearest2=None,
+                 nearest=None):
+        """``summary``: the uint64 words of `pgsd_neighbours_device` -- n, nowhere, pairs, count_min, count_max, closest,
+        the closest pair's two rows, the 257 words of ``count_hist``, then ``bins`` words of ``pair_hist``."""
+        s = numpy.asarray(summary, dtype=numpy.uint64).reshape(-1)
+        self.r, self.bins, self.dimensions = float(r), int(bins), int(dimensions)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        if s.shape[0] != _NEIGHBOURS_SUMMARY_WORDS + _NEIGHBOURS_COUNT_BINS + self.bins:
+            raise ValueError("the summary holds %d words" % (_NEIGHBOURS_SUMMARY_WORDS + _NEIGHBOURS_COUNT_BINS + self.bins))
+        self.n, self.nowhere, self.pairs, self.count_min, self.count_max, self.closest = (int(v) for v in s[:6])
+        self.closest_rows = None if self.closest == _NEIGHBOURS_NONE else (int(s[6]), int(s[7]))
+        self.count_hist = s[_NEIGHBOURS_SUMMARY_WORDS:_NEIGHBOURS_SUMMARY_WORDS + _NEIGHBOURS_COUNT_BINS].copy()
+        self.pair_hist = s[_NEIGHBOURS_SUMMARY_WORDS + _NEIGHBOURS_COUNT_BINS:].copy() if self.bins else None
+        self.edges2 = neighbour_edges2(self.r, self.bins) if self.bins else None
+        self.closest2 = float(closest2)
+        self.rows, self.cell, self.count, self.nearest2, self.nearest = rows, cell, count, nearest2, nearest
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        rows = (_NEIGHBOURS_NONE, _NEIGHBOURS_NONE) if self.closest_rows is None else self.closest_rows
+        head = numpy.array([self.n, self.nowhere, self.pairs, self.count_min, self.count_max, self.closest, rows[0], rows[1]],
+                           dtype=numpy.uint64)
+        return numpy.concatenate([head, self.count_hist] + ([self.pair_hist] if self.bins else []))
+
+    @property
+    def mean_count(self):
+        """Neighbours per entry that has a cell (NaN where there is none)."""
+        somewhere = self.n - self.nowhere
+        return self.pairs / somewhere if somewhere else float('nan')
+
+    @property
+    def isolated(self):
+        """The entries that have a cell and no neighbour."""
+        return int(self.count_hist[0])
+
+    @property
+    def closest_distance(self):
+        return float(numpy.sqrt(self.closest2))
+
+    def rdf(self, volume):
+        """``(r_mid, g)``: the radial distribution function from ``pair_hist`` -- per bin the ordered pairs over what an
+        ideal gas of the same density ``(n - nowhere) / volume`` gives, ``(n - nowhere) * density * shell``, with the
+        shell volumes between the edges, ``4/3 pi (r_k+1^3 - r_k^3)`` (``pi (r_k+1^2 - r_k^2)`` and an area for
+        ``dimensions == 2``).  Host arithmetic on the counts: not part of what the GPU equals exactly."""
+        if not self.bins:
+            raise ValueError("rdf needs the pair histogram (bins >= 1)")
+        edges = numpy.sqrt(self.edges2)
+        if self.dimensions == 2:
+            shell = numpy.pi * (edges[1:] ** 2 - edges[:-1] ** 2)
+        else:
+            shell = 4.0 / 3.0 * numpy.pi * (edges[1:] ** 3 - edges[:-1] ** 3)
+        somewhere = self.n - self.nowhere
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            g = self.pair_hist.astype(numpy.float64) / (somewhere * (somewhere / float(volume)) * shell)
+        return 0.5 * (edges[1:] + edges[:-1]), g
+
+    def __repr__(self):
+        return "Neighbours(r=%r, grid=%r, n=%d, nowhere=%d, pairs=%d, count=[%d, %d], closest2=%r)" % (
+            self.r, self.grid, self.n, self.nowhere, self.pairs, self.count_min, self.count_max, self.closest2)
+
+
+def _axis_offsets(c):
+    """The cell offsets of one axis of `particle_neighbours`: -1 and +1 are the same cell at two cells."""
+    return (0,) if c == 1 else (0, 1) if c == 2 else (-1, 0, 1)
+
+
+def particle_neighbours(position, box, r, rows=None, cells=None, dimensions=3, bins=0):
+    """The neighbour census of a row list inside the range ``r``: per entry the number of neighbours and the nearest one,
+    and over the list the count histogram, the closest pair and -- with ``bins`` -- the pair histogram g(r) is made
+    from.  The definition the GPU pair pass (`pgsd.fl.PGSDFile.neighbours_device`,
+    `HOOMDTrajectory.frame_neighbours_device`) equals exactly: every result is an integer count or a minimum, so none
+    depends on the order of traversal, and the arithmetic of one pair is `pair_distance2`.
+
+    Args:
+        position: ``N x 3`` float32 or float64.
+        box: ``(Lx, Ly, Lz, xy, xz, yz)``.
+        r (float): the range, finite and positive.
+        rows: the list (any order, repeats allowed; ``None``: every row).  It is put into cell order by `cell_order`;
+            everything per entry is in that order, and both ``i`` and ``j`` come from it.
+        cells: ``(cx, cy, cz)`` or ``None``: `neighbour_grid_for`.
+        dimensions: 2 never looks at z.
+        bins: 0, or 1 to 1024 bins of ``pair_hist`` over `neighbour_edges2`; a neighbour pair's bin is
+            ``numpy.searchsorted(edges2, d2, side='right') - 1``.
+
+    **Candidates.**  Entry ``j`` is a candidate of entry ``i`` when ``j != i`` as a list position (the same row listed
+    twice is two entries at distance 0), both have a cell (an id below ``n_cells``) and ``j``'s cell is periodically
+    adjacent to ``i``'s: per axis the offsets ``{0}`` at one cell, ``{0, +1}`` at two (-1 and +1 are the same cell and
+    must not count twice) and ``{-1, 0, +1}`` otherwise, indices wrapping modulo the count.  ``j`` is a neighbour when
+    ``pair_distance2(x_i, x_j) < r*r``, strictly, ``r*r`` formed once in float64.  This is what a cell list evaluates;
+    it equals a search over all pairs except where the rounding of a wrapped fraction puts a pair at distance ``r``
+    minus a few ulp into cells two apart.
+
+    ValueError: ``r`` not finite or not positive; ``r`` above half the nearest plane distance of an axis that takes part
+    (`ghost_fractions` ``> 0.5``: an image would count twice); ``cells`` with a count above `cell_grid_for` ``(box, r)``'s
+    (narrower than ``r``) or more than 2^20 cells; ``bins`` outside 0 to 1024; what `cell_order` refuses.
+
+    Returns a `Neighbours`.
+    """
+    dimensions = int(dimensions)
+    grid = _neighbour_grid(box, r, cells, dimensions)
+    r = float(r)
+    bins = int(bins)
+    if bins:
+        edges2 = neighbour_edges2(r, bins)
+    p = numpy.asarray(position)
+    p = p.reshape(-1, 3) if p.size else numpy.zeros((0, 3), dtype=numpy.float32)
+    if p.dtype not in (numpy.float32, numpy.float64):
+        raise ValueError("position holds float32 or float64 values")
+    rows = numpy.arange(p.shape[0], dtype=numpy.int64) if rows is None else rows
+    rows_sorted, cell_sorted, _ = cell_order(p, box, rows, grid, dimensions)
+    n = rows_sorted.shape[0]
+    cx, cy, cz = grid
+    n_cells = cx * cy * cz
+    vectors = box_vectors(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+    r2 = numpy.float64(r) * numpy.float64(r)
+    offs = cell_offsets(cell_sorted, n_cells)
+    xs = p[rows_sorted].astype(numpy.float64)
+    count = numpy.zeros(n, dtype=numpy.uint32)
+    nearest2 = numpy.full(n, numpy.inf, dtype=numpy.float64)
+    nearest = numpy.full(n, _NEIGHBOURS_NONE, dtype=numpy.int64)
+    pair_hist = numpy.zeros(bins, dtype=numpy.uint64)
+    somewhere = int(offs[n_cells])                       # the entries that have a cell come first
+    ids = cell_sorted[:somewhere]
+    ix, iy, iz = ids % cx, (ids // cx) % cy, ids // (cx * cy)
+    for oz in _axis_offsets(cz):
+        for oy in _axis_offsets(cy):
+            for ox in _axis_offsets(cx):
+                other = ((ix + ox) % cx) + cx * (((iy + oy) % cy) + cy * ((iz + oz) % cz))
+                first, length = offs[other], offs[other + 1] - offs[other]
+                ends = numpy.cumsum(length)
+                lo = 0
+                while lo < somewhere:                   # entries [lo, hi): at most _NEIGHBOURS_PAIRS_PER_STEP candidates
+                    base = int(ends[lo - 1]) if lo else 0
+                    hi = max(int(numpy.searchsorted(ends, base + _NEIGHBOURS_PAIRS_PER_STEP, side='right')), lo + 1)
+                    hi = min(hi, somewhere)
+                    ln = length[lo:hi]
+                    total = int(ln.sum())
+                    if total:
+                        i = numpy.repeat(numpy.arange(lo, hi, dtype=numpy.int64), ln)
+                        start = numpy.cumsum(ln) - ln
+                        j = numpy.repeat(first[lo:hi] - start, ln) + numpy.arange(total, dtype=numpy.int64)
+                        d2 = pair_distance2(xs[i], xs[j], vectors, dimensions)
+                        near = (d2 < r2) & (i != j)
+                        count += numpy.bincount(i[near], minlength=n).astype(numpy.uint32)
+                        if bins:
+                            pair_hist += numpy.bincount(numpy.searchsorted(edges2, d2[near], side='right') - 1,
+                                                        minlength=bins).astype(numpy.uint64)
+                        has = ln > 0                    # (reduceat over the non-empty segments: i ascends)
+                        seg = start[has]
+                        who = numpy.arange(lo, hi, dtype=numpy.int64)[has]
+                        best2 = numpy.minimum.reduceat(numpy.where(near, d2, numpy.inf), seg)
+                        at = numpy.minimum.reduceat(numpy.where(near & (d2 == numpy.repeat(best2, ln[has])), j,
+                                                                _NEIGHBOURS_NONE), seg)
+                        better = (best2 < nearest2[who]) | ((best2 == nearest2[who]) & (at < nearest[who]))
+                        nearest2[who[better]] = best2[better]
+                        nearest[who[better]] = at[better]
+                    lo = hi
+    nearest = nearest.astype(numpy.uint32)
+    summary = numpy.zeros(_NEIGHBOURS_SUMMARY_WORDS + _NEIGHBOURS_COUNT_BINS + bins, dtype=numpy.uint64)
+    summary[0], summary[1], summary[2] = n, n - somewhere, int(count.astype(numpy.uint64).sum())
+    summary[5] = summary[6] = summary[7] = _NEIGHBOURS_NONE
+    closest2 = numpy.inf
+    if somewhere:
+        summary[3], summary[4] = count[:somewhere].min(), count[:somewhere].max()
+        summary[8:8 + _NEIGHBOURS_COUNT_BINS] = numpy.bincount(numpy.minimum(count[:somewhere], 256),
+                                                               minlength=_NEIGHBOURS_COUNT_BINS)
+        k = int(numpy.argmin(nearest2))                 # (the first position that attains the minimum)
+        if nearest[k] != _NEIGHBOURS_NONE:
+            closest2 = nearest2[k]
+            summary[5], summary[6], summary[7] = k, rows_sorted[k], rows_sorted[nearest[k]]
+    summary[8 + _NEIGHBOURS_COUNT_BINS:] = pair_hist
+    return Neighbours(r, bins, grid, dimensions, summary, closest2, rows_sorted, cell_sorted, count, nearest2, nearest)
+
+
+def frame_neighbours(frame_or_arrays, r, bins=0, cells=None, where=None, types=None, domain=None, box=None, dimensions=3):
+    """`particle_neighbours` of a frame's ``position`` over a selection: the host twin of
+    `HOOMDTrajectory.frame_neighbours_device`, which equals it exactly.  The selection -- `where_rows`, `domain_rows` or
+    their intersection, as `frame_moments` forms it -- is the list: both ``i`` and ``j`` come from it.  A position that
+    is stored nowhere puts every row at the origin.  Returns a `Neighbours`."""
+    if hasattr(frame_or_arrays, 'particles'):
+        frame = frame_or_arrays
+        arrays = _particle_arrays(frame.particles)
+        types = frame.particles.types if types is None else types
+        box = frame.configuration.box if box is None else box
+        if frame.configuration.dimensions is not None:
+            dimensions = int(frame.configuration.dimensions)
+        N = int(frame.particles.N)
+    else:
+        arrays = dict((k, v) for k, v in frame_or_arrays.items() if v is not None)
+        if not arrays:
+            raise ValueError("arrays holds no per-particle array")
+        N = len(next(iter(arrays.values())))
+    if box is None:
+        raise ValueError("a neighbour search needs the box")
+    rows = None
+    if where is not None:
+        rows = where_rows(arrays, where, types)
+    if domain is not None:
+        if 'position' not in arrays:
+            raise ValueError("a domain needs box and the 'position' array")
+        inside = domain_rows(arrays['position'], box, domain, dimensions)
+        rows = inside if rows is None else numpy.intersect1d(rows, inside)
+    position = arrays.get('position')
+    if position is None:
+        position = numpy.zeros((N, 3), dtype=numpy.float32)
+    return particle_neighbours(position, box, r, rows=rows, cells=cells, dimensions=dimensions, bins=bins)
+
+
 def frame_moments(frame_or_arrays, by_type=True, centre=True, where=None, types=None, domain=None, box=None, dimensions=3):
     """`particle_moments` of a frame's ``mass``, ``velocity``, ``energy``, ``position`` and ``typeid`` over a selection:
     the host twin of `HOOMDTrajectory.frame_moments_device`, which equals it exactly.
@@ -3377,6 +3716,42 @@ class HOOMDTrajectory(object):
         b = numpy.asarray(box, dtype=numpy.float64).reshape(-1)
         got.grid = grid
         got.cell_volume = (b[0] * b[1] * (b[2] if dims == 3 else 1.0)) / n_cells
+        return got
+
+    def frame_neighbours(self, idx, r, bins=0, cells=None, where=None, domain=None):
+        """`frame_neighbours` of frame ``idx`` read through the host path: a `Neighbours`.  The definition of
+        `frame_neighbours_device`."""
+        return frame_neighbours(self[int(idx)], r, bins=bins, cells=cells, where=where, domain=domain)
+
+    def frame_neighbours_device(self, idx, r, bins=0, cells=None, where=None, domain=None, return_rows=False):
+        """`frame_neighbours` of frame ``idx``, on the GPU: a `Neighbours` whose summary equals
+        ``frame_neighbours(idx, r, ...)`` exactly -- every counter and index, ``closest2`` bit for bit.
+
+        The selection is `frame_moments_device`'s and is the list both ``i`` and ``j`` come from; without one it is
+        every row.  The list is sorted by cell over the staged position chunk
+        (`pgsd.fl.PGSDFile.order_rows_by_cell_device`) with the grid `neighbour_grid_for` gives (or ``cells``, checked
+        like the model's), and the pair pass (`pgsd.fl.PGSDFile.neighbours_device`) runs over the same staged chunk.
+        ``return_rows=True`` leaves ``rows``, ``cell``, ``count``, ``nearest2`` and ``nearest`` in GPU memory on the
+        result; otherwise they are ``None`` and no per-particle data is kept.  One `wait_read` at the end releases the
+        staged chunk.  A frame whose position is stored nowhere has no chunk to search and raises ValueError.
+        """
+        idx = self._frame_index(idx)
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        grid = _neighbour_grid(box, r, cells, dims)
+        if int(bins):
+            neighbour_edges2(r, bins)
+        if f_pos is None:
+            raise ValueError("frame_neighbours_device: the position is stored nowhere (every particle sits at the origin)")
+        try:
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
+            if rows is None:
+                rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
+            cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
+            got = f.neighbours_device(f_pos, 'particles/position', box, r, grid, rows, cell, n=count, dimensions=dims,
+                                      bins=bins, return_rows=return_rows)
+        finally:
+            f.wait_read()
         return got
 
     def _types_of(self, idx):

@@ -239,6 +239,10 @@ cdef extern from "pgsd_private.h" nogil:
                                  const pgsd_index_entry* energy, const pgsd_index_entry* position, const double* defaults,
                                  const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t n_cells,
                                  uint64_t* out_counts, double* out_sums)
+    int pgsd_neighbours_device(pgsd_handle* handle, const pgsd_index_entry* position, const double* vectors, double r,
+                               uint32_t dimensions, const uint32_t* cells, const uint32_t* rows, const int32_t* cell,
+                               uint64_t n, uint32_t bins, const double* edges2, uint32_t* out_count, double* out_nearest2,
+                               uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2)
     int pgsd_chunk_stats_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                                 uint32_t with_norm2, uint64_t* out_counts, double* out_values)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,

@@ -1,0 +1,139 @@
+// tools/labs/pair_ceiling.hip -- the arithmetic ceiling the neighbour census' pair kernel is judged against (DESIGN
+// section 8, "Neighbour census").
+//
+// The per-candidate work of neighbours_pair_kernel on register values alone, with no memory traffic inside the loop:
+// three float64 differences, the single-shift minimum image z, y, x as compares and selects, (dx*dx + dy*dy) + dz*dz
+// without contraction, the strict compare against r*r, the count and the (d2, position) minimum.  The candidate is
+// formed in registers: three float64 additions stand where the kernel converts three loaded elements, and nothing else
+// is added.  Every lane runs ITER candidates; 256 lanes per workgroup and enough workgroups to fill the device eight
+// waves deep.  Prints one JSON line: candidate pairs per second from the dispatch's own begin / end stamps, best and
+// median of the repetitions.
+//
+//   hipcc -O3 --offload-arch=gfx950 tools/labs/pair_ceiling.hip -o pair_ceiling
+//   ./pair_ceiling [reps=20] [iter=4096]
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#define CK(x)                                                                                 \
+    do                                                                                        \
+        {                                                                                     \
+        hipError_t e_ = (x);                                                                  \
+        if (e_ != hipSuccess)                                                                 \
+            {                                                                                 \
+            fprintf(stderr, "%s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); \
+            exit(2);                                                                          \
+            }                                                                                 \
+        } while (0)
+
+struct Box
+    {
+    double v[6]; // Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz
+    double r2;
+    };
+
+__global__ __launch_bounds__(256) void pair_ceiling_kernel(const Box b, uint32_t iter, uint32_t* __restrict__ out_count,
+                                                           double* __restrict__ out_best2, uint32_t* __restrict__ out_best)
+    {
+#pragma clang fp contract(off)
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    const double Lx = b.v[0], Ly = b.v[1], Lz = b.v[2], xyLy = b.v[3], xzLz = b.v[4], yzLz = b.v[5];
+    const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5, r2 = b.r2;
+    // the lane's own position, and a candidate that walks away from it in steps that differ per lane and turns round every
+    // 512 candidates, so that the differences stay within a box length or two and every branch of the fold is taken
+    const double xi0 = -hx + (double)(k & 1023) * (Lx / 1024.0), xi1 = -hy + (double)((k >> 10) & 1023) * (Ly / 1024.0);
+    const double xi2 = -hz + (double)(k >> 20) * (Lz / 4096.0);
+    double s0 = Lx / 977.0 + (double)(k & 63) * 1e-3, s1 = -Ly / 1931.0, s2 = Lz / 2953.0;
+    double xj0 = xi0, xj1 = xi1, xj2 = xi2;
+    uint32_t count = 0, best = 0xFFFFFFFFu;
+    double best2 = __builtin_huge_val();
+    for (uint32_t j = 0; j < iter; j++)
+        {
+        if ((j & 511) == 511) // (wave-uniform, once per 512 candidates)
+            {
+            s0 = -s0;
+            s1 = -s1;
+            s2 = -s2;
+            }
+        xj0 = xj0 + s0;
+        xj1 = xj1 + s1;
+        xj2 = xj2 + s2;
+        double dx = xj0 - xi0, dy = xj1 - xi1, dz = xj2 - xi2;
+            {
+            const bool up = dz >= hz, down = dz < -hz;
+            dx = up ? dx - xzLz : (down ? dx + xzLz : dx);
+            dy = up ? dy - yzLz : (down ? dy + yzLz : dy);
+            dz = up ? dz - Lz : (down ? dz + Lz : dz);
+            }
+            {
+            const bool up = dy >= hy, down = dy < -hy;
+            dx = up ? dx - xyLy : (down ? dx + xyLy : dx);
+            dy = up ? dy - Ly : (down ? dy + Ly : dy);
+            }
+            {
+            const bool up = dx >= hx, down = dx < -hx;
+            dx = up ? dx - Lx : (down ? dx + Lx : dx);
+            }
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        const bool near = d2 < r2 && j != k;
+        count += near ? 1u : 0u;
+        if (near && (d2 < best2 || (d2 == best2 && j < best)))
+            {
+            best2 = d2;
+            best = j;
+            }
+        }
+    out_count[k] = count;
+    out_best2[k] = best2;
+    out_best[k] = best;
+    }
+
+int main(int argc, char** argv)
+    {
+    const int reps = argc > 1 ? atoi(argv[1]) : 20;
+    const uint32_t iter = argc > 2 ? (uint32_t)atoi(argv[2]) : 4096u;
+    int cus = 256;
+    CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+    const uint32_t blocks = (uint32_t)cus * 8u; // 32 waves per compute unit: eight per SIMD
+    const size_t lanes = (size_t)blocks * 256;
+    uint32_t *count, *best;
+    double* best2;
+    CK(hipMalloc(&count, lanes * sizeof(uint32_t)));
+    CK(hipMalloc(&best, lanes * sizeof(uint32_t)));
+    CK(hipMalloc(&best2, lanes * sizeof(double)));
+    const Box b = {{40.0, 40.0, 40.0, 0.25 * 40.0, 0.125 * 40.0, -0.0625 * 40.0}, 0.197 * 0.197};
+    hipEvent_t t0, t1;
+    CK(hipEventCreate(&t0));
+    CK(hipEventCreate(&t1));
+    std::vector<double> ms;
+    for (int r = 0; r < reps + 2; r++)
+        {
+        hipExtLaunchKernelGGL(pair_ceiling_kernel, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, iter, count, best2, best);
+        CK(hipGetLastError());
+        CK(hipEventSynchronize(t1));
+        float t = 0;
+        CK(hipEventElapsedTime(&t, t0, t1));
+        if (r >= 2) // (two warm-up launches)
+            ms.push_back(t);
+        }
+    std::vector<uint32_t> h(lanes);
+    CK(hipMemcpy(h.data(), count, lanes * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint64_t near = 0;
+    for (uint32_t c : h)
+        near += c;
+    std::sort(ms.begin(), ms.end());
+    const double pairs = (double)lanes * iter;
+    printf("{\"kind\": \"pair_ceiling\", \"lanes\": %zu, \"iter\": %u, \"pairs\": %.0f, \"near\": %llu, \"best_ms\": %.4f, "
+           "\"median_ms\": %.4f, \"pairs_per_s_best\": %.4g, \"pairs_per_s_median\": %.4g}\n",
+           lanes, iter, pairs, (unsigned long long)near, ms.front(), ms[ms.size() / 2], pairs / (ms.front() * 1e-3),
+           pairs / (ms[ms.size() / 2] * 1e-3));
+    CK(hipFree(count));
+    CK(hipFree(best));
+    CK(hipFree(best2));
+    return 0;
+    }
