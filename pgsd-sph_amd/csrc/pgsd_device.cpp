@@ -211,6 +211,7 @@ int DevicePipeline::init()
         warm_order_kernels();
         warm_cells_kernels();
         warm_neighbours_kernels();
+        warm_sph_kernels();
         int brc = compare_buffers();
         if (brc != PGSD_SUCCESS)
             return brc;
@@ -763,6 +764,16 @@ int device_pipeline_neighbours(DevicePipeline* p, long long file_offset, size_t 
     std::string local;
     int rc = report(p, p->neighbours(file_offset, bytes, a, edges2, out_count, out_nearest2, out_nearest, out_summary,
                                      out_closest2, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
+int device_pipeline_sph_sums(DevicePipeline* p, const ChunkRange* ranges, const SphArgs& a, double* out_number,
+                             double* out_density, double* out_shepard, uint64_t* out_summary, std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->sph_sums(ranges, a, out_number, out_density, out_shepard, out_summary, &local), err, true);
     if (rc != PGSD_SUCCESS && err && !local.empty())
         *err = local; // the launcher's own message comes first
     return rc;

@@ -156,6 +156,8 @@ class DevicePipeline
     int cell_moments(const ChunkRange* ranges, CellMomentsArgs c, uint64_t* out_counts, double* out_sums, std::string* why);
     int neighbours(long long file_offset, size_t bytes, NeighboursArgs a, const double* edges2, uint32_t* out_count,
                    double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2, std::string* why);
+    int sph_sums(const ChunkRange* ranges, SphArgs a, double* out_number, double* out_density, double* out_shepard,
+                 uint64_t* out_summary, std::string* why);
     int wait_read();
 
     // ---- accessors ----

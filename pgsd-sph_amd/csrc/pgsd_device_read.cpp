@@ -597,6 +597,27 @@ int DevicePipeline::neighbours(long long file_offset, size_t bytes, NeighboursAr
                                                     m_res.pack_stream, err); });
     }
 
+// SPH kernel sums: the position chunk the ordering left staged (or staged here) and the mass and density chunks that are
+// present; the lists and the per-entry outputs are the caller's.
+int DevicePipeline::sph_sums(const ChunkRange* ranges, SphArgs a, double* out_number, double* out_density, double* out_shepard,
+                             uint64_t* out_summary, std::string* why)
+    {
+    const bool given[3] = {true, (a.present & 2u) != 0, (a.present & 4u) != 0};
+    a.mass = a.density = nullptr;
+    const void** const all[3] = {&a.pos, &a.mass, &a.density};
+    ChunkRange stored[3];
+    const void** slots[3];
+    size_t n_stored = 0;
+    for (int i = 0; i < 3; i++)
+        if (given[i])
+            {
+            stored[n_stored] = ranges[i];
+            slots[n_stored++] = all[i];
+            }
+    return staged_launch(stored, slots, n_stored, a.N, true, why, [&](std::string* err)
+                         { return launch_sph_sums(a, out_number, out_density, out_shepard, out_summary, m_res.pack_stream, err); });
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

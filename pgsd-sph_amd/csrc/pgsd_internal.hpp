@@ -7,6 +7,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <sched.h>
 #include <sys/uio.h>
 #include <functional>
@@ -465,6 +466,55 @@ inline void neighbours_of_nothing(uint32_t bins, uint64_t* out_summary, double* 
 int device_pipeline_neighbours(DevicePipeline*, long long file_offset, size_t bytes, const NeighboursArgs& a,
                                const double* edges2, uint32_t* out_count, double* out_nearest2, uint32_t* out_nearest,
                                uint64_t* out_summary, double* out_closest2, std::string* err);
+// SPH kernel sums (pgsd.hoomd.sph_kernel_sums is the definition): per entry of a row list in cell order the sums
+// sigma * sum w, sigma * sum m_j w and sigma * sum (m_j / rho_j) w over the entries inside the support 2h, in the defined
+// order, and over the list their ranges, the largest deviation from the stored density and the entries below a threshold.
+enum
+    {
+    SPH_WENDLAND_C2 = 0,
+    SPH_CUBIC_SPLINE = 1,
+    SPH_SUMMARY_WORDS = 13, // n, nowhere, not_finite, surface, deviation_at, deviation_row, 3 x (min, max), deviation
+    SPH_NONE = 0xFFFFFFFFu
+    };
+struct SphArgs
+    {
+    const void* pos;      // the staged position chunk
+    const void* mass;     // the staged mass and density chunks, or null: the default stands for every row
+    const void* density;
+    uint64_t N;           // their rows
+    const uint32_t* rows; // device, n entries in cell order
+    const int32_t* cell;  // device, n ids, non-decreasing, in [0, n_cells]; n_cells: nowhere
+    uint64_t n;
+    double vectors[6];    // Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz
+    double r2, inv_h, sigma; // (2h)*(2h), 1/h and the normalisation, formed once on the host
+    double mass_default, density_default;
+    double surface_below;
+    uint32_t cells[3];
+    uint32_t n_cells;
+    uint32_t dims, f64, mass_f64, density_f64; // f64: the position chunk's elements
+    uint32_t kernel, volume, surface;          // volume: the third sum, the deviation and the surface count are formed
+    uint32_t present;                          // bit 1: a mass chunk, bit 2: a density chunk is stored (ranges[1], ranges[2])
+    };
+// the summary of no entry
+inline void sph_sums_of_nothing(uint64_t* out_summary)
+    {
+    const double lo = HUGE_VAL, hi = -HUGE_VAL, zero = 0.0;
+    std::fill(out_summary, out_summary + SPH_SUMMARY_WORDS, (uint64_t)0);
+    out_summary[4] = out_summary[5] = SPH_NONE;
+    for (int s = 0; s < 3; s++)
+        {
+        memcpy(&out_summary[6 + 2 * s], &lo, sizeof(double));
+        memcpy(&out_summary[7 + 2 * s], &hi, sizeof(double));
+        }
+    memcpy(&out_summary[12], &zero, sizeof(double));
+    }
+// stage the chunks that are present (ranges[0 .. 2]: position, mass, density; a.pos, a.mass and a.density are filled in)
+// -- or take them from what an earlier call left staged --, check the lists, sum on the GPU; out_number, out_density,
+// out_shepard (device, a.n entries each, or null; the last is written with a.volume only); out_summary (host, 13 words)
+// is written on success only, and so are the device outputs; synchronous.  An entry >= a.N, an id outside [0, n_cells]
+// and a descending id refuse the call.  The staged rows stay until the next wait_read.
+int device_pipeline_sph_sums(DevicePipeline*, const ChunkRange* ranges, const SphArgs& a, double* out_number,
+                             double* out_density, double* out_shepard, uint64_t* out_summary, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

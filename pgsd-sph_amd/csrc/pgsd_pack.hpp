@@ -303,6 +303,14 @@ int launch_cell_moments(const CellMomentsArgs& c, uint64_t* out_counts, double* 
 int launch_neighbours(const NeighboursArgs& a, const double* edges2, uint32_t* out_count, double* out_nearest2,
                       uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2, hipStream_t stream, std::string* err);
 
+// SPH kernel sums (pgsd_sph.hip; SphArgs, a.pos, a.mass and a.density filled in): check, offsets, compaction of the listed
+// positions, masses and volumes, one lane per entry over the runs of the adjacent cells in the defined order, one
+// workgroup for the ranges and the deviation.  out_number, out_density, out_shepard (device, a.n entries each, or null);
+// out_summary (host, 13 words) is written on success only.  Synchronises `stream`; PGSD_ERROR_INVALID_ARGUMENT for an id
+// that descends or lies outside [0, n_cells] and for an entry >= a.N
+int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, double* out_shepard, uint64_t* out_summary,
+                    hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);
@@ -362,6 +370,7 @@ void warm_census_kernels();
 void warm_order_kernels();
 void warm_cells_kernels();
 void warm_neighbours_kernels();
+void warm_sph_kernels();
 
 // algorithmic traffic of one job: bytes that must be read (needed columns only, plus the
 // gather index) and chunk bytes written

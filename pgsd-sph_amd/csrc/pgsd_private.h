@@ -44,6 +44,10 @@
  *                     pgsd_neighbours_device (pgsd.fl's neighbours_device, behind pgsd.hoomd's frame_neighbours_device:
  *                     per entry of a row list in cell order the neighbours inside a range and the nearest of them, and
  *                     over the list the count histogram, the closest pair and the pair histogram of g(r))
+ *                     pgsd_sph_sums_device (pgsd.fl's sph_sums_device, behind pgsd.hoomd's frame_kernel_sums_device: per
+ *                     entry of a row list in cell order the SPH summation density, number density and Shepard sum over
+ *                     the kernel support, in a defined order, and over the list their ranges, the largest deviation from
+ *                     the stored density and the entries below a Shepard threshold)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -377,6 +381,54 @@ extern "C"
                                double r, uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
                                const int32_t* cell, uint64_t n, uint32_t bins, const double* edges2, uint32_t* out_count,
                                double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2);
+
+    /* SPH kernel sums (pgsd.hoomd.sph_kernel_sums is the definition, and the results equal it exactly: every counter and
+       index, every float bit for bit -- a NaN is a NaN, its sign and payload are the processor's).  position: an N x 3
+       float32 or float64 chunk; mass, density: N x 1 float32 or float64 chunks, each of its own element type, either may
+       be NULL: defaults[0] then stands for every mass and defaults[1] for every density, and with density == NULL and
+       defaults[1] a NaN there is NO VOLUME: no third sum, no deviation, no surface count.  vectors, dimensions, cells,
+       rows, cell and n are pgsd_neighbours_device's; the range of the search is the support 2h, so the cells are no
+       narrower than 2h.  kernel: 0 Wendland C2, 1 cubic spline.
+       On the host, once, in float64: r2 = (2h)*(2h), inv_h = 1/h and sigma = 21/(16 pi h^3) (3-D) or 7/(4 pi h^2) (2-D)
+       for Wendland C2, 1/(pi h^3) or 10/(7 pi h^2) for the cubic spline; the GPU receives them and never recomputes them.
+       ONE PAIR i <- j, float64 from the stored values, no contraction: d2 as pgsd_neighbours_device forms it; j
+       contributes when d2 < r2, strictly; i itself contributes (list position j == i: d2 = 0, w = 1) and the same row
+       listed twice is two entries; rr = sqrt(d2), q = rr * inv_h;
+           Wendland C2    t = 1.0 - 0.5*q, t2 = t*t, w = (t2*t2) * (2.0*q + 1.0)
+           cubic spline   q2 = q*q; if q < 1.0: w = (1.0 - 1.5*q2) + 0.75*(q2*q), else u = 2.0 - q, w = 0.25*((u*u)*u)
+       Three accumulators per entry start at +0.0: a_n += w, a_m += m_j * w, a_v += V_j * w with V_j = m_j / rho_j, one
+       float64 division of the stored values taken as it is (rho_j == 0 gives what IEEE gives).
+       THE ORDER of the candidates is part of the definition: the cells with oz over the offsets of the z axis ({0} at one
+       cell, {0, +1} at two, {-1, 0, +1} otherwise, in that order), inside it oy, inside it ox, the cell ((ix+ox) % cx,
+       (iy+oy) % cy, (iz+oz) % cz); inside a cell ascending list position.  After the last candidate number = sigma*a_n,
+       density = sigma*a_m, shepard = sigma*a_v.  An entry with id n_cells is nowhere: it contributes to nobody and its
+       three values are +0.0.
+       Device outputs, n float64 entries each, each optional (NULL): out_number, out_density, out_shepard (the last is
+       not written where there is no volume).
+       Host output, 13 words:
+           out_summary[0 .. 3]    n; the entries nowhere; the entries that have a cell and whose density sum is NaN or
+                                  infinite; the entries that have a cell and shepard < surface_below, strictly (0 without
+                                  a volume or with surface_below a NaN: none asked for)
+           out_summary[4], [5]    the list position of the deviation and its row, 0xFFFFFFFF without one
+           out_summary[6 .. 11]   as float64 bit patterns the minimum and the maximum of number, of density and of shepard
+                                  over the entries that have a cell, kept by strict compares from +inf and -inf: a NaN
+                                  never replaces a value (shepard without a volume: +inf, -inf)
+           out_summary[12]        as a float64 bit pattern the deviation density_i - (double)rho_i of the largest
+                                  magnitude over the entries that have a cell, its sign kept, the smaller list position
+                                  on a tie, a NaN never; +0.0 without one
+       No float is summed over the list, so the summary depends on no order.  The chunks are staged whole unless an
+       earlier call (the ordering, a selection) left them staged, the pass runs on the handle's GPU and the call
+       synchronises; the staged rows are kept until the next pgsd_device_wait_read.  n == 0 succeeds with the summary of
+       no entry and launches nothing.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), every output as it was: everything
+       pgsd_neighbours_device refuses for the range 2h; a mass or density chunk that is not one float32 or float64
+       column or has another N than position; h not finite or not positive; an unknown kernel. */
+    int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                             const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
+                             const double defaults[2], const double vectors[6], double h, uint32_t kernel,
+                             uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows, const int32_t* cell,
+                             uint64_t n, double surface_below, double* out_number, double* out_density,
+                             double* out_shepard, uint64_t* out_summary);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

@@ -1036,6 +1036,136 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                    const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
+                                    const double defaults[2], const double vectors[6], double h, uint32_t kernel,
+                                    uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows, const int32_t* cell,
+                                    uint64_t n, double surface_below, double* out_number, double* out_density,
+                                    double* out_shepard, uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_sph_sums_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !defaults || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const auto refuse = [](const std::string& msg)
+    {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    };
+    pgsd_index_entry c = *position; // a flush may move the index storage
+    if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
+        return refuse("the position chunk holds float32 or float64 elements");
+    if (c.M != 3)
+        return refuse("the position chunk has 3 columns");
+    if (c.N >= (1ull << 32))
+        return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+    if (n >= (1ull << 32))
+        return refuse("a list holds fewer than 2^32 entries");
+    if (dimensions != 2 && dimensions != 3)
+        return refuse("dimensions is 2 or 3");
+    if (!(h > 0.0 && h < HUGE_VAL))
+        return refuse("the smoothing length must be finite and positive");
+    if (kernel != SPH_WENDLAND_C2 && kernel != SPH_CUBIC_SPLINE)
+        return refuse("the kernel is 0 (Wendland C2) or 1 (cubic spline)");
+    ChunkRange ranges[3];
+    memset(ranges, 0, sizeof(ranges));
+    SphArgs a;
+    memset(&a, 0, sizeof(a));
+    const struct pgsd_index_entry* columns[2] = {mass, density};
+    for (int i = 0; i < 2; i++)
+        {
+        if (!columns[i])
+            continue;
+        const pgsd_index_entry m = *columns[i];
+        const std::string subject = i ? "the density chunk" : "the mass chunk";
+        if (m.type != PGSD_TYPE_FLOAT && m.type != PGSD_TYPE_DOUBLE)
+            return refuse(subject + " holds float32 or float64 elements");
+        if (m.M != 1)
+            return refuse(subject + " has 1 column");
+        if (m.N != c.N)
+            return refuse(subject + " and the position chunk differ in their number of rows");
+        int rc = whole_chunk_range(s, handle, m, &ranges[1 + i].file_offset, &ranges[1 + i].bytes);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        (i ? a.density_f64 : a.mass_f64) = m.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+        a.present |= 2u << i;
+        }
+    // the range of the search is the support 2h; the grid is checked as pgsd_neighbours_device checks its own:
+    // pgsd.hoomd.ghost_fractions and cell_grid_for, from the tilt factors the vectors hold
+    const double r = 2.0 * h;
+    if (!(r < HUGE_VAL))
+        return refuse("the smoothing length must be finite and positive");
+    const double Lx = vectors[0], Ly = vectors[1], Lz = vectors[2];
+    if (!(Lx > 0.0 && Ly > 0.0 && (dimensions == 2 || Lz > 0.0)))
+        return refuse("box lengths must be positive (Lz unless dimensions == 2)");
+    const double xy = vectors[3] / Ly, xz = Lz > 0.0 ? vectors[4] / Lz : 0.0, yz = Lz > 0.0 ? vectors[5] / Lz : 0.0;
+    const double t = xy * yz - xz;
+    const double u = 1.0 + xy * xy;
+    const double plane[3] = {Lx / std::sqrt(u + t * t), Ly / std::sqrt(1.0 + yz * yz), Lz};
+    uint64_t n_cells = 1;
+    for (int k = 0; k < 3; k++)
+        {
+        if (cells[k] < 1 || cells[k] > ORDER_MAX_AXIS_CELLS)
+            return refuse("every axis takes 1 to 1024 cells");
+        n_cells *= cells[k];
+        if (k == 2 && dimensions == 2)
+            {
+            if (cells[2] != 1)
+                return refuse("dimensions == 2 takes one z cell (z is not looked at)");
+            continue;
+            }
+        const double g = r / plane[k];
+        if (!(g <= 0.5))
+            return refuse("the support 2h exceeds half the box's nearest plane distance on an axis: an image would count twice");
+        const double most = std::min(std::max(std::floor(1.0 / g), 1.0), (double)ORDER_MAX_AXIS_CELLS);
+        if ((double)cells[k] > most)
+            return refuse("the cells are narrower than the support 2h on an axis");
+        }
+    if (n_cells > CELLS_MAX_CELLS)
+        return refuse("a grid holds 1 to 2^20 cells");
+    int rc = whole_chunk_range(s, handle, c, &ranges[0].file_offset, &ranges[0].bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    a.N = c.N;
+    a.rows = rows;
+    a.cell = cell;
+    a.n = n;
+    std::copy(vectors, vectors + 6, a.vectors);
+    // host arithmetic in float64, formed once: the GPU receives these and never recomputes them
+    const double pi = 3.141592653589793;
+    a.r2 = r * r;
+    a.inv_h = 1.0 / h;
+    if (dimensions == 3)
+        a.sigma = kernel == SPH_WENDLAND_C2 ? 21.0 / (16.0 * pi * (h * h * h)) : 1.0 / (pi * (h * h * h));
+    else
+        a.sigma = kernel == SPH_WENDLAND_C2 ? 7.0 / (4.0 * pi * (h * h)) : 10.0 / (7.0 * pi * (h * h));
+    a.mass_default = defaults[0];
+    a.density_default = defaults[1];
+    a.volume = density || defaults[1] == defaults[1] ? 1u : 0u;
+    a.surface = a.volume && surface_below == surface_below ? 1u : 0u;
+    a.surface_below = surface_below;
+    std::copy(cells, cells + 3, a.cells);
+    a.n_cells = (uint32_t)n_cells;
+    a.dims = dimensions;
+    a.f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    a.kernel = kernel;
+    if (n == 0)
+        {
+        sph_sums_of_nothing(out_summary);
+        return PGSD_SUCCESS;
+        }
+    if (c.N == 0)
+        return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "SPH kernel sums: ", [&](std::string* err)
+                          { return device_pipeline_sph_sums(s->dev, ranges, a, out_number, out_density, out_shepard, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position_a,
                                                const struct pgsd_index_entry* image_a,
                                                const struct pgsd_index_entry* position_b,

@@ -1,0 +1,479 @@
+// pgsd_sph.hip -- the SPH kernel sums on gfx950: per entry i of a row list in cell order the three weighted pair sums
+// sigma * sum_j W_ij, sigma * sum_j m_j W_ij and sigma * sum_j (m_j / rho_j) W_ij over the entries j of the periodically
+// adjacent cells that lie strictly inside the kernel support 2h (i itself among them), and over the list their ranges,
+// the largest deviation of the summation density from the stored one and the entries below a Shepard threshold.
+// pgsd.hoomd.sph_kernel_sums is the definition and this file equals it exactly, the floats bit for bit: a float sum
+// depends on its order, so the ORDER of the candidates is part of the definition -- oz over the offsets of the z axis
+// ({0} at one cell, {0, +1} at two, {-1, 0, +1} otherwise), inside it oy, inside it ox, the cell ((ix+ox) % cx, (iy+oy) %
+// cy, (iz+oz) % cz), inside a cell ascending list position -- and every lane adds in that order.  The arithmetic of one
+// pair is the census kernel's d2 (pgsd.hoomd.pair_distance2), then rr = sqrt(d2), q = rr * inv_h and the polynomial of
+// pgsd.hoomd.sph_weight, float64 without contraction; r2 = (2h)*(2h), inv_h = 1/h and sigma come from the host.
+//   cells_check_kernel, cells_offsets_kernel   pgsd_cells.hip's, unchanged (pgsd_cells.hpp): the refusal protocol and the
+//                          CSR offsets; every kernel here reads the device flag first and does nothing where it is set,
+//                          and clamps what it takes from the offsets to n
+//   sph_compact_kernel<F64>   lane per entry: xs[k] = position[rows[k]] in the chunk's own element type, m[k] the mass
+//                          and V[k] = m / rho (one float64 division of the stored values) as float64, so that the pair
+//                          loop reads runs instead of gathering
+//   sph_pair_kernel<F64, KERNEL, VOL>   lane per entry i: x_i and the three accumulators in registers; the x cells of
+//                          one (y, z) row of the grid are min(3, cx) cells taken cyclically from (ix-1) mod cx (from ix
+//                          at two cells, from 0 at one): run 0 goes up to cx, run 1 continues from 0 -- the defined
+//                          order at every ix and every cx, in at most two runs of xs.  The counters (not_finite, surface)
+//                          go through LDS counters and 64-bit integer atomics; the minima, maxima and the deviation
+//                          leave as one partial per workgroup
+//   sph_final_kernel       one workgroup: the partials in a fixed strided scan, then the words of the summary
+// No float atomic anywhere, no private (scratch) memory in any instance.  Shared device helpers: pgsd_stats.hpp,
+// pgsd_kernels.hpp; the launcher's host side: pgsd_scratch.hpp.
+#include "pgsd_stats.hpp"
+#include "pgsd_cells.hpp"
+#include "pgsd_scratch.hpp"
+
+#include <type_traits>
+
+namespace pgsd_amd
+    {
+#define SPH_WAVES (SEL_THREADS / 64)
+// one workgroup's share of what is no count: per sum the smallest and largest value over its entries that have a cell
+// (+inf / -inf: it has none, or NaNs only) and the deviation of the largest magnitude with its list position (SPH_NONE:
+// it has none)
+struct SphPartial
+    {
+    double lo[3], hi[3];
+    double dev;
+    uint32_t at, pad;
+    };
+
+// does the deviation (d, i) replace (e, k): the larger magnitude, then the smaller position; an empty slot never does
+__device__ __forceinline__ bool sph_dev_before(double d, uint32_t i, double e, uint32_t k)
+    {
+    if (i == SPH_NONE)
+        return false;
+    if (k == SPH_NONE)
+        return true;
+    const double ad = __builtin_fabs(d), ae = __builtin_fabs(e);
+    return ad > ae || (ad == ae && i < k);
+    }
+
+__device__ __forceinline__ void sph_merge(SphPartial& p, const SphPartial& o)
+    {
+#pragma unroll
+    for (int s = 0; s < 3; s++)
+        {
+        p.lo[s] = o.lo[s] < p.lo[s] ? o.lo[s] : p.lo[s];
+        p.hi[s] = o.hi[s] > p.hi[s] ? o.hi[s] : p.hi[s];
+        }
+    if (sph_dev_before(o.dev, o.at, p.dev, p.at))
+        {
+        p.dev = o.dev;
+        p.at = o.at;
+        }
+    }
+
+__device__ __forceinline__ SphPartial sph_nothing()
+    {
+    SphPartial p;
+#pragma unroll
+    for (int s = 0; s < 3; s++)
+        {
+        p.lo[s] = __builtin_huge_val();
+        p.hi[s] = -__builtin_huge_val();
+        }
+    p.dev = 0.0;
+    p.at = SPH_NONE;
+    p.pad = 0;
+    return p;
+    }
+
+// one value of a float32 or float64 column as a double (exact)
+__device__ __forceinline__ double sph_column(const void* base, uint32_t f64, uint64_t row)
+    {
+    return f64 ? ((const double*)base)[row] : (double)((const float*)base)[row];
+    }
+
+template<bool F64>
+__global__ __launch_bounds__(SEL_THREADS) void sph_compact_kernel(const SphArgs a, const uint32_t* flag_dev, void* __restrict__ xs,
+                                                                  double* __restrict__ ms, double* __restrict__ vs)
+    {
+    const uint64_t k = (uint64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
+    if (k >= a.n || *flag_dev != 0)
+        return;
+    const uint64_t row = a.rows[k];
+    if (row >= a.N) // (the check kernel has refused such a list: nothing is loaded for it)
+        return;
+    if constexpr (F64)
+        {
+        const double* q = (const double*)a.pos + row * 3;
+        double* o = (double*)xs + k * 3;
+        o[0] = q[0];
+        o[1] = q[1];
+        o[2] = q[2];
+        }
+    else
+        {
+        const u32x3 v = *(const u32x3_a4*)((const uint32_t*)a.pos + row * 3);
+        *(u32x3_a4*)((uint32_t*)xs + k * 3) = v;
+        }
+    const double m = a.mass ? sph_column(a.mass, a.mass_f64, row) : a.mass_default;
+    ms[k] = m;
+    if (a.volume)
+        vs[k] = m / (a.density ? sph_column(a.density, a.density_f64, row) : a.density_default);
+    }
+
+// w(q) of pgsd.hoomd.sph_weight: the operations as written there, one rounding each
+template<int KERNEL> __device__ __forceinline__ double sph_weight(double q)
+    {
+#pragma clang fp contract(off)
+    if constexpr (KERNEL == SPH_WENDLAND_C2)
+        {
+        const double t = 1.0 - 0.5 * q;
+        const double t2 = t * t;
+        return (t2 * t2) * (2.0 * q + 1.0);
+        }
+    else
+        {
+        const double q2 = q * q;
+        if (q < 1.0)
+            return (1.0 - 1.5 * q2) + 0.75 * (q2 * q);
+        const double u = 2.0 - q;
+        return 0.25 * ((u * u) * u);
+        }
+    }
+
+// words: the summary in device memory, zeroed by the launcher (words 2 and 3, not_finite and surface, are added to here)
+template<bool F64, int KERNEL, bool VOL>
+__global__ __launch_bounds__(SEL_THREADS) void sph_pair_kernel(const SphArgs a, const uint32_t* __restrict__ offs,
+                                                               const uint32_t* flag_dev, const void* __restrict__ xs,
+                                                               const double* __restrict__ ms, const double* __restrict__ vs,
+                                                               double* __restrict__ out_number, double* __restrict__ out_density,
+                                                               double* __restrict__ out_shepard,
+                                                               unsigned long long* __restrict__ words,
+                                                               SphPartial* __restrict__ part)
+    {
+#pragma clang fp contract(off)
+    typedef typename std::conditional<F64, double, float>::type elem_t;
+    __shared__ uint32_t s_not_finite, s_surface;
+    __shared__ SphPartial s_part[SPH_WAVES];
+    if (*flag_dev != 0)
+        return;
+    if (threadIdx.x == 0)
+        {
+        s_not_finite = 0;
+        s_surface = 0;
+        }
+    __syncthreads();
+    const uint64_t n = a.n;
+    const uint64_t k64 = (uint64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
+    const uint32_t k = (uint32_t)k64; // (n < 2^32)
+    const bool live = k64 < n;
+    const int32_t c = live ? a.cell[k] : (int32_t)a.n_cells;
+    const bool has = live && c >= 0 && (uint32_t)c < a.n_cells;
+    const elem_t* x = (const elem_t*)xs;
+    double a_n = 0.0, a_m = 0.0, a_v = 0.0;
+    if (has)
+        {
+        const double xi0 = (double)x[(size_t)k * 3 + 0], xi1 = (double)x[(size_t)k * 3 + 1], xi2 = (double)x[(size_t)k * 3 + 2];
+        const double Lx = a.vectors[0], Ly = a.vectors[1], Lz = a.vectors[2];
+        const double xyLy = a.vectors[3], xzLz = a.vectors[4], yzLz = a.vectors[5];
+        const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5; // (exact halves)
+        const double r2 = a.r2, inv_h = a.inv_h;
+        const bool three = a.dims != 2;
+        const int cx = (int)a.cells[0], cy = (int)a.cells[1], cz = (int)a.cells[2];
+        const int ix = (int)((uint32_t)c % (uint32_t)cx), iy = (int)(((uint32_t)c / (uint32_t)cx) % (uint32_t)cy);
+        const int iz = (int)((uint32_t)c / ((uint32_t)cx * (uint32_t)cy));
+        // the x cells in the defined order: `take` cells cyclically from `from`, as run 0 [from, b0) and run 1 [0, b1)
+        const int take = min(3, cx);
+        const int from = cx == 1 ? 0 : (cx == 2 ? ix : (ix == 0 ? cx - 1 : ix - 1));
+        const int b0 = min(from + take, cx), b1 = max(from + take - cx, 0);
+        const int ylo = cy >= 3 ? -1 : 0, yhi = cy >= 2 ? 1 : 0;
+        const int zlo = cz >= 3 ? -1 : 0, zhi = cz >= 2 ? 1 : 0;
+        for (int oz = zlo; oz <= zhi; oz++)
+            {
+            int wz = iz + oz;
+            wz = wz < 0 ? wz + cz : (wz >= cz ? wz - cz : wz);
+            for (int oy = ylo; oy <= yhi; oy++)
+                {
+                int wy = iy + oy;
+                wy = wy < 0 ? wy + cy : (wy >= cy ? wy - cy : wy);
+                const uint32_t row0 = (uint32_t)cx * ((uint32_t)wy + (uint32_t)cy * (uint32_t)wz);
+                for (int run = 0; run < 2; run++)
+                    {
+                    const int ra = run ? 0 : from, rb = run ? b1 : b0;
+                    if (rb <= ra)
+                        continue;
+                    const uint32_t lo = (uint32_t)min((uint64_t)offs[row0 + (uint32_t)ra], n);
+                    const uint32_t hi = (uint32_t)min((uint64_t)offs[row0 + (uint32_t)rb], n);
+                    for (uint32_t j = lo; j < hi; j++)
+                        {
+                        const double xj0 = (double)x[(size_t)j * 3 + 0], xj1 = (double)x[(size_t)j * 3 + 1];
+                        double dx = xj0 - xi0, dy = xj1 - xi1, dz = 0.0;
+                        if (three)
+                            {
+                            dz = (double)x[(size_t)j * 3 + 2] - xi2;
+                            const bool up = dz >= hz, down = dz < -hz;
+                            dx = up ? dx - xzLz : (down ? dx + xzLz : dx);
+                            dy = up ? dy - yzLz : (down ? dy + yzLz : dy);
+                            dz = up ? dz - Lz : (down ? dz + Lz : dz);
+                            }
+                            {
+                            const bool up = dy >= hy, down = dy < -hy;
+                            dx = up ? dx - xyLy : (down ? dx + xyLy : dx);
+                            dy = up ? dy - Ly : (down ? dy + Ly : dy);
+                            }
+                            {
+                            const bool up = dx >= hx, down = dx < -hx;
+                            dx = up ? dx - Lx : (down ? dx + Lx : dx);
+                            }
+                        const double d2 = (dx * dx + dy * dy) + dz * dz;
+                        if (d2 < r2)
+                            {
+                            const double rr = __builtin_sqrt(d2);
+                            const double q = rr * inv_h;
+                            const double w = sph_weight<KERNEL>(q);
+                            a_n = a_n + w;
+                            a_m = a_m + ms[j] * w;
+                            if constexpr (VOL)
+                                a_v = a_v + vs[j] * w;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    // (an entry without a cell: the accumulators are +0.0, and so are the products)
+    const double number = a.sigma * a_n, density = a.sigma * a_m, shepard = a.sigma * a_v;
+    if (live)
+        {
+        if (out_number)
+            out_number[k] = number;
+        if (out_density)
+            out_density[k] = density;
+        if (VOL && out_shepard)
+            out_shepard[k] = shepard;
+        }
+    SphPartial p = sph_nothing();
+    if (has)
+        {
+        // (a NaN passes no compare: it replaces neither bound)
+        p.lo[0] = number < p.lo[0] ? number : p.lo[0];
+        p.hi[0] = number > p.hi[0] ? number : p.hi[0];
+        p.lo[1] = density < p.lo[1] ? density : p.lo[1];
+        p.hi[1] = density > p.hi[1] ? density : p.hi[1];
+        if (!(__builtin_fabs(density) < __builtin_huge_val()))
+            atomicAdd(&s_not_finite, 1u);
+        if constexpr (VOL)
+            {
+            p.lo[2] = shepard < p.lo[2] ? shepard : p.lo[2];
+            p.hi[2] = shepard > p.hi[2] ? shepard : p.hi[2];
+            if (a.surface && shepard < a.surface_below)
+                atomicAdd(&s_surface, 1u);
+            const uint64_t row = a.rows[k];
+            const double rho = a.density ? sph_column(a.density, a.density_f64, row < a.N ? row : 0) : a.density_default;
+            const double dev = density - rho;
+            if (dev == dev)
+                {
+                p.dev = dev;
+                p.at = k;
+                }
+            }
+        }
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1)
+        {
+        SphPartial o;
+#pragma unroll
+        for (int s = 0; s < 3; s++)
+            {
+            o.lo[s] = __shfl_xor(p.lo[s], h, 64);
+            o.hi[s] = __shfl_xor(p.hi[s], h, 64);
+            }
+        o.dev = __shfl_xor(p.dev, h, 64);
+        o.at = __shfl_xor(p.at, h, 64);
+        sph_merge(p, o);
+        }
+    if ((threadIdx.x & 63) == 0)
+        s_part[threadIdx.x >> 6] = p;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        {
+        SphPartial q = s_part[0];
+#pragma unroll
+        for (int w = 1; w < SPH_WAVES; w++)
+            sph_merge(q, s_part[w]);
+        part[blockIdx.x] = q;
+        if (s_not_finite)
+            atomicAdd(&words[2], (unsigned long long)s_not_finite);
+        if (s_surface)
+            atomicAdd(&words[3], (unsigned long long)s_surface);
+        }
+    }
+
+// One workgroup.  The words: n, nowhere, not_finite, surface, deviation_at, deviation_row, then as bit patterns the
+// minimum and maximum of number, density and shepard and the deviation.
+__global__ __launch_bounds__(SEL_THREADS) void sph_final_kernel(const SphArgs a, const uint32_t* __restrict__ offs,
+                                                                const uint32_t* flag_dev, const SphPartial* __restrict__ part,
+                                                                uint32_t n_parts, unsigned long long* __restrict__ words)
+    {
+    __shared__ SphPartial s_part[SEL_THREADS];
+    if (*flag_dev != 0)
+        return;
+    SphPartial p = sph_nothing();
+    for (uint32_t t = threadIdx.x; t < n_parts; t += SEL_THREADS)
+        sph_merge(p, part[t]);
+    s_part[threadIdx.x] = p;
+    __syncthreads();
+    if (threadIdx.x != 0)
+        return;
+    for (uint32_t t = 1; t < SEL_THREADS; t++)
+        sph_merge(p, s_part[t]);
+    const uint64_t n = a.n;
+    const uint64_t somewhere = min((uint64_t)offs[a.n_cells], n);
+    const bool any = p.at != SPH_NONE && p.at < n;
+    words[0] = n;
+    words[1] = n - somewhere;
+    words[4] = any ? p.at : SPH_NONE;
+    words[5] = any ? a.rows[p.at] : SPH_NONE;
+#pragma unroll
+    for (int s = 0; s < 3; s++)
+        {
+        words[6 + 2 * s] = (unsigned long long)__double_as_longlong(p.lo[s]);
+        words[7 + 2 * s] = (unsigned long long)__double_as_longlong(p.hi[s]);
+        }
+    words[12] = (unsigned long long)__double_as_longlong(any ? p.dev : 0.0);
+    }
+
+// ------------------------------------------------------------------ host side
+namespace
+    {
+// The family's scratch space (grow-only, per device, its own lock held), in bytes: the device flag word (16), the
+// offsets (n_cells + 2 words), the compacted positions (n x 3 elements), masses and volumes (n doubles each), the
+// partials (one per workgroup) and the summary; the pinned flag word is the host's view of a refused list, the pinned
+// host block the landing place of the summary.
+constexpr size_t SPH_SUMMARY_BYTES = (size_t)SPH_SUMMARY_WORDS * sizeof(uint64_t);
+Scratch g_sph_scratch("SPH kernel sums", 1.25, 1u << 16, SPH_SUMMARY_BYTES, sizeof(uint64_t));
+std::mutex g_sph_lock;
+
+size_t sph_round16(size_t bytes)
+    {
+    return (bytes + 15) & ~(size_t)15;
+    }
+
+const char* sph_refused = "a cell id descends or lies outside [0, n_cells], or an entry of the row list lies outside "
+                          "the chunks (nothing was computed)";
+
+template<bool F64, int KERNEL>
+void sph_launch_pair(bool vol, dim3 grid, dim3 block, hipStream_t stream, const SphArgs& a, const uint32_t* offs,
+                     const uint32_t* flag_dev, const void* xs, const double* ms, const double* vs, double* out_number,
+                     double* out_density, double* out_shepard, unsigned long long* words, SphPartial* part)
+    {
+    if (vol)
+        hipLaunchKernelGGL((sph_pair_kernel<F64, KERNEL, true>), grid, block, 0, stream, a, offs, flag_dev, xs, ms, vs,
+                           out_number, out_density, out_shepard, words, part);
+    else
+        hipLaunchKernelGGL((sph_pair_kernel<F64, KERNEL, false>), grid, block, 0, stream, a, offs, flag_dev, xs, ms, vs,
+                           out_number, out_density, out_shepard, words, part);
+    }
+    } // namespace
+
+void warm_sph_kernels()
+    {
+    warm_kernel((const void*)sph_pair_kernel<false, SPH_WENDLAND_C2, true>);
+    }
+
+int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, double* out_shepard, uint64_t* out_summary,
+                    hipStream_t stream, std::string* err)
+    {
+    static const char* what = "SPH kernel sums";
+    const auto fail = [err](const char* why) { return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, std::string(what) + ": " + why); };
+    if (!out_summary)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    if (a.n >= (1ull << 32))
+        return fail("a list holds fewer than 2^32 entries");
+    if (a.N >= (1ull << 32))
+        return fail("chunks of 2^32 rows or more have no 32-bit row list");
+    uint64_t n_cells = 1;
+    for (int i = 0; i < 3; i++)
+        {
+        if (a.cells[i] < 1 || a.cells[i] > ORDER_MAX_AXIS_CELLS)
+            return fail("every axis takes 1 to 1024 cells");
+        n_cells *= a.cells[i];
+        }
+    if (n_cells > CELLS_MAX_CELLS || n_cells != a.n_cells)
+        return fail("a grid holds 1 to 2^20 cells");
+    if (a.kernel != SPH_WENDLAND_C2 && a.kernel != SPH_CUBIC_SPLINE)
+        return fail("the kernel is 0 (Wendland C2) or 1 (cubic spline)");
+    const uint64_t n = a.n;
+    if (n == 0)
+        {
+        sph_sums_of_nothing(out_summary);
+        return PGSD_SUCCESS;
+        }
+    if (a.N == 0)
+        return fail(sph_refused);
+    if (!a.rows || !a.cell || !a.pos)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const uint32_t n_blocks = (uint32_t)((n + SEL_THREADS - 1) / SEL_THREADS);
+    const size_t offs_bytes = sph_round16(((size_t)a.n_cells + 2) * sizeof(uint32_t));
+    const size_t xs_bytes = sph_round16((size_t)n * 3 * (a.f64 ? sizeof(double) : sizeof(float)));
+    const size_t col_bytes = sph_round16((size_t)n * sizeof(double));
+    const size_t part_bytes = sph_round16((size_t)n_blocks * sizeof(SphPartial));
+    const size_t words_bytes = SPH_SUMMARY_BYTES;
+    LaunchScope scope(g_sph_lock, g_sph_scratch, 16 + offs_bytes + xs_bytes + 2 * col_bytes + part_bytes + words_bytes, stream,
+                      err);
+    if (scope.rc() != PGSD_SUCCESS)
+        return scope.rc();
+    char* dev = scope.mem().dev;
+    uint32_t* flag_dev = (uint32_t*)dev;
+    uint32_t* offs = (uint32_t*)(dev + 16);
+    void* xs = dev + 16 + offs_bytes;
+    double* ms = (double*)((char*)xs + xs_bytes);
+    double* vs = (double*)((char*)ms + col_bytes);
+    SphPartial* part = (SphPartial*)((char*)vs + col_bytes);
+    unsigned long long* words = (unsigned long long*)((char*)part + part_bytes);
+    uint32_t* host_flag = (uint32_t*)scope.mem().mapped;
+    uint32_t* host_flag_dev = (uint32_t*)scope.mem().mapped_dev;
+    __atomic_store_n(host_flag, 0u, __ATOMIC_RELEASE);
+    const dim3 block(SEL_THREADS), per_entry(n_blocks);
+    const bool vol = a.volume != 0;
+    hipError_t e = hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(words, 0, words_bytes, stream);
+    if (e == hipSuccess)
+        {
+        hipLaunchKernelGGL(cells_check_kernel, per_entry, block, 0, stream, a.rows, a.cell, n, a.N, a.n_cells, flag_dev,
+                           host_flag_dev);
+        hipLaunchKernelGGL(cells_offsets_kernel, dim3((a.n_cells + 2 + SEL_THREADS - 1) / SEL_THREADS), block, 0, stream, a.cell,
+                           n, a.n_cells, flag_dev, offs);
+        if (a.f64)
+            {
+            hipLaunchKernelGGL(sph_compact_kernel<true>, per_entry, block, 0, stream, a, flag_dev, xs, ms, vs);
+            if (a.kernel == SPH_WENDLAND_C2)
+                sph_launch_pair<true, SPH_WENDLAND_C2>(vol, per_entry, block, stream, a, offs, flag_dev, xs, ms, vs, out_number,
+                                                       out_density, out_shepard, words, part);
+            else
+                sph_launch_pair<true, SPH_CUBIC_SPLINE>(vol, per_entry, block, stream, a, offs, flag_dev, xs, ms, vs, out_number,
+                                                        out_density, out_shepard, words, part);
+            }
+        else
+            {
+            hipLaunchKernelGGL(sph_compact_kernel<false>, per_entry, block, 0, stream, a, flag_dev, xs, ms, vs);
+            if (a.kernel == SPH_WENDLAND_C2)
+                sph_launch_pair<false, SPH_WENDLAND_C2>(vol, per_entry, block, stream, a, offs, flag_dev, xs, ms, vs, out_number,
+                                                        out_density, out_shepard, words, part);
+            else
+                sph_launch_pair<false, SPH_CUBIC_SPLINE>(vol, per_entry, block, stream, a, offs, flag_dev, xs, ms, vs, out_number,
+                                                         out_density, out_shepard, words, part);
+            }
+        hipLaunchKernelGGL(sph_final_kernel, dim3(1), block, 0, stream, a, offs, flag_dev, part, n_blocks, words);
+        e = hipGetLastError();
+        }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(scope.mem().host, words, words_bytes, hipMemcpyDeviceToHost, stream);
+    const int rc = scope.finish(what, e);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (__atomic_load_n(host_flag, __ATOMIC_ACQUIRE) != 0)
+        return fail(sph_refused);
+    const uint64_t* landed = (const uint64_t*)scope.mem().host;
+    std::copy(landed, landed + SPH_SUMMARY_WORDS, out_summary);
+    return PGSD_SUCCESS;
+    }
+    } // namespace pgsd_amd

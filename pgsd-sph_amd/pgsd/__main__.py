@@ -22,7 +22,12 @@
            ``--neighbours R`` adds the neighbour census inside the range R: the search grid, the entries and those
            nowhere, the mean, smallest and largest neighbour count, the isolated entries and the closest pair with its
            rows and distance, and with ``--bins B`` the g(r) table (``--types``; ``pgsd.hoomd.frame_neighbours`` on the
-           host: no GPU).
+           host: no GPU);
+           ``--sph [H]`` adds the SPH kernel sums for the smoothing length H (without H: the frame's ``slength``, which
+           must be uniform): the search grid and the entries, the range of the summation density, its largest deviation
+           from the stored density with the row, the range of the Shepard sum and -- with ``--surface S`` -- the entries
+           whose Shepard sum is below S (``--kernel wendland_c2|cubic_spline``, ``--types``;
+           ``pgsd.hoomd.frame_kernel_sums`` on the host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -93,6 +98,28 @@ def _cmd_info(args):
         _print_cells(args, frame)
     if args.neighbours is not None:
         _print_neighbours(args, frame)
+    if args.sph is not None:
+        _print_sph(args, frame)
+
+
+def _print_sph(args, frame):
+    """``info --sph``: `pgsd.hoomd.frame_kernel_sums` of one frame, on the host."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_kernel_sums(traj[frame], None if args.sph < 0 else args.sph, kernel=args.kernel, where=where,
+                                    surface_below=args.surface)
+    print("SPH sums of frame %d with h = %r (%s) over %d x %d x %d cells%s:"
+          % ((frame, m.h, m.kernel) + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  entries:      %d  nowhere: %d" % (m.n, m.nowhere))
+    if m.n > m.nowhere:
+        print("  density:      smallest %r  largest %r  not finite: %d" % (m.density_min, m.density_max, m.not_finite))
+        if m.deviation is not None:
+            print("  deviation:    %r from the stored density at row %d" % (m.deviation, m.deviation_row))
+        if m.volume:
+            print("  shepard:      smallest %r  largest %r" % (m.shepard_min, m.shepard_max))
+        if m.surface is not None:
+            print("  surface:      %d entries below %r" % (m.surface, m.surface_below))
 
 
 def _print_neighbours(args, frame):
@@ -331,6 +358,13 @@ def main(argv=None):
     p.add_argument('--neighbours', type=float, default=None, metavar='R',
                    help="print the neighbour census inside the range R: grid, entries, mean, smallest and largest count, "
                         "isolated entries and the closest pair")
+    p.add_argument('--sph', type=float, nargs='?', const=-1.0, default=None, metavar='H',
+                   help="print the SPH kernel sums for the smoothing length H (without H: the frame's uniform slength): "
+                        "grid, entries, density range, largest deviation from the stored density, Shepard range")
+    p.add_argument('--kernel', type=str, default='wendland_c2', choices=('wendland_c2', 'cubic_spline'),
+                   help="the kernel of --sph (default: wendland_c2)")
+    p.add_argument('--surface', type=float, default=None, metavar='S',
+                   help="with --sph: count the entries whose Shepard sum is below S (the free surface)")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")
     p.add_argument('--minimum-image', action='store_true',
                    help="--displacement of the wrapped positions, folded into the box, instead of through the image flags")

@@ -1954,6 +1954,98 @@ cdef class PGSDFile:
             got.nearest2 = _device_head(out_nearest2, count)
         return got
 
+    def sph_sums_device(self, frame, name, box, h, cells, rows, cell, n=None, mass=None, density=None, defaults=None,
+                        dimensions=3, kernel='wendland_c2', surface_below=None, return_rows=False):
+        """The SPH kernel sums of a row list in cell order on the GPU: summation density, number density and Shepard sum
+        over the kernel support ``2h``, in the order that is part of their definition.
+
+        Args:
+            frame (int), name (str): the position chunk, N x 3 float32 or float64.
+            box: ``(Lx, Ly, Lz, xy, xz, yz)``; the kernel receives :func:`pgsd.hoomd.box_vectors` of it.
+            h (float): the smoothing length, finite and positive; the support ``2h`` is at most half the box's nearest
+                plane distance on every axis.
+            cells: ``(cx, cy, cz)``, no narrower than ``2h`` (:func:`pgsd.hoomd.neighbour_grid_for` of ``2h``).
+            rows, cell: 32-bit row indices and int32 cell ids in GPU memory, one id per entry, non-decreasing, in
+                ``[0, n_cells]`` -- what :meth:`order_rows_by_cell_device` leaves for the same grid.
+            n (int): the number of entries to take (``None``: all of ``rows``).
+            mass, density: ``(frame, name)`` of an N x 1 float32 or float64 chunk, or ``None``: stored nowhere.
+            defaults: ``(mass, density)`` that stand for a chunk stored nowhere; ``None``: every mass is 1.0 and, without a
+                density chunk, there is no volume sum (a NaN as the density default says the same).
+            dimensions (int): 2 never looks at z and takes the 2-D normalisation.
+            kernel (str): ``'wendland_c2'`` or ``'cubic_spline'``.
+            surface_below (float): count the entries whose Shepard sum is below it (``None``: no count).
+            return_rows (bool): keep the per-entry results in GPU memory.
+
+        Returns:
+            A :class:`pgsd.hoomd.KernelSums`: exactly :func:`pgsd.hoomd.sph_kernel_sums` of the same list -- every counter
+            and index, every float bit for bit.  With ``return_rows`` its ``rows`` and ``cell`` are the arguments and
+            ``number``, ``density`` and ``shepard`` (``None`` without a volume) are float64 arrays of ``n`` entries in GPU
+            memory; otherwise the five are ``None``.  The chunks are staged whole unless an earlier call left them
+            staged; the staged rows are kept until the next :meth:`wait_read`.  What the library refuses
+            (:c:func:`pgsd_sph_sums_device`) raises ValueError and computes nothing.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry, e_mass, e_density
+        cdef const C.pgsd_index_entry* p_mass = NULL
+        cdef const C.pgsd_index_entry* p_density = NULL
+        self._entry(frame, name, &entry)
+        if mass is not None:
+            self._entry(mass[0], mass[1], &e_mass)
+            p_mass = &e_mass
+        if density is not None:
+            self._entry(density[0], density[1], &e_density)
+            p_density = &e_density
+        c_box = numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6]
+        if c_box.shape[0] != 6:
+            raise ValueError("box must hold 6 values")
+        c_vectors = numpy.ascontiguousarray(_hoomd.box_vectors(c_box), dtype=numpy.float64)
+        grid = [int(v) for v in cells]
+        if len(grid) != 3 or any(not 0 <= v < (1 << 32) for v in grid):
+            raise ValueError("sph_sums_device: cells holds three counts, each 1 to 1024")
+        c_cells = numpy.array(grid, dtype=numpy.uint32)
+        if kernel not in _hoomd.SPH_KERNELS:
+            raise ValueError("sph_sums_device: the kernel is one of %s: %r" % (', '.join(_hoomd.SPH_KERNELS), kernel))
+        c_defaults = numpy.ascontiguousarray(
+            numpy.array([1.0, float('nan')] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+        if c_defaults.shape[0] != 2:
+            raise ValueError("sph_sums_device: defaults holds a mass and a density")
+        volume = density is not None or c_defaults[1] == c_defaults[1]
+        c_rows, count = _row_list("sph_sums_device", rows, n)
+        c_cell, _ = _row_list("sph_sums_device", cell, count)
+        summary = numpy.zeros(13, dtype=numpy.uint64)
+        cdef uintptr_t p_number = 0, p_rho = 0, p_shepard = 0
+        out_number = out_rho = out_shepard = None
+        if return_rows:
+            device = self.pipeline_device()
+            out_number = _device_empty((max(count, 1),), numpy.float64, device)
+            out_rho = _device_empty((max(count, 1),), numpy.float64, device)
+            p_number, p_rho = out_number.data_ptr(), out_rho.data_ptr()
+            if volume:
+                out_shepard = _device_empty((max(count, 1),), numpy.float64, device)
+                p_shepard = out_shepard.data_ptr()
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef uint32_t c_kernel = _hoomd.SPH_KERNELS.index(kernel)
+        cdef double c_h = float(h), c_surface = float('nan') if surface_below is None else float(surface_below)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_sph_sums_device(&self._handle, &entry, p_mass, p_density, <const double*>p_defaults,
+                                            <const double*>p_vectors, c_h, c_kernel, c_dims, <const uint32_t*>p_cells,
+                                            <const uint32_t*>p_rows, <const int32_t*>p_cell, c_n, c_surface,
+                                            <double*>p_number, <double*>p_rho, <double*>p_shepard, <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("sph_sums_device", retval, "refused", self._name, err)
+        got = _hoomd.KernelSums(c_h, kernel, grid, int(dimensions), summary, volume, surface_below)
+        if return_rows:
+            got.rows, got.cell = _device_head(rows, count), _device_head(cell, count)
+            got.number, got.density = _device_head(out_number, count), _device_head(out_rho, count)
+            got.shepard = _device_head(out_shepard, count) if volume else None
+        return got
+
     def frame_displacements_device(self, chunks, vectors_a, vectors_b, minimum_image=False, dimensions=3, type0=0,
                                    n_types=1, rows=None, n=None, out=None):
         """Drift, squared displacement and the largest move between two frames per particle type, reduced on the GPU in

@@ -1794,6 +1794,306 @@ def frame_neighbours(frame_or_arrays, r, bins=0, cells=None, where=None, types=N
     return particle_neighbours(position, box, r, rows=rows, cells=cells, dimensions=dimensions, bins=bins)
 
 
+# ---- SPH kernel sums: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_sums_device`) equals exactly
+SPH_KERNELS = ('wendland_c2', 'cubic_spline')
+_SPH_SUMMARY_WORDS = 13     # n, nowhere, not_finite, surface, deviation_at, deviation_row, 3 x (min, max), deviation
+
+
+def _sph_kernel_id(kernel):
+    if kernel not in SPH_KERNELS:
+        raise ValueError("the kernel is one of %s: %r" % (', '.join(SPH_KERNELS), kernel))
+    return SPH_KERNELS.index(kernel)
+
+
+def _sph_length(h):
+    h = float(h)
+    if not (h > 0.0 and h < float('inf')):
+        raise ValueError("the smoothing length must be finite and positive: %r" % (h,))
+    return h
+
+
+def sph_sigma(kernel, h, dimensions=3):
+    """The normalisation of an SPH kernel of support ``2h``, float64 on the host: ``21/(16 pi h^3)`` and ``7/(4 pi h^2)``
+    for ``wendland_c2`` in 3-D and 2-D, ``1/(pi h^3)`` and ``10/(7 pi h^2)`` for ``cubic_spline``."""
+    k, h = _sph_kernel_id(kernel), numpy.float64(_sph_length(h))
+    if int(dimensions) == 3:
+        return float((21.0 / (16.0 * numpy.pi * (h * h * h))) if k == 0 else (1.0 / (numpy.pi * (h * h * h))))
+    return float((7.0 / (4.0 * numpy.pi * (h * h))) if k == 0 else (10.0 / (7.0 * numpy.pi * (h * h))))
+
+
+def sph_weight(q, kernel='wendland_c2'):
+    """``w(q)`` of one pair, float64 without contraction, for ``q = |x_i - x_j| * (1/h)`` below 2.  ``wendland_c2``:
+    ``t = 1.0 - 0.5*q``, ``t2 = t*t``, ``w = (t2*t2) * (2.0*q + 1.0)``.  ``cubic_spline``: ``q2 = q*q``; where ``q < 1.0``
+    ``w = (1.0 - 1.5*q2) + 0.75*(q2*q)``, otherwise ``u = 2.0 - q`` and ``w = 0.25*((u*u)*u)``."""
+    q = numpy.asarray(q, dtype=numpy.float64)
+    if _sph_kernel_id(kernel) == 0:
+        t = 1.0 - 0.5 * q
+        t2 = t * t
+        return (t2 * t2) * (2.0 * q + 1.0)
+    q2 = q * q
+    u = 2.0 - q
+    return numpy.where(q < 1.0, (1.0 - 1.5 * q2) + 0.75 * (q2 * q), 0.25 * ((u * u) * u))
+
+
+class KernelSums(object):
+    """The SPH kernel sums of a list in cell order (`sph_kernel_sums`).
+
+    Attributes:
+        h (float), kernel (str), grid (``(cx, cy, cz)``), dimensions (int), surface_below (float or ``None``), volume
+            (bool: was a ``density`` given): what was asked; sigma (float): `sph_sigma`.
+        rows, cell: the list in cell order and its cell ids (``n_cells``: nowhere).
+        number, density, shepard (float64): per entry, in list order, ``sigma * sum w``, ``sigma * sum m_j w`` and
+            ``sigma * sum (m_j / rho_j) w`` over the entries inside ``2h``, the entry itself among them; ``+0.0`` for an
+            entry nowhere.  ``shepard`` is ``None`` without ``density``.  The five per-entry arrays are numpy arrays from
+            the model; from the GPU they are ``None`` unless ``return_rows`` left them in GPU memory.
+        n, nowhere (int): the entries, and those without a cell.
+        number_min, number_max, density_min, density_max, shepard_min, shepard_max (float): over the entries that have a
+            cell, by strict compares from ``+inf`` / ``-inf`` (a NaN never replaces a value); the last two ``None``
+            without ``density``.
+        not_finite (int): the entries that have a cell and whose ``density`` sum is NaN or infinite.
+        deviation (float), deviation_at (int), deviation_row (int): ``density_i - float64(rho_i)`` where its magnitude is
+            the largest over the entries that have a cell, sign kept, the smaller list position on a tie, a NaN never;
+            the position and its row.  All ``None`` without ``density`` or where no entry has a number for it.
+        surface (int or ``None``): the entries that have a cell and ``shepard < surface_below``.
+    """
+
+    __slots__ = ('h', 'kernel', 'grid', 'dimensions', 'surface_below', 'volume', 'sigma', 'rows', 'cell', 'number', 'density',
+                 'shepard', 'n', 'nowhere', 'not_finite', 'surface', 'deviation', 'deviation_at', 'deviation_row',
+                 'number_min', 'number_max', 'density_min', 'density_max', 'shepard_min', 'shepard_max', '_words')
+
+    def __init__(self, h, kernel, grid, dimensions, summary, volume, surface_below=None, rows=None, cell=None, number=None,
+                 density=None, shepard=None):
+        """``summary``: the 13 uint64 words of `pgsd_sph_sums_device` -- n, nowhere, not_finite, surface, deviation_at,
+        deviation_row, then as float64 bit patterns the minimum and maximum of number, density and shepard and the
+        deviation."""
+        s = numpy.ascontiguousarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _SPH_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _SPH_SUMMARY_WORDS)
+        self._words = s.copy()
+        self.h, self.kernel, self.dimensions, self.volume = float(h), kernel, int(dimensions), bool(volume)
+        self.sigma = sph_sigma(kernel, h, dimensions)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.surface_below = None if surface_below is None else float(surface_below)
+        self.n, self.nowhere, self.not_finite = int(s[0]), int(s[1]), int(s[2])
+        f = s[6:13].view(numpy.float64)
+        self.number_min, self.number_max, self.density_min, self.density_max = (float(v) for v in f[:4])
+        self.shepard_min, self.shepard_max = (float(f[4]), float(f[5])) if self.volume else (None, None)
+        self.surface = int(s[3]) if self.volume and self.surface_below is not None else None
+        found = self.volume and int(s[4]) != _NEIGHBOURS_NONE
+        self.deviation = float(f[6]) if found else None
+        self.deviation_at, self.deviation_row = (int(s[4]), int(s[5])) if found else (None, None)
+        self.rows, self.cell, self.number, self.density, self.shepard = rows, cell, number, density, shepard
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return self._words.copy()
+
+    def __repr__(self):
+        return "KernelSums(h=%r, kernel=%r, grid=%r, n=%d, nowhere=%d, density=[%r, %r], deviation=%r)" % (
+            self.h, self.kernel, self.grid, self.n, self.nowhere, self.density_min, self.density_max, self.deviation)
+
+
+def _sph_summary(n, somewhere, rows_sorted, number, density, shepard, rho, surface_below):
+    """The summary words from the per-entry results (``shepard``, ``rho`` None without a density): no float is summed, so
+    no order enters."""
+    words = numpy.zeros(_SPH_SUMMARY_WORDS, dtype=numpy.uint64)
+    f = words[6:13].view(numpy.float64)
+    words[0], words[1] = n, n - somewhere
+    words[4] = words[5] = _NEIGHBOURS_NONE
+    f[0:6:2], f[1:6:2], f[6] = numpy.inf, -numpy.inf, 0.0
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        for k, v in enumerate((number, density, shepard)):
+            if v is None or not somewhere:
+                continue
+            v = v[:somewhere]
+            ok = v[v == v]
+            if ok.size:
+                f[2 * k], f[2 * k + 1] = min(numpy.inf, ok.min()), max(-numpy.inf, ok.max())
+        words[2] = int(numpy.count_nonzero(~numpy.isfinite(density[:somewhere])))
+        if shepard is not None and somewhere:
+            if surface_below is not None:
+                words[3] = int(numpy.count_nonzero(shepard[:somewhere] < numpy.float64(surface_below)))
+            dev = density[:somewhere] - rho[:somewhere]
+            size = numpy.where(dev == dev, numpy.abs(dev), -1.0)
+            k = int(numpy.argmax(size))                 # (the first position that attains the maximum)
+            if size[k] >= 0.0:
+                words[4], words[5], f[6] = k, rows_sorted[k], dev[k]
+    return words
+
+
+def sph_kernel_sums(position, box, h, mass=None, density=None, rows=None, cells=None, dimensions=3, kernel='wendland_c2',
+                    surface_below=None):
+    """The SPH kernel sums of a row list: per entry ``i`` the number density ``sigma * sum_j W_ij``, the summation density
+    ``rho_i = sigma * sum_j m_j W_ij`` and the Shepard sum ``sigma * sum_j (m_j / rho_j) W_ij`` over the entries ``j``
+    inside the kernel support ``2h``, and over the list their ranges, the largest deviation of the summation density
+    from the stored one and the entries below a Shepard threshold (the free surface).  The definition the GPU pass
+    (`pgsd.fl.PGSDFile.sph_sums_device`, `HOOMDTrajectory.frame_kernel_sums_device`) equals exactly, the floats bit for
+    bit -- so the ORDER of every sum is part of it.
+
+    Args:
+        position: ``N x 3`` float32 or float64; box: ``(Lx, Ly, Lz, xy, xz, yz)``.
+        h (float): the smoothing length, finite and positive; the support, the range of the search, is ``2h``.
+        mass, density: ``N`` float32 or float64 values, or ``None``: every ``m_j`` is 1.0; no volume sum, no deviation, no
+            surface count.
+        rows: the list (any order, repeats allowed; ``None``: every row), put into cell order by `cell_order`; both ``i``
+            and ``j`` come from it and everything per entry is in that order.
+        cells: ``(cx, cy, cz)`` or ``None``: `neighbour_grid_for` ``(box, 2*h)``.  The grid and every refusal are
+            `particle_neighbours`' for the range ``2*h``.
+        kernel: ``'wendland_c2'`` or ``'cubic_spline'`` (`sph_weight`); surface_below: a float or ``None``.
+
+    **One pair**, float64 throughout without contraction, float32 inputs converted exactly: ``d2 = pair_distance2(x_i,
+    x_j)``; ``j`` contributes when ``d2 < r2``, strictly, with ``r2 = (2h)*(2h)`` formed once; ``i`` itself contributes
+    (``d2 = 0``, ``w = 1``) and a row listed twice is two entries; ``rr = sqrt(d2)``, ``q = rr * inv_h`` with ``inv_h =
+    1/h`` formed once, ``w = sph_weight(q)``.  Three accumulators per entry start at ``+0.0``: ``a_n += w``, ``a_m += m_j
+    * w``, ``a_v += V_j * w`` with ``V_j = m_j / rho_j``, one float64 division of the stored values taken as it is
+    (``rho_j = 0`` gives what IEEE gives).
+
+    **The order.**  Candidate cells are visited with ``oz`` over `_axis_offsets` ``(cz)``, inside it ``oy``, inside it
+    ``ox``, each tuple in its own order; the cell is ``((ix+ox) % cx, (iy+oy) % cy, (iz+oz) % cz)``; inside a cell the
+    order is ascending list position.  After the last candidate ``number = sigma*a_n``, ``density = sigma*a_m``,
+    ``shepard = sigma*a_v`` with `sph_sigma`.  An entry without a cell contributes to nobody and its values are ``+0.0``.
+
+    Returns a `KernelSums`.
+    """
+    dimensions = int(dimensions)
+    h = _sph_length(h)
+    kid = _sph_kernel_id(kernel)
+    support = float(numpy.float64(2.0) * numpy.float64(h))
+    grid = _neighbour_grid(box, support, cells, dimensions)
+    if surface_below is not None:
+        surface_below = float(surface_below)
+        if surface_below != surface_below:
+            raise ValueError("surface_below is a number or None")
+    p = numpy.asarray(position)
+    p = p.reshape(-1, 3) if p.size else numpy.zeros((0, 3), dtype=numpy.float32)
+    if p.dtype not in (numpy.float32, numpy.float64):
+        raise ValueError("position holds float32 or float64 values")
+    columns = []
+    for name, v in (('mass', mass), ('density', density)):
+        if v is not None:
+            v = numpy.asarray(v)
+            if v.dtype not in (numpy.float32, numpy.float64) or v.size != p.shape[0]:
+                raise ValueError("%s holds one float32 or float64 value per row of position" % name)
+            v = v.reshape(-1).astype(numpy.float64)
+        columns.append(v)
+    mass, density = columns
+    rows = numpy.arange(p.shape[0], dtype=numpy.int64) if rows is None else rows
+    rows_sorted, cell_sorted, _ = cell_order(p, box, rows, grid, dimensions)
+    n = rows_sorted.shape[0]
+    cx, cy, cz = grid
+    n_cells = cx * cy * cz
+    vectors = box_vectors(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+    r2 = numpy.float64(support) * numpy.float64(support)
+    inv_h = numpy.float64(1.0) / numpy.float64(h)
+    sigma = numpy.float64(sph_sigma(kernel, h, dimensions))
+    offs = cell_offsets(cell_sorted, n_cells)
+    at = rows_sorted.astype(numpy.int64)
+    xs = p[at].astype(numpy.float64)
+    m = numpy.ones(n, dtype=numpy.float64) if mass is None else mass[at]
+    rho = None if density is None else density[at]
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        vol = None if rho is None else m / rho
+    a_n, a_m = numpy.zeros(n, dtype=numpy.float64), numpy.zeros(n, dtype=numpy.float64)
+    a_v = None if vol is None else numpy.zeros(n, dtype=numpy.float64)
+    somewhere = int(offs[n_cells])                       # the entries that have a cell come first
+    ids = cell_sorted[:somewhere]
+    ix, iy, iz = ids % cx, (ids // cx) % cy, ids // (cx * cy)
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        for oz in _axis_offsets(cz):
+            for oy in _axis_offsets(cy):
+                for ox in _axis_offsets(cx):
+                    other = ((ix + ox) % cx) + cx * (((iy + oy) % cy) + cy * ((iz + oz) % cz))
+                    first, length = offs[other], offs[other + 1] - offs[other]
+                    ends = numpy.cumsum(length)
+                    lo = 0
+                    while lo < somewhere:               # entries [lo, hi): at most _NEIGHBOURS_PAIRS_PER_STEP candidates
+                        base = int(ends[lo - 1]) if lo else 0
+                        hi = max(int(numpy.searchsorted(ends, base + _NEIGHBOURS_PAIRS_PER_STEP, side='right')), lo + 1)
+                        hi = min(hi, somewhere)
+                        ln = length[lo:hi]
+                        total = int(ln.sum())
+                        if total:
+                            # pairs sorted by i, then ascending j inside this cell: numpy.add.at adds them one after
+                            # the other in this order, so that together with the loops around it each entry's sum is
+                            # the sequential one of the definition
+                            i = numpy.repeat(numpy.arange(lo, hi, dtype=numpy.int64), ln)
+                            start = numpy.cumsum(ln) - ln
+                            j = numpy.repeat(first[lo:hi] - start, ln) + numpy.arange(total, dtype=numpy.int64)
+                            d2 = pair_distance2(xs[i], xs[j], vectors, dimensions)
+                            near = d2 < r2
+                            i, j = i[near], j[near]
+                            w = sph_weight(numpy.sqrt(d2[near]) * inv_h, kernel)
+                            numpy.add.at(a_n, i, w)
+                            numpy.add.at(a_m, i, m[j] * w)
+                            if a_v is not None:
+                                numpy.add.at(a_v, i, vol[j] * w)
+                        lo = hi
+        number, rho_sum = sigma * a_n, sigma * a_m
+        shepard = None if a_v is None else sigma * a_v
+    for v in (number, rho_sum, shepard):
+        if v is not None:
+            v[somewhere:] = 0.0
+    words = _sph_summary(n, somewhere, rows_sorted, number, rho_sum, shepard, rho, surface_below)
+    return KernelSums(h, SPH_KERNELS[kid], grid, dimensions, words, density is not None, surface_below, rows_sorted,
+                      cell_sorted, number, rho_sum, shepard)
+
+
+def _uniform_slength(lo, hi):
+    """``h=None``: the frame's smoothing length, if its smallest and largest value are equal."""
+    if not lo == hi:
+        raise ValueError("h=None needs one smoothing length for the frame: slength ranges from %r to %r (a per-particle "
+                         "smoothing length is not supported; pass h)" % (lo, hi))
+    return float(lo)
+
+
+def frame_kernel_sums(frame_or_arrays, h=None, kernel='wendland_c2', cells=None, where=None, types=None, domain=None,
+                      surface_below=None, box=None, dimensions=3):
+    """`sph_kernel_sums` of a frame's ``position``, ``mass`` and ``density`` over a selection: the host twin of
+    `HOOMDTrajectory.frame_kernel_sums_device`, which equals it exactly.  The selection -- `where_rows`, `domain_rows` or
+    their intersection, as `frame_neighbours` forms it -- is the list: both ``i`` and ``j`` come from it.  ``h=None``
+    takes the frame's ``slength`` if its smallest and largest value (over every row) are equal and raises ValueError if
+    they differ; a ``slength`` stored nowhere is the schema default 1.0.  A position that is stored nowhere puts every
+    row at the origin; without a ``mass`` array every mass is 1.0, without a ``density`` array there is no volume sum.
+    Returns a `KernelSums`."""
+    if hasattr(frame_or_arrays, 'particles'):
+        frame = frame_or_arrays
+        arrays = _particle_arrays(frame.particles)
+        types = frame.particles.types if types is None else types
+        box = frame.configuration.box if box is None else box
+        if frame.configuration.dimensions is not None:
+            dimensions = int(frame.configuration.dimensions)
+        N = int(frame.particles.N)
+    else:
+        arrays = dict((k, v) for k, v in frame_or_arrays.items() if v is not None)
+        if not arrays:
+            raise ValueError("arrays holds no per-particle array")
+        N = len(next(iter(arrays.values())))
+    if box is None:
+        raise ValueError("a kernel sum needs the box")
+    if h is None:
+        s = arrays.get('slength')
+        if s is None or numpy.asarray(s).size == 0:
+            h = float(_PARTICLE_FIELDS['slength'][2])
+        else:
+            s = numpy.asarray(s).reshape(-1).astype(numpy.float64)
+            s = s[s == s]                               # (`column_stats`' minimum and maximum: over what is no NaN)
+            h = _uniform_slength(float(s.min()) if s.size else numpy.inf, float(s.max()) if s.size else -numpy.inf)
+    rows = None
+    if where is not None:
+        rows = where_rows(arrays, where, types)
+    if domain is not None:
+        if 'position' not in arrays:
+            raise ValueError("a domain needs box and the 'position' array")
+        inside = domain_rows(arrays['position'], box, domain, dimensions)
+        rows = inside if rows is None else numpy.intersect1d(rows, inside)
+    position = arrays.get('position')
+    if position is None:
+        position = numpy.zeros((N, 3), dtype=numpy.float32)
+    return sph_kernel_sums(position, box, h, mass=arrays.get('mass'), density=arrays.get('density'), rows=rows, cells=cells,
+                           dimensions=dimensions, kernel=kernel, surface_below=surface_below)
+
+
 def frame_moments(frame_or_arrays, by_type=True, centre=True, where=None, types=None, domain=None, box=None, dimensions=3):
     """`particle_moments` of a frame's ``mass``, ``velocity``, ``energy``, ``position`` and ``typeid`` over a selection:
     the host twin of `HOOMDTrajectory.frame_moments_device`, which equals it exactly.
@@ -3750,6 +4050,61 @@ class HOOMDTrajectory(object):
             cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
             got = f.neighbours_device(f_pos, 'particles/position', box, r, grid, rows, cell, n=count, dimensions=dims,
                                       bins=bins, return_rows=return_rows)
+        finally:
+            f.wait_read()
+        return got
+
+    def frame_kernel_sums(self, idx, h=None, kernel='wendland_c2', cells=None, where=None, domain=None, surface_below=None):
+        """`frame_kernel_sums` of frame ``idx`` read through the host path: a `KernelSums`.  The definition of
+        `frame_kernel_sums_device`."""
+        return frame_kernel_sums(self[int(idx)], h, kernel=kernel, cells=cells, where=where, domain=domain,
+                                 surface_below=surface_below)
+
+    def frame_kernel_sums_device(self, idx, h=None, kernel='wendland_c2', cells=None, where=None, domain=None,
+                                 surface_below=None, return_rows=False):
+        """`frame_kernel_sums` of frame ``idx``, on the GPU: a `KernelSums` that equals ``frame_kernel_sums(idx, h,
+        ...)`` exactly -- every counter and index, every float bit for bit.
+
+        ``h=None`` takes the frame's ``slength`` if its smallest and largest value are equal
+        (`pgsd.fl.PGSDFile.chunk_stats_device` of the whole chunk; stored nowhere: the schema default 1.0) and raises
+        ValueError if they differ.  The selection is `frame_neighbours_device`'s and is the list both ``i`` and ``j``
+        come from; without one it is every row.  The list is sorted by cell over the staged position chunk with the
+        grid `neighbour_grid_for` gives for the support ``2h`` (or ``cells``, checked like the model's), and the pass
+        (`pgsd.fl.PGSDFile.sph_sums_device`) runs over the same staged chunk and the effective ``mass`` and ``density``
+        chunks; one that is stored nowhere costs nothing, its schema default stands for every row.
+        ``return_rows=True`` leaves ``rows``, ``cell``, ``number``, ``density`` and ``shepard`` in GPU memory on the
+        result; otherwise they are ``None`` and no per-particle data is kept.  One `wait_read` at the end releases the
+        staged chunks.  A frame whose position is stored nowhere has no chunk to search and raises ValueError.
+        """
+        idx = self._frame_index(idx)
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        _sph_kernel_id(kernel)
+        try:
+            if h is None:
+                f_h = self._effective_frame(idx, 'particles/slength', n_global)
+                if f_h is None or n_global == 0:
+                    h = float(_PARTICLE_FIELDS['slength'][2])
+                else:
+                    stats = f.chunk_stats_device(f_h, 'particles/slength')
+                    h = _uniform_slength(float(stats.min[0]), float(stats.max[0]))
+            h = _sph_length(h)
+            grid = _neighbour_grid(box, float(numpy.float64(2.0) * numpy.float64(h)), cells, dims)
+            if f_pos is None:
+                raise ValueError("frame_kernel_sums_device: the position is stored nowhere (every particle sits at the "
+                                 "origin)")
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
+            if rows is None:
+                rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
+            cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
+            chunks = []
+            for name in ('mass', 'density'):
+                fr = self._effective_frame(idx, 'particles/' + name, n_global)
+                chunks.append(None if fr is None else (fr, 'particles/' + name))
+            defaults = [float(_PARTICLE_FIELDS[name][2]) for name in ('mass', 'density')]
+            got = f.sph_sums_device(f_pos, 'particles/position', box, h, grid, rows, cell, n=count, mass=chunks[0],
+                                    density=chunks[1], defaults=defaults, dimensions=dims, kernel=kernel,
+                                    surface_below=surface_below, return_rows=return_rows)
         finally:
             f.wait_read()
         return got

@@ -9,8 +9,16 @@
 // waves deep.  Prints one JSON line: candidate pairs per second from the dispatch's own begin / end stamps, best and
 // median of the repetitions.
 //
+//
+// Variant `sph` ("SPH sums"): the per-candidate work of sph_pair_kernel<*, KERNEL, true> on register
+// values -- the same differences, fold, d2 and strict compare, and under the compare rr = sqrt(d2), q = rr * inv_h, the
+// kernel's polynomial and the three accumulations a_n += w, a_m += m_j * w, a_v += V_j * w, m_j and V_j formed in
+// registers.  The candidate turns round at a step that differs per lane, so that the about 1.7 % of the candidates that
+// lie inside the range are spread over the lanes' iterations as they are in a real list (a wave takes the branch in
+// nearly every iteration), instead of all lanes taking it together.
+//
 //   hipcc -O3 --offload-arch=gfx950 tools/labs/pair_ceiling.hip -o pair_ceiling
-//   ./pair_ceiling [reps=20] [iter=4096]
+//   ./pair_ceiling [reps=20] [iter=4096] [variant=census|sph_wendland|sph_spline]
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -18,6 +26,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #define CK(x)                                                                                 \
@@ -93,10 +102,128 @@ __global__ __launch_bounds__(256) void pair_ceiling_kernel(const Box b, uint32_t
     out_best[k] = best;
     }
 
+template<int KERNEL>
+__global__ __launch_bounds__(256) void sph_ceiling_kernel(const Box b, double inv_h, uint32_t iter, uint32_t* __restrict__ out_count,
+                                                          double* __restrict__ out_sums)
+    {
+#pragma clang fp contract(off)
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    const double Lx = b.v[0], Ly = b.v[1], Lz = b.v[2], xyLy = b.v[3], xzLz = b.v[4], yzLz = b.v[5];
+    const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5, r2 = b.r2;
+    const double xi0 = -hx + (double)(k & 1023) * (Lx / 1024.0), xi1 = -hy + (double)((k >> 10) & 1023) * (Ly / 1024.0);
+    const double xi2 = -hz + (double)(k >> 20) * (Lz / 4096.0);
+    double s0 = Lx / 977.0 + (double)(k & 63) * 1e-3, s1 = -Ly / 1931.0, s2 = Lz / 2953.0;
+    double xj0 = xi0, xj1 = xi1, xj2 = xi2;
+    const uint32_t phase = (k & 63) * 8; // the lane's own turning step
+    uint32_t count = 0;
+    double a_n = 0.0, a_m = 0.0, a_v = 0.0;
+    for (uint32_t j = 0; j < iter; j++)
+        {
+        const bool turn = ((j + phase) & 511) == 511;
+        s0 = turn ? -s0 : s0;
+        s1 = turn ? -s1 : s1;
+        s2 = turn ? -s2 : s2;
+        xj0 = xj0 + s0;
+        xj1 = xj1 + s1;
+        xj2 = xj2 + s2;
+        double dx = xj0 - xi0, dy = xj1 - xi1, dz = xj2 - xi2;
+            {
+            const bool up = dz >= hz, down = dz < -hz;
+            dx = up ? dx - xzLz : (down ? dx + xzLz : dx);
+            dy = up ? dy - yzLz : (down ? dy + yzLz : dy);
+            dz = up ? dz - Lz : (down ? dz + Lz : dz);
+            }
+            {
+            const bool up = dy >= hy, down = dy < -hy;
+            dx = up ? dx - xyLy : (down ? dx + xyLy : dx);
+            dy = up ? dy - Ly : (down ? dy + Ly : dy);
+            }
+            {
+            const bool up = dx >= hx, down = dx < -hx;
+            dx = up ? dx - Lx : (down ? dx + Lx : dx);
+            }
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 < r2)
+            {
+            const double rr = __builtin_sqrt(d2);
+            const double q = rr * inv_h;
+            double w;
+            if constexpr (KERNEL == 0)
+                {
+                const double t = 1.0 - 0.5 * q;
+                const double t2 = t * t;
+                w = (t2 * t2) * (2.0 * q + 1.0);
+                }
+            else
+                {
+                const double q2 = q * q;
+                const double u = 2.0 - q;
+                w = q < 1.0 ? (1.0 - 1.5 * q2) + 0.75 * (q2 * q) : 0.25 * ((u * u) * u);
+                }
+            const double mj = 1.0 + (double)(j & 7u), vj = mj * 0.5;
+            a_n = a_n + w;
+            a_m = a_m + mj * w;
+            a_v = a_v + vj * w;
+            count++;
+            }
+        }
+    out_count[k] = count;
+    out_sums[(size_t)k * 3 + 0] = a_n;
+    out_sums[(size_t)k * 3 + 1] = a_m;
+    out_sums[(size_t)k * 3 + 2] = a_v;
+    }
+
+static int run_sph(int reps, uint32_t iter, int kernel)
+    {
+    int cus = 256;
+    CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+    const uint32_t blocks = (uint32_t)cus * 8u;
+    const size_t lanes = (size_t)blocks * 256;
+    uint32_t* count;
+    double* sums;
+    CK(hipMalloc(&count, lanes * sizeof(uint32_t)));
+    CK(hipMalloc(&sums, lanes * 3 * sizeof(double)));
+    const Box b = {{40.0, 40.0, 40.0, 0.25 * 40.0, 0.125 * 40.0, -0.0625 * 40.0}, 0.197 * 0.197};
+    const double inv_h = 1.0 / (0.197 / 2);
+    hipEvent_t t0, t1;
+    CK(hipEventCreate(&t0));
+    CK(hipEventCreate(&t1));
+    std::vector<double> ms;
+    for (int r = 0; r < reps + 2; r++)
+        {
+        if (kernel == 0)
+            hipExtLaunchKernelGGL(sph_ceiling_kernel<0>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
+        else
+            hipExtLaunchKernelGGL(sph_ceiling_kernel<1>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
+        CK(hipGetLastError());
+        CK(hipEventSynchronize(t1));
+        float t = 0;
+        CK(hipEventElapsedTime(&t, t0, t1));
+        if (r >= 2) // (two warm-up launches)
+            ms.push_back(t);
+        }
+    std::vector<uint32_t> h(lanes);
+    CK(hipMemcpy(h.data(), count, lanes * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint64_t near = 0;
+    for (uint32_t c : h)
+        near += c;
+    std::sort(ms.begin(), ms.end());
+    const double pairs = (double)lanes * iter;
+    printf("{\"kind\": \"pair_ceiling\", \"variant\": \"%s\", \"lanes\": %zu, \"iter\": %u, \"pairs\": %.0f, \"near\": %llu, "
+           "\"best_ms\": %.4f, \"median_ms\": %.4f, \"worst_ms\": %.4f, \"pairs_per_s_best\": %.4g, \"pairs_per_s_median\": %.4g}\n",
+           kernel == 0 ? "sph_wendland" : "sph_spline", lanes, iter, pairs, (unsigned long long)near, ms.front(),
+           ms[ms.size() / 2], ms.back(), pairs / (ms.front() * 1e-3), pairs / (ms[ms.size() / 2] * 1e-3));
+    CK(hipFree(count));
+    CK(hipFree(sums));
+    return 0;
+    }
+
 int main(int argc, char** argv)
     {
     const int reps = argc > 1 ? atoi(argv[1]) : 20;
     const uint32_t iter = argc > 2 ? (uint32_t)atoi(argv[2]) : 4096u;
+    if (argc > 3 && std::string(argv[3]) != "census")
+        return run_sph(reps, iter, std::string(argv[3]) == "sph_spline" ? 1 : 0);
     int cus = 256;
     CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
     const uint32_t blocks = (uint32_t)cus * 8u; // 32 waves per compute unit: eight per SIMD
