@@ -1,5 +1,6 @@
 // pgsd_cells.hpp -- the two kernels every pass over a row list in cell order begins with (defined in pgsd_cells.hip,
-// launched from there, from pgsd_neighbours.hip and from pgsd_sph.hip): the check of the lists and the CSR offsets.  The refusal protocol is
+// launched from there, from pgsd_neighbours.hip, from pgsd_sph.hip and from pgsd_sph_gradients.hip): the check of the lists
+// and the CSR offsets.  The refusal protocol is
 // order_key_kernel's: a device flag word and a pinned one; every later kernel reads the device flag first and does
 // nothing where it is set, and clamps what it derives from the offsets to n.  Seen by the HIP compiler alone.
 #ifndef PGSD_CELLS_HPP

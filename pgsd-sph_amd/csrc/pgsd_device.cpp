@@ -212,6 +212,7 @@ int DevicePipeline::init()
         warm_cells_kernels();
         warm_neighbours_kernels();
         warm_sph_kernels();
+        warm_sph_gradients_kernels();
         int brc = compare_buffers();
         if (brc != PGSD_SUCCESS)
             return brc;
@@ -774,6 +775,17 @@ int device_pipeline_sph_sums(DevicePipeline* p, const ChunkRange* ranges, const 
     {
     std::string local;
     int rc = report(p, p->sph_sums(ranges, a, out_number, out_density, out_shepard, out_summary, &local), err, true);
+    if (rc != PGSD_SUCCESS && err && !local.empty())
+        *err = local; // the launcher's own message comes first
+    return rc;
+    }
+
+int device_pipeline_sph_gradients(DevicePipeline* p, const ChunkRange* ranges, const SphGradientsArgs& a, double* out_rate,
+                                  double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary,
+                                  std::string* err)
+    {
+    std::string local;
+    int rc = report(p, p->sph_gradients(ranges, a, out_rate, out_divergence, out_curl, out_normal, out_summary, &local), err, true);
     if (rc != PGSD_SUCCESS && err && !local.empty())
         *err = local; // the launcher's own message comes first
     return rc;

@@ -158,6 +158,8 @@ class DevicePipeline
                    double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2, std::string* why);
     int sph_sums(const ChunkRange* ranges, SphArgs a, double* out_number, double* out_density, double* out_shepard,
                  uint64_t* out_summary, std::string* why);
+    int sph_gradients(const ChunkRange* ranges, SphGradientsArgs a, double* out_rate, double* out_divergence, double* out_curl,
+                      double* out_normal, uint64_t* out_summary, std::string* why);
     int wait_read();
 
     // ---- accessors ----

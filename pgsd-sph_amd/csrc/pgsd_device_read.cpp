@@ -618,6 +618,27 @@ int DevicePipeline::sph_sums(const ChunkRange* ranges, SphArgs a, double* out_nu
                          { return launch_sph_sums(a, out_number, out_density, out_shepard, out_summary, m_res.pack_stream, err); });
     }
 
+// SPH kernel gradients: as sph_sums, and the velocity chunk where one is stored
+int DevicePipeline::sph_gradients(const ChunkRange* ranges, SphGradientsArgs a, double* out_rate, double* out_divergence,
+                                  double* out_curl, double* out_normal, uint64_t* out_summary, std::string* why)
+    {
+    const bool given[4] = {true, (a.present & 2u) != 0, (a.present & 4u) != 0, (a.present & 8u) != 0};
+    a.mass = a.density = a.velocity = nullptr;
+    const void** const all[4] = {&a.pos, &a.mass, &a.density, &a.velocity};
+    ChunkRange stored[4];
+    const void** slots[4];
+    size_t n_stored = 0;
+    for (int i = 0; i < 4; i++)
+        if (given[i])
+            {
+            stored[n_stored] = ranges[i];
+            slots[n_stored++] = all[i];
+            }
+    return staged_launch(stored, slots, n_stored, a.N, true, why, [&](std::string* err)
+                         { return launch_sph_gradients(a, out_rate, out_divergence, out_curl, out_normal, out_summary,
+                                                       m_res.pack_stream, err); });
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

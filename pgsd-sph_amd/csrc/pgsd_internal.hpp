@@ -515,6 +515,41 @@ inline void sph_sums_of_nothing(uint64_t* out_summary)
 // and a descending id refuse the call.  The staged rows stay until the next wait_read.
 int device_pipeline_sph_sums(DevicePipeline*, const ChunkRange* ranges, const SphArgs& a, double* out_number,
                              double* out_density, double* out_shepard, uint64_t* out_summary, std::string* err);
+// SPH kernel gradients (pgsd.hoomd.sph_kernel_gradients is the definition): per entry of a row list in cell order the
+// density rate, the velocity divergence and curl and the colour gradient over the entries inside the support 2h, in the
+// sums' order, and over the list the ranges of the two scalars and the largest curl and normal.  The grid, the support,
+// the list and the defaults are SphArgs' (surface and surface_below are not looked at).
+enum
+    {
+    SPHG_SUMMARY_WORDS = 13 // n, nowhere, not_finite, curl_at, curl_row, normal_at, normal_row, 2 x (min, max), curl2, normal2
+    };
+struct SphGradientsArgs : SphArgs
+    {
+    const void* velocity;  // the staged velocity chunk, N x 3, or null: the zero vector stands for every row
+    double G;              // -((sigma*inv_h)*inv_h), formed once on the host
+    uint32_t velocity_f64; // present bit 3: a velocity chunk is stored (ranges[3])
+    };
+// the summary of no entry
+inline void sph_gradients_of_nothing(uint64_t* out_summary)
+    {
+    const double lo = HUGE_VAL, hi = -HUGE_VAL, zero = 0.0;
+    std::fill(out_summary, out_summary + SPHG_SUMMARY_WORDS, (uint64_t)0);
+    out_summary[3] = out_summary[4] = out_summary[5] = out_summary[6] = SPH_NONE;
+    for (int s = 0; s < 2; s++)
+        {
+        memcpy(&out_summary[7 + 2 * s], &lo, sizeof(double));
+        memcpy(&out_summary[8 + 2 * s], &hi, sizeof(double));
+        memcpy(&out_summary[11 + s], &zero, sizeof(double));
+        }
+    }
+// stage the chunks that are present (ranges[0 .. 3]: position, mass, density, velocity; a.pos, a.mass, a.density and
+// a.velocity are filled in) -- or take them from what an earlier call left staged --, check the lists, sum on the GPU;
+// out_rate, out_divergence (device, a.n entries each, or null), out_curl, out_normal (device, a.n x 3, or null; the last
+// three are written with a.volume only); out_summary (host, 13 words) is written on success only, and so are the device
+// outputs; synchronous.  The refusals and the staging are device_pipeline_sph_sums'.
+int device_pipeline_sph_gradients(DevicePipeline*, const ChunkRange* ranges, const SphGradientsArgs& a, double* out_rate,
+                                  double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary,
+                                  std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

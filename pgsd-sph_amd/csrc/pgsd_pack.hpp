@@ -311,6 +311,15 @@ int launch_neighbours(const NeighboursArgs& a, const double* edges2, uint32_t* o
 int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, double* out_shepard, uint64_t* out_summary,
                     hipStream_t stream, std::string* err);
 
+// SPH kernel gradients (pgsd_sph_gradients.hip; SphGradientsArgs, the chunk pointers filled in): check, offsets,
+// compaction of the listed positions, masses, volumes and velocities, one lane per entry over the candidates in the sums'
+// order (pgsd_traverse.hpp), one workgroup for the ranges and the largest norms.  out_rate, out_divergence (device, a.n
+// entries), out_curl, out_normal (device, a.n x 3), each or null; out_summary (host, 13 words) is written on success only.
+// Synchronises `stream`; PGSD_ERROR_INVALID_ARGUMENT for an id that descends or lies outside [0, n_cells] and for an
+// entry >= a.N
+int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* out_divergence, double* out_curl,
+                         double* out_normal, uint64_t* out_summary, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);
@@ -371,6 +380,7 @@ void warm_order_kernels();
 void warm_cells_kernels();
 void warm_neighbours_kernels();
 void warm_sph_kernels();
+void warm_sph_gradients_kernels();
 
 // algorithmic traffic of one job: bytes that must be read (needed columns only, plus the
 // gather index) and chunk bytes written

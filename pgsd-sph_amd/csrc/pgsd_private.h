@@ -48,6 +48,10 @@
  *                     entry of a row list in cell order the SPH summation density, number density and Shepard sum over
  *                     the kernel support, in a defined order, and over the list their ranges, the largest deviation from
  *                     the stored density and the entries below a Shepard threshold)
+ *                     pgsd_sph_gradients_device (pgsd.fl's sph_gradients_device, behind pgsd.hoomd's
+ *                     frame_kernel_gradients_device: per entry of the same list, over the same support and in the same
+ *                     order, the density rate of the continuity equation, the velocity divergence and curl and the
+ *                     colour gradient, and over the list their ranges and the largest vorticity and surface normal)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -429,6 +433,47 @@ extern "C"
                              uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows, const int32_t* cell,
                              uint64_t n, double surface_below, double* out_number, double* out_density,
                              double* out_shepard, uint64_t* out_summary);
+
+    /* SPH kernel gradients (pgsd.hoomd.sph_kernel_gradients is the definition, and the results equal it exactly: every
+       counter and index, every float bit for bit -- a NaN is a NaN).  position, mass, density, defaults, vectors, h,
+       kernel, dimensions, cells, rows, cell and n are pgsd_sph_sums_device's, and so are the grid, the support 2h, r2,
+       inv_h, sigma, V_j = m_j / rho_j, "no volume" and THE ORDER of the candidates.  velocity: an N x 3 float32 or float64
+       chunk of its own element type, or NULL: the zero vector stands for every row.
+       On the host, once, in float64: G = -((sigma*inv_h)*inv_h).
+       ONE PAIR i <- j, float64 from the stored values (converted before any subtraction), no contraction: d = x_j - x_i
+       under the minimum image and d2 as pgsd_neighbours_device forms them; j contributes when d2 < r2, strictly; i itself
+       and coincident entries are candidates like any other (d = 0, so their terms are zero); rr = sqrt(d2), q = rr * inv_h;
+           Wendland C2    t = 1.0 - 0.5*q, F = -5.0 * ((t*t)*t)
+           cubic spline   if q < 1.0: F = 2.25*q - 3.0, else u = 2.0 - q, F = (-0.75*(u*u)) / q
+       e_k = F * d_k (grad_i W_ij = G * e), u_k = v_j[k] - v_i[k], dot = (u0*e0 + u1*e1) + u2*e2, c0 = e1*u2 - e2*u1,
+       c1 = e2*u0 - e0*u2, c2 = e0*u1 - e1*u0.  Eight accumulators per entry start at +0.0 and add in the defined order:
+       a_r += m_j * dot, a_d += V_j * dot, a_w[k] += V_j * c_k, a_c[k] += V_j * e_k.  After the last candidate
+       density_rate = -(G*a_r), divergence = G*a_d, curl[k] = G*a_w[k], normal[k] = G*a_c[k].  An entry with id n_cells is
+       nowhere: it contributes to nobody and all its values are +0.0.  With dimensions == 2 d_z is 0 and nothing else
+       differs.
+       Device outputs, float64, each optional (NULL): out_density_rate and out_divergence, n entries; out_curl and
+       out_normal, n x 3.  The last three are not written where there is no volume.
+       Host output, 13 words:
+           out_summary[0 .. 2]    n; the entries nowhere; the entries that have a cell and whose density_rate is NaN or
+                                  infinite
+           out_summary[3], [4]    the list position of the largest curl and its row; [5], [6] the same of the largest
+                                  normal; 0xFFFFFFFF without one
+           out_summary[7 .. 10]   as float64 bit patterns the minimum and the maximum of divergence and of density_rate
+                                  over the entries that have a cell, kept by strict compares from +inf and -inf: a NaN
+                                  never replaces a value (divergence without a volume: +inf, -inf)
+           out_summary[11], [12]  as float64 bit patterns the largest curl2 = (c0*c0 + c1*c1) + c2*c2 of the outputs and
+                                  the largest normal2 over the entries that have a cell, the smaller list position on a
+                                  tie, a NaN never; +0.0 without one
+       No float is summed over the list.  Staging, synchronisation and n == 0 are pgsd_sph_sums_device's.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), every output as it was: everything
+       pgsd_sph_sums_device refuses; a velocity chunk that is not three float32 or float64 columns or has another N than
+       position. */
+    int pgsd_sph_gradients_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                  const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
+                                  const struct pgsd_index_entry* density, const double defaults[2], const double vectors[6],
+                                  double h, uint32_t kernel, uint32_t dimensions, const uint32_t cells[3],
+                                  const uint32_t* rows, const int32_t* cell, uint64_t n, double* out_density_rate,
+                                  double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

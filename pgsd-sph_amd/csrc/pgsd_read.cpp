@@ -1036,19 +1036,16 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
-extern "C" int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
-                                    const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
-                                    const double defaults[2], const double vectors[6], double h, uint32_t kernel,
-                                    uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows, const int32_t* cell,
-                                    uint64_t n, double surface_below, double* out_number, double* out_density,
-                                    double* out_shepard, uint64_t* out_summary)
-    try
+// What pgsd_sph_sums_device and pgsd_sph_gradients_device share: every refusal of the former (and, for the latter, of a
+// velocity chunk), the ranges of the chunks that are stored (position, mass, density, velocity) and the arguments of the
+// pass -- the support, the grid, r2, inv_h, sigma and G, formed once in float64.  PGSD_SUCCESS: `ranges` and `a` are set.
+static int sph_arguments(const char* who, Impl* s, struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                         const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
+                         const struct pgsd_index_entry* velocity, const double defaults[2], const double vectors[6], double h,
+                         uint32_t kernel, uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
+                         const int32_t* cell, uint64_t n, double surface_below, ChunkRange ranges[4], SphGradientsArgs& a)
     {
-    static const char* who = "pgsd_sph_sums_device";
-    Impl* s = impl_of(handle);
-    if (!s || !position || !defaults || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell)))
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
+    const auto refuse = [who](const std::string& msg)
     {
         set_last_error(std::string(who) + ": " + msg);
         return PGSD_ERROR_INVALID_ARGUMENT;
@@ -1068,10 +1065,8 @@ extern "C" int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgs
         return refuse("the smoothing length must be finite and positive");
     if (kernel != SPH_WENDLAND_C2 && kernel != SPH_CUBIC_SPLINE)
         return refuse("the kernel is 0 (Wendland C2) or 1 (cubic spline)");
-    ChunkRange ranges[3];
-    memset(ranges, 0, sizeof(ranges));
-    SphArgs a;
-    memset(&a, 0, sizeof(a));
+    memset(ranges, 0, 4 * sizeof(ChunkRange));
+    a = SphGradientsArgs();
     const struct pgsd_index_entry* columns[2] = {mass, density};
     for (int i = 0; i < 2; i++)
         {
@@ -1090,6 +1085,21 @@ extern "C" int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgs
             return rc;
         (i ? a.density_f64 : a.mass_f64) = m.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
         a.present |= 2u << i;
+        }
+    if (velocity)
+        {
+        const pgsd_index_entry m = *velocity;
+        if (m.type != PGSD_TYPE_FLOAT && m.type != PGSD_TYPE_DOUBLE)
+            return refuse("the velocity chunk holds float32 or float64 elements");
+        if (m.M != 3)
+            return refuse("the velocity chunk has 3 columns");
+        if (m.N != c.N)
+            return refuse("the velocity chunk and the position chunk differ in their number of rows");
+        int rc = whole_chunk_range(s, handle, m, &ranges[3].file_offset, &ranges[3].bytes);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        a.velocity_f64 = m.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+        a.present |= 8u;
         }
     // the range of the search is the support 2h; the grid is checked as pgsd_neighbours_device checks its own:
     // pgsd.hoomd.ghost_fractions and cell_grid_for, from the tilt factors the vectors hold
@@ -1150,16 +1160,81 @@ extern "C" int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgs
     a.dims = dimensions;
     a.f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
     a.kernel = kernel;
+    a.G = -((a.sigma * a.inv_h) * a.inv_h);
+    return PGSD_SUCCESS;
+    }
+
+extern "C" int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                    const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
+                                    const double defaults[2], const double vectors[6], double h, uint32_t kernel,
+                                    uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows, const int32_t* cell,
+                                    uint64_t n, double surface_below, double* out_number, double* out_density,
+                                    double* out_shepard, uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_sph_sums_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !defaults || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    ChunkRange ranges[4];
+    SphGradientsArgs g;
+    int rc = sph_arguments(who, s, handle, position, mass, density, nullptr, defaults, vectors, h, kernel, dimensions, cells,
+                           rows, cell, n, surface_below, ranges, g);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    const SphArgs a = g;
     if (n == 0)
         {
         sph_sums_of_nothing(out_summary);
         return PGSD_SUCCESS;
         }
-    if (c.N == 0)
-        return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
+    if (a.N == 0)
+        {
+        set_last_error(std::string(who) + ": an entry of the row list lies outside the chunks (nothing was computed)");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
     // (the launcher writes the outputs on success only, behind its last check)
     return reduction_call(who, "SPH kernel sums: ", [&](std::string* err)
                           { return device_pipeline_sph_sums(s->dev, ranges, a, out_number, out_density, out_shepard, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_sph_gradients_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                         const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
+                                         const struct pgsd_index_entry* density, const double defaults[2],
+                                         const double vectors[6], double h, uint32_t kernel, uint32_t dimensions,
+                                         const uint32_t cells[3], const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                         double* out_density_rate, double* out_divergence, double* out_curl,
+                                         double* out_normal, uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_sph_gradients_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !defaults || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    ChunkRange ranges[4];
+    SphGradientsArgs a;
+    int rc = sph_arguments(who, s, handle, position, mass, density, velocity, defaults, vectors, h, kernel, dimensions, cells,
+                           rows, cell, n, NAN, ranges, a);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (n == 0)
+        {
+        sph_gradients_of_nothing(out_summary);
+        return PGSD_SUCCESS;
+        }
+    if (a.N == 0)
+        {
+        set_last_error(std::string(who) + ": an entry of the row list lies outside the chunks (nothing was computed)");
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "SPH kernel gradients: ", [&](std::string* err)
+                          { return device_pipeline_sph_gradients(s->dev, ranges, a, out_density_rate, out_divergence, out_curl,
+                                                                 out_normal, out_summary, err); });
     }
 catch (...)
     {

@@ -1,0 +1,95 @@
+// pgsd_traverse.hpp -- the traversal of the candidates of one entry of a row list in cell order, as one inlined device
+// template over a per-candidate functor: the cells of pgsd.hoomd.sph_kernel_sums' defined order (oz over the offsets of
+// the z axis -- {0} at one cell, {0, +1} at two, {-1, 0, +1} otherwise --, inside it oy, inside it ox, the cell ((ix+ox) %
+// cx, (iy+oy) % cy, (iz+oz) % cz), inside a cell ascending list position), taken as at most two cyclic x-runs per (y, z)
+// row of the grid; the clamping of what comes from the offsets to n; HOOMD's single-shift minimum image in float64
+// without contraction (pgsd.hoomd.pair_displacement) and the strict test d2 < r2.  The functor receives (j, dx, dy, dz, d2)
+// of every candidate that passes, in the defined order, and is inlined with what it captures: accumulators it holds by
+// reference stay in registers.  Used by pgsd_sph_gradients.hip; pgsd_neighbours.hip and pgsd_sph.hip still carry their own
+// copies of this loop.  Seen by the HIP compiler alone.
+#ifndef PGSD_TRAVERSE_HPP
+#define PGSD_TRAVERSE_HPP
+
+#include "pgsd_kernels.hpp"
+
+namespace pgsd_amd
+    {
+// what the traversal reads besides the compacted positions and the offsets
+struct TraverseGrid
+    {
+    double vectors[6]; // Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz
+    double r2;
+    uint32_t cells[3];
+    uint32_t dims;
+    };
+
+// xs: n x 3 compacted positions of element type elem_t; offs: n_cells + 1 CSR offsets; k: the entry, c: its cell id,
+// inside [0, n_cells)
+template<typename elem_t, typename Functor>
+__device__ __forceinline__ void traverse_candidates(const elem_t* __restrict__ x, const uint32_t* __restrict__ offs, uint64_t n,
+                                                    uint32_t k, uint32_t c, const TraverseGrid& g, Functor&& each)
+    {
+#pragma clang fp contract(off)
+    const double xi0 = (double)x[(size_t)k * 3 + 0], xi1 = (double)x[(size_t)k * 3 + 1], xi2 = (double)x[(size_t)k * 3 + 2];
+    const double Lx = g.vectors[0], Ly = g.vectors[1], Lz = g.vectors[2];
+    const double xyLy = g.vectors[3], xzLz = g.vectors[4], yzLz = g.vectors[5];
+    const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5; // (exact halves)
+    const double r2 = g.r2;
+    const bool three = g.dims != 2;
+    const int cx = (int)g.cells[0], cy = (int)g.cells[1], cz = (int)g.cells[2];
+    const int ix = (int)(c % (uint32_t)cx), iy = (int)((c / (uint32_t)cx) % (uint32_t)cy);
+    const int iz = (int)(c / ((uint32_t)cx * (uint32_t)cy));
+    // the x cells in the defined order: `take` cells cyclically from `from`, as run 0 [from, b0) and run 1 [0, b1)
+    const int take = min(3, cx);
+    const int from = cx == 1 ? 0 : (cx == 2 ? ix : (ix == 0 ? cx - 1 : ix - 1));
+    const int b0 = min(from + take, cx), b1 = max(from + take - cx, 0);
+    const int ylo = cy >= 3 ? -1 : 0, yhi = cy >= 2 ? 1 : 0;
+    const int zlo = cz >= 3 ? -1 : 0, zhi = cz >= 2 ? 1 : 0;
+    for (int oz = zlo; oz <= zhi; oz++)
+        {
+        int wz = iz + oz;
+        wz = wz < 0 ? wz + cz : (wz >= cz ? wz - cz : wz);
+        for (int oy = ylo; oy <= yhi; oy++)
+            {
+            int wy = iy + oy;
+            wy = wy < 0 ? wy + cy : (wy >= cy ? wy - cy : wy);
+            const uint32_t row0 = (uint32_t)cx * ((uint32_t)wy + (uint32_t)cy * (uint32_t)wz);
+            for (int run = 0; run < 2; run++)
+                {
+                const int ra = run ? 0 : from, rb = run ? b1 : b0;
+                if (rb <= ra)
+                    continue;
+                const uint32_t lo = (uint32_t)min((uint64_t)offs[row0 + (uint32_t)ra], n);
+                const uint32_t hi = (uint32_t)min((uint64_t)offs[row0 + (uint32_t)rb], n);
+                for (uint32_t j = lo; j < hi; j++)
+                    {
+                    const double xj0 = (double)x[(size_t)j * 3 + 0], xj1 = (double)x[(size_t)j * 3 + 1];
+                    double dx = xj0 - xi0, dy = xj1 - xi1, dz = 0.0;
+                    if (three)
+                        {
+                        dz = (double)x[(size_t)j * 3 + 2] - xi2;
+                        const bool up = dz >= hz, down = dz < -hz;
+                        dx = up ? dx - xzLz : (down ? dx + xzLz : dx);
+                        dy = up ? dy - yzLz : (down ? dy + yzLz : dy);
+                        dz = up ? dz - Lz : (down ? dz + Lz : dz);
+                        }
+                        {
+                        const bool up = dy >= hy, down = dy < -hy;
+                        dx = up ? dx - xyLy : (down ? dx + xyLy : dx);
+                        dy = up ? dy - Ly : (down ? dy + Ly : dy);
+                        }
+                        {
+                        const bool up = dx >= hx, down = dx < -hx;
+                        dx = up ? dx - Lx : (down ? dx + Lx : dx);
+                        }
+                    const double d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (d2 < r2)
+                        each(j, dx, dy, dz, d2);
+                    }
+                }
+            }
+        }
+    }
+    } // namespace pgsd_amd
+
+#endif

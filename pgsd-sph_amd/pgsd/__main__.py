@@ -27,7 +27,11 @@
            must be uniform): the search grid and the entries, the range of the summation density, its largest deviation
            from the stored density with the row, the range of the Shepard sum and -- with ``--surface S`` -- the entries
            whose Shepard sum is below S (``--kernel wendland_c2|cubic_spline``, ``--types``;
-           ``pgsd.hoomd.frame_kernel_sums`` on the host: no GPU).
+           ``pgsd.hoomd.frame_kernel_sums`` on the host: no GPU);
+           ``--sph-gradients [H]`` adds the SPH kernel gradients for the smoothing length H (without H: the frame's
+           uniform ``slength``): the search grid and the entries, the ranges of the velocity divergence and of the
+           density rate of the continuity equation and the largest vorticity and surface normal, each with its row
+           (``--kernel``, ``--types``; ``pgsd.hoomd.frame_kernel_gradients`` on the host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -100,6 +104,28 @@ def _cmd_info(args):
         _print_neighbours(args, frame)
     if args.sph is not None:
         _print_sph(args, frame)
+    if args.sph_gradients is not None:
+        _print_sph_gradients(args, frame)
+
+
+def _print_sph_gradients(args, frame):
+    """``info --sph-gradients``: `pgsd.hoomd.frame_kernel_gradients` of one frame, on the host."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_kernel_gradients(traj[frame], None if args.sph_gradients < 0 else args.sph_gradients,
+                                         kernel=args.kernel, where=where)
+    print("SPH gradients of frame %d with h = %r (%s) over %d x %d x %d cells%s:"
+          % ((frame, m.h, m.kernel) + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  entries:      %d  nowhere: %d" % (m.n, m.nowhere))
+    if m.n > m.nowhere:
+        if m.volume:
+            print("  divergence:   smallest %r  largest %r" % (m.divergence_min, m.divergence_max))
+        print("  density rate: smallest %r  largest %r  not finite: %d" % (m.density_rate_min, m.density_rate_max, m.not_finite))
+        if m.curl2 is not None:
+            print("  vorticity:    largest %r at row %d" % (m.curl2 ** 0.5, m.curl_row))
+        if m.normal2 is not None:
+            print("  normal:       largest %r at row %d" % (m.normal2 ** 0.5, m.normal_row))
 
 
 def _print_sph(args, frame):
@@ -361,8 +387,11 @@ def main(argv=None):
     p.add_argument('--sph', type=float, nargs='?', const=-1.0, default=None, metavar='H',
                    help="print the SPH kernel sums for the smoothing length H (without H: the frame's uniform slength): "
                         "grid, entries, density range, largest deviation from the stored density, Shepard range")
+    p.add_argument('--sph-gradients', type=float, nargs='?', const=-1.0, default=None, metavar='H',
+                   help="print the SPH kernel gradients for the smoothing length H (without H: the frame's uniform "
+                        "slength): grid, entries, divergence and density-rate ranges, largest vorticity and normal")
     p.add_argument('--kernel', type=str, default='wendland_c2', choices=('wendland_c2', 'cubic_spline'),
-                   help="the kernel of --sph (default: wendland_c2)")
+                   help="the kernel of --sph and --sph-gradients (default: wendland_c2)")
     p.add_argument('--surface', type=float, default=None, metavar='S',
                    help="with --sph: count the entries whose Shepard sum is below S (the free surface)")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")

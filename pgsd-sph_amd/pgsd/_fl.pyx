@@ -484,6 +484,11 @@ def _device_head(x, k):
     return x.view(shape=(int(k),)) if isinstance(x, DeviceBuffer) else x[:int(k)]
 
 
+def _device_head_rows(x, k):
+    """The first ``k`` rows of a dense 2-D array in GPU memory, as a view."""
+    return x.view(shape=(int(k),) + tuple(x.shape[1:])) if isinstance(x, DeviceBuffer) else x[:int(k)]
+
+
 def _device_at(x, i):
     """``x[i]`` of a dense array in GPU memory, as a view."""
     if not isinstance(x, DeviceBuffer):
@@ -2044,6 +2049,98 @@ cdef class PGSDFile:
             got.rows, got.cell = _device_head(rows, count), _device_head(cell, count)
             got.number, got.density = _device_head(out_number, count), _device_head(out_rho, count)
             got.shepard = _device_head(out_shepard, count) if volume else None
+        return got
+
+    def sph_gradients_device(self, frame, name, box, h, cells, rows, cell, n=None, velocity=None, mass=None, density=None,
+                             defaults=None, dimensions=3, kernel='wendland_c2', return_rows=False):
+        """The SPH kernel gradients of a row list in cell order on the GPU: the density rate of the continuity equation,
+        the velocity divergence and curl and the colour gradient (the surface normal) over the kernel support ``2h``,
+        in the order that is part of their definition.
+
+        Args:
+            frame, name, box, h, cells, rows, cell, n, mass, density, defaults, dimensions, kernel: as
+                :meth:`sph_sums_device` takes them.
+            velocity: ``(frame, name)`` of an N x 3 float32 or float64 chunk, or ``None``: stored nowhere, every velocity
+                is the zero vector.
+            return_rows (bool): keep the per-entry results in GPU memory.
+
+        Returns:
+            A :class:`pgsd.hoomd.KernelGradients`: exactly :func:`pgsd.hoomd.sph_kernel_gradients` of the same list --
+            every counter and index, every float bit for bit.  With ``return_rows`` its ``rows`` and ``cell`` are the
+            arguments, ``density_rate`` and ``divergence`` are float64 arrays of ``n`` entries and ``curl`` and ``normal``
+            of ``n x 3`` in GPU memory (the last three ``None`` without a volume); otherwise the six are ``None``.  The
+            chunks are staged whole unless an earlier call left them staged; the staged rows are kept until the next
+            :meth:`wait_read`.  What the library refuses (:c:func:`pgsd_sph_gradients_device`) raises ValueError and
+            computes nothing.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry, e_velocity, e_mass, e_density
+        cdef const C.pgsd_index_entry* p_velocity = NULL
+        cdef const C.pgsd_index_entry* p_mass = NULL
+        cdef const C.pgsd_index_entry* p_density = NULL
+        self._entry(frame, name, &entry)
+        if velocity is not None:
+            self._entry(velocity[0], velocity[1], &e_velocity)
+            p_velocity = &e_velocity
+        if mass is not None:
+            self._entry(mass[0], mass[1], &e_mass)
+            p_mass = &e_mass
+        if density is not None:
+            self._entry(density[0], density[1], &e_density)
+            p_density = &e_density
+        c_box = numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6]
+        if c_box.shape[0] != 6:
+            raise ValueError("box must hold 6 values")
+        c_vectors = numpy.ascontiguousarray(_hoomd.box_vectors(c_box), dtype=numpy.float64)
+        grid = [int(v) for v in cells]
+        if len(grid) != 3 or any(not 0 <= v < (1 << 32) for v in grid):
+            raise ValueError("sph_gradients_device: cells holds three counts, each 1 to 1024")
+        c_cells = numpy.array(grid, dtype=numpy.uint32)
+        if kernel not in _hoomd.SPH_KERNELS:
+            raise ValueError("sph_gradients_device: the kernel is one of %s: %r" % (', '.join(_hoomd.SPH_KERNELS), kernel))
+        c_defaults = numpy.ascontiguousarray(
+            numpy.array([1.0, float('nan')] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+        if c_defaults.shape[0] != 2:
+            raise ValueError("sph_gradients_device: defaults holds a mass and a density")
+        volume = density is not None or c_defaults[1] == c_defaults[1]
+        c_rows, count = _row_list("sph_gradients_device", rows, n)
+        c_cell, _ = _row_list("sph_gradients_device", cell, count)
+        summary = numpy.zeros(13, dtype=numpy.uint64)
+        cdef uintptr_t p_rate = 0, p_divergence = 0, p_curl = 0, p_normal = 0
+        out_rate = out_divergence = out_curl = out_normal = None
+        if return_rows:
+            device = self.pipeline_device()
+            out_rate = _device_empty((max(count, 1),), numpy.float64, device)
+            p_rate = out_rate.data_ptr()
+            if volume:
+                out_divergence = _device_empty((max(count, 1),), numpy.float64, device)
+                out_curl = _device_empty((max(count, 1), 3), numpy.float64, device)
+                out_normal = _device_empty((max(count, 1), 3), numpy.float64, device)
+                p_divergence, p_curl, p_normal = out_divergence.data_ptr(), out_curl.data_ptr(), out_normal.data_ptr()
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef uint32_t c_kernel = _hoomd.SPH_KERNELS.index(kernel)
+        cdef double c_h = float(h)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_sph_gradients_device(&self._handle, &entry, p_velocity, p_mass, p_density,
+                                                 <const double*>p_defaults, <const double*>p_vectors, c_h, c_kernel, c_dims,
+                                                 <const uint32_t*>p_cells, <const uint32_t*>p_rows, <const int32_t*>p_cell,
+                                                 c_n, <double*>p_rate, <double*>p_divergence, <double*>p_curl,
+                                                 <double*>p_normal, <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("sph_gradients_device", retval, "refused", self._name, err)
+        got = _hoomd.KernelGradients(c_h, kernel, grid, int(dimensions), summary, volume)
+        if return_rows:
+            got.rows, got.cell = _device_head(rows, count), _device_head(cell, count)
+            got.density_rate = _device_head(out_rate, count)
+            if volume:
+                got.divergence = _device_head(out_divergence, count)
+                got.curl, got.normal = _device_head_rows(out_curl, count), _device_head_rows(out_normal, count)
         return got
 
     def frame_displacements_device(self, chunks, vectors_a, vectors_b, minimum_image=False, dimensions=3, type0=0,

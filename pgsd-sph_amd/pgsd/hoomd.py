@@ -1477,6 +1477,17 @@ def pair_distance2(xi, xj, vectors, dimensions=3):
     One shift per axis and no division: this is not the ``rint(d / L)`` fold of `displacement_vectors`.  It has HOOMD's
     range of validity -- a stored position more than one image outside the box is not folded fully, and its pairs are
     whatever this formula gives, here and on the GPU alike."""
+    dx, dy, dz = pair_displacement(xi, xj, vectors, dimensions)
+    with numpy.errstate(over='ignore', invalid='ignore'):
+        return (dx * dx + dy * dy) + dz * dz
+
+
+def pair_displacement(xi, xj, vectors, dimensions=3):
+    """The displacement ``(dx, dy, dz)`` of the pair ``i -> j`` -- ``x_j - x_i`` under HOOMD's single-shift minimum image
+    -- with exactly `pair_distance2`'s arithmetic, which is ``(dx*dx + dy*dy) + dz*dz`` of it: float64 throughout, float32
+    positions converted exactly before the subtraction, z folded first (only if ``dimensions == 3``), then y, then x,
+    one shift per axis; with ``dimensions == 2`` ``dz`` is 0 and z is never looked at.  The arithmetic of one pair of
+    `sph_kernel_gradients` and of its GPU kernel."""
     dimensions = int(dimensions)
     if dimensions not in (2, 3):
         raise ValueError("dimensions must be 2 or 3")
@@ -1504,7 +1515,7 @@ def pair_distance2(xi, xj, vectors, dimensions=3):
         h = v[0] / 2
         up, down = dx >= h, dx < -h
         dx = numpy.where(up, dx - v[0], numpy.where(down, dx + v[0], dx))
-        return (dx * dx + dy * dy) + dz * dz
+        return dx, dy, dz
 
 
 def _neighbour_range(r):
@@ -1922,6 +1933,90 @@ def _sph_summary(n, somewhere, rows_sorted, number, density, shepard, rho, surfa
     return words
 
 
+def _sph_asked(box, h, cells, dimensions, kernel):
+    """``(dimensions, h, kernel id, support 2h, grid)`` of `sph_kernel_sums` and `sph_kernel_gradients`, checked."""
+    dimensions = int(dimensions)
+    h = _sph_length(h)
+    kid = _sph_kernel_id(kernel)
+    support = float(numpy.float64(2.0) * numpy.float64(h))
+    return dimensions, h, kid, support, _neighbour_grid(box, support, cells, dimensions)
+
+
+class _SphList(object):
+    """What `sph_kernel_sums` and `sph_kernel_gradients` share ahead of their pair loops: the list in cell order
+    (``rows_sorted``, ``cell_sorted``, ``n``, ``somewhere``: the entries that have a cell come first), the CSR offsets,
+    the compacted float64 positions ``xs`` and columns (``None``: not given), ``vectors``, ``r2``, ``inv_h``, ``sigma``."""
+    __slots__ = ('dimensions', 'grid', 'n', 'somewhere', 'rows_sorted', 'cell_sorted', 'offs', 'xs', 'columns', 'vectors',
+                 'r2', 'inv_h', 'sigma')
+
+
+def _sph_list(asked, position, box, rows, columns):
+    """``columns``: ``(name, values or None, width)`` each; a column comes back as float64, in list order."""
+    t = _SphList()
+    t.dimensions, h, kid, support, t.grid = asked
+    p = numpy.asarray(position)
+    p = p.reshape(-1, 3) if p.size else numpy.zeros((0, 3), dtype=numpy.float32)
+    if p.dtype not in (numpy.float32, numpy.float64):
+        raise ValueError("position holds float32 or float64 values")
+    given = []
+    for name, v, width in columns:
+        if v is not None:
+            v = numpy.asarray(v)
+            if v.dtype not in (numpy.float32, numpy.float64) or v.size != p.shape[0] * width:
+                raise ValueError("%s holds %s float32 or float64 value%s per row of position"
+                                 % (name, 'one' if width == 1 else 'three', '' if width == 1 else 's'))
+            v = (v.reshape(-1) if width == 1 else v.reshape(-1, width)).astype(numpy.float64)
+        given.append(v)
+    rows = numpy.arange(p.shape[0], dtype=numpy.int64) if rows is None else rows
+    t.rows_sorted, t.cell_sorted, _ = cell_order(p, box, rows, t.grid, t.dimensions)
+    t.n = t.rows_sorted.shape[0]
+    n_cells = t.grid[0] * t.grid[1] * t.grid[2]
+    t.vectors = box_vectors(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+    t.r2 = numpy.float64(support) * numpy.float64(support)
+    t.inv_h = numpy.float64(1.0) / numpy.float64(h)
+    t.sigma = numpy.float64(sph_sigma(SPH_KERNELS[kid], h, t.dimensions))
+    t.offs = cell_offsets(t.cell_sorted, n_cells)
+    at = t.rows_sorted.astype(numpy.int64)
+    t.xs = p[at].astype(numpy.float64)
+    t.columns = [None if v is None else v[at] for v in given]
+    t.somewhere = int(t.offs[n_cells])                   # the entries that have a cell come first
+    return t
+
+
+def _sph_near_pairs(t):
+    """The pairs of a `_SphList` inside the support, in THE ORDER of `sph_kernel_sums`: steps of ``(i, j, (dx, dy, dz),
+    d2)`` arrays, the pairs of a step sorted by ``i`` and, inside one candidate cell, by ascending ``j``.  `numpy.add.at`
+    adds the pairs of a step one after the other, so that together with the order of the steps each entry's sum is the
+    sequential one of the definition."""
+    cx, cy, cz = t.grid
+    offs, xs, somewhere = t.offs, t.xs, t.somewhere
+    ids = t.cell_sorted[:somewhere]
+    ix, iy, iz = ids % cx, (ids // cx) % cy, ids // (cx * cy)
+    for oz in _axis_offsets(cz):
+        for oy in _axis_offsets(cy):
+            for ox in _axis_offsets(cx):
+                other = ((ix + ox) % cx) + cx * (((iy + oy) % cy) + cy * ((iz + oz) % cz))
+                first, length = offs[other], offs[other + 1] - offs[other]
+                ends = numpy.cumsum(length)
+                lo = 0
+                while lo < somewhere:               # entries [lo, hi): at most _NEIGHBOURS_PAIRS_PER_STEP candidates
+                    base = int(ends[lo - 1]) if lo else 0
+                    hi = max(int(numpy.searchsorted(ends, base + _NEIGHBOURS_PAIRS_PER_STEP, side='right')), lo + 1)
+                    hi = min(hi, somewhere)
+                    ln = length[lo:hi]
+                    total = int(ln.sum())
+                    if total:
+                        i = numpy.repeat(numpy.arange(lo, hi, dtype=numpy.int64), ln)
+                        start = numpy.cumsum(ln) - ln
+                        j = numpy.repeat(first[lo:hi] - start, ln) + numpy.arange(total, dtype=numpy.int64)
+                        d = pair_displacement(xs[i], xs[j], t.vectors, t.dimensions)
+                        with numpy.errstate(invalid='ignore', over='ignore'):
+                            d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+                            near = d2 < t.r2
+                        yield i[near], j[near], (d[0][near], d[1][near], d[2][near]), d2[near]
+                    lo = hi
+
+
 def sph_kernel_sums(position, box, h, mass=None, density=None, rows=None, cells=None, dimensions=3, kernel='wendland_c2',
                     surface_below=None):
     """The SPH kernel sums of a row list: per entry ``i`` the number density ``sigma * sum_j W_ij``, the summation density
@@ -1956,79 +2051,28 @@ def sph_kernel_sums(position, box, h, mass=None, density=None, rows=None, cells=
 
     Returns a `KernelSums`.
     """
-    dimensions = int(dimensions)
-    h = _sph_length(h)
-    kid = _sph_kernel_id(kernel)
-    support = float(numpy.float64(2.0) * numpy.float64(h))
-    grid = _neighbour_grid(box, support, cells, dimensions)
+    asked = _sph_asked(box, h, cells, dimensions, kernel)
     if surface_below is not None:
         surface_below = float(surface_below)
         if surface_below != surface_below:
             raise ValueError("surface_below is a number or None")
-    p = numpy.asarray(position)
-    p = p.reshape(-1, 3) if p.size else numpy.zeros((0, 3), dtype=numpy.float32)
-    if p.dtype not in (numpy.float32, numpy.float64):
-        raise ValueError("position holds float32 or float64 values")
-    columns = []
-    for name, v in (('mass', mass), ('density', density)):
-        if v is not None:
-            v = numpy.asarray(v)
-            if v.dtype not in (numpy.float32, numpy.float64) or v.size != p.shape[0]:
-                raise ValueError("%s holds one float32 or float64 value per row of position" % name)
-            v = v.reshape(-1).astype(numpy.float64)
-        columns.append(v)
-    mass, density = columns
-    rows = numpy.arange(p.shape[0], dtype=numpy.int64) if rows is None else rows
-    rows_sorted, cell_sorted, _ = cell_order(p, box, rows, grid, dimensions)
-    n = rows_sorted.shape[0]
-    cx, cy, cz = grid
-    n_cells = cx * cy * cz
-    vectors = box_vectors(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
-    r2 = numpy.float64(support) * numpy.float64(support)
-    inv_h = numpy.float64(1.0) / numpy.float64(h)
-    sigma = numpy.float64(sph_sigma(kernel, h, dimensions))
-    offs = cell_offsets(cell_sorted, n_cells)
-    at = rows_sorted.astype(numpy.int64)
-    xs = p[at].astype(numpy.float64)
-    m = numpy.ones(n, dtype=numpy.float64) if mass is None else mass[at]
-    rho = None if density is None else density[at]
+    t = _sph_list(asked, position, box, rows, (('mass', mass, 1), ('density', density, 1)))
+    dimensions, h, kid, grid = asked[0], asked[1], asked[2], asked[4]
+    n, sigma, rows_sorted, cell_sorted, somewhere = t.n, t.sigma, t.rows_sorted, t.cell_sorted, t.somewhere
+    mass, density = t.columns
+    m = numpy.ones(n, dtype=numpy.float64) if mass is None else mass
+    rho = density
     with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
         vol = None if rho is None else m / rho
     a_n, a_m = numpy.zeros(n, dtype=numpy.float64), numpy.zeros(n, dtype=numpy.float64)
     a_v = None if vol is None else numpy.zeros(n, dtype=numpy.float64)
-    somewhere = int(offs[n_cells])                       # the entries that have a cell come first
-    ids = cell_sorted[:somewhere]
-    ix, iy, iz = ids % cx, (ids // cx) % cy, ids // (cx * cy)
     with numpy.errstate(invalid='ignore', over='ignore'):
-        for oz in _axis_offsets(cz):
-            for oy in _axis_offsets(cy):
-                for ox in _axis_offsets(cx):
-                    other = ((ix + ox) % cx) + cx * (((iy + oy) % cy) + cy * ((iz + oz) % cz))
-                    first, length = offs[other], offs[other + 1] - offs[other]
-                    ends = numpy.cumsum(length)
-                    lo = 0
-                    while lo < somewhere:               # entries [lo, hi): at most _NEIGHBOURS_PAIRS_PER_STEP candidates
-                        base = int(ends[lo - 1]) if lo else 0
-                        hi = max(int(numpy.searchsorted(ends, base + _NEIGHBOURS_PAIRS_PER_STEP, side='right')), lo + 1)
-                        hi = min(hi, somewhere)
-                        ln = length[lo:hi]
-                        total = int(ln.sum())
-                        if total:
-                            # pairs sorted by i, then ascending j inside this cell: numpy.add.at adds them one after
-                            # the other in this order, so that together with the loops around it each entry's sum is
-                            # the sequential one of the definition
-                            i = numpy.repeat(numpy.arange(lo, hi, dtype=numpy.int64), ln)
-                            start = numpy.cumsum(ln) - ln
-                            j = numpy.repeat(first[lo:hi] - start, ln) + numpy.arange(total, dtype=numpy.int64)
-                            d2 = pair_distance2(xs[i], xs[j], vectors, dimensions)
-                            near = d2 < r2
-                            i, j = i[near], j[near]
-                            w = sph_weight(numpy.sqrt(d2[near]) * inv_h, kernel)
-                            numpy.add.at(a_n, i, w)
-                            numpy.add.at(a_m, i, m[j] * w)
-                            if a_v is not None:
-                                numpy.add.at(a_v, i, vol[j] * w)
-                        lo = hi
+        for i, j, d, d2 in _sph_near_pairs(t):
+            w = sph_weight(numpy.sqrt(d2) * t.inv_h, kernel)
+            numpy.add.at(a_n, i, w)
+            numpy.add.at(a_m, i, m[j] * w)
+            if a_v is not None:
+                numpy.add.at(a_v, i, vol[j] * w)
         number, rho_sum = sigma * a_n, sigma * a_m
         shepard = None if a_v is None else sigma * a_v
     for v in (number, rho_sum, shepard):
@@ -2047,15 +2091,9 @@ def _uniform_slength(lo, hi):
     return float(lo)
 
 
-def frame_kernel_sums(frame_or_arrays, h=None, kernel='wendland_c2', cells=None, where=None, types=None, domain=None,
-                      surface_below=None, box=None, dimensions=3):
-    """`sph_kernel_sums` of a frame's ``position``, ``mass`` and ``density`` over a selection: the host twin of
-    `HOOMDTrajectory.frame_kernel_sums_device`, which equals it exactly.  The selection -- `where_rows`, `domain_rows` or
-    their intersection, as `frame_neighbours` forms it -- is the list: both ``i`` and ``j`` come from it.  ``h=None``
-    takes the frame's ``slength`` if its smallest and largest value (over every row) are equal and raises ValueError if
-    they differ; a ``slength`` stored nowhere is the schema default 1.0.  A position that is stored nowhere puts every
-    row at the origin; without a ``mass`` array every mass is 1.0, without a ``density`` array there is no volume sum.
-    Returns a `KernelSums`."""
+def _sph_frame_list(frame_or_arrays, h, where, types, domain, box, dimensions):
+    """The selection of `frame_kernel_sums` and `frame_kernel_gradients` and the ``h=None`` rule: ``(arrays, position, box,
+    dimensions, h, rows)``."""
     if hasattr(frame_or_arrays, 'particles'):
         frame = frame_or_arrays
         arrays = _particle_arrays(frame.particles)
@@ -2090,8 +2128,216 @@ def frame_kernel_sums(frame_or_arrays, h=None, kernel='wendland_c2', cells=None,
     position = arrays.get('position')
     if position is None:
         position = numpy.zeros((N, 3), dtype=numpy.float32)
+    return arrays, position, box, dimensions, h, rows
+
+
+def frame_kernel_sums(frame_or_arrays, h=None, kernel='wendland_c2', cells=None, where=None, types=None, domain=None,
+                      surface_below=None, box=None, dimensions=3):
+    """`sph_kernel_sums` of a frame's ``position``, ``mass`` and ``density`` over a selection: the host twin of
+    `HOOMDTrajectory.frame_kernel_sums_device`, which equals it exactly.  The selection -- `where_rows`, `domain_rows` or
+    their intersection, as `frame_neighbours` forms it -- is the list: both ``i`` and ``j`` come from it.  ``h=None``
+    takes the frame's ``slength`` if its smallest and largest value (over every row) are equal and raises ValueError if
+    they differ; a ``slength`` stored nowhere is the schema default 1.0.  A position that is stored nowhere puts every
+    row at the origin; without a ``mass`` array every mass is 1.0, without a ``density`` array there is no volume sum.
+    Returns a `KernelSums`."""
+    arrays, position, box, dimensions, h, rows = _sph_frame_list(frame_or_arrays, h, where, types, domain, box, dimensions)
     return sph_kernel_sums(position, box, h, mass=arrays.get('mass'), density=arrays.get('density'), rows=rows, cells=cells,
                            dimensions=dimensions, kernel=kernel, surface_below=surface_below)
+
+
+# ---- SPH kernel gradients: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_gradients_device`) equals exactly
+_SPHG_SUMMARY_WORDS = 13    # n, nowhere, not_finite, curl_at, curl_row, normal_at, normal_row, 2 x (min, max), curl2, normal2
+
+
+def sph_gradient_factor(q, kernel='wendland_c2'):
+    """``F(q) = (1/q) dw/dq`` of one pair, float64 without contraction, for ``q = |x_i - x_j| * (1/h)`` below 2, written
+    so that only the spline's outer branch divides.  ``wendland_c2``: ``t = 1.0 - 0.5*q``, ``F = -5.0 * ((t*t)*t)``.
+    ``cubic_spline``: where ``q < 1.0`` ``F = 2.25*q - 3.0``, otherwise ``u = 2.0 - q`` and ``F = (-0.75*(u*u)) / q``.
+    The gradient of the kernel is ``grad_i W_ij = G * F * d`` with ``d = x_j - x_i`` and `sph_gradient_scale` ``G``."""
+    q = numpy.asarray(q, dtype=numpy.float64)
+    if _sph_kernel_id(kernel) == 0:
+        t = 1.0 - 0.5 * q
+        return -5.0 * ((t * t) * t)
+    u = 2.0 - q
+    with numpy.errstate(divide='ignore', invalid='ignore'):
+        return numpy.where(q < 1.0, 2.25 * q - 3.0, (-0.75 * (u * u)) / q)
+
+
+def sph_gradient_scale(kernel, h, dimensions=3):
+    """``G = -((sigma*inv_h)*inv_h)`` with `sph_sigma` and ``inv_h = 1/h``, float64 on the host, formed once."""
+    inv_h = numpy.float64(1.0) / numpy.float64(_sph_length(h))
+    return float(-((numpy.float64(sph_sigma(kernel, h, dimensions)) * inv_h) * inv_h))
+
+
+class KernelGradients(object):
+    """The SPH kernel gradients of a list in cell order (`sph_kernel_gradients`).
+
+    Attributes:
+        h (float), kernel (str), grid (``(cx, cy, cz)``), dimensions (int), volume (bool: was a ``density`` given): what
+            was asked; G (float): `sph_gradient_scale`.
+        rows, cell: the list in cell order and its cell ids (``n_cells``: nowhere).
+        density_rate, divergence (float64, ``n``), curl, normal (float64, ``n x 3``): per entry, in list order, ``sum_j m_j
+            (v_i - v_j) . grad_i W_ij``, ``sum_j V_j (v_j - v_i) . grad_i W_ij``, ``sum_j V_j (v_j - v_i) x grad_i W_ij``
+            written as ``grad x u`` and the colour gradient ``sum_j V_j grad_i W_ij`` over the entries inside ``2h``;
+            ``+0.0`` for an entry nowhere.  The last three are ``None`` without ``density``.  The six per-entry arrays are
+            numpy arrays from the model; from the GPU they are ``None`` unless ``return_rows`` left them in GPU memory.
+        n, nowhere (int): the entries, and those without a cell.
+        not_finite (int): the entries that have a cell and whose ``density_rate`` is NaN or infinite.
+        divergence_min, divergence_max, density_rate_min, density_rate_max (float): over the entries that have a cell, by
+            strict compares from ``+inf`` / ``-inf`` (a NaN never replaces a value); the first two ``None`` without
+            ``density``.
+        curl2, curl_at, curl_row, normal2, normal_at, normal_row: the largest ``(c0*c0 + c1*c1) + c2*c2`` of the ``curl``
+            and of the ``normal`` outputs over the entries that have a cell, its list position (the smaller one on a tie,
+            a NaN never counts) and its row; all ``None`` without ``density`` or where no entry has a number for it.
+    """
+
+    __slots__ = ('h', 'kernel', 'grid', 'dimensions', 'volume', 'G', 'rows', 'cell', 'density_rate', 'divergence', 'curl',
+                 'normal', 'n', 'nowhere', 'not_finite', 'divergence_min', 'divergence_max', 'density_rate_min',
+                 'density_rate_max', 'curl2', 'curl_at', 'curl_row', 'normal2', 'normal_at', 'normal_row', '_words')
+
+    def __init__(self, h, kernel, grid, dimensions, summary, volume, rows=None, cell=None, density_rate=None,
+                 divergence=None, curl=None, normal=None):
+        """``summary``: the 13 uint64 words of `pgsd_sph_gradients_device` -- n, nowhere, not_finite, curl_at, curl_row,
+        normal_at, normal_row, then as float64 bit patterns the minimum and maximum of divergence and density_rate and
+        the largest curl2 and normal2."""
+        s = numpy.ascontiguousarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _SPHG_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _SPHG_SUMMARY_WORDS)
+        self._words = s.copy()
+        self.h, self.kernel, self.dimensions, self.volume = float(h), kernel, int(dimensions), bool(volume)
+        self.G = sph_gradient_scale(kernel, h, dimensions)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.n, self.nowhere, self.not_finite = int(s[0]), int(s[1]), int(s[2])
+        f = s[7:13].view(numpy.float64)
+        self.divergence_min, self.divergence_max = (float(f[0]), float(f[1])) if self.volume else (None, None)
+        self.density_rate_min, self.density_rate_max = float(f[2]), float(f[3])
+        for k, name in enumerate(('curl', 'normal')):
+            found = self.volume and int(s[3 + 2 * k]) != _NEIGHBOURS_NONE
+            setattr(self, name + '2', float(f[4 + k]) if found else None)
+            setattr(self, name + '_at', int(s[3 + 2 * k]) if found else None)
+            setattr(self, name + '_row', int(s[4 + 2 * k]) if found else None)
+        self.rows, self.cell, self.density_rate = rows, cell, density_rate
+        self.divergence, self.curl, self.normal = divergence, curl, normal
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return self._words.copy()
+
+    def __repr__(self):
+        return "KernelGradients(h=%r, kernel=%r, grid=%r, n=%d, nowhere=%d, divergence=[%r, %r], density_rate=[%r, %r])" % (
+            self.h, self.kernel, self.grid, self.n, self.nowhere, self.divergence_min, self.divergence_max,
+            self.density_rate_min, self.density_rate_max)
+
+
+def _sphg_summary(n, somewhere, rows_sorted, rate, divergence, curl, normal):
+    """The summary words from the per-entry results (``divergence``, ``curl``, ``normal`` None without a density): no
+    float is summed over the list, so no order enters."""
+    words = numpy.zeros(_SPHG_SUMMARY_WORDS, dtype=numpy.uint64)
+    f = words[7:13].view(numpy.float64)
+    words[0], words[1] = n, n - somewhere
+    words[3:7] = _NEIGHBOURS_NONE
+    f[0:4:2], f[1:4:2], f[4:6] = numpy.inf, -numpy.inf, 0.0
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        for k, v in enumerate((divergence, rate)):
+            if v is None or not somewhere:
+                continue
+            v = v[:somewhere]
+            ok = v[v == v]
+            if ok.size:
+                f[2 * k], f[2 * k + 1] = min(numpy.inf, ok.min()), max(-numpy.inf, ok.max())
+        words[2] = int(numpy.count_nonzero(~numpy.isfinite(rate[:somewhere])))
+        for k, v in enumerate((curl, normal)):
+            if v is None or not somewhere:
+                continue
+            v = v[:somewhere]
+            norm2 = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+            size = numpy.where(norm2 == norm2, norm2, -1.0)
+            at = int(numpy.argmax(size))                # (the first position that attains the maximum)
+            if size[at] >= 0.0:
+                words[3 + 2 * k], words[4 + 2 * k], f[4 + k] = at, rows_sorted[at], norm2[at]
+    return words
+
+
+def sph_kernel_gradients(position, velocity, box, h, mass=None, density=None, rows=None, cells=None, dimensions=3,
+                         kernel='wendland_c2'):
+    """The SPH kernel gradients of a row list: per entry ``i`` the density rate of the continuity equation ``sum_j m_j
+    (v_i - v_j) . grad_i W_ij``, the velocity divergence ``sum_j V_j (v_j - v_i) . grad_i W_ij``, the curl (the
+    vorticity) ``sum_j V_j grad_i W_ij x (v_j - v_i)`` and the colour gradient ``sum_j V_j grad_i W_ij`` (it points into
+    the fluid at a free surface) over the entries ``j`` inside the kernel support ``2h``, and over the list the ranges of
+    the two scalars and the largest curl and normal with their rows.  The definition the GPU pass
+    (`pgsd.fl.PGSDFile.sph_gradients_device`, `HOOMDTrajectory.frame_kernel_gradients_device`) equals exactly, the floats
+    bit for bit.
+
+    Args:
+        position: ``N x 3`` float32 or float64; velocity: ``N x 3`` float32 or float64, or ``None``: the zero vector.
+        box, h, mass, density, rows, cells, dimensions, kernel: `sph_kernel_sums`'.  The grid, the support ``2h``, ``r2``,
+            ``inv_h``, ``sigma``, the list in cell order, THE ORDER of the candidates and every refusal are its own.
+            Without ``density`` only ``density_rate`` is formed.
+
+    **One pair**, float64 throughout without contraction, float32 inputs converted exactly before any subtraction: ``d =
+    pair_displacement(x_i, x_j)``, ``d2 = (dx*dx + dy*dy) + dz*dz``; ``j`` contributes when ``d2 < r2``, strictly; ``i``
+    itself and coincident entries are candidates like any other (their ``d`` is zero and so are their terms); ``rr =
+    sqrt(d2)``, ``q = rr * inv_h``, ``F = sph_gradient_factor(q)``; ``e_k = F * d_k`` -- the true gradient is ``grad_i W_ij =
+    G * e`` with `sph_gradient_scale` ``G`` --; ``u_k = v_j[k] - v_i[k]``; ``dot = (u0*e0 + u1*e1) + u2*e2``; ``c0 = e1*u2 -
+    e2*u1``, ``c1 = e2*u0 - e0*u2``, ``c2 = e0*u1 - e1*u0``; ``V_j = m_j / rho_j`` as in the sums.  Eight accumulators per
+    entry start at ``+0.0`` and add in the defined order: ``a_r += m_j * dot``, ``a_d += V_j * dot``, ``a_w[k] += V_j *
+    c_k``, ``a_c[k] += V_j * e_k``.  After the last candidate ``density_rate = -(G*a_r)``, ``divergence = G*a_d``,
+    ``curl[k] = G*a_w[k]``, ``normal[k] = G*a_c[k]``.  In 2-D ``d_z`` is 0 and nothing else is special-cased.  An entry
+    without a cell contributes to nobody and all its values are ``+0.0``.
+
+    Returns a `KernelGradients`.
+    """
+    asked = _sph_asked(box, h, cells, dimensions, kernel)
+    t = _sph_list(asked, position, box, rows, (('mass', mass, 1), ('density', density, 1), ('velocity', velocity, 3)))
+    dimensions, h, kid, grid = asked[0], asked[1], asked[2], asked[4]
+    n, somewhere = t.n, t.somewhere
+    mass, rho, v = t.columns
+    m = numpy.ones(n, dtype=numpy.float64) if mass is None else mass
+    v = numpy.zeros((n, 3), dtype=numpy.float64) if v is None else v
+    G = numpy.float64(-((t.sigma * t.inv_h) * t.inv_h))
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        vol = None if rho is None else m / rho
+    a_r = numpy.zeros(n, dtype=numpy.float64)
+    a_d = None if vol is None else numpy.zeros(n, dtype=numpy.float64)
+    a_w = None if vol is None else [numpy.zeros(n, dtype=numpy.float64) for _ in range(3)]
+    a_c = None if vol is None else [numpy.zeros(n, dtype=numpy.float64) for _ in range(3)]
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        for i, j, d, d2 in _sph_near_pairs(t):
+            F = sph_gradient_factor(numpy.sqrt(d2) * t.inv_h, kernel)
+            e = [F * d[0], F * d[1], F * d[2]]
+            u = [v[j, 0] - v[i, 0], v[j, 1] - v[i, 1], v[j, 2] - v[i, 2]]
+            dot = (u[0] * e[0] + u[1] * e[1]) + u[2] * e[2]
+            numpy.add.at(a_r, i, m[j] * dot)
+            if vol is not None:
+                V = vol[j]
+                c = [e[1] * u[2] - e[2] * u[1], e[2] * u[0] - e[0] * u[2], e[0] * u[1] - e[1] * u[0]]
+                numpy.add.at(a_d, i, V * dot)
+                for k in range(3):
+                    numpy.add.at(a_w[k], i, V * c[k])
+                for k in range(3):
+                    numpy.add.at(a_c[k], i, V * e[k])
+        rate = -(G * a_r)
+        divergence = None if vol is None else G * a_d
+        curl = None if vol is None else numpy.stack([G * a for a in a_w], axis=1)
+        normal = None if vol is None else numpy.stack([G * a for a in a_c], axis=1)
+    for a in (rate, divergence, curl, normal):
+        if a is not None:
+            a[somewhere:] = 0.0
+    words = _sphg_summary(n, somewhere, t.rows_sorted, rate, divergence, curl, normal)
+    return KernelGradients(h, SPH_KERNELS[kid], grid, dimensions, words, rho is not None, t.rows_sorted, t.cell_sorted, rate,
+                           divergence, curl, normal)
+
+
+def frame_kernel_gradients(frame_or_arrays, h=None, kernel='wendland_c2', cells=None, where=None, types=None, domain=None,
+                           box=None, dimensions=3):
+    """`sph_kernel_gradients` of a frame's ``position``, ``velocity``, ``mass`` and ``density`` over a selection: the host
+    twin of `HOOMDTrajectory.frame_kernel_gradients_device`, which equals it exactly.  The selection, the ``h=None`` rule,
+    the refusals and the defaults are `frame_kernel_sums`'; a velocity that is stored nowhere is the zero vector.
+    Returns a `KernelGradients`."""
+    arrays, position, box, dimensions, h, rows = _sph_frame_list(frame_or_arrays, h, where, types, domain, box, dimensions)
+    return sph_kernel_gradients(position, arrays.get('velocity'), box, h, mass=arrays.get('mass'),
+                                density=arrays.get('density'), rows=rows, cells=cells, dimensions=dimensions, kernel=kernel)
 
 
 def frame_moments(frame_or_arrays, by_type=True, centre=True, where=None, types=None, domain=None, box=None, dimensions=3):
@@ -4076,35 +4322,73 @@ class HOOMDTrajectory(object):
         result; otherwise they are ``None`` and no per-particle data is kept.  One `wait_read` at the end releases the
         staged chunks.  A frame whose position is stored nowhere has no chunk to search and raises ValueError.
         """
+        f = self.file
+        try:
+            f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults = self._sph_device_list(
+                "frame_kernel_sums_device", idx, h, kernel, cells, where, domain, ('mass', 'density'))
+            got = f.sph_sums_device(f_pos, 'particles/position', box, h, grid, rows, cell, n=count, mass=chunks[0],
+                                    density=chunks[1], defaults=defaults, dimensions=dims, kernel=kernel,
+                                    surface_below=surface_below, return_rows=return_rows)
+        finally:
+            f.wait_read()
+        return got
+
+    def _sph_device_list(self, who, idx, h, kernel, cells, where, domain, names):
+        """What `frame_kernel_sums_device` and `frame_kernel_gradients_device` share ahead of their pass: the ``h=None``
+        rule, the grid for the support ``2h``, the selection as a row list sorted by cell on the GPU and, for each of
+        ``names``, the effective chunk ``(frame, name)`` or ``None``.  ``(f_pos, box, dims, h, grid, rows, cell, count,
+        chunks, [mass default, density default])``; the caller ends with `wait_read`, whatever is raised here."""
         idx = self._frame_index(idx)
         f = self.file
         box, dims, n_global, f_pos = self._census_frame(idx)
         _sph_kernel_id(kernel)
+        if h is None:
+            f_h = self._effective_frame(idx, 'particles/slength', n_global)
+            if f_h is None or n_global == 0:
+                h = float(_PARTICLE_FIELDS['slength'][2])
+            else:
+                stats = f.chunk_stats_device(f_h, 'particles/slength')
+                h = _uniform_slength(float(stats.min[0]), float(stats.max[0]))
+        h = _sph_length(h)
+        grid = _neighbour_grid(box, float(numpy.float64(2.0) * numpy.float64(h)), cells, dims)
+        if f_pos is None:
+            raise ValueError("%s: the position is stored nowhere (every particle sits at the origin)" % who)
+        rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
+        if rows is None:
+            rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
+        cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
+        chunks = []
+        for name in names:
+            fr = self._effective_frame(idx, 'particles/' + name, n_global)
+            chunks.append(None if fr is None else (fr, 'particles/' + name))
+        defaults = [float(_PARTICLE_FIELDS[name][2]) for name in ('mass', 'density')]
+        return f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults
+
+    def frame_kernel_gradients(self, idx, h=None, kernel='wendland_c2', cells=None, where=None, domain=None):
+        """`frame_kernel_gradients` of frame ``idx`` read through the host path: a `KernelGradients`.  The definition of
+        `frame_kernel_gradients_device`."""
+        return frame_kernel_gradients(self[int(idx)], h, kernel=kernel, cells=cells, where=where, domain=domain)
+
+    def frame_kernel_gradients_device(self, idx, h=None, kernel='wendland_c2', cells=None, where=None, domain=None,
+                                      return_rows=False):
+        """`frame_kernel_gradients` of frame ``idx``, on the GPU: a `KernelGradients` that equals
+        ``frame_kernel_gradients(idx, h, ...)`` exactly -- every counter and index, every float bit for bit.
+
+        ``h=None``, the selection, the grid and the ordering are `frame_kernel_sums_device`'s; the pass
+        (`pgsd.fl.PGSDFile.sph_gradients_device`) runs over the staged position chunk and the effective ``velocity``,
+        ``mass`` and ``density`` chunks; one that is stored nowhere costs nothing: the zero vector and the schema defaults
+        stand for every row.  ``return_rows=True`` leaves ``rows``, ``cell``, ``density_rate``, ``divergence``, ``curl``
+        and ``normal`` in GPU memory on the result; otherwise they are ``None`` and no per-particle data is kept.  One
+        `wait_read` at the end releases the staged chunks.  A frame whose position is stored nowhere has no chunk to
+        search and raises ValueError.
+        """
+        f = self.file
         try:
-            if h is None:
-                f_h = self._effective_frame(idx, 'particles/slength', n_global)
-                if f_h is None or n_global == 0:
-                    h = float(_PARTICLE_FIELDS['slength'][2])
-                else:
-                    stats = f.chunk_stats_device(f_h, 'particles/slength')
-                    h = _uniform_slength(float(stats.min[0]), float(stats.max[0]))
-            h = _sph_length(h)
-            grid = _neighbour_grid(box, float(numpy.float64(2.0) * numpy.float64(h)), cells, dims)
-            if f_pos is None:
-                raise ValueError("frame_kernel_sums_device: the position is stored nowhere (every particle sits at the "
-                                 "origin)")
-            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
-            if rows is None:
-                rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
-            cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
-            chunks = []
-            for name in ('mass', 'density'):
-                fr = self._effective_frame(idx, 'particles/' + name, n_global)
-                chunks.append(None if fr is None else (fr, 'particles/' + name))
-            defaults = [float(_PARTICLE_FIELDS[name][2]) for name in ('mass', 'density')]
-            got = f.sph_sums_device(f_pos, 'particles/position', box, h, grid, rows, cell, n=count, mass=chunks[0],
-                                    density=chunks[1], defaults=defaults, dimensions=dims, kernel=kernel,
-                                    surface_below=surface_below, return_rows=return_rows)
+            f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults = self._sph_device_list(
+                "frame_kernel_gradients_device", idx, h, kernel, cells, where, domain, ('mass', 'density', 'velocity'))
+            got = f.sph_gradients_device(f_pos, 'particles/position', box, h, grid, rows, cell, n=count, velocity=chunks[2],
+                                         mass=chunks[0], density=chunks[1], defaults=defaults, dimensions=dims, kernel=kernel,
+                                         return_rows=return_rows)
         finally:
             f.wait_read()
         return got

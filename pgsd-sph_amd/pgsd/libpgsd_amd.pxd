@@ -248,6 +248,12 @@ cdef extern from "pgsd_private.h" nogil:
                              uint32_t kernel, uint32_t dimensions, const uint32_t* cells, const uint32_t* rows,
                              const int32_t* cell, uint64_t n, double surface_below, double* out_number,
                              double* out_density, double* out_shepard, uint64_t* out_summary)
+    int pgsd_sph_gradients_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* velocity,
+                                  const pgsd_index_entry* mass, const pgsd_index_entry* density, const double* defaults,
+                                  const double* vectors, double h, uint32_t kernel, uint32_t dimensions,
+                                  const uint32_t* cells, const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                  double* out_density_rate, double* out_divergence, double* out_curl, double* out_normal,
+                                  uint64_t* out_summary)
     int pgsd_chunk_stats_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                                 uint32_t with_norm2, uint64_t* out_counts, double* out_values)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,

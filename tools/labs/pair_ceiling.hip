@@ -17,8 +17,13 @@
 // lie inside the range are spread over the lanes' iterations as they are in a real list (a wave takes the branch in
 // nearly every iteration), instead of all lanes taking it together.
 //
+// Variant `sph_grad` ("SPH gradients"): the per-candidate work of sphg_pair_kernel<*, KERNEL, true> on
+// register values -- the same differences, fold, d2 and strict compare, and under the compare rr = sqrt(d2), q = rr *
+// inv_h, the factor F(q) (the spline's outer branch divides), e = F * d, u = v_j - v_i, the dot, the cross product and
+// the eight accumulations, m_j, V_j and v_j formed in registers.  The candidates are the `sph` variant's.
+//
 //   hipcc -O3 --offload-arch=gfx950 tools/labs/pair_ceiling.hip -o pair_ceiling
-//   ./pair_ceiling [reps=20] [iter=4096] [variant=census|sph_wendland|sph_spline]
+//   ./pair_ceiling [reps=20] [iter=4096] [variant=census|sph_wendland|sph_spline|sph_grad_wendland|sph_grad_spline]
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -173,6 +178,92 @@ __global__ __launch_bounds__(256) void sph_ceiling_kernel(const Box b, double in
     out_sums[(size_t)k * 3 + 2] = a_v;
     }
 
+template<int KERNEL>
+__global__ __launch_bounds__(256) void sph_grad_ceiling_kernel(const Box b, double inv_h, uint32_t iter, uint32_t* __restrict__ out_count,
+                                                               double* __restrict__ out_sums)
+    {
+#pragma clang fp contract(off)
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    const double Lx = b.v[0], Ly = b.v[1], Lz = b.v[2], xyLy = b.v[3], xzLz = b.v[4], yzLz = b.v[5];
+    const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5, r2 = b.r2;
+    const double xi0 = -hx + (double)(k & 1023) * (Lx / 1024.0), xi1 = -hy + (double)((k >> 10) & 1023) * (Ly / 1024.0);
+    const double xi2 = -hz + (double)(k >> 20) * (Lz / 4096.0);
+    const double vi0 = (double)(k & 15) * 0.125, vi1 = -(double)(k & 7) * 0.25, vi2 = 0.5;
+    double s0 = Lx / 977.0 + (double)(k & 63) * 1e-3, s1 = -Ly / 1931.0, s2 = Lz / 2953.0;
+    double xj0 = xi0, xj1 = xi1, xj2 = xi2;
+    const uint32_t phase = (k & 63) * 8; // the lane's own turning step
+    uint32_t count = 0;
+    double a_r = 0.0, a_d = 0.0, a_w0 = 0.0, a_w1 = 0.0, a_w2 = 0.0, a_c0 = 0.0, a_c1 = 0.0, a_c2 = 0.0;
+    for (uint32_t j = 0; j < iter; j++)
+        {
+        const bool turn = ((j + phase) & 511) == 511;
+        s0 = turn ? -s0 : s0;
+        s1 = turn ? -s1 : s1;
+        s2 = turn ? -s2 : s2;
+        xj0 = xj0 + s0;
+        xj1 = xj1 + s1;
+        xj2 = xj2 + s2;
+        double dx = xj0 - xi0, dy = xj1 - xi1, dz = xj2 - xi2;
+            {
+            const bool up = dz >= hz, down = dz < -hz;
+            dx = up ? dx - xzLz : (down ? dx + xzLz : dx);
+            dy = up ? dy - yzLz : (down ? dy + yzLz : dy);
+            dz = up ? dz - Lz : (down ? dz + Lz : dz);
+            }
+            {
+            const bool up = dy >= hy, down = dy < -hy;
+            dx = up ? dx - xyLy : (down ? dx + xyLy : dx);
+            dy = up ? dy - Ly : (down ? dy + Ly : dy);
+            }
+            {
+            const bool up = dx >= hx, down = dx < -hx;
+            dx = up ? dx - Lx : (down ? dx + Lx : dx);
+            }
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 < r2)
+            {
+            const double rr = __builtin_sqrt(d2);
+            const double q = rr * inv_h;
+            double F;
+            if constexpr (KERNEL == 0)
+                {
+                const double t = 1.0 - 0.5 * q;
+                F = -5.0 * ((t * t) * t);
+                }
+            else
+                {
+                const double u = 2.0 - q;
+                F = q < 1.0 ? 2.25 * q - 3.0 : (-0.75 * (u * u)) / q;
+                }
+            const double mj = 1.0 + (double)(j & 7u), vj = mj * 0.5;
+            const double e0 = F * dx, e1 = F * dy, e2 = F * dz;
+            const double u0 = (double)(j & 3u) - vi0, u1 = (double)(j & 5u) - vi1, u2 = (double)(j & 9u) - vi2;
+            const double dot = (u0 * e0 + u1 * e1) + u2 * e2;
+            const double c0 = e1 * u2 - e2 * u1, c1 = e2 * u0 - e0 * u2, c2 = e0 * u1 - e1 * u0;
+            a_r = a_r + mj * dot;
+            a_d = a_d + vj * dot;
+            a_w0 = a_w0 + vj * c0;
+            a_w1 = a_w1 + vj * c1;
+            a_w2 = a_w2 + vj * c2;
+            a_c0 = a_c0 + vj * e0;
+            a_c1 = a_c1 + vj * e1;
+            a_c2 = a_c2 + vj * e2;
+            count++;
+            }
+        }
+    out_count[k] = count;
+    double* o = out_sums + (size_t)k * 8;
+    o[0] = a_r;
+    o[1] = a_d;
+    o[2] = a_w0;
+    o[3] = a_w1;
+    o[4] = a_w2;
+    o[5] = a_c0;
+    o[6] = a_c1;
+    o[7] = a_c2;
+    }
+
+// kernel: 0 sph_wendland, 1 sph_spline, 2 sph_grad_wendland, 3 sph_grad_spline
 static int run_sph(int reps, uint32_t iter, int kernel)
     {
     int cus = 256;
@@ -182,7 +273,7 @@ static int run_sph(int reps, uint32_t iter, int kernel)
     uint32_t* count;
     double* sums;
     CK(hipMalloc(&count, lanes * sizeof(uint32_t)));
-    CK(hipMalloc(&sums, lanes * 3 * sizeof(double)));
+    CK(hipMalloc(&sums, lanes * 8 * sizeof(double))); // (three per lane for the sums, eight for the gradients)
     const Box b = {{40.0, 40.0, 40.0, 0.25 * 40.0, 0.125 * 40.0, -0.0625 * 40.0}, 0.197 * 0.197};
     const double inv_h = 1.0 / (0.197 / 2);
     hipEvent_t t0, t1;
@@ -193,8 +284,12 @@ static int run_sph(int reps, uint32_t iter, int kernel)
         {
         if (kernel == 0)
             hipExtLaunchKernelGGL(sph_ceiling_kernel<0>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
-        else
+        else if (kernel == 1)
             hipExtLaunchKernelGGL(sph_ceiling_kernel<1>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
+        else if (kernel == 2)
+            hipExtLaunchKernelGGL(sph_grad_ceiling_kernel<0>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
+        else
+            hipExtLaunchKernelGGL(sph_grad_ceiling_kernel<1>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
         CK(hipGetLastError());
         CK(hipEventSynchronize(t1));
         float t = 0;
@@ -209,9 +304,10 @@ static int run_sph(int reps, uint32_t iter, int kernel)
         near += c;
     std::sort(ms.begin(), ms.end());
     const double pairs = (double)lanes * iter;
+    static const char* variants[4] = {"sph_wendland", "sph_spline", "sph_grad_wendland", "sph_grad_spline"};
     printf("{\"kind\": \"pair_ceiling\", \"variant\": \"%s\", \"lanes\": %zu, \"iter\": %u, \"pairs\": %.0f, \"near\": %llu, "
            "\"best_ms\": %.4f, \"median_ms\": %.4f, \"worst_ms\": %.4f, \"pairs_per_s_best\": %.4g, \"pairs_per_s_median\": %.4g}\n",
-           kernel == 0 ? "sph_wendland" : "sph_spline", lanes, iter, pairs, (unsigned long long)near, ms.front(),
+           variants[kernel], lanes, iter, pairs, (unsigned long long)near, ms.front(),
            ms[ms.size() / 2], ms.back(), pairs / (ms.front() * 1e-3), pairs / (ms[ms.size() / 2] * 1e-3));
     CK(hipFree(count));
     CK(hipFree(sums));
@@ -223,7 +319,10 @@ int main(int argc, char** argv)
     const int reps = argc > 1 ? atoi(argv[1]) : 20;
     const uint32_t iter = argc > 2 ? (uint32_t)atoi(argv[2]) : 4096u;
     if (argc > 3 && std::string(argv[3]) != "census")
-        return run_sph(reps, iter, std::string(argv[3]) == "sph_spline" ? 1 : 0);
+        {
+        const std::string v = argv[3];
+        return run_sph(reps, iter, v == "sph_spline" ? 1 : (v == "sph_grad_wendland" ? 2 : (v == "sph_grad_spline" ? 3 : 0)));
+        }
     int cus = 256;
     CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
     const uint32_t blocks = (uint32_t)cus * 8u; // 32 waves per compute unit: eight per SIMD
