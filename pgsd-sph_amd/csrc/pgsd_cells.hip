@@ -275,14 +275,6 @@ namespace
 Scratch g_cells_scratch("cell fields", 1.25, 1u << 16, 0, sizeof(uint64_t));
 std::mutex g_cells_lock;
 
-size_t round16(size_t bytes)
-    {
-    return (bytes + 15) & ~(size_t)15;
-    }
-
-const char* cells_refused = "a cell id descends or lies outside [0, n_cells], or an entry of the row list lies outside the "
-                            "chunks (nothing was computed)";
-
 int cells_arguments(uint64_t n, uint32_t n_cells, std::string* err, const char* what)
     {
     if (n >= (1ull << 32))
@@ -381,19 +373,12 @@ int launch_cell_moments(const CellMomentsArgs& a, uint64_t* out_counts, double* 
     uint64_t* table_bad = (uint64_t*)((char*)table + table_bytes);
     double* part = (double*)((char*)table_bad + bad_bytes);
     uint32_t* host_flag = (uint32_t*)scope.mem().mapped;
-    uint32_t* host_flag_dev = (uint32_t*)scope.mem().mapped_dev;
-    __atomic_store_n(host_flag, 0u, __ATOMIC_RELEASE);
     const dim3 block(SEL_THREADS);
-    hipError_t e = hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), stream);
-    // (empty cells: +0.0 and no bad entry)
-    if (e == hipSuccess)
-        e = hipMemsetAsync(table, 0, table_bytes + bad_bytes, stream);
+    // (the table is zeroed for the empty cells: +0.0 and no bad entry)
+    hipError_t e = cells_open_pass(a.rows, a.cell, n, a.N, n_cells, flag_dev, host_flag, (uint32_t*)scope.mem().mapped_dev, offs,
+                                   table, table_bytes + bad_bytes, stream);
     if (e == hipSuccess)
         {
-        hipLaunchKernelGGL(cells_check_kernel, dim3((unsigned)((n + SEL_THREADS - 1) / SEL_THREADS)), block, 0, stream, a.rows,
-                           a.cell, n, a.N, n_cells, flag_dev, host_flag_dev);
-        hipLaunchKernelGGL(cells_offsets_kernel, dim3((n_cells + 2 + SEL_THREADS - 1) / SEL_THREADS), block, 0, stream, a.cell, n,
-                           n_cells, flag_dev, offs);
         const dim3 per_slab((n_slabs + CELLS_WAVES - 1) / CELLS_WAVES);
         if (a.f64)
             hipLaunchKernelGGL(cells_piece_kernel<true>, per_slab, block, 0, stream, a, offs, flag_dev, table, table_bad, part,

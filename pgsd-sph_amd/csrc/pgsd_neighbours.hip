@@ -9,11 +9,12 @@
 //                          CSR offsets; every kernel here reads the device flag first and does nothing where it is set,
 //                          and clamps what it takes from the offsets to n
 //   neighbours_compact_kernel   lane per entry: xs[k] = position[rows[k]] in the chunk's own element type, so that the
-//                          pair loop reads runs instead of gathering: ids are x-fastest, hence the cells ix-1, ix, ix+1 of
-//                          one (y, z) row of the grid are ONE run of xs wherever x does not wrap, two where it does
-//   neighbours_pair_kernel<F64, HIST>   lane per entry i: x_i and its cell's (ix, iy, iz) in registers; a loop over the
-//                          deduplicated (oy, oz) offsets ({0} at one cell, {0, +1} at two, {-1, 0, +1} otherwise) and the
-//                          one or two x-runs of each; per candidate the fold, d2 and the strict compare; the lane keeps
+//                          pair loop reads runs instead of gathering: ids are x-fastest, hence the x cells of one (y, z)
+//                          row of the grid are ONE run of xs wherever x does not wrap, two where it does
+//   neighbours_pair_kernel<F64, HIST>   lane per entry i: the candidates by traverse_candidates (pgsd_traverse.hpp), in
+//                          the order the SPH kernel sums define -- the census needs no order and takes theirs: the
+//                          deduplicated offsets, the x-runs, the fold, d2 and the strict compare are written there,
+//                          once for the three pair units.  The functor skips j == i by list position; the lane keeps
 //                          its count and the smallest (d2, position) pair.  HIST: the edge table and the pair histogram
 //                          live in LDS; the bin is the one numpy.searchsorted(edges2, d2, 'right') - 1 names, found by
 //                          bisection of the table.  The summary is made here as well: the count histogram, the ordered
@@ -25,6 +26,7 @@
 // pgsd_kernels.hpp; the launcher's host side: pgsd_scratch.hpp.
 #include "pgsd_stats.hpp"
 #include "pgsd_cells.hpp"
+#include "pgsd_traverse.hpp"
 #include "pgsd_scratch.hpp"
 
 #include <type_traits>
@@ -68,19 +70,7 @@ __global__ __launch_bounds__(SEL_THREADS) void neighbours_compact_kernel(const N
     const uint64_t row = a.rows[k];
     if (row >= a.N) // (the check kernel has refused such a list: nothing is loaded for it)
         return;
-    if constexpr (F64)
-        {
-        const double* q = (const double*)a.pos + row * 3;
-        double* o = (double*)xs + k * 3;
-        o[0] = q[0];
-        o[1] = q[1];
-        o[2] = q[2];
-        }
-    else
-        {
-        const u32x3 v = *(const u32x3_a4*)((const uint32_t*)a.pos + row * 3);
-        *(u32x3_a4*)((uint32_t*)xs + k * 3) = v;
-        }
+    compact_position<F64>(a.pos, row, xs, k);
     }
 
 // words: the summary in device memory -- the head (word 2, the ordered pairs, is added to here), the count histogram and
@@ -123,111 +113,41 @@ __global__ __launch_bounds__(SEL_THREADS) void neighbours_pair_kernel(const Neig
     const bool live = k64 < n;
     const int32_t c = live ? a.cell[k] : (int32_t)a.n_cells;
     const bool has = live && c >= 0 && (uint32_t)c < a.n_cells;
-    const elem_t* x = (const elem_t*)xs;
     uint32_t count = 0, best = NEIGHBOURS_NONE;
     double best2 = __builtin_huge_val();
     if (has)
-        {
-        const double xi0 = (double)x[(size_t)k * 3 + 0], xi1 = (double)x[(size_t)k * 3 + 1], xi2 = (double)x[(size_t)k * 3 + 2];
-        const double Lx = a.vectors[0], Ly = a.vectors[1], Lz = a.vectors[2];
-        const double xyLy = a.vectors[3], xzLz = a.vectors[4], yzLz = a.vectors[5];
-        const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5; // (exact halves)
-        const double r2 = a.r2;
-        const bool three = a.dims != 2;
-        const int cx = (int)a.cells[0], cy = (int)a.cells[1], cz = (int)a.cells[2];
-        const int ix = (int)((uint32_t)c % (uint32_t)cx), iy = (int)(((uint32_t)c / (uint32_t)cx) % (uint32_t)cy);
-        const int iz = (int)((uint32_t)c / ((uint32_t)cx * (uint32_t)cy));
-        // the cells ix-1, ix, ix+1 (deduplicated, wrapped) as one or two runs [a0, b0), [a1, b1) of the x row
-        int a0 = 0, b0 = cx, a1 = 0, b1 = 0;
-        if (cx > 3)
-            {
-            if (ix == 0)
-                {
-                b0 = 2;
-                a1 = cx - 1;
-                b1 = cx;
-                }
-            else if (ix == cx - 1)
-                {
-                a0 = cx - 2;
-                b1 = 1;
-                }
-            else
-                {
-                a0 = ix - 1;
-                b0 = ix + 2;
-                }
-            }
-        const int ylo = cy >= 3 ? -1 : 0, yhi = cy >= 2 ? 1 : 0;
-        const int zlo = cz >= 3 ? -1 : 0, zhi = cz >= 2 ? 1 : 0;
-        for (int oz = zlo; oz <= zhi; oz++)
-            {
-            int wz = iz + oz;
-            wz = wz < 0 ? wz + cz : (wz >= cz ? wz - cz : wz);
-            for (int oy = ylo; oy <= yhi; oy++)
-                {
-                int wy = iy + oy;
-                wy = wy < 0 ? wy + cy : (wy >= cy ? wy - cy : wy);
-                const uint32_t row0 = (uint32_t)cx * ((uint32_t)wy + (uint32_t)cy * (uint32_t)wz);
-                for (int run = 0; run < 2; run++)
-                    {
-                    const int ra = run ? a1 : a0, rb = run ? b1 : b0;
-                    if (rb <= ra)
-                        continue;
-                    const uint32_t lo = (uint32_t)min((uint64_t)offs[row0 + (uint32_t)ra], n);
-                    const uint32_t hi = (uint32_t)min((uint64_t)offs[row0 + (uint32_t)rb], n);
-                    for (uint32_t j = lo; j < hi; j++)
-                        {
-                        const double xj0 = (double)x[(size_t)j * 3 + 0], xj1 = (double)x[(size_t)j * 3 + 1];
-                        double dx = xj0 - xi0, dy = xj1 - xi1, dz = 0.0;
-                        if (three)
+        traverse_candidates((const elem_t*)xs, offs, n, k, (uint32_t)c, traverse_grid(a),
+                            [&](uint32_t j, double, double, double, double d2)
                             {
-                            dz = (double)x[(size_t)j * 3 + 2] - xi2;
-                            const bool up = dz >= hz, down = dz < -hz;
-                            dx = up ? dx - xzLz : (down ? dx + xzLz : dx);
-                            dy = up ? dy - yzLz : (down ? dy + yzLz : dy);
-                            dz = up ? dz - Lz : (down ? dz + Lz : dz);
-                            }
-                            {
-                            const bool up = dy >= hy, down = dy < -hy;
-                            dx = up ? dx - xyLy : (down ? dx + xyLy : dx);
-                            dy = up ? dy - Ly : (down ? dy + Ly : dy);
-                            }
-                            {
-                            const bool up = dx >= hx, down = dx < -hx;
-                            dx = up ? dx - Lx : (down ? dx + Lx : dx);
-                            }
-                        const double d2 = (dx * dx + dy * dy) + dz * dz;
-                        const bool near = d2 < r2 && j != k;
-                        count += near ? 1u : 0u;
-                        if (near && nbr_before(d2, j, best2, best))
-                            {
-                            best2 = d2;
-                            best = j;
-                            }
-                        if constexpr (HIST)
-                            {
-                            // the largest b with edges[b] <= d2: searchsorted(edges2, d2, 'right') - 1; a pair outside
-                            // [edges[0], edges[bins]) is in no bin
-                            if (near && bins > 0 && s_edges[0] <= d2 && d2 < s_edges[bins])
-                                {
-                                uint32_t b = 0, e = bins;
-                                while (e - b > 1)
+                                // (the self pair as a flag, not as an early return: with the return the call
+                                // measured 34.2 ms where this form, like the unit's former own loop, takes 33.9 --
+                                // DESIGN.md §8, "One traversal")
+                                const bool other = j != k;
+                                count += other ? 1u : 0u;
+                                if (other && nbr_before(d2, j, best2, best))
                                     {
-                                    const uint32_t mid = (b + e) >> 1;
-                                    if (s_edges[mid] <= d2)
-                                        b = mid;
-                                    else
-                                        e = mid;
+                                    best2 = d2;
+                                    best = j;
                                     }
-                                atomicAdd(&s_hist[b], 1ull);
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
+                                if constexpr (HIST)
+                                    {
+                                    // the largest b with edges[b] <= d2: searchsorted(edges2, d2, 'right') - 1; a pair
+                                    // outside [edges[0], edges[bins]) is in no bin
+                                    if (other && bins > 0 && s_edges[0] <= d2 && d2 < s_edges[bins])
+                                        {
+                                        uint32_t b = 0, e = bins;
+                                        while (e - b > 1)
+                                            {
+                                            const uint32_t mid = (b + e) >> 1;
+                                            if (s_edges[mid] <= d2)
+                                                b = mid;
+                                            else
+                                                e = mid;
+                                            }
+                                        atomicAdd(&s_hist[b], 1ull);
+                                        }
+                                    }
+                            });
     if (live)
         {
         if (out_count)
@@ -331,11 +251,6 @@ constexpr size_t NBR_SUMMARY_BYTES = ((size_t)NEIGHBOURS_HEAD_WORDS + NEIGHBOURS
 Scratch g_neighbours_scratch("neighbour census", 1.25, 1u << 16, NBR_SUMMARY_BYTES, sizeof(uint64_t));
 std::mutex g_neighbours_lock;
 
-size_t nbr_round16(size_t bytes)
-    {
-    return (bytes + 15) & ~(size_t)15;
-    }
-
 const char* neighbours_refused = "a cell id descends or lies outside [0, n_cells], or an entry of the row list lies outside "
                                  "the position chunk (nothing was computed)";
     } // namespace
@@ -352,19 +267,9 @@ int launch_neighbours(const NeighboursArgs& a, const double* edges2, uint32_t* o
     const auto fail = [err](const char* why) { return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, std::string(what) + ": " + why); };
     if (!out_summary || !out_closest2)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    if (a.n >= (1ull << 32))
-        return fail("a list holds fewer than 2^32 entries");
-    if (a.N >= (1ull << 32))
-        return fail("chunks of 2^32 rows or more have no 32-bit row list");
-    uint64_t n_cells = 1;
-    for (int i = 0; i < 3; i++)
-        {
-        if (a.cells[i] < 1 || a.cells[i] > ORDER_MAX_AXIS_CELLS)
-            return fail("every axis takes 1 to 1024 cells");
-        n_cells *= a.cells[i];
-        }
-    if (n_cells > CELLS_MAX_CELLS || n_cells != a.n_cells)
-        return fail("a grid holds 1 to 2^20 cells");
+    int rc = cells_refuse_grid(a.n, a.N, a.cells, a.n_cells, what, err);
+    if (rc != PGSD_SUCCESS)
+        return rc;
     if (a.bins > NEIGHBOURS_MAX_BINS)
         return fail("the pair histogram holds at most 1024 bins");
     if (a.bins > 0 && !edges2)
@@ -382,10 +287,10 @@ int launch_neighbours(const NeighboursArgs& a, const double* edges2, uint32_t* o
     if (!a.rows || !a.cell || !a.pos)
         return PGSD_ERROR_INVALID_ARGUMENT;
     const uint32_t n_blocks = (uint32_t)((n + SEL_THREADS - 1) / SEL_THREADS);
-    const size_t offs_bytes = nbr_round16(((size_t)a.n_cells + 2) * sizeof(uint32_t));
-    const size_t xs_bytes = nbr_round16((size_t)n * 3 * (a.f64 ? sizeof(double) : sizeof(float)));
-    const size_t part_bytes = nbr_round16((size_t)n_blocks * sizeof(NeighboursPartial));
-    const size_t edges_bytes = nbr_round16(((size_t)bins + 1) * sizeof(double));
+    const size_t offs_bytes = round16(((size_t)a.n_cells + 2) * sizeof(uint32_t));
+    const size_t xs_bytes = round16((size_t)n * 3 * (a.f64 ? sizeof(double) : sizeof(float)));
+    const size_t part_bytes = round16((size_t)n_blocks * sizeof(NeighboursPartial));
+    const size_t edges_bytes = round16(((size_t)bins + 1) * sizeof(double));
     const size_t words_bytes = (summary_words + 1) * sizeof(uint64_t);
     LaunchScope scope(g_neighbours_lock, g_neighbours_scratch, 16 + offs_bytes + xs_bytes + part_bytes + edges_bytes + words_bytes,
                       stream, err);
@@ -400,20 +305,15 @@ int launch_neighbours(const NeighboursArgs& a, const double* edges2, uint32_t* o
     unsigned long long* words = (unsigned long long*)((char*)edges_dev + edges_bytes);
     double* closest2 = (double*)(words + summary_words);
     uint32_t* host_flag = (uint32_t*)scope.mem().mapped;
-    uint32_t* host_flag_dev = (uint32_t*)scope.mem().mapped_dev;
-    __atomic_store_n(host_flag, 0u, __ATOMIC_RELEASE);
     const dim3 block(SEL_THREADS), per_entry(n_blocks);
-    hipError_t e = hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(words, 0, words_bytes, stream);
-    if (e == hipSuccess && bins)
+    hipError_t e = hipSuccess;
+    if (bins)
         e = hipMemcpyAsync(edges_dev, edges2, ((size_t)bins + 1) * sizeof(double), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess)
+        e = cells_open_pass(a.rows, a.cell, n, a.N, a.n_cells, flag_dev, host_flag, (uint32_t*)scope.mem().mapped_dev, offs, words,
+                            words_bytes, stream);
+    if (e == hipSuccess)
         {
-        hipLaunchKernelGGL(cells_check_kernel, per_entry, block, 0, stream, a.rows, a.cell, n, a.N, a.n_cells, flag_dev,
-                           host_flag_dev);
-        hipLaunchKernelGGL(cells_offsets_kernel, dim3((a.n_cells + 2 + SEL_THREADS - 1) / SEL_THREADS), block, 0, stream, a.cell,
-                           n, a.n_cells, flag_dev, offs);
         if (a.f64)
             {
             hipLaunchKernelGGL(neighbours_compact_kernel<true>, per_entry, block, 0, stream, a, flag_dev, xs);
@@ -440,7 +340,7 @@ int launch_neighbours(const NeighboursArgs& a, const double* edges2, uint32_t* o
         }
     if (e == hipSuccess)
         e = hipMemcpyAsync(scope.mem().host, words, words_bytes, hipMemcpyDeviceToHost, stream);
-    const int rc = scope.finish(what, e);
+    rc = scope.finish(what, e);
     if (rc != PGSD_SUCCESS)
         return rc;
     if (__atomic_load_n(host_flag, __ATOMIC_ACQUIRE) != 0)

@@ -77,6 +77,12 @@ class Scratch
 
 extern std::mutex g_select_lock;
 
+// the size of one part of a scratch space: the part behind it starts on a 16-byte boundary
+inline size_t round16(size_t bytes)
+    {
+    return (bytes + 15) & ~(size_t)15;
+    }
+
 // Whatever an earlier call of this thread left in the runtime's last-error slot (a failed hipMalloc, the caller's own
 // calls, an unrelated launch) is not this launch's: the slot is read again right behind the launches.
 inline void drop_stale_error()

@@ -14,17 +14,17 @@
 //   sph_compact_kernel<F64>   lane per entry: xs[k] = position[rows[k]] in the chunk's own element type, m[k] the mass
 //                          and V[k] = m / rho (one float64 division of the stored values) as float64, so that the pair
 //                          loop reads runs instead of gathering
-//   sph_pair_kernel<F64, KERNEL, VOL>   lane per entry i: x_i and the three accumulators in registers; the x cells of
-//                          one (y, z) row of the grid are min(3, cx) cells taken cyclically from (ix-1) mod cx (from ix
-//                          at two cells, from 0 at one): run 0 goes up to cx, run 1 continues from 0 -- the defined
-//                          order at every ix and every cx, in at most two runs of xs.  The counters (not_finite, surface)
-//                          go through LDS counters and 64-bit integer atomics; the minima, maxima and the deviation
-//                          leave as one partial per workgroup
+//   sph_pair_kernel<F64, KERNEL, VOL>   lane per entry i: x_i and the three accumulators in registers, the candidates
+//                          by traverse_candidates (pgsd_traverse.hpp) in the defined order: the cells, the x-runs, the
+//                          fold and the strict compare are written there, once for the three pair units.  The counters
+//                          (not_finite, surface) go through LDS counters and 64-bit integer atomics; the minima, maxima
+//                          and the deviation leave as one partial per workgroup
 //   sph_final_kernel       one workgroup: the partials in a fixed strided scan, then the words of the summary
 // No float atomic anywhere, no private (scratch) memory in any instance.  Shared device helpers: pgsd_stats.hpp,
 // pgsd_kernels.hpp; the launcher's host side: pgsd_scratch.hpp.
 #include "pgsd_stats.hpp"
 #include "pgsd_cells.hpp"
+#include "pgsd_traverse.hpp"
 #include "pgsd_scratch.hpp"
 
 #include <type_traits>
@@ -83,12 +83,6 @@ __device__ __forceinline__ SphPartial sph_nothing()
     return p;
     }
 
-// one value of a float32 or float64 column as a double (exact)
-__device__ __forceinline__ double sph_column(const void* base, uint32_t f64, uint64_t row)
-    {
-    return f64 ? ((const double*)base)[row] : (double)((const float*)base)[row];
-    }
-
 template<bool F64>
 __global__ __launch_bounds__(SEL_THREADS) void sph_compact_kernel(const SphArgs a, const uint32_t* flag_dev, void* __restrict__ xs,
                                                                   double* __restrict__ ms, double* __restrict__ vs)
@@ -99,23 +93,11 @@ __global__ __launch_bounds__(SEL_THREADS) void sph_compact_kernel(const SphArgs 
     const uint64_t row = a.rows[k];
     if (row >= a.N) // (the check kernel has refused such a list: nothing is loaded for it)
         return;
-    if constexpr (F64)
-        {
-        const double* q = (const double*)a.pos + row * 3;
-        double* o = (double*)xs + k * 3;
-        o[0] = q[0];
-        o[1] = q[1];
-        o[2] = q[2];
-        }
-    else
-        {
-        const u32x3 v = *(const u32x3_a4*)((const uint32_t*)a.pos + row * 3);
-        *(u32x3_a4*)((uint32_t*)xs + k * 3) = v;
-        }
-    const double m = a.mass ? sph_column(a.mass, a.mass_f64, row) : a.mass_default;
+    compact_position<F64>(a.pos, row, xs, k);
+    const double m = a.mass ? column_value(a.mass, a.mass_f64, row) : a.mass_default;
     ms[k] = m;
     if (a.volume)
-        vs[k] = m / (a.density ? sph_column(a.density, a.density_f64, row) : a.density_default);
+        vs[k] = m / (a.density ? column_value(a.density, a.density_f64, row) : a.density_default);
     }
 
 // w(q) of pgsd.hoomd.sph_weight: the operations as written there, one rounding each
@@ -166,77 +148,22 @@ __global__ __launch_bounds__(SEL_THREADS) void sph_pair_kernel(const SphArgs a, 
     const bool live = k64 < n;
     const int32_t c = live ? a.cell[k] : (int32_t)a.n_cells;
     const bool has = live && c >= 0 && (uint32_t)c < a.n_cells;
-    const elem_t* x = (const elem_t*)xs;
     double a_n = 0.0, a_m = 0.0, a_v = 0.0;
     if (has)
         {
-        const double xi0 = (double)x[(size_t)k * 3 + 0], xi1 = (double)x[(size_t)k * 3 + 1], xi2 = (double)x[(size_t)k * 3 + 2];
-        const double Lx = a.vectors[0], Ly = a.vectors[1], Lz = a.vectors[2];
-        const double xyLy = a.vectors[3], xzLz = a.vectors[4], yzLz = a.vectors[5];
-        const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5; // (exact halves)
-        const double r2 = a.r2, inv_h = a.inv_h;
-        const bool three = a.dims != 2;
-        const int cx = (int)a.cells[0], cy = (int)a.cells[1], cz = (int)a.cells[2];
-        const int ix = (int)((uint32_t)c % (uint32_t)cx), iy = (int)(((uint32_t)c / (uint32_t)cx) % (uint32_t)cy);
-        const int iz = (int)((uint32_t)c / ((uint32_t)cx * (uint32_t)cy));
-        // the x cells in the defined order: `take` cells cyclically from `from`, as run 0 [from, b0) and run 1 [0, b1)
-        const int take = min(3, cx);
-        const int from = cx == 1 ? 0 : (cx == 2 ? ix : (ix == 0 ? cx - 1 : ix - 1));
-        const int b0 = min(from + take, cx), b1 = max(from + take - cx, 0);
-        const int ylo = cy >= 3 ? -1 : 0, yhi = cy >= 2 ? 1 : 0;
-        const int zlo = cz >= 3 ? -1 : 0, zhi = cz >= 2 ? 1 : 0;
-        for (int oz = zlo; oz <= zhi; oz++)
-            {
-            int wz = iz + oz;
-            wz = wz < 0 ? wz + cz : (wz >= cz ? wz - cz : wz);
-            for (int oy = ylo; oy <= yhi; oy++)
-                {
-                int wy = iy + oy;
-                wy = wy < 0 ? wy + cy : (wy >= cy ? wy - cy : wy);
-                const uint32_t row0 = (uint32_t)cx * ((uint32_t)wy + (uint32_t)cy * (uint32_t)wz);
-                for (int run = 0; run < 2; run++)
-                    {
-                    const int ra = run ? 0 : from, rb = run ? b1 : b0;
-                    if (rb <= ra)
-                        continue;
-                    const uint32_t lo = (uint32_t)min((uint64_t)offs[row0 + (uint32_t)ra], n);
-                    const uint32_t hi = (uint32_t)min((uint64_t)offs[row0 + (uint32_t)rb], n);
-                    for (uint32_t j = lo; j < hi; j++)
-                        {
-                        const double xj0 = (double)x[(size_t)j * 3 + 0], xj1 = (double)x[(size_t)j * 3 + 1];
-                        double dx = xj0 - xi0, dy = xj1 - xi1, dz = 0.0;
-                        if (three)
+        const double inv_h = a.inv_h;
+        traverse_candidates((const elem_t*)xs, offs, n, k, (uint32_t)c, traverse_grid(a),
+                            [&](uint32_t j, double, double, double, double d2)
                             {
-                            dz = (double)x[(size_t)j * 3 + 2] - xi2;
-                            const bool up = dz >= hz, down = dz < -hz;
-                            dx = up ? dx - xzLz : (down ? dx + xzLz : dx);
-                            dy = up ? dy - yzLz : (down ? dy + yzLz : dy);
-                            dz = up ? dz - Lz : (down ? dz + Lz : dz);
-                            }
-                            {
-                            const bool up = dy >= hy, down = dy < -hy;
-                            dx = up ? dx - xyLy : (down ? dx + xyLy : dx);
-                            dy = up ? dy - Ly : (down ? dy + Ly : dy);
-                            }
-                            {
-                            const bool up = dx >= hx, down = dx < -hx;
-                            dx = up ? dx - Lx : (down ? dx + Lx : dx);
-                            }
-                        const double d2 = (dx * dx + dy * dy) + dz * dz;
-                        if (d2 < r2)
-                            {
-                            const double rr = __builtin_sqrt(d2);
-                            const double q = rr * inv_h;
-                            const double w = sph_weight<KERNEL>(q);
-                            a_n = a_n + w;
-                            a_m = a_m + ms[j] * w;
-                            if constexpr (VOL)
-                                a_v = a_v + vs[j] * w;
-                            }
-                        }
-                    }
-                }
-            }
+#pragma clang fp contract(off)
+                                const double rr = __builtin_sqrt(d2);
+                                const double q = rr * inv_h;
+                                const double w = sph_weight<KERNEL>(q);
+                                a_n = a_n + w;
+                                a_m = a_m + ms[j] * w;
+                                if constexpr (VOL)
+                                    a_v = a_v + vs[j] * w;
+                            });
         }
     // (an entry without a cell: the accumulators are +0.0, and so are the products)
     const double number = a.sigma * a_n, density = a.sigma * a_m, shepard = a.sigma * a_v;
@@ -266,7 +193,7 @@ __global__ __launch_bounds__(SEL_THREADS) void sph_pair_kernel(const SphArgs a, 
             if (a.surface && shepard < a.surface_below)
                 atomicAdd(&s_surface, 1u);
             const uint64_t row = a.rows[k];
-            const double rho = a.density ? sph_column(a.density, a.density_f64, row < a.N ? row : 0) : a.density_default;
+            const double rho = a.density ? column_value(a.density, a.density_f64, row < a.N ? row : 0) : a.density_default;
             const double dev = density - rho;
             if (dev == dev)
                 {
@@ -351,14 +278,6 @@ constexpr size_t SPH_SUMMARY_BYTES = (size_t)SPH_SUMMARY_WORDS * sizeof(uint64_t
 Scratch g_sph_scratch("SPH kernel sums", 1.25, 1u << 16, SPH_SUMMARY_BYTES, sizeof(uint64_t));
 std::mutex g_sph_lock;
 
-size_t sph_round16(size_t bytes)
-    {
-    return (bytes + 15) & ~(size_t)15;
-    }
-
-const char* sph_refused = "a cell id descends or lies outside [0, n_cells], or an entry of the row list lies outside "
-                          "the chunks (nothing was computed)";
-
 template<bool F64, int KERNEL>
 void sph_launch_pair(bool vol, dim3 grid, dim3 block, hipStream_t stream, const SphArgs& a, const uint32_t* offs,
                      const uint32_t* flag_dev, const void* xs, const double* ms, const double* vs, double* out_number,
@@ -385,19 +304,9 @@ int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, d
     const auto fail = [err](const char* why) { return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, std::string(what) + ": " + why); };
     if (!out_summary)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    if (a.n >= (1ull << 32))
-        return fail("a list holds fewer than 2^32 entries");
-    if (a.N >= (1ull << 32))
-        return fail("chunks of 2^32 rows or more have no 32-bit row list");
-    uint64_t n_cells = 1;
-    for (int i = 0; i < 3; i++)
-        {
-        if (a.cells[i] < 1 || a.cells[i] > ORDER_MAX_AXIS_CELLS)
-            return fail("every axis takes 1 to 1024 cells");
-        n_cells *= a.cells[i];
-        }
-    if (n_cells > CELLS_MAX_CELLS || n_cells != a.n_cells)
-        return fail("a grid holds 1 to 2^20 cells");
+    int rc = cells_refuse_grid(a.n, a.N, a.cells, a.n_cells, what, err);
+    if (rc != PGSD_SUCCESS)
+        return rc;
     if (a.kernel != SPH_WENDLAND_C2 && a.kernel != SPH_CUBIC_SPLINE)
         return fail("the kernel is 0 (Wendland C2) or 1 (cubic spline)");
     const uint64_t n = a.n;
@@ -407,14 +316,14 @@ int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, d
         return PGSD_SUCCESS;
         }
     if (a.N == 0)
-        return fail(sph_refused);
+        return fail(cells_refused);
     if (!a.rows || !a.cell || !a.pos)
         return PGSD_ERROR_INVALID_ARGUMENT;
     const uint32_t n_blocks = (uint32_t)((n + SEL_THREADS - 1) / SEL_THREADS);
-    const size_t offs_bytes = sph_round16(((size_t)a.n_cells + 2) * sizeof(uint32_t));
-    const size_t xs_bytes = sph_round16((size_t)n * 3 * (a.f64 ? sizeof(double) : sizeof(float)));
-    const size_t col_bytes = sph_round16((size_t)n * sizeof(double));
-    const size_t part_bytes = sph_round16((size_t)n_blocks * sizeof(SphPartial));
+    const size_t offs_bytes = round16(((size_t)a.n_cells + 2) * sizeof(uint32_t));
+    const size_t xs_bytes = round16((size_t)n * 3 * (a.f64 ? sizeof(double) : sizeof(float)));
+    const size_t col_bytes = round16((size_t)n * sizeof(double));
+    const size_t part_bytes = round16((size_t)n_blocks * sizeof(SphPartial));
     const size_t words_bytes = SPH_SUMMARY_BYTES;
     LaunchScope scope(g_sph_lock, g_sph_scratch, 16 + offs_bytes + xs_bytes + 2 * col_bytes + part_bytes + words_bytes, stream,
                       err);
@@ -429,19 +338,12 @@ int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, d
     SphPartial* part = (SphPartial*)((char*)vs + col_bytes);
     unsigned long long* words = (unsigned long long*)((char*)part + part_bytes);
     uint32_t* host_flag = (uint32_t*)scope.mem().mapped;
-    uint32_t* host_flag_dev = (uint32_t*)scope.mem().mapped_dev;
-    __atomic_store_n(host_flag, 0u, __ATOMIC_RELEASE);
     const dim3 block(SEL_THREADS), per_entry(n_blocks);
     const bool vol = a.volume != 0;
-    hipError_t e = hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(words, 0, words_bytes, stream);
+    hipError_t e = cells_open_pass(a.rows, a.cell, n, a.N, a.n_cells, flag_dev, host_flag, (uint32_t*)scope.mem().mapped_dev, offs,
+                                   words, words_bytes, stream);
     if (e == hipSuccess)
         {
-        hipLaunchKernelGGL(cells_check_kernel, per_entry, block, 0, stream, a.rows, a.cell, n, a.N, a.n_cells, flag_dev,
-                           host_flag_dev);
-        hipLaunchKernelGGL(cells_offsets_kernel, dim3((a.n_cells + 2 + SEL_THREADS - 1) / SEL_THREADS), block, 0, stream, a.cell,
-                           n, a.n_cells, flag_dev, offs);
         if (a.f64)
             {
             hipLaunchKernelGGL(sph_compact_kernel<true>, per_entry, block, 0, stream, a, flag_dev, xs, ms, vs);
@@ -467,11 +369,11 @@ int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, d
         }
     if (e == hipSuccess)
         e = hipMemcpyAsync(scope.mem().host, words, words_bytes, hipMemcpyDeviceToHost, stream);
-    const int rc = scope.finish(what, e);
+    rc = scope.finish(what, e);
     if (rc != PGSD_SUCCESS)
         return rc;
     if (__atomic_load_n(host_flag, __ATOMIC_ACQUIRE) != 0)
-        return fail(sph_refused);
+        return fail(cells_refused);
     const uint64_t* landed = (const uint64_t*)scope.mem().host;
     std::copy(landed, landed + SPH_SUMMARY_WORDS, out_summary);
     return PGSD_SUCCESS;

@@ -21,7 +21,8 @@
 //                          each with its list position, leave as one partial per workgroup
 //   sphg_final_kernel      one workgroup: the partials in a fixed strided scan, then the words of the summary
 // No float atomic anywhere, no private (scratch) memory in any instance.  Shared device helpers: pgsd_stats.hpp,
-// pgsd_kernels.hpp; the launcher's host side: pgsd_scratch.hpp.
+// pgsd_kernels.hpp, pgsd_traverse.hpp (the position copy and the column read of the compact kernel as well); the
+// launcher's host side: pgsd_scratch.hpp and pgsd_cells.hpp (the argument checks and the opening sequence).
 #include "pgsd_stats.hpp"
 #include "pgsd_cells.hpp"
 #include "pgsd_traverse.hpp"
@@ -81,12 +82,6 @@ __device__ __forceinline__ SphgPartial sphg_nothing()
     return p;
     }
 
-// one value of a float32 or float64 chunk as a double (exact)
-__device__ __forceinline__ double sphg_element(const void* base, uint32_t f64, uint64_t at)
-    {
-    return f64 ? ((const double*)base)[at] : (double)((const float*)base)[at];
-    }
-
 template<bool F64>
 __global__ __launch_bounds__(SEL_THREADS) void sphg_compact_kernel(const SphGradientsArgs a, const uint32_t* flag_dev,
                                                                    void* __restrict__ xs, double* __restrict__ ms,
@@ -98,26 +93,14 @@ __global__ __launch_bounds__(SEL_THREADS) void sphg_compact_kernel(const SphGrad
     const uint64_t row = a.rows[k];
     if (row >= a.N) // (the check kernel has refused such a list: nothing is loaded for it)
         return;
-    if constexpr (F64)
-        {
-        const double* q = (const double*)a.pos + row * 3;
-        double* o = (double*)xs + k * 3;
-        o[0] = q[0];
-        o[1] = q[1];
-        o[2] = q[2];
-        }
-    else
-        {
-        const u32x3 v = *(const u32x3_a4*)((const uint32_t*)a.pos + row * 3);
-        *(u32x3_a4*)((uint32_t*)xs + k * 3) = v;
-        }
-    const double m = a.mass ? sphg_element(a.mass, a.mass_f64, row) : a.mass_default;
+    compact_position<F64>(a.pos, row, xs, k);
+    const double m = a.mass ? column_value(a.mass, a.mass_f64, row) : a.mass_default;
     ms[k] = m;
     if (a.volume)
-        vs[k] = m / (a.density ? sphg_element(a.density, a.density_f64, row) : a.density_default);
+        vs[k] = m / (a.density ? column_value(a.density, a.density_f64, row) : a.density_default);
 #pragma unroll
     for (int c = 0; c < 3; c++)
-        ws[k * 3 + c] = a.velocity ? sphg_element(a.velocity, a.velocity_f64, row * 3 + c) : 0.0;
+        ws[k * 3 + c] = a.velocity ? column_value(a.velocity, a.velocity_f64, row * 3 + c) : 0.0;
     }
 
 // F(q) = (1/q) dw/dq of pgsd.hoomd.sph_gradient_factor: the operations as written there, one rounding each; only the
@@ -168,18 +151,9 @@ __global__ __launch_bounds__(SEL_THREADS) void sphg_pair_kernel(const SphGradien
     double a_r = 0.0, a_d = 0.0, a_w0 = 0.0, a_w1 = 0.0, a_w2 = 0.0, a_c0 = 0.0, a_c1 = 0.0, a_c2 = 0.0;
     if (has)
         {
-        TraverseGrid g;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-            g.vectors[i] = a.vectors[i];
-        g.r2 = a.r2;
-        g.cells[0] = a.cells[0];
-        g.cells[1] = a.cells[1];
-        g.cells[2] = a.cells[2];
-        g.dims = a.dims;
         const double inv_h = a.inv_h;
         const double vi0 = ws[(size_t)k * 3 + 0], vi1 = ws[(size_t)k * 3 + 1], vi2 = ws[(size_t)k * 3 + 2];
-        traverse_candidates((const elem_t*)xs, offs, n, k, (uint32_t)c, g,
+        traverse_candidates((const elem_t*)xs, offs, n, k, (uint32_t)c, traverse_grid(a),
                             [&](uint32_t j, double dx, double dy, double dz, double d2)
                             {
 #pragma clang fp contract(off)
@@ -332,14 +306,6 @@ constexpr size_t SPHG_SUMMARY_BYTES = (size_t)SPHG_SUMMARY_WORDS * sizeof(uint64
 Scratch g_sphg_scratch("SPH kernel gradients", 1.25, 1u << 16, SPHG_SUMMARY_BYTES, sizeof(uint64_t));
 std::mutex g_sphg_lock;
 
-size_t sphg_round16(size_t bytes)
-    {
-    return (bytes + 15) & ~(size_t)15;
-    }
-
-const char* sphg_refused = "a cell id descends or lies outside [0, n_cells], or an entry of the row list lies outside "
-                           "the chunks (nothing was computed)";
-
 struct SphgBuffers
     {
     const uint32_t* offs;
@@ -375,19 +341,9 @@ int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* ou
     const auto fail = [err](const char* why) { return launch_fail(err, PGSD_ERROR_INVALID_ARGUMENT, std::string(what) + ": " + why); };
     if (!out_summary)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    if (a.n >= (1ull << 32))
-        return fail("a list holds fewer than 2^32 entries");
-    if (a.N >= (1ull << 32))
-        return fail("chunks of 2^32 rows or more have no 32-bit row list");
-    uint64_t n_cells = 1;
-    for (int i = 0; i < 3; i++)
-        {
-        if (a.cells[i] < 1 || a.cells[i] > ORDER_MAX_AXIS_CELLS)
-            return fail("every axis takes 1 to 1024 cells");
-        n_cells *= a.cells[i];
-        }
-    if (n_cells > CELLS_MAX_CELLS || n_cells != a.n_cells)
-        return fail("a grid holds 1 to 2^20 cells");
+    int rc = cells_refuse_grid(a.n, a.N, a.cells, a.n_cells, what, err);
+    if (rc != PGSD_SUCCESS)
+        return rc;
     if (a.kernel != SPH_WENDLAND_C2 && a.kernel != SPH_CUBIC_SPLINE)
         return fail("the kernel is 0 (Wendland C2) or 1 (cubic spline)");
     const uint64_t n = a.n;
@@ -397,15 +353,15 @@ int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* ou
         return PGSD_SUCCESS;
         }
     if (a.N == 0)
-        return fail(sphg_refused);
+        return fail(cells_refused);
     if (!a.rows || !a.cell || !a.pos)
         return PGSD_ERROR_INVALID_ARGUMENT;
     const uint32_t n_blocks = (uint32_t)((n + SEL_THREADS - 1) / SEL_THREADS);
-    const size_t offs_bytes = sphg_round16(((size_t)a.n_cells + 2) * sizeof(uint32_t));
-    const size_t xs_bytes = sphg_round16((size_t)n * 3 * (a.f64 ? sizeof(double) : sizeof(float)));
-    const size_t col_bytes = sphg_round16((size_t)n * sizeof(double));
-    const size_t vel_bytes = sphg_round16((size_t)n * 3 * sizeof(double));
-    const size_t part_bytes = sphg_round16((size_t)n_blocks * sizeof(SphgPartial));
+    const size_t offs_bytes = round16(((size_t)a.n_cells + 2) * sizeof(uint32_t));
+    const size_t xs_bytes = round16((size_t)n * 3 * (a.f64 ? sizeof(double) : sizeof(float)));
+    const size_t col_bytes = round16((size_t)n * sizeof(double));
+    const size_t vel_bytes = round16((size_t)n * 3 * sizeof(double));
+    const size_t part_bytes = round16((size_t)n_blocks * sizeof(SphgPartial));
     const size_t words_bytes = SPHG_SUMMARY_BYTES;
     LaunchScope scope(g_sphg_lock, g_sphg_scratch,
                       16 + offs_bytes + xs_bytes + 2 * col_bytes + vel_bytes + part_bytes + words_bytes, stream, err);
@@ -421,20 +377,13 @@ int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* ou
     SphgPartial* part = (SphgPartial*)((char*)ws + vel_bytes);
     unsigned long long* words = (unsigned long long*)((char*)part + part_bytes);
     uint32_t* host_flag = (uint32_t*)scope.mem().mapped;
-    uint32_t* host_flag_dev = (uint32_t*)scope.mem().mapped_dev;
-    __atomic_store_n(host_flag, 0u, __ATOMIC_RELEASE);
     const dim3 block(SEL_THREADS), per_entry(n_blocks);
     const bool vol = a.volume != 0;
     const SphgBuffers b = {offs, flag_dev, xs, ms, vs, ws, out_rate, out_divergence, out_curl, out_normal, words, part};
-    hipError_t e = hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(words, 0, words_bytes, stream);
+    hipError_t e = cells_open_pass(a.rows, a.cell, n, a.N, a.n_cells, flag_dev, host_flag, (uint32_t*)scope.mem().mapped_dev, offs,
+                                   words, words_bytes, stream);
     if (e == hipSuccess)
         {
-        hipLaunchKernelGGL(cells_check_kernel, per_entry, block, 0, stream, a.rows, a.cell, n, a.N, a.n_cells, flag_dev,
-                           host_flag_dev);
-        hipLaunchKernelGGL(cells_offsets_kernel, dim3((a.n_cells + 2 + SEL_THREADS - 1) / SEL_THREADS), block, 0, stream, a.cell,
-                           n, a.n_cells, flag_dev, offs);
         if (a.f64)
             {
             hipLaunchKernelGGL(sphg_compact_kernel<true>, per_entry, block, 0, stream, a, flag_dev, xs, ms, vs, ws);
@@ -456,11 +405,11 @@ int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* ou
         }
     if (e == hipSuccess)
         e = hipMemcpyAsync(scope.mem().host, words, words_bytes, hipMemcpyDeviceToHost, stream);
-    const int rc = scope.finish(what, e);
+    rc = scope.finish(what, e);
     if (rc != PGSD_SUCCESS)
         return rc;
     if (__atomic_load_n(host_flag, __ATOMIC_ACQUIRE) != 0)
-        return fail(sphg_refused);
+        return fail(cells_refused);
     const uint64_t* landed = (const uint64_t*)scope.mem().host;
     std::copy(landed, landed + SPHG_SUMMARY_WORDS, out_summary);
     return PGSD_SUCCESS;

@@ -5,8 +5,9 @@
 // row of the grid; the clamping of what comes from the offsets to n; HOOMD's single-shift minimum image in float64
 // without contraction (pgsd.hoomd.pair_displacement) and the strict test d2 < r2.  The functor receives (j, dx, dy, dz, d2)
 // of every candidate that passes, in the defined order, and is inlined with what it captures: accumulators it holds by
-// reference stay in registers.  Used by pgsd_sph_gradients.hip; pgsd_neighbours.hip and pgsd_sph.hip still carry their own
-// copies of this loop.  Seen by the HIP compiler alone.
+// reference stay in registers.  With it what the compact kernels of the same units share: the copy of one position row
+// into xs and the read of one column value.  Used by pgsd_neighbours.hip, pgsd_sph.hip and pgsd_sph_gradients.hip, which
+// carry no copy of any of it.  Seen by the HIP compiler alone.
 #ifndef PGSD_TRAVERSE_HPP
 #define PGSD_TRAVERSE_HPP
 
@@ -22,6 +23,45 @@ struct TraverseGrid
     uint32_t cells[3];
     uint32_t dims;
     };
+
+// the grid of a family's argument struct (NeighboursArgs, SphArgs, SphGradientsArgs)
+template<typename Args> __device__ __forceinline__ TraverseGrid traverse_grid(const Args& a)
+    {
+    TraverseGrid g;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+        g.vectors[i] = a.vectors[i];
+    g.r2 = a.r2;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        g.cells[i] = a.cells[i];
+    g.dims = a.dims;
+    return g;
+    }
+
+// xs[k] = pos[row], three elements of the chunk's own type (float32 as one 12-byte word triple)
+template<bool F64> __device__ __forceinline__ void compact_position(const void* pos, uint64_t row, void* __restrict__ xs, uint64_t k)
+    {
+    if constexpr (F64)
+        {
+        const double* q = (const double*)pos + row * 3;
+        double* o = (double*)xs + k * 3;
+        o[0] = q[0];
+        o[1] = q[1];
+        o[2] = q[2];
+        }
+    else
+        {
+        const u32x3 v = *(const u32x3_a4*)((const uint32_t*)pos + row * 3);
+        *(u32x3_a4*)((uint32_t*)xs + k * 3) = v;
+        }
+    }
+
+// one value of a float32 or float64 column as a double (exact)
+__device__ __forceinline__ double column_value(const void* base, uint32_t f64, uint64_t at)
+    {
+    return f64 ? ((const double*)base)[at] : (double)((const float*)base)[at];
+    }
 
 // xs: n x 3 compacted positions of element type elem_t; offs: n_cells + 1 CSR offsets; k: the entry, c: its cell id,
 // inside [0, n_cells)

@@ -99,6 +99,12 @@ CASES = {
     'half_box': (_half_box(), dict(box=ORTHO, r=1.3)),
     'on_edges': (_on_edges(), dict(box=CUBE, r=1.0)),
     'boundary': (np.array([[0, 0, 0], [0.5, 0, 0]], np.float64), dict(box=CUBE, r=0.5)),
+    # x axes of 4 and 5 cells, the smallest at which the first and last cell of a row take two x-runs and the inner
+    # ones one (and one of 1 beside them); test_a_case_equals_the_model walks these with a pair histogram as well
+    'x_runs_444': (random_rows(40, 400, CUBE, np.float64), dict(box=CUBE, r=2.0, cells=(4, 4, 4))),
+    'x_runs_511': (random_rows(41, 300, CUBE, np.float64), dict(box=CUBE, r=1.6, cells=(5, 1, 1))),
+    'x_runs_flat_421': (random_rows(42, 300, FLAT, np.float64, 2), dict(box=FLAT, r=1.3, cells=(4, 2, 1), dimensions=2)),
+    'x_runs_triclinic_154': (random_rows(43, 300, TRICLINIC, np.float64), dict(box=TRICLINIC, r=1.3, cells=(1, 5, 4))),
 }
 for _k, (_name, (_switch, _case)) in enumerate(sorted(MUTATIONS.items())):
     _kw = dict(_case)
@@ -184,6 +190,10 @@ def test_a_case_equals_the_model(data, name, key):
     with fl.open(path, 'r') as f:
         got, want = census(f, chunk(name, key), host, **kw)
         assert equal(got, want, (name, key))
+        if name.startswith('x_runs'):       # the HIST instances over the same runs; no entry is without a neighbour
+            binned, model = census(f, chunk(name, key), host, bins=3, **kw)
+            assert equal(binned, model, (name, key, 3)) and int(binned.pair_hist.sum()) == binned.pairs == got.pairs
+            assert got.nowhere == 0 and got.count_min >= 1
         f.wait_read()
     assert want.n == len(host) and int(want.count_hist.sum()) + want.nowhere == want.n
     if name == 'all_nowhere':
