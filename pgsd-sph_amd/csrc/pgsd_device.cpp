@@ -668,129 +668,6 @@ void device_pipeline_read_counters(DevicePipeline* p, uint64_t* pread_bytes, uin
     p->read_counters(pread_bytes, h2d_bytes, reset);
     }
 
-int device_pipeline_select_domain(DevicePipeline* p, long long file_offset, size_t bytes, const DomainArgs& d,
-                                  uint32_t* out_rows, uint64_t* out_count, std::string* err)
-    {
-    return report(p, p->select_domain(file_offset, bytes, d, out_rows, out_count), err, true);
-    }
-
-int device_pipeline_select_where(DevicePipeline* p, const ChunkRange* ranges, const WhereArgs& w, uint32_t* out_rows,
-                                 uint64_t* out_count, std::string* err)
-    {
-    return report(p, p->select_where(ranges, w, out_rows, out_count), err, true);
-    }
-
-int device_pipeline_select_halo(DevicePipeline* p, long long file_offset, size_t bytes, const HaloArgs& h, uint32_t* out_rows,
-                                int32_t* out_shift, uint64_t out_counts[2], std::string* err)
-    {
-    return report(p, p->select_halo(file_offset, bytes, h, out_rows, out_shift, out_counts), err, true);
-    }
-
-int device_pipeline_domain_histogram(DevicePipeline* p, long long file_offset, size_t bytes, const DomainArgs& d,
-                                     uint32_t bins, uint64_t* out_hist, std::string* err)
-    {
-    return report(p, p->domain_histogram(file_offset, bytes, d, bins, out_hist), err, true);
-    }
-
-int device_pipeline_domain_counts(DevicePipeline* p, long long file_offset, size_t bytes, const CellArgs& c,
-                                  uint64_t* out_counts, uint64_t* out_nowhere, std::string* err)
-    {
-    return report(p, p->domain_counts(file_offset, bytes, c, out_counts, out_nowhere), err, true);
-    }
-
-int device_pipeline_order_rows(DevicePipeline* p, long long file_offset, size_t bytes, const OrderArgs& o, uint32_t* rows,
-                               int32_t* shift, int32_t* out_cell, std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->order_rows(file_offset, bytes, o, rows, shift, out_cell, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
-int device_pipeline_chunk_stats(DevicePipeline* p, long long file_offset, size_t bytes, const StatsArgs& s,
-                                uint64_t* out_counts, double* out_values, std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->chunk_stats(file_offset, bytes, s, out_counts, out_values, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
-int device_pipeline_frame_moments(DevicePipeline* p, const ChunkRange* ranges, const MomentsArgs& m, uint64_t* out_counts,
-                                  double* out_sums, std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->frame_moments(ranges, m, out_counts, out_sums, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
-int device_pipeline_frame_displacements(DevicePipeline* p, const ChunkRange* ranges, const DisplacementArgs& d,
-                                        uint64_t* out_counts, double* out_values, std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->frame_displacements(ranges, d, out_counts, out_values, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
-int device_pipeline_cell_offsets(DevicePipeline* p, const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets,
-                                 std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->cell_offsets(cell, n, n_cells, out_offsets, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
-int device_pipeline_cell_moments(DevicePipeline* p, const ChunkRange* ranges, const CellMomentsArgs& c, uint64_t* out_counts,
-                                 double* out_sums, std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->cell_moments(ranges, c, out_counts, out_sums, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
-int device_pipeline_neighbours(DevicePipeline* p, long long file_offset, size_t bytes, const NeighboursArgs& a,
-                               const double* edges2, uint32_t* out_count, double* out_nearest2, uint32_t* out_nearest,
-                               uint64_t* out_summary, double* out_closest2, std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->neighbours(file_offset, bytes, a, edges2, out_count, out_nearest2, out_nearest, out_summary,
-                                     out_closest2, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
-int device_pipeline_sph_sums(DevicePipeline* p, const ChunkRange* ranges, const SphArgs& a, double* out_number,
-                             double* out_density, double* out_shepard, uint64_t* out_summary, std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->sph_sums(ranges, a, out_number, out_density, out_shepard, out_summary, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
-int device_pipeline_sph_gradients(DevicePipeline* p, const ChunkRange* ranges, const SphGradientsArgs& a, double* out_rate,
-                                  double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary,
-                                  std::string* err)
-    {
-    std::string local;
-    int rc = report(p, p->sph_gradients(ranges, a, out_rate, out_divergence, out_curl, out_normal, out_summary, &local), err, true);
-    if (rc != PGSD_SUCCESS && err && !local.empty())
-        *err = local; // the launcher's own message comes first
-    return rc;
-    }
-
 void device_pipeline_set_source_stream(DevicePipeline* p, void* stream)
     {
     p->set_source_stream(stream);

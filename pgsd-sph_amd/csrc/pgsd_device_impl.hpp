@@ -2,7 +2,7 @@
 // pgsd_device.cpp):
 //   pgsd_device.cpp        construction, what the pipeline owns (parked sets, arenas, direct arena, events), error state
 //   pgsd_device_write.cpp  HBM -> file: stage / commit, dispatcher, writers, drain, compare / copy-staged
-//   pgsd_device_read.cpp   file -> HBM: reader engine, spans, row plans, domain selection, deferred unpack
+//   pgsd_device_read.cpp   file -> HBM: reader engine, spans, row plans, deferred unpack, the staged GPU passes
 // Everything else in the library goes through the device_pipeline_* functions of pgsd_internal.hpp.
 #ifndef PGSD_DEVICE_IMPL_HPP
 #define PGSD_DEVICE_IMPL_HPP
@@ -139,27 +139,11 @@ class DevicePipeline
     int read_rows_submit(long long file_offset, size_t bytes, pgsd_unpack_job job, uint64_t src_N, const uint32_t* rows,
                          uint64_t n);
     int plan_rows(RowPlan& plan, std::string* err);
-    int select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count);
-    int select_where(const ChunkRange* ranges, WhereArgs w, uint32_t* out_rows, uint64_t* out_count);
-    int select_halo(long long file_offset, size_t bytes, HaloArgs h, uint32_t* out_rows, int32_t* out_shift,
-                    uint64_t out_counts[2]);
-    int domain_histogram(long long file_offset, size_t bytes, DomainArgs d, uint32_t bins, uint64_t* out_hist);
-    int domain_counts(long long file_offset, size_t bytes, CellArgs c, uint64_t* out_counts, uint64_t* out_nowhere);
-    int order_rows(long long file_offset, size_t bytes, OrderArgs o, uint32_t* rows, int32_t* shift, int32_t* out_cell,
-                   std::string* why);
-    int chunk_stats(long long file_offset, size_t bytes, StatsArgs s, uint64_t* out_counts, double* out_values,
-                    std::string* why);
-    int frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums, std::string* why);
-    int frame_displacements(const ChunkRange* ranges, DisplacementArgs d, uint64_t* out_counts, double* out_values,
-                            std::string* why);
-    int cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets, std::string* why);
-    int cell_moments(const ChunkRange* ranges, CellMomentsArgs c, uint64_t* out_counts, double* out_sums, std::string* why);
-    int neighbours(long long file_offset, size_t bytes, NeighboursArgs a, const double* edges2, uint32_t* out_count,
-                   double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2, std::string* why);
-    int sph_sums(const ChunkRange* ranges, SphArgs a, double* out_number, double* out_density, double* out_shepard,
-                 uint64_t* out_summary, std::string* why);
-    int sph_gradients(const ChunkRange* ranges, SphGradientsArgs a, double* out_rate, double* out_divergence, double* out_curl,
-                      double* out_normal, uint64_t* out_summary, std::string* why);
+    // the one road of a GPU pass over whole staged chunks: the device_pipeline_<pass> functions are defined on it, in
+    // pgsd_device_read.cpp
+    template<class Launch>
+    int staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N,
+                      bool callers_memory, std::string* err, Launch launch, int refused = PGSD_SUCCESS);
     int wait_read();
 
     // ---- accessors ----
@@ -260,10 +244,7 @@ class DevicePipeline
         {
         STAGED_MAX_CHUNKS = (WHERE_MAX_TERMS + 1 > GROUPED_CHUNKS ? WHERE_MAX_TERMS + 1 : GROUPED_CHUNKS)
         };
-    template<class Enqueue>
-    int staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint64_t N, bool callers_memory,
-                      std::string* why, Enqueue enqueue, int refused = PGSD_SUCCESS);
-    template<class Launch> int staged_grouped(const ChunkRange* ranges, GroupedArgs& g, std::string* why, Launch launch);
+    int stage_present(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N);
 
     // Who guards what.  m_mutex: the slab ring's free list, the job queue, tickets, committed direct chunks, every event
     // list and pool, both outstanding counts, m_stop, the error state, the statistics.  m_copy_mutex: enqueues on the

@@ -410,233 +410,227 @@ int DevicePipeline::stage_chunks(const ChunkRange* ranges, size_t n, uint64_t N,
     return rc;
     }
 
-// One staged launch, the flow of every GPU pass over whole chunks: enter(); the n chunks of `ranges` (N rows each) into
-// HBM -- stage_chunks looks in the kept list first, so a chunk that an earlier selection, census, ordering or reduction
-// of this frame staged is not read again, and every chunk stays kept until the next wait_read for an indexed read of
-// the same chunk --; *slots[i] receives chunk i's staged rows; where the pass writes or reads memory of the caller's on
-// the device (`callers_memory`: a row list, shifts), what the caller's stream still does with that memory comes first;
-// `enqueue(why)` launches on the pack stream, synchronises it and returns a pgsd_error; a PGSD_ERROR_DEVICE fails the
-// pipeline with the launcher's message, where the caller takes one.  `refused`: what the entry point has against its
-// arguments, returned once the pipeline is entered.
-template<class Enqueue>
-int DevicePipeline::staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint64_t N, bool callers_memory,
-                                  std::string* why, Enqueue enqueue, int refused)
+// The chunks of a pass that are present (bit i of `present`: ranges[i] is stored, N rows) into HBM through stage_chunks;
+// *slots[i] receives chunk i's staged rows, null where the chunk is absent.  Two slots of one file range -- an elided chunk
+// that both frames of a displacement read from frame 0, one chunk given as mass and as density -- are staged once and
+// share the address: the staging is never handed one range twice.
+int DevicePipeline::stage_present(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N)
     {
-    int rc = enter();
-    if (rc != PGSD_SUCCESS)
-        return rc;
+    if (n > STAGED_MAX_CHUNKS)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    ChunkRange stored[STAGED_MAX_CHUNKS] = {};
     const void* src[STAGED_MAX_CHUNKS] = {};
-    if (refused != PGSD_SUCCESS || n > STAGED_MAX_CHUNKS)
-        return refused != PGSD_SUCCESS ? refused : PGSD_ERROR_INVALID_ARGUMENT;
-    rc = stage_chunks(ranges, n, N, src);
-    if (rc != PGSD_SUCCESS)
-        return rc;
+    int at[STAGED_MAX_CHUNKS]; // slot i's place in `stored`; -1: absent
+    size_t n_stored = 0;
     for (size_t i = 0; i < n; i++)
-        *slots[i] = src[i];
-    if (callers_memory)
         {
-        rc = order_after_source();
-        if (rc != PGSD_SUCCESS)
-            return rc;
+        at[i] = -1;
+        if (!(present & (1u << i)))
+            continue;
+        for (size_t j = 0; j < i && at[i] < 0; j++)
+            if (at[j] >= 0 && ranges[j].file_offset == ranges[i].file_offset && ranges[j].bytes == ranges[i].bytes)
+                at[i] = at[j];
+        if (at[i] < 0)
+            {
+            at[i] = (int)n_stored;
+            stored[n_stored++] = ranges[i];
+            }
         }
-    rc = enqueue(why);
-    if (rc == PGSD_ERROR_DEVICE && why)
-        fail(*why);
+    const int rc = stage_chunks(stored, n_stored, N, src);
+    for (size_t i = 0; i < n && rc == PGSD_SUCCESS; i++)
+        *slots[i] = at[i] < 0 ? nullptr : src[at[i]];
     return rc;
     }
 
-// Domain selection over the position chunk; the row list is the caller's.
-int DevicePipeline::select_domain(long long file_offset, size_t bytes, DomainArgs d, uint32_t* out_rows, uint64_t* out_count)
+// One staged launch, the flow of every GPU pass over whole chunks and the body of its device_pipeline_<pass> below:
+// enter(); `refused`, what the pass has against its arguments, returned once the pipeline is entered; the chunks that are
+// present into HBM (stage_present) -- stage_chunks looks in the kept list first, so a chunk that an earlier selection,
+// census, ordering or reduction of this frame staged is not read again, and every chunk stays kept until the next
+// wait_read for an indexed read of the same chunk --; where the pass writes or reads memory of the caller's on the device
+// (`callers_memory`: a row list, shifts), what the caller's stream still does with that memory comes first;
+// `launch(stream, why)` launches on the pack stream, synchronises it and returns a pgsd_error; a PGSD_ERROR_DEVICE fails
+// the pipeline with the launcher's message.  The message of a failure, for all fourteen passes: the launcher's own first,
+// else the pipeline's, else the thread's last error.
+template<class Launch>
+int DevicePipeline::staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N,
+                                  bool callers_memory, std::string* err, Launch launch, int refused)
+    {
+    std::string why;
+    int rc = enter();
+    if (rc == PGSD_SUCCESS)
+        rc = refused;
+    if (rc == PGSD_SUCCESS)
+        rc = stage_present(ranges, slots, n, present, N);
+    if (rc == PGSD_SUCCESS && callers_memory)
+        rc = order_after_source();
+    if (rc == PGSD_SUCCESS)
+        {
+        rc = launch(m_res.pack_stream, &why);
+        if (rc == PGSD_ERROR_DEVICE)
+            fail(why);
+        }
+    if (rc != PGSD_SUCCESS && err)
+        *err = !why.empty() ? why : !error().empty() ? error() : std::string(last_error());
+    return rc;
+    }
+
+// a pass over one chunk (N rows, staged into *slot)
+template<class Launch>
+static int one_chunk_pass(DevicePipeline* p, long long file_offset, size_t bytes, const void** slot, uint64_t N,
+                          bool callers_memory, std::string* err, Launch launch)
     {
     const ChunkRange range = {file_offset, bytes};
-    const void** const slot = &d.pos;
-    std::string message;
-    return staged_launch(&range, &slot, 1, d.N, true, &message, [&](std::string* err)
-                         { return launch_select_domain(d, out_rows, out_count, m_res.pack_stream, err); });
+    return p->staged_launch(&range, &slot, 1, 1u, N, callers_memory, err, launch);
+    }
+
+// A grouped reduction over up to five chunks of one N: the stored chunks are staged, the absent ones stay null.
+template<class Launch>
+static int grouped_pass(DevicePipeline* p, const ChunkRange* ranges, GroupedArgs& g, std::string* err, Launch launch)
+    {
+    const void** slots[GROUPED_CHUNKS];
+    for (int i = 0; i < GROUPED_CHUNKS; i++)
+        slots[i] = &g.chunk[i];
+    return p->staged_launch(ranges, slots, GROUPED_CHUNKS, g.present, g.N, true, err, launch);
+    }
+
+// Domain selection over the position chunk; the row list is the caller's.
+int device_pipeline_select_domain(DevicePipeline* p, long long file_offset, size_t bytes, const DomainArgs& args,
+                                  uint32_t* out_rows, uint64_t* out_count, std::string* err)
+    {
+    DomainArgs d = args;
+    return one_chunk_pass(p, file_offset, bytes, &d.pos, d.N, true, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_select_domain(d, out_rows, out_count, stream, why); });
     }
 
 // Ghost layer selection: the halo kernels in place of the domain's; the lists are the caller's.
-int DevicePipeline::select_halo(long long file_offset, size_t bytes, HaloArgs h, uint32_t* out_rows, int32_t* out_shift,
-                                uint64_t out_counts[2])
+int device_pipeline_select_halo(DevicePipeline* p, long long file_offset, size_t bytes, const HaloArgs& args, uint32_t* out_rows,
+                                int32_t* out_shift, uint64_t out_counts[2], std::string* err)
     {
-    const ChunkRange range = {file_offset, bytes};
-    const void** const slot = &h.d.pos;
-    std::string message;
-    return staged_launch(&range, &slot, 1, h.d.N, true, &message, [&](std::string* err)
-                         { return launch_select_halo(h, out_rows, out_shift, out_counts, m_res.pack_stream, err); });
+    HaloArgs h = args;
+    return one_chunk_pass(p, file_offset, bytes, &h.d.pos, h.d.N, true, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_select_halo(h, out_rows, out_shift, out_counts, stream, why); });
     }
 
 // Group selection: the chunks of the terms, then the position chunk of the domain, if there is one.
-int DevicePipeline::select_where(const ChunkRange* ranges, WhereArgs w, uint32_t* out_rows, uint64_t* out_count)
+int device_pipeline_select_where(DevicePipeline* p, const ChunkRange* ranges, const WhereArgs& args, uint32_t* out_rows,
+                                 uint64_t* out_count, std::string* err)
     {
+    WhereArgs w = args;
     const int refused = w.n_terms > WHERE_MAX_TERMS ? PGSD_ERROR_INVALID_ARGUMENT : PGSD_SUCCESS;
     const void** slots[WHERE_MAX_TERMS + 1];
     const uint32_t n_terms = refused ? 0 : w.n_terms;
     for (uint32_t j = 0; j < n_terms; j++)
         slots[j] = &w.t[j].base;
     slots[n_terms] = &w.d.pos;
-    std::string message;
-    return staged_launch(
-        ranges, slots, n_terms + (w.has_domain ? 1 : 0), w.N, true, &message,
-        [&](std::string* err) { return launch_select_where(w, out_rows, out_count, m_res.pack_stream, err); }, refused);
+    const uint32_t n = n_terms + (w.has_domain ? 1 : 0);
+    return p->staged_launch(
+        ranges, slots, n, (1u << n) - 1, w.N, true, err,
+        [&](hipStream_t stream, std::string* why) { return launch_select_where(w, out_rows, out_count, stream, why); }, refused);
     }
 
 // Domain census: one counting pass, the result on the host.  Nothing of the caller's is touched on the device, so there
 // is no source stream to order behind.
-int DevicePipeline::domain_histogram(long long file_offset, size_t bytes, DomainArgs d, uint32_t bins, uint64_t* out_hist)
+int device_pipeline_domain_histogram(DevicePipeline* p, long long file_offset, size_t bytes, const DomainArgs& args,
+                                     uint32_t bins, uint64_t* out_hist, std::string* err)
     {
-    const ChunkRange range = {file_offset, bytes};
-    const void** const slot = &d.pos;
-    std::string message;
-    return staged_launch(&range, &slot, 1, d.N, false, &message, [&](std::string* err)
-                         { return launch_axis_histograms(d, bins, out_hist, m_res.pack_stream, err); });
+    DomainArgs d = args;
+    return one_chunk_pass(p, file_offset, bytes, &d.pos, d.N, false, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_axis_histograms(d, bins, out_hist, stream, why); });
     }
 
-int DevicePipeline::domain_counts(long long file_offset, size_t bytes, CellArgs c, uint64_t* out_counts, uint64_t* out_nowhere)
+int device_pipeline_domain_counts(DevicePipeline* p, long long file_offset, size_t bytes, const CellArgs& args,
+                                  uint64_t* out_counts, uint64_t* out_nowhere, std::string* err)
     {
-    const ChunkRange range = {file_offset, bytes};
-    const void** const slot = &c.d.pos;
-    std::string message;
-    return staged_launch(&range, &slot, 1, c.d.N, false, &message, [&](std::string* err)
-                         { return launch_cell_counts(c, out_counts, out_nowhere, m_res.pack_stream, err); });
+    CellArgs c = args;
+    return one_chunk_pass(p, file_offset, bytes, &c.d.pos, c.d.N, false, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_cell_counts(c, out_counts, out_nowhere, stream, why); });
     }
 
 // Cell order: keys, sort and apply; the lists are the caller's and are written in place.
-int DevicePipeline::order_rows(long long file_offset, size_t bytes, OrderArgs o, uint32_t* rows, int32_t* shift,
-                               int32_t* out_cell, std::string* why)
+int device_pipeline_order_rows(DevicePipeline* p, long long file_offset, size_t bytes, const OrderArgs& args, uint32_t* rows,
+                               int32_t* shift, int32_t* out_cell, std::string* err)
     {
-    const ChunkRange range = {file_offset, bytes};
-    const void** const slot = &o.d.pos;
-    return staged_launch(&range, &slot, 1, o.d.N, true, why, [&](std::string* err)
-                         { return launch_order_rows(o, rows, shift, out_cell, m_res.pack_stream, err); });
+    OrderArgs o = args;
+    return one_chunk_pass(p, file_offset, bytes, &o.d.pos, o.d.N, true, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_order_rows(o, rows, shift, out_cell, stream, why); });
     }
 
 // Chunk statistics: the tile and the final kernel; the row list is the caller's.
-int DevicePipeline::chunk_stats(long long file_offset, size_t bytes, StatsArgs s, uint64_t* out_counts, double* out_values,
-                                std::string* why)
+int device_pipeline_chunk_stats(DevicePipeline* p, long long file_offset, size_t bytes, const StatsArgs& args,
+                                uint64_t* out_counts, double* out_values, std::string* err)
     {
-    const ChunkRange range = {file_offset, bytes};
-    const void** const slot = &s.base;
-    return staged_launch(&range, &slot, 1, s.N, true, why, [&](std::string* err)
-                         { return launch_chunk_stats(s, out_counts, out_values, m_res.pack_stream, err); });
-    }
-
-// A grouped reduction over up to five chunks of one N: only the stored chunks are staged and the absent ones stay null.
-// Two chunks of one file range -- an elided chunk that both frames of a displacement read from frame 0 -- are staged once
-// and share the address: the staging is never handed one range twice.  `launch` runs once every address is filled in.
-template<class Launch>
-int DevicePipeline::staged_grouped(const ChunkRange* ranges, GroupedArgs& g, std::string* why, Launch launch)
-    {
-    ChunkRange stored[GROUPED_CHUNKS];
-    const void** slots[GROUPED_CHUNKS];
-    int same_as[GROUPED_CHUNKS];
-    size_t n_stored = 0;
-    for (int i = 0; i < GROUPED_CHUNKS; i++)
-        {
-        g.chunk[i] = nullptr;
-        same_as[i] = -1;
-        if (!(g.present & (1u << i)))
-            continue;
-        for (int j = 0; j < i && same_as[i] < 0; j++)
-            if ((g.present & (1u << j)) && ranges[j].file_offset == ranges[i].file_offset && ranges[j].bytes == ranges[i].bytes)
-                same_as[i] = same_as[j] < 0 ? j : same_as[j];
-        if (same_as[i] >= 0)
-            continue;
-        stored[n_stored] = ranges[i];
-        slots[n_stored++] = &g.chunk[i];
-        }
-    return staged_launch(stored, slots, n_stored, g.N, true, why, [&](std::string* err)
-                         {
-                             for (int i = 0; i < GROUPED_CHUNKS; i++)
-                                 if (same_as[i] >= 0)
-                                     g.chunk[i] = g.chunk[same_as[i]];
-                             return launch(err);
-                         });
+    StatsArgs s = args;
+    return one_chunk_pass(p, file_offset, bytes, &s.base, s.N, true, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_chunk_stats(s, out_counts, out_values, stream, why); });
     }
 
 // Conservation sums and frame displacements; the row list and the displacements' optional output are the caller's.
-int DevicePipeline::frame_moments(const ChunkRange* ranges, MomentsArgs m, uint64_t* out_counts, double* out_sums,
-                                  std::string* why)
+int device_pipeline_frame_moments(DevicePipeline* p, const ChunkRange* ranges, const MomentsArgs& args, uint64_t* out_counts,
+                                  double* out_sums, std::string* err)
     {
-    return staged_grouped(ranges, m, why, [&](std::string* err)
-                          { return launch_frame_moments(m, out_counts, out_sums, m_res.pack_stream, err); });
+    MomentsArgs m = args;
+    return grouped_pass(p, ranges, m, err, [&](hipStream_t stream, std::string* why)
+                        { return launch_frame_moments(m, out_counts, out_sums, stream, why); });
     }
 
-int DevicePipeline::frame_displacements(const ChunkRange* ranges, DisplacementArgs d, uint64_t* out_counts,
-                                        double* out_values, std::string* why)
+int device_pipeline_frame_displacements(DevicePipeline* p, const ChunkRange* ranges, const DisplacementArgs& args,
+                                        uint64_t* out_counts, double* out_values, std::string* err)
     {
-    return staged_grouped(ranges, d, why, [&](std::string* err)
-                          { return launch_frame_displacements(d, out_counts, out_values, m_res.pack_stream, err); });
+    DisplacementArgs d = args;
+    return grouped_pass(p, ranges, d, err, [&](hipStream_t stream, std::string* why)
+                        { return launch_frame_displacements(d, out_counts, out_values, stream, why); });
     }
 
 // Cell fields: the lists are the caller's.  The offsets call stages nothing; the sums stage the chunks that are present
 // like the conservation sums (the typeid slot stays empty).
-int DevicePipeline::cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets, std::string* why)
+int device_pipeline_cell_offsets(DevicePipeline* p, const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets,
+                                 std::string* err)
     {
-    return staged_launch(nullptr, nullptr, 0, 0, true, why, [&](std::string* err)
-                         { return launch_cell_offsets(cell, n, n_cells, out_offsets, m_res.pack_stream, err); });
+    return p->staged_launch(nullptr, nullptr, 0, 0u, 0, true, err, [&](hipStream_t stream, std::string* why)
+                            { return launch_cell_offsets(cell, n, n_cells, out_offsets, stream, why); });
     }
 
-int DevicePipeline::cell_moments(const ChunkRange* ranges, CellMomentsArgs c, uint64_t* out_counts, double* out_sums,
-                                 std::string* why)
+int device_pipeline_cell_moments(DevicePipeline* p, const ChunkRange* ranges, const CellMomentsArgs& args, uint64_t* out_counts,
+                                 double* out_sums, std::string* err)
     {
-    return staged_grouped(ranges, c, why, [&](std::string* err)
-                          { return launch_cell_moments(c, out_counts, out_sums, m_res.pack_stream, err); });
+    CellMomentsArgs c = args;
+    return grouped_pass(p, ranges, c, err, [&](hipStream_t stream, std::string* why)
+                        { return launch_cell_moments(c, out_counts, out_sums, stream, why); });
     }
 
 // Neighbour census: the position chunk the ordering left staged (or staged here); the lists and the per-entry outputs are
 // the caller's.
-int DevicePipeline::neighbours(long long file_offset, size_t bytes, NeighboursArgs a, const double* edges2, uint32_t* out_count,
-                               double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2,
-                               std::string* why)
+int device_pipeline_neighbours(DevicePipeline* p, long long file_offset, size_t bytes, const NeighboursArgs& args,
+                               const double* edges2, uint32_t* out_count, double* out_nearest2, uint32_t* out_nearest,
+                               uint64_t* out_summary, double* out_closest2, std::string* err)
     {
-    const ChunkRange range = {file_offset, bytes};
-    const void** const slot = &a.pos;
-    return staged_launch(&range, &slot, 1, a.N, true, why, [&](std::string* err)
-                         { return launch_neighbours(a, edges2, out_count, out_nearest2, out_nearest, out_summary, out_closest2,
-                                                    m_res.pack_stream, err); });
+    NeighboursArgs a = args;
+    return one_chunk_pass(p, file_offset, bytes, &a.pos, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_neighbours(a, edges2, out_count, out_nearest2, out_nearest, out_summary, out_closest2,
+                                                     stream, why); });
     }
 
 // SPH kernel sums: the position chunk the ordering left staged (or staged here) and the mass and density chunks that are
 // present; the lists and the per-entry outputs are the caller's.
-int DevicePipeline::sph_sums(const ChunkRange* ranges, SphArgs a, double* out_number, double* out_density, double* out_shepard,
-                             uint64_t* out_summary, std::string* why)
+int device_pipeline_sph_sums(DevicePipeline* p, const ChunkRange* ranges, const SphArgs& args, double* out_number,
+                             double* out_density, double* out_shepard, uint64_t* out_summary, std::string* err)
     {
-    const bool given[3] = {true, (a.present & 2u) != 0, (a.present & 4u) != 0};
-    a.mass = a.density = nullptr;
-    const void** const all[3] = {&a.pos, &a.mass, &a.density};
-    ChunkRange stored[3];
-    const void** slots[3];
-    size_t n_stored = 0;
-    for (int i = 0; i < 3; i++)
-        if (given[i])
-            {
-            stored[n_stored] = ranges[i];
-            slots[n_stored++] = all[i];
-            }
-    return staged_launch(stored, slots, n_stored, a.N, true, why, [&](std::string* err)
-                         { return launch_sph_sums(a, out_number, out_density, out_shepard, out_summary, m_res.pack_stream, err); });
+    SphArgs a = args;
+    const void** const slots[3] = {&a.pos, &a.mass, &a.density};
+    return p->staged_launch(ranges, slots, 3, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                            { return launch_sph_sums(a, out_number, out_density, out_shepard, out_summary, stream, why); });
     }
 
-// SPH kernel gradients: as sph_sums, and the velocity chunk where one is stored
-int DevicePipeline::sph_gradients(const ChunkRange* ranges, SphGradientsArgs a, double* out_rate, double* out_divergence,
-                                  double* out_curl, double* out_normal, uint64_t* out_summary, std::string* why)
+// SPH kernel gradients: as the sums, with one more slot: the velocity chunk where one is stored
+int device_pipeline_sph_gradients(DevicePipeline* p, const ChunkRange* ranges, const SphGradientsArgs& args, double* out_rate,
+                                  double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary,
+                                  std::string* err)
     {
-    const bool given[4] = {true, (a.present & 2u) != 0, (a.present & 4u) != 0, (a.present & 8u) != 0};
-    a.mass = a.density = a.velocity = nullptr;
-    const void** const all[4] = {&a.pos, &a.mass, &a.density, &a.velocity};
-    ChunkRange stored[4];
-    const void** slots[4];
-    size_t n_stored = 0;
-    for (int i = 0; i < 4; i++)
-        if (given[i])
-            {
-            stored[n_stored] = ranges[i];
-            slots[n_stored++] = all[i];
-            }
-    return staged_launch(stored, slots, n_stored, a.N, true, why, [&](std::string* err)
-                         { return launch_sph_gradients(a, out_rate, out_divergence, out_curl, out_normal, out_summary,
-                                                       m_res.pack_stream, err); });
+    SphGradientsArgs a = args;
+    const void** const slots[4] = {&a.pos, &a.mass, &a.density, &a.velocity};
+    return p->staged_launch(ranges, slots, 4, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                            { return launch_sph_gradients(a, out_rate, out_divergence, out_curl, out_normal, out_summary, stream,
+                                                          why); });
     }
 
 int DevicePipeline::wait_read()

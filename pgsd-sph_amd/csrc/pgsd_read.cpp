@@ -304,6 +304,73 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+// An entry point's refusal: "<who>: <msg>" becomes the thread's last error.
+struct Refusal
+    {
+    const char* who;
+    int operator()(const std::string& msg) const
+        {
+        set_last_error(std::string(who) + ": " + msg);
+        return PGSD_ERROR_INVALID_ARGUMENT;
+        }
+    };
+
+// A float chunk of a pair pass, `subject` in the messages: float32 or float64 elements, `columns` columns, and -- the
+// position chunk (no N_expected) -- fewer than 2^32 rows, or -- a column chunk -- the position chunk's *N_expected rows.
+static int float_chunk(const Refusal& refuse, const pgsd_index_entry& c, const std::string& subject, uint32_t columns,
+                       const uint64_t* N_expected, uint32_t* is_f64)
+    {
+    if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
+        return refuse(subject + " holds float32 or float64 elements");
+    if (c.M != columns)
+        return refuse(subject + " has " + std::to_string(columns) + (columns == 1 ? " column" : " columns"));
+    if (!N_expected && c.N >= (1ull << 32))
+        return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+    if (N_expected && c.N != *N_expected)
+        return refuse(subject + " and the position chunk differ in their number of rows");
+    *is_f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    return PGSD_SUCCESS;
+    }
+
+// The grid of a pair pass against its box and its reach (`noun` in the messages: the range, the support 2h):
+// pgsd.hoomd.ghost_fractions and cell_grid_for, from the tilt factors the vectors hold (xy * Ly is an exact product of
+// float32 values, so the quotient is the stored factor).  *n_cells: the cells of the grid.
+static int pair_grid(const Refusal& refuse, const double vectors[6], double reach, const char* noun, uint32_t dimensions,
+                     const uint32_t cells[3], uint32_t* n_cells)
+    {
+    const double Lx = vectors[0], Ly = vectors[1], Lz = vectors[2];
+    if (!(Lx > 0.0 && Ly > 0.0 && (dimensions == 2 || Lz > 0.0)))
+        return refuse("box lengths must be positive (Lz unless dimensions == 2)");
+    const double xy = vectors[3] / Ly, xz = Lz > 0.0 ? vectors[4] / Lz : 0.0, yz = Lz > 0.0 ? vectors[5] / Lz : 0.0;
+    const double t = xy * yz - xz;
+    const double u = 1.0 + xy * xy;
+    const double plane[3] = {Lx / std::sqrt(u + t * t), Ly / std::sqrt(1.0 + yz * yz), Lz};
+    uint64_t n = 1;
+    for (int a = 0; a < 3; a++)
+        {
+        if (cells[a] < 1 || cells[a] > ORDER_MAX_AXIS_CELLS)
+            return refuse("every axis takes 1 to 1024 cells");
+        n *= cells[a];
+        if (a == 2 && dimensions == 2)
+            {
+            if (cells[2] != 1)
+                return refuse("dimensions == 2 takes one z cell (z is not looked at)");
+            continue;
+            }
+        const double g = reach / plane[a];
+        if (!(g <= 0.5))
+            return refuse(std::string("the ") + noun
+                          + " exceeds half the box's nearest plane distance on an axis: an image would count twice");
+        const double most = std::min(std::max(std::floor(1.0 / g), 1.0), (double)ORDER_MAX_AXIS_CELLS);
+        if ((double)cells[a] > most)
+            return refuse(std::string("the cells are narrower than the ") + noun + " on an axis");
+        }
+    if (n > CELLS_MAX_CELLS)
+        return refuse("a grid holds 1 to 2^20 cells");
+    *n_cells = (uint32_t)n;
+    return PGSD_SUCCESS;
+    }
+
 // The file range of a device read of a whole chunk, checked against the file; the flush a read needs comes first.
 static int whole_chunk_range(Impl* s, struct pgsd_handle* handle, const pgsd_index_entry& c, long long* foff, size_t* bytes)
     {
@@ -588,11 +655,7 @@ extern "C" int pgsd_order_rows_by_cell_device(struct pgsd_handle* handle, const 
     Impl* s = impl_of(handle);
     if (!s || !position || !box || !cells)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     OrderArgs o;
     memset(&o, 0, sizeof(o));
     o.n_cells = 1;
@@ -745,11 +808,7 @@ extern "C" int pgsd_chunk_stats_device(struct pgsd_handle* handle, const struct 
     Impl* s = impl_of(handle);
     if (!s || !chunk || !out_counts || !out_values)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     pgsd_index_entry c = *chunk; // a flush may move the index storage
     std::string why;
     if (!chunk_stats_supported(c.type, c.M, with_norm2, &why))
@@ -806,11 +865,7 @@ extern "C" int pgsd_frame_moments_device(struct pgsd_handle* handle, const struc
     Impl* s = impl_of(handle);
     if (!s || !defaults || !out_counts || !out_sums)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     const struct pgsd_index_entry* given[MOMENTS_CHUNKS] = {typeid_chunk, mass, velocity, energy, position};
     if (n_types < 1 || n_types > MOMENTS_MAX_TYPES)
         return refuse("a call takes 1 to 4 types");
@@ -863,11 +918,7 @@ extern "C" int pgsd_cell_offsets_device(struct pgsd_handle* handle, const int32_
     Impl* s = impl_of(handle);
     if (!s || !out_offsets || (n > 0 && !cell))
         return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     if (n >= (1ull << 32))
         return refuse("a list holds fewer than 2^32 entries");
     if (n_cells < 1 || n_cells > CELLS_MAX_CELLS)
@@ -891,11 +942,7 @@ extern "C" int pgsd_cell_moments_device(struct pgsd_handle* handle, const struct
     Impl* s = impl_of(handle);
     if (!s || !defaults || !out_counts || !out_sums || (n > 0 && (!rows || !cell)))
         return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     const struct pgsd_index_entry* given[MOMENTS_CHUNKS] = {nullptr, mass, velocity, energy, position};
     CellMomentsArgs a;
     memset(&a, 0, sizeof(a));
@@ -947,54 +994,22 @@ extern "C" int pgsd_neighbours_device(struct pgsd_handle* handle, const struct p
     if (!s || !position || !vectors || !cells || !out_summary || !out_closest2 || (n > 0 && (!rows || !cell))
         || (bins > 0 && !edges2))
         return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     pgsd_index_entry c = *position; // a flush may move the index storage
-    if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
-        return refuse("the position chunk holds float32 or float64 elements");
-    if (c.M != 3)
-        return refuse("the position chunk has 3 columns");
-    if (c.N >= (1ull << 32))
-        return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+    NeighboursArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = float_chunk(refuse, c, "the position chunk", 3, nullptr, &a.f64);
+    if (rc != PGSD_SUCCESS)
+        return rc;
     if (n >= (1ull << 32))
         return refuse("a list holds fewer than 2^32 entries");
     if (dimensions != 2 && dimensions != 3)
         return refuse("dimensions is 2 or 3");
     if (!(r > 0.0 && r < HUGE_VAL))
         return refuse("the range must be finite and positive");
-    const double Lx = vectors[0], Ly = vectors[1], Lz = vectors[2];
-    if (!(Lx > 0.0 && Ly > 0.0 && (dimensions == 2 || Lz > 0.0)))
-        return refuse("box lengths must be positive (Lz unless dimensions == 2)");
-    // pgsd.hoomd.ghost_fractions and cell_grid_for, from the tilt factors the vectors hold (xy * Ly is an exact product
-    // of float32 values, so the quotient is the stored factor)
-    const double xy = vectors[3] / Ly, xz = Lz > 0.0 ? vectors[4] / Lz : 0.0, yz = Lz > 0.0 ? vectors[5] / Lz : 0.0;
-    const double t = xy * yz - xz;
-    const double u = 1.0 + xy * xy;
-    const double plane[3] = {Lx / std::sqrt(u + t * t), Ly / std::sqrt(1.0 + yz * yz), Lz};
-    uint64_t n_cells = 1;
-    for (int a = 0; a < 3; a++)
-        {
-        if (cells[a] < 1 || cells[a] > ORDER_MAX_AXIS_CELLS)
-            return refuse("every axis takes 1 to 1024 cells");
-        n_cells *= cells[a];
-        if (a == 2 && dimensions == 2)
-            {
-            if (cells[2] != 1)
-                return refuse("dimensions == 2 takes one z cell (z is not looked at)");
-            continue;
-            }
-        const double g = r / plane[a];
-        if (!(g <= 0.5))
-            return refuse("the range exceeds half the box's nearest plane distance on an axis: an image would count twice");
-        const double most = std::min(std::max(std::floor(1.0 / g), 1.0), (double)ORDER_MAX_AXIS_CELLS);
-        if ((double)cells[a] > most)
-            return refuse("the cells are narrower than the range on an axis");
-        }
-    if (n_cells > CELLS_MAX_CELLS)
-        return refuse("a grid holds 1 to 2^20 cells");
+    rc = pair_grid(refuse, vectors, r, "range", dimensions, cells, &a.n_cells);
+    if (rc != PGSD_SUCCESS)
+        return rc;
     if (bins > NEIGHBOURS_MAX_BINS)
         return refuse("the pair histogram holds at most 1024 bins");
     for (uint32_t k = 0; k < bins; k++)
@@ -1002,11 +1017,9 @@ extern "C" int pgsd_neighbours_device(struct pgsd_handle* handle, const struct p
             return refuse("the edges of the pair histogram descend (or are not numbers)");
     long long foff = 0;
     size_t bytes = 0;
-    int rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    rc = whole_chunk_range(s, handle, c, &foff, &bytes);
     if (rc != PGSD_SUCCESS)
         return rc;
-    NeighboursArgs a;
-    memset(&a, 0, sizeof(a));
     a.N = c.N;
     a.rows = rows;
     a.cell = cell;
@@ -1015,9 +1028,7 @@ extern "C" int pgsd_neighbours_device(struct pgsd_handle* handle, const struct p
     a.r = r;
     a.r2 = r * r;
     std::copy(cells, cells + 3, a.cells);
-    a.n_cells = (uint32_t)n_cells;
     a.dims = dimensions;
-    a.f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
     a.bins = bins;
     if (n == 0)
         {
@@ -1045,18 +1056,12 @@ static int sph_arguments(const char* who, Impl* s, struct pgsd_handle* handle, c
                          uint32_t kernel, uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
                          const int32_t* cell, uint64_t n, double surface_below, ChunkRange ranges[4], SphGradientsArgs& a)
     {
-    const auto refuse = [who](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     pgsd_index_entry c = *position; // a flush may move the index storage
-    if (c.type != PGSD_TYPE_FLOAT && c.type != PGSD_TYPE_DOUBLE)
-        return refuse("the position chunk holds float32 or float64 elements");
-    if (c.M != 3)
-        return refuse("the position chunk has 3 columns");
-    if (c.N >= (1ull << 32))
-        return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+    uint32_t f64 = 0, n_cells = 0;
+    int rc = float_chunk(refuse, c, "the position chunk", 3, nullptr, &f64);
+    if (rc != PGSD_SUCCESS)
+        return rc;
     if (n >= (1ull << 32))
         return refuse("a list holds fewer than 2^32 entries");
     if (dimensions != 2 && dimensions != 3)
@@ -1067,74 +1072,36 @@ static int sph_arguments(const char* who, Impl* s, struct pgsd_handle* handle, c
         return refuse("the kernel is 0 (Wendland C2) or 1 (cubic spline)");
     memset(ranges, 0, 4 * sizeof(ChunkRange));
     a = SphGradientsArgs();
-    const struct pgsd_index_entry* columns[2] = {mass, density};
-    for (int i = 0; i < 2; i++)
+    // the column chunks that are stored: ranges[1 + i] and bit 1 + i of `present`
+    const struct
         {
-        if (!columns[i])
+        const struct pgsd_index_entry* entry;
+        const char* subject;
+        uint32_t columns;
+        uint32_t* is_f64;
+        } columns[3] = {{mass, "the mass chunk", 1, &a.mass_f64},
+                        {density, "the density chunk", 1, &a.density_f64},
+                        {velocity, "the velocity chunk", 3, &a.velocity_f64}};
+    for (int i = 0; i < 3; i++)
+        {
+        if (!columns[i].entry)
             continue;
-        const pgsd_index_entry m = *columns[i];
-        const std::string subject = i ? "the density chunk" : "the mass chunk";
-        if (m.type != PGSD_TYPE_FLOAT && m.type != PGSD_TYPE_DOUBLE)
-            return refuse(subject + " holds float32 or float64 elements");
-        if (m.M != 1)
-            return refuse(subject + " has 1 column");
-        if (m.N != c.N)
-            return refuse(subject + " and the position chunk differ in their number of rows");
-        int rc = whole_chunk_range(s, handle, m, &ranges[1 + i].file_offset, &ranges[1 + i].bytes);
+        const pgsd_index_entry m = *columns[i].entry;
+        rc = float_chunk(refuse, m, columns[i].subject, columns[i].columns, &c.N, columns[i].is_f64);
+        if (rc == PGSD_SUCCESS)
+            rc = whole_chunk_range(s, handle, m, &ranges[1 + i].file_offset, &ranges[1 + i].bytes);
         if (rc != PGSD_SUCCESS)
             return rc;
-        (i ? a.density_f64 : a.mass_f64) = m.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
         a.present |= 2u << i;
         }
-    if (velocity)
-        {
-        const pgsd_index_entry m = *velocity;
-        if (m.type != PGSD_TYPE_FLOAT && m.type != PGSD_TYPE_DOUBLE)
-            return refuse("the velocity chunk holds float32 or float64 elements");
-        if (m.M != 3)
-            return refuse("the velocity chunk has 3 columns");
-        if (m.N != c.N)
-            return refuse("the velocity chunk and the position chunk differ in their number of rows");
-        int rc = whole_chunk_range(s, handle, m, &ranges[3].file_offset, &ranges[3].bytes);
-        if (rc != PGSD_SUCCESS)
-            return rc;
-        a.velocity_f64 = m.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
-        a.present |= 8u;
-        }
-    // the range of the search is the support 2h; the grid is checked as pgsd_neighbours_device checks its own:
-    // pgsd.hoomd.ghost_fractions and cell_grid_for, from the tilt factors the vectors hold
+    // the range of the search is the support 2h; the grid is checked as pgsd_neighbours_device checks its own
     const double r = 2.0 * h;
     if (!(r < HUGE_VAL))
         return refuse("the smoothing length must be finite and positive");
-    const double Lx = vectors[0], Ly = vectors[1], Lz = vectors[2];
-    if (!(Lx > 0.0 && Ly > 0.0 && (dimensions == 2 || Lz > 0.0)))
-        return refuse("box lengths must be positive (Lz unless dimensions == 2)");
-    const double xy = vectors[3] / Ly, xz = Lz > 0.0 ? vectors[4] / Lz : 0.0, yz = Lz > 0.0 ? vectors[5] / Lz : 0.0;
-    const double t = xy * yz - xz;
-    const double u = 1.0 + xy * xy;
-    const double plane[3] = {Lx / std::sqrt(u + t * t), Ly / std::sqrt(1.0 + yz * yz), Lz};
-    uint64_t n_cells = 1;
-    for (int k = 0; k < 3; k++)
-        {
-        if (cells[k] < 1 || cells[k] > ORDER_MAX_AXIS_CELLS)
-            return refuse("every axis takes 1 to 1024 cells");
-        n_cells *= cells[k];
-        if (k == 2 && dimensions == 2)
-            {
-            if (cells[2] != 1)
-                return refuse("dimensions == 2 takes one z cell (z is not looked at)");
-            continue;
-            }
-        const double g = r / plane[k];
-        if (!(g <= 0.5))
-            return refuse("the support 2h exceeds half the box's nearest plane distance on an axis: an image would count twice");
-        const double most = std::min(std::max(std::floor(1.0 / g), 1.0), (double)ORDER_MAX_AXIS_CELLS);
-        if ((double)cells[k] > most)
-            return refuse("the cells are narrower than the support 2h on an axis");
-        }
-    if (n_cells > CELLS_MAX_CELLS)
-        return refuse("a grid holds 1 to 2^20 cells");
-    int rc = whole_chunk_range(s, handle, c, &ranges[0].file_offset, &ranges[0].bytes);
+    rc = pair_grid(refuse, vectors, r, "support 2h", dimensions, cells, &n_cells);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = whole_chunk_range(s, handle, c, &ranges[0].file_offset, &ranges[0].bytes);
     if (rc != PGSD_SUCCESS)
         return rc;
     a.N = c.N;
@@ -1156,11 +1123,14 @@ static int sph_arguments(const char* who, Impl* s, struct pgsd_handle* handle, c
     a.surface = a.volume && surface_below == surface_below ? 1u : 0u;
     a.surface_below = surface_below;
     std::copy(cells, cells + 3, a.cells);
-    a.n_cells = (uint32_t)n_cells;
+    a.n_cells = n_cells;
     a.dims = dimensions;
-    a.f64 = c.type == PGSD_TYPE_DOUBLE ? 1u : 0u;
+    a.f64 = f64;
     a.kernel = kernel;
     a.G = -((a.sigma * a.inv_h) * a.inv_h);
+    // (a list of no entry has its result whatever the chunks hold: the entry points return it)
+    if (n > 0 && c.N == 0)
+        return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
     return PGSD_SUCCESS;
     }
 
@@ -1187,11 +1157,6 @@ extern "C" int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgs
         {
         sph_sums_of_nothing(out_summary);
         return PGSD_SUCCESS;
-        }
-    if (a.N == 0)
-        {
-        set_last_error(std::string(who) + ": an entry of the row list lies outside the chunks (nothing was computed)");
-        return PGSD_ERROR_INVALID_ARGUMENT;
         }
     // (the launcher writes the outputs on success only, behind its last check)
     return reduction_call(who, "SPH kernel sums: ", [&](std::string* err)
@@ -1226,11 +1191,6 @@ extern "C" int pgsd_sph_gradients_device(struct pgsd_handle* handle, const struc
         sph_gradients_of_nothing(out_summary);
         return PGSD_SUCCESS;
         }
-    if (a.N == 0)
-        {
-        set_last_error(std::string(who) + ": an entry of the row list lies outside the chunks (nothing was computed)");
-        return PGSD_ERROR_INVALID_ARGUMENT;
-        }
     // (the launcher writes the outputs on success only, behind its last check)
     return reduction_call(who, "SPH kernel gradients: ", [&](std::string* err)
                           { return device_pipeline_sph_gradients(s->dev, ranges, a, out_density_rate, out_divergence, out_curl,
@@ -1255,11 +1215,7 @@ extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const
     Impl* s = impl_of(handle);
     if (!s || !position_a || !position_b || !vectors_a || !vectors_b || !out_counts || !out_values)
         return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     const struct pgsd_index_entry* given[DISPLACEMENT_CHUNKS] = {position_a, image_a, position_b, image_b, typeid_chunk};
     if (n_types < 1 || n_types > DISPLACEMENT_MAX_TYPES)
         return refuse("a call takes 1 to 4 types");
@@ -1324,11 +1280,7 @@ extern "C" int pgsd_select_where_device(struct pgsd_handle* handle, uint32_t n_t
     if (!s || !out_count || (n_terms > 0 && (!term_chunks || !columns || !kinds || !lo || !hi || !sets))
         || (position && (!box || !dlo || !dhi)))
         return PGSD_ERROR_INVALID_ARGUMENT;
-    const auto refuse = [](const std::string& msg)
-    {
-        set_last_error(std::string(who) + ": " + msg);
-        return PGSD_ERROR_INVALID_ARGUMENT;
-    };
+    const Refusal refuse = {who};
     if (n_terms > WHERE_MAX_TERMS)
         return refuse("a predicate has at most 4 terms");
     if (n_terms == 0 && !position)

@@ -539,6 +539,64 @@ def _row_list(who, rows, n):
     return (<uintptr_t>&_no_rows if count == 0 else p_rows), count
 
 
+def _box_vectors(box):
+    """:func:`pgsd.hoomd.box_vectors` of a float32 ``(Lx, Ly, Lz, xy, xz, yz)``, as the pair passes receive them."""
+    from . import hoomd as _hoomd
+    c_box = numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6]
+    if c_box.shape[0] != 6:
+        raise ValueError("box must hold 6 values")
+    return numpy.ascontiguousarray(_hoomd.box_vectors(c_box), dtype=numpy.float64)
+
+
+def _cell_counts(who, cells):
+    """(the grid as a list, its uint32 array) of a pair pass's ``cells``."""
+    grid = [int(v) for v in cells]
+    if len(grid) != 3 or any(not 0 <= v < (1 << 32) for v in grid):
+        raise ValueError("%s: cells holds three counts, each 1 to 1024" % who)
+    return grid, numpy.array(grid, dtype=numpy.uint32)
+
+
+def _sph_kernel(who, kernel):
+    """The library's index of an SPH kernel's name."""
+    from . import hoomd as _hoomd
+    if kernel not in _hoomd.SPH_KERNELS:
+        raise ValueError("%s: the kernel is one of %s: %r" % (who, ', '.join(_hoomd.SPH_KERNELS), kernel))
+    return _hoomd.SPH_KERNELS.index(kernel)
+
+
+def _sph_defaults(who, defaults, density):
+    """(the mass and density that stand for a chunk stored nowhere as float64[2], whether there is a volume sum)."""
+    c_defaults = numpy.ascontiguousarray(
+        numpy.array([1.0, float('nan')] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+    if c_defaults.shape[0] != 2:
+        raise ValueError("%s: defaults holds a mass and a density" % who)
+    return c_defaults, density is not None or c_defaults[1] == c_defaults[1]
+
+
+def _moments_defaults(who, defaults):
+    """The row that stands for every row of a chunk stored nowhere -- mass, v[3], energy, x[3] -- as float64[8]."""
+    c_defaults = numpy.ascontiguousarray(
+        numpy.array([1, 0, 0, 0, 0, 0, 0, 0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+    if c_defaults.shape[0] != 8:
+        raise ValueError("%s: defaults holds mass, v[3], energy, x[3]" % who)
+    return c_defaults
+
+
+def _cell_ordered_lists(who, rows, cell, n):
+    """(address of ``rows``, address of ``cell``, entries) of a row list in cell order and its ids, ``n`` entries each."""
+    p_rows, count = _row_list(who, rows, n)
+    return p_rows, _row_list(who, cell, count)[0], count
+
+
+def _per_entry(count, shape_tail, dtype, device):
+    """(array, address) of a per-entry output in the memory of GPU ``device``: ``count`` entries (room for one at least)
+    of ``shape_tail``; ``(None, 0)`` where ``device`` is ``None``: the output is not wanted."""
+    if device is None:
+        return None, 0
+    out = _device_empty((max(count, 1),) + tuple(shape_tail), dtype, device)
+    return out, out.data_ptr()
+
+
 cdef _raise_refused(who, int retval, fallback, extra, int err):
     """A reduction's return code -> exception: a refusal is a ValueError that carries the library's message."""
     if retval == C.PGSD_ERROR_INVALID_ARGUMENT:
@@ -1510,6 +1568,13 @@ cdef class PGSDFile:
         entry[0] = e[0]
         return 0
 
+    cdef const C.pgsd_index_entry* _optional(self, chunk, C.pgsd_index_entry* entry) except? NULL:
+        """:meth:`_entry` of an optional ``(frame, name)``: ``entry``, filled in, or NULL for ``None``."""
+        if chunk is None:
+            return NULL
+        self._entry(chunk[0], chunk[1], entry)
+        return entry
+
     cdef int _entries(self, chunks, C.pgsd_index_entry* entries, const C.pgsd_index_entry** given) except -1:
         """The five chunk slots of a grouped reduction, each ``(frame, name)`` or ``None``: :meth:`_entry` of every chunk
         that is given, NULL for the others."""
@@ -1759,10 +1824,7 @@ cdef class PGSDFile:
         if len(chunks) != 5:
             raise ValueError("frame_moments_device: chunks holds typeid, mass, velocity, energy, position (or None)")
         self._entries(chunks, entries, given)
-        c_defaults = numpy.ascontiguousarray(
-            numpy.array([1, 0, 0, 0, 0, 0, 0, 0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
-        if c_defaults.shape[0] != 8:
-            raise ValueError("frame_moments_device: defaults holds mass, v[3], energy, x[3]")
+        c_defaults = _moments_defaults("frame_moments_device", defaults)
         if not 0 <= int(type0) < (1 << 32) or not 0 <= int(n_types) < (1 << 32):
             raise ValueError("frame_moments_device: a call takes 1 to 4 types from a type id on")
         cdef uintptr_t c_rows = 0
@@ -1853,12 +1915,8 @@ cdef class PGSDFile:
         if len(chunks) != 4:
             raise ValueError("cell_moments_device: chunks holds mass, velocity, energy, position (or None)")
         self._entries([None] + chunks, entries, given)
-        c_defaults = numpy.ascontiguousarray(
-            numpy.array([1, 0, 0, 0, 0, 0, 0, 0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
-        if c_defaults.shape[0] != 8:
-            raise ValueError("cell_moments_device: defaults holds mass, v[3], energy, x[3]")
-        c_rows, count = _row_list("cell_moments_device", rows, n)
-        c_cell, _ = _row_list("cell_moments_device", cell, count)
+        c_defaults = _moments_defaults("cell_moments_device", defaults)
+        c_rows, c_cell, count = _cell_ordered_lists("cell_moments_device", rows, cell, n)
         cells = int(n_cells)
         if not 0 <= cells < (1 << 32):
             raise ValueError("cell_moments_device: a grid holds 1 to 2^20 cells")
@@ -1909,14 +1967,8 @@ cdef class PGSDFile:
         from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
         cdef C.pgsd_index_entry entry
         self._entry(frame, name, &entry)
-        c_box = numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6]
-        if c_box.shape[0] != 6:
-            raise ValueError("box must hold 6 values")
-        c_vectors = numpy.ascontiguousarray(_hoomd.box_vectors(c_box), dtype=numpy.float64)
-        grid = [int(v) for v in cells]
-        if len(grid) != 3 or any(not 0 <= v < (1 << 32) for v in grid):
-            raise ValueError("neighbours_device: cells holds three counts, each 1 to 1024")
-        c_cells = numpy.array(grid, dtype=numpy.uint32)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("neighbours_device", cells)
         k_bins = int(bins)
         if not 0 <= k_bins < (1 << 32):
             raise ValueError("neighbours_device: bins is 0 or 1 to 1024")
@@ -1925,18 +1977,14 @@ cdef class PGSDFile:
             c_edges = numpy.ascontiguousarray(_hoomd.neighbour_edges2(range_, k_bins), dtype=numpy.float64)
         else:
             c_edges = numpy.zeros(1 + (k_bins if k_bins <= 1024 else 0), dtype=numpy.float64)   # (the library refuses the rest)
-        c_rows, count = _row_list("neighbours_device", rows, n)
-        c_cell, _ = _row_list("neighbours_device", cell, count)
+        c_rows, c_cell, count = _cell_ordered_lists("neighbours_device", rows, cell, n)
         summary = numpy.zeros(8 + 257 + (k_bins if k_bins <= 1024 else 0), dtype=numpy.uint64)
         closest2 = numpy.zeros(1, dtype=numpy.float64)
-        cdef uintptr_t p_count = 0, p_nearest2 = 0, p_nearest = 0
-        out_count = out_nearest2 = out_nearest = None
-        if return_rows:
-            device = self.pipeline_device()
-            out_count = _device_empty((max(count, 1),), numpy.int32, device)
-            out_nearest = _device_empty((max(count, 1),), numpy.int32, device)
-            out_nearest2 = _device_empty((max(count, 1),), numpy.float64, device)
-            p_count, p_nearest, p_nearest2 = out_count.data_ptr(), out_nearest.data_ptr(), out_nearest2.data_ptr()
+        cdef uintptr_t p_count, p_nearest2, p_nearest
+        device = self.pipeline_device() if return_rows else None
+        out_count, p_count = _per_entry(count, (), numpy.int32, device)
+        out_nearest, p_nearest = _per_entry(count, (), numpy.int32, device)
+        out_nearest2, p_nearest2 = _per_entry(count, (), numpy.float64, device)
         if not self._explicit_stream:
             self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
         cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
@@ -1991,50 +2039,26 @@ cdef class PGSDFile:
         """
         from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
         cdef C.pgsd_index_entry entry, e_mass, e_density
-        cdef const C.pgsd_index_entry* p_mass = NULL
-        cdef const C.pgsd_index_entry* p_density = NULL
         self._entry(frame, name, &entry)
-        if mass is not None:
-            self._entry(mass[0], mass[1], &e_mass)
-            p_mass = &e_mass
-        if density is not None:
-            self._entry(density[0], density[1], &e_density)
-            p_density = &e_density
-        c_box = numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6]
-        if c_box.shape[0] != 6:
-            raise ValueError("box must hold 6 values")
-        c_vectors = numpy.ascontiguousarray(_hoomd.box_vectors(c_box), dtype=numpy.float64)
-        grid = [int(v) for v in cells]
-        if len(grid) != 3 or any(not 0 <= v < (1 << 32) for v in grid):
-            raise ValueError("sph_sums_device: cells holds three counts, each 1 to 1024")
-        c_cells = numpy.array(grid, dtype=numpy.uint32)
-        if kernel not in _hoomd.SPH_KERNELS:
-            raise ValueError("sph_sums_device: the kernel is one of %s: %r" % (', '.join(_hoomd.SPH_KERNELS), kernel))
-        c_defaults = numpy.ascontiguousarray(
-            numpy.array([1.0, float('nan')] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
-        if c_defaults.shape[0] != 2:
-            raise ValueError("sph_sums_device: defaults holds a mass and a density")
-        volume = density is not None or c_defaults[1] == c_defaults[1]
-        c_rows, count = _row_list("sph_sums_device", rows, n)
-        c_cell, _ = _row_list("sph_sums_device", cell, count)
+        cdef const C.pgsd_index_entry* p_mass = self._optional(mass, &e_mass)
+        cdef const C.pgsd_index_entry* p_density = self._optional(density, &e_density)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("sph_sums_device", cells)
+        cdef uint32_t c_kernel = _sph_kernel("sph_sums_device", kernel)
+        c_defaults, volume = _sph_defaults("sph_sums_device", defaults, density)
+        c_rows, c_cell, count = _cell_ordered_lists("sph_sums_device", rows, cell, n)
         summary = numpy.zeros(13, dtype=numpy.uint64)
-        cdef uintptr_t p_number = 0, p_rho = 0, p_shepard = 0
-        out_number = out_rho = out_shepard = None
-        if return_rows:
-            device = self.pipeline_device()
-            out_number = _device_empty((max(count, 1),), numpy.float64, device)
-            out_rho = _device_empty((max(count, 1),), numpy.float64, device)
-            p_number, p_rho = out_number.data_ptr(), out_rho.data_ptr()
-            if volume:
-                out_shepard = _device_empty((max(count, 1),), numpy.float64, device)
-                p_shepard = out_shepard.data_ptr()
+        cdef uintptr_t p_number, p_rho, p_shepard
+        device = self.pipeline_device() if return_rows else None
+        out_number, p_number = _per_entry(count, (), numpy.float64, device)
+        out_rho, p_rho = _per_entry(count, (), numpy.float64, device)
+        out_shepard, p_shepard = _per_entry(count, (), numpy.float64, device if volume else None)
         if not self._explicit_stream:
             self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
         cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
         cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data
         cdef uint64_t c_n = count
         cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
-        cdef uint32_t c_kernel = _hoomd.SPH_KERNELS.index(kernel)
         cdef double c_h = float(h), c_surface = float('nan') if surface_below is None else float(surface_below)
         cdef int retval, err
         with nogil:
@@ -2075,55 +2099,28 @@ cdef class PGSDFile:
         """
         from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
         cdef C.pgsd_index_entry entry, e_velocity, e_mass, e_density
-        cdef const C.pgsd_index_entry* p_velocity = NULL
-        cdef const C.pgsd_index_entry* p_mass = NULL
-        cdef const C.pgsd_index_entry* p_density = NULL
         self._entry(frame, name, &entry)
-        if velocity is not None:
-            self._entry(velocity[0], velocity[1], &e_velocity)
-            p_velocity = &e_velocity
-        if mass is not None:
-            self._entry(mass[0], mass[1], &e_mass)
-            p_mass = &e_mass
-        if density is not None:
-            self._entry(density[0], density[1], &e_density)
-            p_density = &e_density
-        c_box = numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6]
-        if c_box.shape[0] != 6:
-            raise ValueError("box must hold 6 values")
-        c_vectors = numpy.ascontiguousarray(_hoomd.box_vectors(c_box), dtype=numpy.float64)
-        grid = [int(v) for v in cells]
-        if len(grid) != 3 or any(not 0 <= v < (1 << 32) for v in grid):
-            raise ValueError("sph_gradients_device: cells holds three counts, each 1 to 1024")
-        c_cells = numpy.array(grid, dtype=numpy.uint32)
-        if kernel not in _hoomd.SPH_KERNELS:
-            raise ValueError("sph_gradients_device: the kernel is one of %s: %r" % (', '.join(_hoomd.SPH_KERNELS), kernel))
-        c_defaults = numpy.ascontiguousarray(
-            numpy.array([1.0, float('nan')] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
-        if c_defaults.shape[0] != 2:
-            raise ValueError("sph_gradients_device: defaults holds a mass and a density")
-        volume = density is not None or c_defaults[1] == c_defaults[1]
-        c_rows, count = _row_list("sph_gradients_device", rows, n)
-        c_cell, _ = _row_list("sph_gradients_device", cell, count)
+        cdef const C.pgsd_index_entry* p_velocity = self._optional(velocity, &e_velocity)
+        cdef const C.pgsd_index_entry* p_mass = self._optional(mass, &e_mass)
+        cdef const C.pgsd_index_entry* p_density = self._optional(density, &e_density)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("sph_gradients_device", cells)
+        cdef uint32_t c_kernel = _sph_kernel("sph_gradients_device", kernel)
+        c_defaults, volume = _sph_defaults("sph_gradients_device", defaults, density)
+        c_rows, c_cell, count = _cell_ordered_lists("sph_gradients_device", rows, cell, n)
         summary = numpy.zeros(13, dtype=numpy.uint64)
-        cdef uintptr_t p_rate = 0, p_divergence = 0, p_curl = 0, p_normal = 0
-        out_rate = out_divergence = out_curl = out_normal = None
-        if return_rows:
-            device = self.pipeline_device()
-            out_rate = _device_empty((max(count, 1),), numpy.float64, device)
-            p_rate = out_rate.data_ptr()
-            if volume:
-                out_divergence = _device_empty((max(count, 1),), numpy.float64, device)
-                out_curl = _device_empty((max(count, 1), 3), numpy.float64, device)
-                out_normal = _device_empty((max(count, 1), 3), numpy.float64, device)
-                p_divergence, p_curl, p_normal = out_divergence.data_ptr(), out_curl.data_ptr(), out_normal.data_ptr()
+        cdef uintptr_t p_rate, p_divergence, p_curl, p_normal
+        device = self.pipeline_device() if return_rows else None
+        out_rate, p_rate = _per_entry(count, (), numpy.float64, device)
+        out_divergence, p_divergence = _per_entry(count, (), numpy.float64, device if volume else None)
+        out_curl, p_curl = _per_entry(count, (3,), numpy.float64, device if volume else None)
+        out_normal, p_normal = _per_entry(count, (3,), numpy.float64, device if volume else None)
         if not self._explicit_stream:
             self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
         cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
         cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data
         cdef uint64_t c_n = count
         cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
-        cdef uint32_t c_kernel = _hoomd.SPH_KERNELS.index(kernel)
         cdef double c_h = float(h)
         cdef int retval, err
         with nogil:

@@ -232,6 +232,27 @@ def test_a_second_call_is_served_from_the_staged_rows_and_return_rows(data):
         f.wait_read()
 
 
+def test_one_chunk_given_as_mass_and_as_density(data):
+    """One stored chunk named twice in one call -- as the mass and as the density --: the staging takes the file range
+    once and both slots share its address.  'flat' is the smallest case whose list spans two workgroups."""
+    path, arrays = data
+    name, kw = chunk('flat', 'f32'), CASES['flat'][3]
+    column = chunk('flat_mass', 'f32')
+    host, m = arrays[name], arrays[column]
+    n = len(host)
+    assert n > 256
+    want = hoomd.sph_kernel_sums(host, mass=m, density=m, kernel='wendland_c2', **kw)
+    with fl.open(path, 'r') as f:
+        d_rows = to_device(f, np.arange(n))
+        d_cell = f.order_rows_by_cell_device(0, name, kw['box'], want.grid, d_rows, n=n, dimensions=2)
+        f.device_read_stats(reset=True)
+        got = f.sph_sums_device(0, name, kw['box'], kw['h'], want.grid, d_rows, d_cell, n=n, mass=(0, column),
+                                density=(0, column), dimensions=2, kernel='wendland_c2', return_rows=True)
+        assert f.device_read_stats()["pread_bytes"] == n * 4           # the column once; the position by the ordering
+        assert equal(got, want, "mass is density") and got.volume
+        f.wait_read()
+
+
 # ---------------------------------------------------------------- refusals
 def test_what_the_python_layers_refuse(data):
     path, arrays = data
