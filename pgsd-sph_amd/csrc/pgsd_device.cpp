@@ -227,6 +227,21 @@ int DevicePipeline::init()
         m_res.arenas.push_back(a);
         }
     m_pool = writer_pool_create(m_cfg.n_writers, pin);
+    // The one ordered lane as a warm-then-write pair (pgsd_io.cpp): PGSD_WRITE_WARM=0 keeps the single thread,
+    // PGSD_WRITE_SUBPIECE_KIB (a multiple of 4) sets the sub-piece.  Stays single with several writers, over MPI-IO and
+    // where no two cores of `pin` are known to share an L3.
+    // 512 KiB: on tmpfs 128-512 KiB are level and 1 MiB and more lose the gain; on the disk-backed page cache 256 KiB
+    // loses to the single thread (a turn costs more per call there) and 512 KiB-2 MiB win (profiles/r23_warm_write_subpiece.jsonl)
+    size_t sub_kib = 512;
+    if (const char* v = getenv("PGSD_WRITE_SUBPIECE_KIB"))
+        {
+        if (atoll(v) > 0 && atoll(v) % 4 == 0)
+            sub_kib = (size_t)atoll(v);
+        else
+            fprintf(stderr, "pgsd_amd: PGSD_WRITE_SUBPIECE_KIB=%s is no positive multiple of 4: %zu\n", v, sub_kib);
+        }
+    const char* warm = getenv("PGSD_WRITE_WARM");
+    m_warm = (warm ? atoi(warm) != 0 : true) && m_cfg.n_writers == 1 && writer_pool_enable_warm(m_pool, sub_kib << 10, pin);
     m_dispatcher = std::thread([this] { dispatch_loop(); });
     if (pin)
         (void)pthread_setaffinity_np(m_dispatcher.native_handle(), sizeof(cpu_set_t), pin);

@@ -270,6 +270,7 @@ class DevicePipeline
     size_t m_dused = 0, m_direct_max = 0;
     bool m_direct_failed = false;
     bool m_coalesce = true;              // neighbours in the file leave in one pwritev (write_direct)
+    bool m_warm = false;                 // slab pieces go down the lane as a warm-then-write pair (PGSD_WRITE_WARM)
     size_t m_soft_cap = (size_t)6 << 30; // staging held by frames on their way before stage() waits (PGSD_STAGING_CAP_MIB)
 
     // per-frame events, handed back to the pools by reset_staging() (m_mutex); the timed ones in (begin, end) pairs

@@ -544,6 +544,14 @@ void DevicePipeline::write_piece(int si, size_t n, long long foff)
     double ms = 0;
     if (e != hipSuccess)
         fail(std::string("hipEventSynchronize(copy): ") + hipGetErrorString(e));
+    else if (m_warm)
+        {
+        // the copy has landed: the slab goes down the lane in sub-pieces, warmed outside the turn, written inside it
+        TraceRange tr("pgsd:lane file_off=%llu bytes=%llu", (unsigned long long)foff, n);
+        int w = writer_pool_pwrite_warm(m_pool, m_fd, s.host, n, foff, m_shared, &ms);
+        if (w != 0)
+            fail(std::string("pwrite: ") + strerror(-w), true, -w);
+        }
     else
         {
         TraceRange tr("pgsd:pwrite file_off=%llu bytes=%llu", (unsigned long long)foff, n);

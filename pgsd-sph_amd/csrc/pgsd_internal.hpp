@@ -95,6 +95,15 @@ WriterPool* writer_pool_create(unsigned n_threads, const cpu_set_t* cpus = nullp
 bool numa_cpus_of_pci_device(const char* pci_bus_id, cpu_set_t* out);
 void writer_pool_destroy(WriterPool*);
 void writer_pool_submit(WriterPool*, std::function<void()> fn);
+// The warm-then-write pair (pgsd_io.cpp): a pool of ONE thread gets a helper, both on L3-sharing cores of `cpus` (null:
+// of the process), and carries pieces above `sub_bytes` out as sub-pieces the two take in turn.  false -- and the pool
+// stays as it was -- with several threads, the MPI-IO back end, or where sysfs names no two cores that share an L3
+// (need_topology = false: the pair runs unplaced there; for tests of the lane itself).
+bool writer_pool_enable_warm(WriterPool*, size_t sub_bytes, const cpu_set_t* cpus, bool need_topology = true);
+// pwrite_locked of one piece through the pair, FROM A JOB OF THE POOL (its lane thread); plainly where there is no pair
+// or the piece is no longer than a sub-piece.  0 or -errno; *pwrite_ms: the time inside pwrite calls
+int writer_pool_pwrite_warm(WriterPool*, int fd, const void* buf, size_t bytes, long long offset, bool shared_file,
+                            double* pwrite_ms);
 // Write [buf, buf+bytes) at `offset` of fd, split over the pool; blocks until done.
 // Returns 0 or -errno.
 int writer_pool_pwrite_sync(WriterPool*, int fd, const void* buf, size_t bytes, long long offset,

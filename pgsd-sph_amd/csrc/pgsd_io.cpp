@@ -6,14 +6,17 @@
 // (pgsd_mpiio_plugin.h; the library itself does not link MPI).  Same bytes at the same offsets either way.
 // The small thread pool here carries the device pipeline's writer and reader threads.  For
 // WRITES one thread per file is the measured optimum on the target boxes (buffered writes
-// serialise on the file's inode lock: profiles/r01_io_probe*.log); page-cache READS take no
-// exclusive lock and scale with threads.
+// serialise on the file's inode lock: profiles/r01_io_probe*.log) -- one ordered lane, which may
+// work as a warm-then-write pair (WarmPair below); page-cache READS take no exclusive lock and
+// scale with threads.
 #include "pgsd_internal.hpp"
 #include "pgsd_mpiio_plugin.h"
 
 #include <atomic>
 #include <cctype>
 #include <cerrno>
+#include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <pthread.h>
@@ -28,6 +31,8 @@
 #include <fcntl.h>
 #include <map>
 #include <sys/stat.h>
+#include <sys/syscall.h>
+#include <linux/futex.h>
 #include <functional>
 #include <mutex>
 #include <thread>
@@ -245,14 +250,19 @@ int pwrite_full(int fd, const void* buf, size_t bytes, long long offset)
 // queue asleep instead, which keeps the file at the single-writer rate.
 static int g_write_lock = -1;
 
-int pwrite_locked(int fd, const void* buf, size_t bytes, long long offset, bool shared_file)
+static bool write_lock_wanted()
     {
     if (g_write_lock < 0)
         {
         const char* e = getenv("PGSD_WRITE_LOCK");
         g_write_lock = (e && atoi(e) == 0) ? 0 : 1;
         }
-    if (!shared_file || !g_write_lock)
+    return g_write_lock != 0;
+    }
+
+int pwrite_locked(int fd, const void* buf, size_t bytes, long long offset, bool shared_file)
+    {
+    if (!shared_file || !write_lock_wanted())
         return pwrite_full(fd, buf, bytes, offset);
     while (flock(fd, LOCK_EX) != 0)
         if (errno != EINTR)
@@ -376,6 +386,162 @@ void pread_parallel(int fd, void* buf, size_t bytes, long long offset)
         t.join();
     }
 
+// ------------------------------------------------------------------ the warm-then-write pair
+// One 16 MiB pwrite into a growing tmpfs file holds the file's inode lock for 2.4-2.8 ms, and a sixth of that is the
+// kernel's copy missing the cache on every source line: the GPU's PCIe writes leave a slab in DRAM.  Reading a piece into
+// cache needs no lock, so the ORDERED LANE of a pool (its one writer thread) may run large pieces as a pair: the piece is cut
+// into sub-pieces which the lane thread and one helper thread take in turn -- touch one byte per 64-byte line of the
+// sub-piece, wait for the turn on a ticket, pwrite, pass the ticket on.  Never are the two inside pwrite at once (the
+// ticket, not the kernel's lock, orders them) and the lane thread returns when the piece's last sub-piece is in the file,
+// so what the pool promises about submission order is untouched: the pair is how one job is carried out.
+// tools/labs/warm_write_lab.hip measured it (profiles/r23_warm_write_lab.log).
+namespace
+    {
+inline void futex_sleep(std::atomic<uint32_t>* word, uint32_t seen)
+    {
+    syscall(SYS_futex, (uint32_t*)word, FUTEX_WAIT_PRIVATE, seen, nullptr, nullptr, 0);
+    }
+
+// a word that threads wait on: a bounded spin (the other thread is a sub-piece away), then asleep in the kernel
+struct WaitWord
+    {
+    std::atomic<uint32_t> value {0};
+    std::atomic<uint32_t> sleepers {0};
+
+    template<class Done> uint32_t wait(Done done)
+        {
+        for (int spin = 0; spin < 4000; spin++)
+            {
+            const uint32_t v = value.load(std::memory_order_acquire);
+            if (done(v))
+                return v;
+#if defined(__x86_64__) || defined(__i386__)
+            __builtin_ia32_pause();
+#endif
+            }
+        sleepers.fetch_add(1);
+        uint32_t v;
+        while (!done(v = value.load()))
+            futex_sleep(&value, v);
+        sleepers.fetch_sub(1);
+        return v;
+        }
+
+    void post(uint32_t v)
+        {
+        value.store(v);
+        if (sleepers.load() != 0)
+            syscall(SYS_futex, (uint32_t*)&value, FUTEX_WAKE_PRIVATE, INT_MAX, nullptr, nullptr, 0);
+        }
+    };
+    } // namespace
+
+class WarmPair
+    {
+    public:
+    WarmPair(size_t sub_bytes, const cpu_set_t* cpus) : m_sub(sub_bytes)
+        {
+        m_helper = std::thread([this] { helper(); });
+        if (cpus)
+            (void)pthread_setaffinity_np(m_helper.native_handle(), sizeof(cpu_set_t), cpus);
+        }
+
+    ~WarmPair()
+        {
+        m_stop.store(true);
+        m_gen.post(m_gen.value.load() + 1);
+        m_helper.join();
+        }
+
+    size_t sub_bytes() const
+        {
+        return m_sub;
+        }
+
+    // the lane thread's half of one piece (at least two sub-pieces); 0 or -errno of the first pwrite that failed, after
+    // which the rest of the piece is skipped -- its tickets still pass
+    int write(int fd, const char* buf, size_t bytes, long long offset, double* pwrite_ms)
+        {
+        m_fd = fd;
+        m_buf = buf;
+        m_bytes = bytes;
+        m_offset = offset;
+        m_base = m_ticket.value.load();
+        m_err.store(0);
+        m_pwrite_ns.store(0);
+        m_gen.post(m_gen.value.load() + 1); // publishes the piece to the helper
+        const uint32_t n = run(0);
+        const uint32_t end = m_base + n;
+        m_ticket.wait([end](uint32_t v) { return v == end; });
+        if (pwrite_ms)
+            *pwrite_ms = (double)m_pwrite_ns.load() * 1e-6;
+        return m_err.load();
+        }
+
+    private:
+    void helper()
+        {
+        uint32_t seen = 0;
+        for (;;)
+            {
+            seen = m_gen.wait([seen](uint32_t v) { return v != seen; });
+            if (m_stop.load())
+                return;
+            run(1);
+            }
+        }
+
+    // sub-pieces who, who + 2, ... of the piece in flight; returns how many sub-pieces the piece has
+    uint32_t run(uint32_t who)
+        {
+        const int fd = m_fd;
+        const char* const buf = m_buf;
+        const size_t bytes = m_bytes, sub = m_sub;
+        const long long offset = m_offset;
+        const uint32_t base = m_base, n = (uint32_t)((bytes + sub - 1) / sub);
+        for (uint32_t g = who; g < n; g += 2)
+            {
+            const size_t at = (size_t)g * sub, len = std::min(sub, bytes - at);
+            const unsigned long long foff = (unsigned long long)(offset + (long long)at);
+                {
+                TraceRange tr("pgsd:warm file_off=%llu bytes=%llu", foff, len);
+                unsigned acc = 0;
+                for (const char* q = buf + at; q < buf + at + len; q = (const char*)(((uintptr_t)q | 63) + 1))
+                    acc += (unsigned char)*(const volatile char*)q;
+                m_sink.store(acc, std::memory_order_relaxed);
+                }
+            const uint32_t turn = base + g;
+            m_ticket.wait([turn](uint32_t v) { return v == turn; });
+            if (m_err.load() == 0)
+                {
+                TraceRange tr("pgsd:pwrite file_off=%llu bytes=%llu", foff, len);
+                auto t0 = std::chrono::steady_clock::now();
+                int w = pwrite_full(fd, buf + at, len, offset + (long long)at);
+                m_pwrite_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
+                int none = 0;
+                if (w != 0)
+                    m_err.compare_exchange_strong(none, w);
+                }
+            m_ticket.post(turn + 1);
+            }
+        return n;
+        }
+
+    const size_t m_sub;
+    std::thread m_helper;
+    // the piece in flight: written by the lane thread before m_gen moves, read by the helper behind it
+    int m_fd = -1;
+    const char* m_buf = nullptr;
+    size_t m_bytes = 0;
+    long long m_offset = 0;
+    uint32_t m_base = 0;
+    WaitWord m_gen, m_ticket; // pieces handed to the helper; sub-pieces written, of all pieces so far
+    std::atomic<int> m_err {0};
+    std::atomic<uint64_t> m_pwrite_ns {0};
+    std::atomic<unsigned> m_sink {0};
+    std::atomic<bool> m_stop {false};
+    };
+
 class WriterPool
     {
     public:
@@ -400,6 +566,22 @@ class WriterPool
         m_cv.notify_all();
         for (auto& t : m_threads)
             t.join();
+        delete m_warm;
+        }
+
+    // the lane becomes a pair (one helper thread more); both threads on `cpus`
+    void enable_warm(size_t sub_bytes, const cpu_set_t* cpus)
+        {
+        if (m_warm || m_threads.size() != 1)
+            return;
+        m_warm = new WarmPair(sub_bytes, cpus);
+        if (cpus)
+            (void)pthread_setaffinity_np(m_threads[0].native_handle(), sizeof(cpu_set_t), cpus);
+        }
+
+    WarmPair* warm() const
+        {
+        return m_warm;
         }
 
     void submit(std::function<void()> fn)
@@ -439,6 +621,7 @@ class WriterPool
     std::mutex m_mutex;
     std::condition_variable m_cv;
     bool m_stop;
+    WarmPair* m_warm = nullptr;
     };
 
 WriterPool* writer_pool_create(unsigned n_threads, const cpu_set_t* cpus)
@@ -518,6 +701,89 @@ void writer_pool_destroy(WriterPool* p)
 void writer_pool_submit(WriterPool* p, std::function<void()> fn)
     {
     p->submit(std::move(fn));
+    }
+
+// The CPUs of `within` (null: of this process) that share an L3 with the one this thread runs on -- or, where that one
+// is not among them, with the first that has a neighbour: at least two cores.  Read from sysfs; false where it does not say.
+static bool l3_sharing_cpus(const cpu_set_t* within, cpu_set_t* out)
+    {
+    cpu_set_t allowed;
+    if (!within)
+        {
+        CPU_ZERO(&allowed);
+        if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0)
+            return false;
+        within = &allowed;
+        }
+    if (CPU_COUNT(within) < 2)
+        return false;
+    cpu_set_t tried;
+    CPU_ZERO(&tried);
+    const int here = sched_getcpu();
+    for (int i = -1; i < CPU_SETSIZE; i++)
+        {
+        const int c = i < 0 ? here : i;
+        if (c < 0 || c >= CPU_SETSIZE || !CPU_ISSET(c, within) || CPU_ISSET(c, &tried))
+            continue;
+        char path[128], buf[4096];
+        cpu_set_t siblings;
+        size_t n = 0;
+        snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", c);
+        FILE* f = fopen(path, "r");
+        if (!f)
+            return false;
+        n = fread(buf, 1, sizeof(buf) - 1, f);
+        fclose(f);
+        buf[n] = 0;
+        const int in_group = parse_cpulist(buf, within, out);
+        CPU_OR(&tried, &tried, out);
+        CPU_SET(c, &tried);
+        snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", c);
+        f = fopen(path, "r");
+        if (!f)
+            return false;
+        n = fread(buf, 1, sizeof(buf) - 1, f);
+        fclose(f);
+        buf[n] = 0;
+        if (in_group > parse_cpulist(buf, within, &siblings)) // more than the hardware threads of one core
+            return true;
+        }
+    return false;
+    }
+
+bool writer_pool_enable_warm(WriterPool* p, size_t sub_bytes, const cpu_set_t* cpus, bool need_topology)
+    {
+    if (!p || p->size() != 1 || sub_bytes == 0 || strcmp(io_backend_name(), "posix") != 0)
+        return false;
+    cpu_set_t pair;
+    const bool placed = l3_sharing_cpus(cpus, &pair);
+    if (!placed && need_topology)
+        return false;
+    p->enable_warm(sub_bytes, placed ? &pair : nullptr);
+    return p->warm() != nullptr;
+    }
+
+int writer_pool_pwrite_warm(WriterPool* p, int fd, const void* buf, size_t bytes, long long offset, bool shared_file,
+                            double* pwrite_ms)
+    {
+    WarmPair* pair = p ? p->warm() : nullptr;
+    if (!pair || bytes <= pair->sub_bytes())
+        {
+        auto t0 = std::chrono::steady_clock::now();
+        int rc = pwrite_locked(fd, buf, bytes, offset, shared_file);
+        if (pwrite_ms)
+            *pwrite_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
+        }
+    // the advisory lock of a shared file is taken once per piece: both threads write through the one descriptor
+    bool locked = shared_file && write_lock_wanted();
+    while (locked && flock(fd, LOCK_EX) != 0)
+        if (errno != EINTR)
+            locked = false; // no lock support: write anyway
+    int rc = pair->write(fd, (const char*)buf, bytes, offset, pwrite_ms);
+    if (locked)
+        flock(fd, LOCK_UN);
+    return rc;
     }
 
 int writer_pool_pwrite_sync(WriterPool* pool, int fd, const void* buf, size_t bytes, long long offset,

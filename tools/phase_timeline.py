@@ -70,6 +70,21 @@ def main():
         first_pw = min(s for s, e in pw)
         print("# first pwrite starts %.1f us after the pack launch; last pwrite ends at %.1f us; frame sealed at %.1f us"
               % ((first_pw - t0) / 1e3, (max(e for s, e in pw) - t0) / 1e3, (t1 - t0) / 1e3))
+    # the writer lane: time inside pwrite per 16 MiB written, and -- where the lane is a warm-then-write pair -- how much
+    # of the warming ran under the other thread's pwrite
+    def nbytes(name):
+        return int(name.split("bytes=")[1].split()[0]) if "bytes=" in name else 0
+    pw_named = [(s, e, w, n) for s, e, w, n in inside if n.startswith("pgsd:pwrite file_off")]
+    written = sum(nbytes(n) for s, e, w, n in pw_named)
+    if written:
+        print("# time inside pgsd:pwrite ranges: %.1f us per 16 MiB (%d ranges, %.1f MB)"
+              % (sum(e - s for s, e, w, n in pw_named) / 1e3 * (16 << 20) / written, len(pw_named), written / 1e6))
+    warm = [(s, e, w) for s, e, w, n in inside if n.startswith("pgsd:warm")]
+    if warm:
+        warm_total = sum(e - s for s, e, w in warm)
+        under = sum(overlap((s, e), [(ps, pe) for ps, pe, pw_, n in pw_named if pw_ != w]) for s, e, w in warm)
+        print("# pgsd:warm ranges: %d, %.1f us in all = %.1f us per 16 MiB; %.1f us = %.0f %% of it under a pwrite of the other thread"
+              % (len(warm), warm_total / 1e3, warm_total / 1e3 * (16 << 20) / max(written, 1), under / 1e3, 100.0 * under / max(warm_total, 1)))
 
 
 if __name__ == "__main__":
