@@ -211,6 +211,7 @@ int DevicePipeline::init()
         warm_order_kernels();
         warm_cells_kernels();
         warm_neighbours_kernels();
+        warm_neighbour_list_kernels();
         warm_sph_kernels();
         warm_sph_gradients_kernels();
         int brc = compare_buffers();

@@ -449,7 +449,7 @@ int DevicePipeline::stage_present(const ChunkRange* ranges, const void** const* 
 // wait_read for an indexed read of the same chunk --; where the pass writes or reads memory of the caller's on the device
 // (`callers_memory`: a row list, shifts), what the caller's stream still does with that memory comes first;
 // `launch(stream, why)` launches on the pack stream, synchronises it and returns a pgsd_error; a PGSD_ERROR_DEVICE fails
-// the pipeline with the launcher's message.  The message of a failure, for all fourteen passes: the launcher's own first,
+// the pipeline with the launcher's message.  The message of a failure, for all sixteen passes: the launcher's own first,
 // else the pipeline's, else the thread's last error.
 template<class Launch>
 int DevicePipeline::staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N,
@@ -631,6 +631,28 @@ int device_pipeline_sph_gradients(DevicePipeline* p, const ChunkRange* ranges, c
     return p->staged_launch(ranges, slots, 4, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
                             { return launch_sph_gradients(a, out_rate, out_divergence, out_curl, out_normal, out_summary, stream,
                                                           why); });
+    }
+
+// Neighbour lists: the census's staging for both calls (the fill finds the chunk the offsets call left staged); the lists,
+// the offsets and the segments are the caller's.  No entry: nothing to stage, as the cell offsets.
+int device_pipeline_neighbour_offsets(DevicePipeline* p, long long file_offset, size_t bytes, const NeighbourListArgs& args,
+                                      uint64_t* out_offsets, uint64_t* out_summary, std::string* err)
+    {
+    NeighbourListArgs a = args;
+    const auto launch = [&](hipStream_t stream, std::string* why)
+    { return launch_neighbour_offsets(a, out_offsets, out_summary, stream, why); };
+    if (a.n == 0)
+        return p->staged_launch(nullptr, nullptr, 0, 0u, 0, true, err, launch);
+    return one_chunk_pass(p, file_offset, bytes, &a.pos, a.N, true, err, launch);
+    }
+
+int device_pipeline_neighbour_list(DevicePipeline* p, long long file_offset, size_t bytes, const NeighbourListArgs& args,
+                                   const uint64_t* offsets, uint64_t capacity, uint32_t* out_neighbours,
+                                   double* out_distance2, std::string* err)
+    {
+    NeighbourListArgs a = args;
+    return one_chunk_pass(p, file_offset, bytes, &a.pos, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_neighbour_list(a, offsets, capacity, out_neighbours, out_distance2, stream, why); });
     }
 
 int DevicePipeline::wait_read()

@@ -559,6 +559,33 @@ inline void sph_gradients_of_nothing(uint64_t* out_summary)
 int device_pipeline_sph_gradients(DevicePipeline*, const ChunkRange* ranges, const SphGradientsArgs& a, double* out_rate,
                                   double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary,
                                   std::string* err);
+// Neighbour lists (pgsd.hoomd.neighbour_list is the definition): the neighbours the census counts, handed over as a CSR
+// pair list -- per entry of a row list in cell order the list positions of its neighbours in the order the SPH kernel
+// sums define, in two calls: the offsets (count, scan), then the segments (fill).  The grid, the range and the list are
+// NeighboursArgs' (bins is not looked at).
+enum
+    {
+    NLIST_HALF = 1u,         // bit of the entry points' flags: the segment of i keeps j > i by list position
+    NLIST_SUMMARY_WORDS = 4  // n, nowhere, pairs, longest
+    };
+struct NeighbourListArgs : NeighboursArgs
+    {
+    uint32_t half, pad2;
+    };
+// stage the position chunk (or take it from what the ordering left staged), check the lists, count and scan on the GPU:
+// out_offsets (device, a.n + 1 words) and out_summary (host, 4 words) are written on success only; synchronous.  n == 0:
+// nothing is staged and no kernel runs, out_offsets[0] = 0 is one memset on the pipeline's stream.  The refusals and the
+// staging are device_pipeline_neighbours'.
+int device_pipeline_neighbour_offsets(DevicePipeline*, long long file_offset, size_t bytes, const NeighbourListArgs& a,
+                                      uint64_t* out_offsets, uint64_t* out_summary, std::string* err);
+// ... and fill the segments the offsets (device, a.n + 1 words, as the call above left them for the same arguments) cut
+// out of out_neighbours (device, capacity words) and out_distance2 (device, capacity doubles, or null); synchronous.  No
+// store lands at or beyond `capacity` or outside an entry's segment; offsets that are not this list's, or that hold more
+// pairs than the capacity, refuse the call (PGSD_ERROR_INVALID_ARGUMENT): the outputs are then unspecified inside the
+// capacity and untouched outside it.
+int device_pipeline_neighbour_list(DevicePipeline*, long long file_offset, size_t bytes, const NeighbourListArgs& a,
+                                   const uint64_t* offsets, uint64_t capacity, uint32_t* out_neighbours,
+                                   double* out_distance2, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

@@ -303,6 +303,18 @@ int launch_cell_moments(const CellMomentsArgs& c, uint64_t* out_counts, double* 
 int launch_neighbours(const NeighboursArgs& a, const double* edges2, uint32_t* out_count, double* out_nearest2,
                       uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2, hipStream_t stream, std::string* err);
 
+// neighbour lists (pgsd_neighbour_list.hip; NeighbourListArgs, a.pos filled in).  launch_neighbour_offsets: check,
+// offsets, compaction, one lane per entry counting over the census's traversal, one workgroup scanning the workgroup sums,
+// one pass writing out_offsets (device, a.n + 1 words); out_summary (host, 4 words: n, nowhere, pairs, longest); both are
+// written on success only; a.n == 0 is one memset of out_offsets[0].  launch_neighbour_list: check, offsets, compaction,
+// then the same traversal storing each neighbour (and its d2 where out_distance2 is given) inside the entry's segment of
+// `offsets` (device, a.n + 1 words) and below `capacity`.  Both synchronise `stream`; PGSD_ERROR_INVALID_ARGUMENT for
+// what the census refuses and, from the fill, for offsets that are not this list's or exceed the capacity
+int launch_neighbour_offsets(const NeighbourListArgs& a, uint64_t* out_offsets, uint64_t* out_summary, hipStream_t stream,
+                             std::string* err);
+int launch_neighbour_list(const NeighbourListArgs& a, const uint64_t* offsets, uint64_t capacity, uint32_t* out_neighbours,
+                          double* out_distance2, hipStream_t stream, std::string* err);
+
 // SPH kernel sums (pgsd_sph.hip; SphArgs, a.pos, a.mass and a.density filled in): check, offsets, compaction of the listed
 // positions, masses and volumes, one lane per entry over the runs of the adjacent cells in the defined order, one
 // workgroup for the ranges and the deviation.  out_number, out_density, out_shepard (device, a.n entries each, or null);
@@ -379,6 +391,7 @@ void warm_census_kernels();
 void warm_order_kernels();
 void warm_cells_kernels();
 void warm_neighbours_kernels();
+void warm_neighbour_list_kernels();
 void warm_sph_kernels();
 void warm_sph_gradients_kernels();
 

@@ -44,6 +44,9 @@
  *                     pgsd_neighbours_device (pgsd.fl's neighbours_device, behind pgsd.hoomd's frame_neighbours_device:
  *                     per entry of a row list in cell order the neighbours inside a range and the nearest of them, and
  *                     over the list the count histogram, the closest pair and the pair histogram of g(r))
+ *                     pgsd_neighbour_offsets_device, pgsd_neighbour_list_device (pgsd.fl's neighbour_list_device, behind
+ *                     pgsd.hoomd's frame_neighbour_list_device: the same neighbours handed over as a CSR pair list in a
+ *                     defined order -- count and scan, then fill -- which is what a restarted solver builds first)
  *                     pgsd_sph_sums_device (pgsd.fl's sph_sums_device, behind pgsd.hoomd's frame_kernel_sums_device: per
  *                     entry of a row list in cell order the SPH summation density, number density and Shepard sum over
  *                     the kernel support, in a defined order, and over the list their ranges, the largest deviation from
@@ -385,6 +388,48 @@ extern "C"
                                double r, uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
                                const int32_t* cell, uint64_t n, uint32_t bins, const double* edges2, uint32_t* out_count,
                                double* out_nearest2, uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2);
+
+    /* Neighbour lists (pgsd.hoomd.neighbour_list is the definition, and the results equal it exactly: every offset and
+       index, every distance bit for bit): the neighbours pgsd_neighbours_device counts, handed over as a CSR pair list.
+       position, vectors, r, dimensions, cells, rows, cell and n are pgsd_neighbours_device's, and so are the candidates,
+       the distance of one pair and the strict test d2 < r*r.  flags: bit 0 is the HALF list; every other bit is refused.
+       The SEGMENT of entry i holds the list positions j of its neighbours, j != i as a list position (with the half list:
+       j > i, the same filter of the same segment), in the order the SPH kernel sums define: oz over the offsets of the z
+       axis, inside it oy, inside it ox, the cell ((ix+ox) % cx, (iy+oy) % cy, (iz+oz) % cz), inside a cell ascending list
+       position.  An entry without a cell has an empty segment and is in nobody's.  The size of the list is not known
+       before it is counted, so it is made in two calls.
+
+       pgsd_neighbour_offsets_device counts and scans:
+           out_offsets   device memory, n + 1 uint64: out_offsets[0] = 0, out_offsets[k + 1] - out_offsets[k] the length
+                         of entry k's segment, out_offsets[n] the pairs
+           out_summary   host, 4 uint64: n; the entries nowhere; the pairs; the longest segment (0 at n == 0)
+       The chunk is staged whole unless an earlier call (the ordering) left it staged, the pass runs on the handle's GPU
+       and the call synchronises; the staged rows are kept until the next pgsd_device_wait_read.  n == 0 stages nothing
+       and launches no kernel: out_offsets[0] = 0 is one memset on the pipeline's stream, the summary is four zeros.
+
+       pgsd_neighbour_list_device fills the segments:
+           offsets         device memory, n + 1 uint64, as the call above left them for the SAME arguments
+           capacity        the entries out_neighbours (and out_distance2) have room for
+           out_neighbours  device memory, capacity uint32: the list positions j, segment after segment
+           out_distance2   device memory, capacity doubles, or NULL: d2 of each pair
+       No store lands at an index >= capacity or outside [offsets[k], offsets[k + 1]) of the entry k it belongs to.  Where
+       an entry finds another number of neighbours than its segment holds, the offsets descend or do not begin at 0, or
+       offsets[n] > capacity, the call is refused: PGSD_ERROR_INVALID_ARGUMENT, and the message says that the capacity is
+       too small (naming it and offsets[n]) or that the offsets do not belong to this list.  After such a refusal the
+       output arrays are unspecified inside the capacity and untouched outside it.  n == 0 fills nothing and launches
+       nothing.  The chunk is taken from what the first call left staged (or staged again after a wait_read).
+
+       Both calls refuse everything pgsd_neighbours_device refuses (but for the pair histogram, which they do not have),
+       with its messages; out_offsets and out_summary are written on success only. */
+    int pgsd_neighbour_offsets_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                      const double vectors[6], double r, uint32_t dimensions, const uint32_t cells[3],
+                                      const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t flags,
+                                      uint64_t* out_offsets, uint64_t* out_summary);
+    int pgsd_neighbour_list_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                   const double vectors[6], double r, uint32_t dimensions, const uint32_t cells[3],
+                                   const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t flags,
+                                   const uint64_t* offsets, uint64_t capacity, uint32_t* out_neighbours,
+                                   double* out_distance2);
 
     /* SPH kernel sums (pgsd.hoomd.sph_kernel_sums is the definition, and the results equal it exactly: every counter and
        index, every float bit for bit -- a NaN is a NaN, its sign and payload are the processor's).  position: an N x 3

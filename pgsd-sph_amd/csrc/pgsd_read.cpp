@@ -1047,6 +1047,116 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+// What pgsd_neighbour_offsets_device and pgsd_neighbour_list_device share: every refusal of pgsd_neighbours_device, with
+// its messages and in its order, the undefined bits of `flags`, the range of the position chunk and the arguments of the
+// pass.  PGSD_SUCCESS: `a`, `foff` and `bytes` are set (a.N == 0 is left to the caller: only n > 0 makes it a refusal).
+static int neighbour_list_arguments(const char* who, Impl* s, struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                    const double vectors[6], double r, uint32_t dimensions, const uint32_t cells[3],
+                                    const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t flags, NeighbourListArgs& a,
+                                    long long* foff, size_t* bytes)
+    {
+    const Refusal refuse = {who};
+    pgsd_index_entry c = *position; // a flush may move the index storage
+    memset(&a, 0, sizeof(a));
+    int rc = float_chunk(refuse, c, "the position chunk", 3, nullptr, &a.f64);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (n >= (1ull << 32))
+        return refuse("a list holds fewer than 2^32 entries");
+    if (dimensions != 2 && dimensions != 3)
+        return refuse("dimensions is 2 or 3");
+    if (!(r > 0.0 && r < HUGE_VAL))
+        return refuse("the range must be finite and positive");
+    rc = pair_grid(refuse, vectors, r, "range", dimensions, cells, &a.n_cells);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (flags & ~(uint32_t)NLIST_HALF)
+        return refuse("flags holds undefined bits (bit 0, the half list, is the only one)");
+    rc = whole_chunk_range(s, handle, c, foff, bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    a.N = c.N;
+    a.rows = rows;
+    a.cell = cell;
+    a.n = n;
+    std::copy(vectors, vectors + 6, a.vectors);
+    a.r = r;
+    a.r2 = r * r;
+    std::copy(cells, cells + 3, a.cells);
+    a.dims = dimensions;
+    a.half = (flags & NLIST_HALF) ? 1u : 0u;
+    return PGSD_SUCCESS;
+    }
+
+extern "C" int pgsd_neighbour_offsets_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                             const double vectors[6], double r, uint32_t dimensions, const uint32_t cells[3],
+                                             const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t flags,
+                                             uint64_t* out_offsets, uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_neighbour_offsets_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !vectors || !cells || !out_offsets || !out_summary || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    NeighbourListArgs a;
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = neighbour_list_arguments(who, s, handle, position, vectors, r, dimensions, cells, rows, cell, n, flags, a, &foff,
+                                      &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (n == 0)
+        {
+        // (out_offsets is device memory: its one word goes down the road too, as a memset on the pipeline's stream)
+        rc = ensure_device(s);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        }
+    else if (a.N == 0)
+        return refuse("an entry of the row list lies outside the position chunk (nothing was computed)");
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "neighbour list: ", [&](std::string* err)
+                          { return device_pipeline_neighbour_offsets(s->dev, foff, bytes, a, out_offsets, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_neighbour_list_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                          const double vectors[6], double r, uint32_t dimensions, const uint32_t cells[3],
+                                          const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t flags,
+                                          const uint64_t* offsets, uint64_t capacity, uint32_t* out_neighbours,
+                                          double* out_distance2)
+    try
+    {
+    static const char* who = "pgsd_neighbour_list_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !vectors || !cells || !offsets || (capacity > 0 && !out_neighbours)
+        || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    NeighbourListArgs a;
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = neighbour_list_arguments(who, s, handle, position, vectors, r, dimensions, cells, rows, cell, n, flags, a, &foff,
+                                      &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (n == 0)
+        return PGSD_SUCCESS; // no segment to fill
+    if (a.N == 0)
+        return refuse("an entry of the row list lies outside the position chunk (nothing was computed)");
+    return reduction_call(who, "neighbour list: ", [&](std::string* err)
+                          { return device_pipeline_neighbour_list(s->dev, foff, bytes, a, offsets, capacity, out_neighbours,
+                                                                  out_distance2, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 // What pgsd_sph_sums_device and pgsd_sph_gradients_device share: every refusal of the former (and, for the latter, of a
 // velocity chunk), the ranges of the chunks that are stored (position, mass, density, velocity) and the arguments of the
 // pass -- the support, the grid, r2, inv_h, sigma and G, formed once in float64.  PGSD_SUCCESS: `ranges` and `a` are set.

@@ -12,6 +12,8 @@
 //   pgsd_cells.hip     cell fields: the conservation sums' values per grid cell of a list in cell order, CSR offsets
 //   pgsd_neighbours.hip   the neighbour census: counts, nearest pair and pair histogram inside a range, over the runs
 //                      of adjacent cells of a list in cell order (pgsd_cells.hpp: the check and offsets kernels it shares)
+//   pgsd_neighbour_list.hip   neighbour lists: the census' neighbours as a CSR pair list -- count over the same traversal,
+//                      one-workgroup scan, offsets, fill inside the segments
 //   pgsd_sph.hip       the SPH kernel sums: summation density, number density and Shepard sum inside the support 2h, in
 //                      a defined order of the candidates (the same check and offsets kernels)
 //   pgsd_sph_gradients.hip   the SPH kernel gradients: density rate, velocity divergence and curl and the colour gradient

@@ -6,8 +6,8 @@
 // without contraction (pgsd.hoomd.pair_displacement) and the strict test d2 < r2.  The functor receives (j, dx, dy, dz, d2)
 // of every candidate that passes, in the defined order, and is inlined with what it captures: accumulators it holds by
 // reference stay in registers.  With it what the compact kernels of the same units share: the copy of one position row
-// into xs and the read of one column value.  Used by pgsd_neighbours.hip, pgsd_sph.hip and pgsd_sph_gradients.hip, which
-// carry no copy of any of it.  Seen by the HIP compiler alone.
+// into xs and the read of one column value.  Used by pgsd_neighbours.hip, pgsd_neighbour_list.hip, pgsd_sph.hip and
+// pgsd_sph_gradients.hip, which carry no copy of any of it.  Seen by the HIP compiler alone.
 #ifndef PGSD_TRAVERSE_HPP
 #define PGSD_TRAVERSE_HPP
 

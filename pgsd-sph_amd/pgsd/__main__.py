@@ -23,6 +23,10 @@
            nowhere, the mean, smallest and largest neighbour count, the isolated entries and the closest pair with its
            rows and distance, and with ``--bins B`` the g(r) table (``--types``; ``pgsd.hoomd.frame_neighbours`` on the
            host: no GPU);
+           ``--neighbour-list R`` adds what a neighbour list inside the range R would hold: the search grid, the entries
+           and those nowhere, the pairs, the longest segment and the bytes the list occupies, ``8 (n + 1) + 4 pairs`` and
+           ``8 pairs`` more with distances -- what a restart budgets in HBM before it asks (``--half``: each pair once;
+           ``--types``; ``pgsd.hoomd.frame_neighbour_list`` on the host: no GPU);
            ``--sph [H]`` adds the SPH kernel sums for the smoothing length H (without H: the frame's ``slength``, which
            must be uniform): the search grid and the entries, the range of the summation density, its largest deviation
            from the stored density with the row, the range of the Shepard sum and -- with ``--surface S`` -- the entries
@@ -102,6 +106,8 @@ def _cmd_info(args):
         _print_cells(args, frame)
     if args.neighbours is not None:
         _print_neighbours(args, frame)
+    if args.neighbour_list is not None:
+        _print_neighbour_list(args, frame)
     if args.sph is not None:
         _print_sph(args, frame)
     if args.sph_gradients is not None:
@@ -146,6 +152,20 @@ def _print_sph(args, frame):
             print("  shepard:      smallest %r  largest %r" % (m.shepard_min, m.shepard_max))
         if m.surface is not None:
             print("  surface:      %d entries below %r" % (m.surface, m.surface_below))
+
+
+def _print_neighbour_list(args, frame):
+    """``info --neighbour-list``: `pgsd.hoomd.frame_neighbour_list` of one frame inside the range R, on the host."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_neighbour_list(traj[frame], args.neighbour_list, half=args.half, where=where)
+    print("neighbour list of frame %d inside %r over %d x %d x %d cells%s%s:"
+          % ((frame, m.r) + m.grid + (" (half)" if m.half else "", " (types %s)" % args.types if args.types else "")))
+    print("  entries:      %d  nowhere: %d" % (m.n, m.nowhere))
+    print("  pairs:        %d  longest segment: %d" % (m.pairs, m.longest))
+    print("  bytes:        %d  with distances: %d"
+          % (hoomd.neighbour_list_bytes(m.n, m.pairs), hoomd.neighbour_list_bytes(m.n, m.pairs, True)))
 
 
 def _print_neighbours(args, frame):
@@ -384,6 +404,10 @@ def main(argv=None):
     p.add_argument('--neighbours', type=float, default=None, metavar='R',
                    help="print the neighbour census inside the range R: grid, entries, mean, smallest and largest count, "
                         "isolated entries and the closest pair")
+    p.add_argument('--neighbour-list', type=float, default=None, metavar='R',
+                   help="print what a neighbour list inside the range R holds: grid, entries, pairs, the longest segment "
+                        "and the bytes it occupies, without and with distances")
+    p.add_argument('--half', action='store_true', help="with --neighbour-list: each pair once (j > i by list position)")
     p.add_argument('--sph', type=float, nargs='?', const=-1.0, default=None, metavar='H',
                    help="print the SPH kernel sums for the smoothing length H (without H: the frame's uniform slength): "
                         "grid, entries, density range, largest deviation from the stored density, Shepard range")

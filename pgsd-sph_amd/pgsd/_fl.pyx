@@ -2007,6 +2007,68 @@ cdef class PGSDFile:
             got.nearest2 = _device_head(out_nearest2, count)
         return got
 
+    def neighbour_list_device(self, frame, name, box, r, cells, rows, cell, n=None, dimensions=3, half=False,
+                              distances=False):
+        """The neighbours of a row list in cell order inside the range ``r`` as a CSR pair list, on the GPU: what
+        :meth:`neighbours_device` counts, handed over.
+
+        Args:
+            frame, name, box, r, cells, rows, cell, n, dimensions: as :meth:`neighbours_device` takes them.
+            half (bool): the segment of entry ``i`` keeps only ``j > i`` by list position.
+            distances (bool): also return the squared distance of every pair.
+
+        Returns:
+            A :class:`pgsd.hoomd.NeighbourList`: exactly :func:`pgsd.hoomd.neighbour_list` of the same list -- every offset
+            and index, ``distance2`` bit for bit.  Its ``rows`` and ``cell`` are the arguments; ``offsets`` (uint64, ``n +
+            1``), ``neighbours`` (uint32) and, when asked for, ``distance2`` (float64) are library-owned
+            :class:`DeviceBuffer` s on the pipeline's device, the last two of exactly ``pairs`` entries (an empty view of a
+            one-entry allocation where there is no pair).  Two passes: :c:func:`pgsd_neighbour_offsets_device` counts and
+            scans, the segments are allocated, :c:func:`pgsd_neighbour_list_device` fills them.  The chunk is staged whole
+            unless the ordering left it staged; the staged rows are kept until the next :meth:`wait_read`.  What the
+            library refuses raises ValueError.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("neighbour_list_device", cells)
+        range_ = float(r)
+        c_rows, c_cell, count = _cell_ordered_lists("neighbour_list_device", rows, cell, n)
+        device = self.pipeline_device()
+        summary = numpy.zeros(4, dtype=numpy.uint64)
+        offsets = DeviceBuffer((count + 1,), numpy.uint64, device)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the passes are ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_summary = summary.ctypes.data, p_offsets = offsets.ptr, p_neighbours, p_distance2 = 0
+        cdef uint64_t c_n = count, c_capacity
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0, c_flags = 1 if half else 0
+        cdef double c_r = range_
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_neighbour_offsets_device(&self._handle, &entry, <const double*>p_vectors, c_r, c_dims,
+                                                     <const uint32_t*>p_cells, <const uint32_t*>p_rows,
+                                                     <const int32_t*>p_cell, c_n, c_flags, <uint64_t*>p_offsets,
+                                                     <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("neighbour_list_device", retval, "refused", self._name, err)
+        pairs = int(summary[2])
+        neighbours = DeviceBuffer((max(pairs, 1),), numpy.uint32, device).view(shape=(pairs,))
+        distance2 = DeviceBuffer((max(pairs, 1),), numpy.float64, device).view(shape=(pairs,)) if distances else None
+        p_neighbours = neighbours.ptr
+        if distances:
+            p_distance2 = distance2.ptr
+        c_capacity = pairs
+        with nogil:
+            retval = C.pgsd_neighbour_list_device(&self._handle, &entry, <const double*>p_vectors, c_r, c_dims,
+                                                  <const uint32_t*>p_cells, <const uint32_t*>p_rows, <const int32_t*>p_cell,
+                                                  c_n, c_flags, <const uint64_t*>p_offsets, c_capacity,
+                                                  <uint32_t*>p_neighbours, <double*>p_distance2)
+            err = errno
+        _raise_refused("neighbour_list_device", retval, "refused", self._name, err)
+        return _hoomd.NeighbourList(range_, grid, int(dimensions), bool(half), summary, _device_head(rows, count),
+                                    _device_head(cell, count), offsets, neighbours, distance2)
+
     def sph_sums_device(self, frame, name, box, h, cells, rows, cell, n=None, mass=None, density=None, defaults=None,
                         dimensions=3, kernel='wendland_c2', surface_below=None, return_rows=False):
         """The SPH kernel sums of a row list in cell order on the GPU: summation density, number density and Shepard sum

@@ -1805,6 +1805,151 @@ def frame_neighbours(frame_or_arrays, r, bins=0, cells=None, where=None, types=N
     return particle_neighbours(position, box, r, rows=rows, cells=cells, dimensions=dimensions, bins=bins)
 
 
+# ---- neighbour lists: the definition the GPU passes (`pgsd.fl.PGSDFile.neighbour_list_device`) equal exactly
+_NLIST_SUMMARY_WORDS = 4            # n, nowhere, pairs, longest
+
+
+def neighbour_list_bytes(n, pairs, distances=False):
+    """The bytes a `NeighbourList` of ``n`` entries and ``pairs`` pairs occupies: ``8 (n + 1) + 4 pairs``, plus ``8
+    pairs`` with distances -- what a restart budgets in HBM before it asks for the list."""
+    return 8 * (int(n) + 1) + (12 if distances else 4) * int(pairs)
+
+
+class NeighbourList(object):
+    """The neighbours of a list in cell order as a CSR pair list (`neighbour_list`).
+
+    Attributes:
+        r (float), grid (``(cx, cy, cz)``), dimensions (int), half (bool): what was asked.
+        rows, cell: the list in cell order and its cell ids (``n_cells``: nowhere), as on `Neighbours`.
+        offsets (uint64, ``n + 1``): ``offsets[0] == 0``, ``offsets[k + 1] - offsets[k]`` the length of entry ``k``'s
+            segment, ``offsets[n] == pairs``.
+        neighbours (uint32, ``pairs``): the LIST POSITIONS of the neighbours, segment after segment.
+        distance2 (float64, ``pairs``) or ``None``: `pair_distance2` of each pair, where distances were asked for.
+        n, nowhere (int): the entries, and those without a cell; pairs (int): the entries of ``neighbours``; longest
+            (int): the largest segment length (0 at ``n == 0``).
+        counts (property), `of`, `pair_rows`: host-side conveniences over numpy arrays; on a list whose arrays were left in
+            GPU memory they raise ValueError -- copy the arrays to the host first.
+    """
+
+    __slots__ = ('r', 'grid', 'dimensions', 'half', 'rows', 'cell', 'offsets', 'neighbours', 'distance2', 'n', 'nowhere',
+                 'pairs', 'longest')
+
+    def __init__(self, r, grid, dimensions, half, summary, rows=None, cell=None, offsets=None, neighbours=None,
+                 distance2=None):
+        """``summary``: the four uint64 words of `pgsd_neighbour_offsets_device` -- n, nowhere, pairs, longest."""
+        s = numpy.asarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _NLIST_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _NLIST_SUMMARY_WORDS)
+        self.r, self.dimensions, self.half = float(r), int(dimensions), bool(half)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.n, self.nowhere, self.pairs, self.longest = (int(v) for v in s)
+        self.rows, self.cell, self.offsets, self.neighbours, self.distance2 = rows, cell, offsets, neighbours, distance2
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return numpy.array([self.n, self.nowhere, self.pairs, self.longest], dtype=numpy.uint64)
+
+    @property
+    def nbytes(self):
+        """`neighbour_list_bytes` of this list."""
+        return neighbour_list_bytes(self.n, self.pairs, self.distance2 is not None)
+
+    def _host(self, name):
+        x = getattr(self, name)
+        if not isinstance(x, numpy.ndarray):
+            raise ValueError("NeighbourList.%s is %s: this works on numpy arrays (copy the arrays to the host first)"
+                             % (name, "not set" if x is None else "in GPU memory"))
+        return x
+
+    @property
+    def counts(self):
+        """The segment lengths (uint64, ``n``): the differences of ``offsets``."""
+        return numpy.diff(self._host('offsets'))
+
+    def of(self, k):
+        """The neighbours of entry ``k``: its slice of ``neighbours`` (a view)."""
+        offsets, neighbours = self._host('offsets'), self._host('neighbours')
+        k = int(k)
+        if not 0 <= k < self.n:
+            raise IndexError("entry %d of a list of %d" % (k, self.n))
+        return neighbours[int(offsets[k]):int(offsets[k + 1])]
+
+    def pair_rows(self):
+        """``pairs x 2``: ``(rows[i], rows[j])`` of every pair, in list order."""
+        rows, neighbours = self._host('rows'), self._host('neighbours')
+        i = numpy.repeat(numpy.arange(self.n, dtype=numpy.int64), self.counts.astype(numpy.int64))
+        return numpy.stack([rows[i], rows[neighbours.astype(numpy.int64)]], axis=1)
+
+    def __repr__(self):
+        return "NeighbourList(r=%r, grid=%r, half=%r, n=%d, nowhere=%d, pairs=%d, longest=%d)" % (
+            self.r, self.grid, self.half, self.n, self.nowhere, self.pairs, self.longest)
+
+
+def neighbour_list(position, box, r, rows=None, cells=None, dimensions=3, half=False, distances=False):
+    """The neighbours of a row list inside the range ``r`` as a CSR pair list: what `particle_neighbours` counts, handed
+    over.  The definition the GPU passes (`pgsd.fl.PGSDFile.neighbour_list_device`,
+    `HOOMDTrajectory.frame_neighbour_list_device`) equal exactly.
+
+    The grid, every refusal, the list in cell order (`cell_order`), the candidates, the arithmetic of one pair
+    (`pair_distance2`, strict ``d2 < r*r`` with ``r*r`` formed once) and the treatment of entries without a cell are
+    `particle_neighbours`' for the same ``r``; ``position``, ``box``, ``rows``, ``cells`` and ``dimensions`` are its
+    arguments.  A list has an order, and that is what is new here:
+
+    **The segment of entry** ``i`` holds the list positions ``j`` of its neighbours, ``j != i`` as a list position (a row
+    listed twice is two entries, each the other's neighbour at distance 0), in THE ORDER of `sph_kernel_sums`: ``oz``
+    over `_axis_offsets` ``(cz)``, inside it ``oy``, inside it ``ox``, the cell ``((ix+ox) % cx, (iy+oy) % cy, (iz+oz) %
+    cz)``, inside a cell ascending list position (the walk is `_sph_near_pairs`, shared with the sums).  An entry without
+    a cell has an empty segment and appears in nobody's.
+
+    ``half=True``: the segment of ``i`` keeps only ``j > i`` by list position -- the same filter of the same full segment,
+    in the same order.  At an exact half-box tie in a tilted box ``i -> j`` and ``j -> i`` may differ (`Neighbours`
+    ``.pairs``); the half list is then whatever the filter gives: a pair is listed iff ``i -> j`` with ``i < j`` is inside
+    the range.
+
+    ``distances=True`` adds ``distance2``: ``pair_distance2(x_i, x_j)`` of each pair, bit for bit.
+
+    Returns a `NeighbourList`.  If a frame is read with ``read_frame_device(..., cell_order=grid)`` for the same
+    selection and grid and without a ghost layer, list position ``k`` is row ``k`` of the restarted arrays, so
+    ``neighbours`` indexes them directly (with a ghost layer the owned and the ghost run are sorted separately: not
+    covered).
+    """
+    dimensions = int(dimensions)
+    grid = _neighbour_grid(box, r, cells, dimensions)
+    r = float(r)
+    # (the list ahead of the pair loop is the SPH sums': h is not looked at by the walk, the support stands for r)
+    t = _sph_list((dimensions, 1.0, 0, r, grid), position, box, rows, ())
+    n = t.n
+    parts = [(numpy.zeros(0, numpy.int64), numpy.zeros(0, numpy.int64), numpy.zeros(0, numpy.float64))]
+    for i, j, _, d2 in _sph_near_pairs(t):
+        keep = (j > i) if half else (j != i)
+        parts.append((i[keep], j[keep], d2[keep]))
+    i = numpy.concatenate([p[0] for p in parts])
+    # (stable: an entry's pairs keep the order of the steps, which is the order of the cells, and inside a step ascending j)
+    order = numpy.argsort(i, kind='stable')
+    counts = numpy.bincount(i, minlength=n).astype(numpy.uint64)
+    offsets = numpy.zeros(n + 1, dtype=numpy.uint64)
+    numpy.cumsum(counts, out=offsets[1:])
+    neighbours = numpy.concatenate([p[1] for p in parts])[order].astype(numpy.uint32)
+    distance2 = numpy.concatenate([p[2] for p in parts])[order] if distances else None
+    summary = [n, n - t.somewhere, int(offsets[n]), int(counts.max()) if n else 0]
+    return NeighbourList(r, grid, dimensions, half, summary, t.rows_sorted, t.cell_sorted, offsets, neighbours, distance2)
+
+
+def frame_neighbour_list(frame_or_arrays, r, half=False, distances=False, cells=None, where=None, types=None, domain=None,
+                         box=None, dimensions=3):
+    """`neighbour_list` of a frame's ``position`` over a selection: the host twin of
+    `HOOMDTrajectory.frame_neighbour_list_device`, which equals it exactly.  The selection is `frame_neighbours`' and is
+    the list: both ``i`` and ``j`` come from it.  A position that is stored nowhere puts every row at the origin.
+
+    If the frame is read with ``read_frame_device(idx, where=..., domain=..., cell_order=grid)`` for the same selection
+    and the same grid, without a ghost layer, list position ``k`` is row ``k`` of the restarted arrays, so ``neighbours``
+    indexes them directly.  Returns a `NeighbourList`."""
+    _neighbour_range(r)
+    _, position, box, dimensions, _, rows = _sph_frame_list(frame_or_arrays, float(r), where, types, domain, box, dimensions)
+    return neighbour_list(position, box, r, rows=rows, cells=cells, dimensions=dimensions, half=half, distances=distances)
+
+
 # ---- SPH kernel sums: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_sums_device`) equals exactly
 SPH_KERNELS = ('wendland_c2', 'cubic_spline')
 _SPH_SUMMARY_WORDS = 13     # n, nowhere, not_finite, surface, deviation_at, deviation_row, 3 x (min, max), deviation
@@ -4296,6 +4441,41 @@ class HOOMDTrajectory(object):
             cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
             got = f.neighbours_device(f_pos, 'particles/position', box, r, grid, rows, cell, n=count, dimensions=dims,
                                       bins=bins, return_rows=return_rows)
+        finally:
+            f.wait_read()
+        return got
+
+    def frame_neighbour_list(self, idx, r, half=False, distances=False, cells=None, where=None, domain=None):
+        """`frame_neighbour_list` of frame ``idx`` read through the host path: a `NeighbourList`.  The definition of
+        `frame_neighbour_list_device`."""
+        return frame_neighbour_list(self[int(idx)], r, half=half, distances=distances, cells=cells, where=where,
+                                    domain=domain)
+
+    def frame_neighbour_list_device(self, idx, r, half=False, distances=False, cells=None, where=None, domain=None):
+        """`frame_neighbour_list` of frame ``idx``, on the GPU: a `NeighbourList` that equals
+        ``frame_neighbour_list(idx, r, ...)`` exactly -- every offset and index, ``distance2`` bit for bit -- with
+        ``rows``, ``cell``, ``offsets``, ``neighbours`` and ``distance2`` in GPU memory.
+
+        The selection, the grid, the ordering over the staged position chunk and the one closing `wait_read` are
+        `frame_neighbours_device`'s; the two passes (`pgsd.fl.PGSDFile.neighbour_list_device`) run over the same staged
+        chunk.  Read with ``read_frame_device(idx, where=..., domain=..., cell_order=grid)`` for the same selection and
+        grid, without a ghost layer, row ``k`` of the restarted arrays is list position ``k``: ``neighbours`` indexes
+        them directly.  A frame whose position is stored nowhere has no chunk to search and raises ValueError.
+        """
+        idx = self._frame_index(idx)
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        grid = _neighbour_grid(box, r, cells, dims)
+        if f_pos is None:
+            raise ValueError("frame_neighbour_list_device: the position is stored nowhere (every particle sits at the "
+                             "origin)")
+        try:
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
+            if rows is None:
+                rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
+            cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
+            got = f.neighbour_list_device(f_pos, 'particles/position', box, r, grid, rows, cell, n=count, dimensions=dims,
+                                          half=half, distances=distances)
         finally:
             f.wait_read()
         return got

@@ -243,6 +243,13 @@ cdef extern from "pgsd_private.h" nogil:
                                uint32_t dimensions, const uint32_t* cells, const uint32_t* rows, const int32_t* cell,
                                uint64_t n, uint32_t bins, const double* edges2, uint32_t* out_count, double* out_nearest2,
                                uint32_t* out_nearest, uint64_t* out_summary, double* out_closest2)
+    int pgsd_neighbour_offsets_device(pgsd_handle* handle, const pgsd_index_entry* position, const double* vectors, double r,
+                                      uint32_t dimensions, const uint32_t* cells, const uint32_t* rows, const int32_t* cell,
+                                      uint64_t n, uint32_t flags, uint64_t* out_offsets, uint64_t* out_summary)
+    int pgsd_neighbour_list_device(pgsd_handle* handle, const pgsd_index_entry* position, const double* vectors, double r,
+                                   uint32_t dimensions, const uint32_t* cells, const uint32_t* rows, const int32_t* cell,
+                                   uint64_t n, uint32_t flags, const uint64_t* offsets, uint64_t capacity,
+                                   uint32_t* out_neighbours, double* out_distance2)
     int pgsd_sph_sums_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* mass,
                              const pgsd_index_entry* density, const double* defaults, const double* vectors, double h,
                              uint32_t kernel, uint32_t dimensions, const uint32_t* cells, const uint32_t* rows,
