@@ -214,6 +214,7 @@ int DevicePipeline::init()
         warm_neighbour_list_kernels();
         warm_sph_kernels();
         warm_sph_gradients_kernels();
+        warm_sph_forces_kernels();
         int brc = compare_buffers();
         if (brc != PGSD_SUCCESS)
             return brc;

@@ -449,7 +449,7 @@ int DevicePipeline::stage_present(const ChunkRange* ranges, const void** const* 
 // wait_read for an indexed read of the same chunk --; where the pass writes or reads memory of the caller's on the device
 // (`callers_memory`: a row list, shifts), what the caller's stream still does with that memory comes first;
 // `launch(stream, why)` launches on the pack stream, synchronises it and returns a pgsd_error; a PGSD_ERROR_DEVICE fails
-// the pipeline with the launcher's message.  The message of a failure, for all sixteen passes: the launcher's own first,
+// the pipeline with the launcher's message.  The message of a failure, for all seventeen passes: the launcher's own first,
 // else the pipeline's, else the thread's last error.
 template<class Launch>
 int DevicePipeline::staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N,
@@ -631,6 +631,18 @@ int device_pipeline_sph_gradients(DevicePipeline* p, const ChunkRange* ranges, c
     return p->staged_launch(ranges, slots, 4, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
                             { return launch_sph_gradients(a, out_rate, out_divergence, out_curl, out_normal, out_summary, stream,
                                                           why); });
+    }
+
+// SPH accelerations: as the gradients, with one more slot: the pressure chunk where one is stored
+int device_pipeline_sph_accelerations(DevicePipeline* p, const ChunkRange* ranges, const SphForcesArgs& args,
+                                      double* out_pressure_acc, double* out_viscous_acc, double* out_total,
+                                      uint64_t* out_summary, std::string* err)
+    {
+    SphForcesArgs a = args;
+    const void** const slots[5] = {&a.pos, &a.mass, &a.density, &a.velocity, &a.pressure};
+    return p->staged_launch(ranges, slots, 5, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                            { return launch_sph_accelerations(a, out_pressure_acc, out_viscous_acc, out_total, out_summary,
+                                                              stream, why); });
     }
 
 // Neighbour lists: the census's staging for both calls (the fill finds the chunk the offsets call left staged); the lists,

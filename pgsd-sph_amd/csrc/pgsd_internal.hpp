@@ -559,6 +559,38 @@ inline void sph_gradients_of_nothing(uint64_t* out_summary)
 int device_pipeline_sph_gradients(DevicePipeline*, const ChunkRange* ranges, const SphGradientsArgs& a, double* out_rate,
                                   double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary,
                                   std::string* err);
+// SPH accelerations (pgsd.hoomd.sph_accelerations is the definition): per entry of a row list in cell order the pressure
+// acceleration -sum_j m_j (p_i/rho_i^2 + p_j/rho_j^2) grad_i W_ij, Morris' laminar viscous acceleration for one constant
+// mu and their sum with gravity over the entries inside the support 2h, in the sums' order, and over the list the
+// largest of each with its row.  The grid, the support, the list and the mass and density defaults are SphArgs'
+// (volume, surface and surface_below are not looked at: the density default is a number here).
+enum
+    {
+    SPHF_SUMMARY_WORDS = 12 // n, nowhere, not_finite, 3 x (at, row) of total, pressure, viscous, then total2, pressure2, viscous2
+    };
+struct SphForcesArgs : SphGradientsArgs
+    {
+    const void* pressure;    // the staged pressure chunk, N x 1, or null: the default stands for every row
+    double pressure_default;
+    double eta2, Gv;         // (0.01*h)*h and G*(2.0*mu), formed once on the host (Gv is not looked at without `viscous`)
+    double gravity[3];
+    uint32_t pressure_f64;   // present bit 4: a pressure chunk is stored (ranges[4])
+    uint32_t viscous;        // a viscosity was given: the viscous term is formed
+    };
+// the summary of no entry
+inline void sph_forces_of_nothing(uint64_t* out_summary)
+    {
+    std::fill(out_summary, out_summary + SPHF_SUMMARY_WORDS, (uint64_t)0); // (+0.0 is the zero word)
+    std::fill(out_summary + 3, out_summary + 9, (uint64_t)SPH_NONE);
+    }
+// stage the chunks that are present (ranges[0 .. 4]: position, mass, density, velocity, pressure; the five pointers are
+// filled in) -- or take them from what an earlier call left staged --, check the lists, sum on the GPU; out_pressure_acc,
+// out_viscous_acc, out_total (device, a.n x 3, or null; the second is written with a.viscous only); out_summary (host, 12
+// words) is written on success only, and so are the device outputs; synchronous.  The refusals and the staging are
+// device_pipeline_sph_sums'.
+int device_pipeline_sph_accelerations(DevicePipeline*, const ChunkRange* ranges, const SphForcesArgs& a,
+                                      double* out_pressure_acc, double* out_viscous_acc, double* out_total,
+                                      uint64_t* out_summary, std::string* err);
 // Neighbour lists (pgsd.hoomd.neighbour_list is the definition): the neighbours the census counts, handed over as a CSR
 // pair list -- per entry of a row list in cell order the list positions of its neighbours in the order the SPH kernel
 // sums define, in two calls: the offsets (count, scan), then the segments (fill).  The grid, the range and the list are

@@ -332,6 +332,14 @@ int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, d
 int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* out_divergence, double* out_curl,
                          double* out_normal, uint64_t* out_summary, hipStream_t stream, std::string* err);
 
+// SPH accelerations (pgsd_sph_forces.hip; SphForcesArgs, the chunk pointers filled in): check, offsets, compaction of the
+// listed positions, masses, A = p/rho^2, volumes, densities and velocities, one lane per entry over the candidates in the
+// sums' order (pgsd_traverse.hpp), one workgroup for the largest norms.  out_pressure_acc, out_viscous_acc, out_total
+// (device, a.n x 3), each or null; out_summary (host, 12 words) is written on success only.  Synchronises `stream`;
+// PGSD_ERROR_INVALID_ARGUMENT for an id that descends or lies outside [0, n_cells] and for an entry >= a.N
+int launch_sph_accelerations(const SphForcesArgs& a, double* out_pressure_acc, double* out_viscous_acc, double* out_total,
+                             uint64_t* out_summary, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);
@@ -394,6 +402,7 @@ void warm_neighbours_kernels();
 void warm_neighbour_list_kernels();
 void warm_sph_kernels();
 void warm_sph_gradients_kernels();
+void warm_sph_forces_kernels();
 
 // algorithmic traffic of one job: bytes that must be read (needed columns only, plus the
 // gather index) and chunk bytes written

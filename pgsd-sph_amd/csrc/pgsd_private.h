@@ -55,6 +55,11 @@
  *                     frame_kernel_gradients_device: per entry of the same list, over the same support and in the same
  *                     order, the density rate of the continuity equation, the velocity divergence and curl and the
  *                     colour gradient, and over the list their ranges and the largest vorticity and surface normal)
+ *                     pgsd_sph_accelerations_device (pgsd.fl's sph_accelerations_device, behind pgsd.hoomd's
+ *                     frame_accelerations_device: per entry of the same list, over the same support and in the same
+ *                     order, the pressure and the laminar viscous acceleration and their sum with gravity, and over the
+ *                     list the largest of each with its row -- is the frame in equilibrium, and what time step does it
+ *                     allow)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -519,6 +524,49 @@ extern "C"
                                   double h, uint32_t kernel, uint32_t dimensions, const uint32_t cells[3],
                                   const uint32_t* rows, const int32_t* cell, uint64_t n, double* out_density_rate,
                                   double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary);
+
+    /* SPH accelerations (pgsd.hoomd.sph_accelerations is the definition, and the results equal it exactly: every counter
+       and index, every float bit for bit -- a NaN is a NaN).  position, velocity, mass, density, vectors, h, kernel,
+       dimensions, cells, rows, cell and n are pgsd_sph_gradients_device's, and so are the grid, the support 2h, r2, inv_h,
+       sigma, G, F(q) and THE ORDER of the candidates.  pressure: an N x 1 float32 or float64 chunk, or NULL.  defaults:
+       the mass, the density and the pressure that stand for a chunk stored nowhere (the density default is a number
+       here: there is no "no volume").  viscosity: mu >= 0, or any negative number: no viscous term.  gravity: g[3].
+       On the host, once, in float64: eta2 = (0.01*h)*h and Gv = G * (2.0*mu).
+       PER ENTRY k, once, float64 from the stored values: A_k = p_k / (rho_k*rho_k), V_k = m_k / rho_k (a density of 0
+       gives what IEEE gives).
+       ONE PAIR i <- j, float64, no contraction: d, d2, the strict test d2 < r2, rr = sqrt(d2), q = rr * inv_h and F as in
+       the gradients; i itself and coincident entries are candidates like any other (their e is zero, so an infinite S
+       gives a NaN there);
+           e_k = F * d_k, S = A_i + A_j, a_p[k] += m_j * (S * e_k)
+       and with a viscosity (Morris' laminar viscosity for one constant mu)
+           K = (F * d2) / (d2 + eta2), u_k = v_j[k] - v_i[k], a_v[k] += V_j * (K * u_k).
+       The three or six accumulators per entry start at +0.0 and add in the defined order.  After the last candidate
+           pressure_acc[k] = -(G * a_p[k]), viscous_acc[k] = (Gv * a_v[k]) / rho_i,
+           total[k] = (pressure_acc[k] + viscous_acc[k]) + g[k], or pressure_acc[k] + g[k] without a viscosity.
+       An entry with id n_cells is nowhere: it contributes to nobody and all its values are +0.0, the total too.  With
+       dimensions == 2 d_z is 0 and nothing else differs.
+       Device outputs, n x 3 float64, each optional (NULL): out_pressure_acc, out_viscous_acc (not written without a
+       viscosity), out_total.
+       Host output, 12 words:
+           out_summary[0 .. 2]    n; the entries nowhere; the entries that have a cell and whose total has a component
+                                  that is NaN or infinite
+           out_summary[3 .. 8]    the list position and the row of the largest total, of the largest pressure_acc and of
+                                  the largest viscous_acc; 0xFFFFFFFF without one
+           out_summary[9 .. 11]   as float64 bit patterns the largest total2 = (a0*a0 + a1*a1) + a2*a2 of the outputs,
+                                  pressure2 and viscous2 over the entries that have a cell, the smaller list position on
+                                  a tie, a NaN never; +0.0 without one
+       No float is summed over the list.  Staging, synchronisation and n == 0 are pgsd_sph_sums_device's.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), every output as it was: everything
+       pgsd_sph_gradients_device refuses; a pressure chunk that is not one float32 or float64 column or has another N
+       than position; a viscosity that is NaN or infinite; a gravity component that is not finite. */
+    int pgsd_sph_accelerations_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                      const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
+                                      const struct pgsd_index_entry* density, const struct pgsd_index_entry* pressure,
+                                      const double defaults[3], const double vectors[6], double h, uint32_t kernel,
+                                      uint32_t dimensions, const uint32_t cells[3], double viscosity,
+                                      const double gravity[3], const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                      double* out_pressure_acc, double* out_viscous_acc, double* out_total,
+                                      uint64_t* out_summary);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

@@ -1157,14 +1157,17 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
-// What pgsd_sph_sums_device and pgsd_sph_gradients_device share: every refusal of the former (and, for the latter, of a
-// velocity chunk), the ranges of the chunks that are stored (position, mass, density, velocity) and the arguments of the
-// pass -- the support, the grid, r2, inv_h, sigma and G, formed once in float64.  PGSD_SUCCESS: `ranges` and `a` are set.
+// What pgsd_sph_sums_device, pgsd_sph_gradients_device and pgsd_sph_accelerations_device share: every refusal of the
+// first (and, for the other two, of a velocity chunk; for the last, of a pressure chunk), the ranges of the chunks that
+// are stored (position, mass, density, velocity, pressure) and the arguments of the pass -- the support, the grid, r2,
+// inv_h, sigma and G, formed once in float64.  PGSD_SUCCESS: `ranges` and `a` are set (what the accelerations add to
+// them -- the pressure default, the viscosity and the gravity -- is their entry point's).
 static int sph_arguments(const char* who, Impl* s, struct pgsd_handle* handle, const struct pgsd_index_entry* position,
                          const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
-                         const struct pgsd_index_entry* velocity, const double defaults[2], const double vectors[6], double h,
-                         uint32_t kernel, uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
-                         const int32_t* cell, uint64_t n, double surface_below, ChunkRange ranges[4], SphGradientsArgs& a)
+                         const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* pressure,
+                         const double defaults[2], const double vectors[6], double h, uint32_t kernel, uint32_t dimensions,
+                         const uint32_t cells[3], const uint32_t* rows, const int32_t* cell, uint64_t n, double surface_below,
+                         ChunkRange ranges[5], SphForcesArgs& a)
     {
     const Refusal refuse = {who};
     pgsd_index_entry c = *position; // a flush may move the index storage
@@ -1180,8 +1183,8 @@ static int sph_arguments(const char* who, Impl* s, struct pgsd_handle* handle, c
         return refuse("the smoothing length must be finite and positive");
     if (kernel != SPH_WENDLAND_C2 && kernel != SPH_CUBIC_SPLINE)
         return refuse("the kernel is 0 (Wendland C2) or 1 (cubic spline)");
-    memset(ranges, 0, 4 * sizeof(ChunkRange));
-    a = SphGradientsArgs();
+    memset(ranges, 0, 5 * sizeof(ChunkRange));
+    a = SphForcesArgs();
     // the column chunks that are stored: ranges[1 + i] and bit 1 + i of `present`
     const struct
         {
@@ -1189,10 +1192,11 @@ static int sph_arguments(const char* who, Impl* s, struct pgsd_handle* handle, c
         const char* subject;
         uint32_t columns;
         uint32_t* is_f64;
-        } columns[3] = {{mass, "the mass chunk", 1, &a.mass_f64},
+        } columns[4] = {{mass, "the mass chunk", 1, &a.mass_f64},
                         {density, "the density chunk", 1, &a.density_f64},
-                        {velocity, "the velocity chunk", 3, &a.velocity_f64}};
-    for (int i = 0; i < 3; i++)
+                        {velocity, "the velocity chunk", 3, &a.velocity_f64},
+                        {pressure, "the pressure chunk", 1, &a.pressure_f64}};
+    for (int i = 0; i < 4; i++)
         {
         if (!columns[i].entry)
             continue;
@@ -1256,10 +1260,10 @@ extern "C" int pgsd_sph_sums_device(struct pgsd_handle* handle, const struct pgs
     Impl* s = impl_of(handle);
     if (!s || !position || !defaults || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell)))
         return PGSD_ERROR_INVALID_ARGUMENT;
-    ChunkRange ranges[4];
-    SphGradientsArgs g;
-    int rc = sph_arguments(who, s, handle, position, mass, density, nullptr, defaults, vectors, h, kernel, dimensions, cells,
-                           rows, cell, n, surface_below, ranges, g);
+    ChunkRange ranges[5];
+    SphForcesArgs g;
+    int rc = sph_arguments(who, s, handle, position, mass, density, nullptr, nullptr, defaults, vectors, h, kernel, dimensions,
+                           cells, rows, cell, n, surface_below, ranges, g);
     if (rc != PGSD_SUCCESS)
         return rc;
     const SphArgs a = g;
@@ -1290,12 +1294,13 @@ extern "C" int pgsd_sph_gradients_device(struct pgsd_handle* handle, const struc
     Impl* s = impl_of(handle);
     if (!s || !position || !defaults || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell)))
         return PGSD_ERROR_INVALID_ARGUMENT;
-    ChunkRange ranges[4];
-    SphGradientsArgs a;
-    int rc = sph_arguments(who, s, handle, position, mass, density, velocity, defaults, vectors, h, kernel, dimensions, cells,
-                           rows, cell, n, NAN, ranges, a);
+    ChunkRange ranges[5];
+    SphForcesArgs g;
+    int rc = sph_arguments(who, s, handle, position, mass, density, velocity, nullptr, defaults, vectors, h, kernel, dimensions,
+                           cells, rows, cell, n, NAN, ranges, g);
     if (rc != PGSD_SUCCESS)
         return rc;
+    const SphGradientsArgs a = g;
     if (n == 0)
         {
         sph_gradients_of_nothing(out_summary);
@@ -1305,6 +1310,54 @@ extern "C" int pgsd_sph_gradients_device(struct pgsd_handle* handle, const struc
     return reduction_call(who, "SPH kernel gradients: ", [&](std::string* err)
                           { return device_pipeline_sph_gradients(s->dev, ranges, a, out_density_rate, out_divergence, out_curl,
                                                                  out_normal, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_sph_accelerations_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                             const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
+                                             const struct pgsd_index_entry* density, const struct pgsd_index_entry* pressure,
+                                             const double defaults[3], const double vectors[6], double h, uint32_t kernel,
+                                             uint32_t dimensions, const uint32_t cells[3], double viscosity,
+                                             const double gravity[3], const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                             double* out_pressure_acc, double* out_viscous_acc, double* out_total,
+                                             uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_sph_accelerations_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !defaults || !vectors || !cells || !gravity || !out_summary || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    ChunkRange ranges[5];
+    SphForcesArgs a;
+    int rc = sph_arguments(who, s, handle, position, mass, density, velocity, pressure, defaults, vectors, h, kernel,
+                           dimensions, cells, rows, cell, n, NAN, ranges, a);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    // (a negative viscosity says "none"; a NaN is neither)
+    if (!(viscosity < HUGE_VAL && viscosity > -HUGE_VAL))
+        return refuse("the viscosity must be finite (negative: no viscous term)");
+    for (int k = 0; k < 3; k++)
+        if (!(gravity[k] < HUGE_VAL && gravity[k] > -HUGE_VAL))
+            return refuse("the gravity must hold three finite components");
+    // host arithmetic in float64, formed once
+    a.pressure_default = defaults[2];
+    a.viscous = viscosity >= 0.0 ? 1u : 0u;
+    a.eta2 = (0.01 * h) * h;
+    a.Gv = a.viscous ? a.G * (2.0 * viscosity) : 0.0;
+    std::copy(gravity, gravity + 3, a.gravity);
+    if (n == 0)
+        {
+        sph_forces_of_nothing(out_summary);
+        return PGSD_SUCCESS;
+        }
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "SPH accelerations: ", [&](std::string* err)
+                          { return device_pipeline_sph_accelerations(s->dev, ranges, a, out_pressure_acc, out_viscous_acc,
+                                                                     out_total, out_summary, err); });
     }
 catch (...)
     {

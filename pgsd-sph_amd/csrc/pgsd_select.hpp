@@ -18,7 +18,9 @@
 //                      a defined order of the candidates (the same check and offsets kernels)
 //   pgsd_sph_gradients.hip   the SPH kernel gradients: density rate, velocity divergence and curl and the colour gradient
 //                      over the same support in the same order (pgsd_traverse.hpp: the traversal as an inlined template,
-//                      which the three pair units walk their candidates through)
+//                      which the pair units walk their candidates through)
+//   pgsd_sph_forces.hip   the SPH accelerations: pressure and laminar viscous acceleration and their sum with gravity
+//                      over the same support in the same order, the largest of each with its row
 //   pgsd_stats.hpp     what the two reduction units share: an element as a double, the wave tree, the wave counter
 //   pgsd_device_memory.cpp   pgsd_device_alloc / _free / _copy: device memory owned by the library (no kernel)
 //   pgsd_scratch.hpp / .cpp  the host side all of them stand on: scratch space, launch scope, device scope

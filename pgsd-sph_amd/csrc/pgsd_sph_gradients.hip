@@ -22,7 +22,8 @@
 //   sphg_final_kernel      one workgroup: the partials in a fixed strided scan, then the words of the summary
 // No float atomic anywhere, no private (scratch) memory in any instance.  Shared device helpers: pgsd_stats.hpp,
 // pgsd_kernels.hpp, pgsd_traverse.hpp (the position copy and the column read of the compact kernel as well); the
-// launcher's host side: pgsd_scratch.hpp and pgsd_cells.hpp (the argument checks and the opening sequence).
+// launcher's host side: pgsd_scratch.hpp and pgsd_cells.hpp (the argument checks and the opening sequence).  F(q) is
+// pgsd_traverse.hpp's sphg_factor, which the SPH accelerations (pgsd_sph_forces.hip) take as well.
 #include "pgsd_stats.hpp"
 #include "pgsd_cells.hpp"
 #include "pgsd_traverse.hpp"
@@ -101,25 +102,6 @@ __global__ __launch_bounds__(SEL_THREADS) void sphg_compact_kernel(const SphGrad
 #pragma unroll
     for (int c = 0; c < 3; c++)
         ws[k * 3 + c] = a.velocity ? column_value(a.velocity, a.velocity_f64, row * 3 + c) : 0.0;
-    }
-
-// F(q) = (1/q) dw/dq of pgsd.hoomd.sph_gradient_factor: the operations as written there, one rounding each; only the
-// spline's outer branch divides
-template<int KERNEL> __device__ __forceinline__ double sphg_factor(double q)
-    {
-#pragma clang fp contract(off)
-    if constexpr (KERNEL == SPH_WENDLAND_C2)
-        {
-        const double t = 1.0 - 0.5 * q;
-        return -5.0 * ((t * t) * t);
-        }
-    else
-        {
-        if (q < 1.0)
-            return 2.25 * q - 3.0;
-        const double u = 2.0 - q;
-        return (-0.75 * (u * u)) / q;
-        }
     }
 
 // words: the summary in device memory, zeroed by the launcher (word 2, not_finite, is added to here)

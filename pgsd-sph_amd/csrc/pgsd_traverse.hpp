@@ -6,8 +6,9 @@
 // without contraction (pgsd.hoomd.pair_displacement) and the strict test d2 < r2.  The functor receives (j, dx, dy, dz, d2)
 // of every candidate that passes, in the defined order, and is inlined with what it captures: accumulators it holds by
 // reference stay in registers.  With it what the compact kernels of the same units share: the copy of one position row
-// into xs and the read of one column value.  Used by pgsd_neighbours.hip, pgsd_neighbour_list.hip, pgsd_sph.hip and
-// pgsd_sph_gradients.hip, which carry no copy of any of it.  Seen by the HIP compiler alone.
+// into xs and the read of one column value -- and what the two gradient-weighted units share, the factor F(q).  Used by
+// pgsd_neighbours.hip, pgsd_neighbour_list.hip, pgsd_sph.hip, pgsd_sph_gradients.hip and pgsd_sph_forces.hip, which carry
+// no copy of any of it.  Seen by the HIP compiler alone.
 #ifndef PGSD_TRAVERSE_HPP
 #define PGSD_TRAVERSE_HPP
 
@@ -24,7 +25,7 @@ struct TraverseGrid
     uint32_t dims;
     };
 
-// the grid of a family's argument struct (NeighboursArgs, SphArgs, SphGradientsArgs)
+// the grid of a family's argument struct (NeighboursArgs, SphArgs, SphGradientsArgs, SphForcesArgs)
 template<typename Args> __device__ __forceinline__ TraverseGrid traverse_grid(const Args& a)
     {
     TraverseGrid g;
@@ -61,6 +62,25 @@ template<bool F64> __device__ __forceinline__ void compact_position(const void* 
 __device__ __forceinline__ double column_value(const void* base, uint32_t f64, uint64_t at)
     {
     return f64 ? ((const double*)base)[at] : (double)((const float*)base)[at];
+    }
+
+// F(q) = (1/q) dw/dq of pgsd.hoomd.sph_gradient_factor: the operations as written there, one rounding each; only the
+// spline's outer branch divides.  What the functors of pgsd_sph_gradients.hip and pgsd_sph_forces.hip form e = F * d with.
+template<int KERNEL> __device__ __forceinline__ double sphg_factor(double q)
+    {
+#pragma clang fp contract(off)
+    if constexpr (KERNEL == SPH_WENDLAND_C2)
+        {
+        const double t = 1.0 - 0.5 * q;
+        return -5.0 * ((t * t) * t);
+        }
+    else
+        {
+        if (q < 1.0)
+            return 2.25 * q - 3.0;
+        const double u = 2.0 - q;
+        return (-0.75 * (u * u)) / q;
+        }
     }
 
 // xs: n x 3 compacted positions of element type elem_t; offs: n_cells + 1 CSR offsets; k: the entry, c: its cell id,

@@ -35,7 +35,12 @@
            ``--sph-gradients [H]`` adds the SPH kernel gradients for the smoothing length H (without H: the frame's
            uniform ``slength``): the search grid and the entries, the ranges of the velocity divergence and of the
            density rate of the continuity equation and the largest vorticity and surface normal, each with its row
-           (``--kernel``, ``--types``; ``pgsd.hoomd.frame_kernel_gradients`` on the host: no GPU).
+           (``--kernel``, ``--types``; ``pgsd.hoomd.frame_kernel_gradients`` on the host: no GPU);
+           ``--sph-forces [H]`` adds the SPH accelerations for the smoothing length H (without H: the frame's uniform
+           ``slength``): the search grid and the entries, the largest total, pressure and viscous acceleration, each with
+           its row, the entries whose total is not finite and the force time step ``0.25 sqrt(h / |a|)``
+           (``--viscosity MU``, ``--gravity GX,GY,GZ``, ``--kernel``, ``--types``; ``pgsd.hoomd.frame_accelerations`` on the
+           host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -112,6 +117,34 @@ def _cmd_info(args):
         _print_sph(args, frame)
     if args.sph_gradients is not None:
         _print_sph_gradients(args, frame)
+    if args.sph_forces is not None:
+        _print_sph_forces(args, frame)
+
+
+def _print_sph_forces(args, frame):
+    """``info --sph-forces``: `pgsd.hoomd.frame_accelerations` of one frame, on the host."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    gravity = None
+    if args.gravity is not None:
+        try:
+            gravity = [float(v) for v in args.gravity.split(',')]
+        except ValueError:
+            raise ValueError("--gravity takes GX,GY,GZ: %r" % args.gravity)
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_accelerations(traj[frame], None if args.sph_forces < 0 else args.sph_forces, kernel=args.kernel,
+                                      viscosity=args.viscosity, gravity=gravity, where=where)
+    print("SPH accelerations of frame %d with h = %r (%s) over %d x %d x %d cells%s:"
+          % ((frame, m.h, m.kernel) + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  entries:      %d  nowhere: %d" % (m.n, m.nowhere))
+    print("  viscosity:    %s  gravity: %r %r %r" % (("%r" % m.viscosity if m.viscosity is not None else "none",) + m.gravity))
+    if m.n > m.nowhere:
+        for name, label in (('total', 'total:'), ('pressure', 'pressure:'), ('viscous', 'viscous:')):
+            if getattr(m, name + '2') is not None:
+                print("  %-13s largest %r at row %d" % (label, getattr(m, name + '2') ** 0.5, getattr(m, name + '_row')))
+        print("  not finite:   %d" % m.not_finite)
+        if m.total2 is not None:
+            print("  time step:    %r (0.25 * sqrt(h / largest total))" % m.force_time_step())
 
 
 def _print_sph_gradients(args, frame):
@@ -414,8 +447,15 @@ def main(argv=None):
     p.add_argument('--sph-gradients', type=float, nargs='?', const=-1.0, default=None, metavar='H',
                    help="print the SPH kernel gradients for the smoothing length H (without H: the frame's uniform "
                         "slength): grid, entries, divergence and density-rate ranges, largest vorticity and normal")
+    p.add_argument('--sph-forces', type=float, nargs='?', const=-1.0, default=None, metavar='H',
+                   help="print the SPH accelerations for the smoothing length H (without H: the frame's uniform slength): "
+                        "grid, entries, the largest total, pressure and viscous acceleration and the force time step")
+    p.add_argument('--viscosity', type=float, default=None, metavar='MU',
+                   help="with --sph-forces: the dynamic viscosity of the laminar viscous term (default: no viscous term)")
+    p.add_argument('--gravity', type=str, default=None, metavar='GX,GY,GZ',
+                   help="with --sph-forces: the gravity (default: 0,0,0; write --gravity=-1,0,0 where GX is negative)")
     p.add_argument('--kernel', type=str, default='wendland_c2', choices=('wendland_c2', 'cubic_spline'),
-                   help="the kernel of --sph and --sph-gradients (default: wendland_c2)")
+                   help="the kernel of --sph, --sph-gradients and --sph-forces (default: wendland_c2)")
     p.add_argument('--surface', type=float, default=None, metavar='S',
                    help="with --sph: count the entries whose Shepard sum is below S (the free surface)")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")

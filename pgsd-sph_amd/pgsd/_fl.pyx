@@ -573,6 +573,29 @@ def _sph_defaults(who, defaults, density):
     return c_defaults, density is not None or c_defaults[1] == c_defaults[1]
 
 
+def _force_defaults(who, defaults):
+    """The mass, density and pressure that stand for a chunk stored nowhere as float64[3]; ``None``: the schema's."""
+    c_defaults = numpy.ascontiguousarray(
+        numpy.array([1.0, 0.0, 0.0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+    if c_defaults.shape[0] != 3:
+        raise ValueError("%s: defaults holds a mass, a density and a pressure" % who)
+    return c_defaults
+
+
+def _force_terms(who, viscosity, gravity):
+    """(``mu`` as a float or ``None``, the gravity as float64[3]) of :meth:`PGSDFile.sph_accelerations_device`, checked."""
+    mu = None
+    if viscosity is not None:
+        mu = float(viscosity)
+        if not 0.0 <= mu < float('inf'):
+            raise ValueError("%s: viscosity is a finite number, at least 0, or None: %r" % (who, viscosity))
+    c_gravity = numpy.ascontiguousarray(
+        numpy.array([0.0, 0.0, 0.0] if gravity is None else gravity, dtype=numpy.float64).reshape(-1))
+    if c_gravity.shape[0] != 3 or not numpy.isfinite(c_gravity).all():
+        raise ValueError("%s: gravity holds three finite numbers, or is None" % who)
+    return mu, c_gravity
+
+
 def _moments_defaults(who, defaults):
     """The row that stands for every row of a chunk stored nowhere -- mass, v[3], energy, x[3] -- as float64[8]."""
     c_defaults = numpy.ascontiguousarray(
@@ -2200,6 +2223,75 @@ cdef class PGSDFile:
             if volume:
                 got.divergence = _device_head(out_divergence, count)
                 got.curl, got.normal = _device_head_rows(out_curl, count), _device_head_rows(out_normal, count)
+        return got
+
+    def sph_accelerations_device(self, frame, name, box, h, cells, rows, cell, n=None, velocity=None, mass=None, density=None,
+                                 pressure=None, defaults=None, viscosity=None, gravity=None, dimensions=3,
+                                 kernel='wendland_c2', return_rows=False):
+        """The SPH accelerations of a row list in cell order on the GPU: the pressure acceleration, Morris' laminar viscous
+        acceleration and their sum with gravity over the kernel support ``2h``, in the order that is part of their
+        definition.
+
+        Args:
+            frame, name, box, h, cells, rows, cell, n, velocity, mass, density, dimensions, kernel: as
+                :meth:`sph_gradients_device` takes them.
+            pressure: ``(frame, name)`` of an N x 1 float32 or float64 chunk, or ``None``: stored nowhere.
+            defaults: ``(mass, density, pressure)`` that stand for a chunk stored nowhere; ``None``: 1.0, 0.0 and 0.0, the
+                schema's (the density is a number here: a density of 0 gives what IEEE gives).
+            viscosity (float): the dynamic viscosity ``mu``, finite and at least 0; ``None``: no viscous term.
+            gravity: three finite floats; ``None``: ``(0, 0, 0)``.
+            return_rows (bool): keep the per-entry results in GPU memory.
+
+        Returns:
+            A :class:`pgsd.hoomd.KernelAccelerations`: exactly :func:`pgsd.hoomd.sph_accelerations` of the same list --
+            every counter and index, every float bit for bit.  With ``return_rows`` its ``rows`` and ``cell`` are the
+            arguments and ``pressure_acc``, ``viscous_acc`` (``None`` without a viscosity) and ``total`` are float64
+            arrays of ``n x 3`` in GPU memory; otherwise the five are ``None``.  The chunks are staged whole unless an
+            earlier call left them staged; the staged rows are kept until the next :meth:`wait_read`.  What the library
+            refuses (:c:func:`pgsd_sph_accelerations_device`) raises ValueError and computes nothing.  Needs no tensor
+            library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry, e_velocity, e_mass, e_density, e_pressure
+        self._entry(frame, name, &entry)
+        cdef const C.pgsd_index_entry* p_velocity = self._optional(velocity, &e_velocity)
+        cdef const C.pgsd_index_entry* p_mass = self._optional(mass, &e_mass)
+        cdef const C.pgsd_index_entry* p_density = self._optional(density, &e_density)
+        cdef const C.pgsd_index_entry* p_pressure = self._optional(pressure, &e_pressure)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("sph_accelerations_device", cells)
+        cdef uint32_t c_kernel = _sph_kernel("sph_accelerations_device", kernel)
+        c_defaults = _force_defaults("sph_accelerations_device", defaults)
+        mu, c_gravity = _force_terms("sph_accelerations_device", viscosity, gravity)
+        c_rows, c_cell, count = _cell_ordered_lists("sph_accelerations_device", rows, cell, n)
+        summary = numpy.zeros(12, dtype=numpy.uint64)
+        cdef uintptr_t p_pacc, p_vacc, p_total
+        device = self.pipeline_device() if return_rows else None
+        out_pacc, p_pacc = _per_entry(count, (3,), numpy.float64, device)
+        out_vacc, p_vacc = _per_entry(count, (3,), numpy.float64, device if mu is not None else None)
+        out_total, p_total = _per_entry(count, (3,), numpy.float64, device)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data, p_gravity = c_gravity.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef double c_h = float(h), c_mu = -1.0 if mu is None else mu
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_sph_accelerations_device(&self._handle, &entry, p_velocity, p_mass, p_density, p_pressure,
+                                                     <const double*>p_defaults, <const double*>p_vectors, c_h, c_kernel,
+                                                     c_dims, <const uint32_t*>p_cells, c_mu, <const double*>p_gravity,
+                                                     <const uint32_t*>p_rows, <const int32_t*>p_cell, c_n, <double*>p_pacc,
+                                                     <double*>p_vacc, <double*>p_total, <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("sph_accelerations_device", retval, "refused", self._name, err)
+        got = _hoomd.KernelAccelerations(c_h, kernel, grid, int(dimensions), summary, mu, tuple(c_gravity.tolist()))
+        if return_rows:
+            got.rows, got.cell = _device_head(rows, count), _device_head(cell, count)
+            got.pressure_acc, got.total = _device_head_rows(out_pacc, count), _device_head_rows(out_total, count)
+            if mu is not None:
+                got.viscous_acc = _device_head_rows(out_vacc, count)
         return got
 
     def frame_displacements_device(self, chunks, vectors_a, vectors_b, minimum_image=False, dimensions=3, type0=0,

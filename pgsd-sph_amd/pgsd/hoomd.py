@@ -2485,6 +2485,203 @@ def frame_kernel_gradients(frame_or_arrays, h=None, kernel='wendland_c2', cells=
                                 density=arrays.get('density'), rows=rows, cells=cells, dimensions=dimensions, kernel=kernel)
 
 
+# ---- SPH accelerations: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_accelerations_device`) equals exactly
+_SPHF_SUMMARY_WORDS = 12    # n, nowhere, not_finite, 3 x (at, row) of total, pressure, viscous, then total2, pressure2, viscous2
+_SPHF_NORMS = ('total', 'pressure', 'viscous')
+
+
+def _sph_viscosity(viscosity):
+    """``mu`` as a float, finite and at least 0, or ``None``: no viscous term."""
+    if viscosity is None:
+        return None
+    mu = float(viscosity)
+    if not 0.0 <= mu < numpy.inf:
+        raise ValueError("viscosity is a finite number, at least 0, or None: %r" % (viscosity,))
+    return mu
+
+
+def _sph_gravity(gravity):
+    """``g`` as three finite floats; ``None``: ``(0.0, 0.0, 0.0)``."""
+    g = numpy.array([0.0, 0.0, 0.0] if gravity is None else gravity, dtype=numpy.float64).reshape(-1)
+    if g.shape[0] != 3 or not numpy.isfinite(g).all():
+        raise ValueError("gravity holds three finite numbers, or is None")
+    return tuple(float(c) for c in g)
+
+
+class KernelAccelerations(object):
+    """The SPH accelerations of a list in cell order (`sph_accelerations`).
+
+    Attributes:
+        h (float), kernel (str), grid (``(cx, cy, cz)``), dimensions (int), viscosity (float or ``None``), gravity (three
+            floats): what was asked; G (float): `sph_gradient_scale`.
+        rows, cell: the list in cell order and its cell ids (``n_cells``: nowhere).
+        pressure_acc, viscous_acc, total (float64, ``n x 3``): per entry, in list order, ``-sum_j m_j (p_i/rho_i^2 +
+            p_j/rho_j^2) grad_i W_ij``, Morris' laminar viscous acceleration and ``(pressure_acc + viscous_acc) + g``
+            over the entries inside ``2h``; ``+0.0`` for an entry nowhere.  ``viscous_acc`` is ``None`` without a
+            viscosity.  The three are numpy arrays from the model; from the GPU they are ``None`` unless ``return_rows``
+            left them in GPU memory.
+        n, nowhere (int): the entries, and those without a cell.
+        not_finite (int): the entries that have a cell and whose ``total`` has a component that is NaN or infinite.
+        total2, total_at, total_row, pressure2, pressure_at, pressure_row, viscous2, viscous_at, viscous_row: the largest
+            ``(a0*a0 + a1*a1) + a2*a2`` of the ``total``, ``pressure_acc`` and ``viscous_acc`` outputs over the entries
+            that have a cell, its list position (the smaller one on a tie, a NaN never counts) and its row; ``None``
+            where no entry has a number for it (the last three always without a viscosity).
+    """
+
+    __slots__ = ('h', 'kernel', 'grid', 'dimensions', 'viscosity', 'gravity', 'G', 'rows', 'cell', 'pressure_acc', 'viscous_acc',
+                 'total', 'n', 'nowhere', 'not_finite', 'total2', 'total_at', 'total_row', 'pressure2', 'pressure_at',
+                 'pressure_row', 'viscous2', 'viscous_at', 'viscous_row', '_words')
+
+    def __init__(self, h, kernel, grid, dimensions, summary, viscosity=None, gravity=None, rows=None, cell=None,
+                 pressure_acc=None, viscous_acc=None, total=None):
+        """``summary``: the 12 uint64 words of `pgsd_sph_accelerations_device` -- n, nowhere, not_finite, the list
+        position and the row of the largest total, pressure and viscous acceleration, then as float64 bit patterns the
+        three largest squared norms."""
+        s = numpy.ascontiguousarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _SPHF_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _SPHF_SUMMARY_WORDS)
+        self._words = s.copy()
+        self.h, self.kernel, self.dimensions = float(h), kernel, int(dimensions)
+        self.viscosity, self.gravity = _sph_viscosity(viscosity), _sph_gravity(gravity)
+        self.G = sph_gradient_scale(kernel, h, dimensions)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.n, self.nowhere, self.not_finite = int(s[0]), int(s[1]), int(s[2])
+        f = s[9:12].view(numpy.float64)
+        for k, name in enumerate(_SPHF_NORMS):
+            found = int(s[3 + 2 * k]) != _NEIGHBOURS_NONE and (name != 'viscous' or self.viscosity is not None)
+            setattr(self, name + '2', float(f[k]) if found else None)
+            setattr(self, name + '_at', int(s[3 + 2 * k]) if found else None)
+            setattr(self, name + '_row', int(s[4 + 2 * k]) if found else None)
+        self.rows, self.cell = rows, cell
+        self.pressure_acc, self.viscous_acc, self.total = pressure_acc, viscous_acc, total
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return self._words.copy()
+
+    def force_time_step(self, factor=0.25):
+        """``factor * sqrt(h / sqrt(total2))``, the time step the largest acceleration allows; computed on the host from
+        the summary; ``None`` without a ``total2`` (``inf`` where it is 0)."""
+        if self.total2 is None:
+            return None
+        with numpy.errstate(divide='ignore'):
+            return float(numpy.float64(factor) * numpy.sqrt(numpy.float64(self.h) / numpy.sqrt(numpy.float64(self.total2))))
+
+    def __repr__(self):
+        return "KernelAccelerations(h=%r, kernel=%r, grid=%r, n=%d, nowhere=%d, not_finite=%d, total2=%r, pressure2=%r, " \
+            "viscous2=%r)" % (self.h, self.kernel, self.grid, self.n, self.nowhere, self.not_finite, self.total2,
+                              self.pressure2, self.viscous2)
+
+
+def _sphf_summary(n, somewhere, rows_sorted, total, pressure_acc, viscous_acc):
+    """The summary words from the per-entry results (``viscous_acc`` None without a viscosity): no float is summed over
+    the list, so no order enters."""
+    words = numpy.zeros(_SPHF_SUMMARY_WORDS, dtype=numpy.uint64)
+    f = words[9:12].view(numpy.float64)
+    words[0], words[1] = n, n - somewhere
+    words[3:9] = _NEIGHBOURS_NONE
+    if not somewhere:
+        return words
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        words[2] = int(numpy.count_nonzero(~numpy.isfinite(total[:somewhere]).all(axis=1)))
+        for k, v in enumerate((total, pressure_acc, viscous_acc)):
+            if v is None:
+                continue
+            v = v[:somewhere]
+            norm2 = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+            size = numpy.where(norm2 == norm2, norm2, -1.0)
+            at = int(numpy.argmax(size))                # (the first position that attains the maximum)
+            if size[at] >= 0.0:
+                words[3 + 2 * k], words[4 + 2 * k], f[k] = at, rows_sorted[at], norm2[at]
+    return words
+
+
+def sph_accelerations(position, velocity, box, h, mass=None, density=None, pressure=None, viscosity=None, gravity=None,
+                      rows=None, cells=None, dimensions=3, kernel='wendland_c2'):
+    """The SPH accelerations of a row list, the right-hand side of the momentum equation: per entry ``i`` the pressure
+    acceleration ``-sum_j m_j (p_i/rho_i^2 + p_j/rho_j^2) grad_i W_ij``, Morris' laminar viscous acceleration for one
+    constant ``mu``, ``(1/rho_i) sum_j V_j 2 mu (v_i - v_j) (d . grad_i W_ij) / (|d|^2 + eta^2)``, and their sum with
+    gravity over the entries ``j`` inside the kernel support ``2h``, and over the list the largest of the three with
+    their rows -- is the frame in equilibrium, where is the largest acceleration, what time step does it allow.  The
+    definition the GPU pass (`pgsd.fl.PGSDFile.sph_accelerations_device`, `HOOMDTrajectory.frame_accelerations_device`)
+    equals exactly, the floats bit for bit.
+
+    Args:
+        position, velocity, box, h, mass, rows, cells, dimensions, kernel: `sph_kernel_gradients`'.  The grid, the support
+            ``2h``, ``r2``, ``inv_h``, ``sigma``, ``G``, the list in cell order, THE ORDER of the candidates and every
+            refusal are its own.
+        density, pressure: ``N`` float32 or float64 values, or ``None``: the schema's default, 0.0 in every row (the values
+            that result may be infinite or NaN: that is defined behaviour).
+        viscosity (float): the dynamic viscosity ``mu``, finite and at least 0; ``None``: no viscous term is formed and
+            ``viscous_acc`` is ``None``.
+        gravity: three finite floats; ``None``: ``(0, 0, 0)`` (the addition of ``+0.0`` is still performed).
+
+    **Per entry**, float64, once, before the pair loop: ``A_k = p_k / (rho_k * rho_k)``, ``V_k = m_k / rho_k``.  On the
+    host, once: ``eta2 = (0.01*h)*h`` and ``Gv = G * (2.0*mu)``.
+
+    **One pair**, float64 throughout without contraction, float32 inputs converted exactly before any subtraction: ``d``,
+    ``d2``, the strict test ``d2 < r2``, ``rr``, ``q`` and ``F`` as in `sph_kernel_gradients`; ``i`` itself and coincident
+    entries are candidates like any other (their ``e`` is zero, so an infinite ``S`` gives a NaN there); ``e_k = F *
+    d_k``, ``S = A_i + A_j``, ``a_p[k] += m_j * (S * e_k)``; with a viscosity ``K = (F * d2) / (d2 + eta2)``, ``u_k =
+    v_j[k] - v_i[k]``, ``a_v[k] += V_j * (K * u_k)``.  After the last candidate ``pressure_acc[k] = -(G * a_p[k])``,
+    ``viscous_acc[k] = (Gv * a_v[k]) / rho_i`` and ``total[k] = (pressure_acc[k] + viscous_acc[k]) + g[k]``, or
+    ``pressure_acc[k] + g[k]`` without a viscosity.  In 2-D ``d_z`` is 0 and nothing else is special-cased.  An entry
+    without a cell contributes to nobody and all its values are ``+0.0``.
+
+    Returns a `KernelAccelerations`.
+    """
+    asked = _sph_asked(box, h, cells, dimensions, kernel)
+    mu, g = _sph_viscosity(viscosity), _sph_gravity(gravity)
+    t = _sph_list(asked, position, box, rows, (('mass', mass, 1), ('density', density, 1), ('velocity', velocity, 3),
+                                               ('pressure', pressure, 1)))
+    dimensions, h, kid, grid = asked[0], asked[1], asked[2], asked[4]
+    n, somewhere = t.n, t.somewhere
+    mass, rho, v, p = t.columns
+    m = numpy.ones(n, dtype=numpy.float64) if mass is None else mass
+    rho = numpy.zeros(n, dtype=numpy.float64) if rho is None else rho
+    p = numpy.zeros(n, dtype=numpy.float64) if p is None else p
+    v = numpy.zeros((n, 3), dtype=numpy.float64) if v is None else v
+    G = numpy.float64(-((t.sigma * t.inv_h) * t.inv_h))
+    eta2 = (numpy.float64(0.01) * numpy.float64(h)) * numpy.float64(h)
+    Gv = None if mu is None else G * (numpy.float64(2.0) * numpy.float64(mu))
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        A, V = p / (rho * rho), m / rho
+    a_p = [numpy.zeros(n, dtype=numpy.float64) for _ in range(3)]
+    a_v = None if mu is None else [numpy.zeros(n, dtype=numpy.float64) for _ in range(3)]
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        for i, j, d, d2 in _sph_near_pairs(t):
+            F = sph_gradient_factor(numpy.sqrt(d2) * t.inv_h, kernel)
+            S, mj = A[i] + A[j], m[j]
+            for k in range(3):
+                numpy.add.at(a_p[k], i, mj * (S * (F * d[k])))
+            if a_v is not None:
+                K, Vj = (F * d2) / (d2 + eta2), V[j]
+                for k in range(3):
+                    numpy.add.at(a_v[k], i, Vj * (K * (v[j, k] - v[i, k])))
+        pressure_acc = numpy.stack([-(G * a) for a in a_p], axis=1)
+        viscous_acc = None if a_v is None else numpy.stack([(Gv * a) / rho for a in a_v], axis=1)
+        total = (pressure_acc if viscous_acc is None else pressure_acc + viscous_acc) + numpy.array(g, dtype=numpy.float64)
+    for a in (pressure_acc, viscous_acc, total):
+        if a is not None:
+            a[somewhere:] = 0.0
+    words = _sphf_summary(n, somewhere, t.rows_sorted, total, pressure_acc, viscous_acc)
+    return KernelAccelerations(h, SPH_KERNELS[kid], grid, dimensions, words, mu, g, t.rows_sorted, t.cell_sorted, pressure_acc,
+                               viscous_acc, total)
+
+
+def frame_accelerations(frame_or_arrays, h=None, kernel='wendland_c2', viscosity=None, gravity=None, cells=None, where=None,
+                        types=None, domain=None, box=None, dimensions=3):
+    """`sph_accelerations` of a frame's ``position``, ``velocity``, ``mass``, ``density`` and ``pressure`` over a selection:
+    the host twin of `HOOMDTrajectory.frame_accelerations_device`, which equals it exactly.  The selection, the ``h=None``
+    rule and the refusals are `frame_kernel_sums`'; a velocity that is stored nowhere is the zero vector, a mass 1.0, a
+    density and a pressure the schema's 0.0.  Returns a `KernelAccelerations`."""
+    arrays, position, box, dimensions, h, rows = _sph_frame_list(frame_or_arrays, h, where, types, domain, box, dimensions)
+    return sph_accelerations(position, arrays.get('velocity'), box, h, mass=arrays.get('mass'), density=arrays.get('density'),
+                             pressure=arrays.get('pressure'), viscosity=viscosity, gravity=gravity, rows=rows, cells=cells,
+                             dimensions=dimensions, kernel=kernel)
+
+
 def frame_moments(frame_or_arrays, by_type=True, centre=True, where=None, types=None, domain=None, box=None, dimensions=3):
     """`particle_moments` of a frame's ``mass``, ``velocity``, ``energy``, ``position`` and ``typeid`` over a selection:
     the host twin of `HOOMDTrajectory.frame_moments_device`, which equals it exactly.
@@ -4514,7 +4711,8 @@ class HOOMDTrajectory(object):
         return got
 
     def _sph_device_list(self, who, idx, h, kernel, cells, where, domain, names):
-        """What `frame_kernel_sums_device` and `frame_kernel_gradients_device` share ahead of their pass: the ``h=None``
+        """What `frame_kernel_sums_device`, `frame_kernel_gradients_device` and `frame_accelerations_device` share ahead of
+        their pass: the ``h=None``
         rule, the grid for the support ``2h``, the selection as a row list sorted by cell on the GPU and, for each of
         ``names``, the effective chunk ``(frame, name)`` or ``None``.  ``(f_pos, box, dims, h, grid, rows, cell, count,
         chunks, [mass default, density default])``; the caller ends with `wait_read`, whatever is raised here."""
@@ -4569,6 +4767,39 @@ class HOOMDTrajectory(object):
             got = f.sph_gradients_device(f_pos, 'particles/position', box, h, grid, rows, cell, n=count, velocity=chunks[2],
                                          mass=chunks[0], density=chunks[1], defaults=defaults, dimensions=dims, kernel=kernel,
                                          return_rows=return_rows)
+        finally:
+            f.wait_read()
+        return got
+
+    def frame_accelerations(self, idx, h=None, kernel='wendland_c2', viscosity=None, gravity=None, cells=None, where=None,
+                            domain=None):
+        """`frame_accelerations` of frame ``idx`` read through the host path: a `KernelAccelerations`.  The definition of
+        `frame_accelerations_device`."""
+        return frame_accelerations(self[int(idx)], h, kernel=kernel, viscosity=viscosity, gravity=gravity, cells=cells,
+                                   where=where, domain=domain)
+
+    def frame_accelerations_device(self, idx, h=None, kernel='wendland_c2', viscosity=None, gravity=None, cells=None,
+                                   where=None, domain=None, return_rows=False):
+        """`frame_accelerations` of frame ``idx``, on the GPU: a `KernelAccelerations` that equals
+        ``frame_accelerations(idx, h, ...)`` exactly -- every counter and index, every float bit for bit.
+
+        ``h=None``, the selection, the grid and the ordering are `frame_kernel_sums_device`'s; the pass
+        (`pgsd.fl.PGSDFile.sph_accelerations_device`) runs over the staged position chunk and the effective ``velocity``,
+        ``mass``, ``density`` and ``pressure`` chunks; one that is stored nowhere costs nothing: the zero vector and the
+        schema defaults 1.0, 0.0 and 0.0 stand for every row.  ``return_rows=True`` leaves ``rows``, ``cell``,
+        ``pressure_acc``, ``viscous_acc`` and ``total`` in GPU memory on the result; otherwise they are ``None`` and no
+        per-particle data is kept.  One `wait_read` at the end releases the staged chunks.  A frame whose position is
+        stored nowhere has no chunk to search and raises ValueError.
+        """
+        f = self.file
+        try:
+            mu, g = _sph_viscosity(viscosity), _sph_gravity(gravity)
+            f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults = self._sph_device_list(
+                "frame_accelerations_device", idx, h, kernel, cells, where, domain, ('mass', 'density', 'velocity', 'pressure'))
+            got = f.sph_accelerations_device(f_pos, 'particles/position', box, h, grid, rows, cell, n=count, velocity=chunks[2],
+                                             mass=chunks[0], density=chunks[1], pressure=chunks[3],
+                                             defaults=defaults + [float(_PARTICLE_FIELDS['pressure'][2])], viscosity=mu,
+                                             gravity=g, dimensions=dims, kernel=kernel, return_rows=return_rows)
         finally:
             f.wait_read()
         return got

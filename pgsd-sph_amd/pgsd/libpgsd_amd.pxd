@@ -261,6 +261,13 @@ cdef extern from "pgsd_private.h" nogil:
                                   const uint32_t* cells, const uint32_t* rows, const int32_t* cell, uint64_t n,
                                   double* out_density_rate, double* out_divergence, double* out_curl, double* out_normal,
                                   uint64_t* out_summary)
+    int pgsd_sph_accelerations_device(pgsd_handle* handle, const pgsd_index_entry* position,
+                                      const pgsd_index_entry* velocity, const pgsd_index_entry* mass,
+                                      const pgsd_index_entry* density, const pgsd_index_entry* pressure,
+                                      const double* defaults, const double* vectors, double h, uint32_t kernel,
+                                      uint32_t dimensions, const uint32_t* cells, double viscosity, const double* gravity,
+                                      const uint32_t* rows, const int32_t* cell, uint64_t n, double* out_pressure_acc,
+                                      double* out_viscous_acc, double* out_total, uint64_t* out_summary)
     int pgsd_chunk_stats_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                                 uint32_t with_norm2, uint64_t* out_counts, double* out_values)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,

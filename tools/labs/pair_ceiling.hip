@@ -22,8 +22,15 @@
 // inv_h, the factor F(q) (the spline's outer branch divides), e = F * d, u = v_j - v_i, the dot, the cross product and
 // the eight accumulations, m_j, V_j and v_j formed in registers.  The candidates are the `sph` variant's.
 //
+// Variant `sph_force` ("SPH accelerations"): the per-candidate work of sphf_pair_kernel<*, KERNEL, true>
+// on register values -- the same differences, fold, d2 and strict compare, and under the compare rr = sqrt(d2), q = rr *
+// inv_h, the factor F(q), e = F * d, S = A_i + A_j, the three accumulations a_p[k] += m_j * (S * e_k), and the viscous
+// term's division K = (F * d2) / (d2 + eta2), u = v_j - v_i and a_v[k] += V_j * (K * u_k); m_j, A_j, V_j and v_j formed
+// in registers.  The candidates are the `sph` variant's.
+//
 //   hipcc -O3 --offload-arch=gfx950 tools/labs/pair_ceiling.hip -o pair_ceiling
-//   ./pair_ceiling [reps=20] [iter=4096] [variant=census|sph_wendland|sph_spline|sph_grad_wendland|sph_grad_spline]
+//   ./pair_ceiling [reps=20] [iter=4096]
+//       [variant=census|sph_wendland|sph_spline|sph_grad_wendland|sph_grad_spline|sph_force_wendland|sph_force_spline]
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -263,7 +270,89 @@ __global__ __launch_bounds__(256) void sph_grad_ceiling_kernel(const Box b, doub
     o[7] = a_c2;
     }
 
-// kernel: 0 sph_wendland, 1 sph_spline, 2 sph_grad_wendland, 3 sph_grad_spline
+template<int KERNEL>
+__global__ __launch_bounds__(256) void sph_force_ceiling_kernel(const Box b, double inv_h, uint32_t iter, uint32_t* __restrict__ out_count,
+                                                                double* __restrict__ out_sums)
+    {
+#pragma clang fp contract(off)
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    const double Lx = b.v[0], Ly = b.v[1], Lz = b.v[2], xyLy = b.v[3], xzLz = b.v[4], yzLz = b.v[5];
+    const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5, r2 = b.r2;
+    const double xi0 = -hx + (double)(k & 1023) * (Lx / 1024.0), xi1 = -hy + (double)((k >> 10) & 1023) * (Ly / 1024.0);
+    const double xi2 = -hz + (double)(k >> 20) * (Lz / 4096.0);
+    const double vi0 = (double)(k & 15) * 0.125, vi1 = -(double)(k & 7) * 0.25, vi2 = 0.5;
+    const double Ai = 0.1 + (double)(k & 31) * 0.001, eta2 = (0.01 / inv_h) / inv_h;
+    double s0 = Lx / 977.0 + (double)(k & 63) * 1e-3, s1 = -Ly / 1931.0, s2 = Lz / 2953.0;
+    double xj0 = xi0, xj1 = xi1, xj2 = xi2;
+    const uint32_t phase = (k & 63) * 8; // the lane's own turning step
+    uint32_t count = 0;
+    double a_p0 = 0.0, a_p1 = 0.0, a_p2 = 0.0, a_v0 = 0.0, a_v1 = 0.0, a_v2 = 0.0;
+    for (uint32_t j = 0; j < iter; j++)
+        {
+        const bool turn = ((j + phase) & 511) == 511;
+        s0 = turn ? -s0 : s0;
+        s1 = turn ? -s1 : s1;
+        s2 = turn ? -s2 : s2;
+        xj0 = xj0 + s0;
+        xj1 = xj1 + s1;
+        xj2 = xj2 + s2;
+        double dx = xj0 - xi0, dy = xj1 - xi1, dz = xj2 - xi2;
+            {
+            const bool up = dz >= hz, down = dz < -hz;
+            dx = up ? dx - xzLz : (down ? dx + xzLz : dx);
+            dy = up ? dy - yzLz : (down ? dy + yzLz : dy);
+            dz = up ? dz - Lz : (down ? dz + Lz : dz);
+            }
+            {
+            const bool up = dy >= hy, down = dy < -hy;
+            dx = up ? dx - xyLy : (down ? dx + xyLy : dx);
+            dy = up ? dy - Ly : (down ? dy + Ly : dy);
+            }
+            {
+            const bool up = dx >= hx, down = dx < -hx;
+            dx = up ? dx - Lx : (down ? dx + Lx : dx);
+            }
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 < r2)
+            {
+            const double rr = __builtin_sqrt(d2);
+            const double q = rr * inv_h;
+            double F;
+            if constexpr (KERNEL == 0)
+                {
+                const double t = 1.0 - 0.5 * q;
+                F = -5.0 * ((t * t) * t);
+                }
+            else
+                {
+                const double u = 2.0 - q;
+                F = q < 1.0 ? 2.25 * q - 3.0 : (-0.75 * (u * u)) / q;
+                }
+            const double mj = 1.0 + (double)(j & 7u), vj = mj * 0.5, Aj = 0.1 + (double)(j & 15u) * 0.002;
+            const double e0 = F * dx, e1 = F * dy, e2 = F * dz;
+            const double S = Ai + Aj;
+            a_p0 = a_p0 + mj * (S * e0);
+            a_p1 = a_p1 + mj * (S * e1);
+            a_p2 = a_p2 + mj * (S * e2);
+            const double K = (F * d2) / (d2 + eta2);
+            const double u0 = (double)(j & 3u) - vi0, u1 = (double)(j & 5u) - vi1, u2 = (double)(j & 9u) - vi2;
+            a_v0 = a_v0 + vj * (K * u0);
+            a_v1 = a_v1 + vj * (K * u1);
+            a_v2 = a_v2 + vj * (K * u2);
+            count++;
+            }
+        }
+    out_count[k] = count;
+    double* o = out_sums + (size_t)k * 8;
+    o[0] = a_p0;
+    o[1] = a_p1;
+    o[2] = a_p2;
+    o[3] = a_v0;
+    o[4] = a_v1;
+    o[5] = a_v2;
+    }
+
+// kernel: 0 sph_wendland, 1 sph_spline, 2 sph_grad_wendland, 3 sph_grad_spline, 4 sph_force_wendland, 5 sph_force_spline
 static int run_sph(int reps, uint32_t iter, int kernel)
     {
     int cus = 256;
@@ -273,7 +362,7 @@ static int run_sph(int reps, uint32_t iter, int kernel)
     uint32_t* count;
     double* sums;
     CK(hipMalloc(&count, lanes * sizeof(uint32_t)));
-    CK(hipMalloc(&sums, lanes * 8 * sizeof(double))); // (three per lane for the sums, eight for the gradients)
+    CK(hipMalloc(&sums, lanes * 8 * sizeof(double))); // (three per lane for the sums, eight for the gradients, six for the forces)
     const Box b = {{40.0, 40.0, 40.0, 0.25 * 40.0, 0.125 * 40.0, -0.0625 * 40.0}, 0.197 * 0.197};
     const double inv_h = 1.0 / (0.197 / 2);
     hipEvent_t t0, t1;
@@ -288,8 +377,12 @@ static int run_sph(int reps, uint32_t iter, int kernel)
             hipExtLaunchKernelGGL(sph_ceiling_kernel<1>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
         else if (kernel == 2)
             hipExtLaunchKernelGGL(sph_grad_ceiling_kernel<0>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
-        else
+        else if (kernel == 3)
             hipExtLaunchKernelGGL(sph_grad_ceiling_kernel<1>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
+        else if (kernel == 4)
+            hipExtLaunchKernelGGL(sph_force_ceiling_kernel<0>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
+        else
+            hipExtLaunchKernelGGL(sph_force_ceiling_kernel<1>, dim3(blocks), dim3(256), 0, 0, t0, t1, 0, b, inv_h, iter, count, sums);
         CK(hipGetLastError());
         CK(hipEventSynchronize(t1));
         float t = 0;
@@ -304,7 +397,8 @@ static int run_sph(int reps, uint32_t iter, int kernel)
         near += c;
     std::sort(ms.begin(), ms.end());
     const double pairs = (double)lanes * iter;
-    static const char* variants[4] = {"sph_wendland", "sph_spline", "sph_grad_wendland", "sph_grad_spline"};
+    static const char* variants[6] = {"sph_wendland",      "sph_spline",         "sph_grad_wendland",
+                                      "sph_grad_spline",   "sph_force_wendland", "sph_force_spline"};
     printf("{\"kind\": \"pair_ceiling\", \"variant\": \"%s\", \"lanes\": %zu, \"iter\": %u, \"pairs\": %.0f, \"near\": %llu, "
            "\"best_ms\": %.4f, \"median_ms\": %.4f, \"worst_ms\": %.4f, \"pairs_per_s_best\": %.4g, \"pairs_per_s_median\": %.4g}\n",
            variants[kernel], lanes, iter, pairs, (unsigned long long)near, ms.front(),
@@ -321,7 +415,13 @@ int main(int argc, char** argv)
     if (argc > 3 && std::string(argv[3]) != "census")
         {
         const std::string v = argv[3];
-        return run_sph(reps, iter, v == "sph_spline" ? 1 : (v == "sph_grad_wendland" ? 2 : (v == "sph_grad_spline" ? 3 : 0)));
+        static const char* names[6] = {"sph_wendland",    "sph_spline",         "sph_grad_wendland",
+                                       "sph_grad_spline", "sph_force_wendland", "sph_force_spline"};
+        int kernel = 0;
+        for (int i = 0; i < 6; i++)
+            if (v == names[i])
+                kernel = i;
+        return run_sph(reps, iter, kernel);
         }
     int cus = 256;
     CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
