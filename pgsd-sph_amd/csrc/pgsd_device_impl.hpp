@@ -239,10 +239,11 @@ class DevicePipeline
     void fill_across_launches(std::vector<std::shared_ptr<ReadReq>>& pending);
     const void* kept_chunk(long long file_offset, size_t bytes) const;
     int stage_chunks(const ChunkRange* ranges, size_t n, uint64_t N, const void** src);
-    // the most chunks one pass stages: the larger of what a predicate and a grouped reduction take
+    // the most chunks one pass stages: the largest of what a predicate, a grouped reduction and the SPH samples take
     enum
         {
-        STAGED_MAX_CHUNKS = (WHERE_MAX_TERMS + 1 > GROUPED_CHUNKS ? WHERE_MAX_TERMS + 1 : GROUPED_CHUNKS)
+        STAGED_GROUPED_CHUNKS = (WHERE_MAX_TERMS + 1 > GROUPED_CHUNKS ? WHERE_MAX_TERMS + 1 : GROUPED_CHUNKS),
+        STAGED_MAX_CHUNKS = (STAGED_GROUPED_CHUNKS > SPHS_CHUNKS ? STAGED_GROUPED_CHUNKS : SPHS_CHUNKS)
         };
     int stage_present(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N);
 

@@ -449,7 +449,7 @@ int DevicePipeline::stage_present(const ChunkRange* ranges, const void** const* 
 // wait_read for an indexed read of the same chunk --; where the pass writes or reads memory of the caller's on the device
 // (`callers_memory`: a row list, shifts), what the caller's stream still does with that memory comes first;
 // `launch(stream, why)` launches on the pack stream, synchronises it and returns a pgsd_error; a PGSD_ERROR_DEVICE fails
-// the pipeline with the launcher's message.  The message of a failure, for all seventeen passes: the launcher's own first,
+// the pipeline with the launcher's message.  The message of a failure, for all eighteen passes: the launcher's own first,
 // else the pipeline's, else the thread's last error.
 template<class Launch>
 int DevicePipeline::staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N,
@@ -643,6 +643,21 @@ int device_pipeline_sph_accelerations(DevicePipeline* p, const ChunkRange* range
     return p->staged_launch(ranges, slots, 5, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
                             { return launch_sph_accelerations(a, out_pressure_acc, out_viscous_acc, out_total, out_summary,
                                                               stream, why); });
+    }
+
+// SPH samples: the position, mass and density chunks as the sums take them and up to four value chunks where they are
+// stored; the lists, the points and the per-point outputs are the caller's.  No entry: nothing to stage, as the cell offsets.
+int device_pipeline_sph_samples(DevicePipeline* p, const ChunkRange* ranges, const SphSamplesArgs& args, uint32_t* out_count,
+                                double* out_density, double* out_shepard, double* out_values, uint64_t* out_summary,
+                                std::string* err)
+    {
+    SphSamplesArgs a = args;
+    const auto launch = [&](hipStream_t stream, std::string* why)
+    { return launch_sph_samples(a, out_count, out_density, out_shepard, out_values, out_summary, stream, why); };
+    if (a.n == 0)
+        return p->staged_launch(nullptr, nullptr, 0, 0u, 0, true, err, launch);
+    const void** const slots[SPHS_CHUNKS] = {&a.pos, &a.mass, &a.density, &a.value[0], &a.value[1], &a.value[2], &a.value[3]};
+    return p->staged_launch(ranges, slots, SPHS_CHUNKS, a.present | 1u, a.N, true, err, launch);
     }
 
 // Neighbour lists: the census's staging for both calls (the fill finds the chunk the offsets call left staged); the lists,

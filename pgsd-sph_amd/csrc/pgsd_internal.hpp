@@ -591,6 +591,52 @@ inline void sph_forces_of_nothing(uint64_t* out_summary)
 int device_pipeline_sph_accelerations(DevicePipeline*, const ChunkRange* ranges, const SphForcesArgs& a,
                                       double* out_pressure_acc, double* out_viscous_acc, double* out_total,
                                       uint64_t* out_summary, std::string* err);
+// SPH samples (pgsd.hoomd.sph_samples is the definition): per point of the caller's choosing the entries of a row list in
+// cell order strictly inside the support 2h of it, the density sigma * sum m_j w, the Shepard sum sigma * sum V_j w and per
+// value column sigma * sum V_j w f_j (or, normalised, sum V_j w f_j / sum V_j w), in the sums' order around the point's
+// cell, and over the points how many are nowhere, outside the box, empty or not finite, the largest count and the ranges
+// of the two sums.  The grid, the support, the list and the mass and density defaults are SphArgs' (volume, surface and
+// surface_below are not looked at: the density default is a number here).
+enum
+    {
+    SPHS_SUMMARY_WORDS = 11, // K, nowhere, outside, empty, not_finite, count_max, count_max_at, shepard min, max, density min, max
+    SPHS_MAX_VALUES = 4,     // value chunks of one call
+    SPHS_MAX_WIDTH = 4,      // columns of one value chunk
+    SPHS_MAX_COLUMNS = 8,    // columns of all of them together
+    SPHS_CHUNKS = 3 + SPHS_MAX_VALUES // position, mass, density, then the values
+    };
+struct SphSamplesArgs : SphArgs
+    {
+    const void* value[SPHS_MAX_VALUES];      // the staged value chunks, N x value_columns[s], or null: the default stands
+    double value_default[SPHS_MAX_VALUES];   // ... for every element of the slot
+    uint32_t value_columns[SPHS_MAX_VALUES]; // 0: the slot is unused (the used slots come first)
+    uint32_t value_f64[SPHS_MAX_VALUES];     // present bit 3 + s: value chunk s is stored (ranges[3 + s])
+    DomainArgs d;                            // the box as the cell order's key kernel takes it (L, xy, xz, yz, dims)
+    const double* points;                    // device, K x 3
+    uint64_t K;
+    uint32_t C;                              // the columns together
+    uint32_t normalise;
+    };
+// the summary of no point
+inline void sph_samples_of_nothing(uint64_t* out_summary)
+    {
+    const double lo = HUGE_VAL, hi = -HUGE_VAL;
+    std::fill(out_summary, out_summary + SPHS_SUMMARY_WORDS, (uint64_t)0);
+    out_summary[6] = SPH_NONE;
+    for (int s = 0; s < 2; s++)
+        {
+        memcpy(&out_summary[7 + 2 * s], &lo, sizeof(double));
+        memcpy(&out_summary[8 + 2 * s], &hi, sizeof(double));
+        }
+    }
+// stage the chunks that are present (ranges[0 .. 6]: position, mass, density, the values; the pointers are filled in) --
+// or take them from what an earlier call left staged; a list of no entry stages nothing --, check the lists, sample on the
+// GPU; out_count (device, a.K), out_density, out_shepard (device, a.K), out_values (device, a.K x a.C), each or null;
+// out_summary (host, 11 words) is written on success only, and so are the device outputs; synchronous.  The refusals and
+// the staging are device_pipeline_sph_sums'.
+int device_pipeline_sph_samples(DevicePipeline*, const ChunkRange* ranges, const SphSamplesArgs& a, uint32_t* out_count,
+                                double* out_density, double* out_shepard, double* out_values, uint64_t* out_summary,
+                                std::string* err);
 // Neighbour lists (pgsd.hoomd.neighbour_list is the definition): the neighbours the census counts, handed over as a CSR
 // pair list -- per entry of a row list in cell order the list positions of its neighbours in the order the SPH kernel
 // sums define, in two calls: the offsets (count, scan), then the segments (fill).  The grid, the range and the list are

@@ -340,6 +340,15 @@ int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* ou
 int launch_sph_accelerations(const SphForcesArgs& a, double* out_pressure_acc, double* out_viscous_acc, double* out_total,
                              uint64_t* out_summary, hipStream_t stream, std::string* err);
 
+// SPH samples (pgsd_sph_samples.hip; SphSamplesArgs, the chunk pointers filled in): check, offsets, compaction of the listed
+// positions, masses, volumes and value columns, one lane per point of a.points (device, a.K x 3) over the candidates in the
+// sums' order around the point's cell (pgsd_traverse.hpp), one workgroup for the ranges and the largest count.  out_count
+// (device, a.K), out_density, out_shepard (device, a.K), out_values (device, a.K x a.C), each or null; out_summary (host, 11
+// words) is written on success only.  a.K == 0 launches nothing; a.n == 0 still runs.  Synchronises `stream`;
+// PGSD_ERROR_INVALID_ARGUMENT for an id that descends or lies outside [0, n_cells] and for an entry >= a.N
+int launch_sph_samples(const SphSamplesArgs& a, uint32_t* out_count, double* out_density, double* out_shepard,
+                       double* out_values, uint64_t* out_summary, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);
@@ -403,6 +412,7 @@ void warm_neighbour_list_kernels();
 void warm_sph_kernels();
 void warm_sph_gradients_kernels();
 void warm_sph_forces_kernels();
+void warm_sph_samples_kernels();
 
 // algorithmic traffic of one job: bytes that must be read (needed columns only, plus the
 // gather index) and chunk bytes written

@@ -60,6 +60,9 @@
  *                     order, the pressure and the laminar viscous acceleration and their sum with gravity, and over the
  *                     list the largest of each with its row -- is the frame in equilibrium, and what time step does it
  *                     allow)
+ *                     pgsd_sph_samples_device (pgsd.fl's sph_samples_device, behind pgsd.hoomd's frame_samples_device:
+ *                     the SPH interpolant of the same list at points of the caller's choosing -- a gauge, a line, a
+ *                     slice, a grid to render --, the same candidates in the same order around the point's cell)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -567,6 +570,52 @@ extern "C"
                                       const double gravity[3], const uint32_t* rows, const int32_t* cell, uint64_t n,
                                       double* out_pressure_acc, double* out_viscous_acc, double* out_total,
                                       uint64_t* out_summary);
+
+    /* SPH samples (pgsd.hoomd.sph_samples is the definition, and the results equal it exactly: every counter and index,
+       every float bit for bit -- a NaN is a NaN): the SPH interpolant of a row list at K points of the caller's choosing,
+       the first pass whose centre is no entry of the list.  position, mass, density, vectors, h, kernel, dimensions,
+       cells, rows, cell and n are pgsd_sph_sums_device's, and so are the grid, the support 2h, r2, inv_h, sigma, w(q) and
+       THE ORDER of the candidates.  defaults: the mass and the density that stand for a chunk stored nowhere (the
+       density default is a number here: there is no "no volume").  values[k], k < 4: an N x value_columns[k] float32 or
+       float64 chunk, or NULL: value_defaults[k] stands for every element of it; value_columns[k] == 0: the slot is
+       unused (values may be NULL when every slot is).  The used slots come first; their C <= 8 columns are concatenated
+       in the order given.  box: the float32 box pgsd_order_rows_by_cell_device takes, from which vectors was formed.
+       points: device, K x 3 float64, in the caller's order, which is the order of every per-point output.
+       THE POINT'S CELL is the cell order's key of its position: the wrapped fraction of pgsd.hoomd.domain_rows, the NaN
+       test before the integer conversion; a point with a NaN fraction is nowhere: its count is 0 and every value +0.0,
+       whatever normalise says.  It is OUTSIDE when it has a cell and its fraction before the wrap is < 0 or >= 1 on an
+       axis that takes part: the single-shift minimum image holds inside the box only.
+       CANDIDATES: the cells of the sums' order around the point's cell, inside a cell ascending list position; d is the
+       minimum-image displacement from the point to x_j and j contributes when d2 < r2, strictly.  Entries of the list
+       that are nowhere contribute to no point.
+       ONE CONTRIBUTING PAIR, float64, no contraction: rr = sqrt(d2), q = rr * inv_h, w = w(q);
+           count += 1, a_m += m_j * w, vw = V_j * w, a_v += vw, a_f[c] += vw * f_j[c]    (V_j = m_j / rho_j, once per entry)
+       AFTER THE LAST: density = sigma * a_m, shepard = sigma * a_v, values[c] = sigma * a_f[c], or with normalise != 0
+       values[c] = a_f[c] / a_v as IEEE gives it (a point without a contributing entry: 0/0, a NaN).
+       Device outputs, each optional (NULL): out_count (K uint32), out_density, out_shepard (K float64), out_values (K x C
+       float64).
+       Host output, 11 words:
+           out_summary[0 .. 4]    K; the points nowhere; the points outside; the points that have a cell and count 0; the
+                                  points that have a cell and whose density, shepard or any value is NaN or infinite
+           out_summary[5 .. 6]    the largest count over the points that have a cell and its point, the smaller index on
+                                  a tie; 0 and 0xFFFFFFFF where no point has a cell
+           out_summary[7 .. 10]   as float64 bit patterns the minimum and maximum of shepard, then of density, over the
+                                  points that have a cell, by strict compares from +inf / -inf (a NaN never replaces a value)
+       No float is summed over the points.  K == 0 returns the summary of no point and launches nothing; n == 0 with K > 0
+       still runs: every point that has a cell is empty.  Staging and synchronisation are pgsd_sph_sums_device's.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), every output as it was: everything
+       pgsd_sph_sums_device refuses; K >= 2^32; points NULL with K > 0; a column count above 4, or more than 8 together; a
+       used slot after an unused one; a value chunk that is not float32 or float64, has another width than declared or
+       another N than position; a value default that is NaN while its chunk is absent; a box whose lengths are not
+       positive or that disagrees with vectors. */
+    int pgsd_sph_samples_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
+                                const struct pgsd_index_entry* const values[4], const uint32_t value_columns[4],
+                                const double value_defaults[4], const double defaults[2], const float box[6],
+                                const double vectors[6], double h, uint32_t kernel, uint32_t dimensions,
+                                const uint32_t cells[3], const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                const double* points, uint64_t K, uint32_t normalise, uint32_t* out_count,
+                                double* out_density, double* out_shepard, double* out_values, uint64_t* out_summary);
 
     /* Indexed read: dst row k takes chunk row rows[k] for k < n (rows: device memory, any order), converted by the
        unpack's rules (dst_type, dst_stride / dst_col0, bitcast, fill_rest); dst->order must be NULL.  The chunk is

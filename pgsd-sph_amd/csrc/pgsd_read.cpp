@@ -1157,7 +1157,8 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
-// What pgsd_sph_sums_device, pgsd_sph_gradients_device and pgsd_sph_accelerations_device share: every refusal of the
+// What pgsd_sph_sums_device, pgsd_sph_gradients_device, pgsd_sph_accelerations_device and pgsd_sph_samples_device (which
+// takes the sums' part of it and checks its value chunks, its points and its box itself) share: every refusal of the
 // first (and, for the other two, of a velocity chunk; for the last, of a pressure chunk), the ranges of the chunks that
 // are stored (position, mass, density, velocity, pressure) and the arguments of the pass -- the support, the grid, r2,
 // inv_h, sigma and G, formed once in float64.  PGSD_SUCCESS: `ranges` and `a` are set (what the accelerations add to
@@ -1358,6 +1359,120 @@ extern "C" int pgsd_sph_accelerations_device(struct pgsd_handle* handle, const s
     return reduction_call(who, "SPH accelerations: ", [&](std::string* err)
                           { return device_pipeline_sph_accelerations(s->dev, ranges, a, out_pressure_acc, out_viscous_acc,
                                                                      out_total, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_sph_samples_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                       const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
+                                       const struct pgsd_index_entry* const values[4], const uint32_t value_columns[4],
+                                       const double value_defaults[4], const double defaults[2], const float box[6],
+                                       const double vectors[6], double h, uint32_t kernel, uint32_t dimensions,
+                                       const uint32_t cells[3], const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                       const double* points, uint64_t K, uint32_t normalise, uint32_t* out_count,
+                                       double* out_density, double* out_shepard, double* out_values, uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_sph_samples_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !value_columns || !value_defaults || !defaults || !box || !vectors || !cells || !out_summary
+        || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    ChunkRange shared[5];
+    SphForcesArgs g;
+    int rc = sph_arguments(who, s, handle, position, mass, density, nullptr, nullptr, defaults, vectors, h, kernel, dimensions,
+                           cells, rows, cell, n, NAN, shared, g);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    SphSamplesArgs a = SphSamplesArgs();
+    static_cast<SphArgs&>(a) = g;
+    ChunkRange ranges[SPHS_CHUNKS];
+    memset(ranges, 0, sizeof(ranges));
+    std::copy(shared, shared + 3, ranges);
+    if (K >= (1ull << 32))
+        return refuse("a call takes fewer than 2^32 points");
+    if (K > 0 && !points)
+        return refuse("points is NULL with K > 0");
+    // the value slots: the used ones first, 1 to 4 columns each, at most 8 together
+    bool unused = false;
+    for (int k = 0; k < SPHS_MAX_VALUES; k++)
+        {
+        const uint32_t width = value_columns[k];
+        if (width == 0)
+            {
+            unused = true;
+            continue;
+            }
+        if (unused)
+            return refuse("a used value slot follows an unused one");
+        if (width > SPHS_MAX_WIDTH)
+            return refuse("a value chunk has 1 to 4 columns");
+        a.C += width;
+        a.value_columns[k] = width;
+        a.value_default[k] = value_defaults[k];
+        }
+    if (a.C > SPHS_MAX_COLUMNS)
+        return refuse("the value chunks have at most 8 columns together");
+    const uint64_t N = position->N;
+    for (int k = 0; k < SPHS_MAX_VALUES; k++)
+        {
+        if (a.value_columns[k] == 0)
+            continue;
+        const struct pgsd_index_entry* entry = values ? values[k] : nullptr;
+        if (!entry)
+            {
+            if (value_defaults[k] != value_defaults[k])
+                return refuse("value chunk " + std::to_string(k) + " is stored nowhere and its default is no number");
+            continue;
+            }
+        const pgsd_index_entry m = *entry;
+        rc = float_chunk(refuse, m, "value chunk " + std::to_string(k), a.value_columns[k], &N, &a.value_f64[k]);
+        if (rc == PGSD_SUCCESS)
+            rc = whole_chunk_range(s, handle, m, &ranges[3 + k].file_offset, &ranges[3 + k].bytes);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        a.present |= 8u << k;
+        }
+    // the box of the points' cells is the cell order's, and the one the vectors were formed from
+    if (!(box[0] > 0.0f && box[1] > 0.0f && (dimensions == 2 || box[2] > 0.0f)))
+        return refuse("box lengths must be positive (Lz unless dimensions == 2)");
+    const double expect[6] = {(double)box[0], (double)box[1], (double)box[2], (double)box[3] * (double)box[1],
+                              (double)box[4] * (double)box[2], (double)box[5] * (double)box[2]};
+    for (int k = 0; k < 6; k++)
+        if (!(expect[k] == vectors[k]))
+            return refuse("the box and the vectors disagree");
+    memset(&a.d, 0, sizeof(a.d));
+    a.d.dims = dimensions;
+    for (int k = 0; k < 3; k++)
+        {
+        a.d.L[k] = (double)box[k];
+        a.d.hi[k] = 1.0;
+        }
+    a.d.xy = (double)box[3];
+    a.d.xz = (double)box[4];
+    a.d.yz = (double)box[5];
+    a.points = points;
+    a.K = K;
+    a.normalise = normalise ? 1u : 0u;
+    if (K == 0)
+        {
+        sph_samples_of_nothing(out_summary);
+        return PGSD_SUCCESS;
+        }
+    if (n == 0)
+        {
+        // (no chunk is staged for a list of no entry, but the points are sampled on the device all the same)
+        rc = ensure_device(s);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        }
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "SPH samples: ", [&](std::string* err)
+                          { return device_pipeline_sph_samples(s->dev, ranges, a, out_count, out_density, out_shepard,
+                                                               out_values, out_summary, err); });
     }
 catch (...)
     {

@@ -21,6 +21,8 @@
 //                      which the pair units walk their candidates through)
 //   pgsd_sph_forces.hip   the SPH accelerations: pressure and laminar viscous acceleration and their sum with gravity
 //                      over the same support in the same order, the largest of each with its row
+//   pgsd_sph_samples.hip   the SPH samples: the interpolant of the list at points of the caller's choosing, the same
+//                      candidates in the same order around the point's cell
 //   pgsd_stats.hpp     what the two reduction units share: an element as a double, the wave tree, the wave counter
 //   pgsd_device_memory.cpp   pgsd_device_alloc / _free / _copy: device memory owned by the library (no kernel)
 //   pgsd_scratch.hpp / .cpp  the host side all of them stand on: scratch space, launch scope, device scope

@@ -15,8 +15,9 @@
 //                          and V[k] = m / rho (one float64 division of the stored values) as float64, so that the pair
 //                          loop reads runs instead of gathering
 //   sph_pair_kernel<F64, KERNEL, VOL>   lane per entry i: x_i and the three accumulators in registers, the candidates
-//                          by traverse_candidates (pgsd_traverse.hpp) in the defined order: the cells, the x-runs, the
-//                          fold and the strict compare are written there, once for the three pair units.  The counters
+//                          by traverse_candidates (pgsd_traverse.hpp) in the defined order, weighed by its sph_weight:
+//                          the cells, the x-runs, the fold and the strict compare are written there, once for the pair
+//                          units.  The counters
 //                          (not_finite, surface) go through LDS counters and 64-bit integer atomics; the minima, maxima
 //                          and the deviation leave as one partial per workgroup
 //   sph_final_kernel       one workgroup: the partials in a fixed strided scan, then the words of the summary
@@ -98,26 +99,6 @@ __global__ __launch_bounds__(SEL_THREADS) void sph_compact_kernel(const SphArgs 
     ms[k] = m;
     if (a.volume)
         vs[k] = m / (a.density ? column_value(a.density, a.density_f64, row) : a.density_default);
-    }
-
-// w(q) of pgsd.hoomd.sph_weight: the operations as written there, one rounding each
-template<int KERNEL> __device__ __forceinline__ double sph_weight(double q)
-    {
-#pragma clang fp contract(off)
-    if constexpr (KERNEL == SPH_WENDLAND_C2)
-        {
-        const double t = 1.0 - 0.5 * q;
-        const double t2 = t * t;
-        return (t2 * t2) * (2.0 * q + 1.0);
-        }
-    else
-        {
-        const double q2 = q * q;
-        if (q < 1.0)
-            return (1.0 - 1.5 * q2) + 0.75 * (q2 * q);
-        const double u = 2.0 - q;
-        return 0.25 * ((u * u) * u);
-        }
     }
 
 // words: the summary in device memory, zeroed by the launcher (words 2 and 3, not_finite and surface, are added to here)

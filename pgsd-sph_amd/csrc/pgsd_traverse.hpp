@@ -6,8 +6,10 @@
 // without contraction (pgsd.hoomd.pair_displacement) and the strict test d2 < r2.  The functor receives (j, dx, dy, dz, d2)
 // of every candidate that passes, in the defined order, and is inlined with what it captures: accumulators it holds by
 // reference stay in registers.  With it what the compact kernels of the same units share: the copy of one position row
-// into xs and the read of one column value -- and what the two gradient-weighted units share, the factor F(q).  Used by
-// pgsd_neighbours.hip, pgsd_neighbour_list.hip, pgsd_sph.hip, pgsd_sph_gradients.hip and pgsd_sph_forces.hip, which carry
+// into xs and the read of one column value -- and what the weighted units share, the weight w(q) and the factor F(q).
+// traverse_candidates_around takes the centre from its caller -- a point that is no entry of the list (pgsd_sph_samples.hip)
+// --, traverse_candidates loads entry k's position and forwards to it.  Used by pgsd_neighbours.hip,
+// pgsd_neighbour_list.hip, pgsd_sph.hip, pgsd_sph_gradients.hip, pgsd_sph_forces.hip and pgsd_sph_samples.hip, which carry
 // no copy of any of it.  Seen by the HIP compiler alone.
 #ifndef PGSD_TRAVERSE_HPP
 #define PGSD_TRAVERSE_HPP
@@ -25,7 +27,7 @@ struct TraverseGrid
     uint32_t dims;
     };
 
-// the grid of a family's argument struct (NeighboursArgs, SphArgs, SphGradientsArgs, SphForcesArgs)
+// the grid of a family's argument struct (NeighboursArgs, SphArgs, SphGradientsArgs, SphForcesArgs, SphSamplesArgs)
 template<typename Args> __device__ __forceinline__ TraverseGrid traverse_grid(const Args& a)
     {
     TraverseGrid g;
@@ -83,14 +85,36 @@ template<int KERNEL> __device__ __forceinline__ double sphg_factor(double q)
         }
     }
 
-// xs: n x 3 compacted positions of element type elem_t; offs: n_cells + 1 CSR offsets; k: the entry, c: its cell id,
-// inside [0, n_cells)
-template<typename elem_t, typename Functor>
-__device__ __forceinline__ void traverse_candidates(const elem_t* __restrict__ x, const uint32_t* __restrict__ offs, uint64_t n,
-                                                    uint32_t k, uint32_t c, const TraverseGrid& g, Functor&& each)
+// w(q) of pgsd.hoomd.sph_weight: the operations as written there, one rounding each.  What the functors of pgsd_sph.hip
+// and pgsd_sph_samples.hip weigh a candidate with.
+template<int KERNEL> __device__ __forceinline__ double sph_weight(double q)
     {
 #pragma clang fp contract(off)
-    const double xi0 = (double)x[(size_t)k * 3 + 0], xi1 = (double)x[(size_t)k * 3 + 1], xi2 = (double)x[(size_t)k * 3 + 2];
+    if constexpr (KERNEL == SPH_WENDLAND_C2)
+        {
+        const double t = 1.0 - 0.5 * q;
+        const double t2 = t * t;
+        return (t2 * t2) * (2.0 * q + 1.0);
+        }
+    else
+        {
+        const double q2 = q * q;
+        if (q < 1.0)
+            return (1.0 - 1.5 * q2) + 0.75 * (q2 * q);
+        const double u = 2.0 - q;
+        return 0.25 * ((u * u) * u);
+        }
+    }
+
+// The traversal with the centre handed in: xs: n x 3 compacted positions of element type elem_t; offs: n_cells + 1 CSR
+// offsets; (xi0, xi1, xi2): the centre, a list entry's position or a point of the caller's; c: its cell id, inside
+// [0, n_cells)
+template<typename elem_t, typename Functor>
+__device__ __forceinline__ void traverse_candidates_around(const elem_t* __restrict__ x, const uint32_t* __restrict__ offs,
+                                                           uint64_t n, const double xi0, const double xi1, const double xi2,
+                                                           uint32_t c, const TraverseGrid& g, Functor&& each)
+    {
+#pragma clang fp contract(off)
     const double Lx = g.vectors[0], Ly = g.vectors[1], Lz = g.vectors[2];
     const double xyLy = g.vectors[3], xzLz = g.vectors[4], yzLz = g.vectors[5];
     const double hx = Lx * 0.5, hy = Ly * 0.5, hz = Lz * 0.5; // (exact halves)
@@ -149,6 +173,15 @@ __device__ __forceinline__ void traverse_candidates(const elem_t* __restrict__ x
                 }
             }
         }
+    }
+
+// the traversal around entry k of the list itself: its position is loaded and handed in
+template<typename elem_t, typename Functor>
+__device__ __forceinline__ void traverse_candidates(const elem_t* __restrict__ x, const uint32_t* __restrict__ offs, uint64_t n,
+                                                    uint32_t k, uint32_t c, const TraverseGrid& g, Functor&& each)
+    {
+    traverse_candidates_around(x, offs, n, (double)x[(size_t)k * 3 + 0], (double)x[(size_t)k * 3 + 1],
+                               (double)x[(size_t)k * 3 + 2], c, g, static_cast<Functor&&>(each));
     }
     } // namespace pgsd_amd
 

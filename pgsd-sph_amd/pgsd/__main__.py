@@ -40,7 +40,13 @@
            ``slength``): the search grid and the entries, the largest total, pressure and viscous acceleration, each with
            its row, the entries whose total is not finite and the force time step ``0.25 sqrt(h / |a|)``
            (``--viscosity MU``, ``--gravity GX,GY,GZ``, ``--kernel``, ``--types``; ``pgsd.hoomd.frame_accelerations`` on the
-           host: no GPU).
+           host: no GPU);
+           ``--sample NX,NY,NZ [H]`` adds the SPH interpolant on an NX x NY x NZ lattice of cell-centre points over the box
+           (``pgsd.hoomd.sample_grid``) for the smoothing length H (without H: the frame's uniform ``slength``): the search
+           grid, the points nowhere, outside, empty and not finite, the largest count, the ranges of the density and of
+           the Shepard sum and per sampled column the smallest and largest value (``--fields a,b``: the per-particle
+           fields sampled, default velocity; ``--normalise``: values divided by the Shepard sum; ``--kernel``,
+           ``--types``; ``pgsd.hoomd.frame_samples`` on the host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -119,6 +125,43 @@ def _cmd_info(args):
         _print_sph_gradients(args, frame)
     if args.sph_forces is not None:
         _print_sph_forces(args, frame)
+    if args.sample is not None:
+        _print_sample(args, frame)
+
+
+def _print_sample(args, frame):
+    """``info --sample``: `pgsd.hoomd.frame_samples` of one frame on a `sample_grid` lattice, on the host."""
+    import numpy
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    try:
+        shape = tuple(int(v) for v in args.sample[0].split(','))
+        h = float(args.sample[1]) if len(args.sample) > 1 else None
+        if len(shape) != 3 or len(args.sample) > 2:
+            raise ValueError
+    except ValueError:
+        raise ValueError("--sample takes NX,NY,NZ [H]: %r" % ' '.join(args.sample))
+    fields = tuple(f for f in args.fields.split(',') if f) if args.fields else ('velocity',)
+    with hoomd.open(args.file, 'r') as traj:
+        fr = traj[frame]
+        dims = int(fr.configuration.dimensions)
+        points = hoomd.sample_grid(fr.configuration.box, shape, dims)
+        m = hoomd.frame_samples(fr, points, fields=fields, h=h, kernel=args.kernel, normalise=args.normalise, where=where)
+    print("SPH samples of frame %d with h = %r (%s) on %d x %d x %d points over %d x %d x %d cells%s:"
+          % ((frame, m.h, m.kernel) + shape + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  points:       %d  nowhere: %d  outside: %d  empty: %d  not finite: %d"
+          % (m.points, m.nowhere, m.outside, m.empty, m.not_finite))
+    if m.count_max_at is not None:
+        print("  count:        largest %d at point %d" % (m.count_max, m.count_max_at))
+        print("  density:      smallest %r  largest %r" % (m.density_min, m.density_max))
+        print("  shepard:      smallest %r  largest %r" % (m.shepard_min, m.shepard_max))
+        for k, name in enumerate(fields):
+            v = m.field(k)
+            for c in range(v.shape[1]):
+                ok = v[:, c][v[:, c] == v[:, c]]
+                print("  %-13s smallest %r  largest %r%s"
+                      % ("%s[%d]:" % (name, c), float(ok.min()) if ok.size else None, float(ok.max()) if ok.size else None,
+                         "  (normalised)" if m.normalise else ""))
 
 
 def _print_sph_forces(args, frame):
@@ -419,7 +462,8 @@ def main(argv=None):
     p.add_argument('--stats', action='store_true',
                    help="print count, nan, inf, min, max and mean per field and column of the frame")
     p.add_argument('--fields', type=str, default=None, metavar='NAME[,NAME...]',
-                   help="the per-particle fields of --stats (default: position,velocity,density,pressure,energy)")
+                   help="the per-particle fields of --stats (default: position,velocity,density,pressure,energy) and the float "
+                        "fields --sample interpolates (default: velocity)")
     p.add_argument('--types', type=str, default=None, metavar='NAME[,NAME...]',
                    help="--stats, --moments and --displacement over the particles of these types only")
     p.add_argument('--all-frames', action='store_true',
@@ -454,8 +498,13 @@ def main(argv=None):
                    help="with --sph-forces: the dynamic viscosity of the laminar viscous term (default: no viscous term)")
     p.add_argument('--gravity', type=str, default=None, metavar='GX,GY,GZ',
                    help="with --sph-forces: the gravity (default: 0,0,0; write --gravity=-1,0,0 where GX is negative)")
+    p.add_argument('--sample', type=str, nargs='+', default=None, metavar=('NX,NY,NZ', 'H'),
+                   help="print the SPH interpolant on an NX x NY x NZ lattice of points over the box for the smoothing "
+                        "length H (without H: the frame's uniform slength): the points nowhere, outside and empty, the "
+                        "largest count and the ranges of density, Shepard sum and the sampled fields")
+    p.add_argument('--normalise', action='store_true', help="with --sample: divide every value by the Shepard sum")
     p.add_argument('--kernel', type=str, default='wendland_c2', choices=('wendland_c2', 'cubic_spline'),
-                   help="the kernel of --sph, --sph-gradients and --sph-forces (default: wendland_c2)")
+                   help="the kernel of --sph, --sph-gradients, --sph-forces and --sample (default: wendland_c2)")
     p.add_argument('--surface', type=float, default=None, metavar='S',
                    help="with --sph: count the entries whose Shepard sum is below S (the free surface)")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")

@@ -596,6 +596,66 @@ def _force_terms(who, viscosity, gravity):
     return mu, c_gravity
 
 
+def _sample_defaults(who, defaults):
+    """The mass and the density that stand for a chunk stored nowhere as float64[2]; ``None``: the schema's."""
+    c_defaults = numpy.ascontiguousarray(
+        numpy.array([1.0, 0.0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+    if c_defaults.shape[0] != 2:
+        raise ValueError("%s: defaults holds a mass and a density" % who)
+    return c_defaults
+
+
+def _sample_values(who, values):
+    """``values`` of :meth:`PGSDFile.sph_samples_device`, checked as far as it goes without the file: per value ``(chunk
+    or None, columns or None, default)``; ``columns`` is ``None`` where the stored chunk's own width is meant."""
+    values = tuple(values)
+    if len(values) > 4:
+        raise ValueError("%s: values holds at most 4 chunks: %d" % (who, len(values)))
+    out, total = [], 0
+    for k, v in enumerate(values):
+        v = tuple(v) if isinstance(v, (tuple, list)) else ()
+        if len(v) == 2 and isinstance(v[1], str):
+            out.append((v, None, 0.0))
+            continue
+        if len(v) != 3 or (v[0] is not None and (not isinstance(v[0], (tuple, list)) or len(v[0]) != 2)):
+            raise ValueError("%s: value %d is (frame, name) of a stored chunk or (chunk or None, columns, default)" % (who, k))
+        try:
+            columns, default = int(v[1]), float(v[2])
+        except (TypeError, ValueError):
+            raise ValueError("%s: value %d is (frame, name) of a stored chunk or (chunk or None, columns, default)" % (who, k))
+        if not 1 <= columns <= 4:
+            raise ValueError("%s: value %d has 1 to 4 columns: %r" % (who, k, v[1]))
+        if v[0] is None and default != default:
+            raise ValueError("%s: value %d is stored nowhere and its default is no number" % (who, k))
+        total += columns
+        out.append((None if v[0] is None else tuple(v[0]), columns, default))
+    if total > 8:
+        raise ValueError("%s: the values hold at most 8 columns together: %d" % (who, total))
+    return out
+
+
+def _sample_points(who, points):
+    """``points`` of :meth:`PGSDFile.sph_samples_device`, checked: ``(host float64 K x 3 or None, the device array or None,
+    K)``."""
+    bad = "%s: points holds K x 3 float32 or float64 values (numpy) or K x 3 float64 values in GPU memory" % who
+    if isinstance(points, numpy.ndarray) or isinstance(points, (list, tuple)):
+        a = numpy.asarray(points)
+        if a.dtype not in (numpy.float32, numpy.float64) or (a.size and (a.ndim != 2 or a.shape[1] != 3)):
+            raise ValueError(bad)
+        a = numpy.ascontiguousarray(a.astype(numpy.float64).reshape(-1, 3))
+        if a.shape[0] >= (1 << 32):
+            raise ValueError("%s: a call takes fewer than 2^32 points" % who)
+        return a, None, a.shape[0]
+    if not (isinstance(points, DeviceBuffer) or _is_device_tensor(points) or hasattr(points, '__cuda_array_interface__')):
+        raise ValueError(bad)
+    shape = tuple(int(v) for v in points.shape)
+    if not str(points.dtype).endswith('float64') or len(shape) != 2 or shape[1] != 3:
+        raise ValueError(bad)
+    if shape[0] >= (1 << 32):
+        raise ValueError("%s: a call takes fewer than 2^32 points" % who)
+    return None, points, shape[0]
+
+
 def _moments_defaults(who, defaults):
     """The row that stands for every row of a chunk stored nowhere -- mass, v[3], energy, x[3] -- as float64[8]."""
     c_defaults = numpy.ascontiguousarray(
@@ -2292,6 +2352,103 @@ cdef class PGSDFile:
             got.pressure_acc, got.total = _device_head_rows(out_pacc, count), _device_head_rows(out_total, count)
             if mu is not None:
                 got.viscous_acc = _device_head_rows(out_vacc, count)
+        return got
+
+    def sph_samples_device(self, frame, name, box, h, cells, rows, cell, points, n=None, values=(), mass=None, density=None,
+                           defaults=None, dimensions=3, kernel='wendland_c2', normalise=False):
+        """The SPH interpolant of a row list in cell order at points of the caller's choosing, on the GPU: per point the
+        entries strictly inside the kernel support ``2h`` of it, the density, the Shepard sum and the value columns, in
+        the order that is part of their definition.
+
+        Args:
+            frame, name, box, h, cells, rows, cell, n, mass, density, dimensions, kernel: as :meth:`sph_sums_device` takes
+                them.
+            points: ``K x 3`` float32 or float64 values as a numpy array (converted to float64 and uploaded) or ``K x 3``
+                float64 values in GPU memory; every per-point result is in their order.
+            values: up to 4 values, each ``(frame, name)`` of a stored N x M float32 or float64 chunk, ``1 <= M <= 4``, or
+                ``(chunk or None, columns, default)``: a chunk of that width, or one stored nowhere whose every element is
+                ``default``.  At most 8 columns together, concatenated in the order given.
+            defaults: ``(mass, density)`` that stand for a chunk stored nowhere; ``None``: 1.0 and 0.0, the schema's (the
+                density is a number here: a density of 0 gives what IEEE gives).
+            normalise (bool): divide every value by the Shepard sum (a point with no entry in reach: NaN).
+
+        Returns:
+            A :class:`pgsd.hoomd.KernelSamples`: exactly :func:`pgsd.hoomd.sph_samples` of the same list and points --
+            every counter and index, every float bit for bit -- with ``count`` (uint32, ``K``), ``density``, ``shepard``
+            (float64, ``K``) and ``values`` (float64, ``K x C``) in GPU memory.  The chunks are staged whole unless an
+            earlier call left them staged; the staged rows are kept until the next :meth:`wait_read`.  What the library
+            refuses (:c:func:`pgsd_sph_samples_device`) raises ValueError and computes nothing.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry, e_mass, e_density
+        cdef C.pgsd_index_entry e_values[4]
+        cdef const C.pgsd_index_entry* p_values[4]
+        cdef uint32_t c_columns[4]
+        cdef double c_value_defaults[4]
+        cdef int k
+        self._entry(frame, name, &entry)
+        cdef const C.pgsd_index_entry* p_mass = self._optional(mass, &e_mass)
+        cdef const C.pgsd_index_entry* p_density = self._optional(density, &e_density)
+        c_vectors = _box_vectors(box)
+        c_box = numpy.ascontiguousarray(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+        grid, c_cells = _cell_counts("sph_samples_device", cells)
+        cdef uint32_t c_kernel = _sph_kernel("sph_samples_device", kernel)
+        c_defaults = _sample_defaults("sph_samples_device", defaults)
+        asked = _sample_values("sph_samples_device", values)
+        widths = []
+        for k in range(4):
+            p_values[k] = NULL
+            c_columns[k] = 0
+            c_value_defaults[k] = 0.0
+            if k < len(asked):
+                chunk, columns, default = asked[k]
+                p_values[k] = self._optional(chunk, &e_values[k])
+                if columns is None:
+                    columns = int(e_values[k].M)
+                    if not 1 <= columns <= 4:
+                        raise ValueError("sph_samples_device: value %d has 1 to 4 columns: %r" % (k, columns))
+                c_columns[k] = columns
+                c_value_defaults[k] = default
+                widths.append(columns)
+        if sum(widths) > 8:
+            raise ValueError("sph_samples_device: the values hold at most 8 columns together: %d" % sum(widths))
+        host_points, device_points, n_points = _sample_points("sph_samples_device", points)
+        c_rows, c_cell, count = _cell_ordered_lists("sph_samples_device", rows, cell, n)
+        device = self.pipeline_device()
+        if device_points is None:
+            device_points = _device_from_host(host_points if n_points else numpy.zeros((1, 3)), device)
+        cdef uintptr_t p_points = _device_memory(device_points, "points")[0]
+        summary = numpy.zeros(11, dtype=numpy.uint64)
+        cdef uintptr_t p_count, p_dens, p_shep, p_vals
+        total = sum(widths)
+        out_count, p_count = _per_entry(n_points, (), numpy.uint32, device)
+        out_dens, p_dens = _per_entry(n_points, (), numpy.float64, device)
+        out_shep, p_shep = _per_entry(n_points, (), numpy.float64, device)
+        out_vals, p_vals = _per_entry(n_points, (max(total, 1),), numpy.float64, device)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows`, `cell` and `points`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data, p_box = c_box.ctypes.data
+        cdef uint64_t c_n = count, c_K = n_points
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef uint32_t c_normalise = 1 if normalise else 0
+        cdef double c_h = float(h)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_sph_samples_device(&self._handle, &entry, p_mass, p_density, p_values, c_columns,
+                                               c_value_defaults, <const double*>p_defaults, <const float*>p_box,
+                                               <const double*>p_vectors, c_h, c_kernel, c_dims, <const uint32_t*>p_cells,
+                                               <const uint32_t*>p_rows, <const int32_t*>p_cell, c_n, <const double*>p_points,
+                                               c_K, c_normalise, <uint32_t*>p_count, <double*>p_dens, <double*>p_shep,
+                                               <double*>p_vals, <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("sph_samples_device", retval, "refused", self._name, err)
+        got = _hoomd.KernelSamples(c_h, kernel, grid, int(dimensions), summary, bool(normalise), widths)
+        got.count, got.density = _device_head(out_count, n_points), _device_head(out_dens, n_points)
+        got.shepard = _device_head(out_shep, n_points)
+        got.values = _device_head_rows(out_vals, n_points)
+        if not total:       # (no value column: K x 0)
+            got.values = out_vals.view(shape=(n_points, 0)) if isinstance(out_vals, DeviceBuffer) else out_vals[:n_points, :0]
         return got
 
     def frame_displacements_device(self, chunks, vectors_a, vectors_b, minimum_image=False, dimensions=3, type0=0,

@@ -359,9 +359,10 @@ def domain_rows(position, box, domain, dimensions=3):
     return numpy.flatnonzero(inside)
 
 
-def _wrapped_fractions(position, box, dimensions):
+def _wrapped_fractions(position, box, dimensions, unwrapped=False):
     """The fractional coordinates `domain_rows` documents, wrapped into [0, 1): one float64 array per axis that takes
-    part (x, y, and z unless ``dimensions == 2``).  `domain_rows` and `halo_rows` both compare these."""
+    part (x, y, and z unless ``dimensions == 2``).  `domain_rows` and `halo_rows` both compare these.  ``unwrapped``: the
+    same fractions ``s`` before the wrap (`sph_samples` judges a point outside the box on them)."""
     dimensions = int(dimensions)
     if dimensions not in (2, 3):
         raise ValueError("dimensions must be 2 or 3")
@@ -378,6 +379,8 @@ def _wrapped_fractions(position, box, dimensions):
         s = [((x + Lx / 2) - ((xz - yz * xy) * z + xy * y)) / Lx,
              ((y + Ly / 2) - yz * z) / Ly,
              (z + Lz / 2) / Lz]
+        if unwrapped:
+            return s[:2 if dimensions == 2 else 3]
         out = []
         for a in range(2 if dimensions == 2 else 3):
             f = s[a] - numpy.floor(s[a])
@@ -2133,9 +2136,15 @@ def _sph_near_pairs(t):
     d2)`` arrays, the pairs of a step sorted by ``i`` and, inside one candidate cell, by ascending ``j``.  `numpy.add.at`
     adds the pairs of a step one after the other, so that together with the order of the steps each entry's sum is the
     sequential one of the definition."""
+    return _sph_pairs_around(t, t.xs[:t.somewhere], t.cell_sorted[:t.somewhere])
+
+
+def _sph_pairs_around(t, centres, ids):
+    """`_sph_near_pairs` with the centres handed in: ``centres`` (float64, ``K x 3``) and their cells ``ids`` (each inside
+    the grid) stand where the list's own entries do, ``i`` counts the centres, ``j`` the entries of the list, and ``d =
+    pair_displacement(centres[i], xs[j])``.  The cells, their order and the order inside a step are the same."""
     cx, cy, cz = t.grid
-    offs, xs, somewhere = t.offs, t.xs, t.somewhere
-    ids = t.cell_sorted[:somewhere]
+    offs, xs, somewhere = t.offs, t.xs, ids.shape[0]
     ix, iy, iz = ids % cx, (ids // cx) % cy, ids // (cx * cy)
     for oz in _axis_offsets(cz):
         for oy in _axis_offsets(cy):
@@ -2154,7 +2163,7 @@ def _sph_near_pairs(t):
                         i = numpy.repeat(numpy.arange(lo, hi, dtype=numpy.int64), ln)
                         start = numpy.cumsum(ln) - ln
                         j = numpy.repeat(first[lo:hi] - start, ln) + numpy.arange(total, dtype=numpy.int64)
-                        d = pair_displacement(xs[i], xs[j], t.vectors, t.dimensions)
+                        d = pair_displacement(centres[i], xs[j], t.vectors, t.dimensions)
                         with numpy.errstate(invalid='ignore', over='ignore'):
                             d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
                             near = d2 < t.r2
@@ -2680,6 +2689,295 @@ def frame_accelerations(frame_or_arrays, h=None, kernel='wendland_c2', viscosity
     return sph_accelerations(position, arrays.get('velocity'), box, h, mass=arrays.get('mass'), density=arrays.get('density'),
                              pressure=arrays.get('pressure'), viscosity=viscosity, gravity=gravity, rows=rows, cells=cells,
                              dimensions=dimensions, kernel=kernel)
+
+
+# ---- SPH samples: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_samples_device`) equals exactly
+_SPHS_SUMMARY_WORDS = 11    # K, nowhere, outside, empty, not_finite, count_max, count_max_at, shepard min, max, density min, max
+_SPHS_MAX_VALUES = 4        # value arrays of one call
+_SPHS_MAX_WIDTH = 4         # columns of one value array
+_SPHS_MAX_COLUMNS = 8       # columns of all of them together
+_SPHS_COUNTERS = ('points', 'nowhere', 'outside', 'empty', 'not_finite', 'count_max')
+
+
+def sample_grid(box, shape, dimensions=3, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0)):
+    """The cell-centre points of an ``nx x ny x nz`` lattice over the fractional sub-box ``[lo, hi)`` of ``box``, as
+    float64 real coordinates ``(nx*ny*nz) x 3``, x fastest, then y, then z: points for `sph_samples` and its GPU twin,
+    which both receive them as plain data.
+
+    The fraction on axis ``a`` is ``f_a = lo_a + (hi_a - lo_a) * ((i_a + 0.5) / n_a)``; the real coordinates come from
+    the inverse of `domain_rows`' skew, box rounded to float32 as a file stores it: ``z = f_z*Lz - Lz/2``, ``y = (f_y*Ly -
+    Ly/2) + yz*z``, ``x = (f_x*Lx - Lx/2) + ((xz - yz*xy)*z + xy*y)``.  With ``dimensions == 2`` ``nz`` is 1 and ``z`` is
+    0."""
+    dimensions = int(dimensions)
+    if dimensions not in (2, 3):
+        raise ValueError("dimensions must be 2 or 3")
+    b = numpy.asarray(box, dtype=numpy.float32).reshape(-1)
+    if b.shape[0] < 6:
+        raise ValueError("box must hold 6 values")
+    Lx, Ly, Lz, xy, xz, yz = (numpy.float64(v) for v in b[:6])
+    n = tuple(int(v) for v in shape)
+    if len(n) != 3 or any(v < 1 for v in n):
+        raise ValueError("a sample grid takes three counts (nx, ny, nz), each at least 1: %r" % (shape,))
+    if dimensions == 2 and n[2] != 1:
+        raise ValueError("dimensions == 2 takes nz == 1: z is not looked at")
+    lo = numpy.array(lo, dtype=numpy.float64).reshape(-1)
+    hi = numpy.array(hi, dtype=numpy.float64).reshape(-1)
+    if lo.shape[0] != 3 or hi.shape[0] != 3 or not (numpy.isfinite(lo).all() and numpy.isfinite(hi).all()):
+        raise ValueError("lo and hi hold three finite fractions each")
+    f = [lo[a] + (hi[a] - lo[a]) * ((numpy.arange(n[a], dtype=numpy.float64) + 0.5) / numpy.float64(n[a])) for a in range(3)]
+    fz, fy, fx = numpy.meshgrid(f[2], f[1], f[0], indexing='ij')
+    fx, fy, fz = fx.reshape(-1), fy.reshape(-1), fz.reshape(-1)
+    z = numpy.zeros(fx.shape[0], dtype=numpy.float64) if dimensions == 2 else fz * Lz - Lz / 2
+    y = (fy * Ly - Ly / 2) + yz * z
+    x = (fx * Lx - Lx / 2) + ((xz - yz * xy) * z + xy * y)
+    return numpy.stack([x, y, z], axis=1)
+
+
+class KernelSamples(object):
+    """The SPH interpolant of a list in cell order at probe points (`sph_samples`).
+
+    Attributes:
+        h (float), kernel (str), grid (``(cx, cy, cz)``: the search grid), dimensions (int), normalise (bool), columns
+            (tuple: the width of every value array given): what was asked; sigma (float): `sph_sigma`.
+        count (uint32, ``K``), density, shepard (float64, ``K``), values (float64, ``K x C``): per point, in the caller's
+            order, the list entries strictly inside ``2h``, ``sigma * sum m_j w``, ``sigma * sum V_j w`` and per column
+            ``sigma * sum V_j w f_j`` (with ``normalise``: ``sum V_j w f_j / sum V_j w``); 0 and ``+0.0`` at a point
+            nowhere.  numpy arrays from the model, arrays in GPU memory from the GPU.
+        points, nowhere, outside, empty, not_finite (int): the points; those with a NaN fraction; those that have a cell
+            but whose unwrapped fraction is ``< 0`` or ``>= 1`` on an axis that takes part (the single-shift minimum image
+            holds inside the box only: results not to trust); those that have a cell and no entry inside ``2h``; those
+            that have a cell and whose ``density``, ``shepard`` or any value is NaN or infinite.
+        count_max (int), count_max_at (int or ``None``): the largest ``count`` over the points that have a cell and its
+            point, the smaller index on a tie; ``None`` where no point has a cell.
+        shepard_min, shepard_max, density_min, density_max (float): over the points that have a cell, by strict compares
+            from ``+inf`` / ``-inf`` (a NaN never replaces a value).
+    """
+
+    __slots__ = ('h', 'kernel', 'grid', 'dimensions', 'normalise', 'columns', 'sigma', 'count', 'density', 'shepard', 'values',
+                 'points', 'nowhere', 'outside', 'empty', 'not_finite', 'count_max', 'count_max_at', 'shepard_min',
+                 'shepard_max', 'density_min', 'density_max', '_words')
+
+    def __init__(self, h, kernel, grid, dimensions, summary, normalise=False, columns=(), count=None, density=None,
+                 shepard=None, values=None):
+        """``summary``: the 11 uint64 words of `pgsd_sph_samples_device` -- K, nowhere, outside, empty, not_finite, the
+        largest count and its point, then as float64 bit patterns the minimum and maximum of shepard and of density."""
+        s = numpy.ascontiguousarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _SPHS_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _SPHS_SUMMARY_WORDS)
+        self._words = s.copy()
+        self.h, self.kernel, self.dimensions, self.normalise = float(h), kernel, int(dimensions), bool(normalise)
+        self.sigma = sph_sigma(kernel, h, dimensions)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.columns = tuple(int(c) for c in columns)
+        for k, name in enumerate(_SPHS_COUNTERS):
+            setattr(self, name, int(s[k]))
+        self.count_max_at = None if int(s[6]) == _NEIGHBOURS_NONE else int(s[6])
+        f = s[7:11].view(numpy.float64)
+        self.shepard_min, self.shepard_max, self.density_min, self.density_max = (float(v) for v in f)
+        self.count, self.density, self.shepard, self.values = count, density, shepard, values
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return self._words.copy()
+
+    def field(self, k):
+        """The ``K x M_k`` view of value array ``k`` inside ``values``."""
+        k = int(k)
+        if not 0 <= k < len(self.columns):
+            raise ValueError("there are %d value arrays: no array %d" % (len(self.columns), k))
+        if self.values is None:
+            return None
+        first, width, total = sum(self.columns[:k]), self.columns[k], sum(self.columns)
+        v = self.values
+        if fl is not None and isinstance(v, fl.DeviceBuffer):
+            return v.view(shape=(int(v.shape[0]), width), strides=(8 * total, 8), offset_bytes=8 * first)
+        return v[:, first:first + width]
+
+    def as_grid(self, name_or_k, shape):
+        """``count``, ``density`` or ``shepard`` (by name) or value array ``k`` of the points of `sample_grid` ``(box,
+        shape)``, shaped ``(nz, ny, nx)`` (``(nz, ny, nx, M_k)`` for a value array)."""
+        a = getattr(self, name_or_k) if name_or_k in ('count', 'density', 'shepard') else self.field(name_or_k)
+        nx, ny, nz = (int(v) for v in shape)
+        if a is None or nx * ny * nz != int(a.shape[0]):
+            raise ValueError("as_grid needs the per-point arrays of %d x %d x %d points" % (nx, ny, nz))
+        if fl is not None and isinstance(a, fl.DeviceBuffer):      # (no tensor library: the grid is shaped on the host)
+            k = None if a.is_contiguous() else int(name_or_k)
+            a = a.to_host() if k is None else self.values.to_host()[:, sum(self.columns[:k]):sum(self.columns[:k + 1])]
+        return a.reshape((nz, ny, nx) + tuple(a.shape[1:]))
+
+    def __repr__(self):
+        return "KernelSamples(h=%r, kernel=%r, grid=%r, points=%d, nowhere=%d, outside=%d, empty=%d, shepard=[%r, %r])" % (
+            self.h, self.kernel, self.grid, self.points, self.nowhere, self.outside, self.empty, self.shepard_min,
+            self.shepard_max)
+
+
+def _sphs_summary(has, outside, count, density, shepard, values):
+    """The summary words from the per-point results: no float is summed over the points, so no order enters."""
+    words = numpy.zeros(_SPHS_SUMMARY_WORDS, dtype=numpy.uint64)
+    f = words[7:11].view(numpy.float64)
+    f[0::2], f[1::2] = numpy.inf, -numpy.inf
+    words[0], words[1], words[6] = has.shape[0], int(numpy.count_nonzero(~has)), _NEIGHBOURS_NONE
+    if not has.any():
+        return words
+    words[2] = int(numpy.count_nonzero(outside & has))
+    words[3] = int(numpy.count_nonzero(has & (count == 0)))
+    finite = numpy.isfinite(density) & numpy.isfinite(shepard)
+    if values.shape[1]:
+        finite &= numpy.isfinite(values).all(axis=1)
+    words[4] = int(numpy.count_nonzero(has & ~finite))
+    size = numpy.where(has, count.astype(numpy.int64), -1)
+    at = int(numpy.argmax(size))                        # (the first point that attains the maximum)
+    words[5], words[6] = int(size[at]), at
+    for k, v in enumerate((shepard, density)):
+        ok = v[has & (v == v)]
+        if ok.size:
+            f[2 * k], f[2 * k + 1] = min(numpy.inf, ok.min()), max(-numpy.inf, ok.max())
+    return words
+
+
+def _sphs_points(points):
+    x = numpy.asarray(points)
+    if x.dtype not in (numpy.float32, numpy.float64) or (x.size and (x.ndim != 2 or x.shape[1] != 3)):
+        raise ValueError("points holds K x 3 float32 or float64 values")
+    return x.astype(numpy.float64).reshape(-1, 3)
+
+
+def _sphs_values(values, N):
+    """``values`` of `sph_samples`, checked: ``(float64 arrays N x M, widths)``."""
+    values = tuple(values)
+    if len(values) > _SPHS_MAX_VALUES:
+        raise ValueError("values holds at most %d arrays: %d" % (_SPHS_MAX_VALUES, len(values)))
+    given, widths = [], []
+    for k, v in enumerate(values):
+        v = numpy.asarray(v)
+        width = 1 if v.ndim <= 1 else (int(v.shape[1]) if v.ndim == 2 else 0)
+        if v.dtype not in (numpy.float32, numpy.float64) or not 1 <= width <= _SPHS_MAX_WIDTH or v.size != N * width:
+            raise ValueError("value %d holds N x M float32 or float64 values, 1 <= M <= %d, one row per row of position"
+                             % (k, _SPHS_MAX_WIDTH))
+        given.append(v.astype(numpy.float64).reshape(-1, width))
+        widths.append(width)
+    if sum(widths) > _SPHS_MAX_COLUMNS:
+        raise ValueError("the values hold at most %d columns together: %d" % (_SPHS_MAX_COLUMNS, sum(widths)))
+    return given, tuple(widths)
+
+
+def sph_samples(points, position, box, h, values=(), mass=None, density=None, rows=None, cells=None, dimensions=3,
+                kernel='wendland_c2', normalise=False):
+    """The SPH interpolant of a row list at points of the caller's choosing: per point ``p`` the entries ``j`` of the list
+    strictly inside the kernel support ``2h`` of it, the density ``sigma * sum_j m_j W_pj``, the Shepard sum ``sigma *
+    sum_j V_j W_pj`` and per value column ``sigma * sum_j V_j W_pj f_j`` (``V_j = m_j / rho_j``) -- the water height at a
+    gauge, a pressure profile along a line, the velocity on a slice or a grid to render (`sample_grid`).  The definition
+    the GPU pass (`pgsd.fl.PGSDFile.sph_samples_device`, `HOOMDTrajectory.frame_samples_device`) equals exactly, the floats
+    bit for bit.
+
+    Args:
+        points: ``K x 3`` float32 or float64, converted exactly to float64; every per-point result is in their order.
+        position, box, h, mass, rows, cells, dimensions, kernel: `sph_kernel_sums`'.  The grid, the support ``2h``, ``r2``,
+            ``inv_h``, ``sigma``, the list in cell order and every refusal are its own.
+        density: ``N`` float32 or float64 values, or ``None``: the schema's default, 0.0 in every row (the values that
+            result may be infinite or NaN: that is defined behaviour).
+        values: up to 4 arrays, each ``N x M`` with ``1 <= M <= 4``, float32 or float64, at most 8 columns together; their
+            ``C`` columns are concatenated in the order given.
+        normalise (bool): divide every value by the Shepard sum.
+
+    **The point's cell** is ``cell_ids(points, box, grid, dimensions)``.  A point with a NaN fraction is nowhere: its
+    ``count`` is 0 and every value ``+0.0``, whatever ``normalise`` says.
+
+    **Candidates**: the cells of `sph_kernel_sums`' defined order around the point's cell (``oz``, inside it ``oy``, inside
+    it ``ox``, the wrapped cell), inside a cell ascending list position; ``d = pair_displacement(x_p, x_j)`` and ``j``
+    contributes when ``d2 < r2``, strictly.  Entries of the list that are nowhere contribute to no point.
+
+    **One contributing pair**, float64 without contraction, one rounding per written operation: ``rr = sqrt(d2)``, ``q =
+    rr * inv_h``, ``w = sph_weight(q)``; ``count += 1``, ``a_m += m_j * w``, ``vw = V_j * w``, ``a_v += vw``, ``a_f[c] +=
+    vw * f_j[c]``.  After the last candidate ``density = sigma * a_m``, ``shepard = sigma * a_v`` and ``values[c] = sigma *
+    a_f[c]``, or with ``normalise`` ``values[c] = a_f[c] / a_v`` -- what IEEE gives, so a point with no entry in reach is
+    ``0/0``, a NaN: the blank value a renderer wants.
+
+    Returns a `KernelSamples`.
+    """
+    asked = _sph_asked(box, h, cells, dimensions, kernel)
+    xp = _sphs_points(points)
+    t = _sph_list(asked, position, box, rows, (('mass', mass, 1), ('density', density, 1)))
+    N = numpy.asarray(position).size // 3
+    given, widths = _sphs_values(values, N)
+    dimensions, h, kid, grid = asked[0], asked[1], asked[2], asked[4]
+    n, sigma, K, C = t.n, t.sigma, xp.shape[0], sum(widths)
+    at = t.rows_sorted.astype(numpy.int64)
+    fs = numpy.concatenate([v[at] for v in given], axis=1) if given else numpy.zeros((n, 0), dtype=numpy.float64)
+    mass, rho = t.columns
+    m = numpy.ones(n, dtype=numpy.float64) if mass is None else mass
+    rho = numpy.zeros(n, dtype=numpy.float64) if rho is None else rho
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        vol = m / rho
+    n_cells = grid[0] * grid[1] * grid[2]
+    ids = cell_ids(xp, box, grid, dimensions)
+    has = ids < n_cells
+    outside = numpy.zeros(K, dtype=bool)
+    with numpy.errstate(invalid='ignore'):
+        for s in _wrapped_fractions(xp, box, dimensions, unwrapped=True):
+            outside |= (s < 0.0) | (s >= 1.0)
+    where = numpy.flatnonzero(has)
+    count = numpy.zeros(K, dtype=numpy.uint32)
+    a_m, a_v = numpy.zeros(K, dtype=numpy.float64), numpy.zeros(K, dtype=numpy.float64)
+    a_f = [numpy.zeros(K, dtype=numpy.float64) for _ in range(C)]
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        for i, j, d, d2 in _sph_pairs_around(t, xp[where], ids[where]):
+            i = where[i]
+            w = sph_weight(numpy.sqrt(d2) * t.inv_h, kernel)
+            numpy.add.at(count, i, 1)
+            numpy.add.at(a_m, i, m[j] * w)
+            vw = vol[j] * w
+            numpy.add.at(a_v, i, vw)
+            for c in range(C):
+                numpy.add.at(a_f[c], i, vw * fs[j, c])
+        rho_sum, shepard = sigma * a_m, sigma * a_v
+        out = numpy.zeros((K, C), dtype=numpy.float64)
+        for c in range(C):
+            out[:, c] = a_f[c] / a_v if normalise else sigma * a_f[c]
+    rho_sum[~has], shepard[~has], out[~has] = 0.0, 0.0, 0.0
+    words = _sphs_summary(has, outside, count, rho_sum, shepard, out)
+    return KernelSamples(h, SPH_KERNELS[kid], grid, dimensions, words, normalise, widths, count, rho_sum, shepard, out)
+
+
+def _sphs_fields(fields):
+    """``fields`` of `frame_samples`, checked: the names of per-particle float fields of the schema, ``(name, width,
+    default)`` each.  The default that stands for a field stored nowhere is one number per field."""
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    if len(names) > _SPHS_MAX_VALUES:
+        raise ValueError("fields holds at most %d names: %d" % (_SPHS_MAX_VALUES, len(names)))
+    out = []
+    for name in names:
+        if not isinstance(name, str) or name not in _PARTICLE_FIELDS:
+            raise ValueError("%r is not a per-particle attribute of ParticleData" % (name,))
+        dt, M, default, _ = _PARTICLE_FIELDS[name]
+        default = numpy.asarray(default).reshape(-1)
+        if numpy.dtype(dt) != numpy.float32 or (default != default[0]).any():
+            raise ValueError("particles/%s is no float field with one default for its columns: it cannot be sampled" % name)
+        out.append((name, int(M), float(default[0])))
+    if sum(M for _, M, _ in out) > _SPHS_MAX_COLUMNS:
+        raise ValueError("the fields hold at most %d columns together: %d" % (_SPHS_MAX_COLUMNS, sum(M for _, M, _ in out)))
+    return out
+
+
+def frame_samples(frame_or_arrays, points, fields=('velocity',), h=None, kernel='wendland_c2', normalise=False, cells=None,
+                  where=None, types=None, domain=None, box=None, dimensions=3):
+    """`sph_samples` of a frame's ``position``, ``mass``, ``density`` and the per-particle float ``fields`` over a
+    selection: the host twin of `HOOMDTrajectory.frame_samples_device`, which equals it exactly.  The selection, the
+    ``h=None`` rule and the refusals are `frame_kernel_sums`'; a field that is stored nowhere is its schema default in
+    every row (a frame at rest has its velocity elided and samples as zeros), a mass 1.0, a density the schema's 0.0.
+    Returns a `KernelSamples`."""
+    asked = _sphs_fields(fields)
+    arrays, position, box, dimensions, h, rows = _sph_frame_list(frame_or_arrays, h, where, types, domain, box, dimensions)
+    N = numpy.asarray(position).size // 3
+    values = []
+    for name, M, default in asked:
+        v = arrays.get(name)
+        if v is None or numpy.asarray(v).size == 0 and N:
+            v = numpy.full((N, M), default, dtype=numpy.float32)
+        values.append(numpy.asarray(v).reshape(N, M))
+    return sph_samples(points, position, box, h, values=values, mass=arrays.get('mass'), density=arrays.get('density'),
+                       rows=rows, cells=cells, dimensions=dimensions, kernel=kernel, normalise=normalise)
 
 
 def frame_moments(frame_or_arrays, by_type=True, centre=True, where=None, types=None, domain=None, box=None, dimensions=3):
@@ -4800,6 +5098,39 @@ class HOOMDTrajectory(object):
                                              mass=chunks[0], density=chunks[1], pressure=chunks[3],
                                              defaults=defaults + [float(_PARTICLE_FIELDS['pressure'][2])], viscosity=mu,
                                              gravity=g, dimensions=dims, kernel=kernel, return_rows=return_rows)
+        finally:
+            f.wait_read()
+        return got
+
+    def frame_samples(self, idx, points, fields=('velocity',), h=None, kernel='wendland_c2', normalise=False, cells=None,
+                      where=None, domain=None):
+        """`frame_samples` of frame ``idx`` read through the host path: a `KernelSamples`.  The definition of
+        `frame_samples_device`."""
+        return frame_samples(self[int(idx)], points, fields=fields, h=h, kernel=kernel, normalise=normalise, cells=cells,
+                             where=where, domain=domain)
+
+    def frame_samples_device(self, idx, points, fields=('velocity',), h=None, kernel='wendland_c2', normalise=False,
+                             cells=None, where=None, domain=None):
+        """`frame_samples` of frame ``idx``, on the GPU: a `KernelSamples` that equals ``frame_samples(idx, points, ...)``
+        exactly -- every counter and index, every float bit for bit -- with ``count``, ``density``, ``shepard`` and
+        ``values`` in GPU memory.
+
+        ``points`` is a numpy array (uploaded) or ``K x 3`` float64 values in GPU memory.  ``h=None``, the selection, the
+        grid and the ordering are `frame_kernel_sums_device`'s; the pass (`pgsd.fl.PGSDFile.sph_samples_device`) runs
+        over the staged position chunk and the effective ``mass`` and ``density`` chunks and those of ``fields``; one that
+        is stored nowhere costs nothing: its schema default stands for every row.  One `wait_read` at the end releases the
+        staged chunks.  A frame whose position is stored nowhere has no chunk to search and raises ValueError.
+        """
+        f = self.file
+        try:
+            asked = _sphs_fields(fields)
+            f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults = self._sph_device_list(
+                "frame_samples_device", idx, h, kernel, cells, where, domain,
+                ('mass', 'density') + tuple(name for name, _, _ in asked))
+            values = [(chunk, M, default) for chunk, (_, M, default) in zip(chunks[2:], asked)]
+            got = f.sph_samples_device(f_pos, 'particles/position', box, h, grid, rows, cell, points, n=count, values=values,
+                                       mass=chunks[0], density=chunks[1], defaults=defaults, dimensions=dims, kernel=kernel,
+                                       normalise=normalise)
         finally:
             f.wait_read()
         return got

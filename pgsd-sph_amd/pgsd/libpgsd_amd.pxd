@@ -268,6 +268,13 @@ cdef extern from "pgsd_private.h" nogil:
                                       uint32_t dimensions, const uint32_t* cells, double viscosity, const double* gravity,
                                       const uint32_t* rows, const int32_t* cell, uint64_t n, double* out_pressure_acc,
                                       double* out_viscous_acc, double* out_total, uint64_t* out_summary)
+    int pgsd_sph_samples_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* mass,
+                                const pgsd_index_entry* density, const pgsd_index_entry* const* values,
+                                const uint32_t* value_columns, const double* value_defaults, const double* defaults,
+                                const float* box, const double* vectors, double h, uint32_t kernel, uint32_t dimensions,
+                                const uint32_t* cells, const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                const double* points, uint64_t K, uint32_t normalise, uint32_t* out_count,
+                                double* out_density, double* out_shepard, double* out_values, uint64_t* out_summary)
     int pgsd_chunk_stats_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
                                 uint32_t with_norm2, uint64_t* out_counts, double* out_values)
     int pgsd_read_rows_device(pgsd_handle* handle, const pgsd_index_entry* chunk, const uint32_t* rows, uint64_t n,
