@@ -216,6 +216,7 @@ int DevicePipeline::init()
         warm_sph_gradients_kernels();
         warm_sph_forces_kernels();
         warm_sph_samples_kernels();
+        warm_sph_body_kernels();
         int brc = compare_buffers();
         if (brc != PGSD_SUCCESS)
             return brc;

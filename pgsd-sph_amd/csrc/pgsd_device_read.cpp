@@ -449,7 +449,7 @@ int DevicePipeline::stage_present(const ChunkRange* ranges, const void** const* 
 // wait_read for an indexed read of the same chunk --; where the pass writes or reads memory of the caller's on the device
 // (`callers_memory`: a row list, shifts), what the caller's stream still does with that memory comes first;
 // `launch(stream, why)` launches on the pack stream, synchronises it and returns a pgsd_error; a PGSD_ERROR_DEVICE fails
-// the pipeline with the launcher's message.  The message of a failure, for all eighteen passes: the launcher's own first,
+// the pipeline with the launcher's message.  The message of a failure, for all nineteen passes: the launcher's own first,
 // else the pipeline's, else the thread's last error.
 template<class Launch>
 int DevicePipeline::staged_launch(const ChunkRange* ranges, const void** const* slots, size_t n, uint32_t present, uint64_t N,
@@ -643,6 +643,17 @@ int device_pipeline_sph_accelerations(DevicePipeline* p, const ChunkRange* range
     return p->staged_launch(ranges, slots, 5, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
                             { return launch_sph_accelerations(a, out_pressure_acc, out_viscous_acc, out_total, out_summary,
                                                               stream, why); });
+    }
+
+// SPH body forces: the accelerations' five slots; both lists read the same staged chunks
+int device_pipeline_sph_body_force(DevicePipeline* p, const ChunkRange* ranges, const SphBodyArgs& args, uint32_t* out_contacts,
+                                   double* out_pressure_acc, double* out_viscous_acc, uint64_t* out_summary, std::string* err)
+    {
+    SphBodyArgs a = args;
+    const void** const slots[5] = {&a.pos, &a.mass, &a.density, &a.velocity, &a.pressure};
+    return p->staged_launch(ranges, slots, 5, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                            { return launch_sph_body_force(a, out_contacts, out_pressure_acc, out_viscous_acc, out_summary,
+                                                           stream, why); });
     }
 
 // SPH samples: the position, mass and density chunks as the sums take them and up to four value chunks where they are

@@ -43,6 +43,7 @@ int device_pipeline_neighbours(DevicePipeline*, long long, size_t, const Neighbo
 int device_pipeline_sph_sums(DevicePipeline*, const ChunkRange*, const SphArgs&, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_gradients(DevicePipeline*, const ChunkRange*, const SphGradientsArgs&, double*, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_accelerations(DevicePipeline*, const ChunkRange*, const SphForcesArgs&, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
+int device_pipeline_sph_body_force(DevicePipeline*, const ChunkRange*, const SphBodyArgs&, uint32_t*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_samples(DevicePipeline*, const ChunkRange*, const SphSamplesArgs&, uint32_t*, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_neighbour_offsets(DevicePipeline*, long long, size_t, const NeighbourListArgs&, uint64_t*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_neighbour_list(DevicePipeline*, long long, size_t, const NeighbourListArgs&, const uint64_t*, uint64_t, uint32_t*, double*, std::string*) { return PGSD_ERROR_NO_DEVICE; }

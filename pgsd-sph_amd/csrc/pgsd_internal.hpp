@@ -591,6 +591,35 @@ inline void sph_forces_of_nothing(uint64_t* out_summary)
 int device_pipeline_sph_accelerations(DevicePipeline*, const ChunkRange* ranges, const SphForcesArgs& a,
                                       double* out_pressure_acc, double* out_viscous_acc, double* out_total,
                                       uint64_t* out_summary, std::string* err);
+// SPH body forces (pgsd.hoomd.sph_body_force is the definition): a pair pass between two row lists in cell order on one
+// grid -- the targets (the body: rows, cell and n of SphArgs) and the sources (the fluid) -- and over the targets the
+// ordered sums of the force m_b * acc_b and of the torque r_b x it about a point.  The grid, the support, the columns,
+// their defaults and the per-pair arithmetic are SphForcesArgs' (gravity is not looked at).
+enum
+    {
+    SPHB_SUMMARY_WORDS = 22, // n_t, targets nowhere, n_s, sources nowhere, wetted, pairs, bad, largest (at, row, fp2), 12 sums
+    SPHB_TILE = 4096         // entries of one tile of the ordered sum (pgsd.hoomd._ordered_sum)
+    };
+struct SphBodyArgs : SphForcesArgs
+    {
+    const uint32_t* fluid_rows; // device, n_fluid entries in cell order
+    const int32_t* fluid_cell;  // device, n_fluid ids, non-decreasing, in [0, n_cells]
+    uint64_t n_fluid;
+    double about[3];            // the point the torque is taken about
+    };
+// the summary of no target: n_fluid sources, none of them looked at
+inline void sph_body_force_of_nothing(uint64_t n_fluid, uint64_t* out_summary)
+    {
+    std::fill(out_summary, out_summary + SPHB_SUMMARY_WORDS, (uint64_t)0); // (+0.0 is the zero word)
+    out_summary[2] = n_fluid;
+    out_summary[7] = out_summary[8] = (uint64_t)SPH_NONE;
+    }
+// stage the chunks that are present (ranges[0 .. 4] as device_pipeline_sph_accelerations; both lists read the same staged
+// chunks), check both lists, sum on the GPU; out_contacts (device, a.n words), out_pressure_acc, out_viscous_acc (device,
+// a.n x 3, the second written with a.viscous only), each or null; out_summary (host, 22 words) is written on success
+// only, and so are the device outputs; synchronous.  The refusals and the staging are device_pipeline_sph_sums'.
+int device_pipeline_sph_body_force(DevicePipeline*, const ChunkRange* ranges, const SphBodyArgs& a, uint32_t* out_contacts,
+                                   double* out_pressure_acc, double* out_viscous_acc, uint64_t* out_summary, std::string* err);
 // SPH samples (pgsd.hoomd.sph_samples is the definition): per point of the caller's choosing the entries of a row list in
 // cell order strictly inside the support 2h of it, the density sigma * sum m_j w, the Shepard sum sigma * sum V_j w and per
 // value column sigma * sum V_j w f_j (or, normalised, sum V_j w f_j / sum V_j w), in the sums' order around the point's

@@ -349,6 +349,16 @@ int launch_sph_accelerations(const SphForcesArgs& a, double* out_pressure_acc, d
 int launch_sph_samples(const SphSamplesArgs& a, uint32_t* out_count, double* out_density, double* out_shepard,
                        double* out_values, uint64_t* out_summary, hipStream_t stream, std::string* err);
 
+// SPH body forces (pgsd_sph_body.hip; SphBodyArgs, the chunk pointers filled in): check and offsets of both lists, the
+// accelerations' compaction of each, one lane per target over the sources in the sums' order around the target's cell
+// (pgsd_traverse.hpp), the per-target force and torque terms into a table, the table's ordered sums (tiles of 4096, then
+// one workgroup).  out_contacts (device, a.n), out_pressure_acc, out_viscous_acc (device, a.n x 3), each or null;
+// out_summary (host, 22 words) is written on success only.  a.n == 0 launches nothing; a.n_fluid == 0 still runs.
+// Synchronises `stream`; PGSD_ERROR_INVALID_ARGUMENT for an id of either list that descends or lies outside [0, n_cells]
+// and for an entry >= a.N
+int launch_sph_body_force(const SphBodyArgs& a, uint32_t* out_contacts, double* out_pressure_acc, double* out_viscous_acc,
+                          uint64_t* out_summary, hipStream_t stream, std::string* err);
+
 // mark -> one-block scan -> remap of a row plan (pgsd_internal.hpp) on `stream`; synchronises it and fills in the plan's
 // host side (touched blocks, runs, staged_rows) and rows2 (device)
 int launch_row_plan(RowPlan& plan, hipStream_t stream, std::string* err);
@@ -413,6 +423,7 @@ void warm_sph_kernels();
 void warm_sph_gradients_kernels();
 void warm_sph_forces_kernels();
 void warm_sph_samples_kernels();
+void warm_sph_body_kernels();
 
 // algorithmic traffic of one job: bytes that must be read (needed columns only, plus the
 // gather index) and chunk bytes written

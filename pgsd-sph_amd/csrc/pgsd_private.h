@@ -63,6 +63,9 @@
  *                     pgsd_sph_samples_device (pgsd.fl's sph_samples_device, behind pgsd.hoomd's frame_samples_device:
  *                     the SPH interpolant of the same list at points of the caller's choosing -- a gauge, a line, a
  *                     slice, a grid to render --, the same candidates in the same order around the point's cell)
+ *                     pgsd_sph_body_force_device (pgsd.fl's sph_body_force_device, behind pgsd.hoomd's
+ *                     frame_body_force_device: the force and the torque the fluid exerts on a body -- a pair pass
+ *                     between two lists in cell order on one grid and the ordered sums over the targets)
  *                     pgsd_row_plan_create / _destroy / _query, pgsd_read_rows_planned_device,
  *                     pgsd_device_read_counters (pgsd.fl's plan_rows, read_chunk_device(rows=plan) and
  *                     device_read_stats, behind pgsd.hoomd's read_tracks_device: a few particles through many frames,
@@ -570,6 +573,52 @@ extern "C"
                                       const double gravity[3], const uint32_t* rows, const int32_t* cell, uint64_t n,
                                       double* out_pressure_acc, double* out_viscous_acc, double* out_total,
                                       uint64_t* out_summary);
+
+    /* SPH body forces: the force and the torque the fluid exerts on a body (pgsd.hoomd.sph_body_force is the definition,
+       and the results equal it exactly: every counter and index, every float bit for bit -- a NaN is a NaN).  A pair pass
+       between TWO row lists in cell order on one grid: the targets b (body_rows, body_cell, n_body) and the sources f
+       (fluid_rows, fluid_cell, n_fluid), each checked and given offsets of its own; a row may occur in both, which is not
+       detected.  position, velocity, mass, density, pressure, defaults, vectors, h, kernel, dimensions, cells and
+       viscosity are pgsd_sph_accelerations_device's, and so are the grid, the support 2h, r2, inv_h, sigma, G, eta2, Gv,
+       A_k, V_k and F(q).  about: the point the torque is taken about.
+       THE CANDIDATES of target b: the sources in the cells of the sums' order around b's cell, looked up in the sources'
+       offsets, inside a cell in ascending position in the sources' list; d = x_f - x_b under the single-shift minimum
+       image, the test d2 < r2 is strict.  Entries of either list with id n_cells are nowhere and take no part.
+       ONE PAIR b <- f, float64, no contraction: the accelerations' arithmetic with i = b and j = f;
+           contacts[b] += 1, a_p[k] += m_f * ((A_b + A_f) * e_k), and with a viscosity a_v[k] += V_f * (K * (v_f[k] - v_b[k])).
+       After the last candidate pressure_acc[k] = -(G * a_p[k]), viscous_acc[k] = (Gv * a_v[k]) / rho_b; no gravity enters.
+       A target nowhere has every value +0.0.
+       PER TARGET, one rounding per operation: fp[k] = m_b * pressure_acc[k], fv[k] = m_b * viscous_acc[k]; the arm r = x_b
+       - about under the single-shift minimum image (z, then y, then x; r_z = 0 with dimensions == 2);
+           tp = (r1*fp2 - r2*fp1, r2*fp0 - r0*fp2, r0*fp1 - r1*fp0), tv likewise.
+       A target with a cell is BAD if any of its six or twelve terms is NaN or infinite: all its terms count as +0.0.
+       THE SUMS: each column over the targets' list positions (nowhere: +0.0) in tiles of 4096 -- lane k % 256 adds its 16
+       steps in order, then the halvings 32 .. 1 inside each run of 64 lanes and (w0 + w1) + (w2 + w3) --, over the
+       tiles lane t adds tiles t, t + 256, ... and then the same tree (pgsd.hoomd._ordered_sum).
+       Device outputs, each optional (NULL): out_contacts (n_body uint32), out_pressure_acc, out_viscous_acc (n_body x 3
+       float64; the second is not written without a viscosity).
+       Host output, 22 words:
+           out_summary[0 .. 3]    n_body; the targets nowhere; n_fluid; the sources nowhere
+           out_summary[4 .. 6]    wetted: the targets with a cell and contacts >= 1; pairs: the sum of contacts; bad
+           out_summary[7 .. 9]    the list position, the row and as a float64 bit pattern the largest (fp0*fp0 + fp1*fp1) +
+                                  fp2*fp2 over the targets with a cell that are not bad, the smaller position on a tie,
+                                  a NaN never; 0xFFFFFFFF, 0xFFFFFFFF and +0.0 without one
+           out_summary[10 .. 21]  as float64 bit patterns force_pressure[3], force_viscous[3], torque_pressure[3],
+                                  torque_viscous[3]; the viscous six are +0.0 without a viscosity
+       n_body == 0 launches nothing: the summary is n_fluid in word 2, 0xFFFFFFFF in words 7 and 8 and zeros (no source
+       is looked at).  n_fluid == 0 still runs: every target is dry and every sum +0.0.  Staging and synchronisation are
+       pgsd_sph_sums_device's; both lists read the same staged chunks.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), every output as it was: everything
+       pgsd_sph_accelerations_device refuses, for either list; an about component that is not finite. */
+    int pgsd_sph_body_force_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                   const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
+                                   const struct pgsd_index_entry* density, const struct pgsd_index_entry* pressure,
+                                   const double defaults[3], const double vectors[6], double h, uint32_t kernel,
+                                   uint32_t dimensions, const uint32_t cells[3], double viscosity, const double about[3],
+                                   const uint32_t* body_rows, const int32_t* body_cell, uint64_t n_body,
+                                   const uint32_t* fluid_rows, const int32_t* fluid_cell, uint64_t n_fluid,
+                                   uint32_t* out_contacts, double* out_pressure_acc, double* out_viscous_acc,
+                                   uint64_t* out_summary);
 
     /* SPH samples (pgsd.hoomd.sph_samples is the definition, and the results equal it exactly: every counter and index,
        every float bit for bit -- a NaN is a NaN): the SPH interpolant of a row list at K points of the caller's choosing,

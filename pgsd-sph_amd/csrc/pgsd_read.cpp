@@ -1479,6 +1479,67 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_sph_body_force_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                          const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
+                                          const struct pgsd_index_entry* density, const struct pgsd_index_entry* pressure,
+                                          const double defaults[3], const double vectors[6], double h, uint32_t kernel,
+                                          uint32_t dimensions, const uint32_t cells[3], double viscosity, const double about[3],
+                                          const uint32_t* body_rows, const int32_t* body_cell, uint64_t n_body,
+                                          const uint32_t* fluid_rows, const int32_t* fluid_cell, uint64_t n_fluid,
+                                          uint32_t* out_contacts, double* out_pressure_acc, double* out_viscous_acc,
+                                          uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_sph_body_force_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !defaults || !vectors || !cells || !about || !out_summary || (n_body > 0 && (!body_rows || !body_cell))
+        || (n_fluid > 0 && (!fluid_rows || !fluid_cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    ChunkRange ranges[5];
+    SphForcesArgs g;
+    // (the chunks are checked against the longer list: a list of entries into chunks of no row is refused for either)
+    const bool body_longer = n_body >= n_fluid;
+    int rc = sph_arguments(who, s, handle, position, mass, density, velocity, pressure, defaults, vectors, h, kernel, dimensions,
+                           cells, body_longer ? body_rows : fluid_rows, body_longer ? body_cell : fluid_cell,
+                           body_longer ? n_body : n_fluid, NAN, ranges, g);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (!(viscosity < HUGE_VAL && viscosity > -HUGE_VAL))
+        return refuse("the viscosity must be finite (negative: no viscous term)");
+    for (int k = 0; k < 3; k++)
+        if (!(about[k] < HUGE_VAL && about[k] > -HUGE_VAL))
+            return refuse("about must hold three finite components");
+    SphBodyArgs a = SphBodyArgs();
+    static_cast<SphForcesArgs&>(a) = g;
+    a.rows = body_rows;
+    a.cell = body_cell;
+    a.n = n_body;
+    a.fluid_rows = fluid_rows;
+    a.fluid_cell = fluid_cell;
+    a.n_fluid = n_fluid;
+    // host arithmetic in float64, formed once
+    a.pressure_default = defaults[2];
+    a.viscous = viscosity >= 0.0 ? 1u : 0u;
+    a.eta2 = (0.01 * h) * h;
+    a.Gv = a.viscous ? a.G * (2.0 * viscosity) : 0.0;
+    std::fill(a.gravity, a.gravity + 3, 0.0);
+    std::copy(about, about + 3, a.about);
+    if (n_body == 0)
+        {
+        sph_body_force_of_nothing(n_fluid, out_summary);
+        return PGSD_SUCCESS;
+        }
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "SPH body forces: ", [&](std::string* err)
+                          { return device_pipeline_sph_body_force(s->dev, ranges, a, out_contacts, out_pressure_acc,
+                                                                  out_viscous_acc, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_frame_displacements_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position_a,
                                                const struct pgsd_index_entry* image_a,
                                                const struct pgsd_index_entry* position_b,

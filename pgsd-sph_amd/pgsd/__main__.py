@@ -46,7 +46,12 @@
            grid, the points nowhere, outside, empty and not finite, the largest count, the ranges of the density and of
            the Shepard sum and per sampled column the smallest and largest value (``--fields a,b``: the per-particle
            fields sampled, default velocity; ``--normalise``: values divided by the Shepard sum; ``--kernel``,
-           ``--types``; ``pgsd.hoomd.frame_samples`` on the host: no GPU).
+           ``--types``; ``pgsd.hoomd.frame_samples`` on the host: no GPU);
+           ``--body-force TYPE[,TYPE...] --fluid TYPE[,TYPE...] [H]`` adds the force and the torque the particles of the
+           ``--fluid`` types exert on those of the ``--body-force`` types for the smoothing length H (without H: the
+           frame's uniform ``slength``): the search grid, the counters, the pressure and the viscous force and torque and
+           their sums and the largest pressure force on one particle with its row (``--viscosity MU``, ``--about X,Y,Z``:
+           the point the torque is taken about, ``--kernel``; ``pgsd.hoomd.frame_body_force`` on the host: no GPU).
 ``vtu``    every frame as a VTK ``.vtu`` file plus a ``.pvd`` collection (``pgsd.vtu``); ``--types`` keeps the
            particles of the named types only.
 """
@@ -127,6 +132,41 @@ def _cmd_info(args):
         _print_sph_forces(args, frame)
     if args.sample is not None:
         _print_sample(args, frame)
+    if args.body_force is not None or args.fluid is not None:
+        _print_body_force(args, frame)
+
+
+def _print_body_force(args, frame):
+    """``info --body-force``: `pgsd.hoomd.frame_body_force` of one frame, on the host."""
+    from . import hoomd
+    if args.body_force is None or args.fluid is None:
+        raise ValueError("--body-force TYPE[,TYPE...] and --fluid TYPE[,TYPE...] [H] go together")
+    try:
+        h = float(args.fluid[1]) if len(args.fluid) > 1 else None
+        if len(args.fluid) > 2:
+            raise ValueError
+    except ValueError:
+        raise ValueError("--fluid takes TYPE[,TYPE...] [H]: %r" % ' '.join(args.fluid))
+    about = None
+    if args.about is not None:
+        try:
+            about = [float(v) for v in args.about.split(',')]
+        except ValueError:
+            raise ValueError("--about takes X,Y,Z: %r" % args.about)
+    body = {'type': [t for t in args.body_force.split(',') if t]}
+    fluid = {'type': [t for t in args.fluid[0].split(',') if t]}
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_body_force(traj[frame], body, fluid, h, kernel=args.kernel, viscosity=args.viscosity, about=about)
+    print("SPH body force of frame %d with h = %r (%s) over %d x %d x %d cells (body %s, fluid %s):"
+          % ((frame, m.h, m.kernel) + m.grid + (args.body_force, args.fluid[0])))
+    print("  targets:      %d  nowhere: %d  wetted: %d  bad: %d" % (m.n, m.nowhere, m.wetted, m.bad))
+    print("  sources:      %d  nowhere: %d  pairs: %d" % (m.n_sources, m.sources_nowhere, m.pairs))
+    print("  viscosity:    %s  about: %r %r %r" % (("%r" % m.viscosity if m.viscosity is not None else "none",) + m.about))
+    for label, v in (('force:', m.force), ('  pressure:', m.force_pressure), ('  viscous:', m.force_viscous),
+                     ('torque:', m.torque), ('  pressure:', m.torque_pressure), ('  viscous:', m.torque_viscous)):
+        print("  %-13s %r %r %r" % ((label,) + tuple(v)))
+    if m.largest2 is not None:
+        print("  largest:      %r at row %d (the pressure force on one particle)" % (m.largest2 ** 0.5, m.largest_row))
 
 
 def _print_sample(args, frame):
@@ -495,7 +535,8 @@ def main(argv=None):
                    help="print the SPH accelerations for the smoothing length H (without H: the frame's uniform slength): "
                         "grid, entries, the largest total, pressure and viscous acceleration and the force time step")
     p.add_argument('--viscosity', type=float, default=None, metavar='MU',
-                   help="with --sph-forces: the dynamic viscosity of the laminar viscous term (default: no viscous term)")
+                   help="with --sph-forces and --body-force: the dynamic viscosity of the laminar viscous term (default: no "
+                        "viscous term)")
     p.add_argument('--gravity', type=str, default=None, metavar='GX,GY,GZ',
                    help="with --sph-forces: the gravity (default: 0,0,0; write --gravity=-1,0,0 where GX is negative)")
     p.add_argument('--sample', type=str, nargs='+', default=None, metavar=('NX,NY,NZ', 'H'),
@@ -503,8 +544,17 @@ def main(argv=None):
                         "length H (without H: the frame's uniform slength): the points nowhere, outside and empty, the "
                         "largest count and the ranges of density, Shepard sum and the sampled fields")
     p.add_argument('--normalise', action='store_true', help="with --sample: divide every value by the Shepard sum")
+    p.add_argument('--body-force', type=str, default=None, metavar='TYPE[,TYPE...]',
+                   help="with --fluid: print the force and the torque the fluid's particles exert on the particles of these "
+                        "types: counters, pressure and viscous parts, their sums, the largest particle force")
+    p.add_argument('--fluid', type=str, nargs='+', default=None, metavar=('TYPE[,TYPE...]', 'H'),
+                   help="with --body-force: the types of the fluid and the smoothing length H (without H: the frame's "
+                        "uniform slength)")
+    p.add_argument('--about', type=str, default=None, metavar='X,Y,Z',
+                   help="with --body-force: the point the torque is taken about (default: 0,0,0; write --about=-1,0,0 "
+                        "where X is negative)")
     p.add_argument('--kernel', type=str, default='wendland_c2', choices=('wendland_c2', 'cubic_spline'),
-                   help="the kernel of --sph, --sph-gradients, --sph-forces and --sample (default: wendland_c2)")
+                   help="the kernel of --sph, --sph-gradients, --sph-forces, --sample and --body-force (default: wendland_c2)")
     p.add_argument('--surface', type=float, default=None, metavar='S',
                    help="with --sph: count the entries whose Shepard sum is below S (the free surface)")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")

@@ -656,6 +656,20 @@ def _sample_points(who, points):
     return None, points, shape[0]
 
 
+def _body_terms(who, viscosity, about):
+    """(``mu`` as a float or ``None``, ``about`` as float64[3]) of :meth:`PGSDFile.sph_body_force_device`, checked."""
+    mu = None
+    if viscosity is not None:
+        mu = float(viscosity)
+        if not 0.0 <= mu < float('inf'):
+            raise ValueError("%s: viscosity is a finite number, at least 0, or None: %r" % (who, viscosity))
+    c_about = numpy.ascontiguousarray(
+        numpy.array([0.0, 0.0, 0.0] if about is None else about, dtype=numpy.float64).reshape(-1))
+    if c_about.shape[0] != 3 or not numpy.isfinite(c_about).all():
+        raise ValueError("%s: about holds three finite numbers, or is None" % who)
+    return mu, c_about
+
+
 def _moments_defaults(who, defaults):
     """The row that stands for every row of a chunk stored nowhere -- mass, v[3], energy, x[3] -- as float64[8]."""
     c_defaults = numpy.ascontiguousarray(
@@ -2350,6 +2364,78 @@ cdef class PGSDFile:
         if return_rows:
             got.rows, got.cell = _device_head(rows, count), _device_head(cell, count)
             got.pressure_acc, got.total = _device_head_rows(out_pacc, count), _device_head_rows(out_total, count)
+            if mu is not None:
+                got.viscous_acc = _device_head_rows(out_vacc, count)
+        return got
+
+    def sph_body_force_device(self, frame, name, box, h, cells, body_rows, body_cell, fluid_rows, fluid_cell, n_body=None,
+                              n_fluid=None, velocity=None, mass=None, density=None, pressure=None, defaults=None,
+                              viscosity=None, about=None, dimensions=3, kernel='wendland_c2', return_rows=False):
+        """The force and the torque the fluid exerts on a body, on the GPU: a pair pass between two row lists in cell order
+        on one grid -- the targets (the body) and the sources (the fluid) -- and the ordered sums of the targets' force and
+        torque terms.
+
+        Args:
+            frame, name, box, h, cells, velocity, mass, density, pressure, defaults, viscosity, dimensions, kernel: as
+                :meth:`sph_accelerations_device` takes them.
+            body_rows, body_cell, n_body: the targets -- a row list in GPU memory in cell order
+                (:meth:`order_rows_by_cell_device`), its ids and its entries (``None``: all of ``body_rows``).
+            fluid_rows, fluid_cell, n_fluid: the sources, likewise, ordered on the same grid.
+            about: three finite floats, the point the torque is taken about; ``None``: ``(0, 0, 0)``.
+            return_rows (bool): keep the per-target results in GPU memory.
+
+        Returns:
+            A :class:`pgsd.hoomd.KernelBodyForce`: exactly :func:`pgsd.hoomd.sph_body_force` of the same lists -- every
+            counter and index, every float bit for bit.  With ``return_rows`` its ``rows`` and ``cell`` are the targets'
+            arguments and ``contacts`` (uint32, ``n``), ``pressure_acc`` and ``viscous_acc`` (float64, ``n x 3``; ``None``
+            without a viscosity) are arrays in GPU memory; otherwise the five are ``None``.  The chunks are staged whole
+            unless an earlier call left them staged; the staged rows are kept until the next :meth:`wait_read`.  What
+            the library refuses (:c:func:`pgsd_sph_body_force_device`) raises ValueError and computes nothing.  Needs no
+            tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry, e_velocity, e_mass, e_density, e_pressure
+        self._entry(frame, name, &entry)
+        cdef const C.pgsd_index_entry* p_velocity = self._optional(velocity, &e_velocity)
+        cdef const C.pgsd_index_entry* p_mass = self._optional(mass, &e_mass)
+        cdef const C.pgsd_index_entry* p_density = self._optional(density, &e_density)
+        cdef const C.pgsd_index_entry* p_pressure = self._optional(pressure, &e_pressure)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("sph_body_force_device", cells)
+        cdef uint32_t c_kernel = _sph_kernel("sph_body_force_device", kernel)
+        c_defaults = _force_defaults("sph_body_force_device", defaults)
+        mu, c_about = _body_terms("sph_body_force_device", viscosity, about)
+        c_rows, c_cell, count = _cell_ordered_lists("sph_body_force_device", body_rows, body_cell, n_body)
+        c_rows2, c_cell2, count2 = _cell_ordered_lists("sph_body_force_device", fluid_rows, fluid_cell, n_fluid)
+        summary = numpy.zeros(22, dtype=numpy.uint64)
+        cdef uintptr_t p_contacts, p_pacc, p_vacc
+        device = self.pipeline_device() if return_rows else None
+        out_contacts, p_contacts = _per_entry(count, (), numpy.uint32, device)
+        out_pacc, p_pacc = _per_entry(count, (3,), numpy.float64, device)
+        out_vacc, p_vacc = _per_entry(count, (3,), numpy.float64, device if mu is not None else None)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of the lists
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_rows2 = c_rows2, p_cell2 = c_cell2
+        cdef uintptr_t p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data, p_about = c_about.ctypes.data
+        cdef uint64_t c_n = count, c_n2 = count2
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef double c_h = float(h), c_mu = -1.0 if mu is None else mu
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_sph_body_force_device(&self._handle, &entry, p_velocity, p_mass, p_density, p_pressure,
+                                                  <const double*>p_defaults, <const double*>p_vectors, c_h, c_kernel, c_dims,
+                                                  <const uint32_t*>p_cells, c_mu, <const double*>p_about,
+                                                  <const uint32_t*>p_rows, <const int32_t*>p_cell, c_n,
+                                                  <const uint32_t*>p_rows2, <const int32_t*>p_cell2, c_n2,
+                                                  <uint32_t*>p_contacts, <double*>p_pacc, <double*>p_vacc,
+                                                  <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("sph_body_force_device", retval, "refused", self._name, err)
+        got = _hoomd.KernelBodyForce(c_h, kernel, grid, int(dimensions), summary, mu, tuple(c_about.tolist()))
+        if return_rows:
+            got.rows, got.cell = _device_head(body_rows, count), _device_head(body_cell, count)
+            got.contacts, got.pressure_acc = _device_head(out_contacts, count), _device_head_rows(out_pacc, count)
             if mu is not None:
                 got.viscous_acc = _device_head_rows(out_vacc, count)
         return got

@@ -2691,8 +2691,242 @@ def frame_accelerations(frame_or_arrays, h=None, kernel='wendland_c2', viscosity
                              dimensions=dimensions, kernel=kernel)
 
 
+# ---- SPH body forces: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_body_force_device`) equals exactly
+_SPHB_SUMMARY_WORDS = 22    # n_t, targets nowhere, n_s, sources nowhere, wetted, pairs, bad, largest (at, row, fp2), 12 sums
+_SPHB_PARTS = ('force_pressure', 'force_viscous', 'torque_pressure', 'torque_viscous')
+
+
+def _sph_about(about):
+    """``about`` as three finite floats; ``None``: ``(0.0, 0.0, 0.0)``."""
+    c = numpy.array([0.0, 0.0, 0.0] if about is None else about, dtype=numpy.float64).reshape(-1)
+    if c.shape[0] != 3 or not numpy.isfinite(c).all():
+        raise ValueError("about holds three finite numbers, or is None")
+    return tuple(float(v) for v in c)
+
+
+class KernelBodyForce(object):
+    """The force and torque a fluid exerts on a body (`sph_body_force`): two lists in cell order on one grid, the
+    *targets* (the body) and the *sources* (the fluid).
+
+    Attributes:
+        h (float), kernel (str), grid (``(cx, cy, cz)``), dimensions (int), viscosity (float or ``None``), about (three
+            floats): what was asked; G (float): `sph_gradient_scale`.
+        rows, cell: the targets in cell order and their cell ids (``n_cells``: nowhere).
+        contacts (uint32, ``n``), pressure_acc, viscous_acc (float64, ``n x 3``): per target, in list order, the sources
+            inside ``2h`` and the accelerations they cause; ``+0.0`` for a target nowhere.  ``viscous_acc`` is ``None``
+            without a viscosity.  Numpy arrays from the model; from the GPU ``None`` unless ``return_rows`` left them in
+            GPU memory.
+        n, nowhere, n_sources, sources_nowhere (int): the targets and the sources, and those of each without a cell.
+        wetted (int): the targets that have a cell and at least one contact; pairs (int): the sum of ``contacts``.
+        bad (int): the targets that have a cell and one of whose force or torque terms is NaN or infinite; they count as
+            ``+0.0`` in every sum.
+        force_pressure, force_viscous, torque_pressure, torque_viscous (three floats each): the ordered sums of ``m_b *
+            pressure_acc_b``, ``m_b * viscous_acc_b`` and of ``r_b x`` each over the targets, ``r_b`` the minimum-image
+            arm from ``about``; the viscous parts are ``+0.0`` without a viscosity.
+        force, torque (three floats each): the pressure part plus the viscous part per component.
+        largest2, largest_at, largest_row: the largest ``(fp0*fp0 + fp1*fp1) + fp2*fp2`` of the pressure force of one
+            target that has a cell and is not bad, its list position (the smaller one on a tie, a NaN never counts) and
+            its row; ``None`` without such a target.
+    """
+
+    __slots__ = ('h', 'kernel', 'grid', 'dimensions', 'viscosity', 'about', 'G', 'rows', 'cell', 'contacts', 'pressure_acc',
+                 'viscous_acc', 'n', 'nowhere', 'n_sources', 'sources_nowhere', 'wetted', 'pairs', 'bad', 'force_pressure',
+                 'force_viscous', 'torque_pressure', 'torque_viscous', 'force', 'torque', 'largest2', 'largest_at',
+                 'largest_row', '_words')
+
+    def __init__(self, h, kernel, grid, dimensions, summary, viscosity=None, about=None, rows=None, cell=None, contacts=None,
+                 pressure_acc=None, viscous_acc=None):
+        """``summary``: the 22 uint64 words of `pgsd_sph_body_force_device` -- the targets, those nowhere, the sources,
+        those nowhere, wetted, pairs, bad, the list position, the row and as a float64 bit pattern the squared norm of
+        the largest pressure force, then as bit patterns the twelve sums."""
+        s = numpy.ascontiguousarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _SPHB_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _SPHB_SUMMARY_WORDS)
+        self._words = s.copy()
+        self.h, self.kernel, self.dimensions = float(h), kernel, int(dimensions)
+        self.viscosity, self.about = _sph_viscosity(viscosity), _sph_about(about)
+        self.G = sph_gradient_scale(kernel, h, dimensions)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.n, self.nowhere, self.n_sources, self.sources_nowhere = int(s[0]), int(s[1]), int(s[2]), int(s[3])
+        self.wetted, self.pairs, self.bad = int(s[4]), int(s[5]), int(s[6])
+        found = int(s[7]) != _NEIGHBOURS_NONE
+        self.largest_at = int(s[7]) if found else None
+        self.largest_row = int(s[8]) if found else None
+        self.largest2 = float(s[9:10].view(numpy.float64)[0]) if found else None
+        f = s[10:22].view(numpy.float64)
+        for k, name in enumerate(_SPHB_PARTS):
+            setattr(self, name, tuple(float(v) for v in f[3 * k:3 * k + 3]))
+        with numpy.errstate(invalid='ignore', over='ignore'):
+            self.force = tuple(float(numpy.float64(a) + numpy.float64(b)) for a, b in zip(self.force_pressure, self.force_viscous))
+            self.torque = tuple(float(numpy.float64(a) + numpy.float64(b))
+                                for a, b in zip(self.torque_pressure, self.torque_viscous))
+        self.rows, self.cell = rows, cell
+        self.contacts, self.pressure_acc, self.viscous_acc = contacts, pressure_acc, viscous_acc
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return self._words.copy()
+
+    def __repr__(self):
+        return "KernelBodyForce(h=%r, kernel=%r, grid=%r, n=%d, nowhere=%d, n_sources=%d, wetted=%d, pairs=%d, bad=%d, " \
+            "force=%r, torque=%r)" % (self.h, self.kernel, self.grid, self.n, self.nowhere, self.n_sources, self.wetted,
+                                      self.pairs, self.bad, self.force, self.torque)
+
+
+def _cross(r, f):
+    """``r x f`` of two triples of float64 arrays, one rounding per operation."""
+    return (r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0])
+
+
+def sph_body_force(position, velocity, box, h, body_rows, fluid_rows, mass=None, density=None, pressure=None, viscosity=None,
+                   about=None, cells=None, dimensions=3, kernel='wendland_c2'):
+    """The force and the torque the fluid exerts on a body: a pair pass between two row lists of one frame on one grid --
+    the *targets* ``b`` (``body_rows``) and the *sources* ``f`` (``fluid_rows``) -- with an ordered reduction over the
+    targets on top: drag, lift, buoyancy, the load on a wall.  The definition the GPU pass
+    (`pgsd.fl.PGSDFile.sph_body_force_device`, `HOOMDTrajectory.frame_body_force_device`) equals exactly, the floats bit for
+    bit -- so the ORDER of every sum is part of it.
+
+    Args:
+        position, velocity, box, h, mass, density, pressure, viscosity, cells, dimensions, kernel: `sph_accelerations`'.
+            The grid, the support ``2h``, ``r2``, ``inv_h``, ``sigma``, ``G``, ``eta2``, ``Gv``, the column defaults and
+            every refusal are its own.
+        body_rows, fluid_rows: the two lists (any order, repeats allowed), each put into cell order by `cell_order` with
+            its own offsets; ``None`` is not accepted for either.  A row may occur in both lists: that is not detected,
+            and such a pair is a candidate like any other.
+        about: three finite floats, the point the torque is taken about; ``None``: ``(0, 0, 0)``.
+
+    **Candidates** of target ``b``: the sources in the cells of the sums' order around the target's cell, looked up in
+    the sources' offsets, inside a cell in ascending position in the sources' list; ``d = pair_displacement(x_b, x_f)`` and
+    the test ``d2 < r2`` is strict.  Entries of either list that are nowhere take no part.
+
+    **One pair** ``b <- f``: `sph_accelerations`' arithmetic with ``i = b`` and ``j = f`` -- ``A``, ``V``, ``rho``, ``v``
+    and ``m`` of ``b`` from the targets' columns, those of ``f`` from the sources' --: ``contacts[b] += 1``, ``a_p[k] +=
+    m_f * (S * e_k)`` with ``S = A_b + A_f`` and, with a viscosity, ``a_v[k] += V_f * (K * (v_f[k] - v_b[k]))``.  After
+    the last candidate ``pressure_acc[k] = -(G * a_p[k])`` and ``viscous_acc[k] = (Gv * a_v[k]) / rho_b``; no gravity
+    enters.  A target without a cell has every value ``+0.0``.
+
+    **Per target**, float64, one rounding per operation: ``fp[k] = m_b * pressure_acc[k]``, ``fv[k] = m_b *
+    viscous_acc[k]``, the arm ``r = pair_displacement(about, x_b)`` (in 2-D ``r_z = 0``), ``tp = (r1*fp2 - r2*fp1, r2*fp0
+    - r0*fp2, r0*fp1 - r1*fp0)`` and ``tv`` likewise.  A target with a cell is *bad* if any of its six or twelve terms is
+    NaN or infinite; all its terms then count as ``+0.0``.
+
+    **Sums**: each of the twelve (six, and six ``+0.0``, without a viscosity) is `_ordered_sum` of its column over the
+    targets' list positions, targets nowhere as ``+0.0``.  Without a target no source is looked at, and none counts as
+    nowhere.
+
+    Returns a `KernelBodyForce`.
+    """
+    asked = _sph_asked(box, h, cells, dimensions, kernel)
+    mu, c = _sph_viscosity(viscosity), _sph_about(about)
+    if body_rows is None or fluid_rows is None:
+        raise ValueError("body_rows and fluid_rows are row lists: None is not accepted for either")
+    columns = (('mass', mass, 1), ('density', density, 1), ('velocity', velocity, 3), ('pressure', pressure, 1))
+    T = _sph_list(asked, position, box, body_rows, columns)
+    S = _sph_list(asked, position, box, fluid_rows, columns)
+    dimensions, h, kid, grid = asked[0], asked[1], asked[2], asked[4]
+
+    def filled(t):
+        mass, rho, v, p = t.columns
+        m = numpy.ones(t.n, dtype=numpy.float64) if mass is None else mass
+        rho = numpy.zeros(t.n, dtype=numpy.float64) if rho is None else rho
+        p = numpy.zeros(t.n, dtype=numpy.float64) if p is None else p
+        v = numpy.zeros((t.n, 3), dtype=numpy.float64) if v is None else v
+        with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+            return m, rho, v, p / (rho * rho), m / rho
+
+    m_b, rho_b, v_b, A_b, _ = filled(T)
+    m_f, _, v_f, A_f, V_f = filled(S)
+    n, somewhere = T.n, T.somewhere
+    G = numpy.float64(-((T.sigma * T.inv_h) * T.inv_h))
+    eta2 = (numpy.float64(0.01) * numpy.float64(h)) * numpy.float64(h)
+    Gv = None if mu is None else G * (numpy.float64(2.0) * numpy.float64(mu))
+    contacts = numpy.zeros(n, dtype=numpy.int64)
+    a_p = [numpy.zeros(n, dtype=numpy.float64) for _ in range(3)]
+    a_v = None if mu is None else [numpy.zeros(n, dtype=numpy.float64) for _ in range(3)]
+    zero = numpy.zeros(n, dtype=numpy.float64)
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        for i, j, d, d2 in _sph_pairs_around(S, T.xs[:somewhere], T.cell_sorted[:somewhere]):
+            F = sph_gradient_factor(numpy.sqrt(d2) * T.inv_h, kernel)
+            numpy.add.at(contacts, i, 1)
+            Sij, mj = A_b[i] + A_f[j], m_f[j]
+            for k in range(3):
+                numpy.add.at(a_p[k], i, mj * (Sij * (F * d[k])))
+            if a_v is not None:
+                K, Vj = (F * d2) / (d2 + eta2), V_f[j]
+                for k in range(3):
+                    numpy.add.at(a_v[k], i, Vj * (K * (v_f[j, k] - v_b[i, k])))
+        pressure_acc = numpy.stack([-(G * a) for a in a_p], axis=1)
+        viscous_acc = None if a_v is None else numpy.stack([(Gv * a) / rho_b for a in a_v], axis=1)
+        for a in (pressure_acc, viscous_acc):
+            if a is not None:
+                a[somewhere:] = 0.0
+        fp = [m_b * pressure_acc[:, k] for k in range(3)]
+        r = pair_displacement(numpy.array(c, dtype=numpy.float64), T.xs, T.vectors, dimensions) if n else (zero, zero, zero)
+        terms = fp + list(_cross(r, fp))
+        if viscous_acc is not None:
+            fv = [m_b * viscous_acc[:, k] for k in range(3)]
+            terms = fp + fv + list(_cross(r, fp)) + list(_cross(r, fv))
+        has = numpy.arange(n) < somewhere
+        good = has.copy()
+        for t in terms:
+            good &= numpy.isfinite(t)
+        norm2 = (fp[0] * fp[0] + fp[1] * fp[1]) + fp[2] * fp[2]
+    words = numpy.zeros(_SPHB_SUMMARY_WORDS, dtype=numpy.uint64)
+    f = words[9:22].view(numpy.float64)
+    # (without a target no source is looked at: none counts as nowhere)
+    words[0], words[1], words[2], words[3] = n, n - somewhere, S.n, S.n - S.somewhere if n else 0
+    words[4] = int(numpy.count_nonzero(has & (contacts >= 1)))
+    words[5] = int(contacts.sum())
+    words[6] = int(numpy.count_nonzero(has & ~good))
+    words[7] = words[8] = _NEIGHBOURS_NONE
+    if good.any():
+        size = numpy.where(good & (norm2 == norm2), norm2, -1.0)
+        at = int(numpy.argmax(size))                    # (the first position that attains the maximum)
+        if size[at] >= 0.0:
+            words[7], words[8], f[0] = at, T.rows_sorted[at], norm2[at]
+    for k, t in enumerate(terms):
+        # (the twelve words are force_pressure, force_viscous, torque_pressure, torque_viscous; without a viscosity
+        # `terms` holds the first and the third)
+        slot = k if viscous_acc is not None else (k if k < 3 else k + 3)
+        f[1 + slot] = _ordered_sum(numpy.where(good, t, 0.0))
+    return KernelBodyForce(h, SPH_KERNELS[kid], grid, dimensions, words, mu, c, T.rows_sorted, T.cell_sorted,
+                           contacts.astype(numpy.uint32), pressure_acc, viscous_acc)
+
+
+def _sph_frame_arrays(frame_or_arrays, h, types, box, dimensions):
+    """`_sph_frame_list` without a selection: ``(arrays, types, position, box, dimensions, h)``."""
+    arrays, position, box, dimensions, h, _ = _sph_frame_list(frame_or_arrays, h, None, types, None, box, dimensions)
+    if hasattr(frame_or_arrays, 'particles') and types is None:
+        types = frame_or_arrays.particles.types
+    return arrays, types, position, box, dimensions, h
+
+
+def frame_body_force(frame_or_arrays, body, fluid, h=None, kernel='wendland_c2', viscosity=None, about=None, cells=None,
+                     types=None, domain=None, box=None, dimensions=3):
+    """`sph_body_force` of a frame's ``position``, ``velocity``, ``mass``, ``density`` and ``pressure`` over two selections:
+    the host twin of `HOOMDTrajectory.frame_body_force_device`, which equals it exactly.  ``body`` and ``fluid`` are
+    ``where`` dicts (`where_rows`), both required; with a ``domain`` each selection is intersected with its rows, as
+    `frame_kernel_sums` forms its list.  The ``h=None`` rule, the column defaults and the refusals are
+    `frame_accelerations`'.  Returns a `KernelBodyForce`."""
+    if body is None or fluid is None:
+        raise ValueError("body and fluid are where dicts: both are required")
+    arrays, types, position, box, dimensions, h = _sph_frame_arrays(frame_or_arrays, h, types, box, dimensions)
+    lists = []
+    for where in (body, fluid):
+        rows = where_rows(arrays, where, types)
+        if domain is not None:
+            if 'position' not in arrays:
+                raise ValueError("a domain needs box and the 'position' array")
+            rows = numpy.intersect1d(rows, domain_rows(arrays['position'], box, domain, dimensions))
+        lists.append(rows)
+    return sph_body_force(position, arrays.get('velocity'), box, h, lists[0], lists[1], mass=arrays.get('mass'),
+                          density=arrays.get('density'), pressure=arrays.get('pressure'), viscosity=viscosity, about=about,
+                          cells=cells, dimensions=dimensions, kernel=kernel)
+
+
 # ---- SPH samples: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_samples_device`) equals exactly
-_SPHS_SUMMARY_WORDS = 11    # K, nowhere, outside, empty, not_finite, count_max, count_max_at, shepard min, max, density min, max
+_SPHS_SUMMARY_WORDS = 11   # K, nowhere, outside, empty, not_finite, count_max, count_max_at, shepard min, max, density min, max
 _SPHS_MAX_VALUES = 4        # value arrays of one call
 _SPHS_MAX_WIDTH = 4         # columns of one value array
 _SPHS_MAX_COLUMNS = 8       # columns of all of them together
@@ -5008,12 +5242,14 @@ class HOOMDTrajectory(object):
             f.wait_read()
         return got
 
-    def _sph_device_list(self, who, idx, h, kernel, cells, where, domain, names):
+    def _sph_device_list(self, who, idx, h, kernel, cells, where, domain, names, second=None):
         """What `frame_kernel_sums_device`, `frame_kernel_gradients_device` and `frame_accelerations_device` share ahead of
         their pass: the ``h=None``
         rule, the grid for the support ``2h``, the selection as a row list sorted by cell on the GPU and, for each of
         ``names``, the effective chunk ``(frame, name)`` or ``None``.  ``(f_pos, box, dims, h, grid, rows, cell, count,
-        chunks, [mass default, density default])``; the caller ends with `wait_read`, whatever is raised here."""
+        chunks, [mass default, density default])``; the caller ends with `wait_read`, whatever is raised here.
+        ``second``: one more ``where`` (`frame_body_force_device`), selected and ordered the same way on the same grid;
+        its ``(rows, cell, count)`` is appended to the result."""
         idx = self._frame_index(idx)
         f = self.file
         box, dims, n_global, f_pos = self._census_frame(idx)
@@ -5038,6 +5274,10 @@ class HOOMDTrajectory(object):
             fr = self._effective_frame(idx, 'particles/' + name, n_global)
             chunks.append(None if fr is None else (fr, 'particles/' + name))
         defaults = [float(_PARTICLE_FIELDS[name][2]) for name in ('mass', 'density')]
+        if second is not None:
+            rows2, count2, _ = self._selection_row_list(idx, second, domain, box, dims, n_global, f_pos)
+            cell2 = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows2, n=count2, dimensions=dims)
+            return f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults, (rows2, cell2, count2)
         return f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults
 
     def frame_kernel_gradients(self, idx, h=None, kernel='wendland_c2', cells=None, where=None, domain=None):
@@ -5098,6 +5338,43 @@ class HOOMDTrajectory(object):
                                              mass=chunks[0], density=chunks[1], pressure=chunks[3],
                                              defaults=defaults + [float(_PARTICLE_FIELDS['pressure'][2])], viscosity=mu,
                                              gravity=g, dimensions=dims, kernel=kernel, return_rows=return_rows)
+        finally:
+            f.wait_read()
+        return got
+
+    def frame_body_force(self, idx, body, fluid, h=None, kernel='wendland_c2', viscosity=None, about=None, cells=None,
+                         domain=None):
+        """`frame_body_force` of frame ``idx`` read through the host path: a `KernelBodyForce`.  The definition of
+        `frame_body_force_device`."""
+        return frame_body_force(self[int(idx)], body, fluid, h, kernel=kernel, viscosity=viscosity, about=about, cells=cells,
+                                domain=domain)
+
+    def frame_body_force_device(self, idx, body, fluid, h=None, kernel='wendland_c2', viscosity=None, about=None, cells=None,
+                                domain=None, return_rows=False):
+        """`frame_body_force` of frame ``idx``, on the GPU: a `KernelBodyForce` that equals ``frame_body_force(idx, body,
+        fluid, h, ...)`` exactly -- every counter and index, every float bit for bit.
+
+        ``body`` and ``fluid`` are ``where`` dicts, both required; each is selected on the GPU (with ``domain``:
+        intersected with it) and sorted by cell over the staged position chunk on one grid, `frame_kernel_sums_device`'s
+        for the support ``2h``; ``h=None`` is its rule too.  One pass (`pgsd.fl.PGSDFile.sph_body_force_device`) runs over
+        the staged position chunk and the effective ``velocity``, ``mass``, ``density`` and ``pressure`` chunks, which
+        both lists read; one that is stored nowhere costs nothing.  ``return_rows=True`` leaves the targets' ``rows``,
+        ``cell``, ``contacts``, ``pressure_acc`` and ``viscous_acc`` in GPU memory on the result; otherwise they are
+        ``None``.  One `wait_read` at the end releases the staged chunks.  A frame whose position is stored nowhere has no
+        chunk to search and raises ValueError.
+        """
+        f = self.file
+        try:
+            mu, c = _sph_viscosity(viscosity), _sph_about(about)
+            if body is None or fluid is None:
+                raise ValueError("body and fluid are where dicts: both are required")
+            f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults, (rows2, cell2, count2) = self._sph_device_list(
+                "frame_body_force_device", idx, h, kernel, cells, body, domain, ('mass', 'density', 'velocity', 'pressure'),
+                second=fluid)
+            got = f.sph_body_force_device(f_pos, 'particles/position', box, h, grid, rows, cell, rows2, cell2, n_body=count,
+                                          n_fluid=count2, velocity=chunks[2], mass=chunks[0], density=chunks[1],
+                                          pressure=chunks[3], defaults=defaults + [float(_PARTICLE_FIELDS['pressure'][2])],
+                                          viscosity=mu, about=c, dimensions=dims, kernel=kernel, return_rows=return_rows)
         finally:
             f.wait_read()
         return got

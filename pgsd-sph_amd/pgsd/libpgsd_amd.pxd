@@ -268,6 +268,14 @@ cdef extern from "pgsd_private.h" nogil:
                                       uint32_t dimensions, const uint32_t* cells, double viscosity, const double* gravity,
                                       const uint32_t* rows, const int32_t* cell, uint64_t n, double* out_pressure_acc,
                                       double* out_viscous_acc, double* out_total, uint64_t* out_summary)
+    int pgsd_sph_body_force_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* velocity,
+                                   const pgsd_index_entry* mass, const pgsd_index_entry* density,
+                                   const pgsd_index_entry* pressure, const double* defaults, const double* vectors, double h,
+                                   uint32_t kernel, uint32_t dimensions, const uint32_t* cells, double viscosity,
+                                   const double* about, const uint32_t* body_rows, const int32_t* body_cell, uint64_t n_body,
+                                   const uint32_t* fluid_rows, const int32_t* fluid_cell, uint64_t n_fluid,
+                                   uint32_t* out_contacts, double* out_pressure_acc, double* out_viscous_acc,
+                                   uint64_t* out_summary)
     int pgsd_sph_samples_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* mass,
                                 const pgsd_index_entry* density, const pgsd_index_entry* const* values,
                                 const uint32_t* value_columns, const double* value_defaults, const double* defaults,
