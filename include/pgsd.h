@@ -531,6 +531,9 @@ extern "C"
         uint64_t written_bytes;
         double d2h_ms;              /* sum of event-timed copy durations (profile=1) */
         double write_ms;            /* sum of pwrite wall time over writer threads */
+        uint64_t side_bytes;        /* of written_bytes: went through the side lane's mapping, not through pwrite */
+        double side_ms;             /* sum of populate + copy wall time over the side lane's threads */
+        uint64_t side_on;           /* 1 while the side lane takes part (PGSD_WRITE_SIDE; off after a populate error) */
         };
     int pgsd_device_get_stats(struct pgsd_handle* handle, struct pgsd_device_stats* out, int reset);
 

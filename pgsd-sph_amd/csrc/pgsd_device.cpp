@@ -246,6 +246,25 @@ int DevicePipeline::init()
         }
     const char* warm = getenv("PGSD_WRITE_WARM");
     m_warm = (warm ? atoi(warm) != 0 : true) && m_cfg.n_writers == 1 && writer_pool_enable_warm(m_pool, sub_kib << 10, pin);
+    // The side lane beside the pair (pgsd_io.cpp): PGSD_WRITE_SIDE threads (0: off; at most 3, which makes five I/O
+    // threads per pipeline) insert whole pages of a piece through a shared mapping of the file, PGSD_WRITE_SIDE_BLOCK_KIB
+    // at a time, while the pair pwrites the rest.  Only with the pair, on tmpfs, and for a file no other rank writes.
+    // 3 threads of 512 KiB: profiles/r28_side_lane_lab.log.  With the side lane on, every thread of the lane gets a core
+    // of its own in the pair's L3 group (writer_pool_enable_side).
+    long side = 3, side_kib = 512, side_fail = -1;
+    if (const char* v = getenv("PGSD_WRITE_SIDE"))
+        side = std::min(std::max(atol(v), 0l), 3l);
+    if (const char* v = getenv("PGSD_WRITE_SIDE_BLOCK_KIB"))
+        {
+        if (atol(v) > 0 && atol(v) % 4 == 0)
+            side_kib = atol(v);
+        else
+            fprintf(stderr, "pgsd_amd: PGSD_WRITE_SIDE_BLOCK_KIB=%s is no positive multiple of 4: %ld\n", v, side_kib);
+        }
+    if (const char* v = getenv("PGSD_WRITE_SIDE_FAIL_AT")) // tests: the populate call of that number reports failure
+        side_fail = atol(v);
+    if (m_warm && !m_shared && side > 0)
+        (void)writer_pool_enable_side(m_pool, m_fd, (unsigned)side, (size_t)side_kib << 10, pin, side_fail);
     m_dispatcher = std::thread([this] { dispatch_loop(); });
     if (pin)
         (void)pthread_setaffinity_np(m_dispatcher.native_handle(), sizeof(cpu_set_t), pin);
@@ -372,8 +391,21 @@ void DevicePipeline::stats(pgsd_device_stats* out, int reset)
     {
     std::lock_guard<std::mutex> g(m_mutex);
     *out = m_stats;
+    // the side lane counts for itself, from the pool's first day
+    uint64_t side_bytes = 0;
+    double side_ms = 0;
+    bool side_on = false;
+    if (m_pool)
+        writer_pool_side_counters(m_pool, &side_bytes, &side_ms, &side_on);
+    out->side_bytes = side_bytes - m_side_bytes_base;
+    out->side_ms = side_ms - m_side_ms_base;
+    out->side_on = side_on ? 1 : 0;
     if (reset)
+        {
         memset(&m_stats, 0, sizeof(m_stats));
+        m_side_bytes_base = side_bytes;
+        m_side_ms_base = side_ms;
+        }
     }
 
 bool DevicePipeline::staged_open()

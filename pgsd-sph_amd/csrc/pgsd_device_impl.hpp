@@ -286,6 +286,8 @@ class DevicePipeline
     size_t m_outstanding = 0;
     bool m_stop = false;
     pgsd_device_stats m_stats = {};
+    uint64_t m_side_bytes_base = 0;      // the side lane's counters at the last reset of the statistics
+    double m_side_ms_base = 0;
     WriterPool* m_pool = nullptr;
     std::thread m_dispatcher;
     std::atomic<bool> m_copy_used {false}; // something was enqueued on the copy stream since drain() last synchronised it

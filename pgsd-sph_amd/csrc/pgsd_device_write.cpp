@@ -416,6 +416,9 @@ int DevicePipeline::drain()
     std::unique_lock<std::mutex> lk(m_mutex);
     m_cv_done.wait_for(lk, std::chrono::seconds(30), [this] { return m_outstanding == 0; });
     lk.unlock();
+    // the side lane's windows of the file go behind everything queued (a job of the lane: no piece is in flight in it)
+    WriterPool* pool = m_pool;
+    writer_pool_submit(pool, [pool] { writer_pool_side_drop(pool); });
     return failure_code();
     }
 

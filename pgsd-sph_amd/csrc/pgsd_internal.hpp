@@ -104,6 +104,14 @@ bool writer_pool_enable_warm(WriterPool*, size_t sub_bytes, const cpu_set_t* cpu
 // or the piece is no longer than a sub-piece.  0 or -errno; *pwrite_ms: the time inside pwrite calls
 int writer_pool_pwrite_warm(WriterPool*, int fd, const void* buf, size_t bytes, long long offset, bool shared_file,
                             double* pwrite_ms);
+// The side lane beside the pair (pgsd_io.cpp): up to three threads that insert whole pages of a piece through a
+// MAP_SHARED mapping of `fd` (populate, then copy) while the pair pwrites the rest.  false -- nothing changes -- without
+// the pair or where fstatfs does not say tmpfs; never used for a shared file.  fail_at: tests (-1: never).
+bool writer_pool_enable_side(WriterPool*, int fd, unsigned n_threads, size_t block_bytes, const cpu_set_t* cpus, long fail_at = -1);
+// bytes that went by the side lane and the time its threads spent on them, since the pool was made; is it still on?
+void writer_pool_side_counters(WriterPool*, uint64_t* bytes, double* ms, bool* on);
+// unmap the side lane's windows: from a job of the pool, or while it has none
+void writer_pool_side_drop(WriterPool*);
 // Write [buf, buf+bytes) at `offset` of fd, split over the pool; blocks until done.
 // Returns 0 or -errno.
 int writer_pool_pwrite_sync(WriterPool*, int fd, const void* buf, size_t bytes, long long offset,

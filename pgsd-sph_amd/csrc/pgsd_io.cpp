@@ -30,13 +30,21 @@
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <map>
+#include <sys/mman.h>
 #include <sys/stat.h>
+#include <sys/vfs.h>
 #include <sys/syscall.h>
 #include <linux/futex.h>
 #include <functional>
 #include <mutex>
 #include <thread>
 #include <unistd.h>
+#include <algorithm>
+#include <vector>
+
+#ifndef MADV_POPULATE_WRITE
+#define MADV_POPULATE_WRITE 23
+#endif
 
 namespace pgsd_amd
     {
@@ -433,17 +441,41 @@ struct WaitWord
         if (sleepers.load() != 0)
             syscall(SYS_futex, (uint32_t*)&value, FUTEX_WAKE_PRIVATE, INT_MAX, nullptr, nullptr, 0);
         }
+
+    void add(uint32_t n)
+        {
+        value.fetch_add(n);
+        if (sleepers.load() != 0)
+            syscall(SYS_futex, (uint32_t*)&value, FUTEX_WAKE_PRIVATE, INT_MAX, nullptr, nullptr, 0);
+        }
     };
     } // namespace
+
+// cores (with their hardware threads) that lanes of this process have for themselves: two pipelines never share one
+static std::mutex g_lane_mutex;
+static cpu_set_t g_lane_cores;
 
 class WarmPair
     {
     public:
-    WarmPair(size_t sub_bytes, const cpu_set_t* cpus) : m_sub(sub_bytes)
+    WarmPair(size_t sub_bytes, const cpu_set_t* cpus) : m_sub((sub_bytes + PAGE - 1) / PAGE * PAGE), m_placed(cpus != nullptr)
         {
+        if (cpus)
+            m_cpus = *cpus;
         m_helper = std::thread([this] { helper(); });
         if (cpus)
             (void)pthread_setaffinity_np(m_helper.native_handle(), sizeof(cpu_set_t), cpus);
+        }
+
+    // the CPUs the pair was put on (those that share one L3); null: unplaced
+    const cpu_set_t* cpus() const
+        {
+        return m_placed ? &m_cpus : nullptr;
+        }
+
+    std::thread& helper_thread()
+        {
+        return m_helper;
         }
 
     ~WarmPair()
@@ -451,6 +483,23 @@ class WarmPair
         m_stop.store(true);
         m_gen.post(m_gen.value.load() + 1);
         m_helper.join();
+        for (auto& t : m_side)
+            t.join();
+        drop_windows();
+        if (m_has_cores)
+            {
+            std::lock_guard<std::mutex> g(g_lane_mutex);
+            for (int c = 0; c < CPU_SETSIZE; c++)
+                if (CPU_ISSET(c, &m_cores))
+                    CPU_CLR(c, &g_lane_cores);
+            }
+        }
+
+    // cores of g_lane_cores that are this lane's until it goes
+    void keep_cores(const cpu_set_t& cores)
+        {
+        m_cores = cores;
+        m_has_cores = true;
         }
 
     size_t sub_bytes() const
@@ -458,27 +507,178 @@ class WarmPair
         return m_sub;
         }
 
-    // the lane thread's half of one piece (at least two sub-pieces); 0 or -errno of the first pwrite that failed, after
-    // which the rest of the piece is skipped -- its tickets still pass
-    int write(int fd, const char* buf, size_t bytes, long long offset, double* pwrite_ms)
+    // `n` side threads (at most three) for pieces that go to `fd`, blocks of `block` bytes (rounded up to whole pages);
+    // fail_at >= 0: the populate call of that number (counted over the handle) reports failure, for tests
+    // side thread i goes to CPU cores[i] where there is one, else on `cpus`
+    void enable_side(int fd, unsigned n, size_t block, const cpu_set_t* cpus, const std::vector<int>& cores, long fail_at)
         {
-        m_fd = fd;
-        m_buf = buf;
-        m_bytes = bytes;
-        m_offset = offset;
-        m_base = m_ticket.value.load();
+        if (!m_side.empty() || n == 0)
+            return;
+        m_side_fd = fd;
+        m_block_pages = (uint32_t)std::min<size_t>(std::max<size_t>((block + PAGE - 1) / PAGE, 1), MAX_PAGES);
+        m_fail_at = fail_at;
+        for (unsigned i = 0; i < std::min(n, 3u); i++)
+            {
+            m_side.emplace_back([this] { side(); });
+            cpu_set_t one;
+            CPU_ZERO(&one);
+            if (i < cores.size())
+                CPU_SET(cores[i], &one);
+            if (i < cores.size() || cpus)
+                (void)pthread_setaffinity_np(m_side.back().native_handle(), sizeof(cpu_set_t), i < cores.size() ? &one : cpus);
+            }
+        }
+
+    bool side_on() const
+        {
+        return !m_side.empty() && !m_side_off.load();
+        }
+
+    void side_counters(uint64_t* bytes, double* ms) const
+        {
+        *bytes = m_side_bytes.load();
+        *ms = (double)m_side_ns.load() * 1e-6;
+        }
+
+    // every window goes; only while no piece is in flight (a job of the lane, or the lane's threads joined)
+    void drop_windows()
+        {
+        std::vector<char*> all;
+            {
+            std::lock_guard<std::mutex> g(m_win_mutex);
+            all.swap(m_retired);
+            }
+        for (Window& w : m_windows)
+            all.push_back(w.base);
+        m_windows.clear();
+        for (char* m : all)
+            munmap(m, WINDOW);
+        }
+
+    // The lane thread's half of one piece (longer than a sub-piece); 0 or -errno of the first pwrite that failed, after
+    // which the rest of the piece is skipped -- its tickets still pass.  With `side`, side threads and whole pages of
+    // the file inside the piece, the piece is split and the side lane takes part (below); every other piece goes the
+    // pair's own road, run().
+    int write(int fd, const char* buf, size_t bytes, long long offset, double* pwrite_ms, bool side)
+        {
+        const long long end = offset + (long long)bytes;
+        long long a0 = offset, a1 = end;
         m_err.store(0);
         m_pwrite_ns.store(0);
-        m_gen.post(m_gen.value.load() + 1); // publishes the piece to the helper
-        const uint32_t n = run(0);
-        const uint32_t end = m_base + n;
-        m_ticket.wait([end](uint32_t v) { return v == end; });
+        bool split = false;
+        if (side && side_on() && fd == m_side_fd)
+            {
+            // cut on page boundaries of the FILE: the head fragment up to the first, the tail fragment from the last
+            const long long h = (offset + (long long)PAGE - 1) & ~((long long)PAGE - 1), t = (end - 1) & ~((long long)PAGE - 1);
+            if (t > h && (size_t)(t - h) / PAGE <= MAX_PAGES && map_windows(fd, h, t))
+                {
+                split = true;
+                a0 = h;
+                a1 = t;
+                // the tail first: real bytes that put end-of-file behind the piece before a side thread touches the mapping
+                pwrite_timed(fd, buf + (size_t)(a1 - offset), (size_t)(end - a1), a1);
+                if (a0 != offset)
+                    pwrite_timed(fd, buf, (size_t)(a0 - offset), offset);
+                }
+            }
+        const uint32_t gen = m_gen.value.load() + 1;
+        if (!split)
+            {
+            // the pair alone, as ever: sub-pieces of the whole piece, taken in turn by the two threads
+            m_fd = fd;
+            m_buf = buf;
+            m_bytes = bytes;
+            m_offset = offset;
+            m_base = m_ticket.value.load();
+            m_road.store((uint64_t)gen << 1);
+            m_gen.post(gen); // publishes the piece to the helper
+            const uint32_t n = run(0);
+            const uint32_t last = m_base + n;
+            m_ticket.wait([last](uint32_t v) { return v == last; });
+            if (pwrite_ms)
+                *pwrite_ms = (double)m_pwrite_ns.load() * 1e-6;
+            return m_err.load();
+            }
+        const uint32_t pages = (uint32_t)(((size_t)(a1 - a0) + PAGE - 1) / PAGE);
+        const uint32_t base = m_ticket.value.load();
+        m_vfd.store(fd, std::memory_order_relaxed);
+        m_vbuf.store(buf + (size_t)(a0 - offset), std::memory_order_relaxed);
+        m_va0.store(a0, std::memory_order_relaxed);
+        m_vlen.store((size_t)(a1 - a0), std::memory_order_relaxed);
+        m_vbase.store(base, std::memory_order_relaxed);
+        m_side_done.value.store(0);
+        m_cursors.store(pack(gen, 0, pages));
+        m_road.store((uint64_t)gen << 1 | 1);
+        m_gen.post(gen); // publishes the piece to the helper and the side threads
+        pair(gen);
+        // the cursors have met: what lies below them was the pair's, in claims of m_sub, what lies above the side lane's
+        const uint32_t front = front_of(m_cursors.load()), per = (uint32_t)(m_sub / PAGE);
+        const uint32_t turn_end = base + (front + per - 1) / per, side_pages = pages - front;
+        m_ticket.wait([turn_end](uint32_t v) { return v == turn_end; });
+        m_side_done.wait([side_pages](uint32_t v) { return v == side_pages; });
+        // blocks a side thread gave back (its populate failed): through pwrite, so that ENOSPC reaches the caller as ever
+        std::vector<std::pair<uint32_t, uint32_t>> back;
+            {
+            std::lock_guard<std::mutex> g(m_win_mutex);
+            back.swap(m_returned);
+            }
+        for (auto& b : back)
+            {
+            const size_t at = (size_t)b.first * PAGE, len = std::min((size_t)b.second * PAGE, (size_t)(a1 - a0) - at);
+            pwrite_timed(fd, buf + (size_t)(a0 - offset) + at, len, a0 + (long long)at);
+            }
         if (pwrite_ms)
             *pwrite_ms = (double)m_pwrite_ns.load() * 1e-6;
         return m_err.load();
         }
 
     private:
+    static const size_t PAGE = 4096;
+    static const size_t WINDOW = (size_t)256 << 20; // of the file, per mapping (profiles/r28_side_lane_lab.log)
+    static const uint32_t MAX_PAGES = (1u << 22) - 1;
+
+    // the cursors of the piece in flight in one word, with the piece's number: a thread that still holds an earlier
+    // piece's view cannot claim (its compare-and-swap fails)
+    static uint64_t pack(uint32_t gen, uint32_t front, uint32_t back)
+        {
+        return (uint64_t)(gen & 0xfffffu) << 44 | (uint64_t)front << 22 | back;
+        }
+    static uint32_t front_of(uint64_t c)
+        {
+        return (uint32_t)(c >> 22) & MAX_PAGES;
+        }
+    static uint32_t back_of(uint64_t c)
+        {
+        return (uint32_t)c & MAX_PAGES;
+        }
+
+    struct View // a thread's copy of the piece in flight
+        {
+        int fd;
+        const char* buf;
+        long long a0;
+        size_t len;
+        uint32_t base;
+        };
+    View view() const
+        {
+        return {m_vfd.load(std::memory_order_relaxed), m_vbuf.load(std::memory_order_relaxed), m_va0.load(std::memory_order_relaxed),
+                m_vlen.load(std::memory_order_relaxed), m_vbase.load(std::memory_order_relaxed)};
+        }
+
+    void pwrite_timed(int fd, const char* p, size_t n, long long off)
+        {
+        if (n == 0 || m_err.load() != 0)
+            return;
+        TraceRange tr("pgsd:pwrite file_off=%llu bytes=%llu", (unsigned long long)off, n);
+        auto t0 = std::chrono::steady_clock::now();
+        int w = pwrite_full(fd, p, n, off);
+        m_pwrite_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
+        int none = 0;
+        if (w != 0)
+            m_err.compare_exchange_strong(none, w);
+        }
+
     void helper()
         {
         uint32_t seen = 0;
@@ -487,11 +687,20 @@ class WarmPair
             seen = m_gen.wait([seen](uint32_t v) { return v != seen; });
             if (m_stop.load())
                 return;
-            run(1);
+            // Which road piece `seen` takes was stored before m_gen moved.  Where the word already speaks of a later
+            // piece, `seen` was a split one that the other threads finished (a piece of the pair alone cannot end
+            // without its helper): look again.
+            const uint64_t road = m_road.load();
+            if ((uint32_t)(road >> 1) != seen)
+                continue;
+            if (road & 1)
+                pair(seen);
+            else
+                run(1);
             }
         }
 
-    // sub-pieces who, who + 2, ... of the piece in flight; returns how many sub-pieces the piece has
+    // The pair alone: sub-pieces who, who + 2, ... of the piece in flight; returns how many sub-pieces the piece has
     uint32_t run(uint32_t who)
         {
         const int fd = m_fd;
@@ -527,19 +736,218 @@ class WarmPair
         return n;
         }
 
+    // With the side lane, the pair's half of piece `gen`: claim a sub-piece upwards from the front, read it into cache, wait for the turn
+    // (claim order), pwrite, pass the turn on -- until the cursors meet.
+    void pair(uint32_t gen)
+        {
+        const View v = view();
+        const uint32_t per = (uint32_t)(m_sub / PAGE);
+        for (;;)
+            {
+            uint64_t c = m_cursors.load();
+            uint32_t front, n;
+            for (;;)
+                {
+                front = front_of(c);
+                const uint32_t back = back_of(c);
+                if (c >> 44 != (gen & 0xfffffu) || front >= back)
+                    return;
+                n = std::min(per, back - front);
+                if (m_cursors.compare_exchange_weak(c, pack(gen, front + n, back)))
+                    break;
+                }
+            const size_t at = (size_t)front * PAGE, len = std::min((size_t)n * PAGE, v.len - at);
+            const unsigned long long foff = (unsigned long long)(v.a0 + (long long)at);
+                {
+                TraceRange tr("pgsd:warm file_off=%llu bytes=%llu", foff, len);
+                unsigned acc = 0;
+                for (const char* q = v.buf + at; q < v.buf + at + len; q = (const char*)(((uintptr_t)q | 63) + 1))
+                    acc += (unsigned char)*(const volatile char*)q;
+                m_sink.store(acc, std::memory_order_relaxed);
+                }
+            const uint32_t turn = v.base + front / per; // every claim but a piece's last takes `per` pages
+            m_ticket.wait([turn](uint32_t t) { return t == turn; });
+            pwrite_timed(v.fd, v.buf + at, len, v.a0 + (long long)at);
+            m_ticket.post(turn + 1);
+            }
+        }
+
+    // ---- the side lane: a second stream of page insertions beside the pair's, through a MAP_SHARED mapping of the file.
+    // A store through a mapping inserts a fresh tmpfs page WITHOUT the file's inode lock, which is what the pair's
+    // pwrite spends its time under.  Side threads claim blocks downwards from the back of the piece's whole pages,
+    // populate a block's pages with madvise(MADV_POPULATE_WRITE) -- one call, an error code where a store would have
+    // raised a signal -- and copy the block from the slab into pages that are then present.  A populate error gives
+    // the block back to the lane thread (pwrite: ENOSPC as ever) and switches the side lane off for good.
+    // tools/labs/side_lane_lab.cpp measured it (profiles/r28_side_lane_lab.log).
+    struct Window
+        {
+        size_t index; // the window covers [index * WINDOW, (index + 1) * WINDOW) of the file
+        char* base;
+        };
+
+    // windows for [a0, a1) of the file, by the lane thread before the piece is published; windows out of use go to a
+    // side thread, which unmaps them.  false: the piece takes the pair's road (and on a failed mmap every later one)
+    bool map_windows(int fd, long long a0, long long a1)
+        {
+        const size_t first = (size_t)a0 / WINDOW, last = (size_t)(a1 - 1) / WINDOW;
+        if (last - first > 1)
+            return false;
+        char* base[2] = {nullptr, nullptr};
+        for (size_t w = first; w <= last; w++)
+            {
+            for (Window& have : m_windows)
+                if (have.index == w)
+                    base[w - first] = have.base;
+            if (base[w - first])
+                continue;
+            void* m = mmap(nullptr, WINDOW, PROT_READ | PROT_WRITE, MAP_SHARED, fd, (off_t)(w * WINDOW));
+            if (m == MAP_FAILED)
+                {
+                m_side_off.store(true);
+                return false;
+                }
+            m_windows.push_back({w, (char*)m});
+            base[w - first] = (char*)m;
+            }
+        if (m_windows.size() > 3)
+            {
+            std::lock_guard<std::mutex> g(m_win_mutex);
+            for (size_t i = 0; i < m_windows.size();)
+                if (m_windows[i].index < first || m_windows[i].index > last)
+                    {
+                    m_retired.push_back(m_windows[i].base);
+                    m_windows.erase(m_windows.begin() + (long)i);
+                    }
+                else
+                    i++;
+            }
+        m_win_first.store(first, std::memory_order_relaxed);
+        m_win_base[0].store(base[0], std::memory_order_relaxed);
+        m_win_base[1].store(base[1], std::memory_order_relaxed);
+        return true;
+        }
+
+    void side()
+        {
+        uint32_t seen = 0;
+        for (;;)
+            {
+            seen = m_gen.wait([seen](uint32_t v) { return v != seen; });
+            if (m_stop.load())
+                return;
+            std::vector<char*> retired;
+                {
+                std::lock_guard<std::mutex> g(m_win_mutex);
+                retired.swap(m_retired);
+                }
+            for (char* m : retired)
+                munmap(m, WINDOW);
+            const uint64_t road = m_road.load();
+            if ((uint32_t)(road >> 1) != seen || !(road & 1)) // a later piece already, or one of the pair alone
+                continue;
+            const View v = view();
+            const size_t win_first = m_win_first.load(std::memory_order_relaxed);
+            char* const win_base[2] = {m_win_base[0].load(std::memory_order_relaxed), m_win_base[1].load(std::memory_order_relaxed)};
+            while (!m_side_off.load() && m_err.load() == 0)
+                {
+                uint64_t c = m_cursors.load();
+                uint32_t back = 0, n = 0;
+                for (;;)
+                    {
+                    const uint32_t front = front_of(c);
+                    back = back_of(c);
+                    n = 0;
+                    if (c >> 44 != (seen & 0xfffffu) || front >= back)
+                        break;
+                    n = std::min(m_block_pages, back - front);
+                    if (m_cursors.compare_exchange_weak(c, pack(seen, front, back - n)))
+                        break;
+                    }
+                if (n == 0)
+                    break;
+                // (a successful claim says that piece `seen` is still in flight: the view above is that piece's)
+                const uint32_t first = back - n;
+                size_t len = std::min((size_t)n * PAGE, v.len - (size_t)first * PAGE);
+                long long foff = v.a0 + (long long)first * (long long)PAGE;
+                TraceRange tr("pgsd:side file_off=%llu bytes=%llu", (unsigned long long)foff, len);
+                auto t0 = std::chrono::steady_clock::now();
+                const size_t block_bytes = len;
+                bool ok = true;
+                while (ok && len != 0)
+                    {
+                    const size_t w = (size_t)foff / WINDOW, in = (size_t)foff % WINDOW, now = std::min(len, WINDOW - in);
+                    char* dst = win_base[w - win_first] + in;
+                    const long k = m_populates.fetch_add(1);
+                    errno = 0;
+                    if (k == m_fail_at || madvise(dst, now, MADV_POPULATE_WRITE) != 0)
+                        {
+                        ok = false; // EFAULT (a full tmpfs), ENOMEM, EINVAL (a kernel without the call): no store
+                        if (!m_side_off.exchange(true))
+                            fprintf(stderr, "pgsd_amd: the side lane of the writer is off from here on: populating pages failed (%s)\n",
+                                    errno ? strerror(errno) : "PGSD_WRITE_SIDE_FAIL_AT");
+                        }
+                    else
+                        memcpy(dst, v.buf + (size_t)(foff - v.a0), now);
+                    foff += (long long)now;
+                    len -= now;
+                    }
+                if (ok)
+                    {
+                    m_side_bytes.fetch_add(block_bytes);
+                    m_side_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
+                    }
+                else
+                    {
+                    m_side_off.store(true);
+                    std::lock_guard<std::mutex> g(m_win_mutex);
+                    m_returned.push_back({first, n});
+                    }
+                m_side_done.add(n);
+                }
+            }
+        }
+
     const size_t m_sub;
+    const bool m_placed;
+    cpu_set_t m_cpus;
+    bool m_has_cores = false;
+    cpu_set_t m_cores;
     std::thread m_helper;
-    // the piece in flight: written by the lane thread before m_gen moves, read by the helper behind it
+    // the piece in flight on the pair's own road: written by the lane thread before m_gen moves, read by the helper behind it
     int m_fd = -1;
     const char* m_buf = nullptr;
     size_t m_bytes = 0;
     long long m_offset = 0;
     uint32_t m_base = 0;
-    WaitWord m_gen, m_ticket; // pieces handed to the helper; sub-pieces written, of all pieces so far
+    std::atomic<uint64_t> m_road {0};         // piece number << 1 | the piece is split (the side lane takes part)
+    // the piece in flight with the side lane (atomics: a thread that slept through a whole piece may read while the
+    // next is set up; it then cannot claim)
+    std::atomic<int> m_vfd {-1};
+    std::atomic<const char*> m_vbuf {nullptr}; // the byte that goes to m_va0
+    std::atomic<long long> m_va0 {0};          // the claimed range of the file starts here ...
+    std::atomic<size_t> m_vlen {0};            // ... and is this long: the cursors count its 4 KiB pages
+    std::atomic<uint32_t> m_vbase {0};
+    std::atomic<uint64_t> m_cursors {0};
+    WaitWord m_gen, m_ticket; // pieces handed to the other threads; sub-pieces written, of all pieces so far
     std::atomic<int> m_err {0};
     std::atomic<uint64_t> m_pwrite_ns {0};
     std::atomic<unsigned> m_sink {0};
     std::atomic<bool> m_stop {false};
+    // the side lane
+    std::vector<std::thread> m_side;
+    int m_side_fd = -1;
+    uint32_t m_block_pages = 0;
+    long m_fail_at = -1;
+    std::atomic<long> m_populates {0};
+    std::atomic<bool> m_side_off {false};
+    WaitWord m_side_done;                     // pages of the piece in flight that side threads are done with
+    std::vector<Window> m_windows;            // the lane thread's
+    std::atomic<size_t> m_win_first {0};
+    std::atomic<char*> m_win_base[2] = {{nullptr}, {nullptr}};
+    std::mutex m_win_mutex;                   // m_retired, m_returned
+    std::vector<char*> m_retired;
+    std::vector<std::pair<uint32_t, uint32_t>> m_returned; // first page, pages
+    std::atomic<uint64_t> m_side_bytes {0}, m_side_ns {0};
     };
 
 class WriterPool
@@ -582,6 +990,11 @@ class WriterPool
     WarmPair* warm() const
         {
         return m_warm;
+        }
+
+    std::thread& lane_thread()
+        {
+        return m_threads[0];
         }
 
     void submit(std::function<void()> fn)
@@ -763,6 +1176,105 @@ bool writer_pool_enable_warm(WriterPool* p, size_t sub_bytes, const cpu_set_t* c
     return p->warm() != nullptr;
     }
 
+// Up to `want` CPUs, no two of them hardware threads of one core and none on a core that another lane of this process
+// has: those of `first`, then those of `then` (may be null).  Fewer than `least`: none.  What is picked is entered in
+// g_lane_cores, hardware threads included, and returned in *kept for the lane to give back.
+static std::vector<int> cores_of_their_own(const cpu_set_t* first, const cpu_set_t* then, unsigned want, unsigned least, cpu_set_t* kept)
+    {
+    std::lock_guard<std::mutex> g(g_lane_mutex);
+    std::vector<int> picked;
+    cpu_set_t taken, all;
+    taken = g_lane_cores;
+    memset(&all, 0xff, sizeof(all));
+    for (const cpu_set_t* from : {first, then})
+        for (int c = 0; from && c < CPU_SETSIZE && picked.size() < want; c++)
+            {
+            if (!CPU_ISSET(c, from) || CPU_ISSET(c, &taken))
+                continue;
+            picked.push_back(c);
+            CPU_SET(c, &taken);
+            char path[128], buf[4096];
+            snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", c);
+            if (FILE* f = fopen(path, "r"))
+                {
+                const size_t n = fread(buf, 1, sizeof(buf) - 1, f);
+                fclose(f);
+                buf[n] = 0;
+                cpu_set_t siblings;
+                parse_cpulist(buf, &all, &siblings);
+                CPU_OR(&taken, &taken, &siblings);
+                }
+            }
+    CPU_ZERO(kept);
+    if (picked.size() < least)
+        return {};
+    for (int c = 0; c < CPU_SETSIZE; c++)
+        if (CPU_ISSET(c, &taken) && !CPU_ISSET(c, &g_lane_cores))
+            CPU_SET(c, kept);
+    g_lane_cores = taken;
+    return picked;
+    }
+
+bool writer_pool_enable_side(WriterPool* p, int fd, unsigned n_threads, size_t block_bytes, const cpu_set_t* cpus, long fail_at)
+    {
+    WarmPair* pair = p ? p->warm() : nullptr;
+    struct statfs fs;
+    if (!pair || n_threads == 0 || block_bytes == 0 || fstatfs(fd, &fs) != 0 || (unsigned long)fs.f_type != 0x01021994ul) // TMPFS_MAGIC
+        return false;
+    // Placement as the lab had it (tools/labs/side_lane_lab.cpp): every thread of the lane on a core of its own -- the
+    // lane thread and the helper, which so far moved within their L3 group, on its first two cores, the side threads on
+    // the next ones, and on cores of `cpus` outside the group where it has too few.  Two of these threads on one core
+    // (or on the two hardware threads of one) halve the lane's rate: side threads merely somewhere on `cpus` gave
+    // 5.9-6.6 GB/s in three of five runs, less than the pair alone.  So cores that another pipeline of this process has
+    // are passed over, there are only as many side threads as cores were found for, and where not even one is left
+    // (a small cpuset) the side lane stays off and the pair stays as it was.  A pair that runs unplaced (tests of the
+    // lane itself: nothing is known about the cores) has unplaced side threads.
+    n_threads = std::min(n_threads, 3u);
+    std::vector<int> cores;
+    if (pair->cpus())
+        {
+        cpu_set_t kept;
+        cores = cores_of_their_own(pair->cpus(), cpus, 2 + n_threads, 3, &kept);
+        if (cores.empty())
+            return false;
+        pair->keep_cores(kept);
+        n_threads = (unsigned)cores.size() - 2;
+        }
+    if (cores.size() >= 2)
+        {
+        cpu_set_t one;
+        CPU_ZERO(&one);
+        CPU_SET(cores[0], &one);
+        (void)pthread_setaffinity_np(p->lane_thread().native_handle(), sizeof(one), &one);
+        CPU_ZERO(&one);
+        CPU_SET(cores[1], &one);
+        (void)pthread_setaffinity_np(pair->helper_thread().native_handle(), sizeof(one), &one);
+        cores.erase(cores.begin(), cores.begin() + 2);
+        }
+    else
+        cores.clear();
+    pair->enable_side(fd, n_threads, block_bytes, cpus, cores, fail_at);
+    return pair->side_on();
+    }
+
+void writer_pool_side_counters(WriterPool* p, uint64_t* bytes, double* ms, bool* on)
+    {
+    *bytes = 0;
+    *ms = 0;
+    *on = false;
+    if (WarmPair* pair = p ? p->warm() : nullptr)
+        {
+        pair->side_counters(bytes, ms);
+        *on = pair->side_on();
+        }
+    }
+
+void writer_pool_side_drop(WriterPool* p)
+    {
+    if (WarmPair* pair = p ? p->warm() : nullptr)
+        pair->drop_windows();
+    }
+
 int writer_pool_pwrite_warm(WriterPool* p, int fd, const void* buf, size_t bytes, long long offset, bool shared_file,
                             double* pwrite_ms)
     {
@@ -780,7 +1292,7 @@ int writer_pool_pwrite_warm(WriterPool* p, int fd, const void* buf, size_t bytes
     while (locked && flock(fd, LOCK_EX) != 0)
         if (errno != EINTR)
             locked = false; // no lock support: write anyway
-    int rc = pair->write(fd, (const char*)buf, bytes, offset, pwrite_ms);
+    int rc = pair->write(fd, (const char*)buf, bytes, offset, pwrite_ms, !shared_file);
     if (locked)
         flock(fd, LOCK_UN);
     return rc;

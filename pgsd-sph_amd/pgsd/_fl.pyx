@@ -1595,7 +1595,8 @@ cdef class PGSDFile:
         _raise_on_error(C.pgsd_device_get_stats(&self._handle, &st, 1 if reset else 0), self._name)
         return {"pack_launches": st.pack_launches, "pack_ms": st.pack_ms, "pack_rows": st.pack_rows,
                 "pack_bytes_out": st.pack_bytes_out, "pack_bytes_in": st.pack_bytes_in, "d2h_bytes": st.d2h_bytes,
-                "written_bytes": st.written_bytes, "d2h_ms": st.d2h_ms, "write_ms": st.write_ms}
+                "written_bytes": st.written_bytes, "d2h_ms": st.d2h_ms, "write_ms": st.write_ms,
+                "side_bytes": st.side_bytes, "side_ms": st.side_ms, "side_on": st.side_on}
 
     def device_read_stats(self, reset=False):
         """dict: file bytes the device read path has ``pread`` (``pread_bytes``) and bytes it has copied host-to-device

@@ -113,7 +113,8 @@ class DeviceConfig(ctypes.Structure):
 class DeviceStats(ctypes.Structure):
     _fields_ = [("pack_launches", c_u64), ("pack_ms", ctypes.c_double), ("pack_rows", c_u64),
                 ("pack_bytes_out", c_u64), ("pack_bytes_in", c_u64), ("d2h_bytes", c_u64),
-                ("written_bytes", c_u64), ("d2h_ms", ctypes.c_double), ("write_ms", ctypes.c_double)]
+                ("written_bytes", c_u64), ("d2h_ms", ctypes.c_double), ("write_ms", ctypes.c_double),
+                ("side_bytes", c_u64), ("side_ms", ctypes.c_double), ("side_on", c_u64)]
 
 
 class ExchangeStats(ctypes.Structure):

@@ -167,6 +167,9 @@ cdef extern from "pgsd.h" nogil:
         uint64_t written_bytes
         double d2h_ms
         double write_ms
+        uint64_t side_bytes
+        double side_ms
+        uint64_t side_on
 
     int pgsd_write_chunk_device(pgsd_handle* handle, const char* name, pgsd_type type, uint64_t N, uint32_t M,
                                 uint64_t N_global, uint32_t M_global, uint64_t offset, uint64_t global_size, bint all,

@@ -85,6 +85,14 @@ def main():
         under = sum(overlap((s, e), [(ps, pe) for ps, pe, pw_, n in pw_named if pw_ != w]) for s, e, w in warm)
         print("# pgsd:warm ranges: %d, %.1f us in all = %.1f us per 16 MiB; %.1f us = %.0f %% of it under a pwrite of the other thread"
               % (len(warm), warm_total / 1e3, warm_total / 1e3 * (16 << 20) / max(written, 1), under / 1e3, 100.0 * under / max(warm_total, 1)))
+    # the side lane: blocks that went into the file through the mapping (populate + copy), beside the pwrites
+    side = [(s, e, w, n) for s, e, w, n in inside if n.startswith("pgsd:side")]
+    if side:
+        side_bytes = sum(nbytes(n) for s, e, w, n in side)
+        side_total = sum(e - s for s, e, w, n in side)
+        print("# pgsd:side ranges: %d on %d threads, %.1f MB = %.0f %% of the frame's bytes; %.1f us in all = %.1f us per 16 MiB of them"
+              % (len(side), len(set(w for s, e, w, n in side)), side_bytes / 1e6, 100.0 * side_bytes / max(side_bytes + written, 1),
+                 side_total / 1e3, side_total / 1e3 * (16 << 20) / max(side_bytes, 1)))
 
 
 if __name__ == "__main__":
