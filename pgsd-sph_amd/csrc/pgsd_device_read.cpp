@@ -693,6 +693,17 @@ int device_pipeline_neighbour_list(DevicePipeline* p, long long file_offset, siz
                           { return launch_neighbour_list(a, offsets, capacity, out_neighbours, out_distance2, stream, why); });
     }
 
+// Components: the census's staging; the lists and the per-entry outputs are the caller's (the entry point answers a list
+// of no entry itself: nothing comes down here for it).
+int device_pipeline_components(DevicePipeline* p, long long file_offset, size_t bytes, const NeighboursArgs& args,
+                               uint32_t* out_label, uint32_t* out_component, uint32_t* out_sizes, uint64_t* out_summary,
+                               std::string* err)
+    {
+    NeighboursArgs a = args;
+    return one_chunk_pass(p, file_offset, bytes, &a.pos, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_components(a, out_label, out_component, out_sizes, out_summary, stream, why); });
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

@@ -701,6 +701,22 @@ int device_pipeline_neighbour_offsets(DevicePipeline*, long long file_offset, si
 int device_pipeline_neighbour_list(DevicePipeline*, long long file_offset, size_t bytes, const NeighbourListArgs& a,
                                    const uint64_t* offsets, uint64_t capacity, uint32_t* out_neighbours,
                                    double* out_distance2, std::string* err);
+// Components (pgsd.hoomd.neighbour_components is the definition): the connected components of the graph whose edges are
+// the pairs of the half neighbour list -- the friends-of-friends grouping of a list with the linking length r.  The grid,
+// the range and the list are NeighboursArgs' (bins is not looked at).
+enum
+    {
+    COMPONENTS_SUMMARY_WORDS = 6 // n, nowhere, components, singletons, largest, largest_label
+    };
+// stage the position chunk (or take it from what the ordering left staged), check the lists, link and number on the GPU:
+// out_label (device, a.n words: the smallest list position of the entry's component), out_component (device, a.n words:
+// the dense id, or null), out_sizes (device, room for a.n words of which the first `components` are written, or null);
+// out_summary (host, 6 words) is written on success only; synchronous.  No store lands at an index >= a.n.  a.n > 0 (the
+// entry point answers a list of no entry with six zeros and stages nothing).  The refusals and the staging are
+// device_pipeline_neighbours'.
+int device_pipeline_components(DevicePipeline*, long long file_offset, size_t bytes, const NeighboursArgs& a,
+                               uint32_t* out_label, uint32_t* out_component, uint32_t* out_sizes, uint64_t* out_summary,
+                               std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

@@ -315,6 +315,16 @@ int launch_neighbour_offsets(const NeighbourListArgs& a, uint64_t* out_offsets, 
 int launch_neighbour_list(const NeighbourListArgs& a, const uint64_t* offsets, uint64_t capacity, uint32_t* out_neighbours,
                           double* out_distance2, hipStream_t stream, std::string* err);
 
+// components (pgsd_components.hip; NeighboursArgs, a.pos filled in): check, offsets, compaction, one lane per entry uniting
+// itself with its later neighbours over the census's traversal in a lock-free union-find whose parent array is out_label
+// (device, a.n words), a flatten pass, a count of the roots, one workgroup scanning the workgroups' counts, a numbering
+// pass; out_component (device, a.n words, or null), out_sizes (device, a.n words of which the first `components` are
+// written, or null); out_summary (host, 6 words: n, nowhere, components, singletons, largest, largest_label) is written on
+// success only; a.n == 0 launches nothing.  Synchronises `stream`; PGSD_ERROR_INVALID_ARGUMENT for what the census
+// refuses, PGSD_ERROR_DEVICE where a hook reached the cap of its retries (the pass gave up)
+int launch_components(const NeighboursArgs& a, uint32_t* out_label, uint32_t* out_component, uint32_t* out_sizes,
+                      uint64_t* out_summary, hipStream_t stream, std::string* err);
+
 // SPH kernel sums (pgsd_sph.hip; SphArgs, a.pos, a.mass and a.density filled in): check, offsets, compaction of the listed
 // positions, masses and volumes, one lane per entry over the runs of the adjacent cells in the defined order, one
 // workgroup for the ranges and the deviation.  out_number, out_density, out_shepard (device, a.n entries each, or null);
@@ -419,6 +429,7 @@ void warm_order_kernels();
 void warm_cells_kernels();
 void warm_neighbours_kernels();
 void warm_neighbour_list_kernels();
+void warm_components_kernels();
 void warm_sph_kernels();
 void warm_sph_gradients_kernels();
 void warm_sph_forces_kernels();

@@ -47,6 +47,10 @@
  *                     pgsd_neighbour_offsets_device, pgsd_neighbour_list_device (pgsd.fl's neighbour_list_device, behind
  *                     pgsd.hoomd's frame_neighbour_list_device: the same neighbours handed over as a CSR pair list in a
  *                     defined order -- count and scan, then fill -- which is what a restarted solver builds first)
+ *                     pgsd_components_device (pgsd.fl's components_device, behind pgsd.hoomd's frame_components_device:
+ *                     the connected components of the half list's pairs -- which pieces has the fluid broken into, how
+ *                     many droplets and stray particles are there -- as a label, a dense id and the sizes, by a lock-free
+ *                     union-find over the same traversal)
  *                     pgsd_sph_sums_device (pgsd.fl's sph_sums_device, behind pgsd.hoomd's frame_kernel_sums_device: per
  *                     entry of a row list in cell order the SPH summation density, number density and Shepard sum over
  *                     the kernel support, in a defined order, and over the list their ranges, the largest deviation from
@@ -441,6 +445,33 @@ extern "C"
                                    const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t flags,
                                    const uint64_t* offsets, uint64_t capacity, uint32_t* out_neighbours,
                                    double* out_distance2);
+
+    /* Components (pgsd.hoomd.neighbour_components is the definition, and the results equal it exactly: every word is an
+       integer and none depends on an order of evaluation): the friends-of-friends grouping of a row list in cell order
+       with the linking length r -- the connected components of the graph whose EDGES are the pairs of the half list of
+       pgsd_neighbour_offsets_device / pgsd_neighbour_list_device for the same arguments: i and j, i < j by list position,
+       are joined iff i -> j lies strictly inside the range (d2 < r*r).  A row listed twice is two entries at distance 0,
+       and the two are joined; an entry without a cell has no edge and is a component of its own.  position, vectors, r,
+       dimensions, cells, rows, cell and n are pgsd_neighbour_offsets_device's, and the call refuses everything that call
+       refuses, with its messages and in its order.  flags must be 0: any set bit is refused.
+           out_label      device memory, n uint32, required for n > 0: the smallest list position of the entry's
+                          component (while the pass runs it is the parent array of a lock-free union-find)
+           out_component  device memory, n uint32, or NULL: the dense id -- the number of components whose label is
+                          smaller, so that components are numbered in ascending order of their smallest member
+           out_sizes      device memory with room for n uint32, or NULL: the first `components` words are defined,
+                          out_sizes[c] the entries of component c
+           out_summary    host, 6 uint64, written on success only: n; the entries nowhere; the components; the
+                          singletons (components of one entry, the nowhere entries among them); the largest size; the
+                          label of the largest component, among equal sizes the smallest label
+       No store lands at an index >= n of any output.  The chunk is staged whole unless an earlier call (the ordering)
+       left it staged, the pass runs on the handle's GPU on the pipeline's stream and the call synchronises; the staged
+       rows are kept until the next pgsd_device_wait_read.  n == 0 stages nothing and launches no kernel: the summary is
+       six zeros.  Every loop on the GPU that depends on other lanes carries a hard cap; a pass that reaches it gives up:
+       PGSD_ERROR_DEVICE, "the pass gave up: internal error", instead of a wrong result (the outputs are unspecified). */
+    int pgsd_components_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position, const double vectors[6],
+                               double r, uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
+                               const int32_t* cell, uint64_t n, uint32_t flags, uint32_t* out_label,
+                               uint32_t* out_component, uint32_t* out_sizes, uint64_t* out_summary);
 
     /* SPH kernel sums (pgsd.hoomd.sph_kernel_sums is the definition, and the results equal it exactly: every counter and
        index, every float bit for bit -- a NaN is a NaN, its sign and payload are the processor's).  position: an N x 3

@@ -1047,13 +1047,15 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
-// What pgsd_neighbour_offsets_device and pgsd_neighbour_list_device share: every refusal of pgsd_neighbours_device, with
-// its messages and in its order, the undefined bits of `flags`, the range of the position chunk and the arguments of the
-// pass.  PGSD_SUCCESS: `a`, `foff` and `bytes` are set (a.N == 0 is left to the caller: only n > 0 makes it a refusal).
+// What pgsd_neighbour_offsets_device, pgsd_neighbour_list_device and pgsd_components_device share: every refusal of
+// pgsd_neighbours_device, with its messages and in its order, the undefined bits of `flags` (`defined`: the bits the
+// caller has, `undefined`: what it says of the others), the range of the position chunk and the arguments of the pass.
+// PGSD_SUCCESS: `a`, `foff` and `bytes` are set (a.N == 0 is left to the caller: only n > 0 makes it a refusal).
 static int neighbour_list_arguments(const char* who, Impl* s, struct pgsd_handle* handle, const struct pgsd_index_entry* position,
                                     const double vectors[6], double r, uint32_t dimensions, const uint32_t cells[3],
                                     const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t flags, NeighbourListArgs& a,
-                                    long long* foff, size_t* bytes)
+                                    long long* foff, size_t* bytes, uint32_t defined = NLIST_HALF,
+                                    const char* undefined = "flags holds undefined bits (bit 0, the half list, is the only one)")
     {
     const Refusal refuse = {who};
     pgsd_index_entry c = *position; // a flush may move the index storage
@@ -1070,8 +1072,8 @@ static int neighbour_list_arguments(const char* who, Impl* s, struct pgsd_handle
     rc = pair_grid(refuse, vectors, r, "range", dimensions, cells, &a.n_cells);
     if (rc != PGSD_SUCCESS)
         return rc;
-    if (flags & ~(uint32_t)NLIST_HALF)
-        return refuse("flags holds undefined bits (bit 0, the half list, is the only one)");
+    if (flags & ~defined)
+        return refuse(undefined);
     rc = whole_chunk_range(s, handle, c, foff, bytes);
     if (rc != PGSD_SUCCESS)
         return rc;
@@ -1151,6 +1153,42 @@ extern "C" int pgsd_neighbour_list_device(struct pgsd_handle* handle, const stru
     return reduction_call(who, "neighbour list: ", [&](std::string* err)
                           { return device_pipeline_neighbour_list(s->dev, foff, bytes, a, offsets, capacity, out_neighbours,
                                                                   out_distance2, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_components_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                      const double vectors[6], double r, uint32_t dimensions, const uint32_t cells[3],
+                                      const uint32_t* rows, const int32_t* cell, uint64_t n, uint32_t flags, uint32_t* out_label,
+                                      uint32_t* out_component, uint32_t* out_sizes, uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_components_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell || !out_label)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    NeighbourListArgs a;
+    long long foff = 0;
+    size_t bytes = 0;
+    int rc = neighbour_list_arguments(who, s, handle, position, vectors, r, dimensions, cells, rows, cell, n, flags, a, &foff,
+                                      &bytes, 0u, "flags holds undefined bits (no bit is defined: flags is 0)");
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (n == 0)
+        {
+        // no entry: nothing to stage, nothing to launch
+        std::fill(out_summary, out_summary + COMPONENTS_SUMMARY_WORDS, (uint64_t)0);
+        return PGSD_SUCCESS;
+        }
+    if (a.N == 0)
+        return refuse("an entry of the row list lies outside the position chunk (nothing was computed)");
+    // (the launcher writes the summary on success only, behind its last check)
+    return reduction_call(who, "components: ", [&](std::string* err)
+                          { return device_pipeline_components(s->dev, foff, bytes, a, out_label, out_component, out_sizes,
+                                                              out_summary, err); });
     }
 catch (...)
     {

@@ -14,6 +14,8 @@
 //                      of adjacent cells of a list in cell order (pgsd_cells.hpp: the check and offsets kernels it shares)
 //   pgsd_neighbour_list.hip   neighbour lists: the census' neighbours as a CSR pair list -- count over the same traversal,
 //                      one-workgroup scan, offsets, fill inside the segments
+//   pgsd_components.hip   components: the connected components of the half list's pairs -- a lock-free union-find over
+//                      the same traversal, a flatten pass, the roots numbered by the same scan (pgsd_scan.hpp)
 //   pgsd_sph.hip       the SPH kernel sums: summation density, number density and Shepard sum inside the support 2h, in
 //                      a defined order of the candidates (the same check and offsets kernels)
 //   pgsd_sph_gradients.hip   the SPH kernel gradients: density rate, velocity divergence and curl and the colour gradient

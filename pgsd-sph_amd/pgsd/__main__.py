@@ -27,6 +27,10 @@
            and those nowhere, the pairs, the longest segment and the bytes the list occupies, ``8 (n + 1) + 4 pairs`` and
            ``8 pairs`` more with distances -- what a restart budgets in HBM before it asks (``--half``: each pair once;
            ``--types``; ``pgsd.hoomd.frame_neighbour_list`` on the host: no GPU);
+           ``--components R`` adds the connected components with the linking length R -- the pieces the fluid has broken
+           into: their number, the singletons, the largest with its label and row, the entries nowhere, and with
+           ``--min-size K`` how many components have at least K entries and the share of the entries they hold
+           (``--types``; ``pgsd.hoomd.frame_components`` on the host: no GPU);
            ``--sph [H]`` adds the SPH kernel sums for the smoothing length H (without H: the frame's ``slength``, which
            must be uniform): the search grid and the entries, the range of the summation density, its largest deviation
            from the stored density with the row, the range of the Shepard sum and -- with ``--surface S`` -- the entries
@@ -124,6 +128,8 @@ def _cmd_info(args):
         _print_neighbours(args, frame)
     if args.neighbour_list is not None:
         _print_neighbour_list(args, frame)
+    if args.components is not None:
+        _print_components(args, frame)
     if args.sph is not None:
         _print_sph(args, frame)
     if args.sph_gradients is not None:
@@ -282,6 +288,25 @@ def _print_neighbour_list(args, frame):
     print("  pairs:        %d  longest segment: %d" % (m.pairs, m.longest))
     print("  bytes:        %d  with distances: %d"
           % (hoomd.neighbour_list_bytes(m.n, m.pairs), hoomd.neighbour_list_bytes(m.n, m.pairs, True)))
+
+
+def _print_components(args, frame):
+    """``info --components``: `pgsd.hoomd.frame_components` of one frame with the linking length R, on the host."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_components(traj[frame], args.components, where=where)
+    print("components of frame %d inside %r over %d x %d x %d cells%s:"
+          % ((frame, m.r) + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  entries:      %d  nowhere: %d" % (m.n, m.nowhere))
+    print("  components:   %d  singletons: %d" % (m.components, m.singletons))
+    if m.n:
+        print("  largest:      %d entries, label %d, row %d" % (m.largest, m.largest_label, int(m.rows[m.largest_label])))
+    if args.min_size is not None:
+        kept = m.fragments(args.min_size)
+        held = int(m.sizes[kept].sum())
+        print("  at least %d:   %d components holding %d entries (%.2f %%)"
+              % (args.min_size, len(kept), held, 100.0 * held / m.n if m.n else 0.0))
 
 
 def _print_neighbours(args, frame):
@@ -525,6 +550,11 @@ def main(argv=None):
                    help="print what a neighbour list inside the range R holds: grid, entries, pairs, the longest segment "
                         "and the bytes it occupies, without and with distances")
     p.add_argument('--half', action='store_true', help="with --neighbour-list: each pair once (j > i by list position)")
+    p.add_argument('--components', type=float, default=None, metavar='R',
+                   help="print the connected components with the linking length R: their number, the singletons, the "
+                        "largest with its label and row, the entries nowhere")
+    p.add_argument('--min-size', type=int, default=None, metavar='K',
+                   help="with --components: how many components have at least K entries and their share of the entries")
     p.add_argument('--sph', type=float, nargs='?', const=-1.0, default=None, metavar='H',
                    help="print the SPH kernel sums for the smoothing length H (without H: the frame's uniform slength): "
                         "grid, entries, density range, largest deviation from the stored density, Shepard range")

@@ -2167,6 +2167,52 @@ cdef class PGSDFile:
         return _hoomd.NeighbourList(range_, grid, int(dimensions), bool(half), summary, _device_head(rows, count),
                                     _device_head(cell, count), offsets, neighbours, distance2)
 
+    def components_device(self, frame, name, box, r, cells, rows, cell, n=None, dimensions=3):
+        """The connected components of a row list in cell order within the linking length ``r``, on the GPU: the
+        friends-of-friends grouping whose edges are the pairs of :meth:`neighbour_list_device` with ``half=True``.
+
+        Args:
+            frame, name, box, r, cells, rows, cell, n, dimensions: as :meth:`neighbours_device` takes them.
+
+        Returns:
+            A :class:`pgsd.hoomd.Components`: exactly :func:`pgsd.hoomd.neighbour_components` of the same list -- every
+            label, id, size and summary word.  Its ``rows`` and ``cell`` are the arguments; ``label`` and ``component``
+            (uint32, ``n``) and ``sizes`` (uint32, ``components``: a view of an allocation of ``max(n, 1)`` entries) are
+            library-owned :class:`DeviceBuffer` s on the pipeline's device.  One call,
+            :c:func:`pgsd_components_device`.  The chunk is staged whole unless the ordering left it staged; the staged
+            rows are kept until the next :meth:`wait_read`.  What the library refuses raises ValueError.  Needs no tensor
+            library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry
+        self._entry(frame, name, &entry)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("components_device", cells)
+        range_ = float(r)
+        c_rows, c_cell, count = _cell_ordered_lists("components_device", rows, cell, n)
+        device = self.pipeline_device()
+        summary = numpy.zeros(6, dtype=numpy.uint64)
+        label = DeviceBuffer((max(count, 1),), numpy.uint32, device).view(shape=(count,))
+        component = DeviceBuffer((max(count, 1),), numpy.uint32, device).view(shape=(count,))
+        sizes = DeviceBuffer((max(count, 1),), numpy.uint32, device)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_summary = summary.ctypes.data, p_label = label.ptr, p_component = component.ptr, p_sizes = sizes.ptr
+        cdef uint64_t c_n = count
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef double c_r = range_
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_components_device(&self._handle, &entry, <const double*>p_vectors, c_r, c_dims,
+                                              <const uint32_t*>p_cells, <const uint32_t*>p_rows, <const int32_t*>p_cell, c_n,
+                                              0, <uint32_t*>p_label, <uint32_t*>p_component, <uint32_t*>p_sizes,
+                                              <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("components_device", retval, "refused", self._name, err)
+        return _hoomd.Components(range_, grid, int(dimensions), summary, _device_head(rows, count), _device_head(cell, count),
+                                 label, component, sizes.view(shape=(int(summary[2]),)))
+
     def sph_sums_device(self, frame, name, box, h, cells, rows, cell, n=None, mass=None, density=None, defaults=None,
                         dimensions=3, kernel='wendland_c2', surface_below=None, return_rows=False):
         """The SPH kernel sums of a row list in cell order on the GPU: summation density, number density and Shepard sum

@@ -1953,6 +1953,135 @@ def frame_neighbour_list(frame_or_arrays, r, half=False, distances=False, cells=
     return neighbour_list(position, box, r, rows=rows, cells=cells, dimensions=dimensions, half=half, distances=distances)
 
 
+# ---- components: the definition the GPU pass (`pgsd.fl.PGSDFile.components_device`) equals exactly
+_COMPONENTS_SUMMARY_WORDS = 6       # n, nowhere, components, singletons, largest, largest_label
+
+
+class Components(object):
+    """The connected components of a list in cell order within a linking length (`neighbour_components`).
+
+    Attributes:
+        r (float), grid (``(cx, cy, cz)``), dimensions (int): what was asked.
+        rows, cell: the list in cell order and its cell ids (``n_cells``: nowhere), as on `NeighbourList`.
+        label (uint32, ``n``): the smallest LIST POSITION in the entry's component.
+        component (uint32, ``n``): the dense id -- the number of components whose label is smaller.
+        sizes (uint32, ``components``): ``sizes[c]`` is the number of entries with ``component == c``.
+        n, nowhere (int): the entries, and those without a cell; components (int); singletons (int): the components of
+            one entry, the nowhere entries among them; largest (int): the largest size; largest_label (int): the label of
+            the largest component, among equal sizes the smallest.  All six are 0 at ``n == 0``.
+        `members`, `fragments`: host-side conveniences over numpy arrays; on a result whose arrays were left in GPU memory
+            they raise ValueError -- copy the arrays to the host first.
+    """
+
+    __slots__ = ('r', 'grid', 'dimensions', 'rows', 'cell', 'label', 'component', 'sizes', 'n', 'nowhere', 'components',
+                 'singletons', 'largest', 'largest_label')
+
+    def __init__(self, r, grid, dimensions, summary, rows=None, cell=None, label=None, component=None, sizes=None):
+        """``summary``: the six uint64 words of `pgsd_components_device` -- n, nowhere, components, singletons, largest,
+        largest_label."""
+        s = numpy.asarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _COMPONENTS_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _COMPONENTS_SUMMARY_WORDS)
+        self.r, self.dimensions = float(r), int(dimensions)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.n, self.nowhere, self.components, self.singletons, self.largest, self.largest_label = (int(v) for v in s)
+        self.rows, self.cell, self.label, self.component, self.sizes = rows, cell, label, component, sizes
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return numpy.array([self.n, self.nowhere, self.components, self.singletons, self.largest, self.largest_label],
+                           dtype=numpy.uint64)
+
+    def _host(self, name):
+        x = getattr(self, name)
+        if not isinstance(x, numpy.ndarray):
+            raise ValueError("Components.%s is %s: this works on numpy arrays (copy the arrays to the host first)"
+                             % (name, "not set" if x is None else "in GPU memory"))
+        return x
+
+    def members(self, c):
+        """The list positions of the entries of component ``c``, ascending (the first one is its label)."""
+        component = self._host('component')
+        c = int(c)
+        if not 0 <= c < self.components:
+            raise IndexError("component %d of %d" % (c, self.components))
+        return numpy.nonzero(component == c)[0]
+
+    def fragments(self, min_size=1):
+        """The ids of the components with at least ``min_size`` entries, ascending."""
+        return numpy.nonzero(self._host('sizes') >= int(min_size))[0]
+
+    def __repr__(self):
+        return ("Components(r=%r, grid=%r, n=%d, nowhere=%d, components=%d, singletons=%d, largest=%d, largest_label=%d)"
+                % (self.r, self.grid, self.n, self.nowhere, self.components, self.singletons, self.largest,
+                   self.largest_label))
+
+
+def neighbour_components(position, box, r, rows=None, cells=None, dimensions=3):
+    """The connected components of a row list within the linking length ``r`` -- the friends-of-friends grouping: which
+    pieces has the fluid broken into.  The definition the GPU pass (`pgsd.fl.PGSDFile.components_device`,
+    `HOOMDTrajectory.frame_components_device`) equals exactly.
+
+    The grid, every refusal, the list in cell order and the entries without a cell are `neighbour_list`'s for the same
+    arguments, and so are the arithmetic of one pair and the strict test ``d2 < r*r``.
+
+    **Edges.**  The edges are exactly the pairs of ``neighbour_list(..., half=True)``: ``i`` and ``j`` (``i < j`` by list
+    position) are joined iff ``i -> j`` is inside the range.  At an exact half-box tie in a tilted box ``i -> j`` and ``j
+    -> i`` may differ (`Neighbours` ``.pairs``); the edge is then whatever the half list gives.  A row listed twice is two
+    entries at distance 0, and the two are joined.  An entry without a cell has no edge: it is a component of its own, so
+    the sizes add up to ``n``.
+
+    **The result** is unique and depends on no order of evaluation: ``label`` is the smallest list position in the entry's
+    component, ``component`` the number of components whose label is smaller (components are numbered in ascending order
+    of their smallest member), ``sizes[c]`` the entries with ``component == c``; ``largest_label`` is the label of the
+    largest component, among equal sizes the smallest label.
+
+    Returns a `Components`.  If a frame is read with ``read_frame_device(..., cell_order=grid)`` for the same selection
+    and grid and without a ghost layer, list position ``k`` is row ``k`` of the restarted arrays, so ``label`` indexes
+    them directly and ``component[k]`` belongs to restarted row ``k``.
+    """
+    nl = neighbour_list(position, box, r, rows=rows, cells=cells, dimensions=dimensions, half=True)
+    n = nl.n
+    i = numpy.repeat(numpy.arange(n, dtype=numpy.int64), nl.counts.astype(numpy.int64))
+    j = nl.neighbours.astype(numpy.int64)
+    label = numpy.arange(n, dtype=numpy.int64)
+    while True:                                         # the smallest label travels along the edges, then down the trees
+        low = numpy.minimum(label[i], label[j])
+        before = label.copy()
+        numpy.minimum.at(label, i, low)
+        numpy.minimum.at(label, j, low)
+        while True:
+            down = label[label]
+            if numpy.array_equal(down, label):
+                break
+            label = down
+        if numpy.array_equal(label, before):
+            break
+    roots = numpy.nonzero(label == numpy.arange(n, dtype=numpy.int64))[0]
+    component = numpy.searchsorted(roots, label)
+    sizes = numpy.bincount(component, minlength=roots.shape[0]).astype(numpy.uint32)
+    summary = [n, nl.nowhere, roots.shape[0], int((sizes == 1).sum()), 0, 0]
+    if n:
+        c = int(numpy.argmax(sizes))                    # (the first id that attains the maximum: the smallest label)
+        summary[4], summary[5] = int(sizes[c]), int(roots[c])
+    return Components(nl.r, nl.grid, nl.dimensions, summary, nl.rows, nl.cell, label.astype(numpy.uint32),
+                      component.astype(numpy.uint32), sizes)
+
+
+def frame_components(frame_or_arrays, r, cells=None, where=None, types=None, domain=None, box=None, dimensions=3):
+    """`neighbour_components` of a frame's ``position`` over a selection: the host twin of
+    `HOOMDTrajectory.frame_components_device`, which equals it exactly.  The selection is `frame_neighbour_list`'s and is
+    the list: both ends of an edge come from it.  A position that is stored nowhere puts every row at the origin.
+
+    If the frame is read with ``read_frame_device(idx, where=..., domain=..., cell_order=grid)`` for the same selection
+    and the same grid, without a ghost layer, list position ``k`` is row ``k`` of the restarted arrays, so ``label``
+    indexes them directly.  Returns a `Components`."""
+    _neighbour_range(r)
+    _, position, box, dimensions, _, rows = _sph_frame_list(frame_or_arrays, float(r), where, types, domain, box, dimensions)
+    return neighbour_components(position, box, r, rows=rows, cells=cells, dimensions=dimensions)
+
+
 # ---- SPH kernel sums: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_sums_device`) equals exactly
 SPH_KERNELS = ('wendland_c2', 'cubic_spline')
 _SPH_SUMMARY_WORDS = 13     # n, nowhere, not_finite, surface, deviation_at, deviation_row, 3 x (min, max), deviation
@@ -5205,6 +5334,40 @@ class HOOMDTrajectory(object):
             cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
             got = f.neighbour_list_device(f_pos, 'particles/position', box, r, grid, rows, cell, n=count, dimensions=dims,
                                           half=half, distances=distances)
+        finally:
+            f.wait_read()
+        return got
+
+    def frame_components(self, idx, r, cells=None, where=None, domain=None):
+        """`frame_components` of frame ``idx`` read through the host path: a `Components`.  The definition of
+        `frame_components_device`."""
+        return frame_components(self[int(idx)], r, cells=cells, where=where, domain=domain)
+
+    def frame_components_device(self, idx, r, cells=None, where=None, domain=None):
+        """`frame_components` of frame ``idx``, on the GPU: a `Components` that equals ``frame_components(idx, r, ...)``
+        exactly -- every label, id, size and summary word -- with ``rows``, ``cell``, ``label``, ``component`` and
+        ``sizes`` in GPU memory.
+
+        The selection, the grid, the ordering over the staged position chunk and the one closing `wait_read` are
+        `frame_neighbour_list_device`'s; the pass (`pgsd.fl.PGSDFile.components_device`) runs over the same staged chunk.
+        Read with ``read_frame_device(idx, where=..., domain=..., cell_order=grid)`` for the same selection and grid,
+        without a ghost layer, row ``k`` of the restarted arrays is list position ``k``: ``label`` indexes them directly
+        and ``component[k]`` belongs to restarted row ``k``.  A frame whose position is stored nowhere has no chunk to
+        search and raises ValueError.
+        """
+        idx = self._frame_index(idx)
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        grid = _neighbour_grid(box, r, cells, dims)
+        if f_pos is None:
+            raise ValueError("frame_components_device: the position is stored nowhere (every particle sits at the "
+                             "origin)")
+        try:
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
+            if rows is None:
+                rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
+            cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
+            got = f.components_device(f_pos, 'particles/position', box, r, grid, rows, cell, n=count, dimensions=dims)
         finally:
             f.wait_read()
         return got

@@ -253,6 +253,10 @@ cdef extern from "pgsd_private.h" nogil:
                                    uint32_t dimensions, const uint32_t* cells, const uint32_t* rows, const int32_t* cell,
                                    uint64_t n, uint32_t flags, const uint64_t* offsets, uint64_t capacity,
                                    uint32_t* out_neighbours, double* out_distance2)
+    int pgsd_components_device(pgsd_handle* handle, const pgsd_index_entry* position, const double* vectors, double r,
+                               uint32_t dimensions, const uint32_t* cells, const uint32_t* rows, const int32_t* cell,
+                               uint64_t n, uint32_t flags, uint32_t* out_label, uint32_t* out_component,
+                               uint32_t* out_sizes, uint64_t* out_summary)
     int pgsd_sph_sums_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* mass,
                              const pgsd_index_entry* density, const double* defaults, const double* vectors, double h,
                              uint32_t kernel, uint32_t dimensions, const uint32_t* cells, const uint32_t* rows,
