@@ -22,22 +22,21 @@
 //   cells_long_kernel      lane per slab and value: where the slab holds the first piece of a long cell the lane adds
 //                          that cell's piece sums to +0.0 in ascending order and stores the result
 // No global atomic on a float, no contraction wherever a value is formed or added.  Shared device helpers: pgsd_stats.hpp,
-// pgsd_kernels.hpp; the launchers' host side: pgsd_scratch.hpp.
-#include "pgsd_stats.hpp"
+// pgsd_kernels.hpp; the order of the sum, shared with the component fields: pgsd_pieces.hpp; the launchers' host side:
+// pgsd_scratch.hpp.
+#include "pgsd_pieces.hpp"
 #include "pgsd_cells.hpp"
 #include "pgsd_scratch.hpp"
 
 namespace pgsd_amd
     {
 #define CELLS_WAVES (SEL_THREADS / 64)
-#define CELLS_STEPS (CELLS_PIECE / 64)
 enum
     {
     CELLS_Q = MOMENTS_QUANTITIES,
     CELLS_SLOT_WORDS = CELLS_Q + 1, // nine sums and the bad entries (a 64-bit counter) of a piece
-    CELLS_NO_PIECE = 0xFFFFFFFFu
+    CELLS_NO_PIECE = PIECES_NONE
     };
-static_assert(CELLS_STEPS == SEL_PER_THREAD, "a slab is 16 steps of a wave");
 
 __device__ __forceinline__ void cells_raise(uint32_t* flag_dev, uint32_t* flag_host)
     {
@@ -79,157 +78,72 @@ __global__ __launch_bounds__(SEL_THREADS) void cells_offsets_kernel(const int32_
     offs[c] = (uint32_t)lo;
     }
 
-// Why two slots per slab suffice for the pieces of long cells (cells of more than 1024 entries):
-//   * piece j of a cell whose first entry is s starts at s + 1024 j; with s in slab w that lies in slab w + j, so the
-//     long kernel finds a cell's pieces without a list;
-//   * a slab holds at most one piece of number >= 1: the 1024 entries before such a piece's start belong to its cell, so
-//     a second start of number >= 1 in the same slab would lie in the same cell less than 1024 entries away -- but a
-//     cell's starts are 1024 apart;
-//   * a slab holds at most one FIRST piece of a long cell: the 1024 entries behind its start belong to that cell, so no
-//     other cell starts in the rest of the slab.
-// Slot 0 takes the piece of number >= 1, slot 1 the first piece of a long cell; first[w] is that piece's start, or
-// CELLS_NO_PIECE (every slab's wave writes it: one writer per word, nothing to clear).
+// The walk over a slab's piece starts, the steps of a piece, the nine values and the two-slot partials table (with the
+// argument why two slots suffice) are pgsd_pieces.hpp's, shared with the component fields.  What is the cell fields' own:
+// the segment id is the cell id, the row is the list's, the position is summed as it is, and a piece lands in the result
+// table or in its slot of the partials.
+struct CellsPieces
+    {
+    static constexpr int BATCH_F32 = 4, BATCH_F64 = 2; // steps a lane has in flight (up to 16 and 8 words each)
+    const int32_t* cell;
+    const uint32_t* rows;
+    double* __restrict__ table;
+    uint64_t* __restrict__ table_bad;
+    double* __restrict__ part;
+    uint32_t segments;
+    __device__ __forceinline__ uint32_t id(uint64_t p) const
+        {
+        return (uint32_t)cell[p];
+        }
+    __device__ __forceinline__ bool summed(uint32_t id) const
+        {
+        return (int32_t)id >= 0 && id < segments;
+        }
+    __device__ __forceinline__ void open(uint32_t, uint64_t) const {}
+    __device__ __forceinline__ uint64_t row(uint64_t p, bool ok, int) const
+        {
+        return ok ? rows[p] : 0;
+        }
+    __device__ __forceinline__ void place(double*, bool, int) const {}
+    __device__ __forceinline__ void close(uint32_t c, uint32_t w, bool is_long, bool is_first, const double* sum, uint64_t n_bad,
+                                          uint32_t lane) const
+        {
+        if (lane == 0)
+            {
+            double* out = is_long ? part + ((size_t)2 * w + (is_first ? 1 : 0)) * CELLS_SLOT_WORDS : table + (size_t)c * CELLS_Q;
+#pragma unroll
+            for (int q = 0; q < CELLS_Q; q++)
+                out[q] = sum[q];
+            if (is_long)
+                ((uint64_t*)out)[CELLS_Q] = n_bad;
+            else
+                table_bad[c] = n_bad;
+            }
+        }
+    };
+template<bool F64> struct CellsPiecesOf : CellsPieces
+    {
+    static constexpr int BATCH = F64 ? CellsPieces::BATCH_F64 : CellsPieces::BATCH_F32;
+    };
+
 template<bool F64>
 __global__ __launch_bounds__(SEL_THREADS) void cells_piece_kernel(const CellMomentsArgs s, const uint32_t* __restrict__ offs,
                                                                   const uint32_t* flag_dev, double* __restrict__ table,
                                                                   uint64_t* __restrict__ table_bad, double* __restrict__ part,
                                                                   uint32_t* __restrict__ first, uint32_t n_slabs)
     {
-#pragma clang fp contract(off)
-    constexpr int T = F64 ? STATS_F64 : STATS_F32;
-    constexpr int W1 = F64 ? 2 : 1, W3 = 3 * W1; // 32-bit words of a scalar and of a three-column row
-    constexpr int BATCH = F64 ? 2 : 4;           // steps a lane has in flight (up to 16 and 8 words each)
-    constexpr int Q = CELLS_Q;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * CELLS_WAVES + (threadIdx.x >> 6));
     if (w >= n_slabs || *flag_dev != 0)
         return;
-    const uint64_t n = s.n;
-    const uint64_t base = (uint64_t)w * CELLS_PIECE;
-    const uint32_t* c_mass = (const uint32_t*)s.chunk[1];
-    const uint32_t* c_vel = (const uint32_t*)s.chunk[2];
-    const uint32_t* c_energy = (const uint32_t*)s.chunk[3];
-    const uint32_t* c_pos = (const uint32_t*)s.chunk[4];
-    // the slab's ids, 16 per lane and coalesced; bit j of `starts`: entry base + 64 j + lane starts a piece
-    int32_t id[CELLS_STEPS];
-#pragma unroll
-    for (int j = 0; j < CELLS_STEPS; j++)
-        {
-        const uint64_t k = base + (uint64_t)j * 64 + lane;
-        id[j] = k < n ? s.cell[k] : (int32_t)s.n_cells;
-        }
-    uint32_t starts = 0;
-#pragma unroll
-    for (int j = 0; j < CELLS_STEPS; j++)
-        {
-        const uint64_t k = base + (uint64_t)j * 64 + lane;
-        if (id[j] >= 0 && (uint32_t)id[j] < s.n_cells)
-            {
-            const uint64_t o = min((uint64_t)offs[id[j]], n);
-            if (o <= k && ((k - o) & (CELLS_PIECE - 1)) == 0)
-                starts |= 1u << j;
-            }
-        }
-    uint32_t first_long = CELLS_NO_PIECE;
-    for (int j = 0; j < CELLS_STEPS; j++)
-        {
-        uint64_t mask = __ballot((starts >> j) & 1u);
-        while (mask != 0)
-            {
-            const uint32_t b = (uint32_t)__builtin_ctzll(mask);
-            mask &= mask - 1;
-            const uint64_t at = base + (uint64_t)j * 64 + b; // (wave-uniform, < n: only an entry of the list starts a piece)
-            const uint32_t c = min((uint32_t)__builtin_amdgcn_readfirstlane(s.cell[at]), s.n_cells - 1u);
-            const uint64_t c_lo = min((uint64_t)offs[c], n), c_hi = min((uint64_t)offs[c + 1], n);
-            const uint64_t end = min(at + CELLS_PIECE, c_hi);
-            const bool is_long = c_hi > c_lo && c_hi - c_lo > CELLS_PIECE;
-            const bool is_first = at == c_lo;
-            const uint32_t steps = end > at ? (uint32_t)((end - at + 63) >> 6) : 0u;
-            double acc[Q];
-            uint32_t bad = 0;
-#pragma unroll
-            for (int q = 0; q < Q; q++)
-                acc[q] = 0.0;
-            for (uint32_t t0 = 0; t0 < steps; t0 += BATCH)
-                {
-                RowRegs r_mass[BATCH], r_vel[BATCH], r_energy[BATCH], r_pos[BATCH];
-                bool ok[BATCH];
-#pragma unroll
-                for (int i = 0; i < BATCH; i++)
-                    {
-                    const uint64_t k = at + (uint64_t)(t0 + i) * 64 + lane;
-                    ok[i] = k < end;
-                    const u32x4 zero = {0u, 0u, 0u, 0u};
-                    r_mass[i].lo = r_vel[i].lo = r_vel[i].hi = r_energy[i].lo = r_pos[i].lo = r_pos[i].hi = zero;
-                    const uint64_t row = ok[i] ? s.rows[k] : 0;
-                    ok[i] = ok[i] && row < s.N; // (the check kernel has refused such a list: nothing is loaded for it)
-                    if (ok[i])
-                        {
-                        if (c_mass)
-                            row_load<W1>(c_mass + row * W1, r_mass[i]);
-                        if (c_vel)
-                            row_load<W3>(c_vel + row * W3, r_vel[i]);
-                        if (c_energy)
-                            row_load<W1>(c_energy + row * W1, r_energy[i]);
-                        if (c_pos)
-                            row_load<W3>(c_pos + row * W3, r_pos[i]);
-                        }
-                    }
-#pragma unroll
-                for (int i = 0; i < BATCH; i++)
-                    {
-                    // the nine values of the conservation sums (moments_tile_kernel), in the same association
-                    const double m = c_mass ? stats_elem<T>(r_mass[i], 0) : s.defaults[0];
-                    const double e = c_energy ? stats_elem<T>(r_energy[i], 0) : s.defaults[4];
-                    double v[3], x[3], val[Q];
-#pragma unroll
-                    for (int a = 0; a < 3; a++)
-                        {
-                        v[a] = c_vel ? stats_elem<T>(r_vel[i], a) : s.defaults[1 + a];
-                        x[a] = c_pos ? stats_elem<T>(r_pos[i], a) : s.defaults[5 + a];
-                        }
-                    val[0] = m;
-                    val[4] = (0.5 * m) * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-                    val[5] = m * e;
-#pragma unroll
-                    for (int a = 0; a < 3; a++)
-                        {
-                        val[1 + a] = m * v[a];
-                        val[6 + a] = m * x[a];
-                        }
-                    bool all_fin = true;
-#pragma unroll
-                    for (int q = 0; q < Q; q++)
-                        {
-                        const bool fin = __builtin_fabs(val[q]) < __builtin_huge_val(); // (false for a NaN as well)
-                        all_fin = all_fin && fin;
-                        acc[q] = acc[q] + ((ok[i] && fin) ? val[q] : 0.0);
-                        }
-                    bad += (ok[i] && !all_fin) ? 1u : 0u;
-                    }
-                }
-            double sum[Q];
-#pragma unroll
-            for (int q = 0; q < Q; q++)
-                sum[q] = stats_wave_sum(acc[q]);
-            const uint64_t n_bad = stats_wave_count(bad);
-            if (is_long && is_first)
-                first_long = (uint32_t)at;
-            if (lane == 0)
-                {
-                double* out = is_long ? part + ((size_t)2 * w + (is_first ? 1 : 0)) * CELLS_SLOT_WORDS : table + (size_t)c * Q;
-#pragma unroll
-                for (int q = 0; q < Q; q++)
-                    out[q] = sum[q];
-                if (is_long)
-                    ((uint64_t*)out)[Q] = n_bad;
-                else
-                    table_bad[c] = n_bad;
-                }
-            }
-        }
-    if (lane == 0)
-        first[w] = first_long;
+    CellsPiecesOf<F64> P;
+    P.cell = s.cell;
+    P.rows = s.rows;
+    P.table = table;
+    P.table_bad = table_bad;
+    P.part = part;
+    P.segments = s.n_cells;
+    pieces_walk_slab<F64>(s, P, offs, w, lane, first);
     }
 
 __global__ __launch_bounds__(SEL_THREADS) void cells_long_kernel(const int32_t* __restrict__ cell, const uint32_t* __restrict__ offs,
@@ -248,17 +162,15 @@ __global__ __launch_bounds__(SEL_THREADS) void cells_long_kernel(const int32_t* 
         return;
     const uint32_t c = min((uint32_t)cell[at], n_cells - 1u);
     const uint64_t c_lo = min((uint64_t)offs[c], n), c_hi = min((uint64_t)offs[c + 1], n);
-    const uint64_t pieces = c_hi > c_lo ? (c_hi - c_lo + CELLS_PIECE - 1) / CELLS_PIECE : 0;
     double sum = 0.0;
     uint64_t count = 0;
-    for (uint64_t j = 0; j < pieces && w + j < n_slabs; j++)
-        {
-        const double* slot = part + ((size_t)2 * (w + j) + (j == 0 ? 1 : 0)) * CELLS_SLOT_WORDS;
-        if (q < CELLS_Q)
-            sum = sum + slot[q];
-        else
-            count += ((const uint64_t*)slot)[CELLS_Q];
-        }
+    pieces_long_slots<CELLS_SLOT_WORDS>(part, w, c_lo, c_hi, n_slabs, [&](const double* slot)
+                                        {
+                                        if (q < CELLS_Q)
+                                            sum = sum + slot[q];
+                                        else
+                                            count += ((const uint64_t*)slot)[CELLS_Q];
+                                        });
     if (q < CELLS_Q)
         table[(size_t)c * CELLS_Q + q] = sum;
     else

@@ -213,6 +213,7 @@ int DevicePipeline::init()
         warm_neighbours_kernels();
         warm_neighbour_list_kernels();
         warm_components_kernels();
+        warm_component_moments_kernels();
         warm_sph_kernels();
         warm_sph_gradients_kernels();
         warm_sph_forces_kernels();

@@ -704,6 +704,16 @@ int device_pipeline_components(DevicePipeline* p, long long file_offset, size_t 
                           { return launch_components(a, out_label, out_component, out_sizes, out_summary, stream, why); });
     }
 
+// Component fields: the cell fields' staging; the lists and every output array are the caller's.
+int device_pipeline_component_moments(DevicePipeline* p, const ChunkRange* ranges, const ComponentMomentsArgs& args,
+                                      double* out_sums, double* out_extent, double* out_origin, uint32_t* out_flags,
+                                      uint64_t* out_summary, std::string* err)
+    {
+    ComponentMomentsArgs c = args;
+    return grouped_pass(p, ranges, c, err, [&](hipStream_t stream, std::string* why)
+                        { return launch_component_moments(c, out_sums, out_extent, out_origin, out_flags, out_summary, stream, why); });
+    }
+
 int DevicePipeline::wait_read()
     {
     if (!m_ok)

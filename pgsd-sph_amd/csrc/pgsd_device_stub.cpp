@@ -48,6 +48,7 @@ int device_pipeline_sph_samples(DevicePipeline*, const ChunkRange*, const SphSam
 int device_pipeline_neighbour_offsets(DevicePipeline*, long long, size_t, const NeighbourListArgs&, uint64_t*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_neighbour_list(DevicePipeline*, long long, size_t, const NeighbourListArgs&, const uint64_t*, uint64_t, uint32_t*, double*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_components(DevicePipeline*, long long, size_t, const NeighboursArgs&, uint32_t*, uint32_t*, uint32_t*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
+int device_pipeline_component_moments(DevicePipeline*, const ChunkRange*, const ComponentMomentsArgs&, double*, double*, double*, uint32_t*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_plan_rows(DevicePipeline*, RowPlan&, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_read_planned(DevicePipeline*, long long, size_t, const pgsd_unpack_job&, const RowPlan&, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 void device_pipeline_read_counters(DevicePipeline*, uint64_t* a, uint64_t* b, int) { if (a) *a = 0; if (b) *b = 0; }

@@ -717,6 +717,30 @@ enum
 int device_pipeline_components(DevicePipeline*, long long file_offset, size_t bytes, const NeighboursArgs& a,
                                uint32_t* out_label, uint32_t* out_component, uint32_t* out_sizes, uint64_t* out_summary,
                                std::string* err);
+// Component fields (pgsd.hoomd.component_moments is the definition): per component of a components result the nine sums
+// of the cell fields with the position replaced by the single-shift minimum-image displacement from the component's root
+// (its smallest member), in the cell fields' order over the component's entries in list order; the extent of those
+// displacements, the root's position, and whether the extent reaches half a box length (the piece may percolate).
+enum
+    {
+    CMOM_SUMMARY_WORDS = 6, // n, components, bad entries, wide components, heaviest, widest
+    CMOM_EXTENT = 6         // lo[3], hi[3]
+    };
+struct ComponentMomentsArgs : GroupedArgs // chunk: the conservation sums' order; the typeid slot stays empty
+    {
+    double defaults[8];        // mass, v[3], energy, x[3] (the position is always a chunk: x is not looked at)
+    double vectors[6];         // Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz
+    const uint32_t* label;     // device, n: the smallest list position of the entry's component
+    const uint32_t* component; // device, n: the dense id
+    uint32_t components;
+    uint32_t dimensions;
+    };
+// stage the chunks that are present, check, sort and sum on the GPU; the results land in the caller's device arrays and
+// out_summary (host, 6 words) is written on success only; synchronous.  c.n > 0.  The staged rows stay until the next
+// wait_read.
+int device_pipeline_component_moments(DevicePipeline*, const ChunkRange* ranges, const ComponentMomentsArgs& c,
+                                      double* out_sums, double* out_extent, double* out_origin, uint32_t* out_flags,
+                                      uint64_t* out_summary, std::string* err);
 // A row plan (sparse indexed reads): the chunk's N rows cut into blocks of R rows; `blocks` are the blocks that hold at
 // least one of rows[0 .. n) (ascending: block b's slot in the compact staging is its position in this list), merged
 // into runs of neighbours (run_first[i], run_blocks[i]); rows2[k] = slot * R + rows[k] % R indexes that staging, whose

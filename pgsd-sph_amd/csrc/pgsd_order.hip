@@ -278,6 +278,34 @@ static unsigned order_passes(uint64_t max_key)
     return (bits + SORT_DIGIT_BITS - 1) / SORT_DIGIT_BITS;
     }
 
+// The sort alone, for a unit whose keys are not grid cells (pgsd_component_moments.hip): the passes of order_passes(max_key)
+// over the caller's (key, value) pairs, enqueued on `stream` with no synchronisation.  keys[0] / vals[0] hold the n pairs,
+// keys[1] / vals[1] are their ping-pong twins, table takes sort_pairs_table_words(n) words and totals 256; the result lies
+// in keys[r] / vals[r] for the returned r.  A key above max_key is sorted by its low digits only; no store lands at an
+// index >= n whatever the keys hold.
+size_t sort_pairs_table_words(uint64_t n)
+    {
+    return (size_t)SORT_RADIX * (size_t)((n + SORT_TILE - 1) / SORT_TILE);
+    }
+
+unsigned enqueue_sort_pairs(uint32_t* const keys[2], uint32_t* const vals[2], uint32_t* table, uint32_t* totals, uint64_t n,
+                            uint64_t max_key, hipStream_t stream)
+    {
+    const uint64_t n_tiles = (n + SORT_TILE - 1) / SORT_TILE;
+    const dim3 block(SEL_THREADS), per_tile((unsigned)n_tiles);
+    const unsigned passes = order_passes(max_key);
+    unsigned cur = 0;
+    for (unsigned p = 0; p < passes; p++, cur ^= 1u)
+        {
+        const uint32_t at = p * SORT_DIGIT_BITS;
+        hipLaunchKernelGGL(radix_hist_kernel, per_tile, block, 0, stream, keys[cur], n, at, (uint32_t)n_tiles, table);
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(SORT_RADIX), block, 0, stream, table, (uint32_t)n_tiles, totals);
+        hipLaunchKernelGGL(radix_scatter_kernel, per_tile, block, 0, stream, keys[cur], vals[cur], n, at, (uint32_t)n_tiles,
+                           table, totals, keys[cur ^ 1u], vals[cur ^ 1u]);
+        }
+    return cur;
+    }
+
 int launch_order_rows(const OrderArgs& o, uint32_t* rows, int32_t* shift, int32_t* out_cell, hipStream_t stream,
                       std::string* err)
     {

@@ -265,6 +265,13 @@ int launch_cell_counts(const CellArgs& c, uint64_t* out_counts, uint64_t* out_no
 // is >= o.d.N
 int launch_order_rows(const OrderArgs& o, uint32_t* rows, int32_t* shift, int32_t* out_cell, hipStream_t stream,
                       std::string* err);
+// the cell order's radix sort alone, for keys that are no grid cells (pgsd_component_moments.hip): the 8-bit passes that
+// cover max_key over (key, value) pairs in the caller's memory -- keys[0] / vals[0] in, keys[1] / vals[1] their twins, table
+// of sort_pairs_table_words(n) words, totals of 256 --, enqueued on `stream` without a synchronisation; the sorted pairs
+// lie in keys[r] / vals[r] of the returned r.  Stable; no store at an index >= n whatever the keys hold
+size_t sort_pairs_table_words(uint64_t n);
+unsigned enqueue_sort_pairs(uint32_t* const keys[2], uint32_t* const vals[2], uint32_t* table, uint32_t* totals, uint64_t n,
+                            uint64_t max_key, hipStream_t stream);
 
 // chunk statistics (StatsArgs, base filled in): one pass of a workgroup per tile of 4096 entries, one workgroup over the
 // tiles' partial results; out_counts / out_values (host, C x 3 each) are written on success only; synchronises `stream`.
@@ -294,6 +301,16 @@ int launch_frame_displacements(const DisplacementArgs& d, uint64_t* out_counts, 
 int launch_cell_offsets(const int32_t* cell, uint64_t n, uint32_t n_cells, uint32_t* out_offsets, hipStream_t stream,
                         std::string* err);
 int launch_cell_moments(const CellMomentsArgs& c, uint64_t* out_counts, double* out_sums, hipStream_t stream, std::string* err);
+
+// component fields (pgsd_component_moments.hip; ComponentMomentsArgs, the addresses of the chunks that are present filled
+// in): check, stable sort of the entries by component, offsets, a second check of the numbering, one wave per slab of 1024
+// sorted entries, one lane per slab and word for the components of more than 1024 entries, two kernels for the flags and
+// the summary.  out_sums (device, components x 9), out_extent (device, components x 6), out_origin (device, components x
+// 3), out_flags (device, components x 2 uint32: bad, wide); out_summary (host, 6 words: n, components, bad, wide, heaviest,
+// widest) is written on success only.  Synchronises `stream`; PGSD_ERROR_INVALID_ARGUMENT, with no output touched, for
+// labels and ids that are not a components result of this list and for an entry >= c.N
+int launch_component_moments(const ComponentMomentsArgs& c, double* out_sums, double* out_extent, double* out_origin,
+                             uint32_t* out_flags, uint64_t* out_summary, hipStream_t stream, std::string* err);
 
 // neighbour census (pgsd_neighbours.hip; NeighboursArgs, a.pos filled in): check, offsets, compaction of the listed
 // positions, one lane per entry over the runs of the adjacent cells, one workgroup for the minima.  edges2 (host, a.bins
@@ -430,6 +447,7 @@ void warm_cells_kernels();
 void warm_neighbours_kernels();
 void warm_neighbour_list_kernels();
 void warm_components_kernels();
+void warm_component_moments_kernels();
 void warm_sph_kernels();
 void warm_sph_gradients_kernels();
 void warm_sph_forces_kernels();

@@ -51,6 +51,10 @@
  *                     the connected components of the half list's pairs -- which pieces has the fluid broken into, how
  *                     many droplets and stray particles are there -- as a label, a dense id and the sizes, by a lock-free
  *                     union-find over the same traversal)
+ *                     pgsd_component_moments_device (pgsd.fl's component_moments_device, behind pgsd.hoomd's
+ *                     frame_component_moments_device: what each of those pieces is -- mass, momentum, energies, centre
+ *                     and extent per component, the cell fields' sums over the entries sorted by component, positions
+ *                     as displacements from the component's root, and a flag for a piece that spans half the box)
  *                     pgsd_sph_sums_device (pgsd.fl's sph_sums_device, behind pgsd.hoomd's frame_kernel_sums_device: per
  *                     entry of a row list in cell order the SPH summation density, number density and Shepard sum over
  *                     the kernel support, in a defined order, and over the list their ranges, the largest deviation from
@@ -472,6 +476,40 @@ extern "C"
                                double r, uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
                                const int32_t* cell, uint64_t n, uint32_t flags, uint32_t* out_label,
                                uint32_t* out_component, uint32_t* out_sizes, uint64_t* out_summary);
+
+    /* Component fields (pgsd.hoomd.component_moments is the definition, and the results equal it exactly, every float bit
+       for bit): what each piece of a pgsd_components_device result IS -- per component the nine sums of
+       pgsd_cell_moments_device with the position replaced by the displacement d from the component's ROOT (the entry at
+       list position `label`, its smallest member) to the entry under HOOMD's single-shift minimum image (the arithmetic
+       of one pair of pgsd_neighbours_device; the root's own d is +0.0 by definition), the extent of those displacements
+       and the root's position.  The order of a component's sum is the cell fields' over the component's entries in list
+       order.  mass, velocity, energy, position and defaults are pgsd_cell_moments_device's; the position chunk is
+       required (a position that is stored nowhere is refused).  vectors: Lx, Ly, Lz, xy*Ly, xz*Lz, yz*Lz; dimensions: 2
+       or 3 (2: z is never looked at and d_z is 0).  rows, label, component: device memory, n uint32 each, the list and
+       what pgsd_components_device wrote for it; components: its summary's third word.  flags must be 0.
+           out_sums     device memory, components x 9 float64: mass, momentum[3], kinetic, internal, sum of m d[3]
+           out_extent   device memory, components x 6 float64: lo[3], hi[3] of the finite d of the component, from +0.0
+                        (the root's) by strict comparisons: neither is ever -0.0
+           out_origin   device memory, components x 3 float64: the root's position
+           out_flags    device memory, components x 2 uint32: the entries with a value that is not finite, and `wide`:
+                        1 if hi - lo >= L / 2 on an axis below `dimensions` -- the piece percolates or nearly does, and
+                        its origin-relative centre and extent are reported but not meaningful; 0 guarantees that d is
+                        the piece's one consistent unwrapping
+           out_summary  host, 6 uint64, written on success only: n; components; the bad entries; the wide components;
+                        the id of the largest mass sum and of the largest extent over the axes, among equals the smallest
+                        id (a sum that is a NaN counts as -inf)
+       No store lands at an index >= components of any output.  Refused, with no output touched: label[k] > k, a label
+       that is no root, an id >= components, an id other than its root's, ids that are not the dense ascending numbering
+       of the labels, rows[k] >= N.  The chunks are staged whole unless an earlier call left them staged; the pass runs on
+       the pipeline's stream and the call synchronises; the staged rows are kept until the next pgsd_device_wait_read.
+       n == 0 stages nothing and launches no kernel: the summary is six zeros. */
+    int pgsd_component_moments_device(struct pgsd_handle* handle, const struct pgsd_index_entry* mass,
+                                      const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* energy,
+                                      const struct pgsd_index_entry* position, const double defaults[8],
+                                      const double vectors[6], uint32_t dimensions, const uint32_t* rows, const uint32_t* label,
+                                      const uint32_t* component, uint64_t n, uint64_t components, uint32_t flags,
+                                      double* out_sums, double* out_extent, double* out_origin, uint32_t* out_flags,
+                                      uint64_t* out_summary);
 
     /* SPH kernel sums (pgsd.hoomd.sph_kernel_sums is the definition, and the results equal it exactly: every counter and
        index, every float bit for bit -- a NaN is a NaN, its sign and payload are the processor's).  position: an N x 3

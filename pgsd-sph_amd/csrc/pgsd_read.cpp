@@ -1195,6 +1195,73 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_component_moments_device(struct pgsd_handle* handle, const struct pgsd_index_entry* mass,
+                                             const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* energy,
+                                             const struct pgsd_index_entry* position, const double defaults[8],
+                                             const double vectors[6], uint32_t dimensions, const uint32_t* rows,
+                                             const uint32_t* label, const uint32_t* component, uint64_t n, uint64_t components,
+                                             uint32_t flags, double* out_sums, double* out_extent, double* out_origin,
+                                             uint32_t* out_flags, uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_component_moments_device";
+    Impl* s = impl_of(handle);
+    if (!s || !defaults || !vectors || !out_summary
+        || (n > 0 && (!rows || !label || !component || !out_sums || !out_extent || !out_origin || !out_flags)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    // what needs no chunk is refused first
+    if (!position)
+        return refuse("the position is stored nowhere: a component's origin and extent need the position chunk");
+    if (dimensions != 2 && dimensions != 3)
+        return refuse("dimensions is 2 or 3");
+    for (int i = 0; i < 6; i++)
+        if (!std::isfinite(vectors[i]))
+            return refuse("the box vectors are finite");
+    if (!(vectors[0] > 0.0) || !(vectors[1] > 0.0) || (dimensions == 3 && !(vectors[2] > 0.0)))
+        return refuse("the box lengths are positive");
+    if (flags != 0)
+        return refuse("flags holds undefined bits (no bit is defined: flags is 0)");
+    if (n >= (1ull << 32))
+        return refuse("a list holds fewer than 2^32 entries");
+    if (components > n || (n > 0 && components == 0))
+        return refuse("a list of n entries has 1 to n components (none for n == 0)");
+    const struct pgsd_index_entry* given[MOMENTS_CHUNKS] = {nullptr, mass, velocity, energy, position};
+    ComponentMomentsArgs a;
+    memset(&a, 0, sizeof(a));
+    ChunkRange ranges[MOMENTS_CHUNKS];
+    memset(ranges, 0, sizeof(ranges));
+    std::string why;
+    int rc = grouped_chunks(s, handle, g_moments_slots, "float", given, &a, ranges, &why);
+    if (rc != PGSD_SUCCESS)
+        return why.empty() ? rc : refuse(why);
+    if (n == 0)
+        {
+        // no entry: nothing to stage, nothing to launch
+        std::fill(out_summary, out_summary + CMOM_SUMMARY_WORDS, (uint64_t)0);
+        return PGSD_SUCCESS;
+        }
+    if (a.N == 0)
+        return refuse("an entry of the row list lies outside the chunks (nothing was computed)");
+    std::copy(defaults, defaults + 8, a.defaults);
+    std::copy(vectors, vectors + 6, a.vectors);
+    a.rows = rows;
+    a.label = label;
+    a.component = component;
+    a.n = n;
+    a.components = (uint32_t)components;
+    a.dimensions = dimensions;
+    a.n_types = 1;
+    // (the launcher writes the summary on success only, behind its last check)
+    return reduction_call(who, "component fields: ", [&](std::string* err)
+                          { return device_pipeline_component_moments(s->dev, ranges, a, out_sums, out_extent, out_origin,
+                                                                     out_flags, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 // What pgsd_sph_sums_device, pgsd_sph_gradients_device, pgsd_sph_accelerations_device and pgsd_sph_samples_device (which
 // takes the sums' part of it and checks its value chunks, its points and its box itself) share: every refusal of the
 // first (and, for the other two, of a velocity chunk; for the last, of a pressure chunk), the ranges of the chunks that

@@ -8,7 +8,8 @@
 // The families keep one Scratch each and share two locks: g_select_lock covers the compaction (selections, row plan,
 // pgsd_select_rows), the census and the cell order; the reductions of pgsd_stats.hip have their own, and so have the
 // cell fields of pgsd_cells.hip, the neighbour census of pgsd_neighbours.hip, the neighbour lists of
-// pgsd_neighbour_list.hip, the components of pgsd_components.hip, the SPH kernel sums of pgsd_sph.hip, the SPH kernel gradients of pgsd_sph_gradients.hip, the
+// pgsd_neighbour_list.hip, the components of pgsd_components.hip, the component fields of
+// pgsd_component_moments.hip, the SPH kernel sums of pgsd_sph.hip, the SPH kernel gradients of pgsd_sph_gradients.hip, the
 // SPH accelerations of pgsd_sph_forces.hip and the SPH samples of pgsd_sph_samples.hip (each with a Scratch of its own).  Neither the
 // locks nor the allocations are merged: that would change what may run concurrently and how much memory is held.
 #ifndef PGSD_SCRATCH_HPP

@@ -16,6 +16,8 @@
 //                      one-workgroup scan, offsets, fill inside the segments
 //   pgsd_components.hip   components: the connected components of the half list's pairs -- a lock-free union-find over
 //                      the same traversal, a flatten pass, the roots numbered by the same scan (pgsd_scan.hpp)
+//   pgsd_component_moments.hip   component fields: the cell fields' segmented sums per component -- the entries sorted by
+//                      dense id with the cell order's radix sort, the position as the displacement from the component's root
 //   pgsd_sph.hip       the SPH kernel sums: summation density, number density and Shepard sum inside the support 2h, in
 //                      a defined order of the candidates (the same check and offsets kernels)
 //   pgsd_sph_gradients.hip   the SPH kernel gradients: density rate, velocity divergence and curl and the colour gradient

@@ -1,5 +1,6 @@
 // pgsd_stats.hpp -- device helpers the reductions share (pgsd_stats.hip: chunk statistics and the grouped reductions;
-// pgsd_cells.hip: the per-cell sums): an element of a row in registers as a double, and the wave part of the block tree.
+// pgsd_pieces.hpp: the segmented sums of pgsd_cells.hip and pgsd_component_moments.hip): an element of a row in registers
+// as a double, and the wave part of the block tree.
 // Seen by the HIP compiler alone.
 #ifndef PGSD_STATS_HPP
 #define PGSD_STATS_HPP

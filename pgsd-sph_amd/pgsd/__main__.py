@@ -30,7 +30,11 @@
            ``--components R`` adds the connected components with the linking length R -- the pieces the fluid has broken
            into: their number, the singletons, the largest with its label and row, the entries nowhere, and with
            ``--min-size K`` how many components have at least K entries and the share of the entries they hold
-           (``--types``; ``pgsd.hoomd.frame_components`` on the host: no GPU);
+           (``--types``; ``pgsd.hoomd.frame_components`` on the host: no GPU), and with ``--pieces [K]`` what the K
+           heaviest pieces (default 10) are: size, mass, centre of mass, mean velocity, span and whether the piece is
+           ``wide`` -- its extent reaches half a box length, so it percolates or nearly does and its centre and span are
+           not meaningful --, then the number of wide pieces and of entries with a value that is not finite
+           (``pgsd.hoomd.frame_component_moments`` on the host: no GPU);
            ``--sph [H]`` adds the SPH kernel sums for the smoothing length H (without H: the frame's ``slength``, which
            must be uniform): the search grid and the entries, the range of the summation density, its largest deviation
            from the stored density with the row, the range of the Shepard sum and -- with ``--surface S`` -- the entries
@@ -307,6 +311,19 @@ def _print_components(args, frame):
         held = int(m.sizes[kept].sum())
         print("  at least %d:   %d components holding %d entries (%.2f %%)"
               % (args.min_size, len(kept), held, 100.0 * held / m.n if m.n else 0.0))
+    if args.pieces is not None:
+        with hoomd.open(args.file, 'r') as traj:
+            p = hoomd.frame_component_moments(traj[frame], args.components, where=where)
+        ids = p.heaviest(args.pieces)
+        print("  the %d heaviest of %d pieces (centre, mean velocity and span per axis):" % (len(ids), p.components))
+        triple = lambda v: "(%s)" % ", ".join("%.6g" % x for x in v)    # noqa: E731
+        centre, velocity, span = p.centre_of_mass, p.mean_velocity, p.span
+        for c in ids:
+            print("    piece %d: %d entries, mass %.6g, centre %s, velocity %s, span %s%s"
+                  % (c, int(p.sizes[c]), p.mass[c], triple(centre[c]), triple(velocity[c]), triple(span[c]),
+                     "  WIDE" if p.wide[c] else ""))
+        print("  wide pieces:  %d  (extent >= half a box length: centre and span are not meaningful)" % p.wide_components)
+        print("  bad entries:  %d  (a value that is not finite; left out of the sums)" % p.bad_entries)
 
 
 def _print_neighbours(args, frame):
@@ -553,6 +570,9 @@ def main(argv=None):
     p.add_argument('--components', type=float, default=None, metavar='R',
                    help="print the connected components with the linking length R: their number, the singletons, the "
                         "largest with its label and row, the entries nowhere")
+    p.add_argument('--pieces', type=int, nargs='?', const=10, default=None, metavar='K',
+                   help="with --components: print the K heaviest pieces (default 10) -- size, mass, centre, mean velocity, "
+                        "span, wide -- and the number of wide pieces and of bad entries")
     p.add_argument('--min-size', type=int, default=None, metavar='K',
                    help="with --components: how many components have at least K entries and their share of the entries")
     p.add_argument('--sph', type=float, nargs='?', const=-1.0, default=None, metavar='H',

@@ -2213,6 +2213,68 @@ cdef class PGSDFile:
         return _hoomd.Components(range_, grid, int(dimensions), summary, _device_head(rows, count), _device_head(cell, count),
                                  label, component, sizes.view(shape=(int(summary[2]),)))
 
+    def component_moments_device(self, chunks, box, rows, label, component, n, components, defaults=None, dimensions=3):
+        """Mass, momentum, energies, centre and extent per connected component of a row list, on the GPU: what each piece
+        of a :meth:`components_device` result is.
+
+        Args:
+            chunks: four entries in the order mass, velocity, energy, position, each ``(frame, name)`` or ``None``:
+                stored nowhere, as :meth:`cell_moments_device` takes them.  The position is required.
+            box: ``(Lx, Ly, Lz, xy, xz, yz)``; dimensions: 2 or 3.
+            rows, label, component: 32-bit arrays in GPU memory, ``n`` entries each: the list and what
+                :meth:`components_device` returned for it (``rows``, ``label``, ``component`` of its result).
+            n (int): the entries (``None``: all of ``rows``); components (int): the result's ``components``.
+            defaults: as :meth:`frame_moments_device`'s.
+
+        Returns:
+            A :class:`pgsd.hoomd.ComponentMoments` whose tables are library-owned :class:`DeviceBuffer` s on the
+            pipeline's device, allocated at ``max(components, 1)`` rows and viewed at ``components``: exactly
+            :func:`pgsd.hoomd.component_moments`, every float bit for bit.  ``to_host()`` copies the tables.  One call,
+            :c:func:`pgsd_component_moments_device`.  The chunks are staged whole unless an earlier call left them
+            staged; the staged rows are kept until the next :meth:`wait_read`.  Labels and ids that are not a components
+            result of the list and an entry outside the chunks raise ValueError.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entries[5]
+        cdef const C.pgsd_index_entry* given[5]
+        chunks = list(chunks)
+        if len(chunks) != 4:
+            raise ValueError("component_moments_device: chunks holds mass, velocity, energy, position (or None)")
+        self._entries([None] + chunks, entries, given)
+        c_defaults = _moments_defaults("component_moments_device", defaults)
+        c_vectors = _box_vectors(box)
+        c_rows, count = _row_list("component_moments_device", rows, n)
+        c_label = _row_list("component_moments_device", label, count)[0]
+        c_component = _row_list("component_moments_device", component, count)[0]
+        pieces = int(components)
+        if not 0 <= pieces < (1 << 32):
+            raise ValueError("component_moments_device: a list of n entries has 1 to n components")
+        device = self.pipeline_device()
+        T = max(pieces, 1)
+        summary = numpy.zeros(6, dtype=numpy.uint64)
+        sums = DeviceBuffer((T, 9), numpy.float64, device).view(shape=(pieces, 9))
+        extent = DeviceBuffer((T, 6), numpy.float64, device).view(shape=(pieces, 6))
+        origin = DeviceBuffer((T, 3), numpy.float64, device).view(shape=(pieces, 3))
+        flags = DeviceBuffer((T, 2), numpy.uint32, device).view(shape=(pieces, 2))
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of the lists
+        cdef uintptr_t p_rows = c_rows, p_label = c_label, p_component = c_component
+        cdef uintptr_t p_def = c_defaults.ctypes.data, p_vectors = c_vectors.ctypes.data, p_summary = summary.ctypes.data
+        cdef uintptr_t p_sums = sums.ptr, p_extent = extent.ptr, p_origin = origin.ptr, p_flags = flags.ptr
+        cdef uint64_t c_n = count, c_pieces = pieces
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_component_moments_device(&self._handle, given[1], given[2], given[3], given[4],
+                                                     <const double*>p_def, <const double*>p_vectors, c_dims,
+                                                     <const uint32_t*>p_rows, <const uint32_t*>p_label,
+                                                     <const uint32_t*>p_component, c_n, c_pieces, 0, <double*>p_sums,
+                                                     <double*>p_extent, <double*>p_origin, <uint32_t*>p_flags,
+                                                     <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("component_moments_device", retval, "refused", self._name, err)
+        return _hoomd.ComponentMoments.from_tables(summary, sums, extent, origin, flags)
+
     def sph_sums_device(self, frame, name, box, h, cells, rows, cell, n=None, mass=None, density=None, defaults=None,
                         dimensions=3, kernel='wendland_c2', surface_below=None, return_rows=False):
         """The SPH kernel sums of a row list in cell order on the GPU: summation density, number density and Shepard sum

@@ -1205,9 +1205,11 @@ def _moments_rows(n_rows, rows):
     return n_rows, rows, n_rows if rows is None else rows.shape[0]
 
 
-def _moments_values(arrays, dt, rows, n):
+def _moments_values(arrays, dt, rows, n, x=None):
     """The nine float64 values per entry of `particle_moments`: ``(values, finite, all_finite)``, nine arrays of ``n``
-    values, the same of flags "is finite", and their conjunction.  The one place where the values are formed."""
+    values, the same of flags "is finite", and their conjunction.  The one place where the values are formed.  ``x``:
+    three float64 arrays of ``n`` values that stand in for the position's columns (`component_moments`: the
+    displacements from the root)."""
     dt = numpy.dtype(numpy.float64) if dt is None else dt
 
     def column(name, c):
@@ -1219,7 +1221,7 @@ def _moments_values(arrays, dt, rows, n):
 
     m, e = column('mass', 0), column('energy', 0)
     v = [column('velocity', a) for a in range(3)]
-    x = [column('position', a) for a in range(3)]
+    x = [column('position', a) for a in range(3)] if x is None else [numpy.asarray(c, dtype=numpy.float64) for c in x]
     with numpy.errstate(over='ignore', invalid='ignore', under='ignore'):
         values = ([m] + [m * v[a] for a in range(3)]
                   + [(0.5 * m) * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]), m * e] + [m * x[a] for a in range(3)])
@@ -2080,6 +2082,247 @@ def frame_components(frame_or_arrays, r, cells=None, where=None, types=None, dom
     _neighbour_range(r)
     _, position, box, dimensions, _, rows = _sph_frame_list(frame_or_arrays, float(r), where, types, domain, box, dimensions)
     return neighbour_components(position, box, r, rows=rows, cells=cells, dimensions=dimensions)
+
+
+# ---- component fields: the definition the GPU pass (`pgsd.fl.PGSDFile.component_moments_device`) equals exactly
+_CMOM_SUMMARY_WORDS = 6     # n, components, bad, wide, heaviest, widest
+
+
+class ComponentMoments(object):
+    """What each connected component of a `Components` result is (`component_moments`): arrays of one entry (or one row)
+    per component, in the order of the dense ids.
+
+    Attributes:
+        sizes (``components``): the entries of the component (``components_of.sizes``; ``None`` without it).
+        bad (uint32): the entries at which at least one of the nine per-entry values is not finite.
+        wide (uint32): 1 if the extent reaches half a box length on an axis: the piece percolates, or nearly does, and
+            its `centre_of_mass`, ``lo``, ``hi`` and `span` are reported but not meaningful.  0 guarantees that the
+            displacements are the piece's one consistent unwrapping.
+        mass, kinetic, internal (float64); momentum (float64, x 3): as `CellMoments`'.
+        first_moment (float64, x 3): the sum of ``m d``, ``d`` the displacement from the component's root to the entry.
+        origin (float64, x 3): the root's position; lo, hi (float64, x 3): the extent of the finite ``d``.
+        n, components, bad_entries, wide_components, heaviest_id, widest_id (int): the summary words.
+        components_of: the `Components` this was made from, or ``None``.
+        mean_velocity, centre_of_mass, span (properties), `heaviest`: host-side conveniences over numpy arrays; on a
+            result whose tables were left in GPU memory they raise ValueError -- `to_host` copies the tables first.
+    """
+
+    __slots__ = ('sizes', 'bad', 'wide', 'mass', 'momentum', 'kinetic', 'internal', 'first_moment', 'origin', 'lo', 'hi',
+                 'n', 'components', 'bad_entries', 'wide_components', 'heaviest_id', 'widest_id', 'components_of', '_tables')
+
+    def __init__(self, summary, bad, wide, mass, momentum, kinetic, internal, first_moment, origin, lo, hi, sizes=None,
+                 components_of=None, tables=None):
+        s = numpy.asarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _CMOM_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _CMOM_SUMMARY_WORDS)
+        self.n, self.components, self.bad_entries, self.wide_components, self.heaviest_id, self.widest_id = (int(v) for v in s)
+        self.bad, self.wide, self.mass, self.momentum, self.kinetic, self.internal = bad, wide, mass, momentum, kinetic, internal
+        self.first_moment, self.origin, self.lo, self.hi = first_moment, origin, lo, hi
+        self.sizes, self.components_of, self._tables = sizes, components_of, tables
+
+    @classmethod
+    def from_tables(cls, summary, sums, extent, origin, flags, sizes=None, components_of=None):
+        """From the tables of `pgsd_component_moments_device`: ``sums`` (``components x 9``, the order of the per-entry
+        values), ``extent`` (``x 6``: lo, hi), ``origin`` (``x 3``), ``flags`` (``x 2`` uint32: bad, wide).  numpy arrays
+        are cut into the attributes; tables in GPU memory become strided views of them."""
+        if isinstance(sums, numpy.ndarray):
+            s = numpy.asarray(sums, dtype=numpy.float64).reshape(-1, _MOMENTS_QUANTITIES)
+            e = numpy.asarray(extent, dtype=numpy.float64).reshape(-1, 6)
+            f = numpy.asarray(flags, dtype=numpy.uint32).reshape(-1, 2)
+            o = numpy.asarray(origin, dtype=numpy.float64).reshape(-1, 3)
+            return cls(summary, f[:, 0].copy(), f[:, 1].copy(), s[:, 0].copy(), s[:, 1:4].copy(), s[:, 4].copy(),
+                       s[:, 5].copy(), s[:, 6:9].copy(), o.copy(), e[:, 0:3].copy(), e[:, 3:6].copy(), sizes, components_of)
+        T = int(sums.shape[0])
+
+        def cut(table, width, item, first, M):
+            shape, strides = ((T,), (width * item,)) if M == 1 else ((T, M), (width * item, item))
+            if T == 0:                          # (no component: an empty view has nothing to stride over)
+                return table.view(shape=shape)
+            return table.view(shape=shape, strides=strides, offset_bytes=first * item)
+
+        return cls(summary, cut(flags, 2, 4, 0, 1), cut(flags, 2, 4, 1, 1), cut(sums, 9, 8, 0, 1), cut(sums, 9, 8, 1, 3),
+                   cut(sums, 9, 8, 4, 1), cut(sums, 9, 8, 5, 1), cut(sums, 9, 8, 6, 3), origin, cut(extent, 6, 8, 0, 3),
+                   cut(extent, 6, 8, 3, 3), sizes, components_of, (sums, extent, origin, flags))
+
+    def to_host(self):
+        """The same result over numpy arrays: four device-to-host copies of the tables (and one of ``sizes``); a result
+        that is on the host already is returned as it is."""
+        if self._tables is None:
+            return self
+        sizes = self.sizes
+        if sizes is not None and not isinstance(sizes, numpy.ndarray):
+            sizes = fl._device_to_host(sizes)
+        return ComponentMoments.from_tables(self.summary, *[fl._device_to_host(t) for t in self._tables], sizes=sizes,
+                                            components_of=self.components_of)
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return numpy.array([self.n, self.components, self.bad_entries, self.wide_components, self.heaviest_id,
+                            self.widest_id], dtype=numpy.uint64)
+
+    def _host(self, name):
+        x = getattr(self, name)
+        if not isinstance(x, numpy.ndarray):
+            raise ValueError("ComponentMoments.%s is %s: this works on numpy arrays (to_host() copies the tables first)"
+                             % (name, "not set" if x is None else "in GPU memory"))
+        return x
+
+    def _per_mass(self, a):
+        mass = self._host('mass')
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            return numpy.where(mass[:, None] != 0, a / mass[:, None], numpy.nan)
+
+    @property
+    def mean_velocity(self):
+        return self._per_mass(self._host('momentum'))
+
+    @property
+    def centre_of_mass(self):
+        """``origin + first_moment / mass``: NaN where the mass is 0; not folded into the box."""
+        return self._host('origin') + self._per_mass(self._host('first_moment'))
+
+    @property
+    def span(self):
+        with numpy.errstate(over='ignore'):
+            return self._host('hi') - self._host('lo')
+
+    def heaviest(self, k=1):
+        """The ids of the ``k`` largest masses, heaviest first; among equal masses the smaller id first (a mass sum that
+        is a NaN counts as ``-inf``)."""
+        mass = self._host('mass')
+        key = numpy.where(numpy.isnan(mass), -numpy.inf, mass)
+        return numpy.argsort(-key, kind='stable')[:max(int(k), 0)]
+
+    def __repr__(self):
+        return ("ComponentMoments(n=%d, components=%d, bad=%d, wide=%d, heaviest=%d, widest=%d)"
+                % (self.n, self.components, self.bad_entries, self.wide_components, self.heaviest_id, self.widest_id))
+
+
+def _first_largest(values):
+    """The smallest index that attains the largest value; a NaN counts as ``-inf``; 0 for no value."""
+    v = numpy.asarray(values, dtype=numpy.float64)
+    return int(numpy.argmax(numpy.where(numpy.isnan(v), -numpy.inf, v))) if v.size else 0
+
+
+def component_moments(mass, velocity, energy, position, box, label, component, rows=None, N=None, dimensions=3):
+    """What each connected component is: mass, momentum, kinetic and internal energy, centre and extent per component of
+    a `neighbour_components` result.  The definition the GPU pass (`pgsd.fl.PGSDFile.component_moments_device`,
+    `HOOMDTrajectory.frame_component_moments_device`) equals exactly, every float bit for bit.
+
+    Args:
+        mass, velocity, energy, rows, N: exactly `cell_moments`'; position: an ``N x 3`` array (required).
+        box: ``(Lx, Ly, Lz, xy, xz, yz)``, taken as float32 like `neighbour_components` takes it.
+        label, component: one entry per **list entry** -- `Components` ``.label`` and ``.component`` of the same list.
+
+    ``components`` is ``component.max() + 1`` (0 for no entry).  Per component ``c``:
+
+    **Origin.**  ``origin[c]`` is the float64 position of the component's ROOT, the entry at list position ``label``
+    (the component's smallest member); float32 positions are converted exactly.
+
+    **Displacement.**  The root has ``d = (+0.0, +0.0, +0.0)`` by definition -- no subtraction is made.  Every other entry
+    ``k`` has ``d = pair_displacement(x_root, x_k, box_vectors(box), dimensions)``: HOOMD's single-shift minimum image
+    from the root to the entry.
+
+    **Nine sums.**  `cell_moments`' nine values with the position replaced by ``d``, in `cell_moments`' order over the
+    component's entries in list order (pieces of 1024 counted from the component's first entry, 64 striding lanes, the
+    wave tree, the pieces in sequence, a value that is not finite counting as ``+0.0``, each value for itself).
+    ``bad[c]`` counts the entries with at least one value that is not finite.
+
+    **Extent.**  ``lo[c]`` and ``hi[c]`` start at ``+0.0``, the root's own displacement, and take every other entry's
+    ``d_a`` that is finite by strict comparisons (``d_a < lo_a``, ``d_a > hi_a``): neither is ever ``-0.0`` and the result
+    depends on no order.
+
+    **Wide.**  ``wide[c]`` is 1 if ``hi_a - lo_a >= L_a / 2`` on an axis ``a < dimensions``.  The linking length is at
+    most half the nearest plane distance, so while every span stays below ``L_a / 2`` the displacements are the piece's
+    one consistent unwrapping (`DESIGN.md` has the argument); a wide piece percolates, or nearly does, and its centre and
+    extent are reported but not meaningful.
+
+    **Summary.**  ``n``; ``components``; the bad entries; the wide components; ``heaviest``: the id of the largest mass
+    sum, among equals the smallest id; ``widest``: the id of the largest ``max_a (hi_a - lo_a)``, among equals the
+    smallest id (a NaN counts as ``-inf``).  All 0 for no entry.
+
+    ValueError: what `cell_moments` refuses for its inputs; no position array; lengths that differ; ``label[k] > k``;
+    ``label[label[k]] != label[k]``; ``component[k] != component[label[k]]``; ids that are not the dense ascending
+    numbering of the labels.  Returns a `ComponentMoments`.
+    """
+    dimensions = int(dimensions)
+    if dimensions not in (2, 3):
+        raise ValueError("dimensions must be 2 or 3")
+    if position is None or numpy.asarray(position).ndim != 2:
+        raise ValueError("component_moments takes the position array: a component's origin and extent need it")
+    arrays, dt, n_rows = _moments_arrays(mass, velocity, energy, position, N)
+    n_rows, rows, n = _moments_rows(n_rows, rows)
+    vectors = box_vectors(numpy.asarray(box, dtype=numpy.float32).reshape(-1)[:6])
+    label = numpy.asarray(label).reshape(-1)
+    component = numpy.asarray(component).reshape(-1)
+    if label.shape[0] != n or component.shape[0] != n:
+        raise ValueError("label and component hold one entry per list entry: %d and %d for %d entries"
+                         % (label.shape[0], component.shape[0], n))
+    if n and (label.dtype.kind not in 'iu' or component.dtype.kind not in 'iu'):
+        raise ValueError("label and component hold integers")
+    label, component = label.astype(numpy.int64), component.astype(numpy.int64)
+    at = numpy.arange(n, dtype=numpy.int64)
+    if n:
+        if (label < 0).any() or (label > at).any():
+            raise ValueError("a label lies above its entry: label[k] <= k")
+        if (label[label] != label).any():
+            raise ValueError("a label is no root: label[label[k]] == label[k]")
+        if (component != component[label]).any():
+            raise ValueError("an entry's id differs from its root's")
+        roots = numpy.nonzero(label == at)[0]
+        if not numpy.array_equal(component, numpy.searchsorted(roots, label)):
+            raise ValueError("the ids are not the dense ascending numbering of the labels")
+    components = int(component.max()) + 1 if n else 0
+    # the displacement from the root to the entry; the root's own is +0.0 by definition
+    x = numpy.asarray(arrays['position'])
+    listed = (x if rows is None else x[rows]).astype(numpy.float64)
+    d = [numpy.zeros(n, dtype=numpy.float64) for _ in range(3)]
+    if n:
+        moved = pair_displacement(listed[label], listed, vectors, dimensions)
+        for a in range(3):
+            d[a] = numpy.where(label == at, 0.0, moved[a])
+    values, finite, all_finite = _moments_values(arrays, dt, rows, n, x=d)
+    perm = numpy.argsort(component, kind='stable')
+    sorted_ids = component[perm]
+    offs = numpy.searchsorted(sorted_ids, numpy.arange(components + 2, dtype=numpy.int64), side='left').astype(numpy.int64)
+    sums = numpy.zeros((components, _MOMENTS_QUANTITIES), dtype=numpy.float64)
+    for q in range(_MOMENTS_QUANTITIES):
+        if components:
+            sums[:, q] = _cell_ordered_sums(numpy.where(finite[q], values[q], 0.0)[perm], sorted_ids, offs, components)
+    bad = numpy.bincount(component[~all_finite], minlength=components).astype(numpy.uint32) if n else numpy.zeros(0, numpy.uint32)
+    lo, hi = numpy.zeros((components, 3), dtype=numpy.float64), numpy.zeros((components, 3), dtype=numpy.float64)
+    for a in range(3):
+        take = numpy.isfinite(d[a]) & (label != at)
+        # (the strict comparisons against +0.0 made first: a -0.0 never reaches a bound, whatever minimum / maximum do)
+        low, high = numpy.where(d[a] < 0, d[a], 0.0), numpy.where(d[a] > 0, d[a], 0.0)
+        numpy.minimum.at(lo[:, a], component[take], low[take])
+        numpy.maximum.at(hi[:, a], component[take], high[take])
+    with numpy.errstate(over='ignore'):
+        span = hi - lo
+    wide = numpy.zeros(components, dtype=numpy.uint32)
+    for a in range(dimensions):
+        wide |= (span[:, a] >= vectors[a] / 2).astype(numpy.uint32)
+    origin = listed[perm[offs[:components]]] if n else numpy.zeros((0, 3), dtype=numpy.float64)
+    summary = [n, components, int((~all_finite).sum()), int(wide.sum()), _first_largest(sums[:, 0]),
+               _first_largest(span.max(axis=1) if components else [])]
+    extent = numpy.concatenate([lo, hi], axis=1)
+    return ComponentMoments.from_tables(summary, sums, extent, origin, numpy.stack([bad, wide], axis=1))
+
+
+def frame_component_moments(frame_or_arrays, r, cells=None, where=None, types=None, domain=None, box=None, dimensions=3):
+    """`frame_components` of a frame, then `component_moments` of its ``mass``, ``velocity``, ``energy`` and ``position``
+    over the same list: the host twin of `HOOMDTrajectory.frame_component_moments_device`, which equals it exactly.  The
+    selection, the grid and the refusals are `frame_components`'.  Returns a `ComponentMoments` whose ``components_of``
+    is the `Components` and whose ``sizes`` is its ``sizes``."""
+    _neighbour_range(r)
+    arrays, position, box, dimensions, _, rows = _sph_frame_list(frame_or_arrays, float(r), where, types, domain, box,
+                                                                 dimensions)
+    comps = neighbour_components(position, box, r, rows=rows, cells=cells, dimensions=dimensions)
+    got = component_moments(arrays.get('mass'), arrays.get('velocity'), arrays.get('energy'), position, box, comps.label,
+                            comps.component, rows=comps.rows, N=len(position), dimensions=dimensions)
+    got.components_of, got.sizes = comps, comps.sizes
+    return got
 
 
 # ---- SPH kernel sums: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_sums_device`) equals exactly
@@ -5370,6 +5613,50 @@ class HOOMDTrajectory(object):
             got = f.components_device(f_pos, 'particles/position', box, r, grid, rows, cell, n=count, dimensions=dims)
         finally:
             f.wait_read()
+        return got
+
+    def frame_component_moments(self, idx, r, cells=None, where=None, domain=None):
+        """`frame_component_moments` of frame ``idx`` read through the host path: a `ComponentMoments`.  The definition
+        of `frame_component_moments_device`."""
+        return frame_component_moments(self[int(idx)], r, cells=cells, where=where, domain=domain)
+
+    def frame_component_moments_device(self, idx, r, cells=None, where=None, domain=None):
+        """`frame_component_moments` of frame ``idx``, on the GPU: a `ComponentMoments` that equals
+        ``frame_component_moments(idx, r, ...)`` exactly -- every counter and flag, every float bit for bit -- with its
+        tables, ``sizes`` and the arrays of ``components_of`` in GPU memory (``to_host()`` copies the tables).
+
+        The selection, the grid and the ordering over the staged position chunk are `frame_components_device`'s; the
+        components pass (`pgsd.fl.PGSDFile.components_device`) and then the moments
+        (`pgsd.fl.PGSDFile.component_moments_device`) run over the same staged position chunk and the effective chunks of
+        ``mass``, ``velocity`` and ``energy``; one that is stored nowhere costs nothing, its schema default stands for
+        every row.  One `wait_read` at the end releases the staged chunks, on error paths too.  No per-particle array
+        reaches the host.  A frame whose position is stored nowhere has no chunk to search and raises ValueError.
+        """
+        idx = self._frame_index(idx)
+        f = self.file
+        box, dims, n_global, f_pos = self._census_frame(idx)
+        grid = _neighbour_grid(box, r, cells, dims)
+        if f_pos is None:
+            raise ValueError("frame_component_moments_device: the position is stored nowhere (every particle sits at the "
+                             "origin)")
+        try:
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
+            if rows is None:
+                rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
+            cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
+            comps = f.components_device(f_pos, 'particles/position', box, r, grid, rows, cell, n=count, dimensions=dims)
+            chunks = []
+            for name in ('mass', 'velocity', 'energy'):
+                fr = self._effective_frame(idx, 'particles/' + name, n_global)
+                chunks.append(None if fr is None else (fr, 'particles/' + name))
+            chunks.append((f_pos, 'particles/position'))
+            defaults = numpy.concatenate([numpy.broadcast_to(numpy.asarray(_PARTICLE_FIELDS[name][2], dtype=numpy.float32),
+                                                             (M,)) for name, M, _ in _MOMENTS_INPUTS]).astype(numpy.float64)
+            got = f.component_moments_device(chunks, box, comps.rows, comps.label, comps.component, comps.n,
+                                             comps.components, defaults=defaults, dimensions=dims)
+        finally:
+            f.wait_read()
+        got.components_of, got.sizes = comps, comps.sizes
         return got
 
     def frame_kernel_sums(self, idx, h=None, kernel='wendland_c2', cells=None, where=None, domain=None, surface_below=None):

@@ -257,6 +257,12 @@ cdef extern from "pgsd_private.h" nogil:
                                uint32_t dimensions, const uint32_t* cells, const uint32_t* rows, const int32_t* cell,
                                uint64_t n, uint32_t flags, uint32_t* out_label, uint32_t* out_component,
                                uint32_t* out_sizes, uint64_t* out_summary)
+    int pgsd_component_moments_device(pgsd_handle* handle, const pgsd_index_entry* mass, const pgsd_index_entry* velocity,
+                                      const pgsd_index_entry* energy, const pgsd_index_entry* position, const double* defaults,
+                                      const double* vectors, uint32_t dimensions, const uint32_t* rows, const uint32_t* label,
+                                      const uint32_t* component, uint64_t n, uint64_t components, uint32_t flags,
+                                      double* out_sums, double* out_extent, double* out_origin, uint32_t* out_flags,
+                                      uint64_t* out_summary)
     int pgsd_sph_sums_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* mass,
                              const pgsd_index_entry* density, const double* defaults, const double* vectors, double h,
                              uint32_t kernel, uint32_t dimensions, const uint32_t* cells, const uint32_t* rows,
