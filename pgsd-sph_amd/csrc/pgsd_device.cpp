@@ -216,6 +216,7 @@ int DevicePipeline::init()
         warm_component_moments_kernels();
         warm_sph_kernels();
         warm_sph_gradients_kernels();
+        warm_sph_tensors_kernels();
         warm_sph_forces_kernels();
         warm_sph_samples_kernels();
         warm_sph_body_kernels();

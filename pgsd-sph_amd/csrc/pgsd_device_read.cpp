@@ -633,6 +633,18 @@ int device_pipeline_sph_gradients(DevicePipeline* p, const ChunkRange* ranges, c
                                                           why); });
     }
 
+// SPH gradient tensors: the gradients' four slots
+int device_pipeline_sph_tensors(DevicePipeline* p, const ChunkRange* ranges, const SphTensorsArgs& args, double* out_correction,
+                                double* out_determinant, double* out_gradient, double* out_shear, uint64_t* out_summary,
+                                std::string* err)
+    {
+    SphTensorsArgs a = args;
+    const void** const slots[4] = {&a.pos, &a.mass, &a.density, &a.velocity};
+    return p->staged_launch(ranges, slots, 4, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                            { return launch_sph_tensors(a, out_correction, out_determinant, out_gradient, out_shear, out_summary,
+                                                        stream, why); });
+    }
+
 // SPH accelerations: as the gradients, with one more slot: the pressure chunk where one is stored
 int device_pipeline_sph_accelerations(DevicePipeline* p, const ChunkRange* ranges, const SphForcesArgs& args,
                                       double* out_pressure_acc, double* out_viscous_acc, double* out_total,

@@ -42,6 +42,7 @@ int device_pipeline_cell_moments(DevicePipeline*, const ChunkRange*, const CellM
 int device_pipeline_neighbours(DevicePipeline*, long long, size_t, const NeighboursArgs&, const double*, uint32_t*, double*, uint32_t*, uint64_t*, double*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_sums(DevicePipeline*, const ChunkRange*, const SphArgs&, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_gradients(DevicePipeline*, const ChunkRange*, const SphGradientsArgs&, double*, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
+int device_pipeline_sph_tensors(DevicePipeline*, const ChunkRange*, const SphTensorsArgs&, double*, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_accelerations(DevicePipeline*, const ChunkRange*, const SphForcesArgs&, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_body_force(DevicePipeline*, const ChunkRange*, const SphBodyArgs&, uint32_t*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_samples(DevicePipeline*, const ChunkRange*, const SphSamplesArgs&, uint32_t*, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }

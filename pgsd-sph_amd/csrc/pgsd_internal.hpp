@@ -567,6 +567,39 @@ inline void sph_gradients_of_nothing(uint64_t* out_summary)
 int device_pipeline_sph_gradients(DevicePipeline*, const ChunkRange* ranges, const SphGradientsArgs& a, double* out_rate,
                                   double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary,
                                   std::string* err);
+// SPH gradient tensors (pgsd.hoomd.sph_gradient_tensors is the definition): per entry of a row list in cell order the
+// kernel-gradient correction matrix, its determinant, the corrected velocity-gradient tensor and the shear rate over the
+// entries inside the support 2h, in the sums' order, and over the list the entries left uncorrected, the ranges of the
+// determinant and of the trace and the largest shear rate.  The grid, the support, the list, the defaults and G are
+// SphGradientsArgs' (volume is set: the density default is a number here; surface and surface_below are not looked at).
+enum
+    {
+    SPHT_SUMMARY_WORDS = 14 // n, nowhere, not_finite, uncorrected, det_at, det_row, shear_at, shear_row, det (min, max),
+                            // trace (min, max), the largest shear rate, 0
+    };
+struct SphTensorsArgs : SphGradientsArgs
+    {
+    double det_min; // an entry is corrected where det_min < det < +inf; a number, at least 0
+    };
+// the summary of no entry
+inline void sph_tensors_of_nothing(uint64_t* out_summary)
+    {
+    const double lo = HUGE_VAL, hi = -HUGE_VAL;
+    std::fill(out_summary, out_summary + SPHT_SUMMARY_WORDS, (uint64_t)0); // (+0.0 is the zero word)
+    out_summary[4] = out_summary[5] = out_summary[6] = out_summary[7] = SPH_NONE;
+    for (int s = 0; s < 2; s++)
+        {
+        memcpy(&out_summary[8 + 2 * s], &lo, sizeof(double));
+        memcpy(&out_summary[9 + 2 * s], &hi, sizeof(double));
+        }
+    }
+// stage the chunks that are present (ranges[0 .. 3] as device_pipeline_sph_gradients), check the lists, sum and invert
+// on the GPU; out_correction (device, a.n x 6), out_determinant (a.n), out_gradient (a.n x 9), out_shear (a.n), each or
+// null; out_summary (host, 14 words) is written on success only, and so are the device outputs; synchronous.  The
+// refusals and the staging are device_pipeline_sph_sums'.
+int device_pipeline_sph_tensors(DevicePipeline*, const ChunkRange* ranges, const SphTensorsArgs& a, double* out_correction,
+                                double* out_determinant, double* out_gradient, double* out_shear, uint64_t* out_summary,
+                                std::string* err);
 // SPH accelerations (pgsd.hoomd.sph_accelerations is the definition): per entry of a row list in cell order the pressure
 // acceleration -sum_j m_j (p_i/rho_i^2 + p_j/rho_j^2) grad_i W_ij, Morris' laminar viscous acceleration for one constant
 // mu and their sum with gravity over the entries inside the support 2h, in the sums' order, and over the list the

@@ -359,6 +359,16 @@ int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, d
 int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* out_divergence, double* out_curl,
                          double* out_normal, uint64_t* out_summary, hipStream_t stream, std::string* err);
 
+// SPH gradient tensors (pgsd_sph_tensors.hip; SphTensorsArgs, the chunk pointers filled in): check, offsets, the
+// gradients' compaction (pgsd_sph_compact.hpp), one lane per entry over the candidates in the sums' order
+// (pgsd_traverse.hpp) with the inverse and the epilogue in the same kernel, one workgroup for the ranges, the smallest
+// determinant and the largest shear rate.  out_correction (device, a.n x 6), out_determinant (a.n), out_gradient (a.n x 9),
+// out_shear (a.n), each or null; out_summary (host, 14 words) is written on success only.  Synchronises `stream`;
+// PGSD_ERROR_INVALID_ARGUMENT for an id that descends or lies outside [0, n_cells], for an entry >= a.N and for a det_min
+// that is NaN or negative
+int launch_sph_tensors(const SphTensorsArgs& a, double* out_correction, double* out_determinant, double* out_gradient,
+                       double* out_shear, uint64_t* out_summary, hipStream_t stream, std::string* err);
+
 // SPH accelerations (pgsd_sph_forces.hip; SphForcesArgs, the chunk pointers filled in): check, offsets, compaction of the
 // listed positions, masses, A = p/rho^2, volumes, densities and velocities, one lane per entry over the candidates in the
 // sums' order (pgsd_traverse.hpp), one workgroup for the largest norms.  out_pressure_acc, out_viscous_acc, out_total
@@ -450,6 +460,7 @@ void warm_components_kernels();
 void warm_component_moments_kernels();
 void warm_sph_kernels();
 void warm_sph_gradients_kernels();
+void warm_sph_tensors_kernels();
 void warm_sph_forces_kernels();
 void warm_sph_samples_kernels();
 void warm_sph_body_kernels();

@@ -63,6 +63,10 @@
  *                     frame_kernel_gradients_device: per entry of the same list, over the same support and in the same
  *                     order, the density rate of the continuity equation, the velocity divergence and curl and the
  *                     colour gradient, and over the list their ranges and the largest vorticity and surface normal)
+ *                     pgsd_sph_tensors_device (pgsd.fl's sph_tensors_device, behind pgsd.hoomd's
+ *                     frame_gradient_tensors_device: per entry of the same list, over the same support and in the same
+ *                     order, the kernel-gradient correction matrix, the corrected velocity-gradient tensor and the shear
+ *                     rate, and over the list the entries left uncorrected and the largest shear rate with its row)
  *                     pgsd_sph_accelerations_device (pgsd.fl's sph_accelerations_device, behind pgsd.hoomd's
  *                     frame_accelerations_device: per entry of the same list, over the same support and in the same
  *                     order, the pressure and the laminar viscous acceleration and their sum with gravity, and over the
@@ -599,6 +603,57 @@ extern "C"
                                   double h, uint32_t kernel, uint32_t dimensions, const uint32_t cells[3],
                                   const uint32_t* rows, const int32_t* cell, uint64_t n, double* out_density_rate,
                                   double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary);
+
+    /* SPH gradient tensors (pgsd.hoomd.sph_gradient_tensors is the definition, and the results equal it exactly: every
+       counter and index, every float bit for bit -- a NaN is a NaN).  position, velocity, mass, density, vectors, h,
+       kernel, dimensions, cells, rows, cell and n are pgsd_sph_gradients_device's, and so are the grid, the support 2h, r2,
+       inv_h, sigma, G, F(q), V_j = m_j / rho_j and THE ORDER of the candidates.  defaults: the mass and the density that
+       stand for a chunk stored nowhere (the density default is a number here: there is no "no volume").  det_min: an entry
+       is corrected where det_min < det < +inf; a convention of the caller's, not a tuned figure (an interior particle has
+       det near 1, a flat free surface about one half).
+       ONE PAIR i <- j, float64, no contraction: d, d2, the strict test d2 < r2, rr, q, F, e_k = F * d_k and u_k = v_j[k] -
+       v_i[k] as in the gradients; i itself and coincident entries are candidates like any other.  Fifteen accumulators
+       per entry start at +0.0 and add in the defined order:
+           b_ab += V_j * (d_a * e_b)   for ab in (00, 01, 02, 11, 12, 22)
+           g_ab += V_j * (u_a * e_b)   for all nine ab: row a the velocity component, column b the derivative direction
+       AFTER THE LAST CANDIDATE, every product and sum in the association shown: B_ab = G*b_ab, R_ab = G*g_ab (R is the
+       uncorrected dv_a/dx_b); with dimensions == 3
+           c00 = B11*B22 - B12*B12, c01 = B02*B12 - B01*B22, c02 = B01*B12 - B02*B11,
+           c11 = B00*B22 - B02*B02, c12 = B01*B02 - B00*B12, c22 = B00*B11 - B01*B01,
+           det = (B00*c00 + B01*c01) + B02*c02
+       and with dimensions == 2 (d_z is 0, the z row and column of B vanish)
+           det = B00*B11 - B01*B01, c00 = B11, c01 = -B01, c11 = B00, c02 = c12 = c22 = +0.0;
+       ok = det > det_min and det < +inf (a NaN is never ok).  Where ok: L_ab = c_ab / det (2-D: the three z entries are
+       +0.0, written) and D_ab = (R_a0*L_0b + R_a1*L_1b) + R_a2*L_2b (2-D: D_ab = R_a0*L_0b + R_a1*L_1b for b < 2 and D_a2 =
+       +0.0, written).  Where not ok: L is the identity (2-D: diag(1, 1, 0)) and D_ab = R_ab, both written, not computed.
+           trace = (D00 + D11) + D22, s01 = 0.5*(D01 + D10), s02 = 0.5*(D02 + D20), s12 = 0.5*(D12 + D21),
+           ss = ((D00*D00 + D11*D11) + D22*D22) + 2.0*((s01*s01 + s02*s02) + s12*s12), shear_rate = sqrt(2.0*ss).
+       An entry with id n_cells is nowhere: it contributes to nobody and all its values are +0.0, written.
+       Device outputs, float64, each optional (NULL): out_correction, n x 6 (xx, xy, xz, yy, yz, zz); out_determinant, n;
+       out_velocity_gradient, n x 9, row-major; out_shear_rate, n.
+       Host output, 14 words:
+           out_summary[0 .. 2]    n; the entries nowhere; the entries that have a cell and whose shear_rate is NaN or
+                                  infinite
+           out_summary[3]         the entries that have a cell and are not ok (uncorrected)
+           out_summary[4], [5]    the list position of the smallest determinant and its row: a strict compare from +inf,
+                                  the smaller list position on a tie, a NaN never; 0xFFFFFFFF without one
+           out_summary[6], [7]    the same of the largest shear_rate (any value that is no NaN counts)
+           out_summary[8 .. 11]   as float64 bit patterns the minimum and the maximum of the determinant and of the trace
+                                  over the entries that have a cell, kept by strict compares from +inf and -inf in
+                                  which -0.0 is below +0.0 (both occur, and no bound depends on an order): a NaN never
+                                  replaces a value
+           out_summary[12]        as a float64 bit pattern the largest shear_rate; +0.0 without one
+           out_summary[13]        0
+       No float is summed over the list.  Staging, synchronisation and n == 0 are pgsd_sph_sums_device's.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), every output as it was: everything
+       pgsd_sph_gradients_device refuses; a det_min that is NaN or negative. */
+    int pgsd_sph_tensors_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
+                                const struct pgsd_index_entry* density, const double defaults[2], const double vectors[6],
+                                double h, uint32_t kernel, uint32_t dimensions, double det_min, const uint32_t cells[3],
+                                const uint32_t* rows, const int32_t* cell, uint64_t n, double* out_correction,
+                                double* out_determinant, double* out_velocity_gradient, double* out_shear_rate,
+                                uint64_t* out_summary);
 
     /* SPH accelerations (pgsd.hoomd.sph_accelerations is the definition, and the results equal it exactly: every counter
        and index, every float bit for bit -- a NaN is a NaN).  position, velocity, mass, density, vectors, h, kernel,

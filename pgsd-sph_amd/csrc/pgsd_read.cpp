@@ -1422,6 +1422,47 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_sph_tensors_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                       const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
+                                       const struct pgsd_index_entry* density, const double defaults[2],
+                                       const double vectors[6], double h, uint32_t kernel, uint32_t dimensions, double det_min,
+                                       const uint32_t cells[3], const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                       double* out_correction, double* out_determinant, double* out_velocity_gradient,
+                                       double* out_shear_rate, uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_sph_tensors_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !defaults || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    ChunkRange ranges[5];
+    SphForcesArgs g;
+    int rc = sph_arguments(who, s, handle, position, mass, density, velocity, nullptr, defaults, vectors, h, kernel, dimensions,
+                           cells, rows, cell, n, NAN, ranges, g);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (!(det_min >= 0.0))
+        return refuse("det_min must be a number, at least 0");
+    SphTensorsArgs a = SphTensorsArgs();
+    static_cast<SphGradientsArgs&>(a) = g;
+    a.volume = 1u; // (the density default is a number here: there is no "no volume")
+    a.det_min = det_min;
+    if (n == 0)
+        {
+        sph_tensors_of_nothing(out_summary);
+        return PGSD_SUCCESS;
+        }
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "SPH gradient tensors: ", [&](std::string* err)
+                          { return device_pipeline_sph_tensors(s->dev, ranges, a, out_correction, out_determinant,
+                                                               out_velocity_gradient, out_shear_rate, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_sph_accelerations_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
                                              const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
                                              const struct pgsd_index_entry* density, const struct pgsd_index_entry* pressure,

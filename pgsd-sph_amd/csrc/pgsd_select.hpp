@@ -23,6 +23,9 @@
 //   pgsd_sph_gradients.hip   the SPH kernel gradients: density rate, velocity divergence and curl and the colour gradient
 //                      over the same support in the same order (pgsd_traverse.hpp: the traversal as an inlined template,
 //                      which the pair units walk their candidates through)
+//   pgsd_sph_tensors.hip   the SPH gradient tensors: the kernel-gradient correction matrix, the corrected velocity gradient
+//                      and the shear rate over the same support in the same order (pgsd_sph_compact.hpp: the compaction
+//                      kernel it shares with the gradients)
 //   pgsd_sph_forces.hip   the SPH accelerations: pressure and laminar viscous acceleration and their sum with gravity
 //                      over the same support in the same order, the largest of each with its row
 //   pgsd_sph_samples.hip   the SPH samples: the interpolant of the list at points of the caller's choosing, the same

@@ -11,7 +11,7 @@
 // after its last candidate.
 //   cells_check_kernel, cells_offsets_kernel   pgsd_cells.hip's, unchanged (pgsd_cells.hpp): the refusal protocol and the
 //                          CSR offsets; every kernel here reads the device flag first and does nothing where it is set
-//   sphg_compact_kernel<F64>   lane per entry: xs[k] = position[rows[k]] in the chunk's own element type, m[k] the mass,
+//   sphg_compact_kernel<F64>   (pgsd_sph_compact.hpp, shared with pgsd_sph_tensors.hip) lane per entry: xs[k] = position[rows[k]] in the chunk's own element type, m[k] the mass,
 //                          V[k] = m / rho (one float64 division of the stored values) and the velocity as three float64
 //                          values (an exact conversion, so that the velocity chunk's element type stays out of the pair
 //                          kernel's template list; the zero vector where no velocity is stored)
@@ -27,6 +27,7 @@
 #include "pgsd_stats.hpp"
 #include "pgsd_cells.hpp"
 #include "pgsd_traverse.hpp"
+#include "pgsd_sph_compact.hpp"
 #include "pgsd_scratch.hpp"
 
 #include <type_traits>
@@ -81,27 +82,6 @@ __device__ __forceinline__ SphgPartial sphg_nothing()
         p.at[s] = SPH_NONE;
         }
     return p;
-    }
-
-template<bool F64>
-__global__ __launch_bounds__(SEL_THREADS) void sphg_compact_kernel(const SphGradientsArgs a, const uint32_t* flag_dev,
-                                                                   void* __restrict__ xs, double* __restrict__ ms,
-                                                                   double* __restrict__ vs, double* __restrict__ ws)
-    {
-    const uint64_t k = (uint64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
-    if (k >= a.n || *flag_dev != 0)
-        return;
-    const uint64_t row = a.rows[k];
-    if (row >= a.N) // (the check kernel has refused such a list: nothing is loaded for it)
-        return;
-    compact_position<F64>(a.pos, row, xs, k);
-    const double m = a.mass ? column_value(a.mass, a.mass_f64, row) : a.mass_default;
-    ms[k] = m;
-    if (a.volume)
-        vs[k] = m / (a.density ? column_value(a.density, a.density_f64, row) : a.density_default);
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        ws[k * 3 + c] = a.velocity ? column_value(a.velocity, a.velocity_f64, row * 3 + c) : 0.0;
     }
 
 // words: the summary in device memory, zeroed by the launcher (word 2, not_finite, is added to here)

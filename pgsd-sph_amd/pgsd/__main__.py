@@ -44,6 +44,11 @@
            uniform ``slength``): the search grid and the entries, the ranges of the velocity divergence and of the
            density rate of the continuity equation and the largest vorticity and surface normal, each with its row
            (``--kernel``, ``--types``; ``pgsd.hoomd.frame_kernel_gradients`` on the host: no GPU);
+           ``--sph-tensors [H]`` adds the SPH gradient tensors for the smoothing length H (without H: the frame's uniform
+           ``slength``): the search grid and the entries, those left uncorrected because the determinant of their
+           correction matrix is not above ``--det-min D`` (default 0.25), the ranges of the determinant and of the trace
+           of the corrected velocity gradient and the largest shear rate with its row (``--kernel``, ``--types``;
+           ``pgsd.hoomd.frame_gradient_tensors`` on the host: no GPU);
            ``--sph-forces [H]`` adds the SPH accelerations for the smoothing length H (without H: the frame's uniform
            ``slength``): the search grid and the entries, the largest total, pressure and viscous acceleration, each with
            its row, the entries whose total is not finite and the force time step ``0.25 sqrt(h / |a|)``
@@ -138,6 +143,8 @@ def _cmd_info(args):
         _print_sph(args, frame)
     if args.sph_gradients is not None:
         _print_sph_gradients(args, frame)
+    if args.sph_tensors is not None:
+        _print_sph_tensors(args, frame)
     if args.sph_forces is not None:
         _print_sph_forces(args, frame)
     if args.sample is not None:
@@ -258,6 +265,25 @@ def _print_sph_gradients(args, frame):
             print("  vorticity:    largest %r at row %d" % (m.curl2 ** 0.5, m.curl_row))
         if m.normal2 is not None:
             print("  normal:       largest %r at row %d" % (m.normal2 ** 0.5, m.normal_row))
+
+
+def _print_sph_tensors(args, frame):
+    """``info --sph-tensors``: `pgsd.hoomd.frame_gradient_tensors` of one frame, on the host."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_gradient_tensors(traj[frame], None if args.sph_tensors < 0 else args.sph_tensors, kernel=args.kernel,
+                                         det_min=args.det_min, where=where)
+    print("SPH gradient tensors of frame %d with h = %r (%s), det_min = %r, over %d x %d x %d cells%s:"
+          % ((frame, m.h, m.kernel, m.det_min) + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  entries:      %d  nowhere: %d  uncorrected: %d" % (m.n, m.nowhere, m.uncorrected))
+    if m.n > m.nowhere:
+        print("  determinant:  smallest %r  largest %r" % (m.determinant_min, m.determinant_max))
+        print("  trace:        smallest %r  largest %r" % (m.trace_min, m.trace_max))
+        if m.shear is not None:
+            print("  shear rate:   largest %r at row %d  not finite: %d" % (m.shear, m.shear_row, m.not_finite))
+        else:
+            print("  shear rate:   not finite: %d" % m.not_finite)
 
 
 def _print_sph(args, frame):
@@ -581,6 +607,11 @@ def main(argv=None):
     p.add_argument('--sph-gradients', type=float, nargs='?', const=-1.0, default=None, metavar='H',
                    help="print the SPH kernel gradients for the smoothing length H (without H: the frame's uniform "
                         "slength): grid, entries, divergence and density-rate ranges, largest vorticity and normal")
+    p.add_argument('--sph-tensors', type=float, nargs='?', const=-1.0, default=None, metavar='H',
+                   help="print the SPH gradient tensors for the smoothing length H (without H: the frame's uniform "
+                        "slength): grid, entries, uncorrected entries, determinant and trace ranges, largest shear rate")
+    p.add_argument('--det-min', type=float, default=0.25, metavar='D',
+                   help="with --sph-tensors: an entry is corrected where its determinant is above D (default: 0.25)")
     p.add_argument('--sph-forces', type=float, nargs='?', const=-1.0, default=None, metavar='H',
                    help="print the SPH accelerations for the smoothing length H (without H: the frame's uniform slength): "
                         "grid, entries, the largest total, pressure and viscous acceleration and the force time step")
@@ -604,7 +635,7 @@ def main(argv=None):
                    help="with --body-force: the point the torque is taken about (default: 0,0,0; write --about=-1,0,0 "
                         "where X is negative)")
     p.add_argument('--kernel', type=str, default='wendland_c2', choices=('wendland_c2', 'cubic_spline'),
-                   help="the kernel of --sph, --sph-gradients, --sph-forces, --sample and --body-force (default: wendland_c2)")
+                   help="the kernel of --sph, --sph-gradients, --sph-tensors, --sph-forces, --sample and --body-force (default: wendland_c2)")
     p.add_argument('--surface', type=float, default=None, metavar='S',
                    help="with --sph: count the entries whose Shepard sum is below S (the free surface)")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")

@@ -2408,6 +2408,72 @@ cdef class PGSDFile:
                 got.curl, got.normal = _device_head_rows(out_curl, count), _device_head_rows(out_normal, count)
         return got
 
+    def sph_tensors_device(self, frame, name, box, h, cells, rows, cell, n=None, velocity=None, mass=None, density=None,
+                           defaults=None, dimensions=3, kernel='wendland_c2', det_min=0.25, return_rows=False):
+        """The SPH gradient tensors of a row list in cell order on the GPU: the kernel-gradient correction matrix, its
+        determinant, the corrected velocity-gradient tensor and the shear rate over the kernel support ``2h``, in the
+        order that is part of their definition.
+
+        Args:
+            frame, name, box, h, cells, rows, cell, n, velocity, mass, density, dimensions, kernel: as
+                :meth:`sph_gradients_device` takes them.
+            defaults: ``(mass, density)`` that stand for a chunk stored nowhere; ``None``: the schema's 1.0 and 0.0 (the
+                density default is a number here: there is no "no volume").
+            det_min (float): an entry is corrected where ``det_min < det < inf``; a number, at least 0.
+            return_rows (bool): keep the per-entry results in GPU memory.
+
+        Returns:
+            A :class:`pgsd.hoomd.KernelTensors`: exactly :func:`pgsd.hoomd.sph_gradient_tensors` of the same list --
+            every counter and index, every float bit for bit.  With ``return_rows`` its ``rows`` and ``cell`` are the
+            arguments and ``correction`` (``n x 6``), ``determinant`` (``n``), ``velocity_gradient`` (``n x 9``) and
+            ``shear_rate`` (``n``) are float64 arrays in GPU memory; otherwise the six are ``None``.  The chunks are
+            staged whole unless an earlier call left them staged; the staged rows are kept until the next
+            :meth:`wait_read`.  What the library refuses (:c:func:`pgsd_sph_tensors_device`) raises ValueError and
+            computes nothing.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry, e_velocity, e_mass, e_density
+        self._entry(frame, name, &entry)
+        cdef const C.pgsd_index_entry* p_velocity = self._optional(velocity, &e_velocity)
+        cdef const C.pgsd_index_entry* p_mass = self._optional(mass, &e_mass)
+        cdef const C.pgsd_index_entry* p_density = self._optional(density, &e_density)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("sph_tensors_device", cells)
+        cdef uint32_t c_kernel = _sph_kernel("sph_tensors_device", kernel)
+        c_defaults = _sph_defaults("sph_tensors_device", [1.0, 0.0] if defaults is None else defaults, density)[0]
+        c_rows, c_cell, count = _cell_ordered_lists("sph_tensors_device", rows, cell, n)
+        summary = numpy.zeros(14, dtype=numpy.uint64)
+        cdef uintptr_t p_correction, p_determinant, p_gradient, p_shear
+        device = self.pipeline_device() if return_rows else None
+        out_correction, p_correction = _per_entry(count, (6,), numpy.float64, device)
+        out_determinant, p_determinant = _per_entry(count, (), numpy.float64, device)
+        out_gradient, p_gradient = _per_entry(count, (9,), numpy.float64, device)
+        out_shear, p_shear = _per_entry(count, (), numpy.float64, device)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef double c_h = float(h), c_det_min = float(det_min)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_sph_tensors_device(&self._handle, &entry, p_velocity, p_mass, p_density,
+                                               <const double*>p_defaults, <const double*>p_vectors, c_h, c_kernel, c_dims,
+                                               c_det_min, <const uint32_t*>p_cells, <const uint32_t*>p_rows,
+                                               <const int32_t*>p_cell, c_n, <double*>p_correction, <double*>p_determinant,
+                                               <double*>p_gradient, <double*>p_shear, <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("sph_tensors_device", retval, "refused", self._name, err)
+        got = _hoomd.KernelTensors(c_h, kernel, grid, int(dimensions), summary, c_det_min)
+        if return_rows:
+            got.rows, got.cell = _device_head(rows, count), _device_head(cell, count)
+            got.correction = _device_head_rows(out_correction, count)
+            got.determinant = _device_head(out_determinant, count)
+            got.velocity_gradient = _device_head_rows(out_gradient, count)
+            got.shear_rate = _device_head(out_shear, count)
+        return got
+
     def sph_accelerations_device(self, frame, name, box, h, cells, rows, cell, n=None, velocity=None, mass=None, density=None,
                                  pressure=None, defaults=None, viscosity=None, gravity=None, dimensions=3,
                                  kernel='wendland_c2', return_rows=False):

@@ -2866,8 +2866,251 @@ def frame_kernel_gradients(frame_or_arrays, h=None, kernel='wendland_c2', cells=
                                 density=arrays.get('density'), rows=rows, cells=cells, dimensions=dimensions, kernel=kernel)
 
 
+# ---- SPH gradient tensors: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_tensors_device`) equals exactly
+_SPHT_SUMMARY_WORDS = 14    # n, nowhere, not_finite, uncorrected, det_at, det_row, shear_at, shear_row, det and trace (min, max), shear, 0
+
+
+def _sph_det_min(det_min):
+    """``det_min`` as a float, a number that is at least 0."""
+    d = float(det_min)
+    if not d >= 0.0:
+        raise ValueError("det_min is a number, at least 0: %r" % (det_min,))
+    return d
+
+
+class KernelTensors(object):
+    """The SPH gradient tensors of a list in cell order (`sph_gradient_tensors`).
+
+    Attributes:
+        h (float), kernel (str), grid (``(cx, cy, cz)``), dimensions (int), det_min (float): what was asked; G (float):
+            `sph_gradient_scale`.
+        rows, cell: the list in cell order and its cell ids (``n_cells``: nowhere).
+        correction (float64, ``n x 6``: xx, xy, xz, yy, yz, zz): the kernel-gradient correction matrix ``L_i``, the inverse
+            of ``B_i = sum_j V_j d (x) grad_i W_ij``; the identity (2-D: ``diag(1, 1, 0)``) where the entry stayed
+            uncorrected.
+        determinant (float64, ``n``): ``det B_i`` (2-D: of its x-y block).
+        velocity_gradient (float64, ``n x 9``, row-major ``dv_a/dx_b``): the corrected tensor ``D_i = R_i L_i``; the
+            uncorrected ``R_i`` where the entry stayed uncorrected.
+        shear_rate (float64, ``n``): ``sqrt(2 S:S)`` of the symmetric part of ``D_i``.  All four are ``+0.0`` for an entry
+            nowhere; numpy arrays from the model, from the GPU ``None`` unless ``return_rows`` left them in GPU memory.
+        n, nowhere (int): the entries, and those without a cell.
+        not_finite (int): the entries that have a cell and whose ``shear_rate`` is NaN or infinite.
+        uncorrected (int): the entries that have a cell and whose determinant is not inside ``(det_min, inf)``.
+        determinant_min, determinant_max, trace_min, trace_max (float): over the entries that have a cell, by strict
+            compares from ``+inf`` / ``-inf`` in which ``-0.0`` is below ``+0.0`` (a NaN never replaces a value); the
+            trace is ``(D00 + D11) + D22``.
+        det_at, det_row: the list position of the smallest determinant (a strict compare from ``+inf``, the smaller
+            position on a tie, a NaN never counts) and its row; ``None`` without one.
+        shear, shear_at, shear_row: the largest ``shear_rate`` over the entries that have a cell, its list position (the
+            smaller one on a tie, a NaN never counts) and its row; ``None`` without one.
+    """
+
+    __slots__ = ('h', 'kernel', 'grid', 'dimensions', 'det_min', 'G', 'rows', 'cell', 'correction', 'determinant',
+                 'velocity_gradient', 'shear_rate', 'n', 'nowhere', 'not_finite', 'uncorrected', 'determinant_min',
+                 'determinant_max', 'trace_min', 'trace_max', 'det_at', 'det_row', 'shear', 'shear_at', 'shear_row', '_words')
+
+    def __init__(self, h, kernel, grid, dimensions, summary, det_min=0.25, rows=None, cell=None, correction=None,
+                 determinant=None, velocity_gradient=None, shear_rate=None):
+        """``summary``: the 14 uint64 words of `pgsd_sph_tensors_device` -- n, nowhere, not_finite, uncorrected, det_at,
+        det_row, shear_at, shear_row, then as float64 bit patterns the minimum and maximum of the determinant and of the
+        trace and the largest shear rate, then 0."""
+        s = numpy.ascontiguousarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _SPHT_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _SPHT_SUMMARY_WORDS)
+        self._words = s.copy()
+        self.h, self.kernel, self.dimensions, self.det_min = float(h), kernel, int(dimensions), _sph_det_min(det_min)
+        self.G = sph_gradient_scale(kernel, h, dimensions)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.n, self.nowhere, self.not_finite, self.uncorrected = int(s[0]), int(s[1]), int(s[2]), int(s[3])
+        f = s[8:13].view(numpy.float64)
+        self.determinant_min, self.determinant_max, self.trace_min, self.trace_max = (float(v) for v in f[:4])
+        found = int(s[4]) != _NEIGHBOURS_NONE
+        self.det_at, self.det_row = (int(s[4]), int(s[5])) if found else (None, None)
+        found = int(s[6]) != _NEIGHBOURS_NONE
+        self.shear = float(f[4]) if found else None
+        self.shear_at, self.shear_row = (int(s[6]), int(s[7])) if found else (None, None)
+        self.rows, self.cell, self.correction, self.determinant = rows, cell, correction, determinant
+        self.velocity_gradient, self.shear_rate = velocity_gradient, shear_rate
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return self._words.copy()
+
+    def __repr__(self):
+        return "KernelTensors(h=%r, kernel=%r, grid=%r, n=%d, nowhere=%d, uncorrected=%d, determinant=[%r, %r], shear=%r)" % (
+            self.h, self.kernel, self.grid, self.n, self.nowhere, self.uncorrected, self.determinant_min,
+            self.determinant_max, self.shear)
+
+
+def _spht_summary(n, somewhere, rows_sorted, ok, det, trace, shear):
+    """The summary words from the per-entry results: no float is summed over the list, so no order enters."""
+    words = numpy.zeros(_SPHT_SUMMARY_WORDS, dtype=numpy.uint64)
+    f = words[8:13].view(numpy.float64)
+    words[0], words[1] = n, n - somewhere
+    words[4:8] = _NEIGHBOURS_NONE
+    f[0:4:2], f[1:4:2], f[4] = numpy.inf, -numpy.inf, 0.0
+    if not somewhere:
+        return words
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        for k, v in enumerate((det, trace)):
+            v = v[:somewhere]
+            kept = v[v == v]
+            if kept.size:
+                # (-0.0 is below +0.0: both occur, and the bound of a parallel reduction must not depend on an order)
+                zeros = numpy.signbit(kept[kept == 0.0])
+                lo, hi = min(numpy.inf, kept.min()), max(-numpy.inf, kept.max())
+                f[2 * k] = (-0.0 if zeros.any() else 0.0) if lo == 0.0 else lo
+                f[2 * k + 1] = (0.0 if not zeros.all() else -0.0) if hi == 0.0 else hi
+        words[2] = int(numpy.count_nonzero(~numpy.isfinite(shear[:somewhere])))
+        words[3] = int(numpy.count_nonzero(~ok[:somewhere]))
+        size = numpy.where(det[:somewhere] < numpy.inf, det[:somewhere], numpy.inf)
+        at = int(numpy.argmin(size))                    # (the first position that attains the minimum)
+        if size[at] < numpy.inf:
+            words[4], words[5] = at, rows_sorted[at]
+        s = shear[:somewhere]
+        size = numpy.where(s == s, s, -numpy.inf)
+        at = int(numpy.argmax(size))                    # (the first position that attains the maximum)
+        if size[at] > -numpy.inf:
+            words[6], words[7], f[4] = at, rows_sorted[at], s[at]
+    return words
+
+
+def _spht_epilogue(G, b, g, dimensions, det_min):
+    """What follows the last candidate, for every entry at once: ``b`` the six and ``g`` the nine accumulators (lists of
+    float64 arrays).  ``(ok, L (six arrays), det, D (nine arrays), trace, shear_rate)``, every product and sum in the
+    association `sph_gradient_tensors` writes out, one rounding each."""
+    B00, B01, B02, B11, B12, B22 = (G * a for a in b)
+    R = [G * a for a in g]
+    zero = numpy.zeros_like(B00)
+    if dimensions == 3:
+        c00 = B11 * B22 - B12 * B12
+        c01 = B02 * B12 - B01 * B22
+        c02 = B01 * B12 - B02 * B11
+        c11 = B00 * B22 - B02 * B02
+        c12 = B01 * B02 - B00 * B12
+        c22 = B00 * B11 - B01 * B01
+        det = (B00 * c00 + B01 * c01) + B02 * c02
+    else:
+        det = B00 * B11 - B01 * B01
+        c00, c01, c11 = B11, -B01, B00
+        c02 = c12 = c22 = zero
+    ok = (det > numpy.float64(det_min)) & (det < numpy.inf)
+    safe = numpy.where(ok, det, 1.0)                    # (what is not ok is written below, not computed)
+    c = (c00, c01, c02, c11, c12, c22)
+    identity = (1.0, 0.0, 0.0, 1.0, 0.0, 1.0 if dimensions == 3 else 0.0)
+    if dimensions == 3:
+        L = [numpy.where(ok, c[k] / safe, identity[k]) for k in range(6)]
+    else:
+        L = [numpy.where(ok, c[k] / safe, identity[k]) if k in (0, 1, 3) else numpy.where(ok, 0.0, identity[k])
+             for k in range(6)]
+    Lm = ((L[0], L[1], L[2]), (L[1], L[3], L[4]), (L[2], L[4], L[5]))
+    D = []
+    for a in range(3):
+        for col in range(3):
+            if dimensions == 3:
+                v = (R[3 * a] * Lm[0][col] + R[3 * a + 1] * Lm[1][col]) + R[3 * a + 2] * Lm[2][col]
+            elif col < 2:
+                v = R[3 * a] * Lm[0][col] + R[3 * a + 1] * Lm[1][col]
+            else:
+                v = zero
+            D.append(numpy.where(ok, v, R[3 * a + col]))
+    trace = (D[0] + D[4]) + D[8]
+    s01, s02, s12 = 0.5 * (D[1] + D[3]), 0.5 * (D[2] + D[6]), 0.5 * (D[5] + D[7])
+    ss = ((D[0] * D[0] + D[4] * D[4]) + D[8] * D[8]) + 2.0 * ((s01 * s01 + s02 * s02) + s12 * s12)
+    return ok, L, det, D, trace, numpy.sqrt(2.0 * ss)
+
+
+def sph_gradient_tensors(position, velocity, box, h, mass=None, density=None, rows=None, cells=None, dimensions=3,
+                         kernel='wendland_c2', det_min=0.25):
+    """The SPH gradient tensors of a row list: per entry ``i`` the kernel-gradient correction (renormalisation) matrix
+    ``L_i``, the inverse of ``B_i = sum_j V_j d (x) grad_i W_ij``, its determinant, the corrected velocity-gradient tensor
+    ``D_i = (sum_j V_j (v_j - v_i) (x) grad_i W_ij) L_i`` -- exact for a linear velocity field on any particle arrangement
+    -- and the shear rate ``sqrt(2 S:S)`` of its symmetric part, over the entries ``j`` inside the kernel support ``2h``;
+    over the list the entries that stayed uncorrected, the ranges of the determinant and of the trace and the largest
+    shear rate with its row.  The definition the GPU pass (`pgsd.fl.PGSDFile.sph_tensors_device`,
+    `HOOMDTrajectory.frame_gradient_tensors_device`) equals exactly, the floats bit for bit.
+
+    Args:
+        position, velocity, box, h, mass, rows, cells, dimensions, kernel: `sph_kernel_gradients`'.  The grid, the support
+            ``2h``, ``r2``, ``inv_h``, ``sigma``, ``G``, the list in cell order, THE ORDER of the candidates and every
+            refusal are its own.
+        density: ``N`` float32 or float64 values, or ``None``: the schema's default, 0.0 in every row (the values that
+            result may be infinite or NaN: that is defined behaviour).
+        det_min (float): an entry is corrected where ``det_min < det < inf``; a number, at least 0.  The caller's knob,
+            not a tuned figure: 0.25 is a convention, an interior particle has ``det`` near 1 and a flat free surface
+            about one half.
+
+    **One pair**, float64 throughout without contraction, float32 inputs converted exactly before any subtraction: ``d``,
+    ``d2``, the strict test ``d2 < r2``, ``rr``, ``q``, ``F``, ``e_k = F * d_k`` and ``u_k = v_j[k] - v_i[k]`` as in
+    `sph_kernel_gradients`; ``i`` itself and coincident entries are candidates like any other; ``V_j = m_j / rho_j``.
+    Fifteen accumulators per entry start at ``+0.0`` and add in the defined order: ``b_ab += V_j * (d_a * e_b)`` for ``ab``
+    in ``(00, 01, 02, 11, 12, 22)`` and ``g_ab += V_j * (u_a * e_b)`` for all nine ``ab``, row ``a`` the velocity component
+    and column ``b`` the derivative direction.
+
+    **After the last candidate**, every product and sum in the association shown: ``B_ab = G*b_ab``, ``R_ab = G*g_ab``
+    (``R`` is the uncorrected ``dv_a/dx_b``).  In 3-D ``c00 = B11*B22 - B12*B12``, ``c01 = B02*B12 - B01*B22``, ``c02 =
+    B01*B12 - B02*B11``, ``c11 = B00*B22 - B02*B02``, ``c12 = B01*B02 - B00*B12``, ``c22 = B00*B11 - B01*B01`` and ``det =
+    (B00*c00 + B01*c01) + B02*c02``.  In 2-D (``d_z`` is 0, so the z row and column of ``B`` vanish) ``det = B00*B11 -
+    B01*B01``, ``c00 = B11``, ``c01 = -B01``, ``c11 = B00`` and ``c02 = c12 = c22 = +0.0``.  ``ok = det > det_min and det <
+    inf``; a NaN is never ``ok``.  Where ``ok``: ``L_ab = c_ab / det`` (2-D: the three z entries are ``+0.0``, written) and
+    ``D_ab = (R_a0*L_0b + R_a1*L_1b) + R_a2*L_2b`` (2-D: ``D_ab = R_a0*L_0b + R_a1*L_1b`` for ``b < 2`` and ``D_a2 = +0.0``,
+    written).  Where not ``ok``: ``L`` is the identity (2-D: ``diag(1, 1, 0)``) and ``D_ab = R_ab``, both written, not
+    computed.  Then ``trace = (D00 + D11) + D22``, ``s01 = 0.5*(D01 + D10)``, ``s02 = 0.5*(D02 + D20)``, ``s12 = 0.5*(D12 +
+    D21)``, ``ss = ((D00*D00 + D11*D11) + D22*D22) + 2.0*((s01*s01 + s02*s02) + s12*s12)`` and ``shear_rate =
+    sqrt(2.0*ss)``.  An entry without a cell contributes to nobody and all its values are ``+0.0``, written.
+
+    Returns a `KernelTensors`.
+    """
+    asked = _sph_asked(box, h, cells, dimensions, kernel)
+    det_min = _sph_det_min(det_min)
+    t = _sph_list(asked, position, box, rows, (('mass', mass, 1), ('density', density, 1), ('velocity', velocity, 3)))
+    dimensions, h, kid, grid = asked[0], asked[1], asked[2], asked[4]
+    n, somewhere = t.n, t.somewhere
+    mass, rho, v = t.columns
+    m = numpy.ones(n, dtype=numpy.float64) if mass is None else mass
+    rho = numpy.zeros(n, dtype=numpy.float64) if rho is None else rho
+    v = numpy.zeros((n, 3), dtype=numpy.float64) if v is None else v
+    G = numpy.float64(-((t.sigma * t.inv_h) * t.inv_h))
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        vol = m / rho
+    upper = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+    b = [numpy.zeros(n, dtype=numpy.float64) for _ in range(6)]
+    g = [numpy.zeros(n, dtype=numpy.float64) for _ in range(9)]
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        for i, j, d, d2 in _sph_near_pairs(t):
+            F = sph_gradient_factor(numpy.sqrt(d2) * t.inv_h, kernel)
+            e = [F * d[0], F * d[1], F * d[2]]
+            u = [v[j, 0] - v[i, 0], v[j, 1] - v[i, 1], v[j, 2] - v[i, 2]]
+            V = vol[j]
+            for k, (r, c) in enumerate(upper):
+                numpy.add.at(b[k], i, V * (d[r] * e[c]))
+            for r in range(3):
+                for c in range(3):
+                    numpy.add.at(g[3 * r + c], i, V * (u[r] * e[c]))
+        ok, L, det, D, trace, shear = _spht_epilogue(G, b, g, dimensions, det_min)
+    correction, gradient = numpy.stack(L, axis=1), numpy.stack(D, axis=1)
+    for a in (correction, det, gradient, trace, shear):
+        a[somewhere:] = 0.0
+    words = _spht_summary(n, somewhere, t.rows_sorted, ok, det, trace, shear)
+    return KernelTensors(h, SPH_KERNELS[kid], grid, dimensions, words, det_min, t.rows_sorted, t.cell_sorted, correction, det,
+                         gradient, shear)
+
+
+def frame_gradient_tensors(frame_or_arrays, h=None, kernel='wendland_c2', det_min=0.25, cells=None, where=None, types=None,
+                           domain=None, box=None, dimensions=3):
+    """`sph_gradient_tensors` of a frame's ``position``, ``velocity``, ``mass`` and ``density`` over a selection: the host
+    twin of `HOOMDTrajectory.frame_gradient_tensors_device`, which equals it exactly.  The selection, the ``h=None`` rule,
+    the refusals and the defaults are `frame_kernel_gradients`'; a velocity that is stored nowhere is the zero vector, a
+    mass 1.0 and a density the schema's 0.0.  Returns a `KernelTensors`."""
+    arrays, position, box, dimensions, h, rows = _sph_frame_list(frame_or_arrays, h, where, types, domain, box, dimensions)
+    return sph_gradient_tensors(position, arrays.get('velocity'), box, h, mass=arrays.get('mass'),
+                                density=arrays.get('density'), rows=rows, cells=cells, dimensions=dimensions, kernel=kernel,
+                                det_min=det_min)
+
+
 # ---- SPH accelerations: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_accelerations_device`) equals exactly
-_SPHF_SUMMARY_WORDS = 12    # n, nowhere, not_finite, 3 x (at, row) of total, pressure, viscous, then total2, pressure2, viscous2
+_SPHF_SUMMARY_WORDS = 12   # n, nowhere, not_finite, 3 x (at, row) of total, pressure, viscous, then total2, pressure2, viscous2
 _SPHF_NORMS = ('total', 'pressure', 'viscous')
 
 
@@ -5693,8 +5936,8 @@ class HOOMDTrajectory(object):
         return got
 
     def _sph_device_list(self, who, idx, h, kernel, cells, where, domain, names, second=None):
-        """What `frame_kernel_sums_device`, `frame_kernel_gradients_device` and `frame_accelerations_device` share ahead of
-        their pass: the ``h=None``
+        """What `frame_kernel_sums_device`, `frame_kernel_gradients_device`, `frame_gradient_tensors_device` and
+        `frame_accelerations_device` share ahead of their pass: the ``h=None``
         rule, the grid for the support ``2h``, the selection as a row list sorted by cell on the GPU and, for each of
         ``names``, the effective chunk ``(frame, name)`` or ``None``.  ``(f_pos, box, dims, h, grid, rows, cell, count,
         chunks, [mass default, density default])``; the caller ends with `wait_read`, whatever is raised here.
@@ -5755,6 +5998,37 @@ class HOOMDTrajectory(object):
             got = f.sph_gradients_device(f_pos, 'particles/position', box, h, grid, rows, cell, n=count, velocity=chunks[2],
                                          mass=chunks[0], density=chunks[1], defaults=defaults, dimensions=dims, kernel=kernel,
                                          return_rows=return_rows)
+        finally:
+            f.wait_read()
+        return got
+
+    def frame_gradient_tensors(self, idx, h=None, kernel='wendland_c2', det_min=0.25, cells=None, where=None, domain=None):
+        """`frame_gradient_tensors` of frame ``idx`` read through the host path: a `KernelTensors`.  The definition of
+        `frame_gradient_tensors_device`."""
+        return frame_gradient_tensors(self[int(idx)], h, kernel=kernel, det_min=det_min, cells=cells, where=where,
+                                      domain=domain)
+
+    def frame_gradient_tensors_device(self, idx, h=None, kernel='wendland_c2', det_min=0.25, cells=None, where=None,
+                                      domain=None, return_rows=False):
+        """`frame_gradient_tensors` of frame ``idx``, on the GPU: a `KernelTensors` that equals
+        ``frame_gradient_tensors(idx, h, ...)`` exactly -- every counter and index, every float bit for bit.
+
+        ``h=None``, the selection, the grid and the ordering are `frame_kernel_sums_device`'s; the pass
+        (`pgsd.fl.PGSDFile.sph_tensors_device`) runs over the staged position chunk and the effective ``velocity``,
+        ``mass`` and ``density`` chunks; one that is stored nowhere costs nothing: the zero vector and the schema defaults
+        1.0 and 0.0 stand for every row.  ``return_rows=True`` leaves ``rows``, ``cell``, ``correction``, ``determinant``,
+        ``velocity_gradient`` and ``shear_rate`` in GPU memory on the result; otherwise they are ``None`` and no
+        per-particle data is kept.  One `wait_read` at the end releases the staged chunks.  A frame whose position is
+        stored nowhere has no chunk to search and raises ValueError.
+        """
+        f = self.file
+        try:
+            det_min = _sph_det_min(det_min)
+            f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults = self._sph_device_list(
+                "frame_gradient_tensors_device", idx, h, kernel, cells, where, domain, ('mass', 'density', 'velocity'))
+            got = f.sph_tensors_device(f_pos, 'particles/position', box, h, grid, rows, cell, n=count, velocity=chunks[2],
+                                       mass=chunks[0], density=chunks[1], defaults=defaults, dimensions=dims, kernel=kernel,
+                                       det_min=det_min, return_rows=return_rows)
         finally:
             f.wait_read()
         return got

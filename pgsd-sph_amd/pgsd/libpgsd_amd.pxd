@@ -274,6 +274,12 @@ cdef extern from "pgsd_private.h" nogil:
                                   const uint32_t* cells, const uint32_t* rows, const int32_t* cell, uint64_t n,
                                   double* out_density_rate, double* out_divergence, double* out_curl, double* out_normal,
                                   uint64_t* out_summary)
+    int pgsd_sph_tensors_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* velocity,
+                                const pgsd_index_entry* mass, const pgsd_index_entry* density, const double* defaults,
+                                const double* vectors, double h, uint32_t kernel, uint32_t dimensions, double det_min,
+                                const uint32_t* cells, const uint32_t* rows, const int32_t* cell, uint64_t n,
+                                double* out_correction, double* out_determinant, double* out_velocity_gradient,
+                                double* out_shear_rate, uint64_t* out_summary)
     int pgsd_sph_accelerations_device(pgsd_handle* handle, const pgsd_index_entry* position,
                                       const pgsd_index_entry* velocity, const pgsd_index_entry* mass,
                                       const pgsd_index_entry* density, const pgsd_index_entry* pressure,
