@@ -1,5 +1,5 @@
 // pgsd_cells.hpp -- what every pass over a row list in cell order begins with (pgsd_cells.hip, pgsd_neighbours.hip,
-// pgsd_neighbour_list.hip, pgsd_components.hip, pgsd_sph.hip, pgsd_sph_gradients.hip, pgsd_sph_tensors.hip, pgsd_sph_forces.hip, pgsd_sph_samples.hip): the two kernels, defined in pgsd_cells.hip -- the check of the lists and the CSR
+// pgsd_neighbour_list.hip, pgsd_components.hip, pgsd_sph.hip, pgsd_sph_adaptive.hip, pgsd_sph_gradients.hip, pgsd_sph_tensors.hip, pgsd_sph_forces.hip, pgsd_sph_samples.hip): the two kernels, defined in pgsd_cells.hip -- the check of the lists and the CSR
 // offsets --, and on the host the refusal of a list, chunk or grid before anything is launched (cells_refuse_grid) and the
 // opening sequence on the stream (cells_open_pass), written once for all their launchers.  The refusal protocol is
 // order_key_kernel's: a device flag word and a pinned one; every later kernel reads the device flag first and does

@@ -215,6 +215,7 @@ int DevicePipeline::init()
         warm_components_kernels();
         warm_component_moments_kernels();
         warm_sph_kernels();
+        warm_sph_adaptive_kernels();
         warm_sph_gradients_kernels();
         warm_sph_tensors_kernels();
         warm_sph_forces_kernels();

@@ -621,6 +621,27 @@ int device_pipeline_sph_sums(DevicePipeline* p, const ChunkRange* ranges, const 
                             { return launch_sph_sums(a, out_number, out_density, out_shepard, out_summary, stream, why); });
     }
 
+// SPH sums with a per-particle smoothing length: the sums' three slots and the slength chunk where one is stored
+int device_pipeline_sph_adaptive(DevicePipeline* p, const ChunkRange* ranges, const SphAdaptiveArgs& args, uint32_t* out_count,
+                                 double* out_number, double* out_density, double* out_shepard, double* out_omega,
+                                 uint64_t* out_summary, std::string* err)
+    {
+    SphAdaptiveArgs a = args;
+    const void** const slots[4] = {&a.pos, &a.mass, &a.density, &a.slength};
+    return p->staged_launch(ranges, slots, 4, a.present | 1u, a.N, true, err, [&](hipStream_t stream, std::string* why)
+                            { return launch_sph_adaptive_sums(a, out_count, out_number, out_density, out_shepard, out_omega,
+                                                              out_summary, stream, why); });
+    }
+
+// The smoothing range: the slength chunk alone; the row list is the caller's.
+int device_pipeline_sph_smoothing_range(DevicePipeline* p, long long file_offset, size_t bytes, uint32_t f64,
+                                        const uint32_t* rows, uint64_t n, uint64_t N, uint64_t* out_words, std::string* err)
+    {
+    const void* slength = nullptr;
+    return one_chunk_pass(p, file_offset, bytes, &slength, N, true, err, [&](hipStream_t stream, std::string* why)
+                          { return launch_sph_smoothing_range(slength, f64, rows, n, N, out_words, stream, why); });
+    }
+
 // SPH kernel gradients: as the sums, with one more slot: the velocity chunk where one is stored
 int device_pipeline_sph_gradients(DevicePipeline* p, const ChunkRange* ranges, const SphGradientsArgs& args, double* out_rate,
                                   double* out_divergence, double* out_curl, double* out_normal, uint64_t* out_summary,

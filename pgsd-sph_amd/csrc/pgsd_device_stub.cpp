@@ -41,6 +41,8 @@ int device_pipeline_cell_offsets(DevicePipeline*, const int32_t*, uint64_t, uint
 int device_pipeline_cell_moments(DevicePipeline*, const ChunkRange*, const CellMomentsArgs&, uint64_t*, double*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_neighbours(DevicePipeline*, long long, size_t, const NeighboursArgs&, const double*, uint32_t*, double*, uint32_t*, uint64_t*, double*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_sums(DevicePipeline*, const ChunkRange*, const SphArgs&, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
+int device_pipeline_sph_adaptive(DevicePipeline*, const ChunkRange*, const SphAdaptiveArgs&, uint32_t*, double*, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
+int device_pipeline_sph_smoothing_range(DevicePipeline*, long long, size_t, uint32_t, const uint32_t*, uint64_t, uint64_t, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_gradients(DevicePipeline*, const ChunkRange*, const SphGradientsArgs&, double*, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_tensors(DevicePipeline*, const ChunkRange*, const SphTensorsArgs&, double*, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }
 int device_pipeline_sph_accelerations(DevicePipeline*, const ChunkRange*, const SphForcesArgs&, double*, double*, double*, uint64_t*, std::string*) { return PGSD_ERROR_NO_DEVICE; }

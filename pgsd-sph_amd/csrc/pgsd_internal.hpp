@@ -532,6 +532,55 @@ inline void sph_sums_of_nothing(uint64_t* out_summary)
 // and a descending id refuse the call.  The staged rows stay until the next wait_read.
 int device_pipeline_sph_sums(DevicePipeline*, const ChunkRange* ranges, const SphArgs& a, double* out_number,
                              double* out_density, double* out_shepard, uint64_t* out_summary, std::string* err);
+// SPH sums with a per-particle smoothing length (pgsd.hoomd.sph_adaptive_sums is the definition): per entry of a row list
+// in cell order the candidates inside its own support, the sums' three values with its own h (gather) or the pair's mean
+// (mean) and the grad-h factor omega, on the grid of the declared bound 2 h_max.  The grid, the list and the defaults are
+// SphArgs' (r2 is (2 h_max)^2; inv_h is not looked at; sigma is the mean mode's constant sph_sigma(kernel, 1)).
+enum
+    {
+    SPHA_GATHER = 0,
+    SPHA_MEAN = 1,
+    SPHA_SUMMARY_WORDS = 22 // n, nowhere, bad_h, not_finite, surface, deviation_at, deviation_row, count_min, count_max,
+                            // count_min_at, 5 x (min, max): slength, number, density, shepard, omega; deviation, pairs
+    };
+struct SphAdaptiveArgs : SphArgs
+    {
+    const void* slength; // the staged smoothing-length chunk, or null: h_default stands for every row
+    double h_default;
+    double h_max;        // the declared bound: a listed valid h above it refuses the call
+    uint32_t slength_f64, mode; // present bit 3: a slength chunk is stored (ranges[3])
+    };
+// the summary of no entry
+inline void sph_adaptive_sums_of_nothing(uint64_t* out_summary)
+    {
+    const double lo = HUGE_VAL, hi = -HUGE_VAL;
+    std::fill(out_summary, out_summary + SPHA_SUMMARY_WORDS, (uint64_t)0); // (+0.0 is the zero word)
+    out_summary[5] = out_summary[6] = out_summary[9] = SPH_NONE;
+    for (int s = 0; s < 5; s++)
+        {
+        memcpy(&out_summary[10 + 2 * s], &lo, sizeof(double));
+        memcpy(&out_summary[11 + 2 * s], &hi, sizeof(double));
+        }
+    }
+// the smoothing range of no entry: n = 0, bad = 0, h_min = +inf, h_max = -inf
+inline void sph_range_of_nothing(uint64_t* out_words)
+    {
+    const double lo = HUGE_VAL, hi = -HUGE_VAL;
+    out_words[0] = out_words[1] = 0;
+    memcpy(&out_words[2], &lo, sizeof(double));
+    memcpy(&out_words[3], &hi, sizeof(double));
+    }
+// stage the chunks that are present (ranges[0 .. 3]: position, mass, density, slength), check the lists and the bound, sum
+// on the GPU; out_count (device, a.n uint32), out_number, out_density, out_shepard, out_omega (device, a.n doubles), each
+// or null; out_summary (host, 22 words) is written on success only, and so are the device outputs; synchronous.  The
+// refusals and the staging are device_pipeline_sph_sums'.
+int device_pipeline_sph_adaptive(DevicePipeline*, const ChunkRange* ranges, const SphAdaptiveArgs& a, uint32_t* out_count,
+                                 double* out_number, double* out_density, double* out_shepard, double* out_omega,
+                                 uint64_t* out_summary, std::string* err);
+// stage the smoothing-length chunk (or take it from what an earlier call left staged) and reduce it over a row list
+// (device, n entries; null: every row): out_words (host, 4 words) is written on success only; synchronous
+int device_pipeline_sph_smoothing_range(DevicePipeline*, long long file_offset, size_t bytes, uint32_t f64, const uint32_t* rows,
+                                        uint64_t n, uint64_t N, uint64_t* out_words, std::string* err);
 // SPH kernel gradients (pgsd.hoomd.sph_kernel_gradients is the definition): per entry of a row list in cell order the
 // density rate, the velocity divergence and curl and the colour gradient over the entries inside the support 2h, in the
 // sums' order, and over the list the ranges of the two scalars and the largest curl and normal.  The grid, the support,

@@ -356,6 +356,22 @@ int launch_sph_sums(const SphArgs& a, double* out_number, double* out_density, d
 // entries), out_curl, out_normal (device, a.n x 3), each or null; out_summary (host, 13 words) is written on success only.
 // Synchronises `stream`; PGSD_ERROR_INVALID_ARGUMENT for an id that descends or lies outside [0, n_cells] and for an
 // entry >= a.N
+// SPH sums with a per-particle smoothing length (pgsd_sph_adaptive.hip; SphAdaptiveArgs, the chunk pointers filled in):
+// check, offsets, compaction with the float64 h column and the check of the declared bound h_max, one lane per entry over
+// the candidates in the sums' order for the range 2 h_max (pgsd_traverse.hpp) with the per-pair support test, one workgroup
+// for the summary.  out_count (device, a.n uint32), out_number, out_density, out_shepard (with a.volume), out_omega (gather
+// mode) (device, a.n doubles), each or null; out_summary (host, 22 words) is written on success only.  Synchronises
+// `stream`; PGSD_ERROR_INVALID_ARGUMENT for what launch_sph_sums refuses, an unknown mode, an h_max that is not valid and a
+// listed valid smoothing length above h_max
+int launch_sph_adaptive_sums(const SphAdaptiveArgs& a, uint32_t* out_count, double* out_number, double* out_density,
+                             double* out_shepard, double* out_omega, uint64_t* out_summary, hipStream_t stream,
+                             std::string* err);
+// (n, bad, h_min, h_max) of a staged smoothing-length chunk (float32 or float64, N rows) over a row list (device, n
+// entries; null: every row, n == N): out_words (host, 4 words: two counts, two float64 bit patterns) is written on success
+// only.  Synchronises `stream`; PGSD_ERROR_INVALID_ARGUMENT for an entry >= N
+int launch_sph_smoothing_range(const void* slength, uint32_t f64, const uint32_t* rows, uint64_t n, uint64_t N,
+                               uint64_t* out_words, hipStream_t stream, std::string* err);
+
 int launch_sph_gradients(const SphGradientsArgs& a, double* out_rate, double* out_divergence, double* out_curl,
                          double* out_normal, uint64_t* out_summary, hipStream_t stream, std::string* err);
 
@@ -459,6 +475,7 @@ void warm_neighbour_list_kernels();
 void warm_components_kernels();
 void warm_component_moments_kernels();
 void warm_sph_kernels();
+void warm_sph_adaptive_kernels();
 void warm_sph_gradients_kernels();
 void warm_sph_tensors_kernels();
 void warm_sph_forces_kernels();

@@ -59,6 +59,9 @@
  *                     entry of a row list in cell order the SPH summation density, number density and Shepard sum over
  *                     the kernel support, in a defined order, and over the list their ranges, the largest deviation from
  *                     the stored density and the entries below a Shepard threshold)
+ *                     pgsd_sph_smoothing_range_device, pgsd_sph_adaptive_sums_device (pgsd.fl's smoothing_range_device
+ *                     and sph_adaptive_sums_device, behind pgsd.hoomd's frame_adaptive_sums_device: the sums with the
+ *                     smoothing length stored per particle, the neighbour count and the grad-h factor)
  *                     pgsd_sph_gradients_device (pgsd.fl's sph_gradients_device, behind pgsd.hoomd's
  *                     frame_kernel_gradients_device: per entry of the same list, over the same support and in the same
  *                     order, the density rate of the continuity equation, the velocity divergence and curl and the
@@ -562,6 +565,61 @@ extern "C"
                              uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows, const int32_t* cell,
                              uint64_t n, double surface_below, double* out_number, double* out_density,
                              double* out_shepard, uint64_t* out_summary);
+
+    /* The range of a smoothing-length chunk over a row list (pgsd.hoomd.smoothing_range is the definition): what a caller
+       needs before it can choose the grid of pgsd_sph_adaptive_sums_device, without copying a row to the host.  slength:
+       one float32 or float64 column of N rows, or NULL: h_default stands for every row (nothing is read).  rows: device,
+       n entries < N, or NULL: every row.  h is valid when h > 0.0 and h < +inf.
+       Host output, 4 words: the entries; those whose h is not valid; as float64 bit patterns the smallest and the largest
+       valid h (+inf and -inf without one).  A minimum and a maximum: no order enters.  Staging and synchronisation are
+       pgsd_chunk_stats_device's.  PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), out_words as it was: a
+       chunk that is no such column, an entry >= N. */
+    int pgsd_sph_smoothing_range_device(struct pgsd_handle* handle, const struct pgsd_index_entry* slength, double h_default,
+                                        const uint32_t* rows, uint64_t n, uint64_t N, uint64_t* out_words);
+
+    /* SPH sums with a per-particle smoothing length (pgsd.hoomd.sph_adaptive_sums is the definition, and the results equal
+       it exactly: every counter and index, every float bit for bit -- a NaN is a NaN).  position, mass, density, vectors,
+       kernel, dimensions, cells, rows, cell, n and surface_below are pgsd_sph_sums_device's.  slength: one float32 or
+       float64 column of the position chunk's N rows, or NULL.  defaults: the mass, the density (NaN: no volume sum) and
+       the smoothing length that stand for a chunk stored nowhere.  h_max: the declared bound of the listed valid
+       smoothing lengths; the grid, every refusal and THE ORDER of the candidates are pgsd_sph_sums_device's for h = h_max.
+       mode: 0 gather, 1 mean.
+       h is VALID when h > 0.0 and h < +inf.  An entry whose h is not valid is treated like an entry nowhere: it contributes
+       to nobody and every per-entry output of it is +0.0, written; it is counted in bad_h (if it has a cell), not in
+       nowhere.  An entry is LIVE when it has a cell and a valid h.
+       ONE PAIR i <- j, float64, no contraction, d2 as pgsd_sph_sums_device; i itself and coincident entries are candidates.
+       gather: once per entry s_i = 2.0*h_i, r2_i = s_i*s_i, inv_i = 1.0/h_i; j contributes when d2 < r2_i, strictly; rr =
+       sqrt(d2), q = rr*inv_i, w = w(q), F = F(q) of pgsd_sph_gradients_device; a_n += w, a_m += m_j*w, a_v += V_j*w (with a
+       volume), a_o += m_j*(D*w + (q*q)*F) with D = 2.0 or 3.0, count += 1.  After the last candidate sigma_i = the sums'
+       sigma for h_i, number = sigma_i*a_n, density = sigma_i*a_m, shepard = sigma_i*a_v, omega = 1.0 - a_o/(D*a_m).
+       mean: s = h_i + h_j, j contributes when d2 < s*s; hij = 0.5*s, ih = 1.0/hij, q = sqrt(d2)*ih, w = w(q), p = ih*ih (2-D)
+       or (ih*ih)*ih (3-D), wp = w*p; a_n += wp, a_m += m_j*wp, a_v += V_j*wp, count += 1; afterwards number = C*a_n and so
+       on with C the sums' sigma for h = 1.0; out_omega is not written.
+       Device outputs, each optional (NULL): out_count, n uint32; out_number, out_density, out_shepard (with a volume
+       only), out_omega (gather only), n float64.
+       Host output, 22 words:
+           out_summary[0 .. 4]    n; the entries nowhere; bad_h; the live entries whose density is NaN or infinite; the
+                                  live entries with shepard < surface_below
+           out_summary[5], [6]    the list position of the deviation and its row, with pgsd_sph_sums_device's rule over the
+                                  live entries; 0xFFFFFFFF without one
+           out_summary[7 .. 9]    the smallest and the largest count over the live entries and the list position of the
+                                  smallest (the smaller position on a tie); 0, 0, 0xFFFFFFFF without one
+           out_summary[10 .. 19]  as float64 bit patterns the minimum and maximum of slength, number, density, shepard and
+                                  omega over the live entries, by strict compares from +inf and -inf: a NaN never replaces a
+                                  value (shepard without a volume and omega in mean mode: +inf, -inf)
+           out_summary[20]        as a float64 bit pattern the deviation; +0.0 without one
+           out_summary[21]        pairs, the exact sum of count
+       No float is summed over the list.  Staging, synchronisation and n == 0 are pgsd_sph_sums_device's.
+       PGSD_ERROR_INVALID_ARGUMENT with a pgsd_last_error_string(), every output as it was: everything
+       pgsd_sph_sums_device refuses for the range 2*h_max; an unknown mode; a slength chunk that is not one float32 or
+       float64 column of N rows; an h_max that is not valid; a listed valid h above h_max (found on the device). */
+    int pgsd_sph_adaptive_sums_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                      const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
+                                      const struct pgsd_index_entry* slength, const double defaults[3],
+                                      const double vectors[6], double h_max, uint32_t kernel, uint32_t mode,
+                                      uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows, const int32_t* cell,
+                                      uint64_t n, double surface_below, uint32_t* out_count, double* out_number,
+                                      double* out_density, double* out_shepard, double* out_omega, uint64_t* out_summary);
 
     /* SPH kernel gradients (pgsd.hoomd.sph_kernel_gradients is the definition, and the results equal it exactly: every
        counter and index, every float bit for bit -- a NaN is a NaN).  position, mass, density, defaults, vectors, h,

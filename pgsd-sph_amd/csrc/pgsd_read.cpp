@@ -1387,6 +1387,131 @@ catch (...)
         return pgsd_amd::abi_guard();
     }
 
+extern "C" int pgsd_sph_smoothing_range_device(struct pgsd_handle* handle, const struct pgsd_index_entry* slength,
+                                               double h_default, const uint32_t* rows, uint64_t n, uint64_t N,
+                                               uint64_t* out_words)
+    try
+    {
+    static const char* who = "pgsd_sph_smoothing_range_device";
+    Impl* s = impl_of(handle);
+    if (!s || !out_words)
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    if (N >= (1ull << 32))
+        return refuse("chunks of 2^32 rows or more have no 32-bit row list");
+    if (rows && n >= (1ull << 32))
+        return refuse("a list holds fewer than 2^32 entries");
+    const uint64_t count = rows ? n : N;
+    uint64_t words[4];
+    if (!slength || count == 0)
+        {
+        // no chunk: the default in every row, whatever the list holds -- nothing to read on the device
+        if (slength && slength->N != N)
+            return refuse("the slength chunk holds N rows");
+        sph_range_of_nothing(words);
+        words[0] = count;
+        if (count > 0)
+            {
+            if (h_default > 0.0 && h_default < HUGE_VAL)
+                {
+                memcpy(&words[2], &h_default, sizeof(double));
+                memcpy(&words[3], &h_default, sizeof(double));
+                }
+            else
+                words[1] = count;
+            }
+        std::copy(words, words + 4, out_words);
+        return PGSD_SUCCESS;
+        }
+    pgsd_index_entry c = *slength; // a flush may move the index storage
+    uint32_t f64 = 0;
+    int rc = float_chunk(refuse, c, "the slength chunk", 1, nullptr, &f64);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    if (c.N != N)
+        return refuse("the slength chunk holds N rows");
+    long long foff = 0;
+    size_t bytes = 0;
+    rc = whole_chunk_range(s, handle, c, &foff, &bytes);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    rc = reduction_call(who, "smoothing range: ", [&](std::string* err)
+                        { return device_pipeline_sph_smoothing_range(s->dev, foff, bytes, f64, rows, count, N, words, err); });
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    std::copy(words, words + 4, out_words);
+    return PGSD_SUCCESS;
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
+extern "C" int pgsd_sph_adaptive_sums_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
+                                             const struct pgsd_index_entry* mass, const struct pgsd_index_entry* density,
+                                             const struct pgsd_index_entry* slength, const double defaults[3],
+                                             const double vectors[6], double h_max, uint32_t kernel, uint32_t mode,
+                                             uint32_t dimensions, const uint32_t cells[3], const uint32_t* rows,
+                                             const int32_t* cell, uint64_t n, double surface_below, uint32_t* out_count,
+                                             double* out_number, double* out_density, double* out_shepard, double* out_omega,
+                                             uint64_t* out_summary)
+    try
+    {
+    static const char* who = "pgsd_sph_adaptive_sums_device";
+    Impl* s = impl_of(handle);
+    if (!s || !position || !defaults || !vectors || !cells || !out_summary || (n > 0 && (!rows || !cell)))
+        return PGSD_ERROR_INVALID_ARGUMENT;
+    const Refusal refuse = {who};
+    if (!(h_max > 0.0 && h_max < HUGE_VAL))
+        return refuse("h_max, the largest listed smoothing length, must be finite and positive");
+    if (mode != SPHA_GATHER && mode != SPHA_MEAN)
+        return refuse("the mode is 0 (gather) or 1 (mean)");
+    ChunkRange ranges[5];
+    SphForcesArgs g;
+    // (the grid, the box and the chunks: everything pgsd_sph_sums_device refuses for the range 2 h_max)
+    int rc = sph_arguments(who, s, handle, position, mass, density, nullptr, nullptr, defaults, vectors, h_max, kernel,
+                           dimensions, cells, rows, cell, n, surface_below, ranges, g);
+    if (rc != PGSD_SUCCESS)
+        return rc;
+    SphAdaptiveArgs a = SphAdaptiveArgs();
+    static_cast<SphArgs&>(a) = g;
+    a.h_default = defaults[2];
+    a.h_max = h_max;
+    a.mode = mode;
+    if (slength)
+        {
+        const pgsd_index_entry m = *slength;
+        rc = float_chunk(refuse, m, "the slength chunk", 1, &a.N, &a.slength_f64);
+        if (rc == PGSD_SUCCESS)
+            rc = whole_chunk_range(s, handle, m, &ranges[3].file_offset, &ranges[3].bytes);
+        if (rc != PGSD_SUCCESS)
+            return rc;
+        a.present |= 8u;
+        }
+    if (mode == SPHA_MEAN)
+        {
+        // the mean mode's constant: sph_sigma(kernel, 1.0, dimensions)
+        const double pi = 3.141592653589793;
+        if (dimensions == 3)
+            a.sigma = kernel == SPH_WENDLAND_C2 ? 21.0 / (16.0 * pi * 1.0) : 1.0 / (pi * 1.0);
+        else
+            a.sigma = kernel == SPH_WENDLAND_C2 ? 7.0 / (4.0 * pi * 1.0) : 10.0 / (7.0 * pi * 1.0);
+        }
+    if (n == 0)
+        {
+        sph_adaptive_sums_of_nothing(out_summary);
+        return PGSD_SUCCESS;
+        }
+    // (the launcher writes the outputs on success only, behind its last check)
+    return reduction_call(who, "adaptive SPH sums: ", [&](std::string* err)
+                          { return device_pipeline_sph_adaptive(s->dev, ranges, a, out_count, out_number, out_density,
+                                                                out_shepard, out_omega, out_summary, err); });
+    }
+catch (...)
+    {
+        return pgsd_amd::abi_guard();
+    }
+
 extern "C" int pgsd_sph_gradients_device(struct pgsd_handle* handle, const struct pgsd_index_entry* position,
                                          const struct pgsd_index_entry* velocity, const struct pgsd_index_entry* mass,
                                          const struct pgsd_index_entry* density, const double defaults[2],

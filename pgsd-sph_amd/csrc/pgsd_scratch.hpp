@@ -10,7 +10,7 @@
 // cell fields of pgsd_cells.hip, the neighbour census of pgsd_neighbours.hip, the neighbour lists of
 // pgsd_neighbour_list.hip, the components of pgsd_components.hip, the component fields of
 // pgsd_component_moments.hip, the SPH kernel sums of pgsd_sph.hip, the SPH kernel gradients of pgsd_sph_gradients.hip, the
-// SPH gradient tensors of pgsd_sph_tensors.hip, the
+// SPH gradient tensors of pgsd_sph_tensors.hip, the SPH sums with a per-particle smoothing length of pgsd_sph_adaptive.hip, the
 // SPH accelerations of pgsd_sph_forces.hip and the SPH samples of pgsd_sph_samples.hip (each with a Scratch of its own).  Neither the
 // locks nor the allocations are merged: that would change what may run concurrently and how much memory is held.
 #ifndef PGSD_SCRATCH_HPP

@@ -23,6 +23,8 @@
 //   pgsd_sph_gradients.hip   the SPH kernel gradients: density rate, velocity divergence and curl and the colour gradient
 //                      over the same support in the same order (pgsd_traverse.hpp: the traversal as an inlined template,
 //                      which the pair units walk their candidates through)
+//   pgsd_sph_adaptive.hip   the SPH sums with a per-particle smoothing length: the neighbour count, the three sums and the
+//                      grad-h factor over the support 2 h_i or h_i + h_j, on the grid of the declared bound 2 h_max
 //   pgsd_sph_tensors.hip   the SPH gradient tensors: the kernel-gradient correction matrix, the corrected velocity gradient
 //                      and the shear rate over the same support in the same order (pgsd_sph_compact.hpp: the compaction
 //                      kernel it shares with the gradients)

@@ -9,7 +9,7 @@
 // into xs and the read of one column value -- and what the weighted units share, the weight w(q) and the factor F(q).
 // traverse_candidates_around takes the centre from its caller -- a point that is no entry of the list (pgsd_sph_samples.hip)
 // --, traverse_candidates loads entry k's position and forwards to it.  Used by pgsd_neighbours.hip,
-// pgsd_neighbour_list.hip, pgsd_components.hip, pgsd_sph.hip, pgsd_sph_gradients.hip, pgsd_sph_tensors.hip, pgsd_sph_forces.hip and pgsd_sph_samples.hip, which carry
+// pgsd_neighbour_list.hip, pgsd_components.hip, pgsd_sph.hip, pgsd_sph_adaptive.hip, pgsd_sph_gradients.hip, pgsd_sph_tensors.hip, pgsd_sph_forces.hip and pgsd_sph_samples.hip, which carry
 // no copy of any of it.  Seen by the HIP compiler alone.
 #ifndef PGSD_TRAVERSE_HPP
 #define PGSD_TRAVERSE_HPP
@@ -27,7 +27,7 @@ struct TraverseGrid
     uint32_t dims;
     };
 
-// the grid of a family's argument struct (NeighboursArgs, SphArgs, SphGradientsArgs, SphTensorsArgs, SphForcesArgs, SphSamplesArgs)
+// the grid of a family's argument struct (NeighboursArgs, SphArgs, SphAdaptiveArgs, SphGradientsArgs, SphTensorsArgs, SphForcesArgs, SphSamplesArgs)
 template<typename Args> __device__ __forceinline__ TraverseGrid traverse_grid(const Args& a)
     {
     TraverseGrid g;

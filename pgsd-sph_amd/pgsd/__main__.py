@@ -44,6 +44,11 @@
            uniform ``slength``): the search grid and the entries, the ranges of the velocity divergence and of the
            density rate of the continuity equation and the largest vorticity and surface normal, each with its row
            (``--kernel``, ``--types``; ``pgsd.hoomd.frame_kernel_gradients`` on the host: no GPU);
+           ``--sph-adaptive`` adds the SPH sums with the frame's per-particle ``slength`` (``--mode gather|mean``): the
+           search grid for ``2 h_max``, the range of the smoothing length and the entries without a valid one, the range
+           of the neighbour count and the pairs, the range of the summation density and its largest deviation from the
+           stored density and, in gather mode, the range of the grad-h factor ``omega`` (``--kernel``, ``--surface``,
+           ``--types``; ``pgsd.hoomd.frame_adaptive_sums`` on the host: no GPU);
            ``--sph-tensors [H]`` adds the SPH gradient tensors for the smoothing length H (without H: the frame's uniform
            ``slength``): the search grid and the entries, those left uncorrected because the determinant of their
            correction matrix is not above ``--det-min D`` (default 0.25), the ranges of the determinant and of the trace
@@ -143,6 +148,8 @@ def _cmd_info(args):
         _print_sph(args, frame)
     if args.sph_gradients is not None:
         _print_sph_gradients(args, frame)
+    if args.sph_adaptive:
+        _print_sph_adaptive(args, frame)
     if args.sph_tensors is not None:
         _print_sph_tensors(args, frame)
     if args.sph_forces is not None:
@@ -265,6 +272,27 @@ def _print_sph_gradients(args, frame):
             print("  vorticity:    largest %r at row %d" % (m.curl2 ** 0.5, m.curl_row))
         if m.normal2 is not None:
             print("  normal:       largest %r at row %d" % (m.normal2 ** 0.5, m.normal_row))
+
+
+def _print_sph_adaptive(args, frame):
+    """``info --sph-adaptive``: `pgsd.hoomd.frame_adaptive_sums` of one frame, on the host."""
+    from . import hoomd
+    where = {'type': [t for t in args.types.split(',') if t]} if args.types else None
+    with hoomd.open(args.file, 'r') as traj:
+        m = hoomd.frame_adaptive_sums(traj[frame], kernel=args.kernel, mode=args.mode, where=where, surface_below=args.surface)
+    print("SPH sums of frame %d with the per-particle slength (%s, %s), h_max = %r, over %d x %d x %d cells%s:"
+          % ((frame, m.kernel, m.mode, m.h_max) + m.grid + (" (types %s)" % args.types if args.types else "",)))
+    print("  entries:      %d  nowhere: %d  bad_h: %d" % (m.n, m.nowhere, m.bad_h))
+    if m.count_min is not None:
+        print("  slength:      smallest %r  largest %r" % (m.slength_min, m.slength_max))
+        print("  count:        smallest %d at entry %d  largest %d  pairs: %d" % (m.count_min, m.count_min_at, m.count_max, m.pairs))
+        print("  density:      smallest %r  largest %r  not finite: %d" % (m.density_min, m.density_max, m.not_finite))
+        if m.deviation is not None:
+            print("  deviation:    %r at row %d" % (m.deviation, m.deviation_row))
+        if m.surface is not None:
+            print("  surface:      %d below %r" % (m.surface, m.surface_below))
+        if m.omega_min is not None:
+            print("  omega:        smallest %r  largest %r" % (m.omega_min, m.omega_max))
 
 
 def _print_sph_tensors(args, frame):
@@ -607,6 +635,11 @@ def main(argv=None):
     p.add_argument('--sph-gradients', type=float, nargs='?', const=-1.0, default=None, metavar='H',
                    help="print the SPH kernel gradients for the smoothing length H (without H: the frame's uniform "
                         "slength): grid, entries, divergence and density-rate ranges, largest vorticity and normal")
+    p.add_argument('--sph-adaptive', action='store_true',
+                   help="print the SPH sums with the frame's per-particle slength: grid, h range and bad_h, count range "
+                        "and pairs, density range and deviation, omega range")
+    p.add_argument('--mode', type=str, default='gather', choices=('gather', 'mean'),
+                   help="with --sph-adaptive: the support of a pair, 2 h_i (gather) or h_i + h_j (mean) (default: gather)")
     p.add_argument('--sph-tensors', type=float, nargs='?', const=-1.0, default=None, metavar='H',
                    help="print the SPH gradient tensors for the smoothing length H (without H: the frame's uniform "
                         "slength): grid, entries, uncorrected entries, determinant and trace ranges, largest shear rate")
@@ -635,9 +668,9 @@ def main(argv=None):
                    help="with --body-force: the point the torque is taken about (default: 0,0,0; write --about=-1,0,0 "
                         "where X is negative)")
     p.add_argument('--kernel', type=str, default='wendland_c2', choices=('wendland_c2', 'cubic_spline'),
-                   help="the kernel of --sph, --sph-gradients, --sph-tensors, --sph-forces, --sample and --body-force (default: wendland_c2)")
+                   help="the kernel of --sph, --sph-adaptive, --sph-gradients, --sph-tensors, --sph-forces, --sample and --body-force (default: wendland_c2)")
     p.add_argument('--surface', type=float, default=None, metavar='S',
-                   help="with --sph: count the entries whose Shepard sum is below S (the free surface)")
+                   help="with --sph and --sph-adaptive: count the entries whose Shepard sum is below S (the free surface)")
     p.add_argument('--origin', type=int, default=0, help="the frame --displacement measures from (default: 0)")
     p.add_argument('--minimum-image', action='store_true',
                    help="--displacement of the wrapped positions, folded into the box, instead of through the image flags")

@@ -2343,6 +2343,124 @@ cdef class PGSDFile:
             got.shepard = _device_head(out_shepard, count) if volume else None
         return got
 
+    def smoothing_range_device(self, slength, N, rows=None, n=None, default=1.0):
+        """The range of a smoothing-length chunk over a row list, reduced on the GPU: what chooses the grid of
+        :meth:`sph_adaptive_sums_device` without copying a row to the host.
+
+        Args:
+            slength: ``(frame, name)`` of an N x 1 float32 or float64 chunk, or ``None``: stored nowhere, ``default``
+                stands for every row and nothing is read.
+            N (int): the rows of the frame.
+            rows: ``None`` for all rows, or 32-bit row indices in GPU memory, any order, repeats allowed.
+            n (int): the number of entries of ``rows`` to take (default: all of them).
+
+        Returns:
+            ``(n, bad, h_min, h_max)``: exactly :func:`pgsd.hoomd.smoothing_range`.  The chunk is staged whole unless an
+            earlier call left it staged and is kept until the next :meth:`wait_read`.  An entry outside the chunk raises
+            ValueError.  Needs no tensor library.
+        """
+        cdef C.pgsd_index_entry e_slength
+        cdef const C.pgsd_index_entry* p_slength = self._optional(slength, &e_slength)
+        cdef uintptr_t c_rows = 0
+        count = 0
+        if rows is not None:
+            c_rows, count = _row_list("smoothing_range_device", rows, n)
+        elif n is not None:
+            raise ValueError("smoothing_range_device: n goes with rows")
+        words = numpy.zeros(4, dtype=numpy.uint64)
+        if rows is not None and not self._explicit_stream:
+            self._sync_source_stream()      # the reduction is ordered behind this stream's use of `rows`
+        cdef uintptr_t p_words = words.ctypes.data
+        cdef uint64_t c_n = count, c_N = int(N)
+        cdef double c_default = float(default)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_sph_smoothing_range_device(&self._handle, p_slength, c_default, <const uint32_t*>c_rows, c_n, c_N,
+                                                       <uint64_t*>p_words)
+            err = errno
+        _raise_refused("smoothing_range_device", retval, "refused", self._name, err)
+        f = words[2:].view(numpy.float64)
+        return int(words[0]), int(words[1]), float(f[0]), float(f[1])
+
+    def sph_adaptive_sums_device(self, frame, name, box, h_max, cells, rows, cell, n=None, slength=None, mass=None,
+                                 density=None, defaults=None, dimensions=3, kernel='wendland_c2', mode='gather',
+                                 surface_below=None, return_rows=False):
+        """The SPH kernel sums of a row list in cell order on the GPU with the smoothing length stored per particle: the
+        neighbour count inside each entry's own support, number density, summation density, Shepard sum and, in gather
+        mode, the grad-h factor ``omega``, in the order that is part of their definition.
+
+        Args:
+            frame, name, box, cells, rows, cell, n, mass, density, dimensions, kernel, surface_below: as
+                :meth:`sph_sums_device` takes them; the grid is no narrower than ``2*h_max``.
+            h_max (float): the declared bound of the listed valid smoothing lengths (:meth:`smoothing_range_device`),
+                finite and positive; a listed valid ``h`` above it refuses the call.
+            slength: ``(frame, name)`` of an N x 1 float32 or float64 chunk, or ``None``: stored nowhere.
+            defaults: ``(mass, density, slength)`` that stand for a chunk stored nowhere; ``None``: 1.0, no volume sum
+                without a density chunk (a NaN says the same) and 1.0.
+            mode (str): ``'gather'`` (support ``2 h_i``) or ``'mean'`` (support ``h_i + h_j``).
+            return_rows (bool): keep the per-entry results in GPU memory.
+
+        Returns:
+            A :class:`pgsd.hoomd.AdaptiveSums`: exactly :func:`pgsd.hoomd.sph_adaptive_sums` of the same list -- every
+            counter and index, every float bit for bit -- with ``h_max`` the declared one.  With ``return_rows`` its
+            ``rows`` and ``cell`` are the arguments and ``count`` (uint32), ``number``, ``density``, ``shepard`` (``None``
+            without a volume) and ``omega`` (``None`` in mean mode) are arrays of ``n`` entries in GPU memory; otherwise
+            they are ``None``; ``slength`` is always ``None``.  What the library refuses
+            (:c:func:`pgsd_sph_adaptive_sums_device`) raises ValueError and computes nothing.  Needs no tensor library.
+        """
+        from . import hoomd as _hoomd       # (the result type; pgsd.hoomd imports this module, hence not at the top)
+        cdef C.pgsd_index_entry entry, e_mass, e_density, e_slength
+        self._entry(frame, name, &entry)
+        cdef const C.pgsd_index_entry* p_mass = self._optional(mass, &e_mass)
+        cdef const C.pgsd_index_entry* p_density = self._optional(density, &e_density)
+        cdef const C.pgsd_index_entry* p_slength = self._optional(slength, &e_slength)
+        c_vectors = _box_vectors(box)
+        grid, c_cells = _cell_counts("sph_adaptive_sums_device", cells)
+        cdef uint32_t c_kernel = _sph_kernel("sph_adaptive_sums_device", kernel)
+        if mode not in _hoomd.SPH_MODES:
+            raise ValueError("sph_adaptive_sums_device: the mode is one of %s: %r" % (', '.join(_hoomd.SPH_MODES), mode))
+        cdef uint32_t c_mode = _hoomd.SPH_MODES.index(mode)
+        c_defaults = numpy.ascontiguousarray(
+            numpy.array([1.0, float('nan'), 1.0] if defaults is None else defaults, dtype=numpy.float64).reshape(-1))
+        if c_defaults.shape[0] != 3:
+            raise ValueError("sph_adaptive_sums_device: defaults holds a mass, a density and a smoothing length")
+        volume = density is not None or c_defaults[1] == c_defaults[1]
+        gather = c_mode == 0
+        c_rows, c_cell, count = _cell_ordered_lists("sph_adaptive_sums_device", rows, cell, n)
+        summary = numpy.zeros(22, dtype=numpy.uint64)
+        cdef uintptr_t p_count, p_number, p_rho, p_shepard, p_omega
+        device = self.pipeline_device() if return_rows else None
+        out_count, p_count = _per_entry(count, (), numpy.uint32, device)
+        out_number, p_number = _per_entry(count, (), numpy.float64, device)
+        out_rho, p_rho = _per_entry(count, (), numpy.float64, device)
+        out_shepard, p_shepard = _per_entry(count, (), numpy.float64, device if volume else None)
+        out_omega, p_omega = _per_entry(count, (), numpy.float64, device if gather else None)
+        if not self._explicit_stream:
+            self._sync_source_stream()      # the pass is ordered behind this stream's use of `rows` and `cell`
+        cdef uintptr_t p_rows = c_rows, p_cell = c_cell, p_vectors = c_vectors.ctypes.data, p_cells = c_cells.ctypes.data
+        cdef uintptr_t p_defaults = c_defaults.ctypes.data, p_summary = summary.ctypes.data
+        cdef uint64_t c_n = count
+        cdef uint32_t c_dims = int(dimensions) if 0 <= int(dimensions) < (1 << 32) else 0
+        cdef double c_h = float(h_max), c_surface = float('nan') if surface_below is None else float(surface_below)
+        cdef int retval, err
+        with nogil:
+            retval = C.pgsd_sph_adaptive_sums_device(&self._handle, &entry, p_mass, p_density, p_slength,
+                                                     <const double*>p_defaults, <const double*>p_vectors, c_h, c_kernel,
+                                                     c_mode, c_dims, <const uint32_t*>p_cells, <const uint32_t*>p_rows,
+                                                     <const int32_t*>p_cell, c_n, c_surface, <uint32_t*>p_count,
+                                                     <double*>p_number, <double*>p_rho, <double*>p_shepard,
+                                                     <double*>p_omega, <uint64_t*>p_summary)
+            err = errno
+        _raise_refused("sph_adaptive_sums_device", retval, "refused", self._name, err)
+        got = _hoomd.AdaptiveSums(c_h, kernel, mode, grid, int(dimensions), summary, volume, surface_below)
+        if return_rows:
+            got.rows, got.cell = _device_head(rows, count), _device_head(cell, count)
+            got.count = _device_head(out_count, count)
+            got.number, got.density = _device_head(out_number, count), _device_head(out_rho, count)
+            got.shepard = _device_head(out_shepard, count) if volume else None
+            got.omega = _device_head(out_omega, count) if gather else None
+        return got
+
     def sph_gradients_device(self, frame, name, box, h, cells, rows, cell, n=None, velocity=None, mass=None, density=None,
                              defaults=None, dimensions=3, kernel='wendland_c2', return_rows=False):
         """The SPH kernel gradients of a row list in cell order on the GPU: the density rate of the continuity equation,

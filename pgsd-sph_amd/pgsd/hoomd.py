@@ -2671,6 +2671,271 @@ def frame_kernel_sums(frame_or_arrays, h=None, kernel='wendland_c2', cells=None,
                            dimensions=dimensions, kernel=kernel, surface_below=surface_below)
 
 
+# ---- SPH sums with a per-particle smoothing length: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_adaptive_sums_device`)
+# equals exactly
+SPH_MODES = ('gather', 'mean')
+_SPHA_SUMMARY_WORDS = 22    # n, nowhere, bad_h, not_finite, surface, deviation_at, deviation_row, count_min, count_max,
+#                             count_min_at, 5 x (min, max): slength, number, density, shepard, omega; deviation, pairs
+
+
+def _sph_mode_id(mode):
+    if mode not in SPH_MODES:
+        raise ValueError("the mode is one of %s: %r" % (', '.join(SPH_MODES), mode))
+    return SPH_MODES.index(mode)
+
+
+def _spha_column(slength, N=None):
+    """A smoothing-length column, checked: ``N`` float32 or float64 values, converted to float64 exactly."""
+    s = numpy.asarray(slength)
+    if s.dtype not in (numpy.float32, numpy.float64) or (N is not None and s.size != N):
+        raise ValueError("slength holds one float32 or float64 value per row of position")
+    return s.reshape(-1).astype(numpy.float64)
+
+
+def _spha_valid(h):
+    """Is a smoothing length valid: ``h > 0.0 and h < +inf`` (a NaN is not)."""
+    with numpy.errstate(invalid='ignore'):
+        return (h > 0.0) & (h < numpy.inf)
+
+
+def smoothing_range(slength, rows=None):
+    """``(n, bad, h_min, h_max)`` of a smoothing-length column over a row list (``None``: every row): the entries, those
+    whose ``h`` is not valid (``h > 0.0 and h < +inf``), and the smallest and the largest valid ``h`` as float64
+    (``+inf`` and ``-inf`` without one).  A minimum and a maximum: no order enters.  What
+    `pgsd.fl.PGSDFile.smoothing_range_device` equals exactly."""
+    s = _spha_column(slength)
+    if rows is not None:
+        s = s[_list_rows(rows, s.shape[0])]
+    ok = s[_spha_valid(s)]
+    return (int(s.shape[0]), int(s.shape[0] - ok.shape[0]), float(ok.min()) if ok.size else float('inf'),
+            float(ok.max()) if ok.size else float('-inf'))
+
+
+def _spha_sigma_rows(kid, h, dimensions):
+    """`sph_sigma` of every valid ``h`` of an array, in exactly that function's association; ``+0.0`` elsewhere."""
+    h = numpy.where(_spha_valid(h), h, 1.0)
+    if int(dimensions) == 3:
+        return (21.0 / (16.0 * numpy.pi * (h * h * h))) if kid == 0 else (1.0 / (numpy.pi * (h * h * h)))
+    return (7.0 / (4.0 * numpy.pi * (h * h))) if kid == 0 else (10.0 / (7.0 * numpy.pi * (h * h)))
+
+
+class AdaptiveSums(object):
+    """The SPH sums of a list in cell order with a per-particle smoothing length (`sph_adaptive_sums`).
+
+    Attributes:
+        h_max (float), kernel (str), mode (str), grid (``(cx, cy, cz)``), dimensions (int), surface_below (float or
+            ``None``), volume (bool: was a ``density`` given): what was asked; ``h_max`` is the bound the grid was made
+            for (the model: the largest valid ``h`` of the list; the GPU: the declared one).
+        rows, cell: the list in cell order and its cell ids (``n_cells``: nowhere).
+        slength (float64), count (uint32), number, density, shepard, omega (float64): per entry, in list order: its
+            ``h``, the contributing candidates (itself among them) and the sums; ``+0.0`` (``slength``: as stored) for an
+            entry nowhere or with an invalid ``h``.  ``shepard`` is ``None`` without ``density``, ``omega`` in mean mode.
+            Numpy arrays from the model; from the GPU ``None`` unless ``return_rows`` left them in GPU memory.
+        n, nowhere, bad_h (int): the entries, those without a cell, and those that have a cell and an invalid ``h``.
+        not_finite (int): the entries with a cell and a valid ``h`` (the *live* ones) whose ``density`` is NaN or infinite.
+        surface (int or ``None``): the live entries with ``shepard < surface_below``.
+        deviation, deviation_at, deviation_row: `KernelSums`' over the live entries.
+        count_min, count_max, count_min_at: over the live entries; the smaller list position on a tie; ``None`` without one.
+        pairs (int): the exact sum of ``count``.
+        slength_min, slength_max, number_min, ..., omega_max (float): over the live entries, by strict compares from
+            ``+inf`` / ``-inf`` (a NaN never replaces a value); ``shepard``'s ``None`` without ``density``, ``omega``'s
+            ``None`` in mean mode.
+    """
+
+    __slots__ = ('h_max', 'kernel', 'mode', 'grid', 'dimensions', 'surface_below', 'volume', 'rows', 'cell', 'slength',
+                 'count', 'number', 'density', 'shepard', 'omega', 'n', 'nowhere', 'bad_h', 'not_finite', 'surface',
+                 'deviation', 'deviation_at', 'deviation_row', 'count_min', 'count_max', 'count_min_at', 'pairs',
+                 'slength_min', 'slength_max', 'number_min', 'number_max', 'density_min', 'density_max', 'shepard_min',
+                 'shepard_max', 'omega_min', 'omega_max', '_words')
+
+    def __init__(self, h_max, kernel, mode, grid, dimensions, summary, volume, surface_below=None, rows=None, cell=None,
+                 slength=None, count=None, number=None, density=None, shepard=None, omega=None):
+        """``summary``: the 22 uint64 words of `pgsd_sph_adaptive_sums_device`."""
+        s = numpy.ascontiguousarray(summary, dtype=numpy.uint64).reshape(-1)
+        if s.shape[0] != _SPHA_SUMMARY_WORDS:
+            raise ValueError("the summary holds %d words" % _SPHA_SUMMARY_WORDS)
+        self._words = s.copy()
+        _sph_kernel_id(kernel), _sph_mode_id(mode)
+        self.h_max, self.kernel, self.mode = float(h_max), kernel, mode
+        self.dimensions, self.volume = int(dimensions), bool(volume)
+        self.grid = None if grid is None else tuple(int(v) for v in grid)
+        self.surface_below = None if surface_below is None else float(surface_below)
+        self.n, self.nowhere, self.bad_h, self.not_finite = int(s[0]), int(s[1]), int(s[2]), int(s[3])
+        self.surface = int(s[4]) if self.volume and self.surface_below is not None else None
+        found = self.volume and int(s[5]) != _NEIGHBOURS_NONE
+        f = s[10:21].view(numpy.float64)
+        self.deviation = float(f[10]) if found else None
+        self.deviation_at, self.deviation_row = (int(s[5]), int(s[6])) if found else (None, None)
+        some = int(s[9]) != _NEIGHBOURS_NONE
+        self.count_min, self.count_max, self.count_min_at = (int(s[7]), int(s[8]), int(s[9])) if some else (None, None, None)
+        self.pairs = int(s[21])
+        self.slength_min, self.slength_max, self.number_min, self.number_max = (float(v) for v in f[:4])
+        self.density_min, self.density_max = float(f[4]), float(f[5])
+        self.shepard_min, self.shepard_max = (float(f[6]), float(f[7])) if self.volume else (None, None)
+        self.omega_min, self.omega_max = (float(f[8]), float(f[9])) if mode == 'gather' else (None, None)
+        self.rows, self.cell, self.slength, self.count = rows, cell, slength, count
+        self.number, self.density, self.shepard, self.omega = number, density, shepard, omega
+
+    @property
+    def summary(self):
+        """The uint64 words this was made from."""
+        return self._words.copy()
+
+    def __repr__(self):
+        return ("AdaptiveSums(h_max=%r, kernel=%r, mode=%r, grid=%r, n=%d, nowhere=%d, bad_h=%d, count=[%r, %r], "
+                "density=[%r, %r])" % (self.h_max, self.kernel, self.mode, self.grid, self.n, self.nowhere, self.bad_h,
+                                       self.count_min, self.count_max, self.density_min, self.density_max))
+
+
+def _spha_summary(n, somewhere, live, rows_sorted, h, count, number, density, shepard, omega, rho, surface_below):
+    """The 22 summary words from the per-entry results (``shepard``, ``rho`` None without a density, ``omega`` None in
+    mean mode): no float is summed, so no order enters.  ``live``: the entries that have a cell and a valid ``h``."""
+    words = numpy.zeros(_SPHA_SUMMARY_WORDS, dtype=numpy.uint64)
+    f = words[10:21].view(numpy.float64)
+    words[0], words[1], words[2] = n, n - somewhere, somewhere - int(numpy.count_nonzero(live))
+    words[5] = words[6] = words[9] = _NEIGHBOURS_NONE
+    f[0:10:2], f[1:10:2], f[10] = numpy.inf, -numpy.inf, 0.0
+    words[21] = int(count.astype(numpy.uint64).sum())
+    at = numpy.flatnonzero(live)
+    if not at.size:
+        return words
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        for k, v in enumerate((h, number, density, shepard, omega)):
+            if v is None:
+                continue
+            v = v[at]
+            ok = v[v == v]
+            if ok.size:
+                f[2 * k], f[2 * k + 1] = min(numpy.inf, ok.min()), max(-numpy.inf, ok.max())
+        words[3] = int(numpy.count_nonzero(~numpy.isfinite(density[at])))
+        c = count[at]
+        words[7], words[8], words[9] = int(c.min()), int(c.max()), int(at[int(numpy.argmin(c))])
+        if shepard is not None:
+            if surface_below is not None:
+                words[4] = int(numpy.count_nonzero(shepard[at] < numpy.float64(surface_below)))
+            dev = density[at] - rho[at]
+            size = numpy.where(dev == dev, numpy.abs(dev), -1.0)
+            k = int(numpy.argmax(size))                 # (the first position that attains the maximum)
+            if size[k] >= 0.0:
+                words[5], words[6], f[10] = at[k], rows_sorted[at[k]], dev[k]
+    return words
+
+
+def sph_adaptive_sums(position, box, slength, mass=None, density=None, rows=None, cells=None, dimensions=3,
+                      kernel='wendland_c2', mode='gather', surface_below=None):
+    """The SPH kernel sums of a row list whose smoothing length is stored per particle: per entry ``i`` the neighbour
+    count inside its support, the number density, the summation density, the Shepard sum and -- in gather mode -- the
+    grad-h factor ``Omega_i = 1 + (h_i / (D rho_i)) sum_j m_j dW_ij/dh_i`` (Springel & Hernquist; Price) every
+    variable-``h`` momentum equation divides by.  The definition the GPU pass (`pgsd.fl.PGSDFile.sph_adaptive_sums_device`,
+    `HOOMDTrajectory.frame_adaptive_sums_device`) equals exactly, the floats bit for bit.
+
+    Args:
+        position, box, mass, density, rows, cells, dimensions, kernel, surface_below: as `sph_kernel_sums` takes them.
+        slength: ``N`` float32 or float64 values, converted to float64 exactly.  ``h`` is *valid* when ``h > 0.0 and h <
+            +inf``; an entry with an invalid ``h`` is treated like an entry nowhere -- it contributes to nobody and
+            every per-entry output of it is ``+0.0`` --, but it is counted in ``bad_h`` (if it has a cell), not in
+            ``nowhere``.
+        mode: ``'gather'`` (the support of a pair is ``2 h_i``) or ``'mean'`` (``h_i + h_j``, the pair-symmetric form).
+
+    **The grid and the order.**  ``h_max`` is the largest valid ``h`` over the list (ValueError where a list that is not
+    empty has none); the grid is that of `sph_kernel_sums` for ``h = h_max`` (``cells`` checked against the range ``2
+    h_max``), and so are the cell order, the offsets and THE ORDER of the candidates.
+
+    **One pair**, float64 without contraction; ``d2`` as `sph_kernel_sums`; ``i`` itself and coincident entries are
+    candidates.  *gather*: once per entry ``s_i = 2.0*h_i``, ``r2_i = s_i*s_i``, ``inv_i = 1.0/h_i``; ``j`` contributes
+    when ``d2 < r2_i``, strictly; ``q = sqrt(d2)*inv_i``, ``w = sph_weight(q)``, ``F = sph_gradient_factor(q)``; ``a_n +=
+    w``, ``a_m += m_j*w``, ``a_v += V_j*w``, ``a_o += m_j*(D*w + (q*q)*F)`` with ``D`` 2.0 or 3.0, ``count_i += 1``.  After
+    the last candidate ``number = sigma_i*a_n``, ``density = sigma_i*a_m``, ``shepard = sigma_i*a_v`` with ``sigma_i =
+    sph_sigma(kernel, h_i, dimensions)`` and ``omega = 1.0 - a_o/(D*a_m)``.  *mean*: ``s = h_i + h_j``, ``hij = 0.5*s``,
+    ``ih = 1.0/hij``; ``j`` contributes when ``d2 < s*s``; ``q = sqrt(d2)*ih``, ``w = sph_weight(q)``, ``p = ih*ih`` in 2-D
+    and ``(ih*ih)*ih`` in 3-D, ``wp = w*p``; ``a_n += wp``, ``a_m += m_j*wp``, ``a_v += V_j*wp``; afterwards ``number =
+    C*a_n`` and so on with ``C = sph_sigma(kernel, 1.0, dimensions)``; there is no ``omega``.
+
+    Returns an `AdaptiveSums`.
+    """
+    dimensions = int(dimensions)
+    kid, mid = _sph_kernel_id(kernel), _sph_mode_id(mode)
+    if surface_below is not None:
+        surface_below = float(surface_below)
+        if surface_below != surface_below:
+            raise ValueError("surface_below is a number or None")
+    p = numpy.asarray(position)
+    N = p.reshape(-1, 3).shape[0] if p.size else 0
+    s = _spha_column(slength, N)
+    listed, _, _, h_max = smoothing_range(s, rows)
+    if listed and not h_max > 0.0:
+        raise ValueError("no listed row has a valid smoothing length (finite and positive)")
+    if listed:
+        asked = _sph_asked(box, h_max, cells, dimensions, kernel)
+    else:                                                # (a list of no entry: any grid serves, h_max stays -inf)
+        asked = (dimensions, 1.0, kid, 2.0, (1, 1, 1) if cells is None else _order_cells(cells, dimensions))
+    t = _sph_list(asked, position, box, rows, (('mass', mass, 1), ('density', density, 1), ('slength', s, 1)))
+    grid = asked[4]
+    n, rows_sorted, cell_sorted, somewhere = t.n, t.rows_sorted, t.cell_sorted, t.somewhere
+    mass, density, h = t.columns
+    m = numpy.ones(n, dtype=numpy.float64) if mass is None else mass
+    rho = density
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        vol = None if rho is None else m / rho
+    valid = _spha_valid(h)
+    live = valid & (numpy.arange(n) < somewhere)
+    t.xs = numpy.where(valid[:, None], t.xs, numpy.nan)  # an invalid h: no d2 of it passes a compare, in either role
+    D = numpy.float64(3.0 if dimensions == 3 else 2.0)
+    a_n, a_m = numpy.zeros(n, dtype=numpy.float64), numpy.zeros(n, dtype=numpy.float64)
+    a_v = None if vol is None else numpy.zeros(n, dtype=numpy.float64)
+    a_o = numpy.zeros(n, dtype=numpy.float64) if mid == 0 else None
+    count = numpy.zeros(n, dtype=numpy.uint32)
+    with numpy.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        hv = numpy.where(valid, h, 1.0)
+        two_h = 2.0 * hv
+        r2_i, inv_i = two_h * two_h, 1.0 / hv
+        for i, j, d, d2 in _sph_near_pairs(t):
+            if mid == 0:
+                near = d2 < r2_i[i]
+                i, j, d2 = i[near], j[near], d2[near]
+                q = numpy.sqrt(d2) * inv_i[i]
+                w = sph_weight(q, kernel)
+                F = sph_gradient_factor(q, kernel)
+                numpy.add.at(a_o, i, m[j] * (D * w + (q * q) * F))
+            else:
+                sij = hv[i] + hv[j]
+                near = d2 < sij * sij
+                i, j, d2, sij = i[near], j[near], d2[near], sij[near]
+                ih = 1.0 / (0.5 * sij)
+                w = sph_weight(numpy.sqrt(d2) * ih, kernel)
+                w = w * ((ih * ih) * ih if dimensions == 3 else ih * ih)
+            numpy.add.at(a_n, i, w)
+            numpy.add.at(a_m, i, m[j] * w)
+            if a_v is not None:
+                numpy.add.at(a_v, i, vol[j] * w)
+            count += numpy.bincount(i, minlength=n).astype(numpy.uint32)
+        scale = _spha_sigma_rows(kid, h, dimensions) if mid == 0 else numpy.float64(sph_sigma(kernel, 1.0, dimensions))
+        number, rho_sum = scale * a_n, scale * a_m
+        shepard = None if a_v is None else scale * a_v
+        omega = None if a_o is None else 1.0 - a_o / (D * a_m)
+    for v in (number, rho_sum, shepard, omega):
+        if v is not None:
+            v[~live] = 0.0
+    words = _spha_summary(n, somewhere, live, rows_sorted, h, count, number, rho_sum, shepard, omega, rho, surface_below)
+    return AdaptiveSums(h_max, SPH_KERNELS[kid], SPH_MODES[mid], grid, dimensions, words, density is not None, surface_below,
+                        rows_sorted, cell_sorted, h, count, number, rho_sum, shepard, omega)
+
+
+def frame_adaptive_sums(frame_or_arrays, kernel='wendland_c2', mode='gather', cells=None, where=None, types=None, domain=None,
+                        surface_below=None, box=None, dimensions=3):
+    """`sph_adaptive_sums` of a frame's ``position``, ``slength``, ``mass`` and ``density`` over a selection: the host twin
+    of `HOOMDTrajectory.frame_adaptive_sums_device`, which equals it exactly.  The selection is `frame_kernel_sums`' and
+    is the list: both ``i`` and ``j`` come from it, and so does ``h_max``.  A ``slength`` stored nowhere is the schema
+    default 1.0 in every row; position, mass and density as `frame_kernel_sums`.  Returns an `AdaptiveSums`."""
+    arrays, position, box, dimensions, _, rows = _sph_frame_list(frame_or_arrays, 1.0, where, types, domain, box, dimensions)
+    N = len(numpy.asarray(position).reshape(-1, 3)) if numpy.asarray(position).size else 0
+    s = arrays.get('slength')
+    if s is None or numpy.asarray(s).size == 0:
+        s = numpy.full(N, _PARTICLE_FIELDS['slength'][2], dtype=numpy.float32)
+    return sph_adaptive_sums(position, box, s, mass=arrays.get('mass'), density=arrays.get('density'), rows=rows, cells=cells,
+                             dimensions=dimensions, kernel=kernel, mode=mode, surface_below=surface_below)
+
+
 # ---- SPH kernel gradients: the definition the GPU pass (`pgsd.fl.PGSDFile.sph_gradients_device`) equals exactly
 _SPHG_SUMMARY_WORDS = 13    # n, nowhere, not_finite, curl_at, curl_row, normal_at, normal_row, 2 x (min, max), curl2, normal2
 
@@ -5972,6 +6237,64 @@ class HOOMDTrajectory(object):
             cell2 = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows2, n=count2, dimensions=dims)
             return f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults, (rows2, cell2, count2)
         return f_pos, box, dims, h, grid, rows, cell, count, chunks, defaults
+
+    def frame_adaptive_sums(self, idx, kernel='wendland_c2', mode='gather', cells=None, where=None, domain=None,
+                            surface_below=None):
+        """`frame_adaptive_sums` of frame ``idx`` read through the host path: an `AdaptiveSums`.  The definition of
+        `frame_adaptive_sums_device`."""
+        return frame_adaptive_sums(self[int(idx)], kernel=kernel, mode=mode, cells=cells, where=where, domain=domain,
+                                   surface_below=surface_below)
+
+    def frame_adaptive_sums_device(self, idx, kernel='wendland_c2', mode='gather', cells=None, where=None, domain=None,
+                                   surface_below=None, return_rows=False):
+        """`frame_adaptive_sums` of frame ``idx``, on the GPU: an `AdaptiveSums` that equals ``frame_adaptive_sums(idx,
+        ...)`` exactly -- every counter and index, every float bit for bit.
+
+        The selection is `frame_kernel_sums_device`'s.  `pgsd.fl.PGSDFile.smoothing_range_device` reduces the effective
+        ``slength`` chunk over it (stored nowhere: the schema default 1.0, nothing is read), the grid is
+        `neighbour_grid_for` of ``2*h_max`` (or ``cells``, checked like the model's), the list is sorted by cell over the
+        staged position chunk and the pass (`pgsd.fl.PGSDFile.sph_adaptive_sums_device`) runs over the staged chunks; no
+        row is copied to the host.  ``return_rows=True`` leaves ``rows``, ``cell``, ``count``, ``number``, ``density``,
+        ``shepard`` and ``omega`` in GPU memory on the result.  One `wait_read` at the end releases the staged chunks.
+        A frame whose position is stored nowhere has no chunk to search and raises ValueError, and so does a selection
+        that is not empty and holds no valid smoothing length.
+        """
+        f = self.file
+        who = "frame_adaptive_sums_device"
+        try:
+            idx = self._frame_index(idx)
+            box, dims, n_global, f_pos = self._census_frame(idx)
+            _sph_kernel_id(kernel), _sph_mode_id(mode)
+            if f_pos is None:
+                raise ValueError("%s: the position is stored nowhere (every particle sits at the origin)" % who)
+            rows, count, _ = self._selection_row_list(idx, where, domain, box, dims, n_global, f_pos)
+            if rows is None:
+                rows = fl._device_from_host(numpy.arange(n_global, dtype=numpy.int32), f.pipeline_device())
+            f_h = self._effective_frame(idx, 'particles/slength', n_global)
+            slength = None if f_h is None else (f_h, 'particles/slength')
+            defaults = [float(_PARTICLE_FIELDS[name][2]) for name in ('mass', 'density', 'slength')]
+            listed, _, _, h_max = f.smoothing_range_device(slength, n_global, rows, n=count, default=defaults[2])
+            if not listed:
+                nothing = numpy.zeros(0, dtype=numpy.float64)
+                words = _spha_summary(0, 0, numpy.zeros(0, dtype=bool), None, nothing, numpy.zeros(0, dtype=numpy.uint32),
+                                      nothing, nothing, None, None, None, None)
+                return AdaptiveSums(h_max, kernel, mode, (1, 1, 1) if cells is None else _order_cells(cells, dims), dims, words,
+                                    True, surface_below)
+            if not h_max > 0.0:
+                raise ValueError("no listed row has a valid smoothing length (finite and positive)")
+            grid = _neighbour_grid(box, float(numpy.float64(2.0) * numpy.float64(h_max)), cells, dims)
+            cell = f.order_rows_by_cell_device(f_pos, 'particles/position', box, grid, rows, n=count, dimensions=dims)
+            chunks = []
+            for name in ('mass', 'density'):
+                fr = self._effective_frame(idx, 'particles/' + name, n_global)
+                chunks.append(None if fr is None else (fr, 'particles/' + name))
+            got = f.sph_adaptive_sums_device(f_pos, 'particles/position', box, h_max, grid, rows, cell, n=count,
+                                             slength=slength, mass=chunks[0], density=chunks[1], defaults=defaults,
+                                             dimensions=dims, kernel=kernel, mode=mode, surface_below=surface_below,
+                                             return_rows=return_rows)
+        finally:
+            f.wait_read()
+        return got
 
     def frame_kernel_gradients(self, idx, h=None, kernel='wendland_c2', cells=None, where=None, domain=None):
         """`frame_kernel_gradients` of frame ``idx`` read through the host path: a `KernelGradients`.  The definition of

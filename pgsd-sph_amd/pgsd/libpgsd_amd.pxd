@@ -274,6 +274,15 @@ cdef extern from "pgsd_private.h" nogil:
                                   const uint32_t* cells, const uint32_t* rows, const int32_t* cell, uint64_t n,
                                   double* out_density_rate, double* out_divergence, double* out_curl, double* out_normal,
                                   uint64_t* out_summary)
+    int pgsd_sph_smoothing_range_device(pgsd_handle* handle, const pgsd_index_entry* slength, double h_default,
+                                        const uint32_t* rows, uint64_t n, uint64_t N, uint64_t* out_words)
+    int pgsd_sph_adaptive_sums_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* mass,
+                                      const pgsd_index_entry* density, const pgsd_index_entry* slength,
+                                      const double* defaults, const double* vectors, double h_max, uint32_t kernel,
+                                      uint32_t mode, uint32_t dimensions, const uint32_t* cells, const uint32_t* rows,
+                                      const int32_t* cell, uint64_t n, double surface_below, uint32_t* out_count,
+                                      double* out_number, double* out_density, double* out_shepard, double* out_omega,
+                                      uint64_t* out_summary)
     int pgsd_sph_tensors_device(pgsd_handle* handle, const pgsd_index_entry* position, const pgsd_index_entry* velocity,
                                 const pgsd_index_entry* mass, const pgsd_index_entry* density, const double* defaults,
                                 const double* vectors, double h, uint32_t kernel, uint32_t dimensions, double det_min,
