@@ -3,6 +3,7 @@ call, reuse after growth, two families interleaved on one allocation, and the ca
 per process and grow-only, so inside one pytest session an earlier test has usually grown it already: every case here
 runs its fixed sequence in ONE fresh child process (never more than one at a time) and compares every result with the
 host model there, exactly as the suites of the families do -- integers with numpy.array_equal, sums bit for bit.
+The families that came later, each with a scratch and a lock of its own: tests/test_gpu_scratch_cycle.py.
 
 The "just past the first capacity" sizes follow from the library's constants (csrc/pgsd_scratch.hpp and the families'
 launchers); the child works them out from the same formulas:
